@@ -2,8 +2,10 @@
 """EEG-trials/sec of the train step (fwd + bwd + Adam [+ gradient all-reduce]) on N MI355X.
 
     python bench.py --gpus 1 --steps 50 --warmup 10                      # BASELINE configs[1] ("cfg2"), the default
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full               # the same, with everything listed under --full below
     python bench.py --config cfg3                                        # K=5, H=256, B=1024, bf16 (sequence-batched path)
     python bench.py --config cfg5 --steps 5 --warmup 2                   # C=64, T=1000, H=512 bidirectional, B=512 per GPU
+    python bench.py --steps 50 --warmup 10 --dump-outputs DIR            # also write the last timed step's results as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,12 +20,22 @@ gradient is summed with ONE RCCL all-reduce per step):
 `--gpus N` with N > 1 outside a torchrun environment starts the N ranks ITSELF: the parent process (which never touches a GPU)
 spawns one child per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set and waits for them; rank 0 prints the line.
 
-ONE JSON line on rank 0.  Besides the driver's contract it carries
+A plain run sets up, runs `preheat_steps` + W untimed steps, times exactly K steps, writes --dump-outputs if asked and prints
+ONE JSON line on rank 0: metric, value (trials/s over all ranks), unit, higher_is_better, dtype, ms_per_step (wall clock of one
+timed step), steps, warmup, n_gpus, config and
+  ranks_seen    SUM all-reduce of 1 over the process group: the number of ranks the collective library (RCCL) really joined
+  preheat_steps untimed steps run before the W warm-up steps (GPU clock ramp)
+
+--dump-outputs DIR (rank 0): what a caller of Trainer.step holds after the LAST timed step, copied from the device after the
+timed region -- params (the flat parameter vector), grads (that step's flat gradient), adam_m / adam_v (the Adam moments), all
+float32, and loss (float64, mean CE of that step).  A vector longer than DUMP_MAX_ELEMS is written as a fixed, seeded sample of
+its elements (the same indices in every run).  Inputs, initial weights and the dropout / RReLU streams are seeded, so the
+same arguments give the same inputs in every run and two builds can be compared output for output.
+
+--full adds, after the timed steps (the trainer's state is captured for --dump-outputs before any of it runs):
   other_configs (default config cfg2, any N) the same measurement -- value, ms_per_step, roofline, kernels_us -- for cfg3, cfg4
                 (1024 trials per GPU: global 8192 at N = 8 = BASELINE configs[3]) and cfg5 (512 per GPU = configs[4]), a few steps
                 each, so that every BASELINE config is driver-timed; a failure there is recorded as {"error": ...} in its place
-  ranks_seen    SUM all-reduce of 1 over the process group: the number of ranks the collective library (RCCL) really joined
-  preheat_steps untimed steps run before the W warm-up steps (GPU clock ramp)
   step_ms_events    median / min of the per-step duration measured with HIP events on the launch stream (second loop)
   roofline      dominant kernel (longest average launch): algorithmic FLOP per launch / its launch time measured live with
                 HIP events on the launch stream, against the peak of the arithmetic it runs on; HBM view beside it;
@@ -56,6 +68,7 @@ import torch.distributed as dist
 X4_MIN_B = 513                                 # csrc/nsd_lstm2.hip: batch from which the H = 48 path runs its four-trial matrix-pipe kernels
 PEAK_TFLOPS = {"f32": 157.3, "bf16": 2500.0}   # MI355X_MICROARCH.md: fp32 vector == fp32 matrix rate; dense bf16 MFMA
 HBM_PEAK_GBS = 8000.0                          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_MAX_ELEMS = 1 << 21                       # --dump-outputs: per vector (8 MB of float32); four vectors stay below 64 MB in all
 
 CONFIGS = {
     "cfg2": dict(C=8, H=48, L=2, K=3, T=250, B=256, precision="fp32", bidirectional=False, dtype="f32",
@@ -175,6 +188,7 @@ class _StubTrainer:
 
     def __init__(self, world, name=""):
         self.t = torch.zeros(1024)
+        self.flat = self.grads = self.m = self.v = self.t       # what --dump-outputs reads from a trainer
         self.world = world
         self.fail = os.environ.get("NSD_BENCH_STUB_FAIL") == name        # test hook of the stub only: this config's step raises
 
@@ -197,14 +211,33 @@ def _sync(stub):
         torch.cuda.synchronize()
 
 
+def step_outputs(trainer, loss):
+    """Host copies of what a caller of Trainer.step holds after the most recent step (see --dump-outputs)."""
+    out = {name: t.detach().float().cpu().numpy().ravel() for name, t in
+           (("params", trainer.flat), ("grads", trainer.grads), ("adam_m", trainer.m), ("adam_v", trainer.v))}
+    out["loss"] = np.array([loss], np.float64)
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy per array; a vector longer than DUMP_MAX_ELEMS is replaced by a fixed, seeded sample of its elements."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 class ScanFailure(RuntimeError):
     """A scan group of the sequence-batched path timed out on SOME rank.  Raised on EVERY rank in the same place (the ranks agree
     on the status with one MAX all-reduce first), so the callers may treat it as a collective event."""
 
 
-def run_config(name, args, rank, local, world, dev, steps, warmup, preheat, extras, cpu_baseline, stub=False):
+def run_config(name, args, rank, local, world, dev, steps, warmup, preheat, extras, cpu_baseline, stub=False, full=False,
+               dump_dir=None):
     """Measure one config; returns the output dict on rank 0 (None elsewhere).  Raises ScanFailure on EVERY rank when a scan
-    group timed out on any rank."""
+    group timed out on any rank.  full: the per-step / per-kernel HIP-event loops and the roofline figures as well;
+    dump_dir: rank 0 writes the last timed step's results there."""
     cfg = CONFIGS[name]
     small = cfg["precision"] == "fp32"
     import nsd_amd
@@ -271,11 +304,13 @@ def run_config(name, args, rank, local, world, dev, steps, warmup, preheat, extr
     dt = time.perf_counter() - t0
     check_status("after the timed loop")
     loss = trainer.last_loss()
+    if dump_dir and rank == 0:                  # before the loops below step the trainer further
+        dump_outputs(dump_dir, step_outputs(trainer, loss))
 
     # second loop of the same K steps: per-step HIP events + per-kernel HIP events on the launch stream (kept out of the
     # timed region so that recording does not perturb `value`); profiles/ holds the rocprofv3 summary of the same command
     step_ms, kern_us = None, {}
-    if not args.no_kernel_timing and not stub:
+    if full and not args.no_kernel_timing and not stub:
         step_ms = event_times_ms(do_step, steps)
         if small:
             timer = KernelTimer(["nsd_lstm_head_train_rng", "nsd_lstm_head_train", "nsd_lstm_fwd", "nsd_lstm_bwd_rng", "nsd_lstm_bwd",
@@ -483,12 +518,17 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=None)
     ap.add_argument("--T", type=int, default=None)
     ap.add_argument("--preheat-steps", type=int, default=None, help="untimed steps before the warm-up steps (GPU clock ramp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the per-step / per-kernel HIP-event loops, roofline, inference / T=625 "
+                                                         "points, CPU baseline and (default config) the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0)
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the per-kernel HIP events and the extra points")
-    ap.add_argument("--no-extras", action="store_true", help="skip the inference / T=625 points")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run only: skip the cfg3 / cfg4 / cfg5 measurements")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel HIP events and the extra points")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the inference / T=625 points")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, default config: skip the cfg3 / cfg4 / cfg5 measurements")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))          # (nothing above has initialised a GPU: importing torch does not)
     stub = bool(os.environ.get("NSD_BENCH_STUB"))
@@ -522,25 +562,26 @@ def main():
         sys.exit(code)
 
     try:
-        out = run_config(args.config, args, rank, local, world, dev, steps, warmup, preheat, extras=not args.no_extras,
-                         cpu_baseline=not args.no_cpu_baseline, stub=stub)
+        out = run_config(args.config, args, rank, local, world, dev, steps, warmup, preheat, extras=args.full and not args.no_extras,
+                         cpu_baseline=args.full and not args.no_cpu_baseline, stub=stub, full=args.full, dump_dir=args.dump_outputs)
     except ScanFailure as e:                        # raised on every rank in the same place: leave together
         if rank == 0:
             print(f"bench.py: {e}", file=sys.stderr)
         leave(3)
 
-    # the driver runs `bench.py --gpus N --steps K --warmup W` = cfg2; the other BASELINE configs ride in the same line so that
-    # their numbers are driver-timed too (a few steps each, no CPU leg: ~15 s in all) -- at EVERY N: with N ranks cfg4's line is
-    # BASELINE configs[3] as stated (1024 trials per GPU = global 8192 at N = 8) and cfg5's is configs[4] (512 per GPU).  A failure
-    # in one of them must not cost the headline: it is recorded in its place and the cfg2 line is printed regardless.
-    if args.config == "cfg2" and not args.no_other_configs and args.batch_per_gpu is None and args.T is None and not args.no_kernel_timing:
+    # `bench.py --gpus N --steps K --warmup W --full` (cfg2): the other BASELINE configs ride in the same line so that their numbers
+    # are driver-timed too (a few steps each, no CPU leg: ~15 s in all) -- at EVERY N: with N ranks cfg4's line is BASELINE
+    # configs[3] as stated (1024 trials per GPU = global 8192 at N = 8) and cfg5's is configs[4] (512 per GPU).  A failure in one
+    # of them must not cost the headline: it is recorded in its place and the cfg2 line is printed regardless.
+    if (args.full and args.config == "cfg2" and not args.no_other_configs and args.batch_per_gpu is None and args.T is None
+            and not args.no_kernel_timing):
         others = {}
         plan = (("cfg3", (20, 5, 10)), ("cfg4", (100, 20, 200)), ("cfg5", (8, 2, 3)))
         if stub:
             plan = tuple((n, (2, 1, 1)) for n, _ in plan)
         for name, (k, w, ph) in plan:
             try:
-                o = run_config(name, args, rank, local, world, dev, k, w, ph, extras=False, cpu_baseline=False, stub=stub)
+                o = run_config(name, args, rank, local, world, dev, k, w, ph, extras=False, cpu_baseline=False, stub=stub, full=True)
                 if rank == 0:
                     others[name] = {key: o[key] for key in ("value", "unit", "ms_per_step", "steps", "warmup", "n_gpus", "ranks_seen", "dtype",
                                                             "config", "step_ms_events", "roofline", "kernels_us", "step_frac_of_peak",

@@ -234,10 +234,34 @@ def test_synthetic_producer_and_dead_producer():
 
 
 # ---- which preprocessor does the drop-in resolve?  (reference lstm_eeg_model.py:7-10,66,91; Frontend/app.py:22-28) --------
-REFERENCE_APP = "/root/reference/Neuro-Alpha-App"
+# A stand-in for the reference's app tree: Neuro-Alpha-App/Utilities/ is a directory without __init__.py whose preprocessor.py
+# defines PreProcessor(sr, tailoring_lambda) with .transform([T,C]) -> [T,C] (ValueError for anything not 2-D).  The resolution
+# logic only needs that layout and that surface; the stand-in's transform does no filtering.
+_STANDIN_PREPROCESSOR = '''
+import numpy as np
+
+
+class PreProcessor:
+    def __init__(self, sr, tailoring_lambda=1.25e-29):
+        self.sr, self.tailoring_lambda = sr, tailoring_lambda
+
+    def transform(self, x):
+        if np.ndim(x) != 2:
+            raise ValueError(f"expected [samples, channels], got {np.shape(x)}")
+        return np.asarray(x, np.float32)
+'''
+
+
+def _standin_app(root):
+    app = root / "Neuro-Alpha-App"
+    (app / "Utilities").mkdir(parents=True)
+    (app / "Utilities" / "preprocessor.py").write_text(_STANDIN_PREPROCESSOR)
+    return str(app)
+
+
 _RESOLVE_SNIPPET = r"""
 import sys
-sys.dont_write_bytecode = True                      # the reference tree is read-only
+sys.dont_write_bytecode = True                      # leave the app tree as it is
 sys.path[:0] = [{repo!r}] + {extra!r}
 import nsd_amd
 from nsd_amd import lstm_eeg_model as M
@@ -262,16 +286,16 @@ def _resolve_in_subprocess(extra_path, package=None):
     return out.stdout
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_APP), reason="reference tree not present (GPU box)")
-def test_default_preprocessor_is_the_references_in_both_import_modes():
+def test_default_preprocessor_is_the_references_in_both_import_modes(tmp_path):
+    app = _standin_app(tmp_path)
     # package mode: what the Streamlit app does (Neuro-Alpha-App/ on sys.path, `Utilities.*` imports)
-    out = _resolve_in_subprocess([REFERENCE_APP])
+    out = _resolve_in_subprocess([app])
     assert "RESOLVED Utilities.preprocessor.PreProcessor" in out and "VALUEERROR ok" in out
     # script mode: Utilities/ itself on sys.path (`python tester.py`)
-    out = _resolve_in_subprocess([os.path.join(REFERENCE_APP, "Utilities")])
+    out = _resolve_in_subprocess([os.path.join(app, "Utilities")])
     assert "RESOLVED preprocessor.PreProcessor" in out and "VALUEERROR ok" in out
     # a stub that names its own package gets that package's module first
-    out = _resolve_in_subprocess([REFERENCE_APP], package="Utilities")
+    out = _resolve_in_subprocess([app], package="Utilities")
     assert "RESOLVED Utilities.preprocessor.PreProcessor" in out
 
 

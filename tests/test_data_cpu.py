@@ -6,7 +6,10 @@ import pytest
 
 from nsd_amd import data as D
 
-REF_DATA = "/root/reference/EEG_data_collection"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+FIXTURE = os.path.join(GOLDEN, "recorded_trials.npz")
+# five files of the recorded data set exactly as the reference stores them (one per class prefix)
+CSV_SAMPLE = os.path.join(GOLDEN, "recorded_csv")
 
 
 def _write(d, name, a):
@@ -53,21 +56,26 @@ def test_stratified_split_and_batches():
     assert [len(b) for b in D.epoch_batches(10, 4, 3, 1, drop_last=True)] == [4, 4]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference data set not present (GPU box)")
-def test_reference_dataset_counts():
-    ts = D.load_trials(REF_DATA, D.LABELS_5CLASS)
+def _recorded_csv_dir(d):
+    """The recorded data set as a directory of trial CSVs in the reference's on-disk format (file <stem>.csv, `%.7f`), rebuilt
+    from the packed fixture; the stored sample files show that this is the format of the recorded files."""
+    z = np.load(FIXTURE, allow_pickle=False)
+    for stem, x in zip(z["stem"], z["x"]):
+        _write(d, f"{stem}.csv", x)
+    return str(d)
+
+
+def test_reference_dataset_counts(tmp_path):
+    ts = D.load_trials(_recorded_csv_dir(tmp_path), D.LABELS_5CLASS)
     counts = {p: ts.prefix.count(p) for p in D.PREFIXES}
     assert counts == {"backgroundnoise": 40, "food": 69, "no": 71, "water": 70, "yes": 74}     # SURVEY 2 (#9)
     assert ts.x.shape == (324, 625, 8) and np.isfinite(ts.x).all()
     assert abs(float(ts.x.std()) - 2.73) < 0.05                                                    # SURVEY 8c
 
 
-FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "recorded_trials.npz")
-
-
-def test_packed_fixture_is_the_recorded_data_set():
+def test_packed_fixture_is_the_recorded_data_set(tmp_path):
     """tests/golden/recorded_trials.npz (the form in which the trials reach the GPU box) == what load_trials parses
-    from the reference's CSV directory, for the 3-class and the 5-class label maps."""
+    from the recorded CSV files, for the 3-class and the 5-class label maps."""
     five = D.load_trials_npz(FIXTURE, D.LABELS_5CLASS)
     assert five.x.shape == (324, 625, 8) and five.x.dtype == np.float32 and five.num_classes == 5
     assert {p: five.prefix.count(p) for p in D.PREFIXES} == {"backgroundnoise": 40, "food": 69, "no": 71, "water": 70, "yes": 74}
@@ -76,8 +84,14 @@ def test_packed_fixture_is_the_recorded_data_set():
     assert [int((three.y == c).sum()) for c in range(3)] == [70, 69, 40]               # water, food, backgroundnoise
     with pytest.raises(FileNotFoundError):
         D.load_trials_npz(FIXTURE, {"nothing": 0})
-    if os.path.isdir(REF_DATA):
-        for lm, packed in ((None, three), (D.LABELS_5CLASS, five)):
-            ts = D.load_trials(REF_DATA, lm)
-            assert np.array_equal(ts.x, packed.x) and np.array_equal(ts.y, packed.y)
-            assert [os.path.basename(f) for f in ts.files] == packed.files
+    # the recorded files themselves parse to exactly the packed windows ...
+    sample = D.load_trials(CSV_SAMPLE, D.LABELS_5CLASS)
+    assert sorted(sample.prefix) == sorted(D.PREFIXES)
+    for f, x in zip(sample.files, sample.x):
+        assert np.array_equal(x, five.x[five.files.index(os.path.basename(f))])
+    # ... and so does the whole data set in that format, under both label maps
+    rec = _recorded_csv_dir(tmp_path)
+    for lm, packed in ((None, three), (D.LABELS_5CLASS, five)):
+        ts = D.load_trials(rec, lm)
+        assert np.array_equal(ts.x, packed.x) and np.array_equal(ts.y, packed.y)
+        assert [os.path.basename(f) for f in ts.files] == packed.files

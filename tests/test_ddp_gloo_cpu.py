@@ -167,7 +167,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NSD_BENCH_STUB="1", NSD_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--preheat-steps", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -190,7 +190,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
 
 @pytest.mark.timeout(300)
 def test_bench_keeps_the_headline_when_another_config_fails():
-    """The default run measures cfg3 / cfg4 / cfg5 after the headline config; whatever goes wrong in one of them (here: the stub's
+    """The --full run measures cfg3 / cfg4 / cfg5 after the headline config; whatever goes wrong in one of them (here: the stub's
     step raises MemoryError for cfg3) is recorded in its place, the remaining configs are still measured and the cfg2 line is printed
     with rc 0."""
     import json
@@ -200,7 +200,7 @@ def test_bench_keeps_the_headline_when_another_config_fails():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NSD_BENCH_STUB="1", NSD_DIST_BACKEND="gloo", NSD_BENCH_STUB_FAIL="cfg3")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat-steps", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=240)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -208,3 +208,38 @@ def test_bench_keeps_the_headline_when_another_config_fails():
     assert out["config"]["name"] == "cfg2" and out["value"] > 0
     oc = out["other_configs"]
     assert "MemoryError" in oc["cfg3"]["error"] and oc["cfg4"]["value"] > 0 and oc["cfg5"]["value"] > 0
+
+
+@pytest.mark.timeout(300)
+def test_plain_bench_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline measurement only (no other configs, HIP-event loops, roofline or CPU leg),
+    --steps sets the timed steps, and --dump-outputs writes the last timed step's results: the same arrays from two runs with
+    the same arguments."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(NSD_BENCH_STUB="1", NSD_DIST_BACKEND="gloo")
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--preheat-steps", "1", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert {"metric", "unit", "higher_is_better", "dtype"} <= set(out)
+        assert not {"other_configs", "step_ms_events", "roofline", "kernels_us", "cpu_baseline", "inference", "T625"} & set(out), out
+        files = sorted(os.listdir(d))
+        assert files == ["adam_m.npy", "adam_v.npy", "grads.npy", "loss.npy", "params.npy"], files
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
