@@ -39,7 +39,9 @@
 extern "C" {
 #endif
 
-#define NSD_VERSION 300          /* 0.3.0: sequence-batched path: persistent workspace header (nsd_seq_workspace_init), sticky
+#define NSD_VERSION 301          /* 0.3.1: nsd_lstm_bwd's dx is right after every forward of the batch (the fused head's open
+                                    attention records included), refused before any launch outside its domain; nsd_dx_path.
+                                    0.3.0: sequence-batched path: persistent workspace header (nsd_seq_workspace_init), sticky
                                     status, nsd_seq_guard / nsd_adam_step_guarded; diagnostics left the shipped library */
 #define NSD_MAX_LAYERS 8
 
@@ -182,8 +184,12 @@ int nsd_lstm_bwd_rng(const nsd_dims *d, const float *params, const float *x, con
  * Partial gradients go to the slabs.  dx (optional, may be NULL): dL/dx [B,T,C], what autograd through self.lstm(x)
  * (lstm_eeg_model.py:34) returns for the EEG window -- formed as da0 . W_ih0 behind the backward pass, for H = 48 (L = 2, C <= 8; the
  * one-trial kernel then runs whatever the batch and leaves da0 IN PLACE of layer 0's saved gates: one backward per forward) and on the
- * shape-generic path; on the other paths a non-NULL dx returns NSD_E_INVALID and launches nothing.  The parameter gradients never need it.
+ * shape-generic path with C <= 64 and 4H * C * 4 <= 64 KB.  With H = 48 it follows either forward, nsd_lstm_fwd + a head or
+ * nsd_lstm_head_train at any batch: where the fused head left the attention's per-step backward to the four-trial backward kernel (from
+ * 513 trials), a small kernel forms it first (dL/dscore, d attn.weight, d attn.bias), and every gradient is the one dx = NULL gives.
+ * Where nsd_dx_path(d) == 0 a non-NULL dx returns NSD_E_INVALID and launches nothing.  The parameter gradients never need it.
  */
+int nsd_dx_path(const nsd_dims *d);       /* 1 where nsd_lstm_bwd forms dx for these dims, 0 elsewhere (and for invalid dims) */
 int nsd_lstm_bwd(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm,
                  uint32_t flags, float *workspace, int64_t workspace_bytes, float *dx, void *stream);
 

@@ -63,6 +63,7 @@ SYMBOLS = {
     "nsd_rng_path": (C.c_int, [_dp]),
     "nsd_lstm_head_train_rng": (C.c_int, [_dp, _fp, _fp, _vp, _ip, C.c_float, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
     "nsd_lstm_bwd_rng": (C.c_int, [_dp, _fp, _fp, _vp, C.c_uint32, _fp, C.c_int64, _vp]),
+    "nsd_dx_path": (C.c_int, [_dp]),
     "nsd_lstm_bwd": (C.c_int, [_dp, _fp, _fp, _fp, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
     "nsd_grad_reduce": (C.c_int, [_dp, _fp, C.c_int64, _fp, C.c_int32, _vp]),
     "nsd_grad_reduce_adam": (C.c_int, [_dp, _fp, C.c_int64, _fp, _fp, _fp, _fp] + [C.c_float] * 6 + [C.c_int32, _vp]),
@@ -131,8 +132,8 @@ def lib() -> C.CDLL:
             fn.restype, fn.argtypes = res, args
         if diag and hasattr(L, "nsd_debug_profile_buffer"):      # diagnostic build only; not part of include/nsd.h
             L.nsd_debug_profile_buffer.restype, L.nsd_debug_profile_buffer.argtypes = C.c_int, [_vp]
-        if L.nsd_version() < 300 and not diag:
-            raise NsdError(f"{LIB_PATH} is ABI v{L.nsd_version()}, this binding needs >= 300: rebuild it")
+        if L.nsd_version() < 301 and not diag:
+            raise NsdError(f"{LIB_PATH} is ABI v{L.nsd_version()}, this binding needs >= 301: rebuild it")
         _lib = L
     return _lib
 

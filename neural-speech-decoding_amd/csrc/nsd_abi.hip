@@ -420,14 +420,28 @@ int nsd_lstm_head_train_rng(const nsd_dims *d, const float *params, const float 
     return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, &r, labels, scale, flags, workspace, workspace_bytes, logits, stream);
 }
 
+// where nsd_lstm_bwd forms dx: H = 48 on the fast path (the one-trial kernel leaves da0 in place of layer 0's saved gates: ONE backward per
+// forward then) and the generic path (its da_seq holds layer 0 last), within the dx kernel's domain (W_ih0 staged in 64 KB of LDS)
+static bool dx_shape(const nsd_dims *d) {
+    const bool path = (fast_path_ok(d) && d->H == 48) || (!fast_path_ok(d) && !nsd_lstm_batched_ok(d, true));
+    return path && nsd_dx_ok(4 * d->H, d->C);
+}
+
+int nsd_dx_path(const nsd_dims *d) {
+    if (nsd_check_dims(d) != NSD_OK) return 0;
+    return dx_shape(d) ? 1 : 0;
+}
+
 static int lstm_bwd_impl(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, const RngArgs *rng,
                          uint32_t flags, float *workspace, int64_t workspace_bytes, float *dx, void *stream) {
     if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
     if (!params || !x || !workspace) { nsd_set_error("lstm_bwd: null pointer"); return NSD_E_INVALID; }
-    // dx = dL/dx [B,T,C] (optional): H = 48 (the one-trial kernel leaves da0 in place of layer 0's saved gates: ONE backward per forward
-    // then) and the generic path (its da_seq holds layer 0 last); the other paths do not form it
-    const bool dx_ok = (fast_path_ok(d) && d->H == 48) || (!fast_path_ok(d) && !nsd_lstm_batched_ok(d, true));
-    if (dx && !dx_ok) { nsd_set_error("lstm_bwd: dx is available for H = 48 (L = 2, C <= 8) and on the generic path only (include/nsd.h)"); return NSD_E_INVALID; }
+    // dx = dL/dx [B,T,C] (optional): refused before any launch where it is not formed (dx_shape, nsd_dx_path)
+    if (dx && !dx_shape(d)) {
+        nsd_set_error("lstm_bwd: dx is available for H = 48 (L = 2, C <= 8) and on the generic path with C <= 64 and 4H * C * 4 <= 64 KB "
+                      "only (nsd_dx_path, include/nsd.h)");
+        return NSD_E_INVALID;
+    }
     nsd_ws_layout w;
     if (const int rc = check_ws(d, workspace, workspace_bytes, "lstm_bwd", &w)) return rc;
     if (d->B == 0) return NSD_OK;
@@ -472,7 +486,12 @@ static int lstm_bwd_impl(const nsd_dims *d, const float *params, const float *x,
     a.residual = (flags & NSD_FLAG_RESIDUAL) ? 1 : 0;
     a.ablate = ablate_mask();
     if (rng) a.rng = *rng;
-    if (dx) a.da0_out = workspace + w.gact;                         // (in place of layer 0's saved gates, 4H floats per step: see Lstm2BwdArgs)
+    if (dx) {
+        a.da0_out = workspace + w.gact;                             // (in place of layer 0's saved gates, 4H floats per step: see Lstm2BwdArgs)
+        // the one-trial kernel takes a record's dL/dscore_t as finished: close the records a four-trial forward left open
+        if (const int rc = nsd_att_close_launch(a.hseq1, a.pooled, a.dpooled, workspace + w.adpack, workspace + w.dscore, a.hslabs, a.Ph,
+                                                a.o_attn_w, a.o_attn_b, d->B, d->T, d->H, (hipStream_t)stream)) return rc;
+    }
     if (const int rc = nsd_lstm2_bwd_launch(a, d->H, (hipStream_t)stream)) return rc;
     return dx ? nsd_dx_launch(a.da0_out, params + pl.w_ih[0], dx, (long)d->B * d->T, 4 * d->H, d->C, (hipStream_t)stream) : NSD_OK;
 }

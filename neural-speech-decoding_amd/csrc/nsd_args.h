@@ -126,4 +126,8 @@ int nsd_rrelu_noise_launch(uint64_t seed, uint32_t stream_id, long n, float *out
 int nsd_loss_sum_launch(const float *loss, int B, float *out, hipStream_t st);
 // dx[r][c] = sum_k da0[r][k] * w_ih0[k][c]: r = (trial, step), k = gate * H + unit (nn.LSTM weight_ih_l0 is [4H][C] row-major)
 int nsd_dx_launch(const float *da0, const float *w_ih0, float *dx, long rows, int G4, int C, hipStream_t st);
+bool nsd_dx_ok(int G4, int C);            // the dx kernel's domain (C channels, 4H gate rows: W_ih0 staged in 64 KB of LDS)
+// H = 48, input gradient requested: closes OPEN attention records (left by lstm2_fwd48x4 with defer_att) in front of lstm2_bwd48_kernel<1>
+int nsd_att_close_launch(const float *hseq1, const float *pooled, const float *dpooled, float *adpack, float *dscore, float *hslabs,
+                         long Ph, long o_attn_w, long o_attn_b, int B, int T, int H, hipStream_t st);
 

@@ -318,12 +318,86 @@ __global__ __launch_bounds__(256) void dx_kernel(const float *da0, const float *
         for (int i = 0; i < 8; ++i) if (c0 + i < C) dx[r * C + c0 + i] = acc[i];
     }
 }
+// (the staged weight matrix: dynamic LDS without an opt-in attribute)
+bool nsd_dx_ok(int G4, int C) { return C >= 1 && C <= DX_CMAX && (long)G4 * C * 4 <= 64 * 1024; }
+
 int nsd_dx_launch(const float *da0, const float *w_ih0, float *dx, long rows, int G4, int C, hipStream_t st) {
     if (rows <= 0) return NSD_OK;
-    // (the staged weight matrix: dynamic LDS without an opt-in attribute)
-    if (C > DX_CMAX || (long)G4 * C * 4 > 64 * 1024) { nsd_set_error("dx: C = %d, 4H = %d outside the kernel's domain", C, G4); return NSD_E_INVALID; }
+    if (!nsd_dx_ok(G4, C)) { nsd_set_error("dx: C = %d, 4H = %d outside the kernel's domain", C, G4); return NSD_E_INVALID; }
     hipLaunchKernelGGL(dx_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), (size_t)G4 * C * 4, st, da0, w_ih0, dx, rows, G4, C);
     NSD_CHECK_LAUNCH("dx");
+    return NSD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Closing the attention records of an H = 48 batch in front of the one-trial backward kernel (the input gradient is requested).
+// lstm2_fwd48x4_kernel with the head fused leaves OPEN records {alpha_t, 0, 1, 0} when the four-trial backward kernel is to follow:
+// that kernel forms dL/dscore_t, d attn.weight and d attn.bias on its way.  lstm2_bwd48_kernel<1> -- the only kernel that writes da0 --
+// reads word 1 of a record as the finished dL/dscore_t and has no such code (a test there costs its hot loop).  So this kernel,
+// one workgroup per trial, does it first, with the arithmetic of the four-trial kernel's aux wave (top_t = h1_t: open records exist
+// for the plain two-layer stack only):
+//   dL/dscore_t = alpha_t (dpooled . h1_t - dpooled . pooled),   d attn.weight = sum_t dL/dscore_t h1_t,   d attn.bias = sum_t dL/dscore_t
+// -> closed records {alpha_t, dL/dscore_t, 0, 0}, the workspace's dscore region, the trial's head-slab entries.  A trial whose records
+// are closed already (any other forward) is left alone: the flag is read on the device, whichever forward ran.
+// ------------------------------------------------------------------------------------------------
+constexpr int AC_H = 48, AC_NT = 256, AC_PARTS = AC_NT / AC_H;     // 5 parts of 48 threads sum d attn.weight over the steps of a chunk
+__global__ __launch_bounds__(AC_NT) void att_close_kernel(const float *hseq1, const float *pooled, const float *dpooled, float *adpack,
+                                                          float *dscore, float *hslabs, long Ph, long o_attn_w, long o_attn_b, int B, int T) {
+    __shared__ float dp[AC_H], po[AC_H], ds[AC_NT], part[AC_PARTS][AC_H], red[AC_NT / 64];
+    const int tid = threadIdx.x;
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        const size_t bT = (size_t)b * T;
+        if (adpack[bT * 4 + 2] == 0.f) continue;                   // closed (uniform over the workgroup: read before any barrier of the trial)
+        if (tid < AC_H) { dp[tid] = dpooled[(size_t)b * AC_H + tid]; po[tid] = pooled[(size_t)b * AC_H + tid]; }
+        __syncthreads();
+        float sdot = 0.f;
+        for (int u = 0; u < AC_H; ++u) sdot = fmaf(dp[u], po[u], sdot);
+        const int pu = tid % AC_H, pp = tid / AC_H;                 // d attn.weight: unit pu, steps pp, pp + 5, ... of a chunk
+        float attw = 0.f, dsum = 0.f;
+        for (int t0 = 0; t0 < T; t0 += AC_NT) {
+            const int t = t0 + tid;
+            float v = 0.f;
+            if (t < T) {
+                const float *h = hseq1 + (bT + t) * AC_H;
+                float dd = 0.f;
+                for (int u = 0; u < AC_H; ++u) dd = fmaf(dp[u], h[u], dd);
+                const float al = adpack[(bT + t) * 4];
+                v = al * (dd - sdot);
+                dscore[bT + t] = v;
+                *reinterpret_cast<float4 *>(adpack + (bT + t) * 4) = make_float4(al, v, 0.f, 0.f);
+                dsum += v;
+            }
+            ds[tid] = v;
+            __syncthreads();
+            if (pp < AC_PARTS) {
+                const int n = T - t0 < AC_NT ? T - t0 : AC_NT;
+                for (int k = pp; k < n; k += AC_PARTS) attw = fmaf(ds[k], hseq1[(bT + t0 + k) * AC_H + pu], attw);
+            }
+            __syncthreads();
+        }
+        if (pp < AC_PARTS) part[pp][pu] = attw;
+        dsum = wave_sum(dsum);
+        if ((tid & 63) == 0) red[tid >> 6] = dsum;
+        __syncthreads();
+        float *slab = hslabs + (size_t)b * Ph;
+        if (tid < AC_H) {
+            float s = 0.f;
+            for (int q = 0; q < AC_PARTS; ++q) s += part[q][tid];
+            slab[o_attn_w + tid] = s;
+        }
+        if (tid == 0) slab[o_attn_b] = (red[0] + red[1]) + (red[2] + red[3]);
+        __syncthreads();                                            // (dp / po / part / red are reused by the next trial)
+    }
+}
+
+int nsd_att_close_launch(const float *hseq1, const float *pooled, const float *dpooled, float *adpack, float *dscore, float *hslabs,
+                         long Ph, long o_attn_w, long o_attn_b, int B, int T, int H, hipStream_t st) {
+    if (B <= 0) return NSD_OK;
+    if (H != AC_H) { nsd_set_error("att_close: H = %d (built for 48)", H); return NSD_E_INVALID; }
+    const int grid = B < 4096 ? B : 4096;
+    hipLaunchKernelGGL(att_close_kernel, dim3(grid), dim3(AC_NT), 0, st, hseq1, pooled, dpooled, adpack, dscore, hslabs, Ph, o_attn_w,
+                       o_attn_b, B, T);
+    NSD_CHECK_LAUNCH("att_close");
     return NSD_OK;
 }
 

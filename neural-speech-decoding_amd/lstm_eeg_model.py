@@ -14,6 +14,7 @@ from __future__ import annotations
 import importlib
 import importlib.util
 import math
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -70,18 +71,39 @@ class _EEGFunction(torch.autograd.Function):
         x, logits = ctx.saved_tensors
         drop_lstm, rrelu_slope, drop_head = ctx.masks
         # the gradient w.r.t. the EEG window, where somebody asked for it (x.requires_grad): what autograd through self.lstm(x)
-        # (lstm_eeg_model.py:34) gives the reference's users; the kernels form it for H = 48 and on the generic path
+        # (lstm_eeg_model.py:34) gives the reference's users; the kernels form it where ops.dx_path says so (H = 48 and the generic
+        # path).  Elsewhere the parameter gradients still come back, x gets None, and a warning says why.
         if getattr(ctx, "gates_consumed", False):
             raise NsdError("backward a second time after one that returned the input gradient: the H = 48 kernel forms dx in place of "
                            "layer 0's saved gates -- run the forward pass again")
-        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        ctx.gates_consumed = dx is not None and spec.H == 48
+        B, T, _ = x.shape
+        dx = None
+        if ctx.needs_input_grad[1]:
+            if ops.dx_path(spec, B, T):
+                dx = torch.empty_like(x)
+            else:
+                _warn_no_dx(spec, B)
         g = ops.train_backward(spec, module._flat, x, ctx.ws, logits, dlogits=dlogits.contiguous().float(),
                                drop_lstm=drop_lstm, rrelu_slope=rrelu_slope, drop_head=drop_head,
                                residual=module.residual, dx=dx)
+        # (only the H = 48 fast-path kernel overwrites layer 0's saved gates; the generic path keeps them)
+        ctx.gates_consumed = dx is not None and spec.fast_path() and spec.H == 48
         offs, shapes = spec.offsets(), spec.shapes()
         grads = tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
         return (None, dx, None) + grads            # (ctx.ws lives as long as the graph does: retain_graph may come back)
+
+
+_no_dx_warned = set()
+
+
+def _warn_no_dx(spec, B: int) -> None:
+    """One UserWarning per model shape: x.requires_grad where the kernels form no input gradient."""
+    if spec in _no_dx_warned:
+        return
+    _no_dx_warned.add(spec)
+    warnings.warn(f"EEG_LSTM: no input gradient for {spec} at batch {B} -- the kernels form dL/dx for hidden size 48 (2 layers, <= 8 "
+                  "channels) and on the shape-generic path only (nsd_dx_path); the parameter gradients are returned, x.grad stays None",
+                  UserWarning, stacklevel=3)
 
 
 class _EEGSeqFunction(torch.autograd.Function):

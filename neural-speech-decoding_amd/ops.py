@@ -205,8 +205,41 @@ def ws_view(ws: torch.Tensor, spec: ModelSpec, B: int, T: int, region: str) -> t
     return ws[off:off + n].view(shp)
 
 
+ZSCORE_EPS = 1e-6
+
+
+class _ZScoreFunction(torch.autograd.Function):
+    """zscore as an autograd node (EEG_LSTM(normalize=True) with x.requires_grad): the forward is the kernel, the backward the
+    closed form of y = d / (s + eps), d = x - mean_T x, s = sqrt(mean_T d^2) (population std) per trial and
+    channel (app.py:166-170):  dL/dx = (g - mean_T g) / (s + eps) - d * sum_T(g d) / (T s (s + eps)^2)  (the second term is 0 where s = 0: d = 0 there)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor) -> torch.Tensor:
+        ctx.save_for_backward(x)
+        return _zscore_launch(x, None)
+
+    @staticmethod
+    def backward(ctx, g: torch.Tensor) -> torch.Tensor:
+        (x,) = ctx.saved_tensors
+        x64, g64 = x.double(), g.double()
+        T = x.shape[-2]
+        d = x64 - x64.mean(dim=-2, keepdim=True)
+        s = d.square().mean(dim=-2, keepdim=True).sqrt()
+        se = s + ZSCORE_EPS
+        gd = (g64 * d).sum(dim=-2, keepdim=True)
+        corr = torch.where(s > 0, gd / (T * s.clamp_min(1e-300) * se * se), torch.zeros_like(s))
+        return ((g64 - g64.mean(dim=-2, keepdim=True)) / se - d * corr).to(x.dtype)
+
+
 def zscore(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """(x - mean_T) / (std_T + 1e-6) per trial and channel; x [B,T,C] or [T,C].  (app.py:166-170)"""
+    """(x - mean_T) / (std_T + 1e-6) per trial and channel; x [B,T,C] or [T,C].  (app.py:166-170)
+    Differentiable w.r.t. x where autograd asks for it (no `out` then)."""
+    if out is None and torch.is_grad_enabled() and x.requires_grad:
+        return _ZScoreFunction.apply(x)
+    return _zscore_launch(x, out)
+
+
+def _zscore_launch(x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
     squeeze = x.dim() == 2
     x3 = x.unsqueeze(0) if squeeze else x
     if x3.dim() != 3:
@@ -297,7 +330,7 @@ def train_backward(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: tor
 def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: torch.Tensor, labels: torch.Tensor,
                      logits: torch.Tensor, grads: torch.Tensor, *, scale: Optional[float] = None, drop_lstm=None,
                      rrelu_slope=None, drop_head=None, residual: bool = False, adam: Optional[dict] = None,
-                     fused_head: bool = True, rng: Optional[dict] = None) -> None:
+                     fused_head: bool = True, rng: Optional[dict] = None, dx: Optional[torch.Tensor] = None) -> None:
     """The launches of one training evaluation: lstm fwd + head (fwd, mean CE, bwd) in one launch where the shape allows
     (nsd_lstm_head_train; fused_head=False forces the two separate launches), lstm bwd, slab reduce -> `grads` (flat,
     overwritten).  `logits` [B,K] is an output buffer.
@@ -306,7 +339,9 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     (bit-identical to passing the tensors of nsd_train_masks with the same seed / stream ids); needs rng_path(spec, B, T).
 
     adam=dict(m=, v=, step=, lr=, beta1=, beta2=, eps=, weight_decay=): single-rank training -- the optimizer update of
-    `flat` rides in the reduction launch (nsd_grad_reduce_adam); `grads` is still written."""
+    `flat` rides in the reduction launch (nsd_grad_reduce_adam); `grads` is still written.
+
+    dx [B,T,C] (optional output): dL/dx from nsd_lstm_bwd where dx_path(spec, B, T); not with rng= (nsd_lstm_bwd_rng has no dx)."""
     B, T, _ = x.shape
     d = spec.dims(B, T)
     flags = _lib.NSD_FLAG_TRAIN | (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags
@@ -317,10 +352,13 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     xp, wsp, wsn, st, dev = _dev_f32(x, "x", (B, T, spec.C)), _dev_f32(ws, "workspace"), _nbytes(ws), STREAM, x.device
     dl, sl, dh = _dev_f32(drop_lstm, "drop_lstm"), _dev_f32(rrelu_slope, "rrelu_slope"), _dev_f32(drop_head, "drop_head")
     lp = _dev_f32(logits, "logits", (B, spec.K))
+    dxp = _dev_f32(dx, "dx", (B, T, spec.C))
     if rng is not None:
         # the three random streams of the step are generated inside the kernels: no mask tensors
         if drop_lstm is not None or rrelu_slope is not None or drop_head is not None:
             raise NsdError("train_step_grads: pass either rng= or explicit mask tensors, not both")
+        if dx is not None:
+            raise NsdError("train_step_grads: dx= needs explicit mask tensors (nsd_lstm_bwd_rng forms no input gradient)")
         r = _lib.Rng(int(rng["seed"]) & 0xFFFFFFFFFFFFFFFF, int(rng["base_stream"]) & 0xFFFFFFFF, float(rng["p_lstm"]), float(rng["p_head"]))
         _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labels.data_ptr(), scale, flags, wsp, wsn, lp, st)
         _call("nsd_lstm_bwd_rng", dev, C.byref(d), pp, xp, C.byref(r), flags, wsp, wsn, st)
@@ -330,7 +368,7 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
         else:
             _call("nsd_lstm_fwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, st)
             _call("nsd_head_train", dev, C.byref(d), pp, sl, dh, labels.data_ptr(), scale, wsp, wsn, lp, st)
-        _call("nsd_lstm_bwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, None, st)
+        _call("nsd_lstm_bwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, dxp, st)
     gp = _dev_f32(grads, "grads", (spec.param_count,))
     if adam is None:
         _call("nsd_grad_reduce", dev, C.byref(d), wsp, wsn, gp, 0, st)
@@ -344,6 +382,12 @@ def rng_path(spec: ModelSpec, B: int, T: int) -> bool:
     """True where the kernels can generate the train-mode random streams themselves (nsd_rng_path)."""
     d = spec.dims(B, T)
     return bool(_lib.lib().nsd_rng_path(C.byref(d)))
+
+
+def dx_path(spec: ModelSpec, B: int, T: int) -> bool:
+    """True where nsd_lstm_bwd forms the input gradient dx for this shape (nsd_dx_path)."""
+    d = spec.dims(B, T)
+    return bool(_lib.lib().nsd_dx_path(C.byref(d)))
 
 
 def loss_sum(spec: ModelSpec, ws: torch.Tensor, B: int, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -15,10 +15,12 @@ from nsd_amd import _lib, ops
 from oracle import nsd_oracle as orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ABI_VERSION = 301           # NSD_VERSION of include/nsd.h (301: nsd_lstm_bwd's dx after every forward, nsd_dx_path)
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_of_abi_301():
     hdr = open(os.path.join(ROOT, "include", "nsd.h")).read()
+    assert int(re.search(r"#define NSD_VERSION (\d+)", hdr).group(1)) == ABI_VERSION
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(nsd_[a-z0-9_]+)\s*\(", hdr))
     assert declared, "no prototypes parsed"
@@ -26,11 +28,11 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(L, name), f"{name} declared in nsd.h but not exported"
     assert declared == set(_lib.SYMBOLS), (declared ^ set(_lib.SYMBOLS))
-    assert L.nsd_version() == 300
+    assert L.nsd_version() == ABI_VERSION
     assert not hasattr(L, "nsd_debug_profile_buffer")           # diagnostics are not in the shipped library
 
 
-def test_diagnostics_live_only_in_the_diagnostic_build():
+def test_diagnostics_live_only_in_the_diagnostic_build_of_abi_301():
     """The exchange-mode / forced time-out flag bits and the per-kernel timing entry points (csrc/nsd_diag.h) are not in
     include/nsd.h, not exported by libnsd_hip.so and rejected by it; libnsd_hip_diag.so (same objects, orchestration compiled with
     -DNSD_DIAG=1) has them.  No product module asks for the diagnostic library."""
@@ -47,7 +49,7 @@ def test_diagnostics_live_only_in_the_diagnostic_build():
         assert L.nsd_seq_supported(C.byref(d), bit) == 0
         assert L.nsd_seq_workspace_bytes(C.byref(d), bit) == -1 and b"unknown flag" in L.nsd_last_error()
     with _lib.diagnostic_library() as DL:
-        assert DL is not L and hasattr(DL, "nsd_seq_profile") and DL.nsd_version() == 300
+        assert DL is not L and hasattr(DL, "nsd_seq_profile") and DL.nsd_version() == ABI_VERSION
         assert DL.nsd_seq_supported(C.byref(d), _lib.NSD_DIAG_FLAG_SPREAD_GROUPS) == 1
         assert ops.ModelSpec(H=256, K=5).param_count == 807878        # calls inside the block go to the diagnostic library
         with pytest.raises(nsd_amd.NsdError):
@@ -88,6 +90,19 @@ def test_reference_sizes():
     assert ops.ModelSpec(C=0).dims(1, 1).C == 0
     with pytest.raises(nsd_amd.NsdError):
         _ = ops.ModelSpec(C=0).param_count
+
+
+def test_dx_path_query_follows_the_backward_rule():
+    """nsd_dx_path: where nsd_lstm_bwd forms dL/dx -- H = 48 on the fast path (L = 2, C <= 8), and the shape-generic path within the
+    dx kernel's domain (C <= 64, W_ih0 = 4H x C floats in 64 KB); not H = 32 / 64 on the fast path, not the batched path."""
+    def q(B, T, C, H, L):
+        return ops.dx_path(ops.ModelSpec(C=C, H=H, L=L), B, T)
+    assert q(256, 250, 8, 48, 2) and q(1030, 9, 8, 48, 2) and q(1, 1, 3, 48, 2)
+    assert q(4, 20, 8, 48, 3) and q(6, 17, 8, 40, 2) and q(3, 5, 16, 100, 2)        # generic path
+    assert not q(6, 30, 8, 32, 2) and not q(6, 30, 8, 64, 2)                         # H = 32 / 64 fast path
+    assert not q(512, 20, 8, 64, 2) and not q(32, 20, 8, 128, 2)                     # batched path
+    assert not q(3, 5, 64, 100, 2) and not q(3, 5, 80, 40, 2)                        # W_ih0 beyond 64 KB / C > 64
+    assert not q(4, 0, 8, 48, 2)                                                     # invalid dims
 
 
 def test_workspace_layout_is_disjoint_and_aligned():

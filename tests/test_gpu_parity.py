@@ -5,6 +5,7 @@ Tolerances: class logits within 1e-4 (north_star), argmax identical; gradients w
 largest entry of each tensor (the oneDNN reference and an independent fp32 restatement agree to ~2e-6
 relative); integer / mask streams bit-exact.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -46,14 +47,36 @@ def _t(a, dev):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-def _grad_close(got_flat, ref_flat, d, rtol=2e-4):
+# Bounds of the H = 48, C = 8, K = 3 fast path (the benchmarked kernels) against the oracle and the reference goldens: the LSTM weight
+# gradients (split-bf16 sums over time, nsd_lstm2_bwd48*.hip) within 5e-5 of each tensor's largest element, every other tensor within
+# 2e-5, dL/dx within 2e-5 (the 1e-7 floor and attn.bias's 2e-6 as before).  Measured over the whole suite on the MI355X (178 comparisons,
+# _grad_close's "grad_close worst" line): LSTM weight gradients <= 2.5e-5, dL/dx <= 2.4e-6, the other tensors <= 1.7e-5 wherever the
+# 1e-7 floor is not what holds them (tensors with a largest element below ~5e-3 at T <= 2).  Dropping one of the three split-bf16 MFMAs
+# of either backward kernel fails dozens of these comparisons.
+FAST48 = dict(rtol=2e-5, wtol=5e-5)
+DX_TOL = 2e-5
+
+
+def _grad_close(got_flat, ref_flat, d, rtol=2e-4, wtol=None):
+    """Every gradient tensor within rtol of its largest element (+1e-7); the LSTM weight gradients within wtol where given;
+    attn.bias within 2e-6 absolute.  Prints the worst ratio per tensor class (error / largest element; attn.bias: the error)."""
     got, ref = orc.unflatten(got_flat, d), orc.unflatten(ref_flat, d)
+    worst, bad = {"lstm.weight": 0.0, "other": 0.0, "attn.bias": 0.0}, []
     for k in orc.param_names(d):
-        err = np.abs(got[k] - ref[k]).max()
+        err = float(np.abs(got[k] - ref[k]).max())
         if k == "attn.bias":
-            assert err < 2e-6, (k, err)
-        else:
-            assert err <= rtol * max(np.abs(ref[k]).max(), 1e-6) + 1e-7, (k, err, np.abs(ref[k]).max())
+            worst[k] = max(worst[k], err)
+            if not err < 2e-6:
+                bad.append((k, err))
+            continue
+        scale = max(float(np.abs(ref[k]).max()), 1e-6)
+        cls = "lstm.weight" if k.startswith("lstm.weight") else "other"
+        worst[cls] = max(worst[cls], err / scale)
+        tol = wtol if (wtol is not None and cls == "lstm.weight") else rtol
+        if not err <= tol * scale + 1e-7:
+            bad.append((k, err, scale))
+    print("grad_close worst", {k: f"{v:.2e}" for k, v in worst.items()}, "bounds", (rtol, wtol))
+    assert not bad, bad
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -152,8 +175,9 @@ def _hip_loss_grads(nsd, dev, flat_np, x, y, spec=None, scale=None, **masks):
     return loss, g.cpu().numpy(), logits.cpu().numpy()
 
 
-def _hip_step(nsd, dev, flat_np, x, y, fused_head, residual=False, **masks):
-    """ops.train_step_grads (the launch sequence of Trainer.step) -> loss, grads, logits and the head's workspace outputs."""
+def _hip_step(nsd, dev, flat_np, x, y, fused_head, residual=False, want_dx=False, **masks):
+    """ops.train_step_grads (the launch sequence of Trainer.step) -> loss, grads, logits and the head's workspace outputs
+    (+ dL/dx from the same backward call with want_dx)."""
     from nsd_amd import ops
     spec = ops.ModelSpec()
     B, T, _ = x.shape
@@ -162,11 +186,15 @@ def _hip_step(nsd, dev, flat_np, x, y, fused_head, residual=False, **masks):
     ws.fill_(float("nan"))                                   # nothing may be left unwritten
     logits = torch.full((B, spec.K), float("nan"), device=dev)
     grads = torch.empty_like(flat)
+    dx = torch.full_like(xt, float("nan")) if want_dx else None
     mk = {k: _t(v, dev) for k, v in masks.items()}
-    ops.train_step_grads(spec, flat, xt, ws, _t(y.astype(np.int32), dev), logits, grads, residual=residual, fused_head=fused_head, **mk)
+    ops.train_step_grads(spec, flat, xt, ws, _t(y.astype(np.int32), dev), logits, grads, residual=residual, fused_head=fused_head,
+                         dx=dx, **mk)
     out = {r: ops.ws_view(ws, spec, B, T, r).cpu().numpy().copy() for r in ("alpha", "pooled", "fc0_pre", "dscore", "dpooled", "loss")}
     out["logits"] = logits.cpu().numpy()
     out["grads"] = grads.cpu().numpy()
+    if want_dx:
+        out["dx"] = dx.cpu().numpy()
     return out
 
 
@@ -191,7 +219,7 @@ def test_single_launch_lstm_plus_head_train(nsd, dev, ref_state, B, T, residual)
         loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, D, **masks)
         assert np.abs(a["logits"] - fw["logits"]).max() < LOGIT_TOL
         assert abs(float(a["loss"].sum()) / B - loss_ref) < 5e-5
-        _grad_close(a["grads"], g_ref, D, rtol=3e-4)
+        _grad_close(a["grads"], g_ref, D, **FAST48)
 
 
 def test_randomised_shapes_train_step_and_inference_vs_oracle(nsd, dev, ref_state):
@@ -208,7 +236,7 @@ def test_randomised_shapes_train_step_and_inference_vs_oracle(nsd, dev, ref_stat
         a = _hip_step(nsd, dev, flat_np, x, y, True, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
         assert np.abs(a["logits"] - fw["logits"]).max() < LOGIT_TOL, (B, T)
         assert abs(float(a["loss"].sum()) / B - loss_ref) < 5e-5, (B, T)
-        _grad_close(a["grads"], g_ref, D, rtol=3e-4)
+        _grad_close(a["grads"], g_ref, D, **FAST48)
         with torch.no_grad():
             lg = m(_t(x, dev)).cpu().numpy()
         ref = orc.forward(flat_np, x, D)["logits"]
@@ -257,11 +285,11 @@ def test_gradients_vs_reference_goldens(nsd, dev, golden, ref_state):
     x, y = synth_x(32, 250), synth_labels(32)
     loss, grads, _ = _hip_loss_grads(nsd, dev, flat_np, x, y)
     assert abs(loss - float(g["eval.loss"])) < 2e-5
-    _grad_close(grads, orc.flatten_state({k: g["eval." + k] for k in orc.param_names(D)}, D), D)
+    _grad_close(grads, orc.flatten_state({k: g["eval." + k] for k in orc.param_names(D)}, D), D, **FAST48)
     dl, sl, dh = counter_masks(32, 250, 48, 32)
     loss, grads, _ = _hip_loss_grads(nsd, dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     assert abs(loss - float(g["masked.loss"])) < 5e-5
-    _grad_close(grads, orc.flatten_state({k: g["masked." + k] for k in orc.param_names(D)}, D), D)
+    _grad_close(grads, orc.flatten_state({k: g["masked." + k] for k in orc.param_names(D)}, D), D, **FAST48)
 
 
 @pytest.mark.parametrize("B,T", [(1, 1), (2, 3), (9, 64), (5, 33), (300, 20), (301, 6), (700, 9), (1027, 5)])
@@ -274,7 +302,7 @@ def test_gradients_vs_oracle_ragged_shapes(nsd, dev, ref_state, B, T):
     loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL
     assert abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, D, rtol=3e-4)
+    _grad_close(grads, g_ref, D, **FAST48)
 
 
 def test_residual_extension(nsd, dev, golden):
@@ -283,7 +311,7 @@ def test_residual_extension(nsd, dev, golden):
     x, y = synth_x(5, 40, seed=5), synth_labels(5, seed=5)
     loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, residual=True)
     assert np.abs(logits - e["residual.logits"]).max() < 2e-5
-    _grad_close(grads, orc.flatten_state({k: e["residual.grad." + k] for k in orc.param_names(D)}, D), D)
+    _grad_close(grads, orc.flatten_state({k: e["residual.grad." + k] for k in orc.param_names(D)}, D), D, rtol=2e-4)
     m = _model(nsd, dev, synth_params(8, 48, 2, 3, seed=7), residual=True).eval()
     with torch.no_grad():
         assert np.abs(m(_t(x, dev)).cpu().numpy() - e["residual.logits"]).max() < 2e-5
@@ -507,7 +535,7 @@ def test_trainer_step_matches_oracle_with_its_own_streams(nsd, dev, ref_state):
     dh = orc.dropout_mask(tr.seed, sid + 2, 0.6, (B, 32))
     loss_ref, g_ref, _ = orc.loss_and_grads(flat0, x, y, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     assert abs(tr.last_loss() - loss_ref) < 5e-5
-    _grad_close(tr.grads.cpu().numpy(), g_ref, D, rtol=3e-4)
+    _grad_close(tr.grads.cpu().numpy(), g_ref, D, **FAST48)
     # Adam on the step's own gradient (entries with |g| ~ eps make the update ill-conditioned w.r.t. g itself)
     p, mm, vv = flat0.copy(), np.zeros_like(flat0), np.zeros_like(flat0)
     orc.adam(p, tr.grads.cpu().numpy(), mm, vv, lr=1e-3, step=1)
@@ -966,7 +994,7 @@ def test_two_trials_per_workgroup_forward_equals_the_one_trial_kernel_bitwise(ns
                 loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, xn, yn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn, residual=residual)
                 loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn, residual=residual)
                 assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-                _grad_close(grads, g_ref, D, rtol=3e-4)
+                _grad_close(grads, g_ref, D, **FAST48)
         finally:
             ops.force_fwd48(0)
 
@@ -1025,7 +1053,7 @@ def test_four_trials_per_workgroup_forward_on_the_matrix_pipe(nsd, dev, ref_stat
             ops.force_fwd48(4)
             loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
             assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-            _grad_close(grads, g_ref, D, rtol=3e-4)
+            _grad_close(grads, g_ref, D, **FAST48)
         finally:
             ops.force_fwd48(0)
 
@@ -1069,13 +1097,13 @@ def test_four_trials_per_workgroup_backward_on_the_matrix_pipe(nsd, dev, ref_sta
                 assert torch.isfinite(g4).all(), kw.keys()
                 assert (g2 - g4).abs().max().item() <= 2e-5 * g2.abs().max().item() + 1e-9, (kw.keys(), (g2 - g4).abs().max().item(), g2.abs().max().item())
                 if vi < 2:
-                    _grad_close(g4.cpu().numpy() * 1.0, g_ref, D, rtol=3e-4)
+                    _grad_close(g4.cpu().numpy() * 1.0, g_ref, D, **FAST48)
             # both new kernels together (what the product runs from 513 trials on), against the oracle
             ops.force_fwd48(4)
             ops.force_bwd48(4)
             loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
             assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-            _grad_close(grads, g_ref, D, rtol=3e-4)
+            _grad_close(grads, g_ref, D, **FAST48)
         finally:
             ops.force_fwd48(0)
             ops.force_bwd48(0)
@@ -1172,7 +1200,7 @@ def test_four_trial_kernels_loop_over_trial_groups(nsd, dev, ref_state):
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, D, rtol=3e-4)
+    _grad_close(grads, g_ref, D, **FAST48)
 
 
 @pytest.mark.parametrize("B,T,nb", [(32, 250, 1), (12, 625, 1), (32, 250, 4), (12, 625, 4)])
@@ -1268,7 +1296,7 @@ def test_batch_bands_of_the_dispatch_vs_oracle(nsd, dev, ref_state, B, T):
     for fused in (True, False):
         out = _hip_step(nsd, dev, flat_np, xn, yn, fused, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
         assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL and abs(float(out["loss"].sum()) / B - loss_ref) < 5e-5
-        _grad_close(out["grads"], g_ref, D, rtol=3e-4)
+        _grad_close(out["grads"], g_ref, D, **FAST48)
         res.append(out["grads"])
     assert np.abs(res[0] - res[1]).max() <= 2e-5 * np.abs(res[0]).max()
 
@@ -1327,9 +1355,196 @@ def test_every_sequence_length_up_to_40(nsd, dev, ref_state, nb):
                 loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
                 assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL, T
                 try:
-                    _grad_close(grads, g_ref, D, rtol=3e-4)
+                    _grad_close(grads, g_ref, D, **FAST48)
                 except AssertionError as e:
                     raise AssertionError(f"T={T}: {e}")
         finally:
             ops.force_fwd48(0)
             ops.force_bwd48(0)
+
+
+# ---------------------------------------------------------------------------------------------------
+# dL/dx on every call path of the H = 48 fast path
+@pytest.mark.parametrize("B,T,force", [(513, 9, 0), (1030, 9, 0), (5, 33, 0), (300, 20, 0), (7, 33, 4), (9, 250, 4)])
+def test_input_gradient_after_the_fused_head_vs_oracle(nsd, dev, ref_state, B, T, force):
+    """nsd_lstm_head_train, then nsd_lstm_bwd with dx (ops.train_step_grads(dx=)), against the oracle's forward + backward with the same
+    masks: logits, loss, every gradient tensor, dx, the workspace's alpha and dscore.  From 513 trials (and under the diagnostic
+    library's force_fwd48(4) / force_bwd48(4) at small batches) the fused four-trial forward leaves the attention records OPEN for the
+    four-trial backward kernel; dx sends the backward to the one-trial kernel, which needs them closed first.  5 x 33 and 300 x 20:
+    the forward closes its own records.  The fused and the unfused head agree to 2e-5 at every shape."""
+    from nsd_amd import _lib, ops
+    flat_np = orc.flatten_state(ref_state, D)
+    xn, yn = synth_x(B, T, seed=5 * B + T), synth_labels(B, seed=5 * B + T)
+    dln, sln, dhn = counter_masks(B, T, 48, 32, seed=2 * B + T)
+    masks = dict(drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+    fw = orc.forward(flat_np, xn, D, saves=True, **masks)
+    loss_ref, dl = orc.ce_loss(fw["logits"], yn)
+    g_ref, dx_ref = orc.backward(flat_np, xn, D, fw, dl, want_dx=True, **masks)
+    outs = {}
+    with (_lib.diagnostic_library() if force else contextlib.nullcontext()):
+        try:
+            if force:
+                ops.force_fwd48(force)
+                ops.force_bwd48(force)
+            for fused in (True, False):
+                outs[fused] = _hip_step(nsd, dev, flat_np, xn, yn, fused, want_dx=True, **masks)
+        finally:
+            if force:
+                ops.force_fwd48(0)
+                ops.force_bwd48(0)
+    h1, pooled = fw["hseq"][1].astype(np.float64), fw["pooled"].astype(np.float64)
+    for fused, out in outs.items():
+        assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL, fused
+        assert abs(float(out["loss"].sum()) / B - loss_ref) < 5e-5, fused
+        _grad_close(out["grads"], g_ref, D, **FAST48)
+        err, scale = float(np.abs(out["dx"] - dx_ref).max()), float(np.abs(dx_ref).max())
+        print(f"dx B={B} T={T} fused={fused}: max error / largest element {err / scale:.2e}")
+        assert err <= DX_TOL * scale, (fused, err, scale)
+        assert np.abs(out["alpha"] - fw["alpha"]).max() <= 2e-5 * np.abs(fw["alpha"]).max(), fused
+        # dL/dscore_t = alpha_t dpooled . (h1_t - pooled), in double from the oracle's activations and the kernels' dL/dpooled
+        ds_ref = fw["alpha"] * np.einsum("bth,bh->bt", h1 - pooled[:, None, :], out["dpooled"].astype(np.float64))
+        assert np.abs(out["dscore"] - ds_ref).max() <= 2e-5 * np.abs(ds_ref).max() + 1e-9, fused
+    a, b = outs[True], outs[False]
+    assert np.abs(a["grads"] - b["grads"]).max() <= 2e-5 * np.abs(b["grads"]).max()
+    assert np.abs(a["dx"] - b["dx"]).max() <= 2e-5 * np.abs(b["dx"]).max()
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("B,T", [(256, 250), (512, 250), (1024, 250)])
+def test_benchmarked_shapes_train_step_vs_oracle(nsd, dev, ref_state, B, T):
+    """The shapes bench.py measures (cfg2: 256 x 250, cfg4: 1024 x 250) and the two-trial band between them, through Trainer.step
+    itself: the random streams drawn inside the kernels (nsd_lstm_head_train_rng / nsd_lstm_bwd_rng), the fused reduce + Adam --
+    against the oracle with the same counter-based masks: loss, logits (1e-4, same argmax), every gradient tensor (FAST48), the Adam
+    update.  At 1024 x 250 also dL/dx through the module (eval mode, the unfused head, the one-trial backward kernel)."""
+    from nsd_amd.trainer import Trainer
+    m = _model(nsd, dev, ref_state).train()
+    tr = Trainer(m, lr=1e-3, seed=7)
+    xn, yn = synth_x(B, T, seed=B + 11), synth_labels(B, seed=B + 11)
+    flat0 = orc.flatten_state(ref_state, D)
+    tr.step(_t(xn, dev), _t(yn, dev))
+    logits = tr._buffers(B, T)["logits"].cpu().numpy()
+    sid = 4
+    dln = orc.dropout_mask(tr.seed, sid, 0.6, (1, B, T, 48))
+    sln = orc.rrelu_noise(tr.seed, sid + 1, (B, 32))
+    dhn = orc.dropout_mask(tr.seed, sid + 2, 0.6, (B, 32))
+    loss_ref, g_ref, fw = orc.loss_and_grads(flat0, xn, yn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+    assert abs(tr.last_loss() - loss_ref) < 5e-5
+    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL
+    assert np.array_equal(logits.argmax(1), fw["logits"].argmax(1))
+    grads = tr.grads.cpu().numpy()
+    _grad_close(grads, g_ref, D, **FAST48)
+    p, mm, vv = flat0.copy(), np.zeros_like(flat0), np.zeros_like(flat0)
+    orc.adam(p, grads, mm, vv, lr=1e-3, step=1)
+    assert np.abs(m.flat_parameters().cpu().numpy() - p).max() < 2e-6
+    if B == 1024:
+        m2 = _model(nsd, dev, ref_state).eval()
+        fw2 = orc.forward(flat0, xn, D, saves=True)
+        _, dl2 = orc.ce_loss(fw2["logits"], yn)
+        g2_ref, dx_ref = orc.backward(flat0, xn, D, fw2, dl2, want_dx=True)
+        xg = _t(xn, dev).requires_grad_(True)
+        torch.nn.functional.cross_entropy(m2(xg), _t(yn.astype(np.int64), dev)).backward()
+        g2 = torch.cat([p.grad.reshape(-1) for _, p in m2._named_in_order()]).cpu().numpy()
+        _grad_close(g2, g2_ref, D, **FAST48)
+        err, scale = float(np.abs(xg.grad.cpu().numpy() - dx_ref).max()), float(np.abs(dx_ref).max())
+        print(f"dx B={B} T={T} (module): max error / largest element {err / scale:.2e}")
+        assert err <= DX_TOL * scale, (err, scale)
+
+
+def test_generic_path_dx_outside_the_dx_kernel_is_refused_before_any_launch(nsd, dev):
+    """C = 64, H = 100, L = 2 goes to the shape-generic path (not fast, H % 16 != 0: not batched), where W_ih0 (4H x C floats = 100 KB)
+    does not fit the dx kernel's 64 KB of LDS: nsd_lstm_bwd with dx returns NSD_E_INVALID and the workspace is bit-identical."""
+    import ctypes as C
+    from nsd_amd import _lib, ops
+    spec = ops.ModelSpec(C=64, H=100, L=2, K=3)
+    B, T = 3, 5
+    assert not spec.fast_path() and not ops.dx_path(spec, B, T)
+    d = spec.dims(B, T)
+    ws = ops.new_workspace(spec, B, T, dev)
+    ws.fill_(-1234.5)
+    before = ws.cpu().numpy().copy()
+    flat = torch.zeros(spec.param_count, device=dev)
+    x, dx = torch.zeros((B, T, 64), device=dev), torch.zeros((B, T, 64), device=dev)
+    L = _lib.lib()
+    rc = L.nsd_lstm_bwd(C.byref(d), flat.data_ptr(), x.data_ptr(), None, _lib.NSD_FLAG_TRAIN, ws.data_ptr(), ws.numel() * 4,
+                        dx.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == -1 and b"dx" in L.nsd_last_error()
+    assert np.array_equal(ws.cpu().numpy().view(np.uint32), before.view(np.uint32))
+
+
+def test_input_gradient_on_the_generic_path_survives_a_second_backward(nsd, dev):
+    """H = 48, L = 3 is the generic path: its dx comes from da_seq and leaves the saved gates alone, so retain_graph gives the same
+    parameter gradients and the same dx twice."""
+    torch.manual_seed(3)
+    m = nsd.EEG_LSTM(hidden_size=48, num_layers=3).to(dev).eval()
+    xg = _t(synth_x(4, 20), dev).requires_grad_(True)
+    out = torch.nn.functional.cross_entropy(m(xg), _t(synth_labels(4).astype(np.int64), dev))
+    res = []
+    for _ in range(2):
+        for p in m.parameters():
+            p.grad = None
+        xg.grad = None
+        out.backward(retain_graph=True)
+        res.append(([p.grad.clone() for p in m.parameters()], xg.grad.clone()))
+    assert all(torch.equal(a, b) for a, b in zip(res[0][0], res[1][0]))
+    assert torch.equal(res[0][1], res[1][1]) and torch.isfinite(res[0][1]).all()
+
+
+def test_paths_without_an_input_gradient_still_return_the_parameter_gradients(nsd, dev):
+    """H = 32 (fast path, no dx kernel): x.requires_grad gives the parameter gradients of the oracle, x.grad None and a UserWarning."""
+    from nsd_amd import lstm_eeg_model
+    d = orc.Dims(C=8, H=32, L=2, K=3)
+    st = synth_params(8, 32, 2, 3, seed=4)
+    m = _model(nsd, dev, st).eval()
+    B, T = 6, 30
+    xn, yn = synth_x(B, T, seed=8), synth_labels(B, seed=8)
+    _, g_ref, _ = orc.loss_and_grads(orc.flatten_state(st, d), xn, yn, d)
+    lstm_eeg_model._no_dx_warned.discard(m.spec)
+    xg = _t(xn, dev).requires_grad_(True)
+    with pytest.warns(UserWarning, match="no input gradient"):
+        torch.nn.functional.cross_entropy(m(xg), _t(yn.astype(np.int64), dev)).backward()
+    assert xg.grad is None
+    g = torch.cat([p.grad.reshape(-1) for _, p in m._named_in_order()]).cpu().numpy()
+    _grad_close(g, g_ref, d, rtol=3e-4)
+
+
+def test_normalize_input_gradient_matches_torch_autograd(nsd, dev, ref_state):
+    """normalize=True: x.grad through the z-score (an autograd node: the kernel forward, the closed-form backward) and the model,
+    against CPU autograd of the same composition -- the oracle's z-score definition in torch ops feeding StackedTorchEEG -- 2e-4 of the
+    largest element."""
+    from oracle.torch_ref import StackedTorchEEG
+    B, T = 5, 40
+    ref = StackedTorchEEG(C=8, H=48, L=2, K=3).eval()
+    ref.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in ref_state.items()}, strict=True)
+    m = _model(nsd, dev, ref_state, normalize=True).eval()
+    xn, yn = (3.0 * synth_x(B, T, seed=21) + 1.5).astype(np.float32), synth_labels(B, seed=21).astype(np.int64)
+    xr = torch.from_numpy(xn).double().requires_grad_(True)
+    mu = xr.mean(dim=1, keepdim=True)
+    sd = (xr - mu).square().mean(dim=1, keepdim=True).sqrt() + 1e-6
+    torch.nn.functional.cross_entropy(ref.double()((xr - mu) / sd), torch.from_numpy(yn)).backward()
+    xg = _t(xn, dev).requires_grad_(True)
+    torch.nn.functional.cross_entropy(m(xg), _t(yn, dev)).backward()
+    assert xg.grad is not None and torch.isfinite(xg.grad).all()
+    err, scale = (xg.grad.cpu().double() - xr.grad).abs().max().item(), xr.grad.abs().max().item()
+    print(f"normalize dx: max error {err:.3e}, largest element {scale:.3e}")
+    assert err <= 2e-4 * scale, (err, scale)
+
+
+@pytest.mark.parametrize("B,T", [(514, 11), (600, 6)])
+def test_residual_extension_two_trial_backward_vs_oracle(nsd, dev, ref_state, B, T):
+    """The residual extension from 513 trials on: the four-trial kernels do not take it, so the backward is the two-trial instantiation
+    of nsd_lstm2_bwd48.hip (the only place its residual hand-off dout1 = alpha dpooled + dscore attn_w to layer 0 runs).  Train step with
+    explicit masks against the oracle (residual=True): logits 1e-4, loss, gradients 2e-4 of each tensor's largest element (the bound of
+    the residual golden test); the fused and the unfused head agree."""
+    flat_np = orc.flatten_state(ref_state, D)
+    xn, yn = synth_x(B, T, seed=B + 5 * T), synth_labels(B, seed=B + 5 * T)
+    dln, sln, dhn = counter_masks(B, T, 48, 32, seed=3 * B + T)
+    masks = dict(drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+    loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, xn, yn, D, residual=True, **masks)
+    res = []
+    for fused in (True, False):
+        out = _hip_step(nsd, dev, flat_np, xn, yn, fused, residual=True, **masks)
+        assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL and abs(float(out["loss"].sum()) / B - loss_ref) < 5e-5
+        _grad_close(out["grads"], g_ref, D, rtol=2e-4)
+        res.append(out["grads"])
+    assert np.abs(res[0] - res[1]).max() <= 2e-5 * np.abs(res[0]).max()
