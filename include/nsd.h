@@ -44,6 +44,8 @@ extern "C" {
                                     0.3.0: sequence-batched path: persistent workspace header (nsd_seq_workspace_init), sticky
                                     status, nsd_seq_guard / nsd_adam_step_guarded; diagnostics left the shipped library */
 #define NSD_MAX_LAYERS 8
+#define NSD_MAX_MODELS 32        /* nsd_multi_*: models per launch.  The model-batched entry points are additive and leave NSD_VERSION
+                                    at 301: a caller detects them with nsd_multi_path (a library without them lacks the symbol) */
 
 #define NSD_OK            0
 #define NSD_E_INVALID    -1      /* bad argument / unsupported shape */
@@ -236,6 +238,47 @@ int nsd_train_masks_dev(uint64_t seed, const int64_t *step_dev, float p_lstm, fl
                         int64_t n_head, float *rrelu_slope, float *drop_head, void *stream);
 int nsd_adam_step_dev(int64_t n, float *p, const float *g, float *m, float *v, float lr, float beta1, float beta2, float eps,
                       float weight_decay, float grad_scale, const int64_t *step_dev, void *stream);
+
+/*
+ * ---- model-batched H = 48 path: M models of one shape trained / evaluated in the launches one model uses ----
+ *
+ * Folds, seeds and ensembles of EEG_LSTM (lstm_eeg_model.py:13-39): each model has its own parameters, windows, labels and random
+ * streams; a launch covers all of them.  Layout ("one batch of M*B trials, partitioned by model", d->B = trials PER MODEL):
+ *   params   [M][P]       P = nsd_param_count; each block in the flat order above
+ *   x        model m reads x + m * x_model_stride floats ([B,T,C] each); x_model_stride = 0: every model reads the same windows
+ *   labels   [M*B]  logits / probs [M*B][K]  grads [M][P]
+ *   workspace  the regions of a batch of M*B trials (model m's trial b is trial m*B + b); nsd_multi_workspace_bytes
+ *   rng      NULL (no dropout, eval RReLU slope) or M entries: model m's streams are exactly those of a single-model call with rng[m]
+ *            at batch B (nsd_lstm_head_train_rng).  All entries share p_lstm / p_head.
+ * Each model's step is that of nsd_lstm_head_train_rng (scale 1/B: mean CE per model, lstm_eeg_model.py:32-39) + nsd_lstm_bwd_rng +
+ * nsd_grad_reduce(_adam) on its own; the kernels dispatch on the M*B trials of the launch as the single-model entry points do on B.
+ * Where nsd_multi_path(d, M) == 0 every entry point returns NSD_E_INVALID before any launch (nsd_last_error says why), as it does for
+ * M outside [1, NSD_MAX_MODELS], NULL pointers, mismatched rng probabilities, NSD_FLAG_RESIDUAL or a negative / overlapping
+ * x_model_stride; a workspace smaller than nsd_multi_workspace_bytes gives NSD_E_WORKSPACE.  The residual extension and dx are not
+ * offered here.
+ *   nsd_multi_path            1 for H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8 and 1 <= M <= NSD_MAX_MODELS, else 0
+ *   nsd_multi_train_fwd       forward + head + mean CE per model + head backward; logits [M*B][K]
+ *   nsd_multi_train_bwd       BPTT into the per-workgroup slabs (same rng as the forward call)
+ *   nsd_multi_grad_reduce     grads[m] = model m's slabs summed (overwritten), all models in one launch
+ *   nsd_multi_grad_reduce_adam  the same + torch.optim.Adam on p / m / v [M][P] in that launch (= reduce, then nsd_adam_step(n = M*P))
+ *   nsd_multi_loss_sum        out[m] = sum of model m's per-trial CE losses (device)
+ *   nsd_multi_infer           eval-mode forward + class softmax (lstm_eeg_model.py:32-39, :97) of every model on its windows;
+ *                             scratch: nsd_multi_infer_scratch_bytes(d, M) bytes (0: may be NULL)
+ */
+int     nsd_multi_path(const nsd_dims *d, int32_t M);
+int64_t nsd_multi_workspace_bytes(const nsd_dims *d, int32_t M, nsd_ws_layout *layout_out);
+int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                        const int32_t *labels, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream);
+int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                        uint32_t flags, float *workspace, int64_t workspace_bytes, void *stream);
+int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, void *stream);
+int nsd_multi_grad_reduce_adam(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
+                               float *m, float *v, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                               int32_t step, void *stream);
+int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream);
+int64_t nsd_multi_infer_scratch_bytes(const nsd_dims *d, int32_t M);
+int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,
+                    float *logits, float *probs, void *scratch, void *stream);
 
 /*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----

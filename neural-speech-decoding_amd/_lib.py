@@ -89,7 +89,18 @@ SYMBOLS = {
     "nsd_seq_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
     "nsd_seq_guard": (C.c_int, [_vp, _fp, _vp]),
     "nsd_train_masks": (C.c_int, [C.c_uint64, C.c_uint32, C.c_float, C.c_float, C.c_int64, _fp, C.c_int64, _fp, _fp, _vp]),
+    # model-batched H = 48 path (several models per launch)
+    "nsd_multi_path": (C.c_int, [_dp, C.c_int32]),
+    "nsd_multi_workspace_bytes": (C.c_int64, [_dp, C.c_int32, C.POINTER(WsLayout)]),
+    "nsd_multi_train_fwd": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _vp, _ip, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
+    "nsd_multi_train_bwd": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _vp, C.c_uint32, _fp, C.c_int64, _vp]),
+    "nsd_multi_grad_reduce": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
+    "nsd_multi_grad_reduce_adam": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp] + [C.c_float] * 6 + [C.c_int32, _vp]),
+    "nsd_multi_loss_sum": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
+    "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
+    "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),
 }
+NSD_MAX_MODELS = 32
 
 
 # entry points of the diagnostic build only (csrc/nsd_diag.h)

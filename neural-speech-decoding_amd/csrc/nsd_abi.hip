@@ -4,6 +4,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include "nsd_args.h"
+#include "nsd_multi.h"
 #include "nsd_bf16.h"
 
 // ---- error text -------------------------------------------------------------------------------------------
@@ -603,6 +604,216 @@ int nsd_gemm_bf16(const void *A, int64_t lda, int32_t a_kmajor, const void *B, i
     g.A = (const bf16_t *)A; g.B = (const bf16_t *)B; g.lda = lda; g.ldb = ldb; g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor;
     g.b_shift = b_shift; g.C = C; g.ldc = ldc; g.bias = bias; g.M = M; g.N = N; g.K = K; g.splits = splits; g.epi = epilogue;
     return nsd_gemm_bf16_launch(g, (hipStream_t)stream);
+}
+
+// ---- model-batched H = 48 path (nsd_multi_*, include/nsd.h; nsd_multi.h) ----------------------------------------------------------
+// M = 1 runs the single-model entry points themselves.  M > 1: the kernels' model-batched twins on a workspace of M*B trials.
+static bool multi_shape(const nsd_dims *d, int M) {
+    return nsd_check_dims(d) == NSD_OK && M >= 1 && M <= NSD_MAX_MODELS && fused_train_shape(d) && (int64_t)M * d->B <= 0x7fffffff;
+}
+static int multi_check(const nsd_dims *d, int M, const char *who) {
+    if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (!multi_shape(d, M)) {
+        nsd_set_error("%s: shape outside the model-batched path (nsd_multi_path: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)", who);
+        return NSD_E_INVALID;
+    }
+    return NSD_OK;
+}
+static nsd_dims multi_total(const nsd_dims *d, int M) { nsd_dims t = *d; t.B = M * d->B; return t; }
+static nsd_ws_layout make_multi_ws(const nsd_dims *d, int M, bool have_device) {
+    const nsd_dims t = multi_total(d, M);
+    nsd_ws_layout w = make_ws(&t, have_device);
+    if (M == 1) return w;
+    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+    const int64_t nsl = (int64_t)M * nsd_lstm2_multi_bwd_groups(M, d->B > 0 ? d->B : 1);
+    if (nsl > w.n_slabs) {       // room for M * G slabs: the head slabs (and the generic path's regions, empty here) move behind them
+        const int64_t grow = (nsl - w.n_slabs) * align4(pl.lstm_total);
+        w.n_slabs = nsl; w.hslabs += grow; w.da_seq += grow; w.din += grow; w.total += grow;
+    }
+    return w;
+}
+static int multi_ws(const nsd_dims *d, int M, const void *ws, int64_t bytes, const char *who, nsd_ws_layout *w) {
+    if (!ws) { nsd_set_error("%s: workspace is NULL", who); return NSD_E_INVALID; }
+    *w = make_multi_ws(d, M, true);
+    if (bytes < w->total * (int64_t)sizeof(float)) {
+        nsd_set_error("%s: workspace of %lld bytes is smaller than nsd_multi_workspace_bytes() = %lld", who, (long long)bytes,
+                      (long long)(w->total * (int64_t)sizeof(float)));
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+// rng: NULL or M entries with one p_lstm / p_head
+static int multi_rng(const nsd_rng *rng, int M, const char *who, RngArgs *r, ModelSplit *s) {
+    memset(r, 0, sizeof(*r));
+    if (!rng) return NSD_OK;
+    for (int m = 0; m < M; ++m)
+        if (rng[m].p_lstm != rng[0].p_lstm || rng[m].p_head != rng[0].p_head) {
+            nsd_set_error("%s: rng[%d] has p_lstm / p_head %g / %g, rng[0] %g / %g: all models share the probabilities", who, m,
+                          rng[m].p_lstm, rng[m].p_head, rng[0].p_lstm, rng[0].p_head);
+            return NSD_E_INVALID;
+        }
+    if (make_rng(&rng[0], r) != NSD_OK) return NSD_E_INVALID;
+    s->rng_on = 1;
+    for (int m = 0; m < M; ++m) { s->seed[m] = rng[m].seed; s->base[m] = rng[m].base_stream; }
+    return NSD_OK;
+}
+static int multi_common(const nsd_dims *d, int M, int64_t x_stride, uint32_t flags, const char *who) {
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (flags & (NSD_FLAG_RESIDUAL | NSD_FLAG_BIDIR)) { nsd_set_error("%s: flags 0x%x: no residual extension on the model-batched path", who, flags); return NSD_E_INVALID; }
+    if (x_stride != 0 && (M > 1 && x_stride < (int64_t)d->B * d->T * d->C)) {
+        nsd_set_error("%s: x_model_stride %lld: 0 (one window set for all models) or >= B*T*C = %lld", who, (long long)x_stride,
+                      (long long)d->B * d->T * d->C);
+        return NSD_E_INVALID;
+    }
+    return NSD_OK;
+}
+
+int nsd_multi_path(const nsd_dims *d, int32_t M) { return multi_shape(d, M) ? 1 : 0; }
+
+int64_t nsd_multi_workspace_bytes(const nsd_dims *d, int32_t M, nsd_ws_layout *layout_out) {
+    if (multi_check(d, M, "multi_workspace_bytes") != NSD_OK) return NSD_E_INVALID;
+    const nsd_ws_layout w = make_multi_ws(d, M, device_present());
+    if (layout_out) *layout_out = w;
+    return w.total * (int64_t)sizeof(float);
+}
+
+int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                        const int32_t *labels, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    static const char *who = "multi_train_fwd";
+    if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
+    if (!params || !x || !labels || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    ModelSplit s;
+    memset(&s, 0, sizeof(s));
+    RngArgs r;
+    if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
+    nsd_ws_layout w;
+    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, who, &w)) return rc;
+    if (d->B == 0) return NSD_OK;
+    const float scale = 1.0f / (float)d->B;                     // mean CE per model
+    if (M == 1) return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, rng ? &r : nullptr, labels, scale, flags, workspace,
+                                            workspace_bytes, logits, stream);
+    const nsd_dims t = multi_total(d, M);
+    Lstm2FwdArgs a;
+    build_lstm_fwd(&t, params, x, nullptr, flags, workspace, w, true, nullptr, &a);
+    const HeadArgs h = build_head(d, params);
+    a.B = d->B;
+    a.attn_w = h.attn_w; a.attn_b = h.attn_b; a.ln_w = h.ln_w; a.ln_b = h.ln_b;
+    a.fc0_w = h.fc0_w; a.fc0_b = h.fc0_b; a.fc3_w = h.fc3_w; a.fc3_b = h.fc3_b;
+    a.eval_slope = h.eval_slope; a.K = d->K; a.F = d->F;
+    a.head_train = 1;
+    a.top = nullptr;
+    a.labels = labels; a.scale = scale;
+    a.logits = logits; a.loss = workspace + w.loss; a.alpha = workspace + w.alpha; a.pooled = workspace + w.pooled;
+    a.fc0_pre = workspace + w.fc0_pre; a.dscore = workspace + w.dscore; a.dpooled = workspace + w.dpooled;
+    a.adpack = workspace + w.adpack; a.hslabs = workspace + w.hslabs;
+    a.o_ln_w = h.o_ln_w; a.o_ln_b = h.o_ln_b; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
+    a.o_fc0_w = h.o_fc0_w; a.o_fc0_b = h.o_fc0_b; a.o_fc3_w = h.o_fc3_w; a.o_fc3_b = h.o_fc3_b; a.Ph = h.Ph;
+    a.rng = r;
+    s.x_stride = x_model_stride; s.P = nsd_make_layout(d->C, d->H, d->L, d->K, d->F).total;
+    return nsd_lstm2_multi_fwd_launch(a, s, M, (hipStream_t)stream);
+}
+
+int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                        uint32_t flags, float *workspace, int64_t workspace_bytes, void *stream) {
+    static const char *who = "multi_train_bwd";
+    if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
+    if (!params || !x) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    ModelSplit s;
+    memset(&s, 0, sizeof(s));
+    RngArgs r;
+    if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
+    nsd_ws_layout w;
+    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, who, &w)) return rc;
+    if (d->B == 0) return NSD_OK;
+    if (M == 1) return lstm_bwd_impl(d, params, x, nullptr, rng ? &r : nullptr, flags, workspace, workspace_bytes, nullptr, stream);
+    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+    const int64_t BTH = (int64_t)M * d->B * d->T * d->H;       // per-layer stride of the [L, M*B, T, H] regions
+    Lstm2BwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x;
+    a.w_hh0 = params + pl.w_hh[0]; a.w_ih1 = params + pl.w_ih[1]; a.w_hh1 = params + pl.w_hh[1];
+    a.attn_w = params + pl.attn_w;
+    a.hseq0 = workspace + w.hseq; a.hseq1 = workspace + w.hseq + BTH;
+    a.cseq0 = workspace + w.cseq; a.cseq1 = workspace + w.cseq + BTH;
+    a.gact0 = workspace + w.gact; a.gact1 = workspace + w.gact + 4 * BTH;
+    a.in1seq = workspace + w.inseq;
+    a.alpha = workspace + w.alpha; a.dscore = workspace + w.dscore; a.dpooled = workspace + w.dpooled;
+    a.dsc_pack = workspace + w.adpack;
+    const HeadArgs h = build_head(d, params);
+    a.pooled = workspace + w.pooled; a.dscore_out = workspace + w.dscore; a.hslabs = workspace + w.hslabs;
+    a.Ph = h.Ph; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
+    a.dbg = g_dbg;
+    a.slabs = workspace + w.slabs;
+    a.slab_stride = align4(pl.lstm_total);
+    a.o_w_ih0 = pl.w_ih[0]; a.o_w_hh0 = pl.w_hh[0]; a.o_b_ih0 = pl.b_ih[0]; a.o_b_hh0 = pl.b_hh[0];
+    a.o_w_ih1 = pl.w_ih[1]; a.o_w_hh1 = pl.w_hh[1]; a.o_b_ih1 = pl.b_ih[1]; a.o_b_hh1 = pl.b_hh[1];
+    a.B = d->B; a.T = d->T; a.C = d->C;
+    a.ablate = ablate_mask();
+    a.rng = r;
+    s.x_stride = x_model_stride; s.P = pl.total;
+    return nsd_lstm2_multi_bwd_launch(a, s, M, (hipStream_t)stream);
+}
+
+int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, void *stream) {
+    if (const int rc = multi_check(d, M, "multi_grad_reduce")) return rc;
+    if (!grads) { nsd_set_error("multi_grad_reduce: null pointer"); return NSD_E_INVALID; }
+    nsd_ws_layout w;
+    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_grad_reduce", &w)) return rc;
+    if (M == 1) return nsd_grad_reduce(d, workspace, workspace_bytes, grads, 0, stream);
+    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+    return nsd_multi_grad_reduce_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_multi_bwd_groups(M, d->B) : 0,
+                                        pl.lstm_total, workspace + w.hslabs, pl.total - pl.lstm_total, d->B, M, grads, (hipStream_t)stream);
+}
+
+int nsd_multi_grad_reduce_adam(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
+                               float *m, float *v, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                               int32_t step, void *stream) {
+    if (const int rc = multi_check(d, M, "multi_grad_reduce_adam")) return rc;
+    if (!grads || !p || !m || !v) { nsd_set_error("multi_grad_reduce_adam: null pointer"); return NSD_E_INVALID; }
+    nsd_ws_layout w;
+    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_grad_reduce_adam", &w)) return rc;
+    if (M == 1) return nsd_grad_reduce_adam(d, workspace, workspace_bytes, grads, p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step, stream);
+    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+    return nsd_multi_grad_reduce_adam_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_multi_bwd_groups(M, d->B) : 0,
+                                             pl.lstm_total, workspace + w.hslabs, pl.total - pl.lstm_total, d->B, M, grads, p, m, v, lr,
+                                             beta1, beta2, eps, weight_decay, grad_scale, step, (hipStream_t)stream);
+}
+
+int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {
+    if (const int rc = multi_check(d, M, "multi_loss_sum")) return rc;
+    if (!out) { nsd_set_error("multi_loss_sum: null pointer"); return NSD_E_INVALID; }
+    nsd_ws_layout w;
+    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_loss_sum", &w)) return rc;
+    return nsd_multi_loss_sum_launch(workspace + w.loss, d->B, M, out, (hipStream_t)stream);
+}
+
+int64_t nsd_multi_infer_scratch_bytes(const nsd_dims *d, int32_t M) {
+    if (multi_check(d, M, "multi_infer_scratch_bytes") != NSD_OK) return NSD_E_INVALID;
+    return 0;                                                    // the fused inference tail keeps nothing outside the chip
+}
+
+int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,
+                    float *logits, float *probs, void *scratch, void *stream) {
+    static const char *who = "multi_infer";
+    (void)scratch;
+    if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
+    if (!params || !x || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+    nsd_ws_layout w;
+    memset(&w, 0, sizeof(w));
+    Lstm2FwdArgs a;
+    build_lstm_fwd(d, params, x, nullptr, 0, nullptr, w, false, nullptr, &a);
+    a.top = nullptr;
+    a.attn_w = params + pl.attn_w; a.attn_b = params + pl.attn_b; a.ln_w = params + pl.ln_w; a.ln_b = params + pl.ln_b;
+    a.fc0_w = params + pl.fc0_w; a.fc0_b = params + pl.fc0_b; a.fc3_w = params + pl.fc3_w; a.fc3_b = params + pl.fc3_b;
+    a.eval_slope = (float)((0.125 + 1.0 / 3.0) / 2.0);
+    a.logits_out = logits; a.probs_out = probs; a.K = d->K; a.F = d->F;
+    ModelSplit s;
+    memset(&s, 0, sizeof(s));
+    s.x_stride = x_model_stride; s.P = pl.total;
+    return nsd_lstm2_multi_fwd_launch(a, s, M, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 //     handles t), so there is exactly ONE workgroup barrier per time step.
 #include <stdlib.h>
 #include "nsd_args.h"
+#include "nsd_multi.h"
 #include "nsd_diag.h"
 
 
@@ -612,4 +613,34 @@ int nsd_lstm2_bwd_launch(const Lstm2BwdArgs &a, int H, hipStream_t st) {
     }
     NSD_CHECK_LAUNCH("lstm2_bwd");
     return NSD_OK;
+}
+
+// ---- model-batched H = 48 launches (nsd_multi.h): the rules above applied to the M*B trials of the launch, the grid partitioned by
+// model (G workgroups per model, M*G <= #CUs).  a.B is the trials of ONE model.
+static int per_model(int groups, int M) { const int cap = nsd_num_cus() / M; return groups < cap ? groups : (cap > 0 ? cap : 1); }
+
+int nsd_lstm2_multi_bwd_groups(int M, int B) {
+    const int nb = pick_nb_bwd(M * B);                 // the single-model rule on the M*B trials: one trial per workgroup up to 2 x #CUs
+    return per_model((B + nb - 1) / nb, M);
+}
+
+int nsd_lstm2_multi_fwd_launch(const Lstm2FwdArgs &a, ModelSplit s, int M, hipStream_t st) {
+    const int total = M * a.B, cus = nsd_num_cus();
+    if (a.B <= 0) return NSD_OK;
+    if (nsd_lstm2_fwd48x4_ok(a) && total >= X4_MIN_B) {
+        Lstm2FwdArgs a4 = a;
+        a4.defer_att = a.head_train;                     // the backward of this batch is the four-trial kernel (nsd_lstm2_multi_bwd_launch)
+        s.G = per_model((a.B + 3) / 4, M);
+        return nsd_lstm2_fwd48x4_multi_launch(a4, s, M, st);
+    }
+    if (total > cus && !a.logits_out) { s.G = per_model((a.B + 1) / 2, M); return nsd_lstm2_fwd48_multi_launch(a, s, M, 2, st); }
+    s.G = per_model(a.B, M);
+    return nsd_lstm2_fwd48_multi_launch(a, s, M, 1, st);
+}
+
+int nsd_lstm2_multi_bwd_launch(const Lstm2BwdArgs &a, ModelSplit s, int M, hipStream_t st) {
+    if (a.B <= 0) return NSD_OK;
+    s.G = nsd_lstm2_multi_bwd_groups(M, a.B);
+    if (nsd_lstm2_bwd48x4_ok(a) && M * a.B >= X4_MIN_B) return nsd_lstm2_bwd48x4_multi_launch(a, s, M, st);
+    return nsd_lstm2_bwd48_multi_launch(a, s, M, pick_nb_bwd(M * a.B), st);
 }

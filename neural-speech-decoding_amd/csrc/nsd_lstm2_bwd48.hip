@@ -24,6 +24,7 @@
 // LDS: da ring [2 layers][8 steps][NB][192] + staged records + (NB = 1) the bf16 operand windows, factor records and the d_in1 ring.
 // HBM traffic = saved activations read once (gates, c, h, in1, x) + one slab of partial gradients per workgroup at the end.
 #include "nsd_args.h"
+#include "nsd_multi.h"
 #include "nsd_prof.h"
 #include "nsd_bf16.h"
 #include <type_traits>
@@ -160,8 +161,8 @@ __device__ __forceinline__ void prep_layer(const Lstm2BwdArgs &a, Smem<1> &sm, c
     prep_finish(sm, in, mn, layer, u, dpu, awu);
 }
 
-template <int NB>
-__device__ __forceinline__ void chain_role(const Lstm2BwdArgs &a, Smem<NB> &sm, const int layer, const int r,
+template <int NB, class A>
+__device__ __forceinline__ void chain_role(const A &a, Smem<NB> &sm, const int layer, const int r,
                                            const int n_steps) {
     // lane -> mat-vec coordinates (output group og, input slice kk) and cell coordinates (unit j, gate s)
     const int og = r >> 4, kk = r & 15;
@@ -175,7 +176,7 @@ __device__ __forceinline__ void chain_role(const Lstm2BwdArgs &a, Smem<NB> &sm, 
     Prof prof = prof_init(a.dbg);
 
     const int ngrp = (B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         float dc[NB], dhrec[NB], ct[NB], dpj[NB];
 #pragma unroll
@@ -252,7 +253,7 @@ __device__ __forceinline__ void chain_role(const Lstm2BwdArgs &a, Smem<NB> &sm, 
             }
         }
     }
-    float *slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
     prof_store(a.dbg, prof);
     if (layer == 0) { slab[a.o_b_ih0 + s * H + j] = db; slab[a.o_b_hh0 + s * H + j] = db; }
     else            { slab[a.o_b_ih1 + s * H + j] = db; slab[a.o_b_hh1 + s * H + j] = db; }
@@ -261,8 +262,8 @@ __device__ __forceinline__ void chain_role(const Lstm2BwdArgs &a, Smem<NB> &sm, 
 // ------------------------------------------------------------------------------------------------
 // x1 waves: d_in1[t] = W_ih1^T da1[t] (+ residual pass-through) for layer 0, and dW_ih0 (K = C <= 8)
 // ------------------------------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void x1_role(const Lstm2BwdArgs &a, Smem<NB> &sm, const int r, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void x1_role(const A &a, Smem<NB> &sm, const int r, const int n_steps) {
     const int og = r >> 4, kk = r & 15;
     const int j = 4 * og + (r & 3), s = (r >> 2) & 3;        // s: which copy of unit j this lane is (dW_ih0 channel pair)
     const int T = a.T, B = a.B, C = a.C;
@@ -276,7 +277,7 @@ __device__ __forceinline__ void x1_role(const Lstm2BwdArgs &a, Smem<NB> &sm, con
     Prof prof = prof_init(a.dbg);
 
     const int ngrp = (B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         float dpj[NB];
 #pragma unroll
@@ -331,7 +332,7 @@ __device__ __forceinline__ void x1_role(const Lstm2BwdArgs &a, Smem<NB> &sm, con
         }
     }
     prof_store(a.dbg, prof);
-    float *slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
     if (NB == 2)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -358,7 +359,8 @@ __device__ __forceinline__ float rows_reduce_scatter4(const f32x4 v) {
     const u32x2v q = __builtin_amdgcn_permlane16_swap(__float_as_uint(s02), __float_as_uint(s13), false, false);
     return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
-__device__ __forceinline__ void x1m_role(const Lstm2BwdArgs &a, Smem<1> &sm, const int g, const int lane, const int n_steps) {
+template <class A>
+__device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int g, const int lane, const int n_steps) {
     const int T = a.T, B = a.B;
     const int ks = lane >> 4, ub = (lane >> 2) & 3, jc = lane & 3;  // MFMA operand coordinates: k slice, unit block, A: unit in block / B: step
     float wv[H];
@@ -370,7 +372,7 @@ __device__ __forceinline__ void x1m_role(const Lstm2BwdArgs &a, Smem<1> &sm, con
     const int pu = lane < H ? lane : lane - 16, pl = g == 0 ? 1 : 0;
     const float p_aw = a.attn_w[pu];
     Prof prof = prof_init(a.dbg);
-    for (int grp = blockIdx.x; grp < B; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < B; grp += wg_count(a)) {
         const int b0 = grp;
         const float dpo = a.residual ? a.dpooled[(size_t)b0 * H + uo] : 0.f;
         float p_dp = 0.f, p_c = 0.f;
@@ -486,8 +488,8 @@ __device__ __forceinline__ void dw_compute(const Lstm2BwdArgs &a, Smem<NB> &sm, 
     }
 }
 
-template <int NB>
-__device__ __forceinline__ void dw_role(const Lstm2BwdArgs &a, Smem<NB> &sm, const int dwid, const int lane,
+template <int NB, class A>
+__device__ __forceinline__ void dw_role(const A &a, Smem<NB> &sm, const int dwid, const int lane,
                                         const int n_groups) {
     DwState<NB> st;
     Prof prof = prof_init(a.dbg);
@@ -513,7 +515,7 @@ __device__ __forceinline__ void dw_role(const Lstm2BwdArgs &a, Smem<NB> &sm, con
         }
     };
     const int ngrp = (a.B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         if (a.rng.on) gen_mask(0, b0);
         step_barrier<false>(prof);      // pairs with the stage-initialisation barrier of the other roles
@@ -541,7 +543,7 @@ __device__ __forceinline__ void dw_role(const Lstm2BwdArgs &a, Smem<NB> &sm, con
     }
     prof_store(a.dbg, prof);
     // accumulator tile -> slab: lane holds rows 4*(lane>>4)+r, column lane&15 of each 16x16 tile
-    float *slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
     const long base[3] = {a.o_w_hh1, a.o_w_ih1, a.o_w_hh0};
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -604,9 +606,10 @@ __device__ __forceinline__ void split4_bf16(const f32x4 v, u32x2 &hi, u32x2 &lo)
 // Duties beside the wave's five tiles (instruction count matters more than anything else in this kernel: every role shares its SIMD
 // with a recurrence): waves 0..2 the rows h1[t-1] / in1[t] / h0[t-1] and wave 3 x[t], FOUR steps per request (lane = (step, 16-byte
 // piece) or (step, channel)), split and written every fourth step; waves 4, 5 the da of layer 1 / 0, every step, four columns per lane.
-__device__ DW16_INLINE void dw16_role(const Lstm2BwdArgs &a_in, Smem<1> &sm, const int w_in, const int lane, const int n_steps_in) {
+template <class A>
+__device__ DW16_INLINE void dw16_role(const A &a_in, Smem<1> &sm, const int w_in, const int lane, const int n_steps_in) {
     const int w = __builtin_amdgcn_readfirstlane(w_in), n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
-    const Lstm2BwdArgs a = uniform_copy(a_in);
+    const A a = uniform_copy(a_in);
     DwWin &win = sm.win;
     const int T = a.T, B = a.B, C = a.C;
     Prof prof = prof_init(a.dbg);
@@ -658,7 +661,7 @@ __device__ DW16_INLINE void dw16_role(const Lstm2BwdArgs &a_in, Smem<1> &sm, con
         for (int e = w * 64 + lane; e < NZ; e += 6 * 64) z[e] = zero;
     }
     const int ngrp = B;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b = grp;
         if (a.rng.on) gen_mask(0, b);
         // rows of macro steps m .. m + 3 (this lane: m + rs); out of range -> zeros (switched off at the ADDRESS)
@@ -738,7 +741,7 @@ __device__ DW16_INLINE void dw16_role(const Lstm2BwdArgs &a_in, Smem<1> &sm, con
     }
     prof_store(a.dbg, prof);
     // accumulator tile -> slab: register r of lane l = dW[row 32 w + mfma32_row(r, l)][window column 32 ni + (l & 31)]
-    float *slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
         const int layer = q < 3 ? 1 : 0, c = 32 * (q < 3 ? q : q - 3) + (lane & 31);
@@ -833,15 +836,15 @@ __device__ __forceinline__ void loader_issue_x(const Lstm2BwdArgs &a, Smem<NB> &
     }
 }
 
-template <int NB>
-__device__ __forceinline__ void loader_role(const Lstm2BwdArgs &a, Smem<NB> &sm, const int lane, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void loader_role(const A &a, Smem<NB> &sm, const int lane, const int n_steps) {
     LdDesc d[NQ];
     loader_decode<NB>(a, lane, d);
     Prof prof = prof_init(a.dbg);
     const int ngrp = (a.B + NB - 1) / NB;
     const int T = a.T;
     const int u = lane < H ? lane : lane - 16;                      // prep of a trial's first step: this lane's unit (lanes 48..63 repeat units 32..47)
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         float dpu = 0.f, awu = 0.f, cT1[2] = {0.f, 0.f};
         if constexpr (NB == 1) {                                    // (ordinary loads only in front of the trial's first DMA)
@@ -898,6 +901,7 @@ __device__ __forceinline__ void loader_role(const Lstm2BwdArgs &a, Smem<NB> &sm,
     prof_store(a.dbg, prof);
 }
 
+#if !NSD_MULTI_TU
 template <int NB>
 __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_kernel(Lstm2BwdArgs a) {
     __shared__ __align__(16) Smem<NB> sm;
@@ -949,8 +953,59 @@ __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_kernel(Lstm2BwdArgs a) {
     else                { __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, tid & 63, n_steps); }
 }
 
+#else
+// M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_bwd48.hip, so that the single-model kernels' module is what it was):
+// workgroup blockIdx.x takes model blockIdx.x / s.G; the roles and their placement are those of lstm2_bwd48_kernel, each forming the
+// model's argument block itself (only the pointers it reads are live in it).
+template <int NB>
+__global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_multi_kernel(Lstm2BwdArgs a_in, ModelSplit s) {
+    __shared__ __align__(16) Smem<NB> sm;
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n_groups = (((a_in.T + 2 + dl0(NB)) / 4 + 1) + 1) & ~1;
+    const int n_steps = 4 * n_groups;
+#define NSD_VIEW const ModelView<Lstm2BwdArgs> a = model_view(a_in, s)
+#ifndef NSD_B48_MAP                              // (the defaults of lstm2_bwd48_kernel, which this translation unit does not compile)
+#define NSD_B48_MAP 2
+#endif
+#ifndef NSD_B48_PC
+#define NSD_B48_PC 2
+#endif
+#ifndef NSD_B48_PX
+#define NSD_B48_PX 3
+#endif
+    if constexpr (NB == 1) {
+        const int lane = tid & 63;
+        if (NSD_B48_MAP >= 1) {
+#if NSD_B48_MAP == 2
+            constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3, 3, 3, 4};
+            constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 4, 2, 3, 0, 1, 5, 0};
+#else
+            constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 2, 3, 3, 3, 3, 4};
+            constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 0, 1, 2, 4, 2, 3, 5, 0};
+#endif
+            const int role = ROLE[wave], part = PART[wave];
+            if (role == 0)      { NSD_VIEW; __builtin_amdgcn_s_setprio(NSD_B48_PC); chain_role<NB>(a, sm, 1, 64 * part + lane, n_steps); }
+            else if (role == 1) { NSD_VIEW; __builtin_amdgcn_s_setprio(NSD_B48_PC); chain_role<NB>(a, sm, 0, 64 * part + lane, n_steps); }
+            else if (role == 2) { NSD_VIEW; __builtin_amdgcn_s_setprio(NSD_B48_PX); if (NSD_B48_X1M) x1m_role(a, sm, part, lane, n_steps); else x1_role<NB>(a, sm, 64 * part + lane, n_steps); }
+            else if (role == 3) { NSD_VIEW; dw16_role(a, sm, part, lane, n_steps); }
+            else                { NSD_VIEW; __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, lane, n_steps); }
+            return;
+        }
+    }
+    if (wave < 3)       { NSD_VIEW; __builtin_amdgcn_s_setprio(3); chain_role<NB>(a, sm, 1, tid, n_steps); }
+    else if (wave < 6)  { NSD_VIEW; __builtin_amdgcn_s_setprio(3); chain_role<NB>(a, sm, 0, tid - 192, n_steps); }
+    else if (wave < 9)  { NSD_VIEW; __builtin_amdgcn_s_setprio(2); x1_role<NB>(a, sm, tid - 384, n_steps); }
+    else if (wave < 15) { NSD_VIEW; if constexpr (NB == 1) dw16_role(a, sm, wave - 9, tid & 63, n_steps); else dw_role<NB>(a, sm, wave - 9, tid & 63, n_groups); }
+    else                { NSD_VIEW; __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, tid & 63, n_steps); }
+#undef NSD_VIEW
+}
+
+#endif
+
 }  // namespace
 
+#if !NSD_MULTI_TU
 int nsd_lstm2_bwd48_launch(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t st) {
     // the one-trial instantiation's dW waves address the saved rows through buffer descriptors with 32-bit offsets (0x80000000 = "switched
     // off"): a batch whose [B][T][H] arrays reach 2 GB takes the two-trial instantiation (64-bit addresses; any grid)
@@ -964,3 +1019,17 @@ int nsd_lstm2_bwd48_launch(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t 
     NSD_CHECK_LAUNCH("lstm2_bwd48");
     return NSD_OK;
 }
+
+#else
+int nsd_lstm2_bwd48_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st) {
+    if (nb == 1 && (long)a.B * a.T * H * 4 >= 0x7fffffffL) nb = 2;        // (as nsd_lstm2_bwd48_launch: 32-bit offsets of the one-trial dW waves)
+    if (a.da0_out) { nsd_set_error("lstm2_bwd48 (models): no input gradient on the model-batched path"); return NSD_E_INVALID; }
+    switch (nb) {
+    case 1: hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<1>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s); break;
+    case 2: hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<2>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s); break;
+    default: nsd_set_error("lstm2_bwd48 (models): NB=%d not built (register / LDS budget)", nb); return NSD_E_INVALID;
+    }
+    NSD_CHECK_LAUNCH("lstm2_bwd48_multi");
+    return NSD_OK;
+}
+#endif

@@ -34,6 +34,7 @@
 //   scalar -- no staging through LDS.
 // HBM traffic = saved activations read once + one slab of partial gradients per workgroup at the end.
 #include "nsd_args.h"
+#include "nsd_multi.h"
 #include "nsd_prof.h"
 #include "nsd_bf16.h"
 
@@ -212,11 +213,11 @@ __device__ __forceinline__ float transposed_product(const float (&wv)[H], const 
 // ------------------------------------------------------------------------------------------------
 // (every role is a real function call with its own register allocation -- inlined into one body, hipcc spilled the dW accumulators
 // inside the step loop -- and works on a LOCAL copy of the argument block: the step barrier is an asm statement with a memory clobber)
-template <int LAYER>
-__device__ __attribute__((noinline)) void chain_role(const Lstm2BwdArgs &a_in, const int g_in, const int lane, const int n_steps_in) {
+template <int LAYER, class A>
+__device__ __attribute__((noinline)) void chain_role(const A &a_in, const int g_in, const int lane, const int n_steps_in) {
     BSmem &sm = g_bsm;
     const int g = __builtin_amdgcn_readfirstlane(g_in), n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);    // (arguments arrive in VGPRs: uniform_copy's comment)
-    const Lstm2BwdArgs a = uniform_copy(a_in);
+    const A a = uniform_copy(a_in);
     const int r = lane >> 4, ub = (lane >> 2) & 3, j = lane & 3;
     const int u = 16 * g + 4 * ub + r;                              // this lane's cell after the reduce-scatter
     const int T = a.T, B = a.B;
@@ -229,7 +230,7 @@ __device__ __attribute__((noinline)) void chain_role(const Lstm2BwdArgs &a_in, c
     float db[4] = {0.f, 0.f, 0.f, 0.f};
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NTR - 1) / NTR;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b = grp * NTR + j;
         const bool vb = b < B;
         const unsigned vo4 = vb ? (unsigned)(((size_t)b * T * H + u) * 4) : VOFF_DROP;
@@ -317,7 +318,7 @@ __device__ __attribute__((noinline)) void chain_role(const Lstm2BwdArgs &a_in, c
     }
     prof_store(a.dbg, prof);
     // bias gradients: sum over the four trials of the quad, lane j == 0 writes (b_ih and b_hh get the same sum)
-    float *slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float s = quad_sum(db[q]);
@@ -331,10 +332,11 @@ __device__ __attribute__((noinline)) void chain_role(const Lstm2BwdArgs &a_in, c
 // ------------------------------------------------------------------------------------------------
 // X1: d_in1[t] = W_ih1^T da1[t], t = T - m (da1 written at macro step m - 1) -> LDS for the layer-0 recurrence of macro step m + 1
 // ------------------------------------------------------------------------------------------------
-__device__ __attribute__((noinline)) void x1_role(const Lstm2BwdArgs &a_in, const int g_in, const int lane, const int n_steps_in) {
+template <class A>
+__device__ __attribute__((noinline)) void x1_role(const A &a_in, const int g_in, const int lane, const int n_steps_in) {
     BSmem &sm = g_bsm;
     const int g = __builtin_amdgcn_readfirstlane(g_in), n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
-    const Lstm2BwdArgs a = uniform_copy(a_in);
+    const A a = uniform_copy(a_in);
     const int r = lane >> 4, ub = (lane >> 2) & 3, j = lane & 3;
     const int u = 16 * g + 4 * ub + r;
     const int T = a.T, B = a.B;
@@ -342,7 +344,7 @@ __device__ __attribute__((noinline)) void x1_role(const Lstm2BwdArgs &a_in, cons
     load_wT(a.w_ih1, g, lane, wv);
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NTR - 1) / NTR;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
 #pragma unroll
         for (int s4 = 0; s4 < H; s4 += 8)
             asm volatile("" : "+v"(wv[s4]), "+v"(wv[s4 + 1]), "+v"(wv[s4 + 2]), "+v"(wv[s4 + 3]), "+v"(wv[s4 + 4]), "+v"(wv[s4 + 5]), "+v"(wv[s4 + 6]), "+v"(wv[s4 + 7]));
@@ -366,10 +368,11 @@ __device__ __attribute__((noinline)) void x1_role(const Lstm2BwdArgs &a_in, cons
 // 48..63), split into bf16 halves and written into the row windows at the k row of (step, trial): what the cell lanes do for da.
 // Rows of inactive steps, of t - 1 < 0 and of padding trials read as zeros (switched off at the ADDRESS).
 // ------------------------------------------------------------------------------------------------
-__device__ __attribute__((noinline)) void rows_role(const Lstm2BwdArgs &a_in, const int lane, const int n_steps_in) {
+template <class A>
+__device__ __attribute__((noinline)) void rows_role(const A &a_in, const int lane, const int n_steps_in) {
     BSmem &sm = g_bsm;
     const int n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
-    const Lstm2BwdArgs a = uniform_copy(a_in);
+    const A a = uniform_copy(a_in);
     const int T = a.T, B = a.B;
     const long bth4 = (long)B * T * H * 4;
     const rsrc_t r_h1 = make_rsrc(a.hseq1, bth4), r_in1 = make_rsrc(a.in1seq, bth4), r_h0 = make_rsrc(a.hseq0, bth4);
@@ -379,7 +382,7 @@ __device__ __attribute__((noinline)) void rows_role(const Lstm2BwdArgs &a_in, co
     const int col0 = hb ? 4 * c4 : 48 + 4 * c4;                     // third piece: layer-0 window column (h0 | x)
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NTR - 1) / NTR;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b = grp * NTR + j;
         const unsigned vo = (hb && b < B) ? (unsigned)(((size_t)b * T * H + 4 * c4) * 4) : VOFF_DROP;
         auto prefetch = [&](const int m, f32x4 (&bv)[3]) {
@@ -436,12 +439,12 @@ __device__ __attribute__((noinline)) void rows_role(const Lstm2BwdArgs &a_in, co
 // overwritten from step 4w + 8 on: its products are spread over steps 4w + 4 .. 4w + 7, one column tile per step (three MFMAs per tile:
 // hi.hi, lo.hi, hi.lo); the last window of a trial group is taken behind the loop.
 // ------------------------------------------------------------------------------------------------
-template <int LAYER>
-__device__ __attribute__((noinline)) void dw_role(const Lstm2BwdArgs &a_in, const int d_in, const int lane, const int n_steps_in) {
+template <int LAYER, class A>
+__device__ __attribute__((noinline)) void dw_role(const A &a_in, const int d_in, const int lane, const int n_steps_in) {
     BSmem &sm = g_bsm;
     constexpr int NM = LAYER == 1 ? 2 : 3, NN = LAYER == 1 ? 3 : 2;   // row / column tiles of this wave
     const int d = __builtin_amdgcn_readfirstlane(d_in), n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
-    const Lstm2BwdArgs a = uniform_copy(a_in);
+    const A a = uniform_copy(a_in);
     const int B = a.B;
     const int row0 = 32 * NM * d;                                   // first k' of this wave
     f32x16 acc[NM][NN];
@@ -466,7 +469,7 @@ __device__ __attribute__((noinline)) void dw_role(const Lstm2BwdArgs &a_in, cons
     };
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NTR - 1) / NTR;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         xstep_barrier(prof);
         for (int m0 = 0; m0 < n_steps; m0 += 4) {
             const int w = ((m0 >> 2) + 1) & 1;                      // the window completed at macro step m0 - 1
@@ -484,7 +487,7 @@ __device__ __attribute__((noinline)) void dw_role(const Lstm2BwdArgs &a_in, cons
     }
     prof_store(a.dbg, prof);
     // accumulator tile -> slab: register r of lane l = dW[k' = row0 + 32 mi + mfma32_row(r, l)][column 32 ni + (l & 31) of the window]
-    float *slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
 #pragma unroll
     for (int mi = 0; mi < NM; ++mi)
 #pragma unroll
@@ -511,14 +514,15 @@ __device__ __attribute__((noinline)) void dw_role(const Lstm2BwdArgs &a_in, cons
 // which hold h1_t = o_t tanh(c_t) of their cell.
 // ------------------------------------------------------------------------------------------------
 typedef const __attribute__((address_space(1))) f32x4 *gf32x4_p;
-__device__ __attribute__((noinline)) void aux_role(const Lstm2BwdArgs &a_in, const int lane_in, const int n_steps_in) {
+template <class A>
+__device__ __attribute__((noinline)) void aux_role(const A &a_in, const int lane_in, const int n_steps_in) {
     BSmem &sm = g_bsm;
     // `lane` is made opaque once per chunk (an empty asm): what the request lambdas derive from it -- 28 + 12 per-lane addresses -- is then
     // recomputed per chunk (a few hundred integer instructions per 16 steps) instead of being hoisted out of the chunk loop into registers
     // this wave does not have: spilled, every request of a chunk waited for a scratch reload first (measured: +85 us per launch)
     int lane = lane_in;
     const int n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
-    const Lstm2BwdArgs a = uniform_copy(a_in);
+    const A a = uniform_copy(a_in);
     const int T = a.T, B = a.B;
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NTR - 1) / NTR;
@@ -581,7 +585,7 @@ __device__ __attribute__((noinline)) void aux_role(const Lstm2BwdArgs &a_in, con
         const f32x4 p = *reinterpret_cast<const f32x4 *>(&sm.dpv[an][4 * q]);
         d0 = fmaf(r[0], p[0], d0); d1 = fmaf(r[1], p[1], d1); d0 = fmaf(r[2], p[2], d0); d1 = fmaf(r[3], p[3], d1);
     };
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NTR;
         // Start of a group: the first records, the rows they may need, dL/dpooled and pooled are requested AT ONCE (one round trip to
         // memory in front of the group's first barrier, not three in a row; the addresses are valid whatever the records turn out to be)
@@ -694,6 +698,29 @@ __device__ __attribute__((noinline)) void aux_role(const Lstm2BwdArgs &a_in, con
     prof_store(a.dbg, prof);
 }
 
+#if NSD_MULTI_TU
+// M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_bwd48x4.hip, so that the single-model kernel's module is what it was):
+// workgroup blockIdx.x takes model blockIdx.x / s.G (the roles walk its trial groups wg, wg + G, ... and write slab blockIdx.x).  The roles
+// and their placement (NSD_BX4_MAP 0) are those of lstm2_bwd48x4_kernel; they are called (noinline) and read the model's argument block
+// from LDS: a reference to a local would put it in scratch.
+__global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_multi_kernel(Lstm2BwdArgs a_in, ModelSplit s) {
+    __shared__ ModelView<Lstm2BwdArgs> a;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) a = model_view(a_in, s);
+    __syncthreads();
+    const int n_steps = ((a_in.T + 3 + XCH - 1) / XCH) * XCH;
+    const int g = wave & 3, q = wave >> 2;
+    constexpr int PC = 3, PX = 2, PD = 0;
+    if (g < 3 && q == 0)      { __builtin_amdgcn_s_setprio(PC); chain_role<1>(a, g, lane, n_steps); }
+    else if (g < 3 && q == 1) { __builtin_amdgcn_s_setprio(PC); chain_role<0>(a, g, lane, n_steps); }
+    else if (g < 3 && q == 2) { __builtin_amdgcn_s_setprio(PD); dw_role<1>(a, g, lane, n_steps); }
+    else if (g < 2)           { __builtin_amdgcn_s_setprio(PD); dw_role<0>(a, g, lane, n_steps); }
+    else if (g == 2)          { __builtin_amdgcn_s_setprio(PD); rows_role(a, lane, n_steps); }
+    else if (q < 3)           { __builtin_amdgcn_s_setprio(PX); x1_role(a, q, lane, n_steps); }
+    else                      aux_role(a, lane, n_steps);
+}
+#else
 __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_kernel(Lstm2BwdArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -740,8 +767,19 @@ __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_kernel(Lstm2BwdArgs a) {
     // a workgroup without a trial group (grid = the workspace's slab count) has written a zero slab: every role's sums are zero
 }
 
+#endif
+
 }  // namespace
 
+#if NSD_MULTI_TU
+bool nsd_lstm2_bwd48x4_ok(const Lstm2BwdArgs &a);
+int nsd_lstm2_bwd48x4_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, hipStream_t st) {
+    if (!nsd_lstm2_bwd48x4_ok(a)) { nsd_set_error("lstm2_bwd48x4 (models): launch outside the kernel's domain"); return NSD_E_INVALID; }
+    hipLaunchKernelGGL(lstm2_bwd48x4_multi_kernel, dim3(M * s.G), dim3(NTHR), 0, st, a, s);
+    NSD_CHECK_LAUNCH("lstm2_bwd48x4_multi");
+    return NSD_OK;
+}
+#else
 bool nsd_lstm2_bwd48x4_ok(const Lstm2BwdArgs &a) {
     return !a.residual && a.C <= 8 && (long)a.B * a.T * H * 16 < 0x7fffffffL && a.dsc_pack != nullptr;
 }
@@ -752,3 +790,4 @@ int nsd_lstm2_bwd48x4_launch(const Lstm2BwdArgs &a, int grid, hipStream_t st) {
     NSD_CHECK_LAUNCH("lstm2_bwd48x4");
     return NSD_OK;
 }
+#endif

@@ -24,6 +24,7 @@
 // LDS, DPP quad reduction, lane s of the quad evaluates gate s.  x and the dropout multipliers are staged through
 // LDS in 32-step chunks, prefetched one chunk ahead.
 #include "nsd_args.h"
+#include "nsd_multi.h"
 #include "nsd_prof.h"
 
 namespace {
@@ -150,8 +151,8 @@ __device__ __forceinline__ float4 chunk_mask_at(const Lstm2FwdArgs &a, const int
 // ------------------------------------------------------------------------------------------------
 // layer 0
 // ------------------------------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void l0_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int r, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void l0_role(const A &a, FSmem<NB> &sm, const int r, const int n_steps) {
     const int j = r >> 2, s = r & 3;
     const int T = a.T, B = a.B, C = a.C;
     f32x2 wx[4], wh[4][6];
@@ -175,7 +176,7 @@ __device__ __forceinline__ void l0_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, co
 
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         float c[NB];
 #pragma unroll
@@ -252,8 +253,8 @@ __device__ __forceinline__ void l0_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, co
 // ------------------------------------------------------------------------------------------------
 // layer-1 input projection, one step behind layer 0
 // ------------------------------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void p_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int r, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void p_role(const A &a, FSmem<NB> &sm, const int r, const int n_steps) {
     const int j = r >> 2, s = r & 3;
     const int T = a.T;
     f32x2 wi[4][6];
@@ -266,7 +267,7 @@ __device__ __forceinline__ void p_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, con
         }
     Prof prof = prof_init(a.dbg);
     const int ngrp = (a.B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         step_barrier<false>(prof);
         for (int m0 = 0; m0 < n_steps; m0 += SRING) {
 #pragma unroll
@@ -299,8 +300,8 @@ __device__ __forceinline__ void p_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, con
 // ------------------------------------------------------------------------------------------------
 // layer 1, two steps behind layer 0
 // ------------------------------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void l1_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int r, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void l1_role(const A &a, FSmem<NB> &sm, const int r, const int n_steps) {
     const int j = r >> 2, s = r & 3;
     const int T = a.T, B = a.B;
     f32x2 wh[4][6];
@@ -315,7 +316,7 @@ __device__ __forceinline__ void l1_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, co
     const int hslot = (s == 1) ? 0 : s;
     Prof prof = prof_init(a.dbg);
     const int ngrp = (B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         float c[NB];
 #pragma unroll
         for (int n = 0; n < NB; ++n) c[n] = 0.f;
@@ -382,8 +383,8 @@ struct SvDesc {
     unsigned meta;       // bits 0..15 float offset inside sv[0][0] (ring slot 0, trial 0) | bits 16..23 (t0 + 2) | bit 24 row = 4H floats (else H)
 };
 
-template <int NB>
-__device__ __forceinline__ void saver_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int lane, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void saver_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     const int T = a.T;
     SvDesc d[SPIECES];
     float *const sv_base = a.hseq0;                            // (training launches always carry the whole workspace)
@@ -436,7 +437,7 @@ __device__ __forceinline__ void saver_role(const Lstm2FwdArgs &a, FSmem<NB> &sm,
         }
     };
     const int ngrp = (a.B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         step_barrier<false>(prof);
         for (int m0 = 0; m0 < n_steps; m0 += SCH) {
@@ -569,15 +570,15 @@ __device__ __forceinline__ void pool_loop(PoolRun (&p)[NB], FSmem<NB> &sm, const
 // one 8-step chunk behind the chain (running max m, denominator, weighted sum in lane j); the [T,H] sequence is
 // never written to HBM, so the kernel's traffic is the algorithmic 8 000 B in + K*4 B out per trial.
 // ------------------------------------------------------------------------------------------------
-template <int NB>
-__device__ __forceinline__ void pool_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int lane, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void pool_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     static_assert(NB == 1, "inference tail is built for one trial per workgroup");
     const int T = a.T, K = a.K, F = a.F;
     PoolRun pr[NB];
     pool_init<NB>(pr[0], a, lane);
     Prof prof = prof_init(a.dbg);
     const int ngrp = (a.B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b = grp;
         pool_reset(pr[0]);
         step_barrier<false>(prof);
@@ -720,8 +721,8 @@ __device__ __forceinline__ void tail_all(const Lstm2FwdArgs &a, FSmem<NB> &sm, c
     }
 }
 
-template <int NB>
-__device__ __forceinline__ void tpool_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int lane, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void tpool_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     const int T = a.T, K = a.K, F = a.F;
     PoolRun pr[NB];
     pool_init<NB>(pr[0], a, lane);
@@ -733,7 +734,7 @@ __device__ __forceinline__ void tpool_role(const Lstm2FwdArgs &a, FSmem<NB> &sm,
     const float b0v = lane < F ? a.fc0_b[lane] : 0.f, b3v = lane < K ? a.fc3_b[lane] : 0.f;
     Prof prof = prof_init(a.dbg);
     const int ngrp = (a.B + NB - 1) / NB;
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         // per-trial scalars, fetched while the recurrence runs
         float sl_fv[NB], mk_fv[NB];
@@ -838,14 +839,14 @@ __device__ __forceinline__ void tpool_role(const Lstm2FwdArgs &a, FSmem<NB> &sm,
 // generates the inter-layer dropout multipliers (one row of 48 per step, a whole x chunk ahead of the layer-0 waves that
 // read them from sm.ms; chunk 0 is written by the layer-0 waves themselves).  Same values as nsd_train_masks: the
 // stream index of (b, t, j) is (b*T + t)*48 + j, advanced by additions only.
-template <int NB>
-__device__ __forceinline__ void spare_role(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int lane, const int n_steps) {
+template <int NB, class A>
+__device__ __forceinline__ void spare_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     Prof prof = prof_init(a.dbg);
     const int T = a.T;
     const int ngrp = (a.B + NB - 1) / NB;
     constexpr int XPL = NB * XCH * 8 / 64;                        // x floats per lane and chunk (4 per trial)
     constexpr int MPL = NB * 384 / 64;                            // explicit-multiplier float4 per lane and chunk (6 per trial)
-    for (int grp = blockIdx.x; grp < ngrp; grp += gridDim.x) {
+    for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b0 = grp * NB;
         uint64_t idx[NB];
 #pragma unroll
@@ -890,6 +891,7 @@ __device__ __forceinline__ void spare_role(const Lstm2FwdArgs &a, FSmem<NB> &sm,
     }
 }
 
+#if !NSD_MULTI_TU
 template <int NB>
 __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
     __shared__ __align__(16) FSmem<NB> sm;
@@ -929,8 +931,40 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
     else spare_role<NB>(a, sm, lane, n_steps);
 }
 
+#else
+// M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_fwd48.hip, so that the single-model kernels' module is what it was):
+// workgroup blockIdx.x runs model blockIdx.x / s.G; the roles and their placement are those of lstm2_fwd48_kernel
+template <int NB>
+__global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in, ModelSplit s) {
+    __shared__ __align__(16) FSmem<NB> sm;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n_steps = ((a_in.T + 2 + XCH - 1) / XCH) * XCH;
+    const int g = wave & 3, q = wave >> 2;
+    // (each role forms the view itself: only the pointers it reads are live in it)
+#define NSD_VIEW const ModelView<Lstm2FwdArgs> a = model_view(a_in, s)
+    if (g == 3)      { NSD_VIEW; __builtin_amdgcn_s_setprio(1); p_role<NB>(a, sm, q * 64 + lane, n_steps); }
+    else if (q == 0) { NSD_VIEW; __builtin_amdgcn_s_setprio(3); l1_role<NB>(a, sm, g * 64 + lane, n_steps); }
+    else if (q == 1) { NSD_VIEW; __builtin_amdgcn_s_setprio(2); l0_role<NB>(a, sm, g * 64 + lane, n_steps); }
+    else if (g == 0) {
+        NSD_VIEW;
+        if constexpr (NB == 1) {
+            if (a.logits_out) pool_role<NB>(a, sm, lane, n_steps);
+            else              saver_role<NB>(a, sm, lane, n_steps);
+        } else {
+            saver_role<NB>(a, sm, lane, n_steps);
+        }
+    }
+    else if (g == 1 && a_in.head_train) { NSD_VIEW; tpool_role<NB>(a, sm, lane, n_steps); }
+    else { NSD_VIEW; spare_role<NB>(a, sm, lane, n_steps); }
+#undef NSD_VIEW
+}
+
+#endif
+
 }  // namespace
 
+#if !NSD_MULTI_TU
 int nsd_lstm2_fwd48_launch(const Lstm2FwdArgs &a, int nb, int grid, hipStream_t st) {
     // one trial per workgroup (latency: batches up to one trial per CU, and inference), or two trials per workgroup advancing in
     // lock step (throughput: larger training batches -- two independent dependent chains per wave fill each other's issue gaps)
@@ -949,3 +983,18 @@ int nsd_lstm2_fwd48_launch(const Lstm2FwdArgs &a, int nb, int grid, hipStream_t 
 }
 
 bool nsd_lstm2_fwd48_head_train_fits(int T, int F, int K) { return T <= TT_TMAX && F <= 64 && K <= TT_KMAX && F >= 1 && K >= 1; }
+
+#else
+int nsd_lstm2_fwd48_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st) {
+    if (nb != 1 && nb != 2) { nsd_set_error("lstm2_fwd48 (models): NB=%d not built", nb); return NSD_E_INVALID; }
+    if (nb == 2 && a.logits_out) { nsd_set_error("lstm2_fwd48 (models): the inference tail runs one trial per workgroup"); return NSD_E_INVALID; }
+    if (a.head_train && (!nsd_lstm2_fwd48_head_train_fits(a.T, a.F, a.K) || !(a.top || a.hseq1) || a.logits_out)) {
+        nsd_set_error("lstm2_fwd48 (models): fused train head needs T<=%d, F<=64, K<=%d and the training workspace", TT_TMAX, TT_KMAX);
+        return NSD_E_INVALID;
+    }
+    if (nb == 2) hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<2>), dim3(M * s.G), dim3(NT), 0, st, a, s);
+    else         hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<1>), dim3(M * s.G), dim3(NT), 0, st, a, s);
+    NSD_CHECK_LAUNCH("lstm2_fwd48_multi");
+    return NSD_OK;
+}
+#endif

@@ -29,6 +29,7 @@
 //   MFMAs of the NEXT step (no saver wave, no LDS ring: see "Pending").
 // After the last step: the tail of nsd_lstm2_fwd48.hip's fused train head (alpha, dL/dscore, d attn.weight), one trial at a time.
 #include "nsd_args.h"
+#include "nsd_multi.h"
 #include "nsd_prof.h"
 
 namespace {
@@ -802,6 +803,34 @@ __device__ __forceinline__ void idle_role(const Lstm2FwdArgs &a, XSmem &sm, cons
     }
 }
 
+#if NSD_MULTI_TU
+// M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_fwd48x4.hip, so that the single-model kernel's module is what it was):
+// workgroup blockIdx.x takes model blockIdx.x / s.G, its trial groups wg, wg + G, ...  The roles are those of lstm2_fwd48x4_kernel; the
+// called (noinline) ones read the model's argument block from LDS -- a reference to a local would put it in scratch -- and the inlined
+// ones form it themselves, so that only the pointers they read are live in them.
+__global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_multi_kernel(Lstm2FwdArgs a_in, ModelSplit s) {
+    XSmem &sm = g_sm;
+    __shared__ Lstm2FwdArgs view;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) view = model_view(a_in, s);
+    __syncthreads();
+    const int n_steps = ((a_in.T + 2 + XCH - 1) / XCH) * XCH;
+    const int g = wave & 3, q = wave >> 2;
+    const int ngrp = (a_in.B + NTR - 1) / NTR;
+    const int wg = (int)blockIdx.x - (int)(blockIdx.x / s.G) * s.G;
+    for (int grp = wg; grp < ngrp; grp += s.G) {
+        if (g == 3)      { __builtin_amdgcn_s_setprio(1); p_role(model_view(a_in, s), sm, q, lane, n_steps, grp); }
+        else if (q == 0) { __builtin_amdgcn_s_setprio(3); l1_role(model_view(a_in, s), sm, g, lane, n_steps, grp); }
+        else if (q == 1) { __builtin_amdgcn_s_setprio(2); l0_role(model_view(a_in, s), sm, g, lane, n_steps, grp); }
+        else if (g == 0) { __builtin_amdgcn_s_setprio(0); stage_role(view, lane, n_steps, grp); }
+        else if (a_in.head_train) { __builtin_amdgcn_s_setprio(0); pool_role(view, g - 1, lane, n_steps, grp); }
+        else idle_role(a_in, sm, n_steps, grp);
+        __builtin_amdgcn_s_setprio(0);
+        if (a_in.head_train) tail_all(view, tid, grp * NTR);
+    }
+}
+#else
 __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_kernel(Lstm2FwdArgs a) {
     XSmem &sm = g_sm;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -833,8 +862,19 @@ __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_kernel(Lstm2FwdArgs a) {
     }
 }
 
+#endif
+
 }  // namespace
 
+#if NSD_MULTI_TU
+bool nsd_lstm2_fwd48x4_ok(const Lstm2FwdArgs &a);
+int nsd_lstm2_fwd48x4_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int M, hipStream_t st) {
+    if (!nsd_lstm2_fwd48x4_ok(a)) { nsd_set_error("lstm2_fwd48x4 (models): launch outside the kernel's domain"); return NSD_E_INVALID; }
+    hipLaunchKernelGGL(lstm2_fwd48x4_multi_kernel, dim3(M * s.G), dim3(NTHR), 0, st, a, s);
+    NSD_CHECK_LAUNCH("lstm2_fwd48x4_multi");
+    return NSD_OK;
+}
+#else
 bool nsd_lstm2_fwd48x4_ok(const Lstm2FwdArgs &a) {
     // training launches of the plain two-layer stack; offsets of the saved activations are 32-bit byte offsets
     // (the saved arrays are addressed with 32-bit byte offsets)
@@ -849,3 +889,4 @@ int nsd_lstm2_fwd48x4_launch(const Lstm2FwdArgs &a, int grid, hipStream_t st) {
     NSD_CHECK_LAUNCH("lstm2_fwd48x4");
     return NSD_OK;
 }
+#endif

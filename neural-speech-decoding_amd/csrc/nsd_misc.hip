@@ -1,6 +1,7 @@
 // nsd_misc.hip -- small memory-bound kernels around the LSTM path: per-channel z-score, slab reduction,
 // Adam, counter-based dropout / RReLU-noise streams, loss sum.
 #include "nsd_args.h"
+#include "nsd_multi.h"
 
 // ---------------------------------------------------------------------------------------------
 // z-score: y = (x - mean_T) / (std_T(ddof=0) + 1e-6) per trial and channel.
@@ -66,10 +67,17 @@ int nsd_zscore_launch(const float *x, float *y, int B, int T, int C, hipStream_t
 // optional optimizer tail of the reduction (single-rank training: no all-reduce sits between the two)
 struct AdamTail { float *p, *m, *v; float lr_over_bc1, rsqrt_bc2, beta1, beta2, eps, wd, gscale; };
 
-template <bool ADAM>
+// MODELS (nsd_multi_grad_reduce*): blockIdx.y = model m sums its n_slabs slabs (behind those of models 0 .. m-1) and n_hslabs head slabs
+// into grads + m * (p_lstm + ph), and updates p / m / v there -- the arithmetic of one model's reduction, all models in one launch
+template <bool ADAM, bool MODELS = false>
 __global__ __launch_bounds__(GR_COLS * GR_GROUPS) void grad_reduce_kernel(
         const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs, long ph, int n_hslabs,
         float *grads, int accumulate, AdamTail ad) {
+    if constexpr (MODELS) {
+        const long mo = blockIdx.y;
+        slabs += mo * n_slabs * slab_stride; hslabs += mo * n_hslabs * ph; grads += mo * (p_lstm + ph);
+        if (ADAM) { ad.p += mo * (p_lstm + ph); ad.m += mo * (p_lstm + ph); ad.v += mo * (p_lstm + ph); }
+    }
     __shared__ float part[GR_GROUPS][GR_COLS];
     const int c = threadIdx.x & (GR_COLS - 1), grp = threadIdx.x / GR_COLS;
     const long e = (long)blockIdx.x * GR_COLS + c;
@@ -283,7 +291,9 @@ int nsd_rrelu_noise_launch(uint64_t seed, uint32_t stream_id, long n, float *out
 // ---------------------------------------------------------------------------------------------
 // loss sum (deterministic single workgroup)
 // ---------------------------------------------------------------------------------------------
+template <bool MODELS = false>      // MODELS: workgroup m sums model m's B losses into out[m]
 __global__ __launch_bounds__(256) void loss_sum_kernel(const float *loss, int B, float *out) {
+    if constexpr (MODELS) { loss += (size_t)blockIdx.x * B; out += blockIdx.x; }
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < B; i += 256) s += loss[i];
@@ -402,7 +412,35 @@ int nsd_att_close_launch(const float *hseq1, const float *pooled, const float *d
 }
 
 int nsd_loss_sum_launch(const float *loss, int B, float *out, hipStream_t st) {
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, st, loss, B, out);
+    hipLaunchKernelGGL(loss_sum_kernel<false>, dim3(1), dim3(256), 0, st, loss, B, out);
     NSD_CHECK_LAUNCH("loss_sum");
+    return NSD_OK;
+}
+
+int nsd_multi_loss_sum_launch(const float *loss, int B, int M, float *out, hipStream_t st) {
+    hipLaunchKernelGGL(loss_sum_kernel<true>, dim3(M), dim3(256), 0, st, loss, B, out);
+    NSD_CHECK_LAUNCH("multi_loss_sum");
+    return NSD_OK;
+}
+
+int nsd_multi_grad_reduce_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
+                                 int M, float *grads, hipStream_t st) {
+    const long n = p_lstm + ph;
+    hipLaunchKernelGGL((grad_reduce_kernel<false, true>), dim3((unsigned)((n + GR_COLS - 1) / GR_COLS), M), dim3(GR_COLS * GR_GROUPS), 0, st,
+                       slabs, slab_stride, G, p_lstm, hslabs, ph, B, grads, 0, AdamTail{});
+    NSD_CHECK_LAUNCH("multi_grad_reduce");
+    return NSD_OK;
+}
+
+int nsd_multi_grad_reduce_adam_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
+                                      int M, float *grads, float *p, float *m, float *v, float lr, float b1, float b2, float eps,
+                                      float wd, float gscale, int step, hipStream_t st) {
+    const long n = p_lstm + ph;
+    if (step < 1) { nsd_set_error("multi_grad_reduce_adam: step must be >= 1"); return NSD_E_INVALID; }
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    AdamTail ad{p, m, v, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, wd, gscale};
+    hipLaunchKernelGGL((grad_reduce_kernel<true, true>), dim3((unsigned)((n + GR_COLS - 1) / GR_COLS), M), dim3(GR_COLS * GR_GROUPS), 0, st,
+                       slabs, slab_stride, G, p_lstm, hslabs, ph, B, grads, 0, ad);
+    NSD_CHECK_LAUNCH("multi_grad_reduce_adam");
     return NSD_OK;
 }

@@ -1,0 +1,163 @@
+"""Several H = 48 models per launch: folds, seed sweeps and ensembles (include/nsd.h, nsd_multi_*).
+
+ModelBatchTrainer steps M same-shaped EEG_LSTM models together: one forward, one backward and one reduction + Adam launch for all
+of them.  Model m's step is the step `Trainer(model_m, seed=seeds[m])` would take on its batch: the same random streams (seed, base
+stream 4 * step), the same mean cross-entropy over its own B trials, the same Adam update.  EnsemblePredictor averages the class
+probabilities of M checkpoints computed in one inference launch, behind SimplePredictor's surface and preprocessing.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import ops
+from ._lib import NsdError
+from .lstm_eeg_model import EEG_LSTM, SimplePredictor
+
+
+def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
+    M = len(models)
+    if M < 1:
+        raise NsdError(f"{what}: no models")
+    sp = models[0].spec
+    if len({id(m) for m in models}) != M:
+        raise NsdError(f"{what}: the same module is passed more than once (each model needs its own parameters)")
+    for i, mdl in enumerate(models):
+        if (mdl.spec != sp or mdl.residual != models[0].residual or mdl.precision != models[0].precision
+                or mdl.normalize != models[0].normalize):
+            raise NsdError(f"{what}: model {i} has another shape / options than model 0 (mixed shapes: one launch runs one shape)")
+    if models[0].residual or models[0].precision != "fp32" or sp.D != 1:
+        raise NsdError(f"{what}: the model-batched path runs the plain fp32 stack (no residual extension, no bf16)")
+    if not ops.multi_path(sp, M):
+        raise NsdError(f"{what}: {M} models of {sp} are outside the model-batched path (nsd_multi_path: H = 48, L = 2, C <= 8, "
+                       f"F <= 64, K <= 8, 1 <= M <= 32)")
+
+
+class ModelBatchTrainer:
+    """Trains M same-shaped EEG_LSTM models in the launches one model uses (single GPU).
+
+    The models' parameters are packed into one [M, P] buffer and each model's parameters are re-pointed as views into its row, so
+    every model stays an ordinary module (forward, state_dict, save_reference_checkpoint work as before).  step(x, y) takes
+    x [M,B,T,C] (per-model windows) or a shared [B,T,C], and y [M,B] or a shared [B]."""
+
+    def __init__(self, models: Sequence[EEG_LSTM], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None):
+        import torch.distributed as dist
+        self.models: List[EEG_LSTM] = list(models)
+        _check_models(self.models, "ModelBatchTrainer")
+        if group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            raise NsdError("ModelBatchTrainer: world size > 1 is not supported (model batching is single-GPU; use Trainer for data parallel)")
+        M = len(self.models)
+        self.M, self.spec = M, self.models[0].spec
+        dev = self.models[0].flat_parameters().device
+        if not self.models[0].flat_parameters().is_cuda:
+            raise NsdError("ModelBatchTrainer needs the models on the MI355X (model.to('cuda')); there is no CPU training path")
+        P = self.spec.param_count
+        self.params = torch.empty((M, P), dtype=torch.float32, device=dev)
+        offs = self.spec.offsets()
+        with torch.no_grad():
+            for i, mdl in enumerate(self.models):
+                if mdl.flat_parameters().device != dev:
+                    raise NsdError("ModelBatchTrainer: all models must live on one device")
+                self.params[i].copy_(mdl.flat_parameters())
+                for n, p in mdl._named_in_order():
+                    p.data = self.params[i, offs[n]:offs[n] + p.numel()].view(p.shape)
+                mdl._flat = self.params[i]
+        seeds = list(seeds) if seeds is not None else [1234] * M
+        if len(seeds) != M:
+            raise NsdError(f"ModelBatchTrainer: {len(seeds)} seeds for {M} models")
+        # Trainer's seed of rank 0 (trainer.py): the streams of model m are those of Trainer(model_m, seed=seeds[m])
+        self.seeds = [(int(s) + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.stochastic = stochastic
+        self.m = torch.zeros_like(self.params)
+        self.v = torch.zeros_like(self.params)
+        self.grads = torch.zeros_like(self.params)
+        self.step_count = 0
+        self._bufs = {}
+        self._last = None
+
+    def _buffers(self, B: int, T: int):
+        key = (B, T)
+        if key not in self._bufs:
+            dev = self.params.device
+            self._bufs = {key: {"ws": ops.multi_workspace(self.spec, self.M, B, T, dev),
+                                "logits": torch.empty((self.M * B, self.spec.K), dtype=torch.float32, device=dev)}}
+        return self._bufs[key]
+
+    def step(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        M = self.M
+        if x.dim() == 3:
+            B, T = int(x.shape[0]), int(x.shape[1])
+        elif x.dim() == 4 and x.shape[0] == M:
+            B, T = int(x.shape[1]), int(x.shape[2])
+        else:
+            raise NsdError(f"ModelBatchTrainer.step: x must be [M={M},B,T,C] or [B,T,C], got {tuple(x.shape)}")
+        if B == 0:
+            raise NsdError("ModelBatchTrainer.step: empty batch")
+        if not ops.multi_path(self.spec, M, B, T):
+            raise NsdError(f"ModelBatchTrainer.step: T = {T} is outside the model-batched path (nsd_multi_path: T <= 1024)")
+        x = x.contiguous().float()
+        if self.models[0].normalize:                     # as Trainer: the model is trained on what it is evaluated on
+            x = ops.zscore(x.reshape(-1, T, x.shape[-1])).view(x.shape)
+        y = y.to(torch.int32)
+        if y.dim() == 1:
+            if y.shape[0] != B:
+                raise NsdError(f"ModelBatchTrainer.step: y has {y.shape[0]} labels for {B} trials")
+            y = y.unsqueeze(0).expand(M, B)
+        if tuple(y.shape) != (M, B):
+            raise NsdError(f"ModelBatchTrainer.step: y must be [M,B] or [B], got {tuple(y.shape)}")
+        y = y.contiguous().view(-1)
+        self.step_count += 1
+        sid = (self.step_count & 0x3FFFFFFF) * 4
+        mdl = self.models[0]
+        rngs = ([dict(seed=s, base_stream=sid, p_lstm=mdl.dropout_p, p_head=mdl.head_dropout_p) for s in self.seeds]
+                if self.stochastic else None)
+        buf = self._buffers(B, T)
+        ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
+                             step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                             weight_decay=self.weight_decay)
+        self._last = (B, T)
+
+    def last_losses(self) -> List[float]:
+        """Mean CE of each model's last step (synchronises)."""
+        if self._last is None:
+            return [float("nan")] * self.M
+        B, T = self._last
+        s = ops.multi_loss_sum(self.spec, self._bufs[(B, T)]["ws"], self.M, B, T)
+        return [float(v) / B for v in s.cpu().tolist()]
+
+
+class _EnsembleModel:
+    """What SimplePredictor calls on its model: predict_proba -> the mean of the M models' class probabilities (one launch)."""
+
+    def __init__(self, models: Sequence[EEG_LSTM]):
+        _check_models(models, "EnsemblePredictor")
+        self.models = list(models)
+        self.spec, self.precision, self.normalize = models[0].spec, "fp32", models[0].normalize
+        self.params = torch.stack([m.flat_parameters() for m in self.models]).contiguous()
+
+    def predict_proba(self, x: torch.Tensor) -> torch.Tensor:
+        x = x.contiguous().float()
+        if self.normalize:
+            x = ops.zscore(x)
+        _, probs = ops.multi_infer(self.spec, self.params, x)
+        return probs.mean(0)
+
+
+class EnsemblePredictor(SimplePredictor):
+    """SimplePredictor over M checkpoints of one shape: predict / predict_windows return the mean of the models' class probabilities
+    (and its argmax label), computed for all models in one nsd_multi_infer launch on the shared windows.  Arguments are those of
+    SimplePredictor, with a list of .pth paths in place of one."""
+
+    def __init__(self, pth_paths: Sequence[str], sr: int, **kw):
+        paths = list(pth_paths)
+        if not paths:
+            raise NsdError("EnsemblePredictor: no checkpoints")
+        super().__init__(paths[0], sr, **kw)
+        models = [self.model]
+        for p in paths[1:]:
+            models.append(SimplePredictor(p, sr, **{**kw, "preprocess": "identity"}).model)
+        self.members = models
+        self.model = _EnsembleModel(models)

@@ -571,3 +571,104 @@ def seq_profile_read() -> Dict[str, Tuple[float, int]]:
         _call("nsd_seq_profile_read", None, i, C.byref(ms), C.byref(n))
         out[name] = (float(ms.value), int(n.value))
     return out
+
+
+# ---- model-batched H = 48 path: M models of one shape per launch (include/nsd.h, nsd_multi_*) ----------------------------------------
+def multi_path(spec: ModelSpec, M: int, B: int = 32, T: int = 1) -> bool:
+    """True where nsd_multi_* cover M models of this shape (H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8, 1 <= M <= 32)."""
+    d = spec.dims(B, T)
+    return bool(_lib.lib().nsd_multi_path(C.byref(d), int(M)))
+
+
+def multi_workspace(spec: ModelSpec, M: int, B: int, T: int, device) -> torch.Tensor:
+    """The training workspace of M models of B trials each (regions of a batch of M*B trials)."""
+    d, w = spec.dims(B, T), WsLayout()
+    n = _lib.lib().nsd_multi_workspace_bytes(C.byref(d), int(M), C.byref(w))
+    if n < 0:
+        check(int(n), "nsd_multi_workspace_bytes")
+    return torch.empty(max(int(n) // 4, 1), dtype=torch.float32, device=device)
+
+
+def _multi_rngs(rngs, M: int):
+    if rngs is None:
+        return None
+    if len(rngs) != M:
+        raise NsdError(f"multi: {len(rngs)} rng entries for {M} models")
+    arr = (_lib.Rng * M)()
+    for i, r in enumerate(rngs):
+        arr[i] = _lib.Rng(int(r["seed"]) & 0xFFFFFFFFFFFFFFFF, int(r["base_stream"]) & 0xFFFFFFFF, float(r["p_lstm"]), float(r["p_head"]))
+    return arr
+
+
+def _multi_x(spec: ModelSpec, x: torch.Tensor, M: int) -> Tuple[torch.Tensor, int, int, int]:
+    """x [M,B,T,C] (per-model windows) or [B,T,C] (shared: x_model_stride 0) -> (x, B, T, stride)."""
+    if x.dim() == 4:
+        if x.shape[0] != M:
+            raise NsdError(f"multi: x has {x.shape[0]} model slices for {M} models")
+        _, B, T, Cc = x.shape
+        stride = B * T * Cc
+    elif x.dim() == 3:
+        B, T, Cc = x.shape
+        stride = 0
+    else:
+        raise NsdError(f"multi: x must be [M,B,T,C] or [B,T,C], got {tuple(x.shape)}")
+    if Cc != spec.C:
+        raise NsdError(f"x has {Cc} channels, model expects {spec.C}")
+    return x, int(B), int(T), int(stride)
+
+
+def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, labels: torch.Tensor, ws: torch.Tensor, grads: torch.Tensor,
+                     *, rngs=None, logits: Optional[torch.Tensor] = None, fuse_adam: bool = True, m: Optional[torch.Tensor] = None,
+                     v: Optional[torch.Tensor] = None, step: int = 1, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
+                     eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0) -> torch.Tensor:
+    """One training step of M models at once: params [M,P], x [M,B,T,C] or shared [B,T,C], labels [M*B] int32, grads [M,P].
+    Forward + head + mean CE per model + head backward, BPTT, then the reduction (+ Adam on params / m / v when fuse_adam).
+    rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K]."""
+    M = int(params.shape[0])
+    x, B, T, stride = _multi_x(spec, x, M)
+    d = spec.dims(B, T)
+    if logits is None:
+        logits = torch.empty((M * B, spec.K), dtype=torch.float32, device=params.device)
+    if labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() != M * B:
+        raise NsdError(f"multi: labels must be contiguous int32 [M*B] = [{M * B}]")
+    r = _multi_rngs(rngs, M)
+    rp = C.cast(r, C.c_void_p) if r is not None else None
+    P = spec.param_count
+    pp, xp = _dev_f32(params, "params", (M, P)), _dev_f32(x, "x")
+    _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), 0, ws.data_ptr(), _nbytes(ws),
+          _dev_f32(logits, "logits"), STREAM)
+    _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, 0, ws.data_ptr(), _nbytes(ws), STREAM)
+    if fuse_adam:
+        _call("nsd_multi_grad_reduce_adam", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
+              _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), lr, beta1, beta2, eps, weight_decay, grad_scale, int(step), STREAM)
+    else:
+        _call("nsd_multi_grad_reduce", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), STREAM)
+    return logits
+
+
+def multi_loss_sum(spec: ModelSpec, ws: torch.Tensor, M: int, B: int, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m] = sum of model m's per-trial CE losses of the last multi_train_step (device)."""
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=ws.device)
+    d = spec.dims(B, T)
+    _call("nsd_multi_loss_sum", ws.device, C.byref(d), int(M), ws.data_ptr(), _nbytes(ws), _dev_f32(out, "out", (M,)), STREAM)
+    return out
+
+
+def multi_infer(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, *, want_probs: bool = True
+                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Eval-mode forward of M models in one launch: params [M,P], x [M,B,T,C] or shared [B,T,C] -> logits [M,B,K] (+ probs)."""
+    M = int(params.shape[0])
+    x, B, T, stride = _multi_x(spec, x, M)
+    d = spec.dims(B, T)
+    logits = torch.empty((M, B, spec.K), dtype=torch.float32, device=params.device)
+    probs = torch.empty_like(logits) if want_probs else None
+    if B == 0:
+        return logits, probs
+    nscr = int(_lib.lib().nsd_multi_infer_scratch_bytes(C.byref(d), M))
+    if nscr < 0:
+        check(nscr, "nsd_multi_infer_scratch_bytes")
+    scratch = torch.empty(max(nscr // 4, 1), dtype=torch.float32, device=params.device)
+    _call("nsd_multi_infer", params.device, C.byref(d), M, _dev_f32(params, "params", (M, spec.param_count)), _dev_f32(x, "x"), stride,
+          0, _dev_f32(logits, "logits"), _dev_f32(probs, "probs"), scratch.data_ptr(), STREAM)
+    return logits, probs

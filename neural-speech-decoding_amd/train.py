@@ -35,6 +35,41 @@ def evaluate(model: EEG_LSTM, x: torch.Tensor, y: torch.Tensor, batch: int = 512
     return correct / max(int(x.shape[0]), 1)
 
 
+def concurrent_runs(y_np: np.ndarray, kfold: int, seeds: int, seed: int, batch: int):
+    """The runs of `--kfold K --concurrent [--kfold-seeds N]`: for seed i in 0..N-1 and fold f, run seed seed + i with the folds of
+    D.stratified_folds(y, K, seed + i) and per-fold seed (seed + i) + 101 f -- exactly what `--kfold K --seed <seed + i>` trains one
+    after another.  Refuses (ValueError, with the rule) what would change what a fold sees when the runs share one step: a fold with
+    fewer training windows than --batch, or folds that draw different numbers of batches per epoch."""
+    runs = []
+    for i in range(seeds):
+        s_i = seed + i
+        for f, va in enumerate(D.stratified_folds(y_np, kfold, s_i)):
+            tr = np.setdiff1d(np.arange(len(y_np)), va)
+            runs.append(dict(seed_run=s_i, fold=f, tr=tr, va=va, seed=s_i + 101 * f))
+    if len(runs) > 32:
+        raise ValueError(f"--concurrent: {len(runs)} runs (--kfold-seeds x --kfold) but one launch takes at most 32 models")
+    for r in runs:
+        if len(r["tr"]) < batch:
+            raise ValueError(f"--concurrent: fold {r['fold']} (seed {r['seed_run']}) has {len(r['tr'])} training windows, fewer than "
+                             f"--batch {batch}: its sequential run takes one short batch per epoch, which one shared step cannot")
+    counts = sorted({len(r["tr"]) // batch for r in runs})
+    if len(counts) > 1:
+        raise ValueError(f"--concurrent: the folds draw {counts} batches of {batch} per epoch; one shared step needs the same count "
+                         "for every fold (use the sequential --kfold, or a --batch that divides the fold sizes alike)")
+    return runs
+
+
+def concurrent_epoch(runs, batch: int, epoch: int, step) -> int:
+    """One epoch of the concurrent runs: step(list of index arrays, one per run) for the j-th batch of every run, each run's batches
+    being D.epoch_batches(n_train, batch, seed_f, epoch, drop_last=True) -- those of its sequential run.  Returns the steps taken."""
+    its = [D.epoch_batches(len(r["tr"]), batch, r["seed"], epoch, drop_last=True) for r in runs]
+    n = 0
+    for idxs in zip(*its):
+        step(list(idxs))
+        n += 1
+    return n
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", help="directory with <prefix>_*.csv trials (reference: EEG_data_collection/), or a packed .npz "
@@ -62,7 +97,20 @@ def main(argv=None) -> int:
                                                    "reference's PreProcessor hands them to the model, tests/golden/recorded_trials_filtered.npz)")
     ap.add_argument("--kfold", type=int, default=0, help="K > 1: K-fold cross-validation (mean +- sd of the LAST-epoch validation accuracy, "
                                                          "no epoch selection), then --out is trained on ALL trials with the same recipe")
+    ap.add_argument("--concurrent", action="store_true", help="with --kfold: train the folds together, one model-batched step for all "
+                                                                "of them (ModelBatchTrainer; single GPU, H = 48 fp32)")
+    ap.add_argument("--kfold-seeds", type=int, default=1, help="with --kfold K --concurrent: the K folds for N seeds --seed .. --seed + N - 1 "
+                                                              "in the same launches (N * K <= 32)")
     args = ap.parse_args(argv)
+    if args.kfold_seeds != 1 and not args.concurrent:
+        ap.error("--kfold-seeds needs --kfold K --concurrent (sequentially: one --kfold run per --seed)")
+    if args.concurrent:
+        if args.kfold < 2:
+            ap.error("--concurrent trains the folds of --kfold K (K >= 2) together")
+        if args.kfold_seeds < 1 or args.kfold_seeds * args.kfold > 32:
+            ap.error(f"--concurrent: --kfold-seeds {args.kfold_seeds} x --kfold {args.kfold} models; one launch takes 1 .. 32")
+        if args.precision != "fp32" or args.bidirectional or args.hidden != 48:
+            ap.error("--concurrent: the model-batched path is H = 48 fp32 (--hidden 48, --precision fp32, no --bidirectional)")
 
     rank, local, world = init_distributed()
     if not torch.cuda.is_available():
@@ -132,6 +180,60 @@ def main(argv=None) -> int:
         if rank == 0 and out_path and (not keep_best or best[1] < 0):
             save_reference_checkpoint(model, out_path)
         return {"acc_train_last": acc_tr, "acc_val_last": acc_va, "best_val_acc": best[0], "best_epoch": best[1]}
+
+    if args.kfold > 1 and args.concurrent:
+        if world > 1:
+            print("train: --concurrent runs on one GPU (the model-batched path has no data parallel)", file=sys.stderr)
+            return 2
+        try:
+            runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch)
+        except ValueError as e:
+            print(f"train: {e}", file=sys.stderr)
+            return 2
+        from .multimodel import ModelBatchTrainer
+        models = []
+        for r in runs:
+            torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize).to(dev).train())
+        mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs])
+        tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
+        t0 = time.time()
+        res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in runs]
+
+        def step(idxs):
+            sel = [tr_devs[k][torch.from_numpy(ix).to(dev)] for k, ix in enumerate(idxs)]
+            mbt.step(torch.stack([x_all[s_] for s_ in sel]), torch.stack([y_all[s_] for s_ in sel]))
+
+        def tag(r):
+            return f"fold{r['fold']}" if args.kfold_seeds == 1 else f"seed{r['seed_run']}_fold{r['fold']}"
+        for epoch in range(args.epochs):
+            concurrent_epoch(runs, args.batch, epoch, step)
+            last = epoch == args.epochs - 1
+            if epoch % args.log_every == 0 or last:
+                losses = mbt.last_losses()
+                for k, r in enumerate(runs):
+                    acc_tr = evaluate(models[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
+                    acc_va = evaluate(models[k], x_all[r["va"]], y_all[r["va"]])
+                    res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
+                    emit({"run": tag(r), "epoch": epoch, "loss_last_batch": round(losses[k], 5), "acc_train": round(acc_tr, 4),
+                          "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), "concurrent": True})
+        accs = []
+        for k, r in enumerate(runs):
+            accs.append(res[k]["acc_val_last"])
+            rec = {"fold": r["fold"], "n_train": int(len(r["tr"])), "n_val": int(len(r["va"])),
+                   "acc_val_last_epoch": round(res[k]["acc_val_last"], 4), "acc_train_last_epoch": round(res[k]["acc_train_last"], 4),
+                   "concurrent": True}
+            if args.kfold_seeds > 1:
+                rec["seed"] = r["seed_run"]
+            emit(rec)
+        everything = np.arange(len(y_np))
+        r = fit(everything, everything[:0], args.seed + 7777, "all", args.out, keep_best=False)
+        emit({"done": True, "kfold": args.kfold, "kfold_seeds": args.kfold_seeds, "acc_val_mean": round(float(np.mean(accs)), 4),
+              "acc_val_sd": round(float(np.std(accs, ddof=1)), 4),
+              "acc_val_folds": [round(float(a), 4) for a in accs], "selection": "none: fixed epoch count, last-epoch model",
+              "shipped": {"checkpoint": args.out, "trained_on": int(len(everything)), "acc_train_last_epoch": r["acc_train_last"]},
+              "world": world, "concurrent": True, "args": {k: v for k, v in vars(args).items()}})
+        return 0
 
     if args.kfold > 1:
         # accuracy estimate: k stratified folds, every model trained for the SAME, pre-set number of epochs and scored after its
