@@ -315,7 +315,22 @@ int nsd_gemm_bf16(const void *A, int64_t lda, int32_t a_kmajor, const void *B, i
  * ((l*B + b)*T + t)*D*H + column, RReLU / head dropout index b*F + f); rng == NULL: no dropout, eval RReLU slope.
  *   nsd_seq_train_fwd   forward + head + mean CE (scale = 1/B_global) + head backward; logits[B,K] written
  *   nsd_seq_train_bwd   BPTT + all parameter gradients -> grads[P] (overwritten), same rng as the forward call
- *   nsd_seq_loss_sum    sum of the per-trial CE losses of the last nsd_seq_train_fwd -> out[0] (device)
+ *   nsd_seq_loss_sum    sum of the per-trial CE losses of the last nsd_seq_train_fwd -> out[0] (device); neither
+ *                       nsd_seq_train_fwd_logits nor nsd_seq_head_bwd writes them
+ * Two call sequences train or differentiate the model (one workspace, one rng for every call of a sequence):
+ *   fused mean CE:  nsd_seq_train_fwd -> nsd_seq_train_bwd[_dx]
+ *   any loss:       nsd_seq_train_fwd_logits -> (the caller forms dL/dlogits) -> nsd_seq_head_bwd -> nsd_seq_train_bwd[_dx]
+ *   nsd_seq_train_fwd_logits  the training forward of nsd_seq_train_fwd (same scans, same saved activations, same streams) and a
+ *                       head that writes logits[B,K] only: no labels, no loss, no head backward.  The logits are nsd_seq_train_fwd's
+ *                       bit for bit; time-outs and non-finite values are reported as there.
+ *   nsd_seq_head_bwd    dlogits[B,K] (device fp32, the caller's dL/dlogits at any scale) -> the head backward, recomputed from the
+ *                       saved top-layer sequence with the same rng: it leaves in the workspace what nsd_seq_train_fwd's fused head
+ *                       backward leaves, so nsd_seq_train_bwd[_dx] then returns the gradients of that loss.  Valid after either
+ *                       forward; a second call with other dlogits replaces the first.
+ *   nsd_seq_train_bwd_dx  nsd_seq_train_bwd (grads bit-identical to it) and, with dx != NULL, dL/dx -> dx[B,T,C] (fp32, the layout of
+ *                       x), formed from layer 0's gate gradients and the bf16 W_ih of layer 0 (both directions in one
+ *                       contraction, fp32 accumulation).  dx == NULL: exactly nsd_seq_train_bwd.  No extra workspace: the
+ *                       nsd_seq_workspace_bytes of the forward covers it.
  * Failure reporting (the persistent scan kernels assume that all workgroups of a scan group are resident at once -- true on an
  * MI355X this process has to itself; a CU mask, another process or a partition mode can break it -- and bound every wait: a group
  * that cannot assemble gives up after ~1-2 s).  A time-out is never silent:
@@ -346,6 +361,12 @@ int nsd_seq_train_fwd(const nsd_dims *d, const float *params, const float *x, co
                       float scale, uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream);
 int nsd_seq_train_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace,
                       int64_t workspace_bytes, float *grads, void *stream);
+int nsd_seq_train_fwd_logits(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, uint32_t flags,
+                             void *workspace, int64_t workspace_bytes, float *logits, void *stream);
+int nsd_seq_head_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, const float *dlogits, uint32_t flags,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+int nsd_seq_train_bwd_dx(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace,
+                         int64_t workspace_bytes, float *grads, float *dx, void *stream);
 int nsd_seq_loss_sum(const nsd_dims *d, uint32_t flags, const void *workspace, int64_t workspace_bytes, float *out, void *stream);
 int nsd_seq_workspace_init(void *workspace, int64_t workspace_bytes, void *stream);
 int nsd_seq_status(const void *workspace, int32_t *status_out, void *stream);

@@ -85,6 +85,9 @@ SYMBOLS = {
     "nsd_seq_train_fwd": (C.c_int, [_dp, _fp, _fp, _vp, _ip, C.c_float, C.c_uint32, _vp, C.c_int64, _fp, _vp]),
     "nsd_seq_train_bwd": (C.c_int, [_dp, _fp, _vp, C.c_uint32, _vp, C.c_int64, _fp, _vp]),
     "nsd_seq_loss_sum": (C.c_int, [_dp, C.c_uint32, _vp, C.c_int64, _fp, _vp]),
+    "nsd_seq_train_fwd_logits": (C.c_int, [_dp, _fp, _fp, _vp, C.c_uint32, _vp, C.c_int64, _fp, _vp]),
+    "nsd_seq_head_bwd": (C.c_int, [_dp, _fp, _vp, _fp, C.c_uint32, _vp, C.c_int64, _vp]),
+    "nsd_seq_train_bwd_dx": (C.c_int, [_dp, _fp, _vp, C.c_uint32, _vp, C.c_int64, _fp, _fp, _vp]),
     "nsd_seq_workspace_init": (C.c_int, [_vp, C.c_int64, _vp]),
     "nsd_seq_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
     "nsd_seq_guard": (C.c_int, [_vp, _fp, _vp]),

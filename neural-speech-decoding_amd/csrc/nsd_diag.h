@@ -21,7 +21,7 @@ extern "C" {
 // Opt-in launch timing: nsd_seq_profile(1) records HIP events on the launch stream around the kernels of every following
 // nsd_seq_* call, nsd_seq_profile(0) stops and discards; nsd_seq_profile_read sums the records of one kind and forgets them
 // (BLOCKING).  kind: 0 forward scan, 1 backward scan, 2 input-projection GEMM, 3 weight-gradient GEMMs, 4 input-gradient GEMM,
-// 5 head, 6 head parameter gradients, 7 operand preparation.
+// 5 head, 6 head parameter gradients, 7 operand preparation, 8 dL/dx contraction, 9 head backward from dlogits.
 int nsd_seq_profile(int32_t enable);
 int nsd_seq_profile_read(int32_t kind, float *total_ms, int32_t *count);
 // Pin the H = 48 forward instantiation of the fp32 fast path: 1 / 2 / 4 trials per workgroup (4 = nsd_lstm2_fwd48x4.hip where it

@@ -36,192 +36,32 @@ __device__ __forceinline__ void load_bf16_vals(const bf16_t *p, float (&v)[VPL])
 }
 __device__ __forceinline__ float lane_bcast(const float v, const int src) { return __shfl(v, src, 64); }
 
-template <int VPL, bool TRAIN>
+// What one launch of the head does (MODE of nsd_head_tm_body.h):
+//   HEAD_EVAL    eval slope, no dropout: logits (+ probs)
+//   HEAD_TRAIN   train-mode streams, logits, mean CE and the dense backward from dlogits = scale (p - onehot)   (nsd_seq_train_fwd)
+//   HEAD_LOGITS  train-mode streams, logits only: no labels, no backward                               (nsd_seq_train_fwd_logits)
+//   HEAD_DLOG    train-mode streams, the dense backward from the caller's dlogits [B][K] (no logits written)      (nsd_seq_head_bwd)
+// Everything up to the logits is the same code in every mode, so HEAD_LOGITS's logits are HEAD_TRAIN's bit for bit, and HEAD_DLOG
+// rebuilds exactly the activations HEAD_TRAIN differentiates.  HEAD_EVAL / HEAD_TRAIN are head_tm_kernel<VPL, false / true> as
+// before; the other two are kernels of their own.
+enum { HEAD_EVAL = 0, HEAD_TRAIN = 1, HEAD_LOGITS = 2, HEAD_DLOG = 3 };
+
+template <int VPL, bool TRAIN_>
 __global__ __launch_bounds__(256) void head_tm_kernel(const HeadTmArgs a) {
-    // U rows of the trial in flight per lane: the passes over the sequence are latency-bound (one wave per trial, 4 waves per CU at
-    // B = 1024), so the bytes in flight set the rate -- 4 rows gave 1.3 TB/s
-    constexpr int DH = 64 * VPL, U = VPL >= 16 ? 8 : (VPL >= 8 ? 8 : 16);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x * (blockDim.x >> 6) + wave;        // one wave per trial; 4, 2 or 1 waves per workgroup (see launch_vpl)
-    if (b >= a.B) return;                                       // whole waves leave; nothing below needs the workgroup
-    const int c0 = lane * VPL, T = a.T, F = a.F, K = a.K;
-    // a scan group of this evaluation (or of an earlier one on this workspace) timed out: the sequence below is garbage
-    const bool bad = a.status != nullptr && ((a.status[0] | a.status[-NSD_SEQ_HEADER_WORDS]) & NSD_SEQ_ST_TIMEOUT_MASK) != 0;
-    float aw[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) aw[v] = a.attn_w[c0 + v];
-    const float ab = a.attn_b[0];
-    const long arow = seq_row(0, b, T);                          // tile-major rows: step t of the trial is row arow + 32 t
-    const bf16_t *seq = a.top + arow * DH + c0;
-
-    // ---- pass 1: online softmax over time ------------------------------------------------------------------------------
-    float m = -3.0e38f, l = 0.f, acc[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) acc[v] = 0.f;
-    for (int t0 = 0; t0 < T; t0 += U) {
-        float hv[U][VPL];
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            const int t = t0 + q < T ? t0 + q : T - 1;
-            load_bf16_vals<VPL>(seq + (long)t * 32 * DH, hv[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            if (t0 + q < T) {                                   // (a guard, not a break: the loop must unroll for hv[q] to stay in registers)
-                float part = 0.f;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v) part = fmaf(hv[q][v], aw[v], part);
-                const float s = wave_sum(part) + ab;
-                if (TRAIN && lane == 0) a.alpha[arow + 32L * (t0 + q)] = s;          // raw score; normalised below
-                const float mn = fmaxf(m, s);
-                const float sc = __expf(m - mn), e = __expf(s - mn);
-                l = fmaf(l, sc, e);
-#pragma unroll
-                for (int v = 0; v < VPL; ++v) acc[v] = fmaf(acc[v], sc, e * hv[q][v]);
-                m = mn;
-            }
-        }
-    }
-    const float inv_l = 1.f / l;
-    float pooled[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) pooled[v] = acc[v] * inv_l;
-
-    // ---- LayerNorm ------------------------------------------------------------------------------------------------------
-    float sum = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) sum += pooled[v];
-    const float mu = wave_sum(sum) * (1.f / DH);
-    float sq = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) { const float d = pooled[v] - mu; sq = fmaf(d, d, sq); }
-    const float rstd = rsqrtf(wave_sum(sq) * (1.f / DH) + 1e-5f);
-    float xhat[VPL], ln[VPL], gam[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-        gam[v] = a.ln_w[c0 + v];
-        xhat[v] = (pooled[v] - mu) * rstd;
-        ln[v] = fmaf(xhat[v], gam[v], a.ln_b[c0 + v]);
-    }
-    // ---- fc.0 -> RReLU -> dropout: lane f holds unit f ---------------------------------------------------------------------
-    float pre = 0.f;
-    for (int f = 0; f < F; ++f) {
-        const float *wr = a.fc0_w + (long)f * DH + c0;
-        float part = 0.f;
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) part = fmaf(ln[v], wr[v], part);
-        const float tot = wave_sum(part);
-        if (lane == f) pre = tot + a.fc0_b[f];
-    }
-    float slope = a.eval_slope, dmul = 1.f;
-    if (TRAIN && lane < F) {
-        const long hi = (long)b * F + lane;
-        if (a.rng.on) {
-            const float u = (float)(nsd_rand_u32(a.rng.seed, a.rng.base + 1u, (uint64_t)hi) >> 8) * (1.0f / 16777216.0f);
-            slope = 0.125f + ((float)(1.0 / 3.0) - 0.125f) * u;
-            dmul = nsd_rand_u32(a.rng.seed, a.rng.base + 2u, (uint64_t)hi) >= a.rng.thr_head ? a.rng.keep_head : 0.f;
-        } else {
-            if (a.rrelu_slope) slope = a.rrelu_slope[hi];
-            if (a.drop_head) dmul = a.drop_head[hi];
-        }
-    }
-    const float act = lane < F ? (pre >= 0.f ? pre : pre * slope) * dmul : 0.f;
-    // ---- fc.3: lane k holds class k ---------------------------------------------------------------------------------------
-    float logit = -3.0e38f;
-    for (int k = 0; k < K; ++k) {
-        const float tot = wave_sum(lane < F ? act * a.fc3_w[(long)k * F + lane] : 0.f);
-        if (lane == k) logit = tot + a.fc3_b[k];
-    }
-    if (bad) logit = __uint_as_float(0x7fc00000u);              // NaN: logits, probabilities and the loss all carry it
-    if (lane < K) a.logits[(long)b * K + lane] = logit;
-    const float lmax = wave_max(logit);
-    const float ex = lane < K ? __expf(logit - lmax) : 0.f;
-    const float den = wave_sum(ex);
-    const float prob = ex / den;
-    if (a.probs && lane < K) a.probs[(long)b * K + lane] = prob;
-    if constexpr (!TRAIN) return;
-
-    // ---- mean cross-entropy and the dense backward ----------------------------------------------------------------------
-    const int y = a.labels[b];
-    const float ly = lane_bcast(logit, y);
-    if (lane == 0) a.loss[b] = (lmax - ly) + __logf(den);
-    // p_y - 1 without cancellation: -(sum of the other classes' probabilities)
-    const float others = wave_sum((lane < K && lane != y) ? ex : 0.f) / den;
-    const float dlog = lane < K ? (lane == y ? -others : prob) * a.scale : 0.f;
-    float dact = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const float dk = lane_bcast(dlog, k);
-        if (lane < F) dact = fmaf(dk, a.fc3_w[(long)k * F + lane], dact);
-    }
-    const float dpre = lane < F ? dact * dmul * (pre >= 0.f ? 1.f : slope) : 0.f;
-    float dln[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) dln[v] = 0.f;
-    for (int f = 0; f < F; ++f) {
-        const float df = lane_bcast(dpre, f);
-        const float *wr = a.fc0_w + (long)f * DH + c0;
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) dln[v] = fmaf(df, wr[v], dln[v]);
-    }
-    // LayerNorm backward: dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat))
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) { const float dx = dln[v] * gam[v]; s1 += dx; s2 = fmaf(dx, xhat[v], s2); }
-    const float m1 = wave_sum(s1) * (1.f / DH), m2 = wave_sum(s2) * (1.f / DH);
-    float dpool[VPL];
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) dpool[v] = rstd * (dln[v] * gam[v] - m1 - xhat[v] * m2);
-    // per-trial row for the parameter-gradient reductions
-    float *row = a.hb + (long)b * a.hb_stride;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) {
-        row[c0 + v] = ln[v];
-        row[DH + c0 + v] = dln[v] * xhat[v];
-        row[2 * DH + c0 + v] = dln[v];
-        a.pooled[(long)b * DH + c0 + v] = pooled[v];
-        a.dpooled[(long)b * DH + c0 + v] = dpool[v];
-    }
-    if (lane < F) { row[4 * DH + lane] = dpre; row[4 * DH + F + lane] = act; }
-    if (lane < K) row[4 * DH + 2 * F + lane] = dlog;
-
-    // ---- pass 2: alpha_t, dscore_t, d attn.weight ----------------------------------------------------------------------------
-    float dp_pooled = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) dp_pooled = fmaf(dpool[v], pooled[v], dp_pooled);
-    dp_pooled = wave_sum(dp_pooled);
-    float dattn[VPL], dsum = 0.f;
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) dattn[v] = 0.f;
-    for (int t0 = 0; t0 < T; t0 += U) {
-        float hv[U][VPL], sraw[U];
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            const int t = t0 + q < T ? t0 + q : T - 1;
-            load_bf16_vals<VPL>(seq + (long)t * 32 * DH, hv[q]);
-            sraw[q] = a.alpha[arow + 32L * t];                 // written by this wave's lane 0 in pass 1
-        }
-#pragma unroll
-        for (int q = 0; q < U; ++q) {
-            if (t0 + q < T) {
-                float part = 0.f;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v) part = fmaf(hv[q][v], dpool[v], part);
-                const float qd = wave_sum(part);
-                const float al = __expf(sraw[q] - m) * inv_l;
-                const float ds = al * (qd - dp_pooled);
-                if (lane == 0) {
-                    a.alpha[arow + 32L * (t0 + q)] = al;
-                    a.dscore[arow + 32L * (t0 + q)] = ds;
-                }
-                dsum += ds;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v) dattn[v] = fmaf(ds, hv[q][v], dattn[v]);
-            }
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < VPL; ++v) row[3 * DH + c0 + v] = dattn[v];
-    if (lane == 0) row[4 * DH + 2 * F + K] = dsum;
+    constexpr int MODE = TRAIN_ ? HEAD_TRAIN : HEAD_EVAL;
+    const float *const dlogits = nullptr;
+#include "nsd_head_tm_body.h"
+}
+template <int VPL>
+__global__ __launch_bounds__(256) void head_tm_logits_kernel(const HeadTmArgs a) {
+    constexpr int MODE = HEAD_LOGITS;
+    const float *const dlogits = nullptr;
+#include "nsd_head_tm_body.h"
+}
+template <int VPL>
+__global__ __launch_bounds__(256) void head_tm_dlog_kernel(const HeadTmArgs a, const float *dlogits) {
+    constexpr int MODE = HEAD_DLOG;
+#include "nsd_head_tm_body.h"
 }
 
 // Head parameter gradients, two stages (fixed order -> deterministic): stage 1, one thread per (gradient element, slice of the
@@ -293,7 +133,32 @@ int launch_vpl(const HeadTmArgs &a, hipStream_t st) {
     return NSD_OK;
 }
 
+// the two launches of the any-loss sequence (nsd_seq_train_fwd_logits, nsd_seq_head_bwd): same grid as launch_vpl
+template <int VPL>
+int launch_vpl_ext(const HeadTmArgs &a, const float *dlogits, hipStream_t st) {
+    const int cus = nsd_num_cus();
+    const int wpw = a.B >= 4 * cus ? 4 : (a.B >= 2 * cus ? 2 : 1);
+    const dim3 grid((a.B + wpw - 1) / wpw);
+    if (dlogits) hipLaunchKernelGGL((head_tm_dlog_kernel<VPL>), grid, dim3(64 * wpw), 0, st, a, dlogits);
+    else         hipLaunchKernelGGL((head_tm_logits_kernel<VPL>), grid, dim3(64 * wpw), 0, st, a);
+    NSD_CHECK_LAUNCH(dlogits ? "head_tm_dlog_kernel" : "head_tm_logits_kernel");
+    return NSD_OK;
+}
+
 }  // namespace
+
+int nsd_head_tm_ext_launch(const HeadTmArgs &a, const float *dlogits, hipStream_t st) {
+    if (a.B < 1) return NSD_OK;
+    if (a.F > 64 || a.K > 64) { nsd_set_error("head_tm: F=%d K=%d exceed 64 (one lane per unit / class)", a.F, a.K); return NSD_E_INVALID; }
+    switch (a.DH) {
+    case 64: return launch_vpl_ext<1>(a, dlogits, st);
+    case 128: return launch_vpl_ext<2>(a, dlogits, st);
+    case 256: return launch_vpl_ext<4>(a, dlogits, st);
+    case 512: return launch_vpl_ext<8>(a, dlogits, st);
+    case 1024: return launch_vpl_ext<16>(a, dlogits, st);
+    default: nsd_set_error("head_tm: sequence width %d not covered (64, 128, 256, 512, 1024)", a.DH); return NSD_E_INVALID;
+    }
+}
 
 int nsd_head_tm_launch(const HeadTmArgs &a, hipStream_t st) {
     if (a.B < 1) return NSD_OK;

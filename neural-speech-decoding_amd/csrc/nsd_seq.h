@@ -163,6 +163,17 @@ struct PrepArgs {
 int nsd_seq_prep_launch(const PrepArgs &a, hipStream_t st);
 int nsd_seq_xbf_launch(const float *x, bf16_t *xbf, int B, int Bp, int T, int C, int CP, hipStream_t st);
 
+// ---- input gradient (nsd_seq_dx.hip) ---------------------------------------------------------------------------------------
+struct SeqDx {
+    const bf16_t *da;                        // [T*Bp][D*4H] layer 0's gate gradients, unit-major columns, direction d at d*4H
+    const bf16_t *wx[NSD_SEQ_MAX_DIRS];      // [4H][CP] W_ih0 per direction as the forward built it (accumulator-tile row order)
+    bf16_t *wfrag;                           // scratch of nsd_seq_dx_scratch_bytes: W_ih0^T as MFMA B fragments
+    float *dx;                               // [B][T][C] fp32, the caller's layout
+    int B, Bp, T, C, CP, H, D;
+};
+int64_t nsd_seq_dx_scratch_bytes(int H, int D, int CP);
+int nsd_seq_dx_launch(const SeqDx &a, hipStream_t st);
+
 // ---- head on the time-major sequence (nsd_head_tm.hip) -------------------------------------------------------------------
 struct HeadTmArgs {
     const bf16_t *top;                       // [T*Bp][DH]
@@ -184,6 +195,9 @@ struct HeadTmArgs {
                                              // poisons logits / probs / loss with NaN -- nothing downstream can mistake garbage for a result
 };
 int nsd_head_tm_launch(const HeadTmArgs &a, hipStream_t st);
+// the any-loss sequence: dlogits == null -> logits only with the train-mode streams (a.rng / explicit tensors; nothing of the
+// backward written); dlogits [B][K] fp32 -> the dense backward from it (alpha, dscore, pooled, dpooled, hb rows; no logits)
+int nsd_head_tm_ext_launch(const HeadTmArgs &a, const float *dlogits, hipStream_t st);
 // head parameter gradients from the per-trial rows: grads_head points at ln.weight inside the flat gradient vector
 // (scratch: 16 * (3 DH + F DH + F + K F + K + 1) floats)
 int nsd_head_tm_grads_launch(const float *hb, long hb_stride, int B, int DH, int F, int K, float *scratch, float *g_ln_w, float *g_ln_b,

@@ -14,7 +14,8 @@ namespace {
 // ---- opt-in launch timing: DIAGNOSTIC BUILD ONLY (make diag -> libnsd_hip_diag.so, -DNSD_DIAG=1; declared in nsd_diag.h, not in
 // include/nsd.h).  HIP events on the launch stream around the kernels of the path, so that a benchmark can quote the dominant
 // kernel's own duration.  The product library has neither the state nor the entry points.
-enum { PK_SCAN_FWD = 0, PK_SCAN_BWD = 1, PK_GEMM_XPROJ = 2, PK_GEMM_DW = 3, PK_GEMM_DIN = 4, PK_HEAD = 5, PK_HEAD_GRADS = 6, PK_PREP = 7, PK_COUNT = 8 };
+enum { PK_SCAN_FWD = 0, PK_SCAN_BWD = 1, PK_GEMM_XPROJ = 2, PK_GEMM_DW = 3, PK_GEMM_DIN = 4, PK_HEAD = 5, PK_HEAD_GRADS = 6, PK_PREP = 7,
+       PK_GEMM_DX = 8, PK_HEAD_BWD = 9, PK_COUNT = 10 };
 #if NSD_DIAG
 struct ProfRec { hipEvent_t a, b; int kind; };
 struct ProfState { bool on = false; std::vector<ProfRec> recs; } g_prof;
@@ -288,7 +289,26 @@ HeadTmArgs head_args(Ctx &c, float *logits, float *probs) {
     return h;
 }
 
-int backward(Ctx &c, const RngArgs &rng, float *grads) {
+// dL/dx of the evaluation in `ws` from layer 0's gate gradients (nsd_seq_dx.hip), called once w.da holds them and layer 0's weight
+// gradients are formed.  Layer 0 has no residual term (the extension adds the input to the output for l >= 1 only) and no dropout
+// on its input, so dx = sum_d da0_d . W_ih0_d and nothing else.
+// Scratch: the W_ih0 fragments go to `parts`, the split-K buffer of the weight-gradient GEMMs.  It holds nothing between launches:
+// each weight_grads() writes it (GEMM) and consumes it (seq_reduce_dw) before returning, layer 0's is the last of them, and the
+// head-gradient reduction that follows overwrites its own scratch there before reading it -- the stream orders all of it.
+int input_grad(Ctx &c, float *dx) {
+    const SeqDims &s = c.s;
+    SeqDx a;
+    memset(&a, 0, sizeof(a));
+    a.da = at<bf16_t>(c.ws, c.w.da);                             // [T*Bp][D*4H] on both routes (fused: D = 1, layer 0's block)
+    for (int d = 0; d < s.D; ++d) a.wx[d] = at<bf16_t>(c.ws, c.w.wx[0][d]);
+    a.wfrag = at<bf16_t>(c.ws, c.w.parts);
+    a.dx = dx;
+    a.B = s.B; a.Bp = s.Bp; a.T = s.T; a.C = s.C; a.CP = s.CP; a.H = s.H; a.D = s.D;
+    ProfScope ps(PK_GEMM_DX, c.st);
+    return nsd_seq_dx_launch(a, c.st);
+}
+
+int backward(Ctx &c, const RngArgs &rng, float *grads, float *dx) {
     const SeqDims &s = c.s;
     const int H = s.H, G = 4 * H, DH = s.D * H;
     const long R = (long)s.T * s.Bp;
@@ -368,6 +388,8 @@ int backward(Ctx &c, const RngArgs &rng, float *grads) {
         }
         if (const int rc = weight_grads(1, at<bf16_t>(c.ws, c.w.da2), G, dbp1)) return rc;
         if (const int rc = weight_grads(0, at<bf16_t>(c.ws, c.w.da), G, dbp0)) return rc;
+        if (dx)
+            if (const int rc = input_grad(c, dx)) return rc;
     } else
     for (int l = s.L - 1; l >= 0; --l) {
         const bool masked = lstm_drop && l < s.L - 1;
@@ -398,6 +420,8 @@ int backward(Ctx &c, const RngArgs &rng, float *grads) {
             if (const int rc = nsd_scan_bwd_launch(a, H, s.MG, c.st)) return rc;
         }
         if (const int rc = weight_grads(l, at<bf16_t>(c.ws, c.w.da), (long)s.D * G, at<float>(c.ws, c.w.dbp))) return rc;
+        if (l == 0 && dx)
+            if (const int rc = input_grad(c, dx)) return rc;
         if (l > 0) {                                             // gradient w.r.t. the layer's input, both directions in one contraction
             GemmArgs g;
             memset(&g, 0, sizeof(g));
@@ -545,7 +569,68 @@ int nsd_seq_train_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng
     if (d->B == 0) return NSD_OK;
     RngArgs r;
     if (const int rc = make_rng_args(rng, &r)) return rc;
-    return backward(c, r, grads);
+    return backward(c, r, grads, nullptr);
+}
+
+// The any-loss sequence: the training forward with activations kept and logits out (no labels, no loss, no head backward) ...
+int nsd_seq_train_fwd_logits(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, uint32_t flags, void *workspace,
+                             int64_t workspace_bytes, float *logits, void *stream) {
+    Ctx c;
+    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_train_fwd_logits", &c)) return rc;
+    if (!x || !logits) { nsd_set_error("seq_train_fwd_logits: null pointer"); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    RngArgs r;
+    if (const int rc = make_rng_args(rng, &r)) return rc;
+    if (const int rc = forward(c, x, r, true)) return rc;
+    HeadTmArgs h = head_args(c, logits, nullptr);
+    h.train = 1; h.rng = r;                                      // the streams of nsd_seq_train_fwd's head: the same logits, bit for bit
+    ProfScope ps(PK_HEAD, c.st);
+    return nsd_head_tm_ext_launch(h, nullptr, c.st);
+}
+
+// ... the head backward from the caller's dlogits, recomputed from the saved top-layer sequence with the forward's streams: it leaves
+// what nsd_seq_train_fwd's fused head backward leaves (alpha, dscore, pooled, dpooled, the per-trial rows, zeros for padding trials),
+// so nsd_seq_train_bwd[_dx] then gives the gradients of that loss.  Valid after either forward.
+int nsd_seq_head_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, const float *dlogits, uint32_t flags, void *workspace,
+                     int64_t workspace_bytes, void *stream) {
+    Ctx c;
+    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_head_bwd", &c)) return rc;
+    if (!dlogits) { nsd_set_error("seq_head_bwd: null pointer"); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    RngArgs r;
+    if (const int rc = make_rng_args(rng, &r)) return rc;
+    HeadTmArgs h = head_args(c, nullptr, nullptr);
+    h.train = 1; h.rng = r;
+    h.alpha = at<float>(c.ws, c.w.alpha); h.dscore = at<float>(c.ws, c.w.dscore);
+    h.pooled = at<float>(c.ws, c.w.pooled); h.dpooled = at<float>(c.ws, c.w.dpooled);
+    h.hb = at<float>(c.ws, c.w.hb); h.hb_stride = c.w.hb_stride;
+    const int DH = c.s.D * c.s.H;
+    if (c.s.Bp > c.s.B) {                                        // padding trials: zero dpooled / dscore, as nsd_seq_train_fwd
+        if (hipMemsetAsync(h.dpooled + (long)c.s.B * DH, 0, (size_t)(c.s.Bp - c.s.B) * DH * 4, c.st) != hipSuccess ||
+            hipMemsetAsync(h.alpha, 0, (size_t)c.s.T * c.s.Bp * 4, c.st) != hipSuccess ||
+            hipMemsetAsync(h.dscore, 0, (size_t)c.s.T * c.s.Bp * 4, c.st) != hipSuccess) {
+            nsd_set_error("seq_head_bwd: memset failed");
+            return NSD_E_LAUNCH;
+        }
+    }
+    ProfScope ps(PK_HEAD_BWD, c.st);
+    return nsd_head_tm_ext_launch(h, dlogits, c.st);
+}
+
+// nsd_seq_train_bwd plus dx[B][T][C] (fp32) when dx != null; the parameter gradients are nsd_seq_train_bwd's, bit for bit
+int nsd_seq_train_bwd_dx(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace, int64_t workspace_bytes,
+                         float *grads, float *dx, void *stream) {
+    Ctx c;
+    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_train_bwd_dx", &c)) return rc;
+    if (!grads) { nsd_set_error("seq_train_bwd_dx: null pointer"); return NSD_E_INVALID; }
+    if (dx && nsd_seq_dx_scratch_bytes(c.s.H, c.s.D, c.s.CP) > PARTS_FLOATS * 4) {
+        nsd_set_error("seq_train_bwd_dx: %d input channels exceed the input-gradient scratch", c.s.C);
+        return NSD_E_INVALID;
+    }
+    if (d->B == 0) return NSD_OK;
+    RngArgs r;
+    if (const int rc = make_rng_args(rng, &r)) return rc;
+    return backward(c, r, grads, dx);
 }
 
 int nsd_seq_loss_sum(const nsd_dims *d, uint32_t flags, const void *workspace, int64_t workspace_bytes, float *out, void *stream) {
@@ -597,7 +682,8 @@ int nsd_seq_guard(const void *workspace, float *flag_out, void *stream) {
 // Diagnostic build only (nsd_diag.h).  enable != 0 starts recording HIP events (on the launch stream) around the kernels of
 // every following nsd_seq_* call, 0 stops and discards.  nsd_seq_profile_read sums one kind and forgets its records
 // (BLOCKING: waits for those events).  kind: 0 forward scan, 1 backward scan, 2 input-projection GEMM, 3 weight-gradient
-// GEMMs (+ their reductions), 4 input-gradient GEMM, 5 head, 6 head parameter gradients, 7 operand preparation.
+// GEMMs (+ their reductions), 4 input-gradient GEMM, 5 head, 6 head parameter gradients, 7 operand preparation, 8 dL/dx contraction
+// (nsd_seq_train_bwd_dx), 9 head backward from dlogits (nsd_seq_head_bwd).
 int nsd_seq_profile(int32_t enable) {
     for (ProfRec &r : g_prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     g_prof.recs.clear();

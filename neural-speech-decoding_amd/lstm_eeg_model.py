@@ -110,7 +110,8 @@ class _EEGSeqFunction(torch.autograd.Function):
     """Whole-model autograd node on the sequence-batched bf16 path (nsd_seq_*): x, parameters -> logits; backward needs
     d loss / d logits of a mean cross-entropy, which that path fuses into the forward -- so the node takes the labels
     and returns (logits, loss) with loss the mean CE the kernels computed, and only `loss.backward()` (times a scalar) is
-    supported.  The Trainer calls the ops directly; this node exists so that the nn.Module surface works too."""
+    supported.  The Trainer calls the ops directly; this node exists so that the nn.Module surface works too.  dL/dx comes
+    back where x requires it (nsd_seq_train_bwd_dx)."""
 
     @staticmethod
     def forward(ctx, module: "EEG_LSTM", x: torch.Tensor, labels: torch.Tensor, rng, *params):
@@ -128,10 +129,40 @@ class _EEGSeqFunction(torch.autograd.Function):
         module = ctx.module
         spec = module.spec
         B, T = ctx.shape
-        g = ops.seq_train_bwd(spec, module._flat, ctx.ws, B, T, rng=ctx.rng) * dloss
+        dx = torch.empty((B, T, spec.C), dtype=torch.float32, device=dloss.device) if ctx.needs_input_grad[1] else None
+        g = ops.seq_train_bwd(spec, module._flat, ctx.ws, B, T, rng=ctx.rng, dx=dx) * dloss
+        if dx is not None:
+            dx = dx * dloss
         offs, shapes = spec.offsets(), spec.shapes()
         grads = tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
-        return (None, None, None, None) + grads    # (the workspace stays with the graph: a second backward re-runs the scans on it)
+        return (None, dx, None, None) + grads      # (the workspace stays with the graph: a second backward re-runs the scans on it)
+
+
+class _EEGSeqEvalFunction(torch.autograd.Function):
+    """Eval-mode differentiable forward of the sequence-batched bf16 path: x, parameters -> logits, and a backward from ANY
+    d loss / d logits (nsd_seq_train_fwd_logits -> nsd_seq_head_bwd -> nsd_seq_train_bwd[_dx]): custom losses, distillation,
+    saliency.  No dropout, eval RReLU slope: the logits are those of `with torch.no_grad(): model(x)`, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, module: "EEG_LSTM", x: torch.Tensor, *params):
+        spec, flat = module.spec, module._flat
+        B, T, _ = x.shape
+        ws = ops.seq_workspace(spec, B, T, x.device)
+        logits = ops.seq_train_fwd_logits(spec, flat, x, ws)
+        ctx.module, ctx.ws, ctx.shape = module, ws, (B, T)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        module = ctx.module
+        spec = module.spec
+        B, T = ctx.shape
+        ops.seq_head_bwd(spec, module._flat, ctx.ws, dlogits.contiguous().float(), B, T)
+        dx = torch.empty((B, T, spec.C), dtype=torch.float32, device=dlogits.device) if ctx.needs_input_grad[1] else None
+        g = ops.seq_train_bwd(spec, module._flat, ctx.ws, B, T, dx=dx)
+        offs, shapes = spec.offsets(), spec.shapes()
+        grads = tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
+        return (None, dx) + grads                  # (head_bwd + bwd recompute from the saved sequence: retain_graph gives the same bits)
 
 
 class EEG_LSTM(nn.Module):
@@ -243,9 +274,13 @@ class EEG_LSTM(nn.Module):
             if not self.spec.seq_path(max(x.shape[0], 1), x.shape[1]):
                 raise NsdError(f"precision='bf16': model shape {self.spec} is not covered by the sequence-batched path "
                                "(hidden size 64/128/256/512, fc width and classes <= 64)")
-            if self.training or need_grad:
-                raise NsdError("precision='bf16': training goes through EEG_LSTM.loss(x, labels) or nsd_amd.trainer.Trainer "
-                               "(the path fuses the cross-entropy into the forward); forward() serves eval mode")
+            if self.training:
+                raise NsdError("precision='bf16': no train-mode forward() -- train through EEG_LSTM.loss(x, labels) or "
+                               "nsd_amd.trainer.Trainer (the path draws dropout and fuses the cross-entropy in its kernels); in eval "
+                               "mode forward() is differentiable w.r.t. the parameters and x for any loss")
+            if torch.is_grad_enabled() and (need_grad or x.requires_grad):
+                params = [p for _, p in self._named_in_order()]
+                return _EEGSeqEvalFunction.apply(self, x, *params)
             logits, _ = ops.seq_infer(self.spec, flat, x, want_probs=False)
             return logits
         if not self.training and not need_grad:
@@ -257,8 +292,8 @@ class EEG_LSTM(nn.Module):
 
     def loss(self, x: torch.Tensor, labels: torch.Tensor):
         """precision='bf16' training surface: (logits, mean cross-entropy) with the loss differentiable w.r.t. the
-        parameters -- `model.loss(x, y)[1].backward()` fills `.grad` of all tensors.  Train mode draws the dropout / RReLU
-        streams inside the kernels."""
+        parameters -- `model.loss(x, y)[1].backward()` fills `.grad` of all tensors, and `x.grad` where x requires it.  Train
+        mode draws the dropout / RReLU streams inside the kernels."""
         if self.precision != "bf16":
             raise NsdError("EEG_LSTM.loss is the bf16 path's training surface; with precision='fp32' use "
                            "torch.nn.functional.cross_entropy(model(x), y)")

@@ -536,13 +536,40 @@ def seq_train_fwd(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, labels: 
 
 
 def seq_train_bwd(spec: ModelSpec, flat: torch.Tensor, ws: torch.Tensor, B: int, T: int, *, rng: Optional[dict] = None,
-                  grads: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """BPTT + every parameter gradient of the evaluation seq_train_fwd left in `ws` -> flat gradient vector (overwritten)."""
+                  grads: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """BPTT + every parameter gradient of the evaluation seq_train_fwd left in `ws` -> flat gradient vector (overwritten).
+    dx: optional [B, T, C] fp32 device tensor that receives dL/dx (nsd_seq_train_bwd_dx; the gradients are the same bits)."""
     d = spec.dims(B, T)
     grads = torch.empty(spec.param_count, dtype=torch.float32, device=flat.device) if grads is None else grads
-    _call("nsd_seq_train_bwd", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng), spec.seq_flags,
-          ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (spec.param_count,)), STREAM)
+    if dx is None:
+        _call("nsd_seq_train_bwd", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng), spec.seq_flags,
+              ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (spec.param_count,)), STREAM)
+    else:
+        _call("nsd_seq_train_bwd_dx", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng), spec.seq_flags,
+              ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (spec.param_count,)), _dev_f32(dx, "dx", (B, T, spec.C)), STREAM)
     return grads
+
+
+def seq_train_fwd_logits(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: torch.Tensor, *, rng: Optional[dict] = None,
+                         logits: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The training forward of seq_train_fwd with activations kept in `ws`, logits out and nothing else (no labels, no loss, no
+    head backward): first call of the any-loss sequence seq_train_fwd_logits -> seq_head_bwd -> seq_train_bwd.  The logits are
+    seq_train_fwd's bit for bit."""
+    B, T, _ = x.shape
+    d = spec.dims(B, T)
+    logits = torch.empty((B, spec.K), dtype=torch.float32, device=x.device) if logits is None else logits
+    _call("nsd_seq_train_fwd_logits", x.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _dev_f32(x, "x", (B, T, spec.C)),
+          _seq_rng(rng), spec.seq_flags, ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits", (B, spec.K)), STREAM)
+    return logits
+
+
+def seq_head_bwd(spec: ModelSpec, flat: torch.Tensor, ws: torch.Tensor, dlogits: torch.Tensor, B: int, T: int, *,
+                 rng: Optional[dict] = None) -> None:
+    """Head backward from the caller's dL/dlogits [B, K] (fp32, any scale) on the evaluation in `ws` (either forward, same rng):
+    seq_train_bwd then returns the gradients of that loss."""
+    d = spec.dims(B, T)
+    _call("nsd_seq_head_bwd", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng),
+          _dev_f32(dlogits, "dlogits", (B, spec.K)), spec.seq_flags, ws.data_ptr(), _nbytes(ws), STREAM)
 
 
 def seq_loss_sum(spec: ModelSpec, ws: torch.Tensor, B: int, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -552,7 +579,7 @@ def seq_loss_sum(spec: ModelSpec, ws: torch.Tensor, B: int, T: int, out: Optiona
     return out
 
 
-SEQ_PROFILE_KINDS = ("scan_fwd", "scan_bwd", "gemm_xproj", "gemm_dw", "gemm_din", "head", "head_grads", "prep")
+SEQ_PROFILE_KINDS = ("scan_fwd", "scan_bwd", "gemm_xproj", "gemm_dw", "gemm_din", "head", "head_grads", "prep", "gemm_dx", "head_bwd")
 
 
 def seq_profile(enable: bool) -> None:
