@@ -93,7 +93,7 @@ static nsd_ws_layout make_ws(const nsd_dims *d, bool have_device) {
     // Without a device (symbol / layout checks on CPU) assume the MI355X's 256 CUs.
     const bool fast = fast_path_ok(d) != 0;
     int64_t nsl = B < 256 ? B : 256;
-    if (have_device) nsl = nsd_lstm2_bwd_grid((int)B);
+    if (have_device) nsl = nsd_lstm2_bwd_groups((int)B, 1);
     if (nsl < 1 || !fast) nsl = 1;       // generic path: the weight-gradient GEMMs write one slab
     w.n_slabs = nsl;
     w.slabs = p;   p = align4(p + nsl * align4(pl.lstm_total));
@@ -175,7 +175,8 @@ int nsd_zscore_fwd(const float *x, float *y, int32_t B, int32_t T, int32_t C, vo
 }
 
 // ---- shared argument builders -----------------------------------------------------------------------------
-static int build_lstm_fwd(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm,
+// (M models of d->B trials each in one workspace, nsd_multi.h: the per-layer stride of the saved [L, M*B, T, H] regions; M = 1 otherwise)
+static int build_lstm_fwd(const nsd_dims *d, int M, const float *params, const float *x, const float *drop_lstm,
                           uint32_t flags, float *ws, const nsd_ws_layout &w, bool train, float *top_only,
                           Lstm2FwdArgs *out) {
     const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
@@ -189,7 +190,7 @@ static int build_lstm_fwd(const nsd_dims *d, const float *params, const float *x
     a.B = d->B; a.T = d->T; a.C = d->C;
     a.residual = (flags & NSD_FLAG_RESIDUAL) ? 1 : 0;
     a.ablate = ablate_mask();
-    const int64_t BTH = (int64_t)d->B * d->T * d->H;
+    const int64_t BTH = (int64_t)M * d->B * d->T * d->H;
     if (train) {
         a.hseq0 = ws + w.hseq; a.hseq1 = ws + w.hseq + BTH;
         a.cseq0 = ws + w.cseq; a.cseq1 = ws + w.cseq + BTH;
@@ -217,6 +218,56 @@ static HeadArgs build_head(const nsd_dims *d, const float *params) {
     h.Ph = pl.total - pl.lstm_total;
     h.B = d->B; h.T = d->T; h.H = d->H; h.F = d->F; h.K = d->K;
     return h;
+}
+
+// the head in the tail of the H = 48 forward kernels: its parameters and the RReLU eval slope (inference adds logits_out / probs_out)
+static void attach_head(Lstm2FwdArgs *a, const HeadArgs &h) {
+    a->attn_w = h.attn_w; a->attn_b = h.attn_b; a->ln_w = h.ln_w; a->ln_b = h.ln_b;
+    a->fc0_w = h.fc0_w; a->fc0_b = h.fc0_b; a->fc3_w = h.fc3_w; a->fc3_b = h.fc3_b;
+    a->eval_slope = h.eval_slope; a->K = h.K; a->F = h.F;
+}
+// the fused training head: forward, loss, and the head's backward up to dscore / dpooled and the per-trial head slabs
+static void attach_head_train(Lstm2FwdArgs *a, const HeadArgs &h, const int32_t *labels, float scale, float *logits, float *ws,
+                              const nsd_ws_layout &w) {
+    attach_head(a, h);
+    a->head_train = 1;
+    if (!a->residual) a->top = nullptr;      // top == layer-1 h: the kernel's tail reads hseq1, the saver skips the duplicate
+    a->labels = labels; a->scale = scale;
+    a->logits = logits; a->loss = ws + w.loss; a->alpha = ws + w.alpha; a->pooled = ws + w.pooled;
+    a->fc0_pre = ws + w.fc0_pre; a->dscore = ws + w.dscore; a->dpooled = ws + w.dpooled;
+    a->adpack = ws + w.adpack; a->hslabs = ws + w.hslabs;
+    a->o_ln_w = h.o_ln_w; a->o_ln_b = h.o_ln_b; a->o_attn_w = h.o_attn_w; a->o_attn_b = h.o_attn_b;
+    a->o_fc0_w = h.o_fc0_w; a->o_fc0_b = h.o_fc0_b; a->o_fc3_w = h.o_fc3_w; a->o_fc3_b = h.o_fc3_b; a->Ph = h.Ph;
+}
+
+// (M as in build_lstm_fwd; mask, rng and da0_out are the caller's)
+static Lstm2BwdArgs build_lstm_bwd(const nsd_dims *d, int M, const float *params, const float *x, float *ws, const nsd_ws_layout &w,
+                                   uint32_t flags) {
+    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+    const int64_t BTH = (int64_t)M * d->B * d->T * d->H;
+    Lstm2BwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x;
+    a.w_hh0 = params + pl.w_hh[0]; a.w_ih1 = params + pl.w_ih[1]; a.w_hh1 = params + pl.w_hh[1];
+    a.attn_w = params + pl.attn_w;
+    a.hseq0 = ws + w.hseq; a.hseq1 = ws + w.hseq + BTH;
+    a.cseq0 = ws + w.cseq; a.cseq1 = ws + w.cseq + BTH;
+    a.gact0 = ws + w.gact; a.gact1 = ws + w.gact + 4 * BTH;
+    a.in1seq = ws + w.inseq;
+    a.alpha = ws + w.alpha; a.dscore = ws + w.dscore; a.dpooled = ws + w.dpooled;
+    a.dsc_pack = ws + w.adpack;
+    a.pooled = ws + w.pooled; a.dscore_out = ws + w.dscore; a.hslabs = ws + w.hslabs;
+    const HeadArgs h = build_head(d, params);
+    a.Ph = h.Ph; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
+    a.dbg = g_dbg;
+    a.slabs = ws + w.slabs;
+    a.slab_stride = align4(pl.lstm_total);
+    a.o_w_ih0 = pl.w_ih[0]; a.o_w_hh0 = pl.w_hh[0]; a.o_b_ih0 = pl.b_ih[0]; a.o_b_hh0 = pl.b_hh[0];
+    a.o_w_ih1 = pl.w_ih[1]; a.o_w_hh1 = pl.w_hh[1]; a.o_b_ih1 = pl.b_ih[1]; a.o_b_hh1 = pl.b_hh[1];
+    a.B = d->B; a.T = d->T; a.C = d->C;
+    a.residual = (flags & NSD_FLAG_RESIDUAL) ? 1 : 0;
+    a.ablate = ablate_mask();
+    return a;
 }
 
 #define REQUIRE_FAST(d, name)                                                                              \
@@ -258,16 +309,13 @@ int nsd_infer(const nsd_dims *d, const float *params, const float *x, uint32_t f
         nsd_ws_layout w;
         memset(&w, 0, sizeof(w));
         Lstm2FwdArgs a;
-        build_lstm_fwd(d, params, x, nullptr, flags, nullptr, w, false, (float *)scratch, &a);
+        build_lstm_fwd(d, 1, params, x, nullptr, flags, nullptr, w, false, (float *)scratch, &a);
         if (d->H == 48 && d->F <= 64 && d->K <= 64) {
             // single launch: attention pooling (online softmax), LayerNorm, dense head and class softmax run in the
             // LSTM kernel's tail wave; nothing but x, the parameters and the [B,K] outputs touches HBM
-            const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+            attach_head(&a, build_head(d, params));
             a.top = nullptr;
-            a.attn_w = params + pl.attn_w; a.attn_b = params + pl.attn_b; a.ln_w = params + pl.ln_w; a.ln_b = params + pl.ln_b;
-            a.fc0_w = params + pl.fc0_w; a.fc0_b = params + pl.fc0_b; a.fc3_w = params + pl.fc3_w; a.fc3_b = params + pl.fc3_b;
-            a.eval_slope = (float)((0.125 + 1.0 / 3.0) / 2.0);
-            a.logits_out = logits; a.probs_out = probs; a.K = d->K; a.F = d->F;
+            a.logits_out = logits; a.probs_out = probs;
             return nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
         }
         rc = nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
@@ -306,7 +354,7 @@ int nsd_lstm_fwd(const nsd_dims *d, const float *params, const float *x, const f
                                     (hipStream_t)stream);
     }
     Lstm2FwdArgs a;
-    build_lstm_fwd(d, params, x, drop_lstm, flags, workspace, w, true, nullptr, &a);
+    build_lstm_fwd(d, 1, params, x, drop_lstm, flags, workspace, w, true, nullptr, &a);
     return nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
 }
 
@@ -391,19 +439,9 @@ static int lstm_head_train_impl(const nsd_dims *d, const float *params, const fl
         return nsd_head_train(d, params, rrelu_slope, drop_head, labels, scale, workspace, workspace_bytes, logits, stream);
     }
     Lstm2FwdArgs a;
-    build_lstm_fwd(d, params, x, drop_lstm, flags, workspace, w, true, nullptr, &a);
-    const HeadArgs h = build_head(d, params);
-    a.attn_w = h.attn_w; a.attn_b = h.attn_b; a.ln_w = h.ln_w; a.ln_b = h.ln_b;
-    a.fc0_w = h.fc0_w; a.fc0_b = h.fc0_b; a.fc3_w = h.fc3_w; a.fc3_b = h.fc3_b;
-    a.eval_slope = h.eval_slope; a.K = d->K; a.F = d->F;
-    a.head_train = 1;
-    if (!a.residual) a.top = nullptr;      // top == layer-1 h: the kernel's tail reads hseq1, the saver skips the duplicate
-    a.labels = labels; a.rrelu_slope = rrelu_slope; a.drop_head = drop_head; a.scale = scale;
-    a.logits = logits; a.loss = workspace + w.loss; a.alpha = workspace + w.alpha; a.pooled = workspace + w.pooled;
-    a.fc0_pre = workspace + w.fc0_pre; a.dscore = workspace + w.dscore; a.dpooled = workspace + w.dpooled;
-    a.adpack = workspace + w.adpack; a.hslabs = workspace + w.hslabs;
-    a.o_ln_w = h.o_ln_w; a.o_ln_b = h.o_ln_b; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
-    a.o_fc0_w = h.o_fc0_w; a.o_fc0_b = h.o_fc0_b; a.o_fc3_w = h.o_fc3_w; a.o_fc3_b = h.o_fc3_b; a.Ph = h.Ph;
+    build_lstm_fwd(d, 1, params, x, drop_lstm, flags, workspace, w, true, nullptr, &a);
+    attach_head_train(&a, build_head(d, params), labels, scale, logits, workspace, w);
+    a.rrelu_slope = rrelu_slope; a.drop_head = drop_head;
     if (rng) a.rng = *rng;
     return nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
 }
@@ -461,31 +499,8 @@ static int lstm_bwd_impl(const nsd_dims *d, const float *params, const float *x,
                                     workspace + w.din + BTH, workspace + w.slabs, (hipStream_t)stream)) return rc;
         return dx ? nsd_dx_launch(workspace + w.da_seq, params + pl.w_ih[0], dx, (long)d->B * d->T, 4 * d->H, d->C, (hipStream_t)stream) : NSD_OK;
     }
-    Lstm2BwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.w_hh0 = params + pl.w_hh[0]; a.w_ih1 = params + pl.w_ih[1]; a.w_hh1 = params + pl.w_hh[1];
-    a.attn_w = params + pl.attn_w;
+    Lstm2BwdArgs a = build_lstm_bwd(d, 1, params, x, workspace, w, flags);
     a.mask = drop_lstm;
-    a.hseq0 = workspace + w.hseq; a.hseq1 = workspace + w.hseq + BTH;
-    a.cseq0 = workspace + w.cseq; a.cseq1 = workspace + w.cseq + BTH;
-    a.gact0 = workspace + w.gact; a.gact1 = workspace + w.gact + 4 * BTH;
-    a.in1seq = workspace + w.inseq;
-    a.alpha = workspace + w.alpha; a.dscore = workspace + w.dscore; a.dpooled = workspace + w.dpooled;
-    a.dsc_pack = workspace + w.adpack;
-    {
-        const HeadArgs h = build_head(d, params);
-        a.pooled = workspace + w.pooled; a.dscore_out = workspace + w.dscore; a.hslabs = workspace + w.hslabs;
-        a.Ph = h.Ph; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
-    }
-    a.dbg = g_dbg;
-    a.slabs = workspace + w.slabs;
-    a.slab_stride = align4(pl.lstm_total);
-    a.o_w_ih0 = pl.w_ih[0]; a.o_w_hh0 = pl.w_hh[0]; a.o_b_ih0 = pl.b_ih[0]; a.o_b_hh0 = pl.b_hh[0];
-    a.o_w_ih1 = pl.w_ih[1]; a.o_w_hh1 = pl.w_hh[1]; a.o_b_ih1 = pl.b_ih[1]; a.o_b_hh1 = pl.b_hh[1];
-    a.B = d->B; a.T = d->T; a.C = d->C;
-    a.residual = (flags & NSD_FLAG_RESIDUAL) ? 1 : 0;
-    a.ablate = ablate_mask();
     if (rng) a.rng = *rng;
     if (dx) {
         a.da0_out = workspace + w.gact;                             // (in place of layer 0's saved gates, 4H floats per step: see Lstm2BwdArgs)
@@ -626,7 +641,7 @@ static nsd_ws_layout make_multi_ws(const nsd_dims *d, int M, bool have_device) {
     nsd_ws_layout w = make_ws(&t, have_device);
     if (M == 1) return w;
     const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    const int64_t nsl = (int64_t)M * nsd_lstm2_multi_bwd_groups(M, d->B > 0 ? d->B : 1);
+    const int64_t nsl = (int64_t)M * nsd_lstm2_bwd_groups(d->B > 0 ? d->B : 1, M);
     if (nsl > w.n_slabs) {       // room for M * G slabs: the head slabs (and the generic path's regions, empty here) move behind them
         const int64_t grow = (nsl - w.n_slabs) * align4(pl.lstm_total);
         w.n_slabs = nsl; w.hslabs += grow; w.da_seq += grow; w.din += grow; w.total += grow;
@@ -693,22 +708,9 @@ int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const
     const float scale = 1.0f / (float)d->B;                     // mean CE per model
     if (M == 1) return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, rng ? &r : nullptr, labels, scale, flags, workspace,
                                             workspace_bytes, logits, stream);
-    const nsd_dims t = multi_total(d, M);
     Lstm2FwdArgs a;
-    build_lstm_fwd(&t, params, x, nullptr, flags, workspace, w, true, nullptr, &a);
-    const HeadArgs h = build_head(d, params);
-    a.B = d->B;
-    a.attn_w = h.attn_w; a.attn_b = h.attn_b; a.ln_w = h.ln_w; a.ln_b = h.ln_b;
-    a.fc0_w = h.fc0_w; a.fc0_b = h.fc0_b; a.fc3_w = h.fc3_w; a.fc3_b = h.fc3_b;
-    a.eval_slope = h.eval_slope; a.K = d->K; a.F = d->F;
-    a.head_train = 1;
-    a.top = nullptr;
-    a.labels = labels; a.scale = scale;
-    a.logits = logits; a.loss = workspace + w.loss; a.alpha = workspace + w.alpha; a.pooled = workspace + w.pooled;
-    a.fc0_pre = workspace + w.fc0_pre; a.dscore = workspace + w.dscore; a.dpooled = workspace + w.dpooled;
-    a.adpack = workspace + w.adpack; a.hslabs = workspace + w.hslabs;
-    a.o_ln_w = h.o_ln_w; a.o_ln_b = h.o_ln_b; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
-    a.o_fc0_w = h.o_fc0_w; a.o_fc0_b = h.o_fc0_b; a.o_fc3_w = h.o_fc3_w; a.o_fc3_b = h.o_fc3_b; a.Ph = h.Ph;
+    build_lstm_fwd(d, M, params, x, nullptr, flags, workspace, w, true, nullptr, &a);
+    attach_head_train(&a, build_head(d, params), labels, scale, logits, workspace, w);
     a.rng = r;
     s.x_stride = x_model_stride; s.P = nsd_make_layout(d->C, d->H, d->L, d->K, d->F).total;
     return nsd_lstm2_multi_fwd_launch(a, s, M, (hipStream_t)stream);
@@ -727,31 +729,9 @@ int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const
     if (const int rc = multi_ws(d, M, workspace, workspace_bytes, who, &w)) return rc;
     if (d->B == 0) return NSD_OK;
     if (M == 1) return lstm_bwd_impl(d, params, x, nullptr, rng ? &r : nullptr, flags, workspace, workspace_bytes, nullptr, stream);
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    const int64_t BTH = (int64_t)M * d->B * d->T * d->H;       // per-layer stride of the [L, M*B, T, H] regions
-    Lstm2BwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    a.w_hh0 = params + pl.w_hh[0]; a.w_ih1 = params + pl.w_ih[1]; a.w_hh1 = params + pl.w_hh[1];
-    a.attn_w = params + pl.attn_w;
-    a.hseq0 = workspace + w.hseq; a.hseq1 = workspace + w.hseq + BTH;
-    a.cseq0 = workspace + w.cseq; a.cseq1 = workspace + w.cseq + BTH;
-    a.gact0 = workspace + w.gact; a.gact1 = workspace + w.gact + 4 * BTH;
-    a.in1seq = workspace + w.inseq;
-    a.alpha = workspace + w.alpha; a.dscore = workspace + w.dscore; a.dpooled = workspace + w.dpooled;
-    a.dsc_pack = workspace + w.adpack;
-    const HeadArgs h = build_head(d, params);
-    a.pooled = workspace + w.pooled; a.dscore_out = workspace + w.dscore; a.hslabs = workspace + w.hslabs;
-    a.Ph = h.Ph; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
-    a.dbg = g_dbg;
-    a.slabs = workspace + w.slabs;
-    a.slab_stride = align4(pl.lstm_total);
-    a.o_w_ih0 = pl.w_ih[0]; a.o_w_hh0 = pl.w_hh[0]; a.o_b_ih0 = pl.b_ih[0]; a.o_b_hh0 = pl.b_hh[0];
-    a.o_w_ih1 = pl.w_ih[1]; a.o_w_hh1 = pl.w_hh[1]; a.o_b_ih1 = pl.b_ih[1]; a.o_b_hh1 = pl.b_hh[1];
-    a.B = d->B; a.T = d->T; a.C = d->C;
-    a.ablate = ablate_mask();
+    Lstm2BwdArgs a = build_lstm_bwd(d, M, params, x, workspace, w, flags);
     a.rng = r;
-    s.x_stride = x_model_stride; s.P = pl.total;
+    s.x_stride = x_model_stride; s.P = nsd_make_layout(d->C, d->H, d->L, d->K, d->F).total;
     return nsd_lstm2_multi_bwd_launch(a, s, M, (hipStream_t)stream);
 }
 
@@ -762,7 +742,7 @@ int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, 
     if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_grad_reduce", &w)) return rc;
     if (M == 1) return nsd_grad_reduce(d, workspace, workspace_bytes, grads, 0, stream);
     const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    return nsd_multi_grad_reduce_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_multi_bwd_groups(M, d->B) : 0,
+    return nsd_multi_grad_reduce_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_bwd_groups(d->B, M) : 0,
                                         pl.lstm_total, workspace + w.hslabs, pl.total - pl.lstm_total, d->B, M, grads, (hipStream_t)stream);
 }
 
@@ -775,7 +755,7 @@ int nsd_multi_grad_reduce_adam(const nsd_dims *d, int32_t M, const float *worksp
     if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_grad_reduce_adam", &w)) return rc;
     if (M == 1) return nsd_grad_reduce_adam(d, workspace, workspace_bytes, grads, p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step, stream);
     const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    return nsd_multi_grad_reduce_adam_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_multi_bwd_groups(M, d->B) : 0,
+    return nsd_multi_grad_reduce_adam_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_bwd_groups(d->B, M) : 0,
                                              pl.lstm_total, workspace + w.hslabs, pl.total - pl.lstm_total, d->B, M, grads, p, m, v, lr,
                                              beta1, beta2, eps, weight_decay, grad_scale, step, (hipStream_t)stream);
 }
@@ -804,12 +784,9 @@ int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const flo
     nsd_ws_layout w;
     memset(&w, 0, sizeof(w));
     Lstm2FwdArgs a;
-    build_lstm_fwd(d, params, x, nullptr, 0, nullptr, w, false, nullptr, &a);
-    a.top = nullptr;
-    a.attn_w = params + pl.attn_w; a.attn_b = params + pl.attn_b; a.ln_w = params + pl.ln_w; a.ln_b = params + pl.ln_b;
-    a.fc0_w = params + pl.fc0_w; a.fc0_b = params + pl.fc0_b; a.fc3_w = params + pl.fc3_w; a.fc3_b = params + pl.fc3_b;
-    a.eval_slope = (float)((0.125 + 1.0 / 3.0) / 2.0);
-    a.logits_out = logits; a.probs_out = probs; a.K = d->K; a.F = d->F;
+    build_lstm_fwd(d, M, params, x, nullptr, 0, nullptr, w, false, nullptr, &a);
+    attach_head(&a, build_head(d, params));
+    a.logits_out = logits; a.probs_out = probs;
     ModelSplit s;
     memset(&s, 0, sizeof(s));
     s.x_stride = x_model_stride; s.P = pl.total;

@@ -77,7 +77,7 @@ struct HeadArgs {
 };
 int nsd_lstm2_fwd_launch(const Lstm2FwdArgs &a, int H, hipStream_t st);
 int nsd_lstm2_bwd_launch(const Lstm2BwdArgs &a, int H, hipStream_t st);
-int nsd_lstm2_bwd_grid(int B);
+int nsd_lstm2_bwd_groups(int B, int M);     // workgroups (= slabs) per model of the backward launch: M models of B trials each (plan48, nsd_lstm2.hip)
 int nsd_lstm2_bwd48_launch(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t st);
 int nsd_lstm2_fwd48_launch(const Lstm2FwdArgs &a, int nb, int grid, hipStream_t st);
 bool nsd_lstm2_fwd48_head_train_fits(int T, int F, int K);

@@ -517,10 +517,12 @@ static int nsd_diag_forced_fwd48() { return g_force_fwd48; }
 static int nsd_diag_forced_fwd48() { return 0; }
 static int nsd_diag_forced_bwd48() { return 0; }
 #endif
-static int pick_nb(int B) {
+
+// trials per CU, rounded up to a power of two: 1 while every trial has a CU of its own, 2 up to two trials per CU, 4 beyond
+static int pick_nb(int trials) {
     const int cus = nsd_num_cus();
-    if (B <= cus) return 1;
-    if (B <= 2 * cus) return 2;
+    if (trials <= cus) return 1;
+    if (trials <= 2 * cus) return 2;
     return 4;
 }
 
@@ -543,51 +545,83 @@ static int launch_bwd_h(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t st)
     return 0;
 }
 
-// the backward kernels keep at most 2 trials per workgroup (register budget); larger batches loop.  Up to two trials per CU the
-// ONE-trial instantiation walks two trials one after the other: since round 4 it is the faster one per trial (H = 48: split-bf16 weight
-// gradients, prepared factors, four-step hand-off -- 2 x 127 us against 268-271 us of the two-trial instantiation at 320 .. 512 trials)
-static int pick_nb_bwd(int B) { const int nb = pick_nb(B); return nb > 2 ? 2 : (B <= 2 * nsd_num_cus() ? 1 : nb); }
-
-// number of workgroups (== slabs written) the backward kernel uses for batch B
-int nsd_lstm2_bwd_grid(int B) {
-    const int nb = pick_nb_bwd(B);
-    const int ngrp = (B + nb - 1) / nb;
-    const int cus = nsd_num_cus();
-    return ngrp < cus ? ngrp : cus;
+// ---- the launch plan: which kernel serves a batch, on how many workgroups, and whether the forward leaves the attention records open.
+// One value for the forward, the backward and the workspace's slab count, for one model (M = 1) and for the model-batched launches
+// (nsd_multi.h: B = the trials of ONE model; the bands are those of the M*B trials of the launch, the grid is partitioned by model).
+struct Launch48 {                  // what the rule reads of a launch (all false: the slab count, and the first-generation backward)
+    bool head_train, infer_tail;   // forward: fused training head / inference tail
+    bool fwd_x4_ok, bwd_x4_ok;     // inside the four-trial kernels' domains (nsd_lstm2_fwd48x4_ok / nsd_lstm2_bwd48x4_ok)
+    bool da0_out;                  // backward: input gradient requested
+};
+struct Plan48 {
+    int fwd_nb, bwd_nb;            // trials per workgroup: 1, 2 (nsd_lstm2_fwd48.hip / _bwd48.hip) or 4 (nsd_lstm2_fwd48x4.hip / _bwd48x4.hip)
+    int fwd_groups, bwd_groups;    // workgroups per model (M * groups <= #CUs: one workgroup per CU, batches loop); bwd_groups == slabs per model
+    int defer_att;                 // the fused head leaves the per-step part of the attention's backward to the four-trial backward kernel
+};
+// Forward:  one trial per workgroup while that leaves CUs idle or barely covers them -- latency is all that counts -- and for inference
+//           (the pooling / head tail is built for one trial); two in lock step above one trial per CU (they beat two one after the other,
+//           204 vs 224 us at 320 trials); FOUR with the gate products on the matrix pipe for training batches from X4_MIN_B trials on
+//           (a four-trial step costs about what 2.3 one-trial steps cost).
+// Backward: at most two trials per workgroup outside the four-trial kernel (register budget).  Up to two trials per CU the ONE-trial
+//           instantiation walks them one after the other: it is the faster one per trial (split-bf16 weight gradients, prepared factors,
+//           four-step hand-off -- 2 x 127 us against 268-271 us of the two-trial instantiation at 320 .. 512 trials).  The four-trial
+//           kernel and the input gradient (only the one-trial kernel writes da0; any batch: it loops) change the kernel, never the
+//           grid: the workspace holds one slab per workgroup and is sized without knowing either.
+// The diagnostic twin's force values (0 in the product library) replace the batch-size conditions, never the domain checks.
+static Plan48 plan48(int B, int M, const Launch48 &f) {
+    const int band = pick_nb(M * B), cap = nsd_num_cus() / M;
+    const bool big = M * B >= X4_MIN_B;
+    const int force_f = nsd_diag_forced_fwd48(), force_b = nsd_diag_forced_bwd48();
+    const auto groups = [&](int nb) { const int g = (B + nb - 1) / nb; return g < cap ? g : (cap > 0 ? cap : 1); };
+    Plan48 p;
+    const int slab_nb = band <= 2 ? 1 : 2;
+    const bool bwd_x4 = f.bwd_x4_ok && !f.da0_out && (force_b ? force_b == 4 : big);
+    p.bwd_nb = bwd_x4 ? 4 : f.da0_out ? 1 : slab_nb;
+    p.bwd_groups = groups(slab_nb);
+    const bool fwd_x4 = f.fwd_x4_ok && (force_f ? force_f == 4 : big);
+    const bool two = !f.infer_tail && (force_f ? force_f == 2 : band >= 2);
+    p.fwd_nb = fwd_x4 ? 4 : two ? 2 : 1;
+    p.fwd_groups = groups(p.fwd_nb);
+    p.defer_att = fwd_x4 && f.head_train && p.bwd_nb == 4;
+    return p;
+}
+static Launch48 launch_facts(const Lstm2FwdArgs &a) {
+    Launch48 f = {};
+    f.head_train = a.head_train != 0;
+    f.infer_tail = a.logits_out != nullptr;
+    f.fwd_x4_ok = nsd_lstm2_fwd48x4_ok(a);
+    // what the forward knows of its backward: the backward kernel's domain is the forward's plus the packed attention records, which the
+    // fused head writes.  (It cannot know of a dx request: nsd_lstm_bwd closes the records then, nsd_att_close_launch.)
+    f.bwd_x4_ok = f.fwd_x4_ok && a.adpack != nullptr;
+    return f;
+}
+static Launch48 launch_facts(const Lstm2BwdArgs &a) {
+    Launch48 f = {};
+    f.bwd_x4_ok = nsd_lstm2_bwd48x4_ok(a);
+    f.da0_out = a.da0_out != nullptr;
+    return f;
 }
 
+// workgroups (== slabs written) per model of the backward launch for M models of B trials each
+int nsd_lstm2_bwd_groups(int B, int M) { return plan48(B, M, Launch48{}).bwd_groups; }
+
 int nsd_lstm2_fwd_launch(const Lstm2FwdArgs &a, int H, hipStream_t st) {
-    const int nb = pick_nb(a.B);
-    const int ngrp = (a.B + nb - 1) / nb;
-    const int cap = 2 * nsd_num_cus();
-    const int grid = ngrp < cap ? ngrp : cap;
-    if (grid <= 0) return NSD_OK;
+    if (a.B <= 0) return NSD_OK;
+    if (H == 48) {
+        const Plan48 p = plan48(a.B, 1, launch_facts(a));
+#if NSD_DIAG
+        if (nsd_diag_forced_fwd48() == 8 && nsd_lstm2_fwd48w_ok(a)) return nsd_lstm2_fwd48w_launch(a, p.fwd_groups, st);      // experiment (nsd_lstm2_fwd48w.hip)
+#endif
+        Lstm2FwdArgs ap = a;
+        ap.defer_att = p.defer_att;
+        if (p.fwd_nb == 4) return nsd_lstm2_fwd48x4_launch(ap, p.fwd_groups, st);
+        return nsd_lstm2_fwd48_launch(ap, p.fwd_nb, p.fwd_groups, st);
+    }
+    // first-generation kernels: up to two workgroups per CU
+    const int nb = pick_nb(a.B), ngrp = (a.B + nb - 1) / nb, max_grid = 2 * nsd_num_cus();
+    const int grid = ngrp < max_grid ? ngrp : max_grid;
     switch (H) {
     case 32: launch_fwd_h<32>(a, nb, grid, st); break;
-    case 48: {   // role-split kernels, one workgroup per CU, batches loop:
-                 //  * one trial per workgroup (nsd_lstm2_fwd48.hip) while that leaves CUs idle or barely covers them -- latency is all
-                 //    that counts -- and for inference (the pooling / head tail is built for one trial);
-                 //  * FOUR trials per workgroup with the gate products on the matrix pipe (nsd_lstm2_fwd48x4.hip) for training batches
-                 //    from X4_MIN_B trials on (three or more trials per CU: a four-trial step costs about what 2.3 one-trial steps cost);
-                 //  * two trials per workgroup in lock step (nsd_lstm2_fwd48.hip) where the four-trial kernel does not apply (residual
-                 //    extension) and every CU has at least two trials.
-        const int cus = nsd_num_cus();
-        const int force_nb = nsd_diag_forced_fwd48();           // 0 in the product library (diagnostic build: nsd_diag_force_fwd48)
-        if (force_nb == 8 && nsd_lstm2_fwd48w_ok(a)) return nsd_lstm2_fwd48w_launch(a, a.B < cus ? a.B : cus, st);      // experiment (nsd_lstm2_fwd48w.hip)
-        const bool x4 = nsd_lstm2_fwd48x4_ok(a) && (force_nb ? force_nb == 4 : a.B >= X4_MIN_B);
-        if (x4) {
-            // The backward pass of the same batch takes lstm2_bwd48x4_kernel under the same rule (nsd_lstm2_bwd_launch below; its domain
-            // contains the forward kernel's): the fused head then leaves the per-step part of the attention's backward to it
-            const int force_b = nsd_diag_forced_bwd48();
-            Lstm2FwdArgs a4 = a;
-            a4.defer_att = a.head_train && (force_b ? force_b == 4 : a.B >= X4_MIN_B);
-            const int ngrp4 = (a.B + 3) / 4;
-            return nsd_lstm2_fwd48x4_launch(a4, ngrp4 < cus ? ngrp4 : cus, st);
-        }
-        const bool two = force_nb ? force_nb == 2 : a.B > cus;        // (more than one trial per CU: two in lock step beat two one after the other, 204 vs 224 us at 320 trials)
-        if (two && !a.logits_out) { const int ngrp2 = (a.B + 1) / 2; return nsd_lstm2_fwd48_launch(a, 2, ngrp2 < cus ? ngrp2 : cus, st); }
-        return nsd_lstm2_fwd48_launch(a, 1, a.B < cus ? a.B : cus, st);
-    }
     case 64: launch_fwd_h<64>(a, nb, grid, st); break;
     default: nsd_set_error("lstm2 fwd: unsupported H=%d", H); return NSD_E_INVALID;
     }
@@ -596,51 +630,36 @@ int nsd_lstm2_fwd_launch(const Lstm2FwdArgs &a, int H, hipStream_t st) {
 }
 
 int nsd_lstm2_bwd_launch(const Lstm2BwdArgs &a, int H, hipStream_t st) {
-    const int nb = pick_nb_bwd(a.B);
-    const int grid = nsd_lstm2_bwd_grid(a.B);
-    if (grid <= 0) return NSD_OK;
+    if (a.B <= 0) return NSD_OK;
+    // (the first-generation kernels take the plan's one / two trials per workgroup and its grid: the slab count does not know H)
+    const Plan48 p = plan48(a.B, 1, H == 48 ? launch_facts(a) : Launch48{});
     switch (H) {
-    case 32: launch_bwd_h<32>(a, nb, grid, st); break;
-    case 48: {   // role-split kernels: four trials per workgroup on the matrix pipe (nsd_lstm2_bwd48x4.hip) from X4_MIN_B trials on, else
-                 // one / two trials per workgroup (nsd_lstm2_bwd48.hip).  Same grid either way: the workspace holds one slab per workgroup.
-        const int force_nb = nsd_diag_forced_bwd48();
-        if (a.da0_out) return nsd_lstm2_bwd48_launch(a, 1, grid, st);      // input gradient requested: the one-trial kernel writes da0 (any batch: it loops)
-        if (nsd_lstm2_bwd48x4_ok(a) && (force_nb ? force_nb == 4 : a.B >= X4_MIN_B)) return nsd_lstm2_bwd48x4_launch(a, grid, st);
-        return nsd_lstm2_bwd48_launch(a, nb, grid, st);
-    }
-    case 64: launch_bwd_h<64>(a, nb, grid, st); break;
+    case 32: launch_bwd_h<32>(a, p.bwd_nb, p.bwd_groups, st); break;
+    case 48:
+        if (p.bwd_nb == 4) return nsd_lstm2_bwd48x4_launch(a, p.bwd_groups, st);
+        return nsd_lstm2_bwd48_launch(a, p.bwd_nb, p.bwd_groups, st);
+    case 64: launch_bwd_h<64>(a, p.bwd_nb, p.bwd_groups, st); break;
     default: nsd_set_error("lstm2 bwd: unsupported H=%d", H); return NSD_E_INVALID;
     }
     NSD_CHECK_LAUNCH("lstm2_bwd");
     return NSD_OK;
 }
 
-// ---- model-batched H = 48 launches (nsd_multi.h): the rules above applied to the M*B trials of the launch, the grid partitioned by
-// model (G workgroups per model, M*G <= #CUs).  a.B is the trials of ONE model.
-static int per_model(int groups, int M) { const int cap = nsd_num_cus() / M; return groups < cap ? groups : (cap > 0 ? cap : 1); }
-
-int nsd_lstm2_multi_bwd_groups(int M, int B) {
-    const int nb = pick_nb_bwd(M * B);                 // the single-model rule on the M*B trials: one trial per workgroup up to 2 x #CUs
-    return per_model((B + nb - 1) / nb, M);
-}
-
+// ---- model-batched H = 48 launches (nsd_multi.h): a.B is the trials of ONE model, as the kernels' domain checks see it
 int nsd_lstm2_multi_fwd_launch(const Lstm2FwdArgs &a, ModelSplit s, int M, hipStream_t st) {
-    const int total = M * a.B, cus = nsd_num_cus();
     if (a.B <= 0) return NSD_OK;
-    if (nsd_lstm2_fwd48x4_ok(a) && total >= X4_MIN_B) {
-        Lstm2FwdArgs a4 = a;
-        a4.defer_att = a.head_train;                     // the backward of this batch is the four-trial kernel (nsd_lstm2_multi_bwd_launch)
-        s.G = per_model((a.B + 3) / 4, M);
-        return nsd_lstm2_fwd48x4_multi_launch(a4, s, M, st);
-    }
-    if (total > cus && !a.logits_out) { s.G = per_model((a.B + 1) / 2, M); return nsd_lstm2_fwd48_multi_launch(a, s, M, 2, st); }
-    s.G = per_model(a.B, M);
-    return nsd_lstm2_fwd48_multi_launch(a, s, M, 1, st);
+    const Plan48 p = plan48(a.B, M, launch_facts(a));
+    Lstm2FwdArgs ap = a;
+    ap.defer_att = p.defer_att;
+    s.G = p.fwd_groups;
+    if (p.fwd_nb == 4) return nsd_lstm2_fwd48x4_multi_launch(ap, s, M, st);
+    return nsd_lstm2_fwd48_multi_launch(ap, s, M, p.fwd_nb, st);
 }
 
 int nsd_lstm2_multi_bwd_launch(const Lstm2BwdArgs &a, ModelSplit s, int M, hipStream_t st) {
     if (a.B <= 0) return NSD_OK;
-    s.G = nsd_lstm2_multi_bwd_groups(M, a.B);
-    if (nsd_lstm2_bwd48x4_ok(a) && M * a.B >= X4_MIN_B) return nsd_lstm2_bwd48x4_multi_launch(a, s, M, st);
-    return nsd_lstm2_bwd48_multi_launch(a, s, M, pick_nb_bwd(M * a.B), st);
+    const Plan48 p = plan48(a.B, M, launch_facts(a));
+    s.G = p.bwd_groups;
+    if (p.bwd_nb == 4) return nsd_lstm2_bwd48x4_multi_launch(a, s, M, st);
+    return nsd_lstm2_bwd48_multi_launch(a, s, M, p.bwd_nb, st);
 }

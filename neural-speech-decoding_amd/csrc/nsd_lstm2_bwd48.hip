@@ -1005,30 +1005,33 @@ __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_multi_kernel(Lstm2BwdArg
 
 }  // namespace
 
+// The instantiation that serves nb trials per workgroup, or 0 with the error set.  The one-trial instantiation's dW waves address the saved
+// rows through buffer descriptors with 32-bit offsets (0x80000000 = "switched off"): a batch whose [B][T][H] arrays reach 2 GB takes the
+// two-trial instantiation (64-bit addresses; any grid).  Only the one-trial instantiation writes the input gradient.
+static int bwd48_domain(const Lstm2BwdArgs &a, int nb, bool models, const char *who) {
+    if (nb == 1 && (long)a.B * a.T * H * 4 >= 0x7fffffffL) nb = 2;
+    if (a.da0_out && models) { nsd_set_error("%s: no input gradient on the model-batched path", who); return 0; }
+    if (a.da0_out && nb != 1) { nsd_set_error("%s: the input gradient needs the one-trial instantiation (B * T * H * 4 < 2 GB)", who); return 0; }
+    if (nb != 1 && nb != 2) { nsd_set_error("%s: NB=%d not built (register / LDS budget)", who, nb); return 0; }
+    return nb;
+}
+
 #if !NSD_MULTI_TU
 int nsd_lstm2_bwd48_launch(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t st) {
-    // the one-trial instantiation's dW waves address the saved rows through buffer descriptors with 32-bit offsets (0x80000000 = "switched
-    // off"): a batch whose [B][T][H] arrays reach 2 GB takes the two-trial instantiation (64-bit addresses; any grid)
-    if (nb == 1 && (long)a.B * a.T * H * 4 >= 0x7fffffffL) nb = 2;
-    if (a.da0_out && nb != 1) { nsd_set_error("lstm2_bwd48: the input gradient needs the one-trial instantiation (B * T * H * 4 < 2 GB)"); return NSD_E_INVALID; }
-    switch (nb) {
-    case 1: hipLaunchKernelGGL((lstm2_bwd48_kernel<1>), dim3(grid), dim3(NTHREADS), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((lstm2_bwd48_kernel<2>), dim3(grid), dim3(NTHREADS), 0, st, a); break;
-    default: nsd_set_error("lstm2_bwd48: NB=%d not built (register / LDS budget)", nb); return NSD_E_INVALID;
-    }
+    nb = bwd48_domain(a, nb, false, "lstm2_bwd48");
+    if (nb == 0) return NSD_E_INVALID;
+    if (nb == 1) hipLaunchKernelGGL((lstm2_bwd48_kernel<1>), dim3(grid), dim3(NTHREADS), 0, st, a);
+    else         hipLaunchKernelGGL((lstm2_bwd48_kernel<2>), dim3(grid), dim3(NTHREADS), 0, st, a);
     NSD_CHECK_LAUNCH("lstm2_bwd48");
     return NSD_OK;
 }
 
 #else
 int nsd_lstm2_bwd48_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st) {
-    if (nb == 1 && (long)a.B * a.T * H * 4 >= 0x7fffffffL) nb = 2;        // (as nsd_lstm2_bwd48_launch: 32-bit offsets of the one-trial dW waves)
-    if (a.da0_out) { nsd_set_error("lstm2_bwd48 (models): no input gradient on the model-batched path"); return NSD_E_INVALID; }
-    switch (nb) {
-    case 1: hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<1>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s); break;
-    case 2: hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<2>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s); break;
-    default: nsd_set_error("lstm2_bwd48 (models): NB=%d not built (register / LDS budget)", nb); return NSD_E_INVALID;
-    }
+    nb = bwd48_domain(a, nb, true, "lstm2_bwd48 (models)");
+    if (nb == 0) return NSD_E_INVALID;
+    if (nb == 1) hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<1>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s);
+    else         hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<2>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s);
     NSD_CHECK_LAUNCH("lstm2_bwd48_multi");
     return NSD_OK;
 }

@@ -771,10 +771,15 @@ __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_kernel(Lstm2BwdArgs a) {
 
 }  // namespace
 
+static int bwd48x4_domain(const Lstm2BwdArgs &a, const char *who) {
+    if (nsd_lstm2_bwd48x4_ok(a)) return NSD_OK;
+    nsd_set_error("%s: launch outside the kernel's domain", who);
+    return NSD_E_INVALID;
+}
+
 #if NSD_MULTI_TU
-bool nsd_lstm2_bwd48x4_ok(const Lstm2BwdArgs &a);
 int nsd_lstm2_bwd48x4_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, hipStream_t st) {
-    if (!nsd_lstm2_bwd48x4_ok(a)) { nsd_set_error("lstm2_bwd48x4 (models): launch outside the kernel's domain"); return NSD_E_INVALID; }
+    if (const int rc = bwd48x4_domain(a, "lstm2_bwd48x4 (models)")) return rc;
     hipLaunchKernelGGL(lstm2_bwd48x4_multi_kernel, dim3(M * s.G), dim3(NTHR), 0, st, a, s);
     NSD_CHECK_LAUNCH("lstm2_bwd48x4_multi");
     return NSD_OK;
@@ -785,7 +790,7 @@ bool nsd_lstm2_bwd48x4_ok(const Lstm2BwdArgs &a) {
 }
 
 int nsd_lstm2_bwd48x4_launch(const Lstm2BwdArgs &a, int grid, hipStream_t st) {
-    if (!nsd_lstm2_bwd48x4_ok(a)) { nsd_set_error("lstm2_bwd48x4: launch outside the kernel's domain"); return NSD_E_INVALID; }
+    if (const int rc = bwd48x4_domain(a, "lstm2_bwd48x4")) return rc;
     hipLaunchKernelGGL(lstm2_bwd48x4_kernel, dim3(grid), dim3(NTHR), 0, st, a);
     NSD_CHECK_LAUNCH("lstm2_bwd48x4");
     return NSD_OK;

@@ -964,18 +964,21 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in
 
 }  // namespace
 
+// one trial per workgroup (latency: batches up to one trial per CU, and inference), or two trials per workgroup advancing in
+// lock step (throughput: larger training batches -- two independent dependent chains per wave fill each other's issue gaps)
+static int fwd48_domain(const Lstm2FwdArgs &a, int nb, const char *who) {
+    if (nb != 1 && nb != 2) { nsd_set_error("%s: NB=%d not built", who, nb); return NSD_E_INVALID; }
+    if (nb == 2 && a.logits_out) { nsd_set_error("%s: the inference tail runs one trial per workgroup", who); return NSD_E_INVALID; }
+    if (a.head_train && (!nsd_lstm2_fwd48_head_train_fits(a.T, a.F, a.K) || !(a.top || a.hseq1) || a.logits_out)) {
+        nsd_set_error("%s: fused train head needs T<=%d, F<=64, K<=%d and the training workspace", who, TT_TMAX, TT_KMAX);
+        return NSD_E_INVALID;
+    }
+    return NSD_OK;
+}
+
 #if !NSD_MULTI_TU
 int nsd_lstm2_fwd48_launch(const Lstm2FwdArgs &a, int nb, int grid, hipStream_t st) {
-    // one trial per workgroup (latency: batches up to one trial per CU, and inference), or two trials per workgroup advancing in
-    // lock step (throughput: larger training batches -- two independent dependent chains per wave fill each other's issue gaps)
-    if (nb != 1 && nb != 2) { nsd_set_error("lstm2_fwd48: NB=%d not built", nb); return NSD_E_INVALID; }
-    if (nb == 2 && a.logits_out) { nsd_set_error("lstm2_fwd48: the inference tail runs one trial per workgroup"); return NSD_E_INVALID; }
-    if (a.head_train) {
-        if (!nsd_lstm2_fwd48_head_train_fits(a.T, a.F, a.K) || !(a.top || a.hseq1) || a.logits_out) {
-            nsd_set_error("lstm2_fwd48: fused train head needs T<=%d, F<=64, K<=%d and the training workspace", TT_TMAX, TT_KMAX);
-            return NSD_E_INVALID;
-        }
-    }
+    if (const int rc = fwd48_domain(a, nb, "lstm2_fwd48")) return rc;
     if (nb == 2) hipLaunchKernelGGL((lstm2_fwd48_kernel<2>), dim3(grid), dim3(NT), 0, st, a);
     else         hipLaunchKernelGGL((lstm2_fwd48_kernel<1>), dim3(grid), dim3(NT), 0, st, a);
     NSD_CHECK_LAUNCH("lstm2_fwd48");
@@ -986,12 +989,7 @@ bool nsd_lstm2_fwd48_head_train_fits(int T, int F, int K) { return T <= TT_TMAX 
 
 #else
 int nsd_lstm2_fwd48_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st) {
-    if (nb != 1 && nb != 2) { nsd_set_error("lstm2_fwd48 (models): NB=%d not built", nb); return NSD_E_INVALID; }
-    if (nb == 2 && a.logits_out) { nsd_set_error("lstm2_fwd48 (models): the inference tail runs one trial per workgroup"); return NSD_E_INVALID; }
-    if (a.head_train && (!nsd_lstm2_fwd48_head_train_fits(a.T, a.F, a.K) || !(a.top || a.hseq1) || a.logits_out)) {
-        nsd_set_error("lstm2_fwd48 (models): fused train head needs T<=%d, F<=64, K<=%d and the training workspace", TT_TMAX, TT_KMAX);
-        return NSD_E_INVALID;
-    }
+    if (const int rc = fwd48_domain(a, nb, "lstm2_fwd48 (models)")) return rc;
     if (nb == 2) hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<2>), dim3(M * s.G), dim3(NT), 0, st, a, s);
     else         hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<1>), dim3(M * s.G), dim3(NT), 0, st, a, s);
     NSD_CHECK_LAUNCH("lstm2_fwd48_multi");

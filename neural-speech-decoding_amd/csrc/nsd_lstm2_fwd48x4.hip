@@ -866,10 +866,15 @@ __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_kernel(Lstm2FwdArgs a) {
 
 }  // namespace
 
+static int fwd48x4_domain(const Lstm2FwdArgs &a, const char *who) {
+    if (nsd_lstm2_fwd48x4_ok(a)) return NSD_OK;
+    nsd_set_error("%s: launch outside the kernel's domain", who);
+    return NSD_E_INVALID;
+}
+
 #if NSD_MULTI_TU
-bool nsd_lstm2_fwd48x4_ok(const Lstm2FwdArgs &a);
 int nsd_lstm2_fwd48x4_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int M, hipStream_t st) {
-    if (!nsd_lstm2_fwd48x4_ok(a)) { nsd_set_error("lstm2_fwd48x4 (models): launch outside the kernel's domain"); return NSD_E_INVALID; }
+    if (const int rc = fwd48x4_domain(a, "lstm2_fwd48x4 (models)")) return rc;
     hipLaunchKernelGGL(lstm2_fwd48x4_multi_kernel, dim3(M * s.G), dim3(NTHR), 0, st, a, s);
     NSD_CHECK_LAUNCH("lstm2_fwd48x4_multi");
     return NSD_OK;
@@ -884,7 +889,7 @@ bool nsd_lstm2_fwd48x4_ok(const Lstm2FwdArgs &a) {
 }
 
 int nsd_lstm2_fwd48x4_launch(const Lstm2FwdArgs &a, int grid, hipStream_t st) {
-    if (!nsd_lstm2_fwd48x4_ok(a)) { nsd_set_error("lstm2_fwd48x4: launch outside the kernel's domain"); return NSD_E_INVALID; }
+    if (const int rc = fwd48x4_domain(a, "lstm2_fwd48x4")) return rc;
     hipLaunchKernelGGL(lstm2_fwd48x4_kernel, dim3(grid), dim3(NTHR), 0, st, a);
     NSD_CHECK_LAUNCH("lstm2_fwd48x4");
     return NSD_OK;

@@ -86,10 +86,9 @@ int nsd_lstm2_fwd48_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int
 int nsd_lstm2_fwd48x4_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int M, hipStream_t st);
 int nsd_lstm2_bwd48_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st);
 int nsd_lstm2_bwd48x4_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, hipStream_t st);
-// dispatch by the rules of nsd_lstm2_fwd_launch / nsd_lstm2_bwd_launch applied to the M*B trials of the launch (nsd_lstm2.hip)
+// dispatch by the launch plan of the M*B trials of the launch (plan48, nsd_lstm2.hip)
 int nsd_lstm2_multi_fwd_launch(const Lstm2FwdArgs &a, ModelSplit s, int M, hipStream_t st);
 int nsd_lstm2_multi_bwd_launch(const Lstm2BwdArgs &a, ModelSplit s, int M, hipStream_t st);
-int nsd_lstm2_multi_bwd_groups(int M, int B);     // workgroups (= slabs) per model of the backward launch
 // reductions over model m's G slabs and B head slabs into grads + m*P (and the Adam update of p / m / v + m*P): one launch for all models
 int nsd_multi_grad_reduce_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
                                  int M, float *grads, hipStream_t st);

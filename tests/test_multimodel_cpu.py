@@ -65,6 +65,33 @@ def test_workspace_covers_the_single_model_workspace_of_all_trials(L, M, B, T):
     assert lib.nsd_multi_workspace_bytes(C.byref(_d(L, B=B, T=T)), 0, None) < 0
 
 
+def test_slab_counts_follow_the_launch_plan(L):
+    """n_slabs of nsd_workspace_bytes (M = 1) and nsd_multi_workspace_bytes (M = 2 .. 32) against an independent restatement of the
+    backward's grid rule (plan48, csrc/nsd_lstm2.hip): one trial per workgroup up to 512 trials in the launch, two beyond; one
+    workgroup per CU, the CUs partitioned by model; never fewer slabs than the single-model workspace of all M*B trials.  Without a
+    device the library assumes the MI355X's 256 CUs, as this restatement does."""
+    import torch
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the restatement is written for 256 CUs")
+    lib = L.lib()
+
+    def single(B):
+        nb = 1 if B <= 512 else 2
+        return min(-(-B // nb), 256)
+
+    def multi(M, B):
+        nb = 1 if M * B <= 512 else 2
+        return max(M * min(-(-B // nb), max(256 // M, 1)), single(M * B))
+
+    w = L.WsLayout()
+    for B in list(range(1, 80)) + [127, 128, 129, 255, 256, 257, 300, 511, 512, 513, 575, 1024, 1025, 2100]:
+        assert lib.nsd_workspace_bytes(C.byref(_d(L, B=B)), C.byref(w)) > 0
+        assert w.n_slabs == single(B), B
+        for M in range(2, 33):
+            assert lib.nsd_multi_workspace_bytes(C.byref(_d(L, B=B)), M, C.byref(w)) > 0
+            assert w.n_slabs == multi(M, B), (M, B)
+
+
 def test_refusals_before_any_launch(L):
     """Every refusal returns its code before a launch: the pointers below are never dereferenced (no GPU here)."""
     lib = L.lib()
