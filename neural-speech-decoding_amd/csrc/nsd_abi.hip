@@ -284,12 +284,7 @@ static bool fused_train_shape(const nsd_dims *d) {
 }
 static int make_rng(const nsd_rng *r, RngArgs *out) {
     if (!r) { nsd_set_error("rng: null pointer"); return NSD_E_INVALID; }
-    if (!(r->p_lstm >= 0.f && r->p_lstm < 1.f) || !(r->p_head >= 0.f && r->p_head < 1.f)) { nsd_set_error("rng: p out of [0,1)"); return NSD_E_INVALID; }
-    out->seed = r->seed; out->base = r->base_stream;
-    out->thr_lstm = nsd_drop_threshold(r->p_lstm); out->thr_head = nsd_drop_threshold(r->p_head);
-    out->keep_lstm = 1.0f / (1.0f - r->p_lstm); out->keep_head = 1.0f / (1.0f - r->p_head);
-    out->on = 1;
-    return NSD_OK;
+    return nsd_rng_args(r, out);
 }
 
 int64_t nsd_infer_scratch_bytes(const nsd_dims *d) {

@@ -152,6 +152,15 @@ static inline uint32_t nsd_drop_threshold(float p) {
     if (t > 4294967295.0) t = 4294967295.0;
     return (uint32_t)t;
 }
+// nsd_rng (nsd.h) -> RngArgs with the streams on.  r is not null: whether a null nsd_rng means "off" or is an error is the caller's decision
+static inline int nsd_rng_args(const nsd_rng *r, RngArgs *out) {
+    if (!(r->p_lstm >= 0.f && r->p_lstm < 1.f) || !(r->p_head >= 0.f && r->p_head < 1.f)) { nsd_set_error("rng: p out of [0,1)"); return NSD_E_INVALID; }
+    out->seed = r->seed; out->base = r->base_stream;
+    out->thr_lstm = nsd_drop_threshold(r->p_lstm); out->thr_head = nsd_drop_threshold(r->p_head);
+    out->keep_lstm = 1.0f / (1.0f - r->p_lstm); out->keep_head = 1.0f / (1.0f - r->p_head);
+    out->on = 1;
+    return NSD_OK;
+}
 
 // counter-based random stream shared bit-for-bit with oracle/nsd_oracle.c (nsd_oracle_rand_u32)
 __host__ __device__ __forceinline__ uint32_t nsd_mix32(uint32_t x) {

@@ -36,15 +36,7 @@ __device__ __forceinline__ void load_bf16_vals(const bf16_t *p, float (&v)[VPL])
 }
 __device__ __forceinline__ float lane_bcast(const float v, const int src) { return __shfl(v, src, 64); }
 
-// What one launch of the head does (MODE of nsd_head_tm_body.h):
-//   HEAD_EVAL    eval slope, no dropout: logits (+ probs)
-//   HEAD_TRAIN   train-mode streams, logits, mean CE and the dense backward from dlogits = scale (p - onehot)   (nsd_seq_train_fwd)
-//   HEAD_LOGITS  train-mode streams, logits only: no labels, no backward                               (nsd_seq_train_fwd_logits)
-//   HEAD_DLOG    train-mode streams, the dense backward from the caller's dlogits [B][K] (no logits written)      (nsd_seq_head_bwd)
-// Everything up to the logits is the same code in every mode, so HEAD_LOGITS's logits are HEAD_TRAIN's bit for bit, and HEAD_DLOG
-// rebuilds exactly the activations HEAD_TRAIN differentiates.  HEAD_EVAL / HEAD_TRAIN are head_tm_kernel<VPL, false / true> as
-// before; the other two are kernels of their own.
-enum { HEAD_EVAL = 0, HEAD_TRAIN = 1, HEAD_LOGITS = 2, HEAD_DLOG = 3 };
+// (the modes HEAD_EVAL / HEAD_TRAIN / HEAD_LOGITS / HEAD_DLOG: nsd_seq.h)
 
 template <int VPL, bool TRAIN_>
 __global__ __launch_bounds__(256) void head_tm_kernel(const HeadTmArgs a) {
@@ -120,55 +112,36 @@ __global__ __launch_bounds__(256) void head_tm_grads_sum_kernel(const float *par
     g_attn_b[0] = s;
 }
 
+// the four kernels of a sequence width share one grid
 template <int VPL>
-int launch_vpl(const HeadTmArgs &a, hipStream_t st) {
+int launch_vpl(const HeadTmArgs &a, int mode, const float *dlogits, hipStream_t st) {
     // the passes over the sequence are latency-bound, one wave per trial: with few trials (cfg5: 512 per GPU) four waves per workgroup
     // put them on half of the CUs -- spread the waves over as many CUs as there are trials
     const int cus = nsd_num_cus();
     const int wpw = a.B >= 4 * cus ? 4 : (a.B >= 2 * cus ? 2 : 1);
-    const dim3 grid((a.B + wpw - 1) / wpw);
-    if (a.train) hipLaunchKernelGGL((head_tm_kernel<VPL, true>), grid, dim3(64 * wpw), 0, st, a);
-    else         hipLaunchKernelGGL((head_tm_kernel<VPL, false>), grid, dim3(64 * wpw), 0, st, a);
-    NSD_CHECK_LAUNCH("head_tm_kernel");
-    return NSD_OK;
-}
-
-// the two launches of the any-loss sequence (nsd_seq_train_fwd_logits, nsd_seq_head_bwd): same grid as launch_vpl
-template <int VPL>
-int launch_vpl_ext(const HeadTmArgs &a, const float *dlogits, hipStream_t st) {
-    const int cus = nsd_num_cus();
-    const int wpw = a.B >= 4 * cus ? 4 : (a.B >= 2 * cus ? 2 : 1);
-    const dim3 grid((a.B + wpw - 1) / wpw);
-    if (dlogits) hipLaunchKernelGGL((head_tm_dlog_kernel<VPL>), grid, dim3(64 * wpw), 0, st, a, dlogits);
-    else         hipLaunchKernelGGL((head_tm_logits_kernel<VPL>), grid, dim3(64 * wpw), 0, st, a);
-    NSD_CHECK_LAUNCH(dlogits ? "head_tm_dlog_kernel" : "head_tm_logits_kernel");
+    const dim3 grid((a.B + wpw - 1) / wpw), wg(64 * wpw);
+    switch (mode) {
+    case HEAD_EVAL: hipLaunchKernelGGL((head_tm_kernel<VPL, false>), grid, wg, 0, st, a); break;
+    case HEAD_TRAIN: hipLaunchKernelGGL((head_tm_kernel<VPL, true>), grid, wg, 0, st, a); break;
+    case HEAD_LOGITS: hipLaunchKernelGGL((head_tm_logits_kernel<VPL>), grid, wg, 0, st, a); break;
+    case HEAD_DLOG: hipLaunchKernelGGL((head_tm_dlog_kernel<VPL>), grid, wg, 0, st, a, dlogits); break;
+    default: nsd_set_error("head_tm: unknown mode %d", mode); return NSD_E_INVALID;
+    }
+    NSD_CHECK_LAUNCH(mode == HEAD_DLOG ? "head_tm_dlog_kernel" : mode == HEAD_LOGITS ? "head_tm_logits_kernel" : "head_tm_kernel");
     return NSD_OK;
 }
 
 }  // namespace
 
-int nsd_head_tm_ext_launch(const HeadTmArgs &a, const float *dlogits, hipStream_t st) {
+int nsd_head_tm_launch(const HeadTmArgs &a, int mode, const float *dlogits, hipStream_t st) {
     if (a.B < 1) return NSD_OK;
     if (a.F > 64 || a.K > 64) { nsd_set_error("head_tm: F=%d K=%d exceed 64 (one lane per unit / class)", a.F, a.K); return NSD_E_INVALID; }
     switch (a.DH) {
-    case 64: return launch_vpl_ext<1>(a, dlogits, st);
-    case 128: return launch_vpl_ext<2>(a, dlogits, st);
-    case 256: return launch_vpl_ext<4>(a, dlogits, st);
-    case 512: return launch_vpl_ext<8>(a, dlogits, st);
-    case 1024: return launch_vpl_ext<16>(a, dlogits, st);
-    default: nsd_set_error("head_tm: sequence width %d not covered (64, 128, 256, 512, 1024)", a.DH); return NSD_E_INVALID;
-    }
-}
-
-int nsd_head_tm_launch(const HeadTmArgs &a, hipStream_t st) {
-    if (a.B < 1) return NSD_OK;
-    if (a.F > 64 || a.K > 64) { nsd_set_error("head_tm: F=%d K=%d exceed 64 (one lane per unit / class)", a.F, a.K); return NSD_E_INVALID; }
-    switch (a.DH) {
-    case 64: return launch_vpl<1>(a, st);
-    case 128: return launch_vpl<2>(a, st);
-    case 256: return launch_vpl<4>(a, st);
-    case 512: return launch_vpl<8>(a, st);
-    case 1024: return launch_vpl<16>(a, st);
+    case 64: return launch_vpl<1>(a, mode, dlogits, st);
+    case 128: return launch_vpl<2>(a, mode, dlogits, st);
+    case 256: return launch_vpl<4>(a, mode, dlogits, st);
+    case 512: return launch_vpl<8>(a, mode, dlogits, st);
+    case 1024: return launch_vpl<16>(a, mode, dlogits, st);
     default: nsd_set_error("head_tm: sequence width %d not covered (64, 128, 256, 512, 1024)", a.DH); return NSD_E_INVALID;
     }
 }

@@ -194,10 +194,16 @@ struct HeadTmArgs {
     const int *status;                       // status words of the evaluation (sticky word NSD_SEQ_HEADER_WORDS before): a scan time-out
                                              // poisons logits / probs / loss with NaN -- nothing downstream can mistake garbage for a result
 };
-int nsd_head_tm_launch(const HeadTmArgs &a, hipStream_t st);
-// the any-loss sequence: dlogits == null -> logits only with the train-mode streams (a.rng / explicit tensors; nothing of the
-// backward written); dlogits [B][K] fp32 -> the dense backward from it (alpha, dscore, pooled, dpooled, hb rows; no logits)
-int nsd_head_tm_ext_launch(const HeadTmArgs &a, const float *dlogits, hipStream_t st);
+// What one launch of the head does (MODE of nsd_head_tm_body.h):
+//   HEAD_EVAL    eval slope, no dropout: logits (+ probs)
+//   HEAD_TRAIN   train-mode streams, logits, mean CE and the dense backward from dlogits = scale (p - onehot)   (nsd_seq_train_fwd)
+//   HEAD_LOGITS  train-mode streams, logits only: no labels, no backward                               (nsd_seq_train_fwd_logits)
+//   HEAD_DLOG    train-mode streams, the dense backward from the caller's dlogits [B][K] (no logits written)      (nsd_seq_head_bwd)
+// Everything up to the logits is the same code in every mode, so HEAD_LOGITS's logits are HEAD_TRAIN's bit for bit, and HEAD_DLOG
+// rebuilds exactly the activations HEAD_TRAIN differentiates.  HEAD_EVAL / HEAD_TRAIN are head_tm_kernel<VPL, false / true> as
+// before; the other two are kernels of their own.  dlogits: HEAD_DLOG only, null otherwise.
+enum { HEAD_EVAL = 0, HEAD_TRAIN = 1, HEAD_LOGITS = 2, HEAD_DLOG = 3 };
+int nsd_head_tm_launch(const HeadTmArgs &a, int mode, const float *dlogits, hipStream_t st);
 // head parameter gradients from the per-trial rows: grads_head points at ln.weight inside the flat gradient vector
 // (scratch: 16 * (3 DH + F DH + F + K F + K + 1) floats)
 int nsd_head_tm_grads_launch(const float *hb, long hb_stride, int B, int DH, int F, int K, float *scratch, float *g_ln_w, float *g_ln_b,

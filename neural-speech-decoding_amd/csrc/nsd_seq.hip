@@ -37,6 +37,9 @@ struct ProfScope { ProfScope(int, hipStream_t) {} ~ProfScope() {} };
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
+// scan groups that can be resident at once: a group takes P workgroups per direction, one per CU
+int scan_cap(const SeqDims &s) { return nsd_num_cus() / (s.P * s.D); }
+
 int derive(const nsd_dims *d, uint32_t flags, SeqDims *o) {
     if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
     if (flags & ~(uint32_t)(NSD_FLAG_BIDIR | NSD_FLAG_RESIDUAL | NSD_FLAG_TRAIN | (NSD_DIAG ? NSD_DIAG_FLAG_ALL : 0u))) {
@@ -51,8 +54,7 @@ int derive(const nsd_dims *d, uint32_t flags, SeqDims *o) {
     if (s.F > 64 || s.K > 64) { nsd_set_error("seq path: F=%d K=%d exceed 64", s.F, s.K); return NSD_E_INVALID; }
     s.P = s.H / 32;
     s.CP = (int)align_up(s.C, 16);
-    const int cus = nsd_num_cus();
-    const int cap = cus / (s.P * s.D);                          // groups that can be resident at once
+    const int cus = nsd_num_cus(), cap = scan_cap(s);
     if (cap < 1) { nsd_set_error("seq path: H=%d D=%d needs %d workgroups per group, device has %d CUs", s.H, s.D, s.P * s.D, cus); return NSD_E_INVALID; }
     const int g32 = (s.B + 31) / 32;
     s.MG = (g32 <= cap) ? 32 : 64;
@@ -62,6 +64,14 @@ int derive(const nsd_dims *d, uint32_t flags, SeqDims *o) {
     s.fused2 = (s.D == 1 && s.L == 2 && !s.residual && !(NSD_DIAG && (flags & NSD_DIAG_FLAG_NO_FUSED_LAYERS)) && s.CP <= 64 && nsd_scan2_supported(s.H, s.MG)) ? 1 : 0;
     *o = s;
     return NSD_OK;
+}
+
+// The flag sets of the scans (NSD_SEQ_GROUP_WORDS rendezvous words per group and direction, nsd_seq.h): forward sets of every layer,
+// then the backward sets.  Words in front of the sets of the launch of pass (0 forward, 1 backward), layer l, whose first group is g0;
+// chunks of one layer are disjoint.  The fused two-layer route (D = 1) uses layer 0's sets.  (s, 1, 0, 0) is where the backward half
+// starts, (s, 2, 0, 0) the size of it all.
+int64_t flag_words(const SeqDims &s, int pass, int l, int g0) {
+    return (((int64_t)pass * s.L + l) * s.D * s.groups + (int64_t)g0 * s.D) * NSD_SEQ_GROUP_WORDS;
 }
 
 constexpr long PARTS_FLOATS = 18L * 1024 * 1024;               // 64 splits of cfg3's 1024 x 256 weight gradient
@@ -74,7 +84,7 @@ SeqWs make_ws(const SeqDims &s) {
     auto take = [&](int64_t bytes) { const int64_t at = p; p = align_up(p + bytes, 256); return at; };
     (void)take(NSD_SEQ_HEADER_BYTES);                            // persistent header: sticky status (nsd_seq_workspace_init zeroes it)
     w.status = take(NSD_SEQ_STATUS_WORDS * 4);                   // == NSD_SEQ_HEADER_BYTES: nsd_seq_status / nsd_seq_guard rely on it
-    w.flags_bytes = 2LL * s.L * s.D * s.groups * NSD_SEQ_GROUP_WORDS * 4;        // forward + backward flag sets of every layer (one word per wave)
+    w.flags_bytes = flag_words(s, 2, 0, 0) * 4;
     w.flags = take(w.flags_bytes);
     w.xbf = take(R * s.CP * 2);
     for (int l = 0; l < s.L; ++l) {
@@ -121,17 +131,6 @@ SeqWs make_ws(const SeqDims &s) {
 template <class T>
 T *at(void *ws, int64_t off) { return reinterpret_cast<T *>(reinterpret_cast<char *>(ws) + off); }
 
-int make_rng_args(const nsd_rng *r, RngArgs *out) {
-    memset(out, 0, sizeof(*out));
-    if (!r) return NSD_OK;
-    if (!(r->p_lstm >= 0.f && r->p_lstm < 1.f) || !(r->p_head >= 0.f && r->p_head < 1.f)) { nsd_set_error("rng: p out of [0,1)"); return NSD_E_INVALID; }
-    out->seed = r->seed; out->base = r->base_stream;
-    out->thr_lstm = nsd_drop_threshold(r->p_lstm); out->thr_head = nsd_drop_threshold(r->p_head);
-    out->keep_lstm = 1.0f / (1.0f - r->p_lstm); out->keep_head = 1.0f / (1.0f - r->p_head);
-    out->on = 1;
-    return NSD_OK;
-}
-
 // ---- small reduction kernels of the backward pass -----------------------------------------------------------------------------
 // grads rows are torch's (g*H + u); the GEMM's rows are unit-major c = 4u + g.  out[(g*H+u)*I + i] = sum_z part[z][c][i], i < I
 __global__ __launch_bounds__(256) void seq_reduce_dw_kernel(const float *part, int nparts, int H, int N, int I, float *out) {
@@ -161,7 +160,10 @@ struct Ctx {
     void *ws;
     const float *params;
     hipStream_t st;
-    int cap;                                                     // groups per scan launch
+    const char *who;                                             // the entry point, for its error texts
+    RngArgs rng;                                                 // the caller's streams (all zero: off)
+    bool lstm_drop;                                              // inter-layer dropout is active
+    int cap;                                                     // groups per scan launch: what can be resident at once
     int spread;                                                  // NSD_FLAG_SPREAD_GROUPS
     int l2_mode;                                                 // same-XCD exchange shortcut allowed (diagnostic build: NSD_DIAG_FLAG_NO_L2_EXCHANGE clears it)
     int short_grid;                                              // diagnostic build: NSD_DIAG_FLAG_LOSE_MEMBER -> every scan launch misses its last workgroup
@@ -179,62 +181,71 @@ int split_count(int M, int N, long K) {
     return S;
 }
 
-bool writes_lk(const SeqDims &s, int l, bool lstm_drop) { return (lstm_drop && l < s.L - 1) || (s.residual && l >= 1); }
-const bf16_t *out_of(Ctx &c, int l, bool lstm_drop) { return at<bf16_t>(c.ws, writes_lk(c.s, l, lstm_drop) ? c.w.lk[l] : c.w.hs[l]); }
+// a layer writes its LINKED output lk[l] = (h [+ its input]) * multiplier when that differs from h: inter-layer dropout active
+// (masked: l < L-1) or the residual extension (l >= 1); readers take lk[l] then, hs[l] otherwise
+bool masked(const Ctx &c, int l) { return c.lstm_drop && l < c.s.L - 1; }
+bool writes_lk(const Ctx &c, int l) { return masked(c, l) || (c.s.residual && l >= 1); }
+const bf16_t *out_of(Ctx &c, int l) { return at<bf16_t>(c.ws, writes_lk(c, l) ? c.w.lk[l] : c.w.hs[l]); }
 
-int forward(Ctx &c, const float *x, const RngArgs &rng, bool train) {
+// The launches of one scan (A: one of the four argument structs of nsd_seq.h) over all groups, at most c.cap of them at a time, each
+// chunk on flag sets of its own.  Fills what the four structs share; fill(a) adds the scan's own operands.  bwd: backward pass;
+// l: the layer whose output the rng multiplies (0 for the fused two-layer scans).
+template <class A, class Fill>
+int scan_chunks(Ctx &c, int (*launch)(const A &, int, int, hipStream_t), bool bwd, int l, Fill fill) {
+    const SeqDims &s = c.s;
+    for (int g0 = 0; g0 < s.groups; g0 += c.cap) {
+        A a;
+        memset(&a, 0, sizeof(a));
+        fill(a);
+        a.xch = at<bf16_t>(c.ws, c.w.xch); a.groups_total = s.groups;
+        a.flags = at<unsigned>(c.ws, c.w.flags) + flag_words(s, bwd ? 1 : 0, l, g0);
+        a.status = at<int>(c.ws, c.w.status);
+        a.B = s.B; a.Bp = s.Bp; a.T = s.T; a.groups = s.groups - g0 < c.cap ? s.groups - g0 : c.cap; a.group0 = g0;
+        a.rng = c.rng; a.rng.on = masked(c, l) ? 1 : 0;
+        a.allow_l2_mode = c.l2_mode; a.spread_groups = c.spread; a.diag_short_grid = c.short_grid;
+        ProfScope ps(bwd ? PK_SCAN_BWD : PK_SCAN_FWD, c.st);
+        if (const int rc = launch(a, s.H, s.MG, c.st)) return rc;
+    }
+    return NSD_OK;
+}
+
+int forward(Ctx &c, const float *x, bool train) {
     const SeqDims &s = c.s;
     const int H = s.H, G = 4 * H, DH = s.D * H;
     const long R = (long)s.T * s.Bp;
     if (hipMemsetAsync(at<char>(c.ws, c.w.status), 0, (size_t)(c.w.flags + c.w.flags_bytes - c.w.status), c.st) != hipSuccess) {
         nsd_set_error("seq: memset failed"); return NSD_E_LAUNCH;
     }
-    ProfScope *prep = new ProfScope(PK_PREP, c.st);
-    if (const int rc = nsd_seq_xbf_launch(x, at<bf16_t>(c.ws, c.w.xbf), s.B, s.Bp, s.T, s.C, s.CP, c.st)) { delete prep; return rc; }
-    for (int l = 0; l < s.L; ++l)
-        for (int d = 0; d < s.D; ++d) {
-            PrepArgs p;
-            memset(&p, 0, sizeof(p));
-            p.w_ih = c.params + c.pl.w_ih[l][d]; p.w_hh = c.params + c.pl.w_hh[l][d];
-            p.b_ih = c.params + c.pl.b_ih[l][d]; p.b_hh = c.params + c.pl.b_hh[l][d];
-            p.wf = at<bf16_t>(c.ws, c.w.wf[l][d]); p.wb = at<bf16_t>(c.ws, c.w.wb[l][d]); p.wx = at<bf16_t>(c.ws, c.w.wx[l][d]);
-            p.wxt = l > 0 ? at<bf16_t>(c.ws, c.w.wxt[l]) : nullptr;
-            p.bsum = at<float>(c.ws, c.w.bsum[l][d]);
-            p.H = H; p.I = l == 0 ? s.C : DH; p.Ipad = l == 0 ? s.CP : DH; p.wxt_ld = s.D * G; p.wxt_off = d * G;
-            if (const int rc = nsd_seq_prep_launch(p, c.st)) { delete prep; return rc; }
-        }
-    delete prep;
-    if (s.fused2) {
-        const bool lstm_drop = train && rng.on && rng.thr_lstm != 0;
+    {
+        ProfScope prep(PK_PREP, c.st);
+        if (const int rc = nsd_seq_xbf_launch(x, at<bf16_t>(c.ws, c.w.xbf), s.B, s.Bp, s.T, s.C, s.CP, c.st)) return rc;
+        for (int l = 0; l < s.L; ++l)
+            for (int d = 0; d < s.D; ++d) {
+                PrepArgs p;
+                memset(&p, 0, sizeof(p));
+                p.w_ih = c.params + c.pl.w_ih[l][d]; p.w_hh = c.params + c.pl.w_hh[l][d];
+                p.b_ih = c.params + c.pl.b_ih[l][d]; p.b_hh = c.params + c.pl.b_hh[l][d];
+                p.wf = at<bf16_t>(c.ws, c.w.wf[l][d]); p.wb = at<bf16_t>(c.ws, c.w.wb[l][d]); p.wx = at<bf16_t>(c.ws, c.w.wx[l][d]);
+                p.wxt = l > 0 ? at<bf16_t>(c.ws, c.w.wxt[l]) : nullptr;
+                p.bsum = at<float>(c.ws, c.w.bsum[l][d]);
+                p.H = H; p.I = l == 0 ? s.C : DH; p.Ipad = l == 0 ? s.CP : DH; p.wxt_ld = s.D * G; p.wxt_off = d * G;
+                if (const int rc = nsd_seq_prep_launch(p, c.st)) return rc;
+            }
+    }
+    if (s.fused2)
         // (no projection GEMM: W_ih0 . x_t is CP / 16 <= 4 MFMAs per step inside the scan -- one launch and a 1-GB tile round trip less)
-        for (int g0 = 0; g0 < s.groups; g0 += c.cap) {
-            Scan2FwdArgs a;
-            memset(&a, 0, sizeof(a));
+        return scan_chunks(c, nsd_scan2_fwd_launch, false, 0, [&](Scan2FwdArgs &a) {
             a.wf0 = at<bf16_t>(c.ws, c.w.wf[0][0]); a.wx1 = at<bf16_t>(c.ws, c.w.wx[1][0]); a.wf1 = at<bf16_t>(c.ws, c.w.wf[1][0]);
             a.bsum1 = at<float>(c.ws, c.w.bsum[1][0]);
             a.wx0 = at<bf16_t>(c.ws, c.w.wx[0][0]); a.bsum0 = at<float>(c.ws, c.w.bsum[0][0]); a.xbf = at<bf16_t>(c.ws, c.w.xbf); a.CP = s.CP;
-            a.hs0 = at<bf16_t>(c.ws, c.w.hs[0]); a.lk0 = lstm_drop ? at<bf16_t>(c.ws, c.w.lk[0]) : nullptr; a.hs1 = at<bf16_t>(c.ws, c.w.hs[1]);
-            a.xch = at<bf16_t>(c.ws, c.w.xch); a.groups_total = s.groups;
+            a.hs0 = at<bf16_t>(c.ws, c.w.hs[0]); a.lk0 = writes_lk(c, 0) ? at<bf16_t>(c.ws, c.w.lk[0]) : nullptr; a.hs1 = at<bf16_t>(c.ws, c.w.hs[1]);
             if (train) {
                 a.cs0 = at<bf16_t>(c.ws, c.w.cs[0][0]); a.ga0 = at<bf16_t>(c.ws, c.w.ga[0][0]);
                 a.cs1 = at<bf16_t>(c.ws, c.w.cs[1][0]); a.ga1 = at<bf16_t>(c.ws, c.w.ga[1][0]);
             }
-            a.flags = at<unsigned>(c.ws, c.w.flags) + (long)g0 * NSD_SEQ_GROUP_WORDS;
-            a.status = at<int>(c.ws, c.w.status);
-            a.B = s.B; a.Bp = s.Bp; a.T = s.T; a.groups = s.groups - g0 < c.cap ? s.groups - g0 : c.cap; a.group0 = g0;
-            a.rng = rng; a.rng.on = lstm_drop ? 1 : 0;
-            a.allow_l2_mode = c.l2_mode; a.spread_groups = c.spread; a.diag_short_grid = c.short_grid;
-            ProfScope ps(PK_SCAN_FWD, c.st);
-            if (const int rc = nsd_scan2_fwd_launch(a, H, s.MG, c.st)) return rc;
-        }
-        return NSD_OK;
-    }
+        });
     for (int l = 0; l < s.L; ++l) {
-        // a layer writes its LINKED output lk[l] = (h [+ its input]) * multiplier when that differs from h: inter-layer dropout
-        // active (l < L-1) or the residual extension (l >= 1); readers take lk[l] then, hs[l] otherwise
-        const bool lstm_drop = train && rng.on && rng.thr_lstm != 0;
-        const bool masked = lstm_drop && l < s.L - 1;
-        const bf16_t *in = l == 0 ? at<bf16_t>(c.ws, c.w.xbf) : out_of(c, l - 1, lstm_drop);
+        const bf16_t *in = l == 0 ? at<bf16_t>(c.ws, c.w.xbf) : out_of(c, l - 1);
         const int Kin = l == 0 ? s.CP : DH;
         // layer 0 with at most 64 channels: W_ih . x_t is CP / 16 <= 4 MFMAs per step inside the scan (no GEMM, no tile round trip)
         const bool inproj = l == 0 && s.CP <= 64;
@@ -247,10 +258,7 @@ int forward(Ctx &c, const float *x, const RngArgs &rng, bool train) {
             ProfScope ps(PK_GEMM_XPROJ, c.st);
             if (const int rc = nsd_gemm_bf16_launch(g, c.st)) return rc;
         }
-        for (int g0 = 0; g0 < s.groups; g0 += c.cap) {
-            ScanFwdArgs a;
-            memset(&a, 0, sizeof(a));
-            const int ng = s.groups - g0 < c.cap ? s.groups - g0 : c.cap;
+        if (const int rc = scan_chunks(c, nsd_scan_fwd_launch, false, l, [&](ScanFwdArgs &a) {
             for (int d = 0; d < s.D; ++d) {
                 a.wf[d] = at<bf16_t>(c.ws, c.w.wf[l][d]);
                 a.xproj[d] = at<bf16_t>(c.ws, c.w.xproj[d]);
@@ -258,35 +266,49 @@ int forward(Ctx &c, const float *x, const RngArgs &rng, bool train) {
                 a.cs[d] = train ? at<bf16_t>(c.ws, c.w.cs[l][d]) : nullptr;
                 a.ga[d] = train ? at<bf16_t>(c.ws, c.w.ga[l][d]) : nullptr;
             }
-            a.hs = at<bf16_t>(c.ws, c.w.hs[l]); a.xch = at<bf16_t>(c.ws, c.w.xch); a.groups_total = s.groups;
+            a.hs = at<bf16_t>(c.ws, c.w.hs[l]);
             a.xbf = at<bf16_t>(c.ws, c.w.xbf); a.CP = s.CP;
-            a.lk = writes_lk(s, l, lstm_drop) ? at<bf16_t>(c.ws, c.w.lk[l]) : nullptr;
+            a.lk = writes_lk(c, l) ? at<bf16_t>(c.ws, c.w.lk[l]) : nullptr;
             a.res = (s.residual && l >= 1) ? in : nullptr;
-            a.flags = at<unsigned>(c.ws, c.w.flags) + ((long)l * s.D * s.groups + (long)g0 * s.D) * NSD_SEQ_GROUP_WORDS;   // disjoint per chunk
-            a.status = at<int>(c.ws, c.w.status);
-            a.B = s.B; a.Bp = s.Bp; a.T = s.T; a.D = s.D; a.ld = DH; a.groups = ng; a.group0 = g0; a.layer = l;
-            a.rng = rng;
-            a.rng.on = masked ? 1 : 0;
-            a.allow_l2_mode = c.l2_mode; a.spread_groups = c.spread; a.diag_short_grid = c.short_grid;
-            ProfScope ps(PK_SCAN_FWD, c.st);
-            if (const int rc = nsd_scan_fwd_launch(a, H, s.MG, c.st)) return rc;
-        }
+            a.D = s.D; a.ld = DH; a.layer = l;
+        })) return rc;
     }
     return NSD_OK;
 }
 
-HeadTmArgs head_args(Ctx &c, float *logits, float *probs) {
+// mode: HEAD_EVAL, or one of the train-mode launches, which draw RReLU slopes and head dropout from c.rng (rng off: eval slope, no dropout)
+HeadTmArgs head_args(Ctx &c, int mode, float *logits, float *probs) {
     const SeqDims &s = c.s;
     HeadTmArgs h;
     memset(&h, 0, sizeof(h));
-    h.top = out_of(c, s.L - 1, false);                           // (the last layer is never multiplied; with the residual extension it is lk)
+    h.top = out_of(c, s.L - 1);                                  // (the last layer is never multiplied; with the residual extension it is lk)
     h.ln_w = c.params + c.pl.ln_w; h.ln_b = c.params + c.pl.ln_b; h.attn_w = c.params + c.pl.attn_w; h.attn_b = c.params + c.pl.attn_b;
     h.fc0_w = c.params + c.pl.fc0_w; h.fc0_b = c.params + c.pl.fc0_b; h.fc3_w = c.params + c.pl.fc3_w; h.fc3_b = c.params + c.pl.fc3_b;
     h.eval_slope = (float)((0.125 + 1.0 / 3.0) / 2.0);           // nn.RReLU eval slope, lstm_eeg_model.py:27
     h.logits = logits; h.probs = probs;
+    h.train = mode != HEAD_EVAL; h.rng = c.rng;
     h.B = s.B; h.Bp = s.Bp; h.T = s.T; h.DH = s.D * s.H; h.F = s.F; h.K = s.K;
     h.status = at<int>(c.ws, c.w.status);
     return h;
+}
+
+// The training outputs of the head, which the backward pass reads: alpha, dscore, pooled, dpooled and the per-trial rows.  The
+// padding trials' dpooled / dscore are zeroed so that they contribute nothing to any gradient.  (loss, labels and scale stay with
+// nsd_seq_train_fwd, the one entry that has them.)
+int head_train_outputs(Ctx &c, HeadTmArgs &h) {
+    const SeqDims &s = c.s;
+    const int DH = s.D * s.H;
+    h.alpha = at<float>(c.ws, c.w.alpha); h.dscore = at<float>(c.ws, c.w.dscore);
+    h.pooled = at<float>(c.ws, c.w.pooled); h.dpooled = at<float>(c.ws, c.w.dpooled);
+    h.hb = at<float>(c.ws, c.w.hb); h.hb_stride = c.w.hb_stride;
+    if (s.Bp > s.B &&
+        (hipMemsetAsync(h.dpooled + (long)s.B * DH, 0, (size_t)(s.Bp - s.B) * DH * 4, c.st) != hipSuccess ||
+         hipMemsetAsync(h.alpha, 0, (size_t)s.T * s.Bp * 4, c.st) != hipSuccess ||
+         hipMemsetAsync(h.dscore, 0, (size_t)s.T * s.Bp * 4, c.st) != hipSuccess)) {
+        nsd_set_error("%s: memset failed", c.who);
+        return NSD_E_LAUNCH;
+    }
+    return NSD_OK;
 }
 
 // dL/dx of the evaluation in `ws` from layer 0's gate gradients (nsd_seq_dx.hip), called once w.da holds them and layer 0's weight
@@ -308,21 +330,21 @@ int input_grad(Ctx &c, float *dx) {
     return nsd_seq_dx_launch(a, c.st);
 }
 
-int backward(Ctx &c, const RngArgs &rng, float *grads, float *dx) {
+int backward(Ctx &c, float *grads, float *dx) {
     const SeqDims &s = c.s;
     const int H = s.H, G = 4 * H, DH = s.D * H;
     const long R = (long)s.T * s.Bp;
     float *parts = at<float>(c.ws, c.w.parts);
-    const bool lstm_drop = rng.on && rng.thr_lstm != 0;
     // the backward scans' flag sets (rendezvous words, per-wave step counters) start from zero on EVERY backward call: a second
     // nsd_seq_train_bwd on the same forward (retain_graph) would otherwise find last call's counters at T and race through
-    if (hipMemsetAsync(at<char>(c.ws, c.w.flags) + c.w.flags_bytes / 2, 0, (size_t)(c.w.flags_bytes / 2), c.st) != hipSuccess) {
+    const int64_t bwd_sets = flag_words(s, 1, 0, 0) * 4;
+    if (hipMemsetAsync(at<char>(c.ws, c.w.flags) + bwd_sets, 0, (size_t)(c.w.flags_bytes - bwd_sets), c.st) != hipSuccess) {
         nsd_set_error("seq: memset failed"); return NSD_E_LAUNCH;
     }
     // contractions over the whole sequence for layer l: dW_hh, dW_ih (split-K, fixed-order reduction), biases from the scan's
     // per-tile sums.  da: [T*Bp][ldda] with direction d in columns d*4H..; dbp: [D][groups][4H]
     auto weight_grads = [&](int l, const bf16_t *da, long ldda, const float *dbp) -> int {
-        const bf16_t *in = l == 0 ? at<bf16_t>(c.ws, c.w.xbf) : out_of(c, l - 1, lstm_drop);
+        const bf16_t *in = l == 0 ? at<bf16_t>(c.ws, c.w.xbf) : out_of(c, l - 1);
         const int Kin = l == 0 ? s.CP : DH, I = l == 0 ? s.C : DH;
         for (int d = 0; d < s.D; ++d) {
             ProfScope ps(PK_GEMM_DW, c.st);
@@ -368,35 +390,21 @@ int backward(Ctx &c, const RngArgs &rng, float *grads, float *dx) {
     };
     if (s.fused2) {
         float *dbp0 = at<float>(c.ws, c.w.dbp), *dbp1 = dbp0 + (long)s.groups * G;
-        for (int g0 = 0; g0 < s.groups; g0 += c.cap) {
-            Scan2BwdArgs a;
-            memset(&a, 0, sizeof(a));
+        if (const int rc = scan_chunks(c, nsd_scan2_bwd_launch, true, 0, [&](Scan2BwdArgs &a) {
             a.wb0 = at<bf16_t>(c.ws, c.w.wb[0][0]); a.wb1 = at<bf16_t>(c.ws, c.w.wb[1][0]); a.wxt1 = at<bf16_t>(c.ws, c.w.wxt[1]);
             a.cs0 = at<bf16_t>(c.ws, c.w.cs[0][0]); a.ga0 = at<bf16_t>(c.ws, c.w.ga[0][0]);
             a.cs1 = at<bf16_t>(c.ws, c.w.cs[1][0]); a.ga1 = at<bf16_t>(c.ws, c.w.ga[1][0]);
             a.da0 = at<bf16_t>(c.ws, c.w.da); a.da1 = at<bf16_t>(c.ws, c.w.da2); a.dbp0 = dbp0; a.dbp1 = dbp1;
-            a.xch = at<bf16_t>(c.ws, c.w.xch);
             a.alpha = at<float>(c.ws, c.w.alpha); a.dscore = at<float>(c.ws, c.w.dscore); a.dpooled = at<float>(c.ws, c.w.dpooled);
             a.attn_w = c.params + c.pl.attn_w;
-            a.flags = at<unsigned>(c.ws, c.w.flags) + ((long)s.L * s.D * s.groups + (long)g0) * NSD_SEQ_GROUP_WORDS;
-            a.status = at<int>(c.ws, c.w.status);
-            a.B = s.B; a.Bp = s.Bp; a.T = s.T; a.groups = s.groups - g0 < c.cap ? s.groups - g0 : c.cap; a.group0 = g0; a.groups_total = s.groups;
-            a.rng = rng; a.rng.on = lstm_drop ? 1 : 0;
-            a.allow_l2_mode = c.l2_mode; a.spread_groups = c.spread; a.diag_short_grid = c.short_grid;
-            ProfScope ps(PK_SCAN_BWD, c.st);
-            if (const int rc = nsd_scan2_bwd_launch(a, H, s.MG, c.st)) return rc;
-        }
+        })) return rc;
         if (const int rc = weight_grads(1, at<bf16_t>(c.ws, c.w.da2), G, dbp1)) return rc;
         if (const int rc = weight_grads(0, at<bf16_t>(c.ws, c.w.da), G, dbp0)) return rc;
         if (dx)
             if (const int rc = input_grad(c, dx)) return rc;
     } else
     for (int l = s.L - 1; l >= 0; --l) {
-        const bool masked = lstm_drop && l < s.L - 1;
-        for (int g0 = 0; g0 < s.groups; g0 += c.cap) {
-            ScanBwdArgs a;
-            memset(&a, 0, sizeof(a));
-            const int ng = s.groups - g0 < c.cap ? s.groups - g0 : c.cap;
+        if (const int rc = scan_chunks(c, nsd_scan_bwd_launch, true, l, [&](ScanBwdArgs &a) {
             for (int d = 0; d < s.D; ++d) {
                 a.wb[d] = at<bf16_t>(c.ws, c.w.wb[l][d]);
                 a.cs[d] = at<bf16_t>(c.ws, c.w.cs[l][d]);
@@ -409,16 +417,9 @@ int backward(Ctx &c, const RngArgs &rng, float *grads, float *dx) {
             a.dres = (s.residual && l >= 1) ? at<float>(c.ws, c.w.din[1]) : nullptr;
             a.alpha = at<float>(c.ws, c.w.alpha); a.dscore = at<float>(c.ws, c.w.dscore); a.dpooled = at<float>(c.ws, c.w.dpooled);
             a.attn_w = c.params + c.pl.attn_w;
-            a.flags = at<unsigned>(c.ws, c.w.flags) + ((long)(s.L + l) * s.D * s.groups + (long)g0 * s.D) * NSD_SEQ_GROUP_WORDS;
-            a.dbp = at<float>(c.ws, c.w.dbp); a.groups_total = s.groups; a.xch = at<bf16_t>(c.ws, c.w.xch);
-            a.status = at<int>(c.ws, c.w.status);
-            a.B = s.B; a.Bp = s.Bp; a.T = s.T; a.D = s.D; a.ld = DH; a.groups = ng; a.group0 = g0; a.layer = l;
-            a.rng = rng;
-            a.rng.on = masked ? 1 : 0;
-            a.allow_l2_mode = c.l2_mode; a.spread_groups = c.spread; a.diag_short_grid = c.short_grid;
-            ProfScope ps(PK_SCAN_BWD, c.st);
-            if (const int rc = nsd_scan_bwd_launch(a, H, s.MG, c.st)) return rc;
-        }
+            a.dbp = at<float>(c.ws, c.w.dbp);
+            a.D = s.D; a.ld = DH; a.layer = l;
+        })) return rc;
         if (const int rc = weight_grads(l, at<bf16_t>(c.ws, c.w.da), (long)s.D * G, at<float>(c.ws, c.w.dbp))) return rc;
         if (l == 0 && dx)
             if (const int rc = input_grad(c, dx)) return rc;
@@ -446,21 +447,52 @@ int backward(Ctx &c, const RngArgs &rng, float *grads, float *dx) {
                                     grads + c.pl.attn_b, grads + c.pl.fc0_w, grads + c.pl.fc0_b, grads + c.pl.fc3_w, grads + c.pl.fc3_b, c.st);
 }
 
-int make_ctx(const nsd_dims *d, uint32_t flags, const float *params, void *ws, int64_t ws_bytes, void *stream, const char *who, Ctx *c) {
-    if (const int rc = derive(d, flags, &c->s)) return rc;
-    c->pl = nsd_seq_make_layout(c->s.C, c->s.H, c->s.L, c->s.K, c->s.F, c->s.D);
-    c->w = make_ws(c->s);
-    if (!ws || !params) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
-    if (ws_bytes < c->w.total) {
-        nsd_set_error("%s: workspace of %lld bytes is smaller than nsd_seq_workspace_bytes() = %lld", who, (long long)ws_bytes, (long long)c->w.total);
+// Dims and workspace layout of an entry point.  Refusals, in this order: dims and flags; a null workspace or !ptr_ok (the parameters --
+// for nsd_seq_loss_sum, which has none, its output); a workspace smaller than nsd_seq_workspace_bytes().
+int open_ws(const char *who, const nsd_dims *d, uint32_t flags, const void *ws, int64_t ws_bytes, bool ptr_ok, SeqDims *s, SeqWs *w) {
+    if (const int rc = derive(d, flags, s)) return rc;
+    *w = make_ws(*s);
+    if (!ws || !ptr_ok) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (ws_bytes < w->total) {
+        nsd_set_error("%s: workspace of %lld bytes is smaller than nsd_seq_workspace_bytes() = %lld", who, (long long)ws_bytes, (long long)w->total);
         return NSD_E_WORKSPACE;
     }
-    c->ws = ws; c->params = params; c->st = (hipStream_t)stream;
-    c->cap = nsd_num_cus() / (c->s.P * c->s.D);
+    return NSD_OK;
+}
+
+// The preamble of every entry point that launches model work.  After open_ws's refusals: the entry's own pointers (own_ptrs), an
+// input gradient dx wider than its scratch, the empty batch (EMPTY_BATCH: nothing to launch), the rng (null: streams off).
+// An entry leaves with leave(rc) on anything but NSD_OK.
+constexpr int EMPTY_BATCH = 1;
+int leave(int rc) { return rc == EMPTY_BATCH ? NSD_OK : rc; }
+int enter(Ctx *c, const char *who, const nsd_dims *d, uint32_t flags, const float *params, void *ws, int64_t ws_bytes, bool own_ptrs,
+          const nsd_rng *rng, void *stream, const float *dx = nullptr) {
+    if (const int rc = open_ws(who, d, flags, ws, ws_bytes, params != nullptr, &c->s, &c->w)) return rc;
+    if (!own_ptrs) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (dx && nsd_seq_dx_scratch_bytes(c->s.H, c->s.D, c->s.CP) > PARTS_FLOATS * 4) {
+        nsd_set_error("%s: %d input channels exceed the input-gradient scratch", who, c->s.C);
+        return NSD_E_INVALID;
+    }
+    if (d->B == 0) return EMPTY_BATCH;
+    memset(&c->rng, 0, sizeof(c->rng));
+    if (rng)
+        if (const int rc = nsd_rng_args(rng, &c->rng)) return rc;
+    c->lstm_drop = c->rng.on && c->rng.thr_lstm != 0;
+    c->pl = nsd_seq_make_layout(c->s.C, c->s.H, c->s.L, c->s.K, c->s.F, c->s.D);
+    c->ws = ws; c->params = params; c->st = (hipStream_t)stream; c->who = who;
+    c->cap = scan_cap(c->s);
     c->l2_mode = (NSD_DIAG && (flags & NSD_DIAG_FLAG_NO_L2_EXCHANGE)) ? 0 : 1;
     c->spread = (NSD_DIAG && (flags & NSD_DIAG_FLAG_SPREAD_GROUPS)) ? 1 : 0;
     c->short_grid = (NSD_DIAG && (flags & NSD_DIAG_FLAG_LOSE_MEMBER)) ? 1 : 0;
     return NSD_OK;
+}
+
+// nsd_seq_train_bwd (dx == null) and nsd_seq_train_bwd_dx: the same launches in front of the optional dx contraction, so the same gradients
+int train_bwd(const char *who, const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace, int64_t workspace_bytes,
+              float *grads, float *dx, void *stream) {
+    Ctx c;
+    if (const int rc = enter(&c, who, d, flags, params, workspace, workspace_bytes, grads != nullptr, rng, stream, dx)) return leave(rc);
+    return backward(c, grads, dx);
 }
 
 }  // namespace
@@ -522,70 +554,39 @@ int64_t nsd_seq_workspace_bytes(const nsd_dims *d, uint32_t flags) {
 int nsd_seq_infer(const nsd_dims *d, const float *params, const float *x, uint32_t flags, float *logits, float *probs, void *workspace,
                   int64_t workspace_bytes, void *stream) {
     Ctx c;
-    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_infer", &c)) return rc;
-    if (!x || !logits) { nsd_set_error("seq_infer: null pointer"); return NSD_E_INVALID; }
-    if (d->B == 0) return NSD_OK;
-    RngArgs off;
-    memset(&off, 0, sizeof(off));
-    if (const int rc = forward(c, x, off, false)) return rc;
-    HeadTmArgs h = head_args(c, logits, probs);
+    if (const int rc = enter(&c, "seq_infer", d, flags, params, workspace, workspace_bytes, x && logits, nullptr, stream)) return leave(rc);
+    if (const int rc = forward(c, x, false)) return rc;
+    HeadTmArgs h = head_args(c, HEAD_EVAL, logits, probs);
     ProfScope ps(PK_HEAD, c.st);
-    return nsd_head_tm_launch(h, c.st);
+    return nsd_head_tm_launch(h, HEAD_EVAL, nullptr, c.st);
 }
 
 int nsd_seq_train_fwd(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const int32_t *labels, float scale,
                       uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream) {
     Ctx c;
-    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_train_fwd", &c)) return rc;
-    if (!x || !logits || !labels) { nsd_set_error("seq_train_fwd: null pointer"); return NSD_E_INVALID; }
-    if (d->B == 0) return NSD_OK;
-    RngArgs r;
-    if (const int rc = make_rng_args(rng, &r)) return rc;
-    if (const int rc = forward(c, x, r, true)) return rc;
-    HeadTmArgs h = head_args(c, logits, nullptr);
-    h.train = 1; h.labels = labels; h.scale = scale; h.rng = r;
-    h.alpha = at<float>(c.ws, c.w.alpha); h.dscore = at<float>(c.ws, c.w.dscore);
-    h.pooled = at<float>(c.ws, c.w.pooled); h.dpooled = at<float>(c.ws, c.w.dpooled); h.loss = at<float>(c.ws, c.w.loss);
-    h.hb = at<float>(c.ws, c.w.hb); h.hb_stride = c.w.hb_stride;
-    // padding trials: their dpooled / dscore must be zero so that they contribute nothing to any gradient
-    const int DH = c.s.D * c.s.H;
-    if (c.s.Bp > c.s.B) {
-        if (hipMemsetAsync(h.dpooled + (long)c.s.B * DH, 0, (size_t)(c.s.Bp - c.s.B) * DH * 4, c.st) != hipSuccess ||
-            hipMemsetAsync(h.alpha, 0, (size_t)c.s.T * c.s.Bp * 4, c.st) != hipSuccess ||
-            hipMemsetAsync(h.dscore, 0, (size_t)c.s.T * c.s.Bp * 4, c.st) != hipSuccess) {
-            nsd_set_error("seq_train_fwd: memset failed");
-            return NSD_E_LAUNCH;
-        }
-    }
+    if (const int rc = enter(&c, "seq_train_fwd", d, flags, params, workspace, workspace_bytes, x && logits && labels, rng, stream)) return leave(rc);
+    if (const int rc = forward(c, x, true)) return rc;
+    HeadTmArgs h = head_args(c, HEAD_TRAIN, logits, nullptr);
+    h.labels = labels; h.scale = scale; h.loss = at<float>(c.ws, c.w.loss);
+    if (const int rc = head_train_outputs(c, h)) return rc;
     ProfScope ps(PK_HEAD, c.st);
-    return nsd_head_tm_launch(h, c.st);
+    return nsd_head_tm_launch(h, HEAD_TRAIN, nullptr, c.st);
 }
 
 int nsd_seq_train_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace, int64_t workspace_bytes,
                       float *grads, void *stream) {
-    Ctx c;
-    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_train_bwd", &c)) return rc;
-    if (!grads) { nsd_set_error("seq_train_bwd: null pointer"); return NSD_E_INVALID; }
-    if (d->B == 0) return NSD_OK;
-    RngArgs r;
-    if (const int rc = make_rng_args(rng, &r)) return rc;
-    return backward(c, r, grads, nullptr);
+    return train_bwd("seq_train_bwd", d, params, rng, flags, workspace, workspace_bytes, grads, nullptr, stream);
 }
 
 // The any-loss sequence: the training forward with activations kept and logits out (no labels, no loss, no head backward) ...
 int nsd_seq_train_fwd_logits(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, uint32_t flags, void *workspace,
                              int64_t workspace_bytes, float *logits, void *stream) {
     Ctx c;
-    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_train_fwd_logits", &c)) return rc;
-    if (!x || !logits) { nsd_set_error("seq_train_fwd_logits: null pointer"); return NSD_E_INVALID; }
-    if (d->B == 0) return NSD_OK;
-    RngArgs r;
-    if (const int rc = make_rng_args(rng, &r)) return rc;
-    if (const int rc = forward(c, x, r, true)) return rc;
-    HeadTmArgs h = head_args(c, logits, nullptr);
-    h.train = 1; h.rng = r;                                      // the streams of nsd_seq_train_fwd's head: the same logits, bit for bit
+    if (const int rc = enter(&c, "seq_train_fwd_logits", d, flags, params, workspace, workspace_bytes, x && logits, rng, stream)) return leave(rc);
+    if (const int rc = forward(c, x, true)) return rc;
+    HeadTmArgs h = head_args(c, HEAD_LOGITS, logits, nullptr);   // the streams of nsd_seq_train_fwd's head: the same logits, bit for bit
     ProfScope ps(PK_HEAD, c.st);
-    return nsd_head_tm_ext_launch(h, nullptr, c.st);
+    return nsd_head_tm_launch(h, HEAD_LOGITS, nullptr, c.st);
 }
 
 // ... the head backward from the caller's dlogits, recomputed from the saved top-layer sequence with the forward's streams: it leaves
@@ -594,51 +595,24 @@ int nsd_seq_train_fwd_logits(const nsd_dims *d, const float *params, const float
 int nsd_seq_head_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, const float *dlogits, uint32_t flags, void *workspace,
                      int64_t workspace_bytes, void *stream) {
     Ctx c;
-    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_head_bwd", &c)) return rc;
-    if (!dlogits) { nsd_set_error("seq_head_bwd: null pointer"); return NSD_E_INVALID; }
-    if (d->B == 0) return NSD_OK;
-    RngArgs r;
-    if (const int rc = make_rng_args(rng, &r)) return rc;
-    HeadTmArgs h = head_args(c, nullptr, nullptr);
-    h.train = 1; h.rng = r;
-    h.alpha = at<float>(c.ws, c.w.alpha); h.dscore = at<float>(c.ws, c.w.dscore);
-    h.pooled = at<float>(c.ws, c.w.pooled); h.dpooled = at<float>(c.ws, c.w.dpooled);
-    h.hb = at<float>(c.ws, c.w.hb); h.hb_stride = c.w.hb_stride;
-    const int DH = c.s.D * c.s.H;
-    if (c.s.Bp > c.s.B) {                                        // padding trials: zero dpooled / dscore, as nsd_seq_train_fwd
-        if (hipMemsetAsync(h.dpooled + (long)c.s.B * DH, 0, (size_t)(c.s.Bp - c.s.B) * DH * 4, c.st) != hipSuccess ||
-            hipMemsetAsync(h.alpha, 0, (size_t)c.s.T * c.s.Bp * 4, c.st) != hipSuccess ||
-            hipMemsetAsync(h.dscore, 0, (size_t)c.s.T * c.s.Bp * 4, c.st) != hipSuccess) {
-            nsd_set_error("seq_head_bwd: memset failed");
-            return NSD_E_LAUNCH;
-        }
-    }
+    if (const int rc = enter(&c, "seq_head_bwd", d, flags, params, workspace, workspace_bytes, dlogits != nullptr, rng, stream)) return leave(rc);
+    HeadTmArgs h = head_args(c, HEAD_DLOG, nullptr, nullptr);
+    if (const int rc = head_train_outputs(c, h)) return rc;
     ProfScope ps(PK_HEAD_BWD, c.st);
-    return nsd_head_tm_ext_launch(h, dlogits, c.st);
+    return nsd_head_tm_launch(h, HEAD_DLOG, dlogits, c.st);
 }
 
 // nsd_seq_train_bwd plus dx[B][T][C] (fp32) when dx != null; the parameter gradients are nsd_seq_train_bwd's, bit for bit
 int nsd_seq_train_bwd_dx(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace, int64_t workspace_bytes,
                          float *grads, float *dx, void *stream) {
-    Ctx c;
-    if (const int rc = make_ctx(d, flags, params, workspace, workspace_bytes, stream, "seq_train_bwd_dx", &c)) return rc;
-    if (!grads) { nsd_set_error("seq_train_bwd_dx: null pointer"); return NSD_E_INVALID; }
-    if (dx && nsd_seq_dx_scratch_bytes(c.s.H, c.s.D, c.s.CP) > PARTS_FLOATS * 4) {
-        nsd_set_error("seq_train_bwd_dx: %d input channels exceed the input-gradient scratch", c.s.C);
-        return NSD_E_INVALID;
-    }
-    if (d->B == 0) return NSD_OK;
-    RngArgs r;
-    if (const int rc = make_rng_args(rng, &r)) return rc;
-    return backward(c, r, grads, dx);
+    return train_bwd("seq_train_bwd_dx", d, params, rng, flags, workspace, workspace_bytes, grads, dx, stream);
 }
 
+// (reads the workspace only: no parameters, and an empty batch still gets its sum, 0)
 int nsd_seq_loss_sum(const nsd_dims *d, uint32_t flags, const void *workspace, int64_t workspace_bytes, float *out, void *stream) {
     SeqDims s;
-    if (const int rc = derive(d, flags, &s)) return rc;
-    const SeqWs w = make_ws(s);
-    if (!workspace || !out) { nsd_set_error("seq_loss_sum: null pointer"); return NSD_E_INVALID; }
-    if (workspace_bytes < w.total) { nsd_set_error("seq_loss_sum: workspace too small"); return NSD_E_WORKSPACE; }
+    SeqWs w;
+    if (const int rc = open_ws("seq_loss_sum", d, flags, workspace, workspace_bytes, out != nullptr, &s, &w)) return rc;
     return nsd_loss_sum_launch(reinterpret_cast<const float *>(reinterpret_cast<const char *>(workspace) + w.loss), s.B, out, (hipStream_t)stream);
 }
 

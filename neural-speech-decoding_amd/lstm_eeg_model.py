@@ -48,6 +48,12 @@ class _StackedLSTMParams(nn.Module):
                 + (", bidirectional=True" if self.bidirectional else ""))
 
 
+def _grad_views(spec, g: torch.Tensor) -> tuple:
+    """The flat gradient vector as one view per parameter, in spec.names() order (what an autograd node returns)."""
+    offs, shapes = spec.offsets(), spec.shapes()
+    return tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
+
+
 class _EEGFunction(torch.autograd.Function):
     """Whole-model autograd node: x, 16 parameters -> logits.  Backward returns the parameter gradients as
     views of one flat vector produced by the HIP backward kernels."""
@@ -88,8 +94,7 @@ class _EEGFunction(torch.autograd.Function):
                                residual=module.residual, dx=dx)
         # (only the H = 48 fast-path kernel overwrites layer 0's saved gates; the generic path keeps them)
         ctx.gates_consumed = dx is not None and spec.fast_path() and spec.H == 48
-        offs, shapes = spec.offsets(), spec.shapes()
-        grads = tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
+        grads = _grad_views(spec, g)
         return (None, dx, None) + grads            # (ctx.ws lives as long as the graph does: retain_graph may come back)
 
 
@@ -133,8 +138,7 @@ class _EEGSeqFunction(torch.autograd.Function):
         g = ops.seq_train_bwd(spec, module._flat, ctx.ws, B, T, rng=ctx.rng, dx=dx) * dloss
         if dx is not None:
             dx = dx * dloss
-        offs, shapes = spec.offsets(), spec.shapes()
-        grads = tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
+        grads = _grad_views(spec, g)
         return (None, dx, None, None) + grads      # (the workspace stays with the graph: a second backward re-runs the scans on it)
 
 
@@ -160,8 +164,7 @@ class _EEGSeqEvalFunction(torch.autograd.Function):
         ops.seq_head_bwd(spec, module._flat, ctx.ws, dlogits.contiguous().float(), B, T)
         dx = torch.empty((B, T, spec.C), dtype=torch.float32, device=dlogits.device) if ctx.needs_input_grad[1] else None
         g = ops.seq_train_bwd(spec, module._flat, ctx.ws, B, T, dx=dx)
-        offs, shapes = spec.offsets(), spec.shapes()
-        grads = tuple(g[offs[n]:offs[n] + math.prod(shapes[n])].view(shapes[n]) for n in spec.names())
+        grads = _grad_views(spec, g)
         return (None, dx) + grads                  # (head_bwd + bwd recompute from the saved sequence: retain_graph gives the same bits)
 
 

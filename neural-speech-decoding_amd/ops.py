@@ -100,6 +100,17 @@ def _dev_f32(t: Optional[torch.Tensor], name: str, shape=None) -> Optional[int]:
     return t.data_ptr()
 
 
+def _labels_ptr(labels: torch.Tensor) -> int:
+    if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
+        raise NsdError("labels must be a contiguous int32 tensor on the device")
+    return labels.data_ptr()
+
+
+def _rng_struct(rng: dict) -> "_lib.Rng":
+    """rng=dict(seed=, base_stream=, p_lstm=, p_head=) -> nsd_rng"""
+    return _lib.Rng(int(rng["seed"]) & 0xFFFFFFFFFFFFFFFF, int(rng["base_stream"]) & 0xFFFFFFFF, float(rng["p_lstm"]), float(rng["p_head"]))
+
+
 class _StreamOf:
     """Placeholder argument: replaced by the current HIP stream of the launch device inside _call's device guard."""
 
@@ -307,9 +318,7 @@ def train_backward(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: tor
     if dlogits is None:
         if labels is None:
             raise NsdError("train_backward needs dlogits or labels")
-        if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
-            raise NsdError("labels must be a contiguous int32 tensor on the device")
-        lab_ptr = labels.data_ptr()
+        lab_ptr = _labels_ptr(labels)
     else:
         lab_ptr = None
     scale = (1.0 / max(B, 1)) if scale is None else float(scale)
@@ -346,8 +355,7 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     d = spec.dims(B, T)
     flags = _lib.NSD_FLAG_TRAIN | (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags
     pp = _dev_f32(flat, "params", (spec.param_count,))
-    if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
-        raise NsdError("labels must be a contiguous int32 tensor on the device")
+    labp = _labels_ptr(labels)
     scale = (1.0 / max(B, 1)) if scale is None else float(scale)
     xp, wsp, wsn, st, dev = _dev_f32(x, "x", (B, T, spec.C)), _dev_f32(ws, "workspace"), _nbytes(ws), STREAM, x.device
     dl, sl, dh = _dev_f32(drop_lstm, "drop_lstm"), _dev_f32(rrelu_slope, "rrelu_slope"), _dev_f32(drop_head, "drop_head")
@@ -359,15 +367,15 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
             raise NsdError("train_step_grads: pass either rng= or explicit mask tensors, not both")
         if dx is not None:
             raise NsdError("train_step_grads: dx= needs explicit mask tensors (nsd_lstm_bwd_rng forms no input gradient)")
-        r = _lib.Rng(int(rng["seed"]) & 0xFFFFFFFFFFFFFFFF, int(rng["base_stream"]) & 0xFFFFFFFF, float(rng["p_lstm"]), float(rng["p_head"]))
-        _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labels.data_ptr(), scale, flags, wsp, wsn, lp, st)
+        r = _rng_struct(rng)
+        _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labp, scale, flags, wsp, wsn, lp, st)
         _call("nsd_lstm_bwd_rng", dev, C.byref(d), pp, xp, C.byref(r), flags, wsp, wsn, st)
     else:
         if fused_head:
-            _call("nsd_lstm_head_train", dev, C.byref(d), pp, xp, dl, sl, dh, labels.data_ptr(), scale, flags, wsp, wsn, lp, st)
+            _call("nsd_lstm_head_train", dev, C.byref(d), pp, xp, dl, sl, dh, labp, scale, flags, wsp, wsn, lp, st)
         else:
             _call("nsd_lstm_fwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, st)
-            _call("nsd_head_train", dev, C.byref(d), pp, sl, dh, labels.data_ptr(), scale, wsp, wsn, lp, st)
+            _call("nsd_head_train", dev, C.byref(d), pp, sl, dh, labp, scale, wsp, wsn, lp, st)
         _call("nsd_lstm_bwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, dxp, st)
     gp = _dev_f32(grads, "grads", (spec.param_count,))
     if adam is None:
@@ -465,10 +473,7 @@ def seq_workspace(spec: ModelSpec, B: int, T: int, device) -> torch.Tensor:
 
 
 def _seq_rng(rng: Optional[dict]):
-    if rng is None:
-        return None
-    return C.byref(_lib.Rng(int(rng["seed"]) & 0xFFFFFFFFFFFFFFFF, int(rng["base_stream"]) & 0xFFFFFFFF, float(rng["p_lstm"]),
-                            float(rng["p_head"])))
+    return None if rng is None else C.byref(_rng_struct(rng))
 
 
 SEQ_ST_TIMEOUT_MASK, SEQ_ST_NONFINITE = 3, 4
@@ -526,27 +531,22 @@ def seq_train_fwd(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, labels: 
     """Forward + head + mean CE + head backward of one training evaluation; activations stay in `ws` for seq_train_bwd."""
     B, T, _ = x.shape
     d = spec.dims(B, T)
-    if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
-        raise NsdError("labels must be a contiguous int32 tensor on the device")
+    labp = _labels_ptr(labels)
     logits = torch.empty((B, spec.K), dtype=torch.float32, device=x.device) if logits is None else logits
     scale = (1.0 / max(B, 1)) if scale is None else float(scale)
     _call("nsd_seq_train_fwd", x.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _dev_f32(x, "x", (B, T, spec.C)),
-          _seq_rng(rng), labels.data_ptr(), scale, spec.seq_flags, ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits", (B, spec.K)), STREAM)
+          _seq_rng(rng), labp, scale, spec.seq_flags, ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits", (B, spec.K)), STREAM)
     return logits
 
 
 def seq_train_bwd(spec: ModelSpec, flat: torch.Tensor, ws: torch.Tensor, B: int, T: int, *, rng: Optional[dict] = None,
                   grads: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """BPTT + every parameter gradient of the evaluation seq_train_fwd left in `ws` -> flat gradient vector (overwritten).
-    dx: optional [B, T, C] fp32 device tensor that receives dL/dx (nsd_seq_train_bwd_dx; the gradients are the same bits)."""
+    dx: optional [B, T, C] fp32 device tensor that receives dL/dx (the gradients are the same bits with and without it)."""
     d = spec.dims(B, T)
     grads = torch.empty(spec.param_count, dtype=torch.float32, device=flat.device) if grads is None else grads
-    if dx is None:
-        _call("nsd_seq_train_bwd", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng), spec.seq_flags,
-              ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (spec.param_count,)), STREAM)
-    else:
-        _call("nsd_seq_train_bwd_dx", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng), spec.seq_flags,
-              ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (spec.param_count,)), _dev_f32(dx, "dx", (B, T, spec.C)), STREAM)
+    _call("nsd_seq_train_bwd_dx", flat.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _seq_rng(rng), spec.seq_flags,
+          ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (spec.param_count,)), _dev_f32(dx, "dx", (B, T, spec.C)), STREAM)
     return grads
 
 
@@ -623,7 +623,7 @@ def _multi_rngs(rngs, M: int):
         raise NsdError(f"multi: {len(rngs)} rng entries for {M} models")
     arr = (_lib.Rng * M)()
     for i, r in enumerate(rngs):
-        arr[i] = _lib.Rng(int(r["seed"]) & 0xFFFFFFFFFFFFFFFF, int(r["base_stream"]) & 0xFFFFFFFF, float(r["p_lstm"]), float(r["p_head"]))
+        arr[i] = _rng_struct(r)
     return arr
 
 

@@ -106,12 +106,61 @@ def test_refusals_before_any_launch(L, flags):
     assert bw(nb=need - 256) == E_WS and b"smaller than nsd_seq_workspace_bytes" in lib.nsd_last_error()
     assert bw(nb=need - 256, dx=None) == E_WS
     assert bw(rng=C.byref(bad_rng)) == E_INVALID
-    # an empty batch is a no-op that launches nothing
+    # nsd_seq_infer(d, params, x, flags, logits, probs, ws, bytes, stream)
+    inf = lambda params=FAKE, x=FAKE, fl=flags, logits=FAKE, ws=FAKE, nb=need: lib.nsd_seq_infer(
+        C.byref(d), params, x, fl, logits, None, ws, nb, None)
+    assert inf(x=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert inf(logits=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert inf(params=None) == E_INVALID
+    assert inf(ws=None) == E_INVALID
+    assert inf(fl=flags | (1 << 20)) == E_INVALID and b"unknown flag" in lib.nsd_last_error()
+    assert inf(nb=need - 256) == E_WS and b"smaller than nsd_seq_workspace_bytes" in lib.nsd_last_error()
+    # nsd_seq_train_fwd(d, params, x, rng, labels, scale, flags, ws, bytes, logits, stream)
+    tf = lambda params=FAKE, x=FAKE, rng=None, labels=FAKE, fl=flags, ws=FAKE, nb=need, logits=FAKE: lib.nsd_seq_train_fwd(
+        C.byref(d), params, x, rng, labels, 1.0, fl, ws, nb, logits, None)
+    assert tf(x=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert tf(logits=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert tf(labels=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert tf(params=None) == E_INVALID
+    assert tf(ws=None) == E_INVALID
+    assert tf(fl=flags | (1 << 20)) == E_INVALID and b"unknown flag" in lib.nsd_last_error()
+    assert tf(nb=need - 256) == E_WS
+    assert tf(rng=C.byref(bad_rng)) == E_INVALID and b"rng" in lib.nsd_last_error()
+    # nsd_seq_train_bwd(d, params, rng, flags, ws, bytes, grads, stream)
+    tb = lambda params=FAKE, rng=None, fl=flags, ws=FAKE, nb=need, grads=FAKE: lib.nsd_seq_train_bwd(
+        C.byref(d), params, rng, fl, ws, nb, grads, None)
+    assert tb(grads=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert tb(params=None) == E_INVALID
+    assert tb(ws=None) == E_INVALID
+    assert tb(fl=flags | (1 << 20)) == E_INVALID and b"unknown flag" in lib.nsd_last_error()
+    assert tb(nb=need - 256) == E_WS
+    assert tb(rng=C.byref(bad_rng)) == E_INVALID and b"rng" in lib.nsd_last_error()
+    # nsd_seq_loss_sum(d, flags, ws, bytes, out, stream)
+    ls = lambda fl=flags, ws=FAKE, nb=need, out=FAKE: lib.nsd_seq_loss_sum(C.byref(d), fl, ws, nb, out, None)
+    assert ls(ws=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert ls(out=None) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert ls(fl=flags | (1 << 20)) == E_INVALID and b"unknown flag" in lib.nsd_last_error()
+    assert ls(nb=need - 256) == E_WS
+    # when two things are wrong at once, the earlier check answers: dims and flags, null workspace / params, workspace size, the
+    # entry's own pointers, (empty batch), rng
+    assert inf(nb=need - 256, x=None) == E_WS
+    assert tf(nb=need - 256, labels=None, rng=C.byref(bad_rng)) == E_WS
+    assert tb(nb=need - 256, grads=None) == E_WS
+    assert ls(nb=need - 256, out=None) == E_INVALID         # (no parameters: its `out` is refused where the others' params are)
+    assert tf(x=None, rng=C.byref(bad_rng)) == E_INVALID and b"null" in lib.nsd_last_error()
+    assert tb(grads=None, rng=C.byref(bad_rng)) == E_INVALID and b"null" in lib.nsd_last_error()
+    # an empty batch is a no-op that launches nothing: it returns before the rng is looked at
     d0 = L.Dims(0, 7, 40, 64, 3, 4, 32)
     need0 = lib.nsd_seq_workspace_bytes(C.byref(d0), flags)
     assert lib.nsd_seq_train_fwd_logits(C.byref(d0), FAKE, FAKE, C.byref(ok_rng), flags, FAKE, need0, FAKE, None) == 0
     assert lib.nsd_seq_head_bwd(C.byref(d0), FAKE, None, FAKE, flags, FAKE, need0, None) == 0
     assert lib.nsd_seq_train_bwd_dx(C.byref(d0), FAKE, None, flags, FAKE, need0, FAKE, FAKE, None) == 0
+    assert lib.nsd_seq_infer(C.byref(d0), FAKE, FAKE, flags, FAKE, None, FAKE, need0, None) == 0
+    assert lib.nsd_seq_train_fwd(C.byref(d0), FAKE, FAKE, C.byref(bad_rng), FAKE, 1.0, flags, FAKE, need0, FAKE, None) == 0
+    assert lib.nsd_seq_train_bwd(C.byref(d0), FAKE, C.byref(bad_rng), flags, FAKE, need0, FAKE, None) == 0
+    assert lib.nsd_seq_train_fwd_logits(C.byref(d0), FAKE, FAKE, C.byref(bad_rng), flags, FAKE, need0, FAKE, None) == 0
+    assert lib.nsd_seq_head_bwd(C.byref(d0), FAKE, C.byref(bad_rng), FAKE, flags, FAKE, need0, None) == 0
+    assert lib.nsd_seq_train_bwd_dx(C.byref(d0), FAKE, C.byref(bad_rng), flags, FAKE, need0, FAKE, FAKE, None) == 0
 
 
 def test_profile_kinds_of_the_new_launches(L):
