@@ -240,6 +240,39 @@ int nsd_adam_step_dev(int64_t n, float *p, const float *g, float *m, float *v, f
                       float weight_decay, float grad_scale, const int64_t *step_dev, void *stream);
 
 /*
+ * ---- trial augmentation for the trainers (an EXTENSION: the reference's training notebook is missing and has none) ----
+ *
+ * x[B,T,C] -> y[B,T,C] (fp32) per model, every draw a pure function of (seed, stream, index) like the dropout streams, so a test can
+ * restate a launch bit for bit.  Stream: rng[m].base_stream + 3 (the trainers number a step's streams 4 * step + {0, 1, 2}; + 3 is this
+ * one), seed rng[m].seed; p_lstm / p_head are ignored.  With R(i) = value(seed, base_stream + 3, i) and U(r) = float(r >> 8) * 2^-24:
+ *   per-trial draws    index P(b, slot) = 2^63 | (uint64(b) << 16) | slot
+ *   per-element draws  index E(b, t, c) = (b * T + t) * C + c                       (top bit clear: the two never collide)
+ * b is the trial's index inside ITS model's batch, so model m draws what a single-model call with rng[m] draws.  Four operations, in this
+ * order, each SKIPPED when its parameter is 0 (all four off: y is a bitwise copy of x):
+ *   max_shift S    s_b = int(R(P(b, 0)) % (2S + 1)) - S;  v = x[b, clamp(t - s_b, 0, T - 1), c]   (edge sample repeated)
+ *   scale_range r  a_b = 1 + r * (2 U(R(P(b, 1))) - 1);   v = a_b * v                              (one factor per trial)
+ *   noise_std s    q = R(E(b, t, c)), n = float(sum of the four bytes of q - 510);  v = v + sk * n, sk = float(double(s) / sqrt(21845))
+ *                  (the byte sum has mean 510 and variance 21845: unit-variance Irwin-Hall(4) noise, bounded by +-3.45 s)
+ *   p_channel p    channel c of trial b is dropped when R(P(b, 256 + c)) < floor(p * 2^32):  v = 0 for its whole window (no rescaling)
+ * Every fp32 operation rounds on its own (no FMA contraction).  NSD_AUG_ZSCORE: y = the per-channel z-score of the augmented window,
+ * bitwise what nsd_zscore_fwd gives on the unfused output.
+ *   x_model_stride  floats between two models' windows; 0: every model augments the same windows with its own draws
+ *   step_dev        NULL, or a device step counter: base_stream = 4 * (step_dev[0] & 0x3fffffff) for every model, as nsd_train_masks_dev
+ * NSD_E_INVALID before any launch: M outside [1, NSD_MAX_MODELS]; NULL x / y / aug / rng; max_shift < 0 or >= T; scale_range or
+ * p_channel outside [0, 1); noise_std negative or not finite; C outside [1, 256]; T < 1; a negative x_model_stride or one in
+ * (0, B*T*C); y overlapping x.  B = 0 launches nothing.  Only d->B, T, C are read.  Additive: NSD_VERSION stays 301, a caller detects
+ * the feature by the symbol.
+ */
+typedef struct nsd_aug {
+    int32_t max_shift;
+    float scale_range, p_channel, noise_std;
+} nsd_aug;
+#define NSD_AUG_ZSCORE 1u
+int nsd_augment_path(const nsd_dims *d);       /* 1 where nsd_augment covers d->B / T / C, else 0 */
+int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug, const nsd_rng *rng,
+                const int64_t *step_dev, uint32_t flags, float *y, void *stream);
+
+/*
  * ---- model-batched H = 48 path: M models of one shape trained / evaluated in the launches one model uses ----
  *
  * Folds, seeds and ensembles of EEG_LSTM (lstm_eeg_model.py:13-39): each model has its own parameters, windows, labels and random

@@ -29,6 +29,14 @@ class Rng(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("base_stream", C.c_uint32), ("p_lstm", C.c_float), ("p_head", C.c_float)]
 
 
+class Aug(C.Structure):
+    """nsd_aug of include/nsd.h"""
+    _fields_ = [("max_shift", C.c_int32), ("scale_range", C.c_float), ("p_channel", C.c_float), ("noise_std", C.c_float)]
+
+
+NSD_AUG_ZSCORE = 1
+
+
 class NsdError(RuntimeError):
     pass
 
@@ -92,6 +100,9 @@ SYMBOLS = {
     "nsd_seq_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
     "nsd_seq_guard": (C.c_int, [_vp, _fp, _vp]),
     "nsd_train_masks": (C.c_int, [C.c_uint64, C.c_uint32, C.c_float, C.c_float, C.c_int64, _fp, C.c_int64, _fp, _fp, _vp]),
+    # trial augmentation for the trainers
+    "nsd_augment_path": (C.c_int, [_dp]),
+    "nsd_augment": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _vp, _vp, _vp, C.c_uint32, _fp, _vp]),
     # model-batched H = 48 path (several models per launch)
     "nsd_multi_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_multi_workspace_bytes": (C.c_int64, [_dp, C.c_int32, C.POINTER(WsLayout)]),

@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <stdlib.h>
+#include <math.h>
 #include "nsd_args.h"
 #include "nsd_multi.h"
 #include "nsd_bf16.h"
@@ -614,6 +615,47 @@ int nsd_gemm_bf16(const void *A, int64_t lda, int32_t a_kmajor, const void *B, i
     g.A = (const bf16_t *)A; g.B = (const bf16_t *)B; g.lda = lda; g.ldb = ldb; g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor;
     g.b_shift = b_shift; g.C = C; g.ldc = ldc; g.bias = bias; g.M = M; g.N = N; g.K = K; g.splits = splits; g.epi = epilogue;
     return nsd_gemm_bf16_launch(g, (hipStream_t)stream);
+}
+
+// ---- trial augmentation (nsd_augment, include/nsd.h; nsd_augment.hip) --------------------------------------------------------------
+static bool augment_shape(const nsd_dims *d) {
+    return d && d->B >= 0 && d->T >= 1 && d->C >= 1 && d->C <= 256 && (int64_t)d->T * d->C <= 0x7fffffff;
+}
+int nsd_augment_path(const nsd_dims *d) { return augment_shape(d) ? 1 : 0; }
+
+int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug, const nsd_rng *rng,
+                const int64_t *step_dev, uint32_t flags, float *y, void *stream) {
+    static const char *who = "augment";
+    if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (!x || !y || !aug || !rng) { nsd_set_error("%s: null pointer (x, y, aug, rng)", who); return NSD_E_INVALID; }
+    if (!augment_shape(d)) { nsd_set_error("%s: shape B=%d T=%d C=%d outside nsd_augment_path (B >= 0, T >= 1, 1 <= C <= 256)", who, d->B, d->T, d->C); return NSD_E_INVALID; }
+    if (flags & ~NSD_AUG_ZSCORE) { nsd_set_error("%s: unknown flag bits 0x%x", who, flags); return NSD_E_INVALID; }
+    if (aug->max_shift < 0 || aug->max_shift >= d->T) { nsd_set_error("%s: max_shift %d outside [0, T = %d)", who, aug->max_shift, d->T); return NSD_E_INVALID; }
+    if (!(aug->scale_range >= 0.f && aug->scale_range < 1.f)) { nsd_set_error("%s: scale_range %g outside [0, 1)", who, aug->scale_range); return NSD_E_INVALID; }
+    if (!(aug->p_channel >= 0.f && aug->p_channel < 1.f)) { nsd_set_error("%s: p_channel %g outside [0, 1)", who, aug->p_channel); return NSD_E_INVALID; }
+    if (!(aug->noise_std >= 0.f && aug->noise_std <= 3.4028234e38f)) { nsd_set_error("%s: noise_std %g negative or not finite", who, aug->noise_std); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
+        nsd_set_error("%s: x_model_stride %lld: 0 (one window set for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
+        return NSD_E_INVALID;
+    }
+    if ((int64_t)M * d->B > 0x7fffffff) { nsd_set_error("%s: M * B = %lld trials in one launch", who, (long long)M * d->B); return NSD_E_INVALID; }
+    const float *x_end = x + (M - 1) * x_model_stride + n;
+    const float *y_end = y + (int64_t)M * n;
+    if (n > 0 && x < y_end && y < x_end) { nsd_set_error("%s: y overlaps x (the shift reads other time steps: no in-place form)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    AugArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.y = y; a.x_stride = x_model_stride; a.step_dev = (const long long *)step_dev;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.M = M;
+    a.max_shift = aug->max_shift;
+    a.scale_range = aug->scale_range; a.scale_on = aug->scale_range != 0.f;
+    a.noise_k = (float)((double)aug->noise_std / sqrt(21845.0)); a.noise_on = aug->noise_std != 0.f;
+    a.thr_channel = nsd_drop_threshold(aug->p_channel); a.drop_on = aug->p_channel != 0.f;
+    a.zscore = (flags & NSD_AUG_ZSCORE) != 0;
+    for (int m = 0; m < M; ++m) { a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream; }
+    return nsd_augment_launch(a, (hipStream_t)stream);
 }
 
 // ---- model-batched H = 48 path (nsd_multi_*, include/nsd.h; nsd_multi.h) ----------------------------------------------------------

@@ -108,6 +108,20 @@ int nsd_lstm_batched_bwd(const nsd_dims *d, const ParamLayout &pl, const float *
 int nsd_head_launch(const HeadArgs &a, bool bwd, hipStream_t st);
 int nsd_head_train_launch(const HeadArgs &a, hipStream_t st);   // 1 launched, 0 shape does not fit, <0 error
 int nsd_zscore_launch(const float *x, float *y, int B, int T, int C, hipStream_t st);
+// trial augmentation (nsd_augment of nsd.h; nsd_augment.hip): thresholds and the noise factor are formed on the host
+struct AugArgs {
+    const float *x; float *y;
+    long long x_stride;                      // floats between two models' windows (0: shared)
+    const long long *step_dev;               // null, or the device step counter the stream id is formed from
+    int B, T, C, M;
+    int max_shift;                           // 0: off
+    float scale_range, noise_k;              // noise_k = float(double(noise_std) / sqrt(21845))
+    uint32_t thr_channel;                    // a channel is dropped when its draw is below this
+    int scale_on, noise_on, drop_on, zscore; // an operation is on when its parameter is not 0 (noise_k may round to 0 while noise_std is not)
+    uint64_t seed[NSD_MAX_MODELS];
+    uint32_t base[NSD_MAX_MODELS];
+};
+int nsd_augment_launch(const AugArgs &a, hipStream_t st);
 int nsd_grad_reduce_launch(const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs,
                            long ph, int n_hslabs, float *grads, int accumulate, hipStream_t st);
 int nsd_grad_reduce_adam_launch(const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs,

@@ -39,10 +39,12 @@ class ModelBatchTrainer:
 
     The models' parameters are packed into one [M, P] buffer and each model's parameters are re-pointed as views into its row, so
     every model stays an ordinary module (forward, state_dict, save_reference_checkpoint work as before).  step(x, y) takes
-    x [M,B,T,C] (per-model windows) or a shared [B,T,C], and y [M,B] or a shared [B]."""
+    x [M,B,T,C] (per-model windows) or a shared [B,T,C], and y [M,B] or a shared [B].  augment: ops.Augment, applied per model as
+    Trainer does."""
 
     def __init__(self, models: Sequence[EEG_LSTM], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None):
+                 weight_decay: float = 0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
+                 augment: Optional[ops.Augment] = None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -71,6 +73,9 @@ class ModelBatchTrainer:
         self.seeds = [(int(s) + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF for s in seeds]
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.stochastic = stochastic
+        # as Trainer: model m's trials are augmented with the draws of Trainer(model_m, seed=seeds[m], augment=augment), all models in
+        # one launch; None (or every operation off) is the unaugmented step
+        self.augment = augment if augment is not None and augment.enabled and stochastic else None
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
         self.grads = torch.zeros_like(self.params)
@@ -99,7 +104,7 @@ class ModelBatchTrainer:
         if not ops.multi_path(self.spec, M, B, T):
             raise NsdError(f"ModelBatchTrainer.step: T = {T} is outside the model-batched path (nsd_multi_path: T <= 1024)")
         x = x.contiguous().float()
-        if self.models[0].normalize:                     # as Trainer: the model is trained on what it is evaluated on
+        if self.models[0].normalize and self.augment is None:     # as Trainer: the model is trained on what it is evaluated on
             x = ops.zscore(x.reshape(-1, T, x.shape[-1])).view(x.shape)
         y = y.to(torch.int32)
         if y.dim() == 1:
@@ -112,6 +117,8 @@ class ModelBatchTrainer:
         self.step_count += 1
         sid = (self.step_count & 0x3FFFFFFF) * 4
         mdl = self.models[0]
+        if self.augment is not None:                     # one launch: a shared [B,T,C] becomes [M,B,T,C], each model with its own draws
+            x = ops.augment(x, self.augment, [dict(seed=s, base_stream=sid) for s in self.seeds], M=M, zscore=mdl.normalize)
         rngs = ([dict(seed=s, base_stream=sid, p_lstm=mdl.dropout_p, p_head=mdl.head_dropout_p) for s in self.seeds]
                 if self.stochastic else None)
         buf = self._buffers(B, T)

@@ -262,6 +262,73 @@ def _zscore_launch(x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor
     return y[0] if squeeze else y
 
 
+@dataclass(frozen=True)
+class Augment:
+    """Trial augmentation of a training step (nsd_aug of include/nsd.h; an extension, the reference has none).  Each operation is OFF
+    at 0.  max_shift: time shift of up to +-N steps per trial (edge sample repeated); scale_range r: one amplitude factor in
+    [1 - r, 1 + r] per trial; p_channel: probability that a channel of a trial is zeroed; noise_std: additive unit-variance
+    Irwin-Hall(4) noise times this, per element."""
+    max_shift: int = 0
+    scale_range: float = 0.0
+    p_channel: float = 0.0
+    noise_std: float = 0.0
+
+    def __post_init__(self):
+        if int(self.max_shift) != self.max_shift or self.max_shift < 0:
+            raise ValueError(f"Augment: max_shift {self.max_shift!r} must be an integer >= 0")
+        if not 0.0 <= self.scale_range < 1.0:
+            raise ValueError(f"Augment: scale_range {self.scale_range!r} outside [0, 1)")
+        if not 0.0 <= self.p_channel < 1.0:
+            raise ValueError(f"Augment: p_channel {self.p_channel!r} outside [0, 1)")
+        if not 0.0 <= self.noise_std < float("inf"):
+            raise ValueError(f"Augment: noise_std {self.noise_std!r} negative or not finite")
+
+    @property
+    def enabled(self) -> bool:
+        return bool(self.max_shift or self.scale_range or self.p_channel or self.noise_std)
+
+
+def augment(x: torch.Tensor, aug: Augment, rngs, *, M: int = 1, zscore: bool = False, step_dev: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nsd_augment: the augmented (and, with zscore, z-scored) windows, one launch for all models.
+    x [B,T,C]: the windows of one model (M = 1 -> [B,T,C]) or shared by M models, each with its own draws (-> [M,B,T,C]);
+    x [M,B,T,C]: per-model windows -> [M,B,T,C].  rngs: dict(seed=, base_stream=) or M of them (model m draws what a single-model call
+    with rngs[m] draws; the stream used is base_stream + 3).  step_dev: device int64 step counter; base_stream is then
+    4 * (step_dev[0] & 0x3fffffff) for every model (hipGraph replay).  All operations off: a bitwise copy of x."""
+    if isinstance(rngs, dict):
+        rngs = [rngs]
+    if x.dim() == 4:
+        Mx, B, T, Cc = (int(v) for v in x.shape)
+        if M not in (1, Mx):
+            raise NsdError(f"augment: x has {Mx} model slices, M = {M}")
+        M, stride, shape = Mx, B * T * Cc, (Mx, B, T, Cc)
+    elif x.dim() == 3:
+        B, T, Cc = (int(v) for v in x.shape)
+        M, stride = int(M), 0
+        shape = (B, T, Cc) if M == 1 else (M, B, T, Cc)
+    else:
+        raise NsdError(f"augment: x must be [B,T,C] or [M,B,T,C], got {tuple(x.shape)}")
+    if len(rngs) != M:
+        raise NsdError(f"augment: {len(rngs)} rng entries for {M} models")
+    r = (_lib.Rng * M)()
+    for i, g in enumerate(rngs):
+        r[i] = _lib.Rng(int(g["seed"]) & 0xFFFFFFFFFFFFFFFF, int(g["base_stream"]) & 0xFFFFFFFF, 0.0, 0.0)
+    a = _lib.Aug(int(aug.max_shift), float(aug.scale_range), float(aug.p_channel), float(aug.noise_std))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if out.numel() != M * B * T * Cc:
+        raise NsdError(f"augment: out has {out.numel()} elements for {M} x {B} x {T} x {Cc}")
+    sp = None
+    if step_dev is not None:
+        if step_dev.dtype != torch.int64 or not step_dev.is_cuda:
+            raise NsdError("augment: step_dev must be an int64 tensor on the device")
+        sp = step_dev.data_ptr()
+    d = Dims(B, T, Cc, 1, 1, 1, 1)
+    _call("nsd_augment", x.device, C.byref(d), M, _dev_f32(x, "x"), stride, C.byref(a), C.cast(r, C.c_void_p), sp,
+          _lib.NSD_AUG_ZSCORE if zscore else 0, _dev_f32(out, "out"), STREAM)
+    return out
+
+
 def infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, *, residual: bool = False,
           want_probs: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Eval-mode forward: logits [B,K] (+ softmax probabilities)."""

@@ -20,6 +20,7 @@ import torch
 
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
+from .ops import Augment
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
 
@@ -101,7 +102,17 @@ def main(argv=None) -> int:
                                                                 "of them (ModelBatchTrainer; single GPU, H = 48 fp32)")
     ap.add_argument("--kfold-seeds", type=int, default=1, help="with --kfold K --concurrent: the K folds for N seeds --seed .. --seed + N - 1 "
                                                               "in the same launches (N * K <= 32)")
+    ap.add_argument("--aug-shift", type=int, default=0, help="augmentation: shift each training trial by up to +-N steps (0 = off)")
+    ap.add_argument("--aug-scale", type=float, default=0.0, help="augmentation: one amplitude factor in [1 - r, 1 + r] per trial (0 = off)")
+    ap.add_argument("--aug-channel-drop", type=float, default=0.0, help="augmentation: probability that a channel of a trial is zeroed (0 = off)")
+    ap.add_argument("--aug-noise", type=float, default=0.0, help="augmentation: standard deviation of additive noise per sample (0 = off)")
     args = ap.parse_args(argv)
+    try:
+        augment = Augment(max_shift=args.aug_shift, scale_range=args.aug_scale, p_channel=args.aug_channel_drop, noise_std=args.aug_noise)
+    except ValueError as e:
+        ap.error(str(e))
+    if augment.max_shift >= args.T:
+        ap.error(f"--aug-shift {augment.max_shift} must be smaller than --T {args.T}")
     if args.kfold_seeds != 1 and not args.concurrent:
         ap.error("--kfold-seeds needs --kfold K --concurrent (sequentially: one --kfold run per --seed)")
     if args.concurrent:
@@ -154,7 +165,7 @@ def main(argv=None) -> int:
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
                          bidirectional=args.bidirectional).to(dev).train()
-        trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1)
+        trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment)
         tr_dev = torch.from_numpy(tr_idx).to(dev)
         best = (-1.0, -1)
         t0 = time.time()
@@ -195,7 +206,7 @@ def main(argv=None) -> int:
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
             models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize).to(dev).train())
-        mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs])
+        mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment)
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
         t0 = time.time()
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in runs]

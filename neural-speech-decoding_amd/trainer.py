@@ -92,7 +92,8 @@ def broadcast_parameters(flat: torch.Tensor, group=None, src: int = 0) -> None:
 
 class Trainer:
     def __init__(self, model: EEG_LSTM, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None):
+                 weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None,
+                 augment: Optional[ops.Augment] = None):
         self.model = model
         self.spec = model.spec
         self.flat = model.flat_parameters()
@@ -115,6 +116,9 @@ class Trainer:
         self.in_kernel_rng = True        # dropout / RReLU streams generated inside the kernels where the shape allows
         self.seed = (int(seed) + 0x9E3779B97F4A7C15 * (self.rank + 1)) & 0xFFFFFFFFFFFFFFFF
         self.stochastic = stochastic
+        # trial augmentation (ops.Augment; stream 4 * step + 3 of this rank's seed): training steps only, and only with the other
+        # stochastic parts on.  None -- also for an Augment with every operation off -- is the unaugmented step, launch for launch.
+        self.augment = augment if augment is not None and augment.enabled and stochastic else None
         self.step_count = 0
         self._bufs = {}
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.flat.device)
@@ -169,8 +173,12 @@ class Trainer:
 
     def _prepare_input(self, x: torch.Tensor) -> torch.Tensor:
         """What EEG_LSTM.forward does to a window before the LSTM (lstm_eeg_model.py facade): contiguous fp32 and, for
-        normalize=True, the per-channel z-score -- the model must be trained on what it is evaluated on."""
+        normalize=True, the per-channel z-score -- the model must be trained on what it is evaluated on.  With augmentation on, ONE
+        nsd_augment launch does both (it takes the z-score launch's place)."""
         x = x.contiguous().float()
+        if self.augment is not None and x.shape[0] > 0:
+            return ops.augment(x, self.augment, dict(seed=self.seed, base_stream=(self.step_count & 0x3FFFFFFF) * 4),
+                               zscore=self.model.normalize)
         return ops.zscore(x) if self.model.normalize and x.shape[0] > 0 else x
 
     def _local_grads(self, x: torch.Tensor, y: torch.Tensor, scale: float, fuse_adam: bool = False) -> None:
@@ -263,10 +271,14 @@ class Trainer:
         elif self.stochastic:
             raise ops.NsdError("graph step needs all three random streams (dropout > 0, num_layers > 1) or stochastic=False")
         xin = buf["x"]
-        if self.model.normalize:                               # a static buffer of its own: nothing is allocated inside the capture
+        if self.model.normalize or self.augment is not None:   # a static buffer of its own: nothing is allocated inside the capture
             if "xn" not in buf:
                 buf["xn"] = torch.empty_like(buf["x"])
-            xin = ops.zscore(buf["x"], out=buf["xn"])
+            if self.augment is not None:                       # the stream id comes from the device step counter: the graph replays it
+                xin = ops.augment(buf["x"], self.augment, dict(seed=self.seed, base_stream=0), zscore=self.model.normalize,
+                                  step_dev=self._step_dev, out=buf["xn"])
+            else:
+                xin = ops.zscore(buf["x"], out=buf["xn"])
         ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], buf["y"], buf["logits"], self.grads,
                              scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual)
 
