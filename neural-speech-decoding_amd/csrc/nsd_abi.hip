@@ -72,11 +72,17 @@ static int fast_path_ok(const nsd_dims *d) {
     return d->L == 2 && (d->H == 32 || d->H == 48 || d->H == 64) && d->C <= 8;
 }
 
-static nsd_ws_layout make_ws(const nsd_dims *d, bool have_device) {
+static inline ParamLayout layout_of(const nsd_dims *d) { return nsd_make_layout(d->C, d->H, d->L, d->K, d->F); }
+static inline int residual_of(uint32_t flags) { return (flags & NSD_FLAG_RESIDUAL) ? 1 : 0; }
+
+// workspace of M models of d->B trials each: one batch of M*B trials, partitioned by model (nsd_multi.h); M = 1 is one model's workspace
+static nsd_ws_layout ws_layout(const nsd_dims *d, int M, bool have_device) {
     nsd_ws_layout w;
     memset(&w, 0, sizeof(w));
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    const int64_t B = d->B, T = d->T, H = d->H, L = d->L, F = d->F;
+    const ParamLayout pl = layout_of(d);
+    nsd_dims all = *d;
+    all.B = M * d->B;
+    const int64_t B = all.B, T = d->T, H = d->H, L = d->L, F = d->F;
     int64_t p = 0;
     w.hseq = p;    p = align4(p + L * B * T * H);
     w.cseq = p;    p = align4(p + L * B * T * H);
@@ -92,10 +98,13 @@ static nsd_ws_layout make_ws(const nsd_dims *d, bool have_device) {
     w.adpack = p;  p = align4(p + B * T * 4);
     // LSTM slabs: one per backward workgroup (<= #CUs); head slabs: one per trial, stored behind them.
     // Without a device (symbol / layout checks on CPU) assume the MI355X's 256 CUs.
-    const bool fast = fast_path_ok(d) != 0;
+    const bool fast = fast_path_ok(&all) != 0;
     int64_t nsl = B < 256 ? B : 256;
     if (have_device) nsl = nsd_lstm2_bwd_groups((int)B, 1);
     if (nsl < 1 || !fast) nsl = 1;       // generic path: the weight-gradient GEMMs write one slab
+    // several models: each writes the slabs of its own G workgroups, so there is room for M * G
+    const int64_t own = M > 1 ? (int64_t)M * nsd_lstm2_bwd_groups(d->B > 0 ? d->B : 1, M) : 0;
+    if (nsl < own) nsl = own;
     w.n_slabs = nsl;
     w.slabs = p;   p = align4(p + nsl * align4(pl.lstm_total));
     w.hslabs = p;  p = align4(p + B * (pl.total - pl.lstm_total));
@@ -117,16 +126,41 @@ static long long *const g_dbg = nullptr;
 static int ablate_mask() { return 0; }
 #endif
 
-// workspace size check shared by every entry point that touches the training workspace
-static int check_ws(const nsd_dims *d, const void *workspace, int64_t workspace_bytes, const char *who, nsd_ws_layout *w) {
+// ---- what an entry point works on once its arguments are accepted -----------------------------------------------------------------
+struct Ctx {
+    const nsd_dims *d;
+    int M;                                   // models in the workspace (1: the single-model entry points)
+    ParamLayout pl;
+    nsd_ws_layout w;
+    float *ws;
+    hipStream_t st;
+    float *at(int64_t region) const { return ws + region; }
+};
+constexpr int EMPTY_BATCH = 1;               // accepted, nothing to launch
+static int leave(int rc) { return rc == EMPTY_BATCH ? NSD_OK : rc; }
+
+// The workspace binder of every entry point that touches the training workspace of M models (nsd_workspace_bytes() is M = 1): refuses a
+// null or short workspace, fills the context, reports the empty batch.  (who: "multi_..." names nsd_multi_workspace_bytes() in the text)
+static int bind_ws(Ctx *c, const nsd_dims *d, int M, const void *workspace, int64_t bytes, const char *who, void *stream) {
     if (!workspace) { nsd_set_error("%s: workspace is NULL", who); return NSD_E_INVALID; }
-    *w = make_ws(d, true);
-    const int64_t need = w->total * (int64_t)sizeof(float);
-    if (workspace_bytes < need) {
-        nsd_set_error("%s: workspace of %lld bytes is smaller than nsd_workspace_bytes() = %lld", who, (long long)workspace_bytes, (long long)need);
+    c->w = ws_layout(d, M, true);
+    const int64_t need = c->w.total * (int64_t)sizeof(float);
+    if (bytes < need) {
+        nsd_set_error("%s: workspace of %lld bytes is smaller than %s() = %lld", who, (long long)bytes,
+                      strncmp(who, "multi_", 6) ? "nsd_workspace_bytes" : "nsd_multi_workspace_bytes", (long long)need);
         return NSD_E_WORKSPACE;
     }
-    return NSD_OK;
+    c->d = d; c->M = M; c->pl = layout_of(d); c->ws = (float *)workspace; c->st = (hipStream_t)stream;
+    return d->B == 0 ? EMPTY_BATCH : NSD_OK;
+}
+
+// The preamble of the single-model fp32 workspace entry points.  Refusals, in this order: dims; ptrs_ok (the entry's null-pointer set, the
+// workspace among them); the entry's own refusal (its text, or null); the workspace size; then the empty batch (EMPTY_BATCH: leave(rc)).
+static int enter(Ctx *c, const char *who, const nsd_dims *d, bool ptrs_ok, const char *refusal, const void *workspace, int64_t bytes, void *stream) {
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (!ptrs_ok) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (refusal) { nsd_set_error("%s", refusal); return NSD_E_INVALID; }
+    return bind_ws(c, d, 1, workspace, bytes, who, stream);
 }
 
 static bool device_present() {
@@ -160,7 +194,7 @@ int nsd_param_layout(int32_t C, int32_t H, int32_t L, int32_t K, int32_t F, int6
 
 int64_t nsd_workspace_bytes(const nsd_dims *d, nsd_ws_layout *layout_out) {
     if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    const nsd_ws_layout w = make_ws(d, device_present());
+    const nsd_ws_layout w = ws_layout(d, 1, device_present());
     if (layout_out) *layout_out = w;
     return w.total * (int64_t)sizeof(float);
 }
@@ -176,11 +210,10 @@ int nsd_zscore_fwd(const float *x, float *y, int32_t B, int32_t T, int32_t C, vo
 }
 
 // ---- shared argument builders -----------------------------------------------------------------------------
-// (M models of d->B trials each in one workspace, nsd_multi.h: the per-layer stride of the saved [L, M*B, T, H] regions; M = 1 otherwise)
-static int build_lstm_fwd(const nsd_dims *d, int M, const float *params, const float *x, const float *drop_lstm,
-                          uint32_t flags, float *ws, const nsd_ws_layout &w, bool train, float *top_only,
-                          Lstm2FwdArgs *out) {
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+// (c: the bound training workspace -- c->M models: the per-layer stride of its saved [L, M*B, T, H] regions -- or null: inference into top_only)
+static Lstm2FwdArgs build_lstm_fwd(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, uint32_t flags,
+                                   const Ctx *c, float *top_only) {
+    const ParamLayout pl = layout_of(d);
     Lstm2FwdArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x;
@@ -189,24 +222,24 @@ static int build_lstm_fwd(const nsd_dims *d, int M, const float *params, const f
     a.mask = drop_lstm;
     a.dbg = g_dbg;
     a.B = d->B; a.T = d->T; a.C = d->C;
-    a.residual = (flags & NSD_FLAG_RESIDUAL) ? 1 : 0;
+    a.residual = residual_of(flags);
     a.ablate = ablate_mask();
-    const int64_t BTH = (int64_t)M * d->B * d->T * d->H;
-    if (train) {
-        a.hseq0 = ws + w.hseq; a.hseq1 = ws + w.hseq + BTH;
-        a.cseq0 = ws + w.cseq; a.cseq1 = ws + w.cseq + BTH;
-        a.gact0 = ws + w.gact; a.gact1 = ws + w.gact + 4 * BTH;
-        a.inseq = ws + w.inseq;
-        a.top = ws + w.top;
+    if (c) {
+        const int64_t BTH = (int64_t)c->M * d->B * d->T * d->H;
+        a.hseq0 = c->at(c->w.hseq); a.hseq1 = a.hseq0 + BTH;
+        a.cseq0 = c->at(c->w.cseq); a.cseq1 = a.cseq0 + BTH;
+        a.gact0 = c->at(c->w.gact); a.gact1 = a.gact0 + 4 * BTH;
+        a.inseq = c->at(c->w.inseq);
+        a.top = c->at(c->w.top);
     } else {
         a.top = top_only;
     }
-    *out = a;
-    return NSD_OK;
+    return a;
 }
 
-static HeadArgs build_head(const nsd_dims *d, const float *params) {
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
+// the head's parameters (c == null: inference) and, with them, the head's regions of the bound workspace: the one region -> field map
+static HeadArgs build_head(const nsd_dims *d, const float *params, const Ctx *c = nullptr) {
+    const ParamLayout pl = layout_of(d);
     HeadArgs h;
     memset(&h, 0, sizeof(h));
     h.ln_w = params + pl.ln_w; h.ln_b = params + pl.ln_b; h.attn_w = params + pl.attn_w; h.attn_b = params + pl.attn_b;
@@ -218,6 +251,11 @@ static HeadArgs build_head(const nsd_dims *d, const float *params) {
     h.o_fc3_w = pl.fc3_w - pl.lstm_total; h.o_fc3_b = pl.fc3_b - pl.lstm_total;
     h.Ph = pl.total - pl.lstm_total;
     h.B = d->B; h.T = d->T; h.H = d->H; h.F = d->F; h.K = d->K;
+    if (c) {
+        h.top = c->at(c->w.top); h.alpha = c->at(c->w.alpha); h.pooled = c->at(c->w.pooled); h.fc0_pre = c->at(c->w.fc0_pre);
+        h.loss = c->at(c->w.loss); h.dscore = c->at(c->w.dscore); h.dpooled = c->at(c->w.dpooled);
+        h.hslabs = c->at(c->w.hslabs); h.adpack = c->at(c->w.adpack);
+    }
     return h;
 }
 
@@ -227,48 +265,78 @@ static void attach_head(Lstm2FwdArgs *a, const HeadArgs &h) {
     a->fc0_w = h.fc0_w; a->fc0_b = h.fc0_b; a->fc3_w = h.fc3_w; a->fc3_b = h.fc3_b;
     a->eval_slope = h.eval_slope; a->K = h.K; a->F = h.F;
 }
-// the fused training head: forward, loss, and the head's backward up to dscore / dpooled and the per-trial head slabs
-static void attach_head_train(Lstm2FwdArgs *a, const HeadArgs &h, const int32_t *labels, float scale, float *logits, float *ws,
-                              const nsd_ws_layout &w) {
+// the fused training head: forward, loss, and the head's backward up to dscore / dpooled and the per-trial head slabs (h: bound to the workspace)
+static void attach_head_train(Lstm2FwdArgs *a, const HeadArgs &h, const int32_t *labels, float scale, float *logits) {
     attach_head(a, h);
     a->head_train = 1;
     if (!a->residual) a->top = nullptr;      // top == layer-1 h: the kernel's tail reads hseq1, the saver skips the duplicate
     a->labels = labels; a->scale = scale;
-    a->logits = logits; a->loss = ws + w.loss; a->alpha = ws + w.alpha; a->pooled = ws + w.pooled;
-    a->fc0_pre = ws + w.fc0_pre; a->dscore = ws + w.dscore; a->dpooled = ws + w.dpooled;
-    a->adpack = ws + w.adpack; a->hslabs = ws + w.hslabs;
+    a->logits = logits; a->loss = h.loss; a->alpha = h.alpha; a->pooled = h.pooled;
+    a->fc0_pre = h.fc0_pre; a->dscore = h.dscore; a->dpooled = h.dpooled;
+    a->adpack = h.adpack; a->hslabs = h.hslabs;
     a->o_ln_w = h.o_ln_w; a->o_ln_b = h.o_ln_b; a->o_attn_w = h.o_attn_w; a->o_attn_b = h.o_attn_b;
     a->o_fc0_w = h.o_fc0_w; a->o_fc0_b = h.o_fc0_b; a->o_fc3_w = h.o_fc3_w; a->o_fc3_b = h.o_fc3_b; a->Ph = h.Ph;
 }
 
-// (M as in build_lstm_fwd; mask, rng and da0_out are the caller's)
-static Lstm2BwdArgs build_lstm_bwd(const nsd_dims *d, int M, const float *params, const float *x, float *ws, const nsd_ws_layout &w,
-                                   uint32_t flags) {
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    const int64_t BTH = (int64_t)M * d->B * d->T * d->H;
+// (c.M as in build_lstm_fwd; mask, rng and da0_out are the caller's)
+static Lstm2BwdArgs build_lstm_bwd(const Ctx &c, const float *params, const float *x, uint32_t flags) {
+    const nsd_dims *d = c.d;
+    const ParamLayout &pl = c.pl;
+    const int64_t BTH = (int64_t)c.M * d->B * d->T * d->H;
     Lstm2BwdArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x;
     a.w_hh0 = params + pl.w_hh[0]; a.w_ih1 = params + pl.w_ih[1]; a.w_hh1 = params + pl.w_hh[1];
     a.attn_w = params + pl.attn_w;
-    a.hseq0 = ws + w.hseq; a.hseq1 = ws + w.hseq + BTH;
-    a.cseq0 = ws + w.cseq; a.cseq1 = ws + w.cseq + BTH;
-    a.gact0 = ws + w.gact; a.gact1 = ws + w.gact + 4 * BTH;
-    a.in1seq = ws + w.inseq;
-    a.alpha = ws + w.alpha; a.dscore = ws + w.dscore; a.dpooled = ws + w.dpooled;
-    a.dsc_pack = ws + w.adpack;
-    a.pooled = ws + w.pooled; a.dscore_out = ws + w.dscore; a.hslabs = ws + w.hslabs;
-    const HeadArgs h = build_head(d, params);
+    a.hseq0 = c.at(c.w.hseq); a.hseq1 = a.hseq0 + BTH;
+    a.cseq0 = c.at(c.w.cseq); a.cseq1 = a.cseq0 + BTH;
+    a.gact0 = c.at(c.w.gact); a.gact1 = a.gact0 + 4 * BTH;
+    a.in1seq = c.at(c.w.inseq);
+    const HeadArgs h = build_head(d, params, &c);
+    a.alpha = h.alpha; a.dscore = h.dscore; a.dpooled = h.dpooled;
+    a.dsc_pack = h.adpack;
+    a.pooled = h.pooled; a.dscore_out = h.dscore; a.hslabs = h.hslabs;
     a.Ph = h.Ph; a.o_attn_w = h.o_attn_w; a.o_attn_b = h.o_attn_b;
     a.dbg = g_dbg;
-    a.slabs = ws + w.slabs;
+    a.slabs = c.at(c.w.slabs);
     a.slab_stride = align4(pl.lstm_total);
     a.o_w_ih0 = pl.w_ih[0]; a.o_w_hh0 = pl.w_hh[0]; a.o_b_ih0 = pl.b_ih[0]; a.o_b_hh0 = pl.b_hh[0];
     a.o_w_ih1 = pl.w_ih[1]; a.o_w_hh1 = pl.w_hh[1]; a.o_b_ih1 = pl.b_ih[1]; a.o_b_hh1 = pl.b_hh[1];
     a.B = d->B; a.T = d->T; a.C = d->C;
-    a.residual = (flags & NSD_FLAG_RESIDUAL) ? 1 : 0;
+    a.residual = residual_of(flags);
     a.ablate = ablate_mask();
     return a;
+}
+
+// the layer-by-layer stacks' argument block (StackArgs, nsd_args.h).  c: the bound training workspace, or null: inference in `scratch`
+// (nsd_infer_scratch_bytes(): top_out, the [B,T,H] ping-pong buffer, the batched path's cell state)
+static StackArgs stack_args(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, uint32_t flags, const Ctx *c,
+                            float *scratch) {
+    StackArgs s;
+    memset(&s, 0, sizeof(s));
+    s.d = *d; s.pl = layout_of(d);
+    s.params = params; s.x = x; s.drop_lstm = drop_lstm;
+    s.residual = residual_of(flags);
+    s.bf16 = (flags & NSD_FLAG_BF16) != 0;
+    if (c) {
+        const nsd_ws_layout &w = c->w;
+        s.hseq = c->at(w.hseq); s.cseq = c->at(w.cseq); s.gact = c->at(w.gact); s.inseq = c->at(w.inseq); s.top_out = c->at(w.top);
+        s.alpha = c->at(w.alpha); s.dscore = c->at(w.dscore); s.dpooled = c->at(w.dpooled);
+        s.da_seq = c->at(w.da_seq);
+        s.din_a = c->at(w.din); s.din_b = s.din_a + s.BTH(); s.state = s.din_b + s.BTH();
+        s.slab = c->at(w.slabs);
+    } else {
+        const int64_t bth = align4(s.BTH());
+        s.top_out = scratch; s.scratch2 = scratch + bth; s.cstate = scratch + 2 * bth;
+    }
+    return s;
+}
+
+// the gradient slabs of the bound workspace (per model: the slabs of its backward workgroups, one head slab per trial)
+static SlabSet slab_set(const Ctx &c) {
+    const int B = c.d->B;
+    const int n = B <= 0 ? 0 : c.M > 1 ? nsd_lstm2_bwd_groups(B, c.M) : (int)c.w.n_slabs;
+    return SlabSet{c.at(c.w.slabs), align4(c.pl.lstm_total), n, c.pl.lstm_total, c.at(c.w.hslabs), c.pl.total - c.pl.lstm_total, B};
 }
 
 #define REQUIRE_FAST(d, name)                                                                              \
@@ -302,10 +370,7 @@ int nsd_infer(const nsd_dims *d, const float *params, const float *x, uint32_t f
     if (d->B == 0) return NSD_OK;
     int rc;
     if (fast_path_ok(d)) {
-        nsd_ws_layout w;
-        memset(&w, 0, sizeof(w));
-        Lstm2FwdArgs a;
-        build_lstm_fwd(d, 1, params, x, nullptr, flags, nullptr, w, false, (float *)scratch, &a);
+        Lstm2FwdArgs a = build_lstm_fwd(d, params, x, nullptr, flags, nullptr, (float *)scratch);
         if (d->H == 48 && d->F <= 64 && d->K <= 64) {
             // single launch: attention pooling (online softmax), LayerNorm, dense head and class softmax run in the
             // LSTM kernel's tail wave; nothing but x, the parameters and the [B,K] outputs touches HBM
@@ -316,14 +381,8 @@ int nsd_infer(const nsd_dims *d, const float *params, const float *x, uint32_t f
         }
         rc = nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
     } else {
-        const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-        float *top = (float *)scratch;
-        const int64_t bth = align4((int64_t)d->B * d->T * d->H);
-        if (nsd_lstm_batched_ok(d, false) && !(flags & NSD_FLAG_RESIDUAL))
-            rc = nsd_lstm_batched_infer(d, pl, params, x, top, top + bth, top + 2 * bth, (flags & NSD_FLAG_BF16) != 0, (hipStream_t)stream);
-        else
-            rc = nsd_lstm_generic_fwd(d, pl, params, x, nullptr, (flags & NSD_FLAG_RESIDUAL) ? 1 : 0, nullptr, nullptr, nullptr, nullptr,
-                                      top, top + bth, (hipStream_t)stream);
+        const StackArgs s = stack_args(d, params, x, nullptr, flags, nullptr, (float *)scratch);
+        rc = nsd_lstm_batched_ok(d, false) && !s.residual ? nsd_lstm_batched_fwd(s, (hipStream_t)stream) : nsd_lstm_generic_fwd(s, (hipStream_t)stream);
     }
     if (rc != NSD_OK) return rc;
     HeadArgs h = build_head(d, params);
@@ -334,84 +393,51 @@ int nsd_infer(const nsd_dims *d, const float *params, const float *x, uint32_t f
 
 int nsd_lstm_fwd(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, uint32_t flags,
                  float *workspace, int64_t workspace_bytes, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!params || !x || !workspace) { nsd_set_error("lstm_fwd: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "lstm_fwd", &w)) return rc;
-    if (d->B == 0) return NSD_OK;
+    Ctx c;
+    if (const int rc = enter(&c, "lstm_fwd", d, params && x && workspace, nullptr, workspace, workspace_bytes, stream)) return leave(rc);
     if (!fast_path_ok(d)) {
-        const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-        if (nsd_lstm_batched_ok(d, true))        // large H: per-step batched gate GEMM on the matrix pipe
-            return nsd_lstm_batched_fwd(d, pl, params, x, drop_lstm, (flags & NSD_FLAG_RESIDUAL) ? 1 : 0, workspace + w.hseq,
-                                        workspace + w.cseq, workspace + w.gact, workspace + w.inseq, workspace + w.top,
-                                        (flags & NSD_FLAG_BF16) != 0, (hipStream_t)stream);
-        return nsd_lstm_generic_fwd(d, pl, params, x, drop_lstm, (flags & NSD_FLAG_RESIDUAL) ? 1 : 0, workspace + w.hseq,
-                                    workspace + w.cseq, workspace + w.gact, workspace + w.inseq, workspace + w.top, nullptr,
-                                    (hipStream_t)stream);
+        const StackArgs s = stack_args(d, params, x, drop_lstm, flags, &c, nullptr);
+        // large H: per-step batched gate GEMM on the matrix pipe
+        return nsd_lstm_batched_ok(d, true) ? nsd_lstm_batched_fwd(s, c.st) : nsd_lstm_generic_fwd(s, c.st);
     }
-    Lstm2FwdArgs a;
-    build_lstm_fwd(d, 1, params, x, drop_lstm, flags, workspace, w, true, nullptr, &a);
-    return nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
+    return nsd_lstm2_fwd_launch(build_lstm_fwd(d, params, x, drop_lstm, flags, &c, nullptr), d->H, c.st);
 }
 
 int nsd_head_fwd(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
                  float *workspace, int64_t workspace_bytes, float *logits, float *probs, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!params || !workspace || !logits) { nsd_set_error("head_fwd: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "head_fwd", &w)) return rc;
-    if (d->B == 0) return NSD_OK;
-    HeadArgs h = build_head(d, params);
-    h.top = workspace + w.top;
+    Ctx c;
+    if (const int rc = enter(&c, "head_fwd", d, params && workspace && logits, nullptr, workspace, workspace_bytes, stream)) return leave(rc);
+    HeadArgs h = build_head(d, params, &c);
     h.rrelu_slope = rrelu_slope; h.drop_head = drop_head;
     h.logits = logits; h.probs = probs;
-    h.alpha = workspace + w.alpha; h.pooled = workspace + w.pooled; h.fc0_pre = workspace + w.fc0_pre;
-    return nsd_head_launch(h, false, (hipStream_t)stream);
+    return nsd_head_launch(h, false, c.st);
 }
 
 int nsd_head_bwd(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
                  const float *logits, const float *dlogits, const int32_t *labels, float scale, float *workspace,
                  int64_t workspace_bytes, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!params || !workspace) { nsd_set_error("head_bwd: null pointer"); return NSD_E_INVALID; }
-    if (!dlogits && !(labels && logits)) {
-        nsd_set_error("head_bwd: need dlogits, or labels together with logits");
-        return NSD_E_INVALID;
-    }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "head_bwd", &w)) return rc;
-    if (d->B == 0) return NSD_OK;
-    HeadArgs h = build_head(d, params);
-    h.top = workspace + w.top;
+    Ctx c;
+    const char *refusal = (!dlogits && !(labels && logits)) ? "head_bwd: need dlogits, or labels together with logits" : nullptr;
+    if (const int rc = enter(&c, "head_bwd", d, params && workspace, refusal, workspace, workspace_bytes, stream)) return leave(rc);
+    HeadArgs h = build_head(d, params, &c);
     h.rrelu_slope = rrelu_slope; h.drop_head = drop_head;
-    h.alpha = workspace + w.alpha; h.pooled = workspace + w.pooled; h.fc0_pre = workspace + w.fc0_pre;
     h.logits_in = logits; h.dlogits = dlogits; h.labels = labels; h.scale = scale;
-    h.loss = workspace + w.loss; h.dscore = workspace + w.dscore; h.dpooled = workspace + w.dpooled;
-    h.hslabs = workspace + w.hslabs;
-    h.adpack = workspace + w.adpack;
-    return nsd_head_launch(h, true, (hipStream_t)stream);
+    return nsd_head_launch(h, true, c.st);
 }
 
 int nsd_head_train(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
                    const int32_t *labels, float scale, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!params || !workspace || !logits || !labels) { nsd_set_error("head_train: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "head_train", &w)) return rc;
-    if (d->B == 0) return NSD_OK;
-    HeadArgs h = build_head(d, params);
-    h.top = workspace + w.top;
+    Ctx c;
+    if (const int rc = enter(&c, "head_train", d, params && workspace && logits && labels, nullptr, workspace, workspace_bytes, stream)) return leave(rc);
+    HeadArgs h = build_head(d, params, &c);
     h.rrelu_slope = rrelu_slope; h.drop_head = drop_head;
-    h.alpha = workspace + w.alpha; h.pooled = workspace + w.pooled; h.fc0_pre = workspace + w.fc0_pre;
     h.logits = logits; h.logits_in = logits; h.labels = labels; h.scale = scale;
-    h.loss = workspace + w.loss; h.dscore = workspace + w.dscore; h.dpooled = workspace + w.dpooled;
-    h.hslabs = workspace + w.hslabs; h.adpack = workspace + w.adpack;
-    const int rc = nsd_head_train_launch(h, (hipStream_t)stream);
+    const int rc = nsd_head_train_launch(h, c.st);
     if (rc != 0) return rc < 0 ? rc : NSD_OK;
     // shape does not fit the fused kernel's LDS budget: two passes
-    const int rc2 = nsd_head_launch(h, false, (hipStream_t)stream);
+    const int rc2 = nsd_head_launch(h, false, c.st);
     if (rc2 != NSD_OK) return rc2;
-    return nsd_head_launch(h, true, (hipStream_t)stream);
+    return nsd_head_launch(h, true, c.st);
 }
 
 int nsd_rng_path(const nsd_dims *d) {
@@ -422,11 +448,9 @@ int nsd_rng_path(const nsd_dims *d) {
 static int lstm_head_train_impl(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm,
                                 const float *rrelu_slope, const float *drop_head, const RngArgs *rng, const int32_t *labels,
                                 float scale, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!params || !x || !workspace || !logits || !labels) { nsd_set_error("lstm_head_train: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "lstm_head_train", &w)) return rc;
-    if (d->B == 0) return NSD_OK;
+    Ctx c;
+    if (const int rc = enter(&c, "lstm_head_train", d, params && x && workspace && logits && labels, nullptr, workspace, workspace_bytes, stream))
+        return leave(rc);
     if (!fused_train_shape(d)) {
         if (rng) { nsd_set_error("lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0)"); return NSD_E_INVALID; }
         // shapes outside the fused kernel: the two launches it replaces
@@ -434,12 +458,11 @@ static int lstm_head_train_impl(const nsd_dims *d, const float *params, const fl
         if (rc != NSD_OK) return rc;
         return nsd_head_train(d, params, rrelu_slope, drop_head, labels, scale, workspace, workspace_bytes, logits, stream);
     }
-    Lstm2FwdArgs a;
-    build_lstm_fwd(d, 1, params, x, drop_lstm, flags, workspace, w, true, nullptr, &a);
-    attach_head_train(&a, build_head(d, params), labels, scale, logits, workspace, w);
+    Lstm2FwdArgs a = build_lstm_fwd(d, params, x, drop_lstm, flags, &c, nullptr);
+    attach_head_train(&a, build_head(d, params, &c), labels, scale, logits);
     a.rrelu_slope = rrelu_slope; a.drop_head = drop_head;
     if (rng) a.rng = *rng;
-    return nsd_lstm2_fwd_launch(a, d->H, (hipStream_t)stream);
+    return nsd_lstm2_fwd_launch(a, d->H, c.st);
 }
 
 int nsd_lstm_head_train(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm,
@@ -469,43 +492,30 @@ int nsd_dx_path(const nsd_dims *d) {
 
 static int lstm_bwd_impl(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, const RngArgs *rng,
                          uint32_t flags, float *workspace, int64_t workspace_bytes, float *dx, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!params || !x || !workspace) { nsd_set_error("lstm_bwd: null pointer"); return NSD_E_INVALID; }
     // dx = dL/dx [B,T,C] (optional): refused before any launch where it is not formed (dx_shape, nsd_dx_path)
-    if (dx && !dx_shape(d)) {
-        nsd_set_error("lstm_bwd: dx is available for H = 48 (L = 2, C <= 8) and on the generic path with C <= 64 and 4H * C * 4 <= 64 KB "
-                      "only (nsd_dx_path, include/nsd.h)");
-        return NSD_E_INVALID;
-    }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "lstm_bwd", &w)) return rc;
-    if (d->B == 0) return NSD_OK;
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    const int64_t BTH = (int64_t)d->B * d->T * d->H;
-    if (!fast_path_ok(d) && nsd_lstm_batched_ok(d, true))
-        return nsd_lstm_batched_bwd(d, pl, params, x, drop_lstm, (flags & NSD_FLAG_RESIDUAL) ? 1 : 0, workspace + w.hseq,
-                                    workspace + w.cseq, workspace + w.gact, workspace + w.inseq, workspace + w.alpha,
-                                    workspace + w.dscore, workspace + w.dpooled, workspace + w.da_seq, workspace + w.din,
-                                    workspace + w.din + BTH, workspace + w.din + 2 * BTH, workspace + w.slabs,
-                                    (flags & NSD_FLAG_BF16) != 0, (hipStream_t)stream);
+    const char *refusal = (dx && !nsd_dx_path(d))
+        ? "lstm_bwd: dx is available for H = 48 (L = 2, C <= 8) and on the generic path with C <= 64 and 4H * C * 4 <= 64 KB only (nsd_dx_path, include/nsd.h)"
+        : nullptr;
+    Ctx c;
+    if (const int rc = enter(&c, "lstm_bwd", d, params && x && workspace, refusal, workspace, workspace_bytes, stream)) return leave(rc);
+    const long rows = (long)d->B * d->T;
     if (!fast_path_ok(d)) {
-        if (const int rc = nsd_lstm_generic_bwd(d, pl, params, x, drop_lstm, (flags & NSD_FLAG_RESIDUAL) ? 1 : 0, workspace + w.hseq,
-                                    workspace + w.cseq, workspace + w.gact, workspace + w.inseq, workspace + w.alpha,
-                                    workspace + w.dscore, workspace + w.dpooled, workspace + w.da_seq, workspace + w.din,
-                                    workspace + w.din + BTH, workspace + w.slabs, (hipStream_t)stream)) return rc;
-        return dx ? nsd_dx_launch(workspace + w.da_seq, params + pl.w_ih[0], dx, (long)d->B * d->T, 4 * d->H, d->C, (hipStream_t)stream) : NSD_OK;
+        const StackArgs s = stack_args(d, params, x, drop_lstm, flags, &c, nullptr);
+        if (nsd_lstm_batched_ok(d, true)) return nsd_lstm_batched_bwd(s, c.st);
+        if (const int rc = nsd_lstm_generic_bwd(s, c.st)) return rc;
+        return dx ? nsd_dx_launch(s.da_seq, s.w_ih(0), dx, rows, 4 * d->H, d->C, c.st) : NSD_OK;
     }
-    Lstm2BwdArgs a = build_lstm_bwd(d, 1, params, x, workspace, w, flags);
+    Lstm2BwdArgs a = build_lstm_bwd(c, params, x, flags);
     a.mask = drop_lstm;
     if (rng) a.rng = *rng;
     if (dx) {
-        a.da0_out = workspace + w.gact;                             // (in place of layer 0's saved gates, 4H floats per step: see Lstm2BwdArgs)
+        a.da0_out = c.at(c.w.gact);                                 // (in place of layer 0's saved gates, 4H floats per step: see Lstm2BwdArgs)
         // the one-trial kernel takes a record's dL/dscore_t as finished: close the records a four-trial forward left open
-        if (const int rc = nsd_att_close_launch(a.hseq1, a.pooled, a.dpooled, workspace + w.adpack, workspace + w.dscore, a.hslabs, a.Ph,
-                                                a.o_attn_w, a.o_attn_b, d->B, d->T, d->H, (hipStream_t)stream)) return rc;
+        if (const int rc = nsd_att_close_launch(a.hseq1, a.pooled, a.dpooled, c.at(c.w.adpack), a.dscore_out, a.hslabs, a.Ph,
+                                                a.o_attn_w, a.o_attn_b, d->B, d->T, d->H, c.st)) return rc;
     }
-    if (const int rc = nsd_lstm2_bwd_launch(a, d->H, (hipStream_t)stream)) return rc;
-    return dx ? nsd_dx_launch(a.da0_out, params + pl.w_ih[0], dx, (long)d->B * d->T, 4 * d->H, d->C, (hipStream_t)stream) : NSD_OK;
+    if (const int rc = nsd_lstm2_bwd_launch(a, d->H, c.st)) return rc;
+    return dx ? nsd_dx_launch(a.da0_out, params + c.pl.w_ih[0], dx, rows, 4 * d->H, d->C, c.st) : NSD_OK;
 }
 
 int nsd_lstm_bwd(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, uint32_t flags,
@@ -522,35 +532,25 @@ int nsd_lstm_bwd_rng(const nsd_dims *d, const float *params, const float *x, con
     return lstm_bwd_impl(d, params, x, nullptr, &r, flags, workspace, workspace_bytes, nullptr, stream);
 }
 
+// (the three below launch for an empty batch too: the gradient is zeroed / the parameters decay, the loss sum is 0)
 int nsd_grad_reduce(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, int32_t accumulate, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!workspace || !grads) { nsd_set_error("grad_reduce: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "grad_reduce", &w)) return rc;
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    return nsd_grad_reduce_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? (int)w.n_slabs : 0, pl.lstm_total,
-                                  workspace + w.hslabs, pl.total - pl.lstm_total, d->B, grads, accumulate,
-                                  (hipStream_t)stream);
+    Ctx c;
+    if (const int rc = enter(&c, "grad_reduce", d, workspace && grads, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
+    return nsd_grad_reduce_launch(slab_set(c), 1, grads, accumulate, nullptr, "grad_reduce", c.st);
 }
 
 int nsd_grad_reduce_adam(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, float *p, float *m, float *v, float lr,
                          float beta1, float beta2, float eps, float weight_decay, float grad_scale, int32_t step, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!workspace || !grads || !p || !m || !v) { nsd_set_error("grad_reduce_adam: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "grad_reduce_adam", &w)) return rc;
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    return nsd_grad_reduce_adam_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? (int)w.n_slabs : 0, pl.lstm_total,
-                                       workspace + w.hslabs, pl.total - pl.lstm_total, d->B, grads, p, m, v, lr, beta1, beta2,
-                                       eps, weight_decay, grad_scale, step, (hipStream_t)stream);
+    Ctx c;
+    if (const int rc = enter(&c, "grad_reduce_adam", d, workspace && grads && p && m && v, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
+    const AdamStep adam{p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step};
+    return nsd_grad_reduce_launch(slab_set(c), 1, grads, 0, &adam, "grad_reduce_adam", c.st);
 }
 
 int nsd_loss_sum(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!workspace || !out) { nsd_set_error("loss_sum: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = check_ws(d, workspace, workspace_bytes, "loss_sum", &w)) return rc;
-    return nsd_loss_sum_launch(workspace + w.loss, d->B, out, (hipStream_t)stream);
+    Ctx c;
+    if (const int rc = enter(&c, "loss_sum", d, workspace && out, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
+    return nsd_loss_sum_launch(c.at(c.w.loss), d->B, 1, false, out, "loss_sum", c.st);
 }
 
 int nsd_adam_step(int64_t n, float *p, const float *g, float *m, float *v, float lr, float beta1, float beta2,
@@ -672,29 +672,6 @@ static int multi_check(const nsd_dims *d, int M, const char *who) {
     }
     return NSD_OK;
 }
-static nsd_dims multi_total(const nsd_dims *d, int M) { nsd_dims t = *d; t.B = M * d->B; return t; }
-static nsd_ws_layout make_multi_ws(const nsd_dims *d, int M, bool have_device) {
-    const nsd_dims t = multi_total(d, M);
-    nsd_ws_layout w = make_ws(&t, have_device);
-    if (M == 1) return w;
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    const int64_t nsl = (int64_t)M * nsd_lstm2_bwd_groups(d->B > 0 ? d->B : 1, M);
-    if (nsl > w.n_slabs) {       // room for M * G slabs: the head slabs (and the generic path's regions, empty here) move behind them
-        const int64_t grow = (nsl - w.n_slabs) * align4(pl.lstm_total);
-        w.n_slabs = nsl; w.hslabs += grow; w.da_seq += grow; w.din += grow; w.total += grow;
-    }
-    return w;
-}
-static int multi_ws(const nsd_dims *d, int M, const void *ws, int64_t bytes, const char *who, nsd_ws_layout *w) {
-    if (!ws) { nsd_set_error("%s: workspace is NULL", who); return NSD_E_INVALID; }
-    *w = make_multi_ws(d, M, true);
-    if (bytes < w->total * (int64_t)sizeof(float)) {
-        nsd_set_error("%s: workspace of %lld bytes is smaller than nsd_multi_workspace_bytes() = %lld", who, (long long)bytes,
-                      (long long)(w->total * (int64_t)sizeof(float)));
-        return NSD_E_WORKSPACE;
-    }
-    return NSD_OK;
-}
 // rng: NULL or M entries with one p_lstm / p_head
 static int multi_rng(const nsd_rng *rng, int M, const char *who, RngArgs *r, ModelSplit *s) {
     memset(r, 0, sizeof(*r));
@@ -725,9 +702,17 @@ int nsd_multi_path(const nsd_dims *d, int32_t M) { return multi_shape(d, M) ? 1 
 
 int64_t nsd_multi_workspace_bytes(const nsd_dims *d, int32_t M, nsd_ws_layout *layout_out) {
     if (multi_check(d, M, "multi_workspace_bytes") != NSD_OK) return NSD_E_INVALID;
-    const nsd_ws_layout w = make_multi_ws(d, M, device_present());
+    const nsd_ws_layout w = ws_layout(d, M, device_present());
     if (layout_out) *layout_out = w;
     return w.total * (int64_t)sizeof(float);
+}
+
+// (the model-batched preamble keeps its own order: multi_common / multi_check, pointers, random streams, then the workspace binder)
+static ModelSplit model_split(const nsd_dims *d, int64_t x_model_stride) {
+    ModelSplit s;
+    memset(&s, 0, sizeof(s));
+    s.x_stride = x_model_stride; s.P = layout_of(d).total;
+    return s;
 }
 
 int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
@@ -735,22 +720,18 @@ int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const
     static const char *who = "multi_train_fwd";
     if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
     if (!params || !x || !labels || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
-    ModelSplit s;
-    memset(&s, 0, sizeof(s));
+    ModelSplit s = model_split(d, x_model_stride);
     RngArgs r;
     if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
-    nsd_ws_layout w;
-    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, who, &w)) return rc;
-    if (d->B == 0) return NSD_OK;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream)) return leave(rc);
     const float scale = 1.0f / (float)d->B;                     // mean CE per model
     if (M == 1) return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, rng ? &r : nullptr, labels, scale, flags, workspace,
                                             workspace_bytes, logits, stream);
-    Lstm2FwdArgs a;
-    build_lstm_fwd(d, M, params, x, nullptr, flags, workspace, w, true, nullptr, &a);
-    attach_head_train(&a, build_head(d, params), labels, scale, logits, workspace, w);
+    Lstm2FwdArgs a = build_lstm_fwd(d, params, x, nullptr, flags, &c, nullptr);
+    attach_head_train(&a, build_head(d, params, &c), labels, scale, logits);
     a.rng = r;
-    s.x_stride = x_model_stride; s.P = nsd_make_layout(d->C, d->H, d->L, d->K, d->F).total;
-    return nsd_lstm2_multi_fwd_launch(a, s, M, (hipStream_t)stream);
+    return nsd_lstm2_multi_fwd_launch(a, s, M, c.st);
 }
 
 int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
@@ -758,51 +739,48 @@ int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const
     static const char *who = "multi_train_bwd";
     if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
     if (!params || !x) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
-    ModelSplit s;
-    memset(&s, 0, sizeof(s));
+    ModelSplit s = model_split(d, x_model_stride);
     RngArgs r;
     if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
-    nsd_ws_layout w;
-    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, who, &w)) return rc;
-    if (d->B == 0) return NSD_OK;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream)) return leave(rc);
     if (M == 1) return lstm_bwd_impl(d, params, x, nullptr, rng ? &r : nullptr, flags, workspace, workspace_bytes, nullptr, stream);
-    Lstm2BwdArgs a = build_lstm_bwd(d, M, params, x, workspace, w, flags);
+    Lstm2BwdArgs a = build_lstm_bwd(c, params, x, flags);
     a.rng = r;
-    s.x_stride = x_model_stride; s.P = nsd_make_layout(d->C, d->H, d->L, d->K, d->F).total;
-    return nsd_lstm2_multi_bwd_launch(a, s, M, (hipStream_t)stream);
+    return nsd_lstm2_multi_bwd_launch(a, s, M, c.st);
 }
 
+// (M = 1 goes through the single-model entry point, as the two above do)
 int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, void *stream) {
-    if (const int rc = multi_check(d, M, "multi_grad_reduce")) return rc;
-    if (!grads) { nsd_set_error("multi_grad_reduce: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_grad_reduce", &w)) return rc;
+    static const char *who = "multi_grad_reduce";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!grads) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
     if (M == 1) return nsd_grad_reduce(d, workspace, workspace_bytes, grads, 0, stream);
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    return nsd_multi_grad_reduce_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_bwd_groups(d->B, M) : 0,
-                                        pl.lstm_total, workspace + w.hslabs, pl.total - pl.lstm_total, d->B, M, grads, (hipStream_t)stream);
+    return nsd_grad_reduce_launch(slab_set(c), M, grads, 0, nullptr, who, c.st);
 }
 
 int nsd_multi_grad_reduce_adam(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
                                float *m, float *v, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                int32_t step, void *stream) {
-    if (const int rc = multi_check(d, M, "multi_grad_reduce_adam")) return rc;
-    if (!grads || !p || !m || !v) { nsd_set_error("multi_grad_reduce_adam: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_grad_reduce_adam", &w)) return rc;
+    static const char *who = "multi_grad_reduce_adam";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!grads || !p || !m || !v) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
     if (M == 1) return nsd_grad_reduce_adam(d, workspace, workspace_bytes, grads, p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step, stream);
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    return nsd_multi_grad_reduce_adam_launch(workspace + w.slabs, align4(pl.lstm_total), d->B > 0 ? nsd_lstm2_bwd_groups(d->B, M) : 0,
-                                             pl.lstm_total, workspace + w.hslabs, pl.total - pl.lstm_total, d->B, M, grads, p, m, v, lr,
-                                             beta1, beta2, eps, weight_decay, grad_scale, step, (hipStream_t)stream);
+    const AdamStep adam{p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step};
+    return nsd_grad_reduce_launch(slab_set(c), M, grads, 0, &adam, who, c.st);
 }
 
 int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {
-    if (const int rc = multi_check(d, M, "multi_loss_sum")) return rc;
-    if (!out) { nsd_set_error("multi_loss_sum: null pointer"); return NSD_E_INVALID; }
-    nsd_ws_layout w;
-    if (const int rc = multi_ws(d, M, workspace, workspace_bytes, "multi_loss_sum", &w)) return rc;
-    return nsd_multi_loss_sum_launch(workspace + w.loss, d->B, M, out, (hipStream_t)stream);
+    static const char *who = "multi_loss_sum";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!out) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
+    return nsd_loss_sum_launch(c.at(c.w.loss), d->B, M, true, out, who, c.st);
 }
 
 int64_t nsd_multi_infer_scratch_bytes(const nsd_dims *d, int32_t M) {
@@ -817,17 +795,10 @@ int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const flo
     if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
     if (!params || !x || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     if (d->B == 0) return NSD_OK;
-    const ParamLayout pl = nsd_make_layout(d->C, d->H, d->L, d->K, d->F);
-    nsd_ws_layout w;
-    memset(&w, 0, sizeof(w));
-    Lstm2FwdArgs a;
-    build_lstm_fwd(d, M, params, x, nullptr, 0, nullptr, w, false, nullptr, &a);
+    Lstm2FwdArgs a = build_lstm_fwd(d, params, x, nullptr, 0, nullptr, nullptr);
     attach_head(&a, build_head(d, params));
     a.logits_out = logits; a.probs_out = probs;
-    ModelSplit s;
-    memset(&s, 0, sizeof(s));
-    s.x_stride = x_model_stride; s.P = pl.total;
-    return nsd_lstm2_multi_fwd_launch(a, s, M, (hipStream_t)stream);
+    return nsd_lstm2_multi_fwd_launch(a, model_split(d, x_model_stride), M, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -89,22 +89,47 @@ bool nsd_lstm2_fwd48w_ok(const Lstm2FwdArgs &a);
 int nsd_lstm2_fwd48w_launch(const Lstm2FwdArgs &a, int grid, hipStream_t st);
 bool nsd_lstm2_bwd48x4_ok(const Lstm2BwdArgs &a);
 int nsd_lstm2_bwd48x4_launch(const Lstm2BwdArgs &a, int grid, hipStream_t st);
-int nsd_lstm_generic_fwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, float *hseq, float *cseq, float *gact, float *inseq, float *top_out, float *scratch2,
-                         hipStream_t st);
-int nsd_lstm_generic_bwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, const float *hseq, const float *cseq, const float *gact, const float *inseq,
-                         const float *alpha, const float *dscore, const float *dpooled, float *da_seq, float *din_a, float *din_b,
-                         float *slab, hipStream_t st);
+// The layer-by-layer stacks (nsd_lstm_generic.hip, nsd_lstm_batched.hip): one argument block for their four drivers, built by stack_args()
+// of nsd_abi.hip.  Training binds the saved regions of the workspace; inference leaves them null and ping-pongs between top_out and scratch2.
+struct StackArgs {
+    nsd_dims d;
+    ParamLayout pl;
+    const float *params, *x;
+    const float *drop_lstm;                  // null, or the inter-layer multipliers [L-1][B,T,H]
+    int residual;
+    float *hseq, *cseq, *gact, *inseq;       // saved per layer: h, c [L][B,T,H], gates [L][B,T,4H], layer outputs [L-1][B,T,H]
+    float *top_out;                          // [B,T,H]: the last layer's output
+    const float *alpha, *dscore, *dpooled;   // the head's gradient inputs
+    float *da_seq;                           // generic: [B,T,4H], the layer in flight; batched: [L][B,T,4H]
+    float *din_a, *din_b;                    // [B,T,H] ping-pong for d(layer input)
+    float *state;                            // batched backward: [L][3][B,H] (dhrec, dc, dho) + split-K partials 8 * 4H * max(C,H)
+    float *slab;                             // weight / bias gradients [P_lstm]
+    bool bf16;                               // batched: bf16 GEMM operands
+    float *scratch2, *cstate;                // inference: [B,T,H] ping-pong; batched: cell-state ping-pong [L][2][B,H]
+
+    int64_t BTH() const { return (int64_t)d.B * d.T * d.H; }
+    int I(int l) const { return l == 0 ? d.C : d.H; }
+    const float *w_ih(int l) const { return params + pl.w_ih[l]; }
+    const float *w_hh(int l) const { return params + pl.w_hh[l]; }
+    const float *b_ih(int l) const { return params + pl.b_ih[l]; }
+    const float *b_hh(int l) const { return params + pl.b_hh[l]; }
+    const float *mask(int l) const { return (l < d.L - 1 && drop_lstm) ? drop_lstm + (int64_t)l * BTH() : nullptr; }
+    float *out(int l) const {                // (inference ping-pong: the last layer lands in top_out)
+        if (l == d.L - 1) return top_out;
+        if (inseq) return inseq + (int64_t)l * BTH();
+        return ((d.L - 1 - l) & 1) ? scratch2 : top_out;
+    }
+    const float *in(int l) const { return l == 0 ? x : out(l - 1); }
+    float *din(int l) const { return (l & 1) ? din_a : din_b; }       // written by layer l's backward, read by layer l - 1's
+    float *h(int l) const { return hseq + (int64_t)l * BTH(); }
+    float *c(int l) const { return cseq + (int64_t)l * BTH(); }
+    float *gates(int l) const { return gact + (int64_t)l * 4 * BTH(); }
+};
+int nsd_lstm_generic_fwd(const StackArgs &s, hipStream_t st);
+int nsd_lstm_generic_bwd(const StackArgs &s, hipStream_t st);
 bool nsd_lstm_batched_ok(const nsd_dims *d, bool training);
-int nsd_lstm_batched_infer(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, float *top_out,
-                           float *scratch2, float *cstate, bool bf16, hipStream_t st);
-int nsd_lstm_batched_fwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, float *hseq, float *cseq, float *gact, float *inseq, float *top_out, bool bf16, hipStream_t st);
-int nsd_lstm_batched_bwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, const float *hseq, const float *cseq, const float *gact, const float *inseq,
-                         const float *alpha, const float *dscore, const float *dpooled, float *da_seq, float *din_a, float *din_b,
-                         float *state, float *slab, bool bf16, hipStream_t st);
+int nsd_lstm_batched_fwd(const StackArgs &s, hipStream_t st);
+int nsd_lstm_batched_bwd(const StackArgs &s, hipStream_t st);
 int nsd_head_launch(const HeadArgs &a, bool bwd, hipStream_t st);
 int nsd_head_train_launch(const HeadArgs &a, hipStream_t st);   // 1 launched, 0 shape does not fit, <0 error
 int nsd_zscore_launch(const float *x, float *y, int B, int T, int C, hipStream_t st);
@@ -122,11 +147,14 @@ struct AugArgs {
     uint32_t base[NSD_MAX_MODELS];
 };
 int nsd_augment_launch(const AugArgs &a, hipStream_t st);
-int nsd_grad_reduce_launch(const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs,
-                           long ph, int n_hslabs, float *grads, int accumulate, hipStream_t st);
-int nsd_grad_reduce_adam_launch(const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs,
-                                long ph, int n_hslabs, float *grads, float *p, float *m, float *v, float lr, float b1,
-                                float b2, float eps, float wd, float gscale, int step, hipStream_t st);
+// gradient slabs of M models in one workspace: per model n LSTM slabs (one per backward workgroup) and n_h head slabs (one per trial)
+struct SlabSet {
+    const float *slabs; long stride; int n; long p_lstm;
+    const float *hslabs; long ph; int n_h;
+};
+struct AdamStep { float *p, *m, *v; float lr, b1, b2, eps, wd, gscale; int step; };
+// grads + m*P (+)= model m's slabs; adam != null: and the Adam update of p / m / v + m*P in the same launch (who: the entry point, for the texts)
+int nsd_grad_reduce_launch(const SlabSet &s, int M, float *grads, int accumulate, const AdamStep *adam, const char *who, hipStream_t st);
 int nsd_adam_launch(long n, float *p, const float *g, float *m, float *v, float lr, float b1, float b2, float eps,
                     float wd, float gscale, int step, const float *skip, hipStream_t st);
 int nsd_seq_guard_launch(const int *header, int status_word, float *flag_out, hipStream_t st);
@@ -137,7 +165,8 @@ int nsd_adam_dev_launch(long n, float *p, const float *g, float *m, float *v, fl
                         float wd, float gscale, const long long *step_dev, hipStream_t st);
 int nsd_step_inc_launch(long long *step_dev, hipStream_t st);
 int nsd_rrelu_noise_launch(uint64_t seed, uint32_t stream_id, long n, float *out, hipStream_t st);
-int nsd_loss_sum_launch(const float *loss, int B, float *out, hipStream_t st);
+// out[m] = sum of model m's B losses (per_model: the model-batched instantiation, nsd_multi_loss_sum's at M = 1 too)
+int nsd_loss_sum_launch(const float *loss, int B, int M, bool per_model, float *out, const char *who, hipStream_t st);
 // dx[r][c] = sum_k da0[r][k] * w_ih0[k][c]: r = (trial, step), k = gate * H + unit (nn.LSTM weight_ih_l0 is [4H][C] row-major)
 int nsd_dx_launch(const float *da0, const float *w_ih0, float *dx, long rows, int G4, int C, hipStream_t st);
 bool nsd_dx_ok(int G4, int C);            // the dx kernel's domain (C channels, 4H gate rows: W_ih0 staged in 64 KB of LDS)

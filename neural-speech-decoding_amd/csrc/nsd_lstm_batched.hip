@@ -462,7 +462,7 @@ __global__ void sum_parts2_kernel(const float *part, int nparts, long n, float *
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
-// host drivers (same contracts as nsd_lstm_generic_fwd / _bwd; training only: the forward needs hseq / cseq)
+// host drivers (same contracts as nsd_lstm_generic_fwd / _bwd)
 // ---------------------------------------------------------------------------------------------------------------
 bool nsd_lstm_batched_ok(const nsd_dims *d, bool training) {
     // (16-byte operand loads: the channel count must be a multiple of 4 as well)
@@ -481,61 +481,43 @@ static int launch_fwd_steps(StepFwdAll &all, int B, int T, int H, int L, bool bf
     return NSD_OK;
 }
 
-int nsd_lstm_batched_fwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, float *hseq, float *cseq, float *gact, float *inseq, float *top_out, bool bf16, hipStream_t st) {
-    const int B = d->B, T = d->T, H = d->H, L = d->L;
-    const int64_t BTH = (int64_t)B * T * H;
-    StepFwdAll all;
-    memset(&all, 0, sizeof(all));
-    const float *in = x;
-    for (int l = 0; l < L; ++l) {
-        StepFwdArgs &a = all.lay[l];
-        a.in = in; a.I = l == 0 ? d->C : H;
-        a.w_ih = params + pl.w_ih[l]; a.w_hh = params + pl.w_hh[l]; a.b_ih = params + pl.b_ih[l]; a.b_hh = params + pl.b_hh[l];
-        a.mask = (l < L - 1 && drop_lstm) ? drop_lstm + (int64_t)l * BTH : nullptr;
-        a.res_in = (residual && l >= 1) ? in : nullptr;
-        a.hseq = hseq + (int64_t)l * BTH; a.cseq = cseq + (int64_t)l * BTH; a.gact = gact + (int64_t)l * 4 * BTH;
-        a.out = (l == L - 1) ? top_out : inseq + (int64_t)l * BTH;
-        a.hprev = a.hseq;
-        a.B = B; a.T = T; a.H = H;
-        in = a.out;
-    }
-    return launch_fwd_steps(all, B, T, H, L, bf16, st);
-}
-
-// inference (no residual): only the linked outputs are produced, ping-ponging between top_out and scratch2 so that the
+// forward through all layers, one step-forward argument block per layer.  Training (s.hseq != null): keeps h / c / gates per step.
+// Inference (no residual): only the linked outputs are produced, ping-ponging between top_out and scratch2 so that the
 // last layer lands in top_out (with the one-step skew a layer overwrites a row two launches after its reader is done);
 // cstate: [L][2][B,H] cell-state ping-pong
-int nsd_lstm_batched_infer(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, float *top_out,
-                           float *scratch2, float *cstate, bool bf16, hipStream_t st) {
-    const int B = d->B, T = d->T, H = d->H, L = d->L;
+int nsd_lstm_batched_fwd(const StackArgs &s, hipStream_t st) {
+    const int B = s.d.B, T = s.d.T, H = s.d.H, L = s.d.L;
+    const bool save = s.hseq != nullptr;
     StepFwdAll all;
     memset(&all, 0, sizeof(all));
-    all.c_base = cstate;
-    const float *in = x;
+    if (!save) all.c_base = s.cstate;
     for (int l = 0; l < L; ++l) {
         StepFwdArgs &a = all.lay[l];
-        a.in = in; a.I = l == 0 ? d->C : H;
-        a.w_ih = params + pl.w_ih[l]; a.w_hh = params + pl.w_hh[l]; a.b_ih = params + pl.b_ih[l]; a.b_hh = params + pl.b_hh[l];
-        a.out = ((L - 1 - l) & 1) ? scratch2 : top_out;
-        a.hprev = a.out;                                     // no residual, no multipliers: the linked output is h itself
+        a.in = s.in(l); a.I = s.I(l);
+        a.w_ih = s.w_ih(l); a.w_hh = s.w_hh(l); a.b_ih = s.b_ih(l); a.b_hh = s.b_hh(l);
+        a.out = s.out(l);
+        if (save) {
+            a.mask = s.mask(l);
+            a.res_in = (s.residual && l >= 1) ? a.in : nullptr;
+            a.hseq = s.h(l); a.cseq = s.c(l); a.gact = s.gates(l);
+        }
+        a.hprev = save ? a.hseq : a.out;                     // inference has no residual, no multipliers: the linked output is h itself
         a.B = B; a.T = T; a.H = H;
-        in = a.out;
     }
-    return launch_fwd_steps(all, B, T, H, L, bf16, st);
+    return launch_fwd_steps(all, B, T, H, L, s.bf16, st);
 }
 
 // scratch: `din_a`, `din_b` [B,T,H] ping-pong for d(layer input) (one writer and one reader each, a step apart);
 // `state` >= L*3*B*H + 8 * 4H * max(C,H) floats (per-layer dhrec / dc / dho + the split-K partials); da_seq [L][B,T,4H].
-int nsd_lstm_batched_bwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, const float *hseq, const float *cseq, const float *gact, const float *inseq,
-                         const float *alpha, const float *dscore, const float *dpooled, float *da_seq, float *din_a, float *din_b,
-                         float *state, float *slab, bool bf16, hipStream_t st) {
-    const int B = d->B, T = d->T, H = d->H, L = d->L;
-    const int64_t BTH = (int64_t)B * T * H;
+int nsd_lstm_batched_bwd(const StackArgs &sa, hipStream_t st) {
+    const int B = sa.d.B, T = sa.d.T, H = sa.d.H, L = sa.d.L;
+    const int64_t BTH = sa.BTH();
     const long rows = (long)B * T;
+    const bool bf16 = sa.bf16;
+    const ParamLayout &pl = sa.pl;
+    float *slab = sa.slab;
     // state: [L][3][B,H] (dhrec, dc, dho per layer) + split-K partials; da_seq: [L][B,T,4H]
-    float *parts = state + (size_t)L * 3 * B * H;
+    float *parts = sa.state + (size_t)L * 3 * B * H;
     const int NPART = NSD_DW_SPLITS;
     CellBwdAll call;
     StepBwdAll sall;
@@ -544,23 +526,21 @@ int nsd_lstm_batched_bwd(const nsd_dims *d, const ParamLayout &pl, const float *
     call.L = sall.L = L;
     int max_tiles = 0;
     for (int l = L - 1; l >= 0; --l) {
-        const int I = l == 0 ? d->C : H;
-        float *st_l = state + (size_t)l * 3 * B * H;
-        float *da_l = da_seq + (size_t)l * 4 * BTH;
-        float *din_l = l > 0 ? ((l & 1) ? din_a : din_b) : nullptr;             // written by layer l, read by layer l-1
-        const float *dsrc = l < L - 1 ? (((l + 1) & 1) ? din_a : din_b) : nullptr;
-        const bool res_add = residual && l >= 1;
+        const int I = sa.I(l);
+        float *st_l = sa.state + (size_t)l * 3 * B * H;
+        float *da_l = sa.da_seq + (size_t)l * 4 * BTH;
+        const bool res_add = sa.residual && l >= 1;
         CellBwdArgs &c = call.lay[l];
-        c.gact = gact + (int64_t)l * 4 * BTH; c.cseq = cseq + (int64_t)l * BTH;
-        c.dsrc = dsrc;
-        c.mask = (l < L - 1 && drop_lstm) ? drop_lstm + (int64_t)l * BTH : nullptr;
-        c.alpha = alpha; c.dscore = dscore; c.dpooled = dpooled; c.attn_w = params + pl.attn_w;
+        c.gact = sa.gates(l); c.cseq = sa.c(l);
+        c.dsrc = l < L - 1 ? sa.din(l + 1) : nullptr;
+        c.mask = sa.mask(l);
+        c.alpha = sa.alpha; c.dscore = sa.dscore; c.dpooled = sa.dpooled; c.attn_w = sa.params + pl.attn_w;
         c.dhrec = st_l; c.dc = st_l + (size_t)B * H; c.dho = res_add ? st_l + 2 * (size_t)B * H : nullptr;
         c.da_seq = da_l;
         c.B = B; c.T = T; c.H = H;
         StepBwdArgs &s = sall.lay[l];
-        s.da_seq = da_l; s.w_ih = params + pl.w_ih[l]; s.w_hh = params + pl.w_hh[l];
-        s.dho = c.dho; s.dhrec = st_l; s.din_seq = din_l;
+        s.da_seq = da_l; s.w_ih = sa.w_ih(l); s.w_hh = sa.w_hh(l);
+        s.dho = c.dho; s.dhrec = st_l; s.din_seq = l > 0 ? sa.din(l) : nullptr;
         s.B = B; s.T = T; s.I = I; s.H = H;
         s.n_hh_tiles = (H + TN - 1) / TN;
         s.n_tiles = s.n_hh_tiles + (l > 0 ? (I + TN - 1) / TN : 0);
@@ -577,9 +557,9 @@ int nsd_lstm_batched_bwd(const nsd_dims *d, const ParamLayout &pl, const float *
     NSD_CHECK_LAUNCH("lstm_step_bwd_mfma");
     // weight gradients: dW_ih = da^T . in_l ; dW_hh = da^T . h_l[t-1] ; db = column sums of da
     for (int l = 0; l < L; ++l) {
-        const int I = l == 0 ? d->C : H;
-        const float *da_l = da_seq + (size_t)l * 4 * BTH;
-        const float *in_l = l == 0 ? x : inseq + (int64_t)(l - 1) * BTH;
+        const int I = sa.I(l);
+        const float *da_l = sa.da_seq + (size_t)l * 4 * BTH;
+        const float *in_l = sa.in(l), *h_l = sa.h(l);
         const int M = 4 * H;
         // (layer 0's input has only C columns: its weight gradient stays fp32)
         if (bf16 && l > 0) hipLaunchKernelGGL(gemm_tn_mfma<true>, dim3((I + TN - 1) / TN, (M + TM - 1) / TM, NPART), dim3(256), 0, st, da_l, M,
@@ -589,9 +569,9 @@ int nsd_lstm_batched_bwd(const nsd_dims *d, const ParamLayout &pl, const float *
         hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)(((long)M * I + 255) / 256)), dim3(256), 0, st, parts, NPART, (long)M * I,
                            slab + pl.w_ih[l]);
         if (bf16) hipLaunchKernelGGL(gemm_tn_mfma<true>, dim3((H + TN - 1) / TN, (M + TM - 1) / TM, NPART), dim3(256), 0, st, da_l, M,
-                                     hseq + (int64_t)l * BTH, H, parts, M, H, rows, T);
+                                     h_l, H, parts, M, H, rows, T);
         else      hipLaunchKernelGGL(gemm_tn_mfma<false>, dim3((H + TN - 1) / TN, (M + TM - 1) / TM, NPART), dim3(256), 0, st, da_l, M,
-                                     hseq + (int64_t)l * BTH, H, parts, M, H, rows, T);
+                                     h_l, H, parts, M, H, rows, T);
         hipLaunchKernelGGL(sum_parts_kernel, dim3((unsigned)(((long)M * H + 255) / 256)), dim3(256), 0, st, parts, NPART, (long)M * H,
                            slab + pl.w_hh[l]);
         {   // bias gradients: column sums of da over all rows, 64 row splits (the partials reuse the split-K buffer)

@@ -200,72 +200,58 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float *A, int lda, in
 // ---------------------------------------------------------------------------------------------
 static int gen_grid(int B) { const int cap = 8 * nsd_num_cus(); return B < cap ? B : cap; }
 
-// forward through all layers.  Train mode (save != 0): fills hseq/cseq/gact/inseq/top of the workspace.
-// Inference: only `top_out` [B,T,H] is produced; `scratch2` [B,T,H] is a ping-pong buffer.
-int nsd_lstm_generic_fwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, float *hseq, float *cseq, float *gact, float *inseq, float *top_out, float *scratch2,
-                         hipStream_t st) {
-    const int B = d->B, T = d->T, H = d->H, L = d->L;
-    const int64_t BTH = (int64_t)B * T * H;
-    const float *in = x;
+// forward through all layers.  Training (s.hseq != null): fills hseq / cseq / gact / inseq / top of the workspace.
+// Inference: only s.top_out [B,T,H] is produced; s.scratch2 [B,T,H] is a ping-pong buffer.
+int nsd_lstm_generic_fwd(const StackArgs &s, hipStream_t st) {
+    const int B = s.d.B, H = s.d.H, L = s.d.L;
     for (int l = 0; l < L; ++l) {
         GenFwdArgs a;
         memset(&a, 0, sizeof(a));
-        a.in = in; a.I = l == 0 ? d->C : H;
-        a.w_ih = params + pl.w_ih[l]; a.w_hh = params + pl.w_hh[l]; a.b_ih = params + pl.b_ih[l]; a.b_hh = params + pl.b_hh[l];
-        a.mask = (l < L - 1 && drop_lstm) ? drop_lstm + (int64_t)l * BTH : nullptr;
-        a.res_in = (residual && l >= 1) ? in : nullptr;
-        if (hseq) { a.hseq = hseq + (int64_t)l * BTH; a.cseq = cseq + (int64_t)l * BTH; a.gact = gact + (int64_t)l * 4 * BTH; }
-        if (l == L - 1) a.out = top_out;
-        else if (inseq) a.out = inseq + (int64_t)l * BTH;
-        else a.out = ((L - 1 - l) & 1) ? scratch2 : top_out;   // inference ping-pong; the last layer lands in top_out
-        a.B = B; a.T = T; a.H = H;
+        a.in = s.in(l); a.I = s.I(l);
+        a.w_ih = s.w_ih(l); a.w_hh = s.w_hh(l); a.b_ih = s.b_ih(l); a.b_hh = s.b_hh(l);
+        a.mask = s.mask(l);
+        a.res_in = (s.residual && l >= 1) ? a.in : nullptr;
+        if (s.hseq) { a.hseq = s.h(l); a.cseq = s.c(l); a.gact = s.gates(l); }
+        a.out = s.out(l);
+        a.B = B; a.T = s.d.T; a.H = H;
         const size_t lds = ((size_t)a.I + 6 * (size_t)H) * sizeof(float);
         if (lds > 160 * 1024) { nsd_set_error("generic lstm: H=%d too large for the LDS state", H); return NSD_E_INVALID; }
         if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)lstm_layer_fwd_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(lstm_layer_fwd_gen, dim3(gen_grid(B)), dim3(GEN_NT), lds, st, a);
         NSD_CHECK_LAUNCH("lstm_layer_fwd_gen");
-        in = a.out;
     }
     return NSD_OK;
 }
 
-// backward through all layers; weight / bias gradients are written to slab[0 .. P_lstm)
-int nsd_lstm_generic_bwd(const nsd_dims *d, const ParamLayout &pl, const float *params, const float *x, const float *drop_lstm,
-                         int residual, const float *hseq, const float *cseq, const float *gact, const float *inseq,
-                         const float *alpha, const float *dscore, const float *dpooled, float *da_seq, float *din_a, float *din_b,
-                         float *slab, hipStream_t st) {
-    const int B = d->B, T = d->T, H = d->H, L = d->L;
-    const int64_t BTH = (int64_t)B * T * H;
+// backward through all layers; weight / bias gradients are written to s.slab[0 .. P_lstm)
+int nsd_lstm_generic_bwd(const StackArgs &s, hipStream_t st) {
+    const int B = s.d.B, T = s.d.T, H = s.d.H, L = s.d.L;
     const long rows = (long)B * T;
-    const float *dsrc = nullptr;
     for (int l = L - 1; l >= 0; --l) {
-        const int I = l == 0 ? d->C : H;
+        const int I = s.I(l);
         GenBwdArgs a;
         memset(&a, 0, sizeof(a));
-        a.w_ih = params + pl.w_ih[l]; a.w_hh = params + pl.w_hh[l];
-        a.gact = gact + (int64_t)l * 4 * BTH; a.cseq = cseq + (int64_t)l * BTH;
-        a.dsrc = dsrc;
-        a.mask = (l < L - 1 && drop_lstm) ? drop_lstm + (int64_t)l * BTH : nullptr;
-        a.alpha = alpha; a.dscore = dscore; a.dpooled = dpooled; a.attn_w = params + pl.attn_w;
-        a.da_seq = da_seq;
-        a.din_seq = l > 0 ? ((l & 1) ? din_a : din_b) : nullptr;
-        a.residual_add = (residual && l >= 1) ? 1 : 0;
+        a.w_ih = s.w_ih(l); a.w_hh = s.w_hh(l);
+        a.gact = s.gates(l); a.cseq = s.c(l);
+        a.dsrc = l < L - 1 ? s.din(l + 1) : nullptr;
+        a.mask = s.mask(l);
+        a.alpha = s.alpha; a.dscore = s.dscore; a.dpooled = s.dpooled; a.attn_w = s.params + s.pl.attn_w;
+        a.da_seq = s.da_seq;
+        a.din_seq = l > 0 ? s.din(l) : nullptr;
+        a.residual_add = (s.residual && l >= 1) ? 1 : 0;
         a.B = B; a.T = T; a.I = I; a.H = H;
         const size_t lds = 7 * (size_t)H * sizeof(float);
         if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)lstm_layer_bwd_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(lstm_layer_bwd_gen, dim3(gen_grid(B)), dim3(GEN_NT), lds, st, a);
         NSD_CHECK_LAUNCH("lstm_layer_bwd_gen");
         // weight gradients of this layer: dW_ih = da^T . in_l ; dW_hh = da^T . h_l[t-1] ; db = column sums of da
-        const float *in_l = l == 0 ? x : inseq + (int64_t)(l - 1) * BTH;
         const int M = 4 * H;
-        hipLaunchKernelGGL(gemm_tn_kernel, dim3((I + 63) / 64, (M + 63) / 64), dim3(256), 0, st, da_seq, M, in_l, I,
-                           slab + pl.w_ih[l], I, M, I, rows, 0);
-        hipLaunchKernelGGL(gemm_tn_kernel, dim3((H + 63) / 64, (M + 63) / 64), dim3(256), 0, st, da_seq, M,
-                           hseq + (int64_t)l * BTH, H, slab + pl.w_hh[l], H, M, H, rows, T);
-        hipLaunchKernelGGL(colsum_kernel, dim3((M + 63) / 64), dim3(256), 0, st, da_seq, M, M, rows, slab + pl.b_ih[l], slab + pl.b_hh[l]);
+        hipLaunchKernelGGL(gemm_tn_kernel, dim3((I + 63) / 64, (M + 63) / 64), dim3(256), 0, st, s.da_seq, M, s.in(l), I,
+                           s.slab + s.pl.w_ih[l], I, M, I, rows, 0);
+        hipLaunchKernelGGL(gemm_tn_kernel, dim3((H + 63) / 64, (M + 63) / 64), dim3(256), 0, st, s.da_seq, M,
+                           s.h(l), H, s.slab + s.pl.w_hh[l], H, M, H, rows, T);
+        hipLaunchKernelGGL(colsum_kernel, dim3((M + 63) / 64), dim3(256), 0, st, s.da_seq, M, M, rows, s.slab + s.pl.b_ih[l], s.slab + s.pl.b_hh[l]);
         NSD_CHECK_LAUNCH("generic dW");
-        dsrc = a.din_seq;
     }
     return NSD_OK;
 }

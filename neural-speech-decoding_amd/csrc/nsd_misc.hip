@@ -126,25 +126,19 @@ __global__ __launch_bounds__(GR_COLS * GR_GROUPS) void grad_reduce_kernel(
     }
 }
 
-int nsd_grad_reduce_launch(const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs,
-                           long ph, int n_hslabs, float *grads, int accumulate, hipStream_t st) {
-    const long n = p_lstm + ph;
-    hipLaunchKernelGGL((grad_reduce_kernel<false>), dim3((unsigned)((n + GR_COLS - 1) / GR_COLS)), dim3(GR_COLS * GR_GROUPS), 0, st,
-                       slabs, slab_stride, n_slabs, p_lstm, hslabs, ph, n_hslabs, grads, accumulate, AdamTail{});
-    NSD_CHECK_LAUNCH("grad_reduce");
-    return NSD_OK;
-}
-
-int nsd_grad_reduce_adam_launch(const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs,
-                                long ph, int n_hslabs, float *grads, float *p, float *m, float *v, float lr, float b1,
-                                float b2, float eps, float wd, float gscale, int step, hipStream_t st) {
-    const long n = p_lstm + ph;
-    if (step < 1) { nsd_set_error("grad_reduce_adam: step must be >= 1"); return NSD_E_INVALID; }
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    AdamTail ad{p, m, v, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, wd, gscale};
-    hipLaunchKernelGGL((grad_reduce_kernel<true>), dim3((unsigned)((n + GR_COLS - 1) / GR_COLS)), dim3(GR_COLS * GR_GROUPS), 0, st,
-                       slabs, slab_stride, n_slabs, p_lstm, hslabs, ph, n_hslabs, grads, 0, ad);
-    NSD_CHECK_LAUNCH("grad_reduce_adam");
+int nsd_grad_reduce_launch(const SlabSet &s, int M, float *grads, int accumulate, const AdamStep *adam, const char *who, hipStream_t st) {
+    AdamTail ad{};
+    if (adam) {
+        if (adam->step < 1) { nsd_set_error("%s: step must be >= 1", who); return NSD_E_INVALID; }
+        const double bc1 = 1.0 - pow((double)adam->b1, adam->step), bc2 = 1.0 - pow((double)adam->b2, adam->step);
+        ad = AdamTail{adam->p, adam->m, adam->v, (float)(adam->lr / bc1), (float)(1.0 / sqrt(bc2)), adam->b1, adam->b2, adam->eps, adam->wd, adam->gscale};
+    }
+    const unsigned cols = (unsigned)((s.p_lstm + s.ph + GR_COLS - 1) / GR_COLS);
+    const dim3 grid = M > 1 ? dim3(cols, M) : dim3(cols), wg(GR_COLS * GR_GROUPS);
+    const auto kernel = M > 1 ? (adam ? grad_reduce_kernel<true, true> : grad_reduce_kernel<false, true>)
+                              : (adam ? grad_reduce_kernel<true, false> : grad_reduce_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h, grads, accumulate, ad);
+    NSD_CHECK_LAUNCH(who);
     return NSD_OK;
 }
 
@@ -257,15 +251,14 @@ __global__ void train_masks_kernel(uint64_t seed, uint32_t base_arg, const long 
         }
     }
 }
-static uint32_t drop_threshold(float p) { return nsd_drop_threshold(p); }
 int nsd_train_masks_launch(uint64_t seed, uint32_t base, const long long *step_dev, float p_lstm, float p_head, long n_lstm,
                            float *drop_lstm, long n_head, float *rrelu, float *drop_head, hipStream_t st) {
     if (!(p_lstm >= 0.f && p_lstm < 1.f) || !(p_head >= 0.f && p_head < 1.f)) { nsd_set_error("train_masks: p out of [0,1)"); return NSD_E_INVALID; }
     const long total = n_lstm + 2 * n_head;
     if (total <= 0) return NSD_OK;
     long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(train_masks_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seed, base, step_dev, drop_threshold(p_lstm),
-                       1.0f / (1.0f - p_lstm), drop_threshold(p_head), 1.0f / (1.0f - p_head), n_lstm, drop_lstm, n_head, rrelu, drop_head);
+    hipLaunchKernelGGL(train_masks_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seed, base, step_dev, nsd_drop_threshold(p_lstm),
+                       1.0f / (1.0f - p_lstm), nsd_drop_threshold(p_head), 1.0f / (1.0f - p_head), n_lstm, drop_lstm, n_head, rrelu, drop_head);
     NSD_CHECK_LAUNCH("train_masks");
     return NSD_OK;
 }
@@ -411,36 +404,9 @@ int nsd_att_close_launch(const float *hseq1, const float *pooled, const float *d
     return NSD_OK;
 }
 
-int nsd_loss_sum_launch(const float *loss, int B, float *out, hipStream_t st) {
-    hipLaunchKernelGGL(loss_sum_kernel<false>, dim3(1), dim3(256), 0, st, loss, B, out);
-    NSD_CHECK_LAUNCH("loss_sum");
-    return NSD_OK;
-}
-
-int nsd_multi_loss_sum_launch(const float *loss, int B, int M, float *out, hipStream_t st) {
-    hipLaunchKernelGGL(loss_sum_kernel<true>, dim3(M), dim3(256), 0, st, loss, B, out);
-    NSD_CHECK_LAUNCH("multi_loss_sum");
-    return NSD_OK;
-}
-
-int nsd_multi_grad_reduce_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
-                                 int M, float *grads, hipStream_t st) {
-    const long n = p_lstm + ph;
-    hipLaunchKernelGGL((grad_reduce_kernel<false, true>), dim3((unsigned)((n + GR_COLS - 1) / GR_COLS), M), dim3(GR_COLS * GR_GROUPS), 0, st,
-                       slabs, slab_stride, G, p_lstm, hslabs, ph, B, grads, 0, AdamTail{});
-    NSD_CHECK_LAUNCH("multi_grad_reduce");
-    return NSD_OK;
-}
-
-int nsd_multi_grad_reduce_adam_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
-                                      int M, float *grads, float *p, float *m, float *v, float lr, float b1, float b2, float eps,
-                                      float wd, float gscale, int step, hipStream_t st) {
-    const long n = p_lstm + ph;
-    if (step < 1) { nsd_set_error("multi_grad_reduce_adam: step must be >= 1"); return NSD_E_INVALID; }
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    AdamTail ad{p, m, v, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, wd, gscale};
-    hipLaunchKernelGGL((grad_reduce_kernel<true, true>), dim3((unsigned)((n + GR_COLS - 1) / GR_COLS), M), dim3(GR_COLS * GR_GROUPS), 0, st,
-                       slabs, slab_stride, G, p_lstm, hslabs, ph, B, grads, 0, ad);
-    NSD_CHECK_LAUNCH("multi_grad_reduce_adam");
+int nsd_loss_sum_launch(const float *loss, int B, int M, bool per_model, float *out, const char *who, hipStream_t st) {
+    const auto kernel = per_model ? loss_sum_kernel<true> : loss_sum_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(per_model ? M : 1), dim3(256), 0, st, loss, B, out);
+    NSD_CHECK_LAUNCH(who);
     return NSD_OK;
 }

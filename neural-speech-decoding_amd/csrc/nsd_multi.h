@@ -89,10 +89,3 @@ int nsd_lstm2_bwd48x4_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, i
 // dispatch by the launch plan of the M*B trials of the launch (plan48, nsd_lstm2.hip)
 int nsd_lstm2_multi_fwd_launch(const Lstm2FwdArgs &a, ModelSplit s, int M, hipStream_t st);
 int nsd_lstm2_multi_bwd_launch(const Lstm2BwdArgs &a, ModelSplit s, int M, hipStream_t st);
-// reductions over model m's G slabs and B head slabs into grads + m*P (and the Adam update of p / m / v + m*P): one launch for all models
-int nsd_multi_grad_reduce_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
-                                 int M, float *grads, hipStream_t st);
-int nsd_multi_grad_reduce_adam_launch(const float *slabs, long slab_stride, int G, long p_lstm, const float *hslabs, long ph, int B,
-                                      int M, float *grads, float *p, float *m, float *v, float lr, float b1, float b2, float eps,
-                                      float wd, float gscale, int step, hipStream_t st);
-int nsd_multi_loss_sum_launch(const float *loss, int B, int M, float *out, hipStream_t st);

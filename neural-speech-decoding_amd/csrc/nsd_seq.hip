@@ -613,7 +613,7 @@ int nsd_seq_loss_sum(const nsd_dims *d, uint32_t flags, const void *workspace, i
     SeqDims s;
     SeqWs w;
     if (const int rc = open_ws("seq_loss_sum", d, flags, workspace, workspace_bytes, out != nullptr, &s, &w)) return rc;
-    return nsd_loss_sum_launch(reinterpret_cast<const float *>(reinterpret_cast<const char *>(workspace) + w.loss), s.B, out, (hipStream_t)stream);
+    return nsd_loss_sum_launch(reinterpret_cast<const float *>(reinterpret_cast<const char *>(workspace) + w.loss), s.B, 1, false, out, "loss_sum", (hipStream_t)stream);
 }
 
 // Zero the persistent header of a freshly allocated workspace (the sticky status word).  Call once per allocation; an

@@ -152,6 +152,222 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert b"dx is available for H = 48" in L.nsd_last_error()
 
 
+# ---- order of refusals of the fp32 and model-batched workspace entry points ------------------------------------------------------
+# One row per entry point: (symbol, name in its texts, argument slots).  Slots: "d" dims, "M" models, "ws" / "bytes" the workspace and its
+# size, "rng" an nsd_rng (array), "x_stride", "flags"; ("ptr", name) a pointer of the entry point's null set; any other value is passed as it is.
+_P = lambda name: ("ptr", name)                                     # noqa: E731
+_ADAM = [1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1]
+_SINGLE = [
+    ("nsd_lstm_fwd", "lstm_fwd", ["d", _P("params"), _P("x"), None, "flags", "ws", "bytes", None]),
+    ("nsd_head_fwd", "head_fwd", ["d", _P("params"), None, None, "ws", "bytes", _P("logits"), None, None]),
+    ("nsd_head_bwd", "head_bwd", ["d", _P("params"), None, None, "logits_in", "dlogits", "labels_in", 1.0, "ws", "bytes", None]),
+    ("nsd_head_train", "head_train", ["d", _P("params"), None, None, _P("labels"), 1.0, "ws", "bytes", _P("logits"), None]),
+    ("nsd_lstm_head_train", "lstm_head_train",
+     ["d", _P("params"), _P("x"), None, None, None, _P("labels"), 1.0, "flags", "ws", "bytes", _P("logits"), None]),
+    ("nsd_lstm_head_train_rng", "lstm_head_train",
+     ["d", _P("params"), _P("x"), "rng", _P("labels"), 1.0, "flags", "ws", "bytes", _P("logits"), None]),
+    ("nsd_lstm_bwd", "lstm_bwd", ["d", _P("params"), _P("x"), None, "flags", "ws", "bytes", "dx", None]),
+    ("nsd_lstm_bwd_rng", "lstm_bwd", ["d", _P("params"), _P("x"), "rng", "flags", "ws", "bytes", None]),
+    ("nsd_grad_reduce", "grad_reduce", ["d", "ws", "bytes", _P("grads"), 0, None]),
+    ("nsd_grad_reduce_adam", "grad_reduce_adam", ["d", "ws", "bytes", _P("grads"), _P("p"), _P("m"), _P("v")] + _ADAM + [None]),
+    ("nsd_loss_sum", "loss_sum", ["d", "ws", "bytes", _P("out"), None]),
+]
+_LAUNCH_AT_B0 = {"nsd_grad_reduce", "nsd_grad_reduce_adam", "nsd_loss_sum", "nsd_multi_grad_reduce", "nsd_multi_grad_reduce_adam",
+                 "nsd_multi_loss_sum"}                               # (an empty batch still zeroes / updates: no early return to pin)
+_MULTI = [
+    ("nsd_multi_train_fwd", "multi_train_fwd",
+     ["d", "M", _P("params"), _P("x"), "x_stride", "rng", _P("labels"), "flags", "ws", "bytes", _P("logits"), None]),
+    ("nsd_multi_train_bwd", "multi_train_bwd", ["d", "M", _P("params"), _P("x"), "x_stride", "rng", "flags", "ws", "bytes", None]),
+    ("nsd_multi_grad_reduce", "multi_grad_reduce", ["d", "M", "ws", "bytes", _P("grads"), None]),
+    ("nsd_multi_grad_reduce_adam", "multi_grad_reduce_adam",
+     ["d", "M", "ws", "bytes", _P("grads"), _P("p"), _P("m"), _P("v")] + _ADAM + [None]),
+    ("nsd_multi_loss_sum", "multi_loss_sum", ["d", "M", "ws", "bytes", _P("out"), None]),
+    ("nsd_multi_infer", "multi_infer", ["d", "M", _P("params"), _P("x"), "x_stride", "flags", _P("logits"), None, None, None]),
+]
+_FAKE = 4096                                                        # never dereferenced: every call below is refused, or returns, before a launch
+
+
+def _call(L, sym, slots, **over):
+    """Calls `sym` with valid stand-ins for every slot but the overridden ones; returns (rc, last error text)."""
+    import ctypes as C
+    vals = {"flags": 2, "ws": _FAKE, "x_stride": 0, "dx": None, "logits_in": None, "dlogits": _FAKE, "labels_in": None}
+    vals.update(over)
+    args = []
+    for s in slots:
+        if isinstance(s, tuple):
+            args.append(vals.get(s[1], _FAKE))
+        elif s == "d":
+            args.append(None if vals["d"] is None else C.byref(vals["d"]))
+        elif s == "rng":
+            args.append(None if vals["rng"] is None else C.cast(vals["rng"], C.c_void_p))
+        elif isinstance(s, str):
+            args.append(vals[s])
+        else:
+            args.append(s)
+    rc = getattr(L, sym)(*args)
+    return rc, L.nsd_last_error().decode()
+
+
+def _rngs(M, p=0.6, p_last=None):
+    arr = (_lib.Rng * M)(*[_lib.Rng(1 + m, 4, p, p) for m in range(M)])
+    if p_last is not None:
+        arr[M - 1].p_lstm = p_last
+    return arr
+
+
+@pytest.mark.parametrize("sym,who,slots", _SINGLE, ids=[r[0] for r in _SINGLE])
+def test_refusal_order_of_the_fp32_workspace_entry_points(sym, who, slots):
+    """dims, the entry point's null-pointer set, its own refusal, the workspace size, then B == 0 -- in this order, each before anything is
+    launched (no GPU needed).  The _rng entry points look at the nsd_rng before all of that."""
+    import ctypes as C
+    L = nsd_amd.load_library()
+    d = _lib.Dims(4, 10, 8, 48, 2, 3, 32)
+    need = L.nsd_workspace_bytes(C.byref(d), None)
+    base = dict(d=d, bytes=need - 4, rng=_rngs(1))                   # a short workspace: whatever is refused below is refused ahead of it
+    ptrs = [s[1] for s in slots if isinstance(s, tuple)] + ["ws"]
+    has_rng = "rng" in slots
+
+    rc, err = _call(L, sym, slots, **{**base, "d": None})
+    assert rc == -1 and err == "dims is NULL"
+    rc, err = _call(L, sym, slots, **{**base, "d": _lib.Dims(4, 0, 8, 48, 2, 3, 32)})
+    assert rc == -1 and err == "bad batch dims B=4 T=0"
+    rc, err = _call(L, sym, slots, **{**base, "d": _lib.Dims(4, 10, 8, 48, 9, 3, 32)})
+    assert rc == -1 and err == "bad model dims C=8 H=48 L=9 K=3 F=32"
+    if has_rng:                                                      # the random streams are looked at first, NULL dims or not
+        rc, err = _call(L, sym, slots, **{**base, "d": None, "rng": None})
+        assert rc == -1 and err == "rng: null pointer"
+        rc, err = _call(L, sym, slots, **{**base, "d": None, "rng": _rngs(1, p=1.0)})
+        assert rc == -1 and err == "rng: p out of [0,1)"
+    for p in ptrs:                                                   # bad dims beat a null pointer, a null pointer beats the short workspace
+        rc, err = _call(L, sym, slots, **{**base, p: None, "d": _lib.Dims(-1, 10, 8, 48, 2, 3, 32)})
+        assert rc == -1 and err == "bad batch dims B=-1 T=10", (p, err)
+        rc, err = _call(L, sym, slots, **{**base, p: None})
+        assert rc == -1 and err == f"{who}: null pointer", (p, err)
+
+    d64 = _lib.Dims(4, 10, 8, 64, 2, 3, 32)
+    short64 = L.nsd_workspace_bytes(C.byref(d64), None) - 4
+    if sym == "nsd_head_bwd":
+        for kw in (dict(dlogits=None), dict(dlogits=None, labels_in=_FAKE), dict(dlogits=None, logits_in=_FAKE)):
+            rc, err = _call(L, sym, slots, **{**base, **kw})
+            assert rc == -1 and err == "head_bwd: need dlogits, or labels together with logits"
+            rc, err = _call(L, sym, slots, **{**base, **kw, "params": None})
+            assert rc == -1 and err == "head_bwd: null pointer"
+        rc, err = _call(L, sym, slots, **{**base, "dlogits": None, "labels_in": _FAKE, "logits_in": _FAKE})
+        assert rc == -3
+    if sym == "nsd_lstm_bwd":
+        rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64, "dx": _FAKE})
+        assert rc == -1 and err.startswith("lstm_bwd: dx is available for H = 48")
+        rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64, "dx": _FAKE, "x": None})
+        assert rc == -1 and err == "lstm_bwd: null pointer"
+        rc, err = _call(L, sym, slots, **{**base, "dx": _FAKE})
+        assert rc == -3
+    if sym == "nsd_lstm_bwd_rng":                                    # outside the single-launch path: refused after dims, ahead of the pointers
+        rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64, "params": None})
+        assert rc == -1 and err == "lstm_bwd_rng: shape outside the single-launch path (nsd_rng_path() == 0)"
+        rc, err = _call(L, sym, slots, **{**base, "d": _lib.Dims(4, 0, 8, 64, 2, 3, 32)})
+        assert rc == -1 and err == "bad batch dims B=4 T=0"
+    if sym == "nsd_lstm_head_train_rng":                             # ... and here behind the workspace and the empty batch
+        rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64})
+        assert rc == -3 and err.startswith("lstm_head_train: workspace of")
+        rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64 + 4})
+        assert rc == -1 and err == "lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0)"
+        d64_0 = _lib.Dims(0, 10, 8, 64, 2, 3, 32)
+        rc, err = _call(L, sym, slots, **{**base, "d": d64_0, "bytes": L.nsd_workspace_bytes(C.byref(d64_0), None)})
+        assert rc == 0
+
+    rc, err = _call(L, sym, slots, **base)
+    assert rc == -3 and err == f"{who}: workspace of {need - 4} bytes is smaller than nsd_workspace_bytes() = {need}"
+    rc, err = _call(L, sym, slots, **{**base, "bytes": 0})
+    assert rc == -3 and err.startswith(f"{who}: workspace of 0 bytes")
+    if sym not in _LAUNCH_AT_B0:
+        d0 = _lib.Dims(0, 10, 8, 48, 2, 3, 32)
+        need0 = L.nsd_workspace_bytes(C.byref(d0), None)
+        assert _call(L, sym, slots, **{**base, "d": d0, "bytes": need0})[0] == 0
+        assert _call(L, sym, slots, **{**base, "d": d0, "bytes": need0 - 4})[0] == -3      # the size is checked for an empty batch too
+
+
+@pytest.mark.parametrize("M", [1, 2])
+@pytest.mark.parametrize("sym,who,slots", _MULTI, ids=[r[0] for r in _MULTI])
+def test_refusal_order_of_the_model_batched_entry_points(sym, who, slots, M):
+    """dims / M / shape (then flags and the window stride where there are any), the null-pointer set, the random streams, the workspace,
+    B == 0; M = 1 is refused with the same texts as M > 1."""
+    import ctypes as C
+    L = nsd_amd.load_library()
+    d = _lib.Dims(4, 10, 8, 48, 2, 3, 32)
+    has_ws, has_rng, has_x = "ws" in slots, "rng" in slots, "x_stride" in slots
+    need = L.nsd_multi_workspace_bytes(C.byref(d), M, None)
+    assert need > 0
+    base = dict(d=d, M=M, bytes=need - 4, rng=_rngs(M))
+    ptrs = [s[1] for s in slots if isinstance(s, tuple)]
+    shape_text = f"{who}: shape outside the model-batched path (nsd_multi_path: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)"
+
+    rc, err = _call(L, sym, slots, **{**base, "d": None})
+    assert rc == -1 and err == f"{who}: dims is NULL"
+    for Mbad in (0, 33):
+        rc, err = _call(L, sym, slots, **{**base, "M": Mbad, "d": _lib.Dims(4, 0, 8, 48, 2, 3, 32)})
+        assert rc == -1 and err == f"{who}: M = {Mbad} models outside [1, 32]"
+    for bad in (_lib.Dims(4, 0, 8, 48, 2, 3, 32), _lib.Dims(4, 10, 8, 64, 2, 3, 32), _lib.Dims(4, 10, 8, 40, 2, 3, 32)):
+        rc, err = _call(L, sym, slots, **{**base, "d": bad, ptrs[0]: None})
+        assert rc == -1 and err == shape_text
+    if has_x:
+        rc, err = _call(L, sym, slots, **{**base, "flags": 1, ptrs[0]: None})
+        assert rc == -1 and err == f"{who}: flags 0x1: no residual extension on the model-batched path"
+        if M > 1:
+            rc, err = _call(L, sym, slots, **{**base, "x_stride": 4 * 10 * 8 - 1, ptrs[0]: None})
+            assert rc == -1 and err.startswith(f"{who}: x_model_stride 319: 0 (one window set for all models) or >= B*T*C = 320")
+    for p in ptrs:                                                   # a null pointer: ahead of bad random streams and of the workspace
+        rc, err = _call(L, sym, slots, **{**base, p: None, "rng": _rngs(M, p=1.0), "ws": None})
+        assert rc == -1 and err == f"{who}: null pointer", (p, err)
+    if has_rng:
+        rc, err = _call(L, sym, slots, **{**base, "rng": _rngs(M, p=1.0), "ws": None})
+        assert rc == -1 and err == "rng: p out of [0,1)"
+        if M > 1:
+            rc, err = _call(L, sym, slots, **{**base, "rng": _rngs(M, p_last=0.5), "ws": None})
+            assert rc == -1 and err.startswith(f"{who}: rng[{M - 1}] has p_lstm / p_head 0.5 / 0.6, rng[0] 0.6 / 0.6")
+        rc, err = _call(L, sym, slots, **{**base, "rng": None})      # no random streams (evaluation of the training path): allowed
+        assert rc == -3
+    if has_ws:
+        rc, err = _call(L, sym, slots, **{**base, "ws": None})
+        assert rc == -1 and err == f"{who}: workspace is NULL"
+        rc, err = _call(L, sym, slots, **base)
+        assert rc == -3 and err == f"{who}: workspace of {need - 4} bytes is smaller than nsd_multi_workspace_bytes() = {need}"
+    if sym not in _LAUNCH_AT_B0:
+        d0 = _lib.Dims(0, 10, 8, 48, 2, 3, 32)
+        need0 = L.nsd_multi_workspace_bytes(C.byref(d0), M, None)
+        assert _call(L, sym, slots, **{**base, "d": d0, "bytes": need0})[0] == 0
+        if has_ws:
+            assert _call(L, sym, slots, **{**base, "d": d0, "bytes": need0 - 4})[0] == -3
+
+
+def _ws_layout(L, d, M=None):
+    import ctypes as C
+    w = _lib.WsLayout()
+    n = L.nsd_workspace_bytes(C.byref(d), C.byref(w)) if M is None else L.nsd_multi_workspace_bytes(C.byref(d), M, C.byref(w))
+    return n, tuple(getattr(w, f) for f, _ in _lib.WsLayout._fields_)
+
+
+def test_one_model_of_the_model_batched_workspace_is_the_single_model_workspace():
+    """M = 1 is the single-model case of one layout function, not a special case: same size, same regions.  The shapes outside
+    nsd_multi_path have the single-model layout only: held to the recorded one (one gradient slab, da_seq / din regions in use)."""
+    import ctypes as C
+    L = nsd_amd.load_library()
+    for B, T in ((4, 10), (256, 250), (300, 40), (1025, 7), (0, 10)):
+        d = _lib.Dims(B, T, 8, 48, 2, 3, 32)
+        assert L.nsd_multi_path(C.byref(d), 1) == 1
+        assert _ws_layout(L, d, 1) == _ws_layout(L, d)
+    gen, bat = _lib.Dims(6, 17, 8, 40, 2, 3, 32), _lib.Dims(32, 20, 8, 128, 2, 3, 32)
+    assert L.nsd_multi_path(C.byref(gen), 1) == 0 and L.nsd_multi_path(C.byref(bat), 1) == 0
+    assert L.nsd_multi_workspace_bytes(C.byref(gen), 1, None) == -1 and L.nsd_multi_workspace_bytes(C.byref(bat), 1, None) == -1
+    assert _ws_layout(L, gen) == _WS_GENERIC_H40
+    assert _ws_layout(L, bat) == _WS_BATCHED_H128
+
+
+# (bytes, (hseq, cseq, gact, inseq, top, alpha, pooled, fc0_pre, dscore, dpooled, loss, adpack, slabs, n_slabs, hslabs, da_seq, din, total))
+_WS_GENERIC_H40 = (728672, (0, 8160, 16320, 48960, 53040, 57120, 57224, 57464, 57656, 57760, 58000, 58008, 58416, 1, 79536, 88728, 121368, 182168))
+_WS_BATCHED_H128 = (11513472, (0, 163840, 327680, 983040, 1064960, 1146880, 1147520, 1151616, 1152640, 1153280, 1157376, 1157408, 1159968, 1, 1362720,
+                              1510304, 2165664, 2878368))
+
+
 def test_facade_surface_matches_reference(ref_state):
     import inspect
     sig = inspect.signature(nsd_amd.EEG_LSTM.__init__)
