@@ -168,7 +168,8 @@ int nsd_lstm_head_train(const nsd_dims *d, const float *params, const float *x, 
  * Train-mode random streams generated INSIDE the kernels (no mask tensors in HBM): the three streams of one step are
  * value(seed, base_stream + {0: LSTM inter-layer dropout [B,T,H], 1: RReLU slope [B,F], 2: head dropout [B,F]}, index),
  * the same pure function as nsd_train_masks / oracle -- a step run this way is bit-identical to the same step run with
- * the masks of nsd_train_masks passed explicitly.  Only where nsd_rng_path(d) != 0 (the single-launch H = 48 shape).
+ * the masks of nsd_train_masks passed explicitly.  Only where nsd_rng_path(d) != 0 (the single-launch H = 48 shape: L = 2, C <= 8,
+ * T <= 1024, F <= 64, K <= 8); elsewhere both entry points return NSD_E_INVALID before any launch and nsd_last_error names these limits.
  */
 typedef struct nsd_rng {
     uint64_t seed;

@@ -452,7 +452,7 @@ static int lstm_head_train_impl(const nsd_dims *d, const float *params, const fl
     if (const int rc = enter(&c, "lstm_head_train", d, params && x && workspace && logits && labels, nullptr, workspace, workspace_bytes, stream))
         return leave(rc);
     if (!fused_train_shape(d)) {
-        if (rng) { nsd_set_error("lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0)"); return NSD_E_INVALID; }
+        if (rng) { nsd_set_error("lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)"); return NSD_E_INVALID; }
         // shapes outside the fused kernel: the two launches it replaces
         const int rc = nsd_lstm_fwd(d, params, x, drop_lstm, flags, workspace, workspace_bytes, stream);
         if (rc != NSD_OK) return rc;
@@ -528,7 +528,7 @@ int nsd_lstm_bwd_rng(const nsd_dims *d, const float *params, const float *x, con
     RngArgs r;
     if (make_rng(rng, &r) != NSD_OK) return NSD_E_INVALID;
     if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (!fused_train_shape(d)) { nsd_set_error("lstm_bwd_rng: shape outside the single-launch path (nsd_rng_path() == 0)"); return NSD_E_INVALID; }
+    if (!fused_train_shape(d)) { nsd_set_error("lstm_bwd_rng: shape outside the single-launch path (nsd_rng_path() == 0: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)"); return NSD_E_INVALID; }
     return lstm_bwd_impl(d, params, x, nullptr, &r, flags, workspace, workspace_bytes, nullptr, stream);
 }
 

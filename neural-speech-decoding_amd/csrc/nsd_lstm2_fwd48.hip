@@ -387,7 +387,8 @@ template <int NB, class A>
 __device__ __forceinline__ void saver_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     const int T = a.T;
     SvDesc d[SPIECES];
-    float *const sv_base = a.hseq0;                            // (training launches always carry the whole workspace)
+    // training launches carry the whole workspace; inference without the tail (F or K beyond 64: nsd_head.hip follows) has `top` alone
+    float *const sv_base = a.hseq0 ? a.hseq0 : a.top;
 #pragma unroll
     for (int q = 0; q < SPIECES; ++q) {
         const int e = q * 64 + lane;                       // float4 index in the chunk image [k][layer][84]

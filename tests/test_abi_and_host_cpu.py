@@ -263,14 +263,14 @@ def test_refusal_order_of_the_fp32_workspace_entry_points(sym, who, slots):
         assert rc == -3
     if sym == "nsd_lstm_bwd_rng":                                    # outside the single-launch path: refused after dims, ahead of the pointers
         rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64, "params": None})
-        assert rc == -1 and err == "lstm_bwd_rng: shape outside the single-launch path (nsd_rng_path() == 0)"
+        assert rc == -1 and err == "lstm_bwd_rng: shape outside the single-launch path (nsd_rng_path() == 0: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)"
         rc, err = _call(L, sym, slots, **{**base, "d": _lib.Dims(4, 0, 8, 64, 2, 3, 32)})
         assert rc == -1 and err == "bad batch dims B=4 T=0"
     if sym == "nsd_lstm_head_train_rng":                             # ... and here behind the workspace and the empty batch
         rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64})
         assert rc == -3 and err.startswith("lstm_head_train: workspace of")
         rc, err = _call(L, sym, slots, **{**base, "d": d64, "bytes": short64 + 4})
-        assert rc == -1 and err == "lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0)"
+        assert rc == -1 and err == "lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)"
         d64_0 = _lib.Dims(0, 10, 8, 64, 2, 3, 32)
         rc, err = _call(L, sym, slots, **{**base, "d": d64_0, "bytes": L.nsd_workspace_bytes(C.byref(d64_0), None)})
         assert rc == 0

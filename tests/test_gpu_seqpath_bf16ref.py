@@ -42,7 +42,8 @@ def bound_of(kind: str) -> float:
     return {"clean": REF_GRAD_RTOL_CLEAN, "streams": REF_GRAD_RTOL_STREAMS, "short": REF_GRAD_RTOL_SHORT, "large": REF_GRAD_RTOL_LARGE}[kind]
 
 
-# name -> (C, H, L, K, D, B, T, p (dropout / RReLU / head-dropout streams, None = off), route, bound kind, diag no-fused flag)
+# name -> (C, H, L, K, D, B, T, p (dropout / RReLU / head-dropout streams, None = off), route, bound kind, diag no-fused flag
+#          [, F: width of fc.0, 32 where it is left out])
 CASES = {
     "fused_h64":        (8, 64, 2, 5, 1, 40, 24, None, "fused2", "clean", False),
     "fused_h128":       (8, 128, 2, 3, 1, 64, 20, None, "fused2", "clean", False),
@@ -67,6 +68,11 @@ CFG3_FULL = (8, 256, 2, 5, 1, 1024, 250, None, "fused2", "large", False)
 RNG_SEED, RNG_BASE = 0x5EEDBF16, 24
 
 
+def case_F(case) -> int:
+    """width of fc.0 of a case: its twelfth field, 32 (the reference's) where the case has eleven"""
+    return case[11] if len(case) > 11 else 32
+
+
 def kink_safe(st, F=32):
     """fc.0.bias = +-4 (alternating): the fc.0 pre-activations (spread 0.6 .. 0.8) stay far from the RReLU kink"""
     st = dict(st)
@@ -77,26 +83,28 @@ def kink_safe(st, F=32):
 def case_inputs(case, seed=0):
     """(flat params, x, labels, masks for the emulation, rng dict for the kernels) of a case"""
     C, H, L, K, D, B, T, p = case[:8]
-    st = kink_safe(synth_params(C, H, L, K, seed=1000 + 7 * H + L + 3 * C + seed, D=D))
-    flat = np.concatenate([st[k].ravel() for k in sr.param_layout(C, H, L, K, 32, D)]).astype(np.float32)
+    F = case_F(case)
+    st = kink_safe(synth_params(C, H, L, K, F=F, seed=1000 + 7 * H + L + 3 * C + seed, D=D), F)
+    flat = np.concatenate([st[k].ravel() for k in sr.param_layout(C, H, L, K, F, D)]).astype(np.float32)
     x, y = synth_x(B, T, C=C, seed=B + T + seed), synth_labels(B, K, seed=B + seed)
     masks, rng = {}, None
     if p is not None:
         masks = dict(drop_lstm=orc.dropout_mask(RNG_SEED, RNG_BASE, p, (L - 1, B, T, D * H)) if L > 1 else None,
-                     rrelu_slope=orc.rrelu_noise(RNG_SEED, RNG_BASE + 1, (B, 32)),
-                     drop_head=orc.dropout_mask(RNG_SEED, RNG_BASE + 2, p, (B, 32)))
+                     rrelu_slope=orc.rrelu_noise(RNG_SEED, RNG_BASE + 1, (B, F)),
+                     drop_head=orc.dropout_mask(RNG_SEED, RNG_BASE + 2, p, (B, F)))
         rng = dict(seed=RNG_SEED, base_stream=RNG_BASE, p_lstm=p, p_head=p)
     return flat, x, y, masks, rng
 
 
 def emulate(case, flat, x, y, masks, **kw):
     C, H, L, K, D = case[:5]
-    return sr.seq_bf16_ref(flat, x, y, C=C, H=H, L=L, K=K, D=D, route=case[8], threads=CPU_THREADS, **masks, **kw)
+    return sr.seq_bf16_ref(flat, x, y, C=C, H=H, L=L, K=K, F=case_F(case), D=D, route=case[8], threads=CPU_THREADS, **masks, **kw)
 
 
 def compare(tag, case, got_logits, got_grads, ref, got_loss=None, got_probs=None, rtol=None):
     """every tensor against the emulation; prints the worst errors (pytest -s) before asserting"""
     C, H, L, K, D, B = case[:6]
+    F = case_F(case)
     rtol = bound_of(case[9]) if rtol is None else rtol
     margin = sr.kink_margin(ref["fc0_pre"])
     lerr = float(np.abs(got_logits - ref["logits"]).max())
@@ -107,7 +115,7 @@ def compare(tag, case, got_logits, got_grads, ref, got_loss=None, got_probs=None
         msg += f"  loss {abs(got_loss - ref['loss']):.2e}"
     errs = {}
     if got_grads is not None:
-        errs = sr.rel_errors(got_grads, ref["grads"], C, H, L, K, 32, D)
+        errs = sr.rel_errors(got_grads, ref["grads"], C, H, L, K, F, D)
         lstm = {k: v for k, v in errs.items() if k.startswith("lstm.")}
         head = {k: v for k, v in errs.items() if not k.startswith("lstm.") and k != "attn.bias"}
         wl, wh = max(lstm.items(), key=lambda kv: kv[1]), max(head.items(), key=lambda kv: kv[1])
@@ -121,11 +129,12 @@ def compare(tag, case, got_logits, got_grads, ref, got_loss=None, got_probs=None
     if got_loss is not None:
         assert abs(got_loss - ref["loss"]) < REF_LOSS_TOL
     # argmax agrees wherever the emulation's margin exceeds the logit bound
-    srt = np.sort(ref["logits"], axis=1)
-    clear = (srt[:, -1] - srt[:, -2]) > 2 * REF_LOGIT_TOL
-    assert np.array_equal(got_logits.argmax(1)[clear], ref["logits"].argmax(1)[clear])
+    if K > 1:
+        srt = np.sort(ref["logits"], axis=1)
+        clear = (srt[:, -1] - srt[:, -2]) > 2 * REF_LOGIT_TOL
+        assert np.array_equal(got_logits.argmax(1)[clear], ref["logits"].argmax(1)[clear])
     if got_grads is not None:
-        ga = sr.unflatten(got_grads, C, H, L, K, 32, D)
+        ga = sr.unflatten(got_grads, C, H, L, K, F, D)
         assert abs(float(ga["attn.bias"][0])) < 1e-4                       # analytically zero
         for k, v in errs.items():
             if k != "attn.bias":
@@ -162,7 +171,7 @@ def run_gpu(case, flat, x, y, rng, dev, ws=None):
     import torch
     from nsd_amd import ops
     C, H, L, K, D, B, T = case[:7]
-    spec = ops.ModelSpec(C=C, H=H, L=L, K=K, D=D)
+    spec = ops.ModelSpec(C=C, H=H, L=L, K=K, F=case_F(case), D=D)
     assert spec.seq_path(B, T)
     ft = torch.from_numpy(flat).to(dev)
     xt, yt = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
