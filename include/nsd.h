@@ -274,6 +274,60 @@ int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_st
                 const int64_t *step_dev, uint32_t flags, float *y, void *stream);
 
 /*
+ * ---- soft targets: label smoothing, class weights, mixup, distillation in the fused train step (an EXTENSION) ----
+ *
+ * Every fused head forms its loss either from int32 labels (the entry points above and below) or, through the `_soft` twins, from a
+ * per-trial target row q[b, 0..K) (device fp32, finite, q >= 0, any row sum s_b = sum_k q[b,k]):
+ *   loss_b     = - sum_k q[b,k] * log softmax(logits_b)[k]
+ *   dlogits_bk = scale * (s_b * p_bk - q[b,k])
+ * which is torch.nn.functional.cross_entropy(logits, target_probs, weight=w, label_smoothing=eps) when q holds
+ * w_k * ((1 - eps) * target_k + eps / K) -- up to the normalisation: `scale` stays the caller's (1 / B_global in the trainers), where
+ * torch's weighted `mean` divides by the sum of the weights instead.  A zero row is a trial that contributes nothing.  s p_k - q_k is
+ * formed as (sum_{j != k} (q_j e_k - q_k e_j)) / d, e = exp(logits - max), d = sum e: like the hard path's p_y - 1 = -(sum of the others) / d
+ * it has no O(1) - O(1) difference; the loss is sum_k q_k ((max - logit_k) + log d).  One-hot rows reproduce the hard-label entry point
+ * (same logits bit for bit, same gradients up to the order of a K-term sum).
+ * Each `_soft` entry point is its hard-label twin with `targets` ([B,K]; [M*B][K] for nsd_multi_*) in place of `labels`: same domain,
+ * fallbacks, workspace contents, refusals and NSD_E_WORKSPACE behaviour; the backward calls that follow are the existing ones
+ * (nsd_lstm_bwd[_rng], nsd_multi_train_bwd, nsd_seq_train_bwd[_dx]) and nsd_loss_sum / nsd_multi_loss_sum / nsd_seq_loss_sum read the
+ * soft loss.  nsd_lstm_head_train_soft is the twin of nsd_lstm_head_train (rng == NULL: explicit mask tensors, each may be NULL) AND of
+ * nsd_lstm_head_train_rng (rng != NULL: the three mask pointers must be NULL; NSD_E_INVALID where nsd_rng_path(d) == 0); outside the
+ * single-launch shape it runs nsd_lstm_fwd + nsd_head_train_soft.  Additive: NSD_VERSION stays 301, a caller detects the feature by
+ * the symbols.
+ */
+int nsd_head_train_soft(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
+                        const float *targets, float scale, float *workspace, int64_t workspace_bytes, float *logits, void *stream);
+int nsd_lstm_head_train_soft(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, const float *rrelu_slope,
+                             const float *drop_head, const nsd_rng *rng, const float *targets, float scale, uint32_t flags,
+                             float *workspace, int64_t workspace_bytes, float *logits, void *stream);
+
+/*
+ * nsd_mixup: the target rows of a step from its labels -- label smoothing, class weights -- and, with mix > 0, mixed windows, in ONE
+ * launch for all models.  Per model, with b the trial's index inside ITS model's batch, R(i) = value(seed, base_stream + 3, i),
+ * U(r) = float(r >> 8) * 2^-24 and P(b, slot) as for nsd_augment (the slots used here are ones nsd_augment leaves alone: an augmented
+ * step's draws do not move):
+ *   partner   r = 1 + R(2^63 | 2^62) mod (B - 1)  (B >= 2),  p(b) = (b + r) mod B: a rotation of the batch, a bijection, never b itself
+ *   weights   lambda_b = 1 - mix * U(R(P(b, 1024))),  mu_b = 1 - lambda_b      (mix in [0, 1]; mix = 1: lambda uniform, Beta(1, 1) mixup)
+ *   base(j)[k] = w_k * (k == j ? (1 - eps) + eps / K : eps / K)                 (class_weight == NULL: no multiply)
+ *   y[b]         = lambda_b * x[b] + mu_b * x[p(b)]
+ *   targets[b,k] = lambda_b * base(label_b)[k] + mu_b * base(label_p(b))[k]
+ * Every fp32 operation rounds on its own (no FMA contraction), in this order: ek = eps / float(K); on = (1 - eps) + ek;
+ * base = k == j ? on : ek, then w_k * base; m = mix * U; lambda = 1 - m; mu = 1 - lambda; out = (lambda * a) + (mu * b) for the
+ * windows and the targets alike.  mix == 0 or B == 1: nothing is mixed -- y is a bitwise copy of x and targets[b] = base(label_b)
+ * exactly (no multiplication by lambda = 1); with mix == 0, x and y may both be NULL and the launch only builds targets.  eps == 0,
+ * class_weight == NULL, mix == 0: one-hot rows.  A label outside [0, K) gives the row of no class (eps / K everywhere).
+ *   x_model_stride, rng[m], step_dev   as for nsd_augment (p_lstm / p_head are ignored); labels [M*B], y [M*B][T*C], targets [M*B][K]
+ * NSD_E_INVALID before any launch: M outside [1, NSD_MAX_MODELS]; NULL labels / targets / mix / rng; smoothing outside [0, 1); mix
+ * outside [0, 1]; K outside [1, 64]; T or C < 1; x / y NULL with mix > 0, or only one of the two given; a negative x_model_stride or
+ * one in (0, B*T*C); y overlapping x.  B = 0 launches nothing.  Only d->B, T, C, K are read.  Additive, detected by the symbol.
+ */
+typedef struct nsd_mix {
+    float mix, smoothing;
+} nsd_mix;
+int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels,
+              const float *class_weight /* NULL or [K] device */, const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev,
+              float *y, float *targets /* [M*B][K] */, void *stream);
+
+/*
  * ---- model-batched H = 48 path: M models of one shape trained / evaluated in the launches one model uses ----
  *
  * Folds, seeds and ensembles of EEG_LSTM (lstm_eeg_model.py:13-39): each model has its own parameters, windows, labels and random
@@ -303,6 +357,9 @@ int     nsd_multi_path(const nsd_dims *d, int32_t M);
 int64_t nsd_multi_workspace_bytes(const nsd_dims *d, int32_t M, nsd_ws_layout *layout_out);
 int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
                         const int32_t *labels, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream);
+/* nsd_multi_train_fwd with targets [M*B][K] in place of the labels (soft targets, above) */
+int nsd_multi_train_fwd_soft(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                             const float *targets, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream);
 int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
                         uint32_t flags, float *workspace, int64_t workspace_bytes, void *stream);
 int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, void *stream);
@@ -393,6 +450,9 @@ int nsd_seq_infer(const nsd_dims *d, const float *params, const float *x, uint32
                   void *workspace, int64_t workspace_bytes, void *stream);
 int nsd_seq_train_fwd(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const int32_t *labels,
                       float scale, uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream);
+/* nsd_seq_train_fwd with targets [B][K] in place of the labels (soft targets, above); its logits are nsd_seq_train_fwd's bit for bit */
+int nsd_seq_train_fwd_soft(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const float *targets,
+                           float scale, uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream);
 int nsd_seq_train_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace,
                       int64_t workspace_bytes, float *grads, void *stream);
 int nsd_seq_train_fwd_logits(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, uint32_t flags,

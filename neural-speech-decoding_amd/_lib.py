@@ -37,6 +37,11 @@ class Aug(C.Structure):
 NSD_AUG_ZSCORE = 1
 
 
+class Mix(C.Structure):
+    """nsd_mix of include/nsd.h"""
+    _fields_ = [("mix", C.c_float), ("smoothing", C.c_float)]
+
+
 class NsdError(RuntimeError):
     pass
 
@@ -103,6 +108,12 @@ SYMBOLS = {
     # trial augmentation for the trainers
     "nsd_augment_path": (C.c_int, [_dp]),
     "nsd_augment": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _vp, _vp, _vp, C.c_uint32, _fp, _vp]),
+    # soft targets (label smoothing, class weights, mixup, distillation)
+    "nsd_mixup": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _ip, _fp, _vp, _vp, _vp, _fp, _fp, _vp]),
+    "nsd_head_train_soft": (C.c_int, [_dp, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_int64, _fp, _vp]),
+    "nsd_lstm_head_train_soft": (C.c_int, [_dp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, C.c_float, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
+    "nsd_multi_train_fwd_soft": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _vp, _fp, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
+    "nsd_seq_train_fwd_soft": (C.c_int, [_dp, _fp, _fp, _vp, _fp, C.c_float, C.c_uint32, _vp, C.c_int64, _fp, _vp]),
     # model-batched H = 48 path (several models per launch)
     "nsd_multi_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_multi_workspace_bytes": (C.c_int64, [_dp, C.c_int32, C.POINTER(WsLayout)]),

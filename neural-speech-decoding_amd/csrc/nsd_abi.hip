@@ -266,11 +266,21 @@ static void attach_head(Lstm2FwdArgs *a, const HeadArgs &h) {
     a->eval_slope = h.eval_slope; a->K = h.K; a->F = h.F;
 }
 // the fused training head: forward, loss, and the head's backward up to dscore / dpooled and the per-trial head slabs (h: bound to the workspace)
-static void attach_head_train(Lstm2FwdArgs *a, const HeadArgs &h, const int32_t *labels, float scale, float *logits) {
+// What a fused head's loss is formed from: int32 labels [B] (mean CE) or, the `_soft` entry points, fp32 target rows [B,K].  One of the two.
+struct Target {
+    const int32_t *labels;
+    const float *targets;
+    bool given() const { return labels || targets; }
+};
+static inline Target hard(const int32_t *labels) { return Target{labels, nullptr}; }
+static inline Target soft(const float *targets) { return Target{nullptr, targets}; }
+
+static void attach_head_train(Lstm2FwdArgs *a, const HeadArgs &h, const Target &tg, float scale, float *logits) {
     attach_head(a, h);
-    a->head_train = 1;
+    a->head_train = tg.targets ? HEAD_TRAIN_SOFT : 1;
     if (!a->residual) a->top = nullptr;      // top == layer-1 h: the kernel's tail reads hseq1, the saver skips the duplicate
-    a->labels = labels; a->scale = scale;
+    if (tg.targets) a->targets = tg.targets; else a->labels = tg.labels;
+    a->scale = scale;
     a->logits = logits; a->loss = h.loss; a->alpha = h.alpha; a->pooled = h.pooled;
     a->fc0_pre = h.fc0_pre; a->dscore = h.dscore; a->dpooled = h.dpooled;
     a->adpack = h.adpack; a->hslabs = h.hslabs;
@@ -425,13 +435,13 @@ int nsd_head_bwd(const nsd_dims *d, const float *params, const float *rrelu_slop
     return nsd_head_launch(h, true, c.st);
 }
 
-int nsd_head_train(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
-                   const int32_t *labels, float scale, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+static int head_train_impl(const char *who, const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
+                           const Target &tg, float scale, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
     Ctx c;
-    if (const int rc = enter(&c, "head_train", d, params && workspace && logits && labels, nullptr, workspace, workspace_bytes, stream)) return leave(rc);
+    if (const int rc = enter(&c, who, d, params && workspace && logits && tg.given(), nullptr, workspace, workspace_bytes, stream)) return leave(rc);
     HeadArgs h = build_head(d, params, &c);
     h.rrelu_slope = rrelu_slope; h.drop_head = drop_head;
-    h.logits = logits; h.logits_in = logits; h.labels = labels; h.scale = scale;
+    h.logits = logits; h.logits_in = logits; h.labels = tg.labels; h.targets = tg.targets; h.scale = scale;
     const int rc = nsd_head_train_launch(h, c.st);
     if (rc != 0) return rc < 0 ? rc : NSD_OK;
     // shape does not fit the fused kernel's LDS budget: two passes
@@ -440,26 +450,37 @@ int nsd_head_train(const nsd_dims *d, const float *params, const float *rrelu_sl
     return nsd_head_launch(h, true, c.st);
 }
 
+int nsd_head_train(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
+                   const int32_t *labels, float scale, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    return head_train_impl("head_train", d, params, rrelu_slope, drop_head, hard(labels), scale, workspace, workspace_bytes, logits, stream);
+}
+
+int nsd_head_train_soft(const nsd_dims *d, const float *params, const float *rrelu_slope, const float *drop_head,
+                        const float *targets, float scale, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    return head_train_impl("head_train_soft", d, params, rrelu_slope, drop_head, soft(targets), scale, workspace, workspace_bytes, logits, stream);
+}
+
 int nsd_rng_path(const nsd_dims *d) {
     if (nsd_check_dims(d) != NSD_OK) return 0;
     return fused_train_shape(d) ? 1 : 0;
 }
 
 static int lstm_head_train_impl(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm,
-                                const float *rrelu_slope, const float *drop_head, const RngArgs *rng, const int32_t *labels,
+                                const float *rrelu_slope, const float *drop_head, const RngArgs *rng, const Target &tg,
                                 float scale, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
     Ctx c;
-    if (const int rc = enter(&c, "lstm_head_train", d, params && x && workspace && logits && labels, nullptr, workspace, workspace_bytes, stream))
+    const char *who = tg.targets ? "lstm_head_train_soft" : "lstm_head_train";
+    if (const int rc = enter(&c, who, d, params && x && workspace && logits && tg.given(), nullptr, workspace, workspace_bytes, stream))
         return leave(rc);
     if (!fused_train_shape(d)) {
-        if (rng) { nsd_set_error("lstm_head_train_rng: shape outside the single-launch path (nsd_rng_path() == 0: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)"); return NSD_E_INVALID; }
+        if (rng) { nsd_set_error("%s: shape outside the single-launch path (nsd_rng_path() == 0: H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8)", tg.targets ? "lstm_head_train_soft with rng" : "lstm_head_train_rng"); return NSD_E_INVALID; }
         // shapes outside the fused kernel: the two launches it replaces
         const int rc = nsd_lstm_fwd(d, params, x, drop_lstm, flags, workspace, workspace_bytes, stream);
         if (rc != NSD_OK) return rc;
-        return nsd_head_train(d, params, rrelu_slope, drop_head, labels, scale, workspace, workspace_bytes, logits, stream);
+        return head_train_impl(tg.targets ? "head_train_soft" : "head_train", d, params, rrelu_slope, drop_head, tg, scale, workspace, workspace_bytes, logits, stream);
     }
     Lstm2FwdArgs a = build_lstm_fwd(d, params, x, drop_lstm, flags, &c, nullptr);
-    attach_head_train(&a, build_head(d, params, &c), labels, scale, logits);
+    attach_head_train(&a, build_head(d, params, &c), tg, scale, logits);
     a.rrelu_slope = rrelu_slope; a.drop_head = drop_head;
     if (rng) a.rng = *rng;
     return nsd_lstm2_fwd_launch(a, d->H, c.st);
@@ -468,14 +489,25 @@ static int lstm_head_train_impl(const nsd_dims *d, const float *params, const fl
 int nsd_lstm_head_train(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm,
                         const float *rrelu_slope, const float *drop_head, const int32_t *labels, float scale, uint32_t flags,
                         float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
-    return lstm_head_train_impl(d, params, x, drop_lstm, rrelu_slope, drop_head, nullptr, labels, scale, flags, workspace, workspace_bytes, logits, stream);
+    return lstm_head_train_impl(d, params, x, drop_lstm, rrelu_slope, drop_head, nullptr, hard(labels), scale, flags, workspace, workspace_bytes, logits, stream);
 }
 
 int nsd_lstm_head_train_rng(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const int32_t *labels,
                             float scale, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
     RngArgs r;
     if (make_rng(rng, &r) != NSD_OK) return NSD_E_INVALID;
-    return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, &r, labels, scale, flags, workspace, workspace_bytes, logits, stream);
+    return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, &r, hard(labels), scale, flags, workspace, workspace_bytes, logits, stream);
+}
+
+// the soft-target twin of both: explicit mask tensors (rng == NULL) or the in-kernel streams (rng != NULL, no mask tensors)
+int nsd_lstm_head_train_soft(const nsd_dims *d, const float *params, const float *x, const float *drop_lstm, const float *rrelu_slope,
+                             const float *drop_head, const nsd_rng *rng, const float *targets, float scale, uint32_t flags,
+                             float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    if (!rng) return lstm_head_train_impl(d, params, x, drop_lstm, rrelu_slope, drop_head, nullptr, soft(targets), scale, flags, workspace, workspace_bytes, logits, stream);
+    if (drop_lstm || rrelu_slope || drop_head) { nsd_set_error("lstm_head_train_soft: explicit mask tensors or rng, not both"); return NSD_E_INVALID; }
+    RngArgs r;
+    if (make_rng(rng, &r) != NSD_OK) return NSD_E_INVALID;
+    return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, &r, soft(targets), scale, flags, workspace, workspace_bytes, logits, stream);
 }
 
 // where nsd_lstm_bwd forms dx: H = 48 on the fast path (the one-trial kernel leaves da0 in place of layer 0's saved gates: ONE backward per
@@ -658,6 +690,41 @@ int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_st
     return nsd_augment_launch(a, (hipStream_t)stream);
 }
 
+// ---- soft targets and mixed windows (nsd_mixup, include/nsd.h; nsd_mixup.hip) ------------------------------------------------------
+int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels, const float *class_weight,
+              const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev, float *y, float *targets, void *stream) {
+    static const char *who = "mixup";
+    if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (!labels || !targets || !mix || !rng) { nsd_set_error("%s: null pointer (labels, targets, mix, rng)", who); return NSD_E_INVALID; }
+    if (d->B < 0 || d->T < 1 || d->C < 1 || (int64_t)d->T * d->C > 0x7fffffff) { nsd_set_error("%s: shape B=%d T=%d C=%d (B >= 0, T >= 1, C >= 1)", who, d->B, d->T, d->C); return NSD_E_INVALID; }
+    if (d->K < 1 || d->K > 64) { nsd_set_error("%s: K = %d classes outside [1, 64]", who, d->K); return NSD_E_INVALID; }
+    if (!(mix->smoothing >= 0.f && mix->smoothing < 1.f)) { nsd_set_error("%s: smoothing %g outside [0, 1)", who, mix->smoothing); return NSD_E_INVALID; }
+    if (!(mix->mix >= 0.f && mix->mix <= 1.f)) { nsd_set_error("%s: mix %g outside [0, 1]", who, mix->mix); return NSD_E_INVALID; }
+    if ((x == nullptr) != (y == nullptr)) { nsd_set_error("%s: x and y are given together or not at all", who); return NSD_E_INVALID; }
+    if (mix->mix > 0.f && !x) { nsd_set_error("%s: mix = %g needs the windows x and y", who, mix->mix); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
+        nsd_set_error("%s: x_model_stride %lld: 0 (one window set for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
+        return NSD_E_INVALID;
+    }
+    if ((int64_t)M * d->B > 0x7fffffff) { nsd_set_error("%s: M * B = %lld trials in one launch", who, (long long)M * d->B); return NSD_E_INVALID; }
+    if (x) {
+        const float *x_end = x + (M - 1) * x_model_stride + n;
+        const float *y_end = y + (int64_t)M * n;
+        if (n > 0 && x < y_end && y < x_end) { nsd_set_error("%s: y overlaps x (a trial reads its partner's window: no in-place form)", who); return NSD_E_INVALID; }
+    }
+    if (d->B == 0) return NSD_OK;
+    MixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.y = y; a.x_stride = x_model_stride; a.step_dev = (const long long *)step_dev;
+    a.labels = labels; a.w = class_weight; a.targets = targets;
+    a.n_el = (long)d->T * d->C; a.B = d->B; a.K = d->K; a.M = M;
+    a.mix = mix->mix; a.eps = mix->smoothing;
+    for (int m = 0; m < M; ++m) { a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream; }
+    return nsd_mixup_launch(a, (hipStream_t)stream);
+}
+
 // ---- model-batched H = 48 path (nsd_multi_*, include/nsd.h; nsd_multi.h) ----------------------------------------------------------
 // M = 1 runs the single-model entry points themselves.  M > 1: the kernels' model-batched twins on a workspace of M*B trials.
 static bool multi_shape(const nsd_dims *d, int M) {
@@ -715,23 +782,33 @@ static ModelSplit model_split(const nsd_dims *d, int64_t x_model_stride) {
     return s;
 }
 
-int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
-                        const int32_t *labels, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
-    static const char *who = "multi_train_fwd";
+static int multi_train_fwd_impl(const char *who, const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride,
+                                const nsd_rng *rng, const Target &tg, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits,
+                                void *stream) {
     if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
-    if (!params || !x || !labels || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (!params || !x || !tg.given() || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     ModelSplit s = model_split(d, x_model_stride);
     RngArgs r;
     if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
     Ctx c;
     if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream)) return leave(rc);
     const float scale = 1.0f / (float)d->B;                     // mean CE per model
-    if (M == 1) return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, rng ? &r : nullptr, labels, scale, flags, workspace,
+    if (M == 1) return lstm_head_train_impl(d, params, x, nullptr, nullptr, nullptr, rng ? &r : nullptr, tg, scale, flags, workspace,
                                             workspace_bytes, logits, stream);
     Lstm2FwdArgs a = build_lstm_fwd(d, params, x, nullptr, flags, &c, nullptr);
-    attach_head_train(&a, build_head(d, params, &c), labels, scale, logits);
+    attach_head_train(&a, build_head(d, params, &c), tg, scale, logits);
     a.rng = r;
     return nsd_lstm2_multi_fwd_launch(a, s, M, c.st);
+}
+
+int nsd_multi_train_fwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                        const int32_t *labels, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    return multi_train_fwd_impl("multi_train_fwd", d, M, params, x, x_model_stride, rng, hard(labels), flags, workspace, workspace_bytes, logits, stream);
+}
+
+int nsd_multi_train_fwd_soft(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,
+                             const float *targets, uint32_t flags, float *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    return multi_train_fwd_impl("multi_train_fwd_soft", d, M, params, x, x_model_stride, rng, soft(targets), flags, workspace, workspace_bytes, logits, stream);
 }
 
 int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const nsd_rng *rng,

@@ -2,6 +2,7 @@
 #pragma once
 #include "nsd_common.h"
 
+constexpr int HEAD_TRAIN_SOFT = 2;
 struct Lstm2FwdArgs {
     const float *x;
     const float *w_ih0, *w_hh0, *b_ih0, *b_hh0, *w_ih1, *w_hh1, *b_ih1, *b_hh1;
@@ -19,12 +20,14 @@ struct Lstm2FwdArgs {
     // fused TRAIN head (lstm2_fwd48 only; head_train != 0): attention pooling rides along the recurrence (wave 10), then
     // LayerNorm, dense head, mean-CE and the head's backward run in the kernel's tail -- what nsd_head_train does in a
     // second launch.  Outputs and per-trial gradient slabs are those of HeadArgs.
+    // head_train == HEAD_TRAIN_SOFT: the loss is formed from fp32 target rows [B,K] instead of labels (the `_soft` entry points of nsd.h);
+    // the two pointers share their place in the block, so the hard-label kernels' argument block is what it was
     int head_train;
     // lstm2_fwd48x4 only, set by the launcher when the backward pass of this batch runs lstm2_bwd48x4_kernel: the per-step part of the
     // attention's backward (dL/dscore_t, d attn.weight, d attn.bias) is left to that kernel, which reads the top rows anyway; the
     // forward writes alpha_t and marks the {alpha, dscore} records as open ({alpha_t, 0, 1, 0}: see Lstm2BwdArgs::dsc_pack)
     int defer_att;
-    const int32_t *labels;
+    union { const int32_t *labels; const float *targets; };   // head_train == 1: labels [B]; == HEAD_TRAIN_SOFT: targets [B,K]
     const float *rrelu_slope, *drop_head;
     float scale;
     float *logits, *loss, *alpha, *pooled, *fc0_pre, *dscore, *dpooled, *adpack, *hslabs;
@@ -66,6 +69,7 @@ struct HeadArgs {
     float *alpha, *pooled, *fc0_pre;
     const float *logits_in, *dlogits;
     const int32_t *labels;
+    const float *targets;                    // null, or [B,K] soft targets in place of the labels
     float scale;
     float *loss, *dscore, *dpooled;
     float *adpack;                           // [B,T,4] {alpha, dscore, 0, 0} (backward only, may be null)
@@ -147,6 +151,21 @@ struct AugArgs {
     uint32_t base[NSD_MAX_MODELS];
 };
 int nsd_augment_launch(const AugArgs &a, hipStream_t st);
+// soft targets and mixed windows (nsd_mixup of nsd.h; nsd_mixup.hip)
+struct MixArgs {
+    const float *x; float *y;                // null together: the launch only builds targets
+    long long x_stride;                      // floats between two models' windows (0: shared)
+    const long long *step_dev;               // null, or the device step counter the stream id is formed from
+    const int32_t *labels;                   // [M*B]
+    const float *w;                          // null, or the class weights [K]
+    float *targets;                          // [M*B][K]
+    long n_el;                               // T * C
+    int B, K, M;
+    float mix, eps;
+    uint64_t seed[NSD_MAX_MODELS];
+    uint32_t base[NSD_MAX_MODELS];
+};
+int nsd_mixup_launch(const MixArgs &a, hipStream_t st);
 // gradient slabs of M models in one workspace: per model n LSTM slabs (one per backward workgroup) and n_h head slabs (one per trial)
 struct SlabSet {
     const float *slabs; long stride; int n; long p_lstm;

@@ -102,6 +102,41 @@ __device__ __forceinline__ float wave_max(float v) {
     return rows_combine_max(v);
 }
 
+// Soft-target cross-entropy of one trial by one wave (the `_soft` entry points of nsd.h): lane k < K holds its class's target q (>= 0),
+// logit lg and e = exp(lg - m), d = sum_k e_k; lanes >= K hold q = 0, e = 0.  Returns s p_k - q_k (s = sum_j q_j, p = e / d) formed as
+// (sum_{j != k} (q_j e_k - q_k e_j)) / d: with a one-hot q that is the hard path's -(sum of the others) / d for the label and e_k / d for
+// the rest -- no O(1) - O(1) difference anywhere.  *loss = sum_k q_k ((m - lg_k) + log d) over the lanes < K (the others hold -inf logits).
+__device__ __forceinline__ float soft_ce_wave(const float q, const float lg, const float m, const float e, const float d, const float logd,
+                                              const int lane, const int K, float *loss) {
+    float num = 0.f;
+    for (int j = 0; j < K; ++j) {
+        const float qj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q), j));
+        const float ej = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), j));
+        const float term = qj * e - q * ej;
+        num += j == lane ? 0.f : term;
+    }
+    *loss = wave_sum(lane < K ? q * ((m - lg) + logd) : 0.f);
+    return num / d;
+}
+// the same for one thread that holds all K classes (the LDS-resident heads of nsd_head.hip): dl[k] = scale (s p_k - q_k), returns the loss
+__device__ __forceinline__ float soft_ce_thread(const float *q, const float *lg, const int K, const float scale, float *dl) {
+    float m = lg[0];
+    for (int k = 1; k < K; ++k) m = fmaxf(m, lg[k]);
+    float d = 0.f;
+    for (int k = 0; k < K; ++k) d += expf(lg[k] - m);
+    const float logd = logf(d);
+    float loss = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float ek = expf(lg[k] - m), qk = q[k];
+        float num = 0.f;
+        for (int j = 0; j < K; ++j)
+            if (j != k) num += q[j] * ek - qk * expf(lg[j] - m);
+        dl[k] = num / d * scale;
+        loss += qk * ((m - lg[k]) + logd);
+    }
+    return loss;
+}
+
 // A called function sees the kernel's argument block through a pointer: what it loads from there sits in VGPRs, and hipcc cannot know that
 // every lane holds the same value -- buffer descriptors built from such pointers are used inside WATERFALL loops (one pass per distinct
 // value, a vmcnt(0) in front), loop bounds become vector compares.  uniform_copy() hands every dword through v_readfirstlane: scalar again.

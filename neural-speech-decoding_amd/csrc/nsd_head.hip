@@ -201,6 +201,9 @@ __global__ __launch_bounds__(HEAD_NT) void head_bwd_kernel(HeadArgs a) {
         if (tid == 0) {
             if (a.dlogits) {
                 for (int k = 0; k < K; ++k) vdl[k] = a.dlogits[(size_t)b * K + k];
+            } else if (a.targets) {
+                const float ls = soft_ce_thread(a.targets + (size_t)b * K, a.logits_in + (size_t)b * K, K, a.scale, vdl);
+                if (a.loss) a.loss[b] = ls;
             } else {
                 const float *lg = a.logits_in + (size_t)b * K;
                 const int y = a.labels[b];
@@ -342,7 +345,7 @@ __global__ __launch_bounds__(HEAD_NT) void head_train_kernel(HeadArgs a) {
             if (a.rrelu_slope) sl_f = a.rrelu_slope[(size_t)b * F + tid];
             if (a.drop_head) mk_f = a.drop_head[(size_t)b * F + tid];
         }
-        const int label = a.labels[b];
+        const int label = a.targets ? 0 : a.labels[b];
         __syncthreads();
         // ---- forward ----
         float lmax = -INFINITY;
@@ -388,7 +391,9 @@ __global__ __launch_bounds__(HEAD_NT) void head_train_kernel(HeadArgs a) {
         }
         __syncthreads();
         // ---- mean cross-entropy: dlogits = (softmax - onehot) * scale, without cancellation for the label ----
-        if (tid == 0) {
+        if (tid == 0 && a.targets) {
+            a.loss[b] = soft_ce_thread(a.targets + (size_t)b * K, vlg, K, a.scale, vdl);
+        } else if (tid == 0) {
             float m2 = vlg[0];
             for (int k = 1; k < K; ++k) m2 = fmaxf(m2, vlg[k]);
             float d = 0.f, rest = 0.f;

@@ -115,12 +115,21 @@
         if constexpr (!TRAIN) return;
 
         // ---- mean cross-entropy ------------------------------------------------------------------------------------------
-        const int y = a.labels[b];
-        const float ly = lane_bcast(logit, y);
-        if (lane == 0) a.loss[b] = (lmax - ly) + __logf(den);
-        // p_y - 1 without cancellation: -(sum of the other classes' probabilities)
-        const float others = wave_sum((lane < K && lane != y) ? ex : 0.f) / den;
-        dlog = lane < K ? (lane == y ? -others : prob) * a.scale : 0.f;
+        if (a.targets) {
+            // soft targets (wave-uniform): loss = sum_k q_k ((lmax - logit_k) + log den), dlogits = scale (s p - q) without cancellation
+            float ls;
+            const float q = lane < K ? a.targets[(long)b * K + lane] : 0.f;
+            const float dq = soft_ce_wave(q, logit, lmax, ex, den, __logf(den), lane, K, &ls);
+            if (lane == 0) a.loss[b] = ls;
+            dlog = lane < K ? dq * a.scale : 0.f;
+        } else {
+            const int y = a.labels[b];
+            const float ly = lane_bcast(logit, y);
+            if (lane == 0) a.loss[b] = (lmax - ly) + __logf(den);
+            // p_y - 1 without cancellation: -(sum of the other classes' probabilities)
+            const float others = wave_sum((lane < K && lane != y) ? ex : 0.f) / den;
+            dlog = lane < K ? (lane == y ? -others : prob) * a.scale : 0.f;
+        }
     }
 
     // ---- dense backward ---------------------------------------------------------------------------------------------------

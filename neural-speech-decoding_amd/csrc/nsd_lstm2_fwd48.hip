@@ -722,7 +722,10 @@ __device__ __forceinline__ void tail_all(const Lstm2FwdArgs &a, FSmem<NB> &sm, c
     }
 }
 
-template <int NB, class A>
+// SOFT: the loss is formed from target rows (a.targets, head_train == HEAD_TRAIN_SOFT) instead of labels.  A template parameter of the
+// kernel and not a branch here: with the (wave-uniform) branch in this role, hipcc gave lstm2_fwd48_kernel<1> a 68-byte private segment
+// it does not have without it (profiles/r07_soft_targets.md); this way the hard-label kernels hold no trace of the other mode.
+template <int NB, bool SOFT, class A>
 __device__ __forceinline__ void tpool_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     const int T = a.T, K = a.K, F = a.F;
     PoolRun pr[NB];
@@ -751,7 +754,9 @@ __device__ __forceinline__ void tpool_role(const A &a, FSmem<NB> &sm, const int 
                 sl_f = 0.125f + ((float)(1.0 / 3.0) - 0.125f) * u;
                 mk_f = nsd_rand_u32(a.rng.seed, a.rng.base + 2u, idx) >= a.rng.thr_head ? a.rng.keep_head : 0.f;
             }
-            sl_fv[n] = sl_f; mk_fv[n] = mk_f; labelv[n] = a.labels[b];
+            sl_fv[n] = sl_f; mk_fv[n] = mk_f;
+            // soft targets: the lane's class target travels in the label's register (its bits), so the wait carries nothing more
+            labelv[n] = SOFT ? __float_as_int(lane < K ? a.targets[(size_t)b * K + lane] : 0.f) : a.labels[b];
             pool_reset(pr[n]);
         }
         step_barrier<false>(prof);
@@ -797,10 +802,23 @@ __device__ __forceinline__ void tpool_role(const A &a, FSmem<NB> &sm, const int 
             const float m2 = wave_max(lg);
             const float e = lane < K ? expf(lg - m2) : 0.f;
             const float d = wave_sum(e);
-            const float rest = wave_sum(lane == label ? 0.f : e);
-            const float dl = (lane == label ? -rest / d : e / d) * a.scale;
-            if (lane < K) sm.vdl[lane] = dl;
-            if (lane == label && vb) a.loss[b] = -((lg - m2) - logf(d));
+            // (the hard path's statements in the order they always had -- with the LDS store of dl behind the loss store the one-trial
+            // kernel has the 68 bytes again)
+            const float dl = [&]() {
+                if constexpr (SOFT) {                             // soft targets: `label` holds the bits of the lane's q
+                    float ls;
+                    const float v = soft_ce_wave(__int_as_float(label), lg, m2, e, d, logf(d), lane, K, &ls) * a.scale;
+                    if (lane == 0 && vb) a.loss[b] = ls;
+                    return v;
+                } else {
+                    const float rest = wave_sum(lane == label ? 0.f : e);
+                    const float v = (lane == label ? -rest / d : e / d) * a.scale;
+                    if (lane < K) sm.vdl[lane] = v;
+                    if (lane == label && vb) a.loss[b] = -((lg - m2) - logf(d));
+                    return v;
+                }
+            }();
+            if constexpr (SOFT) { if (lane < K) sm.vdl[lane] = dl; }
             // ---- backward of the dense head ----
             float *slab = a.hslabs + (size_t)(vb ? b : 0) * a.Ph;
             float dz = 0.f;
@@ -893,7 +911,7 @@ __device__ __forceinline__ void spare_role(const A &a, FSmem<NB> &sm, const int 
 }
 
 #if !NSD_MULTI_TU
-template <int NB>
+template <int NB, bool SOFT = false>
 __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
     __shared__ __align__(16) FSmem<NB> sm;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -913,7 +931,7 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
     else if (NSD_FWD48_ONLY_ROLE == 2) l1_role<NB>(a, sm, g * 64 + lane, n_steps);
     else if (NSD_FWD48_ONLY_ROLE == 3) l0_role<NB>(a, sm, g * 64 + lane, n_steps);
     else if (NSD_FWD48_ONLY_ROLE == 4) saver_role<NB>(a, sm, lane, n_steps);
-    else if (NSD_FWD48_ONLY_ROLE == 5) tpool_role<NB>(a, sm, lane, n_steps);
+    else if (NSD_FWD48_ONLY_ROLE == 5) tpool_role<NB, SOFT>(a, sm, lane, n_steps);
     else spare_role<NB>(a, sm, lane, n_steps);
     return;
 #endif
@@ -928,14 +946,14 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
             saver_role<NB>(a, sm, lane, n_steps);               // (inference runs one trial per workgroup: nothing but its latency matters there)
         }
     }
-    else if (g == 1 && a.head_train) tpool_role<NB>(a, sm, lane, n_steps);
+    else if (g == 1 && a.head_train) tpool_role<NB, SOFT>(a, sm, lane, n_steps);
     else spare_role<NB>(a, sm, lane, n_steps);
 }
 
 #else
 // M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_fwd48.hip, so that the single-model kernels' module is what it was):
 // workgroup blockIdx.x runs model blockIdx.x / s.G; the roles and their placement are those of lstm2_fwd48_kernel
-template <int NB>
+template <int NB, bool SOFT = false>
 __global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in, ModelSplit s) {
     __shared__ __align__(16) FSmem<NB> sm;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -956,7 +974,7 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in
             saver_role<NB>(a, sm, lane, n_steps);
         }
     }
-    else if (g == 1 && a_in.head_train) { NSD_VIEW; tpool_role<NB>(a, sm, lane, n_steps); }
+    else if (g == 1 && a_in.head_train) { NSD_VIEW; tpool_role<NB, SOFT>(a, sm, lane, n_steps); }
     else { NSD_VIEW; spare_role<NB>(a, sm, lane, n_steps); }
 #undef NSD_VIEW
 }
@@ -980,8 +998,11 @@ static int fwd48_domain(const Lstm2FwdArgs &a, int nb, const char *who) {
 #if !NSD_MULTI_TU
 int nsd_lstm2_fwd48_launch(const Lstm2FwdArgs &a, int nb, int grid, hipStream_t st) {
     if (const int rc = fwd48_domain(a, nb, "lstm2_fwd48")) return rc;
-    if (nb == 2) hipLaunchKernelGGL((lstm2_fwd48_kernel<2>), dim3(grid), dim3(NT), 0, st, a);
-    else         hipLaunchKernelGGL((lstm2_fwd48_kernel<1>), dim3(grid), dim3(NT), 0, st, a);
+    const bool soft = a.head_train == HEAD_TRAIN_SOFT;
+    if (!soft && nb == 2) hipLaunchKernelGGL((lstm2_fwd48_kernel<2>), dim3(grid), dim3(NT), 0, st, a);
+    else if (!soft)       hipLaunchKernelGGL((lstm2_fwd48_kernel<1>), dim3(grid), dim3(NT), 0, st, a);
+    else if (nb == 2)     hipLaunchKernelGGL((lstm2_fwd48_kernel<2, true>), dim3(grid), dim3(NT), 0, st, a);
+    else                  hipLaunchKernelGGL((lstm2_fwd48_kernel<1, true>), dim3(grid), dim3(NT), 0, st, a);
     NSD_CHECK_LAUNCH("lstm2_fwd48");
     return NSD_OK;
 }
@@ -991,8 +1012,11 @@ bool nsd_lstm2_fwd48_head_train_fits(int T, int F, int K) { return T <= TT_TMAX 
 #else
 int nsd_lstm2_fwd48_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st) {
     if (const int rc = fwd48_domain(a, nb, "lstm2_fwd48 (models)")) return rc;
-    if (nb == 2) hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<2>), dim3(M * s.G), dim3(NT), 0, st, a, s);
-    else         hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<1>), dim3(M * s.G), dim3(NT), 0, st, a, s);
+    const bool soft = a.head_train == HEAD_TRAIN_SOFT;
+    if (!soft && nb == 2) hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<2>), dim3(M * s.G), dim3(NT), 0, st, a, s);
+    else if (!soft)       hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<1>), dim3(M * s.G), dim3(NT), 0, st, a, s);
+    else if (nb == 2)     hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<2, true>), dim3(M * s.G), dim3(NT), 0, st, a, s);
+    else                  hipLaunchKernelGGL((lstm2_fwd48_multi_kernel<1, true>), dim3(M * s.G), dim3(NT), 0, st, a, s);
     NSD_CHECK_LAUNCH("lstm2_fwd48_multi");
     return NSD_OK;
 }

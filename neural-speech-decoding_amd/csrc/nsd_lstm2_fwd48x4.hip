@@ -534,7 +534,8 @@ __device__ __forceinline__ HeadPre dense_head_pre(const Lstm2FwdArgs &a, const i
         h.sl_f = 0.125f + ((float)(1.0 / 3.0) - 0.125f) * u;
         h.mk_f = nsd_rand_u32(a.rng.seed, a.rng.base + 2u, idx) >= a.rng.thr_head ? a.rng.keep_head : 0.f;
     }
-    h.label = a.labels[bs];
+    // soft targets: the lane's class target travels in the label's place (its bits)
+    h.label = a.head_train == HEAD_TRAIN_SOFT ? __float_as_int(lane < K ? a.targets[(size_t)bs * K + lane] : 0.f) : a.labels[bs];
     return h;
 }
 __device__ __forceinline__ void dense_head(const Lstm2FwdArgs &a, XSmem &sm, const int lane, const int b, const int n, const HeadPre &hp) {
@@ -573,10 +574,18 @@ __device__ __forceinline__ void dense_head(const Lstm2FwdArgs &a, XSmem &sm, con
     const float m2 = wave_max(lg);
     const float e = lane < K ? expf(lg - m2) : 0.f;
     const float d = wave_sum(e);
-    const float rest = wave_sum(lane == label ? 0.f : e);
-    const float dl = (lane == label ? -rest / d : e / d) * a.scale;
+    float dl;
+    if (a.head_train == HEAD_TRAIN_SOFT) {                          // soft targets (wave-uniform): `label` holds the bits of the lane's q
+        float ls;
+        const float q = __int_as_float(label);
+        dl = soft_ce_wave(q, lg, m2, e, d, logf(d), lane, K, &ls) * a.scale;
+        if (lane == 0 && vb) a.loss[b] = ls;
+    } else {
+        const float rest = wave_sum(lane == label ? 0.f : e);
+        dl = (lane == label ? -rest / d : e / d) * a.scale;
+        if (lane == label && vb) a.loss[b] = -((lg - m2) - logf(d));
+    }
     if (lane < K) sm.vdl[n][lane] = dl;
-    if (lane == label && vb) a.loss[b] = -((lg - m2) - logf(d));
     float *slab = a.hslabs + (size_t)bs * a.Ph;
     float dz = 0.f;
     if (lane < F) {

@@ -52,7 +52,7 @@ __device__ __forceinline__ ModelView<Lstm2FwdArgs> model_view(const Lstm2FwdArgs
     v.hseq0 = mv(a.hseq0, bth); v.hseq1 = mv(a.hseq1, bth); v.cseq0 = mv(a.cseq0, bth); v.cseq1 = mv(a.cseq1, bth);
     v.gact0 = mv(a.gact0, 4 * bth); v.gact1 = mv(a.gact1, 4 * bth); v.inseq = mv(a.inseq, bth); v.top = mv(a.top, bth);
     v.logits_out = mv(a.logits_out, b * a.K); v.probs_out = mv(a.probs_out, b * a.K);
-    v.labels = mv(a.labels, b);
+    if (a.head_train == HEAD_TRAIN_SOFT) v.targets = mv(a.targets, b * a.K); else v.labels = mv(a.labels, b);
     v.rrelu_slope = mv(a.rrelu_slope, b * a.F); v.drop_head = mv(a.drop_head, b * a.F);
     v.logits = mv(a.logits, b * a.K); v.loss = mv(a.loss, b); v.alpha = mv(a.alpha, bt); v.pooled = mv(a.pooled, b * 48);
     v.fc0_pre = mv(a.fc0_pre, b * a.F); v.dscore = mv(a.dscore, bt); v.dpooled = mv(a.dpooled, b * 48);

@@ -182,6 +182,7 @@ struct HeadTmArgs {
     float *logits, *probs;                   // [B][K]
     // training
     const int32_t *labels;
+    const float *targets;                    // null, or [B][K] soft targets in place of the labels (nsd_seq_train_fwd_soft)
     float scale;
     RngArgs rng;                             // rng.on: RReLU slopes (stream base+1) and head dropout (base+2) drawn here
     const float *rrelu_slope, *drop_head;    // explicit [B][F] tensors instead (tests); null with rng.on

@@ -561,16 +561,27 @@ int nsd_seq_infer(const nsd_dims *d, const float *params, const float *x, uint32
     return nsd_head_tm_launch(h, HEAD_EVAL, nullptr, c.st);
 }
 
-int nsd_seq_train_fwd(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const int32_t *labels, float scale,
-                      uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+// nsd_seq_train_fwd (labels) and nsd_seq_train_fwd_soft (targets [B][K]): one of the two is given
+static int train_fwd(const char *who, const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const int32_t *labels,
+                     const float *targets, float scale, uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream) {
     Ctx c;
-    if (const int rc = enter(&c, "seq_train_fwd", d, flags, params, workspace, workspace_bytes, x && logits && labels, rng, stream)) return leave(rc);
+    if (const int rc = enter(&c, who, d, flags, params, workspace, workspace_bytes, x && logits && (labels || targets), rng, stream)) return leave(rc);
     if (const int rc = forward(c, x, true)) return rc;
     HeadTmArgs h = head_args(c, HEAD_TRAIN, logits, nullptr);
-    h.labels = labels; h.scale = scale; h.loss = at<float>(c.ws, c.w.loss);
+    h.labels = labels; h.targets = targets; h.scale = scale; h.loss = at<float>(c.ws, c.w.loss);
     if (const int rc = head_train_outputs(c, h)) return rc;
     ProfScope ps(PK_HEAD, c.st);
     return nsd_head_tm_launch(h, HEAD_TRAIN, nullptr, c.st);
+}
+
+int nsd_seq_train_fwd(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const int32_t *labels, float scale,
+                      uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    return train_fwd("seq_train_fwd", d, params, x, rng, labels, nullptr, scale, flags, workspace, workspace_bytes, logits, stream);
+}
+
+int nsd_seq_train_fwd_soft(const nsd_dims *d, const float *params, const float *x, const nsd_rng *rng, const float *targets, float scale,
+                           uint32_t flags, void *workspace, int64_t workspace_bytes, float *logits, void *stream) {
+    return train_fwd("seq_train_fwd_soft", d, params, x, rng, nullptr, targets, scale, flags, workspace, workspace_bytes, logits, stream);
 }
 
 int nsd_seq_train_bwd(const nsd_dims *d, const float *params, const nsd_rng *rng, uint32_t flags, void *workspace, int64_t workspace_bytes,

@@ -40,11 +40,12 @@ class ModelBatchTrainer:
     The models' parameters are packed into one [M, P] buffer and each model's parameters are re-pointed as views into its row, so
     every model stays an ordinary module (forward, state_dict, save_reference_checkpoint work as before).  step(x, y) takes
     x [M,B,T,C] (per-model windows) or a shared [B,T,C], and y [M,B] or a shared [B].  augment: ops.Augment, applied per model as
-    Trainer does."""
+    Trainer does.  loss: ops.Loss (label smoothing, class weights, mixup), applied per model as Trainer(model_m, seed=seeds[m], loss=loss)
+    does: nsd_augment (if any) -> nsd_mixup -> the step with targets, each one launch for all models; the scale stays 1 / B per model."""
 
     def __init__(self, models: Sequence[EEG_LSTM], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
-                 augment: Optional[ops.Augment] = None):
+                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -76,6 +77,13 @@ class ModelBatchTrainer:
         # as Trainer: model m's trials are augmented with the draws of Trainer(model_m, seed=seeds[m], augment=augment), all models in
         # one launch; None (or every operation off) is the unaugmented step
         self.augment = augment if augment is not None and augment.enabled and stochastic else None
+        if loss is not None and loss.mixup and not stochastic:       # as Trainer: deterministic steps mix nothing
+            loss = ops.Loss(label_smoothing=loss.label_smoothing, class_weights=loss.class_weights)
+        if loss is not None and loss.enabled:
+            loss.check_classes(self.spec.K)
+            self.loss, self._class_w = loss, loss.weights_tensor(dev)
+        else:
+            self.loss, self._class_w = None, None
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
         self.grads = torch.zeros_like(self.params)
@@ -122,13 +130,19 @@ class ModelBatchTrainer:
         rngs = ([dict(seed=s, base_stream=sid, p_lstm=mdl.dropout_p, p_head=mdl.head_dropout_p) for s in self.seeds]
                 if self.stochastic else None)
         buf = self._buffers(B, T)
+        tg = None
+        if self.loss is not None:                        # one launch for all models, on the windows each would otherwise see
+            lo = self.loss
+            xm, tg = ops.mixup(x if lo.mixup > 0 else None, y, self.spec.K, [dict(seed=s, base_stream=sid) for s in self.seeds], M=M,
+                               label_smoothing=lo.label_smoothing, mix=lo.mixup, class_weights=self._class_w)
+            x = xm if lo.mixup > 0 else x
         ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
                              step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                             weight_decay=self.weight_decay)
+                             weight_decay=self.weight_decay, targets=tg)
         self._last = (B, T)
 
     def last_losses(self) -> List[float]:
-        """Mean CE of each model's last step (synchronises)."""
+        """Mean loss (CE, or the soft-target loss with loss=) of each model's last step (synchronises)."""
         if self._last is None:
             return [float("nan")] * self.M
         B, T = self._last

@@ -329,6 +329,104 @@ def augment(x: torch.Tensor, aug: Augment, rngs, *, M: int = 1, zscore: bool = F
     return out
 
 
+@dataclass(frozen=True)
+class Loss:
+    """The loss of a training step beyond mean cross-entropy on hard labels (nsd_mixup + the `_soft` entry points of include/nsd.h; an
+    extension, the reference has none).  Each part is OFF at its default.  label_smoothing eps in [0, 1): the target of class k is
+    (1 - eps) * onehot_k + eps / K; class_weights: K non-negative finite weights w_k multiplied into the target rows (what
+    torch.nn.functional.cross_entropy(weight=w) puts in the numerator); mixup m in [0, 1]: every trial is mixed with a partner of its
+    batch, window and target alike, lambda = 1 - m * U(0, 1) (m = 1: the uniform, Beta(1, 1), mixup); like the augmentation it is part
+    of a trainer's stochastic steps only (stochastic=False mixes nothing).
+
+    The step's scale stays 1 / global_batch: the loss is sum_b loss_b / B.  torch's weighted `mean` reduction divides by the sum of the
+    trials' weights instead; with class weights the two differ by that (batch-dependent) factor."""
+    label_smoothing: float = 0.0
+    class_weights: Optional[Tuple[float, ...]] = None
+    mixup: float = 0.0
+
+    def __post_init__(self):
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"Loss: label_smoothing {self.label_smoothing!r} outside [0, 1)")
+        if not 0.0 <= self.mixup <= 1.0:
+            raise ValueError(f"Loss: mixup {self.mixup!r} outside [0, 1]")
+        if self.class_weights is not None:
+            w = tuple(float(v) for v in self.class_weights)
+            if len(w) < 1 or not all(0.0 <= v < float("inf") for v in w):
+                raise ValueError(f"Loss: class_weights {self.class_weights!r} must be non-negative and finite, one per class")
+            object.__setattr__(self, "class_weights", w)
+
+    @property
+    def enabled(self) -> bool:
+        return bool(self.label_smoothing or self.mixup or self.class_weights is not None)
+
+    def check_classes(self, K: int) -> None:
+        if self.class_weights is not None and len(self.class_weights) != K:
+            raise ValueError(f"Loss: {len(self.class_weights)} class_weights for a model of {K} classes")
+
+    def weights_tensor(self, device) -> Optional[torch.Tensor]:
+        return None if self.class_weights is None else torch.tensor(self.class_weights, dtype=torch.float32, device=device)
+
+
+def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, label_smoothing: float = 0.0, mix: float = 0.0,
+          class_weights: Optional[torch.Tensor] = None, M: int = 1, step_dev: Optional[torch.Tensor] = None,
+          out: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None
+          ) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """nsd_mixup: the target rows of a step from its int32 labels (label smoothing, class weights) and, with mix > 0, the mixed windows,
+    one launch for all models -> (y, targets [M*B, K]).  x [B,T,C] (one model, or shared by M models -> y [M,B,T,C]) or [M,B,T,C];
+    x = None (mix = 0 only): the launch builds targets alone and y is None.  labels [M*B] int32 (model m's trial b at m * B + b).
+    rngs / step_dev as ops.augment (the stream is base_stream + 3, on index slots nsd_augment does not use).  class_weights: device
+    fp32 [K].  mix = 0 with x given: y is a bitwise copy of x."""
+    if isinstance(rngs, dict):
+        rngs = [rngs]
+    if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
+        raise NsdError("mixup: labels must be a contiguous int32 tensor on the device")
+    dev = labels.device
+    if x is None:
+        M = int(M)
+        if labels.numel() % M:
+            raise NsdError(f"mixup: {labels.numel()} labels for {M} models")
+        B, T, Cc, stride, shape = labels.numel() // M, 1, 1, 0, None
+    elif x.dim() == 4:
+        Mx, B, T, Cc = (int(v) for v in x.shape)
+        if M not in (1, Mx):
+            raise NsdError(f"mixup: x has {Mx} model slices, M = {M}")
+        M, stride, shape = Mx, B * T * Cc, (Mx, B, T, Cc)
+    elif x.dim() == 3:
+        B, T, Cc = (int(v) for v in x.shape)
+        M, stride = int(M), 0
+        shape = (B, T, Cc) if M == 1 else (M, B, T, Cc)
+    else:
+        raise NsdError(f"mixup: x must be [B,T,C] or [M,B,T,C], got {tuple(x.shape)}")
+    if len(rngs) != M:
+        raise NsdError(f"mixup: {len(rngs)} rng entries for {M} models")
+    if labels.numel() != M * B:
+        raise NsdError(f"mixup: {labels.numel()} labels for {M} x {B} trials")
+    r = (_lib.Rng * M)()
+    for i, g in enumerate(rngs):
+        r[i] = _lib.Rng(int(g["seed"]) & 0xFFFFFFFFFFFFFFFF, int(g["base_stream"]) & 0xFFFFFFFF, 0.0, 0.0)
+    mx = _lib.Mix(float(mix), float(label_smoothing))
+    if targets is None:
+        targets = torch.empty((M * B, K), dtype=torch.float32, device=dev)
+    if targets.numel() != M * B * K:
+        raise NsdError(f"mixup: targets has {targets.numel()} elements for {M * B} x {K}")
+    if x is not None:
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        if out.numel() != M * B * T * Cc:
+            raise NsdError(f"mixup: out has {out.numel()} elements for {M} x {B} x {T} x {Cc}")
+    else:
+        out = None
+    sp = None
+    if step_dev is not None:
+        if step_dev.dtype != torch.int64 or not step_dev.is_cuda:
+            raise NsdError("mixup: step_dev must be an int64 tensor on the device")
+        sp = step_dev.data_ptr()
+    d = Dims(B, T, Cc, 1, 1, int(K), 1)
+    _call("nsd_mixup", dev, C.byref(d), M, _dev_f32(x, "x"), stride, labels.data_ptr(), _dev_f32(class_weights, "class_weights", (K,)),
+          C.byref(mx), C.cast(r, C.c_void_p), sp, _dev_f32(out, "out"), _dev_f32(targets, "targets"), STREAM)
+    return out, targets
+
+
 def infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, *, residual: bool = False,
           want_probs: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Eval-mode forward: logits [B,K] (+ softmax probabilities)."""
@@ -406,7 +504,8 @@ def train_backward(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: tor
 def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: torch.Tensor, labels: torch.Tensor,
                      logits: torch.Tensor, grads: torch.Tensor, *, scale: Optional[float] = None, drop_lstm=None,
                      rrelu_slope=None, drop_head=None, residual: bool = False, adam: Optional[dict] = None,
-                     fused_head: bool = True, rng: Optional[dict] = None, dx: Optional[torch.Tensor] = None) -> None:
+                     fused_head: bool = True, rng: Optional[dict] = None, dx: Optional[torch.Tensor] = None,
+                     targets: Optional[torch.Tensor] = None) -> None:
     """The launches of one training evaluation: lstm fwd + head (fwd, mean CE, bwd) in one launch where the shape allows
     (nsd_lstm_head_train; fused_head=False forces the two separate launches), lstm bwd, slab reduce -> `grads` (flat,
     overwritten).  `logits` [B,K] is an output buffer.
@@ -417,12 +516,16 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     adam=dict(m=, v=, step=, lr=, beta1=, beta2=, eps=, weight_decay=): single-rank training -- the optimizer update of
     `flat` rides in the reduction launch (nsd_grad_reduce_adam); `grads` is still written.
 
-    dx [B,T,C] (optional output): dL/dx from nsd_lstm_bwd where dx_path(spec, B, T); not with rng= (nsd_lstm_bwd_rng has no dx)."""
+    dx [B,T,C] (optional output): dL/dx from nsd_lstm_bwd where dx_path(spec, B, T); not with rng= (nsd_lstm_bwd_rng has no dx).
+
+    targets [B,K] fp32 (labels is then ignored and may be None): the loss is - sum_k targets[b,k] log softmax(logits_b)[k] through the
+    `_soft` entry points (nsd_lstm_head_train_soft / nsd_head_train_soft); the backward launches are the same."""
     B, T, _ = x.shape
     d = spec.dims(B, T)
     flags = _lib.NSD_FLAG_TRAIN | (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags
     pp = _dev_f32(flat, "params", (spec.param_count,))
-    labp = _labels_ptr(labels)
+    tgp = _dev_f32(targets, "targets", (B, spec.K))
+    labp = _labels_ptr(labels) if targets is None else None
     scale = (1.0 / max(B, 1)) if scale is None else float(scale)
     xp, wsp, wsn, st, dev = _dev_f32(x, "x", (B, T, spec.C)), _dev_f32(ws, "workspace"), _nbytes(ws), STREAM, x.device
     dl, sl, dh = _dev_f32(drop_lstm, "drop_lstm"), _dev_f32(rrelu_slope, "rrelu_slope"), _dev_f32(drop_head, "drop_head")
@@ -435,14 +538,22 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
         if dx is not None:
             raise NsdError("train_step_grads: dx= needs explicit mask tensors (nsd_lstm_bwd_rng forms no input gradient)")
         r = _rng_struct(rng)
-        _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labp, scale, flags, wsp, wsn, lp, st)
+        if targets is not None:
+            _call("nsd_lstm_head_train_soft", dev, C.byref(d), pp, xp, None, None, None, C.byref(r), tgp, scale, flags, wsp, wsn, lp, st)
+        else:
+            _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labp, scale, flags, wsp, wsn, lp, st)
         _call("nsd_lstm_bwd_rng", dev, C.byref(d), pp, xp, C.byref(r), flags, wsp, wsn, st)
     else:
-        if fused_head:
+        if fused_head and targets is not None:
+            _call("nsd_lstm_head_train_soft", dev, C.byref(d), pp, xp, dl, sl, dh, None, tgp, scale, flags, wsp, wsn, lp, st)
+        elif fused_head:
             _call("nsd_lstm_head_train", dev, C.byref(d), pp, xp, dl, sl, dh, labp, scale, flags, wsp, wsn, lp, st)
         else:
             _call("nsd_lstm_fwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, st)
-            _call("nsd_head_train", dev, C.byref(d), pp, sl, dh, labp, scale, wsp, wsn, lp, st)
+            if targets is not None:
+                _call("nsd_head_train_soft", dev, C.byref(d), pp, sl, dh, tgp, scale, wsp, wsn, lp, st)
+            else:
+                _call("nsd_head_train", dev, C.byref(d), pp, sl, dh, labp, scale, wsp, wsn, lp, st)
         _call("nsd_lstm_bwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, dxp, st)
     gp = _dev_f32(grads, "grads", (spec.param_count,))
     if adam is None:
@@ -594,13 +705,20 @@ def seq_infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: Optional
 
 
 def seq_train_fwd(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, labels: torch.Tensor, ws: torch.Tensor, *,
-                  rng: Optional[dict] = None, scale: Optional[float] = None, logits: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Forward + head + mean CE + head backward of one training evaluation; activations stay in `ws` for seq_train_bwd."""
+                  rng: Optional[dict] = None, scale: Optional[float] = None, logits: Optional[torch.Tensor] = None,
+                  targets: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Forward + head + mean CE + head backward of one training evaluation; activations stay in `ws` for seq_train_bwd.
+    targets [B,K] fp32 (labels is then ignored and may be None): the soft-target loss (nsd_seq_train_fwd_soft), same logits bit for bit."""
     B, T, _ = x.shape
     d = spec.dims(B, T)
-    labp = _labels_ptr(labels)
     logits = torch.empty((B, spec.K), dtype=torch.float32, device=x.device) if logits is None else logits
     scale = (1.0 / max(B, 1)) if scale is None else float(scale)
+    if targets is not None:
+        _call("nsd_seq_train_fwd_soft", x.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _dev_f32(x, "x", (B, T, spec.C)),
+              _seq_rng(rng), _dev_f32(targets, "targets", (B, spec.K)), scale, spec.seq_flags, ws.data_ptr(), _nbytes(ws),
+              _dev_f32(logits, "logits", (B, spec.K)), STREAM)
+        return logits
+    labp = _labels_ptr(labels)
     _call("nsd_seq_train_fwd", x.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _dev_f32(x, "x", (B, T, spec.C)),
           _seq_rng(rng), labp, scale, spec.seq_flags, ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits", (B, spec.K)), STREAM)
     return logits
@@ -714,23 +832,29 @@ def _multi_x(spec: ModelSpec, x: torch.Tensor, M: int) -> Tuple[torch.Tensor, in
 def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, labels: torch.Tensor, ws: torch.Tensor, grads: torch.Tensor,
                      *, rngs=None, logits: Optional[torch.Tensor] = None, fuse_adam: bool = True, m: Optional[torch.Tensor] = None,
                      v: Optional[torch.Tensor] = None, step: int = 1, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
-                     eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0) -> torch.Tensor:
+                     eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
+                     targets: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One training step of M models at once: params [M,P], x [M,B,T,C] or shared [B,T,C], labels [M*B] int32, grads [M,P].
     Forward + head + mean CE per model + head backward, BPTT, then the reduction (+ Adam on params / m / v when fuse_adam).
-    rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K]."""
+    rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K].
+    targets [M*B, K] fp32 (labels is then ignored and may be None): the soft-target loss per model (nsd_multi_train_fwd_soft)."""
     M = int(params.shape[0])
     x, B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
     if logits is None:
         logits = torch.empty((M * B, spec.K), dtype=torch.float32, device=params.device)
-    if labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() != M * B:
+    if targets is None and (labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() != M * B):
         raise NsdError(f"multi: labels must be contiguous int32 [M*B] = [{M * B}]")
     r = _multi_rngs(rngs, M)
     rp = C.cast(r, C.c_void_p) if r is not None else None
     P = spec.param_count
     pp, xp = _dev_f32(params, "params", (M, P)), _dev_f32(x, "x")
-    _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), 0, ws.data_ptr(), _nbytes(ws),
-          _dev_f32(logits, "logits"), STREAM)
+    if targets is not None:
+        _call("nsd_multi_train_fwd_soft", params.device, C.byref(d), M, pp, xp, stride, rp, _dev_f32(targets, "targets", (M * B, spec.K)), 0,
+              ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits"), STREAM)
+    else:
+        _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), 0, ws.data_ptr(), _nbytes(ws),
+              _dev_f32(logits, "logits"), STREAM)
     _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, 0, ws.data_ptr(), _nbytes(ws), STREAM)
     if fuse_adam:
         _call("nsd_multi_grad_reduce_adam", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,

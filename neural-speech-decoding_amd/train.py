@@ -20,7 +20,7 @@ import torch
 
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
-from .ops import Augment
+from .ops import Augment, Loss
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
 
@@ -71,6 +71,35 @@ def concurrent_epoch(runs, batch: int, epoch: int, step) -> int:
     return n
 
 
+def balanced_class_weights(y: np.ndarray, K: int):
+    """--class-weights balanced: w_k = N / (K * n_k) over the labels of the training split (sklearn's `balanced`); a class without
+    trials gets weight 0 (it has no target row to weigh)."""
+    n = np.bincount(np.asarray(y).astype(np.int64), minlength=K)[:K].astype(np.float64)
+    return tuple(float(len(y) / (K * c)) if c > 0 else 0.0 for c in n)
+
+
+def parse_class_weights(text, K: int):
+    """None, the string 'balanced' (resolved per training split by loss_for), or K comma-separated non-negative weights (ValueError)."""
+    if text is None or text == "balanced":
+        return text
+    try:
+        w = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        raise ValueError(f"--class-weights {text!r}: 'balanced' or {K} comma-separated numbers") from None
+    if len(w) != K:
+        raise ValueError(f"--class-weights {text!r}: {len(w)} weights for --classes {K}")
+    Loss(class_weights=w)                    # (range check)
+    return w
+
+
+def loss_for(args, y_train: np.ndarray) -> Loss:
+    """The ops.Loss of a run from --label-smoothing / --class-weights / --mixup and the labels of its training split."""
+    cw = parse_class_weights(args.class_weights, args.classes)
+    if cw == "balanced":
+        cw = balanced_class_weights(y_train, args.classes)
+    return Loss(label_smoothing=args.label_smoothing, class_weights=cw, mixup=args.mixup)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", help="directory with <prefix>_*.csv trials (reference: EEG_data_collection/), or a packed .npz "
@@ -106,7 +135,17 @@ def main(argv=None) -> int:
     ap.add_argument("--aug-scale", type=float, default=0.0, help="augmentation: one amplitude factor in [1 - r, 1 + r] per trial (0 = off)")
     ap.add_argument("--aug-channel-drop", type=float, default=0.0, help="augmentation: probability that a channel of a trial is zeroed (0 = off)")
     ap.add_argument("--aug-noise", type=float, default=0.0, help="augmentation: standard deviation of additive noise per sample (0 = off)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="loss: label smoothing eps in [0, 1) (0 = off)")
+    ap.add_argument("--class-weights", default=None, help="loss: `balanced` (N / (K n_k) over the training split; with --concurrent over "
+                                                          "all trials: one weight vector per launch) or K comma-separated weights w0,w1,...")
+    ap.add_argument("--mixup", type=float, default=0.0, help="loss: mix every training trial with a partner of its batch, lambda = 1 - M * U(0,1) "
+                                                             "(0 = off, 1 = uniform mixup)")
     args = ap.parse_args(argv)
+    try:
+        Loss(label_smoothing=args.label_smoothing, mixup=args.mixup)
+        parse_class_weights(args.class_weights, args.classes)
+    except ValueError as e:
+        ap.error(str(e))
     try:
         augment = Augment(max_shift=args.aug_shift, scale_range=args.aug_scale, p_channel=args.aug_channel_drop, noise_std=args.aug_noise)
     except ValueError as e:
@@ -165,7 +204,7 @@ def main(argv=None) -> int:
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
                          bidirectional=args.bidirectional).to(dev).train()
-        trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment)
+        trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]))
         tr_dev = torch.from_numpy(tr_idx).to(dev)
         best = (-1.0, -1)
         t0 = time.time()
@@ -206,7 +245,8 @@ def main(argv=None) -> int:
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
             models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize).to(dev).train())
-        mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment)
+        mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
+                                loss=loss_for(args, y_np))
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
         t0 = time.time()
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in runs]

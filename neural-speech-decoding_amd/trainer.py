@@ -93,7 +93,7 @@ def broadcast_parameters(flat: torch.Tensor, group=None, src: int = 0) -> None:
 class Trainer:
     def __init__(self, model: EEG_LSTM, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None,
-                 augment: Optional[ops.Augment] = None):
+                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None):
         self.model = model
         self.spec = model.spec
         self.flat = model.flat_parameters()
@@ -119,6 +119,19 @@ class Trainer:
         # trial augmentation (ops.Augment; stream 4 * step + 3 of this rank's seed): training steps only, and only with the other
         # stochastic parts on.  None -- also for an Augment with every operation off -- is the unaugmented step, launch for launch.
         self.augment = augment if augment is not None and augment.enabled and stochastic else None
+        # soft targets (ops.Loss: label smoothing, class weights, mixup): per training step nsd_augment (if any, with its z-score) ->
+        # nsd_mixup -> the step with targets, so the mixing acts on the windows the model would otherwise see; each rank mixes inside
+        # its own shard with its own seed (stream 4 * step + 3, index slots the augmentation does not use).  The scale stays
+        # 1 / global_batch (torch's weighted `mean` would divide by the weight sum instead).  Like the augmentation, the mixing belongs to
+        # the stochastic parts: with stochastic=False nothing is mixed (smoothing and class weights, which draw nothing, stay).  None --
+        # also for a Loss with every part off -- is the hard-label step, launch for launch.
+        if loss is not None and loss.mixup and not stochastic:
+            loss = ops.Loss(label_smoothing=loss.label_smoothing, class_weights=loss.class_weights)
+        if loss is not None and loss.enabled:
+            loss.check_classes(self.spec.K)
+            self.loss, self._class_w = loss, loss.weights_tensor(self.flat.device)
+        else:
+            self.loss, self._class_w = None, None
         self.step_count = 0
         self._bufs = {}
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.flat.device)
@@ -148,8 +161,16 @@ class Trainer:
     def step(self, x: torch.Tensor, y: torch.Tensor, global_batch: Optional[int] = None) -> None:
         """One optimisation step on this rank's shard: x [B,T,C] fp32, y [B] int32 (device tensors).  `global_batch`: trials
         of this step over ALL ranks (default B * world, i.e. equal shards); the CE gradient is scaled by 1/global_batch so
-        that the all-reduced sum is the global mean whatever the shard sizes.  B may be 0 when world > 1."""
+        that the all-reduced sum is the global mean whatever the shard sizes.  B may be 0 when world > 1.
+        y may also be a float32 [B,K] tensor: the trials' target rows, used as they are (distillation, sample weights; loss_b =
+        - sum_k y[b,k] log softmax_k) -- an error together with an enabled loss=, which builds the targets from labels."""
         B = int(x.shape[0])
+        if y.is_floating_point():
+            if self.loss is not None:
+                raise ops.NsdError("Trainer.step: float targets together with loss=: the trainer's Loss builds the targets from int32 labels")
+            if y.dtype != torch.float32 or tuple(y.shape) != (B, self.spec.K):
+                raise ops.NsdError(f"Trainer.step: float targets must be float32 [B,K] = [{B},{self.spec.K}], got {y.dtype} {tuple(y.shape)}")
+            y = y.contiguous()
         if global_batch is None:
             global_batch = B * self.world
         self.step_count += 1
@@ -181,12 +202,25 @@ class Trainer:
                                zscore=self.model.normalize)
         return ops.zscore(x) if self.model.normalize and x.shape[0] > 0 else x
 
+    def _targets(self, x: torch.Tensor, y: torch.Tensor):
+        """(windows, labels, targets) of the step: caller-made float targets as they are; with loss= the nsd_mixup launch on the prepared
+        windows (mixup off: it only builds the target rows and the windows stay where they are); else the hard labels."""
+        if y.is_floating_point():
+            return x, None, y
+        if self.loss is None:
+            return x, y, None
+        lo = self.loss
+        xm, tg = ops.mixup(x if lo.mixup > 0 else None, y, self.spec.K, dict(seed=self.seed, base_stream=(self.step_count & 0x3FFFFFFF) * 4),
+                           label_smoothing=lo.label_smoothing, mix=lo.mixup, class_weights=self._class_w)
+        return (xm if lo.mixup > 0 else x), None, tg
+
     def _local_grads(self, x: torch.Tensor, y: torch.Tensor, scale: float, fuse_adam: bool = False) -> None:
         """Launches that leave this shard's gradient (scaled) in self.grads; fuse_adam: the update rides in the last one."""
         from . import _lib
         sp = self.spec
         B, T, _ = x.shape
         x = self._prepare_input(x)
+        x, y, tg = self._targets(x, y)
         if self.model.precision == "bf16":
             # sequence-batched path: forward (+ head, CE, head backward), backward (+ all parameter gradients), Adam
             key = ("seq", B, T)
@@ -208,7 +242,7 @@ class Trainer:
             if self.stochastic:
                 rng = dict(seed=self.seed, base_stream=(self.step_count & 0x3FFFFFFF) * 4, p_lstm=self.model.dropout_p,
                            p_head=self.model.head_dropout_p)
-            ops.seq_train_fwd(sp, self.flat, x, y, buf["ws"], rng=rng, scale=scale, logits=buf["logits"])
+            ops.seq_train_fwd(sp, self.flat, x, y, buf["ws"], rng=rng, scale=scale, logits=buf["logits"], targets=tg)
             ops.seq_train_bwd(sp, self.flat, buf["ws"], B, T, rng=rng, grads=self.grads)
             ops.seq_guard(buf["ws"], self._skip)
             if self._carried_failure:                          # (seq_guard overwrites the flag with this workspace's status)
@@ -240,7 +274,7 @@ class Trainer:
                 _lib.check(L.nsd_dropout_mask(self.seed, sid + 2, self.model.head_dropout_p, dh.numel(), dh.data_ptr(), st), "dropout_mask")
         ops.train_step_grads(sp, self.flat, x, buf["ws"], y, buf["logits"], self.grads, scale=scale, drop_lstm=dl,
                              rrelu_slope=sl, drop_head=dh, residual=self.model.residual, fused_head=self.fused_head, rng=rng,
-                             adam=dict(m=self.m, v=self.v, **self._hyper()) if fuse_adam else None)
+                             adam=dict(m=self.m, v=self.v, **self._hyper()) if fuse_adam else None, targets=tg)
 
     # ---- hipGraph path ------------------------------------------------------------------------------------
     def static_inputs(self, B: int, T: int):
@@ -279,8 +313,19 @@ class Trainer:
                                   step_dev=self._step_dev, out=buf["xn"])
             else:
                 xin = ops.zscore(buf["x"], out=buf["xn"])
+        tg = None
+        if self.loss is not None:                              # static buffers again; the stream id comes from the device step counter
+            lo = self.loss
+            if "tg" not in buf:
+                buf["tg"] = torch.empty((B, self.spec.K), dtype=torch.float32, device=self.flat.device)
+                buf["xm"] = torch.empty_like(buf["x"]) if lo.mixup > 0 else None
+            xm, tg = ops.mixup(xin if lo.mixup > 0 else None, buf["y"], self.spec.K, dict(seed=self.seed, base_stream=0),
+                               label_smoothing=lo.label_smoothing, mix=lo.mixup, class_weights=self._class_w, step_dev=self._step_dev,
+                               out=buf["xm"], targets=buf["tg"])
+            xin = xm if lo.mixup > 0 else xin
         ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], buf["y"], buf["logits"], self.grads,
-                             scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual)
+                             scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual,
+                             targets=tg)
 
     def _issue_segment_b(self) -> None:
         from . import _lib
@@ -362,7 +407,8 @@ class Trainer:
 
     @_on_own_device
     def last_loss(self) -> float:
-        """Mean CE loss of this rank's shard in the most recent step (synchronises)."""
+        """Mean loss of this rank's shard in the most recent step: CE on the labels or, with loss= / float targets, the soft-target
+        loss sum_b loss_b / B (synchronises)."""
         if not self._last_B:
             return float("nan")
         if self.model.precision == "bf16":

@@ -27,7 +27,14 @@ GRID = [("baseline", []),
         ("shift12_chdrop0.1", ["--aug-shift", "12", "--aug-channel-drop", "0.1"]),
         ("shift31_scale0.1_chdrop0.1", ["--aug-shift", "31", "--aug-scale", "0.1", "--aug-channel-drop", "0.1"]),
         ("shift12_scale0.1_chdrop0.1_noise0.3", ["--aug-shift", "12", "--aug-scale", "0.1", "--aug-channel-drop", "0.1", "--aug-noise", "0.3"]),
-        ("shift31_scale0.1_chdrop0.1_noise0.3", ["--aug-shift", "31", "--aug-scale", "0.1", "--aug-channel-drop", "0.1", "--aug-noise", "0.3"])]
+        ("shift31_scale0.1_chdrop0.1_noise0.3", ["--aug-shift", "31", "--aug-scale", "0.1", "--aug-channel-drop", "0.1", "--aug-noise", "0.3"]),
+        # soft-target recipes (ops.Loss: nsd_mixup + the `_soft` step); not run yet -- no accuracy is claimed for them
+        ("smooth0.1", ["--label-smoothing", "0.1"]),
+        ("balanced", ["--class-weights", "balanced"]),
+        ("mixup1", ["--mixup", "1.0"]),
+        ("smooth0.1_balanced", ["--label-smoothing", "0.1", "--class-weights", "balanced"]),
+        ("mixup0.5_smooth0.1", ["--mixup", "0.5", "--label-smoothing", "0.1"]),
+        ("shift12_mixup1_smooth0.1_balanced", ["--aug-shift", "12", "--mixup", "1.0", "--label-smoothing", "0.1", "--class-weights", "balanced"])]
 
 
 def main():
