@@ -1,0 +1,87 @@
+"""The reference tests/test_gpu_fp32_routes.py rests on, pinned on the host (no GPU): the CPU oracle against the float64 torch
+restatement of the model (oracle/torch_ref.py) at H = 32 / 64 with the residual flag, with C < 8 and at the T edges of the
+first-generation fused kernels (csrc/nsd_lstm2.hip) -- shapes the oracle had never been compared with anything at.
+
+T_EDGES is the table of section (a) of the GPU file; the rows with T in {1, 2, 33, 65, 97} (all of B <= 7) are compared here, with
+the kink-safe fc.0.bias = +-4 the GPU cases use and with the generators' own bias.
+
+Bounds are those of test_oracle_matches_a_float64_restatement_of_the_model (tests/test_head_dims_cpu.py): every gradient tensor within
+5e-6 of its largest element (measured here: 1.3e-6 with the generators' bias, 2.7e-6 with +-4 -- fc.3.bias at K = 2, whose two entries
+are what is left of a sum over the batch that nearly cancels), attn.bias within 2e-6 absolute
+(measured 1.5e-8).  The logits keep that test's 1e-6 with the generators' own bias (measured 2.3e-7); with fc.0.bias = +-4 the fc.0
+activations, and with them the logits, are several times larger, the fp32 oracle differs from float64 by up to 2.1e-6 there, and the
+bound is 5e-6.  The mean loss is held to twice the logits' bound (measured 6.3e-8 / 2.4e-7).  At T = 1 the recurrent weights see
+h[-1] = 0 and the attention's softmax runs over a single step: the gradients of weight_hh and attn.weight are exactly zero in the
+restatement, and the oracle's are compared absolutely (<= 1e-7) instead of being divided by a scale of zero.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle import nsd_oracle as orc
+from oracle.torch_ref import TorchRefEEG
+from tests.test_head_dims_cpu import KINK_MARGIN, head_inputs, kink_margin
+
+# (C, H, K, F, B, T, residual), L = 2.  T: the first step, the step after it (layer 0's backward lags by two macro steps), both sides of
+# each 32-step chunk of the staged x / dropout-mask double buffer, and a fourth chunk (both buffers reused).  Each H sees every C of
+# {8, 7, 5, 1} (C = 7, 5, 1: the odd split of the two-channel pairs of a quad) and both values of the residual flag.
+T_EDGES = [(8, 32, 3, 32, 5, 1, False), (7, 32, 5, 7, 6, 2, True), (5, 32, 3, 32, 8, 31, False), (1, 32, 2, 33, 7, 32, True),
+           (8, 32, 4, 33, 4, 33, True), (7, 32, 3, 32, 8, 64, False), (5, 32, 2, 32, 6, 65, True), (1, 32, 3, 32, 5, 97, False),
+           (1, 64, 3, 32, 4, 1, True), (5, 64, 4, 33, 7, 2, False), (7, 64, 3, 32, 8, 31, True), (8, 64, 5, 7, 5, 32, False),
+           (1, 64, 2, 32, 6, 33, False), (5, 64, 3, 32, 8, 64, True), (7, 64, 2, 33, 5, 65, False), (8, 64, 3, 32, 4, 97, True)]
+CPU_T = (1, 2, 33, 65, 97)
+LOGIT_TOL_OWN_BIAS, LOGIT_TOL_SAFE_BIAS = 1e-6, 5e-6
+
+
+def test_the_table_covers_what_it_promises():
+    for H in (32, 64):
+        rows = [r for r in T_EDGES if r[1] == H]
+        assert sorted(r[5] for r in rows) == [1, 2, 31, 32, 33, 64, 65, 97]
+        assert {r[0] for r in rows} == {8, 7, 5, 1} and {r[6] for r in rows} == {False, True}
+        assert all(4 <= r[4] <= 8 for r in rows)
+    assert all(r[4] <= 7 for r in T_EDGES if r[5] in CPU_T)
+
+
+@pytest.mark.parametrize("safe", [True, False], ids=["safe_bias", "own_bias"])
+@pytest.mark.parametrize("Cc,H,K,F,B,T,residual", [r for r in T_EDGES if r[5] in CPU_T])
+def test_oracle_matches_float64_at_the_fused_kernels_edges(Cc, H, K, F, B, T, residual, safe):
+    d, flat, x, y, masks = head_inputs(Cc, H, K, F, B, T, safe=safe)
+    loss, g, fw = orc.loss_and_grads(flat, x, y, d, residual=residual, **masks)
+    margin = kink_margin(fw)
+    m = TorchRefEEG(Cc, H, 2, K, F=F, residual=residual)
+    m.load_reference_state({k: torch.from_numpy(v) for k, v in orc.unflatten(flat, d).items()})
+    m = m.double()
+    t = lambda a: torch.from_numpy(a).double()           # noqa: E731
+    logits = m(t(x), t(masks["drop_lstm"]), t(masks["rrelu_slope"]), t(masks["drop_head"]))
+    loss64 = torch.nn.functional.cross_entropy(logits, torch.from_numpy(y.astype(np.int64)))
+    loss64.backward()
+    loss64 = float(loss64.detach())
+    lerr = float(np.abs(fw["logits"] - logits.detach().numpy()).max())
+    ref = {k: v.detach().numpy() for k, v in m.reference_named_grads().items()}
+    got = orc.unflatten(g, d)
+    worst, worst_k, zero, ab, bad = 0.0, "", [], 0.0, []
+    for k in orc.param_names(d):
+        scale = float(np.abs(ref[k]).max())
+        err = float(np.abs(got[k] - ref[k].reshape(got[k].shape)).max())
+        if k == "attn.bias":                               # analytically zero: both sides are round-off
+            ab = err
+            if not err < 2e-6:
+                bad.append((k, err))
+        elif scale == 0.0:                                 # an exactly zero reference tensor: absolute, never divided by its scale
+            zero.append(k)
+            if not err <= 1e-7:
+                bad.append((k, err, scale))
+        else:
+            if err / scale > worst:
+                worst, worst_k = err / scale, k
+            if not err <= 5e-6 * scale:
+                bad.append((k, err, scale))
+    print(f"oracle vs float64 C={Cc} H={H} K={K} F={F} B={B} T={T} residual={residual} safe={safe}: logits {lerr:.2e}  "
+          f"loss {abs(loss - loss64):.2e}  grads/max {worst:.2e} ({worst_k})  attn.bias {ab:.1e}  kink margin {margin:.1e}  zero tensors {zero}")
+    assert not bad, bad
+    # T = 1: h[-1] = 0 in both layers, and the softmax over one step is 1 whatever the score
+    assert sorted(zero) == (["attn.weight", "lstm.weight_hh_l0", "lstm.weight_hh_l1"] if T == 1 else []), zero
+    ltol = LOGIT_TOL_SAFE_BIAS if safe else LOGIT_TOL_OWN_BIAS
+    assert lerr < ltol, lerr
+    assert abs(loss - loss64) < 2 * ltol           # log-sum-exp and the label's logit each move by at most the logits' bound
+    assert margin > KINK_MARGIN, margin

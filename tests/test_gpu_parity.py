@@ -55,6 +55,13 @@ def _t(a, dev):
 # of either backward kernel fails dozens of these comparisons.
 FAST48 = dict(rtol=2e-5, wtol=5e-5)
 DX_TOL = 2e-5
+# Bounds of the exact-fp32 routes -- no reduced-precision products: the first-generation H = 32 / 64 kernels of nsd_lstm2.hip, the generic
+# path and the batched MFMA path -- against the oracle, of each tensor's largest element: the LSTM weight gradients within 1e-5, every
+# other tensor within 2e-5 (the 1e-7 floor and attn.bias's 2e-6 as before).  About eight times the worst value measured over
+# tests/test_gpu_fp32_routes.py on one MI355X (1.25e-6: weight_ih_l0 of the generic path at 2051 trials; 2.25e-6: attn.weight at T = 2,
+# and fc.3.bias at K = 2, where the sum over the batch nearly cancels): the room FAST48 has.  Neither exceeds FAST48's.  The comparisons
+# of these routes below measure <= 7.5e-7 / 4.8e-6 (their "grad_close worst" lines).
+FP32_EXACT = dict(rtol=2e-5, wtol=1e-5)
 
 
 def _grad_close(got_flat, ref_flat, d, rtol=2e-4, wtol=None):
@@ -330,7 +337,7 @@ def test_other_fast_path_shapes_vs_oracle(nsd, dev, H, C, K):
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, d, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, rtol=3e-4)
+    _grad_close(grads, g_ref, d, **(FAST48 if H == 48 else FP32_EXACT))       # H = 48: the split-bf16 kernels at C < 8
 
 
 def test_generic_path_cfg3_shape_vs_reference_goldens(nsd, dev, golden):
@@ -389,7 +396,7 @@ def test_generic_path_gradients_vs_oracle(nsd, dev, C, H, L, K, residual):
         kw["drop_lstm"] = dl
     loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, **kw)
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, rtol=3e-4)
+    _grad_close(grads, g_ref, d, **FP32_EXACT)
 
 
 @pytest.mark.parametrize("C,H,L,K,residual,B,T", [(8, 256, 2, 5, False, 20, 21), (8, 112, 2, 3, False, 70, 9), (64, 128, 2, 5, False, 33, 12),
@@ -413,7 +420,7 @@ def test_batched_mfma_path_vs_oracle(nsd, dev, C, H, L, K, residual, B, T):
         kw["drop_lstm"] = dl
     loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, **kw)
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, rtol=3e-4)
+    _grad_close(grads, g_ref, d, **FP32_EXACT)
     # inference on the same kernels (cell state carried in a [B,H] ping-pong instead of the saved sequences)
     flat = _t(flat_np, dev)
     lg, pr = ops.infer(spec, flat, _t(x, dev), residual=residual)
