@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, step_recipe as sr
 from ._lib import NsdError
 
 CLASS_NAMES = ["Food", "Water", "BG-Noise"]   # verbatim from lstm_eeg_model.py:11
@@ -252,12 +252,12 @@ class EEG_LSTM(nn.Module):
         if self._mask_override is not None:
             return self._mask_override
         self._step += 1
-        base = self._step * 4
+        base = sr.base_stream(self._step)                   # (the module's own train-mode calls number their streams as a trainer's steps)
         sp = self.spec
-        drop_lstm = (ops.dropout_mask(self._seed, base, self.dropout_p, (sp.L - 1, B, T, sp.H), device)
+        drop_lstm = (ops.dropout_mask(self._seed, base + sr.SLOT_LSTM_DROPOUT, self.dropout_p, (sp.L - 1, B, T, sp.H), device)
                      if self.dropout_p > 0 and sp.L > 1 else None)
-        rrelu = ops.rrelu_noise(self._seed, base + 1, (B, sp.F), device)
-        drop_head = (ops.dropout_mask(self._seed, base + 2, self.head_dropout_p, (B, sp.F), device)
+        rrelu = ops.rrelu_noise(self._seed, base + sr.SLOT_RRELU, (B, sp.F), device)
+        drop_head = (ops.dropout_mask(self._seed, base + sr.SLOT_HEAD_DROPOUT, self.head_dropout_p, (B, sp.F), device)
                      if self.head_dropout_p > 0 else None)
         return drop_lstm, rrelu, drop_head
 
@@ -307,7 +307,7 @@ class EEG_LSTM(nn.Module):
         rng = None
         if self.training:
             self._step += 1
-            rng = dict(seed=self._seed, base_stream=4 * self._step, p_lstm=self.dropout_p, p_head=self.head_dropout_p)
+            rng = sr.step_rng(self._seed, self._step, self.dropout_p, self.head_dropout_p)
         params = [p for _, p in self._named_in_order()]
         return _EEGSeqFunction.apply(self, x, labels.to(torch.int32).contiguous(), rng, *params)
 

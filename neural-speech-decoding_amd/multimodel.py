@@ -1,9 +1,10 @@
 """Several H = 48 models per launch: folds, seed sweeps and ensembles (include/nsd.h, nsd_multi_*).
 
 ModelBatchTrainer steps M same-shaped EEG_LSTM models together: one forward, one backward and one reduction + Adam launch for all
-of them.  Model m's step is the step `Trainer(model_m, seed=seeds[m])` would take on its batch: the same random streams (seed, base
-stream 4 * step), the same mean cross-entropy over its own B trials, the same Adam update.  EnsemblePredictor averages the class
-probabilities of M checkpoints computed in one inference launch, behind SimplePredictor's surface and preprocessing.
+of them.  Model m's step is the step `Trainer(model_m, seed=seeds[m])` would take on its batch: the same recipe and random
+streams (step_recipe.py, where a step's streams are defined), the same mean cross-entropy over its own B trials, the same Adam
+update.  EnsemblePredictor averages the class probabilities of M checkpoints computed in one inference launch, behind
+SimplePredictor's surface and preprocessing.
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import torch
 from . import ops
 from ._lib import NsdError
 from .lstm_eeg_model import EEG_LSTM, SimplePredictor
+from .step_recipe import StepRecipe, trainer_seed
 
 
 def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
@@ -70,20 +72,12 @@ class ModelBatchTrainer:
         seeds = list(seeds) if seeds is not None else [1234] * M
         if len(seeds) != M:
             raise NsdError(f"ModelBatchTrainer: {len(seeds)} seeds for {M} models")
-        # Trainer's seed of rank 0 (trainer.py): the streams of model m are those of Trainer(model_m, seed=seeds[m])
-        self.seeds = [(int(s) + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+        self.seeds = [trainer_seed(s) for s in seeds]      # the streams of model m are those of Trainer(model_m, seed=seeds[m])
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.stochastic = stochastic
-        # as Trainer: model m's trials are augmented with the draws of Trainer(model_m, seed=seeds[m], augment=augment), all models in
-        # one launch; None (or every operation off) is the unaugmented step
-        self.augment = augment if augment is not None and augment.enabled and stochastic else None
-        if loss is not None and loss.mixup and not stochastic:       # as Trainer: deterministic steps mix nothing
-            loss = ops.Loss(label_smoothing=loss.label_smoothing, class_weights=loss.class_weights)
-        if loss is not None and loss.enabled:
-            loss.check_classes(self.spec.K)
-            self.loss, self._class_w = loss, loss.weights_tensor(dev)
-        else:
-            self.loss, self._class_w = None, None
+        # Trainer's recipe (step_recipe.py), applied per model with its own seed, each launch for all models
+        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev)
+        self.augment, self.loss = self.recipe.augment, self.recipe.loss
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
         self.grads = torch.zeros_like(self.params)
@@ -101,19 +95,13 @@ class ModelBatchTrainer:
 
     def step(self, x: torch.Tensor, y: torch.Tensor) -> None:
         M = self.M
-        if x.dim() == 3:
-            B, T = int(x.shape[0]), int(x.shape[1])
-        elif x.dim() == 4 and x.shape[0] == M:
-            B, T = int(x.shape[1]), int(x.shape[2])
-        else:
+        if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != M):
             raise NsdError(f"ModelBatchTrainer.step: x must be [M={M},B,T,C] or [B,T,C], got {tuple(x.shape)}")
+        B, T = int(x.shape[-3]), int(x.shape[-2])
         if B == 0:
             raise NsdError("ModelBatchTrainer.step: empty batch")
         if not ops.multi_path(self.spec, M, B, T):
             raise NsdError(f"ModelBatchTrainer.step: T = {T} is outside the model-batched path (nsd_multi_path: T <= 1024)")
-        x = x.contiguous().float()
-        if self.models[0].normalize and self.augment is None:     # as Trainer: the model is trained on what it is evaluated on
-            x = ops.zscore(x.reshape(-1, T, x.shape[-1])).view(x.shape)
         y = y.to(torch.int32)
         if y.dim() == 1:
             if y.shape[0] != B:
@@ -121,21 +109,10 @@ class ModelBatchTrainer:
             y = y.unsqueeze(0).expand(M, B)
         if tuple(y.shape) != (M, B):
             raise NsdError(f"ModelBatchTrainer.step: y must be [M,B] or [B], got {tuple(y.shape)}")
-        y = y.contiguous().view(-1)
         self.step_count += 1
-        sid = (self.step_count & 0x3FFFFFFF) * 4
-        mdl = self.models[0]
-        if self.augment is not None:                     # one launch: a shared [B,T,C] becomes [M,B,T,C], each model with its own draws
-            x = ops.augment(x, self.augment, [dict(seed=s, base_stream=sid) for s in self.seeds], M=M, zscore=mdl.normalize)
-        rngs = ([dict(seed=s, base_stream=sid, p_lstm=mdl.dropout_p, p_head=mdl.head_dropout_p) for s in self.seeds]
-                if self.stochastic else None)
+        x, y, tg = self.recipe.prepare(x, y.contiguous().view(-1), self.seeds, self.step_count, M=M)
+        rngs = [self.recipe.rng(s, self.step_count) for s in self.seeds] if self.stochastic else None
         buf = self._buffers(B, T)
-        tg = None
-        if self.loss is not None:                        # one launch for all models, on the windows each would otherwise see
-            lo = self.loss
-            xm, tg = ops.mixup(x if lo.mixup > 0 else None, y, self.spec.K, [dict(seed=s, base_stream=sid) for s in self.seeds], M=M,
-                               label_smoothing=lo.label_smoothing, mix=lo.mixup, class_weights=self._class_w)
-            x = xm if lo.mixup > 0 else x
         ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
                              step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                              weight_decay=self.weight_decay, targets=tg)

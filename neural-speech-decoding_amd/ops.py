@@ -106,9 +106,45 @@ def _labels_ptr(labels: torch.Tensor) -> int:
     return labels.data_ptr()
 
 
-def _rng_struct(rng: dict) -> "_lib.Rng":
-    """rng=dict(seed=, base_stream=, p_lstm=, p_head=) -> nsd_rng"""
-    return _lib.Rng(int(rng["seed"]) & 0xFFFFFFFFFFFFFFFF, int(rng["base_stream"]) & 0xFFFFFFFF, float(rng["p_lstm"]), float(rng["p_head"]))
+# A step owns four consecutive streams of its seed, base_stream + slot (step_recipe.py numbers the steps): inter-layer dropout
+# multipliers, RReLU slopes of the head, head dropout multipliers, and nsd_augment with nsd_mixup (index slots of their own inside it)
+SLOT_LSTM_DROPOUT, SLOT_RRELU, SLOT_HEAD_DROPOUT, SLOT_AUGMENT = 0, 1, 2, 3
+
+
+def _rng_struct(rng: dict, probs: bool = True) -> "_lib.Rng":
+    """rng=dict(seed=, base_stream=, p_lstm=, p_head=) -> nsd_rng (step_recipe.step_rng builds the dict).  probs=False: the launch
+    draws no dropout, the probabilities are not asked for and stay 0."""
+    p = (float(rng["p_lstm"]), float(rng["p_head"])) if probs else (0.0, 0.0)
+    return _lib.Rng(int(rng["seed"]) & 0xFFFFFFFFFFFFFFFF, int(rng["base_stream"]) & 0xFFFFFFFF, *p)
+
+
+def _rng_array(rngs, M: int, what: str, probs: bool = True):
+    """rngs: one rng dict or M of them -> nsd_rng[M] (None stays None)"""
+    rngs = [rngs] if isinstance(rngs, dict) else rngs
+    if rngs is not None and len(rngs) != M:
+        raise NsdError(f"{what}: {len(rngs)} rng entries for {M} models")
+    return None if rngs is None else (_lib.Rng * M)(*[_rng_struct(g, probs) for g in rngs])
+
+
+def _step_ptr(step_dev: Optional[torch.Tensor], what: str) -> Optional[int]:
+    """The device step counter of the hipGraph-replayable entry points (stream ids / Adam's step are read from it on the device)."""
+    if step_dev is not None and (step_dev.dtype != torch.int64 or not step_dev.is_cuda):
+        raise NsdError(f"{what}: step_dev must be an int64 tensor on the device")
+    return None if step_dev is None else step_dev.data_ptr()
+
+
+def _model_windows(x: torch.Tensor, M: int, what: str, forms: str = "[B,T,C] or [M,B,T,C]"):
+    """Model-batched windows x [B,T,C] (one model's, or shared by M models: stride 0) or [M,B,T,C] (M = 1 leaves the count to x)
+    -> (M, B, T, C, x_model_stride, shape of the windows the models see).  what / forms: the caller's words for a refusal."""
+    if x.dim() == 4:
+        Mx, B, T, Cc = (int(v) for v in x.shape)
+        if M not in (1, Mx):
+            raise NsdError(f"{what}: x has {Mx} model slices, M = {M}")
+        return Mx, B, T, Cc, B * T * Cc, (Mx, B, T, Cc)
+    if x.dim() == 3:
+        B, T, Cc = (int(v) for v in x.shape)
+        return int(M), B, T, Cc, 0, ((B, T, Cc) if M == 1 else (int(M), B, T, Cc))
+    raise NsdError(f"{what}: x must be {forms}, got {tuple(x.shape)}")
 
 
 class _StreamOf:
@@ -295,36 +331,15 @@ def augment(x: torch.Tensor, aug: Augment, rngs, *, M: int = 1, zscore: bool = F
     x [M,B,T,C]: per-model windows -> [M,B,T,C].  rngs: dict(seed=, base_stream=) or M of them (model m draws what a single-model call
     with rngs[m] draws; the stream used is base_stream + 3).  step_dev: device int64 step counter; base_stream is then
     4 * (step_dev[0] & 0x3fffffff) for every model (hipGraph replay).  All operations off: a bitwise copy of x."""
-    if isinstance(rngs, dict):
-        rngs = [rngs]
-    if x.dim() == 4:
-        Mx, B, T, Cc = (int(v) for v in x.shape)
-        if M not in (1, Mx):
-            raise NsdError(f"augment: x has {Mx} model slices, M = {M}")
-        M, stride, shape = Mx, B * T * Cc, (Mx, B, T, Cc)
-    elif x.dim() == 3:
-        B, T, Cc = (int(v) for v in x.shape)
-        M, stride = int(M), 0
-        shape = (B, T, Cc) if M == 1 else (M, B, T, Cc)
-    else:
-        raise NsdError(f"augment: x must be [B,T,C] or [M,B,T,C], got {tuple(x.shape)}")
-    if len(rngs) != M:
-        raise NsdError(f"augment: {len(rngs)} rng entries for {M} models")
-    r = (_lib.Rng * M)()
-    for i, g in enumerate(rngs):
-        r[i] = _lib.Rng(int(g["seed"]) & 0xFFFFFFFFFFFFFFFF, int(g["base_stream"]) & 0xFFFFFFFF, 0.0, 0.0)
+    M, B, T, Cc, stride, shape = _model_windows(x, M, "augment")
+    r = _rng_array(rngs, M, "augment", probs=False)
     a = _lib.Aug(int(aug.max_shift), float(aug.scale_range), float(aug.p_channel), float(aug.noise_std))
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
     if out.numel() != M * B * T * Cc:
         raise NsdError(f"augment: out has {out.numel()} elements for {M} x {B} x {T} x {Cc}")
-    sp = None
-    if step_dev is not None:
-        if step_dev.dtype != torch.int64 or not step_dev.is_cuda:
-            raise NsdError("augment: step_dev must be an int64 tensor on the device")
-        sp = step_dev.data_ptr()
     d = Dims(B, T, Cc, 1, 1, 1, 1)
-    _call("nsd_augment", x.device, C.byref(d), M, _dev_f32(x, "x"), stride, C.byref(a), C.cast(r, C.c_void_p), sp,
+    _call("nsd_augment", x.device, C.byref(d), M, _dev_f32(x, "x"), stride, C.byref(a), C.cast(r, C.c_void_p), _step_ptr(step_dev, "augment"),
           _lib.NSD_AUG_ZSCORE if zscore else 0, _dev_f32(out, "out"), STREAM)
     return out
 
@@ -376,8 +391,6 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     x = None (mix = 0 only): the launch builds targets alone and y is None.  labels [M*B] int32 (model m's trial b at m * B + b).
     rngs / step_dev as ops.augment (the stream is base_stream + 3, on index slots nsd_augment does not use).  class_weights: device
     fp32 [K].  mix = 0 with x given: y is a bitwise copy of x."""
-    if isinstance(rngs, dict):
-        rngs = [rngs]
     if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
         raise NsdError("mixup: labels must be a contiguous int32 tensor on the device")
     dev = labels.device
@@ -386,24 +399,11 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
         if labels.numel() % M:
             raise NsdError(f"mixup: {labels.numel()} labels for {M} models")
         B, T, Cc, stride, shape = labels.numel() // M, 1, 1, 0, None
-    elif x.dim() == 4:
-        Mx, B, T, Cc = (int(v) for v in x.shape)
-        if M not in (1, Mx):
-            raise NsdError(f"mixup: x has {Mx} model slices, M = {M}")
-        M, stride, shape = Mx, B * T * Cc, (Mx, B, T, Cc)
-    elif x.dim() == 3:
-        B, T, Cc = (int(v) for v in x.shape)
-        M, stride = int(M), 0
-        shape = (B, T, Cc) if M == 1 else (M, B, T, Cc)
     else:
-        raise NsdError(f"mixup: x must be [B,T,C] or [M,B,T,C], got {tuple(x.shape)}")
-    if len(rngs) != M:
-        raise NsdError(f"mixup: {len(rngs)} rng entries for {M} models")
+        M, B, T, Cc, stride, shape = _model_windows(x, M, "mixup")
+    r = _rng_array(rngs, M, "mixup", probs=False)
     if labels.numel() != M * B:
         raise NsdError(f"mixup: {labels.numel()} labels for {M} x {B} trials")
-    r = (_lib.Rng * M)()
-    for i, g in enumerate(rngs):
-        r[i] = _lib.Rng(int(g["seed"]) & 0xFFFFFFFFFFFFFFFF, int(g["base_stream"]) & 0xFFFFFFFF, 0.0, 0.0)
     mx = _lib.Mix(float(mix), float(label_smoothing))
     if targets is None:
         targets = torch.empty((M * B, K), dtype=torch.float32, device=dev)
@@ -416,14 +416,9 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
             raise NsdError(f"mixup: out has {out.numel()} elements for {M} x {B} x {T} x {Cc}")
     else:
         out = None
-    sp = None
-    if step_dev is not None:
-        if step_dev.dtype != torch.int64 or not step_dev.is_cuda:
-            raise NsdError("mixup: step_dev must be an int64 tensor on the device")
-        sp = step_dev.data_ptr()
     d = Dims(B, T, Cc, 1, 1, int(K), 1)
     _call("nsd_mixup", dev, C.byref(d), M, _dev_f32(x, "x"), stride, labels.data_ptr(), _dev_f32(class_weights, "class_weights", (K,)),
-          C.byref(mx), C.cast(r, C.c_void_p), sp, _dev_f32(out, "out"), _dev_f32(targets, "targets"), STREAM)
+          C.byref(mx), C.cast(r, C.c_void_p), _step_ptr(step_dev, "mixup"), _dev_f32(out, "out"), _dev_f32(targets, "targets"), STREAM)
     return out, targets
 
 
@@ -455,7 +450,6 @@ def train_forward(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: torc
     B, T, Cc = x.shape
     d = spec.dims(B, T)
     flags = _lib.NSD_FLAG_TRAIN | (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags
-    L = _lib.lib()
     pp = _dev_f32(flat, "params", (spec.param_count,))
     _call("nsd_lstm_fwd", x.device, C.byref(d), pp, _dev_f32(x, "x", (B, T, spec.C)),
           _dev_f32(drop_lstm, "drop_lstm", (spec.L - 1, B, T, spec.H)), flags, _dev_f32(ws, "workspace"), _nbytes(ws), STREAM)
@@ -478,7 +472,6 @@ def train_backward(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: tor
     on the H = 48 path: no second backward on the same forward then)."""
     B, T, _ = x.shape
     d = spec.dims(B, T)
-    L = _lib.lib()
     pp = _dev_f32(flat, "params", (spec.param_count,))
     if dlogits is None:
         if labels is None:
@@ -586,15 +579,47 @@ def loss_sum(spec: ModelSpec, ws: torch.Tensor, B: int, T: int, out: Optional[to
 
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, step: int, lr: float = 1e-3,
               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
-              grad_scale: float = 1.0, skip: Optional[torch.Tensor] = None) -> None:
-    """torch.optim.Adam update of the flat vector.  skip: device fp32 flag (ops.seq_guard); non-zero -> nothing is updated."""
-    n = p.numel()
-    if skip is None:
-        _call("nsd_adam_step", p.device, n, _dev_f32(p, "p"), _dev_f32(g, "g", p.shape), _dev_f32(m, "m", p.shape),
-              _dev_f32(v, "v", p.shape), lr, beta1, beta2, eps, weight_decay, grad_scale, step, STREAM)
+              grad_scale: float = 1.0, skip: Optional[torch.Tensor] = None, step_dev: Optional[torch.Tensor] = None) -> None:
+    """torch.optim.Adam update of the flat vector.  skip: device fp32 flag (ops.seq_guard); non-zero -> nothing is updated.
+    step_dev: device int64 step counter read in place of `step` (nsd_adam_step_dev: hipGraph replay); not together with skip."""
+    head = (p.numel(), _dev_f32(p, "p"), _dev_f32(g, "g", p.shape), _dev_f32(m, "m", p.shape), _dev_f32(v, "v", p.shape),
+            lr, beta1, beta2, eps, weight_decay, grad_scale)
+    if step_dev is not None:
+        if skip is not None:
+            raise NsdError("adam_step: pass either skip= or step_dev=, not both")
+        _call("nsd_adam_step_dev", p.device, *head, _step_ptr(step_dev, "adam_step"), STREAM)
+    elif skip is None:
+        _call("nsd_adam_step", p.device, *head, step, STREAM)
     else:
-        _call("nsd_adam_step_guarded", p.device, n, _dev_f32(p, "p"), _dev_f32(g, "g", p.shape), _dev_f32(m, "m", p.shape),
-              _dev_f32(v, "v", p.shape), lr, beta1, beta2, eps, weight_decay, grad_scale, step, _dev_f32(skip, "skip"), STREAM)
+        _call("nsd_adam_step_guarded", p.device, *head, step, _dev_f32(skip, "skip"), STREAM)
+
+
+def step_counter_inc(step_dev: torch.Tensor) -> None:
+    """step_dev[0] += 1 on the device: first launch of a hipGraph-replayed step, whose other launches read the counter."""
+    _call("nsd_step_counter_inc", step_dev.device, _step_ptr(step_dev, "step_counter_inc"), STREAM)
+
+
+def train_masks(seed: int, stream, p_lstm: float, p_head: float, drop_lstm: Optional[torch.Tensor], rrelu: Optional[torch.Tensor],
+                drop_head: Optional[torch.Tensor]) -> None:
+    """Fill the explicit mask tensors of a training step from the streams base + SLOT_* of `seed`: all three in one launch
+    (nsd_train_masks), a subset (a tensor that the model does not need is None) with one launch each.  stream: the step's host
+    base stream id, or the device int64 step counter it is then formed from (nsd_train_masks_dev: hipGraph replay, all three tensors)."""
+    given = [t for t in (drop_lstm, rrelu, drop_head) if t is not None]
+    seed, dev = int(seed) & 0xFFFFFFFFFFFFFFFF, given[0].device if given else None
+    dl, sl, dh = _dev_f32(drop_lstm, "drop_lstm"), _dev_f32(rrelu, "rrelu"), _dev_f32(drop_head, "drop_head")
+    on_dev = torch.is_tensor(stream)
+    if len(given) == 3:
+        _call("nsd_train_masks_dev" if on_dev else "nsd_train_masks", dev, seed, _step_ptr(stream, "train_masks") if on_dev else stream,
+              p_lstm, p_head, drop_lstm.numel(), dl, rrelu.numel(), sl, dh, STREAM)
+        return
+    if on_dev and given:
+        raise NsdError("train_masks: a device step counter needs all three mask tensors")
+    if dl is not None:
+        _call("nsd_dropout_mask", dev, seed, stream + SLOT_LSTM_DROPOUT, p_lstm, drop_lstm.numel(), dl, STREAM)
+    if sl is not None:
+        _call("nsd_rrelu_noise", dev, seed, stream + SLOT_RRELU, rrelu.numel(), sl, STREAM)
+    if dh is not None:
+        _call("nsd_dropout_mask", dev, seed, stream + SLOT_HEAD_DROPOUT, p_head, drop_head.numel(), dh, STREAM)
 
 
 def dropout_mask(seed: int, stream_id: int, p: float, shape, device) -> torch.Tensor:
@@ -801,32 +826,14 @@ def multi_workspace(spec: ModelSpec, M: int, B: int, T: int, device) -> torch.Te
     return torch.empty(max(int(n) // 4, 1), dtype=torch.float32, device=device)
 
 
-def _multi_rngs(rngs, M: int):
-    if rngs is None:
-        return None
-    if len(rngs) != M:
-        raise NsdError(f"multi: {len(rngs)} rng entries for {M} models")
-    arr = (_lib.Rng * M)()
-    for i, r in enumerate(rngs):
-        arr[i] = _rng_struct(r)
-    return arr
-
-
-def _multi_x(spec: ModelSpec, x: torch.Tensor, M: int) -> Tuple[torch.Tensor, int, int, int]:
-    """x [M,B,T,C] (per-model windows) or [B,T,C] (shared: x_model_stride 0) -> (x, B, T, stride)."""
-    if x.dim() == 4:
-        if x.shape[0] != M:
-            raise NsdError(f"multi: x has {x.shape[0]} model slices for {M} models")
-        _, B, T, Cc = x.shape
-        stride = B * T * Cc
-    elif x.dim() == 3:
-        B, T, Cc = x.shape
-        stride = 0
-    else:
-        raise NsdError(f"multi: x must be [M,B,T,C] or [B,T,C], got {tuple(x.shape)}")
+def _multi_x(spec: ModelSpec, x: torch.Tensor, M: int) -> Tuple[int, int, int]:
+    """x [M,B,T,C] (per-model windows) or [B,T,C] (shared: x_model_stride 0) of M models of `spec` -> (B, T, stride)."""
+    if x.dim() == 4 and x.shape[0] != M:                  # M is the parameters' model count here
+        raise NsdError(f"multi: x has {x.shape[0]} model slices for {M} models")
+    _, B, T, Cc, stride, _ = _model_windows(x, M, "multi", "[M,B,T,C] or [B,T,C]")
     if Cc != spec.C:
         raise NsdError(f"x has {Cc} channels, model expects {spec.C}")
-    return x, int(B), int(T), int(stride)
+    return B, T, stride
 
 
 def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, labels: torch.Tensor, ws: torch.Tensor, grads: torch.Tensor,
@@ -839,13 +846,13 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
     rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K].
     targets [M*B, K] fp32 (labels is then ignored and may be None): the soft-target loss per model (nsd_multi_train_fwd_soft)."""
     M = int(params.shape[0])
-    x, B, T, stride = _multi_x(spec, x, M)
+    B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
     if logits is None:
         logits = torch.empty((M * B, spec.K), dtype=torch.float32, device=params.device)
     if targets is None and (labels.dtype != torch.int32 or not labels.is_contiguous() or labels.numel() != M * B):
         raise NsdError(f"multi: labels must be contiguous int32 [M*B] = [{M * B}]")
-    r = _multi_rngs(rngs, M)
+    r = _rng_array(rngs, M, "multi")
     rp = C.cast(r, C.c_void_p) if r is not None else None
     P = spec.param_count
     pp, xp = _dev_f32(params, "params", (M, P)), _dev_f32(x, "x")
@@ -877,7 +884,7 @@ def multi_infer(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, *, want_
                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Eval-mode forward of M models in one launch: params [M,P], x [M,B,T,C] or shared [B,T,C] -> logits [M,B,K] (+ probs)."""
     M = int(params.shape[0])
-    x, B, T, stride = _multi_x(spec, x, M)
+    B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
     logits = torch.empty((M, B, spec.K), dtype=torch.float32, device=params.device)
     probs = torch.empty_like(logits) if want_probs else None

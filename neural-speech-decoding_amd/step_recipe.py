@@ -1,0 +1,87 @@
+"""The one recipe of a training step: which random streams it draws and what the kernels see of (windows, labels, seed, step).
+Trainer.step (eager), Trainer.step_static (hipGraph replay), ModelBatchTrainer.step and EEG_LSTM's train-mode surface take their stream
+numbering from here, and the three trainer steps prepare their inputs through StepRecipe.prepare -- so "the replayed step is the eager
+step" and "model m of the batched step is Trainer(model_m, seed=seeds[m])'s step" follow from the structure.
+A step owns four consecutive streams of its seed, base_stream(step) + SLOT_* (the slots are named beside the launches, in ops.py).
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+
+from . import ops
+from .ops import SLOT_AUGMENT, SLOT_HEAD_DROPOUT, SLOT_LSTM_DROPOUT, SLOT_RRELU          # noqa: F401 (re-exported)
+
+
+def trainer_seed(seed: int, rank: int = 0) -> int:
+    """The seed a trainer's kernels see: the caller's seed moved by a golden-ratio multiple of (rank + 1), so ranks draw apart."""
+    return (int(seed) + 0x9E3779B97F4A7C15 * (rank + 1)) & 0xFFFFFFFFFFFFFFFF
+
+
+def base_stream(step: int) -> int:
+    """First stream id of optimisation step `step`, as a uint32 (what nsd_*_dev form from the device step counter)."""
+    return (int(step) & 0x3FFFFFFF) * 4
+
+
+def step_rng(seed: int, step: int, p_lstm: float = 0.0, p_head: float = 0.0) -> dict:
+    """The rng= / rngs= argument of the ops for step `step` of `seed`."""
+    return dict(seed=seed, base_stream=base_stream(step), p_lstm=p_lstm, p_head=p_head)
+
+
+class StepRecipe:
+    """What a trainer does to a batch before the step's kernels, and with which streams.  `model`: an EEG_LSTM (spec, dropout_p,
+    head_dropout_p, normalize).  augment / loss are the EFFECTIVE ones: augmentation and mixup belong to the stochastic parts, so
+    stochastic=False strips them (smoothing and class weights, which draw nothing, stay); None -- also for an Augment / Loss with every
+    part off -- is the plain step, launch for launch."""
+
+    def __init__(self, model, stochastic: bool, augment: Optional[ops.Augment], loss: Optional[ops.Loss], device):
+        self.spec, self.stochastic, self.normalize = model.spec, stochastic, model.normalize
+        self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
+        self.augment = augment if augment is not None and augment.enabled and stochastic else None
+        if loss is not None and loss.mixup and not stochastic:
+            loss = ops.Loss(label_smoothing=loss.label_smoothing, class_weights=loss.class_weights)
+        on = loss is not None and loss.enabled
+        if on:
+            loss.check_classes(self.spec.K)
+        self.loss, self.class_weights = (loss, loss.weights_tensor(device)) if on else (None, None)
+
+    def rng(self, seed: int, step: int) -> Optional[dict]:
+        """The in-kernel streams of the step (None for a deterministic trainer)."""
+        return step_rng(seed, step, self.p_lstm, self.p_head) if self.stochastic else None
+
+    def static_buffers(self, x: torch.Tensor) -> dict:
+        """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""
+        buf = {}
+        if self.normalize or self.augment is not None:
+            buf["xn"] = torch.empty_like(x)
+        if self.loss is not None:
+            buf["tg"] = torch.empty((x.shape[0], self.spec.K), dtype=torch.float32, device=x.device)
+            buf["xm"] = torch.empty_like(x) if self.loss.mixup > 0 else None
+        return buf
+
+    def prepare(self, x: torch.Tensor, y: torch.Tensor, seeds: Sequence[int], step: int, *, M: int = 1,
+                step_dev: Optional[torch.Tensor] = None, bufs: Optional[dict] = None):
+        """(windows, labels, targets) of step `step`: exactly one of labels / targets is None.  x [B,T,C] (one model, or shared by M)
+        or [M,B,T,C]; y int32 labels [M*B], or float32 target rows that are used as they are; seeds: one per model.
+        Launches nsd_augment (with the z-score fused behind it; without augmentation nsd_zscore_fwd, or nothing), then with loss=
+        nsd_mixup on the windows the model would otherwise see (mixup off: it only builds the target rows).  An empty shard launches
+        nothing.  step_dev (device step counter, with bufs = the trainer's static buffers): the stream ids come from the counter and
+        the outputs go to bufs' xn / xm / tg."""
+        bufs = bufs or {}
+        x = x.contiguous().float()
+        B, T, Cc = x.shape[-3:]
+        if B == 0:
+            return (x, None, y) if y.is_floating_point() else (x, y, None)
+        if self.augment is not None or self.loss is not None:
+            rngs = [step_rng(s, 0 if step_dev is not None else step) for s in seeds]
+        if self.augment is not None:       # a shared [B,T,C] becomes [M,B,T,C], each model with its own draws
+            x = ops.augment(x, self.augment, rngs, M=M, zscore=self.normalize, step_dev=step_dev, out=bufs.get("xn"))
+        elif self.normalize:               # as EEG_LSTM.forward: the model is trained on what it is evaluated on
+            x = ops.zscore(x.reshape(-1, T, Cc), out=bufs.get("xn")).view(x.shape)
+        if y.is_floating_point() or self.loss is None:
+            return (x, None, y) if y.is_floating_point() else (x, y, None)
+        lo = self.loss
+        xm, tg = ops.mixup(x if lo.mixup > 0 else None, y, self.spec.K, rngs, M=M, label_smoothing=lo.label_smoothing, mix=lo.mixup,
+                           class_weights=self.class_weights, step_dev=step_dev, out=bufs.get("xm"), targets=bufs.get("tg"))
+        return (xm if lo.mixup > 0 else x), None, tg

@@ -9,7 +9,8 @@ Per step and per GPU the stream sees, for the reference model's shape, three lau
 pooling + head + CE + head backward (nsd_lstm_head_train_rng, the dropout / RReLU streams drawn in the kernel), BPTT
 (nsd_lstm_bwd_rng), slab reduction + Adam (nsd_grad_reduce_adam); with more than one rank the last becomes
 nsd_grad_reduce -> ONE all-reduce of the flat fp32 gradient over RCCL -> nsd_adam_step.  Other shapes run the unfused
-equivalents (ops.train_step_grads).  Nothing synchronises the host.
+equivalents (ops.train_step_grads).  Nothing synchronises the host.  What the kernels see of (windows, labels, seed, step) and the
+step's four random-stream slots are defined in one place, step_recipe.py, for this trainer's eager and hipGraph steps and ModelBatchTrainer.
 
 Data parallelism: trials are independent, so the global batch is split contiguously over ranks
 (shard_range; shards may differ by one trial and may be EMPTY); every rank scales its CE gradient by 1/B_global, the flat
@@ -29,6 +30,7 @@ import torch.distributed as dist
 
 from . import ops
 from .lstm_eeg_model import EEG_LSTM
+from .step_recipe import StepRecipe, base_stream, trainer_seed
 
 
 def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
@@ -114,24 +116,13 @@ class Trainer:
         broadcast_parameters(self.flat, group)     # identical replicas by construction, not by seeding
         self.fused_head = True           # nsd_lstm_head_train (one launch) where the shape allows; False: two launches
         self.in_kernel_rng = True        # dropout / RReLU streams generated inside the kernels where the shape allows
-        self.seed = (int(seed) + 0x9E3779B97F4A7C15 * (self.rank + 1)) & 0xFFFFFFFFFFFFFFFF
+        self.seed = trainer_seed(seed, self.rank)
         self.stochastic = stochastic
-        # trial augmentation (ops.Augment; stream 4 * step + 3 of this rank's seed): training steps only, and only with the other
-        # stochastic parts on.  None -- also for an Augment with every operation off -- is the unaugmented step, launch for launch.
-        self.augment = augment if augment is not None and augment.enabled and stochastic else None
-        # soft targets (ops.Loss: label smoothing, class weights, mixup): per training step nsd_augment (if any, with its z-score) ->
-        # nsd_mixup -> the step with targets, so the mixing acts on the windows the model would otherwise see; each rank mixes inside
-        # its own shard with its own seed (stream 4 * step + 3, index slots the augmentation does not use).  The scale stays
-        # 1 / global_batch (torch's weighted `mean` would divide by the weight sum instead).  Like the augmentation, the mixing belongs to
-        # the stochastic parts: with stochastic=False nothing is mixed (smoothing and class weights, which draw nothing, stay).  None --
-        # also for a Loss with every part off -- is the hard-label step, launch for launch.
-        if loss is not None and loss.mixup and not stochastic:
-            loss = ops.Loss(label_smoothing=loss.label_smoothing, class_weights=loss.class_weights)
-        if loss is not None and loss.enabled:
-            loss.check_classes(self.spec.K)
-            self.loss, self._class_w = loss, loss.weights_tensor(self.flat.device)
-        else:
-            self.loss, self._class_w = None, None
+        # what a step does to (windows, labels) before its kernels: step_recipe.py, shared with step_static and ModelBatchTrainer.
+        # Each rank augments / mixes inside its own shard with its own seed; the scale stays 1 / global_batch (torch's weighted
+        # `mean` divides by the weight sum).
+        self.recipe = StepRecipe(model, stochastic, augment, loss, self.flat.device)
+        self.augment, self.loss = self.recipe.augment, self.recipe.loss          # the effective ones (None: off)
         self.step_count = 0
         self._bufs = {}
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.flat.device)
@@ -147,7 +138,7 @@ class Trainer:
         if key not in self._bufs:
             sp, dev = self.spec, self.flat.device
             buf = {"ws": ops.new_workspace(sp, B, T, dev),
-                   "logits": torch.empty((B, sp.K), dtype=torch.float32, device=dev)}
+                   "logits": torch.empty((B, sp.K), dtype=torch.float32, device=dev), "rng_ok": ops.rng_path(sp, B, T)}
             if self.stochastic:
                 if self.model.dropout_p > 0 and sp.L > 1:
                     buf["drop_lstm"] = torch.empty((sp.L - 1, B, T, sp.H), dtype=torch.float32, device=dev)
@@ -192,35 +183,19 @@ class Trainer:
         # bf16 path: skipped on the device when any rank's scan timed out (self._skip, summed over ranks by the all-reduce)
         ops.adam_step(self.flat, self.grads, self.m, self.v, skip=self._skip if self.model.precision == "bf16" else None, **self._hyper())
 
-    def _prepare_input(self, x: torch.Tensor) -> torch.Tensor:
-        """What EEG_LSTM.forward does to a window before the LSTM (lstm_eeg_model.py facade): contiguous fp32 and, for
-        normalize=True, the per-channel z-score -- the model must be trained on what it is evaluated on.  With augmentation on, ONE
-        nsd_augment launch does both (it takes the z-score launch's place)."""
-        x = x.contiguous().float()
-        if self.augment is not None and x.shape[0] > 0:
-            return ops.augment(x, self.augment, dict(seed=self.seed, base_stream=(self.step_count & 0x3FFFFFFF) * 4),
-                               zscore=self.model.normalize)
-        return ops.zscore(x) if self.model.normalize and x.shape[0] > 0 else x
-
-    def _targets(self, x: torch.Tensor, y: torch.Tensor):
-        """(windows, labels, targets) of the step: caller-made float targets as they are; with loss= the nsd_mixup launch on the prepared
-        windows (mixup off: it only builds the target rows and the windows stay where they are); else the hard labels."""
-        if y.is_floating_point():
-            return x, None, y
-        if self.loss is None:
-            return x, y, None
-        lo = self.loss
-        xm, tg = ops.mixup(x if lo.mixup > 0 else None, y, self.spec.K, dict(seed=self.seed, base_stream=(self.step_count & 0x3FFFFFFF) * 4),
-                           label_smoothing=lo.label_smoothing, mix=lo.mixup, class_weights=self._class_w)
-        return (xm if lo.mixup > 0 else x), None, tg
+    def _masks(self, buf: dict, step_dev: Optional[torch.Tensor] = None):
+        """Fill the step's explicit mask tensors (those the model needs) from its streams -> (drop_lstm, rrelu, drop_head)."""
+        masks = (buf.get("drop_lstm"), buf.get("rrelu"), buf.get("drop_head"))
+        stream = base_stream(self.step_count) if step_dev is None else step_dev      # graph step: the device counter alone
+        ops.train_masks(self.seed, stream, self.recipe.p_lstm, self.recipe.p_head, *masks)
+        return masks
 
     def _local_grads(self, x: torch.Tensor, y: torch.Tensor, scale: float, fuse_adam: bool = False) -> None:
         """Launches that leave this shard's gradient (scaled) in self.grads; fuse_adam: the update rides in the last one."""
-        from . import _lib
         sp = self.spec
         B, T, _ = x.shape
-        x = self._prepare_input(x)
-        x, y, tg = self._targets(x, y)
+        x, y, tg = self.recipe.prepare(x, y, [self.seed], self.step_count)
+        rng = self.recipe.rng(self.seed, self.step_count)
         if self.model.precision == "bf16":
             # sequence-batched path: forward (+ head, CE, head backward), backward (+ all parameter gradients), Adam
             key = ("seq", B, T)
@@ -238,10 +213,6 @@ class Trainer:
                 self._bufs = {key: {"ws": ops.seq_workspace(sp, B, T, self.flat.device),
                                     "logits": torch.empty((B, sp.K), dtype=torch.float32, device=self.flat.device)}}
             buf = self._bufs[key]
-            rng = None
-            if self.stochastic:
-                rng = dict(seed=self.seed, base_stream=(self.step_count & 0x3FFFFFFF) * 4, p_lstm=self.model.dropout_p,
-                           p_head=self.model.head_dropout_p)
             ops.seq_train_fwd(sp, self.flat, x, y, buf["ws"], rng=rng, scale=scale, logits=buf["logits"], targets=tg)
             ops.seq_train_bwd(sp, self.flat, buf["ws"], B, T, rng=rng, grads=self.grads)
             ops.seq_guard(buf["ws"], self._skip)
@@ -251,27 +222,10 @@ class Trainer:
                 self._adam()
             return
         buf = self._buffers(B, T)
-        L = _lib.lib()
-        st = torch.cuda.current_stream().cuda_stream
-        sid = (self.step_count & 0x3FFFFFFF) * 4
-        dl = buf.get("drop_lstm"); sl = buf.get("rrelu"); dh = buf.get("drop_head")
-        rng = None
-        if "rng_ok" not in buf:
-            buf["rng_ok"] = ops.rng_path(sp, B, T)
-        if self.in_kernel_rng and dl is not None and sl is not None and dh is not None and buf["rng_ok"]:
-            # the three streams of the step are generated inside the LSTM kernels (same values as nsd_train_masks)
-            rng = dict(seed=self.seed, base_stream=sid, p_lstm=self.model.dropout_p, p_head=self.model.head_dropout_p)
-            dl = sl = dh = None
-        elif dl is not None and sl is not None and dh is not None:
-            _lib.check(L.nsd_train_masks(self.seed, sid, self.model.dropout_p, self.model.head_dropout_p, dl.numel(),
-                                         dl.data_ptr(), sl.numel(), sl.data_ptr(), dh.data_ptr(), st), "train_masks")
+        if self.in_kernel_rng and buf["rng_ok"] and all(k in buf for k in ("drop_lstm", "rrelu", "drop_head")):
+            dl = sl = dh = None        # the three streams of the step are generated inside the LSTM kernels (same values as nsd_train_masks)
         else:
-            if dl is not None:
-                _lib.check(L.nsd_dropout_mask(self.seed, sid, self.model.dropout_p, dl.numel(), dl.data_ptr(), st), "dropout_mask")
-            if sl is not None:
-                _lib.check(L.nsd_rrelu_noise(self.seed, sid + 1, sl.numel(), sl.data_ptr(), st), "rrelu_noise")
-            if dh is not None:
-                _lib.check(L.nsd_dropout_mask(self.seed, sid + 2, self.model.head_dropout_p, dh.numel(), dh.data_ptr(), st), "dropout_mask")
+            (dl, sl, dh), rng = self._masks(buf), None
         ops.train_step_grads(sp, self.flat, x, buf["ws"], y, buf["logits"], self.grads, scale=scale, drop_lstm=dl,
                              rrelu_slope=sl, drop_head=dh, residual=self.model.residual, fused_head=self.fused_head, rng=rng,
                              adam=dict(m=self.m, v=self.v, **self._hyper()) if fuse_adam else None, targets=tg)
@@ -289,50 +243,24 @@ class Trainer:
             dev = self.flat.device
             buf["x"] = torch.zeros((B, T, self.spec.C), dtype=torch.float32, device=dev)
             buf["y"] = torch.zeros((B,), dtype=torch.int32, device=dev)
+            buf.update(self.recipe.static_buffers(buf["x"]))       # xn / xm / tg: what the step makes of x and y
         return buf["x"], buf["y"]
 
     def _issue_segment_a(self, B: int, T: int) -> None:
         """step counter, random streams, lstm fwd, fused head, lstm bwd, slab reduce -> self.grads"""
-        from . import _lib
-        L = _lib.lib()
         buf = self._buffers(B, T)
-        st = torch.cuda.current_stream().cuda_stream
-        dl = buf.get("drop_lstm"); sl = buf.get("rrelu"); dh = buf.get("drop_head")
-        _lib.check(L.nsd_step_counter_inc(self._step_dev.data_ptr(), st), "step_counter_inc")
-        if dl is not None and sl is not None and dh is not None:
-            _lib.check(L.nsd_train_masks_dev(self.seed, self._step_dev.data_ptr(), self.model.dropout_p, self.model.head_dropout_p,
-                                             dl.numel(), dl.data_ptr(), sl.numel(), sl.data_ptr(), dh.data_ptr(), st), "train_masks_dev")
-        elif self.stochastic:
+        ops.step_counter_inc(self._step_dev)
+        if self.stochastic and not all(k in buf for k in ("drop_lstm", "rrelu", "drop_head")):
             raise ops.NsdError("graph step needs all three random streams (dropout > 0, num_layers > 1) or stochastic=False")
-        xin = buf["x"]
-        if self.model.normalize or self.augment is not None:   # a static buffer of its own: nothing is allocated inside the capture
-            if "xn" not in buf:
-                buf["xn"] = torch.empty_like(buf["x"])
-            if self.augment is not None:                       # the stream id comes from the device step counter: the graph replays it
-                xin = ops.augment(buf["x"], self.augment, dict(seed=self.seed, base_stream=0), zscore=self.model.normalize,
-                                  step_dev=self._step_dev, out=buf["xn"])
-            else:
-                xin = ops.zscore(buf["x"], out=buf["xn"])
-        tg = None
-        if self.loss is not None:                              # static buffers again; the stream id comes from the device step counter
-            lo = self.loss
-            if "tg" not in buf:
-                buf["tg"] = torch.empty((B, self.spec.K), dtype=torch.float32, device=self.flat.device)
-                buf["xm"] = torch.empty_like(buf["x"]) if lo.mixup > 0 else None
-            xm, tg = ops.mixup(xin if lo.mixup > 0 else None, buf["y"], self.spec.K, dict(seed=self.seed, base_stream=0),
-                               label_smoothing=lo.label_smoothing, mix=lo.mixup, class_weights=self._class_w, step_dev=self._step_dev,
-                               out=buf["xm"], targets=buf["tg"])
-            xin = xm if lo.mixup > 0 else xin
-        ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], buf["y"], buf["logits"], self.grads,
+        dl, sl, dh = self._masks(buf, step_dev=self._step_dev)
+        # static buffers throughout, and every stream id from the device step counter: the graph replays it
+        xin, y, tg = self.recipe.prepare(buf["x"], buf["y"], [self.seed], 0, step_dev=self._step_dev, bufs=buf)
+        ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], y, buf["logits"], self.grads,
                              scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual,
                              targets=tg)
 
     def _issue_segment_b(self) -> None:
-        from . import _lib
-        st = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().nsd_adam_step_dev(self.flat.numel(), self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                                                self.v.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                self.weight_decay, 1.0, self._step_dev.data_ptr(), st), "adam_step_dev")
+        ops.adam_step(self.flat, self.grads, self.m, self.v, step_dev=self._step_dev, **self._hyper())
 
     @_on_own_device
     def step_static(self, B: int, T: int) -> None:

@@ -508,3 +508,28 @@ def test_loss_off_is_the_parents_step(nsd, dev, normalize):
         assert names == mbase and torch.equal(p, mp), kw
     mon, _ = run_multi(loss=nsd.Loss(mixup=0.5))
     assert mon.count("nsd_mixup") == 3 and mon.count("nsd_multi_train_fwd_soft") == 3 and len(mon) == len(mbase) + 3
+
+
+def test_explicit_mask_step_equals_in_kernel_streams_with_augmentation_and_loss(nsd, dev):
+    """Trainer.in_kernel_rng = False (explicit mask tensors, filled through ops.train_masks) against True, both with augmentation and
+    loss= on, three steps: parameters, Adam moments, gradients and loss bitwise equal.  The kernels promise the identity
+    (test_gpu_parity.py::test_in_kernel_random_streams_equal_explicit_masks); this holds the trainer's plumbing around them to it."""
+    from nsd_amd.trainer import Trainer
+    A = nsd.Augment(max_shift=3, scale_range=0.1, p_channel=0.2, noise_std=0.3)
+    Ls = nsd.Loss(label_smoothing=0.1, mixup=0.5)
+    ta, tb = (Trainer(_model(nsd, dev, 11), lr=1e-3, seed=9, augment=A, loss=Ls) for _ in range(2))
+    tb.in_kernel_rng = False
+    # model m of the model-batched trainer carries the seed of Trainer(model_m, seed=seeds[m]) on rank 0
+    from nsd_amd.step_recipe import trainer_seed
+    seeds = [3, 2**64 - 1]
+    mbt = nsd.ModelBatchTrainer([_model(nsd, dev, 100 + m) for m in range(2)], seeds=seeds)
+    assert mbt.seeds == [trainer_seed(s, 0) for s in seeds] == [Trainer(_model(nsd, dev, 1), seed=s).seed for s in seeds]
+    for step in range(1, 4):
+        x, y = _batch(dev, 32, 40, seed=step)
+        names = [_launches(t, x, y, steps=1) for t in (ta, tb)]
+        assert "nsd_train_masks" not in names[0] and names[1].count("nsd_train_masks") == 1, step
+        assert [n for n in names[1] if n != "nsd_train_masks"][:2] == ["nsd_augment", "nsd_mixup"] == names[0][:2], step
+        for a, b in ((ta.flat, tb.flat), (ta.m, tb.m), (ta.v, tb.v), (ta.grads, tb.grads)):
+            assert torch.equal(a, b), step
+        assert ta.last_loss() == tb.last_loss(), step
+    assert not torch.equal(ta.flat, _model(nsd, dev, 11).flat_parameters())
