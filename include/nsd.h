@@ -19,6 +19,11 @@
  *     unless stated) valid on the current HIP device; the library allocates
  *     nothing and never synchronises: work is enqueued on `stream`
  *     (a hipStream_t passed as void*; NULL = the legacy default stream).
+ *   - buffer contents before a call are never read unless documented (an output, a workspace or a scratch buffer may hold
+ *     arbitrary bytes, NaN patterns and the leftovers of another shape included; a training workspace carries one
+ *     evaluation from its forward call to the calls that follow it, and the sequence workspace keeps its header), nothing
+ *     outside the stated extents is written (a workspace or scratch buffer of exactly the size its *_bytes function returns
+ *     is enough), inputs are never written.
  *   - re-entrant per stream; kernels are deterministic (no float atomics).
  *   - shapes: B trials, T time steps, C channels, H hidden, L layers,
  *     K classes, F = width of the first dense layer (32 in the reference).
@@ -427,7 +432,10 @@ int nsd_gemm_bf16(const void *A, int64_t lda, int32_t a_kmajor, const void *B, i
  * that cannot assemble gives up after ~1-2 s).  A time-out is never silent:
  *   - the workspace starts with a persistent header whose first word is a STICKY status (OR of every time-out code; bit 0 a
  *     forward, bit 1 a backward scan).  nsd_seq_workspace_init zeroes it: call it once after allocating the workspace (an
- *     uninitialised header reads as a failure).  No forward / backward call ever clears it.
+ *     uninitialised header reads as a failure).  No forward / backward call ever clears it.  The header is all the workspace
+ *     needs before first use: the rest may hold arbitrary bytes, before nsd_seq_workspace_init and after it (every ring slot,
+ *     rendezvous word and padded row an evaluation reads is set by that evaluation), and a workspace that served another
+ *     shape serves the next one without a second nsd_seq_workspace_init.
  *   - logits, probs and the per-trial loss of an evaluation on a workspace that reports a time-out are NaN.
  * Non-finite values (a NaN / Inf window, NaN / Inf or diverged weights) propagate as in the reference's torch.nn.LSTM
  * (lstm_eeg_model.py:34): the logits / probs / loss of the affected trials are NaN, the other trials of the batch are

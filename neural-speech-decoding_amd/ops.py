@@ -422,23 +422,46 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     return out, targets
 
 
-def infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, *, residual: bool = False,
-          want_probs: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Eval-mode forward: logits [B,K] (+ softmax probabilities)."""
+def _out_f32(out: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
+    """The caller's output buffer (element count checked; dtype, device and contiguity by _dev_f32 at the launch), or a fresh one"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    n = 1
+    for v in shape:
+        n *= int(v)
+    if out.numel() != n:
+        raise NsdError(f"{what}: the output buffer has {out.numel()} elements for {tuple(shape)}")
+    return out
+
+
+def _scratch_ptr(scratch: Optional[torch.Tensor], nbytes: int, device, what: str):
+    """(tensor kept alive, device pointer) of an inference scratch: the caller's (at least nbytes long) or a fresh one"""
+    if scratch is None:
+        scratch = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device)
+    elif not scratch.is_cuda or not scratch.is_contiguous() or _nbytes(scratch) < nbytes:
+        raise NsdError(f"{what}: scratch must be a contiguous device buffer of at least {nbytes} bytes")
+    return scratch, scratch.data_ptr()
+
+
+def infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, *, residual: bool = False, want_probs: bool = True,
+          logits: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None,
+          scratch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Eval-mode forward: logits [B,K] (+ softmax probabilities).  logits / probs / scratch: optional caller-owned buffers (scratch: at
+    least nsd_infer_scratch_bytes long, any dtype)."""
     B, T, Cc = x.shape
     if Cc != spec.C:
         raise NsdError(f"x has {Cc} channels, model expects {spec.C}")
     d = spec.dims(B, T)
-    logits = torch.empty((B, spec.K), dtype=torch.float32, device=x.device)
-    probs = torch.empty_like(logits) if want_probs else None
+    logits = _out_f32(logits, (B, spec.K), x.device, "infer: logits")
+    probs = _out_f32(probs, (B, spec.K), x.device, "infer: probs") if want_probs else None
     if B == 0:                      # empty batch: nothing to launch (empty tensors have no device pointer)
         _dev_f32(flat, "params", (spec.param_count,)); _dev_f32(x, "x")
         return logits, probs
     nscr = _lib.lib().nsd_infer_scratch_bytes(C.byref(d))
-    scratch = torch.empty(max(int(nscr) // 4, 1), dtype=torch.float32, device=x.device)
+    scratch, scrp = _scratch_ptr(scratch, int(nscr), x.device, "infer")
     _call("nsd_infer", x.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _dev_f32(x, "x"),
           (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags, _dev_f32(logits, "logits"),
-          _dev_f32(probs, "probs"), scratch.data_ptr(), STREAM)
+          _dev_f32(probs, "probs"), scrp, STREAM)
     return logits, probs
 
 
@@ -636,11 +659,11 @@ def rrelu_noise(seed: int, stream_id: int, shape, device) -> torch.Tensor:
 
 # ---- sequence-batched path (large hidden sizes): building blocks ---------------------------------------------------------
 def gemm_bf16(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool = False, b_kmajor: bool = False, b_shift: int = 0,
-              epilogue: int = 0, bias: Optional[torch.Tensor] = None, splits: int = 1) -> torch.Tensor:
+              epilogue: int = 0, bias: Optional[torch.Tensor] = None, splits: int = 1, c: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C[M,N] = A . B on the matrix pipe (nsd_gemm_bf16): bf16 device tensors, fp32 accumulate.
     a: [M,K] (or [K,M] when a_kmajor), b: [N,K] (or [K,N] when b_kmajor).  epilogue 0 -> fp32 [splits,M,N] summed here when
     splits > 1; 1 -> bf16 [M,N]; 2 -> bf16 accumulator tiles [N/32, M/32, 64, 16] (+ bias[m]); 3 -> the same tiles, register group
-    first: [N/32, M/32, 4, 64, 4]."""
+    first: [N/32, M/32, 4, 64, 4].  c: optional caller-owned output of exactly that many elements of that dtype."""
     for t, n in ((a, "a"), (b, "b")):
         if not t.is_cuda or t.dtype != torch.bfloat16 or not t.is_contiguous():
             raise NsdError(f"gemm_bf16: {n} must be a contiguous bf16 tensor on the MI355X")
@@ -649,14 +672,12 @@ def gemm_bf16(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool = False, b_kma
     if K != Kb:
         raise NsdError(f"gemm_bf16: K mismatch {K} vs {Kb}")
     dev = a.device
-    if epilogue == 0:
-        c = torch.empty((max(splits, 1), M, N), dtype=torch.float32, device=dev)
-    elif epilogue == 1:
-        c = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
-    elif epilogue == 2:
-        c = torch.empty((N // 32, M // 32, 64, 16), dtype=torch.bfloat16, device=dev)
-    else:
-        c = torch.empty((N // 32, M // 32, 4, 64, 4), dtype=torch.bfloat16, device=dev)
+    cshape = {0: (max(splits, 1), M, N), 1: (M, N), 2: (N // 32, M // 32, 64, 16)}.get(epilogue, (N // 32, M // 32, 4, 64, 4))
+    cdtype = torch.float32 if epilogue == 0 else torch.bfloat16
+    if c is None:
+        c = torch.empty(cshape, dtype=cdtype, device=dev)
+    elif not c.is_cuda or c.dtype != cdtype or not c.is_contiguous() or tuple(c.shape) != cshape:
+        raise NsdError(f"gemm_bf16: c must be a contiguous {cdtype} device tensor of shape {cshape}")
     _call("nsd_gemm_bf16", dev, a.data_ptr(), a.shape[1], int(a_kmajor), b.data_ptr(), b.shape[1], int(b_kmajor), int(b_shift),
           c.data_ptr(), N, int(epilogue), _dev_f32(bias, "bias", (M,)), M, N, K, int(splits), STREAM)
     if epilogue == 0:
@@ -713,14 +734,14 @@ def seq_raise_on_timeout(ws: torch.Tensor, what: str, nonfinite: bool = False) -
                        "are invalid (NaN logits / loss, the guarded Adam update was skipped); allocate a fresh workspace to go on")
 
 
-def seq_infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: Optional[torch.Tensor] = None, *,
-              want_probs: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+def seq_infer(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: Optional[torch.Tensor] = None, *, want_probs: bool = True,
+              logits: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     B, T, Cc = x.shape
     if Cc != spec.C:
         raise NsdError(f"x has {Cc} channels, model expects {spec.C}")
     d = spec.dims(B, T)
-    logits = torch.empty((B, spec.K), dtype=torch.float32, device=x.device)
-    probs = torch.empty_like(logits) if want_probs else None
+    logits = _out_f32(logits, (B, spec.K), x.device, "seq_infer: logits")
+    probs = _out_f32(probs, (B, spec.K), x.device, "seq_infer: probs") if want_probs else None
     if B == 0:
         return logits, probs
     ws = seq_workspace(spec, B, T, x.device) if ws is None else ws
@@ -880,20 +901,21 @@ def multi_loss_sum(spec: ModelSpec, ws: torch.Tensor, M: int, B: int, T: int, ou
     return out
 
 
-def multi_infer(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, *, want_probs: bool = True
-                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Eval-mode forward of M models in one launch: params [M,P], x [M,B,T,C] or shared [B,T,C] -> logits [M,B,K] (+ probs)."""
+def multi_infer(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, *, want_probs: bool = True, logits: Optional[torch.Tensor] = None,
+                probs: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Eval-mode forward of M models in one launch: params [M,P], x [M,B,T,C] or shared [B,T,C] -> logits [M,B,K] (+ probs).
+    logits / probs / scratch: optional caller-owned buffers (scratch: at least nsd_multi_infer_scratch_bytes long, any dtype)."""
     M = int(params.shape[0])
     B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
-    logits = torch.empty((M, B, spec.K), dtype=torch.float32, device=params.device)
-    probs = torch.empty_like(logits) if want_probs else None
+    logits = _out_f32(logits, (M, B, spec.K), params.device, "multi_infer: logits")
+    probs = _out_f32(probs, (M, B, spec.K), params.device, "multi_infer: probs") if want_probs else None
     if B == 0:
         return logits, probs
     nscr = int(_lib.lib().nsd_multi_infer_scratch_bytes(C.byref(d), M))
     if nscr < 0:
         check(nscr, "nsd_multi_infer_scratch_bytes")
-    scratch = torch.empty(max(nscr // 4, 1), dtype=torch.float32, device=params.device)
+    scratch, scrp = _scratch_ptr(scratch, nscr, params.device, "multi_infer")
     _call("nsd_multi_infer", params.device, C.byref(d), M, _dev_f32(params, "params", (M, spec.param_count)), _dev_f32(x, "x"), stride,
-          0, _dev_f32(logits, "logits"), _dev_f32(probs, "probs"), scratch.data_ptr(), STREAM)
+          0, _dev_f32(logits, "logits"), _dev_f32(probs, "probs"), scrp, STREAM)
     return logits, probs
