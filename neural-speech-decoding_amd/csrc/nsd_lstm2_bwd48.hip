@@ -17,7 +17,7 @@
 //                 v_mfma_f32_32x32x16_bf16, K = 16 macro steps per instruction (dw16_role): 180 matrix-pipe cycles per step instead of
 //                 864 for the fp32 form; waves 0..3 also bring the saved rows (four steps per request), waves 4, 5 convert da.
 //   "loader"      LDS-DMA stream of the saved activations, one 8-step chunk ahead; the factors of a trial's first step.
-//   Roles are placed by SIMD (wave & 3), priorities follow the measured critical waves (kernel body).
+//   Roles are placed by SIMD (wave & 3), priorities follow the measured critical waves (the role table in front of the kernels).
 // TWO trials per workgroup (NB = 2, batches of 257 .. 575 trials): the first-generation roles -- per-gate-lane factors in the chains,
 // x1 step by step on the VALU with dW_ih0, weight gradients as v_mfma_f32_16x16x4_f32 with K = 4 time steps (dw_role).
 //
@@ -32,13 +32,18 @@
 
 namespace {
 
-#ifndef NSD_B48_X1M
-#define NSD_B48_X1M 1             // one trial per workgroup: the hand-off d_in1 = W_ih1^T da1 as v_mfma_f32_4x4x1 over FOUR steps at a time (layer 0 runs 5 macro steps behind layer 1 instead of 2)
-#endif
 constexpr int H = 48;
 constexpr int G4 = 192;
-// macro steps layer 0 runs behind layer 1, minus the 2 of the step-by-step hand-off
-constexpr int dl0(const int nb) { return (nb == 1 && NSD_B48_X1M) ? 3 : 0; }
+// macro steps layer 0 runs behind layer 1, minus the 2 of the step-by-step hand-off.  One trial per workgroup: the hand-off d_in1 =
+// W_ih1^T da1 is a v_mfma_f32_4x4x1 over FOUR steps at a time (x1m_role), so layer 0 runs 5 macro steps behind layer 1 instead of 2.
+// The step-by-step hand-off at one trial per workgroup measured 128.2-128.9 us against 125.1-125.3 (profiles/r04_split_bf16.md) and is
+// gone from the source, like the one-trial placement by wave index (129.4-129.9 us placed by SIMD against 130.5-131.0, same note) and the
+// build switch that made dw16_role a call (DESIGN 4.2 names the commit that last had them).
+constexpr int dl0(const int nb) { return nb == 1 ? 3 : 0; }
+// Issue priorities.  One trial per workgroup: the x1 waves above the recurrences -- the prepared factors moved the critical wave to x1 +
+// prep (the other order: 136-137 us against 128.2-128.9; all three roles at one priority: not kept; profiles/r04_split_bf16.md).
+// Two trials per workgroup (first-generation roles): the critical path as it reads, the two recurrences first, then the hand-off to layer 0.
+constexpr int PRIO1_CHAIN = 2, PRIO1_X1 = 3, PRIO2_CHAIN = 3, PRIO2_X1 = 2, PRIO_LOADER = 1;
 constexpr int RING = 8;
 constexpr int NTHREADS = 1024;
 #ifndef NSD_DW_SLEEP
@@ -76,7 +81,7 @@ struct NoWin {};
 template <int NB>
 struct Smem {
     float ring[2][RING][NB][G4];           // [layer][macro step % RING][trial][gate*48+unit]
-    float din1[2][NB][H];
+    float din1[2][NB][H];                  // (two trials per workgroup only: the step-by-step hand-off.  Smem<1> keeps it unread -- the LDS layout is part of the kernel's code)
     float stage[2][NB][2][CHUNK][REC];     // [buffer][trial][layer][step in chunk][record]  (linear per trial)
     float xst[2][NB][CHUNK][8];            // (two trials per workgroup only) x[T+2-m] rows for the x1 waves (dW_ih0), same chunking
     typename std::conditional<NB == 1, DwWin, NoWin>::type win;
@@ -204,7 +209,7 @@ __device__ __forceinline__ void chain_role(const A &a, Smem<NB> &sm, const int l
                     const float *pfl = &sm.win.pf[k & 1][layer][j][0];
                     const float4 pf = *reinterpret_cast<const float4 *>(pfl);
                     const float qr = pfl[4 + s];
-                    const float dout = layer == 1 ? pf.z : (NSD_B48_X1M ? sm.win.din1x[(k + 6 - dl0(NB)) & 7][j] : sm.din1[(k + 1) & 1][0][j]) * pf.z;
+                    const float dout = layer == 1 ? pf.z : sm.win.din1x[(k + 6 - dl0(NB)) & 7][j] * pf.z;
                     if (prev_active) dhrec[0] = slice_dot_t(&sm.ring[layer][(k + RING - 1) & (RING - 1)][0][12 * kk], wp);
                     if (active) {
                         const float dht = dout + dhrec[0];
@@ -260,10 +265,11 @@ __device__ __forceinline__ void chain_role(const A &a, Smem<NB> &sm, const int l
 }
 
 // ------------------------------------------------------------------------------------------------
-// x1 waves: d_in1[t] = W_ih1^T da1[t] (+ residual pass-through) for layer 0, and dW_ih0 (K = C <= 8)
+// x1 waves, TWO trials per workgroup: d_in1[t] = W_ih1^T da1[t] (+ residual pass-through) for layer 0, and dW_ih0 (K = C <= 8)
 // ------------------------------------------------------------------------------------------------
-template <int NB, class A>
-__device__ __forceinline__ void x1_role(const A &a, Smem<NB> &sm, const int r, const int n_steps) {
+template <class A>
+__device__ __forceinline__ void x1_role(const A &a, Smem<2> &sm, const int r, const int n_steps) {
+    constexpr int NB = 2;
     const int og = r >> 4, kk = r & 15;
     const int j = 4 * og + (r & 3), s = (r >> 2) & 3;        // s: which copy of unit j this lane is (dW_ih0 channel pair)
     const int T = a.T, B = a.B, C = a.C;
@@ -282,14 +288,11 @@ __device__ __forceinline__ void x1_role(const A &a, Smem<NB> &sm, const int r, c
         float dpj[NB];
 #pragma unroll
         for (int n = 0; n < NB; ++n) dpj[n] = (a.residual && b0 + n < B) ? a.dpooled[(size_t)(b0 + n) * H + j] : 0.f;
-        // prep duty (one trial per workgroup): wave 0 of the role prepares layer 1's factors of the NEXT macro step, wave 1 layer 0's
-        const int pw = r >> 6, pu = (r & 63) < H ? (r & 63) : (r & 63) - 16, pl = pw == 0 ? 1 : 0;
-        float p_dp = 0.f, p_aw = 0.f, p_c = 0.f;
-        if (NB == 1 && pw < 2) {
-            p_dp = a.dpooled[(size_t)b0 * H + pu];
-            p_aw = a.attn_w[pu];
-            p_c = (pl == 1 ? a.cseq1 : a.cseq0)[((size_t)b0 * T + (T - 1)) * H + pu];
-        }
+        // (What is left of the one-trial prep duty this role once had, and read by nothing: without this expression hipcc orders the
+        // two-trial kernel's instructions differently -- same registers, spills and length -- and the refactor that removed the duty was
+        // held to identical machine code: profiles/h48_variants_same_isa.md.  It goes with the next change that may move the kernel.)
+        const int pu = (r & 63) < H ? (r & 63) : (r & 63) - 16;
+        (void)pu;
         step_barrier<false>(prof);
 
         for (int m0 = 0; m0 < n_steps; m0 += CHUNK) {
@@ -303,10 +306,7 @@ __device__ __forceinline__ void x1_role(const A &a, Smem<NB> &sm, const int r, c
                 const int e = (k + PREV) & (RING - 1);
 #pragma unroll
                 for (int n = 0; n < NB; ++n) {
-                    float2 xv = {0.f, 0.f};
-                    if (NB == 2) xv = *reinterpret_cast<const float2 *>(&sm.xst[sb][n][k][2 * s]);
-                    PrepIn pin;
-                    if constexpr (NB == 1) { if (pw < 2) pin = prep_load(a, sm, m + 1, pl, pu, p_c); }      // (requested ahead of the mat-vec: its latency hides there)
+                    const float2 xv = *reinterpret_cast<const float2 *>(&sm.xst[sb][n][k][2 * s]);
                     if (t1p >= 0 && t1p < T) {
                         float inp = slice_dot_t(&sm.ring[1][e][n][12 * kk], wp);
                         if (a.residual && b0 + n < B) {
@@ -317,8 +317,7 @@ __device__ __forceinline__ void x1_role(const A &a, Smem<NB> &sm, const int r, c
                         }
                         if (s == 0) sm.din1[k & 1][n][j] = inp;
                     }
-                    if constexpr (NB == 1) { if (pw < 2) prep_finish(sm, pin, m + 1, pl, pu, p_dp, p_aw); }
-                    if (NB == 2 && t0p >= 0 && t0p < T && b0 + n < B) {       // (one trial per workgroup: dW_ih0 rides in the dW waves' layer-0 window)
+                    if (t0p >= 0 && t0p < T && b0 + n < B) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
                             const float d = sm.ring[0][e][n][g * H + j];
@@ -333,7 +332,6 @@ __device__ __forceinline__ void x1_role(const A &a, Smem<NB> &sm, const int r, c
     }
     prof_store(a.dbg, prof);
     float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;
-    if (NB == 2)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         if (c0 < C) slab[a.o_w_ih0 + (size_t)(g * H + j) * C + c0] = dWih0[g][0];
@@ -433,7 +431,7 @@ __device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int g, c
 }
 
 // ------------------------------------------------------------------------------------------------
-// dW waves: three [192,48] outer-product sums on the matrix pipe, K = 4 time steps per MFMA
+// dW waves, TWO trials per workgroup: three [192,48] outer-product sums on the matrix pipe, K = 4 time steps per MFMA
 // ------------------------------------------------------------------------------------------------
 template <int NB>
 struct DwState {
@@ -488,9 +486,10 @@ __device__ __forceinline__ void dw_compute(const Lstm2BwdArgs &a, Smem<NB> &sm, 
     }
 }
 
-template <int NB, class A>
-__device__ __forceinline__ void dw_role(const A &a, Smem<NB> &sm, const int dwid, const int lane,
+template <class A>
+__device__ __forceinline__ void dw_role(const A &a, Smem<2> &sm, const int dwid, const int lane,
                                         const int n_groups) {
+    constexpr int NB = 2;
     DwState<NB> st;
     Prof prof = prof_init(a.dbg);
 #pragma unroll
@@ -573,11 +572,6 @@ __device__ __forceinline__ void dw_role(const A &a, Smem<NB> &sm, const int dwid
 // The window of steps 16 W .. 16 W + 15 is complete behind the barrier of step 16 W + 16; its five tiles are taken at steps
 // 16 W + 17 .. + 21, the last window of a trial behind the loop (its da sits in the ring until the next trial's chains start).
 // ------------------------------------------------------------------------------------------------
-#ifndef NSD_DW16_NOINLINE
-#define DW16_INLINE __forceinline__
-#else
-#define DW16_INLINE __attribute__((noinline))
-#endif
 template <class F, int... I>
 __device__ __forceinline__ void static_for(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 __device__ __forceinline__ void split1_bf16(const float v, unsigned short &hi, unsigned short &lo) {
@@ -607,7 +601,7 @@ __device__ __forceinline__ void split4_bf16(const f32x4 v, u32x2 &hi, u32x2 &lo)
 // with a recurrence): waves 0..2 the rows h1[t-1] / in1[t] / h0[t-1] and wave 3 x[t], FOUR steps per request (lane = (step, 16-byte
 // piece) or (step, channel)), split and written every fourth step; waves 4, 5 the da of layer 1 / 0, every step, four columns per lane.
 template <class A>
-__device__ DW16_INLINE void dw16_role(const A &a_in, Smem<1> &sm, const int w_in, const int lane, const int n_steps_in) {
+__device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int w_in, const int lane, const int n_steps_in) {
     const int w = __builtin_amdgcn_readfirstlane(w_in), n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
     const A a = uniform_copy(a_in);
     DwWin &win = sm.win;
@@ -901,6 +895,33 @@ __device__ __forceinline__ void loader_role(const A &a, Smem<NB> &sm, const int 
     prof_store(a.dbg, prof);
 }
 
+// Role of a wave, written once for both entry points.  VIEW = the statement that forms a role's argument block `a` inside its branch
+// (empty where `a` is the kernel's parameter): each role forms the model's block itself, so that only the pointers it reads are live in it.
+// One trial per workgroup -- roles by SIMD (waves w and w + 4 share one; a SIMD's instructions per step are what bounds the step -- per-wave
+// stamps: the younger recurrence of a SIMD that carries two runs at 1 065 cycles of work against 840 -- so the SIMDs with TWO recurrences
+// get the light dW waves (rows duty), the other two the x1 waves, the da converters and the loader):
+//   SIMD 0: chain1_0 chain0_1 x1_2 dW0 | SIMD 1: chain1_1 chain0_2 dW4 dW1 | SIMD 2: chain1_2 x1_0 dW2 dW5 | SIMD 3: chain0_0 x1_1 dW3 loader
+// (ROLE: 0 chain1, 1 chain0, 2 x1, 3 dW, 4 loader; PART: which wave of the role.)
+// Two trials per workgroup -- the first-generation roles by wave index.
+#define NSD_B48_ROLE_TABLE(VIEW) \
+    if constexpr (NB == 1) { \
+        constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3, 3, 3, 4}; \
+        constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 4, 2, 3, 0, 1, 5, 0}; \
+        const int lane = tid & 63; \
+        const int role = ROLE[wave], part = PART[wave]; \
+        if (role == 0)      { VIEW; __builtin_amdgcn_s_setprio(PRIO1_CHAIN); chain_role<NB>(a, sm, 1, 64 * part + lane, n_steps); } \
+        else if (role == 1) { VIEW; __builtin_amdgcn_s_setprio(PRIO1_CHAIN); chain_role<NB>(a, sm, 0, 64 * part + lane, n_steps); } \
+        else if (role == 2) { VIEW; __builtin_amdgcn_s_setprio(PRIO1_X1); x1m_role(a, sm, part, lane, n_steps); } \
+        else if (role == 3) { VIEW; dw16_role(a, sm, part, lane, n_steps); } \
+        else                { VIEW; __builtin_amdgcn_s_setprio(PRIO_LOADER); loader_role<NB>(a, sm, lane, n_steps); } \
+    } else { \
+        if (wave < 3)       { VIEW; __builtin_amdgcn_s_setprio(PRIO2_CHAIN); chain_role<NB>(a, sm, 1, tid, n_steps); } \
+        else if (wave < 6)  { VIEW; __builtin_amdgcn_s_setprio(PRIO2_CHAIN); chain_role<NB>(a, sm, 0, tid - 192, n_steps); } \
+        else if (wave < 9)  { VIEW; __builtin_amdgcn_s_setprio(PRIO2_X1); x1_role(a, sm, tid - 384, n_steps); } \
+        else if (wave < 15) { VIEW; dw_role(a, sm, wave - 9, tid & 63, n_groups); } \
+        else                { VIEW; __builtin_amdgcn_s_setprio(PRIO_LOADER); loader_role<NB>(a, sm, tid & 63, n_steps); } \
+    }
+
 #if !NSD_MULTI_TU
 template <int NB>
 __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_kernel(Lstm2BwdArgs a) {
@@ -912,51 +933,12 @@ __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_kernel(Lstm2BwdArgs a) {
     // finish the last group after the loop, on their own.)
     const int n_groups = (((a.T + 2 + dl0(NB)) / 4 + 1) + 1) & ~1;
     const int n_steps = 4 * n_groups;
-    // issue priority follows the critical path: the two recurrences first, then the hand-off to layer 0
-    if constexpr (NB == 1) {
-#ifndef NSD_B48_MAP
-#define NSD_B48_MAP 2
-#endif
-        // Roles by SIMD (waves w and w + 4 share one; a SIMD's instructions per step are what bounds the step -- per-wave stamps:
-        // the younger recurrence of a SIMD that carries two runs at 1 065 cycles of work against 840 -- so the SIMDs with TWO
-        // recurrences get the four light dW waves (rows duty), the other two the x1 waves, the da converters and the loader):
-        //   SIMD 0: chain1_0 chain0_1 dW0 dW2 | SIMD 1: chain1_1 chain0_2 dW1 dW3 | SIMD 2: chain1_2 x1_0 x1_2 dW5 | SIMD 3: chain0_0 x1_1 dW4 loader
-#if NSD_B48_MAP == 2
-        //   SIMD 0: chain1_0 chain0_1 x1_2 dW0 | SIMD 1: chain1_1 chain0_2 dW4 dW1 | SIMD 2: chain1_2 x1_0 dW2 dW5 | SIMD 3: chain0_0 x1_1 dW3 loader
-        constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3, 3, 3, 4};
-        constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 4, 2, 3, 0, 1, 5, 0};
-#else
-        constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 2, 3, 3, 3, 3, 4};        // 0 chain1, 1 chain0, 2 x1, 3 dW, 4 loader
-        constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 0, 1, 2, 4, 2, 3, 5, 0};
-#endif
-        const int lane = tid & 63;
-        if (NSD_B48_MAP >= 1) {
-            const int role = ROLE[wave], part = PART[wave];
-#ifndef NSD_B48_PC
-#define NSD_B48_PC 2
-#endif
-#ifndef NSD_B48_PX
-#define NSD_B48_PX 3
-#endif
-            if (role == 0)      { __builtin_amdgcn_s_setprio(NSD_B48_PC); chain_role<NB>(a, sm, 1, 64 * part + lane, n_steps); }
-            else if (role == 1) { __builtin_amdgcn_s_setprio(NSD_B48_PC); chain_role<NB>(a, sm, 0, 64 * part + lane, n_steps); }
-            else if (role == 2) { __builtin_amdgcn_s_setprio(NSD_B48_PX); if (NSD_B48_X1M) x1m_role(a, sm, part, lane, n_steps); else x1_role<NB>(a, sm, 64 * part + lane, n_steps); }
-            else if (role == 3) dw16_role(a, sm, part, lane, n_steps);
-            else                { __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, lane, n_steps); }
-            return;
-        }
-    }
-    if (wave < 3)       { __builtin_amdgcn_s_setprio(3); chain_role<NB>(a, sm, 1, tid, n_steps); }
-    else if (wave < 6)  { __builtin_amdgcn_s_setprio(3); chain_role<NB>(a, sm, 0, tid - 192, n_steps); }
-    else if (wave < 9)  { __builtin_amdgcn_s_setprio(2); x1_role<NB>(a, sm, tid - 384, n_steps); }
-    else if (wave < 15) { if constexpr (NB == 1) dw16_role(a, sm, wave - 9, tid & 63, n_steps); else dw_role<NB>(a, sm, wave - 9, tid & 63, n_groups); }
-    else                { __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, tid & 63, n_steps); }
+    NSD_B48_ROLE_TABLE()
 }
 
 #else
 // M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_bwd48.hip, so that the single-model kernels' module is what it was):
-// workgroup blockIdx.x takes model blockIdx.x / s.G; the roles and their placement are those of lstm2_bwd48_kernel, each forming the
-// model's argument block itself (only the pointers it reads are live in it).
+// workgroup blockIdx.x takes model blockIdx.x / s.G
 template <int NB>
 __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_multi_kernel(Lstm2BwdArgs a_in, ModelSplit s) {
     __shared__ __align__(16) Smem<NB> sm;
@@ -964,44 +946,11 @@ __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_multi_kernel(Lstm2BwdArg
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n_groups = (((a_in.T + 2 + dl0(NB)) / 4 + 1) + 1) & ~1;
     const int n_steps = 4 * n_groups;
-#define NSD_VIEW const ModelView<Lstm2BwdArgs> a = model_view(a_in, s)
-#ifndef NSD_B48_MAP                              // (the defaults of lstm2_bwd48_kernel, which this translation unit does not compile)
-#define NSD_B48_MAP 2
-#endif
-#ifndef NSD_B48_PC
-#define NSD_B48_PC 2
-#endif
-#ifndef NSD_B48_PX
-#define NSD_B48_PX 3
-#endif
-    if constexpr (NB == 1) {
-        const int lane = tid & 63;
-        if (NSD_B48_MAP >= 1) {
-#if NSD_B48_MAP == 2
-            constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3, 3, 3, 4};
-            constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 4, 2, 3, 0, 1, 5, 0};
-#else
-            constexpr int ROLE[16] = {0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 2, 3, 3, 3, 3, 4};
-            constexpr int PART[16] = {0, 1, 2, 0, 1, 2, 0, 1, 0, 1, 2, 4, 2, 3, 5, 0};
-#endif
-            const int role = ROLE[wave], part = PART[wave];
-            if (role == 0)      { NSD_VIEW; __builtin_amdgcn_s_setprio(NSD_B48_PC); chain_role<NB>(a, sm, 1, 64 * part + lane, n_steps); }
-            else if (role == 1) { NSD_VIEW; __builtin_amdgcn_s_setprio(NSD_B48_PC); chain_role<NB>(a, sm, 0, 64 * part + lane, n_steps); }
-            else if (role == 2) { NSD_VIEW; __builtin_amdgcn_s_setprio(NSD_B48_PX); if (NSD_B48_X1M) x1m_role(a, sm, part, lane, n_steps); else x1_role<NB>(a, sm, 64 * part + lane, n_steps); }
-            else if (role == 3) { NSD_VIEW; dw16_role(a, sm, part, lane, n_steps); }
-            else                { NSD_VIEW; __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, lane, n_steps); }
-            return;
-        }
-    }
-    if (wave < 3)       { NSD_VIEW; __builtin_amdgcn_s_setprio(3); chain_role<NB>(a, sm, 1, tid, n_steps); }
-    else if (wave < 6)  { NSD_VIEW; __builtin_amdgcn_s_setprio(3); chain_role<NB>(a, sm, 0, tid - 192, n_steps); }
-    else if (wave < 9)  { NSD_VIEW; __builtin_amdgcn_s_setprio(2); x1_role<NB>(a, sm, tid - 384, n_steps); }
-    else if (wave < 15) { NSD_VIEW; if constexpr (NB == 1) dw16_role(a, sm, wave - 9, tid & 63, n_steps); else dw_role<NB>(a, sm, wave - 9, tid & 63, n_groups); }
-    else                { NSD_VIEW; __builtin_amdgcn_s_setprio(1); loader_role<NB>(a, sm, tid & 63, n_steps); }
-#undef NSD_VIEW
+    NSD_B48_ROLE_TABLE(const ModelView<Lstm2BwdArgs> a = model_view(a_in, s))
 }
 
 #endif
+#undef NSD_B48_ROLE_TABLE
 
 }  // namespace
 

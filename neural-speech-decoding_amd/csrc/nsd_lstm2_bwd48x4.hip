@@ -55,29 +55,26 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 #ifndef NSD_BX4_DWD
 #define NSD_BX4_DWD 4
 #endif
-constexpr int DWD = NSD_BX4_DWD;
+constexpr int DWD = NSD_BX4_DWD;  // steps the rows wave's B rows are requested ahead (= unroll of its step loop; 16 % DWD == 0)
 #ifndef NSD_BX4_DW_SLEEP
 #define NSD_BX4_DW_SLEEP 0
 #endif
 #ifndef NSD_BX4_X1_SLEEP
 #define NSD_BX4_X1_SLEEP 0
 #endif
-#ifndef NSD_BX4_B96
-#define NSD_BX4_B96 1
-#endif
 #ifndef NSD_BX4_CHD
 #define NSD_BX4_CHD 2
 #endif
-#ifndef NSD_BX4_CONV
-#define NSD_BX4_CONV 0            // who splits da into the bf16 windows: 0 the cell lanes (from their registers, at the step), 1 the rows wave (from the fp32 vectors in LDS, one step behind)
-#endif
-#ifndef NSD_BX4_VAR
-#define NSD_BX4_VAR 0             // timing experiments (never in the library): 1 no d attn.weight in C1, 2 records never open, 4 open without the row requests
-#endif
+// da is split into the bf16 windows by the cell lanes, from their registers, at the step.  The rows wave doing it from the fp32 vectors in
+// LDS one step behind was measured and lost (profiles/r04_split_bf16.md); that variant and the timing experiments on the open records are
+// gone from the source (DESIGN 4.2 names the commit that last had them).
+// Issue priorities follow the critical path: the two recurrences first, then the hand-off to layer 0, the weight gradients and the rows
+// last.  All equal, or reversed, measured the same (profiles/r04_x4_kernels.md: 376-385 us, no effect); the natural order stayed.
+constexpr int PRIO_CHAIN = 3, PRIO_X1 = 2, PRIO_DW = 0;
 constexpr int WK = 16;            // k rows of a weight-gradient window: 4 macro steps x 4 trials = the K of one v_mfma_f32_32x32x16_bf16
 constexpr int ARS = 224;          // bf16 elements per k row of the da windows: 192 + pad (448 B = 192 mod 256: the four k rows of a transposed read's block fall into four different 64-byte bank groups)
 constexpr int BRS = 96;           // ... of the row windows (192 B)
-constexpr int CHD = NSD_BX4_CHD;   // steps a cell lane requests its saved activations ahead (= unroll of the recurrences' step loop; even, 16 % CHD == 0)   // steps the dW waves' B rows are requested ahead (= unroll of their step loop; 16 % DWD == 0)
+constexpr int CHD = NSD_BX4_CHD;   // steps a cell lane requests its saved activations ahead (= unroll of the recurrences' step loop; even, 16 % CHD == 0)
 
 struct BSmem {
     float da[2][2][NTR][VSD];     // [slot m & 1][layer][trial][4 unit + gate]
@@ -286,10 +283,8 @@ __device__ __attribute__((noinline)) void chain_role(const A &a_in, const int g_
                 if (LAYER == 1) {
                     const f32x4 ad = *reinterpret_cast<const f32x4 *>(&sm.sc[(m >> 4) & 1][j][m & (XCH - 1)][0]);
                     dout = fmaf(ad[0], dpj, ad[1] * awj);
-                    if (!(NSD_BX4_VAR & 1)) {
                     attw = fmaf(ad[1], ht, attw);                   // (dscore is zero on inactive steps and padding trials)
                     open_rec = fmaxf(open_rec, ad[2]);
-                    }
                 } else {
                     const float mkv = masked ? sm.mk[(m >> 4) & 1][j][m & (XCH - 1)][u] : 1.f;
                     dout = sm.din1[(k + 1) & 1][j][u] * mkv;        // written by the X1 waves at macro step m - 1
@@ -309,7 +304,7 @@ __device__ __attribute__((noinline)) void chain_role(const A &a_in, const int g_
                 }
                 if (active) ct = cpk;                               // c[t-1] is the cell state of the next step handled
                 *reinterpret_cast<f32x4 *>(&sm.da[k & 1][LAYER][j][4 * u]) = dav;      // (zeros for inactive steps / padding trials: dW and X1 add nothing)
-                if (!NSD_BX4_CONV) put_da(sm, LAYER, m, j, 4 * u, dav);     // the weight gradients' operand: row (step, trial) of the window being filled
+                put_da(sm, LAYER, m, j, 4 * u, dav);                // the weight gradients' operand: row (step, trial) of the window being filled
                 prof_mark<4, true>(prof);                           // seg4: cell backward, da in LDS
                 xstep_barrier(prof);
             }
@@ -407,22 +402,6 @@ __device__ __attribute__((noinline)) void rows_role(const A &a_in, const int lan
                     put_row(sm, 1, m, j, 48 + 4 * c4, bq[k][1]);
                 }
                 put_row(sm, 0, m, j, col0, hb ? bq[k][2] : xv);
-                if (NSD_BX4_CONV) {                                  // da of macro step m - 1, both layers: 384 pieces of four columns, six per lane
-                    if (m >= 1) {
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) {
-                            const int rem = lane + 64 * (i % 3), jj = rem / 48, pc = rem - 48 * jj;
-                            put_da(sm, i / 3, m - 1, jj, 4 * pc, *reinterpret_cast<const f32x4 *>(&sm.da[(m + 1) & 1][i / 3][jj][4 * pc]));
-                        }
-                    }
-                    if (m == n_steps - 1) {                          // (the last macro step is an inactive one: zeros, nobody converts it)
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) {
-                            const int rem = lane + 64 * (i % 3), jj = rem / 48, pc = rem - 48 * jj;
-                            put_da(sm, i / 3, m, jj, 4 * pc, f32x4{0.f, 0.f, 0.f, 0.f});
-                        }
-                    }
-                }
                 __builtin_amdgcn_sched_barrier(0);
                 if (!ablated(a.ablate, 8)) prefetch(m + DWD, bq[k]);     // (behind the last use of these registers: the loads land in place)
                 xstep_barrier(prof);
@@ -476,8 +455,7 @@ __device__ __attribute__((noinline)) void dw_role(const A &a_in, const int d_in,
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (NSD_BX4_DW_SLEEP) __builtin_amdgcn_s_sleep(NSD_BX4_DW_SLEEP);
-                if (!NSD_BX4_CONV) { if (m0 >= 4 && k < NN) part(w, k); }
-                else               { if (m0 >= 4 && k >= 1 && k - 1 < NN) part(w, k - 1); }     // (the window is complete one step later)
+                if (m0 >= 4 && k < NN) part(w, k);
                 xstep_barrier(prof);
             }
         }
@@ -603,7 +581,7 @@ __device__ __attribute__((noinline)) void aux_role(const A &a_in, const int lane
             const int e = lane + 64 * i, n = e / H;
             dpe[i] = ((gfl_p)a.dpooled)[(size_t)(b0 + n < B ? b0 + n : B - 1) * H + (e - n * H)];
         }
-        const bool open = (NSD_BX4_VAR & 2) ? false : __any(scr0[2] != 0.f) != 0;
+        const bool open = __any(scr0[2] != 0.f) != 0;
         float sdot = 0.f, dsum = 0.f;
         auto close_record = [&](const int c, const f32x4 rec, const float dd) -> f32x4 {
             const int b = b0 + an, t = T - 1 - (16 * c + as);
@@ -654,7 +632,7 @@ __device__ __attribute__((noinline)) void aux_role(const A &a_in, const int lane
                 f32x4 rr[12];
                 const unsigned ro = row_off(b0, c + 1);
 #pragma unroll
-                for (int q = 0; q < 12; ++q) if (!(NSD_BX4_VAR & 4)) rr[q] = row_at(ro, q);
+                for (int q = 0; q < 12; ++q) rr[q] = row_at(ro, q);
                 steps(0, 6);
                 float d0 = 0.f, d1 = 0.f;
 #pragma unroll
@@ -698,11 +676,23 @@ __device__ __attribute__((noinline)) void aux_role(const A &a_in, const int lane
     prof_store(a.dbg, prof);
 }
 
+// Role of a wave = f(SIMD g = wave & 3, slot q = wave >> 2), written once for both entry points.  SIMDs 0..2: the two recurrences + two of
+// {five dW waves, rows wave}; SIMD 3: the three X1 waves + aux (matrix pipe per step and SIMD: 96 x 8 + ~2 x 144 cycles / 144 x 8).  The
+// round-4 placement (X1 beside the recurrences of its SIMD, the dW / rows waves on SIMD 3) lost: profiles/r04_x4_kernels.md.
+// `a` is the argument block in scope: the kernel's parameter, or the model's view of it in LDS.
+#define NSD_BX4_ROLE_TABLE \
+    if (g < 3 && q == 0)      { __builtin_amdgcn_s_setprio(PRIO_CHAIN); chain_role<1>(a, g, lane, n_steps); } \
+    else if (g < 3 && q == 1) { __builtin_amdgcn_s_setprio(PRIO_CHAIN); chain_role<0>(a, g, lane, n_steps); } \
+    else if (g < 3 && q == 2) { __builtin_amdgcn_s_setprio(PRIO_DW); dw_role<1>(a, g, lane, n_steps); } \
+    else if (g < 2)           { __builtin_amdgcn_s_setprio(PRIO_DW); dw_role<0>(a, g, lane, n_steps); } \
+    else if (g == 2)          { __builtin_amdgcn_s_setprio(PRIO_DW); rows_role(a, lane, n_steps); } \
+    else if (q < 3)           { __builtin_amdgcn_s_setprio(PRIO_X1); x1_role(a, q, lane, n_steps); } \
+    else                      aux_role(a, lane, n_steps)
+
 #if NSD_MULTI_TU
 // M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_bwd48x4.hip, so that the single-model kernel's module is what it was):
 // workgroup blockIdx.x takes model blockIdx.x / s.G (the roles walk its trial groups wg, wg + G, ... and write slab blockIdx.x).  The roles
-// and their placement (NSD_BX4_MAP 0) are those of lstm2_bwd48x4_kernel; they are called (noinline) and read the model's argument block
-// from LDS: a reference to a local would put it in scratch.
+// are called (noinline) and read the model's argument block from LDS: a reference to a local would put it in scratch.
 __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_multi_kernel(Lstm2BwdArgs a_in, ModelSplit s) {
     __shared__ ModelView<Lstm2BwdArgs> a;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -711,14 +701,7 @@ __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_multi_kernel(Lstm2BwdArgs 
     __syncthreads();
     const int n_steps = ((a_in.T + 3 + XCH - 1) / XCH) * XCH;
     const int g = wave & 3, q = wave >> 2;
-    constexpr int PC = 3, PX = 2, PD = 0;
-    if (g < 3 && q == 0)      { __builtin_amdgcn_s_setprio(PC); chain_role<1>(a, g, lane, n_steps); }
-    else if (g < 3 && q == 1) { __builtin_amdgcn_s_setprio(PC); chain_role<0>(a, g, lane, n_steps); }
-    else if (g < 3 && q == 2) { __builtin_amdgcn_s_setprio(PD); dw_role<1>(a, g, lane, n_steps); }
-    else if (g < 2)           { __builtin_amdgcn_s_setprio(PD); dw_role<0>(a, g, lane, n_steps); }
-    else if (g == 2)          { __builtin_amdgcn_s_setprio(PD); rows_role(a, lane, n_steps); }
-    else if (q < 3)           { __builtin_amdgcn_s_setprio(PX); x1_role(a, q, lane, n_steps); }
-    else                      aux_role(a, lane, n_steps);
+    NSD_BX4_ROLE_TABLE;
 }
 #else
 __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_kernel(Lstm2BwdArgs a) {
@@ -737,37 +720,11 @@ __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_kernel(Lstm2BwdArgs a) {
     else aux_role(a, lane, n_steps);
     return;
 #endif
-#ifndef NSD_BX4_PRIO
-#define NSD_BX4_PRIO 0
-#endif
-#ifndef NSD_BX4_MAP
-#define NSD_BX4_MAP 0
-#endif
-    constexpr int PC = NSD_BX4_PRIO == 0 ? 3 : NSD_BX4_PRIO == 1 ? 0 : 1, PX = NSD_BX4_PRIO == 0 ? 2 : NSD_BX4_PRIO == 1 ? 0 : 1, PD = NSD_BX4_PRIO == 2 ? 3 : 0;
-#if NSD_BX4_MAP == 0
-    // SIMDs 0..2: the two recurrences + two of {five dW waves, rows wave}; SIMD 3: the three X1 waves + aux (matrix pipe per step and
-    // SIMD: 96 x 8 + ~2 x 144 cycles / 144 x 8)
-    if (g < 3 && q == 0)      { __builtin_amdgcn_s_setprio(PC); chain_role<1>(a, g, lane, n_steps); }
-    else if (g < 3 && q == 1) { __builtin_amdgcn_s_setprio(PC); chain_role<0>(a, g, lane, n_steps); }
-    else if (g < 3 && q == 2) { __builtin_amdgcn_s_setprio(PD); dw_role<1>(a, g, lane, n_steps); }
-    else if (g < 2)           { __builtin_amdgcn_s_setprio(PD); dw_role<0>(a, g, lane, n_steps); }
-    else if (g == 2)          { __builtin_amdgcn_s_setprio(PD); rows_role(a, lane, n_steps); }
-    else if (q < 3)           { __builtin_amdgcn_s_setprio(PX); x1_role(a, q, lane, n_steps); }
-    else                      aux_role(a, lane, n_steps);
-#else
-    // the round-4 placement: X1 beside the recurrences of its SIMD, the dW / rows waves on SIMD 3
-    if (g < 3 && q == 0)      { __builtin_amdgcn_s_setprio(PC); chain_role<1>(a, g, lane, n_steps); }
-    else if (g < 3 && q == 1) { __builtin_amdgcn_s_setprio(PC); chain_role<0>(a, g, lane, n_steps); }
-    else if (g < 3 && q == 2) { __builtin_amdgcn_s_setprio(PX); x1_role(a, g, lane, n_steps); }
-    else if (g < 3)           { __builtin_amdgcn_s_setprio(PD); dw_role<1>(a, g, lane, n_steps); }
-    else if (q < 2)           { __builtin_amdgcn_s_setprio(PD); dw_role<0>(a, q, lane, n_steps); }
-    else if (q == 2)          { __builtin_amdgcn_s_setprio(PD); rows_role(a, lane, n_steps); }
-    else                      aux_role(a, lane, n_steps);
-#endif
+    NSD_BX4_ROLE_TABLE;
     // a workgroup without a trial group (grid = the workspace's slab count) has written a zero slab: every role's sums are zero
 }
-
 #endif
+#undef NSD_BX4_ROLE_TABLE
 
 }  // namespace
 

@@ -910,6 +910,32 @@ __device__ __forceinline__ void spare_role(const A &a, FSmem<NB> &sm, const int 
     }
 }
 
+// Role table, written once for both entry points.  The step time is set by the VALU issue load of the busiest SIMD, and the dispatcher
+// deals the waves of a workgroup round-robin over the 4 SIMDs (waves w and w+4 share one; checked with HW_REG_HW_ID).  So roles
+// are placed by g = wave & 3 (the SIMD) and q = wave >> 2 (the slot on it):
+//     g = 0..2 :  L1 part g | L0 part g | {saver or inference pool, train pool, spare (dropout stream)}[g]
+//     g = 3    :  P part 0  | P part 1  | P part 2
+// i.e. ~155 / 150 / 135 / 135 VALU instructions per step and SIMD, instead of one SIMD carrying an L1, an L0 and
+// a P wave (~180).  s_setprio follows the critical path: L1 > L0 > P > the rest.
+// RAW = the kernel's argument block (uniform fields only); VIEW = the statement that forms a role's block `a` inside its branch (empty
+// where `a` is the kernel's parameter).  A macro, because it expands to the token sequence both kernels had: a template over the
+// argument source cost lstm2_fwd48_kernel<1, false> a VGPR and 13 SGPR spills (profiles/h48_variants_same_isa.md).
+#define NSD_FWD48_ROLE_TABLE(RAW, VIEW) \
+    if (g == 3)      { VIEW; __builtin_amdgcn_s_setprio(1); p_role<NB>(a, sm, q * 64 + lane, n_steps); } \
+    else if (q == 0) { VIEW; __builtin_amdgcn_s_setprio(3); l1_role<NB>(a, sm, g * 64 + lane, n_steps); } \
+    else if (q == 1) { VIEW; __builtin_amdgcn_s_setprio(2); l0_role<NB>(a, sm, g * 64 + lane, n_steps); } \
+    else if (g == 0) { \
+        VIEW; \
+        if constexpr (NB == 1) { \
+            if (a.logits_out) pool_role<NB>(a, sm, lane, n_steps); \
+            else              saver_role<NB>(a, sm, lane, n_steps); \
+        } else { \
+            saver_role<NB>(a, sm, lane, n_steps);               /* (inference runs one trial per workgroup: nothing but its latency matters there) */ \
+        } \
+    } \
+    else if (g == 1 && RAW.head_train) { VIEW; tpool_role<NB, SOFT>(a, sm, lane, n_steps); } \
+    else { VIEW; spare_role<NB>(a, sm, lane, n_steps); }
+
 #if !NSD_MULTI_TU
 template <int NB, bool SOFT = false>
 __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
@@ -918,13 +944,6 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // macro steps 0..T+1, padded to whole x chunks so that every role runs the same number of barriers
     const int n_steps = ((a.T + 2 + XCH - 1) / XCH) * XCH;
-    // Role table.  The step time is set by the VALU issue load of the busiest SIMD, and the dispatcher deals the waves
-    // of a workgroup round-robin over the 4 SIMDs (waves w and w+4 share one; checked with HW_REG_HW_ID).  So roles
-    // are placed by g = wave & 3 (the SIMD) and q = wave >> 2 (the slot on it):
-    //     g = 0..2 :  L1 part g | L0 part g | {saver or inference pool, train pool, spare (dropout stream)}[g]
-    //     g = 3    :  P part 0  | P part 1  | P part 2
-    // i.e. ~155 / 150 / 135 / 135 VALU instructions per step and SIMD, instead of one SIMD carrying an L1, an L0 and
-    // a P wave (~180).  s_setprio follows the critical path: L1 > L0 > P > the rest.
     const int g = wave & 3, q = wave >> 2;
 #ifdef NSD_FWD48_ONLY_ROLE                                     // resource probe (never built into the library): one role alone
     if (NSD_FWD48_ONLY_ROLE == 1) p_role<NB>(a, sm, q * 64 + lane, n_steps);
@@ -935,24 +954,12 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_kernel(Lstm2FwdArgs a) {
     else spare_role<NB>(a, sm, lane, n_steps);
     return;
 #endif
-    if (g == 3)      { __builtin_amdgcn_s_setprio(1); p_role<NB>(a, sm, q * 64 + lane, n_steps); }
-    else if (q == 0) { __builtin_amdgcn_s_setprio(3); l1_role<NB>(a, sm, g * 64 + lane, n_steps); }
-    else if (q == 1) { __builtin_amdgcn_s_setprio(2); l0_role<NB>(a, sm, g * 64 + lane, n_steps); }
-    else if (g == 0) {
-        if constexpr (NB == 1) {
-            if (a.logits_out) pool_role<NB>(a, sm, lane, n_steps);
-            else              saver_role<NB>(a, sm, lane, n_steps);
-        } else {
-            saver_role<NB>(a, sm, lane, n_steps);               // (inference runs one trial per workgroup: nothing but its latency matters there)
-        }
-    }
-    else if (g == 1 && a.head_train) tpool_role<NB, SOFT>(a, sm, lane, n_steps);
-    else spare_role<NB>(a, sm, lane, n_steps);
+    NSD_FWD48_ROLE_TABLE(a, )
 }
 
 #else
 // M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_fwd48.hip, so that the single-model kernels' module is what it was):
-// workgroup blockIdx.x runs model blockIdx.x / s.G; the roles and their placement are those of lstm2_fwd48_kernel
+// workgroup blockIdx.x runs model blockIdx.x / s.G; each role forms the model's view itself: only the pointers it reads are live in it
 template <int NB, bool SOFT = false>
 __global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in, ModelSplit s) {
     __shared__ __align__(16) FSmem<NB> sm;
@@ -960,26 +967,11 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n_steps = ((a_in.T + 2 + XCH - 1) / XCH) * XCH;
     const int g = wave & 3, q = wave >> 2;
-    // (each role forms the view itself: only the pointers it reads are live in it)
-#define NSD_VIEW const ModelView<Lstm2FwdArgs> a = model_view(a_in, s)
-    if (g == 3)      { NSD_VIEW; __builtin_amdgcn_s_setprio(1); p_role<NB>(a, sm, q * 64 + lane, n_steps); }
-    else if (q == 0) { NSD_VIEW; __builtin_amdgcn_s_setprio(3); l1_role<NB>(a, sm, g * 64 + lane, n_steps); }
-    else if (q == 1) { NSD_VIEW; __builtin_amdgcn_s_setprio(2); l0_role<NB>(a, sm, g * 64 + lane, n_steps); }
-    else if (g == 0) {
-        NSD_VIEW;
-        if constexpr (NB == 1) {
-            if (a.logits_out) pool_role<NB>(a, sm, lane, n_steps);
-            else              saver_role<NB>(a, sm, lane, n_steps);
-        } else {
-            saver_role<NB>(a, sm, lane, n_steps);
-        }
-    }
-    else if (g == 1 && a_in.head_train) { NSD_VIEW; tpool_role<NB, SOFT>(a, sm, lane, n_steps); }
-    else { NSD_VIEW; spare_role<NB>(a, sm, lane, n_steps); }
-#undef NSD_VIEW
+    NSD_FWD48_ROLE_TABLE(a_in, const ModelView<Lstm2FwdArgs> a = model_view(a_in, s))
 }
 
 #endif
+#undef NSD_FWD48_ROLE_TABLE
 
 }  // namespace
 

@@ -148,7 +148,6 @@ __device__ __attribute__((noinline)) void tail_all(const Lstm2FwdArgs &a_in, con
 
 // One barrier per macro step.  Raw s_barrier behind lgkmcnt(0): the step's LDS writes are complete, the asynchronous buffer stores of
 // the saved activations are NOT waited for (__syncthreads() would drain vmcnt every step).
-template <bool RAW_UNUSED = false>
 __device__ __forceinline__ void xstep_barrier(Prof &p) {
     if (kProfile && p.on) {
         const long long t = clock64();
@@ -812,11 +811,25 @@ __device__ __forceinline__ void idle_role(const Lstm2FwdArgs &a, XSmem &sm, cons
     }
 }
 
+// Role of a wave = f(SIMD g = wave & 3, slot q = wave >> 2) for one trial group, written once for both entry points (the dispatcher deals
+// the waves round-robin over the SIMDs).  Issue priority follows the critical path: layer 1, then layer 0, then the projection that
+// feeds layer 1 a step later; the helpers last.  RAW = the kernel's argument block (uniform fields only), INL = what an inlined role
+// gets, CALLED = what a called (noinline) role gets.
+#define NSD_X4_ROLE_TABLE(RAW, INL, CALLED) \
+    if (g == 3)      { __builtin_amdgcn_s_setprio(1); p_role(INL, sm, q, lane, n_steps, grp); } \
+    else if (q == 0) { __builtin_amdgcn_s_setprio(3); l1_role(INL, sm, g, lane, n_steps, grp); } \
+    else if (q == 1) { __builtin_amdgcn_s_setprio(2); l0_role(INL, sm, g, lane, n_steps, grp); } \
+    else if (g == 0) { __builtin_amdgcn_s_setprio(0); stage_role(CALLED, lane, n_steps, grp); } \
+    else if (RAW.head_train) { __builtin_amdgcn_s_setprio(0); pool_role(CALLED, g - 1, lane, n_steps, grp); } \
+    else idle_role(RAW, sm, n_steps, grp); \
+    __builtin_amdgcn_s_setprio(0); \
+    if (RAW.head_train) tail_all(CALLED, tid, grp * NTR)
+
 #if NSD_MULTI_TU
 // M models of one shape (nsd_multi.h; compiled as nsd_lstm2_multi_fwd48x4.hip, so that the single-model kernel's module is what it was):
-// workgroup blockIdx.x takes model blockIdx.x / s.G, its trial groups wg, wg + G, ...  The roles are those of lstm2_fwd48x4_kernel; the
-// called (noinline) ones read the model's argument block from LDS -- a reference to a local would put it in scratch -- and the inlined
-// ones form it themselves, so that only the pointers they read are live in them.
+// workgroup blockIdx.x takes model blockIdx.x / s.G, its trial groups wg, wg + G, ...  The called (noinline) roles read the model's
+// argument block from LDS -- a reference to a local would put it in scratch -- and the inlined ones form it themselves, so that only the
+// pointers they read are live in them.
 __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_multi_kernel(Lstm2FwdArgs a_in, ModelSplit s) {
     XSmem &sm = g_sm;
     __shared__ Lstm2FwdArgs view;
@@ -829,14 +842,7 @@ __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_multi_kernel(Lstm2FwdArgs 
     const int ngrp = (a_in.B + NTR - 1) / NTR;
     const int wg = (int)blockIdx.x - (int)(blockIdx.x / s.G) * s.G;
     for (int grp = wg; grp < ngrp; grp += s.G) {
-        if (g == 3)      { __builtin_amdgcn_s_setprio(1); p_role(model_view(a_in, s), sm, q, lane, n_steps, grp); }
-        else if (q == 0) { __builtin_amdgcn_s_setprio(3); l1_role(model_view(a_in, s), sm, g, lane, n_steps, grp); }
-        else if (q == 1) { __builtin_amdgcn_s_setprio(2); l0_role(model_view(a_in, s), sm, g, lane, n_steps, grp); }
-        else if (g == 0) { __builtin_amdgcn_s_setprio(0); stage_role(view, lane, n_steps, grp); }
-        else if (a_in.head_train) { __builtin_amdgcn_s_setprio(0); pool_role(view, g - 1, lane, n_steps, grp); }
-        else idle_role(a_in, sm, n_steps, grp);
-        __builtin_amdgcn_s_setprio(0);
-        if (a_in.head_train) tail_all(view, tid, grp * NTR);
+        NSD_X4_ROLE_TABLE(a_in, model_view(a_in, s), view);
     }
 }
 #else
@@ -846,7 +852,7 @@ __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_kernel(Lstm2FwdArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // macro steps 0 .. T+1, padded to whole 16-step chunks: every role runs the same number of barriers
     const int n_steps = ((a.T + 2 + XCH - 1) / XCH) * XCH;
-    const int g = wave & 3, q = wave >> 2;                          // SIMD, slot (the dispatcher deals the waves round-robin over the SIMDs)
+    const int g = wave & 3, q = wave >> 2;                          // SIMD, slot
     // One trial group at a time (a launch with at most four trials per CU has one group per workgroup): the roles reload their
     // weights per group, so that nothing of a role is live across the fused head's tail
     const int ngrp = (a.B + NTR - 1) / NTR;
@@ -860,18 +866,11 @@ __global__ __launch_bounds__(NTHR) void lstm2_fwd48x4_kernel(Lstm2FwdArgs a) {
         else tail_all(a, tid, grp * NTR);
         continue;
 #endif
-        if (g == 3)      { __builtin_amdgcn_s_setprio(1); p_role(a, sm, q, lane, n_steps, grp); }
-        else if (q == 0) { __builtin_amdgcn_s_setprio(3); l1_role(a, sm, g, lane, n_steps, grp); }
-        else if (q == 1) { __builtin_amdgcn_s_setprio(2); l0_role(a, sm, g, lane, n_steps, grp); }
-        else if (g == 0) { __builtin_amdgcn_s_setprio(0); stage_role(a, lane, n_steps, grp); }
-        else if (a.head_train) { __builtin_amdgcn_s_setprio(0); pool_role(a, g - 1, lane, n_steps, grp); }
-        else idle_role(a, sm, n_steps, grp);
-        __builtin_amdgcn_s_setprio(0);
-        if (a.head_train) tail_all(a, tid, grp * NTR);
+        NSD_X4_ROLE_TABLE(a, a, a);
     }
 }
-
 #endif
+#undef NSD_X4_ROLE_TABLE
 
 }  // namespace
 
@@ -890,8 +889,7 @@ int nsd_lstm2_fwd48x4_multi_launch(const Lstm2FwdArgs &a, const ModelSplit &s, i
 }
 #else
 bool nsd_lstm2_fwd48x4_ok(const Lstm2FwdArgs &a) {
-    // training launches of the plain two-layer stack; offsets of the saved activations are 32-bit byte offsets
-    // (the saved arrays are addressed with 32-bit byte offsets)
+    // training launches of the plain two-layer stack; the saved arrays are addressed with 32-bit byte offsets
     if ((long)a.B * a.T * H * 16 >= 0x7fffffffL) return false;
     return a.hseq0 != nullptr && a.hseq1 && a.cseq0 && a.cseq1 && a.gact0 && a.gact1 && a.inseq && !a.logits_out && !a.residual && a.C <= 8 &&
            (!a.head_train || (a.T <= TT_TMAX && a.F <= 64 && a.K <= TT_KMAX && a.F >= 1 && a.K >= 1));
