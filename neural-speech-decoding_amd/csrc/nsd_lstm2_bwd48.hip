@@ -26,6 +26,7 @@
 #include "nsd_args.h"
 #include "nsd_multi.h"
 #include "nsd_prof.h"
+#include "nsd_ring_block.h"
 #include "nsd_bf16.h"
 #include <type_traits>
 #include <utility>
@@ -193,15 +194,16 @@ __device__ __forceinline__ void chain_role(const A &a, Smem<NB> &sm, const int l
         }
         step_barrier<false>(prof);      // chunk 0 of the stage has been written by the loader wave
 
-        // unrolled by the ring length (== stage chunk): every LDS offset of a step is an immediate
+        // unrolled by the ring length (== stage chunk): every LDS offset of a step is an immediate.  A step reads da of the previous
+        // step (prev_active) and forms its own (active): macro steps tb - T + 2 .. tb do both, and a ring block of such steps runs
+        // without the two tests (one trial per workgroup)
+        const int tb = layer == 1 ? T - 1 : T + 1 + dl0(NB);      // t = tb - m
         for (int m0 = 0; m0 < n_steps; m0 += CHUNK) {
             const int sb = (m0 / CHUNK) & 1;
-#pragma unroll
-            for (int k = 0; k < CHUNK; ++k) {
-                const int m = m0 + k;
-                const int t = layer == 1 ? (T - 1 - m) : (T + 1 + dl0(NB) - m);
-                const bool active = (t >= 0 && t < T);
-                const bool prev_active = (t + 1 >= 0 && t + 1 < T);
+            ring_block<NB, CHUNK>(m0 >= tb - T + 2 && m0 + CHUNK - 1 <= tb, [&](const int k, const auto inside) {
+                const int t = tb - (m0 + k);
+                const bool active = inside.value || (t >= 0 && t < T);
+                const bool prev_active = inside.value || (t + 1 >= 0 && t + 1 < T);
                 if constexpr (NB == 1) {
                     // One trial per workgroup: everything that does not depend on the recurrence comes READY from the loader wave's
                     // prep of the previous step (two LDS reads instead of six and ~20 instructions less per step in the six waves whose
@@ -255,7 +257,7 @@ __device__ __forceinline__ void chain_role(const A &a, Smem<NB> &sm, const int l
                     }
                 }
                 step_barrier<false>(prof);
-            }
+            });
         }
     }
     float *slab = a.slabs + (size_t)wg_id(a) * a.slab_stride;

@@ -26,6 +26,7 @@
 #include "nsd_args.h"
 #include "nsd_multi.h"
 #include "nsd_prof.h"
+#include "nsd_ring_block.h"
 
 namespace {
 
@@ -51,6 +52,15 @@ constexpr int P_SLEEP = NSD_P_SLEEP, S_SLEEP = NSD_S_SLEEP;   // see step_barrie
 // fused train head limits (larger shapes use the separate head kernel)
 constexpr int TT_TMAX = 1024, TT_KMAX = 8, TT_W0S = 49;
 constexpr int NT_TRAIN = NT;
+// What the chain roles of the single-model one-trial kernels do beyond the untested ring blocks: lane selects as arithmetic with
+// per-lane constants, layer 0's multiplier read pinned.  The model-batched twin leaves them out: it is at the SGPR limit, and with them
+// its one-trial instantiation spills 16 kernel-argument SGPRs in the entry block and gets a 68-byte private segment
+// (profiles/h48_step_census.md; tests/test_h48_private_segments_cpu.py holds every forward instantiation to none).
+#if NSD_MULTI_TU
+template <int NB> constexpr bool LEAN = false;
+#else
+template <int NB> constexpr bool LEAN = NB == 1;
+#endif
 constexpr int TT_PARTS = NT_TRAIN / 48;   // 16
 
 template <int NB>
@@ -118,9 +128,13 @@ __host__ __device__ constexpr float gate_scale(const int g) { return g == 2 ? -2
 
 struct CellOut { float gate, c, h; };     // gate: this lane's activation (un-scaled), c: new cell state, h: o * tanh(c) * hmul
 // arg: exp2 argument of this lane's gate; cK: scaled cell state (updated); hmul: multiplier folded into h (dropout)
+// LANEK (LEAN; the two-trial kernels have no registers for the constants): the selects by lane become arithmetic
+// with per-lane constants that the time loop carries -- fma(1, r, 0) and x * 1 are r and x exactly, so the values are the same
+template <bool LANEK>
 __device__ __forceinline__ CellOut cell_step(const float arg, float &cK, const int s, const float hmul) {
     const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(arg));
-    const float act = s == 2 ? fmaf(2.f * KC, r, -KC) : r;                 // lane 2: KC * tanh(pre)
+    const float act = LANEK ? fmaf(s == 2 ? 2.f * KC : 1.f, r, s == 2 ? -KC : 0.f)
+                            : (s == 2 ? fmaf(2.f * KC, r, -KC) : r);       // lane 2: KC * tanh(pre)
     const float o = quad_bcast<3>(act);
     const float o2 = (2.f * hmul) * o, on = -hmul * o;                      // off the chain (the cell is still being formed)
     const float igK = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(act), QP(0, 0, 0, 0), 0xF, 0xF, true)) * act;   // lane 2: i * KC g
@@ -130,7 +144,7 @@ __device__ __forceinline__ CellOut cell_step(const float arg, float &cK, const i
     CellOut out;
     out.h = fmaf(o2, rc, on);
     out.c = cK * INV_KC;
-    out.gate = s == 2 ? act * INV_KC : act;
+    out.gate = LANEK ? act * (s == 2 ? INV_KC : 1.f) : (s == 2 ? act * INV_KC : act);
     return out;
 }
 
@@ -209,39 +223,43 @@ __device__ __forceinline__ void l0_role(const A &a, FSmem<NB> &sm, const int r, 
         for (int q = 0; q < MPT; ++q) *reinterpret_cast<float4 *>(&sm.ms[0][0][0][0] + 4 * (r + 192 * q)) = mask_at(r + 192 * q, 0);
         step_barrier<false>(prof);
 
+        // one step of ring slot kr (step k of the staged chunk in buffer cb)
+        auto step = [&](const int cb, const int k, const int kr) {
+#pragma unroll
+            for (int n = 0; n < NB; ++n) {
+                float mk = sm.ms[cb][n][k][j];
+                const float2 xq = *reinterpret_cast<const float2 *>(&sm.xs[cb][n][k][2 * s]);
+                const f32x2 xv = {xq.x, xq.y};
+                f32x2 hv[6];
+                load_slice(&sm.sv[(kr + SRING - 1) & (SRING - 1)][n][0][192 + s * KS], hv);
+                // The multiplier is pinned in front of the operands in the (in-order) LDS queue: left alone, hipcc sinks its read below the
+                // quad reduction and waits a whole LDS latency for it in front of the first exponential, in every step.  (Two trials per
+                // workgroup: the loop as it was.)
+                if constexpr (LEAN<NB>) { asm volatile("" : "+v"(mk)); __builtin_amdgcn_sched_barrier(0); }
+                f32x2 acc[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    acc[g] = pk_fma(wx[g], xv, (f32x2){g == s ? biasK : 0.f, 0.f});
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) acc[g] = pk_fma(wh[g][q], hv[q], acc[g]);
+                }
+                const CellOut o = cell_step<LEAN<NB>>(reduce_pick(acc, s), c[n], s, s == 2 ? mk : 1.f);   // lane 2: h * dropout multiplier
+                float *sr = &sm.sv[kr][n][0][0];
+                sr[192 + 48 * hslot + j] = o.h;                 // slots: h | c | masked h | spare (h again)
+                sr[192 + 48 + j] = o.c;                         // the quad's four lanes hold the same c
+                sr[4 * j + s] = o.gate;
+            }
+        };
         for (int m0 = 0; m0 < n_steps; m0 += XCH) {
             // (the NEXT chunk of x and of the explicit multipliers is fetched and written to the other LDS half by the spare wave: 19
             // registers held across the chunk by these chain waves were what pushed the two-trial instantiation into scratch)
             const int cb = (m0 / XCH) & 1;
             for (int kh = 0; kh < XCH; kh += SRING) {
-#pragma unroll
-              for (int kr = 0; kr < SRING; ++kr) {
-                const int k = kh + kr;
-                const int m = m0 + k;
-                if (m < T && !ablated(a.ablate, 64)) {
-#pragma unroll
-                    for (int n = 0; n < NB; ++n) {
-                        const float mk = sm.ms[cb][n][k][j];
-                        const float2 xq = *reinterpret_cast<const float2 *>(&sm.xs[cb][n][k][2 * s]);
-                        const f32x2 xv = {xq.x, xq.y};
-                        f32x2 hv[6];
-                        load_slice(&sm.sv[(kr + SRING - 1) & (SRING - 1)][n][0][192 + s * KS], hv);
-                        f32x2 acc[4];
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            acc[g] = pk_fma(wx[g], xv, (f32x2){g == s ? biasK : 0.f, 0.f});
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) acc[g] = pk_fma(wh[g][q], hv[q], acc[g]);
-                        }
-                        const CellOut o = cell_step(reduce_pick(acc, s), c[n], s, s == 2 ? mk : 1.f);   // lane 2: h * dropout multiplier
-                        float *sr = &sm.sv[kr][n][0][0];
-                        sr[192 + 48 * hslot + j] = o.h;                 // slots: h | c | masked h | spare (h again)
-                        sr[192 + 48 + j] = o.c;                         // the quad's four lanes hold the same c
-                        sr[4 * j + s] = o.gate;
-                    }
-                }
-                step_barrier<false>(prof);
-              }
+              const int mb = m0 + kh;                           // active window: m in [0, T)
+              ring_block<NB, SRING>(mb + SRING <= T, [&](const int kr, const auto inside) {
+                  if ((inside.value || mb + kr < T) && !ablated(a.ablate, 64)) step(cb, kh + kr, kr);
+                  step_barrier<false>(prof);
+              });
             }
         }
         if (a.head_train) tail_all<NB>(a, sm, threadIdx.x, b0);   // (its first barrier: the save ring of this trial group is drained)
@@ -269,27 +287,26 @@ __device__ __forceinline__ void p_role(const A &a, FSmem<NB> &sm, const int r, c
     const int ngrp = (a.B + NB - 1) / NB;
     for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         step_barrier<false>(prof);
-        for (int m0 = 0; m0 < n_steps; m0 += SRING) {
+        auto step = [&](const int k) {
 #pragma unroll
-          for (int k = 0; k < SRING; ++k) {
-            const int m = m0 + k;
-            if (m >= 1 && m <= T && !ablated(a.ablate, 128)) {
+            for (int n = 0; n < NB; ++n) {
+                f32x2 iv[6];
+                load_slice(&sm.sv[(k + SRING - 1) & (SRING - 1)][n][0][288 + s * KS], iv);
+                f32x2 acc[4];
 #pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    f32x2 iv[6];
-                    load_slice(&sm.sv[(k + SRING - 1) & (SRING - 1)][n][0][288 + s * KS], iv);
-                    f32x2 acc[4];
+                for (int g = 0; g < 4; ++g) {
+                    acc[g] = wi[g][0] * iv[0];
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        acc[g] = wi[g][0] * iv[0];
-#pragma unroll
-                        for (int q = 1; q < 6; ++q) acc[g] = pk_fma(wi[g][q], iv[q], acc[g]);
-                    }
-                    sm.pb[k & 1][n][s * H + j] = reduce_pick(acc, s);
+                    for (int q = 1; q < 6; ++q) acc[g] = pk_fma(wi[g][q], iv[q], acc[g]);
                 }
+                sm.pb[k & 1][n][s * H + j] = reduce_pick(acc, s);
             }
-            step_barrier<false, P_SLEEP>(prof);
-          }
+        };
+        for (int m0 = 0; m0 < n_steps; m0 += SRING) {
+          ring_block<NB, SRING>(m0 >= 1 && m0 + SRING <= T + 1, [&](const int k, const auto inside) {      // window: m in [1, T]
+              if ((inside.value || (m0 + k >= 1 && m0 + k <= T)) && !ablated(a.ablate, 128)) step(k);
+              step_barrier<false, P_SLEEP>(prof);
+          });
         }
         if (a.head_train) tail_all<NB>(a, sm, threadIdx.x, grp * NB);   // (its first barrier: the save ring of this trial group is drained)
         else step_barrier<false>(prof);      // save ring drained
@@ -324,44 +341,45 @@ __device__ __forceinline__ void l1_role(const A &a, FSmem<NB> &sm, const int r, 
         // The time loop is unrolled by the ring length: ring slots, buffer parities and every LDS offset become
         // immediates.  (A wave issues about one instruction per 5 cycles whatever its ILP -- tools/isa_loops.py --
         // so scalar index arithmetic in the step body costs as much as the FMAs.)
-        for (int m0 = 0; m0 < n_steps; m0 += SRING) {
+        const bool res = a.residual != 0;      // (a copy: read from the argument block in the step, the flag costs the model-batched
+                                               // one-trial kernel, which is at its SGPR limit, an entry-block spill and a 68-byte private segment)
+        auto step = [&](const int k) {
+            const int prv = (k & 1) ^ 1;
 #pragma unroll
-          for (int k = 0; k < SRING; ++k) {
-            const int m = m0 + k;
-            const int t = m - 2;
-            prof_mark<-1, false>(prof);
-            if (t >= 0 && t < T && !ablated(a.ablate, 1024)) {
-                const int prv = (k & 1) ^ 1;
+            for (int n = 0; n < NB; ++n) {
+                const float pj = sm.pb[prv][n][s * H + j];          // input projection of this step (gate s)
+                f32x2 hv[6];
+                load_slice(&sm.sv[(k + SRING - 1) & (SRING - 1)][n][1][192 + s * KS], hv);
+                prof_mark<0, true>(prof);        // seg0: LDS operands arrived
+                const float pjb = pj + biasK;
+                f32x2 acc[4];
 #pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    const float pj = sm.pb[prv][n][s * H + j];          // input projection of this step (gate s)
-                    f32x2 hv[6];
-                    load_slice(&sm.sv[(k + SRING - 1) & (SRING - 1)][n][1][192 + s * KS], hv);
-                    prof_mark<0, true>(prof);        // seg0: LDS operands arrived
-                    const float pjb = pj + biasK;
-                    f32x2 acc[4];
+                for (int g = 0; g < 4; ++g) {
+                    acc[g] = pk_fma(wh[g][0], hv[0], (f32x2){g == s ? pjb : 0.f, 0.f});
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        acc[g] = pk_fma(wh[g][0], hv[0], (f32x2){g == s ? pjb : 0.f, 0.f});
-#pragma unroll
-                        for (int q = 1; q < 6; ++q) acc[g] = pk_fma(wh[g][q], hv[q], acc[g]);
-                    }
-                    prof_mark<1, false>(prof);       // seg1: 24 pk_fma issued (not necessarily retired)
-                    const float arg = reduce_pick(acc, s);
-                    prof_mark<2, false>(prof);       // seg2: quad reduction + select
-                    CellOut o = cell_step(arg, c[n], s, 1.f);
-                    prof_mark<4, true>(prof);        // seg4: gates, cell update, tanh
-                    float *sr = &sm.sv[k][n][1][0];
-                    // layer-1 input of step t was written two macro steps ago
-                    if (a.residual && s == 2) o.h += sm.sv[(k + SRING - 2) & (SRING - 1)][n][0][288 + j];
-                    sr[192 + 48 * hslot + j] = o.h;               // slots: h | c | top | spare (h again)
-                    sr[192 + 48 + j] = o.c;
-                    sr[4 * j + s] = o.gate;
-                    prof_mark<5, false>(prof);       // seg5: record for the saver wave
+                    for (int q = 1; q < 6; ++q) acc[g] = pk_fma(wh[g][q], hv[q], acc[g]);
                 }
+                prof_mark<1, false>(prof);       // seg1: 24 pk_fma issued (not necessarily retired)
+                const float arg = reduce_pick(acc, s);
+                prof_mark<2, false>(prof);       // seg2: quad reduction + select
+                CellOut o = cell_step<LEAN<NB>>(arg, c[n], s, 1.f);
+                prof_mark<4, true>(prof);        // seg4: gates, cell update, tanh
+                float *sr = &sm.sv[k][n][1][0];
+                // layer-1 input of step t was written two macro steps ago
+                if (res && s == 2) o.h += sm.sv[(k + SRING - 2) & (SRING - 1)][n][0][288 + j];
+                sr[192 + 48 * hslot + j] = o.h;               // slots: h | c | top | spare (h again)
+                sr[192 + 48 + j] = o.c;
+                sr[4 * j + s] = o.gate;
+                prof_mark<5, false>(prof);       // seg5: record for the saver wave
             }
-            step_barrier<false>(prof);
-          }
+        };
+        for (int m0 = 0; m0 < n_steps; m0 += SRING) {
+          const bool in_window = m0 >= 2 && m0 + SRING <= T + 2;      // window: t = m - 2 in [0, T)
+          ring_block<NB, SRING>(in_window, [&](const int k, const auto inside) {
+              prof_mark<-1, false>(prof);
+              if ((inside.value || (m0 + k >= 2 && m0 + k < T + 2)) && !ablated(a.ablate, 1024)) step(k);
+              step_barrier<false>(prof);
+          });
         }
         if (a.head_train) tail_all<NB>(a, sm, threadIdx.x, grp * NB);   // (its first barrier: the save ring of this trial group is drained)
         else step_barrier<false>(prof);      // save ring drained
@@ -372,68 +390,64 @@ __device__ __forceinline__ void l1_role(const A &a, FSmem<NB> &sm, const int r, 
 // ------------------------------------------------------------------------------------------------
 // saver wave: LDS save ring -> HBM with 16-byte stores, one 8-step chunk behind the chain
 // ------------------------------------------------------------------------------------------------
-constexpr int SPIECES = 2 * SCH * SREC4 / 64;     // 24 wave-wide pieces (1 KB) per trial and chunk
-
-// One 16-byte piece of the chunk image per lane and q: where it lies in the ring and where it goes.  Two registers per piece (24
-// pieces): the destination as a 32-bit float offset from the workspace's hseq region (all saved arrays live in ONE workspace buffer,
-// a few hundred MB), and {ring offset, time index in chunk 0, row length} packed -- five registers per piece (a 64-bit pointer and
-// three ints) left no room for two trials' worth of pieces in flight.
+// A step of the saver moves ring slot k of the completed chunk: three wave-wide pieces, float4 e = 192 k + 64 u + lane (u = 0..2) of the
+// chunk image [k][layer][96].  Of a piece only the slot depends on k: (layer, w) = ((64 u + lane) / 96, (64 u + lane) % 96) is the same in
+// all eight steps, so a lane keeps THREE descriptors, decoded once in front of the time loop, instead of 24 packed ones whose bit-fields
+// every step took apart again (48 scalar instructions per step, on a SIMD shared with an L1 and an L0 chain wave).
 struct SvDesc {
-    int dst;             // float offset of (trial 0, t = 0) for this lane's 16 bytes, relative to sv_base; < 0: not saved
-    unsigned meta;       // bits 0..15 float offset inside sv[0][0] (ring slot 0, trial 0) | bits 16..23 (t0 + 2) | bit 24 row = 4H floats (else H)
+    float *dst;          // (trial 0, t = 0) of this lane's 16 bytes MOVED BACK by the layer's lag (layer 1: two rows), so that a macro
+                         // step's index leads to the row of the step the layer handles in it.  For layer 1 it lies BEFORE the array
+                         // and is valid only with mk >= lag, which every use tests ((unsigned)(mk - lag) < T, or an untested chunk
+                         // with mk >= 8).  (The lag as part of the index costs registers: the two-trial twin spills again.)
+    int ring;            // float offset inside sv[0][0] (ring slot 0, trial 0)
+    unsigned row;        // floats per time step of the destination (4H for the gates, else H); 0: not saved
+    int lag;             // macro steps the layer runs behind layer 0
 };
 
 template <int NB, class A>
 __device__ __forceinline__ void saver_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     const int T = a.T;
-    SvDesc d[SPIECES];
-    // training launches carry the whole workspace; inference without the tail (F or K beyond 64: nsd_head.hip follows) has `top` alone
-    float *const sv_base = a.hseq0 ? a.hseq0 : a.top;
+    SvDesc d[3];
 #pragma unroll
-    for (int q = 0; q < SPIECES; ++q) {
-        const int e = q * 64 + lane;                       // float4 index in the chunk image [k][layer][84]
-        const int k = e / (2 * SREC4), rem = e - k * (2 * SREC4);
+    for (int u = 0; u < 3; ++u) {
+        const int rem = u * 64 + lane;
         const int layer = rem / SREC4, w = rem - layer * SREC4;
-        const int t0 = k - (layer == 1 ? 2 : 0);
-        const int lds_off = (k * NB * 2 + layer) * SREC + 4 * w;
-        float *dst = nullptr; int wide = 0;
-        if (w < 48)      { dst = layer == 0 ? a.gact0 : a.gact1; wide = 1; if (dst) dst += 4 * w; }
+        float *dst = nullptr; unsigned row = H;
+        if (w < 48)      { dst = layer == 0 ? a.gact0 : a.gact1; row = 4 * H; if (dst) dst += 4 * w; }
         else if (w < 60) { dst = layer == 0 ? a.hseq0 : a.hseq1; if (dst) dst += 4 * (w - 48); }
         else if (w < 72) { dst = layer == 0 ? a.cseq0 : a.cseq1; if (dst) dst += 4 * (w - 60); }
         else if (w < 84) { dst = layer == 0 ? a.inseq : a.top;   if (dst) dst += 4 * (w - 72); }
-        d[q].dst = (dst && sv_base) ? (int)(dst - sv_base) : -1;
-        d[q].meta = (unsigned)lds_off | ((unsigned)(t0 + 2) << 16) | ((unsigned)wide << 24);
+        d[u].lag = 2 * layer;
+        d[u].row = (dst && (a.hseq0 || a.top)) ? row : 0u;
+        d[u].ring = layer * SREC + 4 * w;
+        d[u].dst = dst ? dst - (size_t)d[u].lag * row : nullptr;
     }
     Prof prof = prof_init(a.dbg);
-    // The LDS reads of a batch of pieces are all issued before the first store: one LDS latency per call instead of one
-    // per piece (the lane conditions are divergent, so the compiler would otherwise serialise read -> wait -> store).
-    auto flush = [&](const int chunk, const int b0, const int q0, const int q1) {
-        const float *ring = &sm.sv[(chunk & 1) * SCH][0][0][0];
+    // Ring slot k of chunk `chunk` (macro step mk = SCH chunk + k, t = mk - lag).  EDGE: the chunk may hold steps outside [0, T) (the
+    // trial's first chunk, and the one that holds T with the padding behind it); every other chunk tests nothing but the destination.
+    // The LDS reads of the three pieces are all issued before the first store: one LDS latency per call instead of one per piece (the
+    // lane conditions are divergent, so the compiler would otherwise serialise read -> wait -> store).  (Reads by every lane, tested
+    // or not, sent the piece buffer to scratch.)
+    auto flush = [&](auto edge, const int chunk, const int b0, const int k) {
+        constexpr bool EDGE = decltype(edge)::value;
+        const float *ring = &sm.sv[(chunk & 1) * SCH][0][0][0] + k * (NB * 2 * SREC);
+        const int mk = SCH * chunk + k;
+        float4 v[3][NB];
+        bool ok[3];
 #pragma unroll
-        for (int qb = 0; qb < SPIECES; qb += 3) {
-            if (qb < q0 || qb >= q1) continue;
-            float4 v[3][NB];
-            bool ok[3];
+        for (int u = 0; u < 3; ++u) {
+            ok[u] = d[u].row != 0u && (!EDGE || (unsigned)(mk - d[u].lag) < (unsigned)T);
 #pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int q = qb + u;
-                const int t = (int)((d[q].meta >> 16) & 0xffu) - 2 + SCH * chunk;
-                ok[u] = d[q].dst >= 0 && (unsigned)t < (unsigned)T;
+            for (int n = 0; n < NB; ++n)
+                v[u][n] = ok[u] ? *reinterpret_cast<const float4 *>(ring + d[u].ring + n * 2 * SREC) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
 #pragma unroll
-                for (int n = 0; n < NB; ++n)
-                    v[u][n] = ok[u] ? *reinterpret_cast<const float4 *>(ring + (d[q].meta & 0xffffu) + n * 2 * SREC) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+        for (int u = 0; u < 3; ++u) {
 #pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int q = qb + u;
-                const int t = (int)((d[q].meta >> 16) & 0xffu) - 2 + SCH * chunk;
-                const unsigned row = (d[q].meta >> 24) & 1u ? 4u * H : (unsigned)H;
-#pragma unroll
-                for (int n = 0; n < NB; ++n) {
-                    const int b = b0 + n;
-                    if (ok[u] && b < a.B)
-                        *reinterpret_cast<float4 *>(sv_base + d[q].dst + (size_t)((unsigned)(b * T + t)) * row) = v[u][n];
-                }
+            for (int n = 0; n < NB; ++n) {
+                const int b = b0 + n;
+                if (ok[u] && b < a.B)
+                    *reinterpret_cast<float4 *>(d[u].dst + (size_t)((unsigned)(b * T + mk)) * d[u].row) = v[u][n];
             }
         }
     };
@@ -442,26 +456,23 @@ __device__ __forceinline__ void saver_role(const A &a, FSmem<NB> &sm, const int 
         const int b0 = grp * NB;
         step_barrier<false>(prof);
         for (int m0 = 0; m0 < n_steps; m0 += SCH) {
-            const int done = m0 / SCH - 1;                 // chunk completed before this one started
-            // 24 pieces, 3 per step
-            if (done >= 0) flush(done, b0, 0, 3);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 3, 6);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 6, 9);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 9, 12);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 12, 15);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 15, 18);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 18, 21);
-            step_barrier<false, S_SLEEP>(prof);
-            if (done >= 0) flush(done, b0, 21, 24);
-            step_barrier<false, S_SLEEP>(prof);
+            const int done = m0 / SCH - 1;                 // chunk completed before this one started; one ring slot of it per step
+            if (done >= 1 && SCH * done + SCH <= T) {      // all of its steps lie in [0, T), for both layers
+#pragma unroll
+                for (int k = 0; k < SCH; ++k) {
+                    flush(std::false_type{}, done, b0, k);
+                    step_barrier<false, S_SLEEP>(prof);
+                }
+            } else {
+#pragma unroll 1
+                for (int k = 0; k < SCH; ++k) {
+                    if (done >= 0) flush(std::true_type{}, done, b0, k);
+                    step_barrier<false, S_SLEEP>(prof);
+                }
+            }
         }
-        flush(n_steps / SCH - 1, b0, 0, SPIECES);          // last chunk (its LDS image is complete: barrier above)
+#pragma unroll 1
+        for (int k = 0; k < SCH; ++k) flush(std::true_type{}, n_steps / SCH - 1, b0, k);   // last chunk (its LDS image is complete: barrier above)
         if (a.head_train) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail reads the top rows back
         if (a.head_train) tail_all<NB>(a, sm, threadIdx.x, b0);
         else step_barrier<false>(prof);                     // keep the ring intact until it has been read

@@ -3,11 +3,18 @@
 
     tools/isa_digest.py --csrc neural-speech-decoding_amd/csrc --out /tmp/isa_pr.json
     tools/isa_digest.py --compare /tmp/isa_parent.json /tmp/isa_pr.json
+    tools/isa_digest.py --census --csrc neural-speech-decoding_amd/csrc          (step bodies of the one- and two-trial H = 48 kernels)
 
 Each of the eight files is compiled device-only in three flavours (the Makefile's FLAGS, + -DNSD_PROFILE=1, + -DNSD_ABLATE_HOOKS=1),
 unbundled and disassembled; per function symbol the digest is the sha256 of its instructions (raw encodings included, leading
 addresses dropped), and per kernel the record of its code-object note (registers, spills, LDS, scratch, kernarg size).  Two builds of
 one source give equal digests; the device ELF itself carries a per-build id and is not compared.
+
+--census: the shipped flavour of the role-split kernels as assembly; per kernel, every stretch of instructions between two s_barrier
+in text order is a step body of some role.  Bodies are grouped by what they hold (packed products, exponentials, matrix and
+store instructions: the groups are named by that, not by role) and by whether control enters or leaves them (a label or a branch inside: a tested body), and each group prints
+its instruction counts, the index of every `s_waitcnt lgkmcnt(0)`, of the first v_pk_fma_f32 / v_pk_mul_f32, of the first v_exp_f32 and
+of every LDS write (the first ds_write_b32 of a chain body is h), with the instructions between the last v_fma_f32 and that write.
 """
 import argparse
 import concurrent.futures
@@ -93,6 +100,98 @@ def compare(pa, pb, table, subset=False):
     return bad
 
 
+CENSUS_FILES = ["nsd_lstm2_fwd48", "nsd_lstm2_bwd48", "nsd_lstm2_multi_fwd48", "nsd_lstm2_multi_bwd48"]
+
+
+def role_of(ops):
+    n = lambda *pre: sum(o.startswith(pre) for o in ops)
+    pk, ex, mf = n("v_pk_fma_f32", "v_pk_mul_f32"), n("v_exp_f32"), n("v_mfma")
+    # named by content, not by role: which role of a kernel a group is follows from the kernel's source (forward: 28 packed products +
+    # exponentials = layer 0, 24 + exponentials = layer 1, 24 alone = projection, 16-byte stores alone = saver; backward: 24 alone =
+    # the recurrences)
+    if n("global_load_lds"):
+        return "LDS-DMA"
+    if mf:
+        return "matrix instructions"
+    if pk and ex:
+        return f"{pk} packed products + exponentials"
+    if pk:
+        return f"{pk} packed products"
+    if n("global_store_dwordx4") and not ex:
+        return "16-byte stores, no products"
+    return None
+
+
+def census(csrc, files):
+    flags = make_flags(csrc)
+    for name in files:
+        asm = subprocess.run([f"{ROCM}/bin/hipcc", *flags, "--cuda-device-only", "-S", name + ".hip", "-o", "-"], check=True,
+                             capture_output=True, text=True, cwd=os.path.abspath(csrc)).stdout
+        kernel, body, groups, meta = None, None, {}, {}
+        def close(kernel, groups, meta):
+            if kernel is None:
+                return
+            print(f"\n{name} {kernel}\n    " + " ".join(f"{k}={v}" for k, v in sorted(meta.items())))
+            for (role, tested), g in sorted(groups.items()):
+                c = lambda key: "..".join(str(v) for v in sorted({min(x[key] for x in g), max(x[key] for x in g)}))
+                r = g[0]
+                print(f"  {role}{' [tested: label or branch inside]' if tested else ''}: {len(g)} bodies\n"
+                      f"    instr {c('n')} vector {c('vec')} packed {c('pk')} lds rd/wr {c('rd')}/{c('wr')} stores {c('st')} "
+                      f"scalar incl. waits, nops, branches {c('sc')} (branches {c('br')})\n"
+                      f"    per body, instr/scalar: {' '.join(str(x['n']) + '/' + str(x['sc']) for x in g)}\n"
+                      f"    first body: lgkmcnt(0) at {r['w0']} | first product at {r['p0']} | first v_exp_f32 at {r['e0']} | lds writes at {r['wi']}"
+                      f" | between the last v_fma_f32 and the first write: {r['gap']}")
+        for line in asm.splitlines():
+            m = re.match(r"^(_Z\w+):", line)
+            if m and "kernel" in m.group(1):
+                close(kernel, groups, meta)
+                kernel, body, groups, meta = m.group(1), None, {}, {}
+                continue
+            if kernel is None:
+                continue
+            km = re.match(r"^\s*; (NumVgprs|ScratchSize|LDSByteSize|NumSgprs|codeLenInByte)\s*[:=]\s*(\d+)", line)
+            if km:
+                meta[km.group(1)] = int(km.group(2))
+                continue
+            t = line.strip()
+            if re.match(r"^\.LBB\w+:", t):
+                if body is not None:
+                    body["label"] = True
+                continue
+            if not t or t[0] in ".;" or line[0] not in "\t ":
+                continue
+            op = t.split()[0]
+            if op == "s_endpgm":
+                body = None
+                continue
+            if op == "s_barrier":
+                if body is not None and body["ops"]:
+                    ops = body["ops"]
+                    role = role_of([o for o, _ in ops])
+                    if role:
+                        names = [o for o, _ in ops]
+                        idx = lambda f: [i for i, (o, a) in enumerate(ops) if f(o, a)]
+                        first = lambda l: l[0] if l else None
+                        wr = idx(lambda o, a: o.startswith("ds_write"))
+                        fm = idx(lambda o, a: o.startswith("v_fma_f32") or o.startswith("v_fmac_f32"))
+                        lastf = max([i for i in fm if wr and i < wr[0]], default=None)
+                        rec = {"n": len(ops), "vec": sum(o.startswith("v_") for o in names),
+                               "pk": sum(o.startswith(("v_pk_fma_f32", "v_pk_mul_f32")) for o in names),
+                               "rd": sum(o.startswith("ds_read") for o in names), "wr": len(wr),
+                               "st": sum(o.startswith(("global_store", "buffer_store")) for o in names),
+                               "sc": sum(o.startswith("s_") for o in names), "br": sum(o.startswith(("s_cbranch", "s_branch")) for o in names),
+                               "w0": idx(lambda o, a: o == "s_waitcnt" and "lgkmcnt(0)" in a),
+                               "p0": first(idx(lambda o, a: o.startswith(("v_pk_fma_f32", "v_pk_mul_f32")))),
+                               "e0": first(idx(lambda o, a: o.startswith("v_exp_f32"))), "wi": wr,
+                               "gap": names[lastf + 1:wr[0]] if lastf is not None else None}
+                        groups.setdefault((role, bool(body["label"] or rec["br"])), []).append(rec)
+                body = {"ops": [], "label": False}
+                continue
+            if body is not None:
+                body["ops"].append((op, t[len(op):]))
+        close(kernel, groups, meta)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--csrc")
@@ -102,7 +201,11 @@ if __name__ == "__main__":
     ap.add_argument("--compare", nargs=2)
     ap.add_argument("--subset", action="store_true", help="with --compare: only the objects the right side has")
     ap.add_argument("--table", action="store_true", help="with --compare: print every symbol, not only the differing ones")
+    ap.add_argument("--census", action="store_true", help="step bodies (between two s_barrier) of the role-split kernels: instruction counts and wait positions")
     o = ap.parse_args()
+    if o.census:
+        census(o.csrc, o.files if o.files != FILES else CENSUS_FILES[:2])
+        sys.exit(0)
     if o.compare:
         sys.exit(1 if compare(*o.compare, o.table, o.subset) else 0)
     digest(o.csrc, o.out, o.jobs, o.files)
