@@ -333,6 +333,68 @@ int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stri
               float *y, float *targets /* [M*B][K] */, void *stream);
 
 /*
+ * ---- global-norm gradient clipping and learning-rate schedules in the step tail (an EXTENSION: the reference's recipe is missing) ----
+ *
+ * Step indexing: s is the 1-based Adam step, e = s - 1.
+ * Schedule factor f(s), formed in double:
+ *   warm-up             W = warmup_steps >= 0;  e < W: f = (e + 1) / W;  otherwise e' = e - W and
+ *   NSD_SCHED_CONSTANT  f = 1
+ *   NSD_SCHED_COSINE    N' = total_steps - W >= 1, r = min_ratio in [0, 1]:  f = r + (1 - r) * 0.5 * (1 + cos(pi * min(e', N') / N'))
+ *                       (past N' it holds at r)
+ *   NSD_SCHED_STEP      f = gamma ^ floor(e' / step_size),  step_size >= 1, gamma in (0, 1]
+ *   lr_eff = (float)((double)lr * f),  lr_over_bc1 = (float)((double)lr_eff / bc1)
+ * With W = 0 the last two are torch's CosineAnnealingLR(T_max = N', eta_min = lr * r) closed form up to T_max, and StepLR.
+ * Clipping, torch.nn.utils.clip_grad_norm_ with norm_type = 2:
+ *   g~_e = fp32(grads[e] * grad_scale)             (the fp32 product Adam forms anyway)
+ *   S    = sum_e (double)g~_e^2                    (the squares are exact in double; the sum is taken in a FIXED order: per reduction
+ *                                                   workgroup over its lanes, then a fixed tree over the workgroups' partials)
+ *   norm = (float)sqrt(S)
+ *   coef = max_norm > 0 ? (float)min(1.0, max_norm / (sqrt(S) + 1e-6)) : 1
+ *   Adam takes gi = fmaf(weight_decay, p, g~_e * coef): decay after clipping, as in torch, where decay lives in the optimizer.
+ * Bitwise: when nothing is clipped coef is exactly 1.0f and g~ * coef == g~; a constant schedule gives lr_eff == lr.  An unclipped,
+ * constant-schedule step with a host `step` leaves grads, p, m, v bitwise what nsd_grad_reduce_adam / nsd_adam_step leave (the Adam
+ * arithmetic is adam_kernel's, in its order; the host forms bc1, bc2 and f with libm as there).  With step_dev they are formed on the
+ * device, as nsd_adam_step_dev does (its pow / cos differ from libm's in the last place).
+ * Non-finite: when S is Inf or NaN the update is skipped entirely -- p, m, v untouched, the model's sticky `skipped` counter + 1, `norm`
+ * records the non-finite value, coef reads 0.  Also with max_norm = 0, which means: report the norm and guard, do not clip.
+ *
+ * opt_state (device, caller-owned, nsd_opt_state_bytes(n_or_P, M) bytes; n_or_P: the flat route's n, or a model's parameter count):
+ * M records nsd_opt_record, then private scratch (the workgroups' partial sums, doubles).  nsd_opt_state_init zeroes the buffer once
+ * after allocation (the records' sticky counter needs one initialisation); the scratch may hold anything, before and after it: every
+ * call writes all of it that it reads.  norm, coef, lr are overwritten by every update; skipped is only ever incremented.
+ *   nsd_lr_factor              HOST only: f(step); negative for invalid fields or step < 1
+ *   nsd_grad_reduce_clip_adam  the single-rank fp32 tail: nsd_grad_reduce (grads bit for bit) + norm, then the update: two launches.
+ *                              step_dev != NULL: s is read from the device counter and `step` is ignored (hipGraph replay: the
+ *                              graph replays the schedule with no host argument changing)
+ *   nsd_multi_grad_reduce_clip_adam  the same for M models: one norm, one record, one skip decision per model; model m is bitwise a
+ *                              single-model call (domain and refusals of nsd_multi_grad_reduce_adam)
+ *   nsd_grad_norm              flat route, launch 1: the partial sums of g[0..n) * grad_scale -> opt_state's scratch
+ *   nsd_adam_step_clip         flat route, launch 2: the update from what nsd_grad_norm(n, g, opt->grad_scale) left (after the all-reduce
+ *                              at world > 1, on the bf16 sequence path, in graph segment B).  skip: NULL, or the device flag of
+ *                              nsd_adam_step_guarded -- non-zero: nothing is written, the record included
+ * NSD_E_INVALID before any launch: NULL opt / pointers; max_norm negative or NaN; unknown sched; warmup_steps < 0; cosine with
+ * total_steps <= warmup_steps; step_size < 1; gamma outside (0, 1]; min_ratio outside [0, 1]; step < 1 without step_dev; n < 0.
+ * NSD_E_WORKSPACE: opt_state_bytes < nsd_opt_state_bytes, or a short workspace.  Additive: NSD_VERSION stays 301, detected by the symbols.
+ */
+#define NSD_SCHED_CONSTANT 0
+#define NSD_SCHED_COSINE   1
+#define NSD_SCHED_STEP     2
+typedef struct nsd_opt {
+    float lr, beta1, beta2, eps, weight_decay, grad_scale, max_norm;
+    int32_t sched, warmup_steps, total_steps, step_size;
+    float min_ratio, gamma;
+} nsd_opt;
+typedef struct nsd_opt_record { float norm, coef, lr; uint32_t skipped; } nsd_opt_record;   /* 16 B per model, first bytes of opt_state */
+double  nsd_lr_factor(const nsd_opt *opt, int64_t step);
+int64_t nsd_opt_state_bytes(int64_t n_or_P, int32_t M);
+int nsd_opt_state_init(void *opt_state, int64_t opt_state_bytes, void *stream);
+int nsd_grad_reduce_clip_adam(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, float *p, float *m, float *v,
+                              const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state, int64_t opt_state_bytes, void *stream);
+int nsd_grad_norm(int64_t n, const float *g, float grad_scale, void *opt_state, int64_t opt_state_bytes, void *stream);
+int nsd_adam_step_clip(int64_t n, float *p, const float *g, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                       const float *skip, void *opt_state, int64_t opt_state_bytes, void *stream);
+
+/*
  * ---- model-batched H = 48 path: M models of one shape trained / evaluated in the launches one model uses ----
  *
  * Folds, seeds and ensembles of EEG_LSTM (lstm_eeg_model.py:13-39): each model has its own parameters, windows, labels and random
@@ -371,6 +433,10 @@ int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, 
 int nsd_multi_grad_reduce_adam(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
                                float *m, float *v, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                int32_t step, void *stream);
+/* nsd_grad_reduce_clip_adam for M models (clipping and schedules, above): grads / p / m / v [M][P], opt_state of nsd_opt_state_bytes(P, M) */
+int nsd_multi_grad_reduce_clip_adam(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
+                                    float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state,
+                                    int64_t opt_state_bytes, void *stream);
 int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream);
 int64_t nsd_multi_infer_scratch_bytes(const nsd_dims *d, int32_t M);
 int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,

@@ -42,6 +42,21 @@ class Mix(C.Structure):
     _fields_ = [("mix", C.c_float), ("smoothing", C.c_float)]
 
 
+class Opt(C.Structure):
+    """nsd_opt of include/nsd.h"""
+    _fields_ = ([(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale", "max_norm")]
+                + [(n, C.c_int32) for n in ("sched", "warmup_steps", "total_steps", "step_size")]
+                + [("min_ratio", C.c_float), ("gamma", C.c_float)])
+
+
+class OptRecord(C.Structure):
+    """nsd_opt_record of include/nsd.h"""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("lr", C.c_float), ("skipped", C.c_uint32)]
+
+
+NSD_SCHED = {"constant": 0, "cosine": 1, "step": 2}
+
+
 class NsdError(RuntimeError):
     pass
 
@@ -121,6 +136,14 @@ SYMBOLS = {
     "nsd_multi_train_bwd": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _vp, C.c_uint32, _fp, C.c_int64, _vp]),
     "nsd_multi_grad_reduce": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
     "nsd_multi_grad_reduce_adam": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp] + [C.c_float] * 6 + [C.c_int32, _vp]),
+    # global-norm clipping and learning-rate schedules in the step tail
+    "nsd_lr_factor": (C.c_double, [_vp, C.c_int64]),
+    "nsd_opt_state_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "nsd_opt_state_init": (C.c_int, [_vp, C.c_int64, _vp]),
+    "nsd_grad_reduce_clip_adam": (C.c_int, [_dp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
+    "nsd_grad_norm": (C.c_int, [C.c_int64, _fp, C.c_float, _vp, C.c_int64, _vp]),
+    "nsd_adam_step_clip": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _fp, _vp, C.c_int64, _vp]),
+    "nsd_multi_grad_reduce_clip_adam": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
     "nsd_multi_loss_sum": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
     "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
     "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),

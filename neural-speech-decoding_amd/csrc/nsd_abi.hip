@@ -597,6 +597,64 @@ int nsd_adam_step_guarded(int64_t n, float *p, const float *g, float *m, float *
     return nsd_adam_launch(n, p, g, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step, skip, (hipStream_t)stream);
 }
 
+// ---- global-norm clipping and learning-rate schedules (nsd_opt, include/nsd.h; nsd_optim.hip) ---------------------------------------
+// refusals shared by the launching entry points, before any launch: the fields of opt, the step, then the size of opt_state
+static int opt_enter(const char *who, const nsd_opt *o, int32_t step, const int64_t *step_dev, const void *state, int64_t bytes, int64_t n, int M) {
+    if (const int rc = nsd_opt_check(o, who)) return rc;
+    if (!step_dev && step < 1) { nsd_set_error("%s: step %d must be >= 1 (or pass step_dev)", who, step); return NSD_E_INVALID; }
+    if (!state) { nsd_set_error("%s: opt_state is NULL", who); return NSD_E_INVALID; }
+    const int64_t need = nsd_opt_state_need(n, M);
+    if (bytes < need) {
+        nsd_set_error("%s: opt_state of %lld bytes is smaller than nsd_opt_state_bytes() = %lld", who, (long long)bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+double nsd_lr_factor(const nsd_opt *opt, int64_t step) {
+    if (nsd_opt_check(opt, "lr_factor") != NSD_OK) return -1.0;
+    if (step < 1) { nsd_set_error("lr_factor: step %lld must be >= 1", (long long)step); return -1.0; }
+    return nsd_lr_factor_host(opt, step);
+}
+
+int64_t nsd_opt_state_bytes(int64_t n_or_P, int32_t M) {
+    if (n_or_P < 0 || M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("opt_state_bytes: n = %lld, M = %d (n >= 0, 1 <= M <= %d)", (long long)n_or_P, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    return nsd_opt_state_need(n_or_P, M);
+}
+
+int nsd_opt_state_init(void *opt_state, int64_t opt_state_bytes, void *stream) {
+    if (!opt_state || opt_state_bytes < (int64_t)sizeof(nsd_opt_record)) { nsd_set_error("opt_state_init: opt_state is NULL or shorter than one record"); return NSD_E_INVALID; }
+    return nsd_opt_state_init_launch(opt_state, opt_state_bytes, (hipStream_t)stream);
+}
+
+int nsd_grad_reduce_clip_adam(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, float *p, float *m, float *v,
+                              const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state, int64_t opt_state_bytes, void *stream) {
+    static const char *who = "grad_reduce_clip_adam";
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (!workspace || !grads || !p || !m || !v) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, layout_of(d).total, 1)) return rc;
+    Ctx c;
+    if (const int rc = enter(&c, who, d, true, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
+    return nsd_reduce_clip_adam_launch(slab_set(c), 1, grads, p, m, v, opt, step, (const long long *)step_dev, opt_state, who, c.st);
+}
+
+int nsd_grad_norm(int64_t n, const float *g, float grad_scale, void *opt_state, int64_t opt_state_bytes, void *stream) {
+    if (n < 0 || !g || !opt_state) { nsd_set_error("grad_norm: null pointer or n<0"); return NSD_E_INVALID; }
+    if (opt_state_bytes < nsd_opt_state_need(n, 1)) {
+        nsd_set_error("grad_norm: opt_state of %lld bytes is smaller than nsd_opt_state_bytes() = %lld", (long long)opt_state_bytes, (long long)nsd_opt_state_need(n, 1));
+        return NSD_E_WORKSPACE;
+    }
+    return nsd_grad_norm_launch(n, g, grad_scale, opt_state, (hipStream_t)stream);
+}
+
+int nsd_adam_step_clip(int64_t n, float *p, const float *g, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                       const float *skip, void *opt_state, int64_t opt_state_bytes, void *stream) {
+    static const char *who = "adam_step_clip";
+    if (n < 0 || !p || !g || !m || !v) { nsd_set_error("%s: null pointer or n<0", who); return NSD_E_INVALID; }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, n, 1)) return rc;
+    return nsd_adam_clip_flat_launch(n, p, g, m, v, opt, step, (const long long *)step_dev, skip, opt_state, (hipStream_t)stream);
+}
+
 int nsd_train_masks(uint64_t seed, uint32_t base_stream, float p_lstm, float p_head, int64_t n_lstm, float *drop_lstm,
                     int64_t n_head, float *rrelu_slope, float *drop_head, void *stream) {
     if (n_lstm < 0 || n_head < 0 || (n_lstm > 0 && !drop_lstm) || (n_head > 0 && (!rrelu_slope || !drop_head))) {
@@ -849,6 +907,19 @@ int nsd_multi_grad_reduce_adam(const nsd_dims *d, int32_t M, const float *worksp
     if (M == 1) return nsd_grad_reduce_adam(d, workspace, workspace_bytes, grads, p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step, stream);
     const AdamStep adam{p, m, v, lr, beta1, beta2, eps, weight_decay, grad_scale, step};
     return nsd_grad_reduce_launch(slab_set(c), M, grads, 0, &adam, who, c.st);
+}
+
+int nsd_multi_grad_reduce_clip_adam(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
+                                    float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state,
+                                    int64_t opt_state_bytes, void *stream) {
+    static const char *who = "multi_grad_reduce_clip_adam";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!grads || !p || !m || !v) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, layout_of(d).total, M)) return rc;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
+    if (M == 1) return nsd_grad_reduce_clip_adam(d, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state, opt_state_bytes, stream);
+    return nsd_reduce_clip_adam_launch(slab_set(c), M, grads, p, m, v, opt, step, (const long long *)step_dev, opt_state, who, c.st);
 }
 
 int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {

@@ -176,6 +176,17 @@ struct AdamStep { float *p, *m, *v; float lr, b1, b2, eps, wd, gscale; int step;
 int nsd_grad_reduce_launch(const SlabSet &s, int M, float *grads, int accumulate, const AdamStep *adam, const char *who, hipStream_t st);
 int nsd_adam_launch(long n, float *p, const float *g, float *m, float *v, float lr, float b1, float b2, float eps,
                     float wd, float gscale, int step, const float *skip, hipStream_t st);
+// global-norm clipping and learning-rate schedules (nsd_opt of nsd.h; nsd_optim.hip).  state: the caller's opt_state, already checked
+// against nsd_opt_state_need(n or P, M); o: already through nsd_opt_check
+int nsd_opt_check(const nsd_opt *o, const char *who);
+double nsd_lr_factor_host(const nsd_opt *o, long long step);
+int64_t nsd_opt_state_need(int64_t n, int M);
+int nsd_opt_state_init_launch(void *state, int64_t bytes, hipStream_t st);
+int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int step,
+                                const long long *step_dev, void *state, const char *who, hipStream_t st);
+int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st);
+int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float *v, const nsd_opt *o, int step, const long long *step_dev,
+                              const float *skip, void *state, hipStream_t st);
 int nsd_seq_guard_launch(const int *header, int status_word, float *flag_out, hipStream_t st);
 int nsd_dropout_mask_launch(uint64_t seed, uint32_t stream_id, float p, long n, float *out, hipStream_t st);
 int nsd_train_masks_launch(uint64_t seed, uint32_t base, const long long *step_dev, float p_lstm, float p_head, long n_lstm,

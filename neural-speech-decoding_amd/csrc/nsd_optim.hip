@@ -1,0 +1,249 @@
+// nsd_optim.hip -- global-norm gradient clipping and learning-rate schedules in the step tail (nsd_opt of include/nsd.h).
+//
+// The clipped tail is TWO launches with no signalling between workgroups:
+//   1. a reduction that also leaves, per workgroup, the double sum of its squared scaled gradients (reduce_norm_kernel for the slabs of the
+//      fused tail, norm_flat_kernel for a flat vector) in the scratch part of opt_state;
+//   2. adam_clip_kernel, the one update kernel of every route: each workgroup first sums those partials in the same fixed order (the
+//      sums, and with them the skip decision, are identical in every workgroup), forms coef, the schedule factor and the bias
+//      corrections in double, then updates its elements; workgroup 0 of a model writes the model's record.
+// A ticket counter whose last reduction workgroup finishes the update alone was weighed and not built.
+#include <math.h>
+#include <float.h>
+#include <string.h>
+#include "nsd_args.h"
+
+// ---- schedule factor f(s), double: the same expression on the host (nsd_lr_factor, host-step launches) and on the device (step_dev) ----
+__host__ __device__ static inline double lr_factor_of(int sched, int W, int total, int step_size, float min_ratio, float gamma, long long s) {
+    const long long e = s - 1;
+    if (e < W) return (double)(e + 1) / (double)W;
+    const long long ep = e - W;
+    if (sched == NSD_SCHED_COSINE) {
+        const long long np = (long long)total - W;
+        const double r = (double)min_ratio;
+        const long long q = ep < np ? ep : np;
+        return r + (1.0 - r) * 0.5 * (1.0 + cos(3.14159265358979323846 * (double)q / (double)np));
+    }
+    if (sched == NSD_SCHED_STEP) return pow((double)gamma, (double)(ep / step_size));
+    return 1.0;
+}
+
+// nsd_opt's fields: 0, or the NSD_E_INVALID refusal with the field named (who: the entry point)
+int nsd_opt_check(const nsd_opt *o, const char *who) {
+    if (!o) { nsd_set_error("%s: opt is NULL", who); return NSD_E_INVALID; }
+    if (!(o->max_norm >= 0.f)) { nsd_set_error("%s: max_norm %g negative or NaN", who, o->max_norm); return NSD_E_INVALID; }
+    if (o->sched != NSD_SCHED_CONSTANT && o->sched != NSD_SCHED_COSINE && o->sched != NSD_SCHED_STEP) {
+        nsd_set_error("%s: sched %d unknown (NSD_SCHED_CONSTANT / _COSINE / _STEP)", who, o->sched); return NSD_E_INVALID;
+    }
+    if (o->warmup_steps < 0) { nsd_set_error("%s: warmup_steps %d negative", who, o->warmup_steps); return NSD_E_INVALID; }
+    if (o->sched == NSD_SCHED_COSINE && o->total_steps <= o->warmup_steps) {
+        nsd_set_error("%s: total_steps %d must exceed warmup_steps %d for the cosine schedule", who, o->total_steps, o->warmup_steps); return NSD_E_INVALID;
+    }
+    if (o->step_size < 1) { nsd_set_error("%s: step_size %d must be >= 1", who, o->step_size); return NSD_E_INVALID; }
+    if (!(o->gamma > 0.f && o->gamma <= 1.f)) { nsd_set_error("%s: gamma %g outside (0, 1]", who, o->gamma); return NSD_E_INVALID; }
+    if (!(o->min_ratio >= 0.f && o->min_ratio <= 1.f)) { nsd_set_error("%s: min_ratio %g outside [0, 1]", who, o->min_ratio); return NSD_E_INVALID; }
+    return NSD_OK;
+}
+
+double nsd_lr_factor_host(const nsd_opt *o, long long step) {
+    return lr_factor_of(o->sched, o->warmup_steps, o->total_steps, o->step_size, o->min_ratio, o->gamma, step);
+}
+
+// ---- opt_state: M records, then per model the workgroups' partial sums (doubles) ------------------------------------------------------
+// fused tail: one partial per 32 columns; flat route: one per workgroup of norm_flat_kernel (never more than that: 256 >= 32)
+constexpr int ON_COLS = 32, ON_GROUPS = 8, ON_UNROLL = 8;     // the tiling of grad_reduce_kernel (nsd_misc.hip), whose sums these must equal
+constexpr int FLAT_NT = 256, FLAT_MAX_PARTS = 2048;
+static inline long col_parts(long P) { return (P + ON_COLS - 1) / ON_COLS; }
+static inline long flat_parts(long n) { const long b = (n + FLAT_NT - 1) / FLAT_NT; return b < FLAT_MAX_PARTS ? b : FLAT_MAX_PARTS; }
+int64_t nsd_opt_state_need(int64_t n, int M) { return (int64_t)M * (int64_t)sizeof(nsd_opt_record) + (int64_t)M * col_parts(n) * (int64_t)sizeof(double); }
+static inline double *parts_of(void *state, int M) { return reinterpret_cast<double *>(static_cast<char *>(state) + (size_t)M * sizeof(nsd_opt_record)); }
+
+__global__ void opt_state_init_kernel(uint32_t *w, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) w[i] = 0u;
+}
+int nsd_opt_state_init_launch(void *state, int64_t bytes, hipStream_t st) {
+    const long words = (long)(bytes / 4);
+    if (words <= 0) return NSD_OK;
+    long blocks = (words + 255) / 256; if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(opt_state_init_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (uint32_t *)state, words);
+    NSD_CHECK_LAUNCH("opt_state_init");
+    return NSD_OK;
+}
+
+// ---- launch 1, fused tail: grad_reduce_kernel's column sums (same tiling, same association order: grads is nsd_grad_reduce's bit for
+// bit) and the workgroup's double sum of (fp32(grads[e] * gscale))^2, lanes in order; lanes past P add exactly 0 ----------------------
+template <bool MODELS>
+__global__ __launch_bounds__(ON_COLS * ON_GROUPS) void reduce_norm_kernel(
+        const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs, long ph, int n_hslabs,
+        float *grads, float gscale, double *parts) {
+    if constexpr (MODELS) {
+        const long mo = blockIdx.y;
+        slabs += mo * n_slabs * slab_stride; hslabs += mo * n_hslabs * ph; grads += mo * (p_lstm + ph);
+        parts += mo * gridDim.x;
+    }
+    __shared__ float part[ON_GROUPS][ON_COLS];
+    __shared__ double sq[ON_COLS];
+    const int c = threadIdx.x & (ON_COLS - 1), grp = threadIdx.x / ON_COLS;
+    const long e = (long)blockIdx.x * ON_COLS + c;
+    float s0 = 0.f;
+    if (e < p_lstm + ph) {
+        const float *p; long stride; int n;
+        if (e < p_lstm) { p = slabs + e; stride = slab_stride; n = n_slabs; }
+        else { p = hslabs + (e - p_lstm); stride = ph; n = n_hslabs; }
+        int q = grp;
+        float acc[ON_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ON_UNROLL; ++u) acc[u] = 0.f;
+        for (; q + (ON_UNROLL - 1) * ON_GROUPS < n; q += ON_UNROLL * ON_GROUPS) {
+            float vload[ON_UNROLL];
+#pragma unroll
+            for (int u = 0; u < ON_UNROLL; ++u) vload[u] = p[(size_t)(q + u * ON_GROUPS) * stride];
+#pragma unroll
+            for (int u = 0; u < ON_UNROLL; ++u) acc[u] += vload[u];
+        }
+        for (; q < n; q += ON_GROUPS) acc[0] += p[(size_t)q * stride];
+#pragma unroll
+        for (int w = ON_UNROLL / 2; w >= 1; w >>= 1)
+#pragma unroll
+            for (int u = 0; u < w; ++u) acc[u] += acc[u + w];
+        s0 = acc[0];
+    }
+    part[grp][c] = s0 + 0.f;
+    __syncthreads();
+    if (grp == 0) {
+        double q2 = 0.0;
+        if (e < p_lstm + ph) {
+            float s = 0.f;
+#pragma unroll
+            for (int g = 0; g < ON_GROUPS; ++g) s += part[g][c];
+            grads[e] = s;
+            const float gt = s * gscale;
+            q2 = (double)gt * (double)gt;
+        }
+        sq[c] = q2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < ON_COLS; ++i) t += sq[i];
+        parts[blockIdx.x] = t;
+    }
+}
+
+// ---- launch 1, flat route: workgroup b's double sum of (fp32(g[i] * gscale))^2 over its grid-stride elements (each thread in index
+// order, then a fixed tree over the threads) ------------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum_256(double v, double *red) {      // every thread returns the total; fixed association
+    red[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int w = FLAT_NT / 2; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+__global__ __launch_bounds__(FLAT_NT) void norm_flat_kernel(long n, const float *g, float gscale, double *parts) {
+    __shared__ double red[FLAT_NT];
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * FLAT_NT + threadIdx.x; i < n; i += (long)gridDim.x * FLAT_NT) {
+        const float gt = g[i] * gscale;
+        s += (double)gt * (double)gt;
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) parts[blockIdx.x] = s;
+}
+
+// ---- launch 2: the Adam update of every route ---------------------------------------------------------------------------------------
+// Host step (step_dev == null): lr_eff, lr / bc1 and 1 / sqrt(bc2) arrive formed on the host, as nsd_adam_step forms them -- an unclipped
+// constant-schedule step is that entry point's bit for bit.  Device step: formed here from the counter, as adam_dev_kernel does.
+struct OptK {
+    float lr, b1, b2, eps, wd, gscale, max_norm;
+    int sched, warmup, total, step_size;
+    float min_ratio, gamma;
+    float lr_eff, lr_over_bc1, rsqrt_bc2;       // host step only
+    const long long *step_dev;
+};
+__global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, const float *g, float *m, float *v, OptK o,
+                                                            const double *parts, int n_parts, nsd_opt_record *rec, const float *skip) {
+    if (skip != nullptr && skip[0] != 0.f) return;                    // the caller's guard: nothing is written, the record included
+    const long mo = blockIdx.y;
+    p += mo * n; g += mo * n; m += mo * n; v += mo * n; parts += mo * n_parts; rec += mo;
+    __shared__ double red[FLAT_NT];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_parts; i += FLAT_NT) s += parts[i];
+    const double S = block_sum_256(s, red);
+    const double nrm = sqrt(S);
+    const bool finite = fabs(S) <= DBL_MAX;                            // false for Inf and NaN
+    float lr_eff = o.lr_eff, lr_over_bc1 = o.lr_over_bc1, rsqrt_bc2 = o.rsqrt_bc2;
+    if (o.step_dev != nullptr) {
+        const long long sn = o.step_dev[0];
+        const double st = (double)sn;
+        const double bc1 = 1.0 - pow((double)o.b1, st), bc2 = 1.0 - pow((double)o.b2, st);
+        lr_eff = (float)((double)o.lr * lr_factor_of(o.sched, o.warmup, o.total, o.step_size, o.min_ratio, o.gamma, sn));
+        lr_over_bc1 = (float)((double)lr_eff / bc1);
+        rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    float coef = 1.f;
+    if (o.max_norm > 0.f) { const double c = (double)o.max_norm / (nrm + 1e-6); coef = (float)(c < 1.0 ? c : 1.0); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        rec->norm = (float)nrm; rec->coef = finite ? coef : 0.f; rec->lr = lr_eff;
+        if (!finite) rec->skipped += 1u;                               // one writer per model: no atomic
+    }
+    if (!finite) return;                                               // uniform over the grid: every workgroup formed the same S
+    for (long i = (long)blockIdx.x * FLAT_NT + threadIdx.x; i < n; i += (long)gridDim.x * FLAT_NT) {
+        const float pi = p[i];                                         // the arithmetic of adam_kernel, in its order
+        const float gi = fmaf(o.wd, pi, (g[i] * o.gscale) * coef);
+        const float mi = o.b1 * m[i] + (1.f - o.b1) * gi;
+        const float vi = o.b2 * v[i] + (1.f - o.b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        const float denom = sqrtf(vi) * rsqrt_bc2 + o.eps;
+        p[i] = pi - lr_over_bc1 * (mi / denom);
+    }
+}
+
+static OptK opt_kernel_args(const nsd_opt *o, int step, const long long *step_dev) {
+    OptK k;
+    memset(&k, 0, sizeof(k));
+    k.lr = o->lr; k.b1 = o->beta1; k.b2 = o->beta2; k.eps = o->eps; k.wd = o->weight_decay; k.gscale = o->grad_scale; k.max_norm = o->max_norm;
+    k.sched = o->sched; k.warmup = o->warmup_steps; k.total = o->total_steps; k.step_size = o->step_size;
+    k.min_ratio = o->min_ratio; k.gamma = o->gamma; k.step_dev = step_dev;
+    if (!step_dev) {
+        const double bc1 = 1.0 - pow((double)o->beta1, step), bc2 = 1.0 - pow((double)o->beta2, step);
+        k.lr_eff = (float)((double)o->lr * nsd_lr_factor_host(o, step));
+        k.lr_over_bc1 = (float)(k.lr_eff / bc1);
+        k.rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    return k;
+}
+
+static int adam_clip_launch(long n, int M, float *p, const float *g, float *m, float *v, const OptK &k, long n_parts, void *state,
+                            const float *skip, const char *who, hipStream_t st) {
+    long blocks = (n + FLAT_NT - 1) / FLAT_NT; if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(FLAT_NT), 0, st, n, p, g, m, v, k,
+                       (const double *)parts_of(state, M), (int)n_parts, (nsd_opt_record *)state, skip);
+    NSD_CHECK_LAUNCH(who);
+    return NSD_OK;
+}
+
+// the fused tail of M models (M = 1: the single-model entry point): reduction with norm, then the update
+int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int step,
+                                const long long *step_dev, void *state, const char *who, hipStream_t st) {
+    const long P = s.p_lstm + s.ph, cols = col_parts(P);
+    const dim3 grid = M > 1 ? dim3((unsigned)cols, (unsigned)M) : dim3((unsigned)cols), wg(ON_COLS * ON_GROUPS);
+    const auto kernel = M > 1 ? reduce_norm_kernel<true> : reduce_norm_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h, grads, o->grad_scale, parts_of(state, M));
+    NSD_CHECK_LAUNCH(who);
+    return adam_clip_launch(P, M, p, grads, m, v, opt_kernel_args(o, step, step_dev), cols, state, nullptr, who, st);
+}
+
+int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st) {
+    if (n <= 0) return NSD_OK;
+    hipLaunchKernelGGL(norm_flat_kernel, dim3((unsigned)flat_parts(n)), dim3(FLAT_NT), 0, st, n, g, gscale, parts_of(state, 1));
+    NSD_CHECK_LAUNCH("grad_norm");
+    return NSD_OK;
+}
+
+int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float *v, const nsd_opt *o, int step, const long long *step_dev,
+                              const float *skip, void *state, hipStream_t st) {
+    if (n <= 0) return NSD_OK;
+    return adam_clip_launch(n, 1, p, g, m, v, opt_kernel_args(o, step, step_dev), flat_parts(n), state, skip, "adam_step_clip", st);
+}

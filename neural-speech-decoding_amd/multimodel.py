@@ -43,11 +43,13 @@ class ModelBatchTrainer:
     every model stays an ordinary module (forward, state_dict, save_reference_checkpoint work as before).  step(x, y) takes
     x [M,B,T,C] (per-model windows) or a shared [B,T,C], and y [M,B] or a shared [B].  augment: ops.Augment, applied per model as
     Trainer does.  loss: ops.Loss (label smoothing, class weights, mixup), applied per model as Trainer(model_m, seed=seeds[m], loss=loss)
-    does: nsd_augment (if any) -> nsd_mixup -> the step with targets, each one launch for all models; the scale stays 1 / B per model."""
+    does: nsd_augment (if any) -> nsd_mixup -> the step with targets, each one launch for all models; the scale stays 1 / B per model.
+    clip_grad_norm / lr_schedule: as Trainer's, the norm taken per model."""
 
     def __init__(self, models: Sequence[EEG_LSTM], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
-                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None):
+                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None,
+                 clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -81,6 +83,12 @@ class ModelBatchTrainer:
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
         self.grads = torch.zeros_like(self.params)
+        # clipping and schedule as in Trainer: one global norm, one record and one skip decision PER MODEL (nsd_multi_grad_reduce_clip_adam)
+        if clip_grad_norm is not None and not clip_grad_norm >= 0.0:
+            raise ValueError(f"ModelBatchTrainer: clip_grad_norm {clip_grad_norm!r} negative or NaN")
+        self.clip_grad_norm, self.lr_schedule = clip_grad_norm, lr_schedule
+        self._opt_on = clip_grad_norm is not None or lr_schedule is not None
+        self._opt_state = ops.opt_state(P, M, dev) if self._opt_on else None
         self.step_count = 0
         self._bufs = {}
         self._last = None
@@ -115,8 +123,29 @@ class ModelBatchTrainer:
         buf = self._buffers(B, T)
         ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
                              step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                             weight_decay=self.weight_decay, targets=tg)
+                             weight_decay=self.weight_decay, targets=tg, opt=self._opt() if self._opt_on else None, opt_state=self._opt_state)
         self._last = (B, T)
+
+    def _opt(self):
+        return ops.opt_struct(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
+                              max_norm=self.clip_grad_norm, schedule=self.lr_schedule)
+
+    def last_grad_norms(self) -> List[float]:
+        """Each model's global gradient norm of the last step, before clipping (synchronises; NaN with both options off or before a step)."""
+        if not self._opt_on or self._last is None:
+            return [float("nan")] * self.M
+        return [r["norm"] for r in ops.opt_records(self._opt_state, self.M)]
+
+    def last_lr(self) -> float:
+        """Learning rate of the last update (one schedule for all models; synchronises)."""
+        if self._opt_on and self._last is not None:
+            return ops.opt_records(self._opt_state, self.M)[0]["lr"]
+        opt = self._opt()
+        return float(torch.tensor(float(opt.lr) * ops.lr_factor(opt, max(self.step_count, 1)), dtype=torch.float32))
+
+    def skipped_steps(self) -> List[int]:
+        """Per model: updates skipped on the device because its gradient norm was not finite (sticky; synchronises)."""
+        return [r["skipped"] for r in ops.opt_records(self._opt_state, self.M)] if self._opt_on else [0] * self.M
 
     def last_losses(self) -> List[float]:
         """Mean loss (CE, or the soft-target loss with loss=) of each model's last step (synchronises)."""

@@ -422,6 +422,90 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     return out, targets
 
 
+@dataclass(frozen=True)
+class LrSchedule:
+    """Learning-rate schedule of a trainer (the schedule fields of nsd_opt, include/nsd.h; an extension, the reference has none):
+    lr_eff(s) = lr * f(s), s the 1-based step.  warmup_steps W: f = s / W for s <= W, then `kind` on e' = s - 1 - W: "constant" f = 1;
+    "cosine" f = r + (1 - r) (1 + cos(pi min(e', N') / N')) / 2 with N' = total_steps - W and r = min_ratio (torch's CosineAnnealingLR
+    closed form, held at r past N'); "step" f = gamma ^ floor(e' / step_size) (torch's StepLR).  The factor is a function of the step
+    alone, evaluated by the update kernel -- from the device step counter under hipGraph replay."""
+    kind: str = "constant"
+    warmup_steps: int = 0
+    total_steps: int = 0
+    min_ratio: float = 0.0
+    step_size: int = 1
+    gamma: float = 1.0
+
+    def __post_init__(self):
+        if self.kind not in _lib.NSD_SCHED:
+            raise ValueError(f"LrSchedule: kind {self.kind!r} is not one of {sorted(_lib.NSD_SCHED)}")
+        for name in ("warmup_steps", "total_steps", "step_size"):
+            v = getattr(self, name)
+            if int(v) != v or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError(f"LrSchedule: {name} {v!r} must be an int32")
+        if self.warmup_steps < 0:
+            raise ValueError(f"LrSchedule: warmup_steps {self.warmup_steps!r} negative")
+        if self.kind == "cosine" and self.total_steps <= self.warmup_steps:
+            raise ValueError(f"LrSchedule: cosine needs total_steps {self.total_steps!r} > warmup_steps {self.warmup_steps!r}")
+        if self.step_size < 1:
+            raise ValueError(f"LrSchedule: step_size {self.step_size!r} must be >= 1")
+        if not 0.0 < self.gamma <= 1.0:
+            raise ValueError(f"LrSchedule: gamma {self.gamma!r} outside (0, 1]")
+        if not 0.0 <= self.min_ratio <= 1.0:
+            raise ValueError(f"LrSchedule: min_ratio {self.min_ratio!r} outside [0, 1]")
+
+
+def opt_struct(*, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+               grad_scale: float = 1.0, max_norm: Optional[float] = None, schedule: Optional[LrSchedule] = None) -> "_lib.Opt":
+    """nsd_opt from Adam's hyper-parameters, a clip threshold (None or 0: report the norm and guard, do not clip) and a schedule."""
+    sc = schedule if schedule is not None else LrSchedule()
+    return _lib.Opt(lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0 if max_norm is None else float(max_norm),
+                    _lib.NSD_SCHED[sc.kind], int(sc.warmup_steps), int(sc.total_steps), int(sc.step_size), float(sc.min_ratio), float(sc.gamma))
+
+
+def lr_factor(opt: "_lib.Opt", step: int) -> float:
+    """f(step) of opt's schedule, on the host (nsd_lr_factor)."""
+    f = float(_lib.lib().nsd_lr_factor(C.byref(opt), int(step)))
+    if f < 0:
+        check(-1, "nsd_lr_factor")
+    return f
+
+
+def opt_state_bytes(n: int, M: int = 1) -> int:
+    nb = int(_lib.lib().nsd_opt_state_bytes(int(n), int(M)))
+    if nb < 0:
+        check(nb, "nsd_opt_state_bytes")
+    return nb
+
+
+def opt_state(n: int, M: int, device) -> torch.Tensor:
+    """The opt_state of the clipped tail for M models of n parameters (or a flat vector of n, M = 1): records zeroed."""
+    st = torch.empty(opt_state_bytes(n, M), dtype=torch.uint8, device=device)
+    _call("nsd_opt_state_init", st.device, st.data_ptr(), _nbytes(st), STREAM)
+    return st
+
+
+def opt_records(state: torch.Tensor, M: int = 1) -> List[dict]:
+    """The M records at the head of an opt_state: [{norm, coef, lr, skipped}] (synchronises)."""
+    raw = state[:16 * M].cpu()
+    f, u = raw.view(torch.float32).view(M, 4), raw.view(torch.int32).view(M, 4)
+    return [dict(norm=float(f[i, 0]), coef=float(f[i, 1]), lr=float(f[i, 2]), skipped=int(u[i, 3]) & 0xFFFFFFFF) for i in range(M)]
+
+
+def grad_norm(g: torch.Tensor, state: torch.Tensor, grad_scale: float = 1.0) -> None:
+    """Flat route, launch 1 (nsd_grad_norm): the partial sums of (g * grad_scale)^2 -> state's scratch, for adam_step_clip."""
+    _call("nsd_grad_norm", g.device, g.numel(), _dev_f32(g, "g"), grad_scale, state.data_ptr(), _nbytes(state), STREAM)
+
+
+def adam_step_clip(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, opt: "_lib.Opt", state: torch.Tensor, *,
+                   step: int = 0, step_dev: Optional[torch.Tensor] = None, skip: Optional[torch.Tensor] = None) -> None:
+    """Flat route, launch 2 (nsd_adam_step_clip): the clipped / scheduled Adam update from the norm grad_norm(g, state, opt.grad_scale)
+    left.  step_dev: the device step counter read in place of `step`; skip: the device flag of the guarded update."""
+    _call("nsd_adam_step_clip", p.device, p.numel(), _dev_f32(p, "p"), _dev_f32(g, "g", p.shape), _dev_f32(m, "m", p.shape),
+          _dev_f32(v, "v", p.shape), C.byref(opt), int(step), _step_ptr(step_dev, "adam_step_clip"), _dev_f32(skip, "skip"),
+          state.data_ptr(), _nbytes(state), STREAM)
+
+
 def _out_f32(out: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
     """The caller's output buffer (element count checked; dtype, device and contiguity by _dev_f32 at the launch), or a fresh one"""
     if out is None:
@@ -530,7 +614,8 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     (bit-identical to passing the tensors of nsd_train_masks with the same seed / stream ids); needs rng_path(spec, B, T).
 
     adam=dict(m=, v=, step=, lr=, beta1=, beta2=, eps=, weight_decay=): single-rank training -- the optimizer update of
-    `flat` rides in the reduction launch (nsd_grad_reduce_adam); `grads` is still written.
+    `flat` rides in the reduction launch (nsd_grad_reduce_adam); `grads` is still written.  With opt= (ops.opt_struct) and opt_state=
+    (ops.opt_state) in the dict the tail is nsd_grad_reduce_clip_adam instead (global-norm clipping, schedule; step_dev= optional).
 
     dx [B,T,C] (optional output): dL/dx from nsd_lstm_bwd where dx_path(spec, B, T); not with rng= (nsd_lstm_bwd_rng has no dx).
 
@@ -574,6 +659,12 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     gp = _dev_f32(grads, "grads", (spec.param_count,))
     if adam is None:
         _call("nsd_grad_reduce", dev, C.byref(d), wsp, wsn, gp, 0, st)
+    elif adam.get("opt") is not None:
+        # clipping / schedule on: reduction with norm, then the update (nsd_grad_reduce_clip_adam); step_dev: the graph-replay form
+        state = adam["opt_state"]
+        _call("nsd_grad_reduce_clip_adam", dev, C.byref(d), wsp, wsn, gp, pp, _dev_f32(adam["m"], "m", flat.shape), _dev_f32(adam["v"], "v", flat.shape),
+              C.byref(adam["opt"]), int(adam.get("step", 0)), _step_ptr(adam.get("step_dev"), "train_step_grads"), state.data_ptr(),
+              _nbytes(state), st)
     else:
         _call("nsd_grad_reduce_adam", dev, C.byref(d), wsp, wsn, gp, pp, _dev_f32(adam["m"], "m", flat.shape), _dev_f32(adam["v"], "v", flat.shape),
               adam.get("lr", 1e-3), adam.get("beta1", 0.9), adam.get("beta2", 0.999), adam.get("eps", 1e-8),
@@ -861,11 +952,13 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
                      *, rngs=None, logits: Optional[torch.Tensor] = None, fuse_adam: bool = True, m: Optional[torch.Tensor] = None,
                      v: Optional[torch.Tensor] = None, step: int = 1, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
                      eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
-                     targets: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     targets: Optional[torch.Tensor] = None, opt=None, opt_state: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One training step of M models at once: params [M,P], x [M,B,T,C] or shared [B,T,C], labels [M*B] int32, grads [M,P].
     Forward + head + mean CE per model + head backward, BPTT, then the reduction (+ Adam on params / m / v when fuse_adam).
     rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K].
-    targets [M*B, K] fp32 (labels is then ignored and may be None): the soft-target loss per model (nsd_multi_train_fwd_soft)."""
+    targets [M*B, K] fp32 (labels is then ignored and may be None): the soft-target loss per model (nsd_multi_train_fwd_soft).
+    opt (ops.opt_struct) with opt_state (ops.opt_state(P, M)): the tail is nsd_multi_grad_reduce_clip_adam -- one norm, record and skip
+    decision per model; the Adam arguments of this call are then ignored."""
     M = int(params.shape[0])
     B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
@@ -884,7 +977,10 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
         _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), 0, ws.data_ptr(), _nbytes(ws),
               _dev_f32(logits, "logits"), STREAM)
     _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, 0, ws.data_ptr(), _nbytes(ws), STREAM)
-    if fuse_adam:
+    if fuse_adam and opt is not None:
+        _call("nsd_multi_grad_reduce_clip_adam", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
+              _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), C.byref(opt), int(step), None, opt_state.data_ptr(), _nbytes(opt_state), STREAM)
+    elif fuse_adam:
         _call("nsd_multi_grad_reduce_adam", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
               _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), lr, beta1, beta2, eps, weight_decay, grad_scale, int(step), STREAM)
     else:

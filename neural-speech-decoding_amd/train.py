@@ -20,7 +20,7 @@ import torch
 
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
-from .ops import Augment, Loss
+from .ops import Augment, Loss, LrSchedule
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
 
@@ -100,6 +100,15 @@ def loss_for(args, y_train: np.ndarray) -> Loss:
     return Loss(label_smoothing=args.label_smoothing, class_weights=cw, mixup=args.mixup)
 
 
+def schedule_for(args, total_steps: int):
+    """The ops.LrSchedule of a run of total_steps optimisation steps (epochs x steps per epoch) from --lr-schedule and its options;
+    None without them."""
+    if args.lr_schedule is None:
+        return None
+    return LrSchedule(kind=args.lr_schedule, warmup_steps=args.warmup_steps, total_steps=max(int(total_steps), args.warmup_steps + 1),
+                      min_ratio=args.lr_min_ratio, step_size=args.lr_step_size, gamma=args.lr_gamma)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", help="directory with <prefix>_*.csv trials (reference: EEG_data_collection/), or a packed .npz "
@@ -140,7 +149,23 @@ def main(argv=None) -> int:
                                                           "all trials: one weight vector per launch) or K comma-separated weights w0,w1,...")
     ap.add_argument("--mixup", type=float, default=0.0, help="loss: mix every training trial with a partner of its batch, lambda = 1 - M * U(0,1) "
                                                              "(0 = off, 1 = uniform mixup)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, help="optimizer: clip the global L2 norm of the gradient to this "
+                                                                       "(0 = report the norm and skip non-finite steps, no clipping)")
+    ap.add_argument("--lr-schedule", default=None, choices=("constant", "cosine", "step"),
+                    help="optimizer: learning-rate schedule over epochs x steps per epoch, after --warmup-steps of linear warm-up")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="optimizer: linear warm-up over the first N steps")
+    ap.add_argument("--lr-min-ratio", type=float, default=0.0, help="optimizer: cosine schedule's floor as a fraction of --lr")
+    ap.add_argument("--lr-step-size", type=int, default=1, help="optimizer: step schedule: steps between two decays")
+    ap.add_argument("--lr-gamma", type=float, default=1.0, help="optimizer: step schedule: factor of a decay, in (0, 1]")
     args = ap.parse_args(argv)
+    if args.clip_grad_norm is not None and not args.clip_grad_norm >= 0.0:
+        ap.error(f"--clip-grad-norm {args.clip_grad_norm} negative")
+    if args.lr_schedule is None and (args.warmup_steps or args.lr_min_ratio or args.lr_step_size != 1 or args.lr_gamma != 1.0):
+        args.lr_schedule = "constant"        # a schedule option alone (warm-up) turns the schedule on
+    try:
+        schedule_for(args, 1 + max(args.warmup_steps, 0))
+    except ValueError as e:
+        ap.error(str(e))
     try:
         Loss(label_smoothing=args.label_smoothing, mixup=args.mixup)
         parse_class_weights(args.class_weights, args.classes)
@@ -204,7 +229,10 @@ def main(argv=None) -> int:
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
                          bidirectional=args.bidirectional).to(dev).train()
-        trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]))
+        steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
+        trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
+                          clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch))
+        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None
         tr_dev = torch.from_numpy(tr_idx).to(dev)
         best = (-1.0, -1)
         t0 = time.time()
@@ -225,8 +253,9 @@ def main(argv=None) -> int:
                 if keep_best and out_path and acc_va > best[0]:
                     best = (acc_va, epoch)
                     save_reference_checkpoint(model, out_path)
+                extra = {"grad_norm": trainer.last_grad_norm(), "lr": trainer.last_lr(), "skipped": trainer.skipped_steps()} if opt_on else {}
                 emit({"run": tag, "epoch": epoch, "loss_last_batch": round(trainer.last_loss(), 5), "acc_train": round(acc_tr, 4),
-                      "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2)})
+                      "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), **extra})
         if rank == 0 and out_path and (not keep_best or best[1] < 0):
             save_reference_checkpoint(model, out_path)
         return {"acc_train_last": acc_tr, "acc_val_last": acc_va, "best_val_acc": best[0], "best_epoch": best[1]}
@@ -245,8 +274,11 @@ def main(argv=None) -> int:
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
             models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize).to(dev).train())
+        steps_per_epoch = concurrent_epoch(runs, args.batch, 0, lambda idxs: None)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
-                                loss=loss_for(args, y_np))
+                                loss=loss_for(args, y_np), clip_grad_norm=args.clip_grad_norm,
+                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch))
+        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
         t0 = time.time()
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in runs]
@@ -262,12 +294,14 @@ def main(argv=None) -> int:
             last = epoch == args.epochs - 1
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
+                norms, lr_now, skipped = (mbt.last_grad_norms(), mbt.last_lr(), mbt.skipped_steps()) if opt_on else (None, None, None)
                 for k, r in enumerate(runs):
                     acc_tr = evaluate(models[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
                     acc_va = evaluate(models[k], x_all[r["va"]], y_all[r["va"]])
                     res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
                     emit({"run": tag(r), "epoch": epoch, "loss_last_batch": round(losses[k], 5), "acc_train": round(acc_tr, 4),
-                          "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), "concurrent": True})
+                          "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
+                          **({"grad_norm": norms[k], "lr": lr_now, "skipped": skipped[k]} if opt_on else {})})
         accs = []
         for k, r in enumerate(runs):
             accs.append(res[k]["acc_val_last"])

@@ -9,7 +9,9 @@ Per step and per GPU the stream sees, for the reference model's shape, three lau
 pooling + head + CE + head backward (nsd_lstm_head_train_rng, the dropout / RReLU streams drawn in the kernel), BPTT
 (nsd_lstm_bwd_rng), slab reduction + Adam (nsd_grad_reduce_adam); with more than one rank the last becomes
 nsd_grad_reduce -> ONE all-reduce of the flat fp32 gradient over RCCL -> nsd_adam_step.  Other shapes run the unfused
-equivalents (ops.train_step_grads).  Nothing synchronises the host.  What the kernels see of (windows, labels, seed, step) and the
+equivalents (ops.train_step_grads).  With clip_grad_norm= / lr_schedule= the last launch becomes nsd_grad_reduce_clip_adam (one rank) or
+nsd_grad_norm + nsd_adam_step_clip behind the all-reduce: global-norm clipping and the schedule are evaluated by the update kernel
+(DESIGN.md 4.4).  Nothing synchronises the host.  What the kernels see of (windows, labels, seed, step) and the
 step's four random-stream slots are defined in one place, step_recipe.py, for this trainer's eager and hipGraph steps and ModelBatchTrainer.
 
 Data parallelism: trials are independent, so the global batch is split contiguously over ranks
@@ -95,7 +97,8 @@ def broadcast_parameters(flat: torch.Tensor, group=None, src: int = 0) -> None:
 class Trainer:
     def __init__(self, model: EEG_LSTM, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None,
-                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None):
+                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None,
+                 clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None):
         self.model = model
         self.spec = model.spec
         self.flat = model.flat_parameters()
@@ -104,6 +107,13 @@ class Trainer:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
+        # global-norm clipping (clip_grad_norm: the threshold; 0.0: report the norm and skip non-finite steps without clipping) and the
+        # learning-rate schedule, both evaluated by the update kernel (nsd_opt, include/nsd.h).  Both None: the plain step, launch for launch.
+        if clip_grad_norm is not None and not clip_grad_norm >= 0.0:
+            raise ValueError(f"Trainer: clip_grad_norm {clip_grad_norm!r} negative or NaN")
+        self.clip_grad_norm, self.lr_schedule = clip_grad_norm, lr_schedule
+        self._opt_on = clip_grad_norm is not None or lr_schedule is not None
+        self._opt_state = ops.opt_state(self.flat.numel(), 1, self.flat.device) if self._opt_on else None
         # the flat gradient with ONE extra element behind it: the bf16 path's failure flag (ops.seq_guard).  The whole buffer is
         # what the ranks all-reduce, so a scan time-out on ANY rank makes EVERY rank skip the update (guarded Adam) -- still
         # one collective per step.  Always 0 on the fp32 path.
@@ -179,9 +189,27 @@ class Trainer:
         return dict(step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                     weight_decay=self.weight_decay)
 
-    def _adam(self) -> None:
+    def _opt(self):
+        """nsd_opt of this trainer (clipping / schedule on)"""
+        return ops.opt_struct(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
+                              max_norm=self.clip_grad_norm, schedule=self.lr_schedule)
+
+    def _fused_tail(self, step_dev: Optional[torch.Tensor] = None) -> dict:
+        """adam= of ops.train_step_grads: the update in the reduction's tail (with clipping / a schedule: nsd_grad_reduce_clip_adam)"""
+        if not self._opt_on:
+            return dict(m=self.m, v=self.v, **self._hyper())
+        return dict(m=self.m, v=self.v, opt=self._opt(), opt_state=self._opt_state, step=self.step_count, step_dev=step_dev)
+
+    def _adam(self, step_dev: Optional[torch.Tensor] = None) -> None:
         # bf16 path: skipped on the device when any rank's scan timed out (self._skip, summed over ranks by the all-reduce)
-        ops.adam_step(self.flat, self.grads, self.m, self.v, skip=self._skip if self.model.precision == "bf16" else None, **self._hyper())
+        skip = self._skip if self.model.precision == "bf16" else None
+        if self._opt_on:
+            # flat route: every rank forms the norm of the same all-reduced bits, hence the same coef
+            opt = self._opt()
+            ops.grad_norm(self.grads, self._opt_state, opt.grad_scale)
+            ops.adam_step_clip(self.flat, self.grads, self.m, self.v, opt, self._opt_state, step=self.step_count, step_dev=step_dev, skip=skip)
+            return
+        ops.adam_step(self.flat, self.grads, self.m, self.v, skip=skip, step_dev=step_dev, **self._hyper())
 
     def _masks(self, buf: dict, step_dev: Optional[torch.Tensor] = None):
         """Fill the step's explicit mask tensors (those the model needs) from its streams -> (drop_lstm, rrelu, drop_head)."""
@@ -228,7 +256,7 @@ class Trainer:
             (dl, sl, dh), rng = self._masks(buf), None
         ops.train_step_grads(sp, self.flat, x, buf["ws"], y, buf["logits"], self.grads, scale=scale, drop_lstm=dl,
                              rrelu_slope=sl, drop_head=dh, residual=self.model.residual, fused_head=self.fused_head, rng=rng,
-                             adam=dict(m=self.m, v=self.v, **self._hyper()) if fuse_adam else None, targets=tg)
+                             adam=self._fused_tail() if fuse_adam else None, targets=tg)
 
     # ---- hipGraph path ------------------------------------------------------------------------------------
     def static_inputs(self, B: int, T: int):
@@ -247,7 +275,8 @@ class Trainer:
         return buf["x"], buf["y"]
 
     def _issue_segment_a(self, B: int, T: int) -> None:
-        """step counter, random streams, lstm fwd, fused head, lstm bwd, slab reduce -> self.grads"""
+        """step counter, random streams, lstm fwd, fused head, lstm bwd, slab reduce -> self.grads (one rank with clipping / a schedule:
+        the clipped tail rides here as in the eager step, reading the device counter, and segment B is empty)"""
         buf = self._buffers(B, T)
         ops.step_counter_inc(self._step_dev)
         if self.stochastic and not all(k in buf for k in ("drop_lstm", "rrelu", "drop_head")):
@@ -257,10 +286,11 @@ class Trainer:
         xin, y, tg = self.recipe.prepare(buf["x"], buf["y"], [self.seed], 0, step_dev=self._step_dev, bufs=buf)
         ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], y, buf["logits"], self.grads,
                              scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual,
-                             targets=tg)
+                             adam=self._fused_tail(self._step_dev) if self._opt_on and self.world == 1 else None, targets=tg)
 
     def _issue_segment_b(self) -> None:
-        ops.adam_step(self.flat, self.grads, self.m, self.v, step_dev=self._step_dev, **self._hyper())
+        if not (self._opt_on and self.world == 1):
+            self._adam(step_dev=self._step_dev)
 
     @_on_own_device
     def step_static(self, B: int, T: int) -> None:
@@ -350,14 +380,44 @@ class Trainer:
         ops.loss_sum(self.spec, ws, self._last_B, self._last_T, out=self._loss)
         return float(self._loss.item()) / self._last_B
 
+    # ---- clipping / schedule readouts (all synchronise) ---------------------------------------------------------------
+    def _record(self) -> Optional[dict]:
+        """The device record of the last clipped / scheduled update; None with both options off or before the first step."""
+        if not self._opt_on or not self._last_B:
+            return None
+        with torch.cuda.device(self.flat.device):
+            return ops.opt_records(self._opt_state)[0]
+
+    def last_grad_norm(self) -> float:
+        """Global L2 norm of the last step's gradient before clipping (NaN with clip_grad_norm / lr_schedule off, or before a step)."""
+        rec = self._record()
+        return float("nan") if rec is None else rec["norm"]
+
+    def last_lr(self) -> float:
+        """Learning rate of the last update, as the kernel formed it; before the first step or with both options off, lr * f(step)
+        from the host."""
+        rec = self._record()
+        if rec is not None:
+            return rec["lr"]
+        opt = self._opt()
+        return float(torch.tensor(float(opt.lr) * ops.lr_factor(opt, max(self.step_count, 1)), dtype=torch.float32))
+
+    def skipped_steps(self) -> int:
+        """Updates skipped on the device because the gradient norm was not finite (sticky; 0 with both options off)."""
+        return ops.opt_records(self._opt_state)[0]["skipped"] if self._opt_on else 0
+
     def state_dict(self):
         return {"model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
-                "adam_m": self.m.cpu(), "adam_v": self.v.cpu(), "step": self.step_count}
+                "adam_m": self.m.cpu(), "adam_v": self.v.cpu(), "step": self.step_count, "skipped": self.skipped_steps()}
 
     def load_state_dict(self, sd):
         self.model.load_state_dict(sd["model"], strict=True)
         self.flat = self.model.flat_parameters()
         self.m.copy_(sd["adam_m"]); self.v.copy_(sd["adam_v"]); self.step_count = int(sd["step"])
+        # the schedule resumes with the step (f depends on it alone); the sticky counter goes back into the device record
+        if self._opt_on:
+            self._opt_state[12:16].view(torch.int32).fill_(int(sd.get("skipped", 0)))
+            self._step_dev.fill_(self.step_count)            # a captured graph reads the step, and with it the schedule, from here
 
 
 def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:

@@ -34,7 +34,14 @@ GRID = [("baseline", []),
         ("mixup1", ["--mixup", "1.0"]),
         ("smooth0.1_balanced", ["--label-smoothing", "0.1", "--class-weights", "balanced"]),
         ("mixup0.5_smooth0.1", ["--mixup", "0.5", "--label-smoothing", "0.1"]),
-        ("shift12_mixup1_smooth0.1_balanced", ["--aug-shift", "12", "--mixup", "1.0", "--label-smoothing", "0.1", "--class-weights", "balanced"])]
+        ("shift12_mixup1_smooth0.1_balanced", ["--aug-shift", "12", "--mixup", "1.0", "--label-smoothing", "0.1", "--class-weights", "balanced"]),
+        # optimizer recipes (clipping / schedules in the step tail); not run yet -- no accuracy is claimed for them
+        ("clip1", ["--clip-grad-norm", "1.0"]),
+        ("clip0.1", ["--clip-grad-norm", "0.1"]),
+        ("cosine_warm50", ["--lr-schedule", "cosine", "--warmup-steps", "50", "--lr-min-ratio", "0.05"]),
+        ("clip1_cosine_warm50", ["--clip-grad-norm", "1.0", "--lr-schedule", "cosine", "--warmup-steps", "50", "--lr-min-ratio", "0.05"]),
+        ("shift12_clip1_cosine_warm50", ["--aug-shift", "12", "--clip-grad-norm", "1.0", "--lr-schedule", "cosine", "--warmup-steps", "50",
+                                         "--lr-min-ratio", "0.05"])]
 
 
 def main():
