@@ -138,19 +138,21 @@ __device__ __forceinline__ void load_wT(const float *w, const int og, const int 
 // One trial per workgroup: the per-step factors of one layer's cells for macro step mn, from the staged records -- what every gate
 // lane of the recurrences used to form for itself, once per unit and one step ahead (by x1 waves 0 / 1 for layer 1 / 0; by the loader
 // wave for a trial's first step).  c_t is the c[t-1] field of the record one macro step earlier (c[T-1], `cT1`, at the first step).
+// INSIDE (h48_bwd_sched::x1m_inside): the step is neither a trial's first (t == T - 1) nor its last (t == 0) nor past it -- no test.
+// `has_mk`: layer 0 has dropout multipliers (a.mask || a.rng.on, formed once per launch by the caller).
 struct PrepIn { float4 gc; float cprev, ct, mk; float2 ad; };
-__device__ __forceinline__ PrepIn prep_load(const Lstm2BwdArgs &a, Smem<1> &sm, const int mn, const int layer, const int u, const float cT1) {
-    const int T = a.T;
+template <bool INSIDE = false>
+__device__ __forceinline__ PrepIn prep_load(const int T, const bool has_mk, Smem<1> &sm, const int mn, const int layer, const int u, const float cT1) {
     const int t = layer == 1 ? T - 1 - mn : T + 1 + dl0(1) - mn;
     const float *rec = &sm.stage[(mn >> 3) & 1][0][layer][mn & 7][0];
     const float *recp = &sm.stage[((mn - 1) >> 3) & 1][0][layer][(mn - 1) & 7][0];
     PrepIn in;
     in.gc = *reinterpret_cast<const float4 *>(rec + 4 * u);
-    in.cprev = t > 0 ? rec[192 + u] : 0.f;
-    in.ct = t == T - 1 ? cT1 : recp[192 + u];
+    in.cprev = (INSIDE || t > 0) ? rec[192 + u] : 0.f;
+    in.ct = (!INSIDE && t == T - 1) ? cT1 : recp[192 + u];
     in.ad = make_float2(0.f, 0.f); in.mk = 1.f;
     if (layer == 1) in.ad = *reinterpret_cast<const float2 *>(rec + 240);
-    else if (a.mask || a.rng.on) in.mk = rec[240 + u];
+    else if (has_mk) in.mk = rec[240 + u];
     return in;
 }
 __device__ __forceinline__ void prep_finish(Smem<1> &sm, const PrepIn &in, const int mn, const int layer, const int u, const float dpu, const float awu) {
@@ -163,7 +165,7 @@ __device__ __forceinline__ void prep_finish(Smem<1> &sm, const PrepIn &in, const
 }
 __device__ __forceinline__ void prep_layer(const Lstm2BwdArgs &a, Smem<1> &sm, const int mn, const int layer, const int u,
                                            const float dpu, const float awu, const float cT1) {
-    const PrepIn in = prep_load(a, sm, mn, layer, u, cT1);
+    const PrepIn in = prep_load(a.T, a.mask || a.rng.on, sm, mn, layer, u, cT1);
     prep_finish(sm, in, mn, layer, u, dpu, awu);
 }
 
@@ -200,7 +202,7 @@ __device__ __forceinline__ void chain_role(const A &a, Smem<NB> &sm, const int l
         const int tb = layer == 1 ? T - 1 : T + 1 + dl0(NB);      // t = tb - m
         for (int m0 = 0; m0 < n_steps; m0 += CHUNK) {
             const int sb = (m0 / CHUNK) & 1;
-            ring_block<NB, CHUNK>(m0 >= tb - T + 2 && m0 + CHUNK - 1 <= tb, [&](const int k, const auto inside) {
+            ring_block<NB, CHUNK>(h48_bwd_sched::chain_inside(layer, T, m0, dl0(NB)), [&](const int k, const auto inside) {
                 const int t = tb - (m0 + k);
                 const bool active = inside.value || (t >= 0 && t < T);
                 const bool prev_active = inside.value || (t + 1 >= 0 && t + 1 < T);
@@ -359,8 +361,17 @@ __device__ __forceinline__ float rows_reduce_scatter4(const f32x4 v) {
     const u32x2v q = __builtin_amdgcn_permlane16_swap(__float_as_uint(s02), __float_as_uint(s13), false, false);
     return __uint_as_float(q[0]) + __uint_as_float(q[1]);
 }
-template <class A>
-__device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int g, const int lane, const int n_steps) {
+// DUTY: the layer whose factors this wave prepares for the NEXT macro step (wave 0 of the role: layer 1, wave 1: layer 0), or -1 (wave 2).
+// RES (residual pass-through) and DX (the input gradient's operand leaves from the wave without a prep duty: nsd_lstm_bwd with dx
+// only) are per-launch flags: one loop each, chosen in front of the role (x1m_dispatch), so that no step tests them.  Blocks that
+// h48_bwd_sched::x1m_inside names run without a test of the step index; the others keep the tests, rolled up (ring_block).
+template <int DUTY, bool RES, bool DX, class A>
+__device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int lane_in, const int n_steps) {
+    static_assert(!DX || DUTY < 0, "the input gradient's operand leaves from the wave without a prep duty");
+    int lane = lane_in;                                             // (kept out of the block in front of the dispatch: see dw16_role)
+    asm volatile("; x1m %1" : "+v"(lane) : "n"(4 * (DUTY + 1) + 2 * (RES ? 1 : 0) + (DX ? 1 : 0)));
+    constexpr int g = DUTY == 1 ? 0 : DUTY == 0 ? 1 : 2;            // wave of the role = which 16 output units
+    constexpr int sched = DUTY == 1 ? h48_bwd_sched::X1_PREP1 : DUTY == 0 ? h48_bwd_sched::X1_PREP0 : DX ? h48_bwd_sched::X1_DX : h48_bwd_sched::X1_PLAIN;
     const int T = a.T, B = a.B;
     const int ks = lane >> 4, ub = (lane >> 2) & 3, jc = lane & 3;  // MFMA operand coordinates: k slice, unit block, A: unit in block / B: step
     float wv[H];
@@ -368,15 +379,16 @@ __device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int g, c
     for (int sidx = 0; sidx < H; ++sidx) wv[sidx] = a.w_ih1[(size_t)(48 * ks + sidx) * H + 16 * g + 4 * ub + jc];
     const int uo = 16 * g + 4 * ub + ks;                            // after the reduce-scatter: this lane's unit, for step c0 + jc
     const float awo = a.attn_w[uo];
-    // prep duty: wave 0 of the role prepares layer 1's factors of the NEXT macro step, wave 1 layer 0's
-    const int pu = lane < H ? lane : lane - 16, pl = g == 0 ? 1 : 0;
+    constexpr int pl = DUTY == 1 ? 1 : 0;
+    const int pu = lane < H ? lane : lane - 16;
     const float p_aw = a.attn_w[pu];
+    const bool has_mk = a.mask || a.rng.on;
     Prof prof = prof_init(a.dbg);
     for (int grp = wg_id(a); grp < B; grp += wg_count(a)) {
         const int b0 = grp;
-        const float dpo = a.residual ? a.dpooled[(size_t)b0 * H + uo] : 0.f;
+        const float dpo = RES ? a.dpooled[(size_t)b0 * H + uo] : 0.f;
         float p_dp = 0.f, p_c = 0.f;
-        if (g < 2) {
+        if constexpr (DUTY >= 0) {
             p_dp = a.dpooled[(size_t)b0 * H + pu];
             p_c = (pl == 1 ? a.cseq1 : a.cseq0)[((size_t)b0 * T + (T - 1)) * H + pu];
         }
@@ -385,12 +397,12 @@ __device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int g, c
             asm volatile("" : "+v"(wv[s4]), "+v"(wv[s4 + 1]), "+v"(wv[s4 + 2]), "+v"(wv[s4 + 3]), "+v"(wv[s4 + 4]), "+v"(wv[s4 + 5]), "+v"(wv[s4 + 6]), "+v"(wv[s4 + 7]));
         step_barrier<false>(prof);
         for (int m0 = 0; m0 < n_steps; m0 += CHUNK) {
-#pragma unroll
-            for (int k = 0; k < CHUNK; ++k) {
+            ring_block<1, CHUNK>(h48_bwd_sched::x1m_inside(sched, T, m0), [&](const int k, const auto inside) {
+                constexpr bool IN = decltype(inside)::value;
                 const int m = m0 + k;
                 PrepIn pin;
-                if (g < 2) pin = prep_load(a, sm, m + 1, pl, pu, p_c);      // (requested ahead of the products: its latency hides there)
-                if ((k & 3) == 0 && m >= 4) {
+                if constexpr (DUTY >= 0) pin = prep_load<IN>(T, has_mk, sm, m + 1, pl, pu, p_c);      // (requested ahead of the products: its latency hides there)
+                if ((k & 3) == 0 && (IN || m >= 4)) {
                     // layer-1 macro steps c0 .. c0 + 3 = m - 4 .. m - 1 (ring slots (k + 4 + j) & 7); a column past the trial's first step
                     // (c > T - 1) holds stale da and is never used
                     const float *vj = &sm.ring[1][(k + 4 + jc) & 7][0][48 * ks];
@@ -410,26 +422,39 @@ __device__ __forceinline__ void x1m_role(const A &a, Smem<1> &sm, const int g, c
                     }
                     float inp = rows_reduce_scatter4((acc0 + acc1) + (acc2 + acc3));
                     const int c = m - 4 + jc;
-                    if (a.residual) {       // dout1 = alpha * dpooled + dscore * attn_w passes through: the scalars sit in the record of macro step c
+                    if constexpr (RES) {    // dout1 = alpha * dpooled + dscore * attn_w passes through: the scalars sit in the record of macro step c
                         const float *recp = &sm.stage[(c >> 3) & 1][0][1][c & 7][0];
                         inp += fmaf(recp[240], dpo, recp[241] * awo);
                     }
                     sm.win.din1x[(k + 4 + jc) & 7][uo] = inp;
                 }
-                if (g < 2) prep_finish(sm, pin, m + 1, pl, pu, p_dp, p_aw);
-                if (g == 2 && a.da0_out && m >= 1) {
+                if constexpr (DUTY >= 0) prep_finish(sm, pin, m + 1, pl, pu, p_dp, p_aw);
+                if constexpr (DX) {
                     // the input gradient's operand (nsd_lstm_bwd with dx): da0 of macro step m - 1 leaves as it is, 768 bytes per step, from
                     // the one wave of the role without a prep duty (in the dW waves the test alone cost the training kernel 8 us)
                     const int t0 = T + 2 + dl0(1) - m;
-                    if (t0 >= 0 && t0 < T && lane < H)
+                    if ((IN || (m >= 1 && t0 >= 0 && t0 < T)) && lane < H)
                         *reinterpret_cast<f32x4 *>(a.da0_out + ((size_t)b0 * T + t0) * G4 + 4 * lane) =
                             *reinterpret_cast<const f32x4 *>(&sm.ring[0][(k + 7) & 7][0][4 * lane]);
                 }
                 step_barrier<false>(prof);
-            }
+            });
         }
     }
     prof_store(a.dbg, prof);
+}
+// the role's loop for this wave and this launch (part: wave of the role)
+template <class A>
+__device__ __forceinline__ void x1m_dispatch(const A &a, Smem<1> &sm, const int part, const int lane, const int n_steps) {
+    if (part == 0) {
+        if (a.residual) x1m_role<1, true, false>(a, sm, lane, n_steps); else x1m_role<1, false, false>(a, sm, lane, n_steps);
+    } else if (part == 1) {
+        if (a.residual) x1m_role<0, true, false>(a, sm, lane, n_steps); else x1m_role<0, false, false>(a, sm, lane, n_steps);
+    } else if (a.da0_out) {
+        if (a.residual) x1m_role<-1, true, true>(a, sm, lane, n_steps); else x1m_role<-1, false, true>(a, sm, lane, n_steps);
+    } else {
+        if (a.residual) x1m_role<-1, true, false>(a, sm, lane, n_steps); else x1m_role<-1, false, false>(a, sm, lane, n_steps);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -602,9 +627,33 @@ __device__ __forceinline__ void split4_bf16(const f32x4 v, u32x2 &hi, u32x2 &lo)
 // Duties beside the wave's five tiles (instruction count matters more than anything else in this kernel: every role shares its SIMD
 // with a recurrence): waves 0..2 the rows h1[t-1] / in1[t] / h0[t-1] and wave 3 x[t], FOUR steps per request (lane = (step, 16-byte
 // piece) or (step, channel)), split and written every fourth step; waves 4, 5 the da of layer 1 / 0, every step, four columns per lane.
-template <class A>
-__device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int w_in, const int lane, const int n_steps_in) {
-    const int w = __builtin_amdgcn_readfirstlane(w_in), n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
+// One instantiation per duty (DUTY = wave of the role) and per RNG (multipliers drawn in the kernel: a per-launch flag), chosen in front
+// of the role (dw16_dispatch): a wave carries its own addresses and its own step and nothing of the other five duties.  A half
+// (8 steps) comes in up to three forms: FIRST (the trial's first 16 steps: no window is complete, no tiles), INSIDE (a converter's da
+// lies inside [0, T) for every step: h48_bwd_sched::dw_conv_inside; the row duties have no test of the step index) and tested.
+// LDS addresses: the windows lie past the reach of an LDS instruction's 16-bit offset from the start of the workgroup's memory, and
+// hipcc kept every (lane part + region) sum it met in a register of its own -- two dozen of them, spilled in front of the loop and
+// reloaded in it.  So a wave holds one lane base INSIDE each region it touches (da windows, row windows, ring), made opaque once per
+// half, and everything else is an immediate or the window bit of the step (one v_add per half or tile).
+#define NSD_LDS __attribute__((address_space(3)))
+typedef NSD_LDS unsigned short lds_u16;
+constexpr int SA_W = WK * ARS, SA_HL = 2 * SA_W, SA_L = 2 * SA_HL;   // strides of DwWin::wa [layer][hi, lo][window][k][column] in elements
+constexpr int SB_W = WK * BRS, SB_HL = 2 * SB_W, SB_L = 2 * SB_HL;   // ... of DwWin::wb
+static_assert(sizeof(DwWin::wa) < 65536 && sizeof(DwWin::wb) < 65536, "a window region within reach of one lane base");
+// window_frag from a lane base: p = first k row's address of this lane (window_frag's lane recipe, formed once per wave)
+template <int RS>
+__device__ __forceinline__ bf16x8 lds_frag(const lds_u16 *p) {
+    const s16x4 e0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 NSD_LDS *)(p));
+    const s16x4 e1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 NSD_LDS *)(p + 4 * RS));
+    return cat_tr(e0, e1);
+}
+template <int DUTY, bool RNG, class A>
+__device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int lane_in, const int n_steps_in) {
+    constexpr int w = DUTY;
+    // (the lane index through an instantiation's own empty statement: what the twelve instantiations compute alike stays in them)
+    int lane = lane_in;
+    asm volatile("; dw16 %1" : "+v"(lane) : "n"(2 * DUTY + (RNG ? 1 : 0)));
+    const int n_steps = __builtin_amdgcn_readfirstlane(n_steps_in);
     const A a = uniform_copy(a_in);
     DwWin &win = sm.win;
     const int T = a.T, B = a.B, C = a.C;
@@ -618,30 +667,52 @@ __device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int 
     const float *src = w == 0 ? a.hseq1 : w == 1 ? a.in1seq : w == 2 ? a.hseq0 : a.x;
     const int rw = w == 3 ? C : H;                                  // floats per time step of the source
     const int rs = w == 3 ? lane >> 4 : l48 / 12, rp = w == 3 ? lane & 15 : l48 - 12 * rs;
-    const int rl = w < 2 ? 1 : 0;                                   // layer of the window the rows go to
+    constexpr int rl = w < 2 ? 1 : 0;                               // layer of the window the rows go to
     const int rc = w == 3 ? H + rp : (w == 1 ? H : 0) + 4 * rp;     // first window column of this lane
     const long sbytes = (long)B * T * rw * 4;
     const __amdgpu_buffer_rsrc_t r_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(src), 0, (int)(sbytes > 0x7fffffffL ? 0x7fffffffL : sbytes), 0x00020000);
     constexpr unsigned DROP = 0x80000000u;
-    // layer-0 dropout multipliers drawn in the kernel: one value per dW lane and chunk, a chunk ahead like the loader (as before)
-    const int L = w * 64 + lane, mk_k = L / H, mk_j = L - mk_k * H;
+    // lane bases: fa / fb = this lane's first k row of a transposed read (window_frag's recipe) in wa (this wave's 32 rows) / wb;
+    // cw / cr = a converter's four columns in its layer's da windows / in the ring; rwp = a row duty's (step, piece) in its layer's row windows
+    constexpr int cl = w >= 4 ? 5 - w : 0;
+    lds_u16 *fa, *fb, *cw = nullptr, *rwp = nullptr;
+    const NSD_LDS float *cr = nullptr;
+    {
+        const int G = lane >> 4, i = lane & 15;
+        fa = (lds_u16 *)(&win.wa[0][0][0][0][0]) + (8 * (G >> 1) + (i >> 2)) * ARS + 32 * w + 16 * (G & 1) + 4 * (i & 3);
+        fb = (lds_u16 *)(&win.wb[0][0][0][0][0]) + (8 * (G >> 1) + (i >> 2)) * BRS + 16 * (G & 1) + 4 * (i & 3);
+        if constexpr (w >= 4) {
+            cw = (lds_u16 *)(&win.wa[cl][0][0][0][0]) + 4 * l48;
+            cr = (const NSD_LDS float *)(&sm.ring[cl][0][0][0]) + 4 * l48;
+        } else {
+            rwp = (lds_u16 *)(&win.wb[rl][0][0][0][0]) + rs * BRS + rc;
+        }
+    }
+    // layer-0 dropout multipliers drawn in the kernel: one value per dW lane and chunk, a chunk ahead like the loader.  The counter of
+    // the draw is ((b T + t) H + unit) with t = T + 1 + DL0 - 8 chunk - mk_k: a 64-bit scalar per chunk plus ONE signed lane constant
+    int mk_k = 0, mk_c = 0, mk_o = 0;                               // lane: step in chunk, unit - 48 step, float offset in a stage buffer
+    if constexpr (RNG) {
+        const int L = w * 64 + lane, mk_j = L - (L / H) * H;
+        mk_k = L / H; mk_c = mk_j - mk_k * H; mk_o = mk_k * REC + 240 + mk_j;
+    }
     auto gen_mask = [&](const int chunk, const int b) {
-        const int t = T + 1 + dl0(1) - (chunk * CHUNK + mk_k);
+        asm volatile("" : "+v"(mk_k), "+v"(mk_c), "+v"(mk_o));
+        const int tc = T + 1 + dl0(1) - chunk * CHUNK, t = tc - mk_k;
         if (t >= 0 && t < T)
-            sm.stage[chunk & 1][0][0][mk_k][240 + mk_j] =
-                nsd_rand_u32(a.rng.seed, a.rng.base, ((uint64_t)b * T + t) * H + mk_j) < a.rng.thr_lstm ? 0.f : a.rng.keep_lstm;
+            (&sm.stage[chunk & 1][0][0][0][0])[mk_o] =
+                nsd_rand_u32(a.rng.seed, a.rng.base, ((uint64_t)b * T + tc) * H + (int64_t)mk_c) < a.rng.thr_lstm ? 0.f : a.rng.keep_lstm;
     };
     bf16x8 ah, al;                                                  // this wave's rows of a window, kept over the window's tiles of one layer
-    auto a_frags = [&](const int W, const int layer) {
-        ah = window_frag<ARS>(&win.wa[layer][0][W & 1][0][0], 32 * w, lane);
-        al = window_frag<ARS>(&win.wa[layer][1][W & 1][0][0], 32 * w, lane);
-    };
-    auto tile = [&](const int W, auto qc) {
+    auto tile = [&](const int Wn, auto qc) {
         constexpr int q = decltype(qc)::value;
         constexpr int layer = q < 3 ? 1 : 0, ni = q < 3 ? q : q - 3;
-        if (q == 0 || q == 3) a_frags(W, layer);
-        const bf16x8 bh = window_frag<BRS>(&win.wb[layer][0][W & 1][0][0], 32 * ni, lane);
-        const bf16x8 bl = window_frag<BRS>(&win.wb[layer][1][W & 1][0][0], 32 * ni, lane);
+        const lds_u16 *faw = fa + (Wn & 1) * SA_W, *fbw = fb + (Wn & 1) * SB_W;
+        if (q == 0 || q == 3) {
+            ah = lds_frag<ARS>(faw + layer * SA_L);
+            al = lds_frag<ARS>(faw + layer * SA_L + SA_HL);
+        }
+        const bf16x8 bh = lds_frag<BRS>(fbw + layer * SB_L + 32 * ni);
+        const bf16x8 bl = lds_frag<BRS>(fbw + layer * SB_L + SB_HL + 32 * ni);
         if (!ablated(a.ablate, 1)) {
             acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[q], 0, 0, 0);
             acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[q], 0, 0, 0);
@@ -659,18 +730,19 @@ __device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int 
     const int ngrp = B;
     for (int grp = wg_id(a); grp < ngrp; grp += wg_count(a)) {
         const int b = grp;
-        if (a.rng.on) gen_mask(0, b);
+        if (RNG) gen_mask(0, b);
         // rows of macro steps m .. m + 3 (this lane: m + rs); out of range -> zeros (switched off at the ADDRESS)
         auto request = [&](const int m) -> f32x4 {
             const int t = (rl == 1 ? T - 1 : T + 1 + dl0(1)) - m - rs;
             const int tt = (w == 1 || w == 3) ? t : t - 1;
             const bool ok = t >= 0 && t < T && tt >= 0 && (w != 3 || rp < C);
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            // (offsets in 32 bits: B * T * H * 4 < 2 GB on this instantiation, bwd48_domain)
             if (w == 3) {
-                const unsigned off = ok ? (unsigned)((((size_t)b * T + tt) * C + rp) * 4) : DROP;
+                const unsigned off = ok ? ((unsigned)(b * T + tt) * (unsigned)C + (unsigned)rp) * 4u : DROP;
                 v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_s, (int)off, 0, 0));
             } else {
-                const unsigned off = ok ? (unsigned)((((size_t)b * T + tt) * H + 4 * rp) * 4) : DROP;
+                const unsigned off = ok ? ((unsigned)(b * T + tt) * (unsigned)H + 4u * (unsigned)rp) * 4u : DROP;
                 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_s, (int)off, 0, 0));
             }
             return v;
@@ -678,55 +750,86 @@ __device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int 
         f32x4 bq = {0.f, 0.f, 0.f, 0.f};
         if (w < 4) bq = request(0);
         step_barrier<false>(prof);      // pairs with the stage-initialisation barrier of the other roles
-        auto half = [&](const int m0, auto phc) {
+        auto half = [&](const int m0, auto phc, auto firstc, auto insidec) {
             constexpr int PH = decltype(phc)::value;
+            constexpr bool FIRST = decltype(firstc)::value, INSIDE = decltype(insidec)::value;
+            asm volatile("" : "+v"(fa), "+v"(fb));
+            if constexpr (w >= 4) asm volatile("" : "+v"(cw), "+v"(cr)); else asm volatile("" : "+v"(rwp));
+            const int wi = (m0 >> 4) & 1;                            // window of the half's steps
             static_for([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 const int m = m0 + k;
                 constexpr int p = PH + k;                            // m & 15
-                const int wi = (m >> 4) & 1;
-                if (w >= 4 && m >= 1) {                              // da of macro step m - 1 (written by the chains at that step)
-                    const int mm = m - 1, cl = 5 - w;
+                if constexpr (w >= 4) if (INSIDE || m >= 1) {        // da of macro step m - 1 (written by the chains at that step)
+                    const int mm = m - 1;
+                    constexpr int pm = (p + 15) & 15;                // mm & 15; its window is this half's except in front of a window's first step
+                    const int wm = p == 0 ? wi ^ 1 : wi;
                     const int t = cl == 1 ? T - 1 - mm : T + 1 + dl0(1) - mm;
-                    f32x4 v = *reinterpret_cast<const f32x4 *>(&sm.ring[cl][mm & (RING - 1)][0][4 * l48]);
-                    if (!(t >= 0 && t < T)) v = f32x4{0.f, 0.f, 0.f, 0.f};       // (the chains do not write on inactive steps)
+                    f32x4 v = *reinterpret_cast<const NSD_LDS f32x4 *>(cr + ((k + RING - 1) & (RING - 1)) * G4);
+                    if (!INSIDE && !(t >= 0 && t < T)) v = f32x4{0.f, 0.f, 0.f, 0.f};       // (the chains do not write on inactive steps)
                     u32x2 hi, lo;
                     split4_bf16(v, hi, lo);
-                    *reinterpret_cast<u32x2 *>(&win.wa[cl][0][(mm >> 4) & 1][mm & 15][4 * l48]) = hi;
-                    *reinterpret_cast<u32x2 *>(&win.wa[cl][1][(mm >> 4) & 1][mm & 15][4 * l48]) = lo;
+                    *reinterpret_cast<NSD_LDS u32x2 *>(cw + wm * SA_W + pm * ARS) = hi;
+                    *reinterpret_cast<NSD_LDS u32x2 *>(cw + wm * SA_W + pm * ARS + SA_HL) = lo;
                 }
-                if (w < 4 && (k & 3) == 0) {                         // the rows of steps m .. m + 3, requested four steps ago
+                if constexpr (w < 4 && (k & 3) == 0) {               // the rows of steps m .. m + 3, requested four steps ago
                     if (w == 3) {
                         unsigned short hi, lo;
                         split1_bf16(bq[0], hi, lo);
-                        win.wb[0][0][wi][p + rs][rc] = hi;
-                        win.wb[0][1][wi][p + rs][rc] = lo;
+                        rwp[wi * SB_W + p * BRS] = hi;
+                        rwp[wi * SB_W + p * BRS + SB_HL] = lo;
                     } else {
                         u32x2 hi, lo;
                         split4_bf16(bq, hi, lo);
-                        *reinterpret_cast<u32x2 *>(&win.wb[rl][0][wi][p + rs][rc]) = hi;
-                        *reinterpret_cast<u32x2 *>(&win.wb[rl][1][wi][p + rs][rc]) = lo;
+                        *reinterpret_cast<NSD_LDS u32x2 *>(rwp + wi * SB_W + p * BRS) = hi;
+                        *reinterpret_cast<NSD_LDS u32x2 *>(rwp + wi * SB_W + p * BRS + SB_HL) = lo;
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     bq = request(m + 4);
                 }
-                if (a.rng.on && k == 1) gen_mask((m >> 3) + 1, b);  // second step of a chunk: the old records are dead
-                if (p >= 1 && p <= 5 && m >= 17) tile((m - 17) >> 4, std::integral_constant<int, (p >= 1 && p <= 5) ? p - 1 : 0>{});
+                if (RNG && k == 1) gen_mask((m >> 3) + 1, b);       // second step of a chunk: the old records are dead
+                if (p >= 1 && p <= 5 && !FIRST) tile((m - 17) >> 4, std::integral_constant<int, (p >= 1 && p <= 5) ? p - 1 : 0>{});
                 step_barrier<false, DW_SLEEP>(prof);
             }, std::make_integer_sequence<int, 8>{});
         };
-        for (int m0 = 0; m0 < n_steps; m0 += 16) {
-            half(m0, std::integral_constant<int, 0>{});
-            if (m0 + 8 < n_steps) half(m0 + 8, std::integral_constant<int, 8>{});
+        // A half WITH tiles (the first of a window) comes in one form per loop -- steady state, then the trial's end: with both forms
+        // inside one loop the five accumulator tiles meet behind every choice and hipcc spills them.  A half without tiles may choose.
+        // (A row duty has one form per half: it is handed INSIDE = true.)
+        constexpr auto PH0 = std::integral_constant<int, 0>{};
+        constexpr auto PH8 = std::integral_constant<int, 8>{};
+        auto second_half = [&](const int m0) {
+            bool in = true;
+            if constexpr (DUTY >= 4) in = h48_bwd_sched::dw_conv_inside(5 - DUTY, T, m0);
+            if (in) half(m0, PH8, std::false_type{}, std::true_type{});
+            else    half(m0, PH8, std::false_type{}, std::false_type{});
+        };
+        // the first 16 steps: no window is complete (h48_bwd_sched::dw_tiles), the converters test every step.  (The step index of the
+        // first half through an empty statement: as a literal, every lane value of its four requests is formed in front of the trial
+        // loop and kept over it.)
+        int m0 = 0;
+        asm volatile("" : "+s"(m0));
+        half(m0, PH0, std::true_type{}, std::integral_constant<bool, (DUTY < 4)>{});
+        if (8 < n_steps) second_half(m0 + 8);
+        m0 += 16;
+        for (; m0 < n_steps && (DUTY < 4 || h48_bwd_sched::dw_conv_inside(5 - DUTY, T, m0)); m0 += 16) {
+            half(m0, PH0, std::false_type{}, std::true_type{});
+            if (m0 + 8 < n_steps) second_half(m0 + 8);
         }
+        if constexpr (DUTY >= 4)
+            for (; m0 < n_steps; m0 += 16) {
+                half(m0, PH0, std::false_type{}, std::false_type{});
+                if (m0 + 8 < n_steps) second_half(m0 + 8);
+            }
         // behind the loop: the last window's tiles.  Its row of the last macro step (always an inactive one: n_steps >= T + 3) and, when
         // the step count is 8 mod 16, its second half get zeros in THIS wave's da columns.
         {
-            const int Wl = (n_steps - 1) >> 4, cl = lane >> 5, cc = 32 * w + (lane & 31);
+            int lz = lane;
+            asm volatile("" : "+v"(lz), "+v"(fa), "+v"(fb));
+            const int Wl = (n_steps - 1) >> 4, zl = lz >> 5, cc = 32 * w + (lz & 31);
             const int k0 = (n_steps - 1) & 15;
             for (int k = k0; k < 16; ++k) {
-                win.wa[cl][0][Wl & 1][k][cc] = 0;
-                win.wa[cl][1][Wl & 1][k][cc] = 0;
+                win.wa[zl][0][Wl & 1][k][cc] = 0;
+                win.wa[zl][1][Wl & 1][k][cc] = 0;
             }
             tile(Wl, std::integral_constant<int, 0>{});
             tile(Wl, std::integral_constant<int, 1>{});
@@ -750,6 +853,17 @@ __device__ __forceinline__ void dw16_role(const A &a_in, Smem<1> &sm, const int 
             if (okc) slab[base + (size_t)row * ld + col] = acc[q][r];
         }
     }
+}
+#undef NSD_LDS
+// the role's instantiation for this wave and this launch (part: wave of the role)
+template <class A>
+__device__ __forceinline__ void dw16_dispatch(const A &a, Smem<1> &sm, const int part, const int lane, const int n_steps) {
+    static_for([&](auto wc) {
+        constexpr int W = decltype(wc)::value;
+        if (part == W) {
+            if (a.rng.on) dw16_role<W, true>(a, sm, lane, n_steps); else dw16_role<W, false>(a, sm, lane, n_steps);
+        }
+    }, std::make_integer_sequence<int, 6>{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -860,6 +974,7 @@ __device__ __forceinline__ void loader_role(const A &a, Smem<NB> &sm, const int 
             if constexpr (NB == 1) {
                 // next chunk: 4 pieces per step during steps 0..4; all landed before step 6 ends -- the x1 waves prepare the factors of the
                 // chunk's first step during step 7
+                // (chunks wholly inside [0, T) without the pieces' range test: measured, no gain -- profiles/h48_bwd_helper_loops.md)
                 if (on) loader_issue<NB, 0, 4>(a, sm, d, chunk + 1, nb, b0);
                 step_barrier<true, LD_SLEEP>(prof);
                 if (on) loader_issue<NB, 4, 8>(a, sm, d, chunk + 1, nb, b0);
@@ -913,8 +1028,8 @@ __device__ __forceinline__ void loader_role(const A &a, Smem<NB> &sm, const int 
         const int role = ROLE[wave], part = PART[wave]; \
         if (role == 0)      { VIEW; __builtin_amdgcn_s_setprio(PRIO1_CHAIN); chain_role<NB>(a, sm, 1, 64 * part + lane, n_steps); } \
         else if (role == 1) { VIEW; __builtin_amdgcn_s_setprio(PRIO1_CHAIN); chain_role<NB>(a, sm, 0, 64 * part + lane, n_steps); } \
-        else if (role == 2) { VIEW; __builtin_amdgcn_s_setprio(PRIO1_X1); x1m_role(a, sm, part, lane, n_steps); } \
-        else if (role == 3) { VIEW; dw16_role(a, sm, part, lane, n_steps); } \
+        else if (role == 2) { VIEW; __builtin_amdgcn_s_setprio(PRIO1_X1); x1m_dispatch(a, sm, part, lane, n_steps); } \
+        else if (role == 3) { VIEW; dw16_dispatch(a, sm, part, lane, n_steps); } \
         else                { VIEW; __builtin_amdgcn_s_setprio(PRIO_LOADER); loader_role<NB>(a, sm, lane, n_steps); } \
     } else { \
         if (wave < 3)       { VIEW; __builtin_amdgcn_s_setprio(PRIO2_CHAIN); chain_role<NB>(a, sm, 1, tid, n_steps); } \

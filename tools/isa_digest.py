@@ -12,7 +12,7 @@ one source give equal digests; the device ELF itself carries a per-build id and 
 
 --census: the shipped flavour of the role-split kernels as assembly; per kernel, every stretch of instructions between two s_barrier
 in text order is a step body of some role.  Bodies are grouped by what they hold (packed products, exponentials, matrix and
-store instructions: the groups are named by that, not by role) and by whether control enters or leaves them (a label or a branch inside: a tested body), and each group prints
+store instructions, and for the backward's helper waves 4x4x1 products, bf16 conversions, 32x32x16 tile products and LDS-DMA requests: the groups are named by that, not by role) and by whether control enters or leaves them (a label or a branch inside: a tested body), and each group prints
 its instruction counts, the index of every `s_waitcnt lgkmcnt(0)`, of the first v_pk_fma_f32 / v_pk_mul_f32, of the first v_exp_f32 and
 of every LDS write (the first ds_write_b32 of a chain body is h), with the instructions between the last v_fma_f32 and that write.
 """
@@ -109,8 +109,16 @@ def role_of(ops):
     # named by content, not by role: which role of a kernel a group is follows from the kernel's source (forward: 28 packed products +
     # exponentials = layer 0, 24 + exponentials = layer 1, 24 alone = projection, 16-byte stores alone = saver; backward: 24 alone =
     # the recurrences)
+    # the backward's helper waves, by what only they hold: the loader its LDS-DMA requests, the x1 waves the 4x4x1 products of the
+    # four-step hand-off (with exponentials: a wave that also prepares a layer's factors; a prep step between two hand-offs is
+    # "exponentials, no products"), the dW waves the bf16 conversions of their duty and the 32x32x16 tiles
+    cv, m4, m32 = n("v_cvt_pk_bf16_f32"), n("v_mfma_f32_4x4x1"), n("v_mfma_f32_32x32x16")
     if n("global_load_lds"):
         return "LDS-DMA"
+    if m4:
+        return f"{m4} 4x4x1 products" + (" + exponentials" if ex else "")
+    if cv or m32:
+        return " + ".join(x for x in (f"{cv} bf16 conversions" if cv else "", f"{m32} 32x32x16 tile products" if m32 else "") if x)
     if mf:
         return "matrix instructions"
     if pk and ex:
@@ -119,6 +127,8 @@ def role_of(ops):
         return f"{pk} packed products"
     if n("global_store_dwordx4") and not ex:
         return "16-byte stores, no products"
+    if ex:
+        return "exponentials, no products"
     return None
 
 
