@@ -443,6 +443,50 @@ int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const flo
                     float *logits, float *probs, void *scratch, void *stream);
 
 /*
+ * ---- resumable H = 48 inference: decode live streams chunk by chunk (an EXTENSION: the reference decodes whole windows only) ----
+ *
+ * EEG_LSTM (lstm_eeg_model.py:13-39) is causal: two forward LSTM layers and a softmax pooling over time that can be formed online.  The
+ * state of a stream after t samples is h and c of both layers plus the pooling's running max, denominator and weighted sum: one SLOT of
+ * nsd_stream_layout.stride floats in a caller-owned device buffer of S slots.  nsd_stream_step advances B streams by a chunk of d->T
+ * samples each and, when asked, reads the decision of the prefix seen so far: row b of logits / probs is what nsd_infer returns for the
+ * first t samples of that stream (t = the slot's step count after the call; there is no upper limit on t).  The pooling is updated once
+ * per step in a fixed order that does not depend on where a chunk begins, so the state after t samples, and every output read from it,
+ * is bit for bit a function of the samples alone -- not of how they were cut into chunks, of the slot, or of the other streams of a call.
+ *   nsd_stream_path          1 for H = 48, L = 2, C <= 8, F <= 64, K <= 64, else 0 (and for invalid dims).  Only the model dims are read.
+ *   nsd_stream_state_bytes   bytes of a state of S >= 1 slots (S * stride * 4); <0 outside nsd_stream_path
+ *   nsd_stream_state_layout  float offsets inside a slot: h[l][H], c[l][H], pool_max, pool_den, pool_acc[H]; `steps`: the float offset of
+ *                            the slot's int64 step count (8-byte aligned); `stride`: floats per slot.  The layout is public: a slot can be
+ *                            checkpointed and restored by copying its stride floats.  h[1] is the top LSTM layer's own output (without
+ *                            the residual extension's sum); pool_acc / pool_den is the pooled vector of the prefix.
+ *   nsd_stream_reset         slots == NULL: all S slots; else the n slots of the DEVICE array slots[n] (indices outside [0, S) are
+ *                            skipped).  A reset slot has zero h and c, an empty pooling state (max -inf, denominator 0) and step count
+ *                            0.  A state must be reset once before its first nsd_stream_step; it may hold anything before that.
+ *   nsd_stream_step          d->B streams, chunk length d->T >= 1, x [B,T,C]; slots: DEVICE int32[B] of distinct indices in [0, S), or
+ *                            NULL for 0 .. B-1; flags: NSD_FLAG_RESIDUAL (the same on every call of a stream); logits [B,K] or NULL
+ *                            (advance only: no readout); probs [B,K] or NULL.
+ * Failure behaviour.  Every refusal happens before any launch: NSD_E_INVALID for NULL d / params / x / state, probs without logits,
+ * S < 1, n < 0 or n > S (reset), B > S, a shape outside nsd_stream_path, flags other than NSD_FLAG_RESIDUAL; NSD_E_WORKSPACE when
+ * state_bytes < nsd_stream_state_bytes(d, S).  B = 0 (n = 0) launches nothing.  A slot index outside [0, S) can only be seen on the
+ * device: that stream is skipped, its rows of logits / probs are NaN, no memory outside the state is touched.  Duplicate slots in one call
+ * are undefined (two workgroups would race on one slot).  A sample that is not finite (NaN or +-Inf) makes that stream's state, and every
+ * output read from it, NaN until the slot is reset; the other streams are unaffected.  No host synchronisation, no allocation: the call
+ * can be captured in a single-stream graph and replayed -- the step count lives in the state, nothing in the arguments changes per call.
+ * Additive: NSD_VERSION stays 301, a caller detects the feature by the symbols.
+ */
+typedef struct nsd_stream_layout {
+    int64_t h[NSD_MAX_LAYERS], c[NSD_MAX_LAYERS];   /* [H] each, entries 0 .. L-1 */
+    int64_t pool_max, pool_den, pool_acc;           /* 1, 1, [H] */
+    int64_t steps;                                  /* int64 step count: float offset, even */
+    int64_t stride;                                 /* floats per slot */
+} nsd_stream_layout;
+int     nsd_stream_path(const nsd_dims *d);
+int64_t nsd_stream_state_bytes(const nsd_dims *d, int32_t S);
+int     nsd_stream_state_layout(const nsd_dims *d, nsd_stream_layout *out);
+int nsd_stream_reset(const nsd_dims *d, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream);
+int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, const int32_t *slots, uint32_t flags, void *state,
+                    int64_t state_bytes, int32_t S, float *logits, float *probs, void *stream);
+
+/*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----
  *
  * Building block, exported so that it can be tested and timed on its own: C[M,N] = A . B with bf16 operands (device

@@ -65,6 +65,12 @@ class Dims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "T", "C", "H", "L", "K", "F")]
 
 
+class StreamLayout(C.Structure):
+    """nsd_stream_layout of include/nsd.h: float offsets inside one slot of a stream state"""
+    _fields_ = ([("h", C.c_int64 * 8), ("c", C.c_int64 * 8)]
+                + [(n, C.c_int64) for n in ("pool_max", "pool_den", "pool_acc", "steps", "stride")])
+
+
 class WsLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("hseq", "cseq", "gact", "inseq", "top", "alpha", "pooled", "fc0_pre",
                                           "dscore", "dpooled", "loss", "adpack", "slabs", "n_slabs", "hslabs", "da_seq", "din", "total")]
@@ -147,6 +153,12 @@ SYMBOLS = {
     "nsd_multi_loss_sum": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
     "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
     "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),
+    # resumable H = 48 inference (streams decoded chunk by chunk)
+    "nsd_stream_path": (C.c_int, [_dp]),
+    "nsd_stream_state_bytes": (C.c_int64, [_dp, C.c_int32]),
+    "nsd_stream_state_layout": (C.c_int, [_dp, C.POINTER(StreamLayout)]),
+    "nsd_stream_reset": (C.c_int, [_dp, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
+    "nsd_stream_step": (C.c_int, [_dp, _fp, _fp, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _vp]),
 }
 NSD_MAX_MODELS = 32
 

@@ -949,4 +949,74 @@ int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const flo
     return nsd_lstm2_multi_fwd_launch(a, model_split(d, x_model_stride), M, (hipStream_t)stream);
 }
 
+// ---- resumable H = 48 inference (nsd_stream48.hip) ----
+// the model dims alone: B and T are the call's (streams advanced, chunk length), not the state's
+static bool stream_shape(const nsd_dims *d) {
+    return d && check_model(d->C, d->H, d->L, d->K, d->F) == NSD_OK && d->H == 48 && d->L == 2 && d->C <= 8 && d->F <= 64 && d->K <= 64;
+}
+// the preamble of the entry points that touch a stream state: shape, pointers, slot count, size
+static int stream_enter(const nsd_dims *d, const char *who, bool ptrs_ok, const void *state, int64_t state_bytes, int32_t S) {
+    if (!stream_shape(d)) {
+        nsd_set_error("%s: shape outside the resumable path (nsd_stream_path: H = 48, L = 2, C <= 8, F <= 64, K <= 64)", who);
+        return NSD_E_INVALID;
+    }
+    if (!ptrs_ok || !state) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (S < 1) { nsd_set_error("%s: S = %d slots", who, S); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)S * STREAM_STRIDE * (int64_t)sizeof(float);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_stream_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int nsd_stream_path(const nsd_dims *d) { return stream_shape(d) ? 1 : 0; }
+
+int64_t nsd_stream_state_bytes(const nsd_dims *d, int32_t S) {
+    if (!stream_shape(d) || S < 1) { nsd_set_error("stream_state_bytes: shape outside nsd_stream_path, or S < 1"); return NSD_E_INVALID; }
+    return (int64_t)S * STREAM_STRIDE * (int64_t)sizeof(float);
+}
+
+int nsd_stream_state_layout(const nsd_dims *d, nsd_stream_layout *out) {
+    if (!stream_shape(d) || !out) { nsd_set_error("stream_state_layout: shape outside nsd_stream_path, or null pointer"); return NSD_E_INVALID; }
+    memset(out, 0, sizeof(*out));
+    out->h[0] = STREAM_H0; out->h[1] = STREAM_H1; out->c[0] = STREAM_C0; out->c[1] = STREAM_C1;
+    out->pool_max = STREAM_MAX; out->pool_den = STREAM_DEN; out->pool_acc = STREAM_ACC;
+    out->steps = STREAM_STEPS; out->stride = STREAM_STRIDE;
+    return NSD_OK;
+}
+
+int nsd_stream_reset(const nsd_dims *d, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream) {
+    static const char *who = "stream_reset";
+    if (const int rc = stream_enter(d, who, true, state, state_bytes, S)) return rc;
+    if (slots && (n < 0 || n > S)) { nsd_set_error("%s: n = %d slots of S = %d", who, n, S); return NSD_E_INVALID; }
+    const int count = slots ? n : S;
+    if (count == 0) return NSD_OK;
+    return nsd_stream_reset_launch((float *)state, S, slots, count, (hipStream_t)stream);
+}
+
+int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, const int32_t *slots, uint32_t flags, void *state,
+                    int64_t state_bytes, int32_t S, float *logits, float *probs, void *stream) {
+    static const char *who = "stream_step";
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (const int rc = stream_enter(d, who, params && x, state, state_bytes, S)) return rc;
+    if (probs && !logits) { nsd_set_error("%s: probs without logits", who); return NSD_E_INVALID; }
+    if (flags & ~NSD_FLAG_RESIDUAL) { nsd_set_error("%s: flags 0x%x (only NSD_FLAG_RESIDUAL applies)", who, flags); return NSD_E_INVALID; }
+    if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    const HeadArgs h = build_head(d, params);
+    const ParamLayout pl = layout_of(d);
+    StreamArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x;
+    a.w_ih0 = params + pl.w_ih[0]; a.w_hh0 = params + pl.w_hh[0]; a.b_ih0 = params + pl.b_ih[0]; a.b_hh0 = params + pl.b_hh[0];
+    a.w_ih1 = params + pl.w_ih[1]; a.w_hh1 = params + pl.w_hh[1]; a.b_ih1 = params + pl.b_ih[1]; a.b_hh1 = params + pl.b_hh[1];
+    a.attn_w = h.attn_w; a.attn_b = h.attn_b; a.ln_w = h.ln_w; a.ln_b = h.ln_b;
+    a.fc0_w = h.fc0_w; a.fc0_b = h.fc0_b; a.fc3_w = h.fc3_w; a.fc3_b = h.fc3_b;
+    a.eval_slope = h.eval_slope;
+    a.slots = slots; a.state = (float *)state; a.logits = logits; a.probs = probs;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.K = d->K; a.F = d->F; a.S = S; a.residual = residual_of(flags);
+    return nsd_stream48_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

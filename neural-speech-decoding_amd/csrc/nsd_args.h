@@ -204,3 +204,19 @@ bool nsd_dx_ok(int G4, int C);            // the dx kernel's domain (C channels,
 int nsd_att_close_launch(const float *hseq1, const float *pooled, const float *dpooled, float *adpack, float *dscore, float *hslabs,
                          long Ph, long o_attn_w, long o_attn_b, int B, int T, int H, hipStream_t st);
 
+// resumable H = 48 inference (nsd_stream_* of nsd.h; nsd_stream48.hip).  One slot of the caller's state, in floats: the public layout
+// nsd_stream_state_layout reports
+constexpr int STREAM_H0 = 0, STREAM_H1 = 48, STREAM_C0 = 96, STREAM_C1 = 144, STREAM_ACC = 192, STREAM_MAX = 240, STREAM_DEN = 241,
+              STREAM_STEPS = 242 /* int64: 8-byte aligned */, STREAM_STRIDE = 256;
+struct StreamArgs {
+    const float *x;                          // [B,T,C]: the chunk
+    const float *w_ih0, *w_hh0, *b_ih0, *b_hh0, *w_ih1, *w_hh1, *b_ih1, *b_hh1;
+    const float *attn_w, *attn_b, *ln_w, *ln_b, *fc0_w, *fc0_b, *fc3_w, *fc3_b;
+    const int32_t *slots;                    // null: stream b lives in slot b
+    float *state;                            // [S][STREAM_STRIDE]
+    float *logits, *probs;                   // null: advance only / no class softmax
+    float eval_slope;
+    int B, T, C, K, F, S, residual;
+};
+int nsd_stream48_launch(const StreamArgs &a, hipStream_t st);
+int nsd_stream_reset_launch(float *state, int S, const int32_t *slots, int n, hipStream_t st);

@@ -470,3 +470,15 @@ class SimplePredictor:
         _raise_on_poison(self.model, probs, "SimplePredictor.predict_windows")
         return probs, [self.class_names[int(i)] for i in probs.argmax(1)]
 
+
+    def open_stream(self, streams: int = 1, chunk_transform=None):
+        """Resumable decoding (an extension, see stream.py): a PredictorStream whose push(chunk [n,C] or [B,n,C]) advances `streams`
+        live streams and returns (probs, labels) of each stream's whole prefix -- predict() on the samples seen so far, without
+        waiting for the window to end.  Allowed when the predictor's preprocessor is the identity one, or when the caller passes
+        `chunk_transform` ([n,C] -> [n,C], applied to every chunk in place of the preprocessor: a causal filter of the caller's)."""
+        from .stream import PredictorStream
+        if chunk_transform is None and not isinstance(self.pre, IdentityPreProcessor):
+            raise NsdError("SimplePredictor.open_stream: the reference's window filter (PreProcessor.transform, preprocessor.py:21-36) "
+                           "works on a whole window and is not causal, so a stream cannot be filtered with it chunk by chunk; pass "
+                           "chunk_transform=<causal [n,C] -> [n,C] callable>, or build the predictor with preprocess=\"identity\"")
+        return PredictorStream(self, streams, chunk_transform)

@@ -1015,3 +1015,79 @@ def multi_infer(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, *, want_
     _call("nsd_multi_infer", params.device, C.byref(d), M, _dev_f32(params, "params", (M, spec.param_count)), _dev_f32(x, "x"), stride,
           0, _dev_f32(logits, "logits"), _dev_f32(probs, "probs"), scrp, STREAM)
     return logits, probs
+
+
+# ---- resumable H = 48 inference: streams decoded chunk by chunk (nsd_stream_* of include/nsd.h) ----
+
+def stream_path(spec: ModelSpec) -> bool:
+    """True where nsd_stream_step covers this model (H = 48, L = 2, C <= 8, F <= 64, K <= 64, one direction)."""
+    d = spec.dims(1, 1)
+    return spec.D == 1 and bool(_lib.lib().nsd_stream_path(C.byref(d)))
+
+
+def stream_layout(spec: ModelSpec) -> "_lib.StreamLayout":
+    """Float offsets of h[l], c[l], pool_max, pool_den, pool_acc and the int64 step count inside one slot, and the slot stride."""
+    d, lay = spec.dims(1, 1), _lib.StreamLayout()
+    check(_lib.lib().nsd_stream_state_layout(C.byref(d), C.byref(lay)), "nsd_stream_state_layout")
+    return lay
+
+
+def stream_state_bytes(spec: ModelSpec, S: int) -> int:
+    d = spec.dims(1, 1)
+    n = int(_lib.lib().nsd_stream_state_bytes(C.byref(d), int(S)))
+    if n < 0:
+        check(n, "nsd_stream_state_bytes")
+    return n
+
+
+def stream_state(spec: ModelSpec, S: int, device="cuda") -> torch.Tensor:
+    """A reset state of S slots on `device`: fp32 [S, stride] (one row per stream; stream_layout names the columns)."""
+    state = torch.empty((int(S), int(stream_layout(spec).stride)), dtype=torch.float32, device=device)
+    stream_reset(spec, state)
+    return state
+
+
+def _slots_ptr(slots: Optional[torch.Tensor], what: str) -> Optional[int]:
+    if slots is None:
+        return None
+    if slots.dtype != torch.int32 or not slots.is_cuda or not slots.is_contiguous() or slots.dim() != 1:
+        raise NsdError(f"{what}: slots must be a contiguous 1-D int32 tensor on the device")
+    return slots.data_ptr()
+
+
+def stream_reset(spec: ModelSpec, state: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """Reset all slots of `state`, or the ones a device int32 tensor names: zero h and c, empty pooling state, step count 0."""
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    d = spec.dims(0, 1)
+    n = 0 if slots is None else int(slots.numel())
+    if slots is not None and n == 0:
+        return
+    _call("nsd_stream_reset", state.device, C.byref(d), _dev_f32(state, "state"), _nbytes(state), S, _slots_ptr(slots, "stream_reset"), n,
+          STREAM)
+
+
+def stream_step(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, state: torch.Tensor, *, slots: Optional[torch.Tensor] = None,
+                residual: bool = False, read: bool = True, want_probs: bool = True, logits: Optional[torch.Tensor] = None,
+                probs: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Advance B streams by the chunk x [B,n,C] (stream b lives in slot slots[b], or b) and, with read=True, return what ops.infer gives
+    on each stream's whole prefix: logits [B,K] (+ probs).  read=False advances only and returns (None, None).  logits / probs:
+    optional caller-owned buffers."""
+    if x.dim() != 3 or x.shape[-1] != spec.C:
+        raise NsdError(f"stream_step: x must be [B, n, {spec.C}], got {tuple(x.shape)}")
+    B, T, _ = (int(v) for v in x.shape)
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"stream_step: {int(slots.numel())} slot indices for {B} streams")
+    d = spec.dims(B, T)
+    if read:
+        logits = _out_f32(logits, (B, spec.K), x.device, "stream_step: logits")
+        probs = _out_f32(probs, (B, spec.K), x.device, "stream_step: probs") if want_probs else None
+    else:
+        logits = probs = None
+    if B == 0:
+        _dev_f32(flat, "params", (spec.param_count,)); _dev_f32(state, "state")
+        return logits, probs
+    _call("nsd_stream_step", x.device, C.byref(d), _dev_f32(flat, "params", (spec.param_count,)), _dev_f32(x, "x"),
+          _slots_ptr(slots, "stream_step"), _lib.NSD_FLAG_RESIDUAL if residual else 0, _dev_f32(state, "state"), _nbytes(state), S,
+          _dev_f32(logits, "logits"), _dev_f32(probs, "probs"), STREAM)
+    return logits, probs

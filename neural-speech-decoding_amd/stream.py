@@ -1,0 +1,126 @@
+"""Resumable decoding of live EEG streams on the MI355X: the model advances chunk by chunk while the samples arrive, and a decision
+can be read after any chunk (nsd_stream_* of include/nsd.h, csrc/nsd_stream48.hip).
+
+An extension: the reference decodes whole windows (SimplePredictor.predict, lstm_eeg_model.py:86-101).  EEG_LSTM itself is causal
+(lstm_eeg_model.py:32-39: forward LSTM layers, a softmax pooling over time), so the probabilities read after t samples are those of
+`model.predict_proba` on the first t samples, and they do not depend on how the samples were cut into chunks.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import NsdError
+
+
+class StreamDecoder:
+    """`streams` independent live streams of one eval-mode EEG_LSTM, each with its own slot of device state.
+
+      push(samples, slots=None, read=True)   samples [n, C] (one stream) or [B, n, C]; slots: the B slot indices (default 0 .. B-1).
+                                             Returns class probabilities [B, K] of every pushed stream's whole prefix (device
+                                             tensor), or None with read=False (advance only: no readout)
+      reset(slots=None)                      restart all streams, or the named ones
+      steps                                  samples seen per slot (int64 numpy [streams])
+      state_dict() / load_state_dict()       checkpoint / restore the stream state (not the model)
+    """
+
+    def __init__(self, model, streams: int = 1):
+        from .lstm_eeg_model import EEG_LSTM
+        if not isinstance(model, EEG_LSTM):
+            raise NsdError(f"StreamDecoder: expected an EEG_LSTM, got {type(model).__name__}")
+        if model.training:
+            raise NsdError("StreamDecoder: the model must be in eval mode (model.eval()): a stream is decoded without dropout")
+        if model.precision != "fp32" or model.spec.D != 1:
+            raise NsdError("StreamDecoder: the bf16 sequence path and bidirectional models are not resumable (a bidirectional model is "
+                           "not causal); use an fp32, one-directional EEG_LSTM")
+        if model.normalize:
+            raise NsdError("StreamDecoder: normalize=True z-scores over the whole window, which a stream has not seen yet; "
+                           "normalise the chunks causally on the caller's side")
+        if not ops.stream_path(model.spec):
+            raise NsdError(f"StreamDecoder: model shape {model.spec} is outside nsd_stream_path (hidden size 48, 2 layers, <= 8 channels, "
+                           "fc width and classes <= 64)")
+        if int(streams) < 1:
+            raise NsdError(f"StreamDecoder: streams = {streams}")
+        flat = model.flat_parameters()
+        if not flat.is_cuda:
+            raise NsdError("StreamDecoder runs only on the MI355X HIP path: move the model to the GPU first; there is no CPU fallback")
+        self.model, self.streams, self.device = model, int(streams), flat.device
+        self._layout = ops.stream_layout(model.spec)
+        self.state = ops.stream_state(model.spec, self.streams, self.device)
+
+    def _slots(self, slots, n: Optional[int] = None) -> Optional[torch.Tensor]:
+        if slots is None:
+            return None
+        if not torch.is_tensor(slots):
+            idx = [int(v) for v in np.asarray(slots).reshape(-1)]
+            if any(v < 0 or v >= self.streams for v in idx) or len(set(idx)) != len(idx):
+                raise NsdError(f"StreamDecoder: slots {idx} must be distinct indices in [0, {self.streams})")
+            slots = torch.tensor(idx, dtype=torch.int32)
+        slots = slots.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        if n is not None and int(slots.numel()) != n:
+            raise NsdError(f"StreamDecoder: {int(slots.numel())} slots for {n} streams")
+        return slots
+
+    @torch.no_grad()
+    def push(self, samples, slots=None, read: bool = True) -> Optional[torch.Tensor]:
+        x = samples if torch.is_tensor(samples) else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32))
+        if x.dim() == 2:
+            x = x[None]
+        if x.dim() != 3 or x.shape[-1] != self.model.spec.C or x.shape[1] < 1:
+            raise NsdError(f"StreamDecoder.push: samples must be [n, {self.model.spec.C}] or [B, n, {self.model.spec.C}] with n >= 1, "
+                           f"got {tuple(x.shape)}")
+        if x.shape[0] > self.streams:
+            raise NsdError(f"StreamDecoder.push: {x.shape[0]} streams pushed, the decoder has {self.streams}")
+        x = x.to(self.device, non_blocking=True).contiguous().float()
+        _, probs = ops.stream_step(self.model.spec, self.model.flat_parameters(), x, self.state, slots=self._slots(slots, int(x.shape[0])),
+                                   residual=self.model.residual, read=read)
+        return probs
+
+    def reset(self, slots=None) -> None:
+        ops.stream_reset(self.model.spec, self.state, self._slots(slots))
+
+    @property
+    def steps(self) -> np.ndarray:
+        col = int(self._layout.steps) // 2
+        return self.state.view(torch.int64)[:, col].cpu().numpy().copy()
+
+    def state_dict(self) -> dict:
+        return {"state": self.state.detach().cpu().clone(), "stride": int(self._layout.stride)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        st = sd["state"]
+        if tuple(st.shape) != tuple(self.state.shape) or int(sd.get("stride", st.shape[-1])) != int(self._layout.stride):
+            raise NsdError(f"StreamDecoder.load_state_dict: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
+        self.state.copy_(st.to(self.device, dtype=torch.float32))
+
+
+class PredictorStream:
+    """What SimplePredictor.open_stream returns: numpy chunks in, (probs float32 [B, K], labels) out -- predict(), chunk by chunk."""
+
+    def __init__(self, predictor, streams: int, chunk_transform=None):
+        self.predictor, self.chunk_transform = predictor, chunk_transform
+        self.decoder = StreamDecoder(predictor.model, streams)
+
+    def push(self, chunk: np.ndarray, slots=None, read: bool = True):
+        x = np.asarray(chunk)
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3:
+            raise ValueError(f"Expected [n, C] or [B, n, C] samples, got {x.shape}")
+        f = self.chunk_transform or self.predictor.pre.transform
+        x = np.stack([np.ascontiguousarray(f(c), dtype=np.float32) for c in x])
+        probs = self.decoder.push(x, slots=slots, read=read)
+        if probs is None:
+            return None
+        p = probs.cpu().numpy().astype(np.float32)
+        return p, [self.predictor.class_names[int(i)] for i in p.argmax(1)]
+
+    def reset(self, slots=None) -> None:
+        self.decoder.reset(slots)
+
+    @property
+    def steps(self) -> np.ndarray:
+        return self.decoder.steps

@@ -7,6 +7,10 @@ stand-in keeps the process / queue contract `run_trials` relies on:
     (serial_port, num_channels, window_seconds, out_queue, start_recording, buffer_size)
   * while recording, emits payload dicts {"sr", "channels", "data" float32[T,C], "t_emit"} with
     put_nowait, dropping the oldest item when the queue is full (streaming_process.py:58-69)
+`chunk_seconds` (keyword-only, default None: exactly the above) cuts every window into chunks of that many seconds for a resumable
+decoder (stream.py): the same windows, each payload carrying the same keys with "data" float32[n,C] plus "seq" (index of the chunk
+inside its window, from 0) and "last" (True on the window's final chunk, which may be shorter).  Chunks are never dropped: a decoder
+that lost one would no longer hold the window's prefix.
 `serial_port` selects the source:
   "replay:<dir-or-glob>"   recorded trial CSVs ([625,8] rows x channels, format of
                            Neural_decoding_data_collector.py:129-139), cycled in sorted order
@@ -41,7 +45,8 @@ def synthetic_window(T: int, C: int, rng: np.random.RandomState, sr: int = SAMPL
 
 class StreamingProcess(Process):
     def __init__(self, serial_port: str, num_channels: int = 8, window_seconds: float = 5.0, out_queue: Queue = None,
-                 start_recording: bool = False, buffer_size: int = 450000, *args, realtime: bool = False, **kwargs):
+                 start_recording: bool = False, buffer_size: int = 450000, *args, realtime: bool = False,
+                 chunk_seconds: float = None, **kwargs):
         super().__init__(*args, **kwargs)
         self.serial_port = serial_port
         self.num_channels = int(num_channels)
@@ -50,6 +55,9 @@ class StreamingProcess(Process):
         self.out_queue = out_queue or Queue(maxsize=8)
         self.recording_flag = Value('b', start_recording)
         self.realtime = bool(realtime)
+        if chunk_seconds is not None and not float(chunk_seconds) > 0:
+            raise ValueError(f"chunk_seconds={chunk_seconds!r}: expected a positive number of seconds, or None")
+        self.chunk_seconds = None if chunk_seconds is None else float(chunk_seconds)
         self._running = Event()
         self._running.set()
 
@@ -77,7 +85,33 @@ class StreamingProcess(Process):
             raise RuntimeError(f"serial acquisition from {src!r} needs the NeuroPawn board + brainflow, which this "
                                "build does not drive; use 'replay:<dir>' or 'synthetic:'")
 
+    def _run_chunked(self):
+        """chunk_seconds mode: every window leaves as consecutive chunks; a full queue is waited for, never emptied"""
+        gen = self._windows()
+        channels = list(range(1, self.num_channels + 1))
+        while self._running.is_set():
+            if not self.recording_flag.value:
+                time.sleep(0.01)
+                continue
+            sr, window = next(gen)
+            window = np.asarray(window, dtype=np.float32)
+            n = max(1, int(self.chunk_seconds * sr))
+            starts = list(range(0, window.shape[0], n))
+            for seq, s0 in enumerate(starts):
+                if self.realtime:
+                    time.sleep(self.chunk_seconds)
+                payload = {"sr": sr, "channels": channels, "data": np.ascontiguousarray(window[s0:s0 + n]), "t_emit": time.time(),
+                           "seq": seq, "last": seq == len(starts) - 1}
+                while self._running.is_set():
+                    try:
+                        self.out_queue.put(payload, timeout=0.05)
+                        break
+                    except Exception:
+                        continue
+
     def run(self):
+        if self.chunk_seconds is not None:
+            return self._run_chunked()
         gen = self._windows()
         channels = list(range(1, self.num_channels + 1))
         last_emit_ts = 0.0

@@ -104,6 +104,18 @@ def _windows(producer, q: Queue, timeout: float, verbose: bool) -> Iterator[Tupl
         yield np.asarray(payload["data"]), payload["sr"], payload.get("channels")
 
 
+def _chunks(producer, q: Queue, timeout: float, verbose: bool) -> Iterator[dict]:
+    """chunk_seconds mode: the payloads themselves ("seq" / "last" say where a chunk stands in its window), same liveness rules"""
+    while True:
+        if not producer.is_alive():
+            raise RuntimeError("Producer exited unexpectedly")
+        try:
+            yield q.get(timeout=timeout)
+        except _queue.Empty:
+            if verbose:
+                print("Waiting for chunk...", flush=True)
+
+
 def _report(res: TrialResult) -> None:
     if res.avg_probs is None:
         print("No trials completed; no average available.")
@@ -115,14 +127,20 @@ def _report(res: TrialResult) -> None:
 
 def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels: int = 8, window_seconds: float = 5.0,
                model_path: str = DEFAULT_MODEL, verbose: bool = True, *, producer_factory=None,
-               queue_timeout: float = 6.5, predictor_kwargs: Optional[dict] = None) -> TrialResult:
+               queue_timeout: float = 6.5, predictor_kwargs: Optional[dict] = None, chunk_seconds: Optional[float] = None,
+               chunk_transform=None) -> TrialResult:
     """Collect `trials` windows, run SimplePredictor on each, return the averages.
 
     Positional / keyword interface: the reference's.  Keyword-only additions: `producer_factory`
     (callable(serial_port=, num_channels=, window_seconds=, out_queue=) -> process; default StreamingProcess),
     `queue_timeout` (the reference hard-codes 6.5 s), `predictor_kwargs` (extra SimplePredictor kwargs, e.g.
-    {"preprocess": "identity"} when the reference's MindsAI filter is not importable).
+    {"preprocess": "identity"} when the reference's MindsAI filter is not importable), `chunk_seconds` (None: the window mode
+    above; a value: the producer cuts every window into chunks of that length and a resumable decoder -- SimplePredictor.open_stream
+    -- advances while they arrive; the trial's decision is read at its last chunk) with `chunk_transform` (open_stream's).
     """
+    if chunk_seconds is not None:
+        return _run_trials_chunked(trials, serial_port, num_channels, window_seconds, model_path, verbose, producer_factory,
+                                   queue_timeout, predictor_kwargs, chunk_seconds, chunk_transform)
     q = Queue(maxsize=_QUEUE_DEPTH)
     producer = (producer_factory or StreamingProcess)(serial_port=serial_port, num_channels=num_channels,
                                                       window_seconds=window_seconds, out_queue=q)
@@ -139,6 +157,44 @@ def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels
                                             class_names=list(_HARNESS_LABELS), **(predictor_kwargs or {}))
             probs, label = predictor.predict(window)
             mean.add(probs, window)
+            if verbose:
+                print(f"[Trial {mean.n:02d} @ {time.strftime('%H:%M:%S')}] pred={label} probs={np.round(probs, 3)}")
+        res = mean.result()
+        if verbose:
+            _report(res)
+        return res
+
+
+def _run_trials_chunked(trials, serial_port, num_channels, window_seconds, model_path, verbose, producer_factory, queue_timeout,
+                        predictor_kwargs, chunk_seconds, chunk_transform) -> TrialResult:
+    q = Queue(maxsize=_QUEUE_DEPTH)
+    producer = (producer_factory or StreamingProcess)(serial_port=serial_port, num_channels=num_channels,
+                                                      window_seconds=window_seconds, out_queue=q, chunk_seconds=chunk_seconds)
+    mean = _RunningMean(classes=len(_HARNESS_LABELS))
+    stream, parts = None, []
+    with _recording(producer):
+        source = _chunks(producer, q, queue_timeout, verbose)
+        while mean.n < trials:
+            payload = next(source)
+            if stream is None:
+                predictor = SimplePredictor(pth_path=resolve_model_path(model_path), sr=payload["sr"], channel_order=payload.get("channels"),
+                                            input_size=num_channels, hidden_size=48, num_layers=2, num_classes=3,
+                                            dropout=0.60, device="cpu", tailoring_lambda=1.25e-29,
+                                            class_names=list(_HARNESS_LABELS), **(predictor_kwargs or {}))
+                stream = predictor.open_stream(streams=1, chunk_transform=chunk_transform)
+            if payload["seq"] == 0:            # a window starts: whatever an interrupted one left is dropped
+                stream.reset()
+                parts = []
+            elif not parts:
+                continue                       # joined in the middle of a window: wait for the next one
+            data = np.asarray(payload["data"])
+            parts.append(data)
+            out = stream.push(data, read=bool(payload["last"]))
+            if out is None:
+                continue
+            probs, label = out[0][0], out[1][0]
+            mean.add(probs, np.concatenate(parts, axis=0))
+            parts = []
             if verbose:
                 print(f"[Trial {mean.n:02d} @ {time.strftime('%H:%M:%S')}] pred={label} probs={np.round(probs, 3)}")
         res = mean.result()
