@@ -12,6 +12,7 @@ import nsd_amd
 from nsd_amd import _lib
 from oracle import nsd_oracle as orc
 from tests import augment_ref as ar
+from tests.train_cli import parse_train_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID = -1
@@ -192,34 +193,12 @@ def test_augment_dataclass():
         A().max_shift = 3                                          # frozen
 
 
-def _parse(argv, monkeypatch):
-    """Run nsd_amd.train.main up to the point where it looks for a device; returns the argparse namespace it built there."""
-    from nsd_amd import train
-    seen = {}
-
-    def stop():
-        raise RuntimeError("a device was touched")
-    monkeypatch.setattr(train, "init_distributed", stop)
-    real = train.argparse.ArgumentParser.parse_args
-
-    def spy(self, *a, **kw):
-        seen["args"] = real(self, *a, **kw)
-        return seen["args"]
-    monkeypatch.setattr(train.argparse.ArgumentParser, "parse_args", spy)
-    try:
-        train.main(argv)
-    except RuntimeError as e:
-        assert "device was touched" in str(e)
-        seen["reached_device"] = True
-    return seen
-
-
 def test_cli_flags_parse(monkeypatch):
-    seen = _parse(["--synthetic", "16", "--aug-shift", "12", "--aug-scale", "0.1", "--aug-channel-drop", "0.2", "--aug-noise", "0.3"],
+    seen = parse_train_args(["--synthetic", "16", "--aug-shift", "12", "--aug-scale", "0.1", "--aug-channel-drop", "0.2", "--aug-noise", "0.3"],
                   monkeypatch)
     a = seen["args"]
     assert (a.aug_shift, a.aug_scale, a.aug_channel_drop, a.aug_noise) == (12, 0.1, 0.2, 0.3) and seen.get("reached_device")
-    d = _parse(["--synthetic", "16"], monkeypatch)["args"]
+    d = parse_train_args(["--synthetic", "16"], monkeypatch)["args"]
     assert (d.aug_shift, d.aug_scale, d.aug_channel_drop, d.aug_noise) == (0, 0.0, 0.0, 0.0)
 
 
@@ -227,5 +206,5 @@ def test_cli_flags_parse(monkeypatch):
                                  ["--aug-shift", "625"]])
 def test_cli_out_of_range_is_an_argparse_error_before_any_device(bad, monkeypatch, capsys):
     with pytest.raises(SystemExit) as e:
-        _parse(["--synthetic", "16"] + bad, monkeypatch)
+        parse_train_args(["--synthetic", "16"] + bad, monkeypatch)
     assert e.value.code == 2 and "error:" in capsys.readouterr().err

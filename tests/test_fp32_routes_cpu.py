@@ -2,7 +2,7 @@
 restatement of the model (oracle/torch_ref.py) at H = 32 / 64 with the residual flag, with C < 8 and at the T edges of the
 first-generation fused kernels (csrc/nsd_lstm2.hip) -- shapes the oracle had never been compared with anything at.
 
-T_EDGES is the table of section (a) of the GPU file; the rows with T in {1, 2, 33, 65, 97} (all of B <= 7) are compared here, with
+T_EDGES (tests/gpu_harness.py) is the table of section (a) of the GPU file; the rows with T in {1, 2, 33, 65, 97} (all of B <= 7) are compared here, with
 the kink-safe fc.0.bias = +-4 the GPU cases use and with the generators' own bias.
 
 Bounds are those of test_oracle_matches_a_float64_restatement_of_the_model (tests/test_head_dims_cpu.py): every gradient tensor within
@@ -20,15 +20,8 @@ import torch
 
 from oracle import nsd_oracle as orc
 from oracle.torch_ref import TorchRefEEG
-from tests.test_head_dims_cpu import KINK_MARGIN, head_inputs, kink_margin
+from tests.gpu_harness import KINK_MARGIN, T_EDGES, head_inputs, kink_margin
 
-# (C, H, K, F, B, T, residual), L = 2.  T: the first step, the step after it (layer 0's backward lags by two macro steps), both sides of
-# each 32-step chunk of the staged x / dropout-mask double buffer, and a fourth chunk (both buffers reused).  Each H sees every C of
-# {8, 7, 5, 1} (C = 7, 5, 1: the odd split of the two-channel pairs of a quad) and both values of the residual flag.
-T_EDGES = [(8, 32, 3, 32, 5, 1, False), (7, 32, 5, 7, 6, 2, True), (5, 32, 3, 32, 8, 31, False), (1, 32, 2, 33, 7, 32, True),
-           (8, 32, 4, 33, 4, 33, True), (7, 32, 3, 32, 8, 64, False), (5, 32, 2, 32, 6, 65, True), (1, 32, 3, 32, 5, 97, False),
-           (1, 64, 3, 32, 4, 1, True), (5, 64, 4, 33, 7, 2, False), (7, 64, 3, 32, 8, 31, True), (8, 64, 5, 7, 5, 32, False),
-           (1, 64, 2, 32, 6, 33, False), (5, 64, 3, 32, 8, 64, True), (7, 64, 2, 33, 5, 65, False), (8, 64, 3, 32, 4, 97, True)]
 CPU_T = (1, 2, 33, 65, 97)
 LOGIT_TOL_OWN_BIAS, LOGIT_TOL_SAFE_BIAS = 1e-6, 5e-6
 

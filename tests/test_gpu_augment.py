@@ -7,29 +7,11 @@ import pytest
 import torch
 
 from tests import augment_ref as ar
+from tests.gpu_harness import dev, nsd, sync_at_the_end  # noqa: F401  (fixtures; sync_at_the_end is autouse)
 
 pytestmark = pytest.mark.gpu
 
 ALL = dict(max_shift=3, scale_range=0.2, p_channel=0.25, noise_std=0.3)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()
-    return nsd_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync_at_the_end():
-    yield
-    torch.cuda.synchronize()        # every test ends with the device idle (ops._call has checked the return code of every ABI call)
 
 
 def _x(shape, seed=0):

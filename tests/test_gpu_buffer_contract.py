@@ -49,12 +49,9 @@ from tests import augment_ref as ar
 from tests import buffer_contract as bc
 from tests import mixup_ref as mr
 from tests.golden.make_goldens import synth_labels, synth_params, synth_x
-from tests.test_gpu_head_dims import _vs_oracle
-from tests.test_gpu_multimodel import _grad_ok
-from tests.test_gpu_parity import DX_TOL, LOGIT_TOL, _t
-from tests.test_gpu_seq_autograd import DUAL_RTOL, EQUIV_RTOL, duality, per_tensor
-from tests.test_gpu_seqpath_bf16ref import CASES, case_F, case_inputs, compare, emulate
-from tests.test_head_dims_cpu import KINK_MARGIN, head_inputs, kink_margin, kink_safe
+from tests.gpu_harness import (KINK_MARGIN, LOGIT_TOL, PROB_TOL, assert_step_vs_oracle, bounds_of, cus, dev, head_inputs, kink_safe, multi_grad_ok,  # noqa: F401
+                               nsd, oracle_step, oracle_streams, to_dev)
+from tests.seq_bf16_harness import CASES, DUAL_RTOL, EQUIV_RTOL, case_F, case_inputs, compare, duality, emulate, per_tensor
 
 pytestmark = pytest.mark.gpu
 
@@ -62,24 +59,6 @@ T_START = time.time()
 SLOWEST = [0.0, ""]
 _BASE = {}                       # route id -> outputs of its "zeros" run (or the exception that run ended with)
 _SEQ_TIMED_OUT = []              # route ids whose workspace reported a scan time-out: no sequence route runs after one
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()          # raises if libnsd_hip.so is missing: no fallback
-    return nsd_amd
-
-
-@pytest.fixture(scope="module")
-def cus(dev):
-    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
 
 
 def _np(t):
@@ -121,7 +100,7 @@ def _batch(mb, cus, grow):
 class Fp32Step(Route):
     """ops.train_step_grads (nsd_lstm_head_train[_rng] or nsd_lstm_fwd + nsd_head_train, nsd_lstm_bwd[_rng], nsd_grad_reduce) and
     nsd_loss_sum.  how: "masks" explicit mask tensors, "rng" in-kernel streams, "unfused" fused_head=False (three launches before the
-    reduction).  Reference: the oracle through tests/test_gpu_head_dims.py's _vs_oracle (FAST48 on the H = 48 fast path, FP32_EXACT on
+    reduction).  Reference: the oracle through assert_step_vs_oracle (FAST48 on the H = 48 fast path, FP32_EXACT on
     every other route, LOGIT_TOL, its loss bound); dx at DX_TOL."""
 
     def __init__(self, rid, Cc, H, L, K, F, mb, T, residual=False, how="masks", dx=False):
@@ -140,8 +119,8 @@ class Fp32Step(Route):
                          rrelu_slope=orc.rrelu_noise(RNG["seed"], RNG["base_stream"] + 1, (B, F)),
                          drop_head=orc.dropout_mask(RNG["seed"], RNG["base_stream"] + 2, RNG["p_head"], (B, F)))
         ctx = types.SimpleNamespace(d=d, spec=ops.ModelSpec(C=Cc, H=H, L=L, K=K, F=F), B=B, T=T, flat_np=flat, x_np=x, y_np=y, masks_np=masks,
-                                    flat=_t(flat, dev), x=_t(x.copy(), dev), y=_t(y.astype(np.int32), dev),
-                                    masks={} if self.how == "rng" else {k: _t(v, dev) for k, v in masks.items()})
+                                    flat=to_dev(flat, dev), x=to_dev(x.copy(), dev), y=to_dev(y.astype(np.int32), dev),
+                                    masks={} if self.how == "rng" else {k: to_dev(v, dev) for k, v in masks.items()})
         ctx.inputs = [ctx.flat, ctx.x, ctx.y] + list(ctx.masks.values())
         if self.how == "rng":
             assert ops.rng_path(ctx.spec, B, T)
@@ -163,16 +142,11 @@ class Fp32Step(Route):
 
     def check(self, ctx, got, dev):
         d, flat, x, y, masks = ctx.d, ctx.flat_np, ctx.x_np, ctx.y_np, ctx.masks_np
-        fw = orc.forward(flat, x, d, saves=True, residual=self.residual, **masks)
-        assert kink_margin(fw) > KINK_MARGIN, kink_margin(fw)
-        loss, dl = orc.ce_loss(fw["logits"], y)
-        bw = orc.backward(flat, x, d, fw, dl, residual=self.residual, want_dx=self.dx, **masks)
-        g_ref, dx_ref = bw if self.dx else (bw, None)
-        _vs_oracle(self.id, d, _np(got["logits"]), float(got["loss_sum"][0]) / ctx.B, _np(got["grads"]), (loss, g_ref, fw, dx_ref))
+        ref = oracle_step(d, flat, x, labels=y, masks=masks, residual=self.residual, want_dx=self.dx, kink=KINK_MARGIN)
+        out = dict(logits=_np(got["logits"]), grads=_np(got["grads"]), mean_loss=float(got["loss_sum"][0]) / ctx.B)
         if self.dx:
-            err, scale = float(np.abs(_np(got["dx"]) - dx_ref).max()), float(np.abs(dx_ref).max())
-            print(f"[{self.id}] dx: max error / largest element {err / scale:.2e}")
-            assert err <= DX_TOL * scale, (err, scale)
+            out["dx"] = _np(got["dx"])
+        assert_step_vs_oracle(out, ref, d, bounds_of(d), tag=self.id)
 
 
 class Infer(Route):
@@ -189,8 +163,8 @@ class Infer(Route):
         B, T = _batch(self.mb, cus, grow), self.T + (2 if grow else 0)
         d, flat, x, _, _ = _inputs(Cc, H, L, K, F, B, T)
         flat = _other(flat) if grow else flat
-        ctx = types.SimpleNamespace(d=d, spec=ops.ModelSpec(C=Cc, H=H, L=L, K=K, F=F), B=B, T=T, flat_np=flat, x_np=x, flat=_t(flat, dev),
-                                    x=_t(x.copy(), dev))
+        ctx = types.SimpleNamespace(d=d, spec=ops.ModelSpec(C=Cc, H=H, L=L, K=K, F=F), B=B, T=T, flat_np=flat, x_np=x, flat=to_dev(flat, dev),
+                                    x=to_dev(x.copy(), dev))
         ctx.inputs = [ctx.flat, ctx.x]
         return ctx
 
@@ -210,7 +184,7 @@ class Infer(Route):
         lerr = float(np.abs(_np(got["logits"]) - ref["logits"]).max())
         perr = float(np.abs(_np(got["probs"]) - ref["probs"]).max()) if self.probs else 0.0
         print(f"[{self.id}] infer logits {lerr:.2e}  probs {perr:.2e}  scratch {bc.infer_scratch_bytes(ctx.spec, ctx.B, ctx.T)} bytes")
-        assert lerr < LOGIT_TOL and perr < 1e-5, (lerr, perr)
+        assert lerr < LOGIT_TOL and perr < PROB_TOL, (lerr, perr)
 
 
 # (id, C, H, L, K, F, (m, a): B = m * cus + a, T, residual, how, dx)
@@ -269,8 +243,8 @@ def _multi_problem(B, T, dev, grow, head=MULTI_HEAD):
     x = np.stack([synth_x(B, T, seed=20 + m) for m in range(M)])
     y = np.stack([synth_labels(B, K=K, seed=30 + m) for m in range(M)]).astype(np.int32)
     rngs = [dict(seed=1000 + 17 * m, base_stream=4 * (m + 1), p_lstm=0.6, p_head=0.6) for m in range(M)]
-    return types.SimpleNamespace(spec=spec, d=d, M=M, B=B, T=T, params_np=params, x_np=x, y_np=y, rngs=rngs, params=_t(params, dev),
-                                 x=_t(x.copy(), dev), y=_t(y.reshape(-1), dev))
+    return types.SimpleNamespace(spec=spec, d=d, M=M, B=B, T=T, params_np=params, x_np=x, y_np=y, rngs=rngs, params=to_dev(params, dev),
+                                 x=to_dev(x.copy(), dev), y=to_dev(y.reshape(-1), dev))
 
 
 class MultiStep(Route):
@@ -291,12 +265,12 @@ class MultiStep(Route):
         ctx.inputs = [ctx.x, ctx.y]
         if self.soft:                                       # smoothed, weighted rows: any row sum
             q = np.stack([mr.base_rows(ctx.y_np[m], K, 0.1, np.linspace(0.5, 1.5, K).astype(np.float32)) for m in range(M)])
-            ctx.q_np, ctx.q = q, _t(q.reshape(M * B, K), dev)
+            ctx.q_np, ctx.q = q, to_dev(q.reshape(M * B, K), dev)
             ctx.inputs.append(ctx.q)
         if self.adam:
             rs = np.random.RandomState(3)
-            ctx.m0 = _t((rs.random_sample(ctx.params_np.shape) * 1e-3).astype(np.float32), dev)
-            ctx.v0 = _t((rs.random_sample(ctx.params_np.shape) * 1e-6).astype(np.float32), dev)
+            ctx.m0 = to_dev((rs.random_sample(ctx.params_np.shape) * 1e-3).astype(np.float32), dev)
+            ctx.v0 = to_dev((rs.random_sample(ctx.params_np.shape) * 1e-6).astype(np.float32), dev)
             ctx.inputs += [ctx.params, ctx.m0, ctx.v0]     # the launches work on copies inside the arena
         else:
             ctx.inputs.append(ctx.params)
@@ -329,18 +303,14 @@ class MultiStep(Route):
             s1, sm = float(ops.loss_sum(spec, ws, B, T).item()) / B, float(got["losses"][m]) / B
             l1, g1 = l1.cpu(), g1.cpu()
             assert float((lg[m] - l1).abs().max()) <= 1e-6 * max(float(l1.abs().max()), 1.0), m
-            _grad_ok(spec, got["grads"][m], g1)
+            multi_grad_ok(spec, got["grads"][m], g1)
             assert abs(sm - s1) <= 1e-6 * max(1.0, abs(s1)), (m, sm, s1)
         if not self.soft:                                   # the last model against the oracle, its masks from its own streams
             r, m = ctx.rngs[M - 1], M - 1
-            masks = dict(drop_lstm=orc.dropout_mask(r["seed"], r["base_stream"], 0.6, (1, B, T, 48)),
-                         rrelu_slope=orc.rrelu_noise(r["seed"], r["base_stream"] + 1, (B, spec.F)),
-                         drop_head=orc.dropout_mask(r["seed"], r["base_stream"] + 2, 0.6, (B, spec.F)))
-            fw = orc.forward(ctx.params_np[m], ctx.x_np[m], ctx.d, saves=True, **masks)
-            assert kink_margin(fw) > KINK_MARGIN
-            loss, dl = orc.ce_loss(fw["logits"], ctx.y_np[m])
-            g_ref = orc.backward(ctx.params_np[m], ctx.x_np[m], ctx.d, fw, dl, **masks)
-            _vs_oracle(f"{self.id} model {m}", ctx.d, _np(lg[m]), float(got["losses"][m]) / B, _np(got["grads"][m]), (loss, g_ref, fw, None))
+            ref = oracle_step(ctx.d, ctx.params_np[m], ctx.x_np[m], labels=ctx.y_np[m], kink=KINK_MARGIN,
+                              masks=oracle_streams(r["seed"], r["base_stream"], B, T, 48, spec.F))
+            out = dict(logits=_np(lg[m]), grads=_np(got["grads"][m]), mean_loss=float(got["losses"][m]) / B)
+            assert_step_vs_oracle(out, ref, ctx.d, bounds_of(ctx.d), tag=f"{self.id} model {m}")
         if self.adam:
             pb, mb, vb = ctx.params.clone(), ctx.m0.clone(), ctx.v0.clone()
             gb = torch.empty_like(pb)
@@ -412,8 +382,8 @@ class SeqCase(Route):
         flat, x, y, masks, rng = case_inputs(case, seed=1 if grow else 0)
         spec = ops.ModelSpec(C=Cc, H=H, L=L, K=K, F=case_F(case), D=D)
         assert spec.seq_path(B, T)
-        ctx = types.SimpleNamespace(case=case, spec=spec, B=B, T=T, flat_np=flat, x_np=x, y_np=y, masks_np=masks, rng=rng, flat=_t(flat, dev),
-                                    x=_t(x.copy(), dev), y=_t(y, dev))
+        ctx = types.SimpleNamespace(case=case, spec=spec, B=B, T=T, flat_np=flat, x_np=x, y_np=y, masks_np=masks, rng=rng, flat=to_dev(flat, dev),
+                                    x=to_dev(x.copy(), dev), y=to_dev(y, dev))
         ctx.inputs = [ctx.flat, ctx.x, ctx.y]
         return ctx
 
@@ -515,7 +485,7 @@ def _ns(**kw):
 # nsd_zscore_fwd: the shape and bound of tests/test_gpu_parity.py's z-score test (2e-5 against the oracle)
 def _zs_make(dev, grow):
     x = synth_x(9 + (3 if grow else 0), 77 + (2 if grow else 0), C=5, seed=2 + grow)
-    return _ns(x_np=x, x=_t(x.copy(), dev))
+    return _ns(x_np=x, x=to_dev(x.copy(), dev))
 
 
 def _zs_out(ctx, arena):
@@ -546,7 +516,7 @@ def _aug_make(dev, grow):
     B, T = 5 + (3 if grow else 0), 7 + (2 if grow else 0)
     x = synth_x(3 * B, T, C=5, seed=7 + grow).reshape(3, B, T, 5)
     lab = synth_labels(3 * B, 3, seed=9 + grow).reshape(3, B).astype(np.int32)
-    return _ns(x_np=x, lab_np=lab, x=_t(x.copy(), dev), lab=_t(lab.reshape(-1), dev), w=_t(MIX["weights"], dev))
+    return _ns(x_np=x, lab_np=lab, x=to_dev(x.copy(), dev), lab=to_dev(lab.reshape(-1), dev), w=to_dev(MIX["weights"], dev))
 
 
 def _aug_launch(zscore):
@@ -562,7 +532,7 @@ def _aug_verify(zscore):
         from nsd_amd import ops
         ref = ar.augment_models(ctx.x_np, [(r["seed"], r["base_stream"]) for r in AUG_RNGS], **AUG)
         if zscore:                                          # bitwise what nsd_zscore_fwd gives on the unfused output (include/nsd.h)
-            ref = _np(ops.zscore(_t(ref.reshape((-1,) + ref.shape[2:]), dev))).reshape(ref.shape)
+            ref = _np(ops.zscore(to_dev(ref.reshape((-1,) + ref.shape[2:]), dev))).reshape(ref.shape)
         assert np.array_equal(_np(got["y"]).view(np.uint32), ref.view(np.uint32))
     return verify
 
@@ -654,7 +624,7 @@ def _adam_make(dev, grow):
     rs = np.random.RandomState(11 + grow)
     p, g = rs.standard_normal(n).astype(np.float32), rs.standard_normal(n).astype(np.float32)
     m, v = (rs.standard_normal(n) * 1e-3).astype(np.float32), (rs.random_sample(n) * 1e-6).astype(np.float32)
-    return _ns(p0_np=p, g_np=g, m0_np=m, v0_np=v, p0=_t(p, dev), g=_t(g, dev), m0=_t(m, dev), v0=_t(v, dev),
+    return _ns(p0_np=p, g_np=g, m0_np=m, v0_np=v, p0=to_dev(p, dev), g=to_dev(g, dev), m0=to_dev(m, dev), v0=to_dev(v, dev),
                skip0=torch.zeros(1, device=dev), skip1=torch.ones(1, device=dev), step_dev=torch.tensor([3], dtype=torch.int64, device=dev))
 
 
@@ -697,7 +667,7 @@ ROUTES += [Small(f"adam-step{'-' + f if f else ''}-n1001", _adam_make, _adam_lau
 def _acc_make(dev, grow):
     ctx = Fp32Step("", 8, 48, 2, 8, 64, (0, 5), 9).setup(dev, 0, grow)
     assert ctx.spec.param_count == 33753
-    ctx.old = _t((np.random.RandomState(5).standard_normal(ctx.spec.param_count) * 1e-2).astype(np.float32), dev)
+    ctx.old = to_dev((np.random.RandomState(5).standard_normal(ctx.spec.param_count) * 1e-2).astype(np.float32), dev)
     ctx.inputs.append(ctx.old)
     return ctx
 
@@ -733,7 +703,7 @@ def _gemm_make(M, N, K, kmajor, seed, grow_m=8):
         rs = np.random.RandomState(seed + grow)
         a = _bf(rs.standard_normal((K, Mm) if kmajor else (Mm, K)).astype(np.float32), dev)
         b = _bf(rs.standard_normal((K, N) if kmajor else (N, K)).astype(np.float32), dev)
-        return _ns(a=a, b=b, bias=_t(rs.standard_normal(Mm).astype(np.float32), dev), x=a)
+        return _ns(a=a, b=b, bias=to_dev(rs.standard_normal(Mm).astype(np.float32), dev), x=a)
     return make
 
 

@@ -25,7 +25,7 @@ Every case takes fc.0.bias = +-4 (head_inputs(safe=True)) and asserts that the O
 from the RReLU kink before it compares gradients.  Every train case runs with all three masks on (L = 1 has no inter-layer dropout).
 
 Bounds: logits 1e-4 (LOGIT_TOL), mean loss 5e-5, alpha / pooled / fc0_pre 5e-5, attn.bias 2e-6 absolute, probabilities 1e-5: the
-suite's own.  Gradients: FP32_EXACT (tests/test_gpu_parity.py), of each tensor's largest element (+1e-7) -- about eight times the worst
+suite's own.  Gradients: FP32_EXACT (tests/gpu_harness.py), of each tensor's largest element (+1e-7) -- about eight times the worst
 value measured over this whole file on one MI355X against the oracle, rounded up to one significant digit (the room FAST48 has), and
 no more than FAST48's 5e-5 / 2e-5:
   LSTM weights   wtol = 1e-5   measured 1.25e-6 (weight_ih_l0 of the generic L = 3 case, 2051 trials: 4102 rows summed by one workgroup;
@@ -47,35 +47,13 @@ import torch
 
 from oracle import nsd_oracle as orc
 from tests.golden.make_goldens import synth_labels, synth_params, synth_x
-from tests.test_fp32_routes_cpu import T_EDGES
-from tests.test_gpu_parity import FAST48, FP32_EXACT, LOGIT_TOL, _grad_close, _model, _t
-from tests.test_head_dims_cpu import KINK_MARGIN, head_inputs, kink_margin, kink_safe
+from tests.gpu_harness import (FAST48, FP32_EXACT, HEAD_TOL, KINK_MARGIN, LOGIT_TOL, PROB_TOL, T_EDGES, assert_step_vs_oracle, cus, dev, grad_class,  # noqa: F401
+                               grad_errors, head_inputs, kink_safe, model_from_state, nsd, oracle_step, spec_of, to_dev, train_step)
 
 pytestmark = pytest.mark.gpu
 
-LOSS_TOL = 5e-5
-HEAD_TOL = 5e-5                  # alpha, pooled, fc0_pre: section (a) of tests/test_gpu_head_dims.py
-NAN = float("nan")
 WORST = {}                       # class of number -> (worst value seen in this run, where): printed by the last test
 T_START = time.time()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()          # raises if libnsd_hip.so is missing: no fallback
-    return nsd_amd
-
-
-@pytest.fixture(scope="module")
-def cus(dev):
-    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
 
 
 def test_fp32_exact_is_no_looser_than_fast48():
@@ -83,13 +61,9 @@ def test_fp32_exact_is_no_looser_than_fast48():
 
 
 def _note(key, value, where):
-    if float(value) >= WORST.get(key, (0.0, ""))[0]:
-        WORST[key] = (float(value), where)
-
-
-def _spec(d):
-    from nsd_amd import ops
-    return ops.ModelSpec(C=d.C, H=d.H, L=d.L, K=d.K, F=d.F)
+    v = float(value)
+    if v != v or v >= WORST.get(key, (0.0, ""))[0]:          # (a NaN is noted, and stays)
+        WORST[key] = (v, where)
 
 
 @functools.lru_cache(maxsize=None)
@@ -99,79 +73,57 @@ def _inputs(Cc, H, L, K, F, B, T):
 
 
 def _oracle(d, flat, x, y, masks, residual):
-    """(loss, grads, forward) of the oracle; asserts the kink margin on ITS pre-activations first"""
-    fw = orc.forward(flat, x, d, saves=True, residual=residual, **masks)
-    margin = kink_margin(fw)
-    assert margin > KINK_MARGIN, margin
-    loss, dl = orc.ce_loss(fw["logits"], y)
-    return loss, orc.backward(flat, x, d, fw, dl, residual=residual, **masks), fw
+    """the oracle's step; asserts the kink margin on ITS pre-activations first"""
+    return oracle_step(d, flat, x, labels=y, masks=masks, residual=residual, kink=KINK_MARGIN)
 
 
 def _step(dev, d, flat_np, x, y, residual, **masks):
-    """ops.train_step_grads (the launch sequence of Trainer.step: for these shapes nsd_lstm_fwd + nsd_head_train, nsd_lstm_bwd,
-    nsd_grad_reduce) with the workspace, logits and gradients full of NaN beforehand -- nothing may be left unwritten"""
-    from nsd_amd import ops
-    spec = _spec(d)
-    B, T, _ = x.shape
-    flat, xt = _t(flat_np, dev), _t(x, dev)
-    ws = ops.new_workspace(spec, B, T, dev)
-    ws.fill_(NAN)
-    logits = torch.full((B, spec.K), NAN, device=dev)
-    grads = torch.full_like(flat, NAN)
-    mk = {k: _t(v, dev) for k, v in masks.items()}
-    ops.train_step_grads(spec, flat, xt, ws, _t(y.astype(np.int32), dev), logits, grads, residual=residual, **mk)
-    out = {r: ops.ws_view(ws, spec, B, T, r).cpu().numpy().copy() for r in ("alpha", "pooled", "fc0_pre", "loss")}
-    out.update(logits=logits.cpu().numpy(), grads=grads.cpu().numpy(), mean_loss=float(out["loss"].astype(np.float64).sum()) / B)
-    return out
+    """the launch sequence of Trainer.step: for these shapes nsd_lstm_fwd + nsd_head_train, nsd_lstm_bwd, nsd_grad_reduce"""
+    return train_step(dev, spec_of(d), flat_np, x, labels=y, residual=residual, masks=masks, saves=("alpha", "pooled", "fc0_pre"))
 
 
-def _grad_worst(tag, got_flat, ref_flat, d):
+def _note_grad_errors(tag, got_flat, ref_flat, d):
     """error / largest element of the worst tensor per class, against the oracle: what FP32_EXACT is derived from"""
-    got, ref = orc.unflatten(got_flat, d), orc.unflatten(ref_flat, d)
+    per, ref = grad_errors(got_flat, ref_flat, d)[0], orc.unflatten(ref_flat, d)
     worst = {"lstm.weight": (0.0, ""), "other": (0.0, "")}
-    for k in orc.param_names(d):
-        err = float(np.abs(got[k] - ref[k]).max())
-        if k == "attn.bias":
+    for k, (err, scale) in per.items():
+        cls = grad_class(k)
+        if cls == "attn.bias":
             _note("grad attn.bias (abs)", err, tag)
-            continue
-        if not np.abs(ref[k]).any():                        # exactly zero in the oracle (T = 1): absolute, held by _grad_close's 1e-7 floor
+        elif not np.abs(ref[k]).any():                      # exactly zero in the oracle (T = 1): absolute, held by grad_close's 1e-7 floor
             _note("grad of a zero tensor (abs)", err, f"{tag}: {k}")
-            continue
-        cls = "lstm.weight" if k.startswith("lstm.weight") else "other"
-        ratio = err / max(float(np.abs(ref[k]).max()), 1e-6)
-        if ratio >= worst[cls][0]:
-            worst[cls] = (ratio, k)
-        _note(f"grad {cls} / max", ratio, f"{tag}: {k}")
+        else:
+            ratio = err / scale
+            if ratio != ratio or ratio >= worst[cls][0]:
+                worst[cls] = (ratio, k)
+            _note(f"grad {cls} / max", ratio, f"{tag}: {k}")
     return worst
 
 
 def _vs_oracle(tag, d, out, ref, head=True):
     """logits, mean loss, the head's saved intermediates and every gradient tensor of a train step against _oracle's; prints first"""
-    loss_ref, g_ref, fw = ref
     logits, grads = out["logits"], out["grads"]
-    lerr = float(np.abs(logits - fw["logits"]).max())
-    herr = {k: float(np.abs(out[k] - fw[k]).max()) for k in ("alpha", "pooled", "fc0_pre")} if head else {}
+    lerr, serr = float(np.abs(logits - ref["logits"]).max()), abs(out["mean_loss"] - ref["loss"])
+    herr = {k: float(np.abs(out[k] - ref["fw"][k]).max()) for k in ("alpha", "pooled", "fc0_pre")} if head else {}
     finite = bool(np.isfinite(logits).all() and np.isfinite(grads).all())
-    w = _grad_worst(tag, grads, g_ref, d) if finite else {}
-    print(f"[{tag}] C={d.C} H={d.H} L={d.L} K={d.K} F={d.F} B={logits.shape[0]}: logits {lerr:.2e}  loss {abs(out['mean_loss'] - loss_ref):.2e}  "
+    w = _note_grad_errors(tag, grads, ref["grads"], d) if finite else {}
+    print(f"[{tag}] C={d.C} H={d.H} L={d.L} K={d.K} F={d.F} B={logits.shape[0]}: logits {lerr:.2e}  loss {serr:.2e}  "
           + "  ".join(f"{k} {v:.2e}" for k, v in herr.items())
           + "  grads / max: " + "  ".join(f"{c} {v:.2e} ({k})" for c, (v, k) in w.items()))
     assert finite, tag
     _note("logits (abs)", lerr, tag)
-    _note("loss (abs)", abs(out["mean_loss"] - loss_ref), tag)
-    assert lerr < LOGIT_TOL, (tag, lerr)
-    assert abs(out["mean_loss"] - loss_ref) < LOSS_TOL, (tag, out["mean_loss"], loss_ref)
+    _note("loss (abs)", serr, tag)
     for k, v in herr.items():
         _note(f"{k} (abs)", v, tag)
         assert v < HEAD_TOL, (tag, k, v)
-    _grad_close(grads, g_ref, d, **FP32_EXACT)
+    assert_step_vs_oracle(out, ref, d, FP32_EXACT)
 
 
 def _infer_vs_oracle(tag, dev, d, flat_np, x, residual):
     """ops.infer against the oracle's eval-mode forward: logits, probabilities (rows summing to 1), argmax where the oracle's top-two
     gap is clear, and trials 0, B // 2, B - 1 of the batch equal to their single-trial runs bit for bit"""
     from nsd_amd import ops
-    spec, flat, xt = _spec(d), _t(flat_np, dev), _t(x, dev)
+    spec, flat, xt = spec_of(d), to_dev(flat_np, dev), to_dev(x, dev)
     B = x.shape[0]
     lg_t, pr_t = ops.infer(spec, flat, xt, residual=residual)
     lg, pr = lg_t.cpu().numpy(), pr_t.cpu().numpy()
@@ -185,7 +137,7 @@ def _infer_vs_oracle(tag, dev, d, flat_np, x, residual):
     _note("infer probs (abs)", perr, tag)
     assert np.isfinite(lg).all() and np.isfinite(pr).all(), tag
     assert lerr < LOGIT_TOL, (tag, lerr)
-    assert perr < 1e-5, (tag, perr)
+    assert perr < PROB_TOL, (tag, perr)
     assert np.abs(pr.sum(1) - 1.0).max() < 1e-5
     srt = np.sort(ref["logits"], axis=1)
     clear = (srt[:, -1] - srt[:, -2]) > 2 * LOGIT_TOL
@@ -197,7 +149,7 @@ def _fast_path(d, B, T):
     """nsd_fast_path at the batch of the call (ModelSpec.fast_path asks at one trial; H = 64 depends on B)"""
     import ctypes as C
     from nsd_amd import _lib
-    dd = _spec(d).dims(B, T)
+    dd = spec_of(d).dims(B, T)
     return int(_lib.lib().nsd_fast_path(C.byref(dd)))
 
 
@@ -208,13 +160,13 @@ def _fast_path(d, B, T):
 def test_t_edges_one_trial_per_workgroup_vs_oracle(nsd, dev, cus, Cc, H, K, F, B, T, residual):
     from nsd_amd import ops
     d, flat, x, y, masks = _inputs(Cc, H, 2, K, F, B, T)
-    assert B <= cus and _fast_path(d, B, T) == 1 and not ops.rng_path(_spec(d), B, T)
-    assert ops.workspace_layout(_spec(d), B, T)[1].n_slabs == B            # one workgroup, one slab per trial
+    assert B <= cus and _fast_path(d, B, T) == 1 and not ops.rng_path(spec_of(d), B, T)
+    assert ops.workspace_layout(spec_of(d), B, T)[1].n_slabs == B            # one workgroup, one slab per trial
     ref = _oracle(d, flat, x, y, masks, residual)
     out = _step(dev, d, flat, x, y, residual, **masks)
     _vs_oracle(f"a T={T} residual={residual}", d, out, ref)
     if T == 1:                                             # h[-1] = 0: exactly zero in the oracle
-        g, g_ref = orc.unflatten(out["grads"], d), orc.unflatten(ref[1], d)
+        g, g_ref = orc.unflatten(out["grads"], d), orc.unflatten(ref["grads"], d)
         for k in ("lstm.weight_hh_l0", "lstm.weight_hh_l1"):
             assert np.abs(g_ref[k]).max() == 0.0
             _note("T=1 max |weight_hh grad|", np.abs(g[k]).max(), k)
@@ -263,7 +215,7 @@ def test_batch_bands_vs_oracle(nsd, dev, cus, row):
     B = m * cus + a
     d, flat, x, y, masks = _inputs(Cc, H, 2, K, F, B, T)
     nf, gf, grid_f, nb, gb, grid_b = _plan(B, cus)
-    n_slabs = ops.workspace_layout(_spec(d), B, T)[1].n_slabs
+    n_slabs = ops.workspace_layout(spec_of(d), B, T)[1].n_slabs
     print(f"[b {_band_id(row)}] cus={cus} B={B}: fast_path {_fast_path(d, B, T)}  n_slabs {n_slabs}  restated plan: fwd<{H},{nf}> {gf} groups on "
           f"{grid_f} workgroups, bwd<{H},{nb}> {gb} groups on {grid_b}")
     assert _fast_path(d, B, T) == fast
@@ -311,7 +263,7 @@ def test_generic_route_at_many_trials_vs_oracle(nsd, dev, cus, Cc, H, L, K, F, m
     from nsd_amd import ops
     B = mb[0] * cus + mb[1]
     d, flat, x, y, masks = _inputs(Cc, H, L, K, F, B, T)
-    assert _fast_path(d, B, T) == 0 and not (H % 16 == 0 and H >= 64) and ops.workspace_layout(_spec(d), B, T)[1].n_slabs == 1
+    assert _fast_path(d, B, T) == 0 and not (H % 16 == 0 and H >= 64) and ops.workspace_layout(spec_of(d), B, T)[1].n_slabs == 1
     assert (B > 8 * cus) == loops and ("drop_lstm" in masks) == (L > 1)
     tag = f"d generic H={H} L={L}"
     ref = _oracle(d, flat, x, y, masks, residual)
@@ -331,12 +283,12 @@ def test_trainer_step_at_hidden_size_32_matches_oracle_with_its_own_streams(nsd,
     H, K, F = 32, 3, 32
     d = orc.Dims(C=8, H=H, L=2, K=K, F=F)
     state = kink_safe(synth_params(8, H, 2, K, F=F, seed=H + F + K), F)
-    m = _model(nsd, dev, state).train()
+    m = model_from_state(nsd, dev, state).train()
     tr = Trainer(m, lr=1e-3, seed=7)
     B, T = cus + 44, 12
     x, y = synth_x(B, T, seed=F), synth_labels(B, K=K, seed=K)
     flat0 = orc.flatten_state(state, d)
-    tr.step(_t(x, dev), _t(y, dev))
+    tr.step(to_dev(x, dev), to_dev(y, dev))
     assert tr._bufs[(B, T)]["rng_ok"] is False
     masks = dict(drop_lstm=orc.dropout_mask(tr.seed, 4, 0.6, (1, B, T, H)), rrelu_slope=orc.rrelu_noise(tr.seed, 5, (B, F)),
                  drop_head=orc.dropout_mask(tr.seed, 6, 0.6, (B, F)))

@@ -5,8 +5,8 @@ The x1 waves and the dW waves of nsd_lstm2_bwd48.hip run the blocks of 8 macro s
 steps (no complete window, no hand-off before step 4, layer 0 five steps behind) and its last blocks (t <= 0, da outside the trial)
 keep the tests.  The edges are the first hand-off group, one, two and three 16-step windows, step counts that are 0 and 8 mod 16,
 and a workgroup's second trial (accumulators and windows carried across).  Everything goes through ops.train_step_grads -- the
-trainer's launch sequence, fused head -- or the module, against the CPU oracle within the bounds tests/test_gpu_parity.py holds
-this path to (restated here): LSTM weight gradients within 5e-5 of each tensor's largest element, every other tensor 2e-5
+trainer's launch sequence, fused head -- or the module, against the CPU oracle within the bounds of this path
+(tests/gpu_harness.py): LSTM weight gradients within 5e-5 of each tensor's largest element, every other tensor 2e-5
 (+1e-7; attn.bias 2e-6 absolute), logits 1e-4, batch-mean loss 5e-5, dL/dx 2e-5; against stock autograd 2e-4 as the existing
 input-gradient test.  The whole file takes a few seconds."""
 import numpy as np
@@ -15,70 +15,16 @@ import torch
 
 from oracle import nsd_oracle as orc
 from tests.golden.make_goldens import counter_masks, synth_labels, synth_params, synth_x
+from tests.gpu_harness import FAST48, D, assert_step_vs_oracle, dev, nsd, oracle_step, spec_of, to_dev, train_step  # noqa: F401  (dev, nsd: fixtures)
 
 pytestmark = pytest.mark.gpu
 
-D = orc.Dims()
-LOGIT_TOL, LOSS_TOL, DX_TOL = 1e-4, 5e-5, 2e-5
-FAST48 = dict(rtol=2e-5, wtol=5e-5)
 RNG = dict(seed=123, base_stream=12, p_lstm=0.6, p_head=0.6)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()          # raises if libnsd_hip.so is missing: no fallback
-    return nsd_amd
-
-
-def _t(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _grad_close(got_flat, ref_flat, d, rtol, wtol):
-    """tests/test_gpu_parity.py's bound: every gradient tensor within rtol of its largest element (+1e-7), the LSTM weight
-    gradients within wtol, attn.bias within 2e-6 absolute"""
-    got, ref = orc.unflatten(got_flat, d), orc.unflatten(ref_flat, d)
-    worst, bad = {"lstm.weight": 0.0, "other": 0.0, "attn.bias": 0.0}, []
-    for k in orc.param_names(d):
-        err = float(np.abs(got[k] - ref[k]).max())
-        if k == "attn.bias":
-            worst[k] = max(worst[k], err)
-            if not err < 2e-6:
-                bad.append((k, err))
-            continue
-        scale = max(float(np.abs(ref[k]).max()), 1e-6)
-        cls = "lstm.weight" if k.startswith("lstm.weight") else "other"
-        worst[cls] = max(worst[cls], err / scale)
-        if not err <= (wtol if cls == "lstm.weight" else rtol) * scale + 1e-7:
-            bad.append((k, err, scale))
-    print("grad_close worst", {k: f"{v:.2e}" for k, v in worst.items()}, "bounds", (rtol, wtol))
-    assert not bad, bad
-
-
-def _step(dev, flat_np, x, y, *, spec=None, masks=None, rng=None, residual=False, want_dx=False):
-    """ops.train_step_grads (fused head) -> logits, per-trial loss, flat gradient (+ dx)"""
-    from nsd_amd import ops
-    spec = spec or ops.ModelSpec()
-    B, T, _ = x.shape
-    flat, xt = _t(flat_np, dev), _t(x, dev)
-    ws = ops.new_workspace(spec, B, T, dev)
-    ws.fill_(float("nan"))                                   # nothing may be left unwritten
-    logits = torch.full((B, spec.K), float("nan"), device=dev)
-    grads = torch.empty_like(flat)
-    dx = torch.full_like(xt, float("nan")) if want_dx else None
-    ops.train_step_grads(spec, flat, xt, ws, _t(y.astype(np.int32), dev), logits, grads, residual=residual, fused_head=True, rng=rng, dx=dx,
-                         **{k: _t(v, dev) for k, v in (masks or {}).items()})
-    out = dict(logits=logits.cpu().numpy(), grads=grads.cpu().numpy(), loss=ops.ws_view(ws, spec, B, T, "loss").cpu().numpy().copy())
-    if want_dx:
-        out["dx"] = dx.cpu().numpy()
-    return out
+def _step(dev, flat_np, x, y, *, spec=None, **kw):
+    """the fused step of the reference model (or of spec)"""
+    return train_step(dev, spec or spec_of(D), flat_np, x, labels=y, **kw)
 
 
 def _streams(B, T):
@@ -88,12 +34,8 @@ def _streams(B, T):
                 drop_head=orc.dropout_mask(s, sid + 2, p, (B, 32)))
 
 
-def _against_oracle(out, flat_np, x, y, d, masks, residual=False):
-    B = x.shape[0]
-    loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, d, residual=residual, **masks)
-    assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL
-    assert abs(float(out["loss"].sum()) / B - loss_ref) < LOSS_TOL
-    _grad_close(out["grads"], g_ref, d, **FAST48)
+def _against_oracle(out, flat_np, x, y, d, masks, residual=False, want_dx=False):
+    assert_step_vs_oracle(out, oracle_step(d, flat_np, x, labels=y, masks=masks, residual=residual, want_dx=want_dx), d, FAST48)
 
 
 @pytest.fixture(scope="module")
@@ -157,8 +99,8 @@ def test_input_gradient_against_stock_autograd(nsd, dev, ref_state, T):
     xn, yn = synth_x(B, T, seed=900 + T), synth_labels(B, seed=901 + T).astype(np.int64)
     xr = torch.from_numpy(xn).requires_grad_(True)
     torch.nn.functional.cross_entropy(ref(xr), torch.from_numpy(yn)).backward()
-    xg = _t(xn, dev).requires_grad_(True)
-    torch.nn.functional.cross_entropy(m(xg), _t(yn, dev)).backward()
+    xg = to_dev(xn, dev).requires_grad_(True)
+    torch.nn.functional.cross_entropy(m(xg), to_dev(yn, dev)).backward()
     assert xg.grad is not None and torch.isfinite(xg.grad).all()
     err, scale = (xg.grad.cpu() - xr.grad).abs().max().item(), xr.grad.abs().max().item()
     print(f"dx T={T}: max error {err:.3e}, largest element {scale:.3e}")
@@ -176,12 +118,6 @@ def test_a_workgroup_walks_two_trials(nsd, dev, flat_ref):
     x, y = synth_x(B, T, seed=41), synth_labels(B, seed=42)
     masks = _streams(B, T)
     out = _step(dev, flat_ref, x, y, masks=masks, want_dx=True)
-    _against_oracle(out, flat_ref, x, y, D, masks)
-    fw = orc.forward(flat_ref, x, D, saves=True, **masks)
-    _, dl = orc.ce_loss(fw["logits"], y)
-    _, dx_ref = orc.backward(flat_ref, x, D, fw, dl.astype(np.float32), want_dx=True, **masks)
-    err, scale = float(np.abs(out["dx"] - dx_ref).max()), float(np.abs(dx_ref).max())
-    print(f"dx B={B} T={T}: max error / largest element {err / scale:.2e}")
-    assert err <= DX_TOL * scale, (err, scale)
+    _against_oracle(out, flat_ref, x, y, D, masks, want_dx=True)
     again = _step(dev, flat_ref, x, y, masks=masks, want_dx=True)
     assert again["grads"].tobytes() == out["grads"].tobytes() and again["dx"].tobytes() == out["dx"].tobytes()

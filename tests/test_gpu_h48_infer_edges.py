@@ -17,12 +17,11 @@ import torch
 
 from oracle import nsd_oracle as orc
 from tests.golden.make_goldens import synth_params, synth_x
-from tests.test_gpu_parity import LOGIT_TOL, D, _t, dev, nsd  # noqa: F401  (dev, nsd: fixtures)
+from tests.gpu_harness import INFER_T, LOGIT_TOL, PROB_TOL, D, dev, nsd, to_dev  # noqa: F401  (dev, nsd: fixtures)
 
 pytestmark = pytest.mark.gpu
 
-PROB_TOL, ROW_SUM_TOL, ARGMAX_GAP = 1e-5, 1e-6, 1e-3
-INFER_T = tuple(range(1, 101)) + (126, 127, 158, 250, 254, 255, 256, 257, 1022, 1023, 1024, 1025, 1026)
+ROW_SUM_TOL, ARGMAX_GAP = 1e-6, 1e-3
 
 
 def _infer(dev, spec, flat, x, *, residual=False, want_probs=True):
@@ -60,8 +59,8 @@ def test_inference_vs_oracle_at_every_step_count(nsd, dev, ref_state, T):
     from nsd_amd import ops
     spec, B = ops.ModelSpec(), 3
     flat_np = orc.flatten_state(ref_state, D)
-    flat, xn = _t(flat_np, dev), synth_x(B, T, seed=500 + T)
-    x = _t(xn, dev)
+    flat, xn = to_dev(flat_np, dev), synth_x(B, T, seed=500 + T)
+    x = to_dev(xn, dev)
     lg, pr = _infer(dev, spec, flat, x)
     _check_vs_oracle(lg, pr, flat_np, xn, D, what=("T", T))
     for b in range(B):
@@ -79,12 +78,12 @@ def test_inference_residual_flag_and_three_channels(nsd, dev, ref_state, T):
     from nsd_amd import ops
     B = 3
     flat_np, xn = orc.flatten_state(ref_state, D), synth_x(B, T, seed=700 + T)
-    lg, pr = _infer(dev, ops.ModelSpec(), _t(flat_np, dev), _t(xn, dev), residual=True)
+    lg, pr = _infer(dev, ops.ModelSpec(), to_dev(flat_np, dev), to_dev(xn, dev), residual=True)
     _check_vs_oracle(lg, pr, flat_np, xn, D, residual=True, what=("residual", T))
     d3, spec3 = orc.Dims(C=3), ops.ModelSpec(C=3)
     flat3, x3 = orc.flatten_state(synth_params(3, 48, 2, 3, seed=43), d3), synth_x(B, T, C=3, seed=800 + T)
     for residual in (False, True):
-        lg, pr = _infer(dev, spec3, _t(flat3, dev), _t(x3, dev), residual=residual)
+        lg, pr = _infer(dev, spec3, to_dev(flat3, dev), to_dev(x3, dev), residual=residual)
         _check_vs_oracle(lg, pr, flat3, x3, d3, residual=residual, what=("C=3", residual, T))
 
 
@@ -95,7 +94,7 @@ def test_inference_when_a_workgroup_pools_a_second_trial(nsd, dev, ref_state, T)
     spec = ops.ModelSpec()
     B = torch.cuda.get_device_properties(dev).multi_processor_count + 2
     flat_np, xn = orc.flatten_state(ref_state, D), synth_x(B, T, seed=900 + T)
-    flat, x = _t(flat_np, dev), _t(xn, dev)
+    flat, x = to_dev(flat_np, dev), to_dev(xn, dev)
     lg, pr = _infer(dev, spec, flat, x)
     _check_vs_oracle(lg, pr, flat_np, xn, D, what=("B", B, "T", T))
     for b in (0, 1, B - 2, B - 1):                            # first and second trial of the workgroups that loop

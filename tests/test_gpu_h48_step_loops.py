@@ -11,40 +11,17 @@ import pytest
 import torch
 
 from oracle import nsd_oracle as orc
-from tests import mixup_ref as mr
 from tests.golden.make_goldens import counter_masks, synth_labels, synth_x
-from tests.test_gpu_multimodel import _multi, _problem, _single, _spec
-from tests.test_gpu_parity import DX_TOL, FAST48, LOGIT_TOL, D, _grad_close, _t, dev, nsd  # noqa: F401  (dev, nsd: fixtures)
-from tests.test_gpu_soft_targets import LOSS_TOL, _oracle_streams, _targets
+from tests.gpu_harness import (BWD_T, FAST48, FWD_T, D, assert_step_vs_oracle, dev, multi_problem, multi_single, multi_step, nsd, oracle_step,  # noqa: F401
+                               oracle_streams, soft_targets, spec_of, train_step)
 
 pytestmark = pytest.mark.gpu
 
-# T' of the forward's prefix pairs: around the ring (16), the x chunk (32) and their multiples, +-2 for layer 1's lag
-FWD_T = (1, 2, 3, 13, 14, 15, 16, 17, 18, 29, 30, 31, 32, 33, 34, 47, 48, 49, 63, 64, 65)
-# ... and what the backward adds: its 8-step ring, the four-step hand-off groups and layer 0's five-step lag
-BWD_T = tuple(sorted(set(FWD_T) | {4, 5, 6, 7, 8, 9, 11, 12, 20, 21, 24, 25}))
 RNG = dict(seed=77, base_stream=8, p_lstm=0.6, p_head=0.6)
 
 
-def _step(dev, flat_np, x, *, labels=None, targets=None, masks=None, rng=None, want_dx=False, fused=True, residual=False, saves=()):
-    """ops.train_step_grads -> logits, per-trial loss, flat gradient (+ dx, + the named workspace regions)"""
-    from nsd_amd import ops
-    spec = ops.ModelSpec()
-    B, T, _ = x.shape
-    flat, xt = _t(flat_np, dev), _t(x, dev)
-    ws = ops.new_workspace(spec, B, T, dev)
-    ws.fill_(float("nan"))                                   # nothing may be left unwritten
-    logits = torch.full((B, spec.K), float("nan"), device=dev)
-    grads = torch.empty_like(flat)
-    dx = torch.full_like(xt, float("nan")) if want_dx else None
-    ops.train_step_grads(spec, flat, xt, ws, _t(labels, dev), logits, grads, residual=residual, fused_head=fused, rng=rng, dx=dx,
-                         targets=_t(targets, dev), **{k: _t(v, dev) for k, v in (masks or {}).items()})
-    out = dict(logits=logits.cpu().numpy(), grads=grads.cpu().numpy(), loss=ops.ws_view(ws, spec, B, T, "loss").cpu().numpy().copy())
-    if want_dx:
-        out["dx"] = dx.cpu().numpy()
-    for r in saves:
-        out[r] = ops.ws_view(ws, spec, B, T, r).cpu().numpy().copy()
-    return out
+def _step(dev, flat_np, x, **kw):
+    return train_step(dev, spec_of(D), flat_np, x, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -83,32 +60,17 @@ def test_forward_saves_of_a_prefix_are_bit_equal(nsd, dev, ref_state, residual, 
 # ---------------------------------------------------------------------------------------------------
 # backward and the whole step against the oracle
 # ---------------------------------------------------------------------------------------------------
-def _oracle(flat_np, x, masks, labels=None, targets=None):
-    fw = orc.forward(flat_np, x, D, saves=True, **masks)
-    if targets is None:
-        loss, dl = orc.ce_loss(fw["logits"], labels)
-    else:
-        loss, dl = mr.soft_ce(fw["logits"], targets, 1.0 / x.shape[0])
-    g, dx = orc.backward(flat_np, x, D, fw, dl.astype(np.float32), want_dx=True, **masks)
-    return fw["logits"], float(np.sum(loss)) / x.shape[0] if np.ndim(loss) else float(loss), g, dx      # (mean loss)
-
-
 def _check_step_vs_oracle(dev, flat_np, B, T):
     """hard labels and soft targets; explicit multipliers with and without dx, and the same streams drawn in the kernels"""
-    x, y, q = synth_x(B, T, seed=7 * B + T), synth_labels(B, seed=B + T), _targets(B, 3, seed=3 * B + T)
-    masks = _oracle_streams(RNG["seed"], RNG["base_stream"], B, T, 48, 32)           # the values the kernels draw from RNG
+    x, y, q = synth_x(B, T, seed=7 * B + T), synth_labels(B, seed=B + T), soft_targets(B, 3, seed=3 * B + T)
+    masks = oracle_streams(RNG["seed"], RNG["base_stream"], B, T, 48, 32)           # the values the kernels draw from RNG
     for kind, tgt in (("hard", dict(labels=y)), ("soft", dict(targets=q))):
-        lg_ref, loss_ref, g_ref, dx_ref = _oracle(flat_np, x, masks, **tgt)
+        ref = oracle_step(D, flat_np, x, masks=masks, want_dx=True, **tgt)
         plain = _step(dev, flat_np, x, masks=masks, **tgt)
         with_dx = _step(dev, flat_np, x, masks=masks, want_dx=True, **tgt)
         drawn = _step(dev, flat_np, x, rng=RNG, **tgt)
         for name, out in (("plain", plain), ("dx", with_dx), ("rng", drawn)):
-            assert np.abs(out["logits"] - lg_ref).max() < LOGIT_TOL, (kind, name)
-            assert abs(float(out["loss"].sum()) / B - loss_ref) < LOSS_TOL, (kind, name)
-            _grad_close(out["grads"], g_ref, D, **FAST48)
-        err, scale = float(np.abs(with_dx["dx"] - dx_ref).max()), float(np.abs(dx_ref).max())
-        print(f"dx B={B} T={T} {kind}: max error / largest element {err / scale:.2e}")
-        assert err <= DX_TOL * scale, (kind, err, scale)
+            assert_step_vs_oracle(out, ref, D, FAST48)
         # the two mask modes run the same arithmetic on the same values
         for k in ("logits", "loss", "grads"):
             assert drawn[k].tobytes() == plain[k].tobytes(), (kind, k)
@@ -132,11 +94,11 @@ def test_step_vs_oracle_when_a_workgroup_walks_a_second_trial(nsd, dev, ref_stat
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("T", [15, 33])
 def test_model_batched_launch_is_bit_equal_to_single_model_launches(nsd, dev, T):
-    spec, M, B = _spec(nsd), 2, 3
-    params, x, y, rngs = _problem(spec, M, B, T, dev, seed=T)
-    lg, gr, ls = _multi(nsd, spec, params, x, y, rngs, dev)
+    spec, M, B = spec_of(D), 2, 3
+    params, x, y, rngs = multi_problem(spec, M, B, T, dev, seed=T)
+    lg, gr, ls = multi_step(nsd, spec, params, x, y, rngs, dev)
     for m in range(M):
-        l1, g1, s1 = _single(nsd, spec, params[m].clone(), x[m], y[m], rngs[m], dev)
+        l1, g1, s1 = multi_single(nsd, spec, params[m].clone(), x[m], y[m], rngs[m], dev)
         assert torch.equal(lg[m], l1), m
         assert torch.equal(gr[m], g1), m
         assert float(ls[m]) == s1, m

@@ -7,7 +7,7 @@ is not LEAN, the backward twin keeps a private segment.  The single-model kernel
 ops.multi_infer, against
   * the CPU oracle, each model's streams regenerated on the host from rngs[m] (as tests/test_gpu_multimodel.py does), and
   * the model's own single-model ops.train_step_grads / ops.infer run.
-Bounds against the oracle are the project's (tests/test_gpu_parity.py): logits 1e-4, batch-mean loss 5e-5, FAST48 (LSTM weight
+Bounds against the oracle are the project's (tests/gpu_harness.py): logits 1e-4, batch-mean loss 5e-5, FAST48 (LSTM weight
 gradients 5e-5 of each tensor's largest element, the other tensors 2e-5 + 1e-7, attn.bias 2e-6 absolute), probabilities 1e-5.
 The workspace and every output are NaN-filled before every call.
 """
@@ -18,15 +18,11 @@ import pytest
 import torch
 
 from oracle import nsd_oracle as orc
-from tests import mixup_ref as mr
-from tests.test_gpu_h48_infer_edges import INFER_T, PROB_TOL
-from tests.test_gpu_h48_step_loops import BWD_T
-from tests.test_gpu_multimodel import _grad_ok, _problem
-from tests.test_gpu_parity import FAST48, LOGIT_TOL, _grad_close, dev, nsd  # noqa: F401  (dev, nsd: fixtures)
+from tests.gpu_harness import (BWD_T, FAST48, INFER_T, KINK, LOGIT_TOL, PROB_TOL, assert_step_vs_oracle, dev, kink_margin, multi_grad_ok,  # noqa: F401
+                               multi_problem, nsd, oracle_step, oracle_streams)
 
 pytestmark = pytest.mark.gpu
 
-LOSS_TOL = 5e-5
 EDGE_T = tuple(sorted(set(range(1, 49)) | set(BWD_T)))       # every step count up to 48, then the ring / x-chunk edges up to 65
 
 
@@ -62,55 +58,38 @@ def _single(spec, flat, x, y, rng, dev, targets=None):
 
 
 def _streams(rng, B, T):
-    if rng is None:                                           # no dropout, the eval slope: the oracle's defaults
-        return {}
-    return dict(drop_lstm=orc.dropout_mask(rng["seed"], rng["base_stream"], 0.6, (1, B, T, 48)),
-                rrelu_slope=orc.rrelu_noise(rng["seed"], rng["base_stream"] + 1, (B, 32)),
-                drop_head=orc.dropout_mask(rng["seed"], rng["base_stream"] + 2, 0.6, (B, 32)))
+    """no rng: no dropout, the eval slope -- the oracle's defaults"""
+    return {} if rng is None else oracle_streams(rng["seed"], rng["base_stream"], B, T, 48, 32)
 
 
-# The head's RReLU has a kink at 0: a pre-activation of fc.0 that the oracle and a kernel round to different sides of it changes that
-# trial's whole backward (1 / B of every gradient), without either being wrong.  The kernels' fc.0 sums 48 fp32 products of LayerNorm
-# outputs (|.| <= 3) and weights (|.| <= 0.2) in another order than the oracle's: at most 48 x 2^-24 x 0.6 = 1.7e-6 apart.  The inputs
-# are drawn again (seed + 100000, ...) until every pre-activation of the oracle is three times that away from 0; with 3 x 171 trials
-# at T = 16 the first draw has one at +6.5e-9 (model 1, trial 168, unit 14; +7.7e-9 in the float64 model, from which the oracle's
-# pre-activations are at most 1.8e-7 away): the four-trial twin took the oracle's side, the single-model kernel the other.
-KINK = 5e-6
-
-
+# The inputs are drawn again (seed + 100000, ...) until every fc.0 pre-activation of the oracle is KINK (tests/gpu_harness.py) away
+# from 0; with 3 x 171 trials at T = 16 the first draw has one at +6.5e-9 (model 1, trial 168, unit 14; +7.7e-9 in the float64 model,
+# from which the oracle's pre-activations are at most 1.8e-7 away): the four-trial twin took the oracle's side, the single-model
+# kernel the other.
 def _kink_margin(spec, flat, x, rng):
     d = orc.Dims(C=spec.C, K=spec.K)
-    fw = orc.forward(flat.cpu().numpy(), x.cpu().numpy(), d, saves=True, **_streams(rng, x.shape[0], x.shape[1]))
-    return float(np.abs(fw["fc0_pre"]).min())
+    return kink_margin(orc.forward(flat.cpu().numpy(), x.cpu().numpy(), d, saves=True, **_streams(rng, x.shape[0], x.shape[1])))
 
 
 def _problem_off_kink(spec, M, B, T, dev, seed, with_streams=(True,)):
-    """tests/test_gpu_multimodel.py's _problem, drawn again until no fc.0 pre-activation lies within KINK of the RReLU kink"""
+    """multi_problem, drawn again until no fc.0 pre-activation lies within KINK of the RReLU kink"""
     for k in range(50):
-        params, x, y, rngs = _problem(spec, M, B, T, dev, seed=seed + 100000 * k)
+        params, x, y, rngs = multi_problem(spec, M, B, T, dev, seed=seed + 100000 * k)
         if all(_kink_margin(spec, params[m], x[m], rngs[m] if on else None) > KINK for m in range(M) for on in with_streams):
             return params, x, y, rngs
     raise AssertionError("no draw away from the RReLU kink")
 
 
 def _vs_oracle(spec, flat, x, y, rng, lg, gr, loss_sum, targets=None, what=None):
-    """one model of a launch against the oracle: logits, batch-mean loss, every gradient tensor (FAST48)"""
+    """one model of a launch against the oracle: logits, batch-mean loss, every gradient tensor (FAST48); the oracle asserts KINK on
+    its own pre-activations (a condition on the inputs: _problem_off_kink)"""
     d = orc.Dims(C=spec.C, K=spec.K)
     B, T, _ = x.shape
-    flat_np, xn, masks = flat.cpu().numpy(), x.cpu().numpy(), _streams(rng, B, T)
-    fw = orc.forward(flat_np, xn, d, saves=True, **masks)
-    if targets is None:
-        loss_ref, dl = orc.ce_loss(fw["logits"], y.cpu().numpy())
-    else:
-        per, dl = mr.soft_ce(fw["logits"], targets.cpu().numpy(), 1.0 / B)
-        loss_ref = float(np.sum(per)) / B
-    assert float(np.abs(fw["fc0_pre"]).min()) > KINK, what     # (a condition on the inputs: _problem_off_kink)
-    g_ref = orc.backward(flat_np, xn, d, fw, np.asarray(dl, np.float32), **masks)
-    e_l, e_s = float(np.abs(lg.cpu().numpy() - fw["logits"]).max()), abs(float(loss_sum) / B - loss_ref)
-    print(f"twin {what}: logits {e_l:.2e} loss {e_s:.2e}")
-    assert e_l < LOGIT_TOL, (what, e_l)
-    assert e_s < LOSS_TOL, (what, e_s)
-    _grad_close(gr.cpu().numpy(), g_ref, d, **FAST48)
+    tgt = dict(labels=y.cpu().numpy()) if targets is None else dict(targets=targets.cpu().numpy())
+    ref = oracle_step(d, flat.cpu().numpy(), x.cpu().numpy(), masks=_streams(rng, B, T), kink=KINK, **tgt)
+    out = dict(logits=lg.cpu().numpy(), grads=gr.cpu().numpy(), mean_loss=float(loss_sum) / B)
+    print(f"twin {what}: logits {float(np.abs(out['logits'] - ref['logits']).max()):.2e} loss {abs(out['mean_loss'] - ref['loss']):.2e}")
+    assert_step_vs_oracle(out, ref, d, FAST48)
 
 
 def _bit_equal_to_singles(spec, params, x, y, rngs, dev, got, targets=None):
@@ -134,7 +113,7 @@ def _close_to_singles(spec, params, x, y, rngs, dev, got, models=None):
     for m in (range(lg.shape[0]) if models is None else models):
         l1, g1, s1 = _single(spec, params[m], x[m], y[m], rngs[m], dev)
         assert float((lg[m] - l1).abs().max()) <= 1e-6 * max(float(l1.abs().max()), 1.0), m
-        _grad_ok(spec, gr[m], g1)
+        multi_grad_ok(spec, gr[m], g1)
         a, b = float(ls[m]) / B, float(s1) / B
         assert abs(a - b) <= 1e-6 * max(1.0, abs(b)), (m, a, b)
 
@@ -283,7 +262,7 @@ def test_multi_infer_is_bit_equal_to_infer_at_every_step_count(nsd, dev, T):
     path's 1024 steps the call is refused."""
     from nsd_amd import ops
     spec, M, B = _spec(nsd), 2, 3
-    params, x, _, _ = _problem(spec, M, B, T, dev, seed=9000 + T)
+    params, x, _, _ = multi_problem(spec, M, B, T, dev, seed=9000 + T)
     if not ops.multi_path(spec, M, B, T):
         assert T > 1024
         with pytest.raises(nsd.NsdError):
@@ -302,7 +281,7 @@ def test_multi_infer_when_a_workgroup_pools_a_second_trial(nsd, dev, T):
     """M = 2, B = #CUs / 2 + 3: three workgroups of each model reset the pooling state (pool_reset) and walk a second trial."""
     spec, M = _spec(nsd), 2
     B = torch.cuda.get_device_properties(dev).multi_processor_count // 2 + 3
-    params, x, _, _ = _problem(spec, M, B, T, dev, seed=9500 + T)
+    params, x, _, _ = multi_problem(spec, M, B, T, dev, seed=9500 + T)
     lg, pr = _multi_infer(spec, params, x, dev)
     d = orc.Dims()
     for m in range(M):

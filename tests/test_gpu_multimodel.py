@@ -3,73 +3,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_harness import LOGIT_TOL, LOSS_TOL, D, dev, multi_grad_ok, multi_problem, multi_single, multi_step, nsd, spec_of  # noqa: F401  (dev, nsd: fixtures)
+
 pytestmark = pytest.mark.gpu
-
-SPEC = dict(C=8, H=48, L=2, K=3, F=32)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()
-    return nsd_amd
-
-
-def _spec(nsd):
-    return nsd.ModelSpec(**SPEC)
-
-
-def _problem(spec, M, B, T, dev, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    params = ((torch.rand((M, spec.param_count), generator=g) - 0.5) * 0.4).to(dev)
-    x = torch.randn((M, B, T, spec.C), generator=g).to(dev)
-    y = torch.randint(0, spec.K, (M, B), generator=g, dtype=torch.int32).to(dev)
-    rngs = [dict(seed=1000 + 17 * m, base_stream=4 * (m + 1), p_lstm=0.6, p_head=0.6) for m in range(M)]
-    return params, x, y, rngs
-
-
-def _single(nsd, spec, flat, x, y, rng, dev, adam=None):
-    from nsd_amd import ops
-    B, T, _ = x.shape
-    ws = ops.new_workspace(spec, B, T, dev)
-    logits = torch.empty((B, spec.K), dtype=torch.float32, device=dev)
-    grads = torch.empty(spec.param_count, dtype=torch.float32, device=dev)
-    ops.train_step_grads(spec, flat, x.contiguous(), ws, y.contiguous(), logits, grads, rng=rng, adam=adam)
-    loss = ops.loss_sum(spec, ws, B, T)
-    return logits, grads, float(loss.item()) / B
-
-
-def _multi(nsd, spec, params, x, y, rngs, dev, fuse_adam=False, m=None, v=None, step=1):
-    from nsd_amd import ops
-    M = params.shape[0]
-    B, T = y.shape[1], x.shape[-2]
-    ws = ops.multi_workspace(spec, M, B, T, dev)
-    grads = torch.empty_like(params)
-    logits = ops.multi_train_step(spec, params, x, y.contiguous().view(-1), ws, grads, rngs=rngs, fuse_adam=fuse_adam, m=m, v=v, step=step)
-    losses = ops.multi_loss_sum(spec, ws, M, B, T).cpu().double() / B
-    return logits.view(M, B, spec.K), grads, losses
-
-
-def _grad_ok(spec, got, ref):
-    """The H = 48 bounds of test_gpu_parity.py (_grad_close with FAST48): LSTM weight gradients within 5e-5 of their largest element,
-    the other tensors within 2e-5 (+1e-7), attn.bias (a sum over time that is zero but for rounding) within 2e-6 absolute."""
-    offs, shapes = spec.offsets(), spec.shapes()
-    for n, shp in shapes.items():
-        n_el = int(np.prod(shp))
-        a, b = got[offs[n]:offs[n] + n_el], ref[offs[n]:offs[n] + n_el]
-        err = float((a - b).abs().max())
-        if n == "attn.bias":
-            assert err < 2e-6, (n, err)
-            continue
-        tol = 5e-5 if n.startswith("lstm.weight") else 2e-5
-        scale = max(float(b.abs().max()), 1e-6)
-        assert err <= tol * scale + 1e-7, (n, err, scale)
 
 
 @pytest.mark.parametrize("B", [32, 300, 600])
@@ -78,17 +14,17 @@ def test_one_model_is_todays_path_bitwise(nsd, dev, B):
     nsd_grad_reduce(_adam) themselves, so no model-batched kernel runs here.  The test pins that routing (and the 1/B loss scale,
     the workspace layout and the Adam tail of the multi entry points at M = 1); the model-batched kernels are held to single-model
     runs and to the oracle by the tests below."""
-    spec = _spec(nsd)
-    params, x, y, rngs = _problem(spec, 1, B, 40, dev, seed=B)
-    lg, gr, ls = _multi(nsd, spec, params, x, y, rngs, dev)
-    l1, g1, s1 = _single(nsd, spec, params[0].clone(), x[0], y[0], rngs[0], dev)
+    spec = spec_of(D)
+    params, x, y, rngs = multi_problem(spec, 1, B, 40, dev, seed=B)
+    lg, gr, ls = multi_step(nsd, spec, params, x, y, rngs, dev)
+    l1, g1, s1 = multi_single(nsd, spec, params[0].clone(), x[0], y[0], rngs[0], dev)
     assert torch.equal(lg[0], l1) and torch.equal(gr[0], g1) and float(ls[0]) == s1
     # Adam rides in the reduction: p / m / v after the step equal the single-model fused launch
     p_multi, p_single = params.clone(), params[0].clone()
     mm, vv = torch.zeros_like(p_multi), torch.zeros_like(p_multi)
     m1, v1 = torch.zeros_like(p_single), torch.zeros_like(p_single)
-    _multi(nsd, spec, p_multi, x, y, rngs, dev, fuse_adam=True, m=mm, v=vv, step=1)
-    _single(nsd, spec, p_single, x[0], y[0], rngs[0], dev, adam=dict(m=m1, v=v1, step=1))
+    multi_step(nsd, spec, p_multi, x, y, rngs, dev, fuse_adam=True, m=mm, v=vv, step=1)
+    multi_single(nsd, spec, p_single, x[0], y[0], rngs[0], dev, adam=dict(m=m1, v=v1, step=1))
     assert torch.equal(p_multi[0], p_single) and torch.equal(mm[0], m1) and torch.equal(vv[0], v1)
 
 
@@ -96,25 +32,25 @@ def test_one_model_is_todays_path_bitwise(nsd, dev, B):
 def test_models_equal_separate_runs(nsd, dev, M, B, T):
     """(5, 32) / (10, 32): one-trial kernels, (2, 200): two-trial forward + one-trial backward, (25, 32) / (3, 171) / (17, 32): the
     four-trial kernels (3 x 171: partial groups in every model), at T = 9 .. 625 (625: the recorded trials' length)."""
-    spec = _spec(nsd)
-    params, x, y, rngs = _problem(spec, M, B, T, dev, seed=M * 1000 + B)
-    lg, gr, ls = _multi(nsd, spec, params, x, y, rngs, dev)
+    spec = spec_of(D)
+    params, x, y, rngs = multi_problem(spec, M, B, T, dev, seed=M * 1000 + B)
+    lg, gr, ls = multi_step(nsd, spec, params, x, y, rngs, dev)
     for m in range(M):
-        l1, g1, s1 = _single(nsd, spec, params[m].clone(), x[m], y[m], rngs[m], dev)
+        l1, g1, s1 = multi_single(nsd, spec, params[m].clone(), x[m], y[m], rngs[m], dev)
         assert float((lg[m] - l1).abs().max()) <= 1e-6 * max(float(l1.abs().max()), 1.0), m
-        _grad_ok(spec, gr[m], g1)
+        multi_grad_ok(spec, gr[m], g1)
         assert abs(float(ls[m]) - s1) <= 1e-6 * max(1.0, abs(s1)), (m, float(ls[m]), s1)
 
 
 @pytest.mark.parametrize("M,B", [(5, 32), (5, 120)])
 def test_models_are_isolated(nsd, dev, M, B):
-    spec = _spec(nsd)
-    params, x, y, rngs = _problem(spec, M, B, 24, dev, seed=7)
-    lg, gr, _ = _multi(nsd, spec, params, x, y, rngs, dev)
+    spec = spec_of(D)
+    params, x, y, rngs = multi_problem(spec, M, B, 24, dev, seed=7)
+    lg, gr, _ = multi_step(nsd, spec, params, x, y, rngs, dev)
     p2, x2 = params.clone(), x.clone()
     p2[2] += 0.01
     x2[2] *= -1.5
-    lg2, gr2, _ = _multi(nsd, spec, p2, x2, y, rngs, dev)
+    lg2, gr2, _ = multi_step(nsd, spec, p2, x2, y, rngs, dev)
     for m in range(M):
         if m == 2:
             assert not torch.equal(lg[m], lg2[m])
@@ -123,24 +59,24 @@ def test_models_are_isolated(nsd, dev, M, B):
 
 
 def test_shared_input_equals_replicated(nsd, dev):
-    spec = _spec(nsd)
+    spec = spec_of(D)
     M, B, T = 4, 32, 30
-    params, x, y, rngs = _problem(spec, M, B, T, dev, seed=11)
+    params, x, y, rngs = multi_problem(spec, M, B, T, dev, seed=11)
     shared = x[0].contiguous()
-    lg, gr, ls = _multi(nsd, spec, params, shared, y, rngs, dev)
-    lr, grr, lsr = _multi(nsd, spec, params, shared.unsqueeze(0).expand(M, B, T, spec.C).contiguous(), y, rngs, dev)
+    lg, gr, ls = multi_step(nsd, spec, params, shared, y, rngs, dev)
+    lr, grr, lsr = multi_step(nsd, spec, params, shared.unsqueeze(0).expand(M, B, T, spec.C).contiguous(), y, rngs, dev)
     assert torch.equal(lg, lr) and torch.equal(gr, grr) and torch.equal(ls, lsr)
 
 
 def test_fused_reduce_adam_equals_reduce_then_adam(nsd, dev):
     from nsd_amd import ops
-    spec = _spec(nsd)
+    spec = spec_of(D)
     M, B, T = 6, 32, 20
-    params, x, y, rngs = _problem(spec, M, B, T, dev, seed=3)
+    params, x, y, rngs = multi_problem(spec, M, B, T, dev, seed=3)
     pa, ma, va = params.clone(), torch.rand_like(params) * 1e-3, torch.rand_like(params) * 1e-6
     pb, mb, vb = pa.clone(), ma.clone(), va.clone()
-    _, ga, _ = _multi(nsd, spec, pa, x, y, rngs, dev, fuse_adam=True, m=ma, v=va, step=3)
-    _, gb, _ = _multi(nsd, spec, pb, x, y, rngs, dev, fuse_adam=False)
+    _, ga, _ = multi_step(nsd, spec, pa, x, y, rngs, dev, fuse_adam=True, m=ma, v=va, step=3)
+    _, gb, _ = multi_step(nsd, spec, pb, x, y, rngs, dev, fuse_adam=False)
     ops.adam_step(pb.view(-1), gb.view(-1), mb.view(-1), vb.view(-1), step=3, lr=1e-3)
     assert torch.equal(ga, gb) and torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb)
 
@@ -148,8 +84,8 @@ def test_fused_reduce_adam_equals_reduce_then_adam(nsd, dev):
 @pytest.mark.parametrize("M,B", [(3, 40), (8, 32)])
 def test_multi_infer_equals_infer(nsd, dev, M, B):
     from nsd_amd import ops
-    spec = _spec(nsd)
-    params, x, _, _ = _problem(spec, M, B, 50, dev, seed=5)
+    spec = spec_of(D)
+    params, x, _, _ = multi_problem(spec, M, B, 50, dev, seed=5)
     lg, pr = ops.multi_infer(spec, params, x)
     for m in range(M):
         l1, p1 = ops.infer(spec, params[m].contiguous(), x[m].contiguous())
@@ -223,12 +159,12 @@ def test_model_batch_trainer_matches_sequential_trainers(nsd, dev):
 def test_models_against_the_oracle(nsd, dev):
     """Each model of a (5, 32, 250) model-batched step against the CPU oracle, with the dropout / RReLU masks of rng[m] regenerated
     on the host (as test_thirty_step_training_trajectory_matches_oracle does): the oracle is independent of the shared role code.
-    Bounds of test_gpu_parity.py against the oracle: logits 1e-4, loss 5e-5, gradients those of _grad_ok."""
+    Bounds of tests/gpu_harness.py against the oracle: logits 1e-4, loss 5e-5, gradients those of multi_grad_ok."""
     from oracle import nsd_oracle as orc
-    spec = _spec(nsd)
+    spec = spec_of(D)
     M, B, T = 5, 32, 250
-    params, x, y, rngs = _problem(spec, M, B, T, dev, seed=250)
-    lg, gr, ls = _multi(nsd, spec, params, x, y, rngs, dev)
+    params, x, y, rngs = multi_problem(spec, M, B, T, dev, seed=250)
+    lg, gr, ls = multi_step(nsd, spec, params, x, y, rngs, dev)
     d = orc.Dims()
     for m in range(M):
         r = rngs[m]
@@ -237,9 +173,9 @@ def test_models_against_the_oracle(nsd, dev):
         dh = orc.dropout_mask(r["seed"], r["base_stream"] + 2, 0.6, (B, 32))
         loss_ref, g_ref, fw = orc.loss_and_grads(params[m].cpu().numpy(), x[m].cpu().numpy(), y[m].cpu().numpy(), d, drop_lstm=dl,
                                                  rrelu_slope=sl, drop_head=dh)
-        assert np.abs(lg[m].cpu().numpy() - fw["logits"]).max() < 1e-4, m
-        assert abs(float(ls[m]) - loss_ref) < 5e-5, (m, float(ls[m]), loss_ref)
-        _grad_ok(spec, gr[m].cpu(), torch.from_numpy(np.asarray(g_ref, np.float32)))
+        assert np.abs(lg[m].cpu().numpy() - fw["logits"]).max() < LOGIT_TOL, m
+        assert abs(float(ls[m]) - loss_ref) < LOSS_TOL, (m, float(ls[m]), loss_ref)
+        multi_grad_ok(spec, gr[m].cpu(), torch.from_numpy(np.asarray(g_ref, np.float32)))
 
 
 def test_train_kfold_concurrent_matches_sequential(dev, tmp_path):

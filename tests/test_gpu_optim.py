@@ -29,29 +29,12 @@ import torch
 from tests import buffer_contract as bc
 from tests import optim_ref as ref
 from tests.golden.make_goldens import synth_labels, synth_params, synth_x
-from tests.test_head_dims_cpu import head_inputs
+from tests.gpu_harness import dev, head_inputs, nsd, to_dev  # noqa: F401  (dev, nsd: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-6
 LR = 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()          # raises if libnsd_hip.so is missing: no fallback
-    return nsd_amd
-
-
-def _t(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _same(a: torch.Tensor, b: torch.Tensor) -> bool:
@@ -126,10 +109,10 @@ def _flat_problem(n):
 
 
 def _flat_run(ops, dev, p0, gs, opt, state, skip=None):
-    p, m, v = _t(p0, dev), torch.zeros(len(p0), device=dev), torch.zeros(len(p0), device=dev)
+    p, m, v = to_dev(p0, dev), torch.zeros(len(p0), device=dev), torch.zeros(len(p0), device=dev)
     recs = []
     for s, g in enumerate(gs, 1):
-        gt = _t(g, dev)
+        gt = to_dev(g, dev)
         ops.grad_norm(gt, state, opt.grad_scale)
         ops.adam_step_clip(p, gt, m, v, opt, state, step=s, skip=skip)
         recs.append(_records(ops, state)[0])
@@ -162,9 +145,9 @@ def test_flat_route_unclipped_is_adam_step_bitwise(nsd, dev, n):
     """max_norm = 10 max |g| and max_norm = 0 with a constant schedule: p, m, v bitwise what nsd_adam_step leaves, seven steps"""
     from nsd_amd import ops
     p0, gs, norms = _flat_problem(n)
-    pa, ma, va = _t(p0, dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    pa, ma, va = to_dev(p0, dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
     for s, g in enumerate(gs, 1):
-        ops.adam_step(pa, _t(g, dev), ma, va, step=s, lr=LR, weight_decay=1e-2, grad_scale=0.5)
+        ops.adam_step(pa, to_dev(g, dev), ma, va, step=s, lr=LR, weight_decay=1e-2, grad_scale=0.5)
     for max_norm in (10.0 * max(norms), 0.0):
         opt, state = ops.opt_struct(lr=LR, weight_decay=1e-2, grad_scale=0.5, max_norm=max_norm), ops.opt_state(n, 1, dev)
         p, m, v, recs = _flat_run(ops, dev, p0, gs, opt, state)
@@ -182,7 +165,7 @@ def test_flat_route_honours_skip(nsd, dev):
     p, m, v, _ = _flat_run(ops, dev, p0, gs[:2], opt, state)
     before = (p.clone(), m.clone(), v.clone(), state[:16].clone())
     flag = torch.ones(1, device=dev)
-    gt = _t(gs[2], dev)
+    gt = to_dev(gs[2], dev)
     ops.grad_norm(gt, state)
     ops.adam_step_clip(p, gt, m, v, opt, state, step=3, skip=flag)
     torch.cuda.synchronize()
@@ -204,7 +187,7 @@ def test_flat_route_skips_non_finite_gradients(nsd, dev):
     for k, bad in enumerate((float("inf"), float("nan")), 1):
         g = gs[2].copy()
         g[5] = bad
-        gt = _t(g, dev)
+        gt = to_dev(g, dev)
         ops.grad_norm(gt, state)
         ops.adam_step_clip(p, gt, m, v, opt, state, step=3)
         rec = _records(ops, state)[0]
@@ -212,7 +195,7 @@ def test_flat_route_skips_non_finite_gradients(nsd, dev):
         assert _same(p, before[0]) and _same(m, before[1]) and _same(v, before[2])
         assert rec["skipped"] == k and (math.isinf(rec["norm"]) if k == 1 else math.isnan(rec["norm"])) and rec["coef"] == 0.0
     pa, ma, va = (t.clone() for t in before)
-    gt = _t(gs[2], dev)
+    gt = to_dev(gs[2], dev)
     ops.adam_step(pa, gt, ma, va, step=3, lr=LR)
     ops.grad_norm(gt, state)
     ops.adam_step_clip(p, gt, m, v, opt, state, step=3)
@@ -234,9 +217,9 @@ def _evaluation(ops, dev, Cc, H, L, K, F, B, T):
     """a real forward + backward: the workspace holds the slabs, grads is nsd_grad_reduce's"""
     _, flat, x, y, _ = head_inputs(Cc, H, K, F, B, T, L=L)
     spec = ops.ModelSpec(C=Cc, H=H, L=L, K=K, F=F)
-    flat_t, ws = _t(flat, dev), ops.new_workspace(spec, B, T, dev)
+    flat_t, ws = to_dev(flat, dev), ops.new_workspace(spec, B, T, dev)
     logits, grads = torch.empty((B, K), device=dev), torch.full((spec.param_count,), float("nan"), device=dev)
-    ops.train_step_grads(spec, flat_t, _t(x, dev), ws, _t(y, dev), logits, grads)
+    ops.train_step_grads(spec, flat_t, to_dev(x, dev), ws, to_dev(y, dev), logits, grads)
     return spec, flat_t, ws, grads
 
 
@@ -255,7 +238,7 @@ def test_fused_tail(nsd, dev, shape):
     state = ops.opt_state(P, 1, dev)
 
     def run(tail, **kw):
-        p, m, v, g = _t(p0, dev), _t(m0, dev), _t(v0, dev), torch.full((P,), float("nan"), device=dev)
+        p, m, v, g = to_dev(p0, dev), to_dev(m0, dev), to_dev(v0, dev), torch.full((P,), float("nan"), device=dev)
         tail(ops, spec, B, T, ws, g, p, m, v, **kw)
         return p, m, v, g
     # clipped, weight decay on, step 3 of a run in progress
@@ -289,10 +272,10 @@ def batched(nsd, dev):
     P = spec.param_count
     from oracle import nsd_oracle as orc
     d = orc.Dims()
-    params = torch.stack([_t(orc.flatten_state(synth_params(8, 48, 2, 3, seed=70 + i), d), dev) for i in range(MB)]).contiguous()
+    params = torch.stack([to_dev(orc.flatten_state(synth_params(8, 48, 2, 3, seed=70 + i), d), dev) for i in range(MB)]).contiguous()
     x0 = synth_x(BB, TB, seed=5)
-    x = torch.stack([_t(x0 * np.float32(s), dev) for s in (1.0, 30.0, 1e-3)]).contiguous()
-    y = _t(np.tile(synth_labels(BB, seed=5), MB), dev)
+    x = torch.stack([to_dev(x0 * np.float32(s), dev) for s in (1.0, 30.0, 1e-3)]).contiguous()
+    y = to_dev(np.tile(synth_labels(BB, seed=5), MB), dev)
     ws = ops.multi_workspace(spec, MB, BB, TB, dev)
     grads = torch.empty((MB, P), device=dev)
     ops.multi_train_step(spec, params, x, y, ws, grads, fuse_adam=False)
@@ -326,7 +309,7 @@ def test_model_batched_tail_is_the_single_model_tail_per_model(nsd, dev, batched
     max_norm = math.sqrt(sorted(norms)[1] * sorted(norms)[2])        # between the two largest norms: one model clips, two do not
     opt = ops.opt_struct(lr=LR, weight_decay=1e-2, max_norm=max_norm)
     m0, v0 = _moments(MB * P, seed=3)
-    p, m, v = params.clone(), _t(m0, dev).view(MB, P).clone(), _t(v0, dev).view(MB, P).clone()
+    p, m, v = params.clone(), to_dev(m0, dev).view(MB, P).clone(), to_dev(v0, dev).view(MB, P).clone()
     g, state = torch.full((MB, P), float("nan"), device=dev), ops.opt_state(P, MB, dev)
     _multi_tail_clip(ops, spec, MB, BB, TB, ws, g, p, m, v, opt, state, step=3)
     recs = _records(ops, state, MB)
@@ -337,7 +320,7 @@ def test_model_batched_tail_is_the_single_model_tail_per_model(nsd, dev, batched
     for i in range(MB):
         assert _ulps(recs[i]["norm"], norms[i]) <= 1 and clipped[i] == (norms[i] > max_norm)
         w1, s1 = _single_ws_of_model(ops, dev, batched, i), ops.opt_state(P, 1, dev)
-        p1, m1, v1 = params[i].clone(), _t(m0, dev).view(MB, P)[i].clone(), _t(v0, dev).view(MB, P)[i].clone()
+        p1, m1, v1 = params[i].clone(), to_dev(m0, dev).view(MB, P)[i].clone(), to_dev(v0, dev).view(MB, P)[i].clone()
         g1 = torch.full((P,), float("nan"), device=dev)
         _tail_clip(ops, spec, BB, TB, w1, g1, p1, m1, v1, opt, s1, step=3)
         r1 = _records(ops, s1)[0]
@@ -393,12 +376,12 @@ def test_schedule_from_the_device_step_counter(nsd, dev, kind):
     sched = nsd.LrSchedule(kind, warmup_steps=W_S, total_steps=W_S + NP_S, min_ratio=0.1, step_size=2, gamma=0.5)
     opt = ops.opt_struct(lr=LR, max_norm=0.5 * norms[0], schedule=sched)
     m0, v0 = _moments(n, seed=1)
-    gt, state, step_dev = _t(gs[0], dev), ops.opt_state(n, 1, dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    gt, state, step_dev = to_dev(gs[0], dev), ops.opt_state(n, 1, dev), torch.zeros(1, dtype=torch.int64, device=dev)
     lrs = []
     for s in (1, W_S, W_S + 1, NP_S, NP_S + 5):
         out = []
         for on_device in (False, True):
-            p, m, v = _t(p0, dev), _t(m0, dev), _t(v0, dev)
+            p, m, v = to_dev(p0, dev), to_dev(m0, dev), to_dev(v0, dev)
             step_dev.fill_(s)
             ops.grad_norm(gt, state)
             ops.adam_step_clip(p, gt, m, v, opt, state, step=0 if on_device else s, step_dev=step_dev if on_device else None)
@@ -424,7 +407,7 @@ def _ref_model(nsd, dev, ref_state, **kw):
 
 
 def _xy(dev, seed=8):
-    return _t(synth_x(BT, TT, seed=seed), dev), _t(synth_labels(BT, seed=seed), dev)
+    return to_dev(synth_x(BT, TT, seed=seed), dev), to_dev(synth_labels(BT, seed=seed), dev)
 
 
 COSINE = dict(kind="cosine", warmup_steps=2, total_steps=10, min_ratio=0.1)
@@ -541,7 +524,7 @@ def test_bf16_path_takes_the_flat_route_and_keeps_its_guard(nsd, dev):
     torch.manual_seed(11)
     model = nsd.EEG_LSTM(8, 64, 2, 5, dropout=0.6, precision="bf16").to(dev).train()
     tr = Trainer(model, lr=LR, seed=3, clip_grad_norm=0.05)
-    x, y = _t(synth_x(32, 5, seed=4), dev), _t(synth_labels(32, 5, seed=4), dev)
+    x, y = to_dev(synth_x(32, 5, seed=4), dev), to_dev(synth_labels(32, 5, seed=4), dev)
     names = _launches(lambda: tr.step(x, y), steps=2)
     assert names[-2:] == ["nsd_grad_norm", "nsd_adam_step_clip"] and "nsd_adam_step_guarded" not in names
     want = ref.grad_norm(tr.grads.cpu().numpy())[1]
@@ -670,7 +653,7 @@ def test_buffer_contract_flat_route(nsd, dev):
     from nsd_amd import ops
     for n in (31764, 2**20 + 1):
         p0, gs, norms = _flat_problem(n)
-        g, p, m, v = _t(gs[0], dev), _t(p0, dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        g, p, m, v = to_dev(gs[0], dev), to_dev(p0, dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
         opt = ops.opt_struct(lr=LR, max_norm=0.1 * norms[0])
 
         def launch(state, p, m, v):

@@ -3,7 +3,8 @@ from the reference.  Needs a real MI355X: run with `pytest -m gpu`.
 
 Tolerances: class logits within 1e-4 (north_star), argmax identical; gradients within 2e-4 of the
 largest entry of each tensor (the oneDNN reference and an independent fp32 restatement agree to ~2e-6
-relative); integer / mask streams bit-exact.
+relative); integer / mask streams bit-exact.  The bounds with their derivations, the gradient comparator and the
+driver of ops.train_step_grads are in tests/gpu_harness.py.
 """
 import contextlib
 import os
@@ -14,85 +15,18 @@ import torch
 
 from oracle import nsd_oracle as orc
 from tests.golden.make_goldens import SYNTH_SHAPES, counter_masks, synth_labels, synth_params, synth_x
+from tests.gpu_harness import (DX_TOL, FAST48, FP32_EXACT, GRAD_RTOL_12, GRAD_RTOL_SATURATED, GRAD_RTOL_X4, HEAD_SAVES, LOGIT_TOL, LOSS_TOL, D,
+                               dev, forward_backward, grad_close, model_from_state, nsd, spec_of, to_dev, train_step, write_pth)  # noqa: F401  (dev, nsd: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-LOGIT_TOL = 1e-4
-D = orc.Dims()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()          # raises if libnsd_hip.so is missing: no fallback
-    return nsd_amd
-
-
-def _model(nsd, dev, state, **kw):
-    H = state["lstm.weight_hh_l0"].shape[1]
-    L = sum(1 for k in state if k.startswith("lstm.weight_hh_l"))
-    m = nsd.EEG_LSTM(input_size=state["lstm.weight_ih_l0"].shape[1], hidden_size=H, num_layers=L,
-                     num_classes=state["fc.3.weight"].shape[0], **kw)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state.items()}, strict=True)
-    return m.to(dev)
-
-
-def _t(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-# Bounds of the H = 48, C = 8, K = 3 fast path (the benchmarked kernels) against the oracle and the reference goldens: the LSTM weight
-# gradients (split-bf16 sums over time, nsd_lstm2_bwd48*.hip) within 5e-5 of each tensor's largest element, every other tensor within
-# 2e-5, dL/dx within 2e-5 (the 1e-7 floor and attn.bias's 2e-6 as before).  Measured over the whole suite on the MI355X (178 comparisons,
-# _grad_close's "grad_close worst" line): LSTM weight gradients <= 2.5e-5, dL/dx <= 2.4e-6, the other tensors <= 1.7e-5 wherever the
-# 1e-7 floor is not what holds them (tensors with a largest element below ~5e-3 at T <= 2).  Dropping one of the three split-bf16 MFMAs
-# of either backward kernel fails dozens of these comparisons.
-FAST48 = dict(rtol=2e-5, wtol=5e-5)
-DX_TOL = 2e-5
-# Bounds of the exact-fp32 routes -- no reduced-precision products: the first-generation H = 32 / 64 kernels of nsd_lstm2.hip, the generic
-# path and the batched MFMA path -- against the oracle, of each tensor's largest element: the LSTM weight gradients within 1e-5, every
-# other tensor within 2e-5 (the 1e-7 floor and attn.bias's 2e-6 as before).  About eight times the worst value measured over
-# tests/test_gpu_fp32_routes.py on one MI355X (1.25e-6: weight_ih_l0 of the generic path at 2051 trials; 2.25e-6: attn.weight at T = 2,
-# and fc.3.bias at K = 2, where the sum over the batch nearly cancels): the room FAST48 has.  Neither exceeds FAST48's.  The comparisons
-# of these routes below measure <= 7.5e-7 / 4.8e-6 (their "grad_close worst" lines).
-FP32_EXACT = dict(rtol=2e-5, wtol=1e-5)
-
-
-def _grad_close(got_flat, ref_flat, d, rtol=2e-4, wtol=None):
-    """Every gradient tensor within rtol of its largest element (+1e-7); the LSTM weight gradients within wtol where given;
-    attn.bias within 2e-6 absolute.  Prints the worst ratio per tensor class (error / largest element; attn.bias: the error)."""
-    got, ref = orc.unflatten(got_flat, d), orc.unflatten(ref_flat, d)
-    worst, bad = {"lstm.weight": 0.0, "other": 0.0, "attn.bias": 0.0}, []
-    for k in orc.param_names(d):
-        err = float(np.abs(got[k] - ref[k]).max())
-        if k == "attn.bias":
-            worst[k] = max(worst[k], err)
-            if not err < 2e-6:
-                bad.append((k, err))
-            continue
-        scale = max(float(np.abs(ref[k]).max()), 1e-6)
-        cls = "lstm.weight" if k.startswith("lstm.weight") else "other"
-        worst[cls] = max(worst[cls], err / scale)
-        tol = wtol if (wtol is not None and cls == "lstm.weight") else rtol
-        if not err <= tol * scale + 1e-7:
-            bad.append((k, err, scale))
-    print("grad_close worst", {k: f"{v:.2e}" for k, v in worst.items()}, "bounds", (rtol, wtol))
-    assert not bad, bad
-
 
 # ---------------------------------------------------------------------------------------------------
 # inference
 # ---------------------------------------------------------------------------------------------------
 def test_real_trials_match_reference(nsd, dev, golden, ref_state):
     g = golden("real_trials")
-    m = _model(nsd, dev, ref_state).eval()
-    x = _t(g["x"], dev)
+    m = model_from_state(nsd, dev, ref_state).eval()
+    x = to_dev(g["x"], dev)
     with torch.no_grad():
         lg = m(x).cpu().numpy()
         pr = m.predict_proba(x).cpu().numpy()
@@ -107,15 +41,15 @@ def test_real_trials_match_reference(nsd, dev, golden, ref_state):
 @pytest.mark.parametrize("B,T", SYNTH_SHAPES)
 def test_synthetic_shapes_match_reference(nsd, dev, golden, ref_state, B, T):
     ref = golden("synthetic")[f"logits_{B}x{T}"]
-    m = _model(nsd, dev, ref_state).eval()
+    m = model_from_state(nsd, dev, ref_state).eval()
     with torch.no_grad():
-        lg = m(_t(synth_x(B, T), dev)).cpu().numpy()
+        lg = m(to_dev(synth_x(B, T), dev)).cpu().numpy()
     assert np.abs(lg - ref).max() < LOGIT_TOL
     assert np.array_equal(lg.argmax(-1), ref.argmax(-1))
 
 
 def test_empty_batch_and_bad_shapes(nsd, dev, ref_state):
-    m = _model(nsd, dev, ref_state).eval()
+    m = model_from_state(nsd, dev, ref_state).eval()
     with torch.no_grad():
         assert tuple(m(torch.zeros(0, 50, 8, device=dev)).shape) == (0, 3)
     with pytest.raises(ValueError):
@@ -128,8 +62,8 @@ def test_empty_batch_and_bad_shapes(nsd, dev, ref_state):
 
 def test_noncontiguous_input_like_predict(nsd, dev, ref_state, golden):
     g = golden("real_trials")
-    m = _model(nsd, dev, ref_state).eval()
-    xt = _t(np.ascontiguousarray(g["x"][:3].transpose(0, 2, 1)), dev).transpose(1, 2)   # [B,T,C] view of [B,C,T]
+    m = model_from_state(nsd, dev, ref_state).eval()
+    xt = to_dev(np.ascontiguousarray(g["x"][:3].transpose(0, 2, 1)), dev).transpose(1, 2)   # [B,T,C] view of [B,C,T]
     assert not xt.is_contiguous()
     with torch.no_grad():
         lg = m(xt).cpu().numpy()
@@ -147,10 +81,10 @@ def test_train_forward_intermediates(nsd, dev, ref_state, B, T, masked):
     dl, sl, dh = counter_masks(B, T, 48, 32, seed=B * 100 + T) if masked else (None, None, None)
     ref = orc.forward(flat_np, x, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh, saves=True)
     spec = ops.ModelSpec()
-    flat, xt = _t(flat_np, dev), _t(x, dev)
+    flat, xt = to_dev(flat_np, dev), to_dev(x, dev)
     ws = ops.new_workspace(spec, B, T, dev)
-    logits, probs = ops.train_forward(spec, flat, xt, ws, drop_lstm=_t(dl, dev), rrelu_slope=_t(sl, dev),
-                                      drop_head=_t(dh, dev), want_probs=True)
+    logits, probs = ops.train_forward(spec, flat, xt, ws, drop_lstm=to_dev(dl, dev), rrelu_slope=to_dev(sl, dev),
+                                      drop_head=to_dev(dh, dev), want_probs=True)
     v = lambda r: ops.ws_view(ws, spec, B, T, r).cpu().numpy()
     assert np.abs(v("hseq") - ref["hseq"]).max() < 2e-5
     assert np.abs(v("cseq") - ref["cseq"]).max() < 5e-5
@@ -168,43 +102,6 @@ def test_train_forward_intermediates(nsd, dev, ref_state, B, T, masked):
 # ---------------------------------------------------------------------------------------------------
 # gradients
 # ---------------------------------------------------------------------------------------------------
-def _hip_loss_grads(nsd, dev, flat_np, x, y, spec=None, scale=None, **masks):
-    from nsd_amd import ops
-    spec = spec or ops.ModelSpec()
-    B, T, _ = x.shape
-    flat, xt = _t(flat_np, dev), _t(x, dev)
-    ws = ops.new_workspace(spec, B, T, dev)
-    mk = {k: _t(v, dev) for k, v in masks.items() if k != "residual"}
-    res = masks.get("residual", False)
-    logits, _ = ops.train_forward(spec, flat, xt, ws, residual=res, **mk)
-    g = ops.train_backward(spec, flat, xt, ws, logits, labels=_t(y.astype(np.int32), dev), scale=scale, residual=res, **mk)
-    loss = float(ops.loss_sum(spec, ws, B, T).item()) / B
-    return loss, g.cpu().numpy(), logits.cpu().numpy()
-
-
-def _hip_step(nsd, dev, flat_np, x, y, fused_head, residual=False, want_dx=False, **masks):
-    """ops.train_step_grads (the launch sequence of Trainer.step) -> loss, grads, logits and the head's workspace outputs
-    (+ dL/dx from the same backward call with want_dx)."""
-    from nsd_amd import ops
-    spec = ops.ModelSpec()
-    B, T, _ = x.shape
-    flat, xt = _t(flat_np, dev), _t(x, dev)
-    ws = ops.new_workspace(spec, B, T, dev)
-    ws.fill_(float("nan"))                                   # nothing may be left unwritten
-    logits = torch.full((B, spec.K), float("nan"), device=dev)
-    grads = torch.empty_like(flat)
-    dx = torch.full_like(xt, float("nan")) if want_dx else None
-    mk = {k: _t(v, dev) for k, v in masks.items()}
-    ops.train_step_grads(spec, flat, xt, ws, _t(y.astype(np.int32), dev), logits, grads, residual=residual, fused_head=fused_head,
-                         dx=dx, **mk)
-    out = {r: ops.ws_view(ws, spec, B, T, r).cpu().numpy().copy() for r in ("alpha", "pooled", "fc0_pre", "dscore", "dpooled", "loss")}
-    out["logits"] = logits.cpu().numpy()
-    out["grads"] = grads.cpu().numpy()
-    if want_dx:
-        out["dx"] = dx.cpu().numpy()
-    return out
-
-
 @pytest.mark.parametrize("B,T,residual", [(1, 1, False), (3, 2, False), (32, 250, False), (7, 625, False), (300, 33, False),
                                           (13, 64, True), (2, 1024, False)])
 def test_single_launch_lstm_plus_head_train(nsd, dev, ref_state, B, T, residual):
@@ -214,19 +111,19 @@ def test_single_launch_lstm_plus_head_train(nsd, dev, ref_state, B, T, residual)
     x, y = synth_x(B, T, seed=3 * B + T), synth_labels(B, seed=B + 2 * T)
     dl, sl, dh = counter_masks(B, T, 48, 32, seed=11 * B + T)
     masks = dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    a = _hip_step(nsd, dev, flat_np, x, y, True, residual=residual, **masks)
-    b = _hip_step(nsd, dev, flat_np, x, y, False, residual=residual, **masks)
+    a = train_step(dev, spec_of(D), flat_np, x, labels=y, residual=residual, masks=masks, saves=HEAD_SAVES)
+    b = train_step(dev, spec_of(D), flat_np, x, labels=y, fused=False, residual=residual, masks=masks, saves=HEAD_SAVES)
     for k in ("logits", "alpha", "pooled", "fc0_pre", "loss"):
         assert np.isfinite(a[k]).all(), k
         assert np.abs(a[k] - b[k]).max() <= 2e-5 * max(1.0, np.abs(b[k]).max()), k
     for k in ("dscore", "dpooled"):
         assert np.abs(a[k] - b[k]).max() <= 1e-4 * np.abs(b[k]).max() + 1e-9, k
-    _grad_close(a["grads"], b["grads"], D, rtol=2e-4)
+    grad_close(a["grads"], b["grads"], D, rtol=GRAD_RTOL_12)
     if not residual and B * T <= 8000:
         loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, D, **masks)
         assert np.abs(a["logits"] - fw["logits"]).max() < LOGIT_TOL
-        assert abs(float(a["loss"].sum()) / B - loss_ref) < 5e-5
-        _grad_close(a["grads"], g_ref, D, **FAST48)
+        assert abs(a["mean_loss"] - loss_ref) < LOSS_TOL
+        grad_close(a["grads"], g_ref, D, **FAST48)
 
 
 def test_randomised_shapes_train_step_and_inference_vs_oracle(nsd, dev, ref_state):
@@ -234,18 +131,18 @@ def test_randomised_shapes_train_step_and_inference_vs_oracle(nsd, dev, ref_stat
     oracle (ragged batches, T not a multiple of any chunk size, T = 1..70)."""
     rng = np.random.default_rng(20261003)
     flat_np = orc.flatten_state(ref_state, D)
-    m = _model(nsd, dev, ref_state).eval()
+    m = model_from_state(nsd, dev, ref_state).eval()
     for _ in range(12):
         B, T = int(rng.integers(1, 41)), int(rng.integers(1, 71))
         x, y = synth_x(B, T, seed=int(rng.integers(1 << 30))), synth_labels(B, seed=int(rng.integers(1 << 30)))
         dl, sl, dh = counter_masks(B, T, 48, 32, seed=int(rng.integers(1 << 30)))
         loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-        a = _hip_step(nsd, dev, flat_np, x, y, True, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
+        a = train_step(dev, spec_of(D), flat_np, x, labels=y, masks=dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh))
         assert np.abs(a["logits"] - fw["logits"]).max() < LOGIT_TOL, (B, T)
-        assert abs(float(a["loss"].sum()) / B - loss_ref) < 5e-5, (B, T)
-        _grad_close(a["grads"], g_ref, D, **FAST48)
+        assert abs(a["mean_loss"] - loss_ref) < LOSS_TOL, (B, T)
+        grad_close(a["grads"], g_ref, D, **FAST48)
         with torch.no_grad():
-            lg = m(_t(x, dev)).cpu().numpy()
+            lg = m(to_dev(x, dev)).cpu().numpy()
         ref = orc.forward(flat_np, x, D)["logits"]
         assert np.abs(lg - ref).max() < LOGIT_TOL and np.array_equal(lg.argmax(1), ref.argmax(1)), (B, T)
 
@@ -258,12 +155,12 @@ def test_fused_path_boundaries(nsd, dev, ref_state, B, T):
     x, y = synth_x(B, T, seed=B + T), synth_labels(B, seed=B)
     dl, sl, dh = counter_masks(B, T, 48, 32, seed=B * T)
     masks = dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    a = _hip_step(nsd, dev, flat_np, x, y, True, **masks)
-    b = _hip_step(nsd, dev, flat_np, x, y, False, **masks)
+    a = train_step(dev, spec_of(D), flat_np, x, labels=y, masks=masks, saves=HEAD_SAVES)
+    b = train_step(dev, spec_of(D), flat_np, x, labels=y, fused=False, masks=masks, saves=HEAD_SAVES)
     for k in ("logits", "alpha", "pooled", "loss"):
         assert np.isfinite(a[k]).all(), k
         assert np.abs(a[k] - b[k]).max() <= 2e-5 * max(1.0, np.abs(b[k]).max()), k
-    _grad_close(a["grads"], b["grads"], D, rtol=2e-4)
+    grad_close(a["grads"], b["grads"], D, rtol=GRAD_RTOL_12)
 
 
 @pytest.mark.parametrize("scale", [1e-6, 50.0, 3000.0])
@@ -274,29 +171,29 @@ def test_tiny_and_saturating_inputs(nsd, dev, ref_state, scale):
     B, T = 9, 60
     x = (synth_x(B, T, seed=77) * scale / 2.7).astype(np.float32)
     y = synth_labels(B, seed=77)
-    m = _model(nsd, dev, ref_state).eval()
+    m = model_from_state(nsd, dev, ref_state).eval()
     with torch.no_grad():
-        lg = m(_t(x, dev)).cpu().numpy()
+        lg = m(to_dev(x, dev)).cpu().numpy()
     ref = orc.forward(flat_np, x, D)["logits"]
     assert np.isfinite(lg).all()
     assert np.abs(lg - ref).max() < LOGIT_TOL * max(1.0, np.abs(ref).max() / 10.0)
-    a = _hip_step(nsd, dev, flat_np, x, y, True)
+    a = train_step(dev, spec_of(D), flat_np, x, labels=y)
     loss_ref, g_ref, _ = orc.loss_and_grads(flat_np, x, y, D)
-    assert np.isfinite(a["grads"]).all() and abs(float(a["loss"].sum()) / B - loss_ref) < 1e-4 * max(1.0, abs(loss_ref))
-    _grad_close(a["grads"], g_ref, D, rtol=5e-4)
+    assert np.isfinite(a["grads"]).all() and abs(a["mean_loss"] - loss_ref) < 1e-4 * max(1.0, abs(loss_ref))
+    grad_close(a["grads"], g_ref, D, rtol=GRAD_RTOL_SATURATED)
 
 
 def test_gradients_vs_reference_goldens(nsd, dev, golden, ref_state):
     g = golden("grads_32x250")
     flat_np = orc.flatten_state(ref_state, D)
     x, y = synth_x(32, 250), synth_labels(32)
-    loss, grads, _ = _hip_loss_grads(nsd, dev, flat_np, x, y)
+    loss, grads, _ = forward_backward(dev, flat_np, x, y)
     assert abs(loss - float(g["eval.loss"])) < 2e-5
-    _grad_close(grads, orc.flatten_state({k: g["eval." + k] for k in orc.param_names(D)}, D), D, **FAST48)
+    grad_close(grads, orc.flatten_state({k: g["eval." + k] for k in orc.param_names(D)}, D), D, **FAST48)
     dl, sl, dh = counter_masks(32, 250, 48, 32)
-    loss, grads, _ = _hip_loss_grads(nsd, dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    assert abs(loss - float(g["masked.loss"])) < 5e-5
-    _grad_close(grads, orc.flatten_state({k: g["masked." + k] for k in orc.param_names(D)}, D), D, **FAST48)
+    loss, grads, _ = forward_backward(dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
+    assert abs(loss - float(g["masked.loss"])) < LOSS_TOL
+    grad_close(grads, orc.flatten_state({k: g["masked." + k] for k in orc.param_names(D)}, D), D, **FAST48)
 
 
 @pytest.mark.parametrize("B,T", [(1, 1), (2, 3), (9, 64), (5, 33), (300, 20), (301, 6), (700, 9), (1027, 5)])
@@ -306,22 +203,22 @@ def test_gradients_vs_oracle_ragged_shapes(nsd, dev, ref_state, B, T):
     x, y = synth_x(B, T, seed=B + T), synth_labels(B, seed=B + T)
     dl, sl, dh = counter_masks(B, T, 48, 32, seed=7 * B + T)
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL
-    assert abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, D, **FAST48)
+    assert abs(loss - loss_ref) < LOSS_TOL
+    grad_close(grads, g_ref, D, **FAST48)
 
 
 def test_residual_extension(nsd, dev, golden):
     e = golden("extensions")
     flat_np = orc.flatten_state(synth_params(8, 48, 2, 3, seed=7), D)
     x, y = synth_x(5, 40, seed=5), synth_labels(5, seed=5)
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, residual=True)
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, residual=True)
     assert np.abs(logits - e["residual.logits"]).max() < 2e-5
-    _grad_close(grads, orc.flatten_state({k: e["residual.grad." + k] for k in orc.param_names(D)}, D), D, rtol=2e-4)
-    m = _model(nsd, dev, synth_params(8, 48, 2, 3, seed=7), residual=True).eval()
+    grad_close(grads, orc.flatten_state({k: e["residual.grad." + k] for k in orc.param_names(D)}, D), D, rtol=GRAD_RTOL_12)
+    m = model_from_state(nsd, dev, synth_params(8, 48, 2, 3, seed=7), residual=True).eval()
     with torch.no_grad():
-        assert np.abs(m(_t(x, dev)).cpu().numpy() - e["residual.logits"]).max() < 2e-5
+        assert np.abs(m(to_dev(x, dev)).cpu().numpy() - e["residual.logits"]).max() < 2e-5
 
 
 @pytest.mark.parametrize("H,C,K", [(32, 8, 3), (64, 8, 5), (48, 5, 4), (48, 1, 2)])
@@ -335,9 +232,9 @@ def test_other_fast_path_shapes_vs_oracle(nsd, dev, H, C, K):
     x, y = synth_x(B, T, C=C, seed=H), synth_labels(B, K=K, seed=H)
     dl, sl, dh = counter_masks(B, T, H, 32, seed=H)
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, d, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, **(FAST48 if H == 48 else FP32_EXACT))       # H = 48: the split-bf16 kernels at C < 8
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, spec=spec, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
+    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+    grad_close(grads, g_ref, d, **(FAST48 if H == 48 else FP32_EXACT))       # H = 48: the split-bf16 kernels at C < 8
 
 
 def test_generic_path_cfg3_shape_vs_reference_goldens(nsd, dev, golden):
@@ -352,29 +249,29 @@ def test_generic_path_cfg3_shape_vs_reference_goldens(nsd, dev, golden):
     st3 = synth_params(8, 256, 2, 5, seed=11)
     flat_np = orc.flatten_state(st3, d3)
     x, y = synth_x(4, 250, seed=3), synth_labels(4, K=5, seed=3)
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec)
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, spec=spec)
     assert np.abs(logits - e["cfg3.logits"]).max() < LOGIT_TOL
     got = orc.unflatten(grads, d3)
     for k in orc.param_names(d3):
         if "cfg3.grad." + k in e.files:
             r = e["cfg3.grad." + k]
-            tol = 2e-6 if k == "attn.bias" else 3e-4 * max(np.abs(r).max(), 1e-6) + 1e-7
+            tol = 2e-6 if k == "attn.bias" else GRAD_RTOL_X4 * max(np.abs(r).max(), 1e-6) + 1e-7
             assert np.abs(got[k] - r).max() <= tol, k
         else:
             r = e["cfg3.gradsample." + k]
-            assert np.abs(got[k].ravel()[::CFG3_STRIDE] - r).max() <= 3e-4 * np.abs(r).max() + 1e-7, k
-    m = _model(nsd, dev, st3).eval()                       # module surface on the generic path
+            assert np.abs(got[k].ravel()[::CFG3_STRIDE] - r).max() <= GRAD_RTOL_X4 * np.abs(r).max() + 1e-7, k
+    m = model_from_state(nsd, dev, st3).eval()                       # module surface on the generic path
     with torch.no_grad():
-        assert np.abs(m(_t(x, dev)).cpu().numpy() - e["cfg3.logits"]).max() < LOGIT_TOL
+        assert np.abs(m(to_dev(x, dev)).cpu().numpy() - e["cfg3.logits"]).max() < LOGIT_TOL
 
 
 @pytest.mark.parametrize("L", [1, 3])
 def test_generic_path_layer_counts_vs_reference_goldens(nsd, dev, golden, L):
     e = golden("extensions")
     st = synth_params(8, 48, L, 3, seed=20 + L)
-    m = _model(nsd, dev, st).eval()
+    m = model_from_state(nsd, dev, st).eval()
     with torch.no_grad():
-        lg = m(_t(synth_x(3, 50, seed=30 + L), dev)).cpu().numpy()
+        lg = m(to_dev(synth_x(3, 50, seed=30 + L), dev)).cpu().numpy()
     assert np.abs(lg - e[f"L{L}.logits"]).max() < 2e-5
 
 
@@ -394,9 +291,9 @@ def test_generic_path_gradients_vs_oracle(nsd, dev, C, H, L, K, residual):
     kw = dict(rrelu_slope=sl, drop_head=dh, residual=residual)
     if dl is not None:
         kw["drop_lstm"] = dl
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, **kw)
-    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, **FP32_EXACT)
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, spec=spec, **kw)
+    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+    grad_close(grads, g_ref, d, **FP32_EXACT)
 
 
 @pytest.mark.parametrize("C,H,L,K,residual,B,T", [(8, 256, 2, 5, False, 20, 21), (8, 112, 2, 3, False, 70, 9), (64, 128, 2, 5, False, 33, 12),
@@ -418,12 +315,12 @@ def test_batched_mfma_path_vs_oracle(nsd, dev, C, H, L, K, residual, B, T):
     kw = dict(rrelu_slope=sl, drop_head=dh, residual=residual)
     if dl is not None:
         kw["drop_lstm"] = dl
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, **kw)
-    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, **FP32_EXACT)
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, spec=spec, **kw)
+    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+    grad_close(grads, g_ref, d, **FP32_EXACT)
     # inference on the same kernels (cell state carried in a [B,H] ping-pong instead of the saved sequences)
-    flat = _t(flat_np, dev)
-    lg, pr = ops.infer(spec, flat, _t(x, dev), residual=residual)
+    flat = to_dev(flat_np, dev)
+    lg, pr = ops.infer(spec, flat, to_dev(x, dev), residual=residual)
     ref = orc.forward(flat_np, x, d, residual=residual)
     assert np.abs(lg.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     assert np.array_equal(lg.argmax(1).cpu().numpy(), ref["logits"].argmax(1))
@@ -442,8 +339,8 @@ def test_batched_path_bf16_operands(nsd, dev, C, H, L, K, B, T):
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, d)
     ops.set_gemm_bf16(True)
     try:
-        loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec)
-        lg, _ = ops.infer(spec, _t(flat_np, dev), _t(x, dev))
+        loss, grads, logits = forward_backward(dev, flat_np, x, y, spec=spec)
+        lg, _ = ops.infer(spec, to_dev(flat_np, dev), to_dev(x, dev))
     finally:
         ops.set_gemm_bf16(False)
     err = np.abs(logits - fw["logits"]).max()
@@ -453,7 +350,7 @@ def test_batched_path_bf16_operands(nsd, dev, C, H, L, K, B, T):
     got, ref = orc.unflatten(grads, d), orc.unflatten(g_ref, d)
     for k in orc.param_names(d):
         assert np.abs(got[k] - ref[k]).max() <= 5e-2 * max(np.abs(ref[k]).max(), 1e-6) + 1e-6, k
-    loss2, grads2, logits2 = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec)
+    loss2, grads2, logits2 = forward_backward(dev, flat_np, x, y, spec=spec)
     assert np.abs(logits2 - fw["logits"]).max() < LOGIT_TOL
 
 
@@ -467,10 +364,10 @@ def test_full_size_properties(nsd, dev, ref_state):
     trials permutes the logits and leaves the summed gradient unchanged to rounding."""
     from nsd_amd import ops
     spec = ops.ModelSpec()
-    flat = _t(orc.flatten_state(ref_state, D), dev)
+    flat = to_dev(orc.flatten_state(ref_state, D), dev)
     B, T = 1024, 250
-    x, y = _t(synth_x(B, T, seed=77), dev), _t(synth_labels(B, seed=77), dev)
-    m = _model(nsd, dev, ref_state).eval()
+    x, y = to_dev(synth_x(B, T, seed=77), dev), to_dev(synth_labels(B, seed=77), dev)
+    m = model_from_state(nsd, dev, ref_state).eval()
     with torch.no_grad():
         big = m(x)
         assert torch.equal(big[:256], m(x[:256])) and torch.equal(big[256:768], m(x[256:768]))
@@ -498,12 +395,12 @@ def test_full_size_properties(nsd, dev, ref_state):
 def test_zscore(nsd, dev, golden):
     from nsd_amd import ops
     z = golden("zscore")
-    got = ops.zscore(_t(z["chunk"], dev)).cpu().numpy()
+    got = ops.zscore(to_dev(z["chunk"], dev)).cpu().numpy()
     assert np.abs(got - z["normalized"]).max() < 2e-5
     x = synth_x(9, 77, C=5, seed=2)
-    assert np.abs(ops.zscore(_t(x, dev)).cpu().numpy() - orc.zscore(x)).max() < 2e-5
+    assert np.abs(ops.zscore(to_dev(x, dev)).cpu().numpy() - orc.zscore(x)).max() < 2e-5
     const = np.ones((2, 10, 8), np.float32)            # zero variance: eps keeps it finite
-    assert np.array_equal(ops.zscore(_t(const, dev)).cpu().numpy(), np.zeros_like(const))
+    assert np.array_equal(ops.zscore(to_dev(const, dev)).cpu().numpy(), np.zeros_like(const))
 
 
 def test_counter_streams_bit_exact(nsd, dev):
@@ -530,19 +427,19 @@ def test_fused_train_masks_bit_exact(nsd, dev):
 def test_trainer_step_matches_oracle_with_its_own_streams(nsd, dev, ref_state):
     """One fused Trainer.step == oracle forward/backward with the same counter-based masks + oracle Adam."""
     from nsd_amd.trainer import Trainer
-    m = _model(nsd, dev, ref_state).train()
+    m = model_from_state(nsd, dev, ref_state).train()
     tr = Trainer(m, lr=1e-3, seed=7)
     B, T = 12, 40
     x, y = synth_x(B, T, seed=4), synth_labels(B, seed=4)
     flat0 = orc.flatten_state(ref_state, D)
-    tr.step(_t(x, dev), _t(y, dev))
+    tr.step(to_dev(x, dev), to_dev(y, dev))
     sid = 4
     dl = orc.dropout_mask(tr.seed, sid, 0.6, (1, B, T, 48))
     sl = orc.rrelu_noise(tr.seed, sid + 1, (B, 32))
     dh = orc.dropout_mask(tr.seed, sid + 2, 0.6, (B, 32))
     loss_ref, g_ref, _ = orc.loss_and_grads(flat0, x, y, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    assert abs(tr.last_loss() - loss_ref) < 5e-5
-    _grad_close(tr.grads.cpu().numpy(), g_ref, D, **FAST48)
+    assert abs(tr.last_loss() - loss_ref) < LOSS_TOL
+    grad_close(tr.grads.cpu().numpy(), g_ref, D, **FAST48)
     # Adam on the step's own gradient (entries with |g| ~ eps make the update ill-conditioned w.r.t. g itself)
     p, mm, vv = flat0.copy(), np.zeros_like(flat0), np.zeros_like(flat0)
     orc.adam(p, tr.grads.cpu().numpy(), mm, vv, lr=1e-3, step=1)
@@ -553,11 +450,11 @@ def test_thirty_step_training_trajectory_matches_oracle(nsd, dev, ref_state):
     """End to end over many steps: 30 Trainer.step calls (in-kernel random streams, fused launches, Adam) against 30
     oracle steps with the same counter-based masks: the loss curve and the final parameters stay together."""
     from nsd_amd.trainer import Trainer
-    m = _model(nsd, dev, ref_state).train()
+    m = model_from_state(nsd, dev, ref_state).train()
     tr = Trainer(m, lr=1e-3, seed=5)
     B, T = 16, 40
     x, y = synth_x(B, T, seed=40), synth_labels(B, seed=40)
-    xt, yt = _t(x, dev), _t(y, dev)
+    xt, yt = to_dev(x, dev), to_dev(y, dev)
     p = orc.flatten_state(ref_state, D).copy()
     mm, vv = np.zeros_like(p), np.zeros_like(p)
     for step in range(1, 31):
@@ -583,8 +480,8 @@ def test_fused_reduce_adam_is_bit_identical_to_separate_launches(nsd, dev, ref_s
     from nsd_amd import ops
     spec = ops.ModelSpec()
     B, T = 37, 50
-    x, y = _t(synth_x(B, T, seed=12), dev), _t(synth_labels(B, seed=12), dev)
-    flat0 = _t(orc.flatten_state(ref_state, D), dev)
+    x, y = to_dev(synth_x(B, T, seed=12), dev), to_dev(synth_labels(B, seed=12), dev)
+    flat0 = to_dev(orc.flatten_state(ref_state, D), dev)
     out = {}
     for fused in (False, True):
         flat, g = flat0.clone(), torch.zeros_like(flat0)
@@ -611,10 +508,10 @@ def test_in_kernel_random_streams_equal_explicit_masks(nsd, dev, ref_state, B, T
     """Trainer.step with the dropout / RReLU streams generated inside the kernels (nsd_lstm_head_train_rng,
     nsd_lstm_bwd_rng) == the same step with the tensors of nsd_train_masks: same values, same arithmetic."""
     from nsd_amd.trainer import Trainer
-    x, y = _t(synth_x(B, T, seed=21), dev), _t(synth_labels(B, seed=21), dev)
+    x, y = to_dev(synth_x(B, T, seed=21), dev), to_dev(synth_labels(B, seed=21), dev)
     out = []
     for in_kernel in (True, False):
-        m = _model(nsd, dev, ref_state).train()
+        m = model_from_state(nsd, dev, ref_state).train()
         tr = Trainer(m, lr=1e-3, seed=11)
         tr.in_kernel_rng = in_kernel
         for _ in range(2):
@@ -641,8 +538,8 @@ def test_multi_rank_launch_sequence_over_rccl_single_rank_group(nsd, dev, ref_st
             pytest.skip(f"cannot create a 1-rank nccl group here: {e}")
     try:
         B, T = 24, 50
-        x, y = _t(synth_x(B, T, seed=31), dev), _t(synth_labels(B, seed=31), dev)
-        ma, mb = _model(nsd, dev, ref_state).train(), _model(nsd, dev, ref_state).train()
+        x, y = to_dev(synth_x(B, T, seed=31), dev), to_dev(synth_labels(B, seed=31), dev)
+        ma, mb = model_from_state(nsd, dev, ref_state).train(), model_from_state(nsd, dev, ref_state).train()
         ta, tb = Trainer(ma, lr=1e-3, seed=9), Trainer(mb, lr=1e-3, seed=9)
         assert ta.seed == tb.seed
         # force the multi-rank code path of tb (its collective runs over the real RCCL group of size 1)
@@ -660,7 +557,7 @@ def test_multi_rank_launch_sequence_over_rccl_single_rank_group(nsd, dev, ref_st
         torch.cuda.synchronize()
         # tb scaled its CE gradient by 1/(B*2) (a power of two: exact), everything downstream is linear in it
         assert torch.equal(ta.grads, 2.0 * tb.grads)
-        assert torch.isfinite(mb.flat_parameters()).all() and not torch.equal(mb.flat_parameters(), _t(orc.flatten_state(ref_state, D), dev))
+        assert torch.isfinite(mb.flat_parameters()).all() and not torch.equal(mb.flat_parameters(), to_dev(orc.flatten_state(ref_state, D), dev))
     finally:
         if created:
             dist.destroy_process_group()
@@ -670,8 +567,8 @@ def test_graph_replay_step_equals_eager_step(nsd, dev, ref_state):
     """Trainer.step_static (captured hipGraphs, device-side step counter) == Trainer.step (eager launches)."""
     from nsd_amd.trainer import Trainer
     B, T = 16, 30
-    x, y = _t(synth_x(B, T, seed=8), dev), _t(synth_labels(B, seed=8), dev)
-    ma, mb = _model(nsd, dev, ref_state).train(), _model(nsd, dev, ref_state).train()
+    x, y = to_dev(synth_x(B, T, seed=8), dev), to_dev(synth_labels(B, seed=8), dev)
+    ma, mb = model_from_state(nsd, dev, ref_state).train(), model_from_state(nsd, dev, ref_state).train()
     ta, tb = Trainer(ma, lr=1e-3, seed=5), Trainer(mb, lr=1e-3, seed=5)
     xs, ys = tb.static_inputs(B, T)
     xs.copy_(x); ys.copy_(y)
@@ -690,12 +587,12 @@ def test_adam_matches_oracle_and_torch(nsd, dev):
     n = 31764
     p0 = rs.standard_normal(n).astype(np.float32)
     po, mo, vo = p0.copy(), np.zeros(n, np.float32), np.zeros(n, np.float32)
-    p, m, v = _t(p0, dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    p, m, v = to_dev(p0, dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
     pt = torch.nn.Parameter(torch.from_numpy(p0.copy()))
     opt = torch.optim.Adam([pt], lr=1e-3)
     for step in range(1, 8):
         g = rs.standard_normal(n).astype(np.float32)
-        ops.adam_step(p, _t(g, dev), m, v, step=step, lr=1e-3)
+        ops.adam_step(p, to_dev(g, dev), m, v, step=step, lr=1e-3)
         orc.adam(po, g, mo, vo, lr=1e-3, step=step)
         pt.grad = torch.from_numpy(g.copy())
         opt.step()
@@ -708,16 +605,16 @@ def test_adam_matches_oracle_and_torch(nsd, dev):
 # ---------------------------------------------------------------------------------------------------
 def test_module_autograd_and_state_dict(nsd, dev, golden, ref_state):
     g = golden("grads_32x250")
-    m = _model(nsd, dev, ref_state)
+    m = model_from_state(nsd, dev, ref_state)
     assert list(m.state_dict().keys()) == list(ref_state.keys())
     m.eval()                                   # eval-mode RReLU, no dropout, but gradients requested
-    x, y = _t(synth_x(32, 250), dev), _t(synth_labels(32).astype(np.int64), dev)
+    x, y = to_dev(synth_x(32, 250), dev), to_dev(synth_labels(32).astype(np.int64), dev)
     loss = torch.nn.functional.cross_entropy(m(x), y)
     loss.backward()
     assert abs(loss.item() - float(g["eval.loss"])) < 2e-5
     for k, p in m.named_parameters():
         r = g["eval." + k]
-        tol = 2e-6 if k == "attn.bias" else 2e-4 * max(np.abs(r).max(), 1e-6) + 1e-7
+        tol = 2e-6 if k == "attn.bias" else GRAD_RTOL_12 * max(np.abs(r).max(), 1e-6) + 1e-7
         assert np.abs(p.grad.cpu().numpy() - r).max() <= tol, k
     # a torch optimizer step on the Parameters is visible to the kernels (views of one flat vector)
     before = m.flat_parameters().clone()
@@ -733,28 +630,21 @@ def test_module_autograd_and_state_dict(nsd, dev, golden, ref_state):
 
 def test_train_mode_is_stochastic_and_seeded(nsd, dev, ref_state):
     torch.manual_seed(5)
-    m = _model(nsd, dev, ref_state).train()
-    x = _t(synth_x(8, 50), dev)
+    m = model_from_state(nsd, dev, ref_state).train()
+    x = to_dev(synth_x(8, 50), dev)
     a, b = m(x), m(x)
     assert not torch.equal(a, b)               # fresh dropout / RReLU noise every call
     torch.manual_seed(5)
-    m2 = _model(nsd, dev, ref_state).train()
+    m2 = model_from_state(nsd, dev, ref_state).train()
     assert torch.equal(m2(x), a)               # same seed -> same stream
     a.sum().backward()
     assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in m.parameters())
 
 
-def _write_pth(tmp_path, ref_state, wrapped=False):
-    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in ref_state.items()}
-    p = os.path.join(tmp_path, "model.pth")
-    torch.save({"state_dict": sd} if wrapped else sd, p)
-    return p
-
-
 @pytest.mark.parametrize("wrapped", [False, True])
 def test_simple_predictor(nsd, dev, golden, ref_state, tmp_path, wrapped):
     g = golden("real_trials")
-    pred = nsd.SimplePredictor(_write_pth(str(tmp_path), ref_state, wrapped), sr=125, device="cpu",
+    pred = nsd.SimplePredictor(write_pth(str(tmp_path), ref_state, wrapped), sr=125, device="cpu",
                                class_names=["Food", "Water", "None"], preprocess="identity")
     for i in (0, 7, 15):
         probs, label = pred.predict(g["x"][i])
@@ -768,7 +658,7 @@ def test_simple_predictor(nsd, dev, golden, ref_state, tmp_path, wrapped):
 def test_predict_windows_equals_per_window_predict(nsd, dev, golden, ref_state, tmp_path):
     """Batched / streaming mode: every window of a long recording in one launch == predict() per window."""
     g = golden("real_trials")
-    pred = nsd.SimplePredictor(_write_pth(str(tmp_path), ref_state, False), sr=125, device="cpu",
+    pred = nsd.SimplePredictor(write_pth(str(tmp_path), ref_state, False), sr=125, device="cpu",
                                class_names=["Food", "Water", "None"], preprocess="identity")
     rec = np.concatenate([g["x"][0], g["x"][3], g["x"][9]], axis=0)            # [1875, 8]
     for window, hop in ((625, None), (250, 100), (625, 625), (2000, 1)):
@@ -790,7 +680,7 @@ def test_run_trials_replay(nsd, dev, golden, ref_state, tmp_path):
     d.mkdir()
     for i in range(4):
         np.savetxt(d / f"food_{i:02d}.csv", g["x"][i], fmt="%.7f", delimiter=",")
-    res = nsd.run_trials(trials=4, serial_port=f"replay:{d}", model_path=_write_pth(str(tmp_path), ref_state),
+    res = nsd.run_trials(trials=4, serial_port=f"replay:{d}", model_path=write_pth(str(tmp_path), ref_state),
                          verbose=False, queue_timeout=20.0, predictor_kwargs={"preprocess": "identity"})
     assert res.trials == 4 and res.avg_probs.shape == (3,) and res.avg_chunk.shape == (625, 8)
     assert np.abs(res.avg_probs - g["probs"][:4].mean(0)).max() < 1e-5
@@ -813,7 +703,7 @@ def test_train_cli_learns_and_writes_reference_loadable_checkpoint(nsd, dev, tmp
     x = (2.7 * rs.standard_normal((384, 40, 8))).astype(np.float32)
     x[np.arange(384), :, y % 8] += 1.5
     with torch.no_grad():
-        acc = (pred.model(_t(x, dev)).argmax(-1).cpu().numpy() == y).mean()
+        acc = (pred.model(to_dev(x, dev)).argmax(-1).cpu().numpy() == y).mean()
     assert acc > 0.8, acc                                          # chance is 1/3
 
 
@@ -826,10 +716,10 @@ def test_reference_logits_on_every_recorded_window(nsd, dev, ref_state):
     from nsd_amd import data as Dm
     ts = Dm.load_trials_npz(RECORDED, Dm.LABELS_5CLASS)
     ref = np.load(RECORDED)["ref_logits_raw"]
-    m = _model(nsd, dev, ref_state).eval()
+    m = model_from_state(nsd, dev, ref_state).eval()
     with torch.no_grad():
-        lg = m(_t(ts.x, dev)).cpu().numpy()
-    assert np.abs(lg - ref).max() < 1e-4
+        lg = m(to_dev(ts.x, dev)).cpu().numpy()
+    assert np.abs(lg - ref).max() < LOGIT_TOL
     assert np.array_equal(lg.argmax(-1), ref.argmax(-1))
     # same confusion behaviour as the reference on the 179 three-class windows (checkpoint label order water/food/noise;
     # fed RAW the reference checkpoint scores 45.8 % -- its 68.7 % of SURVEY 6 needs the MindsAI filter it was trained with)
@@ -858,7 +748,7 @@ def test_train_on_recorded_trials(nsd, dev, tmp_path):
     ts = Dm.load_trials_npz(RECORDED)
     _, va = Dm.stratified_split(ts.y, 0.2, 1)
     with torch.no_grad():
-        acc = float((pred.model(_t(ts.x[va], dev)).argmax(-1).cpu().numpy() == ts.y[va]).mean())
+        acc = float((pred.model(to_dev(ts.x[va], dev)).argmax(-1).cpu().numpy() == ts.y[va]).mean())
     assert acc == pytest.approx(done["best_val_acc"], abs=1e-6)
 
 
@@ -893,7 +783,7 @@ def test_predict_with_the_references_preprocessing(nsd, dev, ref_state, tmp_path
     assert list(rec["stem"]) == list(flt["stem"])
     raw, xf, want, labels = rec["x"], flt["x_filt"], flt["ref_probs"], [str(s) for s in flt["ref_label"]]
     assert np.abs(raw - xf).max() > 1.0                         # the filter really changes the windows (tens of microvolts)
-    pred = nsd.SimplePredictor(_write_pth(str(tmp_path), ref_state, False), sr=125, device="cpu",
+    pred = nsd.SimplePredictor(write_pth(str(tmp_path), ref_state, False), sr=125, device="cpu",
                                preprocess=_ReplayPreProcessor(raw, xf))
     worst, flips = 0.0, 0
     for i in range(0, len(raw), 9):                             # 36 windows one by one, the live loop's shape (B = 1, T = 625)
@@ -926,8 +816,8 @@ def test_shipped_default_checkpoint_is_paired_with_the_references_preprocessing(
     three = [i for i, s in enumerate(rec["prefix"]) if str(s) in Dm.LABELS_3CLASS_CHECKPOINT]
     y = np.array([Dm.LABELS_3CLASS_CHECKPOINT[str(rec["prefix"][i])] for i in three])
     with torch.no_grad():
-        acc_f = float((pred.model(_t(flt["x_filt"][three], dev)).argmax(-1).cpu().numpy() == y).mean())
-        acc_r = float((pred.model(_t(rec["x"][three], dev)).argmax(-1).cpu().numpy() == y).mean())
+        acc_f = float((pred.model(to_dev(flt["x_filt"][three], dev)).argmax(-1).cpu().numpy() == y).mean())
+        acc_r = float((pred.model(to_dev(rec["x"][three], dev)).argmax(-1).cpu().numpy() == y).mean())
     print(f"shipped checkpoint: accuracy on its training windows (filtered) {acc_f:.3f}, on the same windows unfiltered {acc_r:.3f}")
     assert acc_f >= 0.70 and acc_f > acc_r
     probs, label = pred.predict(rec["x"][three[0]])
@@ -966,9 +856,9 @@ def test_two_trials_per_workgroup_forward_equals_the_one_trial_kernel_bitwise(ns
     (The instantiation is pinned through the diagnostic twin of the library: the product has no such hook.)"""
     from nsd_amd import _lib, ops
     spec = ops.ModelSpec()
-    flat = _t(orc.flatten_state(ref_state, D), dev)
-    x, y = _t(synth_x(B, T, seed=B + T), dev), _t(synth_labels(B, seed=B + T).astype(np.int32), dev)
-    dl, sl, dh = (_t(m, dev) for m in counter_masks(B, T, 48, 32, seed=3 * B + T))
+    flat = to_dev(orc.flatten_state(ref_state, D), dev)
+    x, y = to_dev(synth_x(B, T, seed=B + T), dev), to_dev(synth_labels(B, seed=B + T).astype(np.int32), dev)
+    dl, sl, dh = (to_dev(m, dev) for m in counter_masks(B, T, 48, 32, seed=3 * B + T))
     rng = dict(seed=0x1234ABCD, base_stream=44, p_lstm=0.6, p_head=0.6)
     variants = [dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=True), dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=False)]
     if ops.rng_path(spec, B, T) and not residual:
@@ -999,9 +889,9 @@ def test_two_trials_per_workgroup_forward_equals_the_one_trial_kernel_bitwise(ns
                 xn, yn = synth_x(B, T, seed=B + T), synth_labels(B, seed=B + T)
                 dln, sln, dhn = counter_masks(B, T, 48, 32, seed=3 * B + T)
                 loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, xn, yn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn, residual=residual)
-                loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn, residual=residual)
-                assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-                _grad_close(grads, g_ref, D, **FAST48)
+                loss, grads, logits = forward_backward(dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn, residual=residual)
+                assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+                grad_close(grads, g_ref, D, **FAST48)
         finally:
             ops.force_fwd48(0)
 
@@ -1018,11 +908,11 @@ def test_four_trials_per_workgroup_forward_on_the_matrix_pipe(nsd, dev, ref_stat
     from nsd_amd import _lib, ops
     spec = ops.ModelSpec()
     flat_np = orc.flatten_state(ref_state, D)
-    flat = _t(flat_np, dev)
+    flat = to_dev(flat_np, dev)
     xn, yn = synth_x(B, T, seed=B + T), synth_labels(B, seed=B + T)
-    x, y = _t(xn, dev), _t(yn.astype(np.int32), dev)
+    x, y = to_dev(xn, dev), to_dev(yn.astype(np.int32), dev)
     dln, sln, dhn = counter_masks(B, T, 48, 32, seed=3 * B + T)
-    dl, sl, dh = _t(dln, dev), _t(sln, dev), _t(dhn, dev)
+    dl, sl, dh = to_dev(dln, dev), to_dev(sln, dev), to_dev(dhn, dev)
     rng = dict(seed=0x1234ABCD, base_stream=44, p_lstm=0.6, p_head=0.6)
     variants = [dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=True), dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=False)]
     if ops.rng_path(spec, B, T):
@@ -1058,9 +948,9 @@ def test_four_trials_per_workgroup_forward_on_the_matrix_pipe(nsd, dev, ref_stat
                 if vi < 2:                                        # explicit masks: the oracle saw the same ones
                     assert np.abs(l4.cpu().numpy() - fw["logits"]).max() < LOGIT_TOL
             ops.force_fwd48(4)
-            loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
-            assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-            _grad_close(grads, g_ref, D, **FAST48)
+            loss, grads, logits = forward_backward(dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+            assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+            grad_close(grads, g_ref, D, **FAST48)
         finally:
             ops.force_fwd48(0)
 
@@ -1076,11 +966,11 @@ def test_four_trials_per_workgroup_backward_on_the_matrix_pipe(nsd, dev, ref_sta
     from nsd_amd import _lib, ops
     spec = ops.ModelSpec()
     flat_np = orc.flatten_state(ref_state, D)
-    flat = _t(flat_np, dev)
+    flat = to_dev(flat_np, dev)
     xn, yn = synth_x(B, T, seed=B + T), synth_labels(B, seed=B + T)
-    x, y = _t(xn, dev), _t(yn.astype(np.int32), dev)
+    x, y = to_dev(xn, dev), to_dev(yn.astype(np.int32), dev)
     dln, sln, dhn = counter_masks(B, T, 48, 32, seed=3 * B + T)
-    dl, sl, dh = _t(dln, dev), _t(sln, dev), _t(dhn, dev)
+    dl, sl, dh = to_dev(dln, dev), to_dev(sln, dev), to_dev(dhn, dev)
     rng = dict(seed=0x1234ABCD, base_stream=44, p_lstm=0.6, p_head=0.6)
     variants = [dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=True), dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=False)]
     if ops.rng_path(spec, B, T):
@@ -1104,13 +994,13 @@ def test_four_trials_per_workgroup_backward_on_the_matrix_pipe(nsd, dev, ref_sta
                 assert torch.isfinite(g4).all(), kw.keys()
                 assert (g2 - g4).abs().max().item() <= 2e-5 * g2.abs().max().item() + 1e-9, (kw.keys(), (g2 - g4).abs().max().item(), g2.abs().max().item())
                 if vi < 2:
-                    _grad_close(g4.cpu().numpy() * 1.0, g_ref, D, **FAST48)
+                    grad_close(g4.cpu().numpy() * 1.0, g_ref, D, **FAST48)
             # both new kernels together (what the product runs from 513 trials on), against the oracle
             ops.force_fwd48(4)
             ops.force_bwd48(4)
-            loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
-            assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-            _grad_close(grads, g_ref, D, **FAST48)
+            loss, grads, logits = forward_backward(dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+            assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+            grad_close(grads, g_ref, D, **FAST48)
         finally:
             ops.force_fwd48(0)
             ops.force_bwd48(0)
@@ -1127,11 +1017,11 @@ def test_four_trial_kernels_share_the_attention_backward(nsd, dev, ref_state, B,
     from nsd_amd import _lib, ops
     spec = ops.ModelSpec()
     flat_np = orc.flatten_state(ref_state, D)
-    flat = _t(flat_np, dev)
+    flat = to_dev(flat_np, dev)
     xn, yn = synth_x(B, T, seed=B + T), synth_labels(B, seed=B + T)
-    x, y = _t(xn, dev), _t(yn.astype(np.int32), dev)
+    x, y = to_dev(xn, dev), to_dev(yn.astype(np.int32), dev)
     dln, sln, dhn = counter_masks(B, T, 48, 32, seed=3 * B + T)
-    dl, sl, dh = _t(dln, dev), _t(sln, dev), _t(dhn, dev)
+    dl, sl, dh = to_dev(dln, dev), to_dev(sln, dev), to_dev(dhn, dev)
     variants = [dict(drop_lstm=dl, rrelu_slope=sl, drop_head=dh, fused_head=True)]
     if ops.rng_path(spec, B, T):
         variants.append(dict(rng=dict(seed=0x1234ABCD, base_stream=44, p_lstm=0.6, p_head=0.6)))
@@ -1178,21 +1068,21 @@ def test_four_trial_kernels_other_channel_and_class_counts(nsd, dev, C, K, B, T)
         try:
             ops.force_fwd48(4)
             ops.force_bwd48(4)
-            loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, spec=spec, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
+            loss, grads, logits = forward_backward(dev, flat_np, x, y, spec=spec, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
             # ... and the single-launch forward + head with the same masks
-            flat, xt = _t(flat_np, dev), _t(x, dev)
+            flat, xt = to_dev(flat_np, dev), to_dev(x, dev)
             ws = ops.new_workspace(spec, B, T, dev)
             lg = torch.empty((B, K), device=dev)
             g2 = torch.empty_like(flat)
-            ops.train_step_grads(spec, flat, xt, ws, _t(y.astype(np.int32), dev), lg, g2, drop_lstm=_t(dl, dev), rrelu_slope=_t(sl, dev), drop_head=_t(dh, dev))
+            ops.train_step_grads(spec, flat, xt, ws, to_dev(y.astype(np.int32), dev), lg, g2, drop_lstm=to_dev(dl, dev), rrelu_slope=to_dev(sl, dev), drop_head=to_dev(dh, dev))
             torch.cuda.synchronize()
         finally:
             ops.force_fwd48(0)
             ops.force_bwd48(0)
-    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, d, rtol=3e-4)
+    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+    grad_close(grads, g_ref, d, rtol=GRAD_RTOL_X4)
     assert np.abs(lg.cpu().numpy() - fw["logits"]).max() < LOGIT_TOL
-    _grad_close(g2.cpu().numpy(), g_ref, d, rtol=3e-4)
+    grad_close(g2.cpu().numpy(), g_ref, d, rtol=GRAD_RTOL_X4)
 
 
 def test_four_trial_kernels_loop_over_trial_groups(nsd, dev, ref_state):
@@ -1205,9 +1095,9 @@ def test_four_trial_kernels_loop_over_trial_groups(nsd, dev, ref_state):
     x, y = synth_x(B, T, seed=77), synth_labels(B, seed=77)
     dl, sl, dh = counter_masks(B, T, 48, 32, seed=78)
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, x, y, D, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
-    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < 5e-5
-    _grad_close(grads, g_ref, D, **FAST48)
+    loss, grads, logits = forward_backward(dev, flat_np, x, y, drop_lstm=dl, rrelu_slope=sl, drop_head=dh)
+    assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL and abs(loss - loss_ref) < LOSS_TOL
+    grad_close(grads, g_ref, D, **FAST48)
 
 
 @pytest.mark.parametrize("B,T,nb", [(32, 250, 1), (12, 625, 1), (32, 250, 4), (12, 625, 4)])
@@ -1227,7 +1117,7 @@ def test_split_bf16_weight_gradients_stay_within_their_bound(nsd, dev, ref_state
         try:
             ops.force_fwd48(nb)
             ops.force_bwd48(2 if nb == 1 else 4)                 # (2: the one- / two-trial kernel -- one trial per workgroup at these batches)
-            loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+            loss, grads, logits = forward_backward(dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
         finally:
             ops.force_fwd48(0)
             ops.force_bwd48(0)
@@ -1254,12 +1144,12 @@ def test_input_gradient_matches_torch_autograd(nsd, dev, ref_state, B, T, H):
     if H == 48:
         ref.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in ref_state.items()}, strict=True)
     state = {k: v.detach().numpy() for k, v in ref.state_dict().items()}
-    m = _model(nsd, dev, state).eval()
+    m = model_from_state(nsd, dev, state).eval()
     xn, yn = synth_x(B, T, seed=B + T), synth_labels(B, seed=B + T).astype(np.int64)
     xr = torch.from_numpy(xn).requires_grad_(True)
     torch.nn.functional.cross_entropy(ref(xr), torch.from_numpy(yn)).backward()
-    xg = _t(xn, dev).requires_grad_(True)
-    torch.nn.functional.cross_entropy(m(xg), _t(yn, dev)).backward()
+    xg = to_dev(xn, dev).requires_grad_(True)
+    torch.nn.functional.cross_entropy(m(xg), to_dev(yn, dev)).backward()
     assert xg.grad is not None and tuple(xg.grad.shape) == (B, T, 8) and torch.isfinite(xg.grad).all()
     err = (xg.grad.cpu() - xr.grad).abs().max().item()
     scale = xr.grad.abs().max().item()
@@ -1273,8 +1163,8 @@ def test_input_gradient_matches_torch_autograd(nsd, dev, ref_state, B, T, H):
 def test_second_backward_after_an_input_gradient_is_refused(nsd, dev, ref_state):
     """The H = 48 kernel forms dx in place of layer 0's saved gates: a graph that returned dx cannot be walked again (it says so);
     without dx (the training case) retain_graph keeps working and gives the same parameter gradients twice."""
-    m = _model(nsd, dev, ref_state).eval()
-    x = _t(synth_x(4, 20), dev)
+    m = model_from_state(nsd, dev, ref_state).eval()
+    x = to_dev(synth_x(4, 20), dev)
     out = m(x).sum()
     out.backward(retain_graph=True)
     g1 = [p.grad.clone() for p in m.parameters()]
@@ -1301,9 +1191,9 @@ def test_batch_bands_of_the_dispatch_vs_oracle(nsd, dev, ref_state, B, T):
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, xn, yn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
     res = []
     for fused in (True, False):
-        out = _hip_step(nsd, dev, flat_np, xn, yn, fused, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
-        assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL and abs(float(out["loss"].sum()) / B - loss_ref) < 5e-5
-        _grad_close(out["grads"], g_ref, D, **FAST48)
+        out = train_step(dev, spec_of(D), flat_np, xn, labels=yn, fused=fused, masks=dict(drop_lstm=dln, rrelu_slope=sln, drop_head=dhn))
+        assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL and abs(out["mean_loss"] - loss_ref) < LOSS_TOL
+        grad_close(out["grads"], g_ref, D, **FAST48)
         res.append(out["grads"])
     assert np.abs(res[0] - res[1]).max() <= 2e-5 * np.abs(res[0]).max()
 
@@ -1317,9 +1207,9 @@ def test_experimental_one_wave_per_layer_forward_matches_the_product_kernel(nsd,
     from nsd_amd import _lib, ops
     spec = ops.ModelSpec()
     flat_np = orc.flatten_state(ref_state, D)
-    flat = _t(flat_np, dev)
+    flat = to_dev(flat_np, dev)
     xn = synth_x(B, T, seed=B + T)
-    x = _t(xn, dev)
+    x = to_dev(xn, dev)
     dln, sln, dhn = counter_masks(B, T, 48, 32, seed=3 * B + T)
     fw = orc.forward(flat_np, xn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn) if hasattr(orc, "forward") else None
     with _lib.diagnostic_library():
@@ -1329,7 +1219,7 @@ def test_experimental_one_wave_per_layer_forward_matches_the_product_kernel(nsd,
                 ops.force_fwd48(nb)
                 ws = ops.new_workspace(spec, B, T, dev)
                 ws.fill_(float("nan"))
-                logits, _ = ops.train_forward(spec, flat, x, ws, drop_lstm=_t(dln, dev), rrelu_slope=_t(sln, dev), drop_head=_t(dhn, dev))
+                logits, _ = ops.train_forward(spec, flat, x, ws, drop_lstm=to_dev(dln, dev), rrelu_slope=to_dev(sln, dev), drop_head=to_dev(dhn, dev))
                 torch.cuda.synchronize()
                 res[nb] = (logits.clone(), ws.clone())
         finally:
@@ -1359,10 +1249,10 @@ def test_every_sequence_length_up_to_40(nsd, dev, ref_state, nb):
                 xn, yn = synth_x(B, T, seed=50 + T), synth_labels(B, seed=50 + T)
                 dln, sln, dhn = counter_masks(B, T, 48, 32, seed=9 * T + nb)
                 loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, xn, yn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
-                loss, grads, logits = _hip_loss_grads(nsd, dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
+                loss, grads, logits = forward_backward(dev, flat_np, xn, yn, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
                 assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL, T
                 try:
-                    _grad_close(grads, g_ref, D, **FAST48)
+                    grad_close(grads, g_ref, D, **FAST48)
                 except AssertionError as e:
                     raise AssertionError(f"T={T}: {e}")
         finally:
@@ -1394,7 +1284,7 @@ def test_input_gradient_after_the_fused_head_vs_oracle(nsd, dev, ref_state, B, T
                 ops.force_fwd48(force)
                 ops.force_bwd48(force)
             for fused in (True, False):
-                outs[fused] = _hip_step(nsd, dev, flat_np, xn, yn, fused, want_dx=True, **masks)
+                outs[fused] = train_step(dev, spec_of(D), flat_np, xn, labels=yn, fused=fused, want_dx=True, masks=masks, saves=HEAD_SAVES)
         finally:
             if force:
                 ops.force_fwd48(0)
@@ -1402,8 +1292,8 @@ def test_input_gradient_after_the_fused_head_vs_oracle(nsd, dev, ref_state, B, T
     h1, pooled = fw["hseq"][1].astype(np.float64), fw["pooled"].astype(np.float64)
     for fused, out in outs.items():
         assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL, fused
-        assert abs(float(out["loss"].sum()) / B - loss_ref) < 5e-5, fused
-        _grad_close(out["grads"], g_ref, D, **FAST48)
+        assert abs(out["mean_loss"] - loss_ref) < LOSS_TOL, fused
+        grad_close(out["grads"], g_ref, D, **FAST48)
         err, scale = float(np.abs(out["dx"] - dx_ref).max()), float(np.abs(dx_ref).max())
         print(f"dx B={B} T={T} fused={fused}: max error / largest element {err / scale:.2e}")
         assert err <= DX_TOL * scale, (fused, err, scale)
@@ -1424,34 +1314,34 @@ def test_benchmarked_shapes_train_step_vs_oracle(nsd, dev, ref_state, B, T):
     against the oracle with the same counter-based masks: loss, logits (1e-4, same argmax), every gradient tensor (FAST48), the Adam
     update.  At 1024 x 250 also dL/dx through the module (eval mode, the unfused head, the one-trial backward kernel)."""
     from nsd_amd.trainer import Trainer
-    m = _model(nsd, dev, ref_state).train()
+    m = model_from_state(nsd, dev, ref_state).train()
     tr = Trainer(m, lr=1e-3, seed=7)
     xn, yn = synth_x(B, T, seed=B + 11), synth_labels(B, seed=B + 11)
     flat0 = orc.flatten_state(ref_state, D)
-    tr.step(_t(xn, dev), _t(yn, dev))
+    tr.step(to_dev(xn, dev), to_dev(yn, dev))
     logits = tr._buffers(B, T)["logits"].cpu().numpy()
     sid = 4
     dln = orc.dropout_mask(tr.seed, sid, 0.6, (1, B, T, 48))
     sln = orc.rrelu_noise(tr.seed, sid + 1, (B, 32))
     dhn = orc.dropout_mask(tr.seed, sid + 2, 0.6, (B, 32))
     loss_ref, g_ref, fw = orc.loss_and_grads(flat0, xn, yn, D, drop_lstm=dln, rrelu_slope=sln, drop_head=dhn)
-    assert abs(tr.last_loss() - loss_ref) < 5e-5
+    assert abs(tr.last_loss() - loss_ref) < LOSS_TOL
     assert np.abs(logits - fw["logits"]).max() < LOGIT_TOL
     assert np.array_equal(logits.argmax(1), fw["logits"].argmax(1))
     grads = tr.grads.cpu().numpy()
-    _grad_close(grads, g_ref, D, **FAST48)
+    grad_close(grads, g_ref, D, **FAST48)
     p, mm, vv = flat0.copy(), np.zeros_like(flat0), np.zeros_like(flat0)
     orc.adam(p, grads, mm, vv, lr=1e-3, step=1)
     assert np.abs(m.flat_parameters().cpu().numpy() - p).max() < 2e-6
     if B == 1024:
-        m2 = _model(nsd, dev, ref_state).eval()
+        m2 = model_from_state(nsd, dev, ref_state).eval()
         fw2 = orc.forward(flat0, xn, D, saves=True)
         _, dl2 = orc.ce_loss(fw2["logits"], yn)
         g2_ref, dx_ref = orc.backward(flat0, xn, D, fw2, dl2, want_dx=True)
-        xg = _t(xn, dev).requires_grad_(True)
-        torch.nn.functional.cross_entropy(m2(xg), _t(yn.astype(np.int64), dev)).backward()
+        xg = to_dev(xn, dev).requires_grad_(True)
+        torch.nn.functional.cross_entropy(m2(xg), to_dev(yn.astype(np.int64), dev)).backward()
         g2 = torch.cat([p.grad.reshape(-1) for _, p in m2._named_in_order()]).cpu().numpy()
-        _grad_close(g2, g2_ref, D, **FAST48)
+        grad_close(g2, g2_ref, D, **FAST48)
         err, scale = float(np.abs(xg.grad.cpu().numpy() - dx_ref).max()), float(np.abs(dx_ref).max())
         print(f"dx B={B} T={T} (module): max error / largest element {err / scale:.2e}")
         assert err <= DX_TOL * scale, (err, scale)
@@ -1484,8 +1374,8 @@ def test_input_gradient_on_the_generic_path_survives_a_second_backward(nsd, dev)
     parameter gradients and the same dx twice."""
     torch.manual_seed(3)
     m = nsd.EEG_LSTM(hidden_size=48, num_layers=3).to(dev).eval()
-    xg = _t(synth_x(4, 20), dev).requires_grad_(True)
-    out = torch.nn.functional.cross_entropy(m(xg), _t(synth_labels(4).astype(np.int64), dev))
+    xg = to_dev(synth_x(4, 20), dev).requires_grad_(True)
+    out = torch.nn.functional.cross_entropy(m(xg), to_dev(synth_labels(4).astype(np.int64), dev))
     res = []
     for _ in range(2):
         for p in m.parameters():
@@ -1502,17 +1392,17 @@ def test_paths_without_an_input_gradient_still_return_the_parameter_gradients(ns
     from nsd_amd import lstm_eeg_model
     d = orc.Dims(C=8, H=32, L=2, K=3)
     st = synth_params(8, 32, 2, 3, seed=4)
-    m = _model(nsd, dev, st).eval()
+    m = model_from_state(nsd, dev, st).eval()
     B, T = 6, 30
     xn, yn = synth_x(B, T, seed=8), synth_labels(B, seed=8)
     _, g_ref, _ = orc.loss_and_grads(orc.flatten_state(st, d), xn, yn, d)
     lstm_eeg_model._no_dx_warned.discard(m.spec)
-    xg = _t(xn, dev).requires_grad_(True)
+    xg = to_dev(xn, dev).requires_grad_(True)
     with pytest.warns(UserWarning, match="no input gradient"):
-        torch.nn.functional.cross_entropy(m(xg), _t(yn.astype(np.int64), dev)).backward()
+        torch.nn.functional.cross_entropy(m(xg), to_dev(yn.astype(np.int64), dev)).backward()
     assert xg.grad is None
     g = torch.cat([p.grad.reshape(-1) for _, p in m._named_in_order()]).cpu().numpy()
-    _grad_close(g, g_ref, d, rtol=3e-4)
+    grad_close(g, g_ref, d, rtol=GRAD_RTOL_X4)
 
 
 def test_normalize_input_gradient_matches_torch_autograd(nsd, dev, ref_state):
@@ -1523,14 +1413,14 @@ def test_normalize_input_gradient_matches_torch_autograd(nsd, dev, ref_state):
     B, T = 5, 40
     ref = StackedTorchEEG(C=8, H=48, L=2, K=3).eval()
     ref.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in ref_state.items()}, strict=True)
-    m = _model(nsd, dev, ref_state, normalize=True).eval()
+    m = model_from_state(nsd, dev, ref_state, normalize=True).eval()
     xn, yn = (3.0 * synth_x(B, T, seed=21) + 1.5).astype(np.float32), synth_labels(B, seed=21).astype(np.int64)
     xr = torch.from_numpy(xn).double().requires_grad_(True)
     mu = xr.mean(dim=1, keepdim=True)
     sd = (xr - mu).square().mean(dim=1, keepdim=True).sqrt() + 1e-6
     torch.nn.functional.cross_entropy(ref.double()((xr - mu) / sd), torch.from_numpy(yn)).backward()
-    xg = _t(xn, dev).requires_grad_(True)
-    torch.nn.functional.cross_entropy(m(xg), _t(yn, dev)).backward()
+    xg = to_dev(xn, dev).requires_grad_(True)
+    torch.nn.functional.cross_entropy(m(xg), to_dev(yn, dev)).backward()
     assert xg.grad is not None and torch.isfinite(xg.grad).all()
     err, scale = (xg.grad.cpu().double() - xr.grad).abs().max().item(), xr.grad.abs().max().item()
     print(f"normalize dx: max error {err:.3e}, largest element {scale:.3e}")
@@ -1550,8 +1440,8 @@ def test_residual_extension_two_trial_backward_vs_oracle(nsd, dev, ref_state, B,
     loss_ref, g_ref, fw = orc.loss_and_grads(flat_np, xn, yn, D, residual=True, **masks)
     res = []
     for fused in (True, False):
-        out = _hip_step(nsd, dev, flat_np, xn, yn, fused, residual=True, **masks)
-        assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL and abs(float(out["loss"].sum()) / B - loss_ref) < 5e-5
-        _grad_close(out["grads"], g_ref, D, rtol=2e-4)
+        out = train_step(dev, spec_of(D), flat_np, xn, labels=yn, fused=fused, residual=True, masks=masks)
+        assert np.abs(out["logits"] - fw["logits"]).max() < LOGIT_TOL and abs(out["mean_loss"] - loss_ref) < LOSS_TOL
+        grad_close(out["grads"], g_ref, D, rtol=GRAD_RTOL_12)
         res.append(out["grads"])
     assert np.abs(res[0] - res[1]).max() <= 2e-5 * np.abs(res[0]).max()

@@ -11,7 +11,6 @@ prints its worst errors).
 4. the module: eval forward with grad, saliency, loss() with x.grad, normalize=True, retain_graph, cfg5-sized bidirectional;
 5. a NaN sample: what dx and the gradients are then.
 """
-import math
 
 import numpy as np
 import pytest
@@ -21,15 +20,15 @@ from oracle import nsd_oracle as orc
 from oracle.seq_bf16_ref import bf16_round_f32
 from oracle.torch_ref import TorchRefEEG
 from tests.golden.make_goldens import synth_labels, synth_params, synth_x
+from tests.gpu_harness import dev, nsd  # noqa: F401  (fixtures)
+from tests.seq_bf16_harness import DUAL_RTOL, EQUIV_RTOL, any_loss, duality, per_tensor, rel
 
 pytestmark = pytest.mark.gpu
 
-# Bounds: about 3x the worst value measured on one MI355X with this file run with -s (measured values beside them).
-EQUIV_RTOL = 3.5e-3              # measured 1.18e-3 (cfg5_t64, lstm.weight_ih_l0), 9.3e-4 (module x.grad): single bf16 roundings of
-                                 # da flip with the last-ulp difference between the fused head's (p - onehot) * scale and torch's
+# Bounds: about 3x the worst value measured on one MI355X with this file run with -s (measured values beside them); EQUIV_RTOL and
+# DUAL_RTOL, which other files use too, are in tests/seq_bf16_harness.py.
 REF_RTOL = 2.5e-2                # vs float64 autograd at bf16-rounded x and W, per tensor / max |tensor|: measured 9.2e-3 (normalize,
                                  # grads), 6.8e-3 (normalize, dx), 6.1e-3 (t1, dx), 5.9e-3 (fused_h64, attn.weight)
-DUAL_RTOL = 1e-5                 # measured 1.5e-8 (general_l3_res): fp32 accumulation order only
 RNG_SEED, RNG_BASE = 0x5EED0D1, 40
 
 # name -> (C, H, L, K, D, residual, B, T)
@@ -46,19 +45,6 @@ SHAPES = {
 REF_SHAPES = ["fused_h64", "fused_h256", "general_l1_bi", "general_l3_res", "wide_c40", "t1"]   # float64 CPU autograd affordable
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()
-    return nsd_amd
-
-
 def setup(name, dev, rng_on, seed=0):
     from nsd_amd import ops
     C, H, L, K, D, res, B, T = SHAPES[name]
@@ -73,32 +59,6 @@ def setup(name, dev, rng_on, seed=0):
     p = 0.4 if rng_on else None
     rng = dict(seed=RNG_SEED, base_stream=RNG_BASE, p_lstm=p, p_head=p) if rng_on else None
     return spec, st, flat, x, y, rng
-
-
-def rel(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max().clamp_min(1e-30))
-
-
-def per_tensor(spec, g, ref):
-    """per tensor: max |g - ref| / max |ref|.  attn.bias is left out: softmax over time is shift-invariant, so its true gradient is
-    0 and both sides are fp32 round-off (it is checked against attn.weight's scale instead)"""
-    offs, shapes = spec.offsets(), spec.shapes()
-    out = {n: rel(g[offs[n]:offs[n] + math.prod(shapes[n])], ref[offs[n]:offs[n] + math.prod(shapes[n])]) for n in spec.names() if n != "attn.bias"}
-    o, w = offs["attn.bias"], offs["attn.weight"]
-    out["attn.bias/|d attn.weight|"] = float((g[o].double() - ref[o].double()).abs() / ref[w:w + spec.D * spec.H].double().abs().max())
-    return out
-
-
-def any_loss(spec, flat, x, ws, dlogits_of, rng, want_dx=True):
-    """train_fwd_logits -> dlogits_of(logits) -> head_bwd -> train_bwd_dx: (logits, dlogits, grads, dx)"""
-    from nsd_amd import ops
-    B, T, _ = x.shape
-    logits = ops.seq_train_fwd_logits(spec, flat, x, ws, rng=rng)
-    dl = dlogits_of(logits).contiguous()
-    ops.seq_head_bwd(spec, flat, ws, dl, B, T, rng=rng)
-    dx = torch.empty_like(x) if want_dx else None
-    g = ops.seq_train_bwd(spec, flat, ws, B, T, rng=rng, dx=dx)
-    return logits, dl, g, dx
 
 
 @pytest.mark.parametrize("rng_on", [False, True])
@@ -175,20 +135,6 @@ def test_gaussian_dlogits_and_dx_against_float64_autograd(nsd, dev, name, rng_on
     print(f"[{name} rng={rng_on}] vs float64: logits {elg:.2e}  grads worst {worst[1]:.2e} ({worst[0]})  dx {edx:.2e}")
     assert worst[1] < REF_RTOL, errs
     assert edx < REF_RTOL, edx
-
-
-def duality(spec, flat, x, g, dx):
-    """(|sum_d <bf16(W_ih0_d), dW_ih0_d> - <bf16(x), dx>|, sum |W| |dW|)"""
-    offs, shapes = spec.offsets(), spec.shapes()
-    lhs, scale = 0.0, 0.0
-    for sfx in ("", "_reverse")[:spec.D]:
-        n = f"lstm.weight_ih_l0{sfx}"
-        w = bf16_round_f32(flat[offs[n]:offs[n] + math.prod(shapes[n])].contiguous()).double()
-        dw = g[offs[n]:offs[n] + math.prod(shapes[n])].double()
-        lhs += float((w * dw).sum())
-        scale += float((w.abs() * dw.abs()).sum())
-    rhs = float((bf16_round_f32(x.contiguous()).double() * dx.double()).sum())
-    return abs(lhs - rhs), scale
 
 
 @pytest.mark.parametrize("rng_on", [False, True])

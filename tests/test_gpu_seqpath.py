@@ -11,20 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_harness import dev, nsd  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()
-    return nsd_amd
 
 
 def _bf(a, dev):

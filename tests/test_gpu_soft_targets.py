@@ -11,39 +11,10 @@ import torch
 from oracle import nsd_oracle as orc
 from tests import mixup_ref as mr
 from tests.golden.make_goldens import synth_labels, synth_params, synth_x
-from tests.test_gpu_parity import FAST48, FP32_EXACT, LOGIT_TOL, _grad_close
+from tests.gpu_harness import (FAST48, FP32_EXACT, GRAD_RTOL_12, GRAD_RTOL_X4, LOGIT_TOL, LOSS_TOL, dev, grad_close, model_from_state, nsd,  # noqa: F401
+                               oracle_step, oracle_streams, soft_targets, sync_at_the_end, to_dev, train_step)
 
 pytestmark = pytest.mark.gpu
-
-LOSS_TOL = 5e-5                      # batch-mean loss, as tests/test_gpu_parity.py
-# gradients against the oracle, of each tensor's largest element (attn.bias 2e-6 absolute: _grad_close): what tests/test_gpu_parity.py
-# holds each kernel to -- the one- / two-trial H = 48 kernels 2e-4, the four-trial kernels (from 513 trials) 3e-4.  The first-generation
-# H = 32 kernels and the generic path are exact fp32 and take FP32_EXACT (LSTM weights 1e-5, others 2e-5: test_other_fast_path_shapes_vs_oracle,
-# test_generic_path_gradients_vs_oracle, tests/test_gpu_fp32_routes.py); measured here 3.8e-7 / 1.1e-6.
-GRAD_RTOL_12, GRAD_RTOL_X4 = 2e-4, 3e-4
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def nsd():
-    import nsd_amd
-    nsd_amd.load_library()
-    return nsd_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync_at_the_end():
-    yield
-    torch.cuda.synchronize()
-
-
-def _t(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def _bits(a):
@@ -66,14 +37,14 @@ def _mix_configs(K, seed):
 
 
 def _ops_mixup(ops, x, labels, K, rngs, dev, mix=0.0, eps=0.0, weights=None, **kw):
-    return ops.mixup(x, labels, K, rngs, label_smoothing=eps, mix=mix, class_weights=_t(weights, dev), **kw)
+    return ops.mixup(x, labels, K, rngs, label_smoothing=eps, mix=mix, class_weights=to_dev(weights, dev), **kw)
 
 
 @pytest.mark.parametrize("B,T,C,K", MIX_SHAPES)
 def test_mixup_kernel_equals_numpy_bitwise(nsd, dev, B, T, C, K):
     from nsd_amd import ops
     x_np, lab_np = synth_x(B, T, C, seed=B + T + C), synth_labels(B, K, seed=B + K)
-    x, lab = _t(x_np, dev), _t(lab_np, dev)
+    x, lab = to_dev(x_np, dev), to_dev(lab_np, dev)
     for i, kw in enumerate(_mix_configs(K, B + K)):
         seed, base = 0x9E3779B97F4A7C15 + 31 * i, 4 * (i + 1)
         y, tg = _ops_mixup(ops, x, lab, K, dict(seed=seed, base_stream=base), dev, **kw)
@@ -101,7 +72,7 @@ def test_mixup_models_in_one_launch(nsd, dev, B, T, C, K):
     pairs = [(r["seed"], r["base_stream"]) for r in rngs]
     xs_np = synth_x(3 * B, T, C, seed=7).reshape(3, B, T, C)
     lab_np = synth_labels(3 * B, K, seed=9).reshape(3, B)
-    xs, lab = _t(xs_np, dev), _t(lab_np.reshape(-1), dev)
+    xs, lab = to_dev(xs_np, dev), to_dev(lab_np.reshape(-1), dev)
     shared, tg_s = _ops_mixup(ops, xs[0].contiguous(), lab, K, rngs, dev, M=3, **kw)
     own, tg_o = _ops_mixup(ops, xs, lab, K, rngs, dev, **kw)
     ys_ref, tgs_ref = mr.mixup_models(xs_np[0], lab_np, K, pairs, **kw)
@@ -114,39 +85,9 @@ def test_mixup_models_in_one_launch(nsd, dev, B, T, C, K):
 
 
 # ---- 2. the fused H = 48 step against the oracle -------------------------------------------------------------------------------------------
-def _targets(B, K, seed):
-    """non-negative rows with sums != 1 and (B > 1) a zero row"""
-    q = (1.5 * np.random.RandomState(seed).rand(B, K)).astype(np.float32)
-    q[np.random.RandomState(seed + 1).rand(B, K) < 0.2] = 0.0
-    if B > 1:
-        q[1] = 0.0
-    return q
-
-
-def _oracle_streams(seed, sid, B, T, H, F, p=0.6):
-    return dict(drop_lstm=orc.dropout_mask(seed, sid, p, (1, B, T, H)), rrelu_slope=orc.rrelu_noise(seed, sid + 1, (B, F)),
-                drop_head=orc.dropout_mask(seed, sid + 2, p, (B, F)))
-
-
 def _soft_step(dev, spec, flat_np, x, q=None, labels=None, fused_head=True, rng=None, **masks):
-    """ops.train_step_grads with targets= (or labels) -> logits, per-trial loss, grads"""
-    from nsd_amd import ops
-    B, T, _ = x.shape
-    flat, xt = _t(flat_np, dev), _t(x, dev)
-    ws = ops.new_workspace(spec, B, T, dev)
-    ws.fill_(float("nan"))
-    logits = torch.full((B, spec.K), float("nan"), device=dev)
-    grads = torch.empty_like(flat)
-    ops.train_step_grads(spec, flat, xt, ws, _t(labels, dev), logits, grads, fused_head=fused_head, rng=rng, targets=_t(q, dev),
-                         **{k: _t(v, dev) for k, v in masks.items()})
-    return dict(logits=logits.cpu().numpy(), loss=ops.ws_view(ws, spec, B, T, "loss").cpu().numpy().copy(), grads=grads.cpu().numpy(),
-                loss_sum=float(ops.loss_sum(spec, ws, B, T).item()))
-
-
-def _oracle_soft(flat_np, x, q, d, **masks):
-    fw = orc.forward(flat_np, x, d, saves=True, **masks)
-    loss, dl = mr.soft_ce(fw["logits"], q, 1.0 / x.shape[0])
-    return fw["logits"], loss, orc.backward(flat_np, x, d, fw, dl.astype(np.float32), **masks)
+    """train_step with targets= (or labels) -> logits, per-trial loss, grads, loss_sum"""
+    return train_step(dev, spec, flat_np, x, labels=labels, targets=q, fused=fused_head, rng=rng, masks=masks)
 
 
 @pytest.mark.parametrize("K", [3, 8])
@@ -157,19 +98,19 @@ def test_fused_h48_soft_step_vs_oracle(nsd, dev, B, T, K):
     from nsd_amd import ops
     d, spec = orc.Dims(K=K), ops.ModelSpec(K=K)
     flat_np = orc.flatten_state(synth_params(8, 48, 2, K, seed=5 + K), d)
-    x, q = synth_x(B, T, seed=3 * B + T), _targets(B, K, seed=B + K)
+    x, q = synth_x(B, T, seed=3 * B + T), soft_targets(B, K, seed=B + K)
     seed, sid = 77 + B, 8
-    masks = _oracle_streams(seed, sid, B, T, 48, 32)
+    masks = oracle_streams(seed, sid, B, T, 48, 32)
     a = _soft_step(dev, spec, flat_np, x, q, **masks)
     r = _soft_step(dev, spec, flat_np, x, q, rng=dict(seed=seed, base_stream=sid, p_lstm=0.6, p_head=0.6))
     for k in ("logits", "loss", "grads"):
         assert np.isfinite(a[k]).all() and np.array_equal(_bits(a[k]), _bits(r[k])), k
-    lg_ref, loss_ref, g_ref = _oracle_soft(flat_np, x, q, d, **masks)
-    e_lg, e_loss = np.abs(a["logits"] - lg_ref).max(), abs(a["loss_sum"] / B - loss_ref.sum() / B)
-    print(f"soft step B={B} T={T} K={K}: logits {e_lg:.2e} loss {e_loss:.2e} per-trial loss {np.abs(a['loss'] - loss_ref).max():.2e}")
+    ref = oracle_step(d, flat_np, x, targets=q, masks=masks)
+    e_lg, e_loss = np.abs(a["logits"] - ref["logits"]).max(), abs(a["loss_sum"] / B - ref["loss"])
+    print(f"soft step B={B} T={T} K={K}: logits {e_lg:.2e} loss {e_loss:.2e} per-trial loss {np.abs(a['loss'] - ref['loss_per_trial']).max():.2e}")
     assert e_lg < LOGIT_TOL and e_loss < LOSS_TOL
     assert a["loss"][1] == 0.0                                      # a zero row contributes nothing
-    _grad_close(a["grads"], g_ref, d, rtol=GRAD_RTOL_X4 if B >= 513 else GRAD_RTOL_12)
+    grad_close(a["grads"], ref["grads"], d, rtol=GRAD_RTOL_X4 if B >= 513 else GRAD_RTOL_12)
 
 
 # ---- 3. one-hot targets reproduce the hard-label entry point -----------------------------------------------------------------------------
@@ -185,7 +126,7 @@ def test_one_hot_targets_reproduce_the_hard_label_step(nsd, dev, ref_state, B, T
     assert np.array_equal(_bits(hard["logits"]), _bits(soft["logits"]))
     print(f"one-hot B={B}: per-trial loss differs by {np.abs(hard['loss'] - soft['loss']).max():.2e}")
     assert np.abs(hard["loss"] - soft["loss"]).max() <= 1e-6
-    _grad_close(soft["grads"], hard["grads"], d, rtol=GRAD_RTOL_X4 if B >= 513 else GRAD_RTOL_12)
+    grad_close(soft["grads"], hard["grads"], d, rtol=GRAD_RTOL_X4 if B >= 513 else GRAD_RTOL_12)
 
 
 # ---- 4. cancellation ---------------------------------------------------------------------------------------------------------------------
@@ -235,15 +176,15 @@ def test_lstm_head_train_soft_outside_the_single_launch_shape(nsd, dev, C, H, L,
     d, spec = orc.Dims(C=C, H=H, L=L, K=K), ops.ModelSpec(C=C, H=H, L=L, K=K)
     assert not ops.rng_path(spec, B, T)
     flat_np = orc.flatten_state(synth_params(C, H, L, K, seed=H), d)
-    x, q = synth_x(B, T, C, seed=H), _targets(B, K, seed=H)
+    x, q = synth_x(B, T, C, seed=H), soft_targets(B, K, seed=H)
     masks = dict(rrelu_slope=orc.rrelu_noise(3, 1, (B, 32)), drop_head=orc.dropout_mask(3, 2, 0.6, (B, 32)))
     if L > 1:
         masks["drop_lstm"] = orc.dropout_mask(3, 0, 0.6, (L - 1, B, T, H))
     a = _soft_step(dev, spec, flat_np, x, q, **masks)
-    lg_ref, loss_ref, g_ref = _oracle_soft(flat_np, x, q, d, **masks)
-    assert np.abs(a["logits"] - lg_ref).max() < LOGIT_TOL and abs(a["loss_sum"] / B - loss_ref.sum() / B) < LOSS_TOL
+    ref = oracle_step(d, flat_np, x, targets=q, masks=masks)
+    assert np.abs(a["logits"] - ref["logits"]).max() < LOGIT_TOL and abs(a["loss_sum"] / B - ref["loss"]) < LOSS_TOL
     assert a["loss"][1] == 0.0
-    _grad_close(a["grads"], g_ref, d, **FP32_EXACT)
+    grad_close(a["grads"], ref["grads"], d, **FP32_EXACT)
     b = _soft_step(dev, spec, flat_np, x, q, fused_head=False, **masks)          # the two calls made by hand: the same launches
     for k in ("logits", "loss", "grads"):
         assert np.array_equal(_bits(a[k]), _bits(b[k])), k
@@ -259,9 +200,9 @@ def test_multi_train_fwd_soft_is_the_single_model_call_per_model(nsd, dev):
     P = spec.param_count
     params_np = np.stack([orc.flatten_state(synth_params(8, 48, 2, K, seed=40 + m), d) for m in range(M)])
     xs_np = synth_x(M * B, T, seed=6).reshape(M, B, T, 8)
-    q_np = _targets(M * B, K, seed=8)
+    q_np = soft_targets(M * B, K, seed=8)
     rngs = [dict(seed=100 + m, base_stream=4 * (m + 1), p_lstm=0.6, p_head=0.6) for m in range(M)]
-    params, xs, q = _t(params_np, dev), _t(xs_np, dev), _t(q_np, dev)
+    params, xs, q = to_dev(params_np, dev), to_dev(xs_np, dev), to_dev(q_np, dev)
     ws = ops.multi_workspace(spec, M, B, T, dev)
     grads = torch.empty((M, P), device=dev)
     logits = ops.multi_train_step(spec, params, xs, None, ws, grads, rngs=rngs, fuse_adam=False, targets=q)
@@ -272,9 +213,9 @@ def test_multi_train_fwd_soft_is_the_single_model_call_per_model(nsd, dev):
         assert np.array_equal(_bits(grads[m].cpu().numpy()), _bits(one["grads"])), m
         assert np.float32(losses[m]) == np.float32(one["loss_sum"]), m
     # and against the oracle, model 1
-    lg_ref, loss_ref, g_ref = _oracle_soft(params_np[1], xs_np[1], q_np[B:2 * B], d, **_oracle_streams(101, 8, B, T, 48, 32))
-    assert np.abs(logits.view(M, B, K)[1].cpu().numpy() - lg_ref).max() < LOGIT_TOL and abs(losses[1] / B - loss_ref.sum() / B) < LOSS_TOL
-    _grad_close(grads[1].cpu().numpy(), g_ref, d, rtol=GRAD_RTOL_12)
+    ref = oracle_step(d, params_np[1], xs_np[1], targets=q_np[B:2 * B], masks=oracle_streams(101, 8, B, T, 48, 32))
+    assert np.abs(logits.view(M, B, K)[1].cpu().numpy() - ref["logits"]).max() < LOGIT_TOL and abs(losses[1] / B - ref["loss"]) < LOSS_TOL
+    grad_close(grads[1].cpu().numpy(), ref["grads"], d, rtol=GRAD_RTOL_12)
 
 
 # ---- 7. the bf16 sequence path ---------------------------------------------------------------------------------------------------------------
@@ -289,10 +230,10 @@ def test_seq_train_fwd_soft_vs_the_any_loss_sequence(nsd, dev):
     from nsd_amd import ops
     B, T, K = 37, 5, 5
     spec, d = ops.ModelSpec(C=8, H=64, L=2, K=K), orc.Dims(C=8, H=64, L=2, K=K)
-    flat = _t(orc.flatten_state(synth_params(8, 64, 2, K, seed=1), d), dev)
-    x, y = _t(synth_x(B, T, seed=2), dev), _t(synth_labels(B, K, seed=2), dev)
-    q_np = _targets(B, K, seed=3)
-    q = _t(q_np, dev)
+    flat = to_dev(orc.flatten_state(synth_params(8, 64, 2, K, seed=1), d), dev)
+    x, y = to_dev(synth_x(B, T, seed=2), dev), to_dev(synth_labels(B, K, seed=2), dev)
+    q_np = soft_targets(B, K, seed=3)
+    q = to_dev(q_np, dev)
     rng = dict(seed=11, base_stream=8, p_lstm=0.6, p_head=0.6)
     ws = ops.seq_workspace(spec, B, T, dev)
     lg_hard = ops.seq_train_fwd(spec, flat, x, y, ws, rng=rng).clone()
@@ -304,7 +245,7 @@ def test_seq_train_fwd_soft_vs_the_any_loss_sequence(nsd, dev):
     lg = ops.seq_train_fwd_logits(spec, flat, x, ws, rng=rng)
     assert torch.equal(lg, lg_soft)
     loss_ref, dl = mr.soft_ce(lg.cpu().numpy(), q_np, 1.0 / B)
-    ops.seq_head_bwd(spec, flat, ws, _t(dl.astype(np.float32), dev), B, T, rng=rng)
+    ops.seq_head_bwd(spec, flat, ws, to_dev(dl.astype(np.float32), dev), B, T, rng=rng)
     g_any = ops.seq_train_bwd(spec, flat, ws, B, T, rng=rng)
     print(f"bf16 soft loss {loss:.6f} vs float64 {loss_ref.sum() / B:.6f}")
     assert abs(loss - loss_ref.sum() / B) < LOSS_TOL
@@ -341,7 +282,7 @@ def _batch(dev, B, T, seed):
 
 def _ref_mix(x: torch.Tensor, y: torch.Tensor, loss, seed, step, dev):
     xm, tg = mr.mixup(x.cpu().numpy(), y.cpu().numpy(), 3, seed, 4 * step, mix=loss.mixup, eps=loss.label_smoothing, weights=loss.class_weights)
-    return _t(xm, dev), _t(tg, dev)
+    return to_dev(xm, dev), to_dev(tg, dev)
 
 
 @pytest.mark.parametrize("case", ["fp32", "fp32_normalize_augment", "bf16_h64"])
@@ -440,20 +381,19 @@ def test_trainer_step_with_loss_matches_oracle(nsd, dev, ref_state):
     """One Trainer.step with smoothing + weights + mixup == oracle forward / backward with the step's counter-based masks on the
     restatement's mixed windows and targets, + oracle Adam: the bounds of test_trainer_step_matches_oracle_with_its_own_streams."""
     from nsd_amd.trainer import Trainer
-    from tests.test_gpu_parity import _model as ref_model
     d = orc.Dims()
-    m = ref_model(nsd, dev, ref_state).train()
+    m = model_from_state(nsd, dev, ref_state).train()
     Ls = nsd.Loss(label_smoothing=0.1, class_weights=W3, mixup=1.0)
     tr = Trainer(m, lr=1e-3, seed=7, loss=Ls)
     B, T = 12, 40
     x, y = synth_x(B, T, seed=4), synth_labels(B, seed=4)
     flat0 = orc.flatten_state(ref_state, d)
-    tr.step(_t(x, dev), _t(y, dev))
+    tr.step(to_dev(x, dev), to_dev(y, dev))
     xm, q = mr.mixup(x, y, 3, tr.seed, 4, mix=1.0, eps=0.1, weights=W3)
-    masks = _oracle_streams(tr.seed, 4, B, T, 48, 32)
-    _, loss_ref, g_ref = _oracle_soft(flat0, xm, q, d, **masks)
-    assert abs(tr.last_loss() - loss_ref.sum() / B) < LOSS_TOL
-    _grad_close(tr.grads.cpu().numpy(), g_ref, d, **FAST48)
+    masks = oracle_streams(tr.seed, 4, B, T, 48, 32)
+    ref = oracle_step(d, flat0, xm, targets=q, masks=masks)
+    assert abs(tr.last_loss() - ref["loss"]) < LOSS_TOL
+    grad_close(tr.grads.cpu().numpy(), ref["grads"], d, **FAST48)
     p, mm, vv = flat0.copy(), np.zeros_like(flat0), np.zeros_like(flat0)
     orc.adam(p, tr.grads.cpu().numpy(), mm, vv, lr=1e-3, step=1)
     assert np.abs(m.flat_parameters().cpu().numpy() - p).max() < 2e-6

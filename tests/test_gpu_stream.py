@@ -18,24 +18,18 @@ from tests import sharp_attention as sa
 from tests import stream_ref as sr
 from tests.buffer_contract import guarded
 from tests.golden.make_goldens import synth_params, synth_x
-from tests.test_gpu_parity import LOGIT_TOL, D, _t, _write_pth, dev, nsd  # noqa: F401  (dev, nsd: fixtures)
+from tests.gpu_harness import LOGIT_TOL, NAN, PROB_TOL, D, dev, nsd, spec_of, to_dev, write_pth  # noqa: F401  (dev, nsd: fixtures)
 
 pytestmark = pytest.mark.gpu
 
-PROB_TOL, ROW_SUM_TOL, ARGMAX_GAP = 1e-5, 1e-6, 1e-3
+ROW_SUM_TOL, ARGMAX_GAP = 1e-6, 1e-3
 H_TOL, C_TOL, POOLED_TOL = 2e-5, 5e-5, 2e-5
 T41, B41 = 41, 3
-NAN = float("nan")
 
 
 # ---------------------------------------------------------------------------------------------------
 # helpers
 # ---------------------------------------------------------------------------------------------------
-def _spec(d):
-    from nsd_amd import ops
-    return ops.ModelSpec(C=d.C, H=d.H, L=d.L, K=d.K, F=d.F)
-
-
 def _new_state(dev, spec, S):
     """S slots, NaN-filled, then reset through the library"""
     from nsd_amd import ops
@@ -127,9 +121,9 @@ def _whole_run(dev, name, ref_state):
     """the single 41-step call of a variant: final state bytes, logits, probs"""
     if name not in _whole:
         d, residual, flat, x, _ = _case(name, ref_state)
-        spec = _spec(d)
+        spec = spec_of(d)
         state = _new_state(dev, spec, B41)
-        lg, pr = _run_cut(dev, spec, _t(flat, dev), _t(x, dev), [T41], state, residual=residual)
+        lg, pr = _run_cut(dev, spec, to_dev(flat, dev), to_dev(x, dev), [T41], state, residual=residual)
         _whole[name] = (state.cpu().numpy().tobytes(), lg.tobytes(), pr.tobytes())
     return _whole[name]
 
@@ -141,7 +135,7 @@ def _whole_run(dev, name, ref_state):
 @pytest.mark.parametrize("name", list(VARIANTS))
 def test_every_prefix_matches_the_oracle_and_the_cut_does_not_show(nsd, dev, ref_state, name, cut):
     d, residual, flat_np, xn, refs = _case(name, ref_state)
-    spec, flat, x = _spec(d), _t(flat_np, dev), _t(xn, dev)
+    spec, flat, x = spec_of(d), to_dev(flat_np, dev), to_dev(xn, dev)
     state = _new_state(dev, spec, B41)
 
     def each(t, lg, pr):
@@ -157,9 +151,9 @@ def test_every_prefix_matches_the_oracle_and_the_cut_does_not_show(nsd, dev, ref
 @pytest.mark.parametrize("cut", sr.CUTS_41[:3], ids=["ones", "fib", "40+1"])
 def test_advance_only_calls_end_in_the_same_bits(nsd, dev, ref_state, cut):
     d, residual, flat_np, xn, refs = _case("ref", ref_state)
-    spec = _spec(d)
+    spec = spec_of(d)
     state = _new_state(dev, spec, B41)
-    lg, pr = _run_cut(dev, spec, _t(flat_np, dev), _t(xn, dev), cut, state, read_all=False)
+    lg, pr = _run_cut(dev, spec, to_dev(flat_np, dev), to_dev(xn, dev), cut, state, read_all=False)
     sb, lb, pb = _whole_run(dev, "ref", ref_state)
     assert state.cpu().numpy().tobytes() == sb and lg.tobytes() == lb and pr.tobytes() == pb, cut
 
@@ -167,7 +161,7 @@ def test_advance_only_calls_end_in_the_same_bits(nsd, dev, ref_state, cut):
 def test_slot_and_batch_invariance(nsd, dev, ref_state):
     """Stream 1 alone in slot 5 of S = 8 == its row when advanced with two others under a permuted slots array; unnamed slots untouched."""
     d, _, flat_np, xn, refs = _case("ref", ref_state)
-    spec, flat, x = _spec(d), _t(flat_np, dev), _t(xn, dev)
+    spec, flat, x = spec_of(d), to_dev(flat_np, dev), to_dev(xn, dev)
     cut, S = [7, 9, 25], 8
     perm = torch.tensor([6, 5, 2], dtype=torch.int32, device=dev)
     together = _new_state(dev, spec, S)
@@ -188,10 +182,10 @@ def test_slot_and_batch_invariance(nsd, dev, ref_state):
 
 def test_more_streams_than_compute_units(nsd, dev, ref_state):
     """multi_processor_count + 2 streams, chunks of 7 and 9: two workgroups load a second stream's state and walk the loop again."""
-    spec = _spec(D)
+    spec = spec_of(D)
     B = torch.cuda.get_device_properties(dev).multi_processor_count + 2
     flat_np, xn = orc.flatten_state(ref_state, D), synth_x(B, 16, seed=1607)
-    flat, x = _t(flat_np, dev), _t(xn, dev)
+    flat, x = to_dev(flat_np, dev), to_dev(xn, dev)
     state = _new_state(dev, spec, B)
     lg7, pr7 = _step(dev, spec, flat, x[:, :7], state)
     _check_outputs(lg7, pr7, orc.forward(flat_np, np.ascontiguousarray(xn[:, :7]), D), ("B", B, "t", 7))
@@ -210,11 +204,11 @@ def test_more_streams_than_compute_units(nsd, dev, ref_state):
 
 def test_a_stream_longer_than_the_one_shot_limit(nsd, dev, ref_state):
     """1300 samples as ten chunks of 125 and one of 50 (ops.infer leaves its fast path above T = 1024)."""
-    spec, B, T = _spec(D), 2, 1300
+    spec, B, T = spec_of(D), 2, 1300
     flat_np, xn = orc.flatten_state(ref_state, D), synth_x(B, T, seed=1300)
     ref = orc.forward(flat_np, xn, D, saves=True)
     state = _new_state(dev, spec, B)
-    lg, pr = _run_cut(dev, spec, _t(flat_np, dev), _t(xn, dev), [125] * 10 + [50], state, read_all=False)
+    lg, pr = _run_cut(dev, spec, to_dev(flat_np, dev), to_dev(xn, dev), [125] * 10 + [50], state, read_all=False)
     _check_outputs(lg, pr, ref, ("T", T))
     _check_state(spec, state, ref, T, ("T", T))
 
@@ -223,7 +217,7 @@ def test_a_stream_longer_than_the_one_shot_limit(nsd, dev, ref_state):
 @pytest.mark.parametrize("T", [17, 64])
 def test_peaked_attention_in_chunks_of_five(nsd, dev, T, s):
     """attn.weight times 100 / 1000: the running max rises along the stream and the sums are rescaled by exp(-large)."""
-    spec, B = _spec(D), sa.SHARP_B
+    spec, B = spec_of(D), sa.SHARP_B
     flat_np, xn = orc.flatten_state(sa.sharp_state(s), D), sa.sharp_inputs(B, T)[0]
     cut = [5] * (T // 5) + ([T % 5] if T % 5 else [])
     refs = sr.prefix_refs(flat_np, xn, D, sr.cut_points(cut))
@@ -235,7 +229,7 @@ def test_peaked_attention_in_chunks_of_five(nsd, dev, T, s):
         _check_state(spec, state, refs[t], t, ("sharp", s, "t", t))
         seen.append(_fields(spec, state.cpu().numpy())["max"].copy())
 
-    _run_cut(dev, spec, _t(flat_np, dev), _t(xn, dev), cut, state, each=each)
+    _run_cut(dev, spec, to_dev(flat_np, dev), to_dev(xn, dev), cut, state, each=each)
     if s == sa.S_SAT:                                           # the oracle's own alphas: the case does rescale by a vanishing factor
         assert sa.spread(refs[T]["alpha"]) > 40.0              # exp(-40) = 4e-18
     assert (np.diff(np.stack(seen), axis=0) >= 0).all() and (np.stack(seen)[-1] > np.stack(seen)[0]).any()
@@ -247,7 +241,7 @@ def test_peaked_attention_in_chunks_of_five(nsd, dev, T, s):
 def test_reset_of_one_slot_restarts_it(nsd, dev, ref_state):
     from nsd_amd import ops
     d, _, flat_np, xn, refs = _case("ref", ref_state)
-    spec, flat, x = _spec(d), _t(flat_np, dev), _t(xn, dev)
+    spec, flat, x = spec_of(d), to_dev(flat_np, dev), to_dev(xn, dev)
     state = _new_state(dev, spec, B41)
     _step(dev, spec, flat, x[:, :13], state, read=False)
     ops.stream_reset(spec, state, torch.tensor([1], dtype=torch.int32, device=dev))
@@ -267,7 +261,7 @@ def test_reset_of_one_slot_restarts_it(nsd, dev, ref_state):
 def test_a_slot_index_outside_the_state_gives_nan_rows_and_touches_nothing(nsd, dev, ref_state):
     from nsd_amd import ops
     d, _, flat_np, xn, refs = _case("ref", ref_state)
-    spec, flat, x = _spec(d), _t(flat_np, dev), _t(xn, dev)
+    spec, flat, x = spec_of(d), to_dev(flat_np, dev), to_dev(xn, dev)
     S = 4
     state, check = guarded((S, int(ops.stream_layout(spec).stride)), torch.float32, dev, "nan32")
     ops.stream_reset(spec, state)
@@ -290,12 +284,12 @@ def test_a_slot_index_outside_the_state_gives_nan_rows_and_touches_nothing(nsd, 
 def test_a_nan_sample_poisons_its_stream_until_reset(nsd, dev, ref_state):
     from nsd_amd import ops
     d, _, flat_np, xn, refs = _case("ref", ref_state)
-    spec, flat = _spec(d), _t(flat_np, dev)
+    spec, flat = spec_of(d), to_dev(flat_np, dev)
     for poison in (np.nan, np.inf):
         xb = xn.copy()
         xb[1, 4, 2] = poison
         clean, dirty = _new_state(dev, spec, B41), _new_state(dev, spec, B41)
-        x, xd = _t(xn, dev), _t(xb, dev)
+        x, xd = to_dev(xn, dev), to_dev(xb, dev)
         lc, pc = _run_cut(dev, spec, flat, x, [9, 32], clean)
         lg9, pr9 = _step(dev, spec, flat, xd[:, :9], dirty)
         lg, pr = _step(dev, spec, flat, xd[:, 9:], dirty)                   # clean samples: still NaN
@@ -317,7 +311,7 @@ def test_a_nan_sample_poisons_its_stream_until_reset(nsd, dev, ref_state):
 def test_side_stream_and_graph_replay_give_the_same_bits(nsd, dev, ref_state):
     from nsd_amd import ops
     d, _, flat_np, xn, refs = _case("ref", ref_state)
-    spec, flat, x = _spec(d), _t(flat_np, dev), _t(xn, dev)
+    spec, flat, x = spec_of(d), to_dev(flat_np, dev), to_dev(xn, dev)
     sb, lb, pb = _whole_run(dev, "ref", ref_state)
     side = torch.cuda.Stream(device=dev)
     state = _new_state(dev, spec, B41)
@@ -362,11 +356,11 @@ def _eval_model(nsd, dev, ref_state, **kw):
 def test_stream_decoder_push_equals_predict_proba(nsd, dev, ref_state, residual):
     d, _, flat_np, xn, _ = _case("ref", ref_state)
     model = _eval_model(nsd, dev, ref_state, residual=residual)
-    whole = model.predict_proba(_t(xn, dev)).cpu().numpy()
+    whole = model.predict_proba(to_dev(xn, dev)).cpu().numpy()
     ref = orc.forward(flat_np, xn, D, residual=residual)
     dec = nsd.StreamDecoder(model, streams=4)
     assert dec.push(xn[:, :10], read=False) is None
-    p = dec.push(_t(xn[:, 10:25], dev))
+    p = dec.push(to_dev(xn[:, 10:25], dev))
     assert tuple(p.shape) == (3, 3) and p.is_cuda
     p = dec.push(xn[:, 25:]).cpu().numpy()
     assert list(dec.steps) == [T41, T41, T41, 0]
@@ -414,7 +408,7 @@ class _WindowFilter:
 
 def test_open_stream_and_chunked_run_trials(nsd, dev, golden, ref_state, tmp_path, capsys):
     g = golden("real_trials")
-    pth = _write_pth(str(tmp_path), ref_state)
+    pth = write_pth(str(tmp_path), ref_state)
     names = ["Food", "Water", "None"]
     filt = nsd.SimplePredictor(pth, sr=125, device="cpu", class_names=names, preprocess=_WindowFilter())
     with pytest.raises(nsd.NsdError, match="not causal"):

@@ -4,37 +4,16 @@ The model-batched one-trial forward is at its SGPR limit: one more live scalar i
 kernel-argument SGPRs, which leaves a 68-byte private segment and makes every dispatch set up scratch (profiles/h48_step_census.md).
 The sizes are read from the code-object notes of the objects the build leaves beside the sources; an object that is not there is
 compiled device-only with the Makefile's flags."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "neural-speech-decoding_amd", "csrc")
-ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
-LLVM = os.path.join(ROCM, "llvm", "bin")
-TARGET = "--targets=hip-amdgcn-amd-amdhsa--gfx950"
-
-
-def _device_elf(name, tmp):
-    obj, elf = os.path.join(CSRC, name + ".o"), os.path.join(tmp, name + ".elf")
-    run = lambda *c: subprocess.run(c, check=True, capture_output=True, text=True, cwd=CSRC)
-    src = os.path.join(CSRC, name + ".hip")
-    if os.path.exists(obj) and os.path.getmtime(obj) >= os.path.getmtime(src):
-        fat = os.path.join(tmp, name + ".fatbin")
-        run(os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, os.path.join(tmp, name + ".copy.o"))
-    else:
-        flags = re.search(r"^FLAGS\s*\?=\s*(.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).replace("$(ARCH)", "gfx950")
-        fat = os.path.join(tmp, name + ".co")
-        run(os.path.join(ROCM, "bin", "hipcc"), *flags.split(), "--cuda-device-only", "-c", name + ".hip", "-o", fat)
-    run(os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", TARGET, "--input=" + fat, "--output=" + elf)
-    return run(os.path.join(LLVM, "llvm-readelf"), "--notes", elf).stdout
+from tests.code_object import device_elf
 
 
 @pytest.mark.parametrize("name", ["nsd_lstm2_fwd48", "nsd_lstm2_multi_fwd48"])
 def test_forward_kernels_have_no_private_segment(name, tmp_path):
-    notes = _device_elf(name, str(tmp_path))
+    notes = device_elf(name, str(tmp_path))
     sizes = {}
     for block in re.split(r"^\s*- \.agpr_count:", notes, flags=re.M)[1:]:
         kv = dict(re.findall(r"^\s*(\.[a-z_]+):\s*(.+?)\s*$", block, re.M))

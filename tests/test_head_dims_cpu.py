@@ -15,42 +15,11 @@ from nsd_amd import _lib, ops
 from oracle import nsd_oracle as orc
 from oracle import seq_bf16_ref as sr
 from oracle.torch_ref import TorchRefEEG
-from tests.golden.make_goldens import counter_masks, synth_labels, synth_params, synth_x
+from tests.gpu_harness import BASE_SHAPES, KINK_MARGIN, head_inputs, kink_margin
 
 F_GRID = (1, 7, 31, 32, 33, 48, 63, 64, 65)
 K_GRID = (1, 2, 3, 8, 9, 33, 64, 65)
-# (C, H, K, F, B, T), L = 2: the shapes of tests/test_gpu_head_dims.py
-BASE_SHAPES = [(8, 48, 3, 32, 6, 20), (8, 48, 8, 64, 5, 33), (8, 48, 9, 33, 5, 33), (8, 48, 64, 1, 4, 12),
-               (5, 48, 1, 17, 4, 12), (8, 64, 33, 48, 6, 15), (8, 32, 5, 7, 6, 15), (8, 48, 2, 63, 7, 40)]
-KINK_MARGIN = 1e-4               # 100x the fp32 forward error the GPU suite measures on fc.0's pre-activation
 _FAKE = 4096                     # a pointer that is never dereferenced: every call it is passed to is refused before a launch
-
-
-def kink_safe(st, F):
-    """fc.0.bias = +-4, alternating (the convention of tests/test_gpu_seqpath_bf16ref.py): for batches of hundreds of trials, where
-    no seed keeps tens of thousands of fc.0 pre-activations 1e-4 away from the RReLU kink.  Both slopes stay in use."""
-    st = dict(st)
-    st["fc.0.bias"] = np.where(np.arange(F) % 2 == 0, 4.0, -4.0).astype(np.float32)
-    return st
-
-
-def head_inputs(Cc, H, K, F, B, T, L=2, safe=False):
-    """(dims, flat parameters, x, labels, masks) of a shape: every input from the generators of tests/golden/make_goldens.py
-    (safe: fc.0.bias replaced by kink_safe's)"""
-    d = orc.Dims(C=Cc, H=H, L=L, K=K, F=F)
-    st = synth_params(Cc, H, L, K, F=F, seed=H + F + K)
-    flat = orc.flatten_state(kink_safe(st, F) if safe else st, d)
-    x, y = synth_x(B, T, C=Cc, seed=F), synth_labels(B, K=K, seed=K)
-    dl, sl, dh = counter_masks(B, T, H, F, L=L, seed=F + K)
-    masks = dict(rrelu_slope=sl, drop_head=dh)
-    if L > 1:
-        masks["drop_lstm"] = dl
-    return d, flat, x, y, masks
-
-
-def kink_margin(fw):
-    """smallest |fc.0 pre-activation| of the ORACLE's forward: the distance of the data from the RReLU kink"""
-    return float(np.abs(fw["fc0_pre"]).min())
 
 
 # ---- parameter count and layout ---------------------------------------------------------------------------------------------------

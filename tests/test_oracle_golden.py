@@ -6,9 +6,7 @@ import pytest
 from oracle import nsd_oracle as orc
 from tests.golden.make_goldens import (CFG3_STRIDE, SYNTH_SHAPES, counter_masks, synth_labels,
                                        synth_params, synth_x)
-
-D = orc.Dims()          # C=8,H=48,L=2,K=3,F=32
-LOGIT_TOL = 1e-4        # north_star: class logits within 1e-4 fp32, argmax bit-exact
+from tests.gpu_harness import LOGIT_TOL, D       # north_star: class logits within 1e-4 fp32, argmax bit-exact; C=8,H=48,L=2,K=3,F=32
 
 
 def test_param_layout_matches_reference_state_dict(ref_state):

@@ -7,7 +7,7 @@ import torch
 
 from oracle import nsd_oracle as orc
 from oracle import seq_bf16_ref as sr
-from tests import test_gpu_seqpath_bf16ref as gp
+from tests import seq_bf16_harness as gp
 from tests.golden.make_goldens import BIDIR_CASES, synth_labels, synth_params, synth_x
 
 

@@ -14,7 +14,7 @@ import nsd_amd
 from nsd_amd import _lib, ops, train
 from tests import augment_ref as ar
 from tests import mixup_ref as mr
-from tests.test_augment_cpu import _parse
+from tests.train_cli import parse_train_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_INVALID, E_WS = -1, -3
@@ -274,12 +274,12 @@ def test_balanced_weights_on_the_packed_three_class_fixture():
 
 
 def test_cli_loss_flags_parse(monkeypatch):
-    seen = _parse(["--synthetic", "16", "--label-smoothing", "0.1", "--class-weights", "balanced", "--mixup", "0.5"], monkeypatch)
+    seen = parse_train_args(["--synthetic", "16", "--label-smoothing", "0.1", "--class-weights", "balanced", "--mixup", "0.5"], monkeypatch)
     a = seen["args"]
     assert (a.label_smoothing, a.class_weights, a.mixup) == (0.1, "balanced", 0.5) and seen.get("reached_device")
-    a = _parse(["--synthetic", "16", "--class-weights", "1,2,0.5", "--kfold", "5", "--concurrent"], monkeypatch)["args"]
+    a = parse_train_args(["--synthetic", "16", "--class-weights", "1,2,0.5", "--kfold", "5", "--concurrent"], monkeypatch)["args"]
     assert a.class_weights == "1,2,0.5" and train.loss_for(a, np.array([0, 1, 2])).class_weights == (1.0, 2.0, 0.5)
-    d = _parse(["--synthetic", "16"], monkeypatch)["args"]
+    d = parse_train_args(["--synthetic", "16"], monkeypatch)["args"]
     assert (d.label_smoothing, d.class_weights, d.mixup) == (0.0, None, 0.0) and not train.loss_for(d, np.array([0, 1, 2])).enabled
 
 
@@ -287,5 +287,5 @@ def test_cli_loss_flags_parse(monkeypatch):
                                  ["--class-weights", "1,2"], ["--class-weights", "x"], ["--class-weights", "1,-1,1"]])
 def test_cli_loss_out_of_range_is_an_argparse_error_before_any_device(bad, monkeypatch, capsys):
     with pytest.raises(SystemExit) as e:
-        _parse(["--synthetic", "16"] + bad, monkeypatch)
+        parse_train_args(["--synthetic", "16"] + bad, monkeypatch)
     assert e.value.code == 2 and "error:" in capsys.readouterr().err

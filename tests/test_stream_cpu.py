@@ -15,7 +15,7 @@ from nsd_amd.streaming_process import SAMPLING_RATE, StreamingProcess, synthetic
 from oracle import nsd_oracle as orc
 from tests import stream_ref as sr
 from tests.golden.make_goldens import synth_x
-from tests.test_h48_private_segments_cpu import _device_elf
+from tests.code_object import device_elf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STREAM_SYMBOLS = ("nsd_stream_path", "nsd_stream_state_bytes", "nsd_stream_state_layout", "nsd_stream_reset", "nsd_stream_step")
@@ -194,7 +194,7 @@ def test_stream_decoder_needs_the_gpu_and_says_so():
 
 
 def test_stream_kernels_have_no_private_segment(tmp_path):
-    notes = _device_elf("nsd_stream48", str(tmp_path))
+    notes = device_elf("nsd_stream48", str(tmp_path))
     sizes = {}
     for block in re.split(r"^\s*- \.agpr_count:", notes, flags=re.M)[1:]:
         kv = dict(re.findall(r"^\s*(\.[a-z_]+):\s*(.+?)\s*$", block, re.M))
