@@ -487,6 +487,56 @@ int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, cons
                     int64_t state_bytes, int32_t S, float *logits, float *probs, void *stream);
 
 /*
+ * ---- causal front end for live streams and their training (an EXTENSION: the reference filters whole windows on the host) ----
+ *
+ * A per-channel transform that can run chunk by chunk in front of nsd_stream_step, and over whole windows in a training step, so that a
+ * model is trained on what a live stream can deliver.  For one stream, n = samples since the slot's reset (it lives in the state), c the
+ * channel, x[n,c] the raw sample.  Every fp32 operation rounds on its own (no FMA contraction); sqrt and / are the correctly rounded
+ * ones.  Four steps, in this order, each SKIPPED when it is off (all off: y is a bitwise copy of x):
+ *   NSD_PREP_BASELINE  at n == 0: x0[c] = x[0,c] (kept in the state);  v = x[n,c] - x0[c]                  (without the flag v = x[n,c])
+ *   NSD_PREP_CAR       m = (((v[0] + v[1]) + v[2]) + ...) over c = 0 .. C-1, serially;  v = v - m / float(C)
+ *   sections           n_sections in [0, NSD_PREP_MAX_SECTIONS], sos[s] = {b0, b1, b2, a1, a2} (a0 = 1), the same for all channels;
+ *                      direct form II transposed from rest, in order:  y = b0*v + z1;  z1 = (b1*v - a1*y) + z2;  z2 = b2*v - a2*y;  v = y
+ *   running z-score    alpha > 0, oma = 1.0f - alpha.  At n == 0: mu = v, var = var0; otherwise d = v - mu, mu = mu + alpha*d,
+ *                      var = oma * (var + (alpha*d)*d).  Output (v - mu) / (sqrt(var) + 1e-6f) with the updated mu and var.
+ * The baseline comes first because the sections lose the signal under a DC offset of raw amplifier size (fp32 against float64 on a
+ * 1-40 Hz band-pass + notch with offsets up to 2e5: 1.3e-2 of the largest output without it, 3.7e-3 with it behind the common average,
+ * below 1e-5 in this order).  Every sample runs the same operations wherever it falls in a chunk: the state after n samples, and every
+ * output, is bit for bit a function of the samples alone -- not of the cut, the slot, the other streams of the call, the HIP stream or a
+ * graph replay.  Non-finite samples propagate by the arithmetic: a poisoned channel stays NaN until its slot is reset, and with the
+ * common average every channel of that stream is poisoned; other streams are unaffected.
+ *   nsd_prep_path          1 where nsd_prep_step covers C channels with the configuration p (p == NULL: C alone), else 0
+ *   nsd_prep_state_bytes   bytes of a state of S >= 1 slots (S * stride * 4); <0 for C outside [1, 64] or S < 1
+ *   nsd_prep_state_layout  float offsets inside a slot: x0[C], z[NSD_PREP_MAX_SECTIONS][2][C] (z1 then z2 of each section), mu[C],
+ *                          var[C]; `steps`: the float offset of the slot's int64 sample count (8-byte aligned); `stride`: floats per
+ *                          slot.  The layout holds room for the maximum number of sections and depends on C only: a slot can be
+ *                          checkpointed and restored by copying its stride floats.
+ *   nsd_prep_reset         slots == NULL: all S slots; else the n slots of the DEVICE array slots[n] (indices outside [0, S) are
+ *                          skipped).  A reset slot is all zero.  A state is reset once before its first nsd_prep_step.
+ *   nsd_prep_step          x, y [B,T,C] (of d only B, T, C are read); y == x (in place) is allowed, a partial overlap is refused.
+ *     stream mode (state != NULL): d->B streams advance by d->T samples; slots: DEVICE int32[B] of distinct indices, or NULL for
+ *       0 .. B-1.  A slot index outside [0, S) is skipped and its rows of y are NaN.  No host synchronisation, no allocation; nothing in
+ *       the arguments changes from call to call, so the call can be captured and replayed in front of nsd_stream_step.
+ *     window mode (state == NULL, slots == NULL, S ignored): every trial starts from a reset state and nothing is stored.
+ * NSD_E_INVALID before any launch: NULL d / p / x / y; C outside [1, 64]; T < 1; B < 0; B > S or S < 1 (stream mode); slots without a
+ * state; unknown flag bits; n_sections outside [0, NSD_PREP_MAX_SECTIONS]; a coefficient that is not finite; an unstable section (stable:
+ * |a2| < 1 and |a1| < 1 + a2); alpha outside [0, 1); var0 not finite, or var0 <= 0 while alpha > 0; partially overlapping x / y.
+ * NSD_E_WORKSPACE: state_bytes < nsd_prep_state_bytes(C, S).  B = 0 (n = 0) launches nothing.  Additive: NSD_VERSION stays 301, a caller
+ * detects the feature by the symbols.
+ */
+#define NSD_PREP_MAX_SECTIONS 4
+#define NSD_PREP_BASELINE 1u
+#define NSD_PREP_CAR      2u
+typedef struct nsd_prep { uint32_t flags; int32_t n_sections; float sos[NSD_PREP_MAX_SECTIONS][5]; float alpha, var0; } nsd_prep;
+typedef struct nsd_prep_layout { int64_t x0, z, mu, var, steps, stride; } nsd_prep_layout;   /* float offsets in a slot; depends on C only */
+int     nsd_prep_path(int32_t C, const nsd_prep *p);
+int64_t nsd_prep_state_bytes(int32_t C, int32_t S);
+int     nsd_prep_state_layout(int32_t C, nsd_prep_layout *out);
+int     nsd_prep_reset(int32_t C, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream);
+int     nsd_prep_step(const nsd_dims *d, const nsd_prep *p, const float *x, const int32_t *slots,
+                      void *state, int64_t state_bytes, int32_t S, float *y, void *stream);
+
+/*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----
  *
  * Building block, exported so that it can be tested and timed on its own: C[M,N] = A . B with bf16 operands (device

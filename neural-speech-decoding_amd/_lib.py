@@ -71,6 +71,19 @@ class StreamLayout(C.Structure):
                 + [(n, C.c_int64) for n in ("pool_max", "pool_den", "pool_acc", "steps", "stride")])
 
 
+class Prep(C.Structure):
+    """nsd_prep of include/nsd.h"""
+    _fields_ = [("flags", C.c_uint32), ("n_sections", C.c_int32), ("sos", (C.c_float * 5) * 4), ("alpha", C.c_float), ("var0", C.c_float)]
+
+
+class PrepLayout(C.Structure):
+    """nsd_prep_layout of include/nsd.h: float offsets inside one slot of a prep state"""
+    _fields_ = [(n, C.c_int64) for n in ("x0", "z", "mu", "var", "steps", "stride")]
+
+
+NSD_PREP_MAX_SECTIONS, NSD_PREP_BASELINE, NSD_PREP_CAR = 4, 1, 2
+
+
 class WsLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("hseq", "cseq", "gact", "inseq", "top", "alpha", "pooled", "fc0_pre",
                                           "dscore", "dpooled", "loss", "adpack", "slabs", "n_slabs", "hslabs", "da_seq", "din", "total")]
@@ -159,6 +172,12 @@ SYMBOLS = {
     "nsd_stream_state_layout": (C.c_int, [_dp, C.POINTER(StreamLayout)]),
     "nsd_stream_reset": (C.c_int, [_dp, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
     "nsd_stream_step": (C.c_int, [_dp, _fp, _fp, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _vp]),
+    # causal front end for live streams and their training
+    "nsd_prep_path": (C.c_int, [C.c_int32, _vp]),
+    "nsd_prep_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "nsd_prep_state_layout": (C.c_int, [C.c_int32, C.POINTER(PrepLayout)]),
+    "nsd_prep_reset": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
+    "nsd_prep_step": (C.c_int, [_dp, _vp, _fp, _ip, _vp, C.c_int64, C.c_int32, _fp, _vp]),
 }
 NSD_MAX_MODELS = 32
 

@@ -1019,4 +1019,85 @@ int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, cons
     return nsd_stream48_launch(a, (hipStream_t)stream);
 }
 
+// ---- causal front end (nsd_prep_*, include/nsd.h; nsd_prep.hip) ----
+static bool prep_channels(int32_t C) { return C >= 1 && C <= 64; }
+static bool prep_finite(float v) { return v - v == 0.f; }
+// the configuration alone: flags, sections, z-score (who == NULL: a silent query)
+static bool prep_config(const nsd_prep *p, const char *who) {
+#define PREP_REFUSE(...) do { if (who) nsd_set_error(__VA_ARGS__); return false; } while (0)
+    if (p->flags & ~(NSD_PREP_BASELINE | NSD_PREP_CAR)) PREP_REFUSE("%s: unknown flag bits 0x%x", who, p->flags);
+    if (p->n_sections < 0 || p->n_sections > NSD_PREP_MAX_SECTIONS) PREP_REFUSE("%s: n_sections = %d outside [0, %d]", who, p->n_sections, NSD_PREP_MAX_SECTIONS);
+    for (int s = 0; s < p->n_sections; ++s) {
+        for (int k = 0; k < 5; ++k)
+            if (!prep_finite(p->sos[s][k])) PREP_REFUSE("%s: section %d: coefficient %d is not finite", who, s, k);
+        const double a1 = p->sos[s][3], a2 = p->sos[s][4];
+        if (!(fabs(a2) < 1.0 && fabs(a1) < 1.0 + a2)) PREP_REFUSE("%s: section %d is unstable (a1 = %g, a2 = %g: stable means |a2| < 1 and |a1| < 1 + a2)", who, s, a1, a2);
+    }
+    if (!(p->alpha >= 0.f && p->alpha < 1.f)) PREP_REFUSE("%s: alpha %g outside [0, 1)", who, p->alpha);
+    if (!prep_finite(p->var0) || (p->alpha > 0.f && !(p->var0 > 0.f))) PREP_REFUSE("%s: var0 %g (finite, and > 0 with the running z-score)", who, p->var0);
+#undef PREP_REFUSE
+    return true;
+}
+// the preamble of the entry points that touch a prep state: channels, slot count, size
+static int prep_enter(int32_t C, const char *who, const void *state, int64_t state_bytes, int32_t S) {
+    if (!prep_channels(C)) { nsd_set_error("%s: C = %d channels outside [1, 64]", who, C); return NSD_E_INVALID; }
+    if (!state) { nsd_set_error("%s: null state", who); return NSD_E_INVALID; }
+    if (S < 1) { nsd_set_error("%s: S = %d slots", who, S); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)S * prep_stride(C) * (int64_t)sizeof(float);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_prep_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int nsd_prep_path(int32_t C, const nsd_prep *p) { return prep_channels(C) && (!p || prep_config(p, nullptr)) ? 1 : 0; }
+
+int64_t nsd_prep_state_bytes(int32_t C, int32_t S) {
+    if (!prep_channels(C) || S < 1) { nsd_set_error("prep_state_bytes: C outside [1, 64], or S < 1"); return NSD_E_INVALID; }
+    return (int64_t)S * prep_stride(C) * (int64_t)sizeof(float);
+}
+
+int nsd_prep_state_layout(int32_t C, nsd_prep_layout *out) {
+    if (!prep_channels(C) || !out) { nsd_set_error("prep_state_layout: C outside [1, 64], or null pointer"); return NSD_E_INVALID; }
+    out->x0 = PREP_X0; out->z = prep_z(C, 0, 0); out->mu = prep_mu(C); out->var = prep_var(C);
+    out->steps = prep_steps(C); out->stride = prep_stride(C);
+    return NSD_OK;
+}
+
+int nsd_prep_reset(int32_t C, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream) {
+    static const char *who = "prep_reset";
+    if (const int rc = prep_enter(C, who, state, state_bytes, S)) return rc;
+    if (slots && (n < 0 || n > S)) { nsd_set_error("%s: n = %d slots of S = %d", who, n, S); return NSD_E_INVALID; }
+    const int count = slots ? n : S;
+    if (count == 0) return NSD_OK;
+    return nsd_prep_reset_launch((float *)state, C, S, slots, count, (hipStream_t)stream);
+}
+
+int nsd_prep_step(const nsd_dims *d, const nsd_prep *p, const float *x, const int32_t *slots, void *state, int64_t state_bytes,
+                  int32_t S, float *y, void *stream) {
+    static const char *who = "prep_step";
+    if (!d || !p || !x || !y) { nsd_set_error("%s: null pointer (d, p, x, y)", who); return NSD_E_INVALID; }
+    if (!prep_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 64]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if (!prep_config(p, who)) return NSD_E_INVALID;
+    if (slots && !state) { nsd_set_error("%s: slots without a state (window mode takes neither)", who); return NSD_E_INVALID; }
+    if (state) {
+        if (const int rc = prep_enter(d->C, who, state, state_bytes, S)) return rc;
+        if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x != y && x < y + n && y < x + n) { nsd_set_error("%s: y overlaps x partially (in place means y == x)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    CausalPrepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.y = y; a.slots = slots; a.state = (float *)state;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.S = state ? S : 0;
+    a.baseline = (p->flags & NSD_PREP_BASELINE) != 0; a.car = (p->flags & NSD_PREP_CAR) != 0;
+    a.ns = p->n_sections; a.zs = p->alpha > 0.f;
+    memcpy(a.sos, p->sos, sizeof(a.sos));
+    a.alpha = p->alpha; a.oma = 1.0f - p->alpha; a.var0 = p->var0;
+    return nsd_prep_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -220,3 +220,25 @@ struct StreamArgs {
 };
 int nsd_stream48_launch(const StreamArgs &a, hipStream_t st);
 int nsd_stream_reset_launch(float *state, int S, const int32_t *slots, int n, hipStream_t st);
+
+// causal front end (nsd_prep_* of nsd.h; nsd_prep.hip).  One slot of the caller's state, in floats -- the public layout
+// nsd_prep_state_layout reports; it holds room for NSD_PREP_MAX_SECTIONS sections and depends on C alone
+constexpr int PREP_X0 = 0;
+constexpr int PREP_TT = 32;                  // time steps staged through LDS at once
+constexpr int PREP_GRID_CAP = 1024;          // workgroups of a launch; larger calls walk their stream groups grid-stride
+__host__ __device__ constexpr int prep_z(int C, int s, int k) { return C + (2 * s + k) * C; }   // z[s][k][C], k = 0: z1, 1: z2
+__host__ __device__ constexpr int prep_mu(int C) { return (1 + 2 * NSD_PREP_MAX_SECTIONS) * C; }
+__host__ __device__ constexpr int prep_var(int C) { return (2 + 2 * NSD_PREP_MAX_SECTIONS) * C; }
+__host__ __device__ constexpr int prep_steps(int C) { return ((3 + 2 * NSD_PREP_MAX_SECTIONS) * C + 1) & ~1; }   // int64: 8-byte aligned
+__host__ __device__ constexpr int prep_stride(int C) { return (prep_steps(C) + 2 + 3) & ~3; }
+struct CausalPrepArgs {
+    const float *x; float *y;                // [B,T,C]; y == x allowed
+    const int32_t *slots;                    // null: stream b lives in slot b
+    float *state;                            // null: window mode (every trial from a reset state, nothing stored)
+    int B, T, C, S;
+    int baseline, car, ns, zs;               // zs: alpha > 0
+    float sos[NSD_PREP_MAX_SECTIONS][5];     // b0 b1 b2 a1 a2
+    float alpha, oma, var0;                  // oma = 1.0f - alpha
+};
+int nsd_prep_launch(const CausalPrepArgs &a, hipStream_t st);
+int nsd_prep_reset_launch(float *state, int C, int S, const int32_t *slots, int n, hipStream_t st);

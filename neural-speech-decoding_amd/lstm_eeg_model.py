@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import ops, step_recipe as sr
 from ._lib import NsdError
+from .prep import CausalPrep
 
 CLASS_NAMES = ["Food", "Water", "BG-Noise"]   # verbatim from lstm_eeg_model.py:11
 
@@ -180,11 +181,23 @@ class EEG_LSTM(nn.Module):
       precision      "fp32" (default) or "bf16": the sequence-batched path for hidden sizes 64/128/256/512 (BASELINE cfg3 /
                      cfg5) -- bf16 GEMM operands and saved activations, fp32 accumulation and cell state; logits differ
                      from an fp32 run at the 1e-2 level.  bidirectional needs "bf16".
+      prep           a CausalPrep: the causal front end (nsd_prep_step, window mode: every trial from a reset state) in front of the
+                     LSTM, where normalize runs its z-score -- the model then sees what a StreamDecoder feeds it chunk by chunk.
+                     Not together with normalize; no input gradient is offered through it.
     """
 
     def __init__(self, input_size=8, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, *,
-                 residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32"):
+                 residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32",
+                 prep: Optional[CausalPrep] = None):
         super().__init__()
+        if prep is not None and not isinstance(prep, CausalPrep):
+            raise ValueError(f"prep={prep!r}: expected a CausalPrep")
+        if prep is not None and normalize:
+            raise ValueError("prep together with normalize=True: the whole-window z-score is what the causal front end replaces "
+                             "(CausalPrep.design(zscore_seconds=...) is its running form)")
+        if prep is not None and not 1 <= input_size <= 64:
+            raise ValueError(f"prep: the causal front end covers 1 .. 64 channels, input_size = {input_size}")
+        self.prep = prep
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision={precision!r}: expected 'fp32' or 'bf16'")
         self.spec = ops.ModelSpec(C=input_size, H=hidden_size, L=num_layers, K=num_classes, F=ops.FC_HIDDEN,
@@ -248,6 +261,15 @@ class EEG_LSTM(nn.Module):
         return out
 
     # ---- forward --------------------------------------------------------------------------------------
+    def _front_end(self, x: torch.Tensor) -> torch.Tensor:
+        """What stands between the caller's window and the LSTM: the z-score (normalize), the causal front end (prep), or nothing."""
+        if self.prep is not None:
+            if x.requires_grad and torch.is_grad_enabled():
+                raise NsdError("EEG_LSTM(prep=...): dx through the causal front end is not offered -- x.requires_grad would get no "
+                               "gradient; detach x, or differentiate a prep-free model on ops.prep_step(x, prep)")
+            return ops.prep_step(x, self.prep)
+        return ops.zscore(x) if self.normalize else x
+
     def _train_masks(self, B: int, T: int, device):
         if self._mask_override is not None:
             return self._mask_override
@@ -270,8 +292,7 @@ class EEG_LSTM(nn.Module):
             raise NsdError("EEG_LSTM runs only on the MI355X HIP path: move the module and the input to the GPU "
                            f"(module on {flat.device}, input on {x.device}); there is no CPU fallback")
         x = x.contiguous().float()     # predict() hands over a transposed view (preprocessor.py:34)
-        if self.normalize:
-            x = ops.zscore(x)
+        x = self._front_end(x)
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if self.precision == "bf16":
             if not self.spec.seq_path(max(x.shape[0], 1), x.shape[1]):
@@ -302,8 +323,7 @@ class EEG_LSTM(nn.Module):
                            "torch.nn.functional.cross_entropy(model(x), y)")
         flat = self.flat_parameters()
         x = x.contiguous().float()
-        if self.normalize:
-            x = ops.zscore(x)
+        x = self._front_end(x)
         rng = None
         if self.training:
             self._step += 1
@@ -315,8 +335,7 @@ class EEG_LSTM(nn.Module):
     def predict_proba(self, x: torch.Tensor) -> torch.Tensor:
         """Eval-mode class probabilities with the softmax fused into the head kernel (lstm_eeg_model.py:97)."""
         x = x.contiguous().float()
-        if self.normalize:
-            x = ops.zscore(x)
+        x = self._front_end(x)
         if self.precision == "bf16":
             # (the workspace of the evaluation is kept: its status word says whether NaN probabilities are a result or a failure)
             self._last_seq_ws = ops.seq_workspace(self.spec, x.shape[0], x.shape[1], x.device) if x.shape[0] > 0 else None
@@ -415,6 +434,8 @@ class SimplePredictor:
                  tailoring_lambda: float = 1.25e-29, class_names=None, *, preprocess=None,
                  preprocess_package: Optional[str] = None, gpu: str = "cuda", residual: bool = False,
                  normalize: bool = False, bidirectional: bool = False, precision: str = "fp32"):
+        """A checkpoint written from a model with a causal front end carries it ({"state_dict": ..., "nsd_prep": CausalPrep.to_dict()},
+        trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep."""
         self.device = torch.device(device)
         self.class_names = class_names or CLASS_NAMES
         if preprocess is None:
@@ -429,12 +450,14 @@ class SimplePredictor:
             raise NsdError("SimplePredictor needs an MI355X: torch.cuda.is_available() is False and the HIP path has "
                            "no CPU fallback")
         self.gpu = torch.device(gpu)
+        state = torch.load(pth_path, map_location="cpu", weights_only=True)
+        prep = None
+        if isinstance(state, dict) and "state_dict" in state:     # both forms, as lstm_eeg_model.py:79-80
+            prep = CausalPrep.from_dict(state["nsd_prep"]) if state.get("nsd_prep") is not None else None
+            state = state["state_dict"]
         self.model = EEG_LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
                               num_classes=num_classes, dropout=dropout, residual=residual, normalize=normalize,
-                              bidirectional=bidirectional, precision=precision)
-        state = torch.load(pth_path, map_location="cpu", weights_only=True)
-        if isinstance(state, dict) and "state_dict" in state:     # both forms, as lstm_eeg_model.py:79-80
-            state = state["state_dict"]
+                              bidirectional=bidirectional, precision=precision, prep=prep)
         self.model.load_state_dict(state, strict=True)
         self.model.to(self.gpu).eval()
         self.model.flatten_parameters()
@@ -475,7 +498,11 @@ class SimplePredictor:
         """Resumable decoding (an extension, see stream.py): a PredictorStream whose push(chunk [n,C] or [B,n,C]) advances `streams`
         live streams and returns (probs, labels) of each stream's whole prefix -- predict() on the samples seen so far, without
         waiting for the window to end.  Allowed when the predictor's preprocessor is the identity one, or when the caller passes
-        `chunk_transform` ([n,C] -> [n,C], applied to every chunk in place of the preprocessor: a causal filter of the caller's)."""
+        `chunk_transform` ([n,C] -> [n,C], applied to every chunk in place of the preprocessor: a causal filter of the caller's).
+        A model with a causal front end (EEG_LSTM(prep=...), rebuilt from its checkpoint) filters and normalises the chunks on the GPU,
+        with its state carried from chunk to chunk: what the model is fed is bit for bit what predict() feeds it on the whole window, and
+        the probabilities after the last chunk are predict()'s within the resumable path's own bound against nsd_infer (measured 1.5e-7;
+        the readout's pooling is updated per step, nsd_infer's per block of steps, so the last bits can differ)."""
         from .stream import PredictorStream
         if chunk_transform is None and not isinstance(self.pre, IdentityPreProcessor):
             raise NsdError("SimplePredictor.open_stream: the reference's window filter (PreProcessor.transform, preprocessor.py:21-36) "

@@ -27,7 +27,7 @@ def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
         raise NsdError(f"{what}: the same module is passed more than once (each model needs its own parameters)")
     for i, mdl in enumerate(models):
         if (mdl.spec != sp or mdl.residual != models[0].residual or mdl.precision != models[0].precision
-                or mdl.normalize != models[0].normalize):
+                or mdl.normalize != models[0].normalize or mdl.prep != models[0].prep):
             raise NsdError(f"{what}: model {i} has another shape / options than model 0 (mixed shapes: one launch runs one shape)")
     if models[0].residual or models[0].precision != "fp32" or sp.D != 1:
         raise NsdError(f"{what}: the model-batched path runs the plain fp32 stack (no residual extension, no bf16)")
@@ -162,13 +162,12 @@ class _EnsembleModel:
     def __init__(self, models: Sequence[EEG_LSTM]):
         _check_models(models, "EnsemblePredictor")
         self.models = list(models)
-        self.spec, self.precision, self.normalize = models[0].spec, "fp32", models[0].normalize
+        self.spec, self.precision, self.normalize, self.prep = models[0].spec, "fp32", models[0].normalize, models[0].prep
         self.params = torch.stack([m.flat_parameters() for m in self.models]).contiguous()
 
     def predict_proba(self, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous().float()
-        if self.normalize:
-            x = ops.zscore(x)
+        x = self.models[0]._front_end(x)
         _, probs = ops.multi_infer(self.spec, self.params, x)
         return probs.mean(0)
 

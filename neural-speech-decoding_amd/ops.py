@@ -1091,3 +1091,59 @@ def stream_step(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, state: tor
           _slots_ptr(slots, "stream_step"), _lib.NSD_FLAG_RESIDUAL if residual else 0, _dev_f32(state, "state"), _nbytes(state), S,
           _dev_f32(logits, "logits"), _dev_f32(probs, "probs"), STREAM)
     return logits, probs
+
+
+# ---- causal front end for live streams and their training (nsd_prep_* of include/nsd.h; the configuration: prep.CausalPrep) ----
+
+def prep_path(C_: int, prep=None) -> bool:
+    """True where nsd_prep_step covers C_ channels (with the CausalPrep `prep`, when given)."""
+    return bool(_lib.lib().nsd_prep_path(int(C_), None if prep is None else C.cast(C.pointer(prep.struct()), C.c_void_p)))
+
+
+def prep_layout(C_: int) -> "_lib.PrepLayout":
+    """Float offsets of x0[C], z[4][2][C], mu[C], var[C] and the int64 sample count inside one slot, and the slot stride."""
+    lay = _lib.PrepLayout()
+    check(_lib.lib().nsd_prep_state_layout(int(C_), C.byref(lay)), "nsd_prep_state_layout")
+    return lay
+
+
+def prep_state(C_: int, S: int, device="cuda") -> torch.Tensor:
+    """A reset prep state of S slots on `device`: fp32 [S, stride] (one row per stream; prep_layout names the columns)."""
+    state = torch.empty((int(S), int(prep_layout(C_).stride)), dtype=torch.float32, device=device)
+    prep_reset(C_, state)
+    return state
+
+
+def prep_reset(C_: int, state: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """Reset all slots of `state`, or the ones a device int32 tensor names: filters at rest, sample count 0."""
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    n = 0 if slots is None else int(slots.numel())
+    if slots is not None and n == 0:
+        return
+    _call("nsd_prep_reset", state.device, int(C_), _dev_f32(state, "state"), _nbytes(state), S, _slots_ptr(slots, "prep_reset"), n, STREAM)
+
+
+def prep_step(x: torch.Tensor, prep, state: Optional[torch.Tensor] = None, *, slots: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nsd_prep_step on x [B,n,C] (or [M,B,n,C]: M*B trials).  state=None: window mode, every trial from a reset state (what the
+    trainers and predict run).  state [S,stride]: stream mode, stream b advances slot slots[b] (or b) by the chunk.  out: a
+    caller-owned buffer of x's size; out is x: in place."""
+    if x.dim() not in (3, 4):
+        raise NsdError(f"prep_step: x must be [B,n,C] or [M,B,n,C], got {tuple(x.shape)}")
+    T, Cc = int(x.shape[-2]), int(x.shape[-1])
+    B = int(x.numel()) // max(T * Cc, 1)
+    if state is None and slots is not None:
+        raise NsdError("prep_step: slots without a state")
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"prep_step: {int(slots.numel())} slot indices for {B} streams")
+    if out is None:
+        out = torch.empty_like(x)
+    if out.numel() != x.numel():
+        raise NsdError(f"prep_step: out has {out.numel()} elements for {tuple(x.shape)}")
+    if B == 0:
+        return out
+    S = 0 if state is None else (int(state.shape[0]) if state.dim() == 2 else 0)
+    d, p = Dims(B, T, Cc, 1, 1, 1, 1), prep.struct()
+    _call("nsd_prep_step", x.device, C.byref(d), C.cast(C.pointer(p), C.c_void_p), _dev_f32(x, "x"), _slots_ptr(slots, "prep_step"),
+          _dev_f32(state, "state"), 0 if state is None else _nbytes(state), S, _dev_f32(out, "out"), STREAM)
+    return out

@@ -31,12 +31,12 @@ def step_rng(seed: int, step: int, p_lstm: float = 0.0, p_head: float = 0.0) -> 
 
 class StepRecipe:
     """What a trainer does to a batch before the step's kernels, and with which streams.  `model`: an EEG_LSTM (spec, dropout_p,
-    head_dropout_p, normalize).  augment / loss are the EFFECTIVE ones: augmentation and mixup belong to the stochastic parts, so
+    head_dropout_p, normalize, prep).  augment / loss are the EFFECTIVE ones: augmentation and mixup belong to the stochastic parts, so
     stochastic=False strips them (smoothing and class weights, which draw nothing, stay); None -- also for an Augment / Loss with every
     part off -- is the plain step, launch for launch."""
 
     def __init__(self, model, stochastic: bool, augment: Optional[ops.Augment], loss: Optional[ops.Loss], device):
-        self.spec, self.stochastic, self.normalize = model.spec, stochastic, model.normalize
+        self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
         self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
         self.augment = augment if augment is not None and augment.enabled and stochastic else None
         if loss is not None and loss.mixup and not stochastic:
@@ -53,7 +53,7 @@ class StepRecipe:
     def static_buffers(self, x: torch.Tensor) -> dict:
         """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""
         buf = {}
-        if self.normalize or self.augment is not None:
+        if self.normalize or self.augment is not None or self.prep is not None:
             buf["xn"] = torch.empty_like(x)
         if self.loss is not None:
             buf["tg"] = torch.empty((x.shape[0], self.spec.K), dtype=torch.float32, device=x.device)
@@ -64,7 +64,8 @@ class StepRecipe:
                 step_dev: Optional[torch.Tensor] = None, bufs: Optional[dict] = None):
         """(windows, labels, targets) of step `step`: exactly one of labels / targets is None.  x [B,T,C] (one model, or shared by M)
         or [M,B,T,C]; y int32 labels [M*B], or float32 target rows that are used as they are; seeds: one per model.
-        Launches nsd_augment (with the z-score fused behind it; without augmentation nsd_zscore_fwd, or nothing), then with loss=
+        Launches nsd_augment (with the z-score fused behind it; without augmentation nsd_zscore_fwd, or nothing), then for a model with
+        a causal front end nsd_prep_step in window mode (on the augmented windows in place, else into the same buffer), then with loss=
         nsd_mixup on the windows the model would otherwise see (mixup off: it only builds the target rows).  An empty shard launches
         nothing.  step_dev (device step counter, with bufs = the trainer's static buffers): the stream ids come from the counter and
         the outputs go to bufs' xn / xm / tg."""
@@ -79,6 +80,8 @@ class StepRecipe:
             x = ops.augment(x, self.augment, rngs, M=M, zscore=self.normalize, step_dev=step_dev, out=bufs.get("xn"))
         elif self.normalize:               # as EEG_LSTM.forward: the model is trained on what it is evaluated on
             x = ops.zscore(x.reshape(-1, T, Cc), out=bufs.get("xn")).view(x.shape)
+        if self.prep is not None:          # augment -> prep -> mixup: the front end sees the raw (augmented) samples, as a stream's does
+            x = ops.prep_step(x, self.prep, out=x if self.augment is not None else bufs.get("xn"))
         if y.is_floating_point() or self.loss is None:
             return (x, None, y) if y.is_floating_point() else (x, y, None)
         lo = self.loss

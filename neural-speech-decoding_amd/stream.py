@@ -25,6 +25,9 @@ class StreamDecoder:
       reset(slots=None)                      restart all streams, or the named ones
       steps                                  samples seen per slot (int64 numpy [streams])
       state_dict() / load_state_dict()       checkpoint / restore the stream state (not the model)
+
+    A model with a causal front end (EEG_LSTM(prep=...)) is decoded through it: the decoder owns a prep state of the same slots, push
+    runs nsd_prep_step (stream mode) and then nsd_stream_step, and reset / state_dict / load_state_dict cover both states.
     """
 
     def __init__(self, model, streams: int = 1):
@@ -38,7 +41,8 @@ class StreamDecoder:
                            "not causal); use an fp32, one-directional EEG_LSTM")
         if model.normalize:
             raise NsdError("StreamDecoder: normalize=True z-scores over the whole window, which a stream has not seen yet; "
-                           "normalise the chunks causally on the caller's side")
+                           "normalise the chunks causally on the caller's side, or train the model with a causal front end "
+                           "(EEG_LSTM(prep=CausalPrep.design(zscore_seconds=...)))")
         if not ops.stream_path(model.spec):
             raise NsdError(f"StreamDecoder: model shape {model.spec} is outside nsd_stream_path (hidden size 48, 2 layers, <= 8 channels, "
                            "fc width and classes <= 64)")
@@ -50,6 +54,9 @@ class StreamDecoder:
         self.model, self.streams, self.device = model, int(streams), flat.device
         self._layout = ops.stream_layout(model.spec)
         self.state = ops.stream_state(model.spec, self.streams, self.device)
+        self.prep = model.prep
+        self.prep_state = None if self.prep is None else ops.prep_state(model.spec.C, self.streams, self.device)
+        self._prepped = {}                                  # the front end's output, one buffer per chunk shape: push allocates nothing new
 
     def _slots(self, slots, n: Optional[int] = None) -> Optional[torch.Tensor]:
         if slots is None:
@@ -75,12 +82,21 @@ class StreamDecoder:
         if x.shape[0] > self.streams:
             raise NsdError(f"StreamDecoder.push: {x.shape[0]} streams pushed, the decoder has {self.streams}")
         x = x.to(self.device, non_blocking=True).contiguous().float()
-        _, probs = ops.stream_step(self.model.spec, self.model.flat_parameters(), x, self.state, slots=self._slots(slots, int(x.shape[0])),
+        slots = self._slots(slots, int(x.shape[0]))
+        if self.prep is not None:
+            out = self._prepped.get(tuple(x.shape))
+            if out is None:
+                out = self._prepped[tuple(x.shape)] = torch.empty_like(x)
+            x = ops.prep_step(x, self.prep, self.prep_state, slots=slots, out=out)
+        _, probs = ops.stream_step(self.model.spec, self.model.flat_parameters(), x, self.state, slots=slots,
                                    residual=self.model.residual, read=read)
         return probs
 
     def reset(self, slots=None) -> None:
-        ops.stream_reset(self.model.spec, self.state, self._slots(slots))
+        slots = self._slots(slots)
+        ops.stream_reset(self.model.spec, self.state, slots)
+        if self.prep is not None:
+            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
 
     @property
     def steps(self) -> np.ndarray:
@@ -88,13 +104,21 @@ class StreamDecoder:
         return self.state.view(torch.int64)[:, col].cpu().numpy().copy()
 
     def state_dict(self) -> dict:
-        return {"state": self.state.detach().cpu().clone(), "stride": int(self._layout.stride)}
+        sd = {"state": self.state.detach().cpu().clone(), "stride": int(self._layout.stride)}
+        if self.prep is not None:
+            sd["prep_state"] = self.prep_state.detach().cpu().clone()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         st = sd["state"]
         if tuple(st.shape) != tuple(self.state.shape) or int(sd.get("stride", st.shape[-1])) != int(self._layout.stride):
             raise NsdError(f"StreamDecoder.load_state_dict: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
+        ps = sd.get("prep_state")
+        if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
+            raise NsdError("StreamDecoder.load_state_dict: the checkpoint and the decoder differ in their causal front end's state")
         self.state.copy_(st.to(self.device, dtype=torch.float32))
+        if ps is not None:
+            self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
 
 
 class PredictorStream:

@@ -21,6 +21,7 @@ import torch
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
 from .ops import Augment, Loss, LrSchedule
+from .prep import CausalPrep
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
 
@@ -157,7 +158,32 @@ def main(argv=None) -> int:
     ap.add_argument("--lr-min-ratio", type=float, default=0.0, help="optimizer: cosine schedule's floor as a fraction of --lr")
     ap.add_argument("--lr-step-size", type=int, default=1, help="optimizer: step schedule: steps between two decays")
     ap.add_argument("--lr-gamma", type=float, default=1.0, help="optimizer: step schedule: factor of a decay, in (0, 1]")
+    ap.add_argument("--prep-highpass", type=float, default=None, help="causal front end (CausalPrep): 2nd-order Butterworth high-pass corner, Hz")
+    ap.add_argument("--prep-lowpass", type=float, default=None, help="causal front end: 2nd-order Butterworth low-pass corner, Hz")
+    ap.add_argument("--prep-notch", type=float, default=None, help="causal front end: notch frequency, Hz (Q = 30)")
+    ap.add_argument("--prep-zscore-seconds", type=float, default=None, help="causal front end: running z-score with this time constant; its "
+                                                                            "starting variance is calibrated on the training split (with --concurrent: on all trials)")
+    ap.add_argument("--prep-car", action="store_true", help="causal front end: common-average reference")
+    ap.add_argument("--prep-no-baseline", action="store_true", help="causal front end: do not subtract each window's first sample")
     args = ap.parse_args(argv)
+    prep_stage = any(v is not None for v in (args.prep_highpass, args.prep_lowpass, args.prep_notch, args.prep_zscore_seconds)) or args.prep_car
+    prep_design = None
+    if args.prep_no_baseline and not prep_stage:
+        ap.error("--prep-no-baseline alone leaves the front end with nothing to do: give it a filter, a z-score or --prep-car")
+    if prep_stage:
+        if args.normalize:
+            ap.error("--prep-* with --normalize: the running z-score (--prep-zscore-seconds) replaces the whole-window one")
+        try:
+            prep_design = CausalPrep.design(fs=125.0, highpass=args.prep_highpass, lowpass=args.prep_lowpass, notch=args.prep_notch,
+                                            zscore_seconds=args.prep_zscore_seconds, baseline=not args.prep_no_baseline, car=args.prep_car)
+        except ValueError as e:
+            ap.error(str(e))
+
+    def prep_for(idx):
+        """The front end of a run trained on the trials idx: the design, its starting variance calibrated on those trials."""
+        if prep_design is None or prep_design.alpha == 0:
+            return prep_design
+        return prep_design.calibrate(x_np[idx])
     if args.clip_grad_norm is not None and not args.clip_grad_norm >= 0.0:
         ap.error(f"--clip-grad-norm {args.clip_grad_norm} negative")
     if args.lr_schedule is None and (args.warmup_steps or args.lr_min_ratio or args.lr_step_size != 1 or args.lr_gamma != 1.0):
@@ -228,7 +254,7 @@ def main(argv=None) -> int:
         what is written / scored -- the number of epochs is fixed beforehand, nothing is selected."""
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
-                         bidirectional=args.bidirectional).to(dev).train()
+                         bidirectional=args.bidirectional, prep=prep_for(tr_idx)).to(dev).train()
         steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
         trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
                           clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch))
@@ -270,10 +296,10 @@ def main(argv=None) -> int:
             print(f"train: {e}", file=sys.stderr)
             return 2
         from .multimodel import ModelBatchTrainer
-        models = []
+        models, prep_all = [], prep_for(np.arange(len(y_np)))
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all).to(dev).train())
         steps_per_epoch = concurrent_epoch(runs, args.batch, 0, lambda idxs: None)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
                                 loss=loss_for(args, y_np), clip_grad_norm=args.clip_grad_norm,

@@ -422,8 +422,10 @@ class Trainer:
 
 def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:
     """Write a .pth the reference's SimplePredictor loads unchanged (raw state_dict with the reference's
-    key names on CPU; lstm_eeg_model.py:77-81)."""
-    torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, path)
+    key names on CPU; lstm_eeg_model.py:77-81).  A model with a causal front end is written in the dict form both loaders accept,
+    {"state_dict": ..., "nsd_prep": prep.to_dict()}: the reference's loader reads the weights, SimplePredictor here rebuilds the prep too."""
+    sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    torch.save(sd if model.prep is None else {"state_dict": sd, "nsd_prep": model.prep.to_dict()}, path)
 
 
 def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
