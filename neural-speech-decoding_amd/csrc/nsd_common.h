@@ -136,6 +136,16 @@ __device__ __forceinline__ float soft_ce_thread(const float *q, const float *lg,
     }
     return loss;
 }
+// and with the label y in place of the targets: dl[k] = scale (p_k - [k == y]), where for the label class p_y - 1 = -(sum_{k != y} e_k) / d
+// (no cancellation); returns the loss -log p_y
+__device__ __forceinline__ float hard_ce_thread(const int y, const float *lg, const int K, const float scale, float *dl) {
+    float m = lg[0];
+    for (int k = 1; k < K; ++k) m = fmaxf(m, lg[k]);
+    float d = 0.f, rest = 0.f;
+    for (int k = 0; k < K; ++k) { const float e = expf(lg[k] - m); d += e; if (k != y) rest += e; }
+    for (int k = 0; k < K; ++k) dl[k] = (k == y ? -rest / d : expf(lg[k] - m) / d) * scale;
+    return -((lg[y] - m) - logf(d));
+}
 
 // A called function sees the kernel's argument block through a pointer: what it loads from there sits in VGPRs, and hipcc cannot know that
 // every lane holds the same value -- buffer descriptors built from such pointers are used inside WATERFALL loops (one pass per distinct
@@ -171,6 +181,43 @@ __device__ __forceinline__ void stage_head_weights(const float *fc0_w, const flo
         for (int i = 0; i < 8; ++i) { const int e = e0 + lane + 64 * i; v[i] = ((gw_p)fc3_w)[e < n3 ? e : 0]; }
 #pragma unroll
         for (int i = 0; i < 8; ++i) { const int e = e0 + lane + 64 * i; if (e < n3) w3[e] = v[i]; }
+    }
+}
+
+// The eval-mode readout of a pooled prefix by ONE wave (the inference tail of nsd_lstm2_fwd48.hip, nsd_stream48.hip): LayerNorm (biased
+// variance, eps in the sqrt), fc.0 -> RReLU(eval) -> fc.3, and the softmax over classes when probs is not null.  Lane j < HH holds
+// p = pooled[j], the others 0; vec: 64 floats of LDS; row b of logits / probs is written when b < B.  A: an argument struct with
+// ln_w .. fc3_b, eval_slope, K, F (F, K <= 64).
+template <int HH, class A>
+__device__ __forceinline__ void prefix_readout(const A &a, const float p, float *vec, float *logits, float *probs, const int b, const int B,
+                                               const int lane) {
+    const int K = a.K, F = a.F;
+    const float mu = wave_sum(p) * (1.0f / HH);
+    const float dlt = lane < HH ? p - mu : 0.f;
+    const float rstd = 1.0f / sqrtf(wave_sum(dlt * dlt) * (1.0f / HH) + 1e-5f);
+    if (lane < HH) vec[lane] = dlt * rstd * a.ln_w[lane] + a.ln_b[lane];
+    float z = 0.f;
+    if (lane < F) {
+        float acc = a.fc0_b[lane];
+        const float *w = a.fc0_w + (size_t)lane * HH;
+#pragma unroll 8
+        for (int j = 0; j < HH; ++j) acc = fmaf(w[j], vec[j], acc);
+        z = acc >= 0.f ? acc : acc * a.eval_slope;
+    }
+    if (lane < F) vec[lane] = z;                              // all reads of the LayerNorm vector are done (same wave, in order)
+    float lg = -INFINITY;
+    if (lane < K) {
+        float acc = a.fc3_b[lane];
+        const float *w = a.fc3_w + (size_t)lane * F;
+        for (int f = 0; f < F; ++f) acc = fmaf(w[f], vec[f], acc);
+        lg = acc;
+        if (b < B) logits[(size_t)b * K + lane] = acc;
+    }
+    if (probs) {
+        const float mx = wave_max(lg);
+        const float e = lane < K ? __expf(lg - mx) : 0.f;
+        const float d = wave_sum(e);
+        if (lane < K && b < B) probs[(size_t)b * K + lane] = e / d;
     }
 }
 

@@ -585,7 +585,7 @@ __device__ __forceinline__ void pool_loop(PoolRun (&p)[NB], FSmem<NB> &sm, const
 template <int NB, class A>
 __device__ __forceinline__ void pool_role(const A &a, FSmem<NB> &sm, const int lane, const int n_steps) {
     static_assert(NB == 1, "inference tail is built for one trial per workgroup");
-    const int T = a.T, K = a.K, F = a.F;
+    const int T = a.T;
     PoolRun pr[NB];
     pool_init<NB>(pr[0], a, lane);
     Prof prof = prof_init(a.dbg);
@@ -596,35 +596,7 @@ __device__ __forceinline__ void pool_role(const A &a, FSmem<NB> &sm, const int l
         step_barrier<false>(prof);
         pool_loop<NB>(pr, sm, lane, T, n_steps, false, prof);
         const float pooled = pr[0].pooled, den = pr[0].den;
-        // ---- LayerNorm (biased variance, eps in the sqrt), fc.0 -> RReLU(eval) -> fc.3, softmax over classes ----
-        const float p = lane < H ? pooled / den : 0.f;
-        const float mu = wave_sum(p) * (1.0f / H);
-        const float dlt = lane < H ? p - mu : 0.f;
-        const float rstd = 1.0f / sqrtf(wave_sum(dlt * dlt) * (1.0f / H) + 1e-5f);
-        if (lane < H) sm.vec[0][lane] = dlt * rstd * a.ln_w[lane] + a.ln_b[lane];
-        float z = 0.f;
-        if (lane < F) {
-            float acc = a.fc0_b[lane];
-            const float *w = a.fc0_w + (size_t)lane * H;
-#pragma unroll 8
-            for (int j = 0; j < H; ++j) acc = fmaf(w[j], sm.vec[0][j], acc);
-            z = acc >= 0.f ? acc : acc * a.eval_slope;
-        }
-        if (lane < F) sm.vec[0][lane] = z;                    // all reads of the LayerNorm vector are done (same wave, in order)
-        float lg = -INFINITY;
-        if (lane < K) {
-            float acc = a.fc3_b[lane];
-            const float *w = a.fc3_w + (size_t)lane * F;
-            for (int f = 0; f < F; ++f) acc = fmaf(w[f], sm.vec[0][f], acc);
-            lg = acc;
-            if (b < a.B) a.logits_out[(size_t)b * K + lane] = acc;
-        }
-        if (a.probs_out) {
-            const float mx = wave_max(lg);
-            const float e = lane < K ? __expf(lg - mx) : 0.f;
-            const float d = wave_sum(e);
-            if (lane < K && b < a.B) a.probs_out[(size_t)b * K + lane] = e / d;
-        }
+        prefix_readout<H>(a, lane < H ? pooled / den : 0.f, sm.vec[0], a.logits_out, a.probs_out, b, a.B, lane);
         step_barrier<false>(prof);
     }
     prof_store(a.dbg, prof);

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(NT) void stream48_kernel(const StreamArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int role = tid / 192;              // 0 L0, 1 P, 2 L1, 3 pool (wave-uniform: 192 = 3 waves)
     const int r = tid - role * 192, j = r >> 2, s = r & 3;
-    const int T = a.T, C = a.C, K = a.K, F = a.F;
+    const int T = a.T, C = a.C, K = a.K;
 
     // ---- weights of this thread's role, once per launch ----
     f32x2 w[4][6], wx[4];
@@ -233,37 +233,8 @@ __global__ __launch_bounds__(NT) void stream48_kernel(const StreamArgs a) {
                 long long *n = reinterpret_cast<long long *>(st + STREAM_STEPS);
                 *n = *n + T;
             }
-            if (a.logits) {
-                // ---- readout of the prefix: LayerNorm (biased variance, eps in the sqrt), fc.0 -> RReLU(eval) -> fc.3, class softmax ----
-                const float pl = lane < H ? acc / den : 0.f;
-                const float mu = wave_sum(pl) * (1.0f / H);
-                const float dlt = lane < H ? pl - mu : 0.f;
-                const float rstd = 1.0f / sqrtf(wave_sum(dlt * dlt) * (1.0f / H) + 1e-5f);
-                if (lane < H) sm.vec[lane] = dlt * rstd * a.ln_w[lane] + a.ln_b[lane];
-                float z = 0.f;
-                if (lane < F) {
-                    float v = a.fc0_b[lane];
-                    const float *wr = a.fc0_w + (size_t)lane * H;
-#pragma unroll 8
-                    for (int q = 0; q < H; ++q) v = fmaf(wr[q], sm.vec[q], v);
-                    z = v >= 0.f ? v : v * a.eval_slope;
-                }
-                if (lane < F) sm.vec[lane] = z;          // (same wave, LDS in order: the LayerNorm vector has been read)
-                float lg = -INFINITY;
-                if (lane < K) {
-                    float v = a.fc3_b[lane];
-                    const float *wr = a.fc3_w + (size_t)lane * F;
-                    for (int f = 0; f < F; ++f) v = fmaf(wr[f], sm.vec[f], v);
-                    lg = v;
-                    a.logits[(size_t)b * K + lane] = v;
-                }
-                if (a.probs) {
-                    const float mx = wave_max(lg);
-                    const float e = lane < K ? __expf(lg - mx) : 0.f;
-                    const float d = wave_sum(e);
-                    if (lane < K) a.probs[(size_t)b * K + lane] = e / d;
-                }
-            }
+            // the decision of the prefix seen so far
+            if (a.logits) prefix_readout<H>(a, lane < H ? acc / den : 0.f, sm.vec, a.logits, a.probs, b, a.B, lane);
         }
         __syncthreads();                                 // the next stream's state goes into the LDS rows this one's tail has read
     }

@@ -127,6 +127,11 @@ T_EDGES = [(8, 32, 3, 32, 5, 1, False), (7, 32, 5, 7, 6, 2, True), (5, 32, 3, 32
            (8, 32, 4, 33, 4, 33, True), (7, 32, 3, 32, 8, 64, False), (5, 32, 2, 32, 6, 65, True), (1, 32, 3, 32, 5, 97, False),
            (1, 64, 3, 32, 4, 1, True), (5, 64, 4, 33, 7, 2, False), (7, 64, 3, 32, 8, 31, True), (8, 64, 5, 7, 5, 32, False),
            (1, 64, 2, 32, 6, 33, False), (5, 64, 3, 32, 8, 64, True), (7, 64, 2, 33, 5, 65, False), (8, 64, 3, 32, 4, 97, True)]
+# Two branches of the head launchers (csrc/nsd_head.hip) that no other row of the suite takes, on the generic route (section d of
+# tests/test_gpu_fp32_routes.py; (C, H, L, K, F, (m, a): B = m * cus + a, T, residual, grid loops)): H % 4 != 0 -- the scalar score loop, the
+# sequence read in place -- and a sequence that does not fit in LDS beside the vectors (560 rows of 68 floats = 152 320 B of the 144 KB):
+# head_fwd_kernel / head_bwd_kernel read the rows from memory, 16 bytes at a time, and the fused train head declines (150 KB).
+HEAD_BRANCH_ROWS = [(3, 30, 1, 3, 32, (0, 3), 5, False, False), (8, 60, 1, 3, 32, (0, 2), 560, False, False)]
 # Step counts at the loop edges of the one-trial H = 48 kernels, shared by the files that sweep them.
 # T' of the forward's prefix pairs: around the ring (16), the x chunk (32) and their multiples, +-2 for layer 1's lag
 FWD_T = (1, 2, 3, 13, 14, 15, 16, 17, 18, 29, 30, 31, 32, 33, 34, 47, 48, 49, 63, 64, 65)

@@ -47,7 +47,7 @@ import torch
 
 from oracle import nsd_oracle as orc
 from tests.golden.make_goldens import synth_labels, synth_params, synth_x
-from tests.gpu_harness import (FAST48, FP32_EXACT, HEAD_TOL, KINK_MARGIN, LOGIT_TOL, PROB_TOL, T_EDGES, assert_step_vs_oracle, cus, dev, grad_class,  # noqa: F401
+from tests.gpu_harness import (FAST48, FP32_EXACT, HEAD_BRANCH_ROWS, HEAD_TOL, KINK_MARGIN, LOGIT_TOL, PROB_TOL, T_EDGES, assert_step_vs_oracle, cus, dev, grad_class,  # noqa: F401
                                grad_errors, head_inputs, kink_safe, model_from_state, nsd, oracle_step, spec_of, to_dev, train_step)
 
 pytestmark = pytest.mark.gpu
@@ -256,9 +256,10 @@ def test_inference_in_the_batch_bands_vs_oracle(nsd, dev, cus, row):
 # (C, H, L, K, F, (m, a), T, residual, every kernel's grid loops)
 GENERIC = [(3, 40, 1, 3, 32, (1, 44), 5, False, False),     # no other route: H % 16 != 0, C % 4 != 0
            (8, 48, 3, 3, 32, (8, 3), 2, True, True)]        # beyond gen_grid's cap of eight workgroups per CU
+GENERIC += HEAD_BRANCH_ROWS                                  # the head launchers' scalar score loop and unstaged sequence
 
 
-@pytest.mark.parametrize("Cc,H,L,K,F,mb,T,residual,loops", GENERIC, ids=["H40-L1", "H48-L3-res"])
+@pytest.mark.parametrize("Cc,H,L,K,F,mb,T,residual,loops", GENERIC, ids=["H40-L1", "H48-L3-res", "H30-scalar-scores", "H60-T560-unstaged"])
 def test_generic_route_at_many_trials_vs_oracle(nsd, dev, cus, Cc, H, L, K, F, mb, T, residual, loops):
     from nsd_amd import ops
     B = mb[0] * cus + mb[1]

@@ -4,8 +4,12 @@
     tools/isa_digest.py --csrc neural-speech-decoding_amd/csrc --out /tmp/isa_pr.json
     tools/isa_digest.py --compare /tmp/isa_parent.json /tmp/isa_pr.json
     tools/isa_digest.py --census --csrc neural-speech-decoding_amd/csrc          (step bodies of the one- and two-trial H = 48 kernels)
+    tools/isa_digest.py --csrc neural-speech-decoding_amd/csrc --files nsd_stream48 nsd_head --out /tmp/isa_head.json
 
-Each of the eight files is compiled device-only in three flavours (the Makefile's FLAGS, + -DNSD_PROFILE=1, + -DNSD_ABLATE_HOOKS=1),
+Used on the eight H = 48 kernel files (the default), and through --files on nsd_stream48 and nsd_head (digest and --census alike: any
+file of csrc/ that compiles on its own is taken as it is).
+
+Each of the files is compiled device-only in three flavours (the Makefile's FLAGS, + -DNSD_PROFILE=1, + -DNSD_ABLATE_HOOKS=1),
 unbundled and disassembled; per function symbol the digest is the sha256 of its instructions (raw encodings included, leading
 addresses dropped), and per kernel the record of its code-object note (registers, spills, LDS, scratch, kernarg size).  Two builds of
 one source give equal digests; the device ELF itself carries a per-build id and is not compared.
@@ -207,7 +211,7 @@ if __name__ == "__main__":
     ap.add_argument("--csrc")
     ap.add_argument("--out")
     ap.add_argument("--jobs", type=int, default=8)
-    ap.add_argument("--files", nargs="*", default=FILES, help="a subset of the eight files (without .hip)")
+    ap.add_argument("--files", nargs="*", default=FILES, help="files of csrc/ without .hip (default: the eight H = 48 kernel files)")
     ap.add_argument("--compare", nargs=2)
     ap.add_argument("--subset", action="store_true", help="with --compare: only the objects the right side has")
     ap.add_argument("--table", action="store_true", help="with --compare: print every symbol, not only the differing ones")
