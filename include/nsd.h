@@ -487,6 +487,42 @@ int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, cons
                     int64_t state_bytes, int32_t S, float *logits, float *probs, void *stream);
 
 /*
+ * ---- resumable inference of an ensemble: M models per stream in one launch (an EXTENSION, of the two above: nsd_multi_*, nsd_stream_*) ----
+ *
+ * nsd_multi_stream_step advances the B streams of a call in each of M models of one shape -- params [M,P], P = nsd_param_count(d) -- by
+ * one launch of the step nsd_stream_step runs (the same source, csrc/nsd_stream48.hip, compiled with a model view), and can return the
+ * ensemble's mean probabilities.
+ * State: [M][S][stride] floats.  Model m's part starts at float m * S * stride and is an ordinary single-model state of S slots in the
+ * public nsd_stream_layout: it can be handed to nsd_stream_step as it is (with params + m*P).  The whole buffer is a flat state of M*S
+ * slots to nsd_stream_reset -- slot m*S + s is stream s of model m, slots == NULL resets everything -- so there is no reset entry of its
+ * own, and the state must be reset once before its first step.
+ *   nsd_multi_stream_path         1 where nsd_stream_path(d) and 1 <= M <= NSD_MAX_MODELS, else 0
+ *   nsd_multi_stream_state_bytes  M * nsd_stream_state_bytes(d, S); <0 outside the path or for S < 1
+ *   nsd_multi_stream_step         d->B streams, chunk length d->T >= 1.  x: model m reads the chunk [B,T,C] at x + m * x_model_stride
+ *                                 floats; 0: one chunk for all models, else >= B*T*C.  slots: DEVICE int32[B] of distinct indices in
+ *                                 [0, S) or NULL for 0 .. B-1, shared by the models: stream b lives in slot slots[b] of every model's
+ *                                 part.  logits [M,B,K] or NULL (advance only), probs [M,B,K] or NULL, mean_probs [B,K] or NULL.
+ * Contract.  Model m's slots after the call, and its rows of logits / probs, are bit for bit what
+ *   nsd_stream_step(d, params + m*P, x + m*x_model_stride, slots, flags, state + m*S*stride, S*stride*4, S, logits + m*B*K, probs + m*B*K)
+ * leaves and writes, for any M, B, cut of the stream and placement in the grid.
+ * mean_probs[b,k] = (((p_0 + p_1) + p_2) + ... + p_{M-1}) / (float)M with p_m = probs[m,b,k]: a serial fp32 sum in m, every addition
+ * rounded on its own, then one correctly rounded division.  It is formed from the probs buffer by a second small launch that the
+ * same call enqueues behind the step.
+ * Failure behaviour.  As nsd_stream_step, every refusal before any launch: NSD_E_INVALID for all that call refuses, for M outside
+ * [1, NSD_MAX_MODELS], mean_probs without probs, x_model_stride negative or positive and below B*T*C, M*B*K above 2^31 - 1;
+ * NSD_E_WORKSPACE when state_bytes < nsd_multi_stream_state_bytes(d, M, S).  B = 0 launches nothing.  A slot index outside [0, S) is
+ * skipped in every model: its rows of logits, probs and mean_probs are NaN, no state is touched.  A sample that is not finite poisons
+ * that stream in every model that reads it until those slots (m*S + s) are reset; its mean row is NaN, other streams are unaffected.
+ * No host synchronisation, no allocation: the call can be captured in a single-stream graph, with nsd_prep_step in front of it.
+ * Additive: NSD_VERSION stays 301, a caller detects the feature by the symbols.
+ */
+int     nsd_multi_stream_path(const nsd_dims *d, int32_t M);
+int64_t nsd_multi_stream_state_bytes(const nsd_dims *d, int32_t M, int32_t S);
+int nsd_multi_stream_step(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const int32_t *slots,
+                          uint32_t flags, void *state, int64_t state_bytes, int32_t S, float *logits, float *probs, float *mean_probs,
+                          void *stream);
+
+/*
  * ---- causal front end for live streams and their training (an EXTENSION: the reference filters whole windows on the host) ----
  *
  * A per-channel transform that can run chunk by chunk in front of nsd_stream_step, and over whole windows in a training step, so that a

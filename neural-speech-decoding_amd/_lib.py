@@ -172,6 +172,10 @@ SYMBOLS = {
     "nsd_stream_state_layout": (C.c_int, [_dp, C.POINTER(StreamLayout)]),
     "nsd_stream_reset": (C.c_int, [_dp, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
     "nsd_stream_step": (C.c_int, [_dp, _fp, _fp, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _vp]),
+    # resumable inference of M models per launch (an ensemble decoding live streams)
+    "nsd_multi_stream_path": (C.c_int, [_dp, C.c_int32]),
+    "nsd_multi_stream_state_bytes": (C.c_int64, [_dp, C.c_int32, C.c_int32]),
+    "nsd_multi_stream_step": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _fp, _vp]),
     # causal front end for live streams and their training
     "nsd_prep_path": (C.c_int, [C.c_int32, _vp]),
     "nsd_prep_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

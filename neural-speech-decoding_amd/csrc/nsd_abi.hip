@@ -955,16 +955,17 @@ static bool stream_shape(const nsd_dims *d) {
     return d && check_model(d->C, d->H, d->L, d->K, d->F) == NSD_OK && d->H == 48 && d->L == 2 && d->C <= 8 && d->F <= 64 && d->K <= 64;
 }
 // the preamble of the entry points that touch a stream state: shape, pointers, slot count, size
-static int stream_enter(const nsd_dims *d, const char *who, bool ptrs_ok, const void *state, int64_t state_bytes, int32_t S) {
+static int stream_enter(const nsd_dims *d, const char *who, bool ptrs_ok, const void *state, int64_t state_bytes, int32_t S, int32_t M = 1) {
     if (!stream_shape(d)) {
         nsd_set_error("%s: shape outside the resumable path (nsd_stream_path: H = 48, L = 2, C <= 8, F <= 64, K <= 64)", who);
         return NSD_E_INVALID;
     }
     if (!ptrs_ok || !state) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     if (S < 1) { nsd_set_error("%s: S = %d slots", who, S); return NSD_E_INVALID; }
-    const int64_t need = (int64_t)S * STREAM_STRIDE * (int64_t)sizeof(float);
+    const int64_t need = (int64_t)M * S * STREAM_STRIDE * (int64_t)sizeof(float);
     if (state_bytes < need) {
-        nsd_set_error("%s: state of %lld bytes is smaller than nsd_stream_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_%sstream_state_bytes() = %lld", who, (long long)state_bytes,
+                      M > 1 ? "multi_" : "", (long long)need);
         return NSD_E_WORKSPACE;
     }
     return NSD_OK;
@@ -995,15 +996,9 @@ int nsd_stream_reset(const nsd_dims *d, void *state, int64_t state_bytes, int32_
     return nsd_stream_reset_launch((float *)state, S, slots, count, (hipStream_t)stream);
 }
 
-int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, const int32_t *slots, uint32_t flags, void *state,
-                    int64_t state_bytes, int32_t S, float *logits, float *probs, void *stream) {
-    static const char *who = "stream_step";
-    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
-    if (const int rc = stream_enter(d, who, params && x, state, state_bytes, S)) return rc;
-    if (probs && !logits) { nsd_set_error("%s: probs without logits", who); return NSD_E_INVALID; }
-    if (flags & ~NSD_FLAG_RESIDUAL) { nsd_set_error("%s: flags 0x%x (only NSD_FLAG_RESIDUAL applies)", who, flags); return NSD_E_INVALID; }
-    if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
-    if (d->B == 0) return NSD_OK;
+// the step's argument block: one model's parameters, state and outputs (the model-batched launch moves them per model)
+static StreamArgs build_stream(const nsd_dims *d, const float *params, const float *x, const int32_t *slots, uint32_t flags, void *state,
+                               int32_t S, float *logits, float *probs) {
     const HeadArgs h = build_head(d, params);
     const ParamLayout pl = layout_of(d);
     StreamArgs a;
@@ -1016,7 +1011,52 @@ int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, cons
     a.eval_slope = h.eval_slope;
     a.slots = slots; a.state = (float *)state; a.logits = logits; a.probs = probs;
     a.B = d->B; a.T = d->T; a.C = d->C; a.K = d->K; a.F = d->F; a.S = S; a.residual = residual_of(flags);
-    return nsd_stream48_launch(a, (hipStream_t)stream);
+    return a;
+}
+
+int nsd_stream_step(const nsd_dims *d, const float *params, const float *x, const int32_t *slots, uint32_t flags, void *state,
+                    int64_t state_bytes, int32_t S, float *logits, float *probs, void *stream) {
+    static const char *who = "stream_step";
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (const int rc = stream_enter(d, who, params && x, state, state_bytes, S)) return rc;
+    if (probs && !logits) { nsd_set_error("%s: probs without logits", who); return NSD_E_INVALID; }
+    if (flags & ~NSD_FLAG_RESIDUAL) { nsd_set_error("%s: flags 0x%x (only NSD_FLAG_RESIDUAL applies)", who, flags); return NSD_E_INVALID; }
+    if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    return nsd_stream48_launch(build_stream(d, params, x, slots, flags, state, S, logits, probs), (hipStream_t)stream);
+}
+
+// ---- resumable inference of M models per launch (nsd_multi_stream48.hip): state [M][S][STREAM_STRIDE] ----
+int nsd_multi_stream_path(const nsd_dims *d, int32_t M) { return stream_shape(d) && M >= 1 && M <= NSD_MAX_MODELS ? 1 : 0; }
+
+int64_t nsd_multi_stream_state_bytes(const nsd_dims *d, int32_t M, int32_t S) {
+    if (!nsd_multi_stream_path(d, M) || S < 1) {
+        nsd_set_error("multi_stream_state_bytes: shape outside nsd_stream_path, M = %d outside [1, %d], or S < 1", M, NSD_MAX_MODELS);
+        return NSD_E_INVALID;
+    }
+    return (int64_t)M * S * STREAM_STRIDE * (int64_t)sizeof(float);
+}
+
+int nsd_multi_stream_step(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, const int32_t *slots,
+                          uint32_t flags, void *state, int64_t state_bytes, int32_t S, float *logits, float *probs, float *mean_probs,
+                          void *stream) {
+    static const char *who = "multi_stream_step";
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (const int rc = stream_enter(d, who, params && x, state, state_bytes, S, M)) return rc;
+    if (probs && !logits) { nsd_set_error("%s: probs without logits", who); return NSD_E_INVALID; }
+    if (mean_probs && !probs) { nsd_set_error("%s: mean_probs without probs", who); return NSD_E_INVALID; }
+    if (flags & ~NSD_FLAG_RESIDUAL) { nsd_set_error("%s: flags 0x%x (only NSD_FLAG_RESIDUAL applies)", who, flags); return NSD_E_INVALID; }
+    if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
+        nsd_set_error("%s: x_model_stride %lld: 0 (one chunk for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
+        return NSD_E_INVALID;
+    }
+    if ((int64_t)M * d->B * d->K > 0x7fffffff) { nsd_set_error("%s: M * B * K = %lld output values in one launch", who, (long long)M * d->B * d->K); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    const StreamArgs a = build_stream(d, params, x, slots, flags, state, S, logits, probs);
+    return nsd_multi_stream48_launch(a, model_split(d, x_model_stride), M, mean_probs, (hipStream_t)stream);
 }
 
 // ---- causal front end (nsd_prep_*, include/nsd.h; nsd_prep.hip) ----

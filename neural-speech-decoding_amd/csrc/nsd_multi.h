@@ -89,3 +89,6 @@ int nsd_lstm2_bwd48x4_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, i
 // dispatch by the launch plan of the M*B trials of the launch (plan48, nsd_lstm2.hip)
 int nsd_lstm2_multi_fwd_launch(const Lstm2FwdArgs &a, ModelSplit s, int M, hipStream_t st);
 int nsd_lstm2_multi_bwd_launch(const Lstm2BwdArgs &a, ModelSplit s, int M, hipStream_t st);
+// resumable inference of M models (nsd_multi_stream_step; nsd_multi_stream48.hip): a.B streams and a.S slots per model, s.G is set here;
+// mean: null or [B,K], the mean of a.probs over the models, by a second launch
+int nsd_multi_stream48_launch(const StreamArgs &a, ModelSplit s, int M, float *mean, hipStream_t st);

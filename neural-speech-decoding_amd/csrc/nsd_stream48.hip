@@ -18,7 +18,12 @@
 // state is that of the same step.  Every step's arithmetic is the same instruction sequence whatever its place in the chunk, so the
 // state after t samples is a function of the samples alone, not of how they were cut.
 // Thread (unit j, k-slice s) in the chain roles: 4 gates x 12 (+2) weights in VGPRs, DPP quad reduction, lane s evaluates gate s.
-#include "nsd_args.h"
+//
+// The step is one source that two kernels are compiled from: stream48_kernel (one model, this file) and multi_stream48_kernel (M
+// models of one shape per launch: nsd_multi_stream_step; compiled as nsd_multi_stream48.hip, which includes this file with
+// NSD_MULTI_TU set, so that the single-model kernels' module is what it was).  The model-batched kernel works on a model view
+// (nsd_multi.h): pointers moved to its model, the workgroup index and count taken inside the model.
+#include "nsd_multi.h"
 
 namespace {
 
@@ -82,7 +87,38 @@ __device__ __forceinline__ void chunk_x(const StreamArgs &a, const int b, const 
     }
 }
 
-__global__ __launch_bounds__(NT) void stream48_kernel(const StreamArgs a) {
+// The step's one source, compiled as two kernels.  STREAM48_KERNEL: the kernel's name and parameters; STREAM48_VIEW: what `a` is --
+// the argument block itself (the workgroups of the grid share its B streams: wg_id / wg_count are blockIdx.x / gridDim.x) or the view
+// of the workgroup's model (the workgroups of one model share them).  A macro rather than a template body: the single-model kernel
+// keeps its text, and with it its machine code (tools/isa_digest.py)
+#if !NSD_MULTI_TU
+#define STREAM48_KERNEL stream48_kernel(const StreamArgs a)
+#define STREAM48_VIEW
+#else
+// workgroup blockIdx.x runs model blockIdx.x / s.G: params + m*P, x + m*x_stride, state + m*S*STREAM_STRIDE, output rows + m*B*K
+__device__ __forceinline__ ModelView<StreamArgs> model_view(const StreamArgs &a, const ModelSplit &s) {
+    using nsd_multi_detail::mv;
+    const int m = nsd_multi_detail::model_of_block(s);
+    ModelView<StreamArgs> v;
+    static_cast<StreamArgs &>(v) = a;
+    v.wg = (int)blockIdx.x - m * s.G;
+    v.nwg = s.G;
+    const size_t P = (size_t)s.P * m, bk = (size_t)m * a.B * a.K;
+    v.x = a.x + (size_t)s.x_stride * m;
+    v.w_ih0 = a.w_ih0 + P; v.w_hh0 = a.w_hh0 + P; v.b_ih0 = a.b_ih0 + P; v.b_hh0 = a.b_hh0 + P;
+    v.w_ih1 = a.w_ih1 + P; v.w_hh1 = a.w_hh1 + P; v.b_ih1 = a.b_ih1 + P; v.b_hh1 = a.b_hh1 + P;
+    v.attn_w = a.attn_w + P; v.attn_b = a.attn_b + P; v.ln_w = a.ln_w + P; v.ln_b = a.ln_b + P;
+    v.fc0_w = a.fc0_w + P; v.fc0_b = a.fc0_b + P; v.fc3_w = a.fc3_w + P; v.fc3_b = a.fc3_b + P;
+    v.state = a.state + (size_t)m * a.S * STREAM_STRIDE;
+    v.logits = mv(a.logits, bk); v.probs = mv(a.probs, bk);
+    return v;
+}
+#define STREAM48_KERNEL multi_stream48_kernel(const StreamArgs a_in, const ModelSplit ms)
+#define STREAM48_VIEW const ModelView<StreamArgs> a = model_view(a_in, ms);
+#endif
+
+__global__ __launch_bounds__(NT) void STREAM48_KERNEL {
+    STREAM48_VIEW
     __shared__ SSmem sm;
     const int tid = threadIdx.x, lane = tid & 63;
     const int role = tid / 192;              // 0 L0, 1 P, 2 L1, 3 pool (wave-uniform: 192 = 3 waves)
@@ -122,7 +158,7 @@ __global__ __launch_bounds__(NT) void stream48_kernel(const StreamArgs a) {
     const float ab = a.attn_b[0];
     const bool res = a.residual != 0;
 
-    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    for (int b = wg_id(a); b < a.B; b += wg_count(a)) {
         const int slot = a.slots ? a.slots[b] : b;
         if ((unsigned)slot >= (unsigned)a.S) {           // (the same for every thread of the workgroup) skipped: NaN outputs, no state touched
             if (a.logits && tid < K) {
@@ -240,6 +276,7 @@ __global__ __launch_bounds__(NT) void stream48_kernel(const StreamArgs a) {
     }
 }
 
+#if !NSD_MULTI_TU
 // a reset slot: zero h and c, empty pooling state (running max -inf, denominator and sum 0), step count 0
 __global__ __launch_bounds__(256) void stream_reset_kernel(float *state, const int S, const int32_t *slots, const int n) {
     const int i = blockIdx.x;
@@ -250,8 +287,20 @@ __global__ __launch_bounds__(256) void stream_reset_kernel(float *state, const i
     if (e < STREAM_STRIDE) state[(size_t)slot * STREAM_STRIDE + e] = e == STREAM_MAX ? -INFINITY : 0.f;
 }
 
+#else
+// mean[i] = (((p_0[i] + p_1[i]) + p_2[i]) + ...) / float(M), p_m = probs + m*n: a serial sum in m, every operation rounded on its own
+__global__ __launch_bounds__(256) void multi_stream_mean_kernel(const float *probs, float *mean, const int M, const int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float sum = probs[i];
+    for (int m = 1; m < M; ++m) sum = sum + probs[(size_t)m * n + i];
+    mean[i] = sum / (float)M;
+}
+#endif
+
 }  // namespace
 
+#if !NSD_MULTI_TU
 int nsd_stream48_launch(const StreamArgs &a, hipStream_t st) {
     const int cus = nsd_num_cus();
     const int grid = a.B < cus ? a.B : cus;
@@ -266,3 +315,20 @@ int nsd_stream_reset_launch(float *state, int S, const int32_t *slots, int n, hi
     NSD_CHECK_LAUNCH("stream_reset");
     return NSD_OK;
 }
+
+#else
+// a.B streams of each of M models; G = min(B, max(1, CUs / M)) workgroups per model: one workgroup fits a CU (ten waves), so a larger
+// grid would only queue.  mean: null, or [B,K] formed from a.probs by a second launch behind the step
+int nsd_multi_stream48_launch(const StreamArgs &a, ModelSplit s, int M, float *mean, hipStream_t st) {
+    const int per = nsd_num_cus() / M > 1 ? nsd_num_cus() / M : 1;
+    s.G = a.B < per ? a.B : per;
+    hipLaunchKernelGGL(multi_stream48_kernel, dim3(M * s.G), dim3(NT), 0, st, a, s);
+    NSD_CHECK_LAUNCH("multi_stream_step");
+    if (mean) {
+        const int n = a.B * a.K;
+        hipLaunchKernelGGL(multi_stream_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float *)a.probs, mean, M, n);
+        NSD_CHECK_LAUNCH("multi_stream_mean");
+    }
+    return NSD_OK;
+}
+#endif

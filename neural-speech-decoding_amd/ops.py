@@ -1093,6 +1093,65 @@ def stream_step(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, state: tor
     return logits, probs
 
 
+# ---- resumable inference of M models per launch: an ensemble decoding live streams (nsd_multi_stream_* of include/nsd.h) ----
+
+def multi_stream_path(spec: ModelSpec, M: int) -> bool:
+    """True where nsd_multi_stream_step covers M models of this shape (stream_path and 1 <= M <= 32)."""
+    d = spec.dims(1, 1)
+    return spec.D == 1 and bool(_lib.lib().nsd_multi_stream_path(C.byref(d), int(M)))
+
+
+def multi_stream_state(spec: ModelSpec, M: int, S: int, device="cuda") -> torch.Tensor:
+    """A reset state of M models with S slots each on `device`: fp32 [M, S, stride].  state[m] is an ordinary stream_state of model m
+    (stream_step takes it as it is); the flat [M*S, stride] view is what stream_reset takes: slot m*S + s is stream s of model m."""
+    d = spec.dims(1, 1)
+    n = int(_lib.lib().nsd_multi_stream_state_bytes(C.byref(d), int(M), int(S)))
+    if n < 0:
+        check(n, "nsd_multi_stream_state_bytes")
+    state = torch.empty((int(M), int(S), int(stream_layout(spec).stride)), dtype=torch.float32, device=device)
+    if _nbytes(state) != n:
+        raise NsdError(f"multi_stream_state: {_nbytes(state)} bytes for nsd_multi_stream_state_bytes = {n}")
+    stream_reset(spec, state.view(int(M) * int(S), -1))
+    return state
+
+
+def multi_stream_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, state: torch.Tensor, *, slots: Optional[torch.Tensor] = None,
+                      residual: bool = False, read: bool = True, want_mean: bool = True, logits: Optional[torch.Tensor] = None,
+                      probs: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Advance B streams in each of M models by one launch: params [M,P], the chunk x [B,n,C] (shared by the models) or [M,B,n,C],
+    state [M,S,stride]; stream b lives in slot slots[b] (or b) of every model.  With read=True returns (logits [M,B,K], probs [M,B,K],
+    mean [B,K]): per model what stream_step gives, bit for bit, and the mean of the models' probabilities (a serial fp32 sum over the
+    models, divided by M; None with want_mean=False: no second launch).  read=False advances only and returns (None, None, None).
+    logits / probs / mean: optional caller-owned buffers."""
+    if params.dim() != 2:
+        raise NsdError(f"multi_stream_step: params must be [M, {spec.param_count}], got {tuple(params.shape)}")
+    M = int(params.shape[0])
+    if x.dim() not in (3, 4) or x.shape[-1] != spec.C or (x.dim() == 4 and int(x.shape[0]) != M):
+        raise NsdError(f"multi_stream_step: x must be [B, n, {spec.C}] or [{M}, B, n, {spec.C}], got {tuple(x.shape)}")
+    B, T = int(x.shape[-3]), int(x.shape[-2])
+    stride = B * T * spec.C if x.dim() == 4 else 0
+    if state.dim() != 3 or int(state.shape[0]) != M:
+        raise NsdError(f"multi_stream_step: state must be [{M}, S, stride], got {tuple(state.shape)}")
+    S = int(state.shape[1])
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"multi_stream_step: {int(slots.numel())} slot indices for {B} streams")
+    d = spec.dims(B, T)
+    if read:
+        logits = _out_f32(logits, (M, B, spec.K), x.device, "multi_stream_step: logits")
+        probs = _out_f32(probs, (M, B, spec.K), x.device, "multi_stream_step: probs")
+        mean = _out_f32(mean, (B, spec.K), x.device, "multi_stream_step: mean") if want_mean else None
+    else:
+        logits = probs = mean = None
+    pp = _dev_f32(params, "params", (M, spec.param_count))
+    if B == 0:
+        _dev_f32(state, "state")
+        return logits, probs, mean
+    _call("nsd_multi_stream_step", x.device, C.byref(d), M, pp, _dev_f32(x, "x"), stride, _slots_ptr(slots, "multi_stream_step"),
+          _lib.NSD_FLAG_RESIDUAL if residual else 0, _dev_f32(state, "state"), _nbytes(state), S, _dev_f32(logits, "logits"),
+          _dev_f32(probs, "probs"), _dev_f32(mean, "mean"), STREAM)
+    return logits, probs, mean
+
+
 # ---- causal front end for live streams and their training (nsd_prep_* of include/nsd.h; the configuration: prep.CausalPrep) ----
 
 def prep_path(C_: int, prep=None) -> bool:

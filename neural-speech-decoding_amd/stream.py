@@ -16,6 +16,11 @@ from . import ops
 from ._lib import NsdError
 
 
+_NORMALIZE_REFUSAL = ("StreamDecoder: normalize=True z-scores over the whole window, which a stream has not seen yet; "
+                      "normalise the chunks causally on the caller's side, or train the model with a causal front end "
+                      "(EEG_LSTM(prep=CausalPrep.design(zscore_seconds=...)))")
+
+
 class StreamDecoder:
     """`streams` independent live streams of one eval-mode EEG_LSTM, each with its own slot of device state.
 
@@ -40,9 +45,7 @@ class StreamDecoder:
             raise NsdError("StreamDecoder: the bf16 sequence path and bidirectional models are not resumable (a bidirectional model is "
                            "not causal); use an fp32, one-directional EEG_LSTM")
         if model.normalize:
-            raise NsdError("StreamDecoder: normalize=True z-scores over the whole window, which a stream has not seen yet; "
-                           "normalise the chunks causally on the caller's side, or train the model with a causal front end "
-                           "(EEG_LSTM(prep=CausalPrep.design(zscore_seconds=...)))")
+            raise NsdError(_NORMALIZE_REFUSAL)
         if not ops.stream_path(model.spec):
             raise NsdError(f"StreamDecoder: model shape {model.spec} is outside nsd_stream_path (hidden size 48, 2 layers, <= 8 channels, "
                            "fc width and classes <= 64)")
@@ -88,6 +91,9 @@ class StreamDecoder:
             if out is None:
                 out = self._prepped[tuple(x.shape)] = torch.empty_like(x)
             x = ops.prep_step(x, self.prep, self.prep_state, slots=slots, out=out)
+        return self._step(x, slots, read)
+
+    def _step(self, x: torch.Tensor, slots, read: bool) -> Optional[torch.Tensor]:
         _, probs = ops.stream_step(self.model.spec, self.model.flat_parameters(), x, self.state, slots=slots,
                                    residual=self.model.residual, read=read)
         return probs
@@ -121,12 +127,86 @@ class StreamDecoder:
             self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
 
 
+class EnsembleStreamDecoder(StreamDecoder):
+    """`streams` independent live streams decoded by an ensemble of M eval-mode EEG_LSTM models of one shape: every push advances all
+    M models in one launch (nsd_multi_stream_step) and returns the mean of their class probabilities.  StreamDecoder's surface:
+
+      push(samples, slots=None, read=True)   -> mean probabilities [B, K] (device tensor; a serial fp32 sum over the models divided by
+                                             M), or None with read=False
+      member_probs                           the models' own probabilities [M, B, K] of the last read: bit for bit what M StreamDecoders
+                                             return (None before the first read)
+      reset(slots=None), steps               as StreamDecoder's (a slot is reset in every model; the models' step counts agree)
+      state_dict() / load_state_dict()       the [M, S, stride] state (+ the front end's)
+
+    models: a sequence of EEG_LSTM (checked as EnsemblePredictor checks them: one shape and options, fp32, one direction), or the
+    ensemble an EnsemblePredictor holds (its stacked [M, P] parameter buffer is then used, not a copy).  The members share one causal
+    front end (equal `prep`): one prep state of S slots, nsd_prep_step once per push, its output read by all models."""
+
+    def __init__(self, models, streams: int = 1):
+        from .lstm_eeg_model import EEG_LSTM
+        from .multimodel import _check_models
+        who = "EnsembleStreamDecoder"
+        params = getattr(models, "params", None)
+        members = list(getattr(models, "models", models))
+        for m in members:
+            if not isinstance(m, EEG_LSTM):
+                raise NsdError(f"{who}: expected EEG_LSTM members, got {type(m).__name__}")
+        _check_models(members, who)
+        first = members[0]
+        if any(m.training for m in members):
+            raise NsdError(f"{who}: the models must be in eval mode (model.eval()): a stream is decoded without dropout")
+        if first.normalize:
+            raise NsdError(_NORMALIZE_REFUSAL.replace("StreamDecoder", who, 1))
+        if not ops.multi_stream_path(first.spec, len(members)):
+            raise NsdError(f"{who}: {len(members)} models of shape {first.spec} are outside nsd_multi_stream_path (nsd_stream_path: hidden "
+                           "size 48, 2 layers, <= 8 channels, fc width and classes <= 64; 1 <= M <= 32)")
+        if int(streams) < 1:
+            raise NsdError(f"{who}: streams = {streams}")
+        if not all(m.flat_parameters().is_cuda for m in members):
+            raise NsdError(f"{who} runs only on the MI355X HIP path: move the models to the GPU first; there is no CPU fallback")
+        self.members, self.model, self.streams = members, first, int(streams)
+        self.params = params if params is not None else torch.stack([m.flat_parameters() for m in members]).contiguous()
+        self.device = self.params.device
+        self._layout = ops.stream_layout(first.spec)
+        self.state = ops.multi_stream_state(first.spec, len(members), self.streams, self.device)
+        self.prep = first.prep
+        self.prep_state = None if self.prep is None else ops.prep_state(first.spec.C, self.streams, self.device)
+        self._prepped = {}
+        self.member_probs: Optional[torch.Tensor] = None
+
+    def _step(self, x: torch.Tensor, slots, read: bool) -> Optional[torch.Tensor]:
+        _, probs, mean = ops.multi_stream_step(self.model.spec, self.params, x, self.state, slots=slots, residual=self.model.residual,
+                                               read=read)
+        if read:
+            self.member_probs = probs
+        return mean
+
+    def reset(self, slots=None) -> None:
+        slots = self._slots(slots)
+        M, S = len(self.members), self.streams
+        flat = self.state.view(M * S, -1)
+        if slots is None:
+            ops.stream_reset(self.model.spec, flat)
+        else:                                               # slot s of every model: m*S + s of the flat state
+            every = (slots[None, :] + S * torch.arange(M, dtype=torch.int32, device=self.device)[:, None]).reshape(-1).contiguous()
+            ops.stream_reset(self.model.spec, flat, every)
+        if self.prep is not None:
+            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+
+    @property
+    def steps(self) -> np.ndarray:
+        col = int(self._layout.steps) // 2
+        return self.state[0].view(torch.int64)[:, col].cpu().numpy().copy()
+
+
 class PredictorStream:
-    """What SimplePredictor.open_stream returns: numpy chunks in, (probs float32 [B, K], labels) out -- predict(), chunk by chunk."""
+    """What SimplePredictor.open_stream returns: numpy chunks in, (probs float32 [B, K], labels) out -- predict(), chunk by chunk.
+    A predictor with `members` (EnsemblePredictor) is decoded by all of them: an EnsembleStreamDecoder, the probabilities are their mean."""
 
     def __init__(self, predictor, streams: int, chunk_transform=None):
         self.predictor, self.chunk_transform = predictor, chunk_transform
-        self.decoder = StreamDecoder(predictor.model, streams)
+        ensemble = getattr(predictor, "members", None) is not None
+        self.decoder = EnsembleStreamDecoder(predictor.model, streams) if ensemble else StreamDecoder(predictor.model, streams)
 
     def push(self, chunk: np.ndarray, slots=None, read: bool = True):
         x = np.asarray(chunk)

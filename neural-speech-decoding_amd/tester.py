@@ -125,6 +125,16 @@ def _report(res: TrialResult) -> None:
         print(f"Averaged chunk shape: {res.avg_chunk.shape}")
 
 
+def _predictor(model_path, sr, channels, num_channels: int, predictor_kwargs: Optional[dict]):
+    """The reference's predictor of one checkpoint; a list / tuple of checkpoints: an EnsemblePredictor of them (an extension)."""
+    kw = dict(channel_order=channels, input_size=num_channels, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, device="cpu",
+              tailoring_lambda=1.25e-29, class_names=list(_HARNESS_LABELS), **(predictor_kwargs or {}))
+    if isinstance(model_path, (list, tuple)):
+        from .multimodel import EnsemblePredictor
+        return EnsemblePredictor([resolve_model_path(p) for p in model_path], sr, **kw)
+    return SimplePredictor(pth_path=resolve_model_path(model_path), sr=sr, **kw)
+
+
 def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels: int = 8, window_seconds: float = 5.0,
                model_path: str = DEFAULT_MODEL, verbose: bool = True, *, producer_factory=None,
                queue_timeout: float = 6.5, predictor_kwargs: Optional[dict] = None, chunk_seconds: Optional[float] = None,
@@ -137,6 +147,7 @@ def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels
     {"preprocess": "identity"} when the reference's MindsAI filter is not importable), `chunk_seconds` (None: the window mode
     above; a value: the producer cuts every window into chunks of that length and a resumable decoder -- SimplePredictor.open_stream
     -- advances while they arrive; the trial's decision is read at its last chunk) with `chunk_transform` (open_stream's).
+    `model_path` may also be a list of checkpoints: an EnsemblePredictor decodes, in both modes (the mean of the models' probabilities).
     """
     if chunk_seconds is not None:
         return _run_trials_chunked(trials, serial_port, num_channels, window_seconds, model_path, verbose, producer_factory,
@@ -151,10 +162,7 @@ def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels
         while mean.n < trials:
             window, sr, channels = next(source)
             if predictor is None:          # built lazily: the sampling rate and channel list come with the first window
-                predictor = SimplePredictor(pth_path=resolve_model_path(model_path), sr=sr, channel_order=channels,
-                                            input_size=num_channels, hidden_size=48, num_layers=2, num_classes=3,
-                                            dropout=0.60, device="cpu", tailoring_lambda=1.25e-29,
-                                            class_names=list(_HARNESS_LABELS), **(predictor_kwargs or {}))
+                predictor = _predictor(model_path, sr, channels, num_channels, predictor_kwargs)
             probs, label = predictor.predict(window)
             mean.add(probs, window)
             if verbose:
@@ -177,10 +185,7 @@ def _run_trials_chunked(trials, serial_port, num_channels, window_seconds, model
         while mean.n < trials:
             payload = next(source)
             if stream is None:
-                predictor = SimplePredictor(pth_path=resolve_model_path(model_path), sr=payload["sr"], channel_order=payload.get("channels"),
-                                            input_size=num_channels, hidden_size=48, num_layers=2, num_classes=3,
-                                            dropout=0.60, device="cpu", tailoring_lambda=1.25e-29,
-                                            class_names=list(_HARNESS_LABELS), **(predictor_kwargs or {}))
+                predictor = _predictor(model_path, payload["sr"], payload.get("channels"), num_channels, predictor_kwargs)
                 stream = predictor.open_stream(streams=1, chunk_transform=chunk_transform)
             if payload["seq"] == 0:            # a window starts: whatever an interrupted one left is dropped
                 stream.reset()

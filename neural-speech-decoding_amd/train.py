@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
 
@@ -139,6 +140,9 @@ def main(argv=None) -> int:
                                                          "no epoch selection), then --out is trained on ALL trials with the same recipe")
     ap.add_argument("--concurrent", action="store_true", help="with --kfold: train the folds together, one model-batched step for all "
                                                                 "of them (ModelBatchTrainer; single GPU, H = 48 fp32)")
+    ap.add_argument("--save-folds", action="store_true", help="with --kfold K (sequential or --concurrent): keep the fold models -- each is "
+                    "written after its last epoch next to --out, as <out stem>.fold<f>.pth (<out stem>.seed<s>_fold<f>.pth with "
+                    "--kfold-seeds), and the final JSON line lists them under fold_checkpoints: the members of an EnsemblePredictor")
     ap.add_argument("--kfold-seeds", type=int, default=1, help="with --kfold K --concurrent: the K folds for N seeds --seed .. --seed + N - 1 "
                                                               "in the same launches (N * K <= 32)")
     ap.add_argument("--aug-shift", type=int, default=0, help="augmentation: shift each training trial by up to +-N steps (0 = off)")
@@ -203,6 +207,8 @@ def main(argv=None) -> int:
         ap.error(str(e))
     if augment.max_shift >= args.T:
         ap.error(f"--aug-shift {augment.max_shift} must be smaller than --T {args.T}")
+    if args.save_folds and (args.kfold < 2 or not args.out):
+        ap.error("--save-folds keeps the fold models of --kfold K (K >= 2) next to --out")
     if args.kfold_seeds != 1 and not args.concurrent:
         ap.error("--kfold-seeds needs --kfold K --concurrent (sequentially: one --kfold run per --seed)")
     if args.concurrent:
@@ -247,6 +253,18 @@ def main(argv=None) -> int:
         if args.log_jsonl:
             with open(args.log_jsonl, "a") as f:
                 f.write(line + "\n")
+
+    def fold_path(tag: str) -> str:
+        return f"{os.path.splitext(args.out)[0]}.{tag}.pth"
+
+    def done_extra() -> dict:
+        """What --save-folds adds to the final line; without the flag the line is what it was (the flag itself is left out of args)."""
+        return {"fold_checkpoints": fold_paths} if args.save_folds else {}
+
+    def shown_args() -> dict:
+        return {k: v for k, v in vars(args).items() if k != "save_folds" or v}
+
+    fold_paths = []
 
     def fit(tr_idx, va_idx, seed: int, tag: str, out_path, keep_best: bool):
         """Train one model on tr_idx for args.epochs epochs.  keep_best: write the checkpoint of the best validation epoch
@@ -331,6 +349,9 @@ def main(argv=None) -> int:
         accs = []
         for k, r in enumerate(runs):
             accs.append(res[k]["acc_val_last"])
+            if args.save_folds:
+                fold_paths.append(fold_path(tag(r)))
+                save_reference_checkpoint(models[k], fold_paths[-1])
             rec = {"fold": r["fold"], "n_train": int(len(r["tr"])), "n_val": int(len(r["va"])),
                    "acc_val_last_epoch": round(res[k]["acc_val_last"], 4), "acc_train_last_epoch": round(res[k]["acc_train_last"], 4),
                    "concurrent": True}
@@ -343,7 +364,7 @@ def main(argv=None) -> int:
               "acc_val_sd": round(float(np.std(accs, ddof=1)), 4),
               "acc_val_folds": [round(float(a), 4) for a in accs], "selection": "none: fixed epoch count, last-epoch model",
               "shipped": {"checkpoint": args.out, "trained_on": int(len(everything)), "acc_train_last_epoch": r["acc_train_last"]},
-              "world": world, "concurrent": True, "args": {k: v for k, v in vars(args).items()}})
+              "world": world, "concurrent": True, "args": shown_args(), **done_extra()})
         return 0
 
     if args.kfold > 1:
@@ -353,7 +374,9 @@ def main(argv=None) -> int:
         accs = []
         for f, va in enumerate(folds):
             tr = np.setdiff1d(np.arange(len(y_np)), va)
-            r = fit(tr, va, args.seed + 101 * f, f"fold{f}", None, keep_best=False)
+            if args.save_folds:
+                fold_paths.append(fold_path(f"fold{f}"))
+            r = fit(tr, va, args.seed + 101 * f, f"fold{f}", fold_paths[-1] if args.save_folds else None, keep_best=False)
             accs.append(r["acc_val_last"])
             emit({"fold": f, "n_train": int(len(tr)), "n_val": int(len(va)), "acc_val_last_epoch": round(r["acc_val_last"], 4),
                   "acc_train_last_epoch": round(r["acc_train_last"], 4)})
@@ -363,13 +386,13 @@ def main(argv=None) -> int:
               "acc_val_sd": round(float(np.std(accs, ddof=1)), 4) if rank == 0 else None,
               "acc_val_folds": [round(float(a), 4) for a in accs], "selection": "none: fixed epoch count, last-epoch model",
               "shipped": {"checkpoint": args.out, "trained_on": int(len(everything)), "acc_train_last_epoch": r["acc_train_last"]},
-              "world": world, "args": {k: v for k, v in vars(args).items()}})
+              "world": world, "args": shown_args(), **done_extra()})
         return 0
 
     r = fit(tr_idx, va_idx, args.seed, "split", args.out, keep_best=True)
     emit({"done": True, "best_val_acc": r["best_val_acc"], "best_epoch": r["best_epoch"], "acc_val_last_epoch": r["acc_val_last"],
           "checkpoint": args.out, "world": world,
-          "n_train": int(len(tr_idx)), "n_val": int(len(va_idx)), "args": {k: v for k, v in vars(args).items()}})
+          "n_train": int(len(tr_idx)), "n_val": int(len(va_idx)), "args": shown_args()})
     return 0
 
 
