@@ -523,6 +523,63 @@ int nsd_multi_stream_step(const nsd_dims *d, int32_t M, const float *params, con
                           void *stream);
 
 /*
+ * ---- sliding-window decisions for continuous streams in one launch per chunk (an EXTENSION, of nsd_stream_*) ----
+ *
+ * "Every `hop` samples, the decision of the model run from a zero state over the last `window` samples."  window = W >= 1, hop = Hp with
+ * 1 <= Hp <= W, W % Hp == 0 and R = W / Hp <= NSD_WINDOW_MAX_PHASES.  A stream's samples are numbered from its last reset, n = 0, 1, ...
+ * Window k (k = 0, 1, ...) covers samples [k Hp, k Hp + W); its END is e_k = k Hp + W, and its decision exists once sample e_k - 1 has been
+ * pushed.  PHASE r = k mod R decodes the windows k = r (mod R): it idles until sample r Hp, then runs its windows back to back, each from
+ * a reset slot.
+ * Contract.  The decision of window k is bit for bit what nsd_stream_step writes (logits and probs) when a freshly reset slot is given
+ * x[k Hp : k Hp + W] -- whatever the cut of the stream into calls, B, the slot, the placement in the grid, the HIP stream or a graph replay.
+ * State: per stream R PHASE SLOTS followed by a header, stream_stride floats in all; S streams.  A phase slot is an ordinary slot of the
+ * public nsd_stream_layout (phase_stride = its stride); its step count is the number of samples its current window has consumed, in
+ * [0, W), and it can be copied out and handed to nsd_stream_step as it is.  The header records W and Hp (int32 words at the float offsets
+ * `window` and `hop` from the stream's start) and the stream's int64 sample count n at `count` (8-byte aligned).  The count is kept once
+ * per phase, R consecutive int64 from `count` on, all equal between calls: each phase's workgroup reads and writes its own copy, so that
+ * no workgroup of a launch reads a word another one writes.  Everything a call needs is derived on the device from n: nothing in the
+ * arguments changes from call to call, and nsd_prep_step + nsd_window_step can be captured once and replayed.
+ *   nsd_window_path          1 where nsd_stream_path(d) and the conditions on W and Hp above hold, else 0
+ *   nsd_window_rows          D = ceil(T / hop): the decisions a call of T samples can complete per stream; <0 for T < 1 or an invalid w
+ *   nsd_window_state_bytes   bytes of a state of S >= 1 streams (S * stream_stride * 4); <0 outside nsd_window_path or for S < 1
+ *   nsd_window_state_layout  phases = R, phase_stride, window, hop, count, stream_stride: float offsets from a stream's start
+ *   nsd_window_reset         slots == NULL: all S streams; else the n streams of the DEVICE array slots[n] (indices outside [0, S) are
+ *                            skipped).  Every phase slot becomes a reset nsd_stream_layout slot, the header records W and Hp, n = 0.  A
+ *                            state is reset once before its first nsd_window_step, and again to change W or Hp.
+ *   nsd_window_step          d->B streams, chunk length d->T >= 1, x [B,T,C]; slots: DEVICE int32[B] of distinct indices in [0, S), or
+ *                            NULL for 0 .. B-1; flags: NSD_FLAG_RESIDUAL.  Outputs, with D = nsd_window_rows(d->T, w) and n0 the
+ *                            stream's count before the call: the windows with n0 < e_k <= n0 + T are written in ascending e_k to rows
+ *                            0 .. counts[b] - 1 of logits [B,D,K] and probs [B,D,K] (or NULL), ends[b,i] = e_k (int64 [B,D]); rows
+ *                            counts[b] .. D-1 are written too, NaN in logits / probs and -1 in ends, so that a call's outputs are a
+ *                            function of its inputs.  counts: int32 [B].
+ * Failure behaviour.  Every refusal happens before any launch: NSD_E_INVALID for NULL d / w / params / x / state / logits / ends /
+ * counts, a shape outside nsd_window_path, T < 1, S < 1, n < 0 or n > S (reset), B > S, flags other than NSD_FLAG_RESIDUAL, B * D * K
+ * above 2^31 - 1; NSD_E_WORKSPACE when state_bytes < nsd_window_state_bytes(d, w, S).  B = 0 (n = 0) launches nothing.  Seen on the device
+ * only, and never silent: a slot index outside [0, S), or a stream whose header records another (W, Hp) than the call's, is skipped -- all
+ * its D rows are NaN / -1, counts[b] = -1, no state is touched.  Duplicate slots in one call are undefined.  A sample that is not finite
+ * (NaN or +-Inf) poisons exactly the windows that contain it: their rows are NaN, every other window's rows are the bits of the clean
+ * run, and the stream heals on its own once the sample has left every window, because a phase's reset overwrites its state.  No host
+ * synchronisation, no allocation.  Additive: NSD_VERSION stays 301, a caller detects the feature by the symbols.
+ */
+#define NSD_WINDOW_MAX_PHASES 128
+typedef struct nsd_window { int32_t window, hop; } nsd_window;
+typedef struct nsd_window_layout {
+    int64_t phases, phase_stride;                   /* R phase slots of phase_stride floats each, from the stream's start */
+    int64_t window, hop;                            /* int32 words: float offsets */
+    int64_t count;                                  /* int64 sample count (R copies, one per phase): float offset, even */
+    int64_t stream_stride;                          /* floats per stream, a multiple of 4 */
+} nsd_window_layout;
+int     nsd_window_path(const nsd_dims *d, const nsd_window *w);
+int32_t nsd_window_rows(int32_t T, const nsd_window *w);
+int64_t nsd_window_state_bytes(const nsd_dims *d, const nsd_window *w, int32_t S);
+int     nsd_window_state_layout(const nsd_dims *d, const nsd_window *w, nsd_window_layout *out);
+int     nsd_window_reset(const nsd_dims *d, const nsd_window *w, void *state, int64_t state_bytes, int32_t S, const int32_t *slots,
+                         int32_t n, void *stream);
+int     nsd_window_step(const nsd_dims *d, const nsd_window *w, const float *params, const float *x, const int32_t *slots, uint32_t flags,
+                        void *state, int64_t state_bytes, int32_t S, float *logits, float *probs, int64_t *ends, int32_t *counts,
+                        void *stream);
+
+/*
  * ---- causal front end for live streams and their training (an EXTENSION: the reference filters whole windows on the host) ----
  *
  * A per-channel transform that can run chunk by chunk in front of nsd_stream_step, and over whole windows in a training step, so that a

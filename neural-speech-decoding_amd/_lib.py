@@ -71,6 +71,19 @@ class StreamLayout(C.Structure):
                 + [(n, C.c_int64) for n in ("pool_max", "pool_den", "pool_acc", "steps", "stride")])
 
 
+class Window(C.Structure):
+    """nsd_window of include/nsd.h: window and hop of a sliding-window decoder, in samples"""
+    _fields_ = [("window", C.c_int32), ("hop", C.c_int32)]
+
+
+class WindowLayout(C.Structure):
+    """nsd_window_layout of include/nsd.h: float offsets inside one stream of a window state"""
+    _fields_ = [(n, C.c_int64) for n in ("phases", "phase_stride", "window", "hop", "count", "stream_stride")]
+
+
+NSD_WINDOW_MAX_PHASES = 128
+
+
 class Prep(C.Structure):
     """nsd_prep of include/nsd.h"""
     _fields_ = [("flags", C.c_uint32), ("n_sections", C.c_int32), ("sos", (C.c_float * 5) * 4), ("alpha", C.c_float), ("var0", C.c_float)]
@@ -176,6 +189,13 @@ SYMBOLS = {
     "nsd_multi_stream_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_multi_stream_state_bytes": (C.c_int64, [_dp, C.c_int32, C.c_int32]),
     "nsd_multi_stream_step": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _fp, _vp]),
+    # sliding-window decisions for continuous streams
+    "nsd_window_path": (C.c_int, [_dp, C.POINTER(Window)]),
+    "nsd_window_rows": (C.c_int32, [C.c_int32, C.POINTER(Window)]),
+    "nsd_window_state_bytes": (C.c_int64, [_dp, C.POINTER(Window), C.c_int32]),
+    "nsd_window_state_layout": (C.c_int, [_dp, C.POINTER(Window), C.POINTER(WindowLayout)]),
+    "nsd_window_reset": (C.c_int, [_dp, C.POINTER(Window), _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
+    "nsd_window_step": (C.c_int, [_dp, C.POINTER(Window), _fp, _fp, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _vp, _ip, _vp]),
     # causal front end for live streams and their training
     "nsd_prep_path": (C.c_int, [C.c_int32, _vp]),
     "nsd_prep_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

@@ -1059,6 +1059,84 @@ int nsd_multi_stream_step(const nsd_dims *d, int32_t M, const float *params, con
     return nsd_multi_stream48_launch(a, model_split(d, x_model_stride), M, mean_probs, (hipStream_t)stream);
 }
 
+// ---- sliding-window decisions (nsd_window48.hip): state [S][R phase slots + header] ----
+static bool window_ok(const nsd_window *w) {
+    return w && w->window >= 1 && w->hop >= 1 && w->hop <= w->window && w->window % w->hop == 0 && w->window / w->hop <= NSD_WINDOW_MAX_PHASES;
+}
+// the preamble of the entry points that touch a window state: shape, pointers, stream count, size
+static int window_enter(const nsd_dims *d, const nsd_window *w, const char *who, bool ptrs_ok, const void *state, int64_t state_bytes, int32_t S) {
+    if (!d || !w) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (!stream_shape(d) || !window_ok(w)) {
+        nsd_set_error("%s: outside nsd_window_path (nsd_stream_path, 1 <= hop <= window, window %% hop == 0, window / hop <= %d): window %d, hop %d",
+                      who, NSD_WINDOW_MAX_PHASES, w->window, w->hop);
+        return NSD_E_INVALID;
+    }
+    if (!ptrs_ok || !state) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (S < 1) { nsd_set_error("%s: S = %d streams", who, S); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)S * window_stream_stride(w->window / w->hop) * (int64_t)sizeof(float);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_window_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int nsd_window_path(const nsd_dims *d, const nsd_window *w) { return stream_shape(d) && window_ok(w) ? 1 : 0; }
+
+int32_t nsd_window_rows(int32_t T, const nsd_window *w) {
+    if (T < 1 || !window_ok(w)) { nsd_set_error("window_rows: T = %d, or an invalid window / hop", T); return NSD_E_INVALID; }
+    return (int32_t)(((int64_t)T + w->hop - 1) / w->hop);
+}
+
+int64_t nsd_window_state_bytes(const nsd_dims *d, const nsd_window *w, int32_t S) {
+    if (!nsd_window_path(d, w) || S < 1) { nsd_set_error("window_state_bytes: outside nsd_window_path, or S < 1"); return NSD_E_INVALID; }
+    return (int64_t)S * window_stream_stride(w->window / w->hop) * (int64_t)sizeof(float);
+}
+
+int nsd_window_state_layout(const nsd_dims *d, const nsd_window *w, nsd_window_layout *out) {
+    if (!nsd_window_path(d, w) || !out) { nsd_set_error("window_state_layout: outside nsd_window_path, or null pointer"); return NSD_E_INVALID; }
+    const int R = w->window / w->hop;
+    memset(out, 0, sizeof(*out));
+    out->phases = R; out->phase_stride = STREAM_STRIDE;
+    out->window = (int64_t)R * STREAM_STRIDE + WINDOW_HDR_W; out->hop = (int64_t)R * STREAM_STRIDE + WINDOW_HDR_HOP;
+    out->count = (int64_t)R * STREAM_STRIDE + WINDOW_HDR_COUNT;
+    out->stream_stride = window_stream_stride(R);
+    return NSD_OK;
+}
+
+int nsd_window_reset(const nsd_dims *d, const nsd_window *w, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n,
+                     void *stream) {
+    static const char *who = "window_reset";
+    if (const int rc = window_enter(d, w, who, true, state, state_bytes, S)) return rc;
+    if (slots && (n < 0 || n > S)) { nsd_set_error("%s: n = %d streams of S = %d", who, n, S); return NSD_E_INVALID; }
+    const int count = slots ? n : S;
+    if (count == 0) return NSD_OK;
+    return nsd_window_reset_launch((float *)state, S, slots, count, w->window, w->hop, (hipStream_t)stream);
+}
+
+int nsd_window_step(const nsd_dims *d, const nsd_window *w, const float *params, const float *x, const int32_t *slots, uint32_t flags,
+                    void *state, int64_t state_bytes, int32_t S, float *logits, float *probs, int64_t *ends, int32_t *counts, void *stream) {
+    static const char *who = "window_step";
+    if (!d || !w) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (const int rc = window_enter(d, w, who, params && x && logits && ends && counts, state, state_bytes, S)) return rc;
+    if (flags & ~NSD_FLAG_RESIDUAL) { nsd_set_error("%s: flags 0x%x (only NSD_FLAG_RESIDUAL applies)", who, flags); return NSD_E_INVALID; }
+    if (d->T < 1) { nsd_set_error("%s: chunk length T = %d", who, d->T); return NSD_E_INVALID; }
+    if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d", who, d->B, S); return NSD_E_INVALID; }
+    const int R = w->window / w->hop, D = nsd_window_rows(d->T, w);
+    if ((int64_t)d->B * D * d->K > 0x7fffffff || (int64_t)d->B * R > 0x7fffffff) {
+        nsd_set_error("%s: B * D * K = %lld output values (B * R = %lld workgroup passes) in one launch", who, (long long)d->B * D * d->K, (long long)d->B * R);
+        return NSD_E_INVALID;
+    }
+    if (d->B == 0) return NSD_OK;
+    WindowArgs a;
+    memset(&a, 0, sizeof(a));
+    static_cast<StreamArgs &>(a) = build_stream(d, params, x, slots, flags, state, S, logits, probs);
+    a.ends = (long long *)ends; a.counts = counts;
+    a.W = w->window; a.Hp = w->hop; a.R = R; a.D = D;
+    return nsd_window48_launch(a, (hipStream_t)stream);
+}
+
 // ---- causal front end (nsd_prep_*, include/nsd.h; nsd_prep.hip) ----
 static bool prep_channels(int32_t C) { return C >= 1 && C <= 64; }
 static bool prep_finite(float v) { return v - v == 0.f; }

@@ -221,6 +221,21 @@ struct StreamArgs {
 int nsd_stream48_launch(const StreamArgs &a, hipStream_t st);
 int nsd_stream_reset_launch(float *state, int S, const int32_t *slots, int n, hipStream_t st);
 
+// sliding-window decisions (nsd_window_* of nsd.h; nsd_window48.hip).  One stream of the caller's state, in floats: R = window / hop PHASE
+// SLOTS of STREAM_STRIDE floats in the layout above, then a header: the recorded window and hop (int32), two zero words, and one int64
+// sample count PER PHASE.  Phase r's workgroup reads and writes its own copy only, so no workgroup of a launch reads a word that another
+// one writes; between calls all copies are equal and phase 0's is the public one (nsd_window_layout.count).
+constexpr int WINDOW_HDR_W = 0, WINDOW_HDR_HOP = 1, WINDOW_HDR_COUNT = 4 /* int64[R]: 8-byte aligned */;
+__host__ __device__ constexpr int window_hdr_floats(int R) { return (WINDOW_HDR_COUNT + 2 * R + 3) & ~3; }
+__host__ __device__ constexpr int window_stream_stride(int R) { return R * STREAM_STRIDE + window_hdr_floats(R); }
+struct WindowArgs : StreamArgs {             // T: the chunk; logits / probs [B,D,K]
+    long long *ends;                         // [B,D]
+    int32_t *counts;                         // [B]
+    int W, Hp, R, D;
+};
+int nsd_window48_launch(const WindowArgs &a, hipStream_t st);
+int nsd_window_reset_launch(float *state, int S, const int32_t *slots, int n, int W, int Hp, hipStream_t st);
+
 // causal front end (nsd_prep_* of nsd.h; nsd_prep.hip).  One slot of the caller's state, in floats -- the public layout
 // nsd_prep_state_layout reports; it holds room for NSD_PREP_MAX_SECTIONS sections and depends on C alone
 constexpr int PREP_X0 = 0;

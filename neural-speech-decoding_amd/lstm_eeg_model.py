@@ -437,6 +437,7 @@ class SimplePredictor:
         """A checkpoint written from a model with a causal front end carries it ({"state_dict": ..., "nsd_prep": CausalPrep.to_dict()},
         trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep."""
         self.device = torch.device(device)
+        self.sr = sr
         self.class_names = class_names or CLASS_NAMES
         if preprocess is None:
             self.pre = _default_preprocessor(sr, tailoring_lambda, preprocess_package)
@@ -494,7 +495,8 @@ class SimplePredictor:
         return probs, [self.class_names[int(i)] for i in probs.argmax(1)]
 
 
-    def open_stream(self, streams: int = 1, chunk_transform=None):
+    def open_stream(self, streams: int = 1, chunk_transform=None, *, window_seconds: Optional[float] = None,
+                    hop_seconds: Optional[float] = None):
         """Resumable decoding (an extension, see stream.py): a PredictorStream whose push(chunk [n,C] or [B,n,C]) advances `streams`
         live streams and returns (probs, labels) of each stream's whole prefix -- predict() on the samples seen so far, without
         waiting for the window to end.  Allowed when the predictor's preprocessor is the identity one, or when the caller passes
@@ -502,10 +504,17 @@ class SimplePredictor:
         A model with a causal front end (EEG_LSTM(prep=...), rebuilt from its checkpoint) filters and normalises the chunks on the GPU,
         with its state carried from chunk to chunk: what the model is fed is bit for bit what predict() feeds it on the whole window, and
         the probabilities after the last chunk are predict()'s within the resumable path's own bound against nsd_infer (measured 1.5e-7;
-        the readout's pooling is updated per step, nsd_infer's per block of steps, so the last bits can differ)."""
-        from .stream import PredictorStream
+        the readout's pooling is updated per step, nsd_infer's per block of steps, so the last bits can differ).
+        window_seconds and hop_seconds (both, or neither: the object above, unchanged): a continuous stream without cues -- a
+        PredictorSlidingStream whose push returns, per stream, a list of (end_sample, probs float32 [K], label) for the windows the
+        chunk completed: every hop_seconds, the decision of the model run from a zero state over the last window_seconds."""
+        from .stream import PredictorSlidingStream, PredictorStream
+        if (window_seconds is None) != (hop_seconds is None):
+            raise ValueError("SimplePredictor.open_stream: window_seconds and hop_seconds go together (both, or neither)")
         if chunk_transform is None and not isinstance(self.pre, IdentityPreProcessor):
             raise NsdError("SimplePredictor.open_stream: the reference's window filter (PreProcessor.transform, preprocessor.py:21-36) "
                            "works on a whole window and is not causal, so a stream cannot be filtered with it chunk by chunk; pass "
                            "chunk_transform=<causal [n,C] -> [n,C] callable>, or build the predictor with preprocess=\"identity\"")
+        if window_seconds is not None:
+            return PredictorSlidingStream(self, streams, chunk_transform, int(round(window_seconds * self.sr)), int(round(hop_seconds * self.sr)))
         return PredictorStream(self, streams, chunk_transform)

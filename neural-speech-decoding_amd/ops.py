@@ -1152,6 +1152,105 @@ def multi_stream_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, st
     return logits, probs, mean
 
 
+# ---- sliding-window decisions for continuous streams (nsd_window_* of include/nsd.h) ----
+
+def _window(window: int, hop: int) -> "_lib.Window":
+    return _lib.Window(int(window), int(hop))
+
+
+def window_path(spec: ModelSpec, window: int, hop: int) -> bool:
+    """True where nsd_window_step covers this model with this window and hop (stream_path; 1 <= hop <= window, window % hop == 0,
+    window / hop <= 128)."""
+    if not (-2 ** 31 <= int(window) < 2 ** 31 and -2 ** 31 <= int(hop) < 2 ** 31):
+        return False
+    d, w = spec.dims(1, 1), _window(window, hop)
+    return spec.D == 1 and bool(_lib.lib().nsd_window_path(C.byref(d), C.byref(w)))
+
+
+def window_rows(T: int, window: int, hop: int) -> int:
+    """D = ceil(T / hop): the decisions a chunk of T samples can complete per stream."""
+    w = _window(window, hop)
+    n = int(_lib.lib().nsd_window_rows(int(T), C.byref(w)))
+    if n < 0:
+        check(n, "nsd_window_rows")
+    return n
+
+
+def window_layout(spec: ModelSpec, window: int, hop: int) -> "_lib.WindowLayout":
+    """Float offsets inside one stream of a window state: `phases` phase slots of `phase_stride` floats (stream_layout slots), the int32
+    words `window` and `hop`, the int64 sample `count`, and `stream_stride`."""
+    d, w, lay = spec.dims(1, 1), _window(window, hop), _lib.WindowLayout()
+    check(_lib.lib().nsd_window_state_layout(C.byref(d), C.byref(w), C.byref(lay)), "nsd_window_state_layout")
+    return lay
+
+
+def window_state(spec: ModelSpec, window: int, hop: int, S: int, device="cuda") -> torch.Tensor:
+    """A reset window state of S streams on `device`: fp32 [S, stream_stride] (window_layout names the columns)."""
+    d, w = spec.dims(1, 1), _window(window, hop)
+    n = int(_lib.lib().nsd_window_state_bytes(C.byref(d), C.byref(w), int(S)))
+    if n < 0:
+        check(n, "nsd_window_state_bytes")
+    state = torch.empty((int(S), n // (4 * int(S))), dtype=torch.float32, device=device)
+    window_reset(spec, window, hop, state)
+    return state
+
+
+def window_reset(spec: ModelSpec, window: int, hop: int, state: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """Reset all streams of `state`, or the ones a device int32 tensor names: every phase slot a reset stream slot, sample count 0,
+    window and hop recorded in the header."""
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    d, w = spec.dims(0, 1), _window(window, hop)
+    n = 0 if slots is None else int(slots.numel())
+    if slots is not None and n == 0:
+        return
+    _call("nsd_window_reset", state.device, C.byref(d), C.byref(w), _dev_f32(state, "state"), _nbytes(state), S,
+          _slots_ptr(slots, "window_reset"), n, STREAM)
+
+
+_window_out = {}   # (device, B, D, K) -> (logits, probs, ends, counts): a chunk shape's outputs are reused, window_step allocates once
+
+
+def window_step(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, state: torch.Tensor, *, window: int, hop: int,
+                slots: Optional[torch.Tensor] = None, residual: bool = False,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Advance B continuous streams by the chunk x [B,n,C] (stream b lives in slot slots[b], or b) and return the decisions of the
+    windows the chunk completed: (logits [B,D,K], probs [B,D,K], ends int64 [B,D], counts int32 [B]), D = window_rows(n).  Rows
+    0 .. counts[b]-1 of stream b are its completed windows in ascending end; the others are NaN / -1; counts[b] = -1: skipped stream.
+    Each row is bit for bit what stream_step gives from a reset slot on that window's samples.  out: caller-owned buffers; without
+    them the buffers of this chunk shape are reused from call to call (copy what must outlive the next call)."""
+    if x.dim() != 3 or x.shape[-1] != spec.C:
+        raise NsdError(f"window_step: x must be [B, n, {spec.C}], got {tuple(x.shape)}")
+    B, T, _ = (int(v) for v in x.shape)
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"window_step: {int(slots.numel())} slot indices for {B} streams")
+    d, w = spec.dims(B, T), _window(window, hop)
+    D = window_rows(T, window, hop)
+    if out is None:
+        key = (x.device, B, D, spec.K)
+        out = _window_out.get(key)
+        if out is None:
+            out = _window_out[key] = (torch.empty((B, D, spec.K), dtype=torch.float32, device=x.device),
+                                      torch.empty((B, D, spec.K), dtype=torch.float32, device=x.device),
+                                      torch.empty((B, D), dtype=torch.int64, device=x.device),
+                                      torch.empty((B,), dtype=torch.int32, device=x.device))
+    logits, probs, ends, counts = out
+    if (int(logits.numel()) != B * D * spec.K or int(probs.numel()) != B * D * spec.K or int(ends.numel()) != B * D or int(counts.numel()) != B
+            or ends.dtype != torch.int64 or counts.dtype != torch.int32 or not ends.is_cuda or not counts.is_cuda
+            or not ends.is_contiguous() or not counts.is_contiguous()):
+        raise NsdError(f"window_step: out must be (logits [{B},{D},{spec.K}], probs [{B},{D},{spec.K}], ends int64 [{B},{D}], counts int32 [{B}]) "
+                       "on the device")
+    pp = _dev_f32(flat, "params", (spec.param_count,))
+    if B == 0:
+        _dev_f32(state, "state")
+        return logits, probs, ends, counts
+    _call("nsd_window_step", x.device, C.byref(d), C.byref(w), pp, _dev_f32(x, "x"), _slots_ptr(slots, "window_step"),
+          _lib.NSD_FLAG_RESIDUAL if residual else 0, _dev_f32(state, "state"), _nbytes(state), S, _dev_f32(logits, "logits"),
+          _dev_f32(probs, "probs"), ends.data_ptr(), counts.data_ptr(), STREAM)
+    return logits, probs, ends, counts
+
+
 # ---- causal front end for live streams and their training (nsd_prep_* of include/nsd.h; the configuration: prep.CausalPrep) ----
 
 def prep_path(C_: int, prep=None) -> bool:

@@ -21,6 +21,32 @@ _NORMALIZE_REFUSAL = ("StreamDecoder: normalize=True z-scores over the whole win
                       "(EEG_LSTM(prep=CausalPrep.design(zscore_seconds=...)))")
 
 
+def _check_stream_model(model, streams, who: str, more=None) -> torch.Tensor:
+    """The refusals every single-model stream decoder shares -> the model's flat parameters (on the GPU).  more: the decoder's own
+    checks of its configuration, made before the model is asked where it lives"""
+    from .lstm_eeg_model import EEG_LSTM
+    if not isinstance(model, EEG_LSTM):
+        raise NsdError(f"{who}: expected an EEG_LSTM, got {type(model).__name__}")
+    if model.training:
+        raise NsdError(f"{who}: the model must be in eval mode (model.eval()): a stream is decoded without dropout")
+    if model.precision != "fp32" or model.spec.D != 1:
+        raise NsdError(f"{who}: the bf16 sequence path and bidirectional models are not resumable (a bidirectional model is "
+                       "not causal); use an fp32, one-directional EEG_LSTM")
+    if model.normalize:
+        raise NsdError(_NORMALIZE_REFUSAL.replace("StreamDecoder", who, 1))
+    if not ops.stream_path(model.spec):
+        raise NsdError(f"{who}: model shape {model.spec} is outside nsd_stream_path (hidden size 48, 2 layers, <= 8 channels, "
+                       "fc width and classes <= 64)")
+    if int(streams) < 1:
+        raise NsdError(f"{who}: streams = {streams}")
+    if more is not None:
+        more()
+    flat = model.flat_parameters()
+    if not flat.is_cuda:
+        raise NsdError(f"{who} runs only on the MI355X HIP path: move the model to the GPU first; there is no CPU fallback")
+    return flat
+
+
 class StreamDecoder:
     """`streams` independent live streams of one eval-mode EEG_LSTM, each with its own slot of device state.
 
@@ -36,24 +62,7 @@ class StreamDecoder:
     """
 
     def __init__(self, model, streams: int = 1):
-        from .lstm_eeg_model import EEG_LSTM
-        if not isinstance(model, EEG_LSTM):
-            raise NsdError(f"StreamDecoder: expected an EEG_LSTM, got {type(model).__name__}")
-        if model.training:
-            raise NsdError("StreamDecoder: the model must be in eval mode (model.eval()): a stream is decoded without dropout")
-        if model.precision != "fp32" or model.spec.D != 1:
-            raise NsdError("StreamDecoder: the bf16 sequence path and bidirectional models are not resumable (a bidirectional model is "
-                           "not causal); use an fp32, one-directional EEG_LSTM")
-        if model.normalize:
-            raise NsdError(_NORMALIZE_REFUSAL)
-        if not ops.stream_path(model.spec):
-            raise NsdError(f"StreamDecoder: model shape {model.spec} is outside nsd_stream_path (hidden size 48, 2 layers, <= 8 channels, "
-                           "fc width and classes <= 64)")
-        if int(streams) < 1:
-            raise NsdError(f"StreamDecoder: streams = {streams}")
-        flat = model.flat_parameters()
-        if not flat.is_cuda:
-            raise NsdError("StreamDecoder runs only on the MI355X HIP path: move the model to the GPU first; there is no CPU fallback")
+        flat = _check_stream_model(model, streams, "StreamDecoder")
         self.model, self.streams, self.device = model, int(streams), flat.device
         self._layout = ops.stream_layout(model.spec)
         self.state = ops.stream_state(model.spec, self.streams, self.device)
@@ -199,6 +208,101 @@ class EnsembleStreamDecoder(StreamDecoder):
         return self.state[0].view(torch.int64)[:, col].cpu().numpy().copy()
 
 
+class SlidingStreamDecoder(StreamDecoder):
+    """`streams` continuous (uncued) streams of one eval-mode EEG_LSTM: every `hop` samples, the decision of the model run from a zero
+    state over the last `window` samples -- nsd_window_step, one launch per chunk whatever the chunk's place against the hops.
+    window and hop in samples: 1 <= hop <= window, window % hop == 0, window / hop <= 128.
+
+      push(samples, slots=None)      samples [n, C] or [B, n, C] -> (probs [B, D, K], ends int64 [B, D], counts int32 [B]), device tensors,
+                                     D = ceil(n / hop), no host synchronisation: rows 0 .. counts[b]-1 of stream b are the windows the
+                                     chunk completed, in ascending end (ends[b, i]: samples since the reset at which window i ended);
+                                     the other rows are NaN / -1.  The buffers are reused by the next push of the same chunk shape.
+                                     Row i is bit for bit what a StreamDecoder returns when it is reset and fed that window.
+      latest()                       per slot the most recent completed window's (end, probs float32 [K]), or None before the first
+      reset(slots=None), steps       restart streams; samples seen per slot since its reset (int64 numpy [streams])
+      state_dict() / load_state_dict()   checkpoint / restore in the middle of a stream; a checkpoint of another (window, hop) is refused
+
+    A model with a causal front end (EEG_LSTM(prep=...)) is decoded through it: ONE prep state of the same slots runs continuously over
+    the stream (it is not restarted per window), and the windows are cut from its output."""
+
+    def __init__(self, model, streams: int = 1, *, window: int, hop: int):
+        who = "SlidingStreamDecoder"
+
+        def config():
+            if not ops.window_path(model.spec, window, hop):
+                raise NsdError(f"{who}: window = {window}, hop = {hop} samples are outside nsd_window_path (1 <= hop <= window, "
+                               "window % hop == 0, window / hop <= 128)")
+        flat = _check_stream_model(model, streams, who, config)
+        self.model, self.streams, self.device = model, int(streams), flat.device
+        self.window, self.hop = int(window), int(hop)
+        self._layout = ops.window_layout(model.spec, self.window, self.hop)
+        self.state = ops.window_state(model.spec, self.window, self.hop, self.streams, self.device)
+        self.prep = model.prep
+        self.prep_state = None if self.prep is None else ops.prep_state(model.spec.C, self.streams, self.device)
+        self._prepped = {}
+        self._all = torch.arange(self.streams, dtype=torch.int64, device=self.device)
+        self._last_end = torch.full((self.streams,), -1, dtype=torch.int64, device=self.device)
+        self._last_probs = torch.full((self.streams, model.spec.K), float("nan"), dtype=torch.float32, device=self.device)
+
+    @torch.no_grad()
+    def push(self, samples, slots=None):
+        return super().push(samples, slots, True)
+
+    def _step(self, x: torch.Tensor, slots, read: bool):
+        _, probs, ends, counts = ops.window_step(self.model.spec, self.model.flat_parameters(), x, self.state, window=self.window,
+                                                 hop=self.hop, slots=slots, residual=self.model.residual)
+        # the newest completed window of every pushed stream, kept on the device (the output buffers are reused)
+        idx = self._all[:x.shape[0]] if slots is None else slots.long()
+        has = counts > 0
+        row = (counts.long() - 1).clamp_(min=0)
+        self._last_end[idx] = torch.where(has, ends.gather(1, row[:, None])[:, 0], self._last_end[idx])
+        newest = probs.gather(1, row[:, None, None].expand(-1, 1, probs.shape[2]))[:, 0]
+        self._last_probs[idx] = torch.where(has[:, None], newest, self._last_probs[idx])
+        return probs, ends, counts
+
+    def latest(self) -> list:
+        ends, probs = self._last_end.cpu().numpy(), self._last_probs.cpu().numpy()
+        return [None if int(e) < 0 else (int(e), probs[s].copy()) for s, e in enumerate(ends)]
+
+    def reset(self, slots=None) -> None:
+        slots = self._slots(slots)
+        ops.window_reset(self.model.spec, self.window, self.hop, self.state, slots)
+        if self.prep is not None:
+            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+        idx = self._all if slots is None else slots.long()
+        self._last_end[idx] = -1
+        self._last_probs[idx] = float("nan")
+
+    @property
+    def steps(self) -> np.ndarray:
+        col = int(self._layout.count) // 2
+        return self.state.view(torch.int64)[:, col].cpu().numpy().copy()
+
+    def state_dict(self) -> dict:
+        sd = {"state": self.state.detach().cpu().clone(), "window": self.window, "hop": self.hop,
+              "last_end": self._last_end.cpu().clone(), "last_probs": self._last_probs.cpu().clone()}
+        if self.prep is not None:
+            sd["prep_state"] = self.prep_state.detach().cpu().clone()
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        who = "SlidingStreamDecoder.load_state_dict"
+        if (int(sd.get("window", -1)), int(sd.get("hop", -1))) != (self.window, self.hop):
+            raise NsdError(f"{who}: a checkpoint of window = {sd.get('window')}, hop = {sd.get('hop')} for a decoder of window = "
+                           f"{self.window}, hop = {self.hop}")
+        st = sd["state"]
+        if tuple(st.shape) != tuple(self.state.shape):
+            raise NsdError(f"{who}: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
+        ps = sd.get("prep_state")
+        if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
+            raise NsdError(f"{who}: the checkpoint and the decoder differ in their causal front end's state")
+        self.state.copy_(st.to(self.device, dtype=torch.float32))
+        if ps is not None:
+            self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
+        self._last_end.copy_(sd["last_end"].to(self.device))
+        self._last_probs.copy_(sd["last_probs"].to(self.device))
+
+
 class PredictorStream:
     """What SimplePredictor.open_stream returns: numpy chunks in, (probs float32 [B, K], labels) out -- predict(), chunk by chunk.
     A predictor with `members` (EnsemblePredictor) is decoded by all of them: an EnsembleStreamDecoder, the probabilities are their mean."""
@@ -221,6 +325,38 @@ class PredictorStream:
             return None
         p = probs.cpu().numpy().astype(np.float32)
         return p, [self.predictor.class_names[int(i)] for i in p.argmax(1)]
+
+    def reset(self, slots=None) -> None:
+        self.decoder.reset(slots)
+
+    @property
+    def steps(self) -> np.ndarray:
+        return self.decoder.steps
+
+
+class PredictorSlidingStream:
+    """What SimplePredictor.open_stream(window_seconds=, hop_seconds=) returns: numpy chunks of a continuous stream in; per stream a
+    list of (end_sample, probs float32 [K], label) out, one entry per window the chunk completed (a SlidingStreamDecoder of `window`
+    and `hop` samples)."""
+
+    def __init__(self, predictor, streams: int, chunk_transform, window: int, hop: int):
+        if getattr(predictor, "members", None) is not None:
+            raise NsdError("SimplePredictor.open_stream: sliding windows decode one model; an ensemble per sliding stream is not built")
+        self.predictor, self.chunk_transform = predictor, chunk_transform
+        self.decoder = SlidingStreamDecoder(predictor.model, streams, window=window, hop=hop)
+
+    def push(self, chunk: np.ndarray, slots=None) -> list:
+        x = np.asarray(chunk)
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3:
+            raise ValueError(f"Expected [n, C] or [B, n, C] samples, got {x.shape}")
+        f = self.chunk_transform or self.predictor.pre.transform
+        x = np.stack([np.ascontiguousarray(f(c), dtype=np.float32) for c in x])
+        probs, ends, counts = (t.cpu().numpy() for t in self.decoder.push(x, slots=slots))
+        names = self.predictor.class_names
+        return [[(int(ends[b, i]), probs[b, i].astype(np.float32), names[int(probs[b, i].argmax())]) for i in range(max(int(counts[b]), 0))]
+                for b in range(x.shape[0])]
 
     def reset(self, slots=None) -> None:
         self.decoder.reset(slots)

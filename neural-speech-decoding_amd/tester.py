@@ -138,7 +138,7 @@ def _predictor(model_path, sr, channels, num_channels: int, predictor_kwargs: Op
 def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels: int = 8, window_seconds: float = 5.0,
                model_path: str = DEFAULT_MODEL, verbose: bool = True, *, producer_factory=None,
                queue_timeout: float = 6.5, predictor_kwargs: Optional[dict] = None, chunk_seconds: Optional[float] = None,
-               chunk_transform=None) -> TrialResult:
+               chunk_transform=None, hop_seconds: Optional[float] = None) -> TrialResult:
     """Collect `trials` windows, run SimplePredictor on each, return the averages.
 
     Positional / keyword interface: the reference's.  Keyword-only additions: `producer_factory`
@@ -147,8 +147,16 @@ def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels
     {"preprocess": "identity"} when the reference's MindsAI filter is not importable), `chunk_seconds` (None: the window mode
     above; a value: the producer cuts every window into chunks of that length and a resumable decoder -- SimplePredictor.open_stream
     -- advances while they arrive; the trial's decision is read at its last chunk) with `chunk_transform` (open_stream's).
+    `hop_seconds` (with chunk_seconds): no cue -- the decoder is not reset between the producer's windows, their chunks form one
+    continuous stream, and every hop_seconds the window of the last window_seconds is decided (open_stream(window_seconds=,
+    hop_seconds=)); every completed window is printed and counted, `trials` of them end the run.
     `model_path` may also be a list of checkpoints: an EnsemblePredictor decodes, in both modes (the mean of the models' probabilities).
     """
+    if hop_seconds is not None:
+        if chunk_seconds is None:
+            raise ValueError("run_trials: hop_seconds needs chunk_seconds (a sliding decision is made while the chunks arrive)")
+        return _run_trials_sliding(trials, serial_port, num_channels, window_seconds, model_path, verbose, producer_factory,
+                                   queue_timeout, predictor_kwargs, chunk_seconds, chunk_transform, hop_seconds)
     if chunk_seconds is not None:
         return _run_trials_chunked(trials, serial_port, num_channels, window_seconds, model_path, verbose, producer_factory,
                                    queue_timeout, predictor_kwargs, chunk_seconds, chunk_transform)
@@ -202,6 +210,45 @@ def _run_trials_chunked(trials, serial_port, num_channels, window_seconds, model
             parts = []
             if verbose:
                 print(f"[Trial {mean.n:02d} @ {time.strftime('%H:%M:%S')}] pred={label} probs={np.round(probs, 3)}")
+        res = mean.result()
+        if verbose:
+            _report(res)
+        return res
+
+
+def _run_trials_sliding(trials, serial_port, num_channels, window_seconds, model_path, verbose, producer_factory, queue_timeout,
+                        predictor_kwargs, chunk_seconds, chunk_transform, hop_seconds) -> TrialResult:
+    q = Queue(maxsize=_QUEUE_DEPTH)
+    producer = (producer_factory or StreamingProcess)(serial_port=serial_port, num_channels=num_channels,
+                                                      window_seconds=window_seconds, out_queue=q, chunk_seconds=chunk_seconds)
+    mean = _RunningMean(classes=len(_HARNESS_LABELS))
+    stream, tail, base, whole, W = None, None, 0, True, 0
+    with _recording(producer):
+        source = _chunks(producer, q, queue_timeout, verbose)
+        while mean.n < trials:
+            payload = next(source)
+            if stream is None:
+                predictor = _predictor(model_path, payload["sr"], payload.get("channels"), num_channels, predictor_kwargs)
+                stream = predictor.open_stream(streams=1, chunk_transform=chunk_transform, window_seconds=window_seconds,
+                                               hop_seconds=hop_seconds)
+                W = stream.decoder.window
+            if payload["seq"] == 0 and (tail is None or not whole):
+                stream.reset()                 # the stream starts, or an interrupted window broke it: sample 0 is here
+                tail, base = None, 0
+            elif tail is None:
+                continue                       # joined in the middle of a window: wait for the next one
+            whole = bool(payload["last"])
+            data = np.asarray(payload["data"])
+            tail = data if tail is None else np.concatenate([tail, data], axis=0)      # samples base .. of the stream
+            for end, probs, label in stream.push(data)[0]:
+                if mean.n == trials:
+                    break
+                mean.add(probs, tail[end - W - base:end - base])
+                if verbose:
+                    print(f"[Window end={end} @ {time.strftime('%H:%M:%S')}] pred={label} probs={np.round(probs, 3)}")
+            if tail.shape[0] > W:              # the next decision's window reaches back at most W samples
+                base += tail.shape[0] - W
+                tail = tail[-W:]
         res = mean.result()
         if verbose:
             _report(res)
