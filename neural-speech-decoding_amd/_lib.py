@@ -206,8 +206,19 @@ SYMBOLS = {
 NSD_MAX_MODELS = 32
 
 
+class DiagGemm(C.Structure):
+    """nsd_diag_gemm of csrc/nsd_diag.h: every field of the bf16 GEMM's arguments and the kernel selector"""
+    _fields_ = [("A", _vp), ("B", _vp), ("lda", C.c_int64), ("ldb", C.c_int64), ("a_kmajor", C.c_int32), ("b_kmajor", C.c_int32),
+                ("b_shift", C.c_int64), ("b_period", C.c_int64), ("B2", _vp), ("ldb2", C.c_int64), ("b2_shift", C.c_int64),
+                ("n_split", C.c_int32), ("epilogue", C.c_int32), ("C", _vp), ("ldc", C.c_int64), ("bias", _fp), ("add", _fp),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int64), ("splits", C.c_int32), ("kernel", C.c_int32)]
+
+
 # entry points of the diagnostic build only (csrc/nsd_diag.h)
 DIAG_SYMBOLS = {
+    "nsd_diag_gemm_bf16": (C.c_int, [C.POINTER(DiagGemm), _vp]),
+    "nsd_diag_reduce_dw": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _vp]),
+    "nsd_diag_reduce_db": (C.c_int, [_fp, C.c_int32, C.c_int32, _fp, _fp, _vp]),
     "nsd_seq_profile": (C.c_int, [C.c_int32]),
     "nsd_seq_profile_read": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "nsd_diag_force_fwd48": (C.c_int, [C.c_int32]),

@@ -132,4 +132,5 @@ struct GemmArgs {
     int splits;              // split-K parts (GEMM_EPI_F32 only)
     int epi;
 };
-int nsd_gemm_bf16_launch(const GemmArgs &g, hipStream_t st);
+// kernel: 0 = the launcher's own choice (every product call); != 0 pins a kernel for the diagnostic entry of nsd_diag.h
+int nsd_gemm_bf16_launch(const GemmArgs &g, hipStream_t st, int kernel = 0);

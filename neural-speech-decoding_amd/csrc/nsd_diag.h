@@ -1,6 +1,7 @@
 // nsd_diag.h -- what only the DIAGNOSTIC build of the library has (make diag -> libnsd_hip_diag.so, compiled with -DNSD_DIAG=1).
 // None of this is part of include/nsd.h or of libnsd_hip.so: the product library rejects these flag bits (NSD_E_INVALID) and
-// does not export the entry points.  Users: tests/ (exchange-mode agreement, forced time-out), bench.py's per-kernel timing
+// does not export the entry points.  Users: tests/ (exchange-mode agreement, forced time-out, the bf16 GEMM with every argument field
+// and a pinned kernel: tests/test_gpu_gemm_bf16_exact.py), bench.py's per-kernel timing
 // loop (outside the timed region), tools/.
 #pragma once
 #include <stdint.h>
@@ -28,5 +29,30 @@ int nsd_seq_profile_read(int32_t kind, float *total_ms, int32_t *count);
 // applies), 0 = the product's own choice.  Process-wide; tests compare the instantiations on the same inputs.
 int nsd_diag_force_fwd48(int32_t nb);       // 0 = the product's choice, 1 / 2 / 4 trials per workgroup, 8 = the experimental one-wave-per-layer kernel (nsd_lstm2_fwd48w.hip: unfused training launches)
 int nsd_diag_force_bwd48(int32_t nb);       // 0 = the product's choice, 2 = nsd_lstm2_bwd48.hip, 4 = nsd_lstm2_bwd48x4.hip where it applies
+// The bf16 GEMM of the sequence path with EVERY field of GemmArgs (nsd_bf16.h; the public nsd_gemm_bf16 leaves b_period, the second
+// source and the addend at zero) and the kernel pinned: 0 the product's choice, 1 the 128 x 128 kernel, 2 the register-staged
+// 256 x 256 kernel, 22 / 23 / 32 the LDS-DMA 256 x 256 kernel with those stages.  Pointers are device pointers; the arguments pass
+// the launcher's checks as the path's own calls do, and a selector whose kernel cannot run the problem is NSD_E_INVALID (nothing
+// is launched).  Enqueues on `stream`.
+typedef struct nsd_diag_gemm {
+    const void *A, *B;          // bf16
+    int64_t lda, ldb;
+    int32_t a_kmajor, b_kmajor;
+    int64_t b_shift, b_period;
+    const void *B2;             // bf16 or null
+    int64_t ldb2, b2_shift;
+    int32_t n_split, epilogue;
+    void *C;
+    int64_t ldc;
+    const float *bias, *add;
+    int32_t M, N;
+    int64_t K;
+    int32_t splits, kernel;
+} nsd_diag_gemm;
+int nsd_diag_gemm_bf16(const nsd_diag_gemm *args, void *stream);
+// The reductions that follow the weight-gradient GEMMs, alone: out[(g*H + u)*I + i] = sum_z part[z][4u + g][i] over nparts partials
+// of [4H][N] floats, i < I <= N (seq_reduce_dw_kernel); b_ih[g*H + u] = b_hh[g*H + u] = sum_z part[z][4u + g] (seq_reduce_db_kernel).
+int nsd_diag_reduce_dw(const float *part, int32_t nparts, int32_t H, int32_t N, int32_t I, float *out, void *stream);
+int nsd_diag_reduce_db(const float *part, int32_t nparts, int32_t H, float *b_ih, float *b_hh, void *stream);
 }
 #endif

@@ -6,9 +6,12 @@
 //   weight gradients                 dW[4H, I | H]   = da[T*B, 4H]^T . {in | h_prev}[T*B, .]  (both operands k-major: the
 //                                                       contraction runs over the rows -> transposed LDS reads, split-K)
 // (torch.nn.LSTM of Neuro-Alpha-App/Utilities/lstm_eeg_model.py:16-22,34 and autograd through it, for the layers whose
-// input is a full sequence).  Two kernels: 128x128 tile, K chunks of 64, 4 waves as 2x2, each wave 2x2 v_mfma_f32_32x32x16_bf16
-// tiles, operands staged global -> registers -> LDS with the next chunk's loads in flight during the MFMAs; and, where the
-// problem has at least one 256x256 tile per CU, the double-buffered 256x256 kernel further down (namespace big).
+// input is a full sequence).  Three kernels behind one launcher: 128x128 tile, K chunks of 64, 4 waves as 2x2, each wave 2x2
+// v_mfma_f32_32x32x16_bf16 tiles, operands staged global -> registers -> LDS with the next chunk's loads in flight during the MFMAs;
+// where the problem has at least one 256x256 tile per CU, the double-buffered, register-staged 256x256 kernel further down
+// (namespace big); and, there, for two k-contiguous operands, the 256x256 kernel staged by LDS-DMA (namespace dma) with two or three
+// pipeline stages per operand (modes 22 / 23 / 32).  tests/test_gpu_gemm_bf16_exact.py holds each of them, pinned through
+// nsd_diag_gemm_bf16 (nsd_diag.h), bit for bit to the float64 product of operands whose sums are exact in fp32.
 // LDS images: k-contiguous operand [128 rows][64 k + 8 pad] (ds_read_b128 fragments, conflict-free), k-major operand
 // [64 k][128 + 32 pad] (ds_read_b64_tr_b16 fragments: row stride = 16 dwords mod 64 keeps the 4 k-rows x 2 column blocks of
 // a 32-lane half on disjoint banks).
@@ -546,10 +549,11 @@ int launch_stages(const GemmArgs &g, const dim3 grid, hipStream_t st) {
     default: nsd_set_error("gemm_bf16: unknown epilogue %d", g.epi); return NSD_E_INVALID;
     }
 }
-int launch_epi(const GemmArgs &g, const dim3 grid, hipStream_t st) {
+int launch_epi(const GemmArgs &g, const dim3 grid, hipStream_t st, const int stages) {
     // the operand with (many) more rows is the one streamed from HBM: it gets the third stage
     static const int force = [] { const char *e = getenv("NSD_GEMM_DMA_STAGES"); return e ? atoi(e) : 0; }();   // test hook: 22 / 23 / 32
-    const int mode = force ? force : (g.M >= 4 * g.N ? 32 : (g.N >= 4 * g.M ? 23 : 22));
+    // (stages != 0: pinned by the caller -- the diagnostic entry nsd_diag_gemm_bf16 -- and ahead of the environment hook)
+    const int mode = stages ? stages : force ? force : (g.M >= 4 * g.N ? 32 : (g.N >= 4 * g.M ? 23 : 22));
     if (mode == 32) return launch_stages<3, 2>(g, grid, st);
     if (mode == 23) return launch_stages<2, 3>(g, grid, st);
     return launch_stages<2, 2>(g, grid, st);
@@ -576,7 +580,12 @@ int launch_epi(const GemmArgs &g, const dim3 grid, hipStream_t st) {
 static bool getenv_reg_staging() { static const bool v = [] { const char *e = getenv("NSD_GEMM_REG_STAGING"); return e && e[0] == '1'; }(); return v; }
 static bool getenv_small_tiles() { static const bool v = [] { const char *e = getenv("NSD_GEMM_SMALL_TILES"); return e && e[0] == '1'; }(); return v; }
 
-int nsd_gemm_bf16_launch(const GemmArgs &g, hipStream_t st) {
+// kernel (host side only; GemmArgs and the kernels know nothing of it): 0 the choice below, environment hooks included; the
+// diagnostic entry nsd_diag_gemm_bf16 (nsd_diag.h) pins 1 the 128 x 128 kernel, 2 the register-staged 256 x 256 kernel, 22 / 23 / 32
+// the LDS-DMA kernel with those stages.  A pinned kernel keeps its own preconditions -- a 256 x 256 kernel a whole tile in M and
+// N, the LDS-DMA kernel two k-contiguous operands inside its descriptor range -- and is refused, never launched, where they fail;
+// only "fills the machine", a matter of speed, is not asked of it.
+int nsd_gemm_bf16_launch(const GemmArgs &g, hipStream_t st, const int kernel) {
     if (!g.A || !g.B || !g.C || g.M < 1 || g.N < 1 || g.K < 1) { nsd_set_error("gemm_bf16: null pointer or empty problem"); return NSD_E_INVALID; }
     // 16-byte pieces along the contiguous dimension of each operand
     if ((g.a_kmajor ? g.M % 8 : g.K % 8) || (g.b_kmajor ? g.N % 8 : g.K % 8) || g.lda % 8 || g.ldb % 8) {
@@ -594,17 +603,21 @@ int nsd_gemm_bf16_launch(const GemmArgs &g, hipStream_t st) {
         return NSD_E_INVALID;
     }
     if (g.add && (g.epi != GEMM_EPI_F32 || splits != 1)) { nsd_set_error("gemm_bf16: addend needs the fp32 epilogue without split-K"); return NSD_E_INVALID; }
+    // both operands k-contiguous: the LDS-DMA kernel (lane offsets inside a tile's 256 rows must stay below the descriptor range)
+    const bool dma_fits = !g.a_kmajor && !g.b_kmajor && 256L * 2 * (g.lda > g.ldb ? g.lda : g.ldb) + 2 * g.K < 0x7f000000L;
+    if (kernel != 0 && kernel != 1 && kernel != 2 && kernel != 22 && kernel != 23 && kernel != 32) { nsd_set_error("gemm_bf16: unknown kernel selector %d", kernel); return NSD_E_INVALID; }
+    if (kernel >= 2 && (g.M < big::TM || g.N < big::TN)) { nsd_set_error("gemm_bf16: kernel %d needs M, N >= 256 (M=%d N=%d)", kernel, g.M, g.N); return NSD_E_INVALID; }
+    if (kernel >= 22 && !dma_fits) { nsd_set_error("gemm_bf16: kernel %d needs two k-contiguous operands inside the descriptor range", kernel); return NSD_E_INVALID; }
     GemmArgs a = g;
     a.splits = splits;
     // the 256 x 256 kernel where it fills the machine: at least one workgroup per CU (split-K included)
     const long big_wgs = (long)((g.N + big::TN - 1) / big::TN) * ((g.M + big::TM - 1) / big::TM) * splits;
-    if (g.M >= big::TM && g.N >= big::TN && big_wgs >= nsd_num_cus() && !getenv_small_tiles()) {
+    if (kernel ? kernel >= 2 : (g.M >= big::TM && g.N >= big::TN && big_wgs >= nsd_num_cus() && !getenv_small_tiles())) {
         const int tiles = ((g.N + big::TN - 1) / big::TN) * ((g.M + big::TM - 1) / big::TM);
         const dim3 bgrid(tiles >= 16 ? 8 * ((tiles + 7) / 8) : tiles, 1, splits);   // 1-D; >= 16 tiles: padded to a multiple of 8, ids mapped XCD-aware
+        if (kernel ? kernel >= 22 : (dma_fits && !getenv_reg_staging())) return dma::launch_epi(a, bgrid, st, kernel);
         if (g.a_kmajor) return g.b_kmajor ? big::launch_epi<true, true>(a, bgrid, st) : big::launch_epi<true, false>(a, bgrid, st);
         if (g.b_kmajor) return big::launch_epi<false, true>(a, bgrid, st);
-        // both operands k-contiguous: the LDS-DMA kernel (lane offsets inside a tile's 256 rows must stay below the descriptor range)
-        if (!getenv_reg_staging() && 256L * 2 * (g.lda > g.ldb ? g.lda : g.ldb) + 2 * g.K < 0x7f000000L) return dma::launch_epi(a, bgrid, st);
         return big::launch_epi<false, false>(a, bgrid, st);
     }
     const dim3 grid((g.N + GN - 1) / GN, (g.M + GM - 1) / GM, splits);

@@ -689,6 +689,29 @@ int nsd_seq_profile_read(int32_t kind, float *total_ms, int32_t *count) {
     *total_ms = tot; *count = n;
     return NSD_OK;
 }
+// The GEMM with every field of GemmArgs and a pinned kernel; the two reductions of weight_grads alone (nsd_diag.h).
+int nsd_diag_gemm_bf16(const nsd_diag_gemm *p, void *stream) {
+    if (!p) { nsd_set_error("diag_gemm_bf16: null arguments"); return NSD_E_INVALID; }
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = (const bf16_t *)p->A; g.B = (const bf16_t *)p->B; g.lda = p->lda; g.ldb = p->ldb; g.a_kmajor = p->a_kmajor; g.b_kmajor = p->b_kmajor;
+    g.b_shift = p->b_shift; g.b_period = p->b_period;
+    g.B2 = (const bf16_t *)p->B2; g.ldb2 = p->ldb2; g.b2_shift = p->b2_shift; g.n_split = p->n_split;
+    g.C = p->C; g.ldc = p->ldc; g.bias = p->bias; g.add = p->add; g.M = p->M; g.N = p->N; g.K = p->K; g.splits = p->splits; g.epi = p->epilogue;
+    return nsd_gemm_bf16_launch(g, (hipStream_t)stream, p->kernel);
+}
+int nsd_diag_reduce_dw(const float *part, int32_t nparts, int32_t H, int32_t N, int32_t I, float *out, void *stream) {
+    if (!part || !out || nparts < 1 || H < 1 || I < 1 || I > N) { nsd_set_error("diag_reduce_dw: null pointer or bad sizes"); return NSD_E_INVALID; }
+    hipLaunchKernelGGL(seq_reduce_dw_kernel, dim3((unsigned)((4L * H * I + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, nparts, H, N, I, out);
+    NSD_CHECK_LAUNCH("seq_reduce_dw_kernel");
+    return NSD_OK;
+}
+int nsd_diag_reduce_db(const float *part, int32_t nparts, int32_t H, float *b_ih, float *b_hh, void *stream) {
+    if (!part || !b_ih || !b_hh || nparts < 1 || H < 1) { nsd_set_error("diag_reduce_db: null pointer or bad sizes"); return NSD_E_INVALID; }
+    hipLaunchKernelGGL(seq_reduce_db_kernel, dim3((unsigned)((4 * H + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, nparts, H, b_ih, b_hh);
+    NSD_CHECK_LAUNCH("seq_reduce_db_kernel");
+    return NSD_OK;
+}
 #endif
 
 }  // extern "C"

@@ -776,6 +776,91 @@ def gemm_bf16(a: torch.Tensor, b: torch.Tensor, *, a_kmajor: bool = False, b_kma
     return c
 
 
+GEMM_KERNELS = {0: "the product's choice", 1: "128 x 128", 2: "register-staged 256 x 256", 22: "LDS-DMA 256 x 256, stages 2 / 2",
+                23: "LDS-DMA 256 x 256, stages 2 / 3", 32: "LDS-DMA 256 x 256, stages 3 / 2"}
+
+
+def gemm_bf16_diag(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *, M: int, N: int, K: int, kernel: int = 0,
+                   a_off: int = 0, lda: Optional[int] = None, a_kmajor: bool = False,
+                   b_off: int = 0, ldb: Optional[int] = None, b_kmajor: bool = False, b_shift: int = 0, b_period: int = 0,
+                   b2: Optional[torch.Tensor] = None, b2_off: int = 0, ldb2: Optional[int] = None, b2_shift: int = 0, n_split: int = 0,
+                   c_off: int = 0, ldc: Optional[int] = None, epilogue: int = 0, bias: Optional[torch.Tensor] = None,
+                   add: Optional[torch.Tensor] = None, splits: int = 1) -> torch.Tensor:
+    """Diagnostic build only (inside `with _lib.diagnostic_library():`): the bf16 GEMM with every field the sequence path sets
+    (csrc/nsd_bf16.h, GemmArgs) and the kernel pinned (GEMM_KERNELS; nsd_diag_gemm_bf16 of csrc/nsd_diag.h).  a, b, b2: bf16 device
+    BUFFERS; an operand is the view that starts *_off elements in, with leading dimension ld* (default: the operand's own row
+    length): A [M][lda], or [K][lda] when a_kmajor; B [N][ldb], or [K][ldb] when b_kmajor; B2 [K][ldb2] for the columns from n_split.
+    c: the caller's output buffer, written in place from c_off with leading dimension ldc (default N): fp32 [splits][M][ldc]
+    (epilogue 0: the partials, NOT summed), bf16 [M][ldc] (1) or M * N bf16 of accumulator tiles (2, 3).  add: fp32 [M][ldc].
+    A view that leaves its buffer is refused here; everything else is left to the launcher's own checks.  Returns c."""
+    if not _lib.diag_active():
+        raise NsdError("gemm_bf16_diag: the kernel can be pinned in the diagnostic build only: use `with _lib.diagnostic_library():`")
+    M, N, K, splits, epilogue = int(M), int(N), int(K), int(splits), int(epilogue)
+    lda = int(lda if lda is not None else (M if a_kmajor else K))
+    ldb = int(ldb if ldb is not None else (N if b_kmajor else K))
+    ldb2 = int(ldb2 if ldb2 is not None else (N - n_split if b2 is not None else 0))
+    ldc = int(ldc if ldc is not None else N)
+    cdtype = torch.float32 if epilogue == 0 else torch.bfloat16
+    for t, n, dt in ((a, "a", torch.bfloat16), (b, "b", torch.bfloat16), (b2, "b2", torch.bfloat16), (c, "c", cdtype),
+                     (bias, "bias", torch.float32), (add, "add", torch.float32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+            raise NsdError(f"gemm_bf16_diag: {n} must be a contiguous {dt} tensor on the MI355X")
+    if min(M, N, K, lda, ldb, ldc, a_off, b_off, b2_off, c_off) < 0 or ldb2 < 0:
+        raise NsdError("gemm_bf16_diag: negative size, leading dimension or offset")
+
+    def inside(t, name, off, rows, cols, ld, planes=1):
+        last = off + (planes - 1) * rows * ld + (rows - 1) * ld + cols
+        if rows < 1 or cols < 1 or planes < 1 or last > t.numel():
+            raise NsdError(f"gemm_bf16_diag: the view of {name} ({planes} x {rows} x {cols}, ld {ld}, offset {off}) leaves its "
+                           f"buffer of {t.numel()} elements")
+    inside(a, "a", a_off, K if a_kmajor else M, M if a_kmajor else K, lda)
+    ncols_b = n_split if (b2 is not None and b_kmajor) else N
+    inside(b, "b", b_off, K if b_kmajor else N, ncols_b if b_kmajor else K, ldb)
+    if b2 is not None:
+        inside(b2, "b2", b2_off, K, N - n_split, ldb2)
+    if epilogue in (0, 1):
+        inside(c, "c", c_off, M, N, ldc, max(splits, 1) if epilogue == 0 else 1)
+    else:
+        inside(c, "c", c_off, 1, M * N, M * N)
+    if add is not None:
+        inside(add, "add", 0, M, N, ldc)
+    if bias is not None:
+        inside(bias, "bias", 0, 1, M, M)
+    args = _lib.DiagGemm(a.data_ptr() + 2 * a_off, b.data_ptr() + 2 * b_off, lda, ldb, int(a_kmajor), int(b_kmajor), int(b_shift),
+                         int(b_period), None if b2 is None else b2.data_ptr() + 2 * b2_off, ldb2, int(b2_shift), int(n_split), epilogue,
+                         c.data_ptr() + c.element_size() * c_off, ldc, None if bias is None else bias.data_ptr(),
+                         None if add is None else add.data_ptr(), M, N, K, splits, int(kernel))
+    _call("nsd_diag_gemm_bf16", a.device, C.byref(args), STREAM)
+    return c
+
+
+def reduce_dw_diag(part: torch.Tensor, nparts: int, H: int, N: int, I: int, part_off: int = 0) -> torch.Tensor:
+    """Diagnostic build only: seq_reduce_dw_kernel alone (nsd_diag_reduce_dw) -- nparts split-K partials [4H][N] of a weight-gradient
+    GEMM, rows unit-major (4u + g), read from column part_off on; -> [4H][I] fp32 in torch's row order (g * H + u), I <= N - part_off."""
+    if not _lib.diag_active():
+        raise NsdError("reduce_dw_diag: diagnostic build only: use `with _lib.diagnostic_library():`")
+    _dev_f32(part, "part")
+    if min(nparts, H, I) < 1 or part_off < 0 or part_off + I > N or nparts * 4 * H * N > part.numel():
+        raise NsdError("reduce_dw_diag: the partials leave their buffer")
+    out = torch.empty((4 * H, I), dtype=torch.float32, device=part.device)
+    _call("nsd_diag_reduce_dw", part.device, part.data_ptr() + 4 * part_off, int(nparts), int(H), int(N), int(I), out.data_ptr(), STREAM)
+    return out
+
+
+def reduce_db_diag(part: torch.Tensor, nparts: int, H: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Diagnostic build only: seq_reduce_db_kernel alone (nsd_diag_reduce_db) -- nparts rows [4H] in unit-major order -> (b_ih, b_hh),
+    each [4H] in torch's order."""
+    if not _lib.diag_active():
+        raise NsdError("reduce_db_diag: diagnostic build only: use `with _lib.diagnostic_library():`")
+    _dev_f32(part, "part")
+    if min(nparts, H) < 1 or nparts * 4 * H > part.numel():
+        raise NsdError("reduce_db_diag: the partials leave their buffer")
+    b_ih = torch.empty(4 * H, dtype=torch.float32, device=part.device)
+    b_hh = torch.empty_like(b_ih)
+    _call("nsd_diag_reduce_db", part.device, part.data_ptr(), int(nparts), int(H), b_ih.data_ptr(), b_hh.data_ptr(), STREAM)
+    return b_ih, b_hh
+
+
 # ---- sequence-batched path (nsd_seq_*): large hidden sizes, optional bidirectional, bf16 operands -------------------------
 def seq_workspace(spec: ModelSpec, B: int, T: int, device) -> torch.Tensor:
     d = spec.dims(B, T)
