@@ -580,6 +580,50 @@ int     nsd_window_step(const nsd_dims *d, const nsd_window *w, const float *par
                         void *stream);
 
 /*
+ * ---- sliding-window decisions from an ensemble: M models per stream in one launch (an EXTENSION, of the two above: nsd_multi_stream_*,
+ * nsd_window_*) ----
+ *
+ * nsd_multi_window_step is to nsd_window_step what nsd_multi_stream_step is to nsd_stream_step: it advances the B continuous streams of a
+ * call in each of M models of one shape -- params [M,P], P = nsd_param_count(d) -- by one launch of the step nsd_window_step runs (the
+ * same source, csrc/nsd_window48.hip, compiled with a model view), and can return the ensemble's mean probabilities per window.
+ * State: [M][S][stream_stride] floats.  Model m's part starts at float m * S * stream_stride and is an ordinary window state of S streams
+ * in the public nsd_window_layout: it can be handed to nsd_window_step as it is (with params + m*P).  The whole buffer is a flat state of
+ * M*S streams to nsd_window_reset -- stream m*S + s is stream s of model m, slots == NULL resets everything -- so there is no reset entry
+ * of its own, and the state must be reset once before its first step.
+ *   nsd_multi_window_path         1 where nsd_window_path(d, w) and 1 <= M <= NSD_MAX_MODELS, else 0
+ *   nsd_multi_window_state_bytes  M * nsd_window_state_bytes(d, w, S); <0 outside the path or for S < 1
+ *   nsd_multi_window_step         d->B streams, chunk length d->T >= 1.  x: model m reads the chunk [B,T,C] at x + m * x_model_stride
+ *                                 floats; 0: one chunk for all models, else >= B*T*C.  slots: DEVICE int32[B] of distinct indices in
+ *                                 [0, S) or NULL for 0 .. B-1, shared by the models: stream b lives in stream slots[b] of every model's
+ *                                 part.  Outputs, with D = nsd_window_rows(d->T, w): logits [M,B,D,K] (required), probs [M,B,D,K] or
+ *                                 NULL, mean_probs [B,D,K] or NULL, ends int64 [M,B,D], counts int32 [M,B].
+ * Contract.  Model m's part of the state after the call, and its blocks of logits / probs / ends / counts -- the NaN / -1 rows from
+ * counts[m,b] on included -- are bit for bit what
+ *   nsd_window_step(d, w, params + m*P, x + m*x_model_stride, slots, flags, state + m*S*stream_stride, S*stream_stride*4, S,
+ *                   logits + m*B*D*K, probs + m*B*D*K, ends + m*B*D, counts + m*B)
+ * leaves and writes, for any M, B, cut of the stream, slot, placement in the grid, HIP stream or graph replay.  Workgroups m*G ..
+ * m*G + G - 1 walk model m's B*R (stream, phase) pairs, G = min(B*R, max(1, CUs / M)).
+ * mean_probs[b,i,k] = (((p_0 + p_1) + p_2) + ... + p_{M-1}) / (float)M with p_m = probs[m,b,i,k]: a serial fp32 sum in m, every addition
+ * rounded on its own, then one correctly rounded division.  It is formed from the probs buffer by a second small launch that the same
+ * call enqueues behind the step.  Where every model's row i is a decision, the mean row is that mean; where any model's row is NaN -- an
+ * unused row, a poisoned window, a skipped model -- the mean row is NaN (some NaN: test it with isnan, not by its payload).
+ * Failure behaviour.  Every refusal happens before any launch: NSD_E_INVALID for all that nsd_window_step refuses, for M outside
+ * [1, NSD_MAX_MODELS], mean_probs without probs, x_model_stride negative or positive and below B*T*C, M * B * D * K above 2^31 - 1;
+ * NSD_E_WORKSPACE when state_bytes < nsd_multi_window_state_bytes(d, w, M, S).  B = 0 launches nothing.  Seen on the device only, and never
+ * silent: a slot index outside [0, S) is skipped in every model -- counts[m,b] = -1, all its rows NaN / -1, no state touched; a model whose
+ * header for that stream records another (W, Hp) than the call's is skipped for that model alone -- its rows are NaN / -1, its counts[m,b]
+ * is -1, the stream's mean rows are NaN, and the other models' bits are those of the clean run.  A sample that is not finite poisons
+ * exactly the windows that contain it, in every model that reads it, and the stream heals as in nsd_window_step.  No host synchronisation,
+ * no allocation: nsd_prep_step + nsd_multi_window_step (the step and the mean launch) can be captured in one single-stream graph and
+ * replayed.  Additive: NSD_VERSION stays 301, a caller detects the feature by the symbols.
+ */
+int     nsd_multi_window_path(const nsd_dims *d, const nsd_window *w, int32_t M);
+int64_t nsd_multi_window_state_bytes(const nsd_dims *d, const nsd_window *w, int32_t M, int32_t S);
+int     nsd_multi_window_step(const nsd_dims *d, const nsd_window *w, int32_t M, const float *params, const float *x, int64_t x_model_stride,
+                              const int32_t *slots, uint32_t flags, void *state, int64_t state_bytes, int32_t S, float *logits, float *probs,
+                              float *mean_probs, int64_t *ends, int32_t *counts, void *stream);
+
+/*
  * ---- causal front end for live streams and their training (an EXTENSION: the reference filters whole windows on the host) ----
  *
  * A per-channel transform that can run chunk by chunk in front of nsd_stream_step, and over whole windows in a training step, so that a

@@ -196,6 +196,11 @@ SYMBOLS = {
     "nsd_window_state_layout": (C.c_int, [_dp, C.POINTER(Window), C.POINTER(WindowLayout)]),
     "nsd_window_reset": (C.c_int, [_dp, C.POINTER(Window), _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
     "nsd_window_step": (C.c_int, [_dp, C.POINTER(Window), _fp, _fp, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _vp, _ip, _vp]),
+    # sliding-window decisions of M models per launch (an ensemble on continuous streams)
+    "nsd_multi_window_path": (C.c_int, [_dp, C.POINTER(Window), C.c_int32]),
+    "nsd_multi_window_state_bytes": (C.c_int64, [_dp, C.POINTER(Window), C.c_int32, C.c_int32]),
+    "nsd_multi_window_step": (C.c_int, [_dp, C.POINTER(Window), C.c_int32, _fp, _fp, C.c_int64, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32,
+                                        _fp, _fp, _fp, _vp, _ip, _vp]),
     # causal front end for live streams and their training
     "nsd_prep_path": (C.c_int, [C.c_int32, _vp]),
     "nsd_prep_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

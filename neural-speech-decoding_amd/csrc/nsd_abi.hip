@@ -1064,7 +1064,8 @@ static bool window_ok(const nsd_window *w) {
     return w && w->window >= 1 && w->hop >= 1 && w->hop <= w->window && w->window % w->hop == 0 && w->window / w->hop <= NSD_WINDOW_MAX_PHASES;
 }
 // the preamble of the entry points that touch a window state: shape, pointers, stream count, size
-static int window_enter(const nsd_dims *d, const nsd_window *w, const char *who, bool ptrs_ok, const void *state, int64_t state_bytes, int32_t S) {
+static int window_enter(const nsd_dims *d, const nsd_window *w, const char *who, bool ptrs_ok, const void *state, int64_t state_bytes, int32_t S,
+                        int32_t M = 1) {
     if (!d || !w) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     if (!stream_shape(d) || !window_ok(w)) {
         nsd_set_error("%s: outside nsd_window_path (nsd_stream_path, 1 <= hop <= window, window %% hop == 0, window / hop <= %d): window %d, hop %d",
@@ -1073,9 +1074,10 @@ static int window_enter(const nsd_dims *d, const nsd_window *w, const char *who,
     }
     if (!ptrs_ok || !state) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     if (S < 1) { nsd_set_error("%s: S = %d streams", who, S); return NSD_E_INVALID; }
-    const int64_t need = (int64_t)S * window_stream_stride(w->window / w->hop) * (int64_t)sizeof(float);
+    const int64_t need = (int64_t)M * S * window_stream_stride(w->window / w->hop) * (int64_t)sizeof(float);
     if (state_bytes < need) {
-        nsd_set_error("%s: state of %lld bytes is smaller than nsd_window_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_%swindow_state_bytes() = %lld", who, (long long)state_bytes,
+                      M > 1 ? "multi_" : "", (long long)need);
         return NSD_E_WORKSPACE;
     }
     return NSD_OK;
@@ -1135,6 +1137,51 @@ int nsd_window_step(const nsd_dims *d, const nsd_window *w, const float *params,
     a.ends = (long long *)ends; a.counts = counts;
     a.W = w->window; a.Hp = w->hop; a.R = R; a.D = D;
     return nsd_window48_launch(a, (hipStream_t)stream);
+}
+
+// ---- sliding-window decisions of M models per launch (nsd_multi_window48.hip): state [M][S][R phase slots + header] ----
+int nsd_multi_window_path(const nsd_dims *d, const nsd_window *w, int32_t M) {
+    return nsd_window_path(d, w) && M >= 1 && M <= NSD_MAX_MODELS ? 1 : 0;
+}
+
+int64_t nsd_multi_window_state_bytes(const nsd_dims *d, const nsd_window *w, int32_t M, int32_t S) {
+    if (!nsd_multi_window_path(d, w, M) || S < 1) {
+        nsd_set_error("multi_window_state_bytes: outside nsd_window_path, M = %d outside [1, %d], or S < 1", M, NSD_MAX_MODELS);
+        return NSD_E_INVALID;
+    }
+    return (int64_t)M * S * window_stream_stride(w->window / w->hop) * (int64_t)sizeof(float);
+}
+
+int nsd_multi_window_step(const nsd_dims *d, const nsd_window *w, int32_t M, const float *params, const float *x, int64_t x_model_stride,
+                          const int32_t *slots, uint32_t flags, void *state, int64_t state_bytes, int32_t S, float *logits, float *probs,
+                          float *mean_probs, int64_t *ends, int32_t *counts, void *stream) {
+    static const char *who = "multi_window_step";
+    if (!d || !w) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (const int rc = window_enter(d, w, who, params && x && logits && ends && counts, state, state_bytes, S, M)) return rc;
+    if (mean_probs && !probs) { nsd_set_error("%s: mean_probs without probs", who); return NSD_E_INVALID; }
+    if (flags & ~NSD_FLAG_RESIDUAL) { nsd_set_error("%s: flags 0x%x (only NSD_FLAG_RESIDUAL applies)", who, flags); return NSD_E_INVALID; }
+    if (d->T < 1) { nsd_set_error("%s: chunk length T = %d", who, d->T); return NSD_E_INVALID; }
+    if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d", who, d->B, S); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
+        nsd_set_error("%s: x_model_stride %lld: 0 (one chunk for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
+        return NSD_E_INVALID;
+    }
+    const int R = w->window / w->hop, D = nsd_window_rows(d->T, w);
+    if ((int64_t)M * d->B * D * d->K > 0x7fffffff || (int64_t)d->B * R > 0x7fffffff) {
+        nsd_set_error("%s: M * B * D * K = %lld output values (B * R = %lld workgroup passes per model) in one launch", who,
+                      (long long)M * d->B * D * d->K, (long long)d->B * R);
+        return NSD_E_INVALID;
+    }
+    if (d->B == 0) return NSD_OK;
+    WindowArgs a;
+    memset(&a, 0, sizeof(a));
+    static_cast<StreamArgs &>(a) = build_stream(d, params, x, slots, flags, state, S, logits, probs);
+    a.ends = (long long *)ends; a.counts = counts;
+    a.W = w->window; a.Hp = w->hop; a.R = R; a.D = D;
+    return nsd_multi_window48_launch(a, model_split(d, x_model_stride), M, mean_probs, (hipStream_t)stream);
 }
 
 // ---- causal front end (nsd_prep_*, include/nsd.h; nsd_prep.hip) ----

@@ -92,3 +92,6 @@ int nsd_lstm2_multi_bwd_launch(const Lstm2BwdArgs &a, ModelSplit s, int M, hipSt
 // resumable inference of M models (nsd_multi_stream_step; nsd_multi_stream48.hip): a.B streams and a.S slots per model, s.G is set here;
 // mean: null or [B,K], the mean of a.probs over the models, by a second launch
 int nsd_multi_stream48_launch(const StreamArgs &a, ModelSplit s, int M, float *mean, hipStream_t st);
+// sliding-window decisions of M models (nsd_multi_window_step; nsd_multi_window48.hip): a.B streams and a.S streams of state per model,
+// logits / probs [M,B,D,K], ends [M,B,D], counts [M,B]; s.G is set here; mean: null or [B,D,K], the mean of a.probs over the models
+int nsd_multi_window48_launch(const WindowArgs &a, ModelSplit s, int M, float *mean, hipStream_t st);

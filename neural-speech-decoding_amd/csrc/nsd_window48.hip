@@ -13,7 +13,12 @@
 // length and offset where that kernel has the chunk's): sharing the text would have put stream48_kernel's body behind a function or
 // macro boundary, and its machine code is pinned (tools/isa_digest.py).  The library is built with -ffp-contract=off,
 // so equal source gives equal bits; tests/test_gpu_window.py holds the two together byte for byte.
-#include "nsd_args.h"
+//
+// The step is one source that two kernels are compiled from, as nsd_stream48.hip's is: window48_kernel (one model, this file) and
+// multi_window48_kernel (M models of one shape per launch: nsd_multi_window_step; compiled as nsd_multi_window48.hip, which includes this
+// file with NSD_MULTI_TU set, so that the single-model kernels' module is what it was).  The model-batched kernel works on a model view
+// (nsd_multi.h): pointers moved to its model, the workgroup index and count taken inside the model.
+#include "nsd_multi.h"
 
 namespace {
 
@@ -91,7 +96,39 @@ __device__ __forceinline__ void void_rows(const WindowArgs &a, const int b, cons
     }
 }
 
-__global__ __launch_bounds__(NT) void window48_kernel(const WindowArgs a) {
+// WINDOW48_KERNEL: the kernel's name and parameters; WINDOW48_VIEW: what `a` is -- the argument block itself (the workgroups of the grid
+// share its B * R pairs: wg_id / wg_count are blockIdx.x / gridDim.x) or the view of the workgroup's model (the workgroups of one model
+// share them).  A macro rather than a template body: window48_kernel keeps its machine code (tools/isa_digest.py)
+#if !NSD_MULTI_TU
+#define WINDOW48_KERNEL window48_kernel(const WindowArgs a)
+#define WINDOW48_VIEW
+#else
+// workgroup blockIdx.x runs model blockIdx.x / s.G: params + m*P, x + m*x_stride, state + m*S*window_stream_stride(R), logits / probs +
+// m*B*D*K, ends + m*B*D, counts + m*B
+__device__ __forceinline__ ModelView<WindowArgs> model_view(const WindowArgs &a, const ModelSplit &s) {
+    using nsd_multi_detail::mv;
+    const int m = nsd_multi_detail::model_of_block(s);
+    ModelView<WindowArgs> v;
+    static_cast<WindowArgs &>(v) = a;
+    v.wg = (int)blockIdx.x - m * s.G;
+    v.nwg = s.G;
+    const size_t P = (size_t)s.P * m, bd = (size_t)m * a.B * a.D, bdk = bd * a.K;
+    v.x = a.x + (size_t)s.x_stride * m;
+    v.w_ih0 = a.w_ih0 + P; v.w_hh0 = a.w_hh0 + P; v.b_ih0 = a.b_ih0 + P; v.b_hh0 = a.b_hh0 + P;
+    v.w_ih1 = a.w_ih1 + P; v.w_hh1 = a.w_hh1 + P; v.b_ih1 = a.b_ih1 + P; v.b_hh1 = a.b_hh1 + P;
+    v.attn_w = a.attn_w + P; v.attn_b = a.attn_b + P; v.ln_w = a.ln_w + P; v.ln_b = a.ln_b + P;
+    v.fc0_w = a.fc0_w + P; v.fc0_b = a.fc0_b + P; v.fc3_w = a.fc3_w + P; v.fc3_b = a.fc3_b + P;
+    v.state = a.state + (size_t)m * a.S * window_stream_stride(a.R);
+    v.logits = a.logits + bdk; v.probs = mv(a.probs, bdk);
+    v.ends = a.ends + bd; v.counts = a.counts + (size_t)m * a.B;
+    return v;
+}
+#define WINDOW48_KERNEL multi_window48_kernel(const WindowArgs a_in, const ModelSplit ms)
+#define WINDOW48_VIEW const ModelView<WindowArgs> a = model_view(a_in, ms);
+#endif
+
+__global__ __launch_bounds__(NT) void WINDOW48_KERNEL {
+    WINDOW48_VIEW
     __shared__ SSmem sm;
     const int tid = threadIdx.x, lane = tid & 63;
     const int role = tid / 192;              // 0 L0, 1 P, 2 L1, 3 pool (wave-uniform: 192 = 3 waves)
@@ -132,7 +169,7 @@ __global__ __launch_bounds__(NT) void window48_kernel(const WindowArgs a) {
     const bool res = a.residual != 0;
 
     const int items = a.B * R;               // B <= S and the state holds S * R phase slots: below 2^31
-    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+    for (int it = wg_id(a); it < items; it += wg_count(a)) {
         const int b = it / R, ph = it - b * R;
         const int slot = a.slots ? a.slots[b] : b;
         // (all the same for every thread of the workgroup) a slot outside the state, or a state reset with another window / hop: skipped
@@ -298,6 +335,7 @@ __global__ __launch_bounds__(NT) void window48_kernel(const WindowArgs a) {
     }
 }
 
+#if !NSD_MULTI_TU
 // every phase slot a reset stream slot (zero h and c, max -inf, denominator and sum 0, step count 0); the header: window, hop, counts 0
 __global__ __launch_bounds__(256) void window_reset_kernel(float *state, const int S, const int32_t *slots, const int n, const int W,
                                                            const int Hp, const int R) {
@@ -315,8 +353,21 @@ __global__ __launch_bounds__(256) void window_reset_kernel(float *state, const i
         sb[e] = e == WINDOW_HDR_W ? __int_as_float(W) : e == WINDOW_HDR_HOP ? __int_as_float(Hp) : 0.f;
 }
 
+#else
+// mean[i] = (((p_0[i] + p_1[i]) + p_2[i]) + ...) / float(M), p_m = probs + m*n: a serial sum in m, every operation rounded on its own (a
+// row that is NaN in any model is NaN in the mean)
+__global__ __launch_bounds__(256) void multi_window_mean_kernel(const float *probs, float *mean, const int M, const int n) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;      // n <= 2^31 - 1: the last block's index stays below 2^32
+    if (i >= (unsigned)n) return;
+    float sum = probs[i];
+    for (int m = 1; m < M; ++m) sum = sum + probs[(size_t)m * n + i];
+    mean[i] = sum / (float)M;
+}
+#endif
+
 }  // namespace
 
+#if !NSD_MULTI_TU
 // B * R (stream, phase) pairs; one workgroup fits a CU (ten waves), so a grid above the CU count would only queue
 int nsd_window48_launch(const WindowArgs &a, hipStream_t st) {
     const int cus = nsd_num_cus();
@@ -334,3 +385,21 @@ int nsd_window_reset_launch(float *state, int S, const int32_t *slots, int n, in
     NSD_CHECK_LAUNCH("window_reset");
     return NSD_OK;
 }
+
+#else
+// a.B * a.R (stream, phase) pairs of each of M models; G = min(B * R, max(1, CUs / M)) workgroups per model: one workgroup fits a CU (ten
+// waves), so a larger grid would only queue.  mean: null, or [B,D,K] formed from a.probs by a second launch behind the step
+int nsd_multi_window48_launch(const WindowArgs &a, ModelSplit s, int M, float *mean, hipStream_t st) {
+    const int per = nsd_num_cus() / M > 1 ? nsd_num_cus() / M : 1;
+    const long long items = (long long)a.B * a.R;
+    s.G = items < per ? (int)items : per;
+    hipLaunchKernelGGL(multi_window48_kernel, dim3(M * s.G), dim3(NT), 0, st, a, s);
+    NSD_CHECK_LAUNCH("multi_window_step");
+    if (mean) {
+        const long long n = (long long)a.B * a.D * a.K;      // M * n <= 2^31 - 1 (nsd_multi_window_step)
+        hipLaunchKernelGGL(multi_window_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)a.probs, mean, M, (int)n);
+        NSD_CHECK_LAUNCH("multi_window_mean");
+    }
+    return NSD_OK;
+}
+#endif

@@ -507,7 +507,8 @@ class SimplePredictor:
         the readout's pooling is updated per step, nsd_infer's per block of steps, so the last bits can differ).
         window_seconds and hop_seconds (both, or neither: the object above, unchanged): a continuous stream without cues -- a
         PredictorSlidingStream whose push returns, per stream, a list of (end_sample, probs float32 [K], label) for the windows the
-        chunk completed: every hop_seconds, the decision of the model run from a zero state over the last window_seconds."""
+        chunk completed: every hop_seconds, the decision of the model run from a zero state over the last window_seconds (of an
+        EnsemblePredictor: the mean of its members' decisions, all members advanced by one launch per chunk)."""
         from .stream import PredictorSlidingStream, PredictorStream
         if (window_seconds is None) != (hop_seconds is None):
             raise ValueError("SimplePredictor.open_stream: window_seconds and hop_seconds go together (both, or neither)")

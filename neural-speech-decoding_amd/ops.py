@@ -1336,6 +1336,85 @@ def window_step(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, state: tor
     return logits, probs, ends, counts
 
 
+# ---- sliding-window decisions of M models per launch: an ensemble on continuous streams (nsd_multi_window_* of include/nsd.h) ----
+
+def multi_window_path(spec: ModelSpec, window: int, hop: int, M: int) -> bool:
+    """True where nsd_multi_window_step covers M models of this shape with this window and hop (window_path and 1 <= M <= 32)."""
+    if not (-2 ** 31 <= int(window) < 2 ** 31 and -2 ** 31 <= int(hop) < 2 ** 31 and -2 ** 31 <= int(M) < 2 ** 31):
+        return False
+    d, w = spec.dims(1, 1), _window(window, hop)
+    return spec.D == 1 and bool(_lib.lib().nsd_multi_window_path(C.byref(d), C.byref(w), int(M)))
+
+
+def multi_window_state(spec: ModelSpec, window: int, hop: int, M: int, S: int, device="cuda") -> torch.Tensor:
+    """A reset window state of M models with S streams each on `device`: fp32 [M, S, stream_stride].  state[m] is an ordinary
+    window_state of model m (window_step takes it as it is); the flat [M*S, stream_stride] view is what window_reset takes: stream
+    m*S + s is stream s of model m."""
+    d, w = spec.dims(1, 1), _window(window, hop)
+    n = int(_lib.lib().nsd_multi_window_state_bytes(C.byref(d), C.byref(w), int(M), int(S)))
+    if n < 0:
+        check(n, "nsd_multi_window_state_bytes")
+    state = torch.empty((int(M), int(S), n // (4 * int(M) * int(S))), dtype=torch.float32, device=device)
+    window_reset(spec, window, hop, state.view(int(M) * int(S), -1))
+    return state
+
+
+_multi_window_out = {}   # (device, M, B, D, K) -> (logits, probs, mean, ends, counts): reused per chunk shape, as window_step's
+
+
+def multi_window_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, state: torch.Tensor, *, window: int, hop: int,
+                      slots: Optional[torch.Tensor] = None, residual: bool = False, want_mean: bool = True,
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor, torch.Tensor]] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """Advance B continuous streams in each of M models by one launch: params [M,P], the chunk x [B,n,C] (shared by the models) or
+    [M,B,n,C], state [M,S,stream_stride]; stream b lives in stream slots[b] (or b) of every model.  Returns (logits [M,B,D,K], probs
+    [M,B,D,K], mean [B,D,K], ends int64 [M,B,D], counts int32 [M,B]), D = window_rows(n): per model what window_step gives, bit for bit,
+    and per row the mean of the models' probabilities (a serial fp32 sum over the models, divided by M; NaN where any model's row is;
+    None with want_mean=False: no second launch).  out: caller-owned buffers (logits, probs, mean, ends, counts), mean None without
+    the mean; without `out` the buffers of this chunk shape are reused from call to call (copy what must outlive the next call)."""
+    if params.dim() != 2:
+        raise NsdError(f"multi_window_step: params must be [M, {spec.param_count}], got {tuple(params.shape)}")
+    M = int(params.shape[0])
+    if x.dim() not in (3, 4) or x.shape[-1] != spec.C or (x.dim() == 4 and int(x.shape[0]) != M):
+        raise NsdError(f"multi_window_step: x must be [B, n, {spec.C}] or [{M}, B, n, {spec.C}], got {tuple(x.shape)}")
+    B, T = int(x.shape[-3]), int(x.shape[-2])
+    stride = B * T * spec.C if x.dim() == 4 else 0
+    if state.dim() != 3 or int(state.shape[0]) != M:
+        raise NsdError(f"multi_window_step: state must be [{M}, S, stream_stride], got {tuple(state.shape)}")
+    S = int(state.shape[1])
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"multi_window_step: {int(slots.numel())} slot indices for {B} streams")
+    d, w = spec.dims(B, T), _window(window, hop)
+    D = window_rows(T, window, hop)
+    if out is None:
+        key = (x.device, M, B, D, spec.K)
+        out = _multi_window_out.get(key)
+        if out is None:
+            out = _multi_window_out[key] = (torch.empty((M, B, D, spec.K), dtype=torch.float32, device=x.device),
+                                            torch.empty((M, B, D, spec.K), dtype=torch.float32, device=x.device),
+                                            torch.empty((B, D, spec.K), dtype=torch.float32, device=x.device),
+                                            torch.empty((M, B, D), dtype=torch.int64, device=x.device),
+                                            torch.empty((M, B), dtype=torch.int32, device=x.device))
+    logits, probs, mean, ends, counts = out
+    if not want_mean:
+        mean = None
+    n = M * B * D * spec.K
+    if (int(logits.numel()) != n or int(probs.numel()) != n or (want_mean and (mean is None or int(mean.numel()) != B * D * spec.K))
+            or int(ends.numel()) != M * B * D or int(counts.numel()) != M * B
+            or ends.dtype != torch.int64 or counts.dtype != torch.int32 or not ends.is_cuda or not counts.is_cuda
+            or not ends.is_contiguous() or not counts.is_contiguous()):
+        raise NsdError(f"multi_window_step: out must be (logits [{M},{B},{D},{spec.K}], probs [{M},{B},{D},{spec.K}], mean [{B},{D},{spec.K}]"
+                       f"{'' if want_mean else ' or None'}, ends int64 [{M},{B},{D}], counts int32 [{M},{B}]) on the device")
+    pp = _dev_f32(params, "params", (M, spec.param_count))
+    if B == 0:
+        _dev_f32(state, "state")
+        return logits, probs, mean, ends, counts
+    _call("nsd_multi_window_step", x.device, C.byref(d), C.byref(w), M, pp, _dev_f32(x, "x"), stride, _slots_ptr(slots, "multi_window_step"),
+          _lib.NSD_FLAG_RESIDUAL if residual else 0, _dev_f32(state, "state"), _nbytes(state), S, _dev_f32(logits, "logits"),
+          _dev_f32(probs, "probs"), _dev_f32(mean, "mean"), ends.data_ptr(), counts.data_ptr(), STREAM)
+    return logits, probs, mean, ends, counts
+
+
 # ---- causal front end for live streams and their training (nsd_prep_* of include/nsd.h; the configuration: prep.CausalPrep) ----
 
 def prep_path(C_: int, prep=None) -> bool:

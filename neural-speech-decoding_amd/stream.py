@@ -136,6 +136,34 @@ class StreamDecoder:
             self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
 
 
+def _check_ensemble(dec, models, streams, who: str, path):
+    """The refusals every ensemble stream decoder shares, and the members' stacked parameters: sets dec.members / model (member 0) /
+    streams / params [M,P] / device -> (members, first).  models: a sequence of EEG_LSTM, or the ensemble an EnsemblePredictor holds
+    (its stacked parameter buffer is then used, not a copy).  path(first, M): the decoder's own check of shape and configuration"""
+    from .lstm_eeg_model import EEG_LSTM
+    from .multimodel import _check_models
+    params = getattr(models, "params", None)
+    members = list(getattr(models, "models", models))
+    for m in members:
+        if not isinstance(m, EEG_LSTM):
+            raise NsdError(f"{who}: expected EEG_LSTM members, got {type(m).__name__}")
+    _check_models(members, who)
+    first = members[0]
+    if any(m.training for m in members):
+        raise NsdError(f"{who}: the models must be in eval mode (model.eval()): a stream is decoded without dropout")
+    if first.normalize:
+        raise NsdError(_NORMALIZE_REFUSAL.replace("StreamDecoder", who, 1))
+    path(first, len(members))
+    if int(streams) < 1:
+        raise NsdError(f"{who}: streams = {streams}")
+    if not all(m.flat_parameters().is_cuda for m in members):
+        raise NsdError(f"{who} runs only on the MI355X HIP path: move the models to the GPU first; there is no CPU fallback")
+    dec.members, dec.model, dec.streams = members, first, int(streams)
+    dec.params = params if params is not None else torch.stack([m.flat_parameters() for m in members]).contiguous()
+    dec.device = dec.params.device
+    return members, first
+
+
 class EnsembleStreamDecoder(StreamDecoder):
     """`streams` independent live streams decoded by an ensemble of M eval-mode EEG_LSTM models of one shape: every push advances all
     M models in one launch (nsd_multi_stream_step) and returns the mean of their class probabilities.  StreamDecoder's surface:
@@ -152,30 +180,13 @@ class EnsembleStreamDecoder(StreamDecoder):
     front end (equal `prep`): one prep state of S slots, nsd_prep_step once per push, its output read by all models."""
 
     def __init__(self, models, streams: int = 1):
-        from .lstm_eeg_model import EEG_LSTM
-        from .multimodel import _check_models
         who = "EnsembleStreamDecoder"
-        params = getattr(models, "params", None)
-        members = list(getattr(models, "models", models))
-        for m in members:
-            if not isinstance(m, EEG_LSTM):
-                raise NsdError(f"{who}: expected EEG_LSTM members, got {type(m).__name__}")
-        _check_models(members, who)
-        first = members[0]
-        if any(m.training for m in members):
-            raise NsdError(f"{who}: the models must be in eval mode (model.eval()): a stream is decoded without dropout")
-        if first.normalize:
-            raise NsdError(_NORMALIZE_REFUSAL.replace("StreamDecoder", who, 1))
-        if not ops.multi_stream_path(first.spec, len(members)):
-            raise NsdError(f"{who}: {len(members)} models of shape {first.spec} are outside nsd_multi_stream_path (nsd_stream_path: hidden "
-                           "size 48, 2 layers, <= 8 channels, fc width and classes <= 64; 1 <= M <= 32)")
-        if int(streams) < 1:
-            raise NsdError(f"{who}: streams = {streams}")
-        if not all(m.flat_parameters().is_cuda for m in members):
-            raise NsdError(f"{who} runs only on the MI355X HIP path: move the models to the GPU first; there is no CPU fallback")
-        self.members, self.model, self.streams = members, first, int(streams)
-        self.params = params if params is not None else torch.stack([m.flat_parameters() for m in members]).contiguous()
-        self.device = self.params.device
+
+        def path(first, M):
+            if not ops.multi_stream_path(first.spec, M):
+                raise NsdError(f"{who}: {M} models of shape {first.spec} are outside nsd_multi_stream_path (nsd_stream_path: hidden "
+                               "size 48, 2 layers, <= 8 channels, fc width and classes <= 64; 1 <= M <= 32)")
+        members, first = _check_ensemble(self, models, streams, who, path)
         self._layout = ops.stream_layout(first.spec)
         self.state = ops.multi_stream_state(first.spec, len(members), self.streams, self.device)
         self.prep = first.prep
@@ -251,14 +262,17 @@ class SlidingStreamDecoder(StreamDecoder):
     def _step(self, x: torch.Tensor, slots, read: bool):
         _, probs, ends, counts = ops.window_step(self.model.spec, self.model.flat_parameters(), x, self.state, window=self.window,
                                                  hop=self.hop, slots=slots, residual=self.model.residual)
+        self._keep_latest(int(x.shape[0]), slots, probs, ends, counts)
+        return probs, ends, counts
+
+    def _keep_latest(self, B: int, slots, probs: torch.Tensor, ends: torch.Tensor, counts: torch.Tensor) -> None:
         # the newest completed window of every pushed stream, kept on the device (the output buffers are reused)
-        idx = self._all[:x.shape[0]] if slots is None else slots.long()
+        idx = self._all[:B] if slots is None else slots.long()
         has = counts > 0
         row = (counts.long() - 1).clamp_(min=0)
         self._last_end[idx] = torch.where(has, ends.gather(1, row[:, None])[:, 0], self._last_end[idx])
         newest = probs.gather(1, row[:, None, None].expand(-1, 1, probs.shape[2]))[:, 0]
         self._last_probs[idx] = torch.where(has[:, None], newest, self._last_probs[idx])
-        return probs, ends, counts
 
     def latest(self) -> list:
         ends, probs = self._last_end.cpu().numpy(), self._last_probs.cpu().numpy()
@@ -286,7 +300,7 @@ class SlidingStreamDecoder(StreamDecoder):
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
-        who = "SlidingStreamDecoder.load_state_dict"
+        who = f"{type(self).__name__}.load_state_dict"
         if (int(sd.get("window", -1)), int(sd.get("hop", -1))) != (self.window, self.hop):
             raise NsdError(f"{who}: a checkpoint of window = {sd.get('window')}, hop = {sd.get('hop')} for a decoder of window = "
                            f"{self.window}, hop = {self.hop}")
@@ -301,6 +315,75 @@ class SlidingStreamDecoder(StreamDecoder):
             self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
         self._last_end.copy_(sd["last_end"].to(self.device))
         self._last_probs.copy_(sd["last_probs"].to(self.device))
+
+
+class EnsembleSlidingStreamDecoder(SlidingStreamDecoder):
+    """`streams` continuous (uncued) streams decoded by an ensemble of M eval-mode EEG_LSTM models of one shape: every `hop` samples the
+    mean of the M decisions over the last `window` samples -- nsd_multi_window_step, one launch per chunk for all models (and one small
+    launch for the mean).  SlidingStreamDecoder's surface:
+
+      push(samples, slots=None)      -> (mean probs [B, D, K], ends int64 [B, D], counts int32 [B]), device tensors, no host
+                                     synchronisation.  A mean row is the serial fp32 sum of the members' rows divided by M, and NaN
+                                     where any member's row is (an unused row, a poisoned window, a skipped member); ends / counts are
+                                     model 0's.  The buffers are reused by the next push of the same chunk shape.
+      member_probs                   the models' own probabilities [M, B, D, K] of the last push: bit for bit what M
+                                     SlidingStreamDecoders return (None before the first push)
+      latest()                       per slot the most recent completed window's (end, mean probs float32 [K]), or None
+      reset(slots=None), steps       a stream is reset in every model (m*S + s of the flat state) and in the front end; the samples
+                                     seen per slot (the models' counts agree)
+      state_dict() / load_state_dict()   the [M, S, stream_stride] state, window, hop, the last decisions (+ the front end's state); a
+                                     checkpoint of another shape, M, window or hop is refused
+
+    models: as EnsembleStreamDecoder's -- a sequence of EEG_LSTM of one shape and options, or the ensemble an EnsemblePredictor holds
+    (its stacked [M, P] parameter buffer is then used, not a copy).  The members share one causal front end (equal `prep`): one prep
+    state of S slots runs continuously over the stream, nsd_prep_step once per push, its output read by all models."""
+
+    def __init__(self, models, streams: int = 1, *, window: int, hop: int):
+        who = "EnsembleSlidingStreamDecoder"
+
+        def path(first, M):
+            if not ops.multi_window_path(first.spec, window, hop, M):
+                raise NsdError(f"{who}: {M} models of shape {first.spec} with window = {window}, hop = {hop} samples are outside "
+                               "nsd_multi_window_path (nsd_stream_path: hidden size 48, 2 layers, <= 8 channels, fc width and classes "
+                               "<= 64; nsd_window_path: 1 <= hop <= window, window % hop == 0, window / hop <= 128; 1 <= M <= 32)")
+        members, first = _check_ensemble(self, models, streams, who, path)
+        self.window, self.hop = int(window), int(hop)
+        self._layout = ops.window_layout(first.spec, self.window, self.hop)
+        self.state = ops.multi_window_state(first.spec, self.window, self.hop, len(members), self.streams, self.device)
+        self.prep = first.prep
+        self.prep_state = None if self.prep is None else ops.prep_state(first.spec.C, self.streams, self.device)
+        self._prepped = {}
+        self._all = torch.arange(self.streams, dtype=torch.int64, device=self.device)
+        self._last_end = torch.full((self.streams,), -1, dtype=torch.int64, device=self.device)
+        self._last_probs = torch.full((self.streams, first.spec.K), float("nan"), dtype=torch.float32, device=self.device)
+        self.member_probs: Optional[torch.Tensor] = None
+
+    def _step(self, x: torch.Tensor, slots, read: bool):
+        _, probs, mean, ends, counts = ops.multi_window_step(self.model.spec, self.params, x, self.state, window=self.window, hop=self.hop,
+                                                             slots=slots, residual=self.model.residual)
+        self.member_probs = probs
+        self._keep_latest(int(x.shape[0]), slots, mean, ends[0], counts[0])
+        return mean, ends[0], counts[0]
+
+    def reset(self, slots=None) -> None:
+        slots = self._slots(slots)
+        M, S = len(self.members), self.streams
+        flat = self.state.view(M * S, -1)
+        if slots is None:
+            ops.window_reset(self.model.spec, self.window, self.hop, flat)
+        else:                                               # stream s of every model: m*S + s of the flat state
+            every = (slots[None, :] + S * torch.arange(M, dtype=torch.int32, device=self.device)[:, None]).reshape(-1).contiguous()
+            ops.window_reset(self.model.spec, self.window, self.hop, flat, every)
+        if self.prep is not None:
+            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+        idx = self._all if slots is None else slots.long()
+        self._last_end[idx] = -1
+        self._last_probs[idx] = float("nan")
+
+    @property
+    def steps(self) -> np.ndarray:
+        col = int(self._layout.count) // 2
+        return self.state[0].view(torch.int64)[:, col].cpu().numpy().copy()
 
 
 class PredictorStream:
@@ -337,13 +420,13 @@ class PredictorStream:
 class PredictorSlidingStream:
     """What SimplePredictor.open_stream(window_seconds=, hop_seconds=) returns: numpy chunks of a continuous stream in; per stream a
     list of (end_sample, probs float32 [K], label) out, one entry per window the chunk completed (a SlidingStreamDecoder of `window`
-    and `hop` samples)."""
+    and `hop` samples).  A predictor with `members` (EnsemblePredictor) is decoded by all of them: an EnsembleSlidingStreamDecoder, the
+    probabilities are their mean."""
 
     def __init__(self, predictor, streams: int, chunk_transform, window: int, hop: int):
-        if getattr(predictor, "members", None) is not None:
-            raise NsdError("SimplePredictor.open_stream: sliding windows decode one model; an ensemble per sliding stream is not built")
         self.predictor, self.chunk_transform = predictor, chunk_transform
-        self.decoder = SlidingStreamDecoder(predictor.model, streams, window=window, hop=hop)
+        ensemble = getattr(predictor, "members", None) is not None
+        self.decoder = (EnsembleSlidingStreamDecoder if ensemble else SlidingStreamDecoder)(predictor.model, streams, window=window, hop=hop)
 
     def push(self, chunk: np.ndarray, slots=None) -> list:
         x = np.asarray(chunk)

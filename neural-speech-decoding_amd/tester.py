@@ -150,7 +150,8 @@ def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels
     `hop_seconds` (with chunk_seconds): no cue -- the decoder is not reset between the producer's windows, their chunks form one
     continuous stream, and every hop_seconds the window of the last window_seconds is decided (open_stream(window_seconds=,
     hop_seconds=)); every completed window is printed and counted, `trials` of them end the run.
-    `model_path` may also be a list of checkpoints: an EnsemblePredictor decodes, in both modes (the mean of the models' probabilities).
+    `model_path` may also be a list of checkpoints: an EnsemblePredictor decodes, in every mode (the mean of the models' probabilities;
+    with hop_seconds an EnsembleSlidingStreamDecoder: all models advance in one launch per chunk).
     """
     if hop_seconds is not None:
         if chunk_seconds is None:
