@@ -404,7 +404,7 @@ int nsd_adam_step_clip(int64_t n, float *p, const float *g, float *m, float *v, 
  *   labels   [M*B]  logits / probs [M*B][K]  grads [M][P]
  *   workspace  the regions of a batch of M*B trials (model m's trial b is trial m*B + b); nsd_multi_workspace_bytes
  *   rng      NULL (no dropout, eval RReLU slope) or M entries: model m's streams are exactly those of a single-model call with rng[m]
- *            at batch B (nsd_lstm_head_train_rng).  All entries share p_lstm / p_head.
+ *            at batch B (nsd_lstm_head_train_rng).  All entries share p_lstm / p_head (per-model ones: NSD_FLAG_MODEL_P, below).
  * Each model's step is that of nsd_lstm_head_train_rng (scale 1/B: mean CE per model, lstm_eeg_model.py:32-39) + nsd_lstm_bwd_rng +
  * nsd_grad_reduce(_adam) on its own; the kernels dispatch on the M*B trials of the launch as the single-model entry points do on B.
  * Where nsd_multi_path(d, M) == 0 every entry point returns NSD_E_INVALID before any launch (nsd_last_error says why), as it does for
@@ -441,6 +441,38 @@ int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int
 int64_t nsd_multi_infer_scratch_bytes(const nsd_dims *d, int32_t M);
 int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,
                     float *logits, float *probs, void *scratch, void *stream);
+
+/*
+ * ---- per-model step settings: a hyper-parameter grid (configurations x folds) in the launches one model uses ----
+ *
+ * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_multi_hyper_path).  The model axis of the entry points
+ * above holds folds and seeds; with these it also holds configurations: every scalar of a train step is per model.
+ *   nsd_multi_hyper_path      1 where the entry points below are offered (the domain of nsd_multi_path), else 0
+ *   NSD_FLAG_MODEL_P          accepted by nsd_multi_train_fwd, nsd_multi_train_fwd_soft and nsd_multi_train_bwd only: rng[m].p_lstm /
+ *                             rng[m].p_head may differ from model to model (each in [0, 1), 0 included).  The same flag and the same
+ *                             rng array go to the forward and the backward call of a step.  Without the flag mixed probabilities are
+ *                             refused as before; with the flag and equal probabilities the call is bit for bit the unflagged one;
+ *                             M = 1 strips the bit and runs the single-model entry point.  Model m's workgroups run the instructions
+ *                             of a launch of the same M and B in which every model has rng[m]'s probabilities, on the same data.
+ *   nsd_augment_each          nsd_augment with aug pointing to M entries; each operation is skipped per model where that model's
+ *                             parameter is 0; NSD_AUG_ZSCORE stays per launch
+ *   nsd_mixup_each            nsd_mixup with mix pointing to M entries and class_weight NULL or [M][K]; with any mix[m].mix > 0, x and y
+ *                             are required, and a model with mix == 0 gets a bitwise copy of its windows and un-multiplied target rows
+ *   nsd_multi_grad_reduce_clip_adam_each
+ *                             nsd_multi_grad_reduce_clip_adam with opt pointing to M entries: every field per model, grad_scale
+ *                             included; opt_state, records, step / step_dev and the two launches are unchanged
+ * Each entry of aug / mix / opt is validated as the twin validates its one, before any launch; the refusal names the entry
+ * ("augment_each: aug[2]: max_shift ...").  Model m's result is bit for bit that of the twin called with entry m for all models.
+ */
+#define NSD_FLAG_MODEL_P    16u
+int nsd_multi_hyper_path(const nsd_dims *d, int32_t M);
+int nsd_augment_each(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug, const nsd_rng *rng,
+                     const int64_t *step_dev, uint32_t flags, float *y, void *stream);
+int nsd_mixup_each(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels, const float *class_weight,
+                   const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev, float *y, float *targets, void *stream);
+int nsd_multi_grad_reduce_clip_adam_each(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads,
+                                         float *p, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                                         void *opt_state, int64_t opt_state_bytes, void *stream);
 
 /*
  * ---- resumable H = 48 inference: decode live streams chunk by chunk (an EXTENSION: the reference decodes whole windows only) ----

@@ -17,6 +17,7 @@ NSD_FLAG_RESIDUAL = 1
 NSD_FLAG_TRAIN = 2
 NSD_FLAG_BF16 = 4
 NSD_FLAG_BIDIR = 8
+NSD_FLAG_MODEL_P = 16     # nsd_multi_train_fwd / _fwd_soft / _bwd only: rng[m].p_lstm / p_head per model (hyper-parameter grids)
 # honoured by the DIAGNOSTIC build only (csrc/nsd_diag.h, libnsd_hip_diag.so); the product library rejects them
 NSD_DIAG_FLAG_NO_L2_EXCHANGE = 16
 NSD_DIAG_FLAG_SPREAD_GROUPS = 32
@@ -177,6 +178,11 @@ SYMBOLS = {
     "nsd_adam_step_clip": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _fp, _vp, C.c_int64, _vp]),
     "nsd_multi_grad_reduce_clip_adam": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
     "nsd_multi_loss_sum": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
+    # per-model step settings (hyper-parameter grids): the `_each` twins take M entries of nsd_aug / nsd_mix / nsd_opt
+    "nsd_multi_hyper_path": (C.c_int, [_dp, C.c_int32]),
+    "nsd_augment_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _vp, _vp, _vp, C.c_uint32, _fp, _vp]),
+    "nsd_mixup_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _ip, _fp, _vp, _vp, _vp, _fp, _fp, _vp]),
+    "nsd_multi_grad_reduce_clip_adam_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
     "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
     "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),
     # resumable H = 48 inference (streams decoded chunk by chunk)

@@ -1,6 +1,7 @@
 // nsd_abi.hip -- extern "C" entry points of libnsd_hip.so (declared in include/nsd.h).
 // Argument validation, parameter / workspace layout, kernel dispatch.  No allocation, no synchronisation.
 #include <stdarg.h>
+#include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
 #include <math.h>
@@ -635,7 +636,7 @@ int nsd_grad_reduce_clip_adam(const nsd_dims *d, const float *workspace, int64_t
     if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, layout_of(d).total, 1)) return rc;
     Ctx c;
     if (const int rc = enter(&c, who, d, true, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
-    return nsd_reduce_clip_adam_launch(slab_set(c), 1, grads, p, m, v, opt, step, (const long long *)step_dev, opt_state, who, c.st);
+    return nsd_reduce_clip_adam_launch(slab_set(c), 1, grads, p, m, v, opt, 0, step, (const long long *)step_dev, opt_state, who, c.st);
 }
 
 int nsd_grad_norm(int64_t n, const float *g, float grad_scale, void *opt_state, int64_t opt_state_bytes, void *stream) {
@@ -713,18 +714,28 @@ static bool augment_shape(const nsd_dims *d) {
 }
 int nsd_augment_path(const nsd_dims *d) { return augment_shape(d) ? 1 : 0; }
 
-int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug, const nsd_rng *rng,
-                const int64_t *step_dev, uint32_t flags, float *y, void *stream) {
-    static const char *who = "augment";
+// one nsd_aug's fields (who: "augment", or "augment_each: aug[m]")
+static int aug_check(const char *who, const nsd_aug *aug, int T) {
+    if (aug->max_shift < 0 || aug->max_shift >= T) { nsd_set_error("%s: max_shift %d outside [0, T = %d)", who, aug->max_shift, T); return NSD_E_INVALID; }
+    if (!(aug->scale_range >= 0.f && aug->scale_range < 1.f)) { nsd_set_error("%s: scale_range %g outside [0, 1)", who, aug->scale_range); return NSD_E_INVALID; }
+    if (!(aug->p_channel >= 0.f && aug->p_channel < 1.f)) { nsd_set_error("%s: p_channel %g outside [0, 1)", who, aug->p_channel); return NSD_E_INVALID; }
+    if (!(aug->noise_std >= 0.f && aug->noise_std <= 3.4028234e38f)) { nsd_set_error("%s: noise_std %g negative or not finite", who, aug->noise_std); return NSD_E_INVALID; }
+    return NSD_OK;
+}
+
+// each: aug points to M entries (nsd_augment_each), else to one for all models
+static int augment_impl(const char *who, bool each, const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug,
+                        const nsd_rng *rng, const int64_t *step_dev, uint32_t flags, float *y, void *stream) {
     if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
     if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
     if (!x || !y || !aug || !rng) { nsd_set_error("%s: null pointer (x, y, aug, rng)", who); return NSD_E_INVALID; }
     if (!augment_shape(d)) { nsd_set_error("%s: shape B=%d T=%d C=%d outside nsd_augment_path (B >= 0, T >= 1, 1 <= C <= 256)", who, d->B, d->T, d->C); return NSD_E_INVALID; }
     if (flags & ~NSD_AUG_ZSCORE) { nsd_set_error("%s: unknown flag bits 0x%x", who, flags); return NSD_E_INVALID; }
-    if (aug->max_shift < 0 || aug->max_shift >= d->T) { nsd_set_error("%s: max_shift %d outside [0, T = %d)", who, aug->max_shift, d->T); return NSD_E_INVALID; }
-    if (!(aug->scale_range >= 0.f && aug->scale_range < 1.f)) { nsd_set_error("%s: scale_range %g outside [0, 1)", who, aug->scale_range); return NSD_E_INVALID; }
-    if (!(aug->p_channel >= 0.f && aug->p_channel < 1.f)) { nsd_set_error("%s: p_channel %g outside [0, 1)", who, aug->p_channel); return NSD_E_INVALID; }
-    if (!(aug->noise_std >= 0.f && aug->noise_std <= 3.4028234e38f)) { nsd_set_error("%s: noise_std %g negative or not finite", who, aug->noise_std); return NSD_E_INVALID; }
+    for (int m = 0; m < (each ? M : 1); ++m) {
+        char entry[48];
+        if (each) snprintf(entry, sizeof(entry), "%s: aug[%d]", who, m);
+        if (const int rc = aug_check(each ? entry : who, &aug[m], d->T)) return rc;
+    }
     const int64_t n = (int64_t)d->B * d->T * d->C;
     if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
         nsd_set_error("%s: x_model_stride %lld: 0 (one window set for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
@@ -739,28 +750,53 @@ int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_st
     memset(&a, 0, sizeof(a));
     a.x = x; a.y = y; a.x_stride = x_model_stride; a.step_dev = (const long long *)step_dev;
     a.B = d->B; a.T = d->T; a.C = d->C; a.M = M;
-    a.max_shift = aug->max_shift;
-    a.scale_range = aug->scale_range; a.scale_on = aug->scale_range != 0.f;
-    a.noise_k = (float)((double)aug->noise_std / sqrt(21845.0)); a.noise_on = aug->noise_std != 0.f;
-    a.thr_channel = nsd_drop_threshold(aug->p_channel); a.drop_on = aug->p_channel != 0.f;
     a.zscore = (flags & NSD_AUG_ZSCORE) != 0;
-    for (int m = 0; m < M; ++m) { a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream; }
+    for (int m = 0; m < M; ++m) {
+        const nsd_aug *g = each ? &aug[m] : aug;
+        AugArgs::Model &am = a.mod[m];
+        am.max_shift = g->max_shift;
+        am.scale_range = g->scale_range; am.scale_on = g->scale_range != 0.f;
+        am.noise_k = (float)((double)g->noise_std / sqrt(21845.0)); am.noise_on = g->noise_std != 0.f;
+        am.thr_channel = nsd_drop_threshold(g->p_channel); am.drop_on = g->p_channel != 0.f;
+        a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream;
+    }
     return nsd_augment_launch(a, (hipStream_t)stream);
 }
 
+int nsd_augment(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug, const nsd_rng *rng,
+                const int64_t *step_dev, uint32_t flags, float *y, void *stream) {
+    return augment_impl("augment", false, d, M, x, x_model_stride, aug, rng, step_dev, flags, y, stream);
+}
+
+int nsd_augment_each(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_aug *aug, const nsd_rng *rng,
+                     const int64_t *step_dev, uint32_t flags, float *y, void *stream) {
+    return augment_impl("augment_each", true, d, M, x, x_model_stride, aug, rng, step_dev, flags, y, stream);
+}
+
 // ---- soft targets and mixed windows (nsd_mixup, include/nsd.h; nsd_mixup.hip) ------------------------------------------------------
-int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels, const float *class_weight,
-              const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev, float *y, float *targets, void *stream) {
-    static const char *who = "mixup";
+// each: mix points to M entries and class_weight is NULL or [M][K] (nsd_mixup_each), else one nsd_mix and NULL or [K] for all models
+static int mixup_impl(const char *who, bool each, const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels,
+                      const float *class_weight, const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev, float *y, float *targets,
+                      void *stream) {
     if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
     if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
     if (!labels || !targets || !mix || !rng) { nsd_set_error("%s: null pointer (labels, targets, mix, rng)", who); return NSD_E_INVALID; }
     if (d->B < 0 || d->T < 1 || d->C < 1 || (int64_t)d->T * d->C > 0x7fffffff) { nsd_set_error("%s: shape B=%d T=%d C=%d (B >= 0, T >= 1, C >= 1)", who, d->B, d->T, d->C); return NSD_E_INVALID; }
     if (d->K < 1 || d->K > 64) { nsd_set_error("%s: K = %d classes outside [1, 64]", who, d->K); return NSD_E_INVALID; }
-    if (!(mix->smoothing >= 0.f && mix->smoothing < 1.f)) { nsd_set_error("%s: smoothing %g outside [0, 1)", who, mix->smoothing); return NSD_E_INVALID; }
-    if (!(mix->mix >= 0.f && mix->mix <= 1.f)) { nsd_set_error("%s: mix %g outside [0, 1]", who, mix->mix); return NSD_E_INVALID; }
+    for (int m = 0; m < (each ? M : 1); ++m) {
+        char entry[48];
+        if (each) snprintf(entry, sizeof(entry), "%s: mix[%d]", who, m);
+        const char *w = each ? entry : who;
+        if (!(mix[m].smoothing >= 0.f && mix[m].smoothing < 1.f)) { nsd_set_error("%s: smoothing %g outside [0, 1)", w, mix[m].smoothing); return NSD_E_INVALID; }
+        if (!(mix[m].mix >= 0.f && mix[m].mix <= 1.f)) { nsd_set_error("%s: mix %g outside [0, 1]", w, mix[m].mix); return NSD_E_INVALID; }
+    }
     if ((x == nullptr) != (y == nullptr)) { nsd_set_error("%s: x and y are given together or not at all", who); return NSD_E_INVALID; }
-    if (mix->mix > 0.f && !x) { nsd_set_error("%s: mix = %g needs the windows x and y", who, mix->mix); return NSD_E_INVALID; }
+    for (int m = 0; m < (each ? M : 1); ++m)
+        if (mix[m].mix > 0.f && !x) {
+            if (each) nsd_set_error("%s: mix[%d]: mix = %g needs the windows x and y", who, m, mix[m].mix);
+            else nsd_set_error("%s: mix = %g needs the windows x and y", who, mix[m].mix);
+            return NSD_E_INVALID;
+        }
     const int64_t n = (int64_t)d->B * d->T * d->C;
     if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
         nsd_set_error("%s: x_model_stride %lld: 0 (one window set for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
@@ -776,11 +812,24 @@ int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stri
     MixArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.y = y; a.x_stride = x_model_stride; a.step_dev = (const long long *)step_dev;
-    a.labels = labels; a.w = class_weight; a.targets = targets;
+    a.labels = labels; a.w = class_weight; a.w_stride = each ? d->K : 0; a.targets = targets;
     a.n_el = (long)d->T * d->C; a.B = d->B; a.K = d->K; a.M = M;
-    a.mix = mix->mix; a.eps = mix->smoothing;
-    for (int m = 0; m < M; ++m) { a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream; }
+    for (int m = 0; m < M; ++m) {
+        const nsd_mix *g = each ? &mix[m] : mix;
+        a.mix[m] = g->mix; a.eps[m] = g->smoothing;
+        a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream;
+    }
     return nsd_mixup_launch(a, (hipStream_t)stream);
+}
+
+int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels, const float *class_weight,
+              const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev, float *y, float *targets, void *stream) {
+    return mixup_impl("mixup", false, d, M, x, x_model_stride, labels, class_weight, mix, rng, step_dev, y, targets, stream);
+}
+
+int nsd_mixup_each(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const int32_t *labels, const float *class_weight,
+                   const nsd_mix *mix, const nsd_rng *rng, const int64_t *step_dev, float *y, float *targets, void *stream) {
+    return mixup_impl("mixup_each", true, d, M, x, x_model_stride, labels, class_weight, mix, rng, step_dev, y, targets, stream);
 }
 
 // ---- model-batched H = 48 path (nsd_multi_*, include/nsd.h; nsd_multi.h) ----------------------------------------------------------
@@ -797,11 +846,12 @@ static int multi_check(const nsd_dims *d, int M, const char *who) {
     }
     return NSD_OK;
 }
-// rng: NULL or M entries with one p_lstm / p_head
-static int multi_rng(const nsd_rng *rng, int M, const char *who, RngArgs *r, ModelSplit *s) {
+// rng: NULL or M entries with one p_lstm / p_head; with NSD_FLAG_MODEL_P each entry has its own.  Either way the kernels read model m's
+// thresholds and keep factors from s (nsd_multi.h), formed per entry as nsd_rng_args forms them.
+static int multi_rng(const nsd_rng *rng, int M, uint32_t flags, const char *who, RngArgs *r, ModelSplit *s) {
     memset(r, 0, sizeof(*r));
     if (!rng) return NSD_OK;
-    for (int m = 0; m < M; ++m)
+    for (int m = 0; m < M && !(flags & NSD_FLAG_MODEL_P); ++m)
         if (rng[m].p_lstm != rng[0].p_lstm || rng[m].p_head != rng[0].p_head) {
             nsd_set_error("%s: rng[%d] has p_lstm / p_head %g / %g, rng[0] %g / %g: all models share the probabilities", who, m,
                           rng[m].p_lstm, rng[m].p_head, rng[0].p_lstm, rng[0].p_head);
@@ -809,7 +859,12 @@ static int multi_rng(const nsd_rng *rng, int M, const char *who, RngArgs *r, Mod
         }
     if (make_rng(&rng[0], r) != NSD_OK) return NSD_E_INVALID;
     s->rng_on = 1;
-    for (int m = 0; m < M; ++m) { s->seed[m] = rng[m].seed; s->base[m] = rng[m].base_stream; }
+    for (int m = 0; m < M; ++m) {
+        RngArgs rm;
+        if (make_rng(&rng[m], &rm) != NSD_OK) { nsd_set_error("%s: rng[%d]: p_lstm / p_head %g / %g out of [0,1)", who, m, rng[m].p_lstm, rng[m].p_head); return NSD_E_INVALID; }
+        s->seed[m] = rm.seed; s->base[m] = rm.base;
+        s->drop[m].thr_lstm = rm.thr_lstm; s->drop[m].thr_head = rm.thr_head; s->drop[m].keep_lstm = rm.keep_lstm; s->drop[m].keep_head = rm.keep_head;
+    }
     return NSD_OK;
 }
 static int multi_common(const nsd_dims *d, int M, int64_t x_stride, uint32_t flags, const char *who) {
@@ -824,6 +879,7 @@ static int multi_common(const nsd_dims *d, int M, int64_t x_stride, uint32_t fla
 }
 
 int nsd_multi_path(const nsd_dims *d, int32_t M) { return multi_shape(d, M) ? 1 : 0; }
+int nsd_multi_hyper_path(const nsd_dims *d, int32_t M) { return nsd_multi_path(d, M); }
 
 int64_t nsd_multi_workspace_bytes(const nsd_dims *d, int32_t M, nsd_ws_layout *layout_out) {
     if (multi_check(d, M, "multi_workspace_bytes") != NSD_OK) return NSD_E_INVALID;
@@ -847,7 +903,8 @@ static int multi_train_fwd_impl(const char *who, const nsd_dims *d, int32_t M, c
     if (!params || !x || !tg.given() || !logits) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     ModelSplit s = model_split(d, x_model_stride);
     RngArgs r;
-    if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
+    if (multi_rng(rng, M, flags, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
+    flags &= ~NSD_FLAG_MODEL_P;
     Ctx c;
     if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream)) return leave(rc);
     const float scale = 1.0f / (float)d->B;                     // mean CE per model
@@ -876,7 +933,8 @@ int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const
     if (!params || !x) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
     ModelSplit s = model_split(d, x_model_stride);
     RngArgs r;
-    if (multi_rng(rng, M, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
+    if (multi_rng(rng, M, flags, who, &r, &s) != NSD_OK) return NSD_E_INVALID;
+    flags &= ~NSD_FLAG_MODEL_P;
     Ctx c;
     if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream)) return leave(rc);
     if (M == 1) return lstm_bwd_impl(d, params, x, nullptr, rng ? &r : nullptr, flags, workspace, workspace_bytes, nullptr, stream);
@@ -919,7 +977,27 @@ int nsd_multi_grad_reduce_clip_adam(const nsd_dims *d, int32_t M, const float *w
     Ctx c;
     if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
     if (M == 1) return nsd_grad_reduce_clip_adam(d, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state, opt_state_bytes, stream);
-    return nsd_reduce_clip_adam_launch(slab_set(c), M, grads, p, m, v, opt, step, (const long long *)step_dev, opt_state, who, c.st);
+    return nsd_reduce_clip_adam_launch(slab_set(c), M, grads, p, m, v, opt, 0, step, (const long long *)step_dev, opt_state, who, c.st);
+}
+
+// opt: M entries, every field per model (M = 1: the single-model entry point with opt[0])
+int nsd_multi_grad_reduce_clip_adam_each(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads,
+                                         float *p, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                                         void *opt_state, int64_t opt_state_bytes, void *stream) {
+    static const char *who = "multi_grad_reduce_clip_adam_each";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!grads || !p || !m || !v) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (!opt) { nsd_set_error("%s: opt is NULL", who); return NSD_E_INVALID; }
+    for (int mo = 0; mo < M; ++mo) {
+        char entry[64];
+        snprintf(entry, sizeof(entry), "%s: opt[%d]", who, mo);
+        if (const int rc = nsd_opt_check(&opt[mo], entry)) return rc;
+    }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, layout_of(d).total, M)) return rc;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
+    if (M == 1) return nsd_grad_reduce_clip_adam(d, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state, opt_state_bytes, stream);
+    return nsd_reduce_clip_adam_launch(slab_set(c), M, grads, p, m, v, opt, 1, step, (const long long *)step_dev, opt_state, who, c.st);
 }
 
 int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {

@@ -143,13 +143,17 @@ struct AugArgs {
     long long x_stride;                      // floats between two models' windows (0: shared)
     const long long *step_dev;               // null, or the device step counter the stream id is formed from
     int B, T, C, M;
-    int max_shift;                           // 0: off
-    float scale_range, noise_k;              // noise_k = float(double(noise_std) / sqrt(21845))
-    uint32_t thr_channel;                    // a channel is dropped when its draw is below this
-    int scale_on, noise_on, drop_on, zscore; // an operation is on when its parameter is not 0 (noise_k may round to 0 while noise_std is not)
+    int zscore;                              // per launch (it selects the kernel)
+    struct Model {                           // model m's nsd_aug (nsd_augment: M equal entries; nsd_augment_each: its own), read with the
+        int max_shift;                       // workgroup's m: scalar loads from the kernel arguments.  0: off
+        float scale_range, noise_k;          // noise_k = float(double(noise_std) / sqrt(21845))
+        uint32_t thr_channel;                // a channel is dropped when its draw is below this
+        int scale_on, noise_on, drop_on;     // an operation is on when its parameter is not 0 (noise_k may round to 0 while noise_std is not)
+    } mod[NSD_MAX_MODELS];
     uint64_t seed[NSD_MAX_MODELS];
     uint32_t base[NSD_MAX_MODELS];
 };
+static_assert(sizeof(AugArgs) <= 2048, "AugArgs stays well inside the 4 KB kernarg segment");
 int nsd_augment_launch(const AugArgs &a, hipStream_t st);
 // soft targets and mixed windows (nsd_mixup of nsd.h; nsd_mixup.hip)
 struct MixArgs {
@@ -157,11 +161,12 @@ struct MixArgs {
     long long x_stride;                      // floats between two models' windows (0: shared)
     const long long *step_dev;               // null, or the device step counter the stream id is formed from
     const int32_t *labels;                   // [M*B]
-    const float *w;                          // null, or the class weights [K]
+    const float *w;                          // null, or the class weights: model m's row is w + m * w_stride
+    long w_stride;                           // 0 (one row [K] for all models: nsd_mixup) or K ([M][K]: nsd_mixup_each)
     float *targets;                          // [M*B][K]
     long n_el;                               // T * C
     int B, K, M;
-    float mix, eps;
+    float mix[NSD_MAX_MODELS], eps[NSD_MAX_MODELS];   // model m's nsd_mix (nsd_mixup: M equal entries), read with the workgroup's m
     uint64_t seed[NSD_MAX_MODELS];
     uint32_t base[NSD_MAX_MODELS];
 };
@@ -182,8 +187,8 @@ int nsd_opt_check(const nsd_opt *o, const char *who);
 double nsd_lr_factor_host(const nsd_opt *o, long long step);
 int64_t nsd_opt_state_need(int64_t n, int M);
 int nsd_opt_state_init_launch(void *state, int64_t bytes, hipStream_t st);
-int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int step,
-                                const long long *step_dev, void *state, const char *who, hipStream_t st);
+int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int each, int step,
+                                const long long *step_dev, void *state, const char *who, hipStream_t st);   // each: o has M entries
 int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st);
 int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float *v, const nsd_opt *o, int step, const long long *step_dev,
                               const float *skip, void *state, hipStream_t st);

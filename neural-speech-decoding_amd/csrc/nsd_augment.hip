@@ -28,15 +28,16 @@ struct AugTrial {                                          // what one workgroup
     bool dropped;                                          // this thread's channel
 };
 
-__device__ __forceinline__ float aug_value(const AugArgs &a, const AugTrial &tr, const int t, const int ch, const int e) {
+// (am: the parameters of the trial's model, AugArgs::mod[m]; workgroup-uniform)
+__device__ __forceinline__ float aug_value(const AugArgs &a, const AugArgs::Model &am, const AugTrial &tr, const int t, const int ch, const int e) {
     int ts = t;
-    if (a.max_shift) { ts = t - tr.shift; ts = ts < 0 ? 0 : (ts > a.T - 1 ? a.T - 1 : ts); }
+    if (am.max_shift) { ts = t - tr.shift; ts = ts < 0 ? 0 : (ts > a.T - 1 ? a.T - 1 : ts); }
     float v = tr.xb[(size_t)ts * a.C + ch];
-    if (a.scale_on) v = __fmul_rn(tr.scale, v);
-    if (a.noise_on) {
+    if (am.scale_on) v = __fmul_rn(tr.scale, v);
+    if (am.noise_on) {
         const uint32_t q = nsd_rand_u32(tr.seed, tr.stream, tr.ebase + (uint64_t)e);
         const int n = (int)__builtin_amdgcn_sad_u8(q, 0u, 0u) - 510;          // sum of the four bytes, one instruction
-        v = __fadd_rn(v, __fmul_rn(a.noise_k, (float)n));
+        v = __fadd_rn(v, __fmul_rn(am.noise_k, (float)n));
     }
     return tr.dropped ? 0.f : v;
 }
@@ -57,6 +58,7 @@ __global__ __launch_bounds__(AUG_NT) void augment_kernel(const AugArgs a) {
     const long total = (long)a.M * a.B;
     for (long g = blockIdx.x; g < total; g += gridDim.x) {
         const int m = (int)(g / a.B), b = (int)(g - (long)m * a.B);
+        const AugArgs::Model am = a.mod[m];
         AugTrial tr;
         tr.xb = a.x + (size_t)m * a.x_stride + (size_t)b * n_el;
         tr.seed = a.seed[m];
@@ -65,25 +67,25 @@ __global__ __launch_bounds__(AUG_NT) void augment_kernel(const AugArgs a) {
         float *yb = a.y + (size_t)g * n_el;
         // ---- per-trial draws, once per workgroup ----
         const uint64_t pidx = AUG_TRIAL_BIT | ((uint64_t)b << 16);
-        if (a.drop_on && tid < C) draw[2 + tid] = nsd_rand_u32(tr.seed, tr.stream, pidx | (uint64_t)(256 + tid)) < a.thr_channel ? 1u : 0u;
-        if (a.max_shift && tid == AUG_NT - 64)
-            draw[0] = (uint32_t)((int)(nsd_rand_u32(tr.seed, tr.stream, pidx) % (uint32_t)(2 * a.max_shift + 1)) - a.max_shift);
-        if (a.scale_on && tid == AUG_NT - 63) {
+        if (am.drop_on && tid < C) draw[2 + tid] = nsd_rand_u32(tr.seed, tr.stream, pidx | (uint64_t)(256 + tid)) < am.thr_channel ? 1u : 0u;
+        if (am.max_shift && tid == AUG_NT - 64)
+            draw[0] = (uint32_t)((int)(nsd_rand_u32(tr.seed, tr.stream, pidx) % (uint32_t)(2 * am.max_shift + 1)) - am.max_shift);
+        if (am.scale_on && tid == AUG_NT - 63) {
             const float u = (float)(nsd_rand_u32(tr.seed, tr.stream, pidx | 1ull) >> 8) * (1.0f / 16777216.0f);
             const float w = __fadd_rn(__fmul_rn(2.0f, u), -1.0f);                 // exact
-            draw[1] = __float_as_uint(__fadd_rn(1.0f, __fmul_rn(a.scale_range, w)));
+            draw[1] = __float_as_uint(__fadd_rn(1.0f, __fmul_rn(am.scale_range, w)));
         }
         __syncthreads();
-        tr.shift = a.max_shift ? (int)draw[0] : 0;
-        tr.scale = a.scale_on ? __uint_as_float(draw[1]) : 1.0f;
-        tr.dropped = a.drop_on ? draw[2 + ch] != 0u : false;
+        tr.shift = am.max_shift ? (int)draw[0] : 0;
+        tr.scale = am.scale_on ? __uint_as_float(draw[1]) : 1.0f;
+        tr.dropped = am.drop_on ? draw[2 + ch] != 0u : false;
         if constexpr (!ZS) {
-            if (tid < act) for (int t = t0, e = tid; t < T; t += rows, e += act) yb[e] = aug_value(a, tr, t, ch, e);
+            if (tid < act) for (int t = t0, e = tid; t < T; t += rows, e += act) yb[e] = aug_value(a, am, tr, t, ch, e);
         } else {
             // the three passes of zscore_kernel on the augmented window v (same partial sums, same order)
             float s = 0.f;
             if (tid < act) for (int t = t0, e = tid; t < T; t += rows, e += act) {
-                const float v = aug_value(a, tr, t, ch, e);
+                const float v = aug_value(a, am, tr, t, ch, e);
                 if constexpr (STAGE) win[e] = v;
                 s += v;
             }
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(AUG_NT) void augment_kernel(const AugArgs a) {
             const float mu = stat[ch];
             float var = 0.f;
             if (tid < act) for (int t = t0, e = tid; t < T; t += rows, e += act) {
-                const float d = (STAGE ? win[e] : aug_value(a, tr, t, ch, e)) - mu;
+                const float d = (STAGE ? win[e] : aug_value(a, am, tr, t, ch, e)) - mu;
                 var = fmaf(d, d, var);
             }
             __syncthreads();
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(AUG_NT) void augment_kernel(const AugArgs a) {
             __syncthreads();
             const float rs = stat[C + ch];
             if (tid < act) for (int t = t0, e = tid; t < T; t += rows, e += act)
-                yb[e] = ((STAGE ? win[e] : aug_value(a, tr, t, ch, e)) - mu) * rs;
+                yb[e] = ((STAGE ? win[e] : aug_value(a, am, tr, t, ch, e)) - mu) * rs;
         }
         __syncthreads();                                   // (draws, partials and the staged window are reused by the next trial)
     }

@@ -950,7 +950,7 @@ __global__ __launch_bounds__(NT) void lstm2_fwd48_multi_kernel(Lstm2FwdArgs a_in
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n_steps = ((a_in.T + 2 + XCH - 1) / XCH) * XCH;
     const int g = wave & 3, q = wave >> 2;
-    NSD_FWD48_ROLE_TABLE(a_in, const ModelView<Lstm2FwdArgs> a = model_view(a_in, s))
+    NSD_FWD48_ROLE_TABLE(a_in, const ModelView<Lstm2FwdArgs> a = model_view<NB == 2>(a_in, s))
 }
 
 #endif

@@ -23,13 +23,14 @@ __global__ __launch_bounds__(MIX_NT) void mixup_kernel(const MixArgs a) {
     const int tid = threadIdx.x;
     const int B = a.B, K = a.K;
     const long n_el = a.n_el;
-    const bool mixing = a.mix != 0.f && B >= 2;
     const uint32_t base_dev = a.step_dev ? (uint32_t)(a.step_dev[0] & 0x3FFFFFFF) * 4u : 0u;
-    const float eps_k = __fdiv_rn(a.eps, (float)K);
-    const float on = __fadd_rn(__fsub_rn(1.0f, a.eps), eps_k);
     const long total = (long)a.M * B;
     for (long g = blockIdx.x; g < total; g += gridDim.x) {
         const int m = (int)(g / B), b = (int)(g - (long)m * B);
+        const float mix = a.mix[m], eps = a.eps[m];                // the model's nsd_mix: workgroup-uniform
+        const bool mixing = mix != 0.f && B >= 2;
+        const float eps_k = __fdiv_rn(eps, (float)K);
+        const float on = __fadd_rn(__fsub_rn(1.0f, eps), eps_k);
         int p = b;
         float lam = 1.0f, mu = 0.f;
         if (mixing) {
@@ -38,13 +39,13 @@ __global__ __launch_bounds__(MIX_NT) void mixup_kernel(const MixArgs a) {
             const uint32_t r = 1u + nsd_rand_u32(seed, stream, MIX_ROT_INDEX) % (uint32_t)(B - 1);
             p = (int)(((uint32_t)b + r) % (uint32_t)B);
             const float u = (float)(nsd_rand_u32(seed, stream, MIX_TRIAL_BIT | ((uint64_t)b << 16) | MIX_LAMBDA_SLOT) >> 8) * (1.0f / 16777216.0f);
-            lam = __fsub_rn(1.0f, __fmul_rn(a.mix, u));
+            lam = __fsub_rn(1.0f, __fmul_rn(mix, u));
             mu = __fsub_rn(1.0f, lam);
         }
         if (tid < K) {
             const int lb = a.labels[g], lp = a.labels[(long)m * B + p];
             float tb = tid == lb ? on : eps_k, tp = tid == lp ? on : eps_k;
-            if (a.w) { const float w = a.w[tid]; tb = __fmul_rn(w, tb); tp = __fmul_rn(w, tp); }
+            if (a.w) { const float w = a.w[(long)m * a.w_stride + tid]; tb = __fmul_rn(w, tb); tp = __fmul_rn(w, tp); }
             a.targets[g * K + tid] = mixing ? __fadd_rn(__fmul_rn(lam, tb), __fmul_rn(mu, tp)) : tb;
         }
         if (!a.y) continue;                                        // (workgroup-uniform: a targets-only launch)

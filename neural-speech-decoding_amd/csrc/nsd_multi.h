@@ -15,9 +15,14 @@ struct ModelSplit {
     int rng_on;
     long long x_stride;                      // floats between two models' windows
     long long P;                             // floats per model (nsd_param_count)
-    uint64_t seed[NSD_MAX_MODELS];           // model m's random streams: seed[m], base[m] (p_lstm / p_head are shared: Args::rng)
+    uint64_t seed[NSD_MAX_MODELS];           // model m's random streams: seed[m], base[m]
     uint32_t base[NSD_MAX_MODELS];
+    // model m's dropout thresholds and keep factors (nsd_drop_threshold(p), 1 / (1 - p) of rng[m], as nsd_rng_args forms them; equal for
+    // all models without NSD_FLAG_MODEL_P).  Workgroup-uniform: a workgroup never changes model, so the view's values are scalar loads
+    // from the kernel arguments -- one 16-byte record per model, so that one address and one load serve the four.
+    struct Drop { uint32_t thr_lstm; float keep_lstm; uint32_t thr_head; float keep_head; } drop[NSD_MAX_MODELS];
 };
+static_assert(sizeof(ModelSplit) <= 1088, "ModelSplit + the largest argument block stay well inside the 4 KB kernarg segment");
 
 template <class A>
 struct ModelView : A {
@@ -35,6 +40,7 @@ template <class T> __device__ __forceinline__ T *mv(T *p, const size_t off) { re
 __device__ __forceinline__ int model_of_block(const ModelSplit &s) { return __builtin_amdgcn_readfirstlane((int)blockIdx.x / s.G); }
 }  // namespace nsd_multi_detail
 
+template <bool PIN = false>
 __device__ __forceinline__ ModelView<Lstm2FwdArgs> model_view(const Lstm2FwdArgs &a, const ModelSplit &s) {
     using nsd_multi_detail::mv;
     const int m = nsd_multi_detail::model_of_block(s);
@@ -57,7 +63,17 @@ __device__ __forceinline__ ModelView<Lstm2FwdArgs> model_view(const Lstm2FwdArgs
     v.logits = mv(a.logits, b * a.K); v.loss = mv(a.loss, b); v.alpha = mv(a.alpha, bt); v.pooled = mv(a.pooled, b * 48);
     v.fc0_pre = mv(a.fc0_pre, b * a.F); v.dscore = mv(a.dscore, bt); v.dpooled = mv(a.dpooled, b * 48);
     v.adpack = mv(a.adpack, 4 * bt); v.hslabs = mv(a.hslabs, b * a.Ph);
-    if (s.rng_on) { v.rng.seed = s.seed[m]; v.rng.base = s.base[m]; }
+    if (s.rng_on) {
+        // PIN (set by the two-trial instantiations of nsd_lstm2_fwd48.hip's kernel): the record's index passes through an empty volatile
+        // asm, so its loads stay in the role that reads them and are not hoisted to the kernel's entry.  Each instantiation takes the
+        // form with which its VGPR count, spills and private segment are those it had before the record existed
+        // (profiles/hyper_grid.md): the values are scalar either way, what differs is where the SGPR spills fall.
+        int md = m;
+        if constexpr (PIN) asm volatile("" : "+s"(md));
+        const ModelSplit::Drop &r = s.drop[md];
+        v.rng.seed = s.seed[m]; v.rng.base = s.base[m];
+        v.rng.thr_lstm = r.thr_lstm; v.rng.thr_head = r.thr_head; v.rng.keep_lstm = r.keep_lstm; v.rng.keep_head = r.keep_head;
+    }
     return v;
 }
 
@@ -77,7 +93,11 @@ __device__ __forceinline__ ModelView<Lstm2BwdArgs> model_view(const Lstm2BwdArgs
     v.dsc_pack = a.dsc_pack + 4 * bt; v.pooled = a.pooled + b * 48; v.dscore_out = a.dscore_out + bt;
     v.hslabs = a.hslabs + b * a.Ph;
     v.slabs = a.slabs + (size_t)m * s.G * a.slab_stride;
-    if (s.rng_on) { v.rng.seed = s.seed[m]; v.rng.base = s.base[m]; }
+    if (s.rng_on) {
+        const ModelSplit::Drop &r = s.drop[m];
+        v.rng.seed = s.seed[m]; v.rng.base = s.base[m];
+        v.rng.thr_lstm = r.thr_lstm; v.rng.thr_head = r.thr_head; v.rng.keep_lstm = r.keep_lstm; v.rng.keep_head = r.keep_head;
+    }
     return v;
 }
 

@@ -71,10 +71,15 @@ int nsd_opt_state_init_launch(void *state, int64_t bytes, hipStream_t st) {
 
 // ---- launch 1, fused tail: grad_reduce_kernel's column sums (same tiling, same association order: grads is nsd_grad_reduce's bit for
 // bit) and the workgroup's double sum of (fp32(grads[e] * gscale))^2, lanes in order; lanes past P add exactly 0 ----------------------
+// gscale: one float, or for M models one per model by value in the launch arguments (nsd_opt::grad_scale of each model's entry; the
+// uniform entry point fills M equal ones): blockIdx.y is workgroup-uniform, so model mo's is a scalar load from the kernel arguments
+template <bool MODELS> struct GScale { float g; __device__ __forceinline__ float of(long) const { return g; } };
+template <> struct GScale<true> { float g[NSD_MAX_MODELS]; __device__ __forceinline__ float of(long mo) const { return g[mo]; } };
 template <bool MODELS>
 __global__ __launch_bounds__(ON_COLS * ON_GROUPS) void reduce_norm_kernel(
         const float *slabs, long slab_stride, int n_slabs, long p_lstm, const float *hslabs, long ph, int n_hslabs,
-        float *grads, float gscale, double *parts) {
+        float *grads, GScale<MODELS> gs, double *parts) {
+    const float gscale = gs.of(MODELS ? (long)blockIdx.y : 0);
     if constexpr (MODELS) {
         const long mo = blockIdx.y;
         slabs += mo * n_slabs * slab_stride; hslabs += mo * n_hslabs * ph; grads += mo * (p_lstm + ph);
@@ -162,10 +167,18 @@ struct OptK {
     float lr_eff, lr_over_bc1, rsqrt_bc2;       // host step only
     const long long *step_dev;
 };
-__global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, const float *g, float *m, float *v, OptK o,
+// M models: an OptK per model by value in the launch arguments, indexed by blockIdx.y (workgroup-uniform: scalar loads).  The uniform
+// model-batched entry point fills M equal entries, so a model's workgroups run the same instructions on either route.
+struct OptKSet { OptK k[NSD_MAX_MODELS]; };
+static_assert(sizeof(OptKSet) <= 2560, "the per-model optimizer block stays well inside the 4 KB kernarg segment");
+__device__ __forceinline__ const OptK &opt_of(const OptK &k, long) { return k; }
+__device__ __forceinline__ const OptK &opt_of(const OptKSet &k, long mo) { return k.k[mo]; }
+template <class OK>
+__global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, const float *g, float *m, float *v, OK ok,
                                                             const double *parts, int n_parts, nsd_opt_record *rec, const float *skip) {
     if (skip != nullptr && skip[0] != 0.f) return;                    // the caller's guard: nothing is written, the record included
     const long mo = blockIdx.y;
+    const OptK &o = opt_of(ok, mo);
     p += mo * n; g += mo * n; m += mo * n; v += mo * n; parts += mo * n_parts; rec += mo;
     __shared__ double red[FLAT_NT];
     double s = 0.0;
@@ -215,24 +228,41 @@ static OptK opt_kernel_args(const nsd_opt *o, int step, const long long *step_de
     return k;
 }
 
-static int adam_clip_launch(long n, int M, float *p, const float *g, float *m, float *v, const OptK &k, long n_parts, void *state,
+template <class OK>
+static int adam_clip_launch(long n, int M, float *p, const float *g, float *m, float *v, const OK &k, long n_parts, void *state,
                             const float *skip, const char *who, hipStream_t st) {
     long blocks = (n + FLAT_NT - 1) / FLAT_NT; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks, (unsigned)M), dim3(FLAT_NT), 0, st, n, p, g, m, v, k,
+    hipLaunchKernelGGL(adam_clip_kernel<OK>, dim3((unsigned)blocks, (unsigned)M), dim3(FLAT_NT), 0, st, n, p, g, m, v, k,
                        (const double *)parts_of(state, M), (int)n_parts, (nsd_opt_record *)state, skip);
     NSD_CHECK_LAUNCH(who);
     return NSD_OK;
 }
 
-// the fused tail of M models (M = 1: the single-model entry point): reduction with norm, then the update
-int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int step,
+// the fused tail of M models (M = 1: the single-model entry point): reduction with norm, then the update.  o: one nsd_opt for all
+// models, or with each != 0 (M > 1) one per model
+int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int each, int step,
                                 const long long *step_dev, void *state, const char *who, hipStream_t st) {
     const long P = s.p_lstm + s.ph, cols = col_parts(P);
-    const dim3 grid = M > 1 ? dim3((unsigned)cols, (unsigned)M) : dim3((unsigned)cols), wg(ON_COLS * ON_GROUPS);
-    const auto kernel = M > 1 ? reduce_norm_kernel<true> : reduce_norm_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h, grads, o->grad_scale, parts_of(state, M));
+    const dim3 wg(ON_COLS * ON_GROUPS);
+    if (M == 1) {
+        hipLaunchKernelGGL(reduce_norm_kernel<false>, dim3((unsigned)cols), wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h, grads,
+                           GScale<false>{o->grad_scale}, parts_of(state, M));
+        NSD_CHECK_LAUNCH(who);
+        return adam_clip_launch(P, M, p, grads, m, v, opt_kernel_args(o, step, step_dev), cols, state, nullptr, who, st);
+    }
+    GScale<true> gs;
+    OptKSet ks;
+    memset(&gs, 0, sizeof(gs));
+    memset(&ks, 0, sizeof(ks));
+    for (int mo = 0; mo < M; ++mo) {
+        const nsd_opt *om = each ? o + mo : o;
+        gs.g[mo] = om->grad_scale;
+        ks.k[mo] = opt_kernel_args(om, step, step_dev);
+    }
+    hipLaunchKernelGGL(reduce_norm_kernel<true>, dim3((unsigned)cols, (unsigned)M), wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h,
+                       grads, gs, parts_of(state, M));
     NSD_CHECK_LAUNCH(who);
-    return adam_clip_launch(P, M, p, grads, m, v, opt_kernel_args(o, step, step_dev), cols, state, nullptr, who, st);
+    return adam_clip_launch(P, M, p, grads, m, v, ks, cols, state, nullptr, who, st);
 }
 
 int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st) {

@@ -44,12 +44,21 @@ class ModelBatchTrainer:
     x [M,B,T,C] (per-model windows) or a shared [B,T,C], and y [M,B] or a shared [B].  augment: ops.Augment, applied per model as
     Trainer does.  loss: ops.Loss (label smoothing, class weights, mixup), applied per model as Trainer(model_m, seed=seeds[m], loss=loss)
     does: nsd_augment (if any) -> nsd_mixup -> the step with targets, each one launch for all models; the scale stays 1 / B per model.
-    clip_grad_norm / lr_schedule: as Trainer's, the norm taken per model."""
+    clip_grad_norm / lr_schedule: as Trainer's, the norm taken per model.
 
-    def __init__(self, models: Sequence[EEG_LSTM], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
-                 augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None,
-                 clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None):
+    A hyper-parameter grid in one launch: lr, betas, eps, weight_decay, clip_grad_norm, lr_schedule, augment and loss each take a scalar
+    or object (one setting for all models, as above) or a sequence of length M, one per model (betas: M pairs); a wrong length raises
+    NsdError.  Model m then takes the step a ModelBatchTrainer of the same models and seeds with setting m for everybody would give it,
+    bit for bit (nsd_augment_each, nsd_mixup_each, nsd_multi_grad_reduce_clip_adam_each).  Sequences of equal entries, like scalars,
+    issue exactly the calls of the single setting.  One model's loss=None beside another model's loss trains on one-hot target rows
+    through the soft-target entry point: the hard-label gradient up to the summation order over the classes (the same bits for K <= 3).
+
+    Dropout comes from each model's own dropout_p / head_dropout_p (NSD_FLAG_MODEL_P is passed only where they differ).  This corrects
+    earlier behaviour: models with different probabilities were all, silently, trained with model 0's."""
+
+    def __init__(self, models: Sequence[EEG_LSTM], lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
+                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -75,23 +84,40 @@ class ModelBatchTrainer:
         if len(seeds) != M:
             raise NsdError(f"ModelBatchTrainer: {len(seeds)} seeds for {M} models")
         self.seeds = [trainer_seed(s) for s in seeds]      # the streams of model m are those of Trainer(model_m, seed=seeds[m])
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        # optimizer settings: one for all models (scalars: today's calls) or one per model (self._each: lists of M)
+        per = {"lr": self._per_model(lr, "lr"), "eps": self._per_model(eps, "eps"), "weight_decay": self._per_model(weight_decay, "weight_decay"),
+               "betas": self._per_model(betas, "betas", pair=True), "clip_grad_norm": self._per_model(clip_grad_norm, "clip_grad_norm"),
+               "lr_schedule": self._per_model(lr_schedule, "lr_schedule")}
+        for c in per["clip_grad_norm"]:
+            if c is not None and not c >= 0.0:
+                raise ValueError(f"ModelBatchTrainer: clip_grad_norm {c!r} negative or NaN")
+        self._each = per if any(any(e != v[0] for e in v[1:]) for v in per.values()) else None
+        lr, eps, weight_decay, betas, clip_grad_norm, lr_schedule = (per[k][0] for k in ("lr", "eps", "weight_decay", "betas", "clip_grad_norm",
+                                                                                           "lr_schedule"))
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay          # (model 0's where they are per model)
         self.stochastic = stochastic
-        # Trainer's recipe (step_recipe.py), applied per model with its own seed, each launch for all models
-        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev)
+        # Trainer's recipe (step_recipe.py), applied per model with its own seed and dropout, each launch for all models
+        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev, models=self.models)
         self.augment, self.loss = self.recipe.augment, self.recipe.loss
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
         self.grads = torch.zeros_like(self.params)
         # clipping and schedule as in Trainer: one global norm, one record and one skip decision PER MODEL (nsd_multi_grad_reduce_clip_adam)
-        if clip_grad_norm is not None and not clip_grad_norm >= 0.0:
-            raise ValueError(f"ModelBatchTrainer: clip_grad_norm {clip_grad_norm!r} negative or NaN")
         self.clip_grad_norm, self.lr_schedule = clip_grad_norm, lr_schedule
-        self._opt_on = clip_grad_norm is not None or lr_schedule is not None
+        self._opt_on = self._each is not None or clip_grad_norm is not None or lr_schedule is not None
         self._opt_state = ops.opt_state(P, M, dev) if self._opt_on else None
         self.step_count = 0
         self._bufs = {}
         self._last = None
+
+    def _per_model(self, v, name: str, pair: bool = False) -> list:
+        """A setting given once or per model -> its M entries (pair: the single setting is itself a pair, per model is M pairs)."""
+        seq = isinstance(v, (list, tuple)) and (not pair or (len(v) > 0 and isinstance(v[0], (list, tuple))))
+        if not seq:
+            return [v] * self.M
+        if len(v) != self.M:
+            raise NsdError(f"ModelBatchTrainer: {name} has {len(v)} entries for {self.M} models")
+        return [tuple(e) for e in v] if pair else list(v)
 
     def _buffers(self, B: int, T: int):
         key = (B, T)
@@ -119,7 +145,7 @@ class ModelBatchTrainer:
             raise NsdError(f"ModelBatchTrainer.step: y must be [M,B] or [B], got {tuple(y.shape)}")
         self.step_count += 1
         x, y, tg = self.recipe.prepare(x, y.contiguous().view(-1), self.seeds, self.step_count, M=M)
-        rngs = [self.recipe.rng(s, self.step_count) for s in self.seeds] if self.stochastic else None
+        rngs = self.recipe.rngs(self.seeds, self.step_count)
         buf = self._buffers(B, T)
         ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
                              step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
@@ -127,8 +153,13 @@ class ModelBatchTrainer:
         self._last = (B, T)
 
     def _opt(self):
-        return ops.opt_struct(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
-                              max_norm=self.clip_grad_norm, schedule=self.lr_schedule)
+        """nsd_opt of the step: one, or with per-model settings a list of M"""
+        if self._each is None:
+            return ops.opt_struct(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
+                                  max_norm=self.clip_grad_norm, schedule=self.lr_schedule)
+        e = self._each
+        return [ops.opt_struct(lr=e["lr"][i], beta1=e["betas"][i][0], beta2=e["betas"][i][1], eps=e["eps"][i], weight_decay=e["weight_decay"][i],
+                               max_norm=e["clip_grad_norm"][i], schedule=e["lr_schedule"][i]) for i in range(self.M)]
 
     def last_grad_norms(self) -> List[float]:
         """Each model's global gradient norm of the last step, before clipping (synchronises; NaN with both options off or before a step)."""
@@ -137,11 +168,19 @@ class ModelBatchTrainer:
         return [r["norm"] for r in ops.opt_records(self._opt_state, self.M)]
 
     def last_lr(self) -> float:
-        """Learning rate of the last update (one schedule for all models; synchronises)."""
+        """Learning rate of the last update (one lr and schedule for all models; synchronises).  Where the models have their own:
+        last_lrs()."""
+        if self._each is not None and any(e != v[0] for k in ("lr", "lr_schedule") for v in (self._each[k],) for e in v[1:]):
+            raise NsdError("ModelBatchTrainer.last_lr: the models have their own lr / lr_schedule: use last_lrs()")
+        return self.last_lrs()[0]
+
+    def last_lrs(self) -> List[float]:
+        """Each model's learning rate of the last update (synchronises)."""
         if self._opt_on and self._last is not None:
-            return ops.opt_records(self._opt_state, self.M)[0]["lr"]
-        opt = self._opt()
-        return float(torch.tensor(float(opt.lr) * ops.lr_factor(opt, max(self.step_count, 1)), dtype=torch.float32))
+            return [r["lr"] for r in ops.opt_records(self._opt_state, self.M)]
+        opts = self._opt()
+        opts = opts if isinstance(opts, list) else [opts] * self.M
+        return [float(torch.tensor(float(o.lr) * ops.lr_factor(o, max(self.step_count, 1)), dtype=torch.float32)) for o in opts]
 
     def skipped_steps(self) -> List[int]:
         """Per model: updates skipped on the device because its gradient norm was not finite (sticky; synchronises)."""

@@ -126,6 +126,17 @@ def _rng_array(rngs, M: int, what: str, probs: bool = True):
     return None if rngs is None else (_lib.Rng * M)(*[_rng_struct(g, probs) for g in rngs])
 
 
+def _per_model(v, M: int, what: str, key=lambda e: e):
+    """A step setting given once or per model: a list / tuple of M entries -> (entry 0, None) where all are equal (the caller then takes
+    its existing route, launch for launch) or (None, the list); anything else -> (v, None).  A wrong length raises."""
+    if not isinstance(v, (list, tuple)):
+        return v, None
+    if len(v) != M:
+        raise NsdError(f"{what}: {len(v)} entries for {M} models")
+    v = list(v)
+    return (v[0], None) if all(key(e) == key(v[0]) for e in v[1:]) else (None, v)
+
+
 def _step_ptr(step_dev: Optional[torch.Tensor], what: str) -> Optional[int]:
     """The device step counter of the hipGraph-replayable entry points (stream ids / Adam's step are read from it on the device)."""
     if step_dev is not None and (step_dev.dtype != torch.int64 or not step_dev.is_cuda):
@@ -324,23 +335,27 @@ class Augment:
         return bool(self.max_shift or self.scale_range or self.p_channel or self.noise_std)
 
 
-def augment(x: torch.Tensor, aug: Augment, rngs, *, M: int = 1, zscore: bool = False, step_dev: Optional[torch.Tensor] = None,
+def augment(x: torch.Tensor, aug, rngs, *, M: int = 1, zscore: bool = False, step_dev: Optional[torch.Tensor] = None,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nsd_augment: the augmented (and, with zscore, z-scored) windows, one launch for all models.
     x [B,T,C]: the windows of one model (M = 1 -> [B,T,C]) or shared by M models, each with its own draws (-> [M,B,T,C]);
     x [M,B,T,C]: per-model windows -> [M,B,T,C].  rngs: dict(seed=, base_stream=) or M of them (model m draws what a single-model call
     with rngs[m] draws; the stream used is base_stream + 3).  step_dev: device int64 step counter; base_stream is then
-    4 * (step_dev[0] & 0x3fffffff) for every model (hipGraph replay).  All operations off: a bitwise copy of x."""
+    4 * (step_dev[0] & 0x3fffffff) for every model (hipGraph replay).  All operations off: a bitwise copy of x.
+    aug: one Augment, or a list of M (nsd_augment_each: model m is augmented with aug[m], an operation skipped where its parameter is 0;
+    the z-score stays per launch).  A list of equal entries is the single Augment's launch."""
     M, B, T, Cc, stride, shape = _model_windows(x, M, "augment")
     r = _rng_array(rngs, M, "augment", probs=False)
-    a = _lib.Aug(int(aug.max_shift), float(aug.scale_range), float(aug.p_channel), float(aug.noise_std))
+    aug, augs = _per_model(aug, M, "augment")
+    as_struct = lambda g: _lib.Aug(int(g.max_shift), float(g.scale_range), float(g.p_channel), float(g.noise_std))
+    a = as_struct(aug) if augs is None else (_lib.Aug * M)(*[as_struct(g) for g in augs])
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
     if out.numel() != M * B * T * Cc:
         raise NsdError(f"augment: out has {out.numel()} elements for {M} x {B} x {T} x {Cc}")
     d = Dims(B, T, Cc, 1, 1, 1, 1)
-    _call("nsd_augment", x.device, C.byref(d), M, _dev_f32(x, "x"), stride, C.byref(a), C.cast(r, C.c_void_p), _step_ptr(step_dev, "augment"),
-          _lib.NSD_AUG_ZSCORE if zscore else 0, _dev_f32(out, "out"), STREAM)
+    _call("nsd_augment" if augs is None else "nsd_augment_each", x.device, C.byref(d), M, _dev_f32(x, "x"), stride, C.cast(C.pointer(a), C.c_void_p),
+          C.cast(r, C.c_void_p), _step_ptr(step_dev, "augment"), _lib.NSD_AUG_ZSCORE if zscore else 0, _dev_f32(out, "out"), STREAM)
     return out
 
 
@@ -382,7 +397,7 @@ class Loss:
         return None if self.class_weights is None else torch.tensor(self.class_weights, dtype=torch.float32, device=device)
 
 
-def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, label_smoothing: float = 0.0, mix: float = 0.0,
+def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, label_smoothing=0.0, mix=0.0,
           class_weights: Optional[torch.Tensor] = None, M: int = 1, step_dev: Optional[torch.Tensor] = None,
           out: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None
           ) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
@@ -390,7 +405,10 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     one launch for all models -> (y, targets [M*B, K]).  x [B,T,C] (one model, or shared by M models -> y [M,B,T,C]) or [M,B,T,C];
     x = None (mix = 0 only): the launch builds targets alone and y is None.  labels [M*B] int32 (model m's trial b at m * B + b).
     rngs / step_dev as ops.augment (the stream is base_stream + 3, on index slots nsd_augment does not use).  class_weights: device
-    fp32 [K].  mix = 0 with x given: y is a bitwise copy of x."""
+    fp32 [K].  mix = 0 with x given: y is a bitwise copy of x.
+    label_smoothing / mix: a float each, or a list of M each (nsd_mixup_each; a float beside a list is repeated), class_weights then
+    [K], [M, K] or None; model m's rows and windows are those of the single-setting call with entry m.  Lists of equal entries with
+    class_weights None or [K] are the single-setting launch.  With any mix[m] > 0, x is required."""
     if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous():
         raise NsdError("mixup: labels must be a contiguous int32 tensor on the device")
     dev = labels.device
@@ -404,7 +422,17 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     r = _rng_array(rngs, M, "mixup", probs=False)
     if labels.numel() != M * B:
         raise NsdError(f"mixup: {labels.numel()} labels for {M} x {B} trials")
-    mx = _lib.Mix(float(mix), float(label_smoothing))
+    mix, mixes = _per_model(mix, M, "mixup: mix")
+    label_smoothing, smooths = _per_model(label_smoothing, M, "mixup: label_smoothing")
+    each = mixes is not None or smooths is not None or (class_weights is not None and class_weights.dim() == 2)
+    if each:
+        mixes = mixes if mixes is not None else [mix] * M
+        smooths = smooths if smooths is not None else [label_smoothing] * M
+        if class_weights is not None and class_weights.dim() == 1:
+            class_weights = class_weights.unsqueeze(0).expand(M, K).contiguous()
+        mx = (_lib.Mix * M)(*[_lib.Mix(float(a), float(e)) for a, e in zip(mixes, smooths)])
+    else:
+        mx = _lib.Mix(float(mix), float(label_smoothing))
     if targets is None:
         targets = torch.empty((M * B, K), dtype=torch.float32, device=dev)
     if targets.numel() != M * B * K:
@@ -417,8 +445,8 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     else:
         out = None
     d = Dims(B, T, Cc, 1, 1, int(K), 1)
-    _call("nsd_mixup", dev, C.byref(d), M, _dev_f32(x, "x"), stride, labels.data_ptr(), _dev_f32(class_weights, "class_weights", (K,)),
-          C.byref(mx), C.cast(r, C.c_void_p), _step_ptr(step_dev, "mixup"), _dev_f32(out, "out"), _dev_f32(targets, "targets"), STREAM)
+    _call("nsd_mixup_each" if each else "nsd_mixup", dev, C.byref(d), M, _dev_f32(x, "x"), stride, labels.data_ptr(),
+          _dev_f32(class_weights, "class_weights", (M, K) if each else (K,)), C.cast(C.pointer(mx), C.c_void_p), C.cast(r, C.c_void_p), _step_ptr(step_dev, "mixup"), _dev_f32(out, "out"), _dev_f32(targets, "targets"), STREAM)
     return out, targets
 
 
@@ -1043,7 +1071,9 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
     rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K].
     targets [M*B, K] fp32 (labels is then ignored and may be None): the soft-target loss per model (nsd_multi_train_fwd_soft).
     opt (ops.opt_struct) with opt_state (ops.opt_state(P, M)): the tail is nsd_multi_grad_reduce_clip_adam -- one norm, record and skip
-    decision per model; the Adam arguments of this call are then ignored."""
+    decision per model; the Adam arguments of this call are then ignored.  opt may be a list of M (nsd_multi_grad_reduce_clip_adam_each:
+    every field per model); a list of equal entries is the single opt's launch.  rngs whose p_lstm / p_head differ between models go
+    with NSD_FLAG_MODEL_P (each model drops with its own probabilities); equal ones go without the flag, as before."""
     M = int(params.shape[0])
     B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
@@ -1053,16 +1083,23 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
         raise NsdError(f"multi: labels must be contiguous int32 [M*B] = [{M * B}]")
     r = _rng_array(rngs, M, "multi")
     rp = C.cast(r, C.c_void_p) if r is not None else None
+    fl = _lib.NSD_FLAG_MODEL_P if r is not None and any((g.p_lstm, g.p_head) != (r[0].p_lstm, r[0].p_head) for g in r) else 0
+    opt, opts = _per_model(opt, M, "multi: opt", key=bytes)
     P = spec.param_count
     pp, xp = _dev_f32(params, "params", (M, P)), _dev_f32(x, "x")
     if targets is not None:
-        _call("nsd_multi_train_fwd_soft", params.device, C.byref(d), M, pp, xp, stride, rp, _dev_f32(targets, "targets", (M * B, spec.K)), 0,
+        _call("nsd_multi_train_fwd_soft", params.device, C.byref(d), M, pp, xp, stride, rp, _dev_f32(targets, "targets", (M * B, spec.K)), fl,
               ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits"), STREAM)
     else:
-        _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), 0, ws.data_ptr(), _nbytes(ws),
+        _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), fl, ws.data_ptr(), _nbytes(ws),
               _dev_f32(logits, "logits"), STREAM)
-    _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, 0, ws.data_ptr(), _nbytes(ws), STREAM)
-    if fuse_adam and opt is not None:
+    _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, fl, ws.data_ptr(), _nbytes(ws), STREAM)
+    if fuse_adam and opts is not None:
+        arr = (_lib.Opt * M)(*opts)
+        _call("nsd_multi_grad_reduce_clip_adam_each", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
+              _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), C.cast(arr, C.c_void_p), int(step), None, opt_state.data_ptr(), _nbytes(opt_state),
+              STREAM)
+    elif fuse_adam and opt is not None:
         _call("nsd_multi_grad_reduce_clip_adam", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
               _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), C.byref(opt), int(step), None, opt_state.data_ptr(), _nbytes(opt_state), STREAM)
     elif fuse_adam:

@@ -33,29 +33,71 @@ class StepRecipe:
     """What a trainer does to a batch before the step's kernels, and with which streams.  `model`: an EEG_LSTM (spec, dropout_p,
     head_dropout_p, normalize, prep).  augment / loss are the EFFECTIVE ones: augmentation and mixup belong to the stochastic parts, so
     stochastic=False strips them (smoothing and class weights, which draw nothing, stay); None -- also for an Augment / Loss with every
-    part off -- is the plain step, launch for launch."""
+    part off -- is the plain step, launch for launch.
 
-    def __init__(self, model, stochastic: bool, augment: Optional[ops.Augment], loss: Optional[ops.Loss], device):
+    models (ModelBatchTrainer): the M models of a model-batched step.  Each model then drops with its own dropout_p / head_dropout_p
+    (rngs()), and augment / loss may be sequences of M, one per model (a hyper-parameter grid in one launch).  Sequences whose
+    effective entries are all equal are the single setting, launch for launch.  Where they differ, self.augment / self.loss are lists
+    of M (an Augment() / Loss() with every part off for a model without one: its windows are copied bit for bit and its target rows
+    are one-hot), the launches are nsd_augment_each / nsd_mixup_each, and class weights go as [M, K] (a row of ones -- an exact
+    product -- for a model without weights)."""
+
+    def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None):
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
         self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
-        self.augment = augment if augment is not None and augment.enabled and stochastic else None
-        if loss is not None and loss.mixup and not stochastic:
+        self.probs = [(m.dropout_p, m.head_dropout_p) for m in models] if models is not None else None
+        M = len(models) if models is not None else 1
+        augs = [self._effective_augment(a) for a in self._entries(augment, M, "augment")]
+        losses = [self._effective_loss(lo) for lo in self._entries(loss, M, "loss")]
+        if all(a == augs[0] for a in augs):
+            self.augment = augs[0]
+        else:
+            self.augment = [a if a is not None else ops.Augment() for a in augs]
+        if all(lo == losses[0] for lo in losses):
+            self.loss = losses[0]
+            self.class_weights = None if self.loss is None else self.loss.weights_tensor(device)
+        else:
+            self.loss = [lo if lo is not None else ops.Loss() for lo in losses]
+            rows = [lo.class_weights for lo in self.loss]
+            self.class_weights = None if all(r is None for r in rows) else torch.tensor(
+                [r if r is not None else (1.0,) * self.spec.K for r in rows], dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _entries(v, M: int, name: str) -> list:
+        if not isinstance(v, (list, tuple)):
+            return [v] * M
+        if len(v) != M:
+            raise ops.NsdError(f"StepRecipe: {len(v)} {name} entries for {M} models")
+        return list(v)
+
+    def _effective_augment(self, augment: Optional[ops.Augment]) -> Optional[ops.Augment]:
+        return augment if augment is not None and augment.enabled and self.stochastic else None
+
+    def _effective_loss(self, loss: Optional[ops.Loss]) -> Optional[ops.Loss]:
+        if loss is not None and loss.mixup and not self.stochastic:
             loss = ops.Loss(label_smoothing=loss.label_smoothing, class_weights=loss.class_weights)
-        on = loss is not None and loss.enabled
-        if on:
-            loss.check_classes(self.spec.K)
-        self.loss, self.class_weights = (loss, loss.weights_tensor(device)) if on else (None, None)
+        if loss is None or not loss.enabled:
+            return None
+        loss.check_classes(self.spec.K)
+        return loss
 
     def rng(self, seed: int, step: int) -> Optional[dict]:
         """The in-kernel streams of the step (None for a deterministic trainer)."""
         return step_rng(seed, step, self.p_lstm, self.p_head) if self.stochastic else None
+
+    def rngs(self, seeds: Sequence[int], step: int) -> Optional[list]:
+        """The in-kernel streams of a model-batched step: model m's with its own dropout probabilities (None: deterministic)."""
+        if not self.stochastic:
+            return None
+        probs = self.probs if self.probs is not None else [(self.p_lstm, self.p_head)] * len(seeds)
+        return [step_rng(s, step, pl, ph) for s, (pl, ph) in zip(seeds, probs)]
 
     def static_buffers(self, x: torch.Tensor) -> dict:
         """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""
         buf = {}
         if self.normalize or self.augment is not None or self.prep is not None:
             buf["xn"] = torch.empty_like(x)
-        if self.loss is not None:
+        if self.loss is not None:                    # (a single-model trainer's: self.loss is one Loss)
             buf["tg"] = torch.empty((x.shape[0], self.spec.K), dtype=torch.float32, device=x.device)
             buf["xm"] = torch.empty_like(x) if self.loss.mixup > 0 else None
         return buf
@@ -85,6 +127,11 @@ class StepRecipe:
         if y.is_floating_point() or self.loss is None:
             return (x, None, y) if y.is_floating_point() else (x, y, None)
         lo = self.loss
-        xm, tg = ops.mixup(x if lo.mixup > 0 else None, y, self.spec.K, rngs, M=M, label_smoothing=lo.label_smoothing, mix=lo.mixup,
+        if isinstance(lo, list):                     # per model: the windows are mixed (or copied) as soon as one model mixes
+            smooth, mix = [e.label_smoothing for e in lo], [e.mixup for e in lo]
+            mixing = any(v > 0 for v in mix)
+        else:
+            smooth, mix, mixing = lo.label_smoothing, lo.mixup, lo.mixup > 0
+        xm, tg = ops.mixup(x if mixing else None, y, self.spec.K, rngs, M=M, label_smoothing=smooth, mix=mix,
                            class_weights=self.class_weights, step_dev=step_dev, out=bufs.get("xm"), targets=bufs.get("tg"))
-        return (xm if lo.mixup > 0 else x), None, tg
+        return (xm if mixing else x), None, tg

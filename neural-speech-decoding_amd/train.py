@@ -111,7 +111,8 @@ def schedule_for(args, total_steps: int):
                       min_ratio=args.lr_min_ratio, step_size=args.lr_step_size, gamma=args.lr_gamma)
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
+    """The options of this command (nsd_amd.grid shares them: its --grid keys name options of this parser)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", help="directory with <prefix>_*.csv trials (reference: EEG_data_collection/), or a packed .npz "
                                    "of them (data.load_trials_npz)")
@@ -169,6 +170,11 @@ def main(argv=None) -> int:
                                                                             "starting variance is calibrated on the training split (with --concurrent: on all trials)")
     ap.add_argument("--prep-car", action="store_true", help="causal front end: common-average reference")
     ap.add_argument("--prep-no-baseline", action="store_true", help="causal front end: do not subtract each window's first sample")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     args = ap.parse_args(argv)
     prep_stage = any(v is not None for v in (args.prep_highpass, args.prep_lowpass, args.prep_notch, args.prep_zscore_seconds)) or args.prep_car
     prep_design = None
