@@ -1262,7 +1262,8 @@ def test_every_sequence_length_up_to_40(nsd, dev, ref_state, nb):
 
 # ---------------------------------------------------------------------------------------------------
 # dL/dx on every call path of the H = 48 fast path
-@pytest.mark.parametrize("B,T,force", [(513, 9, 0), (1030, 9, 0), (5, 33, 0), (300, 20, 0), (7, 33, 4), (9, 250, 4)])
+@pytest.mark.parametrize("B,T,force", [(513, 9, 0), (1030, 9, 0), (5, 33, 0), (300, 20, 0), (7, 33, 4), (9, 250, 4),
+                                       (5, 256, 4), (5, 257, 4), (6, 513, 4)])     # att_close_kernel's 256-step chunks: one full, a second of one step, a third
 def test_input_gradient_after_the_fused_head_vs_oracle(nsd, dev, ref_state, B, T, force):
     """nsd_lstm_head_train, then nsd_lstm_bwd with dx (ops.train_step_grads(dx=)), against the oracle's forward + backward with the same
     masks: logits, loss, every gradient tensor, dx, the workspace's alpha and dscore.  From 513 trials (and under the diagnostic
