@@ -555,6 +555,77 @@ int nsd_multi_stream_step(const nsd_dims *d, int32_t M, const float *params, con
                           void *stream);
 
 /*
+ * ---- session calibration: refit the read-out on frozen pooled features in ONE launch (an EXTENSION, of nsd_stream_*) ----
+ *
+ * A model trained on earlier sessions meets a new one: a few cued trials are pushed through a stream, the pooled vector each slot holds is
+ * read out (nsd_stream_features), and the trainable tail of the model -- LayerNorm, fc.0, fc.3 of lstm_eeg_model.py:38-39; the LSTM stack
+ * and the attention stay frozen -- is refitted on those vectors by E full-batch Adam epochs in one launch (nsd_head_fit), one 256-thread
+ * workgroup per model, M models (the folds of an ensemble) per launch, no host in the loop.
+ *   nsd_stream_features   feats[i, j] = pool_acc[j] / pool_den of slot slots[i] (DEVICE int32[n], or NULL for 0 .. n-1), j < H: the one
+ *                         correctly rounded fp32 division whose result nsd_stream_step's read-out is formed from, so the row is exactly
+ *                         the vector whose read-out the slot's decision is.  A slot that was never stepped gives a NaN row (0 / 0), a slot
+ *                         index outside [0, S) a NaN row too; nothing outside feats[n,H] is written.  The state of an ensemble is read
+ *                         as a flat state of M*S slots, as nsd_stream_reset reads it.  Refusals before any launch, as nsd_stream_step:
+ *                         NSD_E_INVALID for NULL d / state / feats, a shape outside nsd_stream_path, S < 1, n < 0, n > S with slots ==
+ *                         NULL; NSD_E_WORKSPACE for state_bytes < nsd_stream_state_bytes(d, S).  n = 0 launches nothing.
+ * nsd_head_fit.  Per model m: theta = params + m*P (the whole flat vector; only its tail is touched), N = d->B trials, features
+ * feats + m*feats_model_stride [N,H], target rows targets[m*N + n][K].  One epoch is one full-batch Adam step on
+ *   LayerNorm (biased variance, eps 1e-5 inside the square root) -> fc.0 -> RReLU -> dropout -> fc.3,
+ *   loss_n = - sum_k q log softmax,  dlogits = scale (s p - q): the soft-target convention above (nsd_head_train_soft), formed without
+ *   the O(1) - O(1) difference.
+ * The gradient of a parameter is the sum over the trials in ascending n, one fmaf chain per parameter: a fixed order that does not depend
+ * on M, on the model's place in the grid, or on the stream.  The update is nsd_adam_step's arithmetic (gi = fmaf(weight_decay, p, g):
+ * coupled L2), every fp32 operation rounded on its own; the bias corrections are formed in double on the device from the 1-based GLOBAL
+ * epoch number s (beta^s by repeated squaring, a function of s alone), lr / bc1 and 1 / sqrt(bc2) rounded to fp32 as there.
+ * Only the tensors named in fit->train change (NSD_FIT_LN: ln.weight, ln.bias; NSD_FIT_FC0: fc.0.*; NSD_FIT_FC3: fc.3.*); every other
+ * float of params -- always all LSTM tensors, attn.weight, attn.bias -- is bit for bit what it was.  The gradient flows through an
+ * untrained tensor unchanged.
+ * Noise.  rng == NULL: the eval slope and no dropout.  Otherwise global epoch e (0-based, from the state) of model m draws what a
+ * trainer's step e draws for a batch of N trials: RReLU slopes [N,F] and head-dropout multipliers [N,F] are the values nsd_train_masks
+ * writes for seed = rng[m].seed, base_stream = rng[m].base_stream + 4e (uint32 wrap), p_head = rng[m].p_head.  p_lstm is ignored.
+ * State (device, caller-owned, nsd_head_fit_state_bytes(d, M) bytes): per model `stride` floats -- m[Pt] at `m`, v[Pt] at `v`, the int64
+ * global epoch count at `epochs` (8-byte aligned), the int32 status word at `status` -- with Pt = 2H + FH + F + KF + K and the tail in
+ * the flat order without the attention: ln.weight ln.bias fc.0.weight fc.0.bias fc.3.weight fc.3.bias.  All-zero bytes is the reset
+ * state (hipMemsetAsync is enough; there is no reset entry point).  The state and the parameters after e1 + e2 epochs are the same bits
+ * whether the epochs ran in one call or in two, and so is row e of loss_out.  loss_out[m, e] = scale * sum_n loss_n before that epoch's
+ * update, the sum serial in n.
+ *   nsd_head_fit_path     1 where nsd_stream_path(d), 1 <= M <= NSD_MAX_MODELS, 1 <= N = d->B <= NSD_FIT_MAX_TRIALS and the workgroup's
+ *                         LDS need, 4 * (N * (2H + F + K + 3) + 2H + F(H+1) + F + K(F|1) + K + Pt + 520) bytes, is at most 160 KiB.  At the
+ *                         reference head (F = 32, K <= 8) that holds up to N = 256; at F = 64, K = 8 up to N = 192, at F = K = 64 up to
+ *                         N = 112.  The limit does not depend on M or on fit->train.
+ * Failure behaviour.  Every refusal happens before any launch.  NSD_E_INVALID: NULL d / params / feats / targets / fit / fit_state; a shape
+ * outside nsd_head_fit_path; epochs outside [1, NSD_FIT_MAX_EPOCHS]; an empty or unknown train mask; lr negative or not finite, a beta
+ * outside [0, 1), eps not positive or not finite, weight_decay negative or not finite, scale not finite (nsd_adam_step itself checks
+ * none of these); a negative feats_model_stride or one in (0, N*H); rng with a p_head outside [0, 1).  NSD_E_WORKSPACE: fit_state_bytes <
+ * nsd_head_fit_state_bytes(d, M).  Seen on the device only, and never silent: when a feature or a target of a model is not finite, or its
+ * status word is already set, the model's parameters, moments and epoch count keep their bits, its row of loss_out is NaN and its status
+ * word becomes (stays) 1 until the state is zeroed; when an epoch's loss is not finite, parameters, moments and the count keep the values
+ * they had before that epoch, that epoch's and the remaining entries of loss_out are NaN and the status word becomes 1.  The other models
+ * of the launch are unaffected.  No host synchronisation, no allocation: the call can be captured in a single-stream graph and replayed
+ * (the epoch count lives in the state).  Additive: NSD_VERSION stays 301, a caller detects the feature by the symbols.
+ */
+int nsd_stream_features(const nsd_dims *d, const void *state, int64_t state_bytes, int32_t S,
+                        const int32_t *slots /* DEVICE int32[n] or NULL = 0..n-1 */, int32_t n, float *feats /* [n,H] */, void *stream);
+#define NSD_FIT_MAX_TRIALS 256
+#define NSD_FIT_MAX_EPOCHS 65536
+#define NSD_FIT_LN  1u   /* ln.weight, ln.bias     */
+#define NSD_FIT_FC0 2u   /* fc.0.weight, fc.0.bias */
+#define NSD_FIT_FC3 4u   /* fc.3.weight, fc.3.bias */
+typedef struct nsd_fit {
+    int32_t epochs;                 /* epochs of THIS call, 1 .. NSD_FIT_MAX_EPOCHS */
+    uint32_t train;                 /* non-empty subset of NSD_FIT_* */
+    float lr, beta1, beta2, eps, weight_decay, scale;   /* scale: 1/N in the Python layer */
+} nsd_fit;
+typedef struct nsd_fit_layout { int64_t m, v, epochs, status, stride; } nsd_fit_layout;  /* float offsets per model */
+int     nsd_head_fit_path(const nsd_dims *d, int32_t M);      /* d->B = N trials */
+int64_t nsd_head_fit_state_bytes(const nsd_dims *d, int32_t M);
+int     nsd_head_fit_state_layout(const nsd_dims *d, nsd_fit_layout *out);
+int nsd_head_fit(const nsd_dims *d, int32_t M, float *params /* [M,P] in/out */,
+                 const float *feats, int64_t feats_model_stride /* 0: one set for all models, else >= N*H */,
+                 const float *targets /* [M*N][K] */, const nsd_fit *fit, const nsd_rng *rng /* NULL or [M] */,
+                 void *fit_state, int64_t fit_state_bytes, float *loss_out /* [M, fit->epochs] or NULL */, void *stream);
+
+/*
  * ---- sliding-window decisions for continuous streams in one launch per chunk (an EXTENSION, of nsd_stream_*) ----
  *
  * "Every `hop` samples, the decision of the model run from a zero state over the last `window` samples."  window = W >= 1, hop = Hp with

@@ -85,6 +85,21 @@ class WindowLayout(C.Structure):
 NSD_WINDOW_MAX_PHASES = 128
 
 
+class Fit(C.Structure):
+    """nsd_fit of include/nsd.h: the settings of one nsd_head_fit call"""
+    _fields_ = ([("epochs", C.c_int32), ("train", C.c_uint32)]
+                + [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "scale")])
+
+
+class FitLayout(C.Structure):
+    """nsd_fit_layout of include/nsd.h: float offsets inside one model's fit state"""
+    _fields_ = [(n, C.c_int64) for n in ("m", "v", "epochs", "status", "stride")]
+
+
+NSD_FIT_MAX_TRIALS, NSD_FIT_MAX_EPOCHS = 256, 65536
+NSD_FIT_LN, NSD_FIT_FC0, NSD_FIT_FC3 = 1, 2, 4
+
+
 class Prep(C.Structure):
     """nsd_prep of include/nsd.h"""
     _fields_ = [("flags", C.c_uint32), ("n_sections", C.c_int32), ("sos", (C.c_float * 5) * 4), ("alpha", C.c_float), ("var0", C.c_float)]
@@ -195,6 +210,12 @@ SYMBOLS = {
     "nsd_multi_stream_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_multi_stream_state_bytes": (C.c_int64, [_dp, C.c_int32, C.c_int32]),
     "nsd_multi_stream_step": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _ip, C.c_uint32, _vp, C.c_int64, C.c_int32, _fp, _fp, _fp, _vp]),
+    # session calibration: the pooled vector of stream slots, the read-out refitted on frozen features in one launch
+    "nsd_stream_features": (C.c_int, [_dp, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _fp, _vp]),
+    "nsd_head_fit_path": (C.c_int, [_dp, C.c_int32]),
+    "nsd_head_fit_state_bytes": (C.c_int64, [_dp, C.c_int32]),
+    "nsd_head_fit_state_layout": (C.c_int, [_dp, C.POINTER(FitLayout)]),
+    "nsd_head_fit": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _fp, C.POINTER(Fit), _vp, _vp, C.c_int64, _fp, _vp]),
     # sliding-window decisions for continuous streams
     "nsd_window_path": (C.c_int, [_dp, C.POINTER(Window)]),
     "nsd_window_rows": (C.c_int32, [C.c_int32, C.POINTER(Window)]),

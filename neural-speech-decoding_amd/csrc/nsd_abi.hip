@@ -1137,6 +1137,86 @@ int nsd_multi_stream_step(const nsd_dims *d, int32_t M, const float *params, con
     return nsd_multi_stream48_launch(a, model_split(d, x_model_stride), M, mean_probs, (hipStream_t)stream);
 }
 
+// ---- session calibration (nsd_head_fit.hip): the pooled vector of stream slots, and the read-out refitted on such vectors ----
+int nsd_stream_features(const nsd_dims *d, const void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, float *feats,
+                        void *stream) {
+    static const char *who = "stream_features";
+    if (const int rc = stream_enter(d, who, feats != nullptr, state, state_bytes, S)) return rc;
+    if (n < 0 || (!slots && n > S)) { nsd_set_error("%s: n = %d rows of S = %d slots", who, n, S); return NSD_E_INVALID; }
+    if (n == 0) return NSD_OK;
+    return nsd_stream_features_launch((const float *)state, S, slots, n, feats, (hipStream_t)stream);
+}
+
+// the model dims, the model count, the trial count d->B and the LDS one workgroup needs for them
+static bool fit_shape(const nsd_dims *d, int32_t M) {
+    return stream_shape(d) && M >= 1 && M <= NSD_MAX_MODELS && d->B >= 1 && d->B <= NSD_FIT_MAX_TRIALS &&
+           fit_lds_floats(d->B, d->F, d->K) * (long)sizeof(float) <= FIT_LDS_MAX;
+}
+int nsd_head_fit_path(const nsd_dims *d, int32_t M) { return fit_shape(d, M) ? 1 : 0; }
+
+int64_t nsd_head_fit_state_bytes(const nsd_dims *d, int32_t M) {
+    if (!stream_shape(d) || M < 1 || M > NSD_MAX_MODELS) {
+        nsd_set_error("head_fit_state_bytes: shape outside nsd_stream_path, or M = %d outside [1, %d]", M, NSD_MAX_MODELS);
+        return NSD_E_INVALID;
+    }
+    return (int64_t)M * fit_stride(d->F, d->K) * (int64_t)sizeof(float);
+}
+
+int nsd_head_fit_state_layout(const nsd_dims *d, nsd_fit_layout *out) {
+    if (!stream_shape(d) || !out) { nsd_set_error("head_fit_state_layout: shape outside nsd_stream_path, or null pointer"); return NSD_E_INVALID; }
+    out->m = 0; out->v = fit_tail(d->F, d->K); out->epochs = fit_epochs_off(d->F, d->K); out->status = fit_status_off(d->F, d->K);
+    out->stride = fit_stride(d->F, d->K);
+    return NSD_OK;
+}
+
+int nsd_head_fit(const nsd_dims *d, int32_t M, float *params, const float *feats, int64_t feats_model_stride, const float *targets,
+                 const nsd_fit *fit, const nsd_rng *rng, void *fit_state, int64_t fit_state_bytes, float *loss_out, void *stream) {
+    static const char *who = "head_fit";
+    if (!d || !params || !feats || !targets || !fit || !fit_state) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (!fit_shape(d, M)) {
+        nsd_set_error("%s: outside nsd_head_fit_path (nsd_stream_path, 1 <= M <= %d, 1 <= N <= %d, %ld bytes of LDS for N, F, K): "
+                      "M = %d, N = %d, H = %d, F = %d, K = %d", who, NSD_MAX_MODELS, NSD_FIT_MAX_TRIALS, FIT_LDS_MAX, M, d->B, d->H, d->F, d->K);
+        return NSD_E_INVALID;
+    }
+    if (fit->epochs < 1 || fit->epochs > NSD_FIT_MAX_EPOCHS) { nsd_set_error("%s: epochs %d outside [1, %d]", who, fit->epochs, NSD_FIT_MAX_EPOCHS); return NSD_E_INVALID; }
+    if (fit->train == 0 || (fit->train & ~(NSD_FIT_LN | NSD_FIT_FC0 | NSD_FIT_FC3))) {
+        nsd_set_error("%s: train mask 0x%x (a non-empty subset of NSD_FIT_LN | NSD_FIT_FC0 | NSD_FIT_FC3)", who, fit->train); return NSD_E_INVALID;
+    }
+    if (!(fit->lr >= 0.f && fit->lr < INFINITY) || !(fit->beta1 >= 0.f && fit->beta1 < 1.f) || !(fit->beta2 >= 0.f && fit->beta2 < 1.f) ||
+        !(fit->eps > 0.f && fit->eps < INFINITY) || !(fit->weight_decay >= 0.f && fit->weight_decay < INFINITY) || !(fit->scale == fit->scale) ||
+        fit->scale == INFINITY || fit->scale == -INFINITY) {
+        nsd_set_error("%s: lr %g (finite, >= 0), betas %g %g (in [0, 1)), eps %g (finite, > 0), weight_decay %g (finite, >= 0), scale %g (finite)",
+                      who, fit->lr, fit->beta1, fit->beta2, fit->eps, fit->weight_decay, fit->scale);
+        return NSD_E_INVALID;
+    }
+    const int64_t nh = (int64_t)d->B * d->H;
+    if (feats_model_stride < 0 || (feats_model_stride > 0 && feats_model_stride < nh)) {
+        nsd_set_error("%s: feats_model_stride %lld: 0 (one set for all models) or >= N*H = %lld", who, (long long)feats_model_stride, (long long)nh);
+        return NSD_E_INVALID;
+    }
+    FitArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int m = 0; rng && m < M; ++m) {
+        if (!(rng[m].p_head >= 0.f && rng[m].p_head < 1.f)) { nsd_set_error("%s: rng[%d].p_head %g outside [0, 1)", who, m, rng[m].p_head); return NSD_E_INVALID; }
+        a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream;
+        a.thr[m] = nsd_drop_threshold(rng[m].p_head); a.keep[m] = 1.0f / (1.0f - rng[m].p_head);
+    }
+    const int64_t need = (int64_t)M * fit_stride(d->F, d->K) * (int64_t)sizeof(float);
+    if (fit_state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_head_fit_state_bytes() = %lld", who, (long long)fit_state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    const ParamLayout pl = layout_of(d);
+    a.params = params; a.P = pl.total;
+    a.o_ln_w = pl.ln_w; a.o_ln_b = pl.ln_b; a.o_fc0_w = pl.fc0_w; a.o_fc0_b = pl.fc0_b; a.o_fc3_w = pl.fc3_w; a.o_fc3_b = pl.fc3_b;
+    a.feats = feats; a.feats_stride = feats_model_stride; a.targets = targets; a.state = (float *)fit_state; a.loss_out = loss_out;
+    a.N = d->B; a.F = d->F; a.K = d->K; a.epochs = fit->epochs; a.train = fit->train;
+    a.lr = fit->lr; a.b1 = fit->beta1; a.b2 = fit->beta2; a.eps = fit->eps; a.wd = fit->weight_decay; a.scale = fit->scale;
+    a.eval_slope = build_head(d, params).eval_slope;
+    a.rng_on = rng ? 1 : 0;
+    return nsd_head_fit_launch(a, M, (hipStream_t)stream);
+}
+
 // ---- sliding-window decisions (nsd_window48.hip): state [S][R phase slots + header] ----
 static bool window_ok(const nsd_window *w) {
     return w && w->window >= 1 && w->hop >= 1 && w->hop <= w->window && w->window % w->hop == 0 && w->window / w->hop <= NSD_WINDOW_MAX_PHASES;

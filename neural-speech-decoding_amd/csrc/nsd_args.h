@@ -226,6 +226,42 @@ struct StreamArgs {
 int nsd_stream48_launch(const StreamArgs &a, hipStream_t st);
 int nsd_stream_reset_launch(float *state, int S, const int32_t *slots, int n, hipStream_t st);
 
+// session calibration (nsd_stream_features / nsd_head_fit of nsd.h; nsd_head_fit.hip).  The trainable tail of a model, in the flat order
+// without the attention: ln.weight[H] ln.bias[H] fc.0.weight[F,H] fc.0.bias[F] fc.3.weight[K,F] fc.3.bias[K] -- Pt floats.  One model's
+// fit state, in floats: m[Pt], v[Pt], the int64 epoch count (8-byte aligned), the int32 status word; the public nsd_fit_layout.
+constexpr int FIT_H = 48, FIT_NT = 256;
+constexpr int FIT_MAX_OWN = 29;              // tail elements per thread at F = K = 64: ceil(7392 / 256)
+__host__ __device__ constexpr int fit_tail(int F, int K) { return 2 * FIT_H + F * FIT_H + F + K * F + K; }
+__host__ __device__ constexpr int fit_epochs_off(int F, int K) { return (2 * fit_tail(F, K) + 1) & ~1; }
+__host__ __device__ constexpr int fit_status_off(int F, int K) { return fit_epochs_off(F, K) + 2; }
+__host__ __device__ constexpr int fit_stride(int F, int K) { return (fit_status_off(F, K) + 1 + 3) & ~3; }
+// LDS image of the tail: fc.0's rows are FIT_H + 1 floats apart and fc.3's F | 1 (odd strides: a lane per row sweeps without conflicts)
+__host__ __device__ constexpr int fit_w3s(int F) { return F | 1; }
+__host__ __device__ constexpr int fit_image(int F, int K) { return 2 * FIT_H + F * (FIT_H + 1) + F + K * fit_w3s(F) + K; }
+// floats of LDS of one workgroup: xhat[N][H], dln[N][H], z / dpre [N][F], dlogits [N][K], loss[N], sign bits [N][2], the tail's image,
+// its gradient [Pt], two 64-float vectors per wave, and 8 words of flags and constants
+__host__ __device__ constexpr long fit_lds_floats(int N, int F, int K) {
+    return (long)N * (2 * FIT_H + F + K + 3) + fit_image(F, K) + fit_tail(F, K) + (FIT_NT / 64) * 128 + 8;
+}
+constexpr long FIT_LDS_MAX = 160 * 1024;     // bytes of LDS one workgroup may hold on gfx950
+struct FitArgs {
+    float *params; long P;                   // model m's flat vector at params + m * P
+    long o_ln_w, o_ln_b, o_fc0_w, o_fc0_b, o_fc3_w, o_fc3_b;
+    const float *feats; long feats_stride;   // [N][H] per model; 0: one set for all
+    const float *targets;                    // [M*N][K]
+    float *state;                            // [M][fit_stride]
+    float *loss_out;                         // [M][epochs] or null
+    int N, F, K, epochs;
+    unsigned train;
+    float lr, b1, b2, eps, wd, scale, eval_slope;
+    int rng_on;
+    uint64_t seed[NSD_MAX_MODELS];
+    uint32_t base[NSD_MAX_MODELS], thr[NSD_MAX_MODELS];
+    float keep[NSD_MAX_MODELS];
+};
+int nsd_head_fit_launch(const FitArgs &a, int M, hipStream_t st);
+int nsd_stream_features_launch(const float *state, int S, const int32_t *slots, int n, float *feats, hipStream_t st);
+
 // sliding-window decisions (nsd_window_* of nsd.h; nsd_window48.hip).  One stream of the caller's state, in floats: R = window / hop PHASE
 // SLOTS of STREAM_STRIDE floats in the layout above, then a header: the recorded window and hop (int32), two zero words, and one int64
 // sample count PER PHASE.  Phase r's workgroup reads and writes its own copy only, so no workgroup of a launch reads a word that another

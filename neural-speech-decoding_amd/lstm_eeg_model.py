@@ -519,3 +519,14 @@ class SimplePredictor:
         if window_seconds is not None:
             return PredictorSlidingStream(self, streams, chunk_transform, int(round(window_seconds * self.sr)), int(round(hop_seconds * self.sr)))
         return PredictorStream(self, streams, chunk_transform)
+
+    def calibrate(self, trials, labels, **fit_kw) -> dict:
+        """Session calibration (an extension, see calibrate.py): refit the read-out (LayerNorm, fc.0, fc.3; the LSTM stack and the
+        attention stay frozen) on a few cued trials of a new session.  trials [N,T,C] (N <= 256), labels [N] class indices.  The
+        trials run through open_stream on reset slots -- preprocessing and a causal front end are exactly what the live stream
+        applies -- their pooled features are read and the read-out is fitted by nsd_amd.HeadFit(**fit_kw) in one launch (of an
+        EnsemblePredictor: all members together, each on its own features).  chunk_transform=: as open_stream's.  The model is updated
+        in place: a decoder that is open keeps its state, and its next read-out uses the fitted head.  Returns a dict with loss and
+        accuracy on the calibration trials before and after, the fit's loss curve and its status."""
+        from .calibrate import calibrate_predictor
+        return calibrate_predictor(self, trials, labels, **fit_kw)

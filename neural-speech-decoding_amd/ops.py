@@ -450,6 +450,15 @@ def mixup(x: Optional[torch.Tensor], labels: torch.Tensor, K: int, rngs, *, labe
     return out, targets
 
 
+def target_rows(labels: torch.Tensor, K: int, M: int = 1, loss: Optional[Loss] = None) -> torch.Tensor:
+    """The target rows [M*B, K] of int32 labels [M*B] with nothing mixed (the nsd_mixup launch at mix = 0, which draws nothing): one-hot
+    rows, or `loss`'s label smoothing and class weights -- what nsd_head_fit takes in place of labels."""
+    loss = loss or Loss()
+    rngs = [dict(seed=0, base_stream=0, p_lstm=0.0, p_head=0.0)] * int(M)
+    return mixup(None, labels, K, rngs, label_smoothing=loss.label_smoothing, mix=0.0, class_weights=loss.weights_tensor(labels.device),
+                 M=int(M))[1]
+
+
 @dataclass(frozen=True)
 class LrSchedule:
     """Learning-rate schedule of a trainer (the schedule fields of nsd_opt, include/nsd.h; an extension, the reference has none):
@@ -1272,6 +1281,91 @@ def multi_stream_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, st
           _lib.NSD_FLAG_RESIDUAL if residual else 0, _dev_f32(state, "state"), _nbytes(state), S, _dev_f32(logits, "logits"),
           _dev_f32(probs, "probs"), _dev_f32(mean, "mean"), STREAM)
     return logits, probs, mean
+
+
+# ---- session calibration: pooled features of stream slots, the read-out refitted on them (nsd_stream_features / nsd_head_fit) ----
+
+FIT_GROUPS = {"ln": _lib.NSD_FIT_LN, "fc0": _lib.NSD_FIT_FC0, "fc3": _lib.NSD_FIT_FC3}
+
+
+def stream_features(spec: ModelSpec, state: torch.Tensor, *, slots: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """feats [n,H]: row i is pool_acc / pool_den of slot slots[i] (or i) of `state` -- fp32 [S, stride], or the [M, S, stride] state of an
+    ensemble read as M*S flat slots.  A never-stepped or out-of-range slot gives a NaN row."""
+    flat = state.view(-1, int(state.shape[-1])) if state.dim() == 3 else state
+    S = int(flat.shape[0]) if flat.dim() == 2 else 0
+    n = (S if slots is None else int(slots.numel())) if n is None else int(n)
+    if slots is not None and int(slots.numel()) != n:
+        raise NsdError(f"stream_features: {int(slots.numel())} slot indices for {n} rows")
+    out = _out_f32(out, (n, spec.H), state.device, "stream_features: feats")
+    d = spec.dims(0, 1)
+    _call("nsd_stream_features", state.device, C.byref(d), _dev_f32(flat, "state"), _nbytes(flat), S, _slots_ptr(slots, "stream_features"), n,
+          _dev_f32(out, "feats"), STREAM)
+    return out
+
+
+def head_fit_path(spec: ModelSpec, M: int, N: int) -> bool:
+    """True where nsd_head_fit covers M models of this shape on N trials (stream_path, 1 <= M <= 32, 1 <= N <= 256, the LDS need)."""
+    d = spec.dims(int(N), 1)
+    return spec.D == 1 and bool(_lib.lib().nsd_head_fit_path(C.byref(d), int(M)))
+
+
+def head_fit_layout(spec: ModelSpec) -> "_lib.FitLayout":
+    """Float offsets of m, v, the int64 epoch count and the int32 status word inside one model's fit state, and its stride."""
+    d, lay = spec.dims(1, 1), _lib.FitLayout()
+    check(_lib.lib().nsd_head_fit_state_layout(C.byref(d), C.byref(lay)), "nsd_head_fit_state_layout")
+    return lay
+
+
+def head_fit_state(spec: ModelSpec, M: int, device="cuda") -> torch.Tensor:
+    """A reset fit state of M models: fp32 zeros [M, stride] (all-zero bytes is the reset state)."""
+    d = spec.dims(1, 1)
+    n = int(_lib.lib().nsd_head_fit_state_bytes(C.byref(d), int(M)))
+    if n < 0:
+        check(n, "nsd_head_fit_state_bytes")
+    state = torch.zeros((int(M), int(head_fit_layout(spec).stride)), dtype=torch.float32, device=device)
+    if _nbytes(state) != n:
+        raise NsdError(f"head_fit_state: {_nbytes(state)} bytes for nsd_head_fit_state_bytes = {n}")
+    return state
+
+
+def fit_mask(train) -> int:
+    """("ln", "fc0", "fc3") names, or the NSD_FIT_* bits themselves -> the train mask of nsd_fit"""
+    if isinstance(train, int):
+        return train
+    bad = [g for g in train if g not in FIT_GROUPS]
+    if bad:
+        raise NsdError(f"head_fit: unknown tensor group(s) {bad}; the groups are {sorted(FIT_GROUPS)}")
+    mask = 0
+    for g in train:
+        mask |= FIT_GROUPS[g]
+    return mask
+
+
+def head_fit(spec: ModelSpec, params: torch.Tensor, feats: torch.Tensor, targets: torch.Tensor, state: torch.Tensor, *, epochs: int,
+             lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+             scale: Optional[float] = None, train=("ln", "fc0", "fc3"), rngs=None, loss_out: Optional[torch.Tensor] = None,
+             want_loss: bool = True) -> Optional[torch.Tensor]:
+    """`epochs` full-batch Adam epochs of the read-out (LayerNorm, fc.0, fc.3) of M models on frozen pooled features, in ONE launch.
+    params [M,P] (or [P]) are updated in place, only the tensors `train` names; feats [N,H] (shared by the models) or [M,N,H]; targets
+    [M,N,K] (or [N,K] for one model) soft target rows; state: head_fit_state, carried between calls (more epochs later continue the
+    same run bit for bit); scale: 1/N by default; rngs: None (eval slope, no dropout) or one rng dict per model (p_head is read).
+    Returns the losses before each epoch's update [M, epochs] (None with want_loss=False)."""
+    p2 = params.view(1, -1) if params.dim() == 1 else params
+    M = int(p2.shape[0])
+    if feats.dim() not in (2, 3) or int(feats.shape[-1]) != spec.H or (feats.dim() == 3 and int(feats.shape[0]) != M):
+        raise NsdError(f"head_fit: feats must be [N, {spec.H}] or [{M}, N, {spec.H}], got {tuple(feats.shape)}")
+    N = int(feats.shape[-2])
+    stride = N * spec.H if feats.dim() == 3 else 0
+    d = spec.dims(N, 1)
+    fit = _lib.Fit(int(epochs), fit_mask(train), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+                   float(1.0 / N if scale is None else scale))
+    if want_loss:
+        loss_out = _out_f32(loss_out, (M, int(epochs)), params.device, "head_fit: loss_out")
+    _call("nsd_head_fit", params.device, C.byref(d), M, _dev_f32(p2, "params", (M, spec.param_count)), _dev_f32(feats, "feats"), stride,
+          _dev_f32(targets.view(M * N, spec.K) if targets.numel() == M * N * spec.K else targets, "targets", (M * N, spec.K)), C.byref(fit),
+          _rng_array(rngs, M, "head_fit"), _dev_f32(state, "fit_state"), _nbytes(state), _dev_f32(loss_out, "loss_out"), STREAM)
+    return loss_out
 
 
 # ---- sliding-window decisions for continuous streams (nsd_window_* of include/nsd.h) ----

@@ -107,6 +107,11 @@ class StreamDecoder:
                                    residual=self.model.residual, read=read)
         return probs
 
+    def features(self, slots=None) -> torch.Tensor:
+        """The pooled vector each slot holds, [n, H] (device tensor; all slots, or the named ones): the vector whose read-out the slot's
+        decision is -- what nsd_amd.HeadFit calibrates the read-out on.  A slot that was never pushed gives a NaN row."""
+        return ops.stream_features(self.model.spec, self.state, slots=self._slots(slots))
+
     def reset(self, slots=None) -> None:
         slots = self._slots(slots)
         ops.stream_reset(self.model.spec, self.state, slots)
@@ -201,6 +206,15 @@ class EnsembleStreamDecoder(StreamDecoder):
             self.member_probs = probs
         return mean
 
+    def features(self, slots=None) -> torch.Tensor:
+        """The pooled vector of each slot in every model, [M, n, H] (device tensor): the ensemble's state read as M*S flat slots"""
+        slots = self._slots(slots)
+        M, S = len(self.members), self.streams
+        if slots is None:
+            return ops.stream_features(self.model.spec, self.state).view(M, S, -1)
+        every = (slots[None, :] + S * torch.arange(M, dtype=torch.int32, device=self.device)[:, None]).reshape(-1).contiguous()
+        return ops.stream_features(self.model.spec, self.state, slots=every).view(M, int(slots.numel()), -1)
+
     def reset(self, slots=None) -> None:
         slots = self._slots(slots)
         M, S = len(self.members), self.streams
@@ -273,6 +287,10 @@ class SlidingStreamDecoder(StreamDecoder):
         self._last_end[idx] = torch.where(has, ends.gather(1, row[:, None])[:, 0], self._last_end[idx])
         newest = probs.gather(1, row[:, None, None].expand(-1, 1, probs.shape[2]))[:, 0]
         self._last_probs[idx] = torch.where(has[:, None], newest, self._last_probs[idx])
+
+    def features(self, slots=None):
+        raise NsdError(f"{type(self).__name__}.features: a sliding decoder's phase slots are in the middle of their windows; read the "
+                       "pooled features of cued trials from a StreamDecoder (open_stream without window_seconds)")
 
     def latest(self) -> list:
         ends, probs = self._last_end.cpu().numpy(), self._last_probs.cpu().numpy()
