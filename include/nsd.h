@@ -475,6 +475,68 @@ int nsd_multi_grad_reduce_clip_adam_each(const nsd_dims *d, int32_t M, const flo
                                          void *opt_state, int64_t opt_state_bytes, void *stream);
 
 /*
+ * ---- early stopping for model batches: held-out metrics, the best-evaluation decision and the snapshot in ONE launch (an EXTENSION) ----
+ *
+ * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_multi_eval_path).  nsd_multi_eval reads the logits of M
+ * models -- what nsd_multi_infer wrote for each model's held-out windows, or any other path's -- and their parameter rows; it is not
+ * H = 48 specific.  One launch, one 256-thread workgroup per model.
+ * Rows that count.  Only the first counts[m] rows of model m count (counts: a HOST array of M entries, validated before the launch and
+ * passed by value, so a captured call replays; NULL: B each).  The rest is padding (folds differ in size by one, nsd_multi_infer wants
+ * one B) and may hold anything, NaN logits and labels outside [0, K) included.
+ * Per counted row, from the fp32 logits in double:  loss = log(sum_k exp(l_k - max)) + max - l_y, k ascending; the prediction is the
+ * first maximal index; confusion[y][pred] += 1, correct += (pred == y), n += 1.  A counted row with a non-finite logit, or with a label
+ * outside [0, K), counts in `nonfinite` ONLY (not in n, correct or confusion) and makes the model's loss_sum NaN, explicitly and not by
+ * what the arithmetic would yield.
+ * Summation order.  loss_sum is formed in an order fixed by the workgroup size alone: lane i of 256 sums rows i, i + 256, ... in
+ * ascending order, then a halving tree combines the lanes (lane i += lane i + s for s = 128, 64, ..., 1).  Model m's record therefore
+ * does not depend on M or on the other models' data.
+ * Selection, with sel != NULL, per model, on the record in sel_state:
+ *   stopped != 0          the select record and the snapshot keep their bytes (the eval record is still written)
+ *   otherwise             evals += 1; mean = loss_sum / n; acc = (double)correct / n.  A non-finite mean sets status bit 0 and counts as
+ *                         "not improved".  Improved, NSD_SELECT_LOSS: no best yet (best_eval == 0), or mean < best_loss - min_delta.
+ *                         Improved, NSD_SELECT_ACC: no best yet, or acc > best_acc + min_delta, or acc == best_acc and mean < best_loss
+ *                         (best_acc = (double)best_correct / best_n; every comparison in double, min_delta widened exactly).
+ *   on improvement        best_loss = mean, best_correct = correct, best_n = n, best_eval = evals, bad = 0, and best_params[m] becomes
+ *                         a byte copy of params[m] (16-byte accesses in the body, single words at the misaligned head and tail of a row;
+ *                         the decision reaches the workgroup through LDS first)
+ *   without               bad += 1; with patience > 0 and bad >= patience: stopped = 1.  No word of the snapshot is written.
+ * sel_state (device, caller-owned, nsd_select_state_bytes(M, P) bytes): M nsd_select_record, padded to a multiple of 16 bytes, then
+ * best_params [M][P].  nsd_select_state_init zeroes the records (and the padding); the snapshot rows may hold anything until their
+ * model's first improvement.  `evals` lives in the record, so a captured call replays: three replays are three evaluations.
+ *   nsd_multi_eval_path   1 where 1 <= M <= NSD_MAX_MODELS, 1 <= K <= 8, B >= 1, M * B * K <= 2^31 - 1 and P >= 0 (P = 0: metrics only)
+ * Failure behaviour.  Every refusal happens before any launch.  NSD_E_INVALID: M outside [1, NSD_MAX_MODELS]; K outside [1, 8]; B < 1;
+ * M * B * K > 2^31 - 1; a counts[m] outside [1, B]; NULL logits, labels or out; sel with a metric other than NSD_SELECT_LOSS / _ACC, with
+ * patience < 0, with a negative or NaN min_delta; sel without params or sel_state, or with P < 1.  NSD_E_WORKSPACE: sel_state_bytes <
+ * nsd_select_state_bytes(M, P).  Writes: out[M] and, with sel, the records and the improved models' snapshot rows; nothing else.  No
+ * host synchronisation, no allocation.
+ */
+#define NSD_SELECT_LOSS 0
+#define NSD_SELECT_ACC  1
+#define NSD_EVAL_MAX_K  8
+typedef struct nsd_select {
+    int32_t metric;                 /* NSD_SELECT_LOSS | NSD_SELECT_ACC */
+    int32_t patience;               /* >= 0; 0: track the best, never stop */
+    float   min_delta;              /* >= 0 */
+} nsd_select;
+typedef struct nsd_eval_record {    /* 280 B per model */
+    double  loss_sum;               /* over the n rows, NaN where nonfinite > 0 */
+    int32_t n, correct, nonfinite, pad;
+    int32_t confusion[NSD_EVAL_MAX_K][NSD_EVAL_MAX_K];   /* [label][prediction] */
+} nsd_eval_record;
+typedef struct nsd_select_record {  /* 40 B per model, first bytes of sel_state */
+    double   best_loss;             /* mean loss of the best evaluation */
+    int32_t  best_correct, best_n, best_eval /* 1-based, 0: none yet */, evals, bad;
+    uint32_t stopped, status /* bit 0: a non-finite evaluation was seen */, pad;
+} nsd_select_record;
+int     nsd_multi_eval_path(int32_t M, int32_t B, int32_t K, int64_t P);
+int64_t nsd_select_state_bytes(int32_t M, int64_t P);
+int     nsd_select_state_init(void *sel_state, int64_t sel_state_bytes, int32_t M, int64_t P, void *stream);
+int     nsd_multi_eval(int32_t M, int32_t B, int32_t K, const float *logits /* [M*B][K] */, const int32_t *labels /* [M*B] */,
+                       const int32_t *counts /* HOST, [M] or NULL = B each */, nsd_eval_record *out /* device, [M] */,
+                       const nsd_select *sel /* NULL: metrics only */, const float *params /* [M][P] */, int64_t P,
+                       void *sel_state, int64_t sel_state_bytes, void *stream);
+
+/*
  * ---- resumable H = 48 inference: decode live streams chunk by chunk (an EXTENSION: the reference decodes whole windows only) ----
  *
  * EEG_LSTM (lstm_eeg_model.py:13-39) is causal: two forward LSTM layers and a softmax pooling over time that can be formed online.  The

@@ -100,6 +100,27 @@ NSD_FIT_MAX_TRIALS, NSD_FIT_MAX_EPOCHS = 256, 65536
 NSD_FIT_LN, NSD_FIT_FC0, NSD_FIT_FC3 = 1, 2, 4
 
 
+class Select(C.Structure):
+    """nsd_select of include/nsd.h: the early-stopping rule of one nsd_multi_eval call"""
+    _fields_ = [("metric", C.c_int32), ("patience", C.c_int32), ("min_delta", C.c_float)]
+
+
+class EvalRecord(C.Structure):
+    """nsd_eval_record of include/nsd.h: one model's held-out metrics"""
+    _fields_ = ([("loss_sum", C.c_double)] + [(n, C.c_int32) for n in ("n", "correct", "nonfinite", "pad")]
+                + [("confusion", (C.c_int32 * 8) * 8)])
+
+
+class SelectRecord(C.Structure):
+    """nsd_select_record of include/nsd.h: one model's best evaluation, patience count and stop flag"""
+    _fields_ = ([("best_loss", C.c_double)] + [(n, C.c_int32) for n in ("best_correct", "best_n", "best_eval", "evals", "bad")]
+                + [(n, C.c_uint32) for n in ("stopped", "status", "pad")])
+
+
+NSD_SELECT_LOSS, NSD_SELECT_ACC, NSD_EVAL_MAX_K = 0, 1, 8
+NSD_SELECT = {"loss": NSD_SELECT_LOSS, "acc": NSD_SELECT_ACC}
+
+
 class Prep(C.Structure):
     """nsd_prep of include/nsd.h"""
     _fields_ = [("flags", C.c_uint32), ("n_sections", C.c_int32), ("sos", (C.c_float * 5) * 4), ("alpha", C.c_float), ("var0", C.c_float)]
@@ -200,6 +221,12 @@ SYMBOLS = {
     "nsd_multi_grad_reduce_clip_adam_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
     "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
     "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),
+    # early stopping for model batches: metrics, the best-evaluation decision and the snapshot in one launch
+    "nsd_multi_eval_path": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "nsd_select_state_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "nsd_select_state_init": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int64, _vp]),
+    "nsd_multi_eval": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, _ip, C.POINTER(C.c_int32), _vp, C.POINTER(Select), _fp, C.c_int64,
+                                 _vp, C.c_int64, _vp]),
     # resumable H = 48 inference (streams decoded chunk by chunk)
     "nsd_stream_path": (C.c_int, [_dp]),
     "nsd_stream_state_bytes": (C.c_int64, [_dp, C.c_int32]),

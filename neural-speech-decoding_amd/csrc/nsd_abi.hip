@@ -1217,6 +1217,76 @@ int nsd_head_fit(const nsd_dims *d, int32_t M, float *params, const float *feats
     return nsd_head_fit_launch(a, M, (hipStream_t)stream);
 }
 
+// ---- early stopping for model batches (nsd_eval.hip): metrics, the best-evaluation decision and the snapshot of M models ----
+// the shape of a call: 0, or the refusal with the field named
+static int eval_shape(const char *who, int32_t M, int32_t B, int32_t K) {
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (K < 1 || K > NSD_EVAL_MAX_K) { nsd_set_error("%s: K = %d outside [1, %d]", who, K, NSD_EVAL_MAX_K); return NSD_E_INVALID; }
+    if (B < 1) { nsd_set_error("%s: B = %d must be >= 1", who, B); return NSD_E_INVALID; }
+    if ((int64_t)M * B * K > 2147483647LL) {
+        nsd_set_error("%s: M * B * K = %lld logits exceed 2^31 - 1", who, (long long)((int64_t)M * B * K)); return NSD_E_INVALID;
+    }
+    return NSD_OK;
+}
+int nsd_multi_eval_path(int32_t M, int32_t B, int32_t K, int64_t P) {
+    return M >= 1 && M <= NSD_MAX_MODELS && K >= 1 && K <= NSD_EVAL_MAX_K && B >= 1 && (int64_t)M * B * K <= 2147483647LL && P >= 0 ? 1 : 0;
+}
+
+int64_t nsd_select_state_bytes(int32_t M, int64_t P) {
+    if (M < 1 || M > NSD_MAX_MODELS || P < 1) {
+        nsd_set_error("select_state_bytes: M = %d, P = %lld (1 <= M <= %d, P >= 1)", M, (long long)P, NSD_MAX_MODELS); return NSD_E_INVALID;
+    }
+    return (int64_t)eval_records_bytes(M) + (int64_t)M * P * (int64_t)sizeof(float);
+}
+
+int nsd_select_state_init(void *sel_state, int64_t sel_state_bytes, int32_t M, int64_t P, void *stream) {
+    static const char *who = "select_state_init";
+    if (!sel_state) { nsd_set_error("%s: sel_state is NULL", who); return NSD_E_INVALID; }
+    const int64_t need = nsd_select_state_bytes(M, P);
+    if (need < 0) return NSD_E_INVALID;
+    if (sel_state_bytes < need) {
+        nsd_set_error("%s: sel_state of %lld bytes is smaller than nsd_select_state_bytes() = %lld", who, (long long)sel_state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return nsd_opt_state_init_launch(sel_state, eval_records_bytes(M), (hipStream_t)stream);      // the records; the snapshot rows stay
+}
+
+int nsd_multi_eval(int32_t M, int32_t B, int32_t K, const float *logits, const int32_t *labels, const int32_t *counts, nsd_eval_record *out,
+                   const nsd_select *sel, const float *params, int64_t P, void *sel_state, int64_t sel_state_bytes, void *stream) {
+    static const char *who = "multi_eval";
+    if (const int rc = eval_shape(who, M, B, K)) return rc;
+    if (!logits) { nsd_set_error("%s: logits is NULL", who); return NSD_E_INVALID; }
+    if (!labels) { nsd_set_error("%s: labels is NULL", who); return NSD_E_INVALID; }
+    if (!out) { nsd_set_error("%s: out is NULL", who); return NSD_E_INVALID; }
+    EvalArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int m = 0; m < M; ++m) {
+        a.counts[m] = counts ? counts[m] : B;
+        if (a.counts[m] < 1 || a.counts[m] > B) { nsd_set_error("%s: counts[%d] = %d outside [1, B = %d]", who, m, a.counts[m], B); return NSD_E_INVALID; }
+    }
+    if (sel) {
+        if (sel->metric != NSD_SELECT_LOSS && sel->metric != NSD_SELECT_ACC) {
+            nsd_set_error("%s: sel->metric %d unknown (NSD_SELECT_LOSS / NSD_SELECT_ACC)", who, sel->metric); return NSD_E_INVALID;
+        }
+        if (sel->patience < 0) { nsd_set_error("%s: sel->patience %d negative", who, sel->patience); return NSD_E_INVALID; }
+        if (!(sel->min_delta >= 0.f)) { nsd_set_error("%s: sel->min_delta %g negative or NaN", who, sel->min_delta); return NSD_E_INVALID; }
+        if (!params) { nsd_set_error("%s: sel without params", who); return NSD_E_INVALID; }
+        if (!sel_state) { nsd_set_error("%s: sel without sel_state", who); return NSD_E_INVALID; }
+        if (P < 1) { nsd_set_error("%s: sel with P = %lld (P >= 1)", who, (long long)P); return NSD_E_INVALID; }
+        const int64_t need = nsd_select_state_bytes(M, P);
+        if (sel_state_bytes < need) {
+            nsd_set_error("%s: sel_state of %lld bytes is smaller than nsd_select_state_bytes() = %lld", who, (long long)sel_state_bytes, (long long)need);
+            return NSD_E_WORKSPACE;
+        }
+        a.select = 1; a.metric = sel->metric; a.patience = sel->patience; a.min_delta = sel->min_delta;
+        a.params = params; a.P = P;
+        a.recs = static_cast<nsd_select_record *>(sel_state);
+        a.best = reinterpret_cast<float *>(static_cast<char *>(sel_state) + eval_records_bytes(M));
+    }
+    a.logits = logits; a.labels = labels; a.out = out; a.B = B; a.K = K;
+    return nsd_multi_eval_launch(a, M, (hipStream_t)stream);
+}
+
 // ---- sliding-window decisions (nsd_window48.hip): state [S][R phase slots + header] ----
 static bool window_ok(const nsd_window *w) {
     return w && w->window >= 1 && w->hop >= 1 && w->hop <= w->window && w->window % w->hop == 0 && w->window / w->hop <= NSD_WINDOW_MAX_PHASES;

@@ -262,6 +262,24 @@ struct FitArgs {
 int nsd_head_fit_launch(const FitArgs &a, int M, hipStream_t st);
 int nsd_stream_features_launch(const float *state, int S, const int32_t *slots, int n, float *feats, hipStream_t st);
 
+// early stopping for model batches (nsd_multi_eval of nsd.h; nsd_eval.hip).  sel_state: M nsd_select_record, padded to 16 bytes, then the
+// snapshot rows [M][P].  The counts travel by value, so a captured launch carries them.
+constexpr int EVAL_NT = 256;
+__host__ __device__ constexpr long eval_records_bytes(int M) { return ((long)M * (long)sizeof(nsd_select_record) + 15) & ~15L; }
+struct EvalArgs {
+    const float *logits;                     // [M*B][K]
+    const int32_t *labels;                   // [M*B]
+    nsd_eval_record *out;                    // [M]
+    int B, K;
+    int select, metric, patience;            // select 0: metrics only
+    float min_delta;
+    const float *params; long P;             // model m's row at params + m * P
+    nsd_select_record *recs;                 // [M]
+    float *best;                             // [M][P]
+    int32_t counts[NSD_MAX_MODELS];
+};
+int nsd_multi_eval_launch(const EvalArgs &a, int M, hipStream_t st);
+
 // sliding-window decisions (nsd_window_* of nsd.h; nsd_window48.hip).  One stream of the caller's state, in floats: R = window / hop PHASE
 // SLOTS of STREAM_STRIDE floats in the layout above, then a header: the recorded window and hop (int32), two zero words, and one int64
 // sample count PER PHASE.  Phase r's workgroup reads and writes its own copy only, so no workgroup of a launch reads a word that another

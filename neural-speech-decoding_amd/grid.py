@@ -13,6 +13,11 @@ Output, JSON lines: one per (configuration, fold, epoch) as --concurrent emits t
 mean +- sd of the last-epoch validation accuracy; one `done` line with the ranking and the best configuration as train.py arguments.
 The best mean over folds is an optimistic estimate (it is selected on the folds it is scored on): re-estimate it on fresh folds.
 No final model is trained.
+
+--early-stop-patience N [--early-stop-metric loss|acc] [--early-stop-min-delta d] [--inner-fraction f] (train's options): every run
+holds out an inner part of its training trials, all models of a launch are scored on theirs after each epoch in two launches
+(ModelBatchTrainer.track_best), and the validation accuracy of a run is that of its best-epoch model, scored once at the end; the
+summaries then carry the selection rule, the chosen epochs and the confusion matrices.
 """
 from __future__ import annotations
 
@@ -100,7 +105,8 @@ def main(argv=None) -> int:
     from .multimodel import ModelBatchTrainer
     from .ops import Augment, Loss
     from .prep import CausalPrep
-    from .train import concurrent_epoch, concurrent_runs, evaluate, loss_for, parse_class_weights, schedule_for
+    from .train import (concurrent_epoch, concurrent_runs, early_stop_settings, evaluate, loss_for, padded_parts, parse_class_weights,
+                        schedule_for, selection_text)
 
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -116,6 +122,10 @@ def main(argv=None) -> int:
         ap.error("grid: no models are kept (train the chosen configuration with nsd_amd.train)")
     if args.lr_schedule is None and (args.warmup_steps or args.lr_min_ratio or args.lr_step_size != 1 or args.lr_gamma != 1.0):
         args.lr_schedule = "constant"
+    try:
+        es = early_stop_settings(args, concurrent=True)          # (the grid's runs are always the model-batched folds)
+    except ValueError as e:
+        ap.error(str(e))
     prep_stage = any(v is not None for v in (args.prep_highpass, args.prep_lowpass, args.prep_notch, args.prep_zscore_seconds)) or args.prep_car
     prep_design = None
     if prep_stage:
@@ -167,7 +177,7 @@ def main(argv=None) -> int:
             ap.error(f"--T {args.T} but the trials have {ts.x.shape[1]} samples")
         x_np, y_np = ts.x, ts.y
     try:
-        runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch)
+        runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch, es["inner_fraction"] if es else None)
         groups = pack_groups(len(configs), len(runs))
     except ValueError as e:
         print(f"grid: {e}", file=sys.stderr)
@@ -211,24 +221,46 @@ def main(argv=None) -> int:
             sel = [tr_devs[k][torch.from_numpy(ix).to(dev)] for (_, k), ix in zip(members, idxs)]
             mbt.step(torch.stack([x_all[s_] for s_ in sel]), torch.stack([y_all[s_] for s_ in sel]))
 
+        if es:       # the held-out sets of all members, padded to one B each: built once per group
+            held = {part: padded_parts(x_all, y_all, [r[part] for r in member_runs]) for part in ("tr", "inner", "va")}
         for epoch in range(args.epochs):
             concurrent_epoch(member_runs, args.batch, epoch, step)
             last = epoch == args.epochs - 1
+            if es:   # every epoch: all members on their inner parts, the best-epoch decision and the snapshot, in two launches
+                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"])
+                last = last or all(e["stopped"] for e in inner)
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
                 norms, lrs, skipped = (mbt.last_grad_norms(), mbt.last_lrs(), mbt.skipped_steps()) if opt_on else (None, None, None)
+                if es:
+                    ev_tr, ev_va = mbt.evaluate(*held["tr"]), mbt.evaluate(*held["va"])
                 for i, (c, k) in enumerate(members):
-                    acc_tr = evaluate(models[i], x_all[tr_devs[k]], y_all[tr_devs[k]])
-                    acc_va = evaluate(models[i], x_all[runs[k]["va"]], y_all[runs[k]["va"]])
+                    if es:
+                        acc_tr, acc_va = ev_tr[i]["acc"], ev_va[i]["acc"]
+                    else:
+                        acc_tr = evaluate(models[i], x_all[tr_devs[k]], y_all[tr_devs[k]])
+                        acc_va = evaluate(models[i], x_all[runs[k]["va"]], y_all[runs[k]["va"]])
                     res[i] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
                     emit({"run": tag(runs[k]), "config_index": c, "config": configs[c], "epoch": epoch, "loss_last_batch": round(losses[i], 5),
                           "acc_train": round(acc_tr, 4), "acc_val": round(acc_va, 4), "n_val": int(len(runs[k]["va"])),
                           "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
-                          **({"grad_norm": norms[i], "lr": lrs[i], "skipped": skipped[i]} if opt_on else {})})
+                          **({"grad_norm": norms[i], "lr": lrs[i], "skipped": skipped[i]} if opt_on else {}),
+                          **({"loss_inner": round(inner[i]["loss"], 5), "acc_inner": round(inner[i]["acc"], 4),
+                              "best_epoch": inner[i]["best_eval"] - 1, "stopped": inner[i]["stopped"]} if es else {})})
+            if es and last:
+                break
+        if es:       # the outer folds of the best-epoch models, in one call
+            best = mbt.restore_best()
+            final = mbt.evaluate(*held["va"])
+            for i in range(len(members)):
+                res[i]["acc_val_last"] = final[i]["acc"]
         for c in group:
-            accs = [res[i]["acc_val_last"] for i, (cc, _) in enumerate(members) if cc == c]
+            mine = [i for i, (cc, _) in enumerate(members) if cc == c]
+            accs = [res[i]["acc_val_last"] for i in mine]
             summaries.append({"summary": True, "config_index": c, "config": configs[c], "acc_val_mean": round(float(np.mean(accs)), 4),
                               "acc_val_sd": round(float(np.std(accs, ddof=1)), 4), "acc_val_folds": [round(float(a), 4) for a in accs],
+                              **({"selection": selection_text(es), "best_epochs": [best[i] - 1 for i in mine],
+                                  "confusion_val": [final[i]["confusion"].tolist() for i in mine]} if es else {}),
                               "train_args": train_args(configs[c])})
             emit(summaries[-1])
         del mbt, models

@@ -109,6 +109,7 @@ class ModelBatchTrainer:
         self.step_count = 0
         self._bufs = {}
         self._last = None
+        self._sel_buf, self._sel_state, self._sel_rule = None, None, None      # early stopping: allocated by the first track_best
 
     def _per_model(self, v, name: str, pair: bool = False) -> list:
         """A setting given once or per model -> its M entries (pair: the single setting is itself a pair, per model is M pairs)."""
@@ -193,6 +194,114 @@ class ModelBatchTrainer:
         B, T = self._last
         s = ops.multi_loss_sum(self.spec, self._bufs[(B, T)]["ws"], self.M, B, T)
         return [float(v) / B for v in s.cpu().tolist()]
+
+    # ---- held-out metrics and early stopping for all models (nsd_multi_eval of include/nsd.h) --------------------------------------
+    # A trainer on which none of these is called allocates nothing for them and issues exactly the calls it issued without them.
+
+    def _held_out(self, x: torch.Tensor, y: torch.Tensor, counts, select, who: str) -> List[dict]:
+        """nsd_multi_infer on the windows (behind the models' front end, as EEG_LSTM.forward), nsd_multi_eval on its logits, ONE read of
+        the records: with selection the eval records lie directly in front of the select state in one allocation, so one copy brings
+        both kinds."""
+        M = self.M
+        if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != M):
+            raise NsdError(f"ModelBatchTrainer.{who}: x must be [M={M},B,T,C] or [B,T,C], got {tuple(x.shape)}")
+        B, T, Cc = (int(v) for v in x.shape[-3:])
+        if B == 0:
+            raise NsdError(f"ModelBatchTrainer.{who}: no windows")
+        y = y.to(torch.int32)
+        if y.dim() == 1 and y.shape[0] == B:
+            y = y.unsqueeze(0).expand(M, B)
+        if tuple(y.shape) != (M, B):
+            raise NsdError(f"ModelBatchTrainer.{who}: y must be [M,B] = [{M},{B}] or [B], got {tuple(y.shape)}")
+        x = x.contiguous().float()
+        if self.models[0].prep is not None:
+            x = ops.prep_step(x, self.models[0].prep)
+        elif self.models[0].normalize:
+            x = ops.zscore(x.reshape(-1, T, Cc)).view(x.shape)
+        logits, _ = ops.multi_infer(self.spec, self.params, x, want_probs=False)
+        if select is None:
+            return ops.eval_records(ops.multi_eval(logits, y.contiguous(), counts=counts), M, self.spec.K)
+        lead = (M * ops.EVAL_RECORD_BYTES + 15) // 16 * 16
+        if self._sel_state is None:
+            self._sel_buf = torch.empty(lead + ops.select_state_bytes(M, self.spec.param_count), dtype=torch.uint8, device=self.params.device)
+            self._sel_state = ops.select_state(M, self.spec.param_count, self.params.device, out=self._sel_buf[lead:])
+        ops.multi_eval(logits, y.contiguous(), counts=counts, out=self._sel_buf[:M * ops.EVAL_RECORD_BYTES], select=select, params=self.params,
+                       state=self._sel_state)
+        raw = self._sel_buf[:lead + M * ops.SELECT_RECORD_BYTES].cpu()
+        recs = ops.eval_records(raw, M, self.spec.K)
+        for r, s in zip(recs, ops.select_records(raw[lead:], M)):
+            r.update(best_eval=s["best_eval"], bad=s["bad"], stopped=bool(s["stopped"]))
+        return recs
+
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, counts=None) -> List[dict]:
+        """Held-out metrics of all M models in two launches and one read: x [M,B,T,C] (each model's own windows) or a shared [B,T,C], y
+        [M,B] or [B] class indices.  counts: None, or M ints -- only model m's first counts[m] windows count, the rest is padding
+        (folds differ in size by one; the padding may hold anything).  Returns M dicts: loss (mean cross-entropy, summed in double),
+        acc, n, nonfinite (windows whose logits were not finite: they count nowhere else and make the loss NaN) and confusion, a
+        [K,K] numpy array indexed [label, prediction].  Synchronises."""
+        return self._held_out(x, y, counts, None, "evaluate")
+
+    def track_best(self, x: torch.Tensor, y: torch.Tensor, counts=None, metric: str = "loss", patience: int = 0,
+                   min_delta: float = 0.0) -> List[dict]:
+        """evaluate(), and in the same launch early stopping per model: is this the model's best evaluation so far (metric "loss": the
+        mean loss fell by more than min_delta; "acc": the accuracy rose by more than min_delta, or stayed with a lower loss), if so copy
+        its parameter row into a snapshot on the device, else count one more bad evaluation and, with patience > 0, mark the model
+        stopped after `patience` of them in a row (patience = 0 tracks the best and never stops).  A non-finite evaluation is a bad
+        one.  Returns evaluate()'s dicts extended by best_eval (1-based number of the best evaluation, 0: none yet), bad and stopped.
+        One rule per trainer: another metric, patience or min_delta on a later call raises.
+
+        A stopped model STILL TRAINS: step() keeps updating its parameters until the caller's loop ends (the step kernels know nothing
+        of this).  Its snapshot and its record are frozen, so restore_best() gives what stopping it would have given; all_stopped()
+        lets the loop end early."""
+        if metric not in ("loss", "acc"):
+            raise NsdError(f"ModelBatchTrainer.track_best: metric {metric!r}: 'loss' or 'acc'")
+        if int(patience) < 0 or not float(min_delta) >= 0.0:
+            raise NsdError(f"ModelBatchTrainer.track_best: patience {patience} / min_delta {min_delta}: both >= 0")
+        rule = dict(metric=metric, patience=int(patience), min_delta=float(min_delta))
+        if self._sel_rule is not None and rule != self._sel_rule:
+            raise NsdError(f"ModelBatchTrainer.track_best: the rule was {self._sel_rule}, now {rule}: one rule per trainer")
+        recs = self._held_out(x, y, counts, rule, "track_best")
+        self._sel_rule = rule
+        return recs
+
+    def _select_records(self) -> List[dict]:
+        if self._sel_state is None:
+            return [dict(best_loss=float("nan"), best_correct=0, best_n=0, best_eval=0, evals=0, bad=0, stopped=0, status=0)] * self.M
+        return ops.select_records(self._sel_state, self.M)
+
+    def stopped(self) -> List[bool]:
+        """Per model: has track_best marked it stopped (synchronises)."""
+        return [bool(r["stopped"]) for r in self._select_records()]
+
+    def all_stopped(self) -> bool:
+        return all(self.stopped())
+
+    def best_evals(self) -> List[int]:
+        """Per model: the 1-based number of its best track_best call, 0 where it has none yet (synchronises)."""
+        return [r["best_eval"] for r in self._select_records()]
+
+    def best_state_dict(self, m: int) -> dict:
+        """The state_dict of model m at its best evaluation, from the snapshot (copies; the model itself is not touched)."""
+        if self._sel_state is None or self.best_evals()[m] == 0:
+            raise NsdError(f"ModelBatchTrainer.best_state_dict: model {m} has no best evaluation yet (call track_best)")
+        row = ops.select_snapshot(self._sel_state, self.M, self.spec.param_count)[m]
+        offs = self.spec.offsets()
+        return {n: row[offs[n]:offs[n] + p.numel()].view(p.shape).clone() for n, p in self.models[m]._named_in_order()}
+
+    def restore_best(self) -> List[int]:
+        """Copy the snapshot row of every model that has a best evaluation back into self.params; returns best_evals().  The modules
+        stay views of their rows, so state_dict() and save_reference_checkpoint see the restored model.  Adam's m and v rows of a
+        restored model are zeroed: training on from a restored model restarts its moments (the snapshot holds parameters only)."""
+        best = self.best_evals()
+        if self._sel_state is not None:
+            snap = ops.select_snapshot(self._sel_state, self.M, self.spec.param_count)
+            with torch.no_grad():
+                for i, b in enumerate(best):
+                    if b > 0:
+                        self.params[i].copy_(snap[i])
+                        self.m[i].zero_()
+                        self.v[i].zero_()
+        return best
 
 
 class _EnsembleModel:

@@ -1368,6 +1368,117 @@ def head_fit(spec: ModelSpec, params: torch.Tensor, feats: torch.Tensor, targets
     return loss_out
 
 
+# ---- early stopping for model batches: metrics, the best-evaluation decision and the snapshot in one launch (nsd_multi_eval) ----
+
+EVAL_RECORD_BYTES, SELECT_RECORD_BYTES = C.sizeof(_lib.EvalRecord), C.sizeof(_lib.SelectRecord)      # 280, 40
+
+
+def multi_eval_path(M: int, B: int, K: int, P: int = 0) -> bool:
+    """True where nsd_multi_eval takes the shape (1 <= M <= 32, 1 <= K <= 8, B >= 1, M * B * K <= 2^31 - 1)."""
+    return bool(_lib.lib().nsd_multi_eval_path(int(M), int(B), int(K), int(P)))
+
+
+def select_records_bytes(M: int) -> int:
+    """Bytes of the M select records at the head of a select state, padded to 16: the snapshot rows [M, P] follow."""
+    return (int(M) * SELECT_RECORD_BYTES + 15) // 16 * 16
+
+
+def select_state_bytes(M: int, P: int) -> int:
+    n = int(_lib.lib().nsd_select_state_bytes(int(M), int(P)))
+    if n < 0:
+        check(n, "nsd_select_state_bytes")
+    return n
+
+
+def select_state(M: int, P: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The select state of M models of P parameters: records zeroed (nsd_select_state_init), snapshot rows [M, P] not yet written.
+    out: the caller's contiguous device bytes to initialise in place of a fresh buffer (select_state_bytes(M, P) of them)."""
+    n = select_state_bytes(M, P)
+    st = torch.empty(n, dtype=torch.uint8, device=device) if out is None else out
+    if st.dtype != torch.uint8 or not st.is_cuda or not st.is_contiguous() or st.numel() != n:
+        raise NsdError(f"select_state: out must be {n} contiguous bytes on the device")
+    _call("nsd_select_state_init", st.device, st.data_ptr(), _nbytes(st), int(M), int(P), STREAM)
+    return st
+
+
+def select_snapshot(state: torch.Tensor, M: int, P: int) -> torch.Tensor:
+    """The snapshot rows [M, P] of a select state: a float32 view, no copy.  A row is defined once its model has a best evaluation."""
+    off = select_records_bytes(M)
+    return state[off:off + 4 * int(M) * int(P)].view(torch.float32).view(int(M), int(P))
+
+
+def eval_buffer(M: int, device) -> torch.Tensor:
+    """An output buffer for multi_eval: M nsd_eval_record, as bytes."""
+    return torch.empty(int(M) * EVAL_RECORD_BYTES, dtype=torch.uint8, device=device)
+
+
+def multi_eval(logits: torch.Tensor, labels: torch.Tensor, *, counts=None, out: Optional[torch.Tensor] = None, select=None,
+               params: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The held-out metrics of M models in ONE launch: logits [M,B,K] fp32 (what multi_infer returns), labels [M,B] int32, counts: None or
+    M host ints -- only model m's first counts[m] rows count, the rest is padding that may hold anything.  Returns `out`, M
+    nsd_eval_record as device bytes (eval_records reads them).  select=dict(metric="loss" | "acc", patience=, min_delta=) with params
+    [M,P] and state (select_state(M, P)) also runs the early-stopping rule of include/nsd.h per model: the record update, the patience
+    count and the copy of an improved model's parameter row into the state's snapshot, all in that launch."""
+    if logits.dim() != 3:
+        raise NsdError(f"multi_eval: logits must be [M,B,K], got {tuple(logits.shape)}")
+    M, B, K = (int(v) for v in logits.shape)
+    if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous() or labels.numel() != M * B:
+        raise NsdError(f"multi_eval: labels must be contiguous int32 [M,B] = [{M},{B}] on the device")
+    cp = None
+    if counts is not None:
+        counts = [int(c) for c in counts]
+        if len(counts) != M:
+            raise NsdError(f"multi_eval: {len(counts)} counts for {M} models")
+        cp = (C.c_int32 * M)(*counts)
+    if out is None:
+        out = eval_buffer(M, logits.device)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() != M * EVAL_RECORD_BYTES:
+        raise NsdError(f"multi_eval: out must be {M * EVAL_RECORD_BYTES} contiguous bytes on the device")
+    sel, pp, P, sp, sbytes = None, None, 0, None, 0
+    if select is not None:
+        metric = select.get("metric", "loss")
+        if metric not in _lib.NSD_SELECT:
+            raise NsdError(f"multi_eval: metric {metric!r}: one of {sorted(_lib.NSD_SELECT)}")
+        if params is None or state is None or params.dim() != 2 or int(params.shape[0]) != M:
+            raise NsdError(f"multi_eval: selection needs params [M={M},P] and a select_state")
+        if state.dtype != torch.uint8 or not state.is_cuda or not state.is_contiguous():
+            raise NsdError("multi_eval: state must be the contiguous device bytes of select_state")
+        sel = C.byref(_lib.Select(_lib.NSD_SELECT[metric], int(select.get("patience", 0)), float(select.get("min_delta", 0.0))))
+        P = int(params.shape[1])
+        pp, sp, sbytes = _dev_f32(params, "params"), state.data_ptr(), _nbytes(state)
+    _call("nsd_multi_eval", logits.device, M, B, K, _dev_f32(logits, "logits"), labels.data_ptr(), cp, out.data_ptr(), sel, pp, P, sp, sbytes,
+          STREAM)
+    return out
+
+
+def _records(raw: torch.Tensor, M: int, struct, what: str):
+    """M C records at the head of a device byte buffer, in one device-to-host copy"""
+    n = int(M) * C.sizeof(struct)
+    if raw.dtype != torch.uint8 or raw.numel() < n:
+        raise NsdError(f"{what}: expected at least {n} bytes, got {raw.numel()} of {raw.dtype}")
+    return (struct * int(M)).from_buffer_copy(raw[:n].cpu().numpy().tobytes())
+
+
+def eval_records(out: torch.Tensor, M: int, K: int) -> List[dict]:
+    """The M records multi_eval wrote: [{loss_sum, loss (mean), acc, n, correct, nonfinite, confusion [K,K] numpy}] (one copy; synchronises)."""
+    import numpy as np
+    recs = []
+    for r in _records(out, M, _lib.EvalRecord, "eval_records"):
+        n = int(r.n)
+        recs.append(dict(loss_sum=float(r.loss_sum), loss=float(r.loss_sum) / n if n else float("nan"), acc=int(r.correct) / n if n else float("nan"),
+                         n=n, correct=int(r.correct), nonfinite=int(r.nonfinite),
+                         confusion=np.array([[r.confusion[i][j] for j in range(K)] for i in range(K)], dtype=np.int64)))
+    return recs
+
+
+def select_records(state: torch.Tensor, M: int) -> List[dict]:
+    """The M records at the head of a select state: [{best_loss, best_correct, best_n, best_eval, evals, bad, stopped, status}] (one copy;
+    synchronises)."""
+    return [dict(best_loss=float(r.best_loss), best_correct=int(r.best_correct), best_n=int(r.best_n), best_eval=int(r.best_eval),
+                 evals=int(r.evals), bad=int(r.bad), stopped=int(r.stopped), status=int(r.status))
+            for r in _records(state, M, _lib.SelectRecord, "select_records")]
+
+
 # ---- sliding-window decisions for continuous streams (nsd_window_* of include/nsd.h) ----
 
 def _window(window: int, hop: int) -> "_lib.Window":

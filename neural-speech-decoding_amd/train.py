@@ -38,17 +38,25 @@ def evaluate(model: EEG_LSTM, x: torch.Tensor, y: torch.Tensor, batch: int = 512
     return correct / max(int(x.shape[0]), 1)
 
 
-def concurrent_runs(y_np: np.ndarray, kfold: int, seeds: int, seed: int, batch: int):
+def concurrent_runs(y_np: np.ndarray, kfold: int, seeds: int, seed: int, batch: int, inner_fraction=None):
     """The runs of `--kfold K --concurrent [--kfold-seeds N]`: for seed i in 0..N-1 and fold f, run seed seed + i with the folds of
     D.stratified_folds(y, K, seed + i) and per-fold seed (seed + i) + 101 f -- exactly what `--kfold K --seed <seed + i>` trains one
     after another.  Refuses (ValueError, with the rule) what would change what a fold sees when the runs share one step: a fold with
-    fewer training windows than --batch, or folds that draw different numbers of batches per epoch."""
+    fewer training windows than --batch, or folds that draw different numbers of batches per epoch.
+    inner_fraction (early stopping): each run's training indices are split once more, D.stratified_split(y[tr], inner_fraction, the
+    run's seed): `tr` becomes the part the model is fitted on -- the checks above apply to it -- and `inner` the part its epochs are
+    compared on; `va`, the outer fold, is disjoint from both."""
     runs = []
     for i in range(seeds):
         s_i = seed + i
         for f, va in enumerate(D.stratified_folds(y_np, kfold, s_i)):
             tr = np.setdiff1d(np.arange(len(y_np)), va)
             runs.append(dict(seed_run=s_i, fold=f, tr=tr, va=va, seed=s_i + 101 * f))
+            if inner_fraction is not None:
+                fit_part, inner = D.stratified_split(y_np[tr], inner_fraction, s_i + 101 * f)
+                if len(inner) == 0:
+                    raise ValueError(f"--inner-fraction {inner_fraction}: fold {f} (seed {s_i}) gets an empty inner split")
+                runs[-1].update(tr=tr[fit_part], inner=tr[inner])
     if len(runs) > 32:
         raise ValueError(f"--concurrent: {len(runs)} runs (--kfold-seeds x --kfold) but one launch takes at most 32 models")
     for r in runs:
@@ -71,6 +79,50 @@ def concurrent_epoch(runs, batch: int, epoch: int, step) -> int:
         step(list(idxs))
         n += 1
     return n
+
+
+EARLY_STOP_OPTIONS = ("early_stop_patience", "early_stop_metric", "early_stop_min_delta", "inner_fraction")
+
+
+def early_stop_settings(args, concurrent: bool):
+    """None where none of --early-stop-patience / --early-stop-metric / --early-stop-min-delta / --inner-fraction is given, else
+    dict(metric, patience, min_delta, inner_fraction) with the defaults filled in.  ValueError, with the rule, for the options without
+    the model-batched runs they need, without a patience, or out of range."""
+    given = [o for o in EARLY_STOP_OPTIONS if getattr(args, o, None) is not None]
+    if not given:
+        return None
+    flag = "--" + given[0].replace("_", "-")
+    if not concurrent:
+        raise ValueError(f"{flag}: early stopping runs on the model-batched folds: give --kfold K --concurrent (or use nsd_amd.grid)")
+    if args.early_stop_patience is None:
+        raise ValueError(f"{flag} needs --early-stop-patience N (N evaluations without improvement stop a model; 0: keep the best epoch, "
+                         "never stop)")
+    if args.early_stop_patience < 0:
+        raise ValueError(f"--early-stop-patience {args.early_stop_patience} negative")
+    min_delta = 0.0 if args.early_stop_min_delta is None else args.early_stop_min_delta
+    if not min_delta >= 0.0:
+        raise ValueError(f"--early-stop-min-delta {min_delta} negative")
+    f = 0.2 if args.inner_fraction is None else args.inner_fraction
+    if not 0.0 < f <= 0.5:
+        raise ValueError(f"--inner-fraction {f} outside (0, 0.5]")
+    return dict(metric=args.early_stop_metric or "loss", patience=args.early_stop_patience, min_delta=min_delta, inner_fraction=f)
+
+
+def selection_text(es) -> str:
+    """The `selection` field of a result: what picked the scored model"""
+    if es is None:
+        return "none: fixed epoch count, last-epoch model"
+    return f"inner split: early stopping on {es['metric']}, patience {es['patience']}"
+
+
+def padded_parts(x_all: torch.Tensor, y_all: torch.Tensor, parts):
+    """The windows of M index arrays of unequal length as one [M,Bmax,T,C] / [M,Bmax] pair for ModelBatchTrainer.evaluate /
+    track_best, and the counts: part m is padded with its own first window, which counts nowhere."""
+    counts = [int(len(p)) for p in parts]
+    bmax = max(counts)
+    idx = np.stack([np.concatenate([np.asarray(p, dtype=np.int64), np.full(bmax - len(p), p[0], dtype=np.int64)]) for p in parts])
+    it = torch.from_numpy(idx).to(x_all.device)
+    return x_all[it].contiguous(), y_all[it].contiguous(), counts
 
 
 def balanced_class_weights(y: np.ndarray, K: int):
@@ -170,6 +222,16 @@ def build_parser() -> argparse.ArgumentParser:
                                                                             "starting variance is calibrated on the training split (with --concurrent: on all trials)")
     ap.add_argument("--prep-car", action="store_true", help="causal front end: common-average reference")
     ap.add_argument("--prep-no-baseline", action="store_true", help="causal front end: do not subtract each window's first sample")
+    ap.add_argument("--early-stop-patience", type=int, default=None,
+                    help="with --kfold K --concurrent: early stopping per fold on an inner split of its training trials -- after every epoch "
+                         "all folds are scored on their inner parts in two launches, each keeps the parameters of its best epoch on the "
+                         "device and stops counting after N epochs without improvement (0: keep the best epoch, never stop); the outer "
+                         "fold is scored once, at the end, with the best-epoch models")
+    ap.add_argument("--early-stop-metric", default=None, choices=("loss", "acc"), help="early stopping: what is compared on the inner split "
+                                                                                      "(default loss; acc: ties go to the lower loss)")
+    ap.add_argument("--early-stop-min-delta", type=float, default=None, help="early stopping: an epoch is better only by more than this (default 0)")
+    ap.add_argument("--inner-fraction", type=float, default=None, help="early stopping: share of each fold's training trials held out as its "
+                                                                       "inner split, in (0, 0.5] (default 0.2)")
     return ap
 
 
@@ -225,6 +287,11 @@ def main(argv=None) -> int:
         if args.precision != "fp32" or args.bidirectional or args.hidden != 48:
             ap.error("--concurrent: the model-batched path is H = 48 fp32 (--hidden 48, --precision fp32, no --bidirectional)")
 
+    try:
+        es = early_stop_settings(args, concurrent=args.concurrent and args.kfold >= 2)
+    except ValueError as e:
+        ap.error(str(e))
+
     rank, local, world = init_distributed()
     if not torch.cuda.is_available():
         print("train: needs an MI355X (no CPU training path)", file=sys.stderr)
@@ -268,7 +335,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if k != "save_folds" or v}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS or v is not None)}
 
     fold_paths = []
 
@@ -315,7 +382,7 @@ def main(argv=None) -> int:
             print("train: --concurrent runs on one GPU (the model-batched path has no data parallel)", file=sys.stderr)
             return 2
         try:
-            runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch)
+            runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch, es["inner_fraction"] if es else None)
         except ValueError as e:
             print(f"train: {e}", file=sys.stderr)
             return 2
@@ -339,28 +406,48 @@ def main(argv=None) -> int:
 
         def tag(r):
             return f"fold{r['fold']}" if args.kfold_seeds == 1 else f"seed{r['seed_run']}_fold{r['fold']}"
+        if es:       # the held-out sets of all folds, padded to one B each (folds differ in size by one): built once
+            held = {part: padded_parts(x_all, y_all, [r[part] for r in runs]) for part in ("tr", "inner", "va")}
         for epoch in range(args.epochs):
             concurrent_epoch(runs, args.batch, epoch, step)
             last = epoch == args.epochs - 1
+            if es:   # every epoch: all folds on their inner parts, the best-epoch decision and the snapshot, in two launches
+                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"])
+                last = last or all(e["stopped"] for e in inner)
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
                 norms, lr_now, skipped = (mbt.last_grad_norms(), mbt.last_lr(), mbt.skipped_steps()) if opt_on else (None, None, None)
+                if es:
+                    ev_tr, ev_va = mbt.evaluate(*held["tr"]), mbt.evaluate(*held["va"])
                 for k, r in enumerate(runs):
-                    acc_tr = evaluate(models[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
-                    acc_va = evaluate(models[k], x_all[r["va"]], y_all[r["va"]])
+                    if es:
+                        acc_tr, acc_va = ev_tr[k]["acc"], ev_va[k]["acc"]
+                    else:
+                        acc_tr = evaluate(models[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
+                        acc_va = evaluate(models[k], x_all[r["va"]], y_all[r["va"]])
                     res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
                     emit({"run": tag(r), "epoch": epoch, "loss_last_batch": round(losses[k], 5), "acc_train": round(acc_tr, 4),
                           "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
-                          **({"grad_norm": norms[k], "lr": lr_now, "skipped": skipped[k]} if opt_on else {})})
+                          **({"grad_norm": norms[k], "lr": lr_now, "skipped": skipped[k]} if opt_on else {}),
+                          **({"loss_inner": round(inner[k]["loss"], 5), "acc_inner": round(inner[k]["acc"], 4),
+                              "best_epoch": inner[k]["best_eval"] - 1, "stopped": inner[k]["stopped"]} if es else {})})
+            if es and last:
+                break
+        if es:       # the outer folds, looked at for the first time as far as the models are concerned: the best-epoch models, one call
+            best = mbt.restore_best()
+            final = mbt.evaluate(*held["va"])
         accs = []
         for k, r in enumerate(runs):
-            accs.append(res[k]["acc_val_last"])
+            accs.append(final[k]["acc"] if es else res[k]["acc_val_last"])
             if args.save_folds:
                 fold_paths.append(fold_path(tag(r)))
                 save_reference_checkpoint(models[k], fold_paths[-1])
             rec = {"fold": r["fold"], "n_train": int(len(r["tr"])), "n_val": int(len(r["va"])),
                    "acc_val_last_epoch": round(res[k]["acc_val_last"], 4), "acc_train_last_epoch": round(res[k]["acc_train_last"], 4),
                    "concurrent": True}
+            if es:
+                rec.update(n_inner=int(len(r["inner"])), best_epoch=best[k] - 1, acc_val_best_epoch=round(final[k]["acc"], 4),
+                           loss_val_best_epoch=round(final[k]["loss"], 5), confusion_val=final[k]["confusion"].tolist())
             if args.kfold_seeds > 1:
                 rec["seed"] = r["seed_run"]
             emit(rec)
@@ -368,7 +455,8 @@ def main(argv=None) -> int:
         r = fit(everything, everything[:0], args.seed + 7777, "all", args.out, keep_best=False)
         emit({"done": True, "kfold": args.kfold, "kfold_seeds": args.kfold_seeds, "acc_val_mean": round(float(np.mean(accs)), 4),
               "acc_val_sd": round(float(np.std(accs, ddof=1)), 4),
-              "acc_val_folds": [round(float(a), 4) for a in accs], "selection": "none: fixed epoch count, last-epoch model",
+              "acc_val_folds": [round(float(a), 4) for a in accs], "selection": selection_text(es),
+              **({"best_epochs": [b - 1 for b in best], "epochs_run": epoch + 1} if es else {}),
               "shipped": {"checkpoint": args.out, "trained_on": int(len(everything)), "acc_train_last_epoch": r["acc_train_last"]},
               "world": world, "concurrent": True, "args": shown_args(), **done_extra()})
         return 0
