@@ -475,6 +475,59 @@ int nsd_multi_grad_reduce_clip_adam_each(const nsd_dims *d, int32_t M, const flo
                                          void *opt_state, int64_t opt_state_bytes, void *stream);
 
 /*
+ * ---- weight averaging in the step tail: EMA / SWA of the parameters, formed by the update launch (an EXTENSION) ----
+ *
+ * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_avg_state_bytes).  Each `_avg` entry point is the twin of
+ * the one it is named after, with `avg, avg_state, avg_state_bytes` appended; its launch count is the twin's (two for the fused tails,
+ * one for the flat update): the average is formed by the update kernel in the iteration that stores p[i].  p, m, v, grads and the
+ * nsd_opt_record are bit for bit what the twin leaves.  No existing entry point changes its launches or its bits.
+ * avg_state (device, caller-owned, nsd_avg_state_bytes(n_or_P, M) bytes): M records nsd_avg_record, then the averaged rows [M][n_or_P]
+ * (fp32) from byte 16 * M.  nsd_avg_state_init zeroes the M records and nothing else; a row may hold anything until its model's first
+ * averaged step, which overwrites all of it.
+ * The rule, per model, at Adam step s (1-based; the host `step`, or step_dev's value where that is given, as the schedule reads it):
+ *   a skipped update (non-finite norm, or the caller's skip flag)           row and n_avg untouched
+ *   s < start_step, or (s - start_step) % every != 0                        row and n_avg untouched
+ *   otherwise, n = n_avg as it stood before the launch and p' the new parameter:
+ *     n == 0          a = p'  (a copy of the word)
+ *     NSD_AVG_EMA     a' = a + w * (p' - a),  w = 1.0f - decay in fp32
+ *     NSD_AVG_SWA     a' = a + (p' - a) / (float)(n + 1)                     (torch.optim.swa_utils.AveragedModel's default)
+ *     then n_avg = n + 1
+ * Every fp32 operation is rounded once (no contraction); the division is IEEE.
+ * The counter.  The launch has no order between workgroups, and every workgroup of a model needs n as it stood BEFORE the launch.  So
+ * every workgroup reads n_avg first and then adds 1 to `arrive`; the workgroup that sees gridDim.x - 1 is the last one, and it alone
+ * writes n_avg = n + 1 and arrive = 0.  Nobody waits for anybody.  The four accesses are relaxed device-scope atomics; there is no
+ * device-scope fence per workgroup (nothing is published from one workgroup to another inside the launch; a workgroup holds the value
+ * of its read before it arrives).  `arrive` reads 0 between launches.  The `_avg` twins may launch fewer workgroups per model than
+ * their twins (every workgroup arrives once): the results do not depend on the grid.
+ *   nsd_multi_grad_reduce_clip_adam_avg       one nsd_avg for all M models
+ *   nsd_multi_grad_reduce_clip_adam_avg_each  opt AND avg point to M entries; avg[m].mode == 0: model m does not average (its row and
+ *                                             record are never touched)
+ *   nsd_adam_step_clip_avg                    the flat route (world > 1 after the all-reduce; the bf16 sequence path with its skip flag)
+ * NSD_E_INVALID before any launch (the `_each` twin names the entry, "...: avg[2]: decay ..."): the twin's refusals; NULL avg or avg_state;
+ * mode outside {NSD_AVG_EMA, NSD_AVG_SWA} (0 also allowed inside `_each`); for EMA decay outside [0, 1) or NaN (ignored for SWA);
+ * start_step < 1; every < 1.  NSD_E_WORKSPACE: avg_state_bytes < nsd_avg_state_bytes.
+ */
+#define NSD_AVG_EMA 1
+#define NSD_AVG_SWA 2
+typedef struct nsd_avg { int32_t mode; float decay; int32_t start_step; int32_t every; } nsd_avg;
+typedef struct nsd_avg_record { uint32_t n_avg; uint32_t arrive; uint32_t pad[2]; } nsd_avg_record;   /* 16 B per model, first bytes of avg_state */
+int64_t nsd_avg_state_bytes(int64_t n_or_P, int32_t M);
+int nsd_avg_state_init(void *avg_state, int64_t avg_state_bytes, int32_t M, void *stream);
+int nsd_grad_reduce_clip_adam_avg(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, float *p, float *m, float *v,
+                                  const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state, int64_t opt_state_bytes, void *stream,
+                                  const nsd_avg *avg, void *avg_state, int64_t avg_state_bytes);
+int nsd_multi_grad_reduce_clip_adam_avg(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
+                                        float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state,
+                                        int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state, int64_t avg_state_bytes);
+int nsd_multi_grad_reduce_clip_adam_avg_each(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads,
+                                             float *p, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                                             void *opt_state, int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state,
+                                             int64_t avg_state_bytes);
+int nsd_adam_step_clip_avg(int64_t n, float *p, const float *g, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                           const float *skip, void *opt_state, int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state,
+                           int64_t avg_state_bytes);
+
+/*
  * ---- early stopping for model batches: held-out metrics, the best-evaluation decision and the snapshot in ONE launch (an EXTENSION) ----
  *
  * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_multi_eval_path).  nsd_multi_eval reads the logits of M

@@ -58,6 +58,14 @@ class OptRecord(C.Structure):
 NSD_SCHED = {"constant": 0, "cosine": 1, "step": 2}
 
 
+class Avg(C.Structure):
+    """nsd_avg of include/nsd.h"""
+    _fields_ = [("mode", C.c_int32), ("decay", C.c_float), ("start_step", C.c_int32), ("every", C.c_int32)]
+
+
+NSD_AVG = {"ema": 1, "swa": 2}
+
+
 class NsdError(RuntimeError):
     pass
 
@@ -219,6 +227,15 @@ SYMBOLS = {
     "nsd_augment_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _vp, _vp, _vp, C.c_uint32, _fp, _vp]),
     "nsd_mixup_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _ip, _fp, _vp, _vp, _vp, _fp, _fp, _vp]),
     "nsd_multi_grad_reduce_clip_adam_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
+    # weight averaging in the update launch: each `_avg` twin takes its twin's arguments, then avg, avg_state, avg_state_bytes
+    "nsd_avg_state_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "nsd_avg_state_init": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp]),
+    "nsd_grad_reduce_clip_adam_avg": (C.c_int, [_dp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "nsd_adam_step_clip_avg": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _fp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "nsd_multi_grad_reduce_clip_adam_avg": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp,
+                                                      _vp, _vp, C.c_int64]),
+    "nsd_multi_grad_reduce_clip_adam_avg_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp,
+                                                           _vp, _vp, C.c_int64]),
     "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
     "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),
     # early stopping for model batches: metrics, the best-evaluation decision and the snapshot in one launch

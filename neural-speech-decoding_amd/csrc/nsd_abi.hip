@@ -656,6 +656,60 @@ int nsd_adam_step_clip(int64_t n, float *p, const float *g, float *m, float *v, 
     return nsd_adam_clip_flat_launch(n, p, g, m, v, opt, step, (const long long *)step_dev, skip, opt_state, (hipStream_t)stream);
 }
 
+// ---- weight averaging in the update launch (nsd_avg, include/nsd.h; nsd_optim.hip) ----------------------------------------------------
+// refusals of the `_avg` twins, before any launch: the fields of avg (each: M entries, mode 0 allowed, the entry named), then avg_state
+static int avg_enter(const char *who, const nsd_avg *avg, int each, const void *state, int64_t bytes, int64_t n, int M) {
+    if (!avg) { nsd_set_error("%s: avg is NULL", who); return NSD_E_INVALID; }
+    for (int mo = 0; mo < (each ? M : 1); ++mo) {
+        char entry[64];
+        snprintf(entry, sizeof(entry), "%s: avg[%d]", who, mo);
+        if (const int rc = nsd_avg_check(&avg[mo], each ? entry : who, each)) return rc;
+    }
+    if (!state) { nsd_set_error("%s: avg_state is NULL", who); return NSD_E_INVALID; }
+    const int64_t need = nsd_avg_state_need(n, M);
+    if (bytes < need) {
+        nsd_set_error("%s: avg_state of %lld bytes is smaller than nsd_avg_state_bytes() = %lld", who, (long long)bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int64_t nsd_avg_state_bytes(int64_t n_or_P, int32_t M) {
+    if (n_or_P < 0 || M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("avg_state_bytes: n = %lld, M = %d (n >= 0, 1 <= M <= %d)", (long long)n_or_P, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    return nsd_avg_state_need(n_or_P, M);
+}
+
+int nsd_avg_state_init(void *avg_state, int64_t avg_state_bytes, int32_t M, void *stream) {
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("avg_state_init: M = %d (1 <= M <= %d)", M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (!avg_state || avg_state_bytes < (int64_t)M * (int64_t)sizeof(nsd_avg_record)) { nsd_set_error("avg_state_init: avg_state is NULL or shorter than %d records", M); return NSD_E_INVALID; }
+    return nsd_opt_state_init_launch(avg_state, (int64_t)M * (int64_t)sizeof(nsd_avg_record), (hipStream_t)stream);    // the records only
+}
+
+int nsd_grad_reduce_clip_adam_avg(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, float *p, float *m, float *v,
+                                  const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state, int64_t opt_state_bytes, void *stream,
+                                  const nsd_avg *avg, void *avg_state, int64_t avg_state_bytes) {
+    static const char *who = "grad_reduce_clip_adam_avg";
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (!workspace || !grads || !p || !m || !v) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, layout_of(d).total, 1)) return rc;
+    if (const int rc = avg_enter(who, avg, 0, avg_state, avg_state_bytes, layout_of(d).total, 1)) return rc;
+    Ctx c;
+    if (const int rc = enter(&c, who, d, true, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
+    const NsdAvgSpec as{avg, 0, avg_state};
+    return nsd_reduce_clip_adam_launch(slab_set(c), 1, grads, p, m, v, opt, 0, step, (const long long *)step_dev, opt_state, who, c.st, &as);
+}
+
+int nsd_adam_step_clip_avg(int64_t n, float *p, const float *g, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                           const float *skip, void *opt_state, int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state,
+                           int64_t avg_state_bytes) {
+    static const char *who = "adam_step_clip_avg";
+    if (n < 0 || !p || !g || !m || !v) { nsd_set_error("%s: null pointer or n<0", who); return NSD_E_INVALID; }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, n, 1)) return rc;
+    if (const int rc = avg_enter(who, avg, 0, avg_state, avg_state_bytes, n, 1)) return rc;
+    const NsdAvgSpec as{avg, 0, avg_state};
+    return nsd_adam_clip_flat_launch(n, p, g, m, v, opt, step, (const long long *)step_dev, skip, opt_state, (hipStream_t)stream, &as);
+}
+
 int nsd_train_masks(uint64_t seed, uint32_t base_stream, float p_lstm, float p_head, int64_t n_lstm, float *drop_lstm,
                     int64_t n_head, float *rrelu_slope, float *drop_head, void *stream) {
     if (n_lstm < 0 || n_head < 0 || (n_lstm > 0 && !drop_lstm) || (n_head > 0 && (!rrelu_slope || !drop_head))) {
@@ -998,6 +1052,46 @@ int nsd_multi_grad_reduce_clip_adam_each(const nsd_dims *d, int32_t M, const flo
     if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
     if (M == 1) return nsd_grad_reduce_clip_adam(d, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state, opt_state_bytes, stream);
     return nsd_reduce_clip_adam_launch(slab_set(c), M, grads, p, m, v, opt, 1, step, (const long long *)step_dev, opt_state, who, c.st);
+}
+
+// the `_avg` twins of the two above (each: opt AND avg have M entries; an entry with mode 0 does not average)
+static int multi_clip_adam_avg(const char *who, int each, const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads,
+                               float *p, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state,
+                               int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state, int64_t avg_state_bytes) {
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!grads || !p || !m || !v) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (!opt) { nsd_set_error("%s: opt is NULL", who); return NSD_E_INVALID; }
+    for (int mo = 0; each && mo < M; ++mo) {
+        char entry[64];
+        snprintf(entry, sizeof(entry), "%s: opt[%d]", who, mo);
+        if (const int rc = nsd_opt_check(&opt[mo], entry)) return rc;
+    }
+    if (const int rc = opt_enter(who, opt, step, step_dev, opt_state, opt_state_bytes, layout_of(d).total, M)) return rc;
+    if (const int rc = avg_enter(who, avg, each, avg_state, avg_state_bytes, layout_of(d).total, M)) return rc;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
+    if (M == 1) {
+        if (avg[0].mode == 0) return nsd_grad_reduce_clip_adam(d, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state, opt_state_bytes, stream);
+        return nsd_grad_reduce_clip_adam_avg(d, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state, opt_state_bytes, stream, avg,
+                                             avg_state, avg_state_bytes);
+    }
+    const NsdAvgSpec as{avg, each, avg_state};
+    return nsd_reduce_clip_adam_launch(slab_set(c), M, grads, p, m, v, opt, each, step, (const long long *)step_dev, opt_state, who, c.st, &as);
+}
+
+int nsd_multi_grad_reduce_clip_adam_avg(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, float *p,
+                                        float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev, void *opt_state,
+                                        int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state, int64_t avg_state_bytes) {
+    return multi_clip_adam_avg("multi_grad_reduce_clip_adam_avg", 0, d, M, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev, opt_state,
+                               opt_state_bytes, stream, avg, avg_state, avg_state_bytes);
+}
+
+int nsd_multi_grad_reduce_clip_adam_avg_each(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads,
+                                             float *p, float *m, float *v, const nsd_opt *opt, int32_t step, const int64_t *step_dev,
+                                             void *opt_state, int64_t opt_state_bytes, void *stream, const nsd_avg *avg, void *avg_state,
+                                             int64_t avg_state_bytes) {
+    return multi_clip_adam_avg("multi_grad_reduce_clip_adam_avg_each", 1, d, M, workspace, workspace_bytes, grads, p, m, v, opt, step, step_dev,
+                               opt_state, opt_state_bytes, stream, avg, avg_state, avg_state_bytes);
 }
 
 int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {

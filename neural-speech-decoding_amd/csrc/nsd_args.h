@@ -187,11 +187,17 @@ int nsd_opt_check(const nsd_opt *o, const char *who);
 double nsd_lr_factor_host(const nsd_opt *o, long long step);
 int64_t nsd_opt_state_need(int64_t n, int M);
 int nsd_opt_state_init_launch(void *state, int64_t bytes, hipStream_t st);
+// weight averaging in the update launch (nsd_avg of nsd.h): avg already through nsd_avg_check, state against nsd_avg_state_need.
+// each: avg has M entries.  A null NsdAvgSpec is the launch without averaging
+struct NsdAvgSpec { const nsd_avg *avg; int each; void *state; };
+int nsd_avg_check(const nsd_avg *a, const char *who, int allow_off);
+int64_t nsd_avg_state_need(int64_t n, int M);
 int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int each, int step,
-                                const long long *step_dev, void *state, const char *who, hipStream_t st);   // each: o has M entries
+                                const long long *step_dev, void *state, const char *who, hipStream_t st,
+                                const NsdAvgSpec *as = nullptr);   // each: o has M entries
 int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st);
 int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float *v, const nsd_opt *o, int step, const long long *step_dev,
-                              const float *skip, void *state, hipStream_t st);
+                              const float *skip, void *state, hipStream_t st, const NsdAvgSpec *as = nullptr);
 int nsd_seq_guard_launch(const int *header, int status_word, float *flag_out, hipStream_t st);
 int nsd_dropout_mask_launch(uint64_t seed, uint32_t stream_id, float p, long n, float *out, hipStream_t st);
 int nsd_train_masks_launch(uint64_t seed, uint32_t base, const long long *step_dev, float p_lstm, float p_head, long n_lstm,

@@ -7,9 +7,17 @@
 //      sums, and with them the skip decision, are identical in every workgroup), forms coef, the schedule factor and the bias
 //      corrections in double, then updates its elements; workgroup 0 of a model writes the model's record.
 // A ticket counter whose last reduction workgroup finishes the update alone was weighed and not built.
+// Weight averaging (nsd_avg of include/nsd.h) rides in launch 2: adam_clip_avg_kernel is the same update body with the averaged row formed
+// in the iteration that stores p[i].  Every workgroup of a model reads n_avg before it works and then adds 1 to `arrive`; the one that
+// sees gridDim.x - 1 is the last and alone writes n_avg + 1 and arrive = 0.  Nobody waits.  All four accesses are relaxed device-scope
+// atomics and there is NO device-scope fence per workgroup: no workgroup publishes data to another inside the launch, the only order
+// needed is "my read of n_avg, then my arrival", and thread 0 holds the read's value (it has handed it round through LDS, behind a
+// barrier) before it issues the add.  A __threadfence() in front of every add was measured at +72 us on the update of 25 models (an L2
+// write-back per workgroup), and 3125 arrivals on one cache line at +16 us, hence the smaller grid (profiles/weight_averaging.md).
 #include <math.h>
 #include <float.h>
 #include <string.h>
+#include <type_traits>
 #include "nsd_args.h"
 
 // ---- schedule factor f(s), double: the same expression on the host (nsd_lr_factor, host-step launches) and on the device (step_dev) ----
@@ -173,9 +181,20 @@ struct OptKSet { OptK k[NSD_MAX_MODELS]; };
 static_assert(sizeof(OptKSet) <= 2560, "the per-model optimizer block stays well inside the 4 KB kernarg segment");
 __device__ __forceinline__ const OptK &opt_of(const OptK &k, long) { return k; }
 __device__ __forceinline__ const OptK &opt_of(const OptKSet &k, long mo) { return k.k[mo]; }
-template <class OK>
-__global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, const float *g, float *m, float *v, OK ok,
-                                                            const double *parts, int n_parts, nsd_opt_record *rec, const float *skip) {
+// weight averaging (nsd_avg): per model by value next to OptK.  NoAvg: the plain update, whose instructions the averaging twin leaves alone
+struct AvgK { int mode; float w; int start, every; };                 // w = 1.0f - decay, formed once on the host in fp32
+struct AvgKSet { AvgK k[NSD_MAX_MODELS]; };
+static_assert(sizeof(OptKSet) + sizeof(AvgKSet) <= 3072, "optimizer and averaging blocks together stay inside the 4 KB kernarg segment");
+struct NoAvg {};
+struct AvgArgs1 { AvgK k; int step; nsd_avg_record *rec; float *rows; };        // step: the host step (ignored with step_dev)
+struct AvgArgsM { AvgKSet k; int step; nsd_avg_record *rec; float *rows; };
+__device__ __forceinline__ const AvgK &avg_of(const AvgArgs1 &a, long) { return a.k; }
+__device__ __forceinline__ const AvgK &avg_of(const AvgArgsM &a, long mo) { return a.k.k[mo]; }
+
+template <class OK, class AV>
+__device__ __forceinline__ void adam_clip_body(long n, float *p, const float *g, float *m, float *v, const OK &ok, const double *parts,
+                                               int n_parts, nsd_opt_record *rec, const float *skip, const AV &av) {
+    constexpr bool AVG = !std::is_same<AV, NoAvg>::value;
     if (skip != nullptr && skip[0] != 0.f) return;                    // the caller's guard: nothing is written, the record included
     const long mo = blockIdx.y;
     const OptK &o = opt_of(ok, mo);
@@ -202,6 +221,24 @@ __global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, co
         if (!finite) rec->skipped += 1u;                               // one writer per model: no atomic
     }
     if (!finite) return;                                               // uniform over the grid: every workgroup formed the same S
+    // averaging: does this step average (uniform over the model's workgroups: s and the settings are), and n_avg as it stood before
+    // the launch.  Thread 0 reads the word and hands it round through LDS, so it holds the value before this workgroup arrives.
+    bool averaging = false;
+    unsigned n0 = 0u;
+    float *row = nullptr;
+    nsd_avg_record *arec = nullptr;
+    if constexpr (AVG) {
+        const AvgK &a = avg_of(av, mo);
+        const long long s = o.step_dev != nullptr ? o.step_dev[0] : (long long)av.step;
+        averaging = a.mode != 0 && s >= a.start && (s - a.start) % a.every == 0;
+        if (averaging) {
+            __shared__ unsigned n_sh;
+            arec = av.rec + mo; row = av.rows + mo * n;
+            if (threadIdx.x == 0) n_sh = __hip_atomic_load(&arec->n_avg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            n0 = n_sh;
+        }
+    }
     for (long i = (long)blockIdx.x * FLAT_NT + threadIdx.x; i < n; i += (long)gridDim.x * FLAT_NT) {
         const float pi = p[i];                                         // the arithmetic of adam_kernel, in its order
         const float gi = fmaf(o.wd, pi, (g[i] * o.gscale) * coef);
@@ -209,8 +246,38 @@ __global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, co
         const float vi = o.b2 * v[i] + (1.f - o.b2) * gi * gi;
         m[i] = mi; v[i] = vi;
         const float denom = sqrtf(vi) * rsqrt_bc2 + o.eps;
-        p[i] = pi - lr_over_bc1 * (mi / denom);
+        const float pn = pi - lr_over_bc1 * (mi / denom);
+        p[i] = pn;
+        if constexpr (AVG) {
+            if (averaging) {
+                if (n0 == 0u) row[i] = pn;                             // the first averaged step copies the word
+                else {
+                    const AvgK &a = avg_of(av, mo);
+                    const float ai = row[i], dlt = pn - ai;            // each operation rounded once (-ffp-contract=off)
+                    row[i] = a.mode == NSD_AVG_EMA ? ai + a.w * dlt : ai + dlt / (float)(n0 + 1u);
+                }
+            }
+        }
     }
+    if constexpr (AVG) {
+        // last arriver: no workgroup waits for another.  (The rows are nobody's input in this launch: the arrival says "I have read
+        // n_avg", not "I have written my elements".)
+        if (averaging && threadIdx.x == 0 &&
+            __hip_atomic_fetch_add(&arec->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+            __hip_atomic_store(&arec->n_avg, n0 + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&arec->arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+template <class OK>
+__global__ __launch_bounds__(FLAT_NT) void adam_clip_kernel(long n, float *p, const float *g, float *m, float *v, OK ok,
+                                                            const double *parts, int n_parts, nsd_opt_record *rec, const float *skip) {
+    adam_clip_body(n, p, g, m, v, ok, parts, n_parts, rec, skip, NoAvg{});
+}
+template <class OK, class AV>
+__global__ __launch_bounds__(FLAT_NT) void adam_clip_avg_kernel(long n, float *p, const float *g, float *m, float *v, OK ok,
+                                                                const double *parts, int n_parts, nsd_opt_record *rec, const float *skip, AV av) {
+    adam_clip_body(n, p, g, m, v, ok, parts, n_parts, rec, skip, av);
 }
 
 static OptK opt_kernel_args(const nsd_opt *o, int step, const long long *step_dev) {
@@ -228,27 +295,78 @@ static OptK opt_kernel_args(const nsd_opt *o, int step, const long long *step_de
     return k;
 }
 
+static AvgK avg_kernel_args(const nsd_avg *a) {
+    AvgK k;
+    memset(&k, 0, sizeof(k));
+    k.mode = a->mode; k.w = a->mode == NSD_AVG_EMA ? 1.0f - a->decay : 0.f; k.start = a->start_step; k.every = a->every;
+    if (k.mode == 0) { k.start = 1; k.every = 1; }
+    return k;
+}
+template <class AV> static void avg_fill(AV *av, int M, const NsdAvgSpec *as, int step) {
+    memset(av, 0, sizeof(*av));
+    av->step = step; av->rec = (nsd_avg_record *)as->state;
+    av->rows = reinterpret_cast<float *>(static_cast<char *>(as->state) + (size_t)M * sizeof(nsd_avg_record));
+}
+
+// as: null -- the plain update kernel, as before averaging existed; else its averaging twin with the model's (models') settings
 template <class OK>
 static int adam_clip_launch(long n, int M, float *p, const float *g, float *m, float *v, const OK &k, long n_parts, void *state,
-                            const float *skip, const char *who, hipStream_t st) {
+                            const float *skip, const char *who, hipStream_t st, const NsdAvgSpec *as = nullptr, int step = 0) {
     long blocks = (n + FLAT_NT - 1) / FLAT_NT; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adam_clip_kernel<OK>, dim3((unsigned)blocks, (unsigned)M), dim3(FLAT_NT), 0, st, n, p, g, m, v, k,
-                       (const double *)parts_of(state, M), (int)n_parts, (nsd_opt_record *)state, skip);
+    // averaging: every workgroup arrives once on its model's record, and the records of all models share a few cache lines, so the
+    // arrivals of a launch queue up behind each other: a grid-stride loop over fewer workgroups per model, about one per CU in all,
+    // more only where a thread would otherwise take more than 8 elements (large flat vectors: there the memory traffic dominates).
+    // The results do not depend on the grid: the update is element-wise and the partials are summed in the order of their index.
+    if (as) {
+        long cap = 256 / M > 32 ? 256 / M : 32;
+        const long by_work = (n + 8 * FLAT_NT - 1) / (8 * FLAT_NT);
+        if (by_work > cap) cap = by_work;
+        if (blocks > cap) blocks = cap;
+    }
+    const dim3 grid((unsigned)blocks, (unsigned)M);
+    const double *parts = parts_of(state, M);
+    if (!as) {
+        hipLaunchKernelGGL(adam_clip_kernel<OK>, grid, dim3(FLAT_NT), 0, st, n, p, g, m, v, k, parts, (int)n_parts, (nsd_opt_record *)state, skip);
+    } else if constexpr (std::is_same<OK, OptK>::value) {
+        AvgArgs1 av;
+        avg_fill(&av, M, as, step);
+        av.k = avg_kernel_args(as->avg);
+        hipLaunchKernelGGL((adam_clip_avg_kernel<OK, AvgArgs1>), grid, dim3(FLAT_NT), 0, st, n, p, g, m, v, k, parts, (int)n_parts,
+                           (nsd_opt_record *)state, skip, av);
+    } else {
+        AvgArgsM av;
+        avg_fill(&av, M, as, step);
+        for (int mo = 0; mo < M; ++mo) av.k.k[mo] = avg_kernel_args(as->each ? as->avg + mo : as->avg);
+        hipLaunchKernelGGL((adam_clip_avg_kernel<OK, AvgArgsM>), grid, dim3(FLAT_NT), 0, st, n, p, g, m, v, k, parts, (int)n_parts,
+                           (nsd_opt_record *)state, skip, av);
+    }
     NSD_CHECK_LAUNCH(who);
     return NSD_OK;
 }
 
+// nsd_avg's fields: 0, or the NSD_E_INVALID refusal with the field named.  allow_off: mode 0 passes (an entry of the `_each` twin)
+int nsd_avg_check(const nsd_avg *a, const char *who, int allow_off) {
+    if (!a) { nsd_set_error("%s: avg is NULL", who); return NSD_E_INVALID; }
+    if (a->mode == 0 && allow_off) return NSD_OK;
+    if (a->mode != NSD_AVG_EMA && a->mode != NSD_AVG_SWA) { nsd_set_error("%s: mode %d unknown (NSD_AVG_EMA / NSD_AVG_SWA)", who, a->mode); return NSD_E_INVALID; }
+    if (a->mode == NSD_AVG_EMA && !(a->decay >= 0.f && a->decay < 1.f)) { nsd_set_error("%s: decay %g outside [0, 1) or NaN", who, a->decay); return NSD_E_INVALID; }
+    if (a->start_step < 1) { nsd_set_error("%s: start_step %d must be >= 1", who, a->start_step); return NSD_E_INVALID; }
+    if (a->every < 1) { nsd_set_error("%s: every %d must be >= 1", who, a->every); return NSD_E_INVALID; }
+    return NSD_OK;
+}
+int64_t nsd_avg_state_need(int64_t n, int M) { return (int64_t)M * (int64_t)sizeof(nsd_avg_record) + (int64_t)M * n * (int64_t)sizeof(float); }
+
 // the fused tail of M models (M = 1: the single-model entry point): reduction with norm, then the update.  o: one nsd_opt for all
 // models, or with each != 0 (M > 1) one per model
 int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p, float *m, float *v, const nsd_opt *o, int each, int step,
-                                const long long *step_dev, void *state, const char *who, hipStream_t st) {
+                                const long long *step_dev, void *state, const char *who, hipStream_t st, const NsdAvgSpec *as) {
     const long P = s.p_lstm + s.ph, cols = col_parts(P);
     const dim3 wg(ON_COLS * ON_GROUPS);
     if (M == 1) {
         hipLaunchKernelGGL(reduce_norm_kernel<false>, dim3((unsigned)cols), wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h, grads,
                            GScale<false>{o->grad_scale}, parts_of(state, M));
         NSD_CHECK_LAUNCH(who);
-        return adam_clip_launch(P, M, p, grads, m, v, opt_kernel_args(o, step, step_dev), cols, state, nullptr, who, st);
+        return adam_clip_launch(P, M, p, grads, m, v, opt_kernel_args(o, step, step_dev), cols, state, nullptr, who, st, as, step);
     }
     GScale<true> gs;
     OptKSet ks;
@@ -262,7 +380,7 @@ int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p,
     hipLaunchKernelGGL(reduce_norm_kernel<true>, dim3((unsigned)cols, (unsigned)M), wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h,
                        grads, gs, parts_of(state, M));
     NSD_CHECK_LAUNCH(who);
-    return adam_clip_launch(P, M, p, grads, m, v, ks, cols, state, nullptr, who, st);
+    return adam_clip_launch(P, M, p, grads, m, v, ks, cols, state, nullptr, who, st, as, step);
 }
 
 int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st) {
@@ -273,7 +391,8 @@ int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipS
 }
 
 int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float *v, const nsd_opt *o, int step, const long long *step_dev,
-                              const float *skip, void *state, hipStream_t st) {
+                              const float *skip, void *state, hipStream_t st, const NsdAvgSpec *as) {
     if (n <= 0) return NSD_OK;
-    return adam_clip_launch(n, 1, p, g, m, v, opt_kernel_args(o, step, step_dev), flat_parts(n), state, skip, "adam_step_clip", st);
+    return adam_clip_launch(n, 1, p, g, m, v, opt_kernel_args(o, step, step_dev), flat_parts(n), state, skip, as ? "adam_step_clip_avg" : "adam_step_clip", st,
+                            as, step);
 }

@@ -3,7 +3,8 @@
     python -m nsd_amd.grid --data trials.npz --T 40 --kfold 5 --epochs 20 --batch 32 --grid lr=1e-3,3e-3 --grid dropout=0.4,0.6
 
 --grid key=v1,v2,... is repeatable and forms the cartesian product (the first key varies slowest).  The keys name options of
-nsd_amd.train: lr, weight_decay, dropout, label_smoothing, mixup, clip_grad_norm, aug_shift, aug_scale, aug_channel_drop, aug_noise.
+nsd_amd.train: lr, weight_decay, dropout, label_smoothing, mixup, clip_grad_norm, aug_shift, aug_scale, aug_channel_drop, aug_noise, and
+beside --avg ema (weight averaging: the averaged models are the scored ones, as in train) avg_decay.
 Every other option is that of `train --kfold K --concurrent` and is shared by all configurations.  The runs are configurations x the
 folds of train.concurrent_runs -- the folds, seeds and initial parameters `train --kfold K --concurrent` trains for that configuration --
 packed as whole configurations into launches of at most 32 models (ModelBatchTrainer with per-model settings); the groups run one after
@@ -37,6 +38,10 @@ GRID_KEYS = {"lr": ("lr", float), "weight_decay": ("weight_decay", float), "drop
              "label_smoothing": ("label_smoothing", float), "mixup": ("mixup", float), "clip_grad_norm": ("clip_grad_norm", float),
              "aug_shift": ("aug_shift", int), "aug_scale": ("aug_scale", float), "aug_channel_drop": ("aug_channel_drop", float),
              "aug_noise": ("aug_noise", float)}
+# an axis that exists only beside another option: --grid avg_decay=... needs --avg ema (weight averaging; the scored models are then the
+# averaged ones, as in train)
+AVG_GRID_KEYS = {"avg_decay": ("avg_decay", float)}
+ALL_KEYS = {**GRID_KEYS, **AVG_GRID_KEYS}
 
 
 def parse_grid(specs: Sequence[str]) -> List[Tuple[str, list]]:
@@ -45,12 +50,12 @@ def parse_grid(specs: Sequence[str]) -> List[Tuple[str, list]]:
     for spec in specs:
         key, sep, vals = spec.partition("=")
         key = key.strip().replace("-", "_")
-        if not sep or key not in GRID_KEYS:
-            raise ValueError(f"--grid {spec!r}: unknown key {key!r}: key=v1,v2,... with key one of {', '.join(GRID_KEYS)}")
+        if not sep or key not in ALL_KEYS:
+            raise ValueError(f"--grid {spec!r}: unknown key {key!r}: key=v1,v2,... with key one of {', '.join(ALL_KEYS)}")
         if key in seen:
             raise ValueError(f"--grid {spec!r}: {key} is given twice")
         seen.add(key)
-        conv = GRID_KEYS[key][1]
+        conv = ALL_KEYS[key][1]
         try:
             values = [conv(v) for v in vals.split(",")]
         except ValueError:
@@ -91,7 +96,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap = train_parser()
     ap.description = __doc__
     ap.add_argument("--grid", action="append", default=[], metavar="KEY=V1,V2,...",
-                    help="repeatable; the cartesian product of all --grid options is searched.  Keys: " + ", ".join(GRID_KEYS))
+                    help="repeatable; the cartesian product of all --grid options is searched.  Keys: " + ", ".join(ALL_KEYS))
     return ap
 
 
@@ -105,8 +110,8 @@ def main(argv=None) -> int:
     from .multimodel import ModelBatchTrainer
     from .ops import Augment, Loss
     from .prep import CausalPrep
-    from .train import (concurrent_epoch, concurrent_runs, early_stop_settings, evaluate, loss_for, padded_parts, parse_class_weights,
-                        schedule_for, selection_text)
+    from .train import (average_for, concurrent_epoch, concurrent_runs, early_stop_settings, evaluate, loss_for, padded_parts,
+                        parse_class_weights, schedule_for, selection_text)
 
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -142,8 +147,9 @@ def main(argv=None) -> int:
     for cfg in configs:
         a = copy.copy(args)
         for k, v in cfg.items():
-            setattr(a, GRID_KEYS[k][0], v)
+            setattr(a, ALL_KEYS[k][0], v)
         try:
+            average_for(a, 1)
             if a.clip_grad_norm is not None and not a.clip_grad_norm >= 0.0:
                 raise ValueError(f"clip_grad_norm {a.clip_grad_norm} negative")
             if not 0.0 <= a.dropout < 1.0:
@@ -212,8 +218,10 @@ def main(argv=None) -> int:
             models, lr=per(lambda c, k: cfg_args[c].lr), weight_decay=per(lambda c, k: cfg_args[c].weight_decay),
             seeds=[runs[k]["seed"] + 1 for _, k in members], augment=per(lambda c, k: augments[c]),
             loss=per(lambda c, k: loss_for(cfg_args[c], y_np[runs[k]["tr"]] if balanced else y_np)),
-            clip_grad_norm=per(lambda c, k: cfg_args[c].clip_grad_norm), lr_schedule=schedule_for(args, args.epochs * steps_per_epoch))
-        opt_on = mbt._opt_on
+            clip_grad_norm=per(lambda c, k: cfg_args[c].clip_grad_norm), lr_schedule=schedule_for(args, args.epochs * steps_per_epoch),
+            average=per(lambda c, k: average_for(cfg_args[c], steps_per_epoch)))
+        opt_on, avg_on, inner, es_epoch0 = mbt._opt_on, args.avg is not None, None, 0
+        avg_start = average_for(cfg_args[0], steps_per_epoch).start_step if avg_on else 0      # (kind, start and stride are shared)
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in members]
         member_runs = [runs[k] for _, k in members]
 
@@ -226,27 +234,34 @@ def main(argv=None) -> int:
         for epoch in range(args.epochs):
             concurrent_epoch(member_runs, args.batch, epoch, step)
             last = epoch == args.epochs - 1
-            if es:   # every epoch: all members on their inner parts, the best-epoch decision and the snapshot, in two launches
-                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"])
+            # --avg: the averaged rows are what is scored, compared and snapshotted, once averaging has begun (as in train)
+            avg_ready = avg_on and (epoch + 1) * steps_per_epoch >= avg_start
+            wts = dict(weights="average") if avg_ready else {}
+            if es and (avg_ready or not avg_on):
+                # every epoch: all members on their inner parts, the best-epoch decision and the snapshot, in two launches
+                if inner is None:
+                    es_epoch0 = epoch        # (--avg-start-epoch: evaluation n is epoch es_epoch0 + n - 1)
+                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"], **wts)
                 last = last or all(e["stopped"] for e in inner)
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
                 norms, lrs, skipped = (mbt.last_grad_norms(), mbt.last_lrs(), mbt.skipped_steps()) if opt_on else (None, None, None)
                 if es:
-                    ev_tr, ev_va = mbt.evaluate(*held["tr"]), mbt.evaluate(*held["va"])
+                    ev_tr, ev_va = mbt.evaluate(*held["tr"], **wts), mbt.evaluate(*held["va"], **wts)
+                scored = mbt.averaged_models() if avg_ready else models
                 for i, (c, k) in enumerate(members):
                     if es:
                         acc_tr, acc_va = ev_tr[i]["acc"], ev_va[i]["acc"]
                     else:
-                        acc_tr = evaluate(models[i], x_all[tr_devs[k]], y_all[tr_devs[k]])
-                        acc_va = evaluate(models[i], x_all[runs[k]["va"]], y_all[runs[k]["va"]])
+                        acc_tr = evaluate(scored[i], x_all[tr_devs[k]], y_all[tr_devs[k]])
+                        acc_va = evaluate(scored[i], x_all[runs[k]["va"]], y_all[runs[k]["va"]])
                     res[i] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
                     emit({"run": tag(runs[k]), "config_index": c, "config": configs[c], "epoch": epoch, "loss_last_batch": round(losses[i], 5),
                           "acc_train": round(acc_tr, 4), "acc_val": round(acc_va, 4), "n_val": int(len(runs[k]["va"])),
                           "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
                           **({"grad_norm": norms[i], "lr": lrs[i], "skipped": skipped[i]} if opt_on else {}),
                           **({"loss_inner": round(inner[i]["loss"], 5), "acc_inner": round(inner[i]["acc"], 4),
-                              "best_epoch": inner[i]["best_eval"] - 1, "stopped": inner[i]["stopped"]} if es else {})})
+                              "best_epoch": es_epoch0 + inner[i]["best_eval"] - 1, "stopped": inner[i]["stopped"]} if inner is not None else {})})
             if es and last:
                 break
         if es:       # the outer folds of the best-epoch models, in one call
@@ -259,7 +274,7 @@ def main(argv=None) -> int:
             accs = [res[i]["acc_val_last"] for i in mine]
             summaries.append({"summary": True, "config_index": c, "config": configs[c], "acc_val_mean": round(float(np.mean(accs)), 4),
                               "acc_val_sd": round(float(np.std(accs, ddof=1)), 4), "acc_val_folds": [round(float(a), 4) for a in accs],
-                              **({"selection": selection_text(es), "best_epochs": [best[i] - 1 for i in mine],
+                              **({"selection": selection_text(es), "best_epochs": [es_epoch0 + best[i] - 1 for i in mine],
                                   "confusion_val": [final[i]["confusion"].tolist() for i in mine]} if es else {}),
                               "train_args": train_args(configs[c])})
             emit(summaries[-1])

@@ -255,6 +255,22 @@ class EEG_LSTM(nn.Module):
             self.flatten_parameters()
         return self._flat
 
+    def view_of(self, row: torch.Tensor) -> "EEG_LSTM":
+        """A second EEG_LSTM of this model's shape and options (eval mode) whose parameters are views of `row`, a flat fp32 vector of
+        param_count elements in state_dict order -- a trainer's averaged row: the module follows whatever is written there later."""
+        sp = self.spec
+        if row.dtype != torch.float32 or row.dim() != 1 or row.numel() != sp.param_count or not row.is_contiguous():
+            raise NsdError(f"EEG_LSTM.view_of: row must be a contiguous float32 vector of {sp.param_count} elements")
+        twin = EEG_LSTM(sp.C, sp.H, sp.L, sp.K, self.head_dropout_p, residual=self.residual, normalize=self.normalize,
+                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep)
+        offs = sp.offsets()
+        with torch.no_grad():
+            for n, p in twin._named_in_order():
+                p.data = row[offs[n]:offs[n] + p.numel()].view(p.shape)
+                p.requires_grad_(False)                    # nobody trains an average: forward() takes the inference launch
+        twin._flat = row
+        return twin.eval()
+
     def _apply(self, fn, *a, **kw):
         out = super()._apply(fn, *a, **kw)
         self._flat = None        # .to()/.cuda() re-created the storages

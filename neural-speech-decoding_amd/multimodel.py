@@ -53,12 +53,17 @@ class ModelBatchTrainer:
     issue exactly the calls of the single setting.  One model's loss=None beside another model's loss trains on one-hot target rows
     through the soft-target entry point: the hard-label gradient up to the summation order over the classes (the same bits for K <= 3).
 
+    average: an ops.Average, or a sequence of M with None for a model that does not average -- a grid axis like lr.  The update launch
+    then also keeps each model's averaged row (weight averaging as Trainer's: the guarded tail is on, nothing is clipped by it, a
+    skipped step does not average; no extra launch).  averaged_models() are modules on those rows; evaluate / track_best take
+    weights="average" to score -- and snapshot -- the averaged rows instead of the last iterates.
+
     Dropout comes from each model's own dropout_p / head_dropout_p (NSD_FLAG_MODEL_P is passed only where they differ).  This corrects
     earlier behaviour: models with different probabilities were all, silently, trained with model 0's."""
 
     def __init__(self, models: Sequence[EEG_LSTM], lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
-                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None):
+                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None, average=None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -104,8 +109,15 @@ class ModelBatchTrainer:
         self.grads = torch.zeros_like(self.params)
         # clipping and schedule as in Trainer: one global norm, one record and one skip decision PER MODEL (nsd_multi_grad_reduce_clip_adam)
         self.clip_grad_norm, self.lr_schedule = clip_grad_norm, lr_schedule
-        self._opt_on = self._each is not None or clip_grad_norm is not None or lr_schedule is not None
+        self.average = self._per_model(average, "average")
+        for a in self.average:
+            if a is not None and not isinstance(a, ops.Average):
+                raise ValueError(f"ModelBatchTrainer: average {a!r}: an ops.Average or None")
+        self._avg_on = any(a is not None for a in self.average)
+        self._opt_on = self._each is not None or clip_grad_norm is not None or lr_schedule is not None or self._avg_on
         self._opt_state = ops.opt_state(P, M, dev) if self._opt_on else None
+        self._avg_state = ops.avg_state(P, M, dev) if self._avg_on else None
+        self._avg_models = None
         self.step_count = 0
         self._bufs = {}
         self._last = None
@@ -150,7 +162,8 @@ class ModelBatchTrainer:
         buf = self._buffers(B, T)
         ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
                              step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                             weight_decay=self.weight_decay, targets=tg, opt=self._opt() if self._opt_on else None, opt_state=self._opt_state)
+                             weight_decay=self.weight_decay, targets=tg, opt=self._opt() if self._opt_on else None, opt_state=self._opt_state,
+                             avg=self.average if self._avg_on else None, avg_state=self._avg_state)
         self._last = (B, T)
 
     def _opt(self):
@@ -161,6 +174,30 @@ class ModelBatchTrainer:
         e = self._each
         return [ops.opt_struct(lr=e["lr"][i], beta1=e["betas"][i][0], beta2=e["betas"][i][1], eps=e["eps"][i], weight_decay=e["weight_decay"][i],
                                max_norm=e["clip_grad_norm"][i], schedule=e["lr_schedule"][i]) for i in range(self.M)]
+
+    # ---- weight averaging -------------------------------------------------------------------------------------------------------
+    def averaged_params(self) -> torch.Tensor:
+        """The averaged rows [M, P], a view of the device buffer the update launch writes.  The row of a model without averaging, or
+        before its first averaged step, holds nothing of use (averaged_counts())."""
+        if not self._avg_on:
+            raise NsdError("ModelBatchTrainer: no weight averaging (pass average=ops.Average(...))")
+        return ops.avg_rows(self._avg_state, self.M, self.spec.param_count)
+
+    def averaged_counts(self) -> List[int]:
+        """Per model: how many steps its average holds (synchronises)."""
+        return [r["n_avg"] for r in ops.avg_records(self._avg_state, self.M)] if self._avg_on else [0] * self.M
+
+    def averaged_models(self) -> List[EEG_LSTM]:
+        """One EEG_LSTM (eval mode) per model whose parameters are views of its averaged row; they follow later steps."""
+        if self._avg_models is None:
+            rows = self.averaged_params()
+            self._avg_models = [mdl.view_of(rows[i]) for i, mdl in enumerate(self.models)]
+        return self._avg_models
+
+    def _weights(self, weights: str, who: str) -> torch.Tensor:
+        if weights not in ("last", "average"):
+            raise NsdError(f"ModelBatchTrainer.{who}: weights {weights!r}: 'last' or 'average'")
+        return self.params if weights == "last" else self.averaged_params()
 
     def last_grad_norms(self) -> List[float]:
         """Each model's global gradient norm of the last step, before clipping (synchronises; NaN with both options off or before a step)."""
@@ -198,11 +235,12 @@ class ModelBatchTrainer:
     # ---- held-out metrics and early stopping for all models (nsd_multi_eval of include/nsd.h) --------------------------------------
     # A trainer on which none of these is called allocates nothing for them and issues exactly the calls it issued without them.
 
-    def _held_out(self, x: torch.Tensor, y: torch.Tensor, counts, select, who: str) -> List[dict]:
+    def _held_out(self, x: torch.Tensor, y: torch.Tensor, counts, select, who: str, weights: str = "last") -> List[dict]:
         """nsd_multi_infer on the windows (behind the models' front end, as EEG_LSTM.forward), nsd_multi_eval on its logits, ONE read of
         the records: with selection the eval records lie directly in front of the select state in one allocation, so one copy brings
         both kinds."""
         M = self.M
+        params = self._weights(weights, who)
         if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != M):
             raise NsdError(f"ModelBatchTrainer.{who}: x must be [M={M},B,T,C] or [B,T,C], got {tuple(x.shape)}")
         B, T, Cc = (int(v) for v in x.shape[-3:])
@@ -218,14 +256,14 @@ class ModelBatchTrainer:
             x = ops.prep_step(x, self.models[0].prep)
         elif self.models[0].normalize:
             x = ops.zscore(x.reshape(-1, T, Cc)).view(x.shape)
-        logits, _ = ops.multi_infer(self.spec, self.params, x, want_probs=False)
+        logits, _ = ops.multi_infer(self.spec, params, x, want_probs=False)
         if select is None:
             return ops.eval_records(ops.multi_eval(logits, y.contiguous(), counts=counts), M, self.spec.K)
         lead = (M * ops.EVAL_RECORD_BYTES + 15) // 16 * 16
         if self._sel_state is None:
             self._sel_buf = torch.empty(lead + ops.select_state_bytes(M, self.spec.param_count), dtype=torch.uint8, device=self.params.device)
             self._sel_state = ops.select_state(M, self.spec.param_count, self.params.device, out=self._sel_buf[lead:])
-        ops.multi_eval(logits, y.contiguous(), counts=counts, out=self._sel_buf[:M * ops.EVAL_RECORD_BYTES], select=select, params=self.params,
+        ops.multi_eval(logits, y.contiguous(), counts=counts, out=self._sel_buf[:M * ops.EVAL_RECORD_BYTES], select=select, params=params,
                        state=self._sel_state)
         raw = self._sel_buf[:lead + M * ops.SELECT_RECORD_BYTES].cpu()
         recs = ops.eval_records(raw, M, self.spec.K)
@@ -233,22 +271,24 @@ class ModelBatchTrainer:
             r.update(best_eval=s["best_eval"], bad=s["bad"], stopped=bool(s["stopped"]))
         return recs
 
-    def evaluate(self, x: torch.Tensor, y: torch.Tensor, counts=None) -> List[dict]:
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, counts=None, weights: str = "last") -> List[dict]:
         """Held-out metrics of all M models in two launches and one read: x [M,B,T,C] (each model's own windows) or a shared [B,T,C], y
         [M,B] or [B] class indices.  counts: None, or M ints -- only model m's first counts[m] windows count, the rest is padding
         (folds differ in size by one; the padding may hold anything).  Returns M dicts: loss (mean cross-entropy, summed in double),
         acc, n, nonfinite (windows whose logits were not finite: they count nowhere else and make the loss NaN) and confusion, a
-        [K,K] numpy array indexed [label, prediction].  Synchronises."""
-        return self._held_out(x, y, counts, None, "evaluate")
+        [K,K] numpy array indexed [label, prediction].  Synchronises.  weights="average": the metrics of the averaged rows
+        (average=) instead of the last iterates."""
+        return self._held_out(x, y, counts, None, "evaluate", weights)
 
     def track_best(self, x: torch.Tensor, y: torch.Tensor, counts=None, metric: str = "loss", patience: int = 0,
-                   min_delta: float = 0.0) -> List[dict]:
+                   min_delta: float = 0.0, weights: str = "last") -> List[dict]:
         """evaluate(), and in the same launch early stopping per model: is this the model's best evaluation so far (metric "loss": the
         mean loss fell by more than min_delta; "acc": the accuracy rose by more than min_delta, or stayed with a lower loss), if so copy
         its parameter row into a snapshot on the device, else count one more bad evaluation and, with patience > 0, mark the model
         stopped after `patience` of them in a row (patience = 0 tracks the best and never stops).  A non-finite evaluation is a bad
         one.  Returns evaluate()'s dicts extended by best_eval (1-based number of the best evaluation, 0: none yet), bad and stopped.
-        One rule per trainer: another metric, patience or min_delta on a later call raises.
+        One rule per trainer: another metric, patience or min_delta on a later call raises.  weights="average": the averaged rows are
+        what is evaluated AND what is snapshotted, so restore_best() puts the best averaged weights into the models.
 
         A stopped model STILL TRAINS: step() keeps updating its parameters until the caller's loop ends (the step kernels know nothing
         of this).  Its snapshot and its record are frozen, so restore_best() gives what stopping it would have given; all_stopped()
@@ -257,11 +297,12 @@ class ModelBatchTrainer:
             raise NsdError(f"ModelBatchTrainer.track_best: metric {metric!r}: 'loss' or 'acc'")
         if int(patience) < 0 or not float(min_delta) >= 0.0:
             raise NsdError(f"ModelBatchTrainer.track_best: patience {patience} / min_delta {min_delta}: both >= 0")
+        self._weights(weights, "track_best")
         rule = dict(metric=metric, patience=int(patience), min_delta=float(min_delta))
-        if self._sel_rule is not None and rule != self._sel_rule:
-            raise NsdError(f"ModelBatchTrainer.track_best: the rule was {self._sel_rule}, now {rule}: one rule per trainer")
-        recs = self._held_out(x, y, counts, rule, "track_best")
-        self._sel_rule = rule
+        if self._sel_rule is not None and (rule, weights) != self._sel_rule:
+            raise NsdError(f"ModelBatchTrainer.track_best: the rule was {self._sel_rule}, now {(rule, weights)}: one rule per trainer")
+        recs = self._held_out(x, y, counts, rule, "track_best", weights)
+        self._sel_rule = (rule, weights)
         return recs
 
     def _select_records(self) -> List[dict]:

@@ -543,6 +543,76 @@ def adam_step_clip(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.T
           state.data_ptr(), _nbytes(state), STREAM)
 
 
+@dataclass(frozen=True)
+class Average:
+    """Weight averaging of a trainer (nsd_avg, include/nsd.h; an extension, the reference has none): the update launch also keeps an
+    averaged copy of the parameters.  kind "ema": a' = a + (1 - decay) (p' - a); "swa": the equal-weight running mean a' = a + (p' - a) /
+    (n + 1) of the averaged iterates (torch.optim.swa_utils.AveragedModel's default; decay is ignored).  Steps before start_step
+    (1-based), steps off the stride `every` and skipped updates do not average; the first averaged step copies the parameters."""
+    kind: str = "ema"
+    decay: float = 0.999
+    start_step: int = 1
+    every: int = 1
+
+    def __post_init__(self):
+        if self.kind not in _lib.NSD_AVG:
+            raise ValueError(f"Average: kind {self.kind!r} is not one of {sorted(_lib.NSD_AVG)}")
+        if self.kind == "ema" and not 0.0 <= self.decay < 1.0:
+            raise ValueError(f"Average: decay {self.decay!r} outside [0, 1)")
+        for name in ("start_step", "every"):
+            v = getattr(self, name)
+            if int(v) != v or not 1 <= v < 2 ** 31:
+                raise ValueError(f"Average: {name} {v!r} must be an int32 >= 1")
+
+    def struct(self) -> "_lib.Avg":
+        return _lib.Avg(_lib.NSD_AVG[self.kind], float(self.decay), int(self.start_step), int(self.every))
+
+
+def _avg_struct(a) -> "_lib.Avg":
+    """nsd_avg of an Average, of None (mode 0: this model does not average, `_each` only) or of a ready _lib.Avg"""
+    return a if isinstance(a, _lib.Avg) else _lib.Avg(0, 0.0, 1, 1) if a is None else a.struct()
+
+
+def avg_state_bytes(n: int, M: int = 1) -> int:
+    nb = int(_lib.lib().nsd_avg_state_bytes(int(n), int(M)))
+    if nb < 0:
+        check(nb, "nsd_avg_state_bytes")
+    return nb
+
+
+def avg_state(n: int, M: int, device) -> torch.Tensor:
+    """The avg_state of weight averaging for M models of n parameters (or a flat vector of n, M = 1): records zeroed, rows zero too
+    (the kernels ask nothing of the rows before a model's first averaged step)."""
+    st = torch.zeros(avg_state_bytes(n, M), dtype=torch.uint8, device=device)
+    _call("nsd_avg_state_init", st.device, st.data_ptr(), _nbytes(st), int(M), STREAM)
+    return st
+
+
+def avg_rows(state: torch.Tensor, M: int, n: int) -> torch.Tensor:
+    """The averaged rows of an avg_state as an [M, n] fp32 view (no copy: it follows later steps)."""
+    return state[16 * M:16 * M + 4 * M * n].view(torch.float32).view(M, n)
+
+
+def avg_records(state: torch.Tensor, M: int = 1) -> List[dict]:
+    """The M records at the head of an avg_state: [{n_avg, arrive}] (synchronises)."""
+    u = state[:16 * M].cpu().view(torch.int32).view(M, 4)
+    return [dict(n_avg=int(u[i, 0]) & 0xFFFFFFFF, arrive=int(u[i, 1]) & 0xFFFFFFFF) for i in range(M)]
+
+
+def _avg_args(avg, avg_state_: torch.Tensor):
+    return C.byref(avg), avg_state_.data_ptr(), _nbytes(avg_state_)
+
+
+def adam_step_clip_avg(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, opt: "_lib.Opt", state: torch.Tensor,
+                       avg, avg_state: torch.Tensor, *, step: int = 0, step_dev: Optional[torch.Tensor] = None,
+                       skip: Optional[torch.Tensor] = None) -> None:
+    """adam_step_clip that also forms the weight average in the same launch (nsd_adam_step_clip_avg): avg an ops.Average, avg_state
+    ops.avg_state(p.numel(), 1)."""
+    _call("nsd_adam_step_clip_avg", p.device, p.numel(), _dev_f32(p, "p"), _dev_f32(g, "g", p.shape), _dev_f32(m, "m", p.shape),
+          _dev_f32(v, "v", p.shape), C.byref(opt), int(step), _step_ptr(step_dev, "adam_step_clip_avg"), _dev_f32(skip, "skip"),
+          state.data_ptr(), _nbytes(state), STREAM, *_avg_args(_avg_struct(avg), avg_state))
+
+
 def _out_f32(out: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
     """The caller's output buffer (element count checked; dtype, device and contiguity by _dev_f32 at the launch), or a fresh one"""
     if out is None:
@@ -698,10 +768,13 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
         _call("nsd_grad_reduce", dev, C.byref(d), wsp, wsn, gp, 0, st)
     elif adam.get("opt") is not None:
         # clipping / schedule on: reduction with norm, then the update (nsd_grad_reduce_clip_adam); step_dev: the graph-replay form
+        # with avg= (ops.Average) and avg_state= also in the dict: its `_avg` twin, the weight average formed by the same update launch
         state = adam["opt_state"]
-        _call("nsd_grad_reduce_clip_adam", dev, C.byref(d), wsp, wsn, gp, pp, _dev_f32(adam["m"], "m", flat.shape), _dev_f32(adam["v"], "v", flat.shape),
+        av = () if adam.get("avg") is None else _avg_args(_avg_struct(adam["avg"]), adam["avg_state"])
+        _call("nsd_grad_reduce_clip_adam_avg" if av else "nsd_grad_reduce_clip_adam", dev, C.byref(d), wsp, wsn, gp, pp,
+              _dev_f32(adam["m"], "m", flat.shape), _dev_f32(adam["v"], "v", flat.shape),
               C.byref(adam["opt"]), int(adam.get("step", 0)), _step_ptr(adam.get("step_dev"), "train_step_grads"), state.data_ptr(),
-              _nbytes(state), st)
+              _nbytes(state), st, *av)
     else:
         _call("nsd_grad_reduce_adam", dev, C.byref(d), wsp, wsn, gp, pp, _dev_f32(adam["m"], "m", flat.shape), _dev_f32(adam["v"], "v", flat.shape),
               adam.get("lr", 1e-3), adam.get("beta1", 0.9), adam.get("beta2", 0.999), adam.get("eps", 1e-8),
@@ -1074,7 +1147,8 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
                      *, rngs=None, logits: Optional[torch.Tensor] = None, fuse_adam: bool = True, m: Optional[torch.Tensor] = None,
                      v: Optional[torch.Tensor] = None, step: int = 1, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
                      eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
-                     targets: Optional[torch.Tensor] = None, opt=None, opt_state: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     targets: Optional[torch.Tensor] = None, opt=None, opt_state: Optional[torch.Tensor] = None, avg=None,
+                     avg_state: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One training step of M models at once: params [M,P], x [M,B,T,C] or shared [B,T,C], labels [M*B] int32, grads [M,P].
     Forward + head + mean CE per model + head backward, BPTT, then the reduction (+ Adam on params / m / v when fuse_adam).
     rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K].
@@ -1082,7 +1156,10 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
     opt (ops.opt_struct) with opt_state (ops.opt_state(P, M)): the tail is nsd_multi_grad_reduce_clip_adam -- one norm, record and skip
     decision per model; the Adam arguments of this call are then ignored.  opt may be a list of M (nsd_multi_grad_reduce_clip_adam_each:
     every field per model); a list of equal entries is the single opt's launch.  rngs whose p_lstm / p_head differ between models go
-    with NSD_FLAG_MODEL_P (each model drops with its own probabilities); equal ones go without the flag, as before."""
+    with NSD_FLAG_MODEL_P (each model drops with its own probabilities); equal ones go without the flag, as before.
+    avg (ops.Average, or a list of M with None for a model that does not average) with avg_state (ops.avg_state(P, M)) and opt: the
+    `_avg` twin of the clipped tail forms each model's weight average in the update launch; a list with different entries goes through
+    nsd_multi_grad_reduce_clip_adam_avg_each together with M opt entries."""
     M = int(params.shape[0])
     B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
@@ -1103,7 +1180,21 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
         _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), fl, ws.data_ptr(), _nbytes(ws),
               _dev_f32(logits, "logits"), STREAM)
     _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, fl, ws.data_ptr(), _nbytes(ws), STREAM)
-    if fuse_adam and opts is not None:
+    avg, avgs = _per_model(avg, M, "multi: avg")
+    if (avg is not None or avgs is not None) and not (fuse_adam and (opt is not None or opts is not None) and avg_state is not None):
+        raise NsdError("multi: avg= needs fuse_adam, opt= / opt_state= (the clipped tail forms the average) and avg_state=")
+    if fuse_adam and (avgs is not None or (avg is not None and opts is not None)):
+        # per-model settings on either side: M entries of both (an equal setting repeated)
+        arr = (_lib.Opt * M)(*(opts if opts is not None else [opt] * M))
+        avr = (_lib.Avg * M)(*[_avg_struct(a) for a in (avgs if avgs is not None else [avg] * M)])
+        _call("nsd_multi_grad_reduce_clip_adam_avg_each", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
+              _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), C.cast(arr, C.c_void_p), int(step), None, opt_state.data_ptr(), _nbytes(opt_state),
+              STREAM, C.cast(avr, C.c_void_p), avg_state.data_ptr(), _nbytes(avg_state))
+    elif fuse_adam and avg is not None:
+        _call("nsd_multi_grad_reduce_clip_adam_avg", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
+              _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), C.byref(opt), int(step), None, opt_state.data_ptr(), _nbytes(opt_state), STREAM,
+              *_avg_args(_avg_struct(avg), avg_state))
+    elif fuse_adam and opts is not None:
         arr = (_lib.Opt * M)(*opts)
         _call("nsd_multi_grad_reduce_clip_adam_each", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)), pp,
               _dev_f32(m, "m", (M, P)), _dev_f32(v, "v", (M, P)), C.cast(arr, C.c_void_p), int(step), None, opt_state.data_ptr(), _nbytes(opt_state),

@@ -21,7 +21,7 @@ import torch
 
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
-from .ops import Augment, Loss, LrSchedule
+from .ops import Augment, Average, Loss, LrSchedule
 from .prep import CausalPrep
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
@@ -163,6 +163,24 @@ def schedule_for(args, total_steps: int):
                       min_ratio=args.lr_min_ratio, step_size=args.lr_step_size, gamma=args.lr_gamma)
 
 
+AVG_OPTIONS = ("avg", "avg_decay", "avg_start_epoch", "avg_every_steps")
+
+
+def average_for(args, steps_per_epoch: int):
+    """The ops.Average of a run from --avg and its options (None without --avg): --avg-start-epoch E, counted from 0, becomes the 1-based
+    step E * steps_per_epoch + 1 -- the first step of that epoch.  ValueError, with the rule, for an option without --avg or out of range."""
+    given = [o for o in AVG_OPTIONS[1:] if getattr(args, o, None) is not None]
+    if getattr(args, "avg", None) is None:
+        if given:
+            raise ValueError(f"--{given[0].replace('_', '-')} needs --avg ema|swa")
+        return None
+    start = 0 if args.avg_start_epoch is None else args.avg_start_epoch
+    if not 0 <= start < args.epochs:
+        raise ValueError(f"--avg-start-epoch {start} outside [0, --epochs {args.epochs})")
+    return Average(kind=args.avg, decay=0.999 if args.avg_decay is None else args.avg_decay, start_step=start * max(int(steps_per_epoch), 1) + 1,
+                   every=1 if args.avg_every_steps is None else args.avg_every_steps)
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The options of this command (nsd_amd.grid shares them: its --grid keys name options of this parser)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -232,6 +250,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--early-stop-min-delta", type=float, default=None, help="early stopping: an epoch is better only by more than this (default 0)")
     ap.add_argument("--inner-fraction", type=float, default=None, help="early stopping: share of each fold's training trials held out as its "
                                                                        "inner split, in (0, 0.5] (default 0.2)")
+    ap.add_argument("--avg", default=None, choices=("ema", "swa"),
+                    help="weight averaging in the update launch: an exponential moving average (ema) or the running mean (swa) of the "
+                         "parameters over the steps; the scored and saved model is then the AVERAGED one, and every record carries the "
+                         "last iterate's accuracy beside it.  Turns the guarded step tail on (non-finite steps are skipped and counted)")
+    ap.add_argument("--avg-decay", type=float, default=None, help="weight averaging: EMA decay in [0, 1) (default 0.999)")
+    ap.add_argument("--avg-start-epoch", type=int, default=None, help="weight averaging: first epoch (from 0) whose steps are averaged (default 0)")
+    ap.add_argument("--avg-every-steps", type=int, default=None, help="weight averaging: average every N-th step from the start (default 1)")
     return ap
 
 
@@ -289,6 +314,7 @@ def main(argv=None) -> int:
 
     try:
         es = early_stop_settings(args, concurrent=args.concurrent and args.kfold >= 2)
+        average_for(args, 1)
     except ValueError as e:
         ap.error(str(e))
 
@@ -335,7 +361,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS or v is not None)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS or v is not None)}
 
     fold_paths = []
 
@@ -347,9 +373,12 @@ def main(argv=None) -> int:
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
                          bidirectional=args.bidirectional, prep=prep_for(tr_idx)).to(dev).train()
         steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
+        average = average_for(args, steps_per_epoch)
         trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
-                          clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch))
-        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None
+                          clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average)
+        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None
+        scored = model                   # --avg: the averaged model, from its first averaged step on
+        acc_va_last_iterate = float("nan")
         tr_dev = torch.from_numpy(tr_idx).to(dev)
         best = (-1.0, -1)
         t0 = time.time()
@@ -365,17 +394,23 @@ def main(argv=None) -> int:
             if epoch % args.log_every == 0 or last:
                 trainer.check()                  # every rank: raises (non-zero exit) if a scan group timed out anywhere
             if rank == 0 and (epoch % args.log_every == 0 or last):
-                acc_tr = evaluate(model, x_all[tr_dev], y_all[tr_dev])
-                acc_va = evaluate(model, x_all[va_idx], y_all[va_idx]) if len(va_idx) else float("nan")
+                if average is not None and trainer.averaged_count() > 0:
+                    scored = trainer.averaged_model()
+                acc_tr = evaluate(scored, x_all[tr_dev], y_all[tr_dev])
+                acc_va = evaluate(scored, x_all[va_idx], y_all[va_idx]) if len(va_idx) else float("nan")
                 if keep_best and out_path and acc_va > best[0]:
                     best = (acc_va, epoch)
-                    save_reference_checkpoint(model, out_path)
+                    save_reference_checkpoint(scored, out_path)
                 extra = {"grad_norm": trainer.last_grad_norm(), "lr": trainer.last_lr(), "skipped": trainer.skipped_steps()} if opt_on else {}
+                if average is not None:
+                    acc_va_last_iterate = evaluate(model, x_all[va_idx], y_all[va_idx]) if len(va_idx) else float("nan")
+                    extra.update(acc_val_last_iterate=round(acc_va_last_iterate, 4), averaged_steps=trainer.averaged_count())
                 emit({"run": tag, "epoch": epoch, "loss_last_batch": round(trainer.last_loss(), 5), "acc_train": round(acc_tr, 4),
                       "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), **extra})
         if rank == 0 and out_path and (not keep_best or best[1] < 0):
-            save_reference_checkpoint(model, out_path)
-        return {"acc_train_last": acc_tr, "acc_val_last": acc_va, "best_val_acc": best[0], "best_epoch": best[1]}
+            save_reference_checkpoint(scored, out_path)
+        return {"acc_train_last": acc_tr, "acc_val_last": acc_va, "best_val_acc": best[0], "best_epoch": best[1],
+                "acc_val_last_iterate": acc_va_last_iterate}
 
     if args.kfold > 1 and args.concurrent:
         if world > 1:
@@ -392,10 +427,12 @@ def main(argv=None) -> int:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
             models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all).to(dev).train())
         steps_per_epoch = concurrent_epoch(runs, args.batch, 0, lambda idxs: None)
+        average = average_for(args, steps_per_epoch)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
                                 loss=loss_for(args, y_np), clip_grad_norm=args.clip_grad_norm,
-                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch))
-        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None
+                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average)
+        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None
+        avg_on, inner, es_epoch0 = average is not None, None, 0
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
         t0 = time.time()
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in runs]
@@ -411,26 +448,36 @@ def main(argv=None) -> int:
         for epoch in range(args.epochs):
             concurrent_epoch(runs, args.batch, epoch, step)
             last = epoch == args.epochs - 1
-            if es:   # every epoch: all folds on their inner parts, the best-epoch decision and the snapshot, in two launches
-                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"])
+            # --avg: what is scored (and, with early stopping, compared and snapshotted) is the averaged row, once averaging has begun
+            avg_ready = avg_on and (epoch + 1) * steps_per_epoch >= average.start_step
+            wts = dict(weights="average") if avg_ready else {}
+            if es and (avg_ready or not avg_on):
+                # every epoch: all folds on their inner parts, the best-epoch decision and the snapshot, in two launches
+                if inner is None:
+                    es_epoch0 = epoch        # (--avg-start-epoch: the first evaluation is that epoch's, so evaluation n is epoch es_epoch0 + n - 1)
+                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"], **wts)
                 last = last or all(e["stopped"] for e in inner)
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
                 norms, lr_now, skipped = (mbt.last_grad_norms(), mbt.last_lr(), mbt.skipped_steps()) if opt_on else (None, None, None)
                 if es:
-                    ev_tr, ev_va = mbt.evaluate(*held["tr"]), mbt.evaluate(*held["va"])
+                    ev_tr, ev_va = mbt.evaluate(*held["tr"], **wts), mbt.evaluate(*held["va"], **wts)
+                    ev_va_iter = mbt.evaluate(*held["va"]) if avg_on else ev_va
+                scored = mbt.averaged_models() if avg_ready else models
                 for k, r in enumerate(runs):
                     if es:
-                        acc_tr, acc_va = ev_tr[k]["acc"], ev_va[k]["acc"]
+                        acc_tr, acc_va, acc_va_iter = ev_tr[k]["acc"], ev_va[k]["acc"], ev_va_iter[k]["acc"]
                     else:
-                        acc_tr = evaluate(models[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
-                        acc_va = evaluate(models[k], x_all[r["va"]], y_all[r["va"]])
-                    res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
+                        acc_tr = evaluate(scored[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
+                        acc_va = evaluate(scored[k], x_all[r["va"]], y_all[r["va"]])
+                        acc_va_iter = evaluate(models[k], x_all[r["va"]], y_all[r["va"]]) if avg_on else acc_va
+                    res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va, acc_val_last_iterate=acc_va_iter)
                     emit({"run": tag(r), "epoch": epoch, "loss_last_batch": round(losses[k], 5), "acc_train": round(acc_tr, 4),
                           "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
                           **({"grad_norm": norms[k], "lr": lr_now, "skipped": skipped[k]} if opt_on else {}),
+                          **({"acc_val_last_iterate": round(acc_va_iter, 4)} if avg_on else {}),
                           **({"loss_inner": round(inner[k]["loss"], 5), "acc_inner": round(inner[k]["acc"], 4),
-                              "best_epoch": inner[k]["best_eval"] - 1, "stopped": inner[k]["stopped"]} if es else {})})
+                              "best_epoch": es_epoch0 + inner[k]["best_eval"] - 1, "stopped": inner[k]["stopped"]} if inner is not None else {})})
             if es and last:
                 break
         if es:       # the outer folds, looked at for the first time as far as the models are concerned: the best-epoch models, one call
@@ -441,12 +488,15 @@ def main(argv=None) -> int:
             accs.append(final[k]["acc"] if es else res[k]["acc_val_last"])
             if args.save_folds:
                 fold_paths.append(fold_path(tag(r)))
-                save_reference_checkpoint(models[k], fold_paths[-1])
+                # (with early stopping restore_best has put the selected row -- the averaged one with --avg -- into the model)
+                save_reference_checkpoint(models[k] if es or not avg_on else mbt.averaged_models()[k], fold_paths[-1])
             rec = {"fold": r["fold"], "n_train": int(len(r["tr"])), "n_val": int(len(r["va"])),
                    "acc_val_last_epoch": round(res[k]["acc_val_last"], 4), "acc_train_last_epoch": round(res[k]["acc_train_last"], 4),
                    "concurrent": True}
+            if avg_on:       # the same training run scored twice: its last iterate and its averaged weights (both after the last epoch)
+                rec.update(acc_val_last_iterate=round(res[k]["acc_val_last_iterate"], 4), acc_val_averaged=round(res[k]["acc_val_last"], 4))
             if es:
-                rec.update(n_inner=int(len(r["inner"])), best_epoch=best[k] - 1, acc_val_best_epoch=round(final[k]["acc"], 4),
+                rec.update(n_inner=int(len(r["inner"])), best_epoch=es_epoch0 + best[k] - 1, acc_val_best_epoch=round(final[k]["acc"], 4),
                            loss_val_best_epoch=round(final[k]["loss"], 5), confusion_val=final[k]["confusion"].tolist())
             if args.kfold_seeds > 1:
                 rec["seed"] = r["seed_run"]
@@ -456,7 +506,7 @@ def main(argv=None) -> int:
         emit({"done": True, "kfold": args.kfold, "kfold_seeds": args.kfold_seeds, "acc_val_mean": round(float(np.mean(accs)), 4),
               "acc_val_sd": round(float(np.std(accs, ddof=1)), 4),
               "acc_val_folds": [round(float(a), 4) for a in accs], "selection": selection_text(es),
-              **({"best_epochs": [b - 1 for b in best], "epochs_run": epoch + 1} if es else {}),
+              **({"best_epochs": [es_epoch0 + b - 1 for b in best], "epochs_run": epoch + 1} if es else {}),
               "shipped": {"checkpoint": args.out, "trained_on": int(len(everything)), "acc_train_last_epoch": r["acc_train_last"]},
               "world": world, "concurrent": True, "args": shown_args(), **done_extra()})
         return 0
@@ -473,7 +523,8 @@ def main(argv=None) -> int:
             r = fit(tr, va, args.seed + 101 * f, f"fold{f}", fold_paths[-1] if args.save_folds else None, keep_best=False)
             accs.append(r["acc_val_last"])
             emit({"fold": f, "n_train": int(len(tr)), "n_val": int(len(va)), "acc_val_last_epoch": round(r["acc_val_last"], 4),
-                  "acc_train_last_epoch": round(r["acc_train_last"], 4)})
+                  "acc_train_last_epoch": round(r["acc_train_last"], 4),
+                  **({"acc_val_last_iterate": round(r["acc_val_last_iterate"], 4), "acc_val_averaged": round(r["acc_val_last"], 4)} if args.avg else {})})
         everything = np.arange(len(y_np))
         r = fit(everything, everything[:0], args.seed + 7777, "all", args.out, keep_best=False)
         emit({"done": True, "kfold": args.kfold, "acc_val_mean": round(float(np.mean(accs)), 4) if rank == 0 else None,
@@ -485,6 +536,7 @@ def main(argv=None) -> int:
 
     r = fit(tr_idx, va_idx, args.seed, "split", args.out, keep_best=True)
     emit({"done": True, "best_val_acc": r["best_val_acc"], "best_epoch": r["best_epoch"], "acc_val_last_epoch": r["acc_val_last"],
+          **({"acc_val_last_iterate": r["acc_val_last_iterate"], "acc_val_averaged": r["acc_val_last"]} if args.avg else {}),
           "checkpoint": args.out, "world": world,
           "n_train": int(len(tr_idx)), "n_val": int(len(va_idx)), "args": shown_args()})
     return 0

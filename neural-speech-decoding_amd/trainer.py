@@ -95,10 +95,18 @@ def broadcast_parameters(flat: torch.Tensor, group=None, src: int = 0) -> None:
 
 
 class Trainer:
+    average: Optional[ops.Average] = None        # weight averaging is off unless __init__ turns it on
+    _avg_state: Optional[torch.Tensor] = None
+
     def __init__(self, model: EEG_LSTM, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None,
                  augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None,
-                 clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None):
+                 clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None,
+                 average: Optional[ops.Average] = None):
+        """average: an ops.Average -- the update launch also keeps an exponential moving average or a running mean (SWA) of the
+        parameters (averaged_model()); no extra launch.  Averaging switches the guarded tail on, as clip_grad_norm=0.0 does: it does
+        not clip, and a step whose gradient norm is not finite is skipped and counted (skipped_steps()); a skipped step does not
+        average.  World > 1: every rank averages its identical replica, with no communication.  None: today's calls, launch for launch."""
         self.model = model
         self.spec = model.spec
         self.flat = model.flat_parameters()
@@ -112,8 +120,13 @@ class Trainer:
         if clip_grad_norm is not None and not clip_grad_norm >= 0.0:
             raise ValueError(f"Trainer: clip_grad_norm {clip_grad_norm!r} negative or NaN")
         self.clip_grad_norm, self.lr_schedule = clip_grad_norm, lr_schedule
-        self._opt_on = clip_grad_norm is not None or lr_schedule is not None
+        if average is not None and not isinstance(average, ops.Average):
+            raise ValueError(f"Trainer: average {average!r}: an ops.Average or None")
+        self.average = average
+        self._opt_on = clip_grad_norm is not None or lr_schedule is not None or average is not None
         self._opt_state = ops.opt_state(self.flat.numel(), 1, self.flat.device) if self._opt_on else None
+        self._avg_state = ops.avg_state(self.flat.numel(), 1, self.flat.device) if average is not None else None
+        self._avg_model = None
         # the flat gradient with ONE extra element behind it: the bf16 path's failure flag (ops.seq_guard).  The whole buffer is
         # what the ranks all-reduce, so a scan time-out on ANY rank makes EVERY rank skip the update (guarded Adam) -- still
         # one collective per step.  Always 0 on the fp32 path.
@@ -198,7 +211,8 @@ class Trainer:
         """adam= of ops.train_step_grads: the update in the reduction's tail (with clipping / a schedule: nsd_grad_reduce_clip_adam)"""
         if not self._opt_on:
             return dict(m=self.m, v=self.v, **self._hyper())
-        return dict(m=self.m, v=self.v, opt=self._opt(), opt_state=self._opt_state, step=self.step_count, step_dev=step_dev)
+        return dict(m=self.m, v=self.v, opt=self._opt(), opt_state=self._opt_state, step=self.step_count, step_dev=step_dev,
+                    avg=self.average, avg_state=self._avg_state)
 
     def _adam(self, step_dev: Optional[torch.Tensor] = None) -> None:
         # bf16 path: skipped on the device when any rank's scan timed out (self._skip, summed over ranks by the all-reduce)
@@ -207,6 +221,10 @@ class Trainer:
             # flat route: every rank forms the norm of the same all-reduced bits, hence the same coef
             opt = self._opt()
             ops.grad_norm(self.grads, self._opt_state, opt.grad_scale)
+            if self.average is not None:
+                ops.adam_step_clip_avg(self.flat, self.grads, self.m, self.v, opt, self._opt_state, self.average, self._avg_state,
+                                       step=self.step_count, step_dev=step_dev, skip=skip)
+                return
             ops.adam_step_clip(self.flat, self.grads, self.m, self.v, opt, self._opt_state, step=self.step_count, step_dev=step_dev, skip=skip)
             return
         ops.adam_step(self.flat, self.grads, self.m, self.v, skip=skip, step_dev=step_dev, **self._hyper())
@@ -308,9 +326,12 @@ class Trainer:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 snap = (self.flat.clone(), self.m.clone(), self.v.clone())
+                avg_snap = self._avg_state.clone() if self._avg_state is not None else None
                 self._issue_segment_a(B, T)
                 self._issue_segment_b()
                 self.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])     # the warm-up step does not count
+                if avg_snap is not None:
+                    self._avg_state.copy_(avg_snap)
                 self._step_dev.fill_(self.step_count)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
@@ -406,9 +427,31 @@ class Trainer:
         """Updates skipped on the device because the gradient norm was not finite (sticky; 0 with both options off)."""
         return ops.opt_records(self._opt_state)[0]["skipped"] if self._opt_on else 0
 
+    # ---- weight averaging ----------------------------------------------------------------------------------------------
+    def averaged_weights(self) -> torch.Tensor:
+        """The averaged parameter row, a flat fp32 view of the device buffer the update launch writes (it follows later steps)."""
+        if self.average is None:
+            raise ops.NsdError("Trainer: no weight averaging (pass average=ops.Average(...))")
+        return ops.avg_rows(self._avg_state, 1, self.flat.numel())[0]
+
+    def averaged_count(self) -> int:
+        """How many steps the average holds (n_avg; synchronises).  0: no step has averaged yet and the row holds nothing of use."""
+        return ops.avg_records(self._avg_state)[0]["n_avg"] if self.average is not None else 0
+
+    def averaged_model(self) -> EEG_LSTM:
+        """An EEG_LSTM (eval mode) whose parameters are views of the averaged row: forward, state_dict, save_reference_checkpoint and
+        SimplePredictor-style consumers work on it, and it follows later steps.  Before the first averaged step its weights are
+        whatever the row held (zeros from the allocation): see averaged_count()."""
+        if self._avg_model is None:
+            self._avg_model = self.model.view_of(self.averaged_weights())
+        return self._avg_model
+
     def state_dict(self):
-        return {"model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
-                "adam_m": self.m.cpu(), "adam_v": self.v.cpu(), "step": self.step_count, "skipped": self.skipped_steps()}
+        sd = {"model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+              "adam_m": self.m.cpu(), "adam_v": self.v.cpu(), "step": self.step_count, "skipped": self.skipped_steps()}
+        if self.average is not None:
+            sd["avg_row"], sd["avg_n"] = self.averaged_weights().cpu(), self.averaged_count()
+        return sd
 
     def load_state_dict(self, sd):
         self.model.load_state_dict(sd["model"], strict=True)
@@ -418,6 +461,9 @@ class Trainer:
         if self._opt_on:
             self._opt_state[12:16].view(torch.int32).fill_(int(sd.get("skipped", 0)))
             self._step_dev.fill_(self.step_count)            # a captured graph reads the step, and with it the schedule, from here
+        if self.average is not None and "avg_row" in sd:
+            self.averaged_weights().copy_(sd["avg_row"])
+            self._avg_state[:4].view(torch.int32).fill_(int(sd["avg_n"]))
 
 
 def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:
