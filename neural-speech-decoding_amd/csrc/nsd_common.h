@@ -49,6 +49,22 @@ __device__ __forceinline__ float quad_sum(float v) {
     return v;
 }
 
+// Reduce-scatter of four pair accumulators over a quad: lane s returns the sum, over the quad's four lanes, of the value it OWNS.
+// Ownership rule: slot i of lane s holds gate (or output unit) i ^ s -- the weights are loaded that way once, in front of the time
+// loop -- so slot 0 is always the lane's own value, and the slot a lane needs from its partner is a fixed one: partner s ^ 1 keeps
+// value 1 ^ (s ^ 1) = s in its slot 1 (and 2 ^ s, my slot 2, in its slot 3); after that stage ra is value s and rb is value 2 ^ s
+// over lanes {s, s ^ 1}, and partner s ^ 2 keeps value 2 ^ (s ^ 2) = s in its rb.  Four pair sums and three DPP adds, no select by
+// lane.  With every lane keeping value g in slot g the same sums take six selects (odd ? r1 : r0 ...); each addition here has the
+// two operands it has there -- (own + lane s^1) + (lane s^2 + lane s^3) of the same pair sums -- so the results are the same bits.
+typedef float nsd_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float quad_reduce_scatter(const nsd_f32x2 (&acc)[4]) {
+    const float r0 = acc[0].x + acc[0].y, r1 = acc[1].x + acc[1].y;
+    const float r2 = acc[2].x + acc[2].y, r3 = acc[3].x + acc[3].y;
+    const float ra = r0 + quad_xor1(r1);
+    const float rb = r2 + quad_xor1(r3);
+    return ra + quad_xor2(rb);
+}
+
 // rotation inside a row of 16 lanes (DPP row_ror:N): lane i receives the value of lane (i + N) % 16 or (i - N) % 16 --
 // only used in sums over all rotations by a multiple of 4, where the direction does not matter
 template <int N>

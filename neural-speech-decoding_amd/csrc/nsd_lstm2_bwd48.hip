@@ -112,27 +112,30 @@ __device__ __forceinline__ float slice_dot_t(const float *dv, const f32x2 (&wp)[
             acc[jj] = pk_fma(wp[jj][2 * q + 1], hi, acc[jj]);
         }
     }
-    const int lane = threadIdx.x;
-    const bool odd = (lane & 1) != 0, hi2 = (lane & 2) != 0;
-    const float r0 = acc[0].x + acc[0].y, r1 = acc[1].x + acc[1].y;
-    const float r2 = acc[2].x + acc[2].y, r3 = acc[3].x + acc[3].y;
-    const float ra = (odd ? r1 : r0) + quad_xor1(odd ? r0 : r1);
-    const float rb = (odd ? r3 : r2) + quad_xor1(odd ? r2 : r3);
-    float v = (hi2 ? rb : ra) + quad_xor2(hi2 ? ra : rb);     // unit (lane & 3) over this quad's 4 slices
+    float v = quad_reduce_scatter(acc);                        // unit (lane & 3) over this quad's 4 slices (slot jj: unit jj ^ (lane & 3), see load_wT)
     v += row_ror<4>(v);
     v += row_ror<8>(v);                                        // ... over all 16 slices
     return v;
 }
 
-// weights of slice_dot_t for W [192][48] row-major (nn.LSTM weight_hh / weight_ih layout)
+// weights of slice_dot_t for W [192][48] row-major (nn.LSTM weight_hh / weight_ih layout): slot jj of the lane with quad position
+// kk & 3 holds unit 4 og + (jj ^ (kk & 3)) -- the ownership rule of quad_reduce_scatter (nsd_common.h).  The four units of a row
+// are read in memory order (one 16-byte load per row, as with unit jj in slot jj) and rotated in registers, once per launch: indexed
+// by jj ^ (kk & 3) the read falls apart into four 4-byte loads per row, 48 per lane in front of the first step.
 __device__ __forceinline__ void load_wT(const float *w, const int og, const int kk, f32x2 (&wp)[4][6]) {
+    const bool odd = (kk & 1) != 0, hi = (kk & 2) != 0;
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
+    for (int p = 0; p < 12; ++p) {
+        const float *row = w + (size_t)(12 * kk + p) * H + 4 * og;
+        const float u0 = row[0], u1 = row[1], u2 = row[2], u3 = row[3];
+        const float a0 = odd ? u1 : u0, a1 = odd ? u0 : u1, a2 = odd ? u3 : u2, a3 = odd ? u2 : u3;      // a[i] = u[i ^ (kk & 1)]
+        const float b[4] = {hi ? a2 : a0, hi ? a3 : a1, hi ? a0 : a2, hi ? a1 : a3};                      // b[i] = u[i ^ (kk & 3)]
 #pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            wp[jj][p].x = w[(size_t)(12 * kk + 2 * p) * H + 4 * og + jj];
-            wp[jj][p].y = w[(size_t)(12 * kk + 2 * p + 1) * H + 4 * og + jj];
+        for (int jj = 0; jj < 4; ++jj) {
+            if (p & 1) wp[jj][p >> 1].y = b[jj];
+            else       wp[jj][p >> 1].x = b[jj];
         }
+    }
 }
 
 // One trial per workgroup: the per-step factors of one layer's cells for macro step mn, from the staged records -- what every gate

@@ -101,17 +101,8 @@ __device__ __forceinline__ void load_slice(const float *p, f32x2 (&v)[6]) {
     }
 }
 
-// gate pre-activations of unit j, reduced over the 4 k-slices of the quad; lane s returns the sum of gate s.
-// Reduce-scatter (3 DPP adds, depth 4) instead of 4 full quad sums (8 DPP adds) + a 3-deep select.
-__device__ __forceinline__ float reduce_pick(const f32x2 (&acc)[4], const int s) {
-    const float r0 = acc[0].x + acc[0].y, r1 = acc[1].x + acc[1].y;
-    const float r2 = acc[2].x + acc[2].y, r3 = acc[3].x + acc[3].y;
-    const bool odd = (s & 1) != 0, hi = (s & 2) != 0;
-    const float ra = (odd ? r1 : r0) + quad_xor1(odd ? r0 : r1);   // gate (odd ? 1 : 0) over lanes {s, s^1}
-    const float rb = (odd ? r3 : r2) + quad_xor1(odd ? r2 : r3);   // gate (odd ? 3 : 2) over lanes {s, s^1}
-    return (hi ? rb : ra) + quad_xor2(hi ? ra : rb);
-}
-
+// gate pre-activations of unit j, reduced over the 4 k-slices of the quad: quad_reduce_scatter (nsd_common.h).  Slot i of lane s
+// holds gate i ^ s (the roles load their weights that way), lane s returns the sum of gate s: 3 DPP adds, no select.
 
 // ---- the step's dependent chain, kept as short as the arithmetic allows (every op on it costs ~10 cycles of every
 // step; instructions off it are free) ----
@@ -127,12 +118,17 @@ constexpr float INV_KC = 1.f / KC;
 __host__ __device__ constexpr float gate_scale(const int g) { return g == 2 ? -2.f * LOG2E_F : -LOG2E_F; }
 
 struct CellOut { float gate, c, h; };     // gate: this lane's activation (un-scaled), c: new cell state, h: o * tanh(c) * hmul
-// arg: exp2 argument of this lane's gate; cK: scaled cell state (updated); hmul: multiplier folded into h (dropout)
+// arg: exp2 argument of this lane's gate; cK: scaled cell state (updated); mk: multiplier folded into h by lane 2 (dropout; 1: none)
 // LANEK (LEAN; the two-trial kernels have no registers for the constants): the selects by lane become arithmetic
 // with per-lane constants that the time loop carries -- fma(1, r, 0) and x * 1 are r and x exactly, so the values are the same
 template <bool LANEK>
-__device__ __forceinline__ CellOut cell_step(const float arg, float &cK, const int s, const float hmul) {
+__device__ __forceinline__ CellOut cell_step(const float arg, float &cK, const int s, const float mk) {
     const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(arg));
+    // (LANEK: the lane select of the multiplier is tied behind the first reciprocal -- left to the scheduler it lands between the last
+    // product and the first exponential, on the chain)
+    float mkv = mk;
+    if (LANEK && !__builtin_constant_p(mk)) asm volatile("" : "+v"(mkv) : "v"(r));
+    const float hmul = s == 2 ? mkv : 1.f;
     const float act = LANEK ? fmaf(s == 2 ? 2.f * KC : 1.f, r, s == 2 ? -KC : 0.f)
                             : (s == 2 ? fmaf(2.f * KC, r, -KC) : r);       // lane 2: KC * tanh(pre)
     const float o = quad_bcast<3>(act);
@@ -171,9 +167,9 @@ __device__ __forceinline__ void l0_role(const A &a, FSmem<NB> &sm, const int r, 
     const int T = a.T, B = a.B, C = a.C;
     f32x2 wx[4], wh[4][6];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int row = g * H + j;
-        const float gs = gate_scale(g);
+    for (int g = 0; g < 4; ++g) {                    // slot g: gate g ^ s
+        const int row = (g ^ s) * H + j;
+        const float gs = gate_scale(g ^ s);
         wx[g].x = (2 * s < C) ? gs * a.w_ih0[(size_t)row * C + 2 * s] : 0.f;
         wx[g].y = (2 * s + 1 < C) ? gs * a.w_ih0[(size_t)row * C + 2 * s + 1] : 0.f;
 #pragma unroll
@@ -239,11 +235,11 @@ __device__ __forceinline__ void l0_role(const A &a, FSmem<NB> &sm, const int r, 
                 f32x2 acc[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    acc[g] = pk_fma(wx[g], xv, (f32x2){g == s ? biasK : 0.f, 0.f});
+                    acc[g] = pk_fma(wx[g], xv, (f32x2){g == 0 ? biasK : 0.f, 0.f});      // slot 0: the lane's own gate
 #pragma unroll
                     for (int q = 0; q < 6; ++q) acc[g] = pk_fma(wh[g][q], hv[q], acc[g]);
                 }
-                const CellOut o = cell_step<LEAN<NB>>(reduce_pick(acc, s), c[n], s, s == 2 ? mk : 1.f);   // lane 2: h * dropout multiplier
+                const CellOut o = cell_step<LEAN<NB>>(quad_reduce_scatter(acc), c[n], s, mk);
                 float *sr = &sm.sv[kr][n][0][0];
                 sr[192 + 48 * hslot + j] = o.h;                 // slots: h | c | masked h | spare (h again)
                 sr[192 + 48 + j] = o.c;                         // the quad's four lanes hold the same c
@@ -280,8 +276,8 @@ __device__ __forceinline__ void p_role(const A &a, FSmem<NB> &sm, const int r, c
     for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            wi[g][q].x = gate_scale(g) * a.w_ih1[(size_t)(g * H + j) * H + s * KS + 2 * q];
-            wi[g][q].y = gate_scale(g) * a.w_ih1[(size_t)(g * H + j) * H + s * KS + 2 * q + 1];
+            wi[g][q].x = gate_scale(g ^ s) * a.w_ih1[(size_t)((g ^ s) * H + j) * H + s * KS + 2 * q];      // slot g: gate g ^ s
+            wi[g][q].y = gate_scale(g ^ s) * a.w_ih1[(size_t)((g ^ s) * H + j) * H + s * KS + 2 * q + 1];
         }
     Prof prof = prof_init(a.dbg);
     const int ngrp = (a.B + NB - 1) / NB;
@@ -299,7 +295,7 @@ __device__ __forceinline__ void p_role(const A &a, FSmem<NB> &sm, const int r, c
 #pragma unroll
                     for (int q = 1; q < 6; ++q) acc[g] = pk_fma(wi[g][q], iv[q], acc[g]);
                 }
-                sm.pb[k & 1][n][s * H + j] = reduce_pick(acc, s);
+                sm.pb[k & 1][n][s * H + j] = quad_reduce_scatter(acc);
             }
         };
         for (int m0 = 0; m0 < n_steps; m0 += SRING) {
@@ -326,8 +322,8 @@ __device__ __forceinline__ void l1_role(const A &a, FSmem<NB> &sm, const int r, 
     for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            wh[g][q].x = gate_scale(g) * a.w_hh1[(size_t)(g * H + j) * H + s * KS + 2 * q];
-            wh[g][q].y = gate_scale(g) * a.w_hh1[(size_t)(g * H + j) * H + s * KS + 2 * q + 1];
+            wh[g][q].x = gate_scale(g ^ s) * a.w_hh1[(size_t)((g ^ s) * H + j) * H + s * KS + 2 * q];      // slot g: gate g ^ s
+            wh[g][q].y = gate_scale(g ^ s) * a.w_hh1[(size_t)((g ^ s) * H + j) * H + s * KS + 2 * q + 1];
         }
     const float biasK = (s == 2 ? gate_scale(2) : gate_scale(0)) * (a.b_ih1[s * H + j] + a.b_hh1[s * H + j]);
     const int hslot = (s == 1) ? 0 : s;
@@ -355,13 +351,13 @@ __device__ __forceinline__ void l1_role(const A &a, FSmem<NB> &sm, const int r, 
                 f32x2 acc[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    acc[g] = pk_fma(wh[g][0], hv[0], (f32x2){g == s ? pjb : 0.f, 0.f});
+                    acc[g] = pk_fma(wh[g][0], hv[0], (f32x2){g == 0 ? pjb : 0.f, 0.f});
 #pragma unroll
                     for (int q = 1; q < 6; ++q) acc[g] = pk_fma(wh[g][q], hv[q], acc[g]);
                 }
                 prof_mark<1, false>(prof);       // seg1: 24 pk_fma issued (not necessarily retired)
-                const float arg = reduce_pick(acc, s);
-                prof_mark<2, false>(prof);       // seg2: quad reduction + select
+                const float arg = quad_reduce_scatter(acc);
+                prof_mark<2, false>(prof);       // seg2: quad reduction
                 CellOut o = cell_step<LEAN<NB>>(arg, c[n], s, 1.f);
                 prof_mark<4, true>(prof);        // seg4: gates, cell update, tanh
                 float *sr = &sm.sv[k][n][1][0];

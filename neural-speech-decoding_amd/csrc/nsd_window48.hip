@@ -49,15 +49,8 @@ __device__ __forceinline__ void load_slice(const float *p, f32x2 (&v)[6]) {
     }
 }
 
-// gate pre-activations of unit j, reduced over the 4 k-slices of the quad; lane s returns the sum of gate s
-__device__ __forceinline__ float reduce_pick(const f32x2 (&acc)[4], const int s) {
-    const float r0 = acc[0].x + acc[0].y, r1 = acc[1].x + acc[1].y;
-    const float r2 = acc[2].x + acc[2].y, r3 = acc[3].x + acc[3].y;
-    const bool odd = (s & 1) != 0, hi = (s & 2) != 0;
-    const float ra = (odd ? r1 : r0) + quad_xor1(odd ? r0 : r1);
-    const float rb = (odd ? r3 : r2) + quad_xor1(odd ? r2 : r3);
-    return (hi ? rb : ra) + quad_xor2(hi ? ra : rb);
-}
+// gate pre-activations of unit j, reduced over the 4 k-slices of the quad: quad_reduce_scatter (nsd_common.h).  Slot g of lane s holds
+// gate g ^ s (the weights are loaded that way), lane s returns the sum of gate s
 
 // lane s holds the pre-activation of gate s (i, f, g, o) of its unit; all four lanes of the quad return the same c and h
 __device__ __forceinline__ float cell_step(const float pre, float &c, const float ga, const float gb, const float gc) {
@@ -148,7 +141,7 @@ __global__ __launch_bounds__(NT) void WINDOW48_KERNEL {
         const float *Wm = role == 0 ? a.w_hh0 : role == 1 ? a.w_ih1 : a.w_hh1;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int row = g * H + j;
+            const int row = (g ^ s) * H + j;             // slot g: gate g ^ s
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
                 w[g][q].x = Wm[(size_t)row * H + s * KS + 2 * q];
@@ -242,11 +235,11 @@ __global__ __launch_bounds__(NT) void WINDOW48_KERNEL {
                         f32x2 ac[4];
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            ac[g] = pk_fma(wx[g], xv, (f32x2){g == s ? bias : 0.f, 0.f});
+                            ac[g] = pk_fma(wx[g], xv, (f32x2){g == 0 ? bias : 0.f, 0.f});
 #pragma unroll
                             for (int q = 0; q < 6; ++q) ac[g] = pk_fma(w[g][q], hv[q], ac[g]);
                         }
-                        hlast = cell_step(reduce_pick(ac, s), c, ga, gb, gc);
+                        hlast = cell_step(quad_reduce_scatter(ac), c, ga, gb, gc);
                         if (s == 0) sm.h0[m & 3][j] = hlast;
                     }
                 } else if (role == 1) {
@@ -260,7 +253,7 @@ __global__ __launch_bounds__(NT) void WINDOW48_KERNEL {
 #pragma unroll
                             for (int q = 1; q < 6; ++q) ac[g] = pk_fma(w[g][q], iv[q], ac[g]);
                         }
-                        sm.pb[(m + 1) & 1][s * H + j] = reduce_pick(ac, s);
+                        sm.pb[(m + 1) & 1][s * H + j] = quad_reduce_scatter(ac);
                     }
                 } else if (role == 2) {
                     if (m >= 2 && m <= len + 1) {
@@ -271,11 +264,11 @@ __global__ __launch_bounds__(NT) void WINDOW48_KERNEL {
                         f32x2 ac[4];
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            ac[g] = pk_fma(w[g][0], hv[0], (f32x2){g == s ? pjb : 0.f, 0.f});
+                            ac[g] = pk_fma(w[g][0], hv[0], (f32x2){g == 0 ? pjb : 0.f, 0.f});
 #pragma unroll
                             for (int q = 1; q < 6; ++q) ac[g] = pk_fma(w[g][q], hv[q], ac[g]);
                         }
-                        hlast = cell_step(reduce_pick(ac, s), c, ga, gb, gc);
+                        hlast = cell_step(quad_reduce_scatter(ac), c, ga, gb, gc);
                         if (s == 0) {
                             sm.h1[t & 1][j] = hlast;
                             sm.top[t & 1][j] = res ? hlast + sm.h0[t & 3][j] : hlast;

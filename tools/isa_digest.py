@@ -18,7 +18,8 @@ one source give equal digests; the device ELF itself carries a per-build id and 
 in text order is a step body of some role.  Bodies are grouped by what they hold (packed products, exponentials, matrix and
 store instructions, and for the backward's helper waves 4x4x1 products, bf16 conversions, 32x32x16 tile products and LDS-DMA requests: the groups are named by that, not by role) and by whether control enters or leaves them (a label or a branch inside: a tested body), and each group prints
 its instruction counts, the index of every `s_waitcnt lgkmcnt(0)`, of the first v_pk_fma_f32 / v_pk_mul_f32, of the first v_exp_f32 and
-of every LDS write (the first ds_write_b32 of a chain body is h), with the instructions between the last v_fma_f32 and that write.
+of every LDS write (the first ds_write_b32 of a chain body is h), with the instructions between the last v_fma_f32 and that write, and
+per body the v_cndmask_b32 inside the quad reduction (between the last packed product and the first exponential / last DPP add).
 """
 import argparse
 import concurrent.futures
@@ -154,7 +155,8 @@ def census(csrc, files):
                       f"scalar incl. waits, nops, branches {c('sc')} (branches {c('br')})\n"
                       f"    per body, instr/scalar: {' '.join(str(x['n']) + '/' + str(x['sc']) for x in g)}\n"
                       f"    first body: lgkmcnt(0) at {r['w0']} | first product at {r['p0']} | first v_exp_f32 at {r['e0']} | lds writes at {r['wi']}"
-                      f" | between the last v_fma_f32 and the first write: {r['gap']}")
+                      f" | between the last v_fma_f32 and the first write: {r['gap']}"
+                      f" | selects in the quad reduction: {' '.join(str(x['sel']) for x in g)}")
         for line in asm.splitlines():
             m = re.match(r"^(_Z\w+):", line)
             if m and "kernel" in m.group(1):
@@ -189,6 +191,15 @@ def census(csrc, files):
                         wr = idx(lambda o, a: o.startswith("ds_write"))
                         fm = idx(lambda o, a: o.startswith("v_fma_f32") or o.startswith("v_fmac_f32"))
                         lastf = max([i for i in fm if wr and i < wr[0]], default=None)
+                        # selects inside the quad reduction: v_cndmask_b32 between the last packed product and the first exponential
+                        # (a body without one: the last DPP add)
+                        pks = idx(lambda o, a: o.startswith(("v_pk_fma_f32", "v_pk_mul_f32")))
+                        red_end = None
+                        if pks:
+                            exps = [i for i in idx(lambda o, a: o.startswith("v_exp_f32")) if i > pks[-1]]
+                            dpps = [i for i in idx(lambda o, a: o.startswith("v_add_f32_dpp")) if i > pks[-1]]
+                            red_end = exps[0] if exps else (dpps[-1] if dpps else None)
+                        sel = sum(o.startswith("v_cndmask_b32") for o in names[pks[-1]:red_end]) if red_end is not None else None
                         rec = {"n": len(ops), "vec": sum(o.startswith("v_") for o in names),
                                "pk": sum(o.startswith(("v_pk_fma_f32", "v_pk_mul_f32")) for o in names),
                                "rd": sum(o.startswith("ds_read") for o in names), "wr": len(wr),
@@ -196,7 +207,7 @@ def census(csrc, files):
                                "sc": sum(o.startswith("s_") for o in names), "br": sum(o.startswith(("s_cbranch", "s_branch")) for o in names),
                                "w0": idx(lambda o, a: o == "s_waitcnt" and "lgkmcnt(0)" in a),
                                "p0": first(idx(lambda o, a: o.startswith(("v_pk_fma_f32", "v_pk_mul_f32")))),
-                               "e0": first(idx(lambda o, a: o.startswith("v_exp_f32"))), "wi": wr,
+                               "e0": first(idx(lambda o, a: o.startswith("v_exp_f32"))), "wi": wr, "sel": sel,
                                "gap": names[lastf + 1:wr[0]] if lastf is not None else None}
                         groups.setdefault((role, bool(body["label"] or rec["br"])), []).append(rec)
                 body = {"ops": [], "label": False}
