@@ -528,6 +528,53 @@ int nsd_adam_step_clip_avg(int64_t n, float *p, const float *g, float *m, float 
                            int64_t avg_state_bytes);
 
 /*
+ * ---- sharpness-aware minimisation (SAM, Foret et al. 2021): the ascent between two forward/backward passes (an EXTENSION) ----
+ *
+ * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_sam_state_bytes).  SAM updates the parameters with the
+ * gradient taken at the parameters moved a distance rho uphill along the normalised gradient.  These entry points form that perturbed
+ * copy on the device; no existing entry point changes its launches or its bits, and THE STEP'S TAIL IS UNCHANGED.  The sequence a
+ * caller issues for one step:
+ *   1. pass 1: the training forward/backward with params = p;
+ *   2. the ascent (below): grads of pass 1, and p_adv in sam_state;
+ *   3. pass 2: the same forward/backward calls with params = the model's row in sam_state and the same x / targets / rng (or mask
+ *      tensors) / flags and the same workspace -- the random streams are counter-based, so pass 2 sees pass 1's draws;
+ *   4. any existing tail on p (nsd_grad_reduce, _adam, _clip_adam, their `_avg` and `multi` forms, or the flat route).
+ * The ascent, per model, with g~_e = fp32(grads[e] * grad_scale) and S = sum_e (double)g~_e^2 exactly as the clipped tail defines
+ * and orders them ("global-norm gradient clipping" above):
+ *   es       = (float)((double)rho / (sqrt(S) + 1e-12))
+ *   p_adv[e] = p[e] + es * g~_e                 every fp32 operation rounded once (no contraction), as the averaged row
+ *   rho == 0, or S not finite:  p_adv[e] = p[e], a copy of the word (signed zeros and NaN payloads survive); the branch is uniform
+ *                               over a model's workgroups.  S not finite: the record's sticky `nonfinite` counter + 1.
+ *   record: norm = (float)sqrt(S), scale = es (0 where the row is a copy)
+ * Launches: two, with no signalling between workgroups, no atomics and no fences.  Launch 1 is the clipped tail's own first launch
+ * (from the slabs: grads is nsd_grad_reduce's bit for bit; flat: nsd_grad_norm's) and leaves the partial sums in opt_state's scratch;
+ * launch 2 sums them in the tail's fixed order in every workgroup and writes the rows; workgroup 0 of a model writes its record.
+ * p and grads (flat: g) are inputs of launch 2 only; m and v are not touched.  opt_state's records are not touched either.
+ * sam_state (device, caller-owned, nsd_sam_state_bytes(n_or_P, M) bytes): M records nsd_sam_record, then the rows p_adv [M][n_or_P]
+ * (fp32) from byte 16 * M.  nsd_sam_state_init zeroes the buffer once after allocation (the sticky counter needs it); the rows are
+ * scratch: every ascent writes all of a model's row.
+ *   nsd_sam_ascend        single-rank fp32 route from the slabs of pass 1
+ *   nsd_multi_sam_ascend  M models in the same two launches.  each != 0: sam and grad_scale point to M entries; each == 0: to one
+ *                         entry for all.  Model m is bit for bit the single-model call.  Domain and refusals of
+ *                         nsd_multi_grad_reduce_clip_adam (M = 1 runs nsd_sam_ascend)
+ *   nsd_sam_ascend_flat   from a flat gradient g[0..n): world > 1 after nsd_grad_reduce (each rank along its own shard's gradient),
+ *                         the bf16 sequence path after nsd_seq_train_bwd.  n == 0 launches nothing.
+ * NSD_E_INVALID before any launch: NULL pointers; rho negative or NaN; n < 0; the rows of sam_state overlapping p or grads.
+ * NSD_E_WORKSPACE: opt_state_bytes < nsd_opt_state_bytes, sam_state_bytes < nsd_sam_state_bytes, or a short workspace.
+ */
+typedef struct nsd_sam { float rho; } nsd_sam;
+typedef struct nsd_sam_record { float norm, scale; uint32_t nonfinite, pad; } nsd_sam_record;   /* 16 B per model, first bytes of sam_state */
+int64_t nsd_sam_state_bytes(int64_t n_or_P, int32_t M);
+int nsd_sam_state_init(void *sam_state, int64_t sam_state_bytes, void *stream);
+int nsd_sam_ascend(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, const float *p, const nsd_sam *sam,
+                   float grad_scale, void *opt_state, int64_t opt_state_bytes, void *sam_state, int64_t sam_state_bytes, void *stream);
+int nsd_multi_sam_ascend(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, const float *p,
+                         const nsd_sam *sam, int32_t each, const float *grad_scale /* HOST: M entries (each != 0) or one */,
+                         void *opt_state, int64_t opt_state_bytes, void *sam_state, int64_t sam_state_bytes, void *stream);
+int nsd_sam_ascend_flat(int64_t n, const float *p, const float *g, const nsd_sam *sam, float grad_scale, void *opt_state,
+                        int64_t opt_state_bytes, void *sam_state, int64_t sam_state_bytes, void *stream);
+
+/*
  * ---- early stopping for model batches: held-out metrics, the best-evaluation decision and the snapshot in ONE launch (an EXTENSION) ----
  *
  * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_multi_eval_path).  nsd_multi_eval reads the logits of M

@@ -66,6 +66,16 @@ class Avg(C.Structure):
 NSD_AVG = {"ema": 1, "swa": 2}
 
 
+class Sam(C.Structure):
+    """nsd_sam of include/nsd.h"""
+    _fields_ = [("rho", C.c_float)]
+
+
+class SamRecord(C.Structure):
+    """nsd_sam_record of include/nsd.h"""
+    _fields_ = [("norm", C.c_float), ("scale", C.c_float), ("nonfinite", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class NsdError(RuntimeError):
     pass
 
@@ -236,6 +246,12 @@ SYMBOLS = {
                                                       _vp, _vp, C.c_int64]),
     "nsd_multi_grad_reduce_clip_adam_avg_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp,
                                                            _vp, _vp, C.c_int64]),
+    # sharpness-aware minimisation: the ascent between the two passes of a step (the tail's first launch, then sam_ascend_kernel)
+    "nsd_sam_state_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "nsd_sam_state_init": (C.c_int, [_vp, C.c_int64, _vp]),
+    "nsd_sam_ascend": (C.c_int, [_dp, _fp, C.c_int64, _fp, _fp, _vp, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "nsd_multi_sam_ascend": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "nsd_sam_ascend_flat": (C.c_int, [C.c_int64, _fp, _fp, _vp, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "nsd_multi_infer_scratch_bytes": (C.c_int64, [_dp, C.c_int32]),
     "nsd_multi_infer": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, _fp, _vp, _vp]),
     # early stopping for model batches: metrics, the best-evaluation decision and the snapshot in one launch

@@ -1094,7 +1094,84 @@ int nsd_multi_grad_reduce_clip_adam_avg_each(const nsd_dims *d, int32_t M, const
                                opt_state, opt_state_bytes, stream, avg, avg_state, avg_state_bytes);
 }
 
-int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {
+// ---- sharpness-aware minimisation: the ascent (nsd_sam, include/nsd.h; nsd_optim.hip) -------------------------------------------------
+static bool bytes_overlap(const void *a, int64_t na, const void *b, int64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return na > 0 && nb > 0 && a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
+}
+// refusals shared by the three entry points, before any launch: sam's fields (each: M entries, the entry named), the two state buffers,
+// then the rows of sam_state against p and grads
+static int sam_enter(const char *who, const nsd_sam *sam, int each, const void *p, const void *grads, const void *opt_state, int64_t opt_bytes,
+                     const void *sam_state, int64_t sam_bytes, int64_t n, int M) {
+    if (!sam) { nsd_set_error("%s: sam is NULL", who); return NSD_E_INVALID; }
+    for (int mo = 0; mo < (each ? M : 1); ++mo) {
+        char entry[64];
+        snprintf(entry, sizeof(entry), "%s: sam[%d]", who, mo);
+        if (const int rc = nsd_sam_check(&sam[mo], each ? entry : who)) return rc;
+    }
+    if (!opt_state || !sam_state) { nsd_set_error("%s: opt_state or sam_state is NULL", who); return NSD_E_INVALID; }
+    if (opt_bytes < nsd_opt_state_need(n, M)) {
+        nsd_set_error("%s: opt_state of %lld bytes is smaller than nsd_opt_state_bytes() = %lld", who, (long long)opt_bytes, (long long)nsd_opt_state_need(n, M));
+        return NSD_E_WORKSPACE;
+    }
+    if (sam_bytes < nsd_sam_state_need(n, M)) {
+        nsd_set_error("%s: sam_state of %lld bytes is smaller than nsd_sam_state_bytes() = %lld", who, (long long)sam_bytes, (long long)nsd_sam_state_need(n, M));
+        return NSD_E_WORKSPACE;
+    }
+    const int64_t row_bytes = (int64_t)M * n * (int64_t)sizeof(float);
+    const char *rows = static_cast<const char *>(sam_state) + (size_t)M * sizeof(nsd_sam_record);
+    if (bytes_overlap(rows, row_bytes, p, row_bytes) || bytes_overlap(rows, row_bytes, grads, row_bytes)) {
+        nsd_set_error("%s: the rows of sam_state overlap p or grads", who);
+        return NSD_E_INVALID;
+    }
+    return NSD_OK;
+}
+
+int64_t nsd_sam_state_bytes(int64_t n_or_P, int32_t M) {
+    if (n_or_P < 0 || M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("sam_state_bytes: n = %lld, M = %d (n >= 0, 1 <= M <= %d)", (long long)n_or_P, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    return nsd_sam_state_need(n_or_P, M);
+}
+
+int nsd_sam_state_init(void *sam_state, int64_t sam_state_bytes, void *stream) {
+    if (!sam_state || sam_state_bytes < (int64_t)sizeof(nsd_sam_record)) { nsd_set_error("sam_state_init: sam_state is NULL or shorter than one record"); return NSD_E_INVALID; }
+    return nsd_opt_state_init_launch(sam_state, sam_state_bytes, (hipStream_t)stream);
+}
+
+int nsd_sam_ascend(const nsd_dims *d, const float *workspace, int64_t workspace_bytes, float *grads, const float *p, const nsd_sam *sam,
+                   float grad_scale, void *opt_state, int64_t opt_state_bytes, void *sam_state, int64_t sam_state_bytes, void *stream) {
+    static const char *who = "sam_ascend";
+    if (nsd_check_dims(d) != NSD_OK) return NSD_E_INVALID;
+    if (!workspace || !grads || !p) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (const int rc = sam_enter(who, sam, 0, p, grads, opt_state, opt_state_bytes, sam_state, sam_state_bytes, layout_of(d).total, 1)) return rc;
+    Ctx c;
+    if (const int rc = enter(&c, who, d, true, nullptr, workspace, workspace_bytes, stream); rc < 0) return rc;
+    return nsd_sam_ascend_slabs_launch(slab_set(c), 1, grads, p, &sam->rho, &grad_scale, opt_state, sam_state, who, c.st);
+}
+
+int nsd_multi_sam_ascend(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, const float *p,
+                         const nsd_sam *sam, int32_t each, const float *grad_scale, void *opt_state, int64_t opt_state_bytes, void *sam_state,
+                         int64_t sam_state_bytes, void *stream) {
+    static const char *who = "multi_sam_ascend";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!grads || !p || !grad_scale) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    if (const int rc = sam_enter(who, sam, each, p, grads, opt_state, opt_state_bytes, sam_state, sam_state_bytes, layout_of(d).total, M)) return rc;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
+    if (M == 1) return nsd_sam_ascend(d, workspace, workspace_bytes, grads, p, sam, grad_scale[0], opt_state, opt_state_bytes, sam_state, sam_state_bytes, stream);
+    float rho[NSD_MAX_MODELS], gs[NSD_MAX_MODELS];
+    for (int mo = 0; mo < M; ++mo) { rho[mo] = sam[each ? mo : 0].rho; gs[mo] = grad_scale[each ? mo : 0]; }
+    return nsd_sam_ascend_slabs_launch(slab_set(c), M, grads, p, rho, gs, opt_state, sam_state, who, c.st);
+}
+
+int nsd_sam_ascend_flat(int64_t n, const float *p, const float *g, const nsd_sam *sam, float grad_scale, void *opt_state, int64_t opt_state_bytes,
+                        void *sam_state, int64_t sam_state_bytes, void *stream) {
+    static const char *who = "sam_ascend_flat";
+    if (n < 0 || !p || !g) { nsd_set_error("%s: null pointer or n<0", who); return NSD_E_INVALID; }
+    if (const int rc = sam_enter(who, sam, 0, p, g, opt_state, opt_state_bytes, sam_state, sam_state_bytes, n, 1)) return rc;
+    return nsd_sam_ascend_flat_launch(n, p, g, sam->rho, grad_scale, opt_state, sam_state, (hipStream_t)stream);
+}
+
+int nsd_multi_loss_sum(const nsd_dims *d, int32_t M,const float *workspace, int64_t workspace_bytes, float *out, void *stream) {
     static const char *who = "multi_loss_sum";
     if (const int rc = multi_check(d, M, who)) return rc;
     if (!out) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }

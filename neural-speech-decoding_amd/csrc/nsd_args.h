@@ -198,6 +198,13 @@ int nsd_reduce_clip_adam_launch(const SlabSet &s, int M, float *grads, float *p,
 int nsd_grad_norm_launch(long n, const float *g, float gscale, void *state, hipStream_t st);
 int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float *v, const nsd_opt *o, int step, const long long *step_dev,
                               const float *skip, void *state, hipStream_t st, const NsdAvgSpec *as = nullptr);
+// sharpness-aware minimisation, the ascent (nsd_sam of nsd.h; nsd_optim.hip): the tail's first launch, then sam_ascend_kernel.  rho and
+// gscale: M entries each, already checked; opt_state against nsd_opt_state_need, sam_state against nsd_sam_state_need
+int nsd_sam_check(const nsd_sam *s, const char *who);
+int64_t nsd_sam_state_need(int64_t n, int M);
+int nsd_sam_ascend_slabs_launch(const SlabSet &s, int M, float *grads, const float *p, const float *rho, const float *gscale, void *opt_state,
+                                void *sam_state, const char *who, hipStream_t st);
+int nsd_sam_ascend_flat_launch(long n, const float *p, const float *g, float rho, float gscale, void *opt_state, void *sam_state, hipStream_t st);
 int nsd_seq_guard_launch(const int *header, int status_word, float *flag_out, hipStream_t st);
 int nsd_dropout_mask_launch(uint64_t seed, uint32_t stream_id, float p, long n, float *out, hipStream_t st);
 int nsd_train_masks_launch(uint64_t seed, uint32_t base, const long long *step_dev, float p_lstm, float p_head, long n_lstm,

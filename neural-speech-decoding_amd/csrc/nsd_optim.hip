@@ -396,3 +396,95 @@ int nsd_adam_clip_flat_launch(long n, float *p, const float *g, float *m, float 
     return adam_clip_launch(n, 1, p, g, m, v, opt_kernel_args(o, step, step_dev), flat_parts(n), state, skip, as ? "adam_step_clip_avg" : "adam_step_clip", st,
                             as, step);
 }
+
+// ---- sharpness-aware minimisation: the ascent (nsd_sam of include/nsd.h) -------------------------------------------------------------
+// Two launches with no signalling between workgroups, as the clipped tail: launch 1 is the tail's own (reduce_norm_kernel for the slabs,
+// norm_flat_kernel for a flat gradient) and leaves grads and the partial sums in opt_state's scratch; launch 2, sam_ascend_kernel, sums
+// the partials in the tail's fixed order in every workgroup, forms the step length in double and writes its grid-stride share of the
+// model's perturbed row.  p and grads are inputs only; rho and grad_scale arrive per model by value (blockIdx.y is workgroup-uniform).
+struct SamK { float rho, gscale; };
+struct SamKSet { SamK k[NSD_MAX_MODELS]; };
+__device__ __forceinline__ const SamK &sam_of(const SamK &k, long) { return k; }
+__device__ __forceinline__ const SamK &sam_of(const SamKSet &k, long mo) { return k.k[mo]; }
+
+template <class SK>
+__global__ __launch_bounds__(FLAT_NT) void sam_ascend_kernel(long n, const float *p, const float *g, SK sk, const double *parts, int n_parts,
+                                                             nsd_sam_record *rec, float *rows) {
+    const long mo = blockIdx.y;
+    const SamK &k = sam_of(sk, mo);
+    p += mo * n; g += mo * n; rows += mo * n; parts += mo * n_parts; rec += mo;
+    __shared__ double red[FLAT_NT];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_parts; i += FLAT_NT) s += parts[i];
+    const double S = block_sum_256(s, red);
+    const double nrm = sqrt(S);
+    const bool finite = fabs(S) <= DBL_MAX;                            // false for Inf and NaN
+    const bool move = finite && k.rho != 0.f;                          // uniform over the model's workgroups: every one formed the same S
+    const float es = move ? (float)((double)k.rho / (nrm + 1e-12)) : 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        rec->norm = (float)nrm; rec->scale = es;
+        if (!finite) rec->nonfinite += 1u;                             // one writer per model: no atomic
+    }
+    const long i0 = (long)blockIdx.x * FLAT_NT + threadIdx.x, stride = (long)gridDim.x * FLAT_NT;
+    if (!move) {                                                       // a copy of the words: signed zeros survive
+        for (long i = i0; i < n; i += stride) rows[i] = p[i];
+        return;
+    }
+    for (long i = i0; i < n; i += stride) {
+        const float gt = g[i] * k.gscale;                              // each operation rounded once (-ffp-contract=off)
+        const float up = es * gt;
+        rows[i] = p[i] + up;
+    }
+}
+
+int nsd_sam_check(const nsd_sam *s, const char *who) {
+    if (!s) { nsd_set_error("%s: sam is NULL", who); return NSD_E_INVALID; }
+    if (!(s->rho >= 0.f)) { nsd_set_error("%s: rho %g negative or NaN", who, s->rho); return NSD_E_INVALID; }
+    return NSD_OK;
+}
+int64_t nsd_sam_state_need(int64_t n, int M) { return (int64_t)M * (int64_t)sizeof(nsd_sam_record) + (int64_t)M * n * (int64_t)sizeof(float); }
+
+// rho, gscale: M entries each
+static int sam_ascend_launch(long n, int M, const float *p, const float *g, const float *rho, const float *gscale, long n_parts, void *opt_state,
+                             void *sam_state, const char *who, hipStream_t st) {
+    long blocks = (n + FLAT_NT - 1) / FLAT_NT; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+    const dim3 grid((unsigned)blocks, (unsigned)M);
+    const double *parts = parts_of(opt_state, M);
+    nsd_sam_record *rec = (nsd_sam_record *)sam_state;
+    float *rows = reinterpret_cast<float *>(static_cast<char *>(sam_state) + (size_t)M * sizeof(nsd_sam_record));
+    if (M == 1) {
+        hipLaunchKernelGGL(sam_ascend_kernel<SamK>, grid, dim3(FLAT_NT), 0, st, n, p, g, SamK{rho[0], gscale[0]}, parts, (int)n_parts, rec, rows);
+    } else {
+        SamKSet ks;
+        memset(&ks, 0, sizeof(ks));
+        for (int mo = 0; mo < M; ++mo) ks.k[mo] = SamK{rho[mo], gscale[mo]};
+        hipLaunchKernelGGL(sam_ascend_kernel<SamKSet>, grid, dim3(FLAT_NT), 0, st, n, p, g, ks, parts, (int)n_parts, rec, rows);
+    }
+    NSD_CHECK_LAUNCH(who);
+    return NSD_OK;
+}
+
+// from the slabs of M models (M = 1: the single-model entry point): the tail's reduction with norm, then the ascent
+int nsd_sam_ascend_slabs_launch(const SlabSet &s, int M, float *grads, const float *p, const float *rho, const float *gscale, void *opt_state,
+                                void *sam_state, const char *who, hipStream_t st) {
+    const long P = s.p_lstm + s.ph, cols = col_parts(P);
+    const dim3 wg(ON_COLS * ON_GROUPS);
+    if (M == 1) {
+        hipLaunchKernelGGL(reduce_norm_kernel<false>, dim3((unsigned)cols), wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h, grads,
+                           GScale<false>{gscale[0]}, parts_of(opt_state, M));
+    } else {
+        GScale<true> gs;
+        memset(&gs, 0, sizeof(gs));
+        for (int mo = 0; mo < M; ++mo) gs.g[mo] = gscale[mo];
+        hipLaunchKernelGGL(reduce_norm_kernel<true>, dim3((unsigned)cols, (unsigned)M), wg, 0, st, s.slabs, s.stride, s.n, s.p_lstm, s.hslabs, s.ph, s.n_h,
+                           grads, gs, parts_of(opt_state, M));
+    }
+    NSD_CHECK_LAUNCH(who);
+    return sam_ascend_launch(P, M, p, grads, rho, gscale, cols, opt_state, sam_state, who, st);
+}
+
+int nsd_sam_ascend_flat_launch(long n, const float *p, const float *g, float rho, float gscale, void *opt_state, void *sam_state, hipStream_t st) {
+    if (n <= 0) return NSD_OK;
+    if (const int rc = nsd_grad_norm_launch(n, g, gscale, opt_state, st)) return rc;
+    return sam_ascend_launch(n, 1, p, g, &rho, &gscale, flat_parts(n), opt_state, sam_state, "sam_ascend_flat", st);
+}

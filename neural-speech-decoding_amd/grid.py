@@ -4,7 +4,8 @@
 
 --grid key=v1,v2,... is repeatable and forms the cartesian product (the first key varies slowest).  The keys name options of
 nsd_amd.train: lr, weight_decay, dropout, label_smoothing, mixup, clip_grad_norm, aug_shift, aug_scale, aug_channel_drop, aug_noise, and
-beside --avg ema (weight averaging: the averaged models are the scored ones, as in train) avg_decay.
+beside --avg ema (weight averaging: the averaged models are the scored ones, as in train) avg_decay; and sam_rho (sharpness-aware
+minimisation, train's --sam-rho; 0 means off for that configuration).
 Every other option is that of `train --kfold K --concurrent` and is shared by all configurations.  The runs are configurations x the
 folds of train.concurrent_runs -- the folds, seeds and initial parameters `train --kfold K --concurrent` trains for that configuration --
 packed as whole configurations into launches of at most 32 models (ModelBatchTrainer with per-model settings); the groups run one after
@@ -41,7 +42,9 @@ GRID_KEYS = {"lr": ("lr", float), "weight_decay": ("weight_decay", float), "drop
 # an axis that exists only beside another option: --grid avg_decay=... needs --avg ema (weight averaging; the scored models are then the
 # averaged ones, as in train)
 AVG_GRID_KEYS = {"avg_decay": ("avg_decay", float)}
-ALL_KEYS = {**GRID_KEYS, **AVG_GRID_KEYS}
+# sharpness-aware minimisation: train's --sam-rho as an axis; 0 is a configuration without it
+SAM_GRID_KEYS = {"sam_rho": ("sam_rho", float)}
+ALL_KEYS = {**GRID_KEYS, **AVG_GRID_KEYS, **SAM_GRID_KEYS}
 
 
 def parse_grid(specs: Sequence[str]) -> List[Tuple[str, list]]:
@@ -111,7 +114,7 @@ def main(argv=None) -> int:
     from .ops import Augment, Loss
     from .prep import CausalPrep
     from .train import (average_for, concurrent_epoch, concurrent_runs, early_stop_settings, evaluate, loss_for, padded_parts,
-                        parse_class_weights, schedule_for, selection_text)
+                        parse_class_weights, sam_for, schedule_for, selection_text)
 
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -150,6 +153,7 @@ def main(argv=None) -> int:
             setattr(a, ALL_KEYS[k][0], v)
         try:
             average_for(a, 1)
+            sam_for(a)
             if a.clip_grad_norm is not None and not a.clip_grad_norm >= 0.0:
                 raise ValueError(f"clip_grad_norm {a.clip_grad_norm} negative")
             if not 0.0 <= a.dropout < 1.0:
@@ -219,7 +223,7 @@ def main(argv=None) -> int:
             seeds=[runs[k]["seed"] + 1 for _, k in members], augment=per(lambda c, k: augments[c]),
             loss=per(lambda c, k: loss_for(cfg_args[c], y_np[runs[k]["tr"]] if balanced else y_np)),
             clip_grad_norm=per(lambda c, k: cfg_args[c].clip_grad_norm), lr_schedule=schedule_for(args, args.epochs * steps_per_epoch),
-            average=per(lambda c, k: average_for(cfg_args[c], steps_per_epoch)))
+            average=per(lambda c, k: average_for(cfg_args[c], steps_per_epoch)), sam=per(lambda c, k: sam_for(cfg_args[c])))
         opt_on, avg_on, inner, es_epoch0 = mbt._opt_on, args.avg is not None, None, 0
         avg_start = average_for(cfg_args[0], steps_per_epoch).start_step if avg_on else 0      # (kind, start and stride are shared)
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in members]

@@ -58,12 +58,18 @@ class ModelBatchTrainer:
     skipped step does not average; no extra launch).  averaged_models() are modules on those rows; evaluate / track_best take
     weights="average" to score -- and snapshot -- the averaged rows instead of the last iterates.
 
+    sam: an ops.Sam, or a sequence of M with None for a model without it -- a grid axis like average.  Sharpness-aware minimisation as
+    Trainer's: every step runs forward and backward twice for all models, the ascent of all models (nsd_multi_sam_ascend, each with its
+    own rho) between them, then the usual tail; the guarded tail is on.  A model without SAM beside one with it also takes both passes,
+    the second on a bitwise copy of its parameters, and is bit for bit the model trained without SAM.  last_sams() reads the records;
+    last_losses() are then the second pass's.
+
     Dropout comes from each model's own dropout_p / head_dropout_p (NSD_FLAG_MODEL_P is passed only where they differ).  This corrects
     earlier behaviour: models with different probabilities were all, silently, trained with model 0's."""
 
     def __init__(self, models: Sequence[EEG_LSTM], lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
-                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None, average=None):
+                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None, average=None, sam=None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -102,7 +108,8 @@ class ModelBatchTrainer:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay          # (model 0's where they are per model)
         self.stochastic = stochastic
         # Trainer's recipe (step_recipe.py), applied per model with its own seed and dropout, each launch for all models
-        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev, models=self.models)
+        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev, models=self.models, sam=self._per_model(sam, "sam"))
+        self.sam = self.recipe.sam                                               # None: off; one Sam; or a list of M
         self.augment, self.loss = self.recipe.augment, self.recipe.loss
         self.m = torch.zeros_like(self.params)
         self.v = torch.zeros_like(self.params)
@@ -114,7 +121,8 @@ class ModelBatchTrainer:
             if a is not None and not isinstance(a, ops.Average):
                 raise ValueError(f"ModelBatchTrainer: average {a!r}: an ops.Average or None")
         self._avg_on = any(a is not None for a in self.average)
-        self._opt_on = self._each is not None or clip_grad_norm is not None or lr_schedule is not None or self._avg_on
+        self._opt_on = self._each is not None or clip_grad_norm is not None or lr_schedule is not None or self._avg_on or self.sam is not None
+        self._sam_state = ops.sam_state(P, M, dev) if self.sam is not None else None
         self._opt_state = ops.opt_state(P, M, dev) if self._opt_on else None
         self._avg_state = ops.avg_state(P, M, dev) if self._avg_on else None
         self._avg_models = None
@@ -163,7 +171,7 @@ class ModelBatchTrainer:
         ops.multi_train_step(self.spec, self.params, x, y, buf["ws"], self.grads, rngs=rngs, logits=buf["logits"], m=self.m, v=self.v,
                              step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
                              weight_decay=self.weight_decay, targets=tg, opt=self._opt() if self._opt_on else None, opt_state=self._opt_state,
-                             avg=self.average if self._avg_on else None, avg_state=self._avg_state)
+                             avg=self.average if self._avg_on else None, avg_state=self._avg_state, **self.recipe.sam_args(self._sam_state))
         self._last = (B, T)
 
     def _opt(self):
@@ -198,6 +206,13 @@ class ModelBatchTrainer:
         if weights not in ("last", "average"):
             raise NsdError(f"ModelBatchTrainer.{who}: weights {weights!r}: 'last' or 'average'")
         return self.params if weights == "last" else self.averaged_params()
+
+    def last_sams(self) -> Optional[List[dict]]:
+        """Per model the record of the last ascent (sam=): {norm, scale, nonfinite} as Trainer.last_sam(); None without sam= or before
+        a step.  Synchronises."""
+        if self.sam is None or self._last is None:
+            return None
+        return ops.sam_records(self._sam_state, self.M)
 
     def last_grad_norms(self) -> List[float]:
         """Each model's global gradient norm of the last step, before clipping (synchronises; NaN with both options off or before a step)."""

@@ -613,6 +613,87 @@ def adam_step_clip_avg(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: tor
           state.data_ptr(), _nbytes(state), STREAM, *_avg_args(_avg_struct(avg), avg_state))
 
 
+@dataclass(frozen=True)
+class Sam:
+    """Sharpness-aware minimisation of a trainer (nsd_sam, include/nsd.h; Foret et al. 2021; an extension, the reference has none): a
+    step takes its gradient at the parameters moved a distance rho uphill along the normalised gradient, p + rho g / (|g| + 1e-12),
+    and updates the real parameters with it: two forward/backward passes on the same batch with the same random draws, the ascent
+    between them, then the step's usual tail.  rho = 0 keeps the two passes and perturbs nothing."""
+    rho: float = 0.05
+
+    def __post_init__(self):
+        if not (isinstance(self.rho, (int, float)) and 0.0 <= self.rho < float("inf")):
+            raise ValueError(f"Sam: rho {self.rho!r} must be a finite number >= 0")
+
+    def struct(self) -> "_lib.Sam":
+        return _lib.Sam(float(self.rho))
+
+
+def _sam_struct(s) -> "_lib.Sam":
+    """nsd_sam of a Sam, of None (rho 0: this model's row is a copy of its parameters, `each` only) or of a ready _lib.Sam"""
+    return s if isinstance(s, _lib.Sam) else _lib.Sam(0.0) if s is None else s.struct()
+
+
+def sam_state_bytes(n: int, M: int = 1) -> int:
+    nb = int(_lib.lib().nsd_sam_state_bytes(int(n), int(M)))
+    if nb < 0:
+        check(nb, "nsd_sam_state_bytes")
+    return nb
+
+
+def sam_state(n: int, M: int, device) -> torch.Tensor:
+    """The sam_state of the ascent for M models of n parameters (or a flat vector of n, M = 1): zeroed."""
+    st = torch.empty(sam_state_bytes(n, M), dtype=torch.uint8, device=device)
+    _call("nsd_sam_state_init", st.device, st.data_ptr(), _nbytes(st), STREAM)
+    return st
+
+
+def sam_rows(state: torch.Tensor, M: int, n: int) -> torch.Tensor:
+    """The perturbed rows p_adv of a sam_state as an [M, n] fp32 view (no copy: pass 2 reads its parameters here)."""
+    return state[16 * M:16 * M + 4 * M * n].view(torch.float32).view(M, n)
+
+
+def sam_records(state: torch.Tensor, M: int = 1) -> List[dict]:
+    """The M records at the head of a sam_state: [{norm, scale, nonfinite}] (synchronises)."""
+    raw = state[:16 * M].cpu()
+    f, u = raw.view(torch.float32).view(M, 4), raw.view(torch.int32).view(M, 4)
+    return [dict(norm=float(f[i, 0]), scale=float(f[i, 1]), nonfinite=int(u[i, 2]) & 0xFFFFFFFF) for i in range(M)]
+
+
+def sam_ascend(spec: ModelSpec, ws: torch.Tensor, B: int, T: int, grads: torch.Tensor, p: torch.Tensor, sam, opt_state: torch.Tensor,
+               sam_state: torch.Tensor, *, grad_scale: float = 1.0) -> None:
+    """The ascent of one model from the slabs a forward/backward left in ws (nsd_sam_ascend): grads as nsd_grad_reduce leaves it, the
+    perturbed row in sam_state (sam_rows).  opt_state: the tail's (ops.opt_state(P, 1)), whose scratch carries the partial sums."""
+    d = spec.dims(B, T)
+    P = spec.param_count
+    _call("nsd_sam_ascend", p.device, C.byref(d), _dev_f32(ws, "workspace"), _nbytes(ws), _dev_f32(grads, "grads", (P,)), _dev_f32(p, "p", (P,)),
+          C.byref(_sam_struct(sam)), float(grad_scale), opt_state.data_ptr(), _nbytes(opt_state), sam_state.data_ptr(), _nbytes(sam_state), STREAM)
+
+
+def multi_sam_ascend(spec: ModelSpec, ws: torch.Tensor, B: int, T: int, grads: torch.Tensor, params: torch.Tensor, sam,
+                     opt_state: torch.Tensor, sam_state: torch.Tensor, *, grad_scale=1.0) -> None:
+    """The ascent of M models in the same two launches (nsd_multi_sam_ascend): params / grads [M,P].  sam: a Sam for all models, or a
+    list of M with None for a model that is not perturbed; grad_scale: a float, or a list of M.  Lists of equal entries issue the
+    single setting's call."""
+    M, P = int(params.shape[0]), spec.param_count
+    d = spec.dims(B, T)
+    sam, sams = _per_model(sam, M, "multi: sam")
+    gs, gss = _per_model(grad_scale, M, "multi: grad_scale")
+    each = sams is not None or gss is not None
+    n = M if each else 1
+    arr = (_lib.Sam * n)(*[_sam_struct(s) for s in (sams if sams is not None else [sam] * n)])
+    garr = (C.c_float * n)(*[float(g) for g in (gss if gss is not None else [gs] * n)])
+    _call("nsd_multi_sam_ascend", params.device, C.byref(d), M, ws.data_ptr(), _nbytes(ws), _dev_f32(grads, "grads", (M, P)),
+          _dev_f32(params, "params", (M, P)), C.cast(arr, C.c_void_p), 1 if each else 0, C.cast(garr, C.c_void_p), opt_state.data_ptr(),
+          _nbytes(opt_state), sam_state.data_ptr(), _nbytes(sam_state), STREAM)
+
+
+def sam_ascend_flat(p: torch.Tensor, g: torch.Tensor, sam, opt_state: torch.Tensor, sam_state: torch.Tensor, *, grad_scale: float = 1.0) -> None:
+    """The ascent from a flat gradient (nsd_sam_ascend_flat): world > 1 after nsd_grad_reduce, the bf16 sequence path after its backward."""
+    _call("nsd_sam_ascend_flat", p.device, p.numel(), _dev_f32(p, "p"), _dev_f32(g, "g", p.shape), C.byref(_sam_struct(sam)), float(grad_scale),
+          opt_state.data_ptr(), _nbytes(opt_state), sam_state.data_ptr(), _nbytes(sam_state), STREAM)
+
+
 def _out_f32(out: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
     """The caller's output buffer (element count checked; dtype, device and contiguity by _dev_f32 at the launch), or a fresh one"""
     if out is None:
@@ -712,7 +793,8 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
                      logits: torch.Tensor, grads: torch.Tensor, *, scale: Optional[float] = None, drop_lstm=None,
                      rrelu_slope=None, drop_head=None, residual: bool = False, adam: Optional[dict] = None,
                      fused_head: bool = True, rng: Optional[dict] = None, dx: Optional[torch.Tensor] = None,
-                     targets: Optional[torch.Tensor] = None) -> None:
+                     targets: Optional[torch.Tensor] = None, sam=None, sam_state: Optional[torch.Tensor] = None,
+                     opt_state: Optional[torch.Tensor] = None) -> None:
     """The launches of one training evaluation: lstm fwd + head (fwd, mean CE, bwd) in one launch where the shape allows
     (nsd_lstm_head_train; fused_head=False forces the two separate launches), lstm bwd, slab reduce -> `grads` (flat,
     overwritten).  `logits` [B,K] is an output buffer.
@@ -727,7 +809,14 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
     dx [B,T,C] (optional output): dL/dx from nsd_lstm_bwd where dx_path(spec, B, T); not with rng= (nsd_lstm_bwd_rng has no dx).
 
     targets [B,K] fp32 (labels is then ignored and may be None): the loss is - sum_k targets[b,k] log softmax(logits_b)[k] through the
-    `_soft` entry points (nsd_lstm_head_train_soft / nsd_head_train_soft); the backward launches are the same."""
+    `_soft` entry points (nsd_lstm_head_train_soft / nsd_head_train_soft); the backward launches are the same.
+
+    sam (ops.Sam) with sam_state (ops.sam_state(P, 1)): sharpness-aware minimisation -- the forward/backward launches above are issued
+    twice with the same arguments but the parameters, first on `flat`, then on the perturbed row the ascent leaves in sam_state
+    (nsd_sam_ascend with the tail's grad_scale; without adam=, the data-parallel step, nsd_grad_reduce then nsd_sam_ascend_flat: each
+    rank ascends along its own shard's gradient); the tail is the same call as without sam and updates `flat`.  The ascent's scratch is
+    the opt_state of adam=, or opt_state= where that carries none.  `logits` and the workspace's loss are then pass 2's.  An empty
+    shard launches nothing more than it does without sam.  sam=None: exactly the calls above."""
     B, T, _ = x.shape
     d = spec.dims(B, T)
     flags = _lib.NSD_FLAG_TRAIN | (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags
@@ -746,12 +835,15 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
         if dx is not None:
             raise NsdError("train_step_grads: dx= needs explicit mask tensors (nsd_lstm_bwd_rng forms no input gradient)")
         r = _rng_struct(rng)
-        if targets is not None:
-            _call("nsd_lstm_head_train_soft", dev, C.byref(d), pp, xp, None, None, None, C.byref(r), tgp, scale, flags, wsp, wsn, lp, st)
-        else:
-            _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labp, scale, flags, wsp, wsn, lp, st)
-        _call("nsd_lstm_bwd_rng", dev, C.byref(d), pp, xp, C.byref(r), flags, wsp, wsn, st)
-    else:
+
+    def forward_backward(pp):
+        if rng is not None:
+            if targets is not None:
+                _call("nsd_lstm_head_train_soft", dev, C.byref(d), pp, xp, None, None, None, C.byref(r), tgp, scale, flags, wsp, wsn, lp, st)
+            else:
+                _call("nsd_lstm_head_train_rng", dev, C.byref(d), pp, xp, C.byref(r), labp, scale, flags, wsp, wsn, lp, st)
+            _call("nsd_lstm_bwd_rng", dev, C.byref(d), pp, xp, C.byref(r), flags, wsp, wsn, st)
+            return
         if fused_head and targets is not None:
             _call("nsd_lstm_head_train_soft", dev, C.byref(d), pp, xp, dl, sl, dh, None, tgp, scale, flags, wsp, wsn, lp, st)
         elif fused_head:
@@ -763,6 +855,22 @@ def train_step_grads(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: t
             else:
                 _call("nsd_head_train", dev, C.byref(d), pp, sl, dh, labp, scale, wsp, wsn, lp, st)
         _call("nsd_lstm_bwd", dev, C.byref(d), pp, xp, dl, flags, wsp, wsn, dxp, st)
+
+    forward_backward(pp)
+    if sam is not None and B > 0:
+        # pass 1 is done; the ascent (it reduces pass 1's slabs into grads on the way), then pass 2 at the perturbed row
+        if sam_state is None:
+            raise NsdError("train_step_grads: sam= needs sam_state= (ops.sam_state(P, 1))")
+        scratch = adam["opt_state"] if adam is not None and adam.get("opt") is not None else opt_state
+        if scratch is None:
+            raise NsdError("train_step_grads: sam= needs an opt_state (in adam=, or opt_state=) for the norm's partial sums")
+        if adam is None:
+            _call("nsd_grad_reduce", dev, C.byref(d), wsp, wsn, _dev_f32(grads, "grads", (spec.param_count,)), 0, st)
+            sam_ascend_flat(flat, grads, sam, scratch, sam_state)
+        else:
+            sam_ascend(spec, ws, B, T, grads, flat, sam, scratch, sam_state,
+                       grad_scale=adam["opt"].grad_scale if adam.get("opt") is not None else 1.0)
+        forward_backward(_dev_f32(sam_rows(sam_state, 1, spec.param_count)[0], "sam row"))
     gp = _dev_f32(grads, "grads", (spec.param_count,))
     if adam is None:
         _call("nsd_grad_reduce", dev, C.byref(d), wsp, wsn, gp, 0, st)
@@ -1148,7 +1256,7 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
                      v: Optional[torch.Tensor] = None, step: int = 1, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
                      eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
                      targets: Optional[torch.Tensor] = None, opt=None, opt_state: Optional[torch.Tensor] = None, avg=None,
-                     avg_state: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     avg_state: Optional[torch.Tensor] = None, sam=None, sam_state: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One training step of M models at once: params [M,P], x [M,B,T,C] or shared [B,T,C], labels [M*B] int32, grads [M,P].
     Forward + head + mean CE per model + head backward, BPTT, then the reduction (+ Adam on params / m / v when fuse_adam).
     rngs: None (no dropout, eval RReLU slope) or M dicts {seed, base_stream, p_lstm, p_head}.  Returns logits [M*B, K].
@@ -1159,7 +1267,11 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
     with NSD_FLAG_MODEL_P (each model drops with its own probabilities); equal ones go without the flag, as before.
     avg (ops.Average, or a list of M with None for a model that does not average) with avg_state (ops.avg_state(P, M)) and opt: the
     `_avg` twin of the clipped tail forms each model's weight average in the update launch; a list with different entries goes through
-    nsd_multi_grad_reduce_clip_adam_avg_each together with M opt entries."""
+    nsd_multi_grad_reduce_clip_adam_avg_each together with M opt entries.
+    sam (ops.Sam, or a list of M with None for a model without it) with sam_state (ops.sam_state(P, M)) and opt_state: sharpness-aware
+    minimisation -- forward and backward are issued twice with the same arguments but the parameters, first on params, then on the
+    perturbed rows nsd_multi_sam_ascend leaves in sam_state (each model with its own rho and its opt's grad_scale; a model without
+    SAM runs pass 2 on a bitwise copy of its parameters); the tail is the same call as without sam.  logits are then pass 2's."""
     M = int(params.shape[0])
     B, T, stride = _multi_x(spec, x, M)
     d = spec.dims(B, T)
@@ -1173,13 +1285,24 @@ def multi_train_step(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, lab
     opt, opts = _per_model(opt, M, "multi: opt", key=bytes)
     P = spec.param_count
     pp, xp = _dev_f32(params, "params", (M, P)), _dev_f32(x, "x")
-    if targets is not None:
-        _call("nsd_multi_train_fwd_soft", params.device, C.byref(d), M, pp, xp, stride, rp, _dev_f32(targets, "targets", (M * B, spec.K)), fl,
-              ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits"), STREAM)
-    else:
-        _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), fl, ws.data_ptr(), _nbytes(ws),
-              _dev_f32(logits, "logits"), STREAM)
-    _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, fl, ws.data_ptr(), _nbytes(ws), STREAM)
+
+    def forward_backward(pp):
+        if targets is not None:
+            _call("nsd_multi_train_fwd_soft", params.device, C.byref(d), M, pp, xp, stride, rp, _dev_f32(targets, "targets", (M * B, spec.K)), fl,
+                  ws.data_ptr(), _nbytes(ws), _dev_f32(logits, "logits"), STREAM)
+        else:
+            _call("nsd_multi_train_fwd", params.device, C.byref(d), M, pp, xp, stride, rp, labels.data_ptr(), fl, ws.data_ptr(), _nbytes(ws),
+                  _dev_f32(logits, "logits"), STREAM)
+        _call("nsd_multi_train_bwd", params.device, C.byref(d), M, pp, xp, stride, rp, fl, ws.data_ptr(), _nbytes(ws), STREAM)
+
+    forward_backward(pp)
+    if sam is not None:
+        # pass 1 is done; the ascent of all models (it reduces pass 1's slabs into grads on the way), then pass 2 at the perturbed rows
+        if sam_state is None or opt_state is None:
+            raise NsdError("multi: sam= needs sam_state= (ops.sam_state(P, M)) and opt_state= (the norm's partial sums)")
+        gsc = [o.grad_scale for o in opts] if opts is not None else opt.grad_scale if opt is not None else grad_scale
+        multi_sam_ascend(spec, ws, B, T, grads, params, sam, opt_state, sam_state, grad_scale=gsc)
+        forward_backward(_dev_f32(sam_rows(sam_state, M, P), "sam rows", (M, P)))
     avg, avgs = _per_model(avg, M, "multi: avg")
     if (avg is not None or avgs is not None) and not (fuse_adam and (opt is not None or opts is not None) and avg_state is not None):
         raise NsdError("multi: avg= needs fuse_adam, opt= / opt_state= (the clipped tail forms the average) and avg_state=")

@@ -40,9 +40,17 @@ class StepRecipe:
     effective entries are all equal are the single setting, launch for launch.  Where they differ, self.augment / self.loss are lists
     of M (an Augment() / Loss() with every part off for a model without one: its windows are copied bit for bit and its target rows
     are one-hot), the launches are nsd_augment_each / nsd_mixup_each, and class weights go as [M, K] (a row of ones -- an exact
-    product -- for a model without weights)."""
+    product -- for a model without weights).
 
-    def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None):
+    sam (ops.Sam; with models a sequence of M, None for a model without it): sharpness-aware minimisation.  What it changes in a step
+    is said here and nowhere else: the step's forward/backward launches are issued TWICE, on the parameters and then on the perturbed
+    rows the ascent leaves in the trainer's sam_state, and everything around them once -- prepare() runs once (one augmentation, one
+    mixup), the step counter advances once, and both passes get the same rng() / rngs() dicts or the same explicit mask tensors, so
+    pass 2 sees pass 1's draws (the streams are counter-based).  The tail is the step's usual one, on the real parameters.  SAM is
+    not one of the stochastic parts: stochastic=False keeps it.  self.sam is None (off: today's calls), one Sam, or where the models
+    differ a list of M (None: that model's second pass runs on a copy of its parameters); passes() drives the two passes."""
+
+    def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None):
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
         self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
         self.probs = [(m.dropout_p, m.head_dropout_p) for m in models] if models is not None else None
@@ -61,6 +69,25 @@ class StepRecipe:
             rows = [lo.class_weights for lo in self.loss]
             self.class_weights = None if all(r is None for r in rows) else torch.tensor(
                 [r if r is not None else (1.0,) * self.spec.K for r in rows], dtype=torch.float32, device=device)
+
+        sams = self._entries(sam, M, "sam")
+        for e in sams:
+            if e is not None and not isinstance(e, ops.Sam):
+                raise ValueError(f"StepRecipe: sam {e!r}: an ops.Sam or None")
+        self.sam = sams[0] if all(e == sams[0] for e in sams) else sams
+
+    def sam_args(self, sam_state: Optional[torch.Tensor]) -> dict:
+        """sam= / sam_state= of ops.train_step_grads / ops.multi_train_step (empty without SAM: the calls are today's)"""
+        return {} if self.sam is None else dict(sam=self.sam, sam_state=sam_state)
+
+    def passes(self, params: torch.Tensor, sam_state: Optional[torch.Tensor], forward_backward, ascend) -> None:
+        """The forward/backward passes of a step whose trainer issues them itself (the bf16 sequence path; the fp32 ops take sam_args()
+        and do the same inside): forward_backward(params) once, and with SAM ascend() and forward_backward(perturbed row) -- the
+        callable is the same, so the batch, targets, rng and workspace of the two passes are."""
+        forward_backward(params)
+        if self.sam is not None and sam_state is not None:
+            ascend()
+            forward_backward(ops.sam_rows(sam_state, 1, params.numel())[0])
 
     @staticmethod
     def _entries(v, M: int, name: str) -> list:

@@ -21,7 +21,7 @@ import torch
 
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
-from .ops import Augment, Average, Loss, LrSchedule
+from .ops import Augment, Average, Loss, LrSchedule, Sam
 from .prep import CausalPrep
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
@@ -181,6 +181,17 @@ def average_for(args, steps_per_epoch: int):
                    every=1 if args.avg_every_steps is None else args.avg_every_steps)
 
 
+def sam_for(args):
+    """The ops.Sam of a run from --sam-rho (None without it, and for 0: a grid's configuration without SAM).  ValueError for a
+    negative or non-finite rho."""
+    rho = getattr(args, "sam_rho", None)
+    if rho is None:
+        return None
+    if not 0.0 <= rho < float("inf"):
+        raise ValueError(f"--sam-rho {rho} must be a finite number >= 0")
+    return Sam(rho) if rho > 0 else None
+
+
 def build_parser() -> argparse.ArgumentParser:
     """The options of this command (nsd_amd.grid shares them: its --grid keys name options of this parser)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -257,6 +268,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--avg-decay", type=float, default=None, help="weight averaging: EMA decay in [0, 1) (default 0.999)")
     ap.add_argument("--avg-start-epoch", type=int, default=None, help="weight averaging: first epoch (from 0) whose steps are averaged (default 0)")
     ap.add_argument("--avg-every-steps", type=int, default=None, help="weight averaging: average every N-th step from the start (default 1)")
+    ap.add_argument("--sam-rho", type=float, default=None,
+                    help="sharpness-aware minimisation: every step takes its gradient at the weights moved this distance uphill along the "
+                         "normalised gradient (two forward/backward passes per step, about twice the time; 0.05 is the paper's default; 0 "
+                         "is off).  Turns the guarded step tail on, and loss_last_batch is then the loss at the perturbed weights")
     return ap
 
 
@@ -315,6 +330,7 @@ def main(argv=None) -> int:
     try:
         es = early_stop_settings(args, concurrent=args.concurrent and args.kfold >= 2)
         average_for(args, 1)
+        sam_for(args)
     except ValueError as e:
         ap.error(str(e))
 
@@ -361,7 +377,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS or v is not None)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + ("sam_rho",) or v is not None)}
 
     fold_paths = []
 
@@ -375,8 +391,9 @@ def main(argv=None) -> int:
         steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
         average = average_for(args, steps_per_epoch)
         trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
-                          clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average)
-        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None
+                          clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average,
+                          sam=sam_for(args))
+        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None or sam_for(args) is not None
         scored = model                   # --avg: the averaged model, from its first averaged step on
         acc_va_last_iterate = float("nan")
         tr_dev = torch.from_numpy(tr_idx).to(dev)
@@ -430,8 +447,8 @@ def main(argv=None) -> int:
         average = average_for(args, steps_per_epoch)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
                                 loss=loss_for(args, y_np), clip_grad_norm=args.clip_grad_norm,
-                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average)
-        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None
+                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average, sam=sam_for(args))
+        opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None or sam_for(args) is not None
         avg_on, inner, es_epoch0 = average is not None, None, 0
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
         t0 = time.time()

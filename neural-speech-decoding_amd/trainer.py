@@ -97,13 +97,20 @@ def broadcast_parameters(flat: torch.Tensor, group=None, src: int = 0) -> None:
 class Trainer:
     average: Optional[ops.Average] = None        # weight averaging is off unless __init__ turns it on
     _avg_state: Optional[torch.Tensor] = None
+    sam: Optional[ops.Sam] = None                # so is sharpness-aware minimisation
+    _sam_state: Optional[torch.Tensor] = None
 
     def __init__(self, model: EEG_LSTM, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None,
                  augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None,
                  clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None,
-                 average: Optional[ops.Average] = None):
-        """average: an ops.Average -- the update launch also keeps an exponential moving average or a running mean (SWA) of the
+                 average: Optional[ops.Average] = None, sam: Optional[ops.Sam] = None):
+        """sam: an ops.Sam -- sharpness-aware minimisation: every step runs its forward/backward twice on the same batch with the same
+        random draws, at the parameters and at the parameters moved rho uphill along the normalised gradient (formed on the device,
+        nsd_sam_ascend), and updates the real parameters with the second gradient; about twice the step's time.  It switches the guarded
+        tail on, as average= does: a non-finite second gradient is skipped and counted in skipped_steps().  World > 1: each rank ascends
+        along its own shard's gradient (no extra collective; the paper's per-replica form).  last_sam() reads the ascent's record.
+        average: an ops.Average -- the update launch also keeps an exponential moving average or a running mean (SWA) of the
         parameters (averaged_model()); no extra launch.  Averaging switches the guarded tail on, as clip_grad_norm=0.0 does: it does
         not clip, and a step whose gradient norm is not finite is skipped and counted (skipped_steps()); a skipped step does not
         average.  World > 1: every rank averages its identical replica, with no communication.  None: today's calls, launch for launch."""
@@ -123,7 +130,11 @@ class Trainer:
         if average is not None and not isinstance(average, ops.Average):
             raise ValueError(f"Trainer: average {average!r}: an ops.Average or None")
         self.average = average
-        self._opt_on = clip_grad_norm is not None or lr_schedule is not None or average is not None
+        if sam is not None and not isinstance(sam, ops.Sam):
+            raise ValueError(f"Trainer: sam {sam!r}: an ops.Sam or None")
+        self.sam = sam
+        self._opt_on = clip_grad_norm is not None or lr_schedule is not None or average is not None or sam is not None
+        self._sam_state = ops.sam_state(self.flat.numel(), 1, self.flat.device) if sam is not None else None
         self._opt_state = ops.opt_state(self.flat.numel(), 1, self.flat.device) if self._opt_on else None
         self._avg_state = ops.avg_state(self.flat.numel(), 1, self.flat.device) if average is not None else None
         self._avg_model = None
@@ -144,7 +155,7 @@ class Trainer:
         # what a step does to (windows, labels) before its kernels: step_recipe.py, shared with step_static and ModelBatchTrainer.
         # Each rank augments / mixes inside its own shard with its own seed; the scale stays 1 / global_batch (torch's weighted
         # `mean` divides by the weight sum).
-        self.recipe = StepRecipe(model, stochastic, augment, loss, self.flat.device)
+        self.recipe = StepRecipe(model, stochastic, augment, loss, self.flat.device, sam=sam)
         self.augment, self.loss = self.recipe.augment, self.recipe.loss          # the effective ones (None: off)
         self.step_count = 0
         self._bufs = {}
@@ -259,8 +270,13 @@ class Trainer:
                 self._bufs = {key: {"ws": ops.seq_workspace(sp, B, T, self.flat.device),
                                     "logits": torch.empty((B, sp.K), dtype=torch.float32, device=self.flat.device)}}
             buf = self._bufs[key]
-            ops.seq_train_fwd(sp, self.flat, x, y, buf["ws"], rng=rng, scale=scale, logits=buf["logits"], targets=tg)
-            ops.seq_train_bwd(sp, self.flat, buf["ws"], B, T, rng=rng, grads=self.grads)
+            def forward_backward(params):
+                ops.seq_train_fwd(sp, params, x, y, buf["ws"], rng=rng, scale=scale, logits=buf["logits"], targets=tg)
+                ops.seq_train_bwd(sp, params, buf["ws"], B, T, rng=rng, grads=self.grads)
+
+            # (with sam=: twice, the flat ascent between them -- StepRecipe.passes; an empty shard takes the one pass it takes today)
+            self.recipe.passes(self.flat, self._sam_state if B > 0 else None, forward_backward,
+                               lambda: ops.sam_ascend_flat(self.flat, self.grads, self.sam, self._opt_state, self._sam_state))
             ops.seq_guard(buf["ws"], self._skip)
             if self._carried_failure:                          # (seq_guard overwrites the flag with this workspace's status)
                 self._skip.add_(1.0)
@@ -274,7 +290,8 @@ class Trainer:
             (dl, sl, dh), rng = self._masks(buf), None
         ops.train_step_grads(sp, self.flat, x, buf["ws"], y, buf["logits"], self.grads, scale=scale, drop_lstm=dl,
                              rrelu_slope=sl, drop_head=dh, residual=self.model.residual, fused_head=self.fused_head, rng=rng,
-                             adam=self._fused_tail() if fuse_adam else None, targets=tg)
+                             adam=self._fused_tail() if fuse_adam else None, targets=tg, opt_state=self._opt_state,
+                             **self.recipe.sam_args(self._sam_state))
 
     # ---- hipGraph path ------------------------------------------------------------------------------------
     def static_inputs(self, B: int, T: int):
@@ -304,7 +321,8 @@ class Trainer:
         xin, y, tg = self.recipe.prepare(buf["x"], buf["y"], [self.seed], 0, step_dev=self._step_dev, bufs=buf)
         ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], y, buf["logits"], self.grads,
                              scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual,
-                             adam=self._fused_tail(self._step_dev) if self._opt_on and self.world == 1 else None, targets=tg)
+                             adam=self._fused_tail(self._step_dev) if self._opt_on and self.world == 1 else None, targets=tg,
+                             opt_state=self._opt_state, **self.recipe.sam_args(self._sam_state))
 
     def _issue_segment_b(self) -> None:
         if not (self._opt_on and self.world == 1):
@@ -387,7 +405,7 @@ class Trainer:
     @_on_own_device
     def last_loss(self) -> float:
         """Mean loss of this rank's shard in the most recent step: CE on the labels or, with loss= / float targets, the soft-target
-        loss sum_b loss_b / B (synchronises)."""
+        loss sum_b loss_b / B (synchronises).  With sam= this is the loss of the step's SECOND pass, at the perturbed weights."""
         if not self._last_B:
             return float("nan")
         if self.model.precision == "bf16":
@@ -426,6 +444,15 @@ class Trainer:
     def skipped_steps(self) -> int:
         """Updates skipped on the device because the gradient norm was not finite (sticky; 0 with both options off)."""
         return ops.opt_records(self._opt_state)[0]["skipped"] if self._opt_on else 0
+
+    def last_sam(self) -> Optional[dict]:
+        """The record of the last ascent (sam=): {norm: the first pass's gradient norm, scale: rho / (norm + 1e-12) as the kernel formed
+        it, nonfinite: ascents whose norm was not finite (sticky; the row was then a copy of the parameters)}.  None without sam= or
+        before a step.  Synchronises."""
+        if self.sam is None or not self._last_B:
+            return None
+        with torch.cuda.device(self.flat.device):
+            return ops.sam_records(self._sam_state)[0]
 
     # ---- weight averaging ----------------------------------------------------------------------------------------------
     def averaged_weights(self) -> torch.Tensor:
