@@ -333,6 +333,48 @@ int nsd_mixup(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stri
               float *y, float *targets /* [M*B][K] */, void *stream);
 
 /*
+ * ---- cropped training: random or regular windows cut from the trials of a step, and the trial's decision pooled from its windows'
+ * (an EXTENSION: the reference trains and decides on whole trials) ----
+ *
+ * nsd_crop: x [B,T,C] per model -> y [M][B*R][W][C], row b * R + r of model m = crop r of that model's trial b, in ONE launch for all
+ * models.  W = c->window, R = c->crops.  The offset o(b, r) of a crop, in samples:
+ *   c->hop == 0   o(b, r) = R(P(b, 2048 + r)) mod (T - W + 1)   with R(i) = value(seed, base_stream + 3, i) and P(b, slot) as for
+ *                 nsd_augment, b the trial's index inside ITS model's batch.  Slots 2048 .. 2048 + NSD_CROP_MAX - 1 are ones
+ *                 nsd_augment (0, 1, 256..511) and nsd_mixup (1024, and the index 2^63 | 2^62) leave alone: a cropped step does not move
+ *                 an augmented or mixed step's draws.  W == T: every offset is 0.
+ *   c->hop > 0    o(b, r) = r * hop, no draws (rng may be NULL); (R - 1) * hop + W <= T.  These are the windows k = 0 .. R - 1 that
+ *                 nsd_window_step with {W, hop} decides on the trial from a reset state.
+ * y[row] is a bitwise copy of x[b, o : o + W, :]; labels_out[row] = labels[b]; targets_out[row, :] is a bitwise copy of targets[b, :]
+ * (K = d->K floats); offsets_out[row] = o.  labels / labels_out, targets / targets_out: [M*B] -> [M*B*R] and [M*B][K] -> [M*B*R][K], each
+ * pair optional (an input without its output is ignored); offsets_out: NULL or [M*B*R].
+ *   x_model_stride, rng[m], step_dev   as for nsd_augment (p_lstm / p_head are ignored): with x_model_stride == 0, M models draw apart
+ *                                      from shared trials
+ * NSD_E_INVALID before any launch: M outside [1, NSD_MAX_MODELS]; NULL x / y / c; B < 0, T or C < 1; window outside [1, T]; crops
+ * outside [1, NSD_CROP_MAX]; hop < 0; a regular grid that leaves the trial; NULL rng with hop == 0; labels_out without labels,
+ * targets_out without targets (or with K < 1); a negative x_model_stride or one in (0, B*T*C); y overlapping x; M * B * R above 2^31 - 1.
+ * B = 0 launches nothing.  Only d->B, T, C (and K with targets) are read.  nsd_crop_path: 1 where d and c pass these checks.
+ *
+ * nsd_crop_pool: the trial-level decision from window decisions.  probs [N][R][K] -> probs_out [N][K]:
+ *   probs_out[n, k] = (((0 + probs[n, 0, k]) + probs[n, 1, k]) + ... + probs[n, cnt - 1, k]) / float(cnt)   (fp32, one rounding each)
+ * cnt = R, or counts[n] with counts given.  A count <= 0 or > R, or a non-finite value anywhere in the trial's cnt counted rows, gives
+ * a NaN row.  logits_out (NULL, or [N][K]) = float(log(double(probs_out))): the nsd_multi_eval loss of these "logits" is -log of the
+ * pooled probability of the label (a row of probabilities sums to 1 up to rounding) and their argmax the pooled decision; a NaN row
+ * counts as non-finite there.  The layout is that of nsd_window_step's probs [B,D,K] and counts [B] (N = B, R = D): a sliding decoder's
+ * output pools without a repack.  NSD_E_INVALID before any launch: N < 0, R < 1, K < 1, N * R * K above 2^31 - 1, NULL probs /
+ * probs_out.  N = 0 launches nothing.  Additive: NSD_VERSION stays 301, a caller detects the feature by the symbols.
+ */
+typedef struct nsd_crop_cfg {
+    int32_t window, crops, hop;
+} nsd_crop_cfg;
+#define NSD_CROP_MAX 64
+int nsd_crop_path(const nsd_dims *d, const nsd_crop_cfg *c);
+int nsd_crop(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_crop_cfg *c, const nsd_rng *rng,
+             const int64_t *step_dev, const int32_t *labels, const float *targets, float *y, int32_t *labels_out, float *targets_out,
+             int32_t *offsets_out, void *stream);
+int nsd_crop_pool(int32_t N, int32_t R, int32_t K, const float *probs /* [N][R][K] */, const int32_t *counts /* NULL or [N] */,
+                  float *probs_out /* [N][K] */, float *logits_out /* NULL or [N][K] */, void *stream);
+
+/*
  * ---- global-norm gradient clipping and learning-rate schedules in the step tail (an EXTENSION: the reference's recipe is missing) ----
  *
  * Step indexing: s is the 1-based Adam step, e = s - 1.

@@ -43,6 +43,14 @@ class Mix(C.Structure):
     _fields_ = [("mix", C.c_float), ("smoothing", C.c_float)]
 
 
+class CropCfg(C.Structure):
+    """nsd_crop_cfg of include/nsd.h: window W, crops per trial R, hop (0: drawn offsets), in samples"""
+    _fields_ = [("window", C.c_int32), ("crops", C.c_int32), ("hop", C.c_int32)]
+
+
+NSD_CROP_MAX = 64
+
+
 class Opt(C.Structure):
     """nsd_opt of include/nsd.h"""
     _fields_ = ([(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale", "max_norm")]
@@ -216,6 +224,10 @@ SYMBOLS = {
     "nsd_lstm_head_train_soft": (C.c_int, [_dp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, C.c_float, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
     "nsd_multi_train_fwd_soft": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, _vp, _fp, C.c_uint32, _fp, C.c_int64, _fp, _vp]),
     "nsd_seq_train_fwd_soft": (C.c_int, [_dp, _fp, _fp, _vp, _fp, C.c_float, C.c_uint32, _vp, C.c_int64, _fp, _vp]),
+    # cropped training: windows cut from the trials of a step, the trial's decision pooled from its windows'
+    "nsd_crop_path": (C.c_int, [_dp, C.POINTER(CropCfg)]),
+    "nsd_crop": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, C.POINTER(CropCfg), _vp, _vp, _ip, _fp, _fp, _ip, _fp, _ip, _vp]),
+    "nsd_crop_pool": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, _ip, _fp, _fp, _vp]),
     # model-batched H = 48 path (several models per launch)
     "nsd_multi_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_multi_workspace_bytes": (C.c_int64, [_dp, C.c_int32, C.POINTER(WsLayout)]),

@@ -886,6 +886,73 @@ int nsd_mixup_each(const nsd_dims *d, int32_t M, const float *x, int64_t x_model
     return mixup_impl("mixup_each", true, d, M, x, x_model_stride, labels, class_weight, mix, rng, step_dev, y, targets, stream);
 }
 
+// ---- cropped training (nsd_crop / nsd_crop_pool, include/nsd.h; nsd_crop.hip) -------------------------------------------------------
+static bool crop_shape(const nsd_dims *d) {
+    return d && d->B >= 0 && d->T >= 1 && d->C >= 1 && (int64_t)d->T * d->C <= 0x7fffffff;
+}
+static bool crop_cfg_ok(const nsd_dims *d, const nsd_crop_cfg *c) {
+    return c && c->window >= 1 && c->window <= d->T && c->crops >= 1 && c->crops <= NSD_CROP_MAX && c->hop >= 0 &&
+           (c->hop == 0 || (int64_t)(c->crops - 1) * c->hop + c->window <= d->T);
+}
+int nsd_crop_path(const nsd_dims *d, const nsd_crop_cfg *c) { return crop_shape(d) && crop_cfg_ok(d, c) ? 1 : 0; }
+
+int nsd_crop(const nsd_dims *d, int32_t M, const float *x, int64_t x_model_stride, const nsd_crop_cfg *c, const nsd_rng *rng,
+             const int64_t *step_dev, const int32_t *labels, const float *targets, float *y, int32_t *labels_out, float *targets_out,
+             int32_t *offsets_out, void *stream) {
+    static const char *who = "crop";
+    if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (!x || !y || !c) { nsd_set_error("%s: null pointer (x, y, c)", who); return NSD_E_INVALID; }
+    if (!crop_shape(d)) { nsd_set_error("%s: shape B=%d T=%d C=%d (B >= 0, T >= 1, C >= 1)", who, d->B, d->T, d->C); return NSD_E_INVALID; }
+    if (c->window < 1 || c->window > d->T) { nsd_set_error("%s: window %d outside [1, T = %d]", who, c->window, d->T); return NSD_E_INVALID; }
+    if (c->crops < 1 || c->crops > NSD_CROP_MAX) { nsd_set_error("%s: crops %d outside [1, %d]", who, c->crops, NSD_CROP_MAX); return NSD_E_INVALID; }
+    if (c->hop < 0) { nsd_set_error("%s: hop %d negative (0: drawn offsets)", who, c->hop); return NSD_E_INVALID; }
+    if (c->hop > 0 && (int64_t)(c->crops - 1) * c->hop + c->window > d->T) {
+        nsd_set_error("%s: the regular grid leaves the trial: (crops - 1) * hop + window = %lld > T = %d", who,
+                      (long long)((int64_t)(c->crops - 1) * c->hop + c->window), d->T);
+        return NSD_E_INVALID;
+    }
+    if (c->hop == 0 && !rng) { nsd_set_error("%s: drawn offsets (hop = 0) need rng", who); return NSD_E_INVALID; }
+    if (labels_out && !labels) { nsd_set_error("%s: labels_out without labels", who); return NSD_E_INVALID; }
+    if (targets_out && !targets) { nsd_set_error("%s: targets_out without targets", who); return NSD_E_INVALID; }
+    if (targets_out && d->K < 1) { nsd_set_error("%s: targets with K = %d classes (K >= 1)", who, d->K); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x_model_stride < 0 || (x_model_stride > 0 && x_model_stride < n)) {
+        nsd_set_error("%s: x_model_stride %lld: 0 (one trial set for all models) or >= B*T*C = %lld", who, (long long)x_model_stride, (long long)n);
+        return NSD_E_INVALID;
+    }
+    const int64_t rows = (int64_t)M * d->B * c->crops;
+    if (rows > 0x7fffffff) { nsd_set_error("%s: M * B * crops = %lld rows in one launch exceed 2^31 - 1", who, (long long)rows); return NSD_E_INVALID; }
+    const float *x_end = x + (M - 1) * x_model_stride + n;
+    const float *y_end = y + rows * c->window * d->C;
+    if (n > 0 && x < y_end && y < x_end) { nsd_set_error("%s: y overlaps x (a crop is a copy: no in-place form)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    CropArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.y = y; a.x_stride = x_model_stride; a.step_dev = (const long long *)step_dev;
+    a.labels = labels_out ? labels : nullptr; a.labels_out = labels_out;
+    a.targets = targets_out ? targets : nullptr; a.targets_out = targets_out; a.offsets_out = offsets_out;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.K = targets_out ? d->K : 0; a.M = M;
+    a.W = c->window; a.R = c->crops; a.hop = c->hop;
+    if (c->hop == 0)
+        for (int m = 0; m < M; ++m) { a.seed[m] = rng[m].seed; a.base[m] = rng[m].base_stream; }
+    return nsd_crop_launch(a, (hipStream_t)stream);
+}
+
+int nsd_crop_pool(int32_t N, int32_t R, int32_t K, const float *probs, const int32_t *counts, float *probs_out, float *logits_out,
+                  void *stream) {
+    static const char *who = "crop_pool";
+    if (N < 0 || R < 1 || K < 1) { nsd_set_error("%s: N = %d, R = %d, K = %d (N >= 0, R >= 1, K >= 1)", who, N, R, K); return NSD_E_INVALID; }
+    if ((int64_t)N * R * K > 2147483647LL) {
+        nsd_set_error("%s: N * R * K = %lld probabilities exceed 2^31 - 1", who, (long long)((int64_t)N * R * K)); return NSD_E_INVALID;
+    }
+    if (!probs || !probs_out) { nsd_set_error("%s: null pointer (probs, probs_out)", who); return NSD_E_INVALID; }
+    if (N == 0) return NSD_OK;
+    CropPoolArgs a;
+    a.probs = probs; a.counts = counts; a.probs_out = probs_out; a.logits_out = logits_out; a.N = N; a.R = R; a.K = K;
+    return nsd_crop_pool_launch(a, (hipStream_t)stream);
+}
+
 // ---- model-batched H = 48 path (nsd_multi_*, include/nsd.h; nsd_multi.h) ----------------------------------------------------------
 // M = 1 runs the single-model entry points themselves.  M > 1: the kernels' model-batched twins on a workspace of M*B trials.
 static bool multi_shape(const nsd_dims *d, int M) {

@@ -171,6 +171,27 @@ struct MixArgs {
     uint32_t base[NSD_MAX_MODELS];
 };
 int nsd_mixup_launch(const MixArgs &a, hipStream_t st);
+// cropped training (nsd_crop / nsd_crop_pool of nsd.h; nsd_crop.hip)
+struct CropArgs {
+    const float *x; float *y;                // [B,T,C] per model -> [M][B*R][W][C]
+    long long x_stride;                      // floats between two models' trials (0: shared)
+    const long long *step_dev;               // null, or the device step counter the stream id is formed from
+    const int32_t *labels; int32_t *labels_out;      // null together, or [M*B] -> [M*B*R]
+    const float *targets; float *targets_out;        // null together, or [M*B][K] -> [M*B*R][K]
+    int32_t *offsets_out;                    // null, or [M*B*R]
+    int B, T, C, K, M;
+    int W, R, hop;                           // hop 0: drawn offsets; > 0: offset r * hop
+    uint64_t seed[NSD_MAX_MODELS];
+    uint32_t base[NSD_MAX_MODELS];
+};
+int nsd_crop_launch(const CropArgs &a, hipStream_t st);
+struct CropPoolArgs {
+    const float *probs;                      // [N][R][K]
+    const int32_t *counts;                   // null (every trial counts R windows), or [N]
+    float *probs_out, *logits_out;           // [N][K]; logits_out may be null
+    int N, R, K;
+};
+int nsd_crop_pool_launch(const CropPoolArgs &a, hipStream_t st);
 // gradient slabs of M models in one workspace: per model n LSTM slabs (one per backward workgroup) and n_h head slabs (one per trial)
 struct SlabSet {
     const float *slabs; long stride; int n; long p_lstm;

@@ -20,6 +20,10 @@ No final model is trained.
 holds out an inner part of its training trials, all models of a launch are scored on theirs after each epoch in two launches
 (ModelBatchTrainer.track_best), and the validation accuracy of a run is that of its best-epoch model, scored once at the end; the
 summaries then carry the selection rule, the chosen epochs and the confusion matrices.
+
+--crop-seconds S [--crops-per-trial R] [--crop-hop-seconds H] (train's options, shared by all configurations: the window sets the launch
+dimensions): cropped training; every accuracy is then trial-level, pooled over the evaluation grid, and the records carry the first
+window's accuracy beside it.
 """
 from __future__ import annotations
 
@@ -111,10 +115,10 @@ def main(argv=None) -> int:
     from . import data as D
     from .lstm_eeg_model import EEG_LSTM
     from .multimodel import ModelBatchTrainer
-    from .ops import Augment, Loss
+    from .ops import Augment, Crop, Loss
     from .prep import CausalPrep
-    from .train import (average_for, concurrent_epoch, concurrent_runs, early_stop_settings, evaluate, loss_for, padded_parts,
-                        parse_class_weights, sam_for, schedule_for, selection_text)
+    from .train import (average_for, concurrent_epoch, concurrent_runs, crop_for, early_stop_settings, evaluate, evaluate_cropped, loss_for,
+                        padded_parts, parse_class_weights, sam_for, schedule_for, selection_text)
 
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -132,8 +136,15 @@ def main(argv=None) -> int:
         args.lr_schedule = "constant"
     try:
         es = early_stop_settings(args, concurrent=True)          # (the grid's runs are always the model-batched folds)
+        crops = crop_for(args)
     except ValueError as e:
         ap.error(str(e))
+    crop_train, crop_eval = crops if crops is not None else (None, None)
+    pooled = dict(crop=crop_eval) if crop_eval is not None else {}           # held-out scoring of a cropped run is trial-level
+
+    def score(mdl, xs, ys):
+        """(accuracy, first-window accuracy or None), as train's"""
+        return (evaluate(mdl, xs, ys), None) if crop_eval is None else evaluate_cropped(mdl, xs, ys, crop_eval)
     prep_stage = any(v is not None for v in (args.prep_highpass, args.prep_lowpass, args.prep_notch, args.prep_zscore_seconds)) or args.prep_car
     prep_design = None
     if prep_stage:
@@ -216,14 +227,15 @@ def main(argv=None) -> int:
         models = []
         for c, k in members:
             torch.manual_seed(runs[k]["seed"])
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, cfg_args[c].dropout, normalize=args.normalize, prep=prep_all).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, cfg_args[c].dropout, normalize=args.normalize, prep=prep_all, crop=crop_train).to(dev).train())
         per = lambda f: [f(c, k) for c, k in members]                                         # noqa: E731
         mbt = ModelBatchTrainer(
             models, lr=per(lambda c, k: cfg_args[c].lr), weight_decay=per(lambda c, k: cfg_args[c].weight_decay),
             seeds=[runs[k]["seed"] + 1 for _, k in members], augment=per(lambda c, k: augments[c]),
             loss=per(lambda c, k: loss_for(cfg_args[c], y_np[runs[k]["tr"]] if balanced else y_np)),
             clip_grad_norm=per(lambda c, k: cfg_args[c].clip_grad_norm), lr_schedule=schedule_for(args, args.epochs * steps_per_epoch),
-            average=per(lambda c, k: average_for(cfg_args[c], steps_per_epoch)), sam=per(lambda c, k: sam_for(cfg_args[c])))
+            average=per(lambda c, k: average_for(cfg_args[c], steps_per_epoch)), sam=per(lambda c, k: sam_for(cfg_args[c])),
+            crop=crop_train)
         opt_on, avg_on, inner, es_epoch0 = mbt._opt_on, args.avg is not None, None, 0
         avg_start = average_for(cfg_args[0], steps_per_epoch).start_step if avg_on else 0      # (kind, start and stride are shared)
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in members]
@@ -245,32 +257,34 @@ def main(argv=None) -> int:
                 # every epoch: all members on their inner parts, the best-epoch decision and the snapshot, in two launches
                 if inner is None:
                     es_epoch0 = epoch        # (--avg-start-epoch: evaluation n is epoch es_epoch0 + n - 1)
-                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"], **wts)
+                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"], **wts, **pooled)
                 last = last or all(e["stopped"] for e in inner)
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
                 norms, lrs, skipped = (mbt.last_grad_norms(), mbt.last_lrs(), mbt.skipped_steps()) if opt_on else (None, None, None)
                 if es:
-                    ev_tr, ev_va = mbt.evaluate(*held["tr"], **wts), mbt.evaluate(*held["va"], **wts)
+                    ev_tr, ev_va = mbt.evaluate(*held["tr"], **wts, **pooled), mbt.evaluate(*held["va"], **wts, **pooled)
+                    ev_first = mbt.evaluate(*held["va"], **wts, crop=Crop(crop_eval.window, 1, 1)) if pooled else None
                 scored = mbt.averaged_models() if avg_ready else models
                 for i, (c, k) in enumerate(members):
                     if es:
-                        acc_tr, acc_va = ev_tr[i]["acc"], ev_va[i]["acc"]
+                        acc_tr, acc_va, acc_first = ev_tr[i]["acc"], ev_va[i]["acc"], ev_first[i]["acc"] if pooled else None
                     else:
-                        acc_tr = evaluate(scored[i], x_all[tr_devs[k]], y_all[tr_devs[k]])
-                        acc_va = evaluate(scored[i], x_all[runs[k]["va"]], y_all[runs[k]["va"]])
+                        acc_tr = score(scored[i], x_all[tr_devs[k]], y_all[tr_devs[k]])[0]
+                        acc_va, acc_first = score(scored[i], x_all[runs[k]["va"]], y_all[runs[k]["va"]])
                     res[i] = dict(acc_train_last=acc_tr, acc_val_last=acc_va)
                     emit({"run": tag(runs[k]), "config_index": c, "config": configs[c], "epoch": epoch, "loss_last_batch": round(losses[i], 5),
                           "acc_train": round(acc_tr, 4), "acc_val": round(acc_va, 4), "n_val": int(len(runs[k]["va"])),
                           "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
                           **({"grad_norm": norms[i], "lr": lrs[i], "skipped": skipped[i]} if opt_on else {}),
+                          **({"acc_val_first_window": round(acc_first, 4)} if acc_first is not None else {}),
                           **({"loss_inner": round(inner[i]["loss"], 5), "acc_inner": round(inner[i]["acc"], 4),
                               "best_epoch": es_epoch0 + inner[i]["best_eval"] - 1, "stopped": inner[i]["stopped"]} if inner is not None else {})})
             if es and last:
                 break
         if es:       # the outer folds of the best-epoch models, in one call
             best = mbt.restore_best()
-            final = mbt.evaluate(*held["va"])
+            final = mbt.evaluate(*held["va"], **pooled)
             for i in range(len(members)):
                 res[i]["acc_val_last"] = final[i]["acc"]
         for c in group:

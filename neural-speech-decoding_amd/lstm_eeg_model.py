@@ -184,12 +184,18 @@ class EEG_LSTM(nn.Module):
       prep           a CausalPrep: the causal front end (nsd_prep_step, window mode: every trial from a reset state) in front of the
                      LSTM, where normalize runs its z-score -- the model then sees what a StreamDecoder feeds it chunk by chunk.
                      Not together with normalize; no input gradient is offered through it.
+      crop           an ops.Crop: the window the model was (or is being) trained on by cropped training (Trainer(crop=)).  It changes
+                     nothing in forward(); it travels with the model and its checkpoints so that predict_trials(), SimplePredictor and
+                     open_stream() know the trained window.
     """
 
     def __init__(self, input_size=8, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, *,
                  residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32",
-                 prep: Optional[CausalPrep] = None):
+                 prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None):
         super().__init__()
+        if crop is not None and not isinstance(crop, ops.Crop):
+            raise ValueError(f"crop={crop!r}: expected an ops.Crop")
+        self.crop = crop
         if prep is not None and not isinstance(prep, CausalPrep):
             raise ValueError(f"prep={prep!r}: expected a CausalPrep")
         if prep is not None and normalize:
@@ -262,7 +268,7 @@ class EEG_LSTM(nn.Module):
         if row.dtype != torch.float32 or row.dim() != 1 or row.numel() != sp.param_count or not row.is_contiguous():
             raise NsdError(f"EEG_LSTM.view_of: row must be a contiguous float32 vector of {sp.param_count} elements")
         twin = EEG_LSTM(sp.C, sp.H, sp.L, sp.K, self.head_dropout_p, residual=self.residual, normalize=self.normalize,
-                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep)
+                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop)
         offs = sp.offsets()
         with torch.no_grad():
             for n, p in twin._named_in_order():
@@ -359,6 +365,37 @@ class EEG_LSTM(nn.Module):
         _, probs = ops.infer(self.spec, self.flat_parameters(), x, residual=self.residual, want_probs=True)
         return probs
 
+    @torch.no_grad()
+    def predict_trials(self, x: torch.Tensor, hop: Optional[int] = None, window: Optional[int] = None):
+        """Trial-level decisions of a model that decides on windows shorter than the trial: x [B,T,C] -> (pooled class probabilities
+        [B,K], the windows' probabilities [B,R,K]).  Every whole window of `window` samples (default: the trained one, self.crop's)
+        `hop` samples apart (default: half the window) is decided -- the front end over the whole trial first, then the cut, then
+        with normalize the z-score of each window, as a cropped training step prepares them (nsd_crop) -- and the trial's decision is
+        the mean of its windows' probabilities (nsd_crop_pool).  These are the decisions a sliding decoder with (window, hop) takes on
+        the trial."""
+        if window is None:
+            if self.crop is None:
+                raise NsdError("EEG_LSTM.predict_trials: give window=, or a model that carries its trained window (crop=)")
+            window = self.crop.window
+        hop = max(int(window) // 2, 1) if hop is None else int(hop)
+        x = x.contiguous().float()
+        if x.dim() != 3 or x.shape[-1] != self.spec.C:
+            raise ValueError(f"Expected x of shape [B, T, {self.spec.C}], got {tuple(x.shape)}")
+        B, T, _ = x.shape
+        grid = ops.Crop.grid(T, int(window), hop)
+        if self.prep is not None:
+            x = ops.prep_step(x, self.prep)
+        xc, _, _ = ops.crop(x, grid)
+        if self.normalize:
+            ops.zscore(xc, out=xc)
+        if self.precision == "bf16":
+            self._last_seq_ws = ops.seq_workspace(self.spec, xc.shape[0], xc.shape[1], x.device) if B > 0 else None
+            probs = ops.seq_infer(self.spec, self.flat_parameters(), xc, ws=self._last_seq_ws, want_probs=True)[1]
+        else:
+            _, probs = ops.infer(self.spec, self.flat_parameters(), xc, residual=self.residual, want_probs=True)
+        probs = probs.view(B, grid.crops, self.spec.K)
+        return ops.crop_pool(probs, want_logits=False)[0], probs
+
 
 # Module names under which the reference's PreProcessor can live, in the reference's own resolution order
 # (lstm_eeg_model.py:7-10): package import first (Frontend/app.py:22-28 puts Neuro-Alpha-App/ on sys.path and imports
@@ -451,7 +488,8 @@ class SimplePredictor:
                  preprocess_package: Optional[str] = None, gpu: str = "cuda", residual: bool = False,
                  normalize: bool = False, bidirectional: bool = False, precision: str = "fp32"):
         """A checkpoint written from a model with a causal front end carries it ({"state_dict": ..., "nsd_prep": CausalPrep.to_dict()},
-        trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep."""
+        trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep.  One written from a model trained on
+        crops carries "nsd_crop" = {window, crops, hop} beside it: the model is rebuilt with that ops.Crop (predict_trial, open_stream)."""
         self.device = torch.device(device)
         self.sr = sr
         self.class_names = class_names or CLASS_NAMES
@@ -468,13 +506,14 @@ class SimplePredictor:
                            "no CPU fallback")
         self.gpu = torch.device(gpu)
         state = torch.load(pth_path, map_location="cpu", weights_only=True)
-        prep = None
+        prep = crop = None
         if isinstance(state, dict) and "state_dict" in state:     # both forms, as lstm_eeg_model.py:79-80
             prep = CausalPrep.from_dict(state["nsd_prep"]) if state.get("nsd_prep") is not None else None
+            crop = ops.Crop(**{k: int(v) for k, v in state["nsd_crop"].items()}) if state.get("nsd_crop") is not None else None
             state = state["state_dict"]
         self.model = EEG_LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
                               num_classes=num_classes, dropout=dropout, residual=residual, normalize=normalize,
-                              bidirectional=bidirectional, precision=precision, prep=prep)
+                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop)
         self.model.load_state_dict(state, strict=True)
         self.model.to(self.gpu).eval()
         self.model.flatten_parameters()
@@ -487,6 +526,23 @@ class SimplePredictor:
         _raise_on_poison(self.model, probs, "SimplePredictor.predict")
         y_idx = int(np.argmax(probs))
         return probs, self.class_names[y_idx]
+
+    def predict_trial(self, trial_TxC: np.ndarray, hop_seconds: Optional[float] = None):
+        """The pooled decision of a trial longer than the window the model was trained on (a checkpoint of cropped training):
+        trial_TxC [T, C] -> (probs np.float32[K], label str).  Every whole trained window, hop_seconds apart (default: half the
+        window), is decided as predict() decides it, and the trial's probabilities are the mean of its windows' (nsd_crop_pool)."""
+        crop = getattr(self.model, "crop", None)
+        if crop is None:
+            raise NsdError("SimplePredictor.predict_trial: the checkpoint carries no trained window (nsd_crop): it was trained on whole "
+                           "trials -- use predict()")
+        hop = max(crop.window // 2, 1) if hop_seconds is None else int(round(hop_seconds * self.sr))
+        if hop < 1:
+            raise ValueError(f"SimplePredictor.predict_trial: hop_seconds {hop_seconds!r} is less than one sample")
+        win_probs, _ = self.predict_windows(trial_TxC, crop.window, hop)
+        if win_probs.shape[0] == 0:
+            raise ValueError(f"SimplePredictor.predict_trial: the trial has {np.asarray(trial_TxC).shape[0]} samples, the trained window {crop.window}")
+        pooled = ops.crop_pool(torch.from_numpy(win_probs[None]).to(self.gpu), want_logits=False)[0][0].cpu().numpy().astype(np.float32)
+        return pooled, self.class_names[int(np.argmax(pooled))]
 
     def predict_windows(self, recording_NxC: np.ndarray, window: int, hop: Optional[int] = None):
         """Batched / streaming mode: classify every `window`-sample window of a longer recording
@@ -524,8 +580,12 @@ class SimplePredictor:
         window_seconds and hop_seconds (both, or neither: the object above, unchanged): a continuous stream without cues -- a
         PredictorSlidingStream whose push returns, per stream, a list of (end_sample, probs float32 [K], label) for the windows the
         chunk completed: every hop_seconds, the decision of the model run from a zero state over the last window_seconds (of an
-        EnsemblePredictor: the mean of its members' decisions, all members advanced by one launch per chunk)."""
+        EnsemblePredictor: the mean of its members' decisions, all members advanced by one launch per chunk).  With a checkpoint of
+        cropped training (nsd_crop), hop_seconds alone is enough: window_seconds defaults to the trained window."""
         from .stream import PredictorSlidingStream, PredictorStream
+        crop = getattr(self.model, "crop", None)
+        if window_seconds is None and hop_seconds is not None and crop is not None:
+            window_seconds = crop.window / float(self.sr)         # a model trained on crops: the window it was trained to decide on
         if (window_seconds is None) != (hop_seconds is None):
             raise ValueError("SimplePredictor.open_stream: window_seconds and hop_seconds go together (both, or neither)")
         if chunk_transform is None and not isinstance(self.pre, IdentityPreProcessor):

@@ -64,12 +64,17 @@ class ModelBatchTrainer:
     the second on a bitwise copy of its parameters, and is bit for bit the model trained without SAM.  last_sams() reads the records;
     last_losses() are then the second pass's.
 
+    crop: an ops.Crop -- cropped training as Trainer's: every model's trials are cut into crop.crops windows of crop.window samples in one
+    launch (each model with its own offsets), the step's kernels see (B * crops, window) and each model's loss is the mean over its
+    crops.  One setting for all models: window and crops set the launch dimensions, so a sequence of differing entries is refused.
+    evaluate / track_best take crop=ops.Crop(W, R, hop > 0) to score trials by their pooled windows.
+
     Dropout comes from each model's own dropout_p / head_dropout_p (NSD_FLAG_MODEL_P is passed only where they differ).  This corrects
     earlier behaviour: models with different probabilities were all, silently, trained with model 0's."""
 
     def __init__(self, models: Sequence[EEG_LSTM], lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, seeds: Optional[Sequence[int]] = None, stochastic: bool = True, group=None,
-                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None, average=None, sam=None):
+                 augment=None, loss=None, clip_grad_norm=None, lr_schedule=None, average=None, sam=None, crop=None):
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
@@ -108,7 +113,12 @@ class ModelBatchTrainer:
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay          # (model 0's where they are per model)
         self.stochastic = stochastic
         # Trainer's recipe (step_recipe.py), applied per model with its own seed and dropout, each launch for all models
-        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev, models=self.models, sam=self._per_model(sam, "sam"))
+        self.recipe = StepRecipe(self.models[0], stochastic, augment, loss, dev, models=self.models, sam=self._per_model(sam, "sam"),
+                                 crop=crop)
+        self.crop = self.recipe.crop
+        for mdl in self.models:
+            if self.crop is not None and mdl.crop is None:
+                mdl.crop = self.crop     # as Trainer: the models and their checkpoints carry the trained window
         self.sam = self.recipe.sam                                               # None: off; one Sam; or a list of M
         self.augment, self.loss = self.recipe.augment, self.recipe.loss
         self.m = torch.zeros_like(self.params)
@@ -155,14 +165,16 @@ class ModelBatchTrainer:
         B, T = int(x.shape[-3]), int(x.shape[-2])
         if B == 0:
             raise NsdError("ModelBatchTrainer.step: empty batch")
+        B, T = self.recipe.dims(B, T)        # (with crop=: the crops the kernels see)
         if not ops.multi_path(self.spec, M, B, T):
             raise NsdError(f"ModelBatchTrainer.step: T = {T} is outside the model-batched path (nsd_multi_path: T <= 1024)")
         y = y.to(torch.int32)
+        Bt = int(x.shape[-3])                # trials
         if y.dim() == 1:
-            if y.shape[0] != B:
-                raise NsdError(f"ModelBatchTrainer.step: y has {y.shape[0]} labels for {B} trials")
-            y = y.unsqueeze(0).expand(M, B)
-        if tuple(y.shape) != (M, B):
+            if y.shape[0] != Bt:
+                raise NsdError(f"ModelBatchTrainer.step: y has {y.shape[0]} labels for {Bt} trials")
+            y = y.unsqueeze(0).expand(M, Bt)
+        if tuple(y.shape) != (M, Bt):
             raise NsdError(f"ModelBatchTrainer.step: y must be [M,B] or [B], got {tuple(y.shape)}")
         self.step_count += 1
         x, y, tg = self.recipe.prepare(x, y.contiguous().view(-1), self.seeds, self.step_count, M=M)
@@ -250,10 +262,16 @@ class ModelBatchTrainer:
     # ---- held-out metrics and early stopping for all models (nsd_multi_eval of include/nsd.h) --------------------------------------
     # A trainer on which none of these is called allocates nothing for them and issues exactly the calls it issued without them.
 
-    def _held_out(self, x: torch.Tensor, y: torch.Tensor, counts, select, who: str, weights: str = "last") -> List[dict]:
+    def _held_out(self, x: torch.Tensor, y: torch.Tensor, counts, select, who: str, weights: str = "last", crop=None) -> List[dict]:
         """nsd_multi_infer on the windows (behind the models' front end, as EEG_LSTM.forward), nsd_multi_eval on its logits, ONE read of
         the records: with selection the eval records lie directly in front of the select state in one allocation, so one copy brings
-        both kinds."""
+        both kinds.  crop (a regular grid): the trials are cut as a cropped step cuts them (front end, nsd_crop, z-score of the
+        crops), nsd_multi_infer decides the B * R windows, nsd_crop_pool pools each trial's R decisions and nsd_multi_eval reads the
+        logarithms of the pooled probabilities as its logits: the loss is -log of the pooled probability of the label, the
+        prediction the pooled decision, and n, counts and the confusion matrix count TRIALS."""
+        if crop is not None and (not isinstance(crop, ops.Crop) or crop.hop < 1):
+            raise NsdError(f"ModelBatchTrainer.{who}: crop {crop!r}: an ops.Crop with a regular grid (hop > 0), so that an evaluation "
+                           f"draws nothing and is the sliding decoder's")
         M = self.M
         params = self._weights(weights, who)
         if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != M):
@@ -269,9 +287,18 @@ class ModelBatchTrainer:
         x = x.contiguous().float()
         if self.models[0].prep is not None:
             x = ops.prep_step(x, self.models[0].prep)
-        elif self.models[0].normalize:
+        elif self.models[0].normalize and crop is None:
             x = ops.zscore(x.reshape(-1, T, Cc)).view(x.shape)
-        logits, _ = ops.multi_infer(self.spec, params, x, want_probs=False)
+        if crop is None:
+            logits, _ = ops.multi_infer(self.spec, params, x, want_probs=False)
+        else:
+            crop.check_trial(T)
+            x, _, _ = ops.crop(x, crop, M=M if x.dim() == 4 else 1)      # (shared trials are cut once: a regular grid draws nothing)
+            if self.models[0].normalize:
+                ops.zscore(x.view(-1, crop.window, Cc), out=x.view(-1, crop.window, Cc))
+            _, probs = ops.multi_infer(self.spec, params, x)                       # [M, B*R, K]
+            _, logits = ops.crop_pool(probs.view(M * B, crop.crops, self.spec.K))
+            logits = logits.view(M, B, self.spec.K)
         if select is None:
             return ops.eval_records(ops.multi_eval(logits, y.contiguous(), counts=counts), M, self.spec.K)
         lead = (M * ops.EVAL_RECORD_BYTES + 15) // 16 * 16
@@ -286,17 +313,20 @@ class ModelBatchTrainer:
             r.update(best_eval=s["best_eval"], bad=s["bad"], stopped=bool(s["stopped"]))
         return recs
 
-    def evaluate(self, x: torch.Tensor, y: torch.Tensor, counts=None, weights: str = "last") -> List[dict]:
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, counts=None, weights: str = "last", crop=None) -> List[dict]:
         """Held-out metrics of all M models in two launches and one read: x [M,B,T,C] (each model's own windows) or a shared [B,T,C], y
         [M,B] or [B] class indices.  counts: None, or M ints -- only model m's first counts[m] windows count, the rest is padding
         (folds differ in size by one; the padding may hold anything).  Returns M dicts: loss (mean cross-entropy, summed in double),
         acc, n, nonfinite (windows whose logits were not finite: they count nowhere else and make the loss NaN) and confusion, a
         [K,K] numpy array indexed [label, prediction].  Synchronises.  weights="average": the metrics of the averaged rows
-        (average=) instead of the last iterates."""
-        return self._held_out(x, y, counts, None, "evaluate", weights)
+        (average=) instead of the last iterates.  crop=ops.Crop(W, R, hop > 0): x holds whole trials and every trial is decided by
+        the mean of the class probabilities of its R windows (offsets 0, hop, ...: the decisions a sliding decoder with (W, hop) takes
+        on it); loss is then -log of the pooled probability of the label, and n, counts and confusion count trials.  A trial with a
+        non-finite window is non-finite, and no other."""
+        return self._held_out(x, y, counts, None, "evaluate", weights, crop)
 
     def track_best(self, x: torch.Tensor, y: torch.Tensor, counts=None, metric: str = "loss", patience: int = 0,
-                   min_delta: float = 0.0, weights: str = "last") -> List[dict]:
+                   min_delta: float = 0.0, weights: str = "last", crop=None) -> List[dict]:
         """evaluate(), and in the same launch early stopping per model: is this the model's best evaluation so far (metric "loss": the
         mean loss fell by more than min_delta; "acc": the accuracy rose by more than min_delta, or stayed with a lower loss), if so copy
         its parameter row into a snapshot on the device, else count one more bad evaluation and, with patience > 0, mark the model
@@ -307,7 +337,7 @@ class ModelBatchTrainer:
 
         A stopped model STILL TRAINS: step() keeps updating its parameters until the caller's loop ends (the step kernels know nothing
         of this).  Its snapshot and its record are frozen, so restore_best() gives what stopping it would have given; all_stopped()
-        lets the loop end early."""
+        lets the loop end early.  crop: as evaluate()'s -- the rule then runs on the trial-level (pooled) metrics."""
         if metric not in ("loss", "acc"):
             raise NsdError(f"ModelBatchTrainer.track_best: metric {metric!r}: 'loss' or 'acc'")
         if int(patience) < 0 or not float(min_delta) >= 0.0:
@@ -316,7 +346,7 @@ class ModelBatchTrainer:
         rule = dict(metric=metric, patience=int(patience), min_delta=float(min_delta))
         if self._sel_rule is not None and (rule, weights) != self._sel_rule:
             raise NsdError(f"ModelBatchTrainer.track_best: the rule was {self._sel_rule}, now {(rule, weights)}: one rule per trainer")
-        recs = self._held_out(x, y, counts, rule, "track_best", weights)
+        recs = self._held_out(x, y, counts, rule, "track_best", weights, crop)
         self._sel_rule = (rule, weights)
         return recs
 

@@ -460,6 +460,113 @@ def target_rows(labels: torch.Tensor, K: int, M: int = 1, loss: Optional[Loss] =
 
 
 @dataclass(frozen=True)
+class Crop:
+    """Cropped training (nsd_crop_cfg of include/nsd.h; an extension, the reference trains on whole trials): every trial of a step is
+    shown to the model as `crops` windows of `window` samples.  hop = 0: the offsets are drawn per trial, crop and step (part of a
+    trainer's stochastic steps); hop > 0: the regular grid 0, hop, 2 hop, ... -- the windows a sliding decoder with (window, hop)
+    decides on the trial, which is how a cropped model is scored (ModelBatchTrainer.evaluate(crop=)) and served."""
+    window: int
+    crops: int = 1
+    hop: int = 0
+
+    def __post_init__(self):
+        for name in ("window", "crops", "hop"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"Crop: {name} {v!r} must be an integer")
+        if self.window < 1:
+            raise ValueError(f"Crop: window {self.window!r} must be >= 1")
+        if not 1 <= self.crops <= _lib.NSD_CROP_MAX:
+            raise ValueError(f"Crop: crops {self.crops!r} outside [1, {_lib.NSD_CROP_MAX}]")
+        if self.hop < 0:
+            raise ValueError(f"Crop: hop {self.hop!r} negative (0: drawn offsets)")
+
+    @property
+    def span(self) -> int:
+        """samples of a trial a regular grid covers (the window itself with drawn offsets)"""
+        return (self.crops - 1) * self.hop + self.window
+
+    def check_trial(self, T: int) -> None:
+        if self.window > T or (self.hop > 0 and self.span > T):
+            raise NsdError(f"{self}: trials of {T} samples are too short (window <= T, and for a regular grid (crops - 1) * hop + window <= T)")
+
+    @staticmethod
+    def grid(T: int, window: int, hop: int) -> "Crop":
+        """The regular grid of every whole window of a trial of T samples: the decisions of a sliding decoder with (window, hop)."""
+        if window > T or hop < 1:
+            raise ValueError(f"Crop.grid: window {window} / hop {hop} for trials of {T} samples")
+        return Crop(window, (T - window) // hop + 1, hop)
+
+
+def crop(x: torch.Tensor, cfg: Crop, rngs=None, *, M: int = 1, labels: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None,
+         step_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+         targets_out: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None):
+    """nsd_crop: cfg.crops windows of cfg.window samples from every trial, one launch for all models -> (y, labels_out, targets_out).
+    x [B,T,C] (one model -> y [B*R,W,C], or shared by M models, each with its own offsets -> [M,B*R,W,C]) or [M,B,T,C]; row b * R + r
+    is crop r of trial b.  labels int32 [M*B] / targets fp32 [M*B,K]: each trial's entry repeated for its crops ([M*B*R] / [M*B*R,K];
+    None stays None).  rngs / step_dev as ops.augment (the stream is base_stream + 3, on index slots of its own); a regular grid
+    (cfg.hop > 0) draws nothing and needs no rngs.  offsets: an int32 [M*B*R] tensor that receives the offsets."""
+    M, B, T, Cc, stride, _ = _model_windows(x, M, "crop")
+    R, W = int(cfg.crops), int(cfg.window)
+    dev = x.device
+    r = _rng_array(rngs, M, "crop", probs=False)
+    rows = M * B * R
+    if out is None:
+        out = torch.empty((B * R, W, Cc) if (M == 1 and x.dim() == 3) else (M, B * R, W, Cc), dtype=torch.float32, device=dev)
+    if out.numel() != rows * W * Cc:
+        raise NsdError(f"crop: out has {out.numel()} elements for {rows} x {W} x {Cc}")
+    K = 1
+    if labels is not None:
+        if labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous() or labels.numel() != M * B:
+            raise NsdError(f"crop: labels must be a contiguous int32 device tensor of {M} x {B} entries")
+        if labels_out is None:
+            labels_out = torch.empty((rows,), dtype=torch.int32, device=dev)
+        if labels_out.dtype != torch.int32 or not labels_out.is_contiguous() or labels_out.numel() != rows:
+            raise NsdError(f"crop: labels_out must be a contiguous int32 tensor of {rows} entries")
+    else:
+        labels_out = None
+    if targets is not None:
+        if targets.dim() != 2 or targets.shape[0] != M * B:
+            raise NsdError(f"crop: targets must be [M*B, K] = [{M * B}, K], got {tuple(targets.shape)}")
+        K = int(targets.shape[1])
+        if targets_out is None:
+            targets_out = torch.empty((rows, K), dtype=torch.float32, device=dev)
+        if targets_out.numel() != rows * K:
+            raise NsdError(f"crop: targets_out has {targets_out.numel()} elements for {rows} x {K}")
+    else:
+        targets_out = None
+    if offsets is not None and (offsets.dtype != torch.int32 or not offsets.is_cuda or not offsets.is_contiguous() or offsets.numel() != rows):
+        raise NsdError(f"crop: offsets must be a contiguous int32 device tensor of {rows} entries")
+    d = Dims(B, T, Cc, 1, 1, K, 1)
+    c = _lib.CropCfg(W, R, int(cfg.hop))
+    _call("nsd_crop", dev, C.byref(d), M, _dev_f32(x, "x"), stride, C.byref(c), C.cast(r, C.c_void_p) if r is not None else None,
+          _step_ptr(step_dev, "crop"), None if labels is None else labels.data_ptr(), _dev_f32(targets, "targets"), _dev_f32(out, "out"),
+          None if labels_out is None else labels_out.data_ptr(), _dev_f32(targets_out, "targets_out"),
+          None if offsets is None else offsets.data_ptr(), STREAM)
+    return out, labels_out, targets_out
+
+
+def crop_pool(probs: torch.Tensor, counts: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+              logits: Optional[torch.Tensor] = None, want_logits: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """nsd_crop_pool: probs [N,R,K] (the class probabilities of each trial's R windows; nsd_window_step's [B,D,K]) -> (pooled
+    probabilities [N,K], their logarithms [N,K] or None).  counts: None, or int32 [N] on the device -- only trial n's first counts[n]
+    windows count (nsd_window_step's counts).  The mean is the serial fp32 sum in ascending window order over the count; a bad count
+    or a non-finite probability among the counted rows gives a NaN row."""
+    if probs.dim() != 3:
+        raise NsdError(f"crop_pool: probs must be [N,R,K], got {tuple(probs.shape)}")
+    N, R, K = (int(v) for v in probs.shape)
+    dev = probs.device
+    if counts is not None and (counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or counts.numel() != N):
+        raise NsdError(f"crop_pool: counts must be a contiguous int32 device tensor of {N} entries")
+    out = _out_f32(out, (N, K), dev, "crop_pool: out")
+    if logits is None and want_logits:
+        logits = torch.empty((N, K), dtype=torch.float32, device=dev)
+    _call("nsd_crop_pool", dev, N, R, K, _dev_f32(probs, "probs"), None if counts is None else counts.data_ptr(), _dev_f32(out, "out"),
+          _dev_f32(logits, "logits", (N, K)), STREAM)
+    return out, logits
+
+
+@dataclass(frozen=True)
 class LrSchedule:
     """Learning-rate schedule of a trainer (the schedule fields of nsd_opt, include/nsd.h; an extension, the reference has none):
     lr_eff(s) = lr * f(s), s the 1-based step.  warmup_steps W: f = s / W for s <= W, then `kind` on e' = s - 1 - W: "constant" f = 1;

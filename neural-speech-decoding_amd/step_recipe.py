@@ -48,9 +48,18 @@ class StepRecipe:
     mixup), the step counter advances once, and both passes get the same rng() / rngs() dicts or the same explicit mask tensors, so
     pass 2 sees pass 1's draws (the streams are counter-based).  The tail is the step's usual one, on the real parameters.  SAM is
     not one of the stochastic parts: stochastic=False keeps it.  self.sam is None (off: today's calls), one Sam, or where the models
-    differ a list of M (None: that model's second pass runs on a copy of its parameters); passes() drives the two passes."""
+    differ a list of M (None: that model's second pass runs on a copy of its parameters); passes() drives the two passes.
 
-    def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None):
+    crop (ops.Crop): cropped training.  The step's kernels then see B * R windows of W samples in place of B trials of T: prepare()
+    cuts them (nsd_crop) behind the front end and in front of the mixing, augment -> prep -> crop -> mixup -- the front end has run
+    over the whole trial before a window begins, as a stream's filter has, and mixup pairs crops.  With normalize the whole-window
+    z-score is of what the model sees: nsd_augment runs without its fused z-score and nsd_zscore_fwd runs on the crops.  Labels and
+    float target rows are repeated per crop.  W and R set the launch dimensions, so cropping is not one of the per-model axes: a
+    sequence must hold equal entries.  Drawn offsets (hop = 0) are a stochastic part, but a deterministic trainer cannot simply drop
+    them -- the step's dimensions hang on the crop -- so stochastic=False with hop = 0 is refused; a regular grid draws nothing and
+    stays.  None: today's step, launch for launch.  dims() gives the dimensions the step's kernels see."""
+
+    def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None, crop=None):
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
         self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
         self.probs = [(m.dropout_p, m.head_dropout_p) for m in models] if models is not None else None
@@ -75,6 +84,25 @@ class StepRecipe:
             if e is not None and not isinstance(e, ops.Sam):
                 raise ValueError(f"StepRecipe: sam {e!r}: an ops.Sam or None")
         self.sam = sams[0] if all(e == sams[0] for e in sams) else sams
+
+        crops = self._entries(crop, M, "crop")
+        for e in crops:
+            if e is not None and not isinstance(e, ops.Crop):
+                raise ValueError(f"StepRecipe: crop {e!r}: an ops.Crop or None")
+        if any(e != crops[0] for e in crops):
+            raise ops.NsdError("StepRecipe: the models have different crop settings: window and crops set the dimensions of the launch, "
+                               "so cropping is not a per-model setting (train models of different windows in different trainers)")
+        self.crop = crops[0]
+        if self.crop is not None and self.crop.hop == 0 and not stochastic:
+            raise ops.NsdError("StepRecipe: stochastic=False with drawn crop offsets (hop = 0): a deterministic trainer draws nothing; "
+                               "give the crop a regular grid (hop > 0)")
+
+    def dims(self, B: int, T: int):
+        """(rows, samples) the step's kernels see for B trials of T samples: (B * crops, window) with a crop, else (B, T)"""
+        if self.crop is None:
+            return B, T
+        self.crop.check_trial(T)
+        return B * self.crop.crops, self.crop.window
 
     def sam_args(self, sam_state: Optional[torch.Tensor]) -> dict:
         """sam= / sam_state= of ops.train_step_grads / ops.multi_train_step (empty without SAM: the calls are today's)"""
@@ -122,8 +150,12 @@ class StepRecipe:
     def static_buffers(self, x: torch.Tensor) -> dict:
         """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""
         buf = {}
-        if self.normalize or self.augment is not None or self.prep is not None:
+        if self.augment is not None or self.prep is not None or (self.normalize and self.crop is None):
             buf["xn"] = torch.empty_like(x)
+        if self.crop is not None:                    # the crops (z-scored in place with normalize) and their labels
+            rows, W = self.dims(int(x.shape[0]), int(x.shape[1]))
+            buf["xc"] = x = torch.empty((rows, W, x.shape[2]), dtype=torch.float32, device=x.device)
+            buf["yc"] = torch.empty((rows,), dtype=torch.int32, device=x.device)
         if self.loss is not None:                    # (a single-model trainer's: self.loss is one Loss)
             buf["tg"] = torch.empty((x.shape[0], self.spec.K), dtype=torch.float32, device=x.device)
             buf["xm"] = torch.empty_like(x) if self.loss.mixup > 0 else None
@@ -137,20 +169,31 @@ class StepRecipe:
         a causal front end nsd_prep_step in window mode (on the augmented windows in place, else into the same buffer), then with loss=
         nsd_mixup on the windows the model would otherwise see (mixup off: it only builds the target rows).  An empty shard launches
         nothing.  step_dev (device step counter, with bufs = the trainer's static buffers): the stream ids come from the counter and
-        the outputs go to bufs' xn / xm / tg."""
+        the outputs go to bufs' xn / xc / yc / xm / tg.
+        With crop: nsd_augment (never z-scoring), nsd_prep_step, nsd_crop -- windows [B*R,W,C] per model, labels or float target
+        rows repeated per crop -- then with normalize nsd_zscore_fwd on the crops in place, then nsd_mixup as above, on crops."""
         bufs = bufs or {}
         x = x.contiguous().float()
         B, T, Cc = x.shape[-3:]
         if B == 0:
             return (x, None, y) if y.is_floating_point() else (x, y, None)
-        if self.augment is not None or self.loss is not None:
+        drawn_crop = self.crop is not None and self.crop.hop == 0
+        if self.augment is not None or self.loss is not None or drawn_crop:
             rngs = [step_rng(s, 0 if step_dev is not None else step) for s in seeds]
         if self.augment is not None:       # a shared [B,T,C] becomes [M,B,T,C], each model with its own draws
-            x = ops.augment(x, self.augment, rngs, M=M, zscore=self.normalize, step_dev=step_dev, out=bufs.get("xn"))
-        elif self.normalize:               # as EEG_LSTM.forward: the model is trained on what it is evaluated on
+            x = ops.augment(x, self.augment, rngs, M=M, zscore=self.normalize and self.crop is None, step_dev=step_dev, out=bufs.get("xn"))
+        elif self.normalize and self.crop is None:   # as EEG_LSTM.forward: the model is trained on what it is evaluated on
             x = ops.zscore(x.reshape(-1, T, Cc), out=bufs.get("xn")).view(x.shape)
         if self.prep is not None:          # augment -> prep -> mixup: the front end sees the raw (augmented) samples, as a stream's does
             x = ops.prep_step(x, self.prep, out=x if self.augment is not None else bufs.get("xn"))
+        if self.crop is not None:          # ... -> prep -> crop -> mixup: the step's dimensions become (B * R, W) here
+            self.crop.check_trial(T)
+            soft = y.is_floating_point()
+            x, yl, yt = ops.crop(x, self.crop, rngs if drawn_crop else None, M=M, labels=None if soft else y, targets=y if soft else None,
+                                 step_dev=step_dev if drawn_crop else None, out=bufs.get("xc"), labels_out=bufs.get("yc"))
+            y = yt if soft else yl
+            if self.normalize:
+                ops.zscore(x.view(-1, self.crop.window, Cc), out=x.view(-1, self.crop.window, Cc))
         if y.is_floating_point() or self.loss is None:
             return (x, None, y) if y.is_floating_point() else (x, y, None)
         lo = self.loss

@@ -21,7 +21,7 @@ import torch
 
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
-from .ops import Augment, Average, Loss, LrSchedule, Sam
+from .ops import Augment, Average, Crop, Loss, LrSchedule, Sam
 from .prep import CausalPrep
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
@@ -36,6 +36,40 @@ def evaluate(model: EEG_LSTM, x: torch.Tensor, y: torch.Tensor, batch: int = 512
             correct += int((pred == y[lo:lo + batch].long()).sum().item())
     model.train(was_training)
     return correct / max(int(x.shape[0]), 1)
+
+
+def evaluate_cropped(model: EEG_LSTM, x: torch.Tensor, y: torch.Tensor, grid: Crop, batch: int = 256):
+    """(trial-level accuracy: each trial decided by the pooled probabilities of the windows of `grid`, accuracy of each trial's FIRST
+    window alone -- what a live user gets after one window) of a model trained on crops; EEG_LSTM.predict_trials does the work."""
+    pooled_ok = first_ok = 0
+    for lo in range(0, x.shape[0], batch):
+        pooled, wins = model.predict_trials(x[lo:lo + batch], hop=grid.hop, window=grid.window)
+        lab = y[lo:lo + batch].long()
+        pooled_ok += int((pooled.argmax(-1) == lab).sum().item())
+        first_ok += int((wins[:, 0].argmax(-1) == lab).sum().item())
+    n = max(int(x.shape[0]), 1)
+    return pooled_ok / n, first_ok / n
+
+
+CROP_OPTIONS = ("crop_seconds", "crops_per_trial", "crop_hop_seconds")
+
+
+def crop_for(args, fs: float = 125.0):
+    """None without --crop-seconds, else (the training Crop: --crops-per-trial drawn windows of --crop-seconds per trial and step, the
+    evaluation grid: every whole window of the trial, --crop-hop-seconds apart -- default half the window).  ValueError, with the
+    rule, for an option without --crop-seconds or out of range."""
+    given = [o for o in CROP_OPTIONS[1:] if getattr(args, o, None) is not None]
+    if getattr(args, "crop_seconds", None) is None:
+        if given:
+            raise ValueError(f"--{given[0].replace('_', '-')} needs --crop-seconds S")
+        return None
+    W = int(round(args.crop_seconds * fs))
+    if not 1 <= W <= args.T:
+        raise ValueError(f"--crop-seconds {args.crop_seconds}: {W} samples, outside [1, --T {args.T}]")
+    hop = max(W // 2, 1) if args.crop_hop_seconds is None else int(round(args.crop_hop_seconds * fs))
+    if hop < 1:
+        raise ValueError(f"--crop-hop-seconds {args.crop_hop_seconds}: less than one sample")
+    return Crop(W, 1 if args.crops_per_trial is None else args.crops_per_trial, 0), Crop.grid(args.T, W, hop)
 
 
 def concurrent_runs(y_np: np.ndarray, kfold: int, seeds: int, seed: int, batch: int, inner_fraction=None):
@@ -272,6 +306,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="sharpness-aware minimisation: every step takes its gradient at the weights moved this distance uphill along the "
                          "normalised gradient (two forward/backward passes per step, about twice the time; 0.05 is the paper's default; 0 "
                          "is off).  Turns the guarded step tail on, and loss_last_batch is then the loss at the perturbed weights")
+    ap.add_argument("--crop-seconds", type=float, default=None,
+                    help="cropped training: every training trial is shown as --crops-per-trial windows of this length, cut at drawn offsets "
+                         "on the device in every step; held-out trials are then decided by the pooled decisions of their windows on a "
+                         "regular grid, and every record carries the accuracy of the first window alone beside it")
+    ap.add_argument("--crops-per-trial", type=int, default=None, help="cropped training: windows per trial and step, 1 .. 64 (default 1)")
+    ap.add_argument("--crop-hop-seconds", type=float, default=None, help="cropped training: distance of the evaluation grid's windows "
+                                                                         "(default: half of --crop-seconds)")
     return ap
 
 
@@ -331,8 +372,10 @@ def main(argv=None) -> int:
         es = early_stop_settings(args, concurrent=args.concurrent and args.kfold >= 2)
         average_for(args, 1)
         sam_for(args)
+        crops = crop_for(args)
     except ValueError as e:
         ap.error(str(e))
+    crop_train, crop_eval = crops if crops is not None else (None, None)
 
     rank, local, world = init_distributed()
     if not torch.cuda.is_available():
@@ -377,7 +420,13 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + ("sam_rho",) or v is not None)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + ("sam_rho",) or v is not None)}
+
+    def score(mdl, xs, ys):
+        """(accuracy, first-window accuracy or None): whole trials, or with --crop-seconds trials pooled over the evaluation grid"""
+        if crop_eval is None:
+            return evaluate(mdl, xs, ys), None
+        return evaluate_cropped(mdl, xs, ys, crop_eval)
 
     fold_paths = []
 
@@ -387,12 +436,12 @@ def main(argv=None) -> int:
         what is written / scored -- the number of epochs is fixed beforehand, nothing is selected."""
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
-                         bidirectional=args.bidirectional, prep=prep_for(tr_idx)).to(dev).train()
+                         bidirectional=args.bidirectional, prep=prep_for(tr_idx), crop=crop_train).to(dev).train()
         steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
         average = average_for(args, steps_per_epoch)
         trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
                           clip_grad_norm=args.clip_grad_norm, lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average,
-                          sam=sam_for(args))
+                          sam=sam_for(args), crop=crop_train)
         opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None or sam_for(args) is not None
         scored = model                   # --avg: the averaged model, from its first averaged step on
         acc_va_last_iterate = float("nan")
@@ -413,14 +462,16 @@ def main(argv=None) -> int:
             if rank == 0 and (epoch % args.log_every == 0 or last):
                 if average is not None and trainer.averaged_count() > 0:
                     scored = trainer.averaged_model()
-                acc_tr = evaluate(scored, x_all[tr_dev], y_all[tr_dev])
-                acc_va = evaluate(scored, x_all[va_idx], y_all[va_idx]) if len(va_idx) else float("nan")
+                acc_tr = score(scored, x_all[tr_dev], y_all[tr_dev])[0]
+                acc_va, acc_va_first = score(scored, x_all[va_idx], y_all[va_idx]) if len(va_idx) else (float("nan"), None)
                 if keep_best and out_path and acc_va > best[0]:
                     best = (acc_va, epoch)
                     save_reference_checkpoint(scored, out_path)
                 extra = {"grad_norm": trainer.last_grad_norm(), "lr": trainer.last_lr(), "skipped": trainer.skipped_steps()} if opt_on else {}
+                if acc_va_first is not None:
+                    extra["acc_val_first_window"] = round(acc_va_first, 4)
                 if average is not None:
-                    acc_va_last_iterate = evaluate(model, x_all[va_idx], y_all[va_idx]) if len(va_idx) else float("nan")
+                    acc_va_last_iterate = score(model, x_all[va_idx], y_all[va_idx])[0] if len(va_idx) else float("nan")
                     extra.update(acc_val_last_iterate=round(acc_va_last_iterate, 4), averaged_steps=trainer.averaged_count())
                 emit({"run": tag, "epoch": epoch, "loss_last_batch": round(trainer.last_loss(), 5), "acc_train": round(acc_tr, 4),
                       "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), **extra})
@@ -442,12 +493,13 @@ def main(argv=None) -> int:
         models, prep_all = [], prep_for(np.arange(len(y_np)))
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all, crop=crop_train).to(dev).train())
         steps_per_epoch = concurrent_epoch(runs, args.batch, 0, lambda idxs: None)
         average = average_for(args, steps_per_epoch)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
                                 loss=loss_for(args, y_np), clip_grad_norm=args.clip_grad_norm,
-                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average, sam=sam_for(args))
+                                lr_schedule=schedule_for(args, args.epochs * steps_per_epoch), average=average, sam=sam_for(args), crop=crop_train)
+        pooled = dict(crop=crop_eval) if crop_eval is not None else {}       # held-out scoring of a cropped run is trial-level
         opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None or sam_for(args) is not None
         avg_on, inner, es_epoch0 = average is not None, None, 0
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
@@ -472,34 +524,37 @@ def main(argv=None) -> int:
                 # every epoch: all folds on their inner parts, the best-epoch decision and the snapshot, in two launches
                 if inner is None:
                     es_epoch0 = epoch        # (--avg-start-epoch: the first evaluation is that epoch's, so evaluation n is epoch es_epoch0 + n - 1)
-                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"], **wts)
+                inner = mbt.track_best(*held["inner"], metric=es["metric"], patience=es["patience"], min_delta=es["min_delta"], **wts, **pooled)
                 last = last or all(e["stopped"] for e in inner)
             if epoch % args.log_every == 0 or last:
                 losses = mbt.last_losses()
                 norms, lr_now, skipped = (mbt.last_grad_norms(), mbt.last_lr(), mbt.skipped_steps()) if opt_on else (None, None, None)
                 if es:
-                    ev_tr, ev_va = mbt.evaluate(*held["tr"], **wts), mbt.evaluate(*held["va"], **wts)
-                    ev_va_iter = mbt.evaluate(*held["va"]) if avg_on else ev_va
+                    ev_tr, ev_va = mbt.evaluate(*held["tr"], **wts, **pooled), mbt.evaluate(*held["va"], **wts, **pooled)
+                    ev_va_iter = mbt.evaluate(*held["va"], **pooled) if avg_on else ev_va
+                    ev_va_first = mbt.evaluate(*held["va"], **wts, crop=Crop(crop_eval.window, 1, 1)) if pooled else None
                 scored = mbt.averaged_models() if avg_ready else models
                 for k, r in enumerate(runs):
                     if es:
                         acc_tr, acc_va, acc_va_iter = ev_tr[k]["acc"], ev_va[k]["acc"], ev_va_iter[k]["acc"]
+                        acc_va_first = ev_va_first[k]["acc"] if pooled else None
                     else:
-                        acc_tr = evaluate(scored[k], x_all[tr_devs[k]], y_all[tr_devs[k]])
-                        acc_va = evaluate(scored[k], x_all[r["va"]], y_all[r["va"]])
-                        acc_va_iter = evaluate(models[k], x_all[r["va"]], y_all[r["va"]]) if avg_on else acc_va
-                    res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va, acc_val_last_iterate=acc_va_iter)
+                        acc_tr = score(scored[k], x_all[tr_devs[k]], y_all[tr_devs[k]])[0]
+                        acc_va, acc_va_first = score(scored[k], x_all[r["va"]], y_all[r["va"]])
+                        acc_va_iter = score(models[k], x_all[r["va"]], y_all[r["va"]])[0] if avg_on else acc_va
+                    res[k] = dict(acc_train_last=acc_tr, acc_val_last=acc_va, acc_val_last_iterate=acc_va_iter, acc_val_first_window=acc_va_first)
                     emit({"run": tag(r), "epoch": epoch, "loss_last_batch": round(losses[k], 5), "acc_train": round(acc_tr, 4),
                           "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), "concurrent": True,
                           **({"grad_norm": norms[k], "lr": lr_now, "skipped": skipped[k]} if opt_on else {}),
                           **({"acc_val_last_iterate": round(acc_va_iter, 4)} if avg_on else {}),
+                          **({"acc_val_first_window": round(acc_va_first, 4)} if acc_va_first is not None else {}),
                           **({"loss_inner": round(inner[k]["loss"], 5), "acc_inner": round(inner[k]["acc"], 4),
                               "best_epoch": es_epoch0 + inner[k]["best_eval"] - 1, "stopped": inner[k]["stopped"]} if inner is not None else {})})
             if es and last:
                 break
         if es:       # the outer folds, looked at for the first time as far as the models are concerned: the best-epoch models, one call
             best = mbt.restore_best()
-            final = mbt.evaluate(*held["va"])
+            final = mbt.evaluate(*held["va"], **pooled)
         accs = []
         for k, r in enumerate(runs):
             accs.append(final[k]["acc"] if es else res[k]["acc_val_last"])
@@ -510,6 +565,8 @@ def main(argv=None) -> int:
             rec = {"fold": r["fold"], "n_train": int(len(r["tr"])), "n_val": int(len(r["va"])),
                    "acc_val_last_epoch": round(res[k]["acc_val_last"], 4), "acc_train_last_epoch": round(res[k]["acc_train_last"], 4),
                    "concurrent": True}
+            if res[k].get("acc_val_first_window") is not None:
+                rec["acc_val_first_window"] = round(res[k]["acc_val_first_window"], 4)
             if avg_on:       # the same training run scored twice: its last iterate and its averaged weights (both after the last epoch)
                 rec.update(acc_val_last_iterate=round(res[k]["acc_val_last_iterate"], 4), acc_val_averaged=round(res[k]["acc_val_last"], 4))
             if es:

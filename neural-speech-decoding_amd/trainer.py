@@ -104,8 +104,12 @@ class Trainer:
                  weight_decay: float = 0.0, seed: int = 1234, stochastic: bool = True, group=None,
                  augment: Optional[ops.Augment] = None, loss: Optional[ops.Loss] = None,
                  clip_grad_norm: Optional[float] = None, lr_schedule: Optional[ops.LrSchedule] = None,
-                 average: Optional[ops.Average] = None, sam: Optional[ops.Sam] = None):
-        """sam: an ops.Sam -- sharpness-aware minimisation: every step runs its forward/backward twice on the same batch with the same
+                 average: Optional[ops.Average] = None, sam: Optional[ops.Sam] = None, crop: Optional[ops.Crop] = None):
+        """crop: an ops.Crop -- cropped training: every trial of a step is shown to the model as crop.crops windows of crop.window
+        samples, cut on the device behind the front end (StepRecipe: augment -> prep -> crop -> mixup).  The step's kernels, workspaces,
+        captured graphs and path checks then see (B * crops, window); the loss scale is 1 / (global_batch * crops), and last_loss() is
+        the mean over the crops.  World > 1: each rank draws its own offsets (trainer_seed), as it augments.  None: today's step.
+        sam: an ops.Sam -- sharpness-aware minimisation: every step runs its forward/backward twice on the same batch with the same
         random draws, at the parameters and at the parameters moved rho uphill along the normalised gradient (formed on the device,
         nsd_sam_ascend), and updates the real parameters with the second gradient; about twice the step's time.  It switches the guarded
         tail on, as average= does: a non-finite second gradient is skipped and counted in skipped_steps().  World > 1: each rank ascends
@@ -155,8 +159,12 @@ class Trainer:
         # what a step does to (windows, labels) before its kernels: step_recipe.py, shared with step_static and ModelBatchTrainer.
         # Each rank augments / mixes inside its own shard with its own seed; the scale stays 1 / global_batch (torch's weighted
         # `mean` divides by the weight sum).
-        self.recipe = StepRecipe(model, stochastic, augment, loss, self.flat.device, sam=sam)
+        self.recipe = StepRecipe(model, stochastic, augment, loss, self.flat.device, sam=sam, crop=crop)
         self.augment, self.loss = self.recipe.augment, self.recipe.loss          # the effective ones (None: off)
+        self.crop = self.recipe.crop
+        self._crops = self.crop.crops if self.crop is not None else 1            # rows of a step per trial
+        if self.crop is not None and model.crop is None:
+            model.crop = self.crop       # the model and its checkpoints carry the window it is trained on (predict_trials, open_stream)
         self.step_count = 0
         self._bufs = {}
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.flat.device)
@@ -166,7 +174,8 @@ class Trainer:
         self._step_dev = torch.zeros(1, dtype=torch.int64, device=self.flat.device)
         self._graphs = {}
 
-    # buffers that depend on the batch shape are created once and reused every step
+    # buffers that depend on the batch shape are created once and reused every step.  (B, T): what the step's kernels see -- with
+    # crop= the crops (recipe.dims), not the trials
     def _buffers(self, B: int, T: int):
         key = (B, T)
         if key not in self._bufs:
@@ -198,6 +207,7 @@ class Trainer:
             y = y.contiguous()
         if global_batch is None:
             global_batch = B * self.world
+        global_batch *= self._crops      # the step's rows over all ranks: with crop= every trial is crops windows
         self.step_count += 1
         if self.world == 1:
             if B == 0:
@@ -207,7 +217,7 @@ class Trainer:
         else:
             DataParallelStep(self._grads_ext, self.reducer, self._local_grads, self._grads_ext.zero_, self._adam)(x, y, global_batch)
         if B > 0:
-            self._last_B, self._last_T = B, int(x.shape[1])
+            self._last_B, self._last_T = self.recipe.dims(B, int(x.shape[1]))
 
     def _hyper(self) -> dict:
         return dict(step=self.step_count, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
@@ -250,8 +260,8 @@ class Trainer:
     def _local_grads(self, x: torch.Tensor, y: torch.Tensor, scale: float, fuse_adam: bool = False) -> None:
         """Launches that leave this shard's gradient (scaled) in self.grads; fuse_adam: the update rides in the last one."""
         sp = self.spec
-        B, T, _ = x.shape
         x, y, tg = self.recipe.prepare(x, y, [self.seed], self.step_count)
+        B, T, _ = x.shape                # (with crop=: the crops)
         rng = self.recipe.rng(self.seed, self.step_count)
         if self.model.precision == "bf16":
             # sequence-batched path: forward (+ head, CE, head backward), backward (+ all parameter gradients), Adam
@@ -301,7 +311,10 @@ class Trainer:
         if self.model.precision == "bf16":
             raise ops.NsdError("Trainer.static_inputs / step_static (hipGraph replay) exist for the fp32 path only; "
                                "precision='bf16' trains through Trainer.step")
-        buf = self._buffers(B, T)
+        buf = self._buffers(*self.recipe.dims(B, T))
+        if "x" in buf and tuple(buf["x"].shape[:2]) != (B, T):     # (crop=: other trials with the same crops)
+            self._bufs, self._graphs = {}, {}
+            buf = self._buffers(*self.recipe.dims(B, T))
         if "x" not in buf:
             dev = self.flat.device
             buf["x"] = torch.zeros((B, T, self.spec.C), dtype=torch.float32, device=dev)
@@ -312,7 +325,7 @@ class Trainer:
     def _issue_segment_a(self, B: int, T: int) -> None:
         """step counter, random streams, lstm fwd, fused head, lstm bwd, slab reduce -> self.grads (one rank with clipping / a schedule:
         the clipped tail rides here as in the eager step, reading the device counter, and segment B is empty)"""
-        buf = self._buffers(B, T)
+        buf = self._buffers(*self.recipe.dims(B, T))
         ops.step_counter_inc(self._step_dev)
         if self.stochastic and not all(k in buf for k in ("drop_lstm", "rrelu", "drop_head")):
             raise ops.NsdError("graph step needs all three random streams (dropout > 0, num_layers > 1) or stochastic=False")
@@ -320,7 +333,8 @@ class Trainer:
         # static buffers throughout, and every stream id from the device step counter: the graph replays it
         xin, y, tg = self.recipe.prepare(buf["x"], buf["y"], [self.seed], 0, step_dev=self._step_dev, bufs=buf)
         ops.train_step_grads(self.spec, self.flat, xin, buf["ws"], y, buf["logits"], self.grads,
-                             scale=1.0 / (B * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh, residual=self.model.residual,
+                             scale=1.0 / (B * self._crops * self.world), drop_lstm=dl, rrelu_slope=sl, drop_head=dh,
+                             residual=self.model.residual,
                              adam=self._fused_tail(self._step_dev) if self._opt_on and self.world == 1 else None, targets=tg,
                              opt_state=self._opt_state, **self.recipe.sam_args(self._sam_state))
 
@@ -370,7 +384,7 @@ class Trainer:
         if gb is not None:
             self.reducer(self.grads)
             gb.replay()
-        self._last_B, self._last_T = B, T
+        self._last_B, self._last_T = self.recipe.dims(B, T)
 
     @_on_own_device
     def scan_status(self) -> int:
@@ -496,9 +510,17 @@ class Trainer:
 def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:
     """Write a .pth the reference's SimplePredictor loads unchanged (raw state_dict with the reference's
     key names on CPU; lstm_eeg_model.py:77-81).  A model with a causal front end is written in the dict form both loaders accept,
-    {"state_dict": ..., "nsd_prep": prep.to_dict()}: the reference's loader reads the weights, SimplePredictor here rebuilds the prep too."""
+    {"state_dict": ..., "nsd_prep": prep.to_dict()}: the reference's loader reads the weights, SimplePredictor here rebuilds the prep too.
+    A model trained on crops (model.crop) adds "nsd_crop" = {window, crops, hop} to that dict; a model with neither is written as before."""
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    torch.save(sd if model.prep is None else {"state_dict": sd, "nsd_prep": model.prep.to_dict()}, path)
+    crop = getattr(model, "crop", None)
+    if model.prep is None and crop is None:
+        torch.save(sd, path)
+        return
+    extra = {} if model.prep is None else {"nsd_prep": model.prep.to_dict()}
+    if crop is not None:
+        extra["nsd_crop"] = {"window": int(crop.window), "crops": int(crop.crops), "hop": int(crop.hop)}
+    torch.save({"state_dict": sd, **extra}, path)
 
 
 def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
