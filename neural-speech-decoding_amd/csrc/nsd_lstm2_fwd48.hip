@@ -61,6 +61,13 @@ template <int NB> constexpr bool LEAN = false;
 #else
 template <int NB> constexpr bool LEAN = NB == 1;
 #endif
+// The fused head's two weight-gradient outer products leave from the three helper waves behind the pooling wave's barrier
+// (train_tail) instead of from the pooling wave alone.  Not in the two-trial instantiations of the model-batched twin: 12 bytes of scratch.
+#if NSD_MULTI_TU
+template <int NB> constexpr bool SPREAD_HEAD = NB == 1;
+#else
+template <int NB> constexpr bool SPREAD_HEAD = true;
+#endif
 constexpr int TT_PARTS = NT_TRAIN / 48;   // 16
 
 template <int NB>
@@ -86,9 +93,9 @@ struct FSmem {
 
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-template <int NB>
+template <int NB, bool HELPER = false>
 __device__ __forceinline__ void train_tail(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int tid, const int b, const int n);
-template <int NB>
+template <int NB, bool HELPER = false>
 __device__ __forceinline__ void tail_all(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int tid, const int b0);
 
 // 12 operands of a k-slice from LDS as 6 pairs
@@ -470,7 +477,7 @@ __device__ __forceinline__ void saver_role(const A &a, FSmem<NB> &sm, const int 
 #pragma unroll 1
         for (int k = 0; k < SCH; ++k) flush(std::true_type{}, n_steps / SCH - 1, b0, k);   // last chunk (its LDS image is complete: barrier above)
         if (a.head_train) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail reads the top rows back
-        if (a.head_train) tail_all<NB>(a, sm, threadIdx.x, b0);
+        if (a.head_train) tail_all<NB, true>(a, sm, threadIdx.x, b0);
         else step_barrier<false>(prof);                     // keep the ring intact until it has been read
     }
     prof_store(a.dbg, prof);
@@ -622,13 +629,26 @@ __device__ __forceinline__ float tail_block_sum(float v, float *red, const int t
 
 // every wave of the workgroup calls this after the ring-drain barrier of trial b (the barrier also published the
 // tpool wave's LDS vectors and, with the saver's vmcnt(0), the top rows in memory)
-template <int NB>
+template <int NB, bool HELPER>
 __device__ __forceinline__ void train_tail(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int tid, const int b, const int n) {
     const int T = a.T;
     float *sc = sm.sc[n];
     if (ablated(a.ablate, 256)) return;
     // without the residual extension the attention input IS the layer-1 output: that sequence is not saved twice
     const float *top = (a.top ? a.top : a.hseq1) + (size_t)b * T * H;
+    // d fc.3.weight = dlogits (x) z and d fc.0.weight = dz (x) LayerNorm output: the vectors were left in LDS by the pooling wave, which
+    // ran the dense head alone while the other eleven waves waited; the K F + F H products and stores are spread over the three helper
+    // waves (saver, pooling, spare = waves 8 .. 10 of the role table; one rounding each: the same bits as from one wave), which have no
+    // row of their own in the loop below up to T = 512.  Not over the recurrence waves: the four arguments live across their time
+    // loops cost every instantiation a private segment.
+    if constexpr (HELPER && SPREAD_HEAD<NB>) {
+        if (!ablated(a.ablate, 512)) {
+            float *hs = a.hslabs + (size_t)b * a.Ph;
+            const int K = a.K, F = a.F, e0 = tid - 8 * 64;
+            for (int e = e0; e < F * H; e += 3 * 64) { const int f = e / H; hs[a.o_fc0_w + e] = sm.vdz[f] * sm.vln[e - f * H]; }
+            for (int e = e0; e < K * F; e += 3 * 64) { const int k = e / F; hs[a.o_fc3_w + e] = sm.vdl[k] * sm.vz[e - k * F]; }
+        }
+    }
     const float mx = sm.md[0], rden = sm.md[1];
     float al[2], dd[2];
     float lsd = 0.f;
@@ -692,12 +712,12 @@ __device__ __forceinline__ void train_tail(const Lstm2FwdArgs &a, FSmem<NB> &sm,
 // What every wave but the train-pooling wave does after the last step of a trial group: for each trial of the group, meet the
 // pooling wave (which has just run that trial's dense head alone and left dpooled / the softmax statistics in LDS), then take
 // part in the trial's tail.  The first of these barriers is also the "save ring drained" barrier of the group.
-template <int NB>
+template <int NB, bool HELPER>
 __device__ __forceinline__ void tail_all(const Lstm2FwdArgs &a, FSmem<NB> &sm, const int tid, const int b0) {
 #pragma unroll 1
     for (int n = 0; n < NB; ++n) {
         __syncthreads();
-        if (b0 + n < a.B) train_tail<NB>(a, sm, tid, b0 + n, n);   // (workgroup-uniform: the padding trial of an odd batch's last group has no tail)
+        if (b0 + n < a.B) train_tail<NB, HELPER>(a, sm, tid, b0 + n, n);   // (workgroup-uniform: the padding trial of an odd batch's last group has no tail)
     }
 }
 
@@ -808,7 +828,10 @@ __device__ __forceinline__ void tpool_role(const A &a, FSmem<NB> &sm, const int 
                 sm.vdz[lane] = dz;
                 if (vb) slab[a.o_fc0_b + lane] = dz;
             }
-            if (vb) {
+            // (SPREAD_HEAD: d fc.3.weight and d fc.0.weight, K F + F H outer-product entries, leave behind the barrier below: train_tail)
+            if constexpr (SPREAD_HEAD<NB>) {
+                if (vb && lane < K) slab[a.o_fc3_b + lane] = dl;
+            } else if (vb) {
                 for (int e2 = lane; e2 < K * F; e2 += 64) slab[a.o_fc3_w + e2] = sm.vdl[e2 / F] * sm.vz[e2 % F];
                 if (lane < K) slab[a.o_fc3_b + lane] = dl;
                 for (int e2 = lane; e2 < F * H; e2 += 64) { const int f = e2 / H; slab[a.o_fc0_w + e2] = sm.vdz[f] * sm.vln[e2 - f * H]; }
@@ -827,7 +850,7 @@ __device__ __forceinline__ void tpool_role(const A &a, FSmem<NB> &sm, const int 
             if (lane < H && vb) a.dpooled[(size_t)b * H + lane] = dpl;
             if (lane == 0) { sm.md[0] = mrun; sm.md[1] = rden; }
             __syncthreads();                                       // n == 0: ring drained; publishes dp / md / sc of trial n
-            if (b < a.B) train_tail<NB>(a, sm, threadIdx.x, b, n);
+            if (b < a.B) train_tail<NB, true>(a, sm, threadIdx.x, b, n);
         }
     }
     prof_store(a.dbg, prof);
@@ -884,7 +907,7 @@ __device__ __forceinline__ void spare_role(const A &a, FSmem<NB> &sm, const int 
                 step_barrier<false, S_SLEEP>(prof);
             }
         }
-        if (a.head_train) tail_all<NB>(a, sm, threadIdx.x, b0);
+        if (a.head_train) tail_all<NB, true>(a, sm, threadIdx.x, b0);
         else step_barrier<false>(prof);
     }
 }
