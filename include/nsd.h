@@ -375,6 +375,31 @@ int nsd_crop_pool(int32_t N, int32_t R, int32_t K, const float *probs /* [N][R][
                   float *probs_out /* [N][K] */, float *logits_out /* NULL or [N][K] */, void *stream);
 
 /*
+ * ---- the step's batch gathered on the device from resident trials (an EXTENSION: the reference has no trainer) ----
+ *
+ * nsd_gather: the trials x_all [N][T][C] (with labels_all [N] and / or target rows targets_all [N][K]) stay on the device for the whole
+ * run, with the run's index schedule table [M][S][B]: row r of model m holds the B trial indices of one step's batch.  One launch forms
+ * the batch of all M models, as the first stage of a step (gather -> augment -> prep -> crop -> mixup):
+ *   c = *step_dev as the kernel reads it when step_dev is non-NULL (hipGraph replay: the step's device counter), else `step`
+ *   r = (c - step_base) mod S, taken non-negative
+ *   i = table[m][r][b]:  x[m][b] is a bitwise copy of x_all[i]; labels[m*B + b] = labels_all[i]; targets[m*B + b, :] is a bitwise copy
+ *   of targets_all[i, :] (K = d->K floats).  labels_all / labels and targets_all / targets: each pair optional (an input without its
+ *   output is ignored).  Duplicate indices within a batch are legal.
+ * An index outside [0, N) reads nothing: every word of that row of x is the quiet NaN 0x7FC00000, its target row likewise, its label 0
+ * (not -1: the head kernels index by it), and bit 0 of status[m] (NULL, or int32 [M], which the caller zeroes) is set; every other row is
+ * what it would have been.  The step's non-finite handling then skips and counts the step.
+ * NSD_E_INVALID before any launch: M outside [1, NSD_MAX_MODELS]; N < 1, S < 1, B < 0, T or C < 1; NULL x_all / table / x; labels
+ * without labels_all, targets without targets_all (or with K < 1); x overlapping x_all; M * B * T * C or M * S * B above 2^31 - 1.
+ * B = 0 launches nothing.  Only d->B, T, C (and K with targets) are read.  nsd_gather_path: 1 where d, M, N, S pass these checks.
+ * Additive: NSD_VERSION stays as it is, a caller detects the feature by the symbols.
+ */
+int nsd_gather_path(const nsd_dims *d, int32_t M, int32_t N, int32_t S);
+int nsd_gather(const nsd_dims *d, int32_t M, int32_t N, const float *x_all /* [N][T][C] */, const int32_t *labels_all /* NULL or [N] */,
+               const float *targets_all /* NULL or [N][K] */, const int32_t *table /* [M][S][B] trial indices */, int32_t S,
+               int64_t step, const int64_t *step_dev, int64_t step_base, float *x /* [M][B][T][C] */, int32_t *labels /* NULL or [M*B] */,
+               float *targets /* NULL or [M*B][K] */, int32_t *status /* NULL or [M] */, void *stream);
+
+/*
  * ---- global-norm gradient clipping and learning-rate schedules in the step tail (an EXTENSION: the reference's recipe is missing) ----
  *
  * Step indexing: s is the 1-based Adam step, e = s - 1.

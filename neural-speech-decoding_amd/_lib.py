@@ -228,6 +228,9 @@ SYMBOLS = {
     "nsd_crop_path": (C.c_int, [_dp, C.POINTER(CropCfg)]),
     "nsd_crop": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, C.POINTER(CropCfg), _vp, _vp, _ip, _fp, _fp, _ip, _fp, _ip, _vp]),
     "nsd_crop_pool": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _fp, _ip, _fp, _fp, _vp]),
+    # the step's batch gathered on the device from the resident trials and the run's index schedule
+    "nsd_gather_path": (C.c_int, [_dp, C.c_int32, C.c_int32, C.c_int32]),
+    "nsd_gather": (C.c_int, [_dp, C.c_int32, C.c_int32, _fp, _ip, _fp, _ip, C.c_int32, C.c_int64, _vp, C.c_int64, _fp, _ip, _fp, _ip, _vp]),
     # model-batched H = 48 path (several models per launch)
     "nsd_multi_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_multi_workspace_bytes": (C.c_int64, [_dp, C.c_int32, C.POINTER(WsLayout)]),

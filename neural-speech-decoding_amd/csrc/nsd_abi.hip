@@ -953,6 +953,43 @@ int nsd_crop_pool(int32_t N, int32_t R, int32_t K, const float *probs, const int
     return nsd_crop_pool_launch(a, (hipStream_t)stream);
 }
 
+// ---- the step's batch from the resident trials (nsd_gather, include/nsd.h; nsd_gather.hip) -------------------------------------------
+static bool gather_shape(const nsd_dims *d, int32_t M, int32_t N, int32_t S) {
+    return d && M >= 1 && M <= NSD_MAX_MODELS && N >= 1 && S >= 1 && d->B >= 0 && d->T >= 1 && d->C >= 1 &&
+           (int64_t)d->T * d->C <= 0x7fffffff && (int64_t)M * d->B * d->T * d->C <= 0x7fffffff && (int64_t)M * S * d->B <= 0x7fffffff;
+}
+int nsd_gather_path(const nsd_dims *d, int32_t M, int32_t N, int32_t S) { return gather_shape(d, M, N, S) ? 1 : 0; }
+
+int nsd_gather(const nsd_dims *d, int32_t M, int32_t N, const float *x_all, const int32_t *labels_all, const float *targets_all,
+               const int32_t *table, int32_t S, int64_t step, const int64_t *step_dev, int64_t step_base, float *x, int32_t *labels,
+               float *targets, int32_t *status, void *stream) {
+    static const char *who = "gather";
+    if (!d) { nsd_set_error("%s: dims is NULL", who); return NSD_E_INVALID; }
+    if (M < 1 || M > NSD_MAX_MODELS) { nsd_set_error("%s: M = %d models outside [1, %d]", who, M, NSD_MAX_MODELS); return NSD_E_INVALID; }
+    if (N < 1 || S < 1) { nsd_set_error("%s: N = %d trials, S = %d schedule rows (both >= 1)", who, N, S); return NSD_E_INVALID; }
+    if (d->B < 0 || d->T < 1 || d->C < 1 || (int64_t)d->T * d->C > 0x7fffffff) {
+        nsd_set_error("%s: shape B=%d T=%d C=%d (B >= 0, T >= 1, C >= 1)", who, d->B, d->T, d->C); return NSD_E_INVALID;
+    }
+    if (!x_all || !table || !x) { nsd_set_error("%s: null pointer (x_all, table, x)", who); return NSD_E_INVALID; }
+    if (labels && !labels_all) { nsd_set_error("%s: labels without labels_all", who); return NSD_E_INVALID; }
+    if (targets && !targets_all) { nsd_set_error("%s: targets without targets_all", who); return NSD_E_INVALID; }
+    if (targets && d->K < 1) { nsd_set_error("%s: targets with K = %d classes (K >= 1)", who, d->K); return NSD_E_INVALID; }
+    const int64_t n_el = (int64_t)d->T * d->C, out = (int64_t)M * d->B * n_el, cells = (int64_t)M * S * d->B;
+    if (out > 0x7fffffff) { nsd_set_error("%s: M * B * T * C = %lld floats in one launch exceed 2^31 - 1", who, (long long)out); return NSD_E_INVALID; }
+    if (cells > 0x7fffffff) { nsd_set_error("%s: M * S * B = %lld table entries exceed 2^31 - 1", who, (long long)cells); return NSD_E_INVALID; }
+    const float *all_end = x_all + (int64_t)N * n_el;
+    if (out > 0 && x_all < x + out && x < all_end) { nsd_set_error("%s: x overlaps x_all (a gather is a copy: no in-place form)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    GatherArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x_all = x_all; a.x = x; a.table = table; a.status = status;
+    a.labels_all = labels ? labels_all : nullptr; a.labels = labels;
+    a.targets_all = targets ? targets_all : nullptr; a.targets = targets;
+    a.step_dev = (const long long *)step_dev; a.step = step; a.step_base = step_base;
+    a.n_el = (long)n_el; a.B = d->B; a.K = targets ? d->K : 0; a.M = M; a.N = N; a.S = S;
+    return nsd_gather_launch(a, (hipStream_t)stream);
+}
+
 // ---- model-batched H = 48 path (nsd_multi_*, include/nsd.h; nsd_multi.h) ----------------------------------------------------------
 // M = 1 runs the single-model entry points themselves.  M > 1: the kernels' model-batched twins on a workspace of M*B trials.
 static bool multi_shape(const nsd_dims *d, int M) {

@@ -192,6 +192,19 @@ struct CropPoolArgs {
     int N, R, K;
 };
 int nsd_crop_pool_launch(const CropPoolArgs &a, hipStream_t st);
+// the step's batch gathered from the resident trials (nsd_gather of nsd.h; nsd_gather.hip)
+struct GatherArgs {
+    const float *x_all; float *x;            // [N][T][C] -> [M][B][T][C]
+    const int32_t *labels_all; int32_t *labels;      // null together, or [N] -> [M*B]
+    const float *targets_all; float *targets;        // null together, or [N][K] -> [M*B][K]
+    const int32_t *table;                    // [M][S][B] trial indices
+    const long long *step_dev;               // null, or the device step counter the row is formed from
+    long long step, step_base;               // row = (counter or step - step_base) mod S, non-negative
+    int32_t *status;                         // null, or [M]: bit 0 = an index outside [0, N)
+    long n_el;                               // T * C
+    int B, K, M, N, S;
+};
+int nsd_gather_launch(const GatherArgs &a, hipStream_t st);
 // gradient slabs of M models in one workspace: per model n LSTM slabs (one per backward workgroup) and n_h head slabs (one per trial)
 struct SlabSet {
     const float *slabs; long stride; int n; long p_lstm;

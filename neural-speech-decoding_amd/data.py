@@ -139,3 +139,96 @@ def epoch_batches(n: int, batch: int, seed: int, epoch: int, drop_last: bool = F
         if drop_last and idx.size < batch:
             break
         yield idx
+
+
+# ---- device-resident trials and the run's index schedule (nsd_gather of include/nsd.h) --------------------------------------------------
+class DeviceTrialSet:
+    """The trials of a run resident on the device: x [N,T,C] fp32 and either int32 labels [N] (an integer y) or fp32 target rows [N,K]
+    (a floating-point y).  Trainer.bind_batches / ModelBatchTrainer.bind_batches gather every step's batch from it on the device."""
+
+    def __init__(self, x, y_or_targets, device):
+        import torch
+        x = torch.as_tensor(x)
+        y = torch.as_tensor(y_or_targets)
+        if x.dim() != 3 or x.shape[0] < 1:
+            raise ValueError(f"DeviceTrialSet: x must be [N,T,C] with N >= 1, got {tuple(x.shape)}")
+        self.x = x.to(device=device, dtype=torch.float32).contiguous()
+        self.labels = self.targets = None
+        if y.is_floating_point():
+            if y.dim() != 2 or y.shape[0] != x.shape[0]:
+                raise ValueError(f"DeviceTrialSet: target rows must be [N,K] = [{x.shape[0]},K], got {tuple(y.shape)}")
+            self.targets = y.to(device=device, dtype=torch.float32).contiguous()
+        else:
+            if y.dim() != 1 or y.shape[0] != x.shape[0]:
+                raise ValueError(f"DeviceTrialSet: labels must be [N] = [{x.shape[0]}], got {tuple(y.shape)}")
+            self.labels = y.to(device=device, dtype=torch.int32).contiguous()
+
+    def __len__(self) -> int:
+        return int(self.x.shape[0])
+
+    @property
+    def y(self):
+        """the labels, or the target rows"""
+        return self.labels if self.labels is not None else self.targets
+
+
+class BatchSchedule:
+    """The index schedule of a run: table int32 [M][S][B] -- row s of model m holds the trial indices (into the DeviceTrialSet) of that
+    model's batch in step s -- and steps_per_epoch.  The constructors restate the host loops of nsd_amd.train: a run through a schedule
+    sees the batches its host loop would have indexed, in the same order."""
+
+    def __init__(self, table, steps_per_epoch: int):
+        table = np.ascontiguousarray(table)
+        if table.ndim != 3 or table.shape[0] < 1 or table.shape[1] < 1 or table.shape[2] < 1:
+            raise ValueError(f"BatchSchedule: table must be [M,S,B] with M, S, B >= 1, got {table.shape}")
+        if not np.issubdtype(table.dtype, np.integer):
+            raise ValueError(f"BatchSchedule: table holds {table.dtype}, not trial indices")
+        if table.min() < 0 or table.max() > 0x7fffffff:
+            raise ValueError("BatchSchedule: a trial index is negative or above 2^31 - 1")
+        if steps_per_epoch < 1 or table.shape[1] % steps_per_epoch:
+            raise ValueError(f"BatchSchedule: {table.shape[1]} rows are no whole number of epochs of {steps_per_epoch} steps")
+        self.table, self.steps_per_epoch = table.astype(np.int32), int(steps_per_epoch)
+
+    M = property(lambda self: int(self.table.shape[0]))
+    steps = property(lambda self: int(self.table.shape[1]))
+    batch = property(lambda self: int(self.table.shape[2]))
+    epochs = property(lambda self: self.steps // self.steps_per_epoch)
+
+    def check_trials(self, n: int) -> None:
+        """ValueError unless every index names one of n trials"""
+        if int(self.table.max()) >= n:
+            raise ValueError(f"BatchSchedule: trial index {int(self.table.max())} for a set of {n} trials")
+
+    @staticmethod
+    def _rows(tr_idx, batch: int, seed: int, epochs: int, drop_last: bool, who: str):
+        tr_idx = np.asarray(tr_idx)
+        n = len(tr_idx)
+        if batch < 1 or epochs < 1:
+            raise ValueError(f"{who}: batch {batch}, epochs {epochs} (both >= 1)")
+        if n < batch:
+            raise ValueError(f"{who}: {n} trials are fewer than one batch of {batch}: the run's only batch is a short one, which a "
+                             "schedule of equal rows cannot hold (such a run keeps the host loop)")
+        if not drop_last and n % batch:
+            raise ValueError(f"{who}: drop_last=False leaves a short tail batch of {n % batch} trials ({n} trials, batch {batch}), which "
+                             "a schedule of equal rows cannot hold (drop it, or choose a batch that divides the trials)")
+        return [tr_idx[idx] for e in range(epochs) for idx in epoch_batches(n, batch, seed, e, drop_last=True)]
+
+    @classmethod
+    def for_run(cls, tr_idx, batch: int, seed: int, epochs: int, drop_last: bool = True) -> "BatchSchedule":
+        """The steps of nsd_amd.train's fit(): tr_idx[idx] for idx in epoch_batches(len(tr_idx), batch, seed, e, drop_last=True),
+        e = 0 .. epochs - 1."""
+        rows = cls._rows(tr_idx, batch, seed, epochs, drop_last, "BatchSchedule.for_run")
+        return cls(np.stack(rows)[None], len(rows) // epochs)
+
+    @classmethod
+    def for_runs(cls, runs, batch: int, epochs: int) -> "BatchSchedule":
+        """The steps of nsd_amd.train's concurrent_epoch: runs is a sequence of dicts with `tr` (the run's trial indices) and `seed`;
+        step j of epoch e gives run k the j-th batch of epoch_batches(len(tr_k), batch, seed_k, e, drop_last=True)."""
+        if len(runs) < 1:
+            raise ValueError("BatchSchedule.for_runs: no runs")
+        per = [cls._rows(r["tr"], batch, r["seed"], epochs, True, f"BatchSchedule.for_runs: run {k}") for k, r in enumerate(runs)]
+        counts = sorted({len(p) for p in per})
+        if len(counts) > 1:
+            raise ValueError(f"BatchSchedule.for_runs: the runs draw {[c // epochs for c in counts]} batches of {batch} per epoch; one "
+                             "shared step needs the same count for every run")
+        return cls(np.stack([np.stack(p) for p in per]), counts[0] // epochs)

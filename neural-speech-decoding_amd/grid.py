@@ -205,6 +205,7 @@ def main(argv=None) -> int:
         return 2
     x_all, y_all = torch.from_numpy(x_np).to(dev), torch.from_numpy(y_np).to(dev)
     prep_all = prep_design if prep_design is None or prep_design.alpha == 0 else prep_design.calibrate(x_np)
+    trials_dev = D.DeviceTrialSet(x_all, y_all, dev) if args.device_batches else None
 
     def emit(rec: dict) -> None:
         line = json.dumps(rec)
@@ -244,6 +245,9 @@ def main(argv=None) -> int:
         def step(idxs):
             sel = [tr_devs[k][torch.from_numpy(ix).to(dev)] for (_, k), ix in zip(members, idxs)]
             mbt.step(torch.stack([x_all[s_] for s_ in sel]), torch.stack([y_all[s_] for s_ in sel]))
+        if args.device_batches:          # the group's schedule on the device, one gather per step for all members (as train's)
+            mbt.bind_batches(trials_dev, D.BatchSchedule.for_runs(member_runs, args.batch, args.epochs))
+            step = lambda idxs, mbt=mbt: mbt.step_scheduled()                                 # noqa: E731
 
         if es:       # the held-out sets of all members, padded to one B each: built once per group
             held = {part: padded_parts(x_all, y_all, [r[part] for r in member_runs]) for part in ("tr", "inner", "va")}

@@ -139,6 +139,7 @@ class ModelBatchTrainer:
         self.step_count = 0
         self._bufs = {}
         self._last = None
+        self._bound = None               # bind_batches: the resident trials, the device schedule and the host's count of its steps
         self._sel_buf, self._sel_state, self._sel_rule = None, None, None      # early stopping: allocated by the first track_best
 
     def _per_model(self, v, name: str, pair: bool = False) -> list:
@@ -185,6 +186,27 @@ class ModelBatchTrainer:
                              weight_decay=self.weight_decay, targets=tg, opt=self._opt() if self._opt_on else None, opt_state=self._opt_state,
                              avg=self.average if self._avg_on else None, avg_state=self._avg_state, **self.recipe.sam_args(self._sam_state))
         self._last = (B, T)
+
+    # ---- device-resident batches --------------------------------------------------------------------------------------------------
+    def bind_batches(self, trials, schedule) -> None:
+        """Keep the trials (a data.DeviceTrialSet with labels) and the M models' index schedule (a data.BatchSchedule, e.g.
+        BatchSchedule.for_runs) on the device: step_scheduled() then forms all models' batches of a step in one launch (nsd_gather)
+        instead of the host indexing and stacking them.  The first step after binding reads row 0; a schedule of the bound shape is
+        copied into the device table in place."""
+        if trials.labels is None:
+            raise NsdError("ModelBatchTrainer.bind_batches: the model-batched step takes int32 labels; the trial set holds target rows")
+        self._bound, _ = StepRecipe.bind(self._bound, trials, schedule, self.M, self.step_count + 1, "ModelBatchTrainer.bind_batches")
+
+    def step_scheduled(self) -> None:
+        """One step of all models on the next row of the bound schedule: one nsd_gather into [M,B,T,C] / [M*B], then step() on them.
+        Stepping past the schedule's last row raises."""
+        who = "ModelBatchTrainer.step_scheduled"
+        b = self._bound
+        if b is not None and self.step_count + 1 != b["first"] + b["taken"]:
+            raise NsdError(f"{who}: other steps were taken since the batches were bound (the row is named by the step count); bind again")
+        b = StepRecipe.take(b, who)
+        x, y = self.recipe.gather(b, self.step_count + 1)
+        self.step(x.view(self.M, b["B"], b["T"], -1), y.view(self.M, b["B"]))
 
     def _opt(self):
         """nsd_opt of the step: one, or with per-model settings a list of M"""
@@ -256,6 +278,7 @@ class ModelBatchTrainer:
         if self._last is None:
             return [float("nan")] * self.M
         B, T = self._last
+        StepRecipe.check_gather(self._bound, "ModelBatchTrainer.last_losses")
         s = ops.multi_loss_sum(self.spec, self._bufs[(B, T)]["ws"], self.M, B, T)
         return [float(v) / B for v in s.cpu().tolist()]
 

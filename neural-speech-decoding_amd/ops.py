@@ -566,6 +566,70 @@ def crop_pool(probs: torch.Tensor, counts: Optional[torch.Tensor] = None, *, out
     return out, logits
 
 
+def gather_path(B: int, T: int, Cc: int, M: int, N: int, S: int) -> bool:
+    """nsd_gather_path: do the shape checks of nsd_gather pass (no device needed)"""
+    d = Dims(int(B), int(T), int(Cc), 1, 1, 1, 1)
+    return bool(_lib.lib().nsd_gather_path(C.byref(d), int(M), int(N), int(S)))
+
+
+def _int32_dev(t: Optional[torch.Tensor], n: Optional[int], name: str) -> Optional[int]:
+    if t is None:
+        return None
+    if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise NsdError(f"gather_batch: {name} must be a contiguous int32 device tensor" + ("" if n is None else f" of {n} entries"))
+    return t.data_ptr()
+
+
+def gather_batch(x_all: torch.Tensor, table: torch.Tensor, *, step: int = 0, step_base: int = 0, step_dev: Optional[torch.Tensor] = None,
+                 labels_all: Optional[torch.Tensor] = None, targets_all: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                 labels_out: Optional[torch.Tensor] = None, targets_out: Optional[torch.Tensor] = None,
+                 status: Optional[torch.Tensor] = None):
+    """nsd_gather: the batch of one step for all models of `table`, one launch -> (x, labels, targets).
+    x_all [N,T,C] fp32: the resident trials; table int32 [M,S,B] (or [S,B]: one model): row r = (c - step_base) mod S holds each
+    model's B trial indices, c = step_dev[0] as the kernel reads it (an int64 device counter: hipGraph replay) or `step`.
+    x [M,B,T,C] ([B,T,C] for an [S,B] table) is the bitwise copy of the named trials; labels_all int32 [N] -> labels [M*B];
+    targets_all fp32 [N,K] -> targets [M*B,K] (None stays None).  out / labels_out / targets_out: the buffers to fill (a static step's).
+    status: int32 [M] on the device, zeroed by the caller: bit 0 is set for a model with an index outside [0, N); such a row is NaN
+    with label 0."""
+    if x_all.dim() != 3:
+        raise NsdError(f"gather_batch: x_all must be [N,T,C], got {tuple(x_all.shape)}")
+    if table.dim() not in (2, 3):
+        raise NsdError(f"gather_batch: table must be int32 [M,S,B] or [S,B], got {tuple(table.shape)}")
+    N, T, Cc = (int(v) for v in x_all.shape)
+    S, B = int(table.shape[-2]), int(table.shape[-1])
+    M = int(table.shape[0]) if table.dim() == 3 else 1
+    dev = x_all.device
+    tp = _int32_dev(table, None, "table")
+    if out is None:
+        out = torch.empty((M, B, T, Cc) if table.dim() == 3 else (B, T, Cc), dtype=torch.float32, device=dev)
+    if out.numel() != M * B * T * Cc:
+        raise NsdError(f"gather_batch: out has {out.numel()} elements for {M} x {B} x {T} x {Cc}")
+    K = 1
+    if labels_all is not None:
+        if labels_out is None:
+            labels_out = torch.empty((M * B,), dtype=torch.int32, device=dev)
+        lp, lop = _int32_dev(labels_all, N, "labels_all"), _int32_dev(labels_out, M * B, "labels_out")
+    else:
+        labels_out, lp, lop = None, None, None
+    if targets_all is not None:
+        if targets_all.dim() != 2 or targets_all.shape[0] != N:
+            raise NsdError(f"gather_batch: targets_all must be [N, K] = [{N}, K], got {tuple(targets_all.shape)}")
+        K = int(targets_all.shape[1])
+        if targets_out is None:
+            targets_out = torch.empty((M * B, K), dtype=torch.float32, device=dev)
+        if targets_out.numel() != M * B * K:
+            raise NsdError(f"gather_batch: targets_out has {targets_out.numel()} elements for {M * B} x {K}")
+    else:
+        targets_out = None
+    if B == 0:                           # nothing to launch (and an empty tensor has no address to hand over)
+        return out, labels_out, targets_out
+    d = Dims(B, T, Cc, 1, 1, K, 1)
+    _call("nsd_gather", dev, C.byref(d), M, N, _dev_f32(x_all, "x_all"), lp, _dev_f32(targets_all, "targets_all"), tp, S, int(step),
+          _step_ptr(step_dev, "gather_batch"), int(step_base), _dev_f32(out, "out"), lop, _dev_f32(targets_out, "targets_out"),
+          _int32_dev(status, M, "status"), STREAM)
+    return out, labels_out, targets_out
+
+
 @dataclass(frozen=True)
 class LrSchedule:
     """Learning-rate schedule of a trainer (the schedule fields of nsd_opt, include/nsd.h; an extension, the reference has none):

@@ -57,7 +57,11 @@ class StepRecipe:
     float target rows are repeated per crop.  W and R set the launch dimensions, so cropping is not one of the per-model axes: a
     sequence must hold equal entries.  Drawn offsets (hop = 0) are a stochastic part, but a deterministic trainer cannot simply drop
     them -- the step's dimensions hang on the crop -- so stochastic=False with hop = 0 is refused; a regular grid draws nothing and
-    stays.  None: today's step, launch for launch.  dims() gives the dimensions the step's kernels see."""
+    stays.  None: today's step, launch for launch.  dims() gives the dimensions the step's kernels see.
+
+    Bound batches (bind() / take() / gather() / check_gather(), behind the trainers' bind_batches and step_scheduled): the trials and
+    the run's index schedule stay on the device and nsd_gather forms each step's batch there, as the stage in front of prepare():
+    gather -> augment -> prep -> crop -> mixup.  It draws nothing and copies bit for bit, so the step behind it is the host-fed step."""
 
     def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None, crop=None):
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
@@ -146,6 +150,71 @@ class StepRecipe:
             return None
         probs = self.probs if self.probs is not None else [(self.p_lstm, self.p_head)] * len(seeds)
         return [step_rng(s, step, pl, ph) for s, (pl, ph) in zip(seeds, probs)]
+
+    def gather(self, bound: dict, step: int, *, step_dev: Optional[torch.Tensor] = None, x: Optional[torch.Tensor] = None,
+               y: Optional[torch.Tensor] = None):
+        """The stage in front of prepare() for a trainer with bound batches (bind_batches): gather -> augment -> prep -> crop -> mixup.
+        One nsd_gather forms the batch of step `step` (1-based, or the device counter step_dev) of all models of the bound table from
+        the resident trials -> (x [M,B,T,C] or [B,T,C], labels [M*B] or target rows [M*B,K]), into the bound buffers or into x / y (a
+        static step's inputs).  The gather draws nothing: no stream moves, and the step behind it is the step on these windows."""
+        trials = bound["trials"]
+        soft = trials.labels is None
+        xo, lo, to = ops.gather_batch(trials.x, bound["table"], step=step, step_base=bound["base"], step_dev=step_dev,
+                                      labels_all=trials.labels, targets_all=trials.targets, out=x if x is not None else bound["x"],
+                                      labels_out=None if soft else (y if y is not None else bound["y"]),
+                                      targets_out=(y if y is not None else bound["y"]) if soft else None, status=bound["status"])
+        return xo, (to if soft else lo)
+
+    @staticmethod
+    def bind(bound: Optional[dict], trials, schedule, M: int, next_step: int, who: str):
+        """The bound-batches record of a trainer of M models whose next step is `next_step` -> (record, kept).  A schedule of the
+        bound shape on the bound trials is copied into the device table in place (kept: captured graphs hold its address and
+        step_base, so the rows are rotated to put row 0 at next_step); anything else gets new buffers."""
+        import numpy as np
+        if schedule.M != M:
+            raise ops.NsdError(f"{who}: the schedule holds {schedule.M} models' batches, the trainer {M}")
+        try:
+            schedule.check_trials(len(trials))
+        except ValueError as e:
+            raise ops.NsdError(f"{who}: {e}") from None
+        S, B = schedule.steps, schedule.batch
+        N, T, Cc = (int(v) for v in trials.x.shape)
+        if not ops.gather_path(B, T, Cc, M, N, S):
+            raise ops.NsdError(f"{who}: M = {M}, N = {N}, S = {S}, B = {B}, T = {T}, C = {Cc} are outside nsd_gather (nsd_gather_path)")
+        kept = bound is not None and bound["trials"] is trials and (bound["M"], bound["S"], bound["B"]) == (M, S, B)
+        if kept:
+            shift = (next_step - bound["base"]) % S
+            bound["table"].copy_(torch.from_numpy(np.roll(schedule.table, shift, axis=1)).view(bound["table"].shape))
+            bound["status"].zero_()
+            bound.update(first=next_step, taken=0)
+            return bound, True
+        dev = trials.x.device
+        one = M == 1
+        y = (torch.empty((M * B, trials.targets.shape[1]), dtype=torch.float32, device=dev) if trials.labels is None
+             else torch.empty((M * B,), dtype=torch.int32, device=dev))
+        return dict(trials=trials, table=torch.from_numpy(schedule.table).to(dev).view((S, B) if one else (M, S, B)), base=next_step,
+                    first=next_step, taken=0, M=M, S=S, B=B, T=T, status=torch.zeros(M, dtype=torch.int32, device=dev),
+                    x=torch.empty((B, T, Cc) if one else (M, B, T, Cc), dtype=torch.float32, device=dev), y=y), False
+
+    @staticmethod
+    def take(bound: Optional[dict], who: str) -> dict:
+        """The host's count of the bound schedule's steps: NsdError without a schedule or past its last row."""
+        if bound is None:
+            raise ops.NsdError(f"{who}: no batches bound (bind_batches(trials, schedule) first)")
+        if bound["taken"] >= bound["S"]:
+            raise ops.NsdError(f"{who}: the bound schedule's {bound['S']} steps are taken; bind the next schedule")
+        bound["taken"] += 1
+        return bound
+
+    @staticmethod
+    def check_gather(bound: Optional[dict], who: str) -> None:
+        """NsdError naming the models whose gather met a trial index outside the set (nsd_gather's status; synchronises)."""
+        if bound is None:
+            return
+        bad = [m for m, s in enumerate(bound["status"].cpu().tolist()) if s]
+        if bad:
+            raise ops.NsdError(f"{who}: the batch schedule of model(s) {bad} named a trial outside the resident set of "
+                               f"{len(bound['trials'])}: those rows were NaN and their steps skipped or spoilt.  Results are invalid")
 
     def static_buffers(self, x: torch.Tensor) -> dict:
         """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""

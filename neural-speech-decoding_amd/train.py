@@ -313,6 +313,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--crops-per-trial", type=int, default=None, help="cropped training: windows per trial and step, 1 .. 64 (default 1)")
     ap.add_argument("--crop-hop-seconds", type=float, default=None, help="cropped training: distance of the evaluation grid's windows "
                                                                          "(default: half of --crop-seconds)")
+    ap.add_argument("--device-batches", action="store_true",
+                    help="keep each run's index schedule on the device beside the trials and gather every step's batch there (nsd_gather) "
+                         "instead of indexing it on the host; a single fp32 model then replays its whole step, gather included, from one "
+                         "hipGraph.  The batches are those of the host loop.  One GPU")
     return ap
 
 
@@ -402,6 +406,10 @@ def main(argv=None) -> int:
         tr_idx, va_idx = D.stratified_split(y_np, args.val_fraction, args.seed)
     x_all = torch.from_numpy(x_np).to(dev)
     y_all = torch.from_numpy(y_np).to(dev)
+    if args.device_batches and world > 1:
+        print("train: --device-batches runs on one GPU (a schedule sharded over ranks is not built)", file=sys.stderr)
+        return 2
+    trials_dev = D.DeviceTrialSet(x_all, y_all, dev) if args.device_batches else None
 
     def emit(rec: dict) -> None:
         if rank != 0:
@@ -420,7 +428,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + ("sam_rho",) or v is not None)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + ("sam_rho",) or v is not None)}
 
     def score(mdl, xs, ys):
         """(accuracy, first-window accuracy or None): whole trials, or with --crop-seconds trials pooled over the evaluation grid"""
@@ -446,11 +454,19 @@ def main(argv=None) -> int:
         scored = model                   # --avg: the averaged model, from its first averaged step on
         acc_va_last_iterate = float("nan")
         tr_dev = torch.from_numpy(tr_idx).to(dev)
+        # --device-batches: the run's schedule goes to the device once and every step gathers its batch there; a single fp32 model with
+        # all three random streams replays the step from one hipGraph.  A run of fewer trials than a batch keeps the host loop.
+        scheduled = trials_dev is not None and len(tr_idx) >= args.batch
+        graph_route = scheduled and args.precision == "fp32" and args.dropout > 0
+        if scheduled:
+            trainer.bind_batches(trials_dev, D.BatchSchedule.for_run(tr_idx, args.batch, seed, args.epochs))
         best = (-1.0, -1)
         t0 = time.time()
         acc_tr = acc_va = float("nan")
         for epoch in range(args.epochs):
-            for idx in D.epoch_batches(len(tr_idx), args.batch, seed, epoch, drop_last=len(tr_idx) >= args.batch):
+            for _ in range(steps_per_epoch if scheduled else 0):
+                trainer.step_scheduled(static=graph_route)
+            for idx in (() if scheduled else D.epoch_batches(len(tr_idx), args.batch, seed, epoch, drop_last=len(tr_idx) >= args.batch)):
                 # every rank takes part in every step (the step ends in a collective): a rank whose shard of a short tail
                 # batch is empty passes zero trials and contributes a zero gradient; the mean is over the GLOBAL batch
                 lo, hi = shard_range(len(idx), rank, world)
@@ -509,6 +525,9 @@ def main(argv=None) -> int:
         def step(idxs):
             sel = [tr_devs[k][torch.from_numpy(ix).to(dev)] for k, ix in enumerate(idxs)]
             mbt.step(torch.stack([x_all[s_] for s_ in sel]), torch.stack([y_all[s_] for s_ in sel]))
+        if trials_dev is not None:       # --device-batches: all runs' schedule on the device, one gather per step for all of them
+            mbt.bind_batches(trials_dev, D.BatchSchedule.for_runs(runs, args.batch, args.epochs))
+            step = lambda idxs: mbt.step_scheduled()
 
         def tag(r):
             return f"fold{r['fold']}" if args.kfold_seeds == 1 else f"seed{r['seed_run']}_fold{r['fold']}"

@@ -173,6 +173,7 @@ class Trainer:
         # hipGraph replay of the step (static-input path): everything that varies per step lives on the device
         self._step_dev = torch.zeros(1, dtype=torch.int64, device=self.flat.device)
         self._graphs = {}
+        self._bound = None               # bind_batches: the resident trials, the device schedule and the host's count of its steps
 
     # buffers that depend on the batch shape are created once and reused every step.  (B, T): what the step's kernels see -- with
     # crop= the crops (recipe.dims), not the trials
@@ -322,11 +323,14 @@ class Trainer:
             buf.update(self.recipe.static_buffers(buf["x"]))       # xn / xm / tg: what the step makes of x and y
         return buf["x"], buf["y"]
 
-    def _issue_segment_a(self, B: int, T: int) -> None:
+    def _issue_segment_a(self, B: int, T: int, scheduled: bool = False) -> None:
         """step counter, random streams, lstm fwd, fused head, lstm bwd, slab reduce -> self.grads (one rank with clipping / a schedule:
-        the clipped tail rides here as in the eager step, reading the device counter, and segment B is empty)"""
+        the clipped tail rides here as in the eager step, reading the device counter, and segment B is empty).  scheduled: the gather
+        of the bound batches fills the static inputs right behind the counter, reading its row from it."""
         buf = self._buffers(*self.recipe.dims(B, T))
         ops.step_counter_inc(self._step_dev)
+        if scheduled:
+            self.recipe.gather(self._bound, 0, step_dev=self._step_dev, x=buf["x"], y=buf["y"])
         if self.stochastic and not all(k in buf for k in ("drop_lstm", "rrelu", "drop_head")):
             raise ops.NsdError("graph step needs all three random streams (dropout > 0, num_layers > 1) or stochastic=False")
         dl, sl, dh = self._masks(buf, step_dev=self._step_dev)
@@ -346,7 +350,11 @@ class Trainer:
     def step_static(self, B: int, T: int) -> None:
         """One optimisation step on the trainer's static input buffers, replayed from captured hipGraphs.
         world == 1: one graph.  world > 1: graph A, the eager RCCL all-reduce of the flat gradient, graph B (Adam)."""
-        key = (B, T)
+        self._replay_static(B, T, False)
+
+    def _replay_static(self, B: int, T: int, scheduled: bool) -> None:
+        """step_static, or with scheduled the same graph with nsd_gather of the bound batches as its first node behind the counter"""
+        key = ("scheduled", B, T) if scheduled else (B, T)
         if self.model.precision == "bf16":
             raise ops.NsdError("Trainer.step_static (hipGraph replay) exists for the fp32 path only; precision='bf16' trains "
                                "through Trainer.step")
@@ -359,7 +367,7 @@ class Trainer:
             with torch.cuda.stream(side):
                 snap = (self.flat.clone(), self.m.clone(), self.v.clone())
                 avg_snap = self._avg_state.clone() if self._avg_state is not None else None
-                self._issue_segment_a(B, T)
+                self._issue_segment_a(B, T, scheduled)
                 self._issue_segment_b()
                 self.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])     # the warm-up step does not count
                 if avg_snap is not None:
@@ -369,7 +377,7 @@ class Trainer:
             torch.cuda.synchronize()
             ga = torch.cuda.CUDAGraph()
             with torch.cuda.graph(ga):
-                self._issue_segment_a(B, T)
+                self._issue_segment_a(B, T, scheduled)
                 if self.world == 1:
                     self._issue_segment_b()
             gb = None
@@ -385,6 +393,38 @@ class Trainer:
             self.reducer(self.grads)
             gb.replay()
         self._last_B, self._last_T = self.recipe.dims(B, T)
+
+    # ---- device-resident batches ------------------------------------------------------------------------------------------
+    @_on_own_device
+    def bind_batches(self, trials, schedule) -> None:
+        """Keep the run's trials (a data.DeviceTrialSet) and index schedule (a data.BatchSchedule of one model) on the device:
+        step_scheduled() then forms every step's batch there (nsd_gather, the first stage of the step) instead of the host indexing
+        it.  The first step after binding reads row 0.  A schedule of the bound shape on the bound trials is copied into the device
+        table in place, so the captured graphs of step_scheduled(static=True) survive; another shape drops them.  One rank only."""
+        if self.world > 1:
+            raise ops.NsdError("Trainer.bind_batches: world size > 1 is not supported (a sharded schedule is a separate piece of work); "
+                               "feed the shards through Trainer.step")
+        self._bound, kept = StepRecipe.bind(self._bound, trials, schedule, 1, self.step_count + 1, "Trainer.bind_batches")
+        if not kept:
+            self._graphs = {k: g for k, g in self._graphs.items() if k[0] != "scheduled"}
+
+    @_on_own_device
+    def step_scheduled(self, static: bool = False) -> None:
+        """One optimisation step on the next row of the bound schedule.  Eager: nsd_gather, then step() on the gathered buffers.
+        static=True (fp32 path, int32 labels): one hipGraph replay -- step_static's graph with the gather as its first node behind the
+        step counter, which names the row; precision='bf16' takes the eager route.  Stepping past the schedule's last row raises."""
+        who = "Trainer.step_scheduled"
+        b = self._bound
+        if b is not None and self.step_count + 1 != b["first"] + b["taken"]:
+            raise ops.NsdError(f"{who}: other steps were taken since the batches were bound (the row is named by the step count); bind again")
+        b = StepRecipe.take(b, who)
+        if static and self.model.precision != "bf16":
+            if b["trials"].labels is None:
+                raise ops.NsdError(f"{who}: the static inputs hold int32 labels; a trial set of target rows steps with static=False")
+            self._replay_static(b["B"], b["T"], True)
+            return
+        x, y = self.recipe.gather(b, self.step_count + 1)
+        self.step(x, y)
 
     @_on_own_device
     def scan_status(self) -> int:
@@ -405,6 +445,7 @@ class Trainer:
         """Raise NsdError if a scan group of the bf16 path timed out on ANY rank since the workspaces were created
         (synchronises this rank's stream; no collective: the flag read here was summed over the ranks by the step's own
         all-reduce, so every rank raises in the same step).  nsd_amd.train calls it on every rank at every log interval."""
+        StepRecipe.check_gather(self._bound, "Trainer")
         if self.model.precision != "bf16":
             return
         if float(self._skip.item()) != 0.0:
@@ -422,6 +463,7 @@ class Trainer:
         loss sum_b loss_b / B (synchronises).  With sam= this is the loss of the step's SECOND pass, at the perturbed weights."""
         if not self._last_B:
             return float("nan")
+        StepRecipe.check_gather(self._bound, "Trainer.last_loss")
         if self.model.precision == "bf16":
             ws = self._bufs[("seq", self._last_B, self._last_T)]["ws"]
             ops.seq_loss_sum(self.spec, ws, self._last_B, self._last_T, out=self._loss)
