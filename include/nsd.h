@@ -1006,6 +1006,70 @@ int     nsd_prep_step(const nsd_dims *d, const nsd_prep *p, const float *x, cons
                       void *state, int64_t state_bytes, int32_t S, float *y, void *stream);
 
 /*
+ * ---- signal-quality gate for live streams (an EXTENSION: the reference has no notion of a bad channel or an artefact) ----
+ *
+ * A causal detector of flat, railed, jumping and high-amplitude spans per channel, in two stages around the front end above:
+ *   nsd_gate_step (stateful)  raw samples -> y (a bad channel holds its last good value, so the sections and the common average behind
+ *                             it stay finite and calm) and one mask word per step;
+ *   nsd_gate_apply (stateless) behind the front end: a bad channel is zeroed in front of the model, a step that is bad on too many
+ *                             channels becomes NaN -- which the window decoders' poison contract turns into "no decision" for exactly
+ *                             the windows that contain it.
+ * For one stream, n = samples since the slot's reset, c the channel, x[n,c] the raw sample, prev = x[n-1,c].  Every fp32 operation
+ * rounds on its own (a - b is one correctly rounded subtraction); everything else is fabsf and comparisons, so the outputs and the state
+ * after n samples are bit for bit a function of the samples alone -- not of the cut, the slot, the other streams of the call, the HIP
+ * stream or a graph replay.  The detectors of nsd_gate, each off at 0:
+ *   rail          bad if |x| >= rail
+ *   jump          bad if n > 0, prev finite and |x - prev| >= jump
+ *   flat_samples  a pair is flat if n > 0, both samples are finite and |x - prev| <= flat_eps;
+ *                 run = flat pair ? min(run + 1, flat_samples) : 0;  bad if run >= flat_samples - 1 (flat_samples equal samples in a row)
+ *   pp_samples    hi, lo over the FINITE raw samples max(0, n - pp_samples + 1) .. n;  bad if there is one and hi - lo >= pp
+ *   raw_bad = !isfinite(x) | rail | jump | flat | pp.   raw_bad: hang = hold_samples, the sample is bad;  else if hang > 0: the sample
+ *   is bad, hang -= 1;  else the sample is good and held = x.   y[n,c] = bad ? held[c] : x[n,c] (held is 0 after a reset);  mask[n] has
+ *   bit c set where channel c is bad, which bounds C to [1, 32].  A step with more than max_bad bits set is REJECTED.
+ *   nsd_gate_path          1 where nsd_gate_step covers C channels with the configuration g (g == NULL: C alone), else 0
+ *   nsd_gate_state_bytes   bytes of a state of S >= 1 slots (S * stride * 4); <0 for C outside [1, 32] or S < 1
+ *   nsd_gate_state_layout  offsets inside a slot in 4-byte words: prev[C], held[C] (fp32), run[C], hang[C] (int32), ring[64][C] (fp32,
+ *                          ring[n mod 64][c] = x[n,c]), bad[C] (int64 counts of bad samples, 8-byte aligned), rejected (int64 count of
+ *                          rejected steps), steps (int64), and the stride.  The layout depends on C only: a slot can be checkpointed
+ *                          and restored by copying its stride words.
+ *   nsd_gate_reset         as nsd_prep_reset: slots == NULL: all S slots; else the n slots of the DEVICE array slots[n] (indices outside
+ *                          [0, S) are skipped).  A reset slot is all zero.
+ *   nsd_gate_step          x, y [B,T,C], mask [B,T] uint32 (of d only B, T, C are read); y == x is allowed, a partial overlap is refused.
+ *     stream mode (state != NULL): slots as in nsd_prep_step; a slot index outside [0, S) is skipped: its rows of y are NaN, its mask
+ *       rows are all ones (0xFFFFFFFF) and no state is touched.  No host synchronisation, no allocation: the call can be captured.
+ *     window mode (state == NULL, slots == NULL, S ignored): every trial starts from a reset state and nothing is stored.
+ *   nsd_gate_apply         v, out [B,T,C], mask [B,T] (of g only max_bad and flags are read).  popcount(mask) > max_bad: all C values of
+ *                          the step are NaN.  Otherwise a bad channel is 0.0f with NSD_GATE_ZERO and left as it is without the flag; a
+ *                          good one is a bitwise copy.  out == v is allowed, a partial overlap is refused.
+ * NSD_E_INVALID before any launch: NULL d / g / x / y / mask (v / out); C outside [1, 32]; T < 1; B < 0; B > S or S < 1 (stream mode);
+ * slots without a state; a threshold (rail, jump, flat_eps, pp) that is negative or not finite; flat_samples < 0; pp_samples outside
+ * [0, NSD_GATE_MAX_SPAN]; hold_samples < 0; max_bad < 0; unknown flag bits; partially overlapping x / y (v / out).
+ * NSD_E_WORKSPACE: state_bytes < nsd_gate_state_bytes(C, S).  B = 0 (n = 0) launches nothing.  Additive: NSD_VERSION stays as it is, a
+ * caller detects the feature by the symbols.
+ */
+#define NSD_GATE_MAX_SPAN 64
+#define NSD_GATE_ZERO 1u
+typedef struct nsd_gate {
+    float   rail;          /* 0 = off.  bad if |x| >= rail */
+    float   jump;          /* 0 = off.  bad if n > 0, prev finite and |x - prev| >= jump */
+    float   flat_eps;      /* with flat_samples > 0: a pair is flat if both finite and |x - prev| <= flat_eps */
+    int32_t flat_samples;  /* 0 = off */
+    float   pp;            /* with pp_samples > 0: bad if hi - lo >= pp over the finite raw samples of the span */
+    int32_t pp_samples;    /* 0 = off, else 1 .. NSD_GATE_MAX_SPAN */
+    int32_t hold_samples;  /* >= 0: after a raw-bad sample the channel stays bad for this many further samples */
+    int32_t max_bad;       /* a step with more than max_bad bad channels is rejected; max_bad >= C: never */
+    uint32_t flags;        /* NSD_GATE_ZERO */
+} nsd_gate;
+typedef struct nsd_gate_layout { int64_t prev, held, run, hang, ring, bad, rejected, steps, stride; } nsd_gate_layout;   /* 4-byte words */
+int     nsd_gate_path(int32_t C, const nsd_gate *g);
+int64_t nsd_gate_state_bytes(int32_t C, int32_t S);
+int     nsd_gate_state_layout(int32_t C, nsd_gate_layout *out);
+int     nsd_gate_reset(int32_t C, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream);
+int     nsd_gate_step(const nsd_dims *d, const nsd_gate *g, const float *x, const int32_t *slots,
+                      void *state, int64_t state_bytes, int32_t S, float *y, uint32_t *mask, void *stream);
+int     nsd_gate_apply(const nsd_dims *d, const nsd_gate *g, const float *v, const uint32_t *mask, float *out, void *stream);
+
+/*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----
  *
  * Building block, exported so that it can be tested and timed on its own: C[M,N] = A . B with bf16 operands (device

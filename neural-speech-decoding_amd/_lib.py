@@ -160,6 +160,20 @@ class PrepLayout(C.Structure):
 NSD_PREP_MAX_SECTIONS, NSD_PREP_BASELINE, NSD_PREP_CAR = 4, 1, 2
 
 
+class Gate(C.Structure):
+    """nsd_gate of include/nsd.h"""
+    _fields_ = [("rail", C.c_float), ("jump", C.c_float), ("flat_eps", C.c_float), ("flat_samples", C.c_int32), ("pp", C.c_float),
+                ("pp_samples", C.c_int32), ("hold_samples", C.c_int32), ("max_bad", C.c_int32), ("flags", C.c_uint32)]
+
+
+class GateLayout(C.Structure):
+    """nsd_gate_layout of include/nsd.h: offsets inside one slot of a gate state, in 4-byte words"""
+    _fields_ = [(n, C.c_int64) for n in ("prev", "held", "run", "hang", "ring", "bad", "rejected", "steps", "stride")]
+
+
+NSD_GATE_MAX_SPAN, NSD_GATE_ZERO = 64, 1
+
+
 class WsLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("hseq", "cseq", "gact", "inseq", "top", "alpha", "pooled", "fc0_pre",
                                           "dscore", "dpooled", "loss", "adpack", "slabs", "n_slabs", "hslabs", "da_seq", "din", "total")]
@@ -309,6 +323,13 @@ SYMBOLS = {
     "nsd_prep_state_layout": (C.c_int, [C.c_int32, C.POINTER(PrepLayout)]),
     "nsd_prep_reset": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
     "nsd_prep_step": (C.c_int, [_dp, _vp, _fp, _ip, _vp, C.c_int64, C.c_int32, _fp, _vp]),
+    # signal-quality gate around the front end
+    "nsd_gate_path": (C.c_int, [C.c_int32, _vp]),
+    "nsd_gate_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "nsd_gate_state_layout": (C.c_int, [C.c_int32, C.POINTER(GateLayout)]),
+    "nsd_gate_reset": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
+    "nsd_gate_step": (C.c_int, [_dp, _vp, _fp, _ip, _vp, C.c_int64, C.c_int32, _fp, _vp, _vp]),
+    "nsd_gate_apply": (C.c_int, [_dp, _vp, _fp, _vp, _fp, _vp]),
 }
 NSD_MAX_MODELS = 32
 

@@ -1768,4 +1768,98 @@ int nsd_prep_step(const nsd_dims *d, const nsd_prep *p, const float *x, const in
     return nsd_prep_launch(a, (hipStream_t)stream);
 }
 
+// ---- signal-quality gate (nsd_gate_*, include/nsd.h; nsd_gate.hip) ----
+static bool gate_channels(int32_t C) { return C >= 1 && C <= 32; }
+// the configuration alone (who == NULL: a silent query)
+static bool gate_config(const nsd_gate *g, const char *who) {
+#define GATE_REFUSE(...) do { if (who) nsd_set_error(__VA_ARGS__); return false; } while (0)
+    const float thr[4] = {g->rail, g->jump, g->flat_eps, g->pp};
+    static const char *const names[4] = {"rail", "jump", "flat_eps", "pp"};
+    for (int k = 0; k < 4; ++k)
+        if (!prep_finite(thr[k]) || thr[k] < 0.f) GATE_REFUSE("%s: %s = %g (a threshold is finite and >= 0)", who, names[k], thr[k]);
+    if (g->flat_samples < 0) GATE_REFUSE("%s: flat_samples = %d < 0", who, g->flat_samples);
+    if (g->pp_samples < 0 || g->pp_samples > NSD_GATE_MAX_SPAN) GATE_REFUSE("%s: pp_samples = %d outside [0, %d]", who, g->pp_samples, NSD_GATE_MAX_SPAN);
+    if (g->hold_samples < 0) GATE_REFUSE("%s: hold_samples = %d < 0", who, g->hold_samples);
+    if (g->max_bad < 0) GATE_REFUSE("%s: max_bad = %d < 0", who, g->max_bad);
+    if (g->flags & ~NSD_GATE_ZERO) GATE_REFUSE("%s: unknown flag bits 0x%x", who, g->flags);
+#undef GATE_REFUSE
+    return true;
+}
+// the preamble of the entry points that touch a gate state: channels, slot count, size
+static int gate_enter(int32_t C, const char *who, const void *state, int64_t state_bytes, int32_t S) {
+    if (!gate_channels(C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, C); return NSD_E_INVALID; }
+    if (!state) { nsd_set_error("%s: null state", who); return NSD_E_INVALID; }
+    if ((uintptr_t)state % 8) { nsd_set_error("%s: state is not 8-byte aligned (it holds int64 counts)", who); return NSD_E_INVALID; }
+    if (S < 1) { nsd_set_error("%s: S = %d slots", who, S); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)S * gate_stride(C) * (int64_t)sizeof(float);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_gate_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int nsd_gate_path(int32_t C, const nsd_gate *g) { return gate_channels(C) && (!g || gate_config(g, nullptr)) ? 1 : 0; }
+
+int64_t nsd_gate_state_bytes(int32_t C, int32_t S) {
+    if (!gate_channels(C) || S < 1) { nsd_set_error("gate_state_bytes: C outside [1, 32], or S < 1"); return NSD_E_INVALID; }
+    return (int64_t)S * gate_stride(C) * (int64_t)sizeof(float);
+}
+
+int nsd_gate_state_layout(int32_t C, nsd_gate_layout *out) {
+    if (!gate_channels(C) || !out) { nsd_set_error("gate_state_layout: C outside [1, 32], or null pointer"); return NSD_E_INVALID; }
+    out->prev = GATE_PREV; out->held = gate_held(C); out->run = gate_run(C); out->hang = gate_hang(C); out->ring = gate_ring(C);
+    out->bad = gate_bad(C); out->rejected = gate_rejected(C); out->steps = gate_steps(C); out->stride = gate_stride(C);
+    return NSD_OK;
+}
+
+int nsd_gate_reset(int32_t C, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream) {
+    static const char *who = "gate_reset";
+    if (const int rc = gate_enter(C, who, state, state_bytes, S)) return rc;
+    if (slots && (n < 0 || n > S)) { nsd_set_error("%s: n = %d slots of S = %d", who, n, S); return NSD_E_INVALID; }
+    const int count = slots ? n : S;
+    if (count == 0) return NSD_OK;
+    return nsd_gate_reset_launch((float *)state, C, S, slots, count, (hipStream_t)stream);
+}
+
+int nsd_gate_step(const nsd_dims *d, const nsd_gate *g, const float *x, const int32_t *slots, void *state, int64_t state_bytes,
+                  int32_t S, float *y, uint32_t *mask, void *stream) {
+    static const char *who = "gate_step";
+    if (!d || !g || !x || !y || !mask) { nsd_set_error("%s: null pointer (d, g, x, y, mask)", who); return NSD_E_INVALID; }
+    if (!gate_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if (!gate_config(g, who)) return NSD_E_INVALID;
+    if (slots && !state) { nsd_set_error("%s: slots without a state (window mode takes neither)", who); return NSD_E_INVALID; }
+    if (state) {
+        if (const int rc = gate_enter(d->C, who, state, state_bytes, S)) return rc;
+        if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (x != y && x < y + n && y < x + n) { nsd_set_error("%s: y overlaps x partially (in place means y == x)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    GateArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.y = y; a.mask = mask; a.slots = slots; a.state = (float *)state;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.S = state ? S : 0;
+    a.rail = g->rail; a.jump = g->jump; a.flat_eps = g->flat_eps; a.pp = g->pp;
+    a.flat_samples = g->flat_samples; a.pp_samples = g->pp_samples; a.hold_samples = g->hold_samples; a.max_bad = g->max_bad;
+    return nsd_gate_launch(a, (hipStream_t)stream);
+}
+
+int nsd_gate_apply(const nsd_dims *d, const nsd_gate *g, const float *v, const uint32_t *mask, float *out, void *stream) {
+    static const char *who = "gate_apply";
+    if (!d || !g || !v || !mask || !out) { nsd_set_error("%s: null pointer (d, g, v, mask, out)", who); return NSD_E_INVALID; }
+    if (!gate_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if (!gate_config(g, who)) return NSD_E_INVALID;
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (v != out && v < out + n && out < v + n) { nsd_set_error("%s: out overlaps v partially (in place means out == v)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    GateApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.v = v; a.mask = mask; a.out = out;
+    a.steps = (long)d->B * d->T; a.C = d->C; a.max_bad = g->max_bad; a.zero = (g->flags & NSD_GATE_ZERO) != 0;
+    return nsd_gate_apply_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -363,3 +363,33 @@ struct CausalPrepArgs {
 };
 int nsd_prep_launch(const CausalPrepArgs &a, hipStream_t st);
 int nsd_prep_reset_launch(float *state, int C, int S, const int32_t *slots, int n, hipStream_t st);
+
+// signal-quality gate (nsd_gate_* of nsd.h; nsd_gate.hip).  One slot of the caller's state in 4-byte words -- the public layout
+// nsd_gate_state_layout reports; it depends on C alone.  prev / held / ring are fp32, run / hang int32, bad / rejected / steps int64
+constexpr int GATE_SPAN = NSD_GATE_MAX_SPAN;                          // rows of the ring, the longest peak-to-peak span
+constexpr int GATE_PREV = 0;
+__host__ __device__ constexpr int gate_held(int C) { return C; }
+__host__ __device__ constexpr int gate_run(int C) { return 2 * C; }
+__host__ __device__ constexpr int gate_hang(int C) { return 3 * C; }
+__host__ __device__ constexpr int gate_ring(int C) { return 4 * C; }   // ring[GATE_SPAN][C]
+__host__ __device__ constexpr int gate_bad(int C) { return ((4 + GATE_SPAN) * C + 1) & ~1; }   // int64[C]: 8-byte aligned
+__host__ __device__ constexpr int gate_rejected(int C) { return gate_bad(C) + 2 * C; }
+__host__ __device__ constexpr int gate_steps(int C) { return gate_rejected(C) + 2; }
+__host__ __device__ constexpr int gate_stride(int C) { return (gate_steps(C) + 2 + 3) & ~3; }
+struct GateArgs {
+    const float *x; float *y;                // [B,T,C]; y == x allowed
+    uint32_t *mask;                          // [B,T]: bit c set where channel c is bad
+    const int32_t *slots;                    // null: stream b lives in slot b
+    float *state;                            // null: window mode (every trial from a reset state, nothing stored)
+    int B, T, C, S;
+    float rail, jump, flat_eps, pp;
+    int flat_samples, pp_samples, hold_samples, max_bad;
+};
+int nsd_gate_launch(const GateArgs &a, hipStream_t st);
+int nsd_gate_reset_launch(float *state, int C, int S, const int32_t *slots, int n, hipStream_t st);
+struct GateApplyArgs {
+    const float *v; const uint32_t *mask; float *out;   // v, out [B,T,C] (out == v allowed), mask [B,T]
+    long steps;                              // B * T
+    int C, max_bad, zero;
+};
+int nsd_gate_apply_launch(const GateApplyArgs &a, hipStream_t st);

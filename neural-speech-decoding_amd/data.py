@@ -232,3 +232,35 @@ class BatchSchedule:
             raise ValueError(f"BatchSchedule.for_runs: the runs draw {[c // epochs for c in counts]} batches of {batch} per epoch; one "
                              "shared step needs the same count for every run")
         return cls(np.stack([np.stack(p) for p in per]), counts[0] // epochs)
+
+
+def screen_trials(x, gate) -> Tuple[np.ndarray, np.ndarray]:
+    """Signal quality of every trial of a set under the SignalGate `gate`: x [N,T,C] -> (bad_fraction float64 [N,C]: the share of each
+    channel's samples the gate calls bad, rejected_fraction float64 [N]: the share of steps with more than gate.max_bad bad channels).
+    A device tensor goes through one window-mode nsd_gate_step over the whole set (every trial from a reset state); a numpy array or a
+    host tensor through the gate's numpy restatement, which gives the same mask words.  train's --gate-drop-trials drops the trials
+    whose rejected fraction exceeds a bound, before the folds are made."""
+    import torch
+    if torch.is_tensor(x) and x.is_cuda:
+        from . import ops
+        if x.dim() != 3:
+            raise ValueError(f"screen_trials: x must be [N,T,C], got {tuple(x.shape)}")
+        N, T, Cc = (int(v) for v in x.shape)
+        if N == 0:
+            return np.zeros((0, Cc)), np.zeros((0,))
+        _, mask = ops.gate_step(x.contiguous().float(), gate)
+        bits = (mask[..., None] >> torch.arange(32, dtype=torch.int32, device=x.device)) & 1          # [N,T,32]
+        bad = bits[..., :Cc].sum(1, dtype=torch.int64).cpu().numpy()
+        rejected = (bits.sum(2) > int(gate.max_bad)).sum(1, dtype=torch.int64).cpu().numpy()
+    else:
+        xs = np.asarray(x.numpy() if torch.is_tensor(x) else x, np.float32)
+        if xs.ndim != 3:
+            raise ValueError(f"screen_trials: x must be [N,T,C], got {xs.shape}")
+        N, T, Cc = xs.shape
+        if N == 0:
+            return np.zeros((0, Cc)), np.zeros((0,))
+        _, mask = gate.reference(xs)
+        bits = (mask[..., None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)
+        bad = bits[..., :Cc].sum(1, dtype=np.int64)
+        rejected = (bits.sum(2, dtype=np.int64) > int(gate.max_bad)).sum(1, dtype=np.int64)
+    return bad / float(T), rejected / float(T)

@@ -117,7 +117,8 @@ def main(argv=None) -> int:
     from .multimodel import ModelBatchTrainer
     from .ops import Augment, Crop, Loss
     from .prep import CausalPrep
-    from .train import (average_for, concurrent_epoch, concurrent_runs, crop_for, early_stop_settings, evaluate, evaluate_cropped, loss_for,
+    from .train import (average_for, concurrent_epoch, concurrent_runs, crop_for, drop_bad_trials, early_stop_settings, evaluate, evaluate_cropped,
+                        gate_for, loss_for,
                         padded_parts, parse_class_weights, sam_for, schedule_for, selection_text)
 
     ap = build_parser()
@@ -155,6 +156,13 @@ def main(argv=None) -> int:
                                             zscore_seconds=args.prep_zscore_seconds, baseline=not args.prep_no_baseline, car=args.prep_car)
         except ValueError as e:
             ap.error(str(e))
+
+    try:
+        gate = gate_for(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if gate is not None and args.normalize:
+        ap.error("--gate-* with --normalize: the whole-window z-score would be taken over held and zeroed channels")
 
     # every configuration as the options `train` would see, checked before anything runs
     cfg_args, augments = [], []
@@ -197,6 +205,7 @@ def main(argv=None) -> int:
         if ts.x.shape[1] != args.T:
             ap.error(f"--T {args.T} but the trials have {ts.x.shape[1]} samples")
         x_np, y_np = ts.x, ts.y
+    x_np, y_np = drop_bad_trials(x_np, y_np, gate, args.gate_drop_trials, "grid")
     try:
         runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch, es["inner_fraction"] if es else None)
         groups = pack_groups(len(configs), len(runs))
@@ -228,7 +237,7 @@ def main(argv=None) -> int:
         models = []
         for c, k in members:
             torch.manual_seed(runs[k]["seed"])
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, cfg_args[c].dropout, normalize=args.normalize, prep=prep_all, crop=crop_train).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, cfg_args[c].dropout, normalize=args.normalize, prep=prep_all, crop=crop_train, gate=gate).to(dev).train())
         per = lambda f: [f(c, k) for c, k in members]                                         # noqa: E731
         mbt = ModelBatchTrainer(
             models, lr=per(lambda c, k: cfg_args[c].lr), weight_decay=per(lambda c, k: cfg_args[c].weight_decay),

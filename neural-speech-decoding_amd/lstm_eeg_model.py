@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import ops, step_recipe as sr
 from ._lib import NsdError
+from .gate import SignalGate
 from .prep import CausalPrep
 
 CLASS_NAMES = ["Food", "Water", "BG-Noise"]   # verbatim from lstm_eeg_model.py:11
@@ -184,6 +185,10 @@ class EEG_LSTM(nn.Module):
       prep           a CausalPrep: the causal front end (nsd_prep_step, window mode: every trial from a reset state) in front of the
                      LSTM, where normalize runs its z-score -- the model then sees what a StreamDecoder feeds it chunk by chunk.
                      Not together with normalize; no input gradient is offered through it.
+      gate           a SignalGate: the signal-quality gate around the front end (gate -> prep -> apply -> LSTM; nsd_gate_step in
+                     window mode, nsd_gate_apply): a bad channel is held through the front end and zeroed in front of the LSTM; in
+                     eval mode a trial with a rejected step has NaN logits ("no decision"), in train mode nothing is rejected.
+                     Not together with normalize; no input gradient is offered through it.
       crop           an ops.Crop: the window the model was (or is being) trained on by cropped training (Trainer(crop=)).  It changes
                      nothing in forward(); it travels with the model and its checkpoints so that predict_trials(), SimplePredictor and
                      open_stream() know the trained window.
@@ -191,8 +196,16 @@ class EEG_LSTM(nn.Module):
 
     def __init__(self, input_size=8, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, *,
                  residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32",
-                 prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None):
+                 prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None, gate: Optional[SignalGate] = None):
         super().__init__()
+        if gate is not None and not isinstance(gate, SignalGate):
+            raise ValueError(f"gate={gate!r}: expected a SignalGate")
+        if gate is not None and normalize:
+            raise ValueError("gate together with normalize=True: the whole-window z-score would be taken over held and zeroed channels "
+                             "(CausalPrep.design(zscore_seconds=...) is its running form behind the gate)")
+        if gate is not None and not 1 <= input_size <= 32:
+            raise ValueError(f"gate: the signal-quality gate covers 1 .. 32 channels, input_size = {input_size}")
+        self.gate = gate
         if crop is not None and not isinstance(crop, ops.Crop):
             raise ValueError(f"crop={crop!r}: expected an ops.Crop")
         self.crop = crop
@@ -268,7 +281,7 @@ class EEG_LSTM(nn.Module):
         if row.dtype != torch.float32 or row.dim() != 1 or row.numel() != sp.param_count or not row.is_contiguous():
             raise NsdError(f"EEG_LSTM.view_of: row must be a contiguous float32 vector of {sp.param_count} elements")
         twin = EEG_LSTM(sp.C, sp.H, sp.L, sp.K, self.head_dropout_p, residual=self.residual, normalize=self.normalize,
-                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop)
+                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop, gate=self.gate)
         offs = sp.offsets()
         with torch.no_grad():
             for n, p in twin._named_in_order():
@@ -284,13 +297,29 @@ class EEG_LSTM(nn.Module):
 
     # ---- forward --------------------------------------------------------------------------------------
     def _front_end(self, x: torch.Tensor) -> torch.Tensor:
-        """What stands between the caller's window and the LSTM: the z-score (normalize), the causal front end (prep), or nothing."""
+        """What stands between the caller's window and the LSTM: the z-score (normalize), the signal-quality gate around the causal
+        front end (gate -> prep -> apply), or nothing."""
+        if self.gate is not None and x.requires_grad and torch.is_grad_enabled():
+            raise NsdError("EEG_LSTM(gate=...): dx through the signal-quality gate is not offered -- x.requires_grad would get no "
+                           "gradient; detach x, or differentiate a gate-free model on the gated windows (ops.gate_step, ops.gate_apply)")
         if self.prep is not None:
             if x.requires_grad and torch.is_grad_enabled():
                 raise NsdError("EEG_LSTM(prep=...): dx through the causal front end is not offered -- x.requires_grad would get no "
                                "gradient; detach x, or differentiate a prep-free model on ops.prep_step(x, prep)")
-            return ops.prep_step(x, self.prep)
+        if self.gate is not None or self.prep is not None:
+            return self._gate_prep(x)
         return ops.zscore(x) if self.normalize else x
+
+    def _gate_prep(self, x: torch.Tensor) -> torch.Tensor:
+        """gate -> prep -> apply over whole windows, each stage where the model has it.  Train mode never rejects a step."""
+        mask = None
+        if self.gate is not None:
+            x, mask = ops.gate_step(x, self.gate)
+        if self.prep is not None:
+            x = ops.prep_step(x, self.prep, out=x if mask is not None else None)
+        if mask is not None:
+            x = ops.gate_apply(x, self.gate, mask, out=x, max_bad=self.spec.C if self.training else None)
+        return x
 
     def _train_masks(self, B: int, T: int, device):
         if self._mask_override is not None:
@@ -383,8 +412,7 @@ class EEG_LSTM(nn.Module):
             raise ValueError(f"Expected x of shape [B, T, {self.spec.C}], got {tuple(x.shape)}")
         B, T, _ = x.shape
         grid = ops.Crop.grid(T, int(window), hop)
-        if self.prep is not None:
-            x = ops.prep_step(x, self.prep)
+        x = self._gate_prep(x)
         xc, _, _ = ops.crop(x, grid)
         if self.normalize:
             ops.zscore(xc, out=xc)
@@ -488,7 +516,8 @@ class SimplePredictor:
                  preprocess_package: Optional[str] = None, gpu: str = "cuda", residual: bool = False,
                  normalize: bool = False, bidirectional: bool = False, precision: str = "fp32"):
         """A checkpoint written from a model with a causal front end carries it ({"state_dict": ..., "nsd_prep": CausalPrep.to_dict()},
-        trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep.  One written from a model trained on
+        trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep.  A signal-quality gate travels the same way
+        ("nsd_gate": SignalGate.to_dict()).  One written from a model trained on
         crops carries "nsd_crop" = {window, crops, hop} beside it: the model is rebuilt with that ops.Crop (predict_trial, open_stream)."""
         self.device = torch.device(device)
         self.sr = sr
@@ -506,14 +535,15 @@ class SimplePredictor:
                            "no CPU fallback")
         self.gpu = torch.device(gpu)
         state = torch.load(pth_path, map_location="cpu", weights_only=True)
-        prep = crop = None
+        prep = crop = gate = None
         if isinstance(state, dict) and "state_dict" in state:     # both forms, as lstm_eeg_model.py:79-80
             prep = CausalPrep.from_dict(state["nsd_prep"]) if state.get("nsd_prep") is not None else None
             crop = ops.Crop(**{k: int(v) for k, v in state["nsd_crop"].items()}) if state.get("nsd_crop") is not None else None
+            gate = SignalGate.from_dict(state["nsd_gate"]) if state.get("nsd_gate") is not None else None
             state = state["state_dict"]
         self.model = EEG_LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
                               num_classes=num_classes, dropout=dropout, residual=residual, normalize=normalize,
-                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop)
+                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop, gate=gate)
         self.model.load_state_dict(state, strict=True)
         self.model.to(self.gpu).eval()
         self.model.flatten_parameters()

@@ -27,7 +27,7 @@ def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
         raise NsdError(f"{what}: the same module is passed more than once (each model needs its own parameters)")
     for i, mdl in enumerate(models):
         if (mdl.spec != sp or mdl.residual != models[0].residual or mdl.precision != models[0].precision
-                or mdl.normalize != models[0].normalize or mdl.prep != models[0].prep):
+                or mdl.normalize != models[0].normalize or mdl.prep != models[0].prep or mdl.gate != models[0].gate):
             raise NsdError(f"{what}: model {i} has another shape / options than model 0 (mixed shapes: one launch runs one shape)")
     if models[0].residual or models[0].precision != "fp32" or sp.D != 1:
         raise NsdError(f"{what}: the model-batched path runs the plain fp32 stack (no residual extension, no bf16)")
@@ -308,8 +308,8 @@ class ModelBatchTrainer:
         if tuple(y.shape) != (M, B):
             raise NsdError(f"ModelBatchTrainer.{who}: y must be [M,B] = [{M},{B}] or [B], got {tuple(y.shape)}")
         x = x.contiguous().float()
-        if self.models[0].prep is not None:
-            x = ops.prep_step(x, self.models[0].prep)
+        if self.models[0].prep is not None or self.models[0].gate is not None:
+            x = self.models[0]._gate_prep(x)
         elif self.models[0].normalize and crop is None:
             x = ops.zscore(x.reshape(-1, T, Cc)).view(x.shape)
         if crop is None:
@@ -420,6 +420,7 @@ class _EnsembleModel:
         _check_models(models, "EnsemblePredictor")
         self.models = list(models)
         self.spec, self.precision, self.normalize, self.prep = models[0].spec, "fp32", models[0].normalize, models[0].prep
+        self.gate = models[0].gate
         self.params = torch.stack([m.flat_parameters() for m in self.models]).contiguous()
 
     def predict_proba(self, x: torch.Tensor) -> torch.Tensor:

@@ -2096,3 +2096,107 @@ def prep_step(x: torch.Tensor, prep, state: Optional[torch.Tensor] = None, *, sl
     _call("nsd_prep_step", x.device, C.byref(d), C.cast(C.pointer(p), C.c_void_p), _dev_f32(x, "x"), _slots_ptr(slots, "prep_step"),
           _dev_f32(state, "state"), 0 if state is None else _nbytes(state), S, _dev_f32(out, "out"), STREAM)
     return out
+
+
+# ---- signal-quality gate around the front end (nsd_gate_* of include/nsd.h; the configuration: gate.SignalGate) ----
+
+def gate_path(C_: int, gate=None) -> bool:
+    """True where nsd_gate_step covers C_ channels (with the SignalGate `gate`, when given)."""
+    return bool(_lib.lib().nsd_gate_path(int(C_), None if gate is None else C.cast(C.pointer(gate.struct()), C.c_void_p)))
+
+
+def gate_layout(C_: int) -> "_lib.GateLayout":
+    """Offsets, in 4-byte words, of prev[C], held[C] (fp32), run[C], hang[C] (int32), ring[64][C] (fp32), bad[C], rejected and steps
+    (int64) inside one slot, and the slot stride."""
+    lay = _lib.GateLayout()
+    check(_lib.lib().nsd_gate_state_layout(int(C_), C.byref(lay)), "nsd_gate_state_layout")
+    return lay
+
+
+def gate_state(C_: int, S: int, device="cuda") -> torch.Tensor:
+    """A reset gate state of S slots on `device`: [S, stride] 4-byte words carried as float32 (one row per stream; gate_layout names
+    the columns, the integer ones are bit patterns: read them through .view(torch.int32) / .view(torch.int64))."""
+    state = torch.empty((int(S), int(gate_layout(C_).stride)), dtype=torch.float32, device=device)
+    gate_reset(C_, state)
+    return state
+
+
+def gate_reset(C_: int, state: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """Reset all slots of `state`, or the ones a device int32 tensor names: everything zero."""
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    n = 0 if slots is None else int(slots.numel())
+    if slots is not None and n == 0:
+        return
+    _call("nsd_gate_reset", state.device, int(C_), _dev_f32(state, "state"), _nbytes(state), S, _slots_ptr(slots, "gate_reset"), n, STREAM)
+
+
+def _mask_ptr(mask: torch.Tensor, what: str, steps: int) -> int:
+    if mask.dtype != torch.int32 or not mask.is_cuda or not mask.is_contiguous() or int(mask.numel()) != steps:
+        raise NsdError(f"{what}: mask must be a contiguous int32 tensor of {steps} words (one per step) on the device")
+    return mask.data_ptr()
+
+
+def gate_step(x: torch.Tensor, gate, state: Optional[torch.Tensor] = None, *, slots: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """nsd_gate_step on x [B,n,C] (or [M,B,n,C]: M*B trials) -> (y, mask): y of x's shape with every bad channel held at its last good
+    value, mask int32 [B,n] (the bits of the uint32 word: bit c set where channel c is bad).  state=None: window mode, every trial from
+    a reset state.  state [S,stride]: stream mode, stream b advances slot slots[b] (or b) by the chunk.  out, mask: caller-owned
+    buffers; out is x: in place."""
+    if x.dim() not in (3, 4):
+        raise NsdError(f"gate_step: x must be [B,n,C] or [M,B,n,C], got {tuple(x.shape)}")
+    T, Cc = int(x.shape[-2]), int(x.shape[-1])
+    B = int(x.numel()) // max(T * Cc, 1)
+    if state is None and slots is not None:
+        raise NsdError("gate_step: slots without a state")
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"gate_step: {int(slots.numel())} slot indices for {B} streams")
+    if out is None:
+        out = torch.empty_like(x)
+    if out.numel() != x.numel():
+        raise NsdError(f"gate_step: out has {out.numel()} elements for {tuple(x.shape)}")
+    if mask is None:
+        mask = torch.empty(tuple(x.shape[:-1]), dtype=torch.int32, device=x.device)
+    if B == 0:
+        return out, mask
+    S = 0 if state is None else (int(state.shape[0]) if state.dim() == 2 else 0)
+    d, g = Dims(B, T, Cc, 1, 1, 1, 1), gate.struct()
+    _call("nsd_gate_step", x.device, C.byref(d), C.cast(C.pointer(g), C.c_void_p), _dev_f32(x, "x"), _slots_ptr(slots, "gate_step"),
+          _dev_f32(state, "state"), 0 if state is None else _nbytes(state), S, _dev_f32(out, "out"), _mask_ptr(mask, "gate_step", B * T),
+          STREAM)
+    return out, mask
+
+
+def gate_apply(v: torch.Tensor, gate, mask: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+               max_bad: Optional[int] = None) -> torch.Tensor:
+    """nsd_gate_apply on v [B,n,C] (or [M,B,n,C]) behind the front end with gate_step's mask: a step with more than max_bad (default:
+    the gate's) bad channels is NaN, else a bad channel is 0 where the gate zeroes and everything else a bitwise copy.  out is v: in
+    place."""
+    if v.dim() not in (3, 4):
+        raise NsdError(f"gate_apply: v must be [B,n,C] or [M,B,n,C], got {tuple(v.shape)}")
+    T, Cc = int(v.shape[-2]), int(v.shape[-1])
+    B = int(v.numel()) // max(T * Cc, 1)
+    if out is None:
+        out = torch.empty_like(v)
+    if out.numel() != v.numel():
+        raise NsdError(f"gate_apply: out has {out.numel()} elements for {tuple(v.shape)}")
+    if B == 0:
+        return out
+    d, g = Dims(B, T, Cc, 1, 1, 1, 1), gate.struct()
+    if max_bad is not None:
+        g.max_bad = int(max_bad)
+    _call("nsd_gate_apply", v.device, C.byref(d), C.cast(C.pointer(g), C.c_void_p), _dev_f32(v, "v"), _mask_ptr(mask, "gate_apply", B * T),
+          _dev_f32(out, "out"), STREAM)
+    return out
+
+
+def gate_quality(C_: int, state: torch.Tensor, slots=None) -> dict:
+    """The counters of a gate state, read in one copy: {"bad_fraction": [n,C], "rejected_fraction": [n], "steps": [n]} (numpy) for all
+    slots, or the listed ones.  A slot with no samples reports fractions of 0."""
+    import numpy as np
+    lay = gate_layout(C_)
+    lo, hi = int(lay.bad), int(lay.steps) + 2
+    rows = state if slots is None else state[torch.as_tensor(list(slots), dtype=torch.long, device=state.device)]
+    words = rows[:, lo:hi].contiguous().cpu().numpy().view(np.int64)          # bad[C], rejected, steps
+    steps = words[:, int(C_) + 1].copy()
+    n = np.maximum(steps, 1).astype(np.float64)
+    return {"bad_fraction": words[:, :int(C_)] / n[:, None], "rejected_fraction": words[:, int(C_)] / n, "steps": steps}

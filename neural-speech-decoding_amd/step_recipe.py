@@ -61,10 +61,15 @@ class StepRecipe:
 
     Bound batches (bind() / take() / gather() / check_gather(), behind the trainers' bind_batches and step_scheduled): the trials and
     the run's index schedule stay on the device and nsd_gather forms each step's batch there, as the stage in front of prepare():
-    gather -> augment -> prep -> crop -> mixup.  It draws nothing and copies bit for bit, so the step behind it is the host-fed step."""
+    gather -> augment -> prep -> crop -> mixup.  It draws nothing and copies bit for bit, so the step behind it is the host-fed step.
+
+    A model with a signal-quality gate (EEG_LSTM(gate=...)) adds its two stages around the front end, in window mode: gather -> augment
+    -> gate -> prep -> apply -> crop -> mixup.  The apply stage of a training step never rejects (max_bad = C), so the loss stays finite;
+    bad trials are dropped at the data-set level (data.screen_trials)."""
 
     def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None, crop=None):
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
+        self.gate = getattr(model, "gate", None)
         self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
         self.probs = [(m.dropout_p, m.head_dropout_p) for m in models] if models is not None else None
         M = len(models) if models is not None else 1
@@ -219,8 +224,10 @@ class StepRecipe:
     def static_buffers(self, x: torch.Tensor) -> dict:
         """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""
         buf = {}
-        if self.augment is not None or self.prep is not None or (self.normalize and self.crop is None):
+        if self.augment is not None or self.prep is not None or self.gate is not None or (self.normalize and self.crop is None):
             buf["xn"] = torch.empty_like(x)
+        if self.gate is not None:                    # the mask words of the signal-quality gate, one per (trial, step)
+            buf["gm"] = torch.empty(tuple(x.shape[:-1]), dtype=torch.int32, device=x.device)
         if self.crop is not None:                    # the crops (z-scored in place with normalize) and their labels
             rows, W = self.dims(int(x.shape[0]), int(x.shape[1]))
             buf["xc"] = x = torch.empty((rows, W, x.shape[2]), dtype=torch.float32, device=x.device)
@@ -253,8 +260,13 @@ class StepRecipe:
             x = ops.augment(x, self.augment, rngs, M=M, zscore=self.normalize and self.crop is None, step_dev=step_dev, out=bufs.get("xn"))
         elif self.normalize and self.crop is None:   # as EEG_LSTM.forward: the model is trained on what it is evaluated on
             x = ops.zscore(x.reshape(-1, T, Cc), out=bufs.get("xn")).view(x.shape)
+        mask = None
+        if self.gate is not None:          # augment -> gate -> prep -> apply: the detector sees the raw (augmented) samples
+            x, mask = ops.gate_step(x, self.gate, out=x if self.augment is not None else bufs.get("xn"), mask=bufs.get("gm"))
         if self.prep is not None:          # augment -> prep -> mixup: the front end sees the raw (augmented) samples, as a stream's does
-            x = ops.prep_step(x, self.prep, out=x if self.augment is not None else bufs.get("xn"))
+            x = ops.prep_step(x, self.prep, out=x if (self.augment is not None or mask is not None) else bufs.get("xn"))
+        if mask is not None:               # a bad channel is zeroed; inside a training step nothing is rejected (the loss stays finite)
+            x = ops.gate_apply(x, self.gate, mask, out=x, max_bad=int(Cc))
         if self.crop is not None:          # ... -> prep -> crop -> mixup: the step's dimensions become (B * R, W) here
             self.crop.check_trial(T)
             soft = y.is_floating_point()

@@ -59,6 +59,9 @@ class StreamDecoder:
 
     A model with a causal front end (EEG_LSTM(prep=...)) is decoded through it: the decoder owns a prep state of the same slots, push
     runs nsd_prep_step (stream mode) and then nsd_stream_step, and reset / state_dict / load_state_dict cover both states.
+    A model with a signal-quality gate (EEG_LSTM(gate=...)) adds a gate state of the same slots: push runs nsd_gate_step -> (nsd_prep_step)
+    -> nsd_gate_apply -> the step; a rejected step is NaN, so this decoder and the ensemble one read NaN until the slot is reset, while the
+    sliding decoders lose exactly the windows that contain it.  quality(slots=None) reports what the gate has seen.
     """
 
     def __init__(self, model, streams: int = 1):
@@ -66,9 +69,75 @@ class StreamDecoder:
         self.model, self.streams, self.device = model, int(streams), flat.device
         self._layout = ops.stream_layout(model.spec)
         self.state = ops.stream_state(model.spec, self.streams, self.device)
+        self._init_front(model)
+
+    def _init_front(self, model) -> None:
+        """What runs in front of the model's step, each with a state of the decoder's slots: the signal-quality gate (model.gate) and
+        the causal front end (model.prep).  Their outputs go to one set of buffers per chunk shape: push allocates nothing new."""
+        C_ = model.spec.C
         self.prep = model.prep
-        self.prep_state = None if self.prep is None else ops.prep_state(model.spec.C, self.streams, self.device)
-        self._prepped = {}                                  # the front end's output, one buffer per chunk shape: push allocates nothing new
+        self.prep_state = None if self.prep is None else ops.prep_state(C_, self.streams, self.device)
+        self._prepped = {}
+        self.gate = getattr(model, "gate", None)
+        self.gate_state = None if self.gate is None else ops.gate_state(C_, self.streams, self.device)
+        self._gated = {}                                    # chunk shape -> (held samples, mask words)
+
+    def _front(self, x: torch.Tensor, slots) -> torch.Tensor:
+        """gate -> prep -> apply on a chunk, in stream mode: a bad channel is held through the front end and zeroed behind it, a step
+        that is bad on too many channels is NaN -- the decoders' poison contract then gives "no decision" where it belongs."""
+        mask = None
+        if self.gate is not None:
+            bufs = self._gated.get(tuple(x.shape))
+            if bufs is None:
+                bufs = self._gated[tuple(x.shape)] = (torch.empty_like(x), torch.empty(tuple(x.shape[:2]), dtype=torch.int32,
+                                                                                         device=x.device))
+            x, mask = ops.gate_step(x, self.gate, self.gate_state, slots=slots, out=bufs[0], mask=bufs[1])
+        if self.prep is not None:
+            out = self._prepped.get(tuple(x.shape))
+            if out is None:
+                out = self._prepped[tuple(x.shape)] = torch.empty_like(x)
+            x = ops.prep_step(x, self.prep, self.prep_state, slots=slots, out=out)
+        if mask is not None:
+            x = ops.gate_apply(x, self.gate, mask, out=x)
+        return x
+
+    def _reset_front(self, slots) -> None:
+        C_ = self.model.spec.C
+        if self.prep is not None:
+            ops.prep_reset(C_, self.prep_state, slots)
+        if self.gate is not None:
+            ops.gate_reset(C_, self.gate_state, slots)
+
+    def _front_state_dict(self, sd: dict) -> dict:
+        if self.prep is not None:
+            sd["prep_state"] = self.prep_state.detach().cpu().clone()
+        if self.gate is not None:
+            sd["gate_state"] = self.gate_state.detach().cpu().clone()
+        return sd
+
+    def _check_front_state(self, sd: dict, who: str):
+        ps, gs = sd.get("prep_state"), sd.get("gate_state")
+        if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
+            raise NsdError(f"{who}: the checkpoint and the decoder differ in their causal front end's state")
+        if (gs is None) != (self.gate is None) or (gs is not None and tuple(gs.shape) != tuple(self.gate_state.shape)):
+            raise NsdError(f"{who}: the checkpoint and the decoder differ in their signal-quality gate's state")
+        return ps, gs
+
+    def _load_front_state(self, ps, gs) -> None:
+        if ps is not None:
+            self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
+        if gs is not None:
+            self.gate_state.copy_(gs.to(self.device, dtype=torch.float32))
+
+    def quality(self, slots=None) -> dict:
+        """What the signal-quality gate has seen per slot since its reset, read from its state in one copy: {"bad_fraction": [n, C]
+        (bad samples / samples, per channel), "rejected_fraction": [n] (rejected steps / samples), "steps": int64 [n]} as numpy
+        arrays, for all slots or the named ones."""
+        if self.gate is None:
+            raise NsdError(f"{type(self).__name__}.quality: the model has no signal-quality gate (EEG_LSTM(gate=SignalGate(...)))")
+        if slots is not None:
+            slots = [int(v) for v in self._slots(slots).cpu().tolist()]
+        return ops.gate_quality(self.model.spec.C, self.gate_state, slots)
 
     def _slots(self, slots, n: Optional[int] = None) -> Optional[torch.Tensor]:
         if slots is None:
@@ -95,12 +164,7 @@ class StreamDecoder:
             raise NsdError(f"StreamDecoder.push: {x.shape[0]} streams pushed, the decoder has {self.streams}")
         x = x.to(self.device, non_blocking=True).contiguous().float()
         slots = self._slots(slots, int(x.shape[0]))
-        if self.prep is not None:
-            out = self._prepped.get(tuple(x.shape))
-            if out is None:
-                out = self._prepped[tuple(x.shape)] = torch.empty_like(x)
-            x = ops.prep_step(x, self.prep, self.prep_state, slots=slots, out=out)
-        return self._step(x, slots, read)
+        return self._step(self._front(x, slots), slots, read)
 
     def _step(self, x: torch.Tensor, slots, read: bool) -> Optional[torch.Tensor]:
         _, probs = ops.stream_step(self.model.spec, self.model.flat_parameters(), x, self.state, slots=slots,
@@ -115,8 +179,7 @@ class StreamDecoder:
     def reset(self, slots=None) -> None:
         slots = self._slots(slots)
         ops.stream_reset(self.model.spec, self.state, slots)
-        if self.prep is not None:
-            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+        self._reset_front(slots)
 
     @property
     def steps(self) -> np.ndarray:
@@ -124,21 +187,15 @@ class StreamDecoder:
         return self.state.view(torch.int64)[:, col].cpu().numpy().copy()
 
     def state_dict(self) -> dict:
-        sd = {"state": self.state.detach().cpu().clone(), "stride": int(self._layout.stride)}
-        if self.prep is not None:
-            sd["prep_state"] = self.prep_state.detach().cpu().clone()
-        return sd
+        return self._front_state_dict({"state": self.state.detach().cpu().clone(), "stride": int(self._layout.stride)})
 
     def load_state_dict(self, sd: dict) -> None:
         st = sd["state"]
         if tuple(st.shape) != tuple(self.state.shape) or int(sd.get("stride", st.shape[-1])) != int(self._layout.stride):
             raise NsdError(f"StreamDecoder.load_state_dict: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
-        ps = sd.get("prep_state")
-        if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
-            raise NsdError("StreamDecoder.load_state_dict: the checkpoint and the decoder differ in their causal front end's state")
+        ps, gs = self._check_front_state(sd, "StreamDecoder.load_state_dict")
         self.state.copy_(st.to(self.device, dtype=torch.float32))
-        if ps is not None:
-            self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
+        self._load_front_state(ps, gs)
 
 
 def _check_ensemble(dec, models, streams, who: str, path):
@@ -194,9 +251,7 @@ class EnsembleStreamDecoder(StreamDecoder):
         members, first = _check_ensemble(self, models, streams, who, path)
         self._layout = ops.stream_layout(first.spec)
         self.state = ops.multi_stream_state(first.spec, len(members), self.streams, self.device)
-        self.prep = first.prep
-        self.prep_state = None if self.prep is None else ops.prep_state(first.spec.C, self.streams, self.device)
-        self._prepped = {}
+        self._init_front(first)
         self.member_probs: Optional[torch.Tensor] = None
 
     def _step(self, x: torch.Tensor, slots, read: bool) -> Optional[torch.Tensor]:
@@ -224,8 +279,7 @@ class EnsembleStreamDecoder(StreamDecoder):
         else:                                               # slot s of every model: m*S + s of the flat state
             every = (slots[None, :] + S * torch.arange(M, dtype=torch.int32, device=self.device)[:, None]).reshape(-1).contiguous()
             ops.stream_reset(self.model.spec, flat, every)
-        if self.prep is not None:
-            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+        self._reset_front(slots)
 
     @property
     def steps(self) -> np.ndarray:
@@ -262,9 +316,7 @@ class SlidingStreamDecoder(StreamDecoder):
         self.window, self.hop = int(window), int(hop)
         self._layout = ops.window_layout(model.spec, self.window, self.hop)
         self.state = ops.window_state(model.spec, self.window, self.hop, self.streams, self.device)
-        self.prep = model.prep
-        self.prep_state = None if self.prep is None else ops.prep_state(model.spec.C, self.streams, self.device)
-        self._prepped = {}
+        self._init_front(model)
         self._all = torch.arange(self.streams, dtype=torch.int64, device=self.device)
         self._last_end = torch.full((self.streams,), -1, dtype=torch.int64, device=self.device)
         self._last_probs = torch.full((self.streams, model.spec.K), float("nan"), dtype=torch.float32, device=self.device)
@@ -299,8 +351,7 @@ class SlidingStreamDecoder(StreamDecoder):
     def reset(self, slots=None) -> None:
         slots = self._slots(slots)
         ops.window_reset(self.model.spec, self.window, self.hop, self.state, slots)
-        if self.prep is not None:
-            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+        self._reset_front(slots)
         idx = self._all if slots is None else slots.long()
         self._last_end[idx] = -1
         self._last_probs[idx] = float("nan")
@@ -313,9 +364,7 @@ class SlidingStreamDecoder(StreamDecoder):
     def state_dict(self) -> dict:
         sd = {"state": self.state.detach().cpu().clone(), "window": self.window, "hop": self.hop,
               "last_end": self._last_end.cpu().clone(), "last_probs": self._last_probs.cpu().clone()}
-        if self.prep is not None:
-            sd["prep_state"] = self.prep_state.detach().cpu().clone()
-        return sd
+        return self._front_state_dict(sd)
 
     def load_state_dict(self, sd: dict) -> None:
         who = f"{type(self).__name__}.load_state_dict"
@@ -325,12 +374,9 @@ class SlidingStreamDecoder(StreamDecoder):
         st = sd["state"]
         if tuple(st.shape) != tuple(self.state.shape):
             raise NsdError(f"{who}: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
-        ps = sd.get("prep_state")
-        if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
-            raise NsdError(f"{who}: the checkpoint and the decoder differ in their causal front end's state")
+        ps, gs = self._check_front_state(sd, who)
         self.state.copy_(st.to(self.device, dtype=torch.float32))
-        if ps is not None:
-            self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
+        self._load_front_state(ps, gs)
         self._last_end.copy_(sd["last_end"].to(self.device))
         self._last_probs.copy_(sd["last_probs"].to(self.device))
 
@@ -368,9 +414,7 @@ class EnsembleSlidingStreamDecoder(SlidingStreamDecoder):
         self.window, self.hop = int(window), int(hop)
         self._layout = ops.window_layout(first.spec, self.window, self.hop)
         self.state = ops.multi_window_state(first.spec, self.window, self.hop, len(members), self.streams, self.device)
-        self.prep = first.prep
-        self.prep_state = None if self.prep is None else ops.prep_state(first.spec.C, self.streams, self.device)
-        self._prepped = {}
+        self._init_front(first)
         self._all = torch.arange(self.streams, dtype=torch.int64, device=self.device)
         self._last_end = torch.full((self.streams,), -1, dtype=torch.int64, device=self.device)
         self._last_probs = torch.full((self.streams, first.spec.K), float("nan"), dtype=torch.float32, device=self.device)
@@ -392,8 +436,7 @@ class EnsembleSlidingStreamDecoder(SlidingStreamDecoder):
         else:                                               # stream s of every model: m*S + s of the flat state
             every = (slots[None, :] + S * torch.arange(M, dtype=torch.int32, device=self.device)[:, None]).reshape(-1).contiguous()
             ops.window_reset(self.model.spec, self.window, self.hop, flat, every)
-        if self.prep is not None:
-            ops.prep_reset(self.model.spec.C, self.prep_state, slots)
+        self._reset_front(slots)
         idx = self._all if slots is None else slots.long()
         self._last_end[idx] = -1
         self._last_probs[idx] = float("nan")

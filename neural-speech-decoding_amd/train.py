@@ -22,6 +22,7 @@ import torch
 from . import data as D
 from .lstm_eeg_model import EEG_LSTM
 from .ops import Augment, Average, Crop, Loss, LrSchedule, Sam
+from .gate import SignalGate
 from .prep import CausalPrep
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
@@ -52,6 +53,35 @@ def evaluate_cropped(model: EEG_LSTM, x: torch.Tensor, y: torch.Tensor, grid: Cr
 
 
 CROP_OPTIONS = ("crop_seconds", "crops_per_trial", "crop_hop_seconds")
+GATE_OPTIONS = ("gate_rail", "gate_jump", "gate_flat_seconds", "gate_pp", "gate_pp_seconds", "gate_hold_seconds", "gate_max_bad_channels",
+                "gate_drop_trials")
+
+
+def gate_for(args) -> Optional[SignalGate]:
+    """The signal-quality gate the --gate-* options describe (None: none of its detectors is on); ValueError names a bad option."""
+    if all(v is None for v in (args.gate_rail, args.gate_jump, args.gate_flat_seconds, args.gate_pp)):
+        if any(getattr(args, k) is not None for k in GATE_OPTIONS):
+            raise ValueError("--gate-*: no detector is on: give --gate-rail, --gate-jump, --gate-flat-seconds or --gate-pp")
+        return None
+    if args.gate_drop_trials is not None and not 0.0 <= args.gate_drop_trials <= 1.0:
+        raise ValueError(f"--gate-drop-trials {args.gate_drop_trials} outside [0, 1]")
+    if args.gate_drop_trials is not None and args.gate_max_bad_channels is None:
+        raise ValueError("--gate-drop-trials needs --gate-max-bad-channels: without it no step is ever rejected and no trial dropped")
+    return SignalGate.design(fs=125.0, rail=args.gate_rail, jump=args.gate_jump, flat_seconds=args.gate_flat_seconds, pp=args.gate_pp,
+                             pp_seconds=0.5 if args.gate_pp_seconds is None else args.gate_pp_seconds,
+                             hold_seconds=0.0 if args.gate_hold_seconds is None else args.gate_hold_seconds,
+                             max_bad_channels=args.gate_max_bad_channels)
+
+
+def drop_bad_trials(x_np, y_np, gate: Optional[SignalGate], fraction: Optional[float], who: str):
+    """--gate-drop-trials: the trials whose rejected fraction (data.screen_trials) exceeds `fraction` leave the set before the folds
+    are made -> (x, y); prints how many."""
+    if gate is None or fraction is None:
+        return x_np, y_np
+    _, rejected = D.screen_trials(x_np, gate)
+    keep = rejected <= fraction
+    print(f"{who}: --gate-drop-trials {fraction}: dropped {int((~keep).sum())} of {len(keep)} trials", file=sys.stderr)
+    return x_np[keep], y_np[keep]
 
 
 def crop_for(args, fs: float = 125.0):
@@ -285,6 +315,16 @@ def build_parser() -> argparse.ArgumentParser:
                                                                             "starting variance is calibrated on the training split (with --concurrent: on all trials)")
     ap.add_argument("--prep-car", action="store_true", help="causal front end: common-average reference")
     ap.add_argument("--prep-no-baseline", action="store_true", help="causal front end: do not subtract each window's first sample")
+    ap.add_argument("--gate-rail", type=float, default=None, help="signal-quality gate (SignalGate): a sample with |x| >= this is bad")
+    ap.add_argument("--gate-jump", type=float, default=None, help="signal-quality gate: a sample-to-sample step >= this is bad")
+    ap.add_argument("--gate-flat-seconds", type=float, default=None, help="signal-quality gate: equal samples for this long are bad")
+    ap.add_argument("--gate-pp", type=float, default=None, help="signal-quality gate: a peak-to-peak swing >= this within --gate-pp-seconds is bad")
+    ap.add_argument("--gate-pp-seconds", type=float, default=None, help="signal-quality gate: the span of --gate-pp (default 0.5, at most 64 samples)")
+    ap.add_argument("--gate-hold-seconds", type=float, default=None, help="signal-quality gate: a channel stays bad this long after its last bad sample")
+    ap.add_argument("--gate-max-bad-channels", type=int, default=None, help="signal-quality gate: a step with more bad channels than this is "
+                                                                             "rejected: no decision (default: never)")
+    ap.add_argument("--gate-drop-trials", type=float, default=None, metavar="FRACTION",
+                    help="signal-quality gate: drop the trials whose share of rejected steps exceeds FRACTION before the folds are made")
     ap.add_argument("--early-stop-patience", type=int, default=None,
                     help="with --kfold K --concurrent: early stopping per fold on an inner split of its training trials -- after every epoch "
                          "all folds are scored on their inner parts in two launches, each keeps the parameters of its best epoch on the "
@@ -335,6 +375,13 @@ def main(argv=None) -> int:
                                             zscore_seconds=args.prep_zscore_seconds, baseline=not args.prep_no_baseline, car=args.prep_car)
         except ValueError as e:
             ap.error(str(e))
+
+    try:
+        gate = gate_for(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if gate is not None and args.normalize:
+        ap.error("--gate-* with --normalize: the whole-window z-score would be taken over held and zeroed channels")
 
     def prep_for(idx):
         """The front end of a run trained on the trials idx: the design, its starting variance calibrated on those trials."""
@@ -394,7 +441,6 @@ def main(argv=None) -> int:
         # class-dependent mean shift on one channel so that there is something to learn
         x_np = (2.7 * rs.standard_normal((args.synthetic, args.T, 8))).astype(np.float32)
         x_np[np.arange(args.synthetic), :, y_np % 8] += 1.5
-        tr_idx, va_idx = D.stratified_split(y_np, args.val_fraction, args.seed)
     else:
         if not args.data:
             ap.error("give --data or --synthetic")
@@ -403,7 +449,8 @@ def main(argv=None) -> int:
         if ts.x.shape[1] != args.T:
             ap.error(f"--T {args.T} but the trials have {ts.x.shape[1]} samples")
         x_np, y_np = ts.x, ts.y
-        tr_idx, va_idx = D.stratified_split(y_np, args.val_fraction, args.seed)
+    x_np, y_np = drop_bad_trials(x_np, y_np, gate, args.gate_drop_trials, "train")
+    tr_idx, va_idx = D.stratified_split(y_np, args.val_fraction, args.seed)
     x_all = torch.from_numpy(x_np).to(dev)
     y_all = torch.from_numpy(y_np).to(dev)
     if args.device_batches and world > 1:
@@ -428,7 +475,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + ("sam_rho",) or v is not None)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + GATE_OPTIONS + ("sam_rho",) or v is not None)}
 
     def score(mdl, xs, ys):
         """(accuracy, first-window accuracy or None): whole trials, or with --crop-seconds trials pooled over the evaluation grid"""
@@ -444,7 +491,7 @@ def main(argv=None) -> int:
         what is written / scored -- the number of epochs is fixed beforehand, nothing is selected."""
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
-                         bidirectional=args.bidirectional, prep=prep_for(tr_idx), crop=crop_train).to(dev).train()
+                         bidirectional=args.bidirectional, prep=prep_for(tr_idx), crop=crop_train, gate=gate).to(dev).train()
         steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
         average = average_for(args, steps_per_epoch)
         trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
@@ -509,7 +556,7 @@ def main(argv=None) -> int:
         models, prep_all = [], prep_for(np.arange(len(y_np)))
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all, crop=crop_train).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all, crop=crop_train, gate=gate).to(dev).train())
         steps_per_epoch = concurrent_epoch(runs, args.batch, 0, lambda idxs: None)
         average = average_for(args, steps_per_epoch)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,

@@ -553,13 +553,16 @@ def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:
     """Write a .pth the reference's SimplePredictor loads unchanged (raw state_dict with the reference's
     key names on CPU; lstm_eeg_model.py:77-81).  A model with a causal front end is written in the dict form both loaders accept,
     {"state_dict": ..., "nsd_prep": prep.to_dict()}: the reference's loader reads the weights, SimplePredictor here rebuilds the prep too.
-    A model trained on crops (model.crop) adds "nsd_crop" = {window, crops, hop} to that dict; a model with neither is written as before."""
+    A model trained on crops (model.crop) adds "nsd_crop" = {window, crops, hop} to that dict, one with a signal-quality gate
+    "nsd_gate" = gate.to_dict(); a model with neither is written as before."""
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    crop = getattr(model, "crop", None)
-    if model.prep is None and crop is None:
+    crop, gate = getattr(model, "crop", None), getattr(model, "gate", None)
+    if model.prep is None and crop is None and gate is None:
         torch.save(sd, path)
         return
     extra = {} if model.prep is None else {"nsd_prep": model.prep.to_dict()}
+    if gate is not None:
+        extra["nsd_gate"] = gate.to_dict()
     if crop is not None:
         extra["nsd_crop"] = {"window": int(crop.window), "crops": int(crop.crops), "hop": int(crop.hop)}
     torch.save({"state_dict": sd, **extra}, path)
