@@ -1070,6 +1070,82 @@ int     nsd_gate_step(const nsd_dims *d, const nsd_gate *g, const float *x, cons
 int     nsd_gate_apply(const nsd_dims *d, const nsd_gate *g, const float *v, const uint32_t *mask, float *out, void *stream);
 
 /*
+ * ---- session alignment: channel covariance and whitening (an EXTENSION: the reference never mixes channels) ----
+ *
+ * Euclidean alignment: a session is whitened by the inverse square root of its mean channel second moment, y = R^(-1/2) x, a fixed
+ * C x C matrix at serve time.  Three stages behind nsd_gate_apply, C in [1, 32] (the gate's range):
+ *   nsd_cov_step (stateful)     accumulates sum[i][j] += (double)v[i] * (double)v[j] over the USED steps of a stream, beside the stream;
+ *   nsd_whiten_fit              forms W = R'^(-1/2) per group of accumulators, on the device;
+ *   nsd_spatial_apply (stateless)  out[b,t,:] = W[sel[b]] . v[b,t,:] in front of the model.
+ * The formula is the RAW second moment R = (1/n) sum_t v[t] v[t]^T, not a centred covariance: the signal behind a high-pass or baseline
+ * stage is near zero-mean, and a raw moment composes over chunks and sessions by adding sums and counts.
+ *
+ * nsd_cov_step.  v [B,T,C] fp32, mask NULL or [B,T] uint32 (the words of nsd_gate_step).  The samples of a stream are taken in ascending
+ * order.  A step is USED if all its C values are finite and, where a mask is given, its word is 0; a used step does, for all i, j,
+ * sum[i][j] = sum[i][j] + (double)v[i] * (double)v[j] (the product of two fp32 values is exact in double, so contraction cannot change
+ * a bit) and count += 1; any other step does skipped += 1 and adds nothing.  The full matrix is stored and is symmetric bit for bit.
+ * Every (i, j) is one serial chain over time: the state after n samples is bit for bit a function of the samples alone -- not of the
+ * cut, the slot, the other streams of the call, the HIP stream or a graph replay.
+ *   stream mode (state != NULL, sums == counts == NULL): one slot is sum[C][C] (double), count, skipped (int64): C*C + 2 8-byte words.
+ *     slots as in nsd_prep_step; a slot index outside [0, S) touches nothing.
+ *   window mode (state == NULL, slots == NULL, S ignored): every trial starts from zero; trial b's matrix goes to sums[b] ([B][C][C]
+ *     double) and its {count, skipped} to counts[b] ([B][2] int64).
+ *   nsd_cov_state_bytes / nsd_cov_state_layout (offsets in 8-byte words) / nsd_cov_reset: as the prep functions of those names; a reset
+ *   slot is all zero.
+ *
+ * nsd_whiten_fit.  N accumulators: accumulator a's matrix is sums + a * sum_stride (doubles), its {count, skipped} counts + a *
+ * count_stride (int64 words) -- window-mode outputs (strides C*C and 2) or a stream state read in place (sums = state, counts =
+ * (int64 *)state + C*C, both strides C*C + 2).  group: DEVICE int32[N] or NULL (every accumulator in group 0); an index outside [0, G) is
+ * ignored and counted in every record.  One workgroup per group, all in double:
+ *   S = sum of the group's matrices in ascending accumulator order, n = sum of their counts;  R = S / n;
+ *   R' = (1 - shrinkage) * R + shrinkage * (tr R / C) * I;
+ *   a cyclic Jacobi eigen-solve of R' (pairs (p, q) row by row; a pair is rotated unless |a_pq| <= 2^-53 * sqrt(|a_pp * a_qq|)); it stops
+ *   after the first sweep that rotates nothing, or after NSD_WHITEN_MAX_SWEEPS sweeps;
+ *   eigenvalues are clipped from below at floor * lambda_max;  W = V diag(lambda^(-1/2)) V^T, symmetric bit for bit, rounded once to fp32.
+ * Record per group (nsd_whiten_record, 64 bytes): steps used and skipped, tr R / C, the smallest and largest eigenvalue before the clip,
+ * sweeps taken, accumulators of the group, ignored accumulators, and a status word:
+ *   NSD_WHITEN_FEW            n < min_steps: W is the identity (a group without accumulators has n = 0)
+ *   NSD_WHITEN_NONFINITE      a sum that is not finite, or tr R <= 0 (tested where FEW is not set): W is the identity
+ *   NSD_WHITEN_CLIPPED        at least one eigenvalue was floored
+ *   NSD_WHITEN_NOT_CONVERGED  the sweep cap was reached; W is written all the same
+ * Where W is the identity the record's trace, eigenvalues and sweeps are 0.  A bad group never touches another group's output.
+ *
+ * nsd_spatial_apply.  v, out [B,T,C], W [n_mat][C][C] fp32, sel: DEVICE int32[B] or NULL (matrix 0 for every row b).
+ *   out[b,t,i] = ((W[i][0]*v[0] + W[i][1]*v[1]) + ...) serially over j, every fp32 operation rounding on its own.  A NaN anywhere in a
+ *   step makes the whole step NaN by the arithmetic (0 * NaN is NaN).  A sel entry outside [0, n_mat) gives NaN rows.  out == v is
+ *   allowed (a workgroup reads all its steps before it writes one), a partial overlap is refused.
+ *
+ * NSD_E_INVALID before any launch: a NULL d / v / out / W / sums / counts / records where one is needed; C outside [1, 32]; T < 1; B < 0;
+ * B > S or S < 1 (stream mode); slots without a state; sums or counts with a state; a state that is not 8-byte aligned; N < 0, G < 1,
+ * n_mat < 1; a stride below its row (sum_stride < C*C, count_stride < 2); shrinkage outside [0, 1]; floor outside (0, 1]; min_steps < 1;
+ * partially overlapping v / out.  NSD_E_WORKSPACE: state_bytes < nsd_cov_state_bytes(C, S).  B = 0 (n = 0) launches nothing; N = 0
+ * still writes G identities.  No allocation, no host synchronisation: every call can be captured.  Additive: NSD_VERSION stays as it
+ * is, a caller detects the feature by the symbols.
+ */
+#define NSD_WHITEN_MAX_SWEEPS 40
+#define NSD_WHITEN_FEW           1u
+#define NSD_WHITEN_NONFINITE     2u
+#define NSD_WHITEN_CLIPPED       4u
+#define NSD_WHITEN_NOT_CONVERGED 8u
+typedef struct nsd_whiten { float shrinkage; float floor; int32_t min_steps; } nsd_whiten;
+typedef struct nsd_whiten_record {
+    int64_t steps, skipped;                  /* used and skipped steps of the group's accumulators */
+    double  trace_mean, eig_min, eig_max;    /* tr R / C; the eigenvalues of R' before the clip */
+    int32_t sweeps; uint32_t status;
+    int32_t accumulators, ignored;           /* accumulators of this group; accumulators of the call with a group index outside [0, G) */
+    int64_t reserved;
+} nsd_whiten_record;
+typedef struct nsd_cov_layout { int64_t sum, count, skipped, stride; } nsd_cov_layout;   /* 8-byte words in a slot; depends on C only */
+int64_t nsd_cov_state_bytes(int32_t C, int32_t S);
+int     nsd_cov_state_layout(int32_t C, nsd_cov_layout *out);
+int     nsd_cov_reset(int32_t C, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream);
+int     nsd_cov_step(const nsd_dims *d, const float *v, const uint32_t *mask, const int32_t *slots,
+                     void *state, int64_t state_bytes, int32_t S, double *sums, int64_t *counts, void *stream);
+int     nsd_whiten_fit(int32_t C, const nsd_whiten *w, const double *sums, int64_t sum_stride, const int64_t *counts, int64_t count_stride,
+                       int32_t N, const int32_t *group, int32_t G, float *W, nsd_whiten_record *records, void *stream);
+int     nsd_spatial_apply(const nsd_dims *d, const float *v, const float *W, int32_t n_mat, const int32_t *sel, float *out, void *stream);
+
+/*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----
  *
  * Building block, exported so that it can be tested and timed on its own: C[M,N] = A . B with bf16 operands (device

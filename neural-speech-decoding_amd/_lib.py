@@ -174,6 +174,26 @@ class GateLayout(C.Structure):
 NSD_GATE_MAX_SPAN, NSD_GATE_ZERO = 64, 1
 
 
+class Whiten(C.Structure):
+    """nsd_whiten of include/nsd.h"""
+    _fields_ = [("shrinkage", C.c_float), ("floor", C.c_float), ("min_steps", C.c_int32)]
+
+
+class WhitenRecord(C.Structure):
+    """nsd_whiten_record of include/nsd.h: one group's fit (64 bytes)"""
+    _fields_ = [("steps", C.c_int64), ("skipped", C.c_int64), ("trace_mean", C.c_double), ("eig_min", C.c_double), ("eig_max", C.c_double),
+                ("sweeps", C.c_int32), ("status", C.c_uint32), ("accumulators", C.c_int32), ("ignored", C.c_int32), ("reserved", C.c_int64)]
+
+
+class CovLayout(C.Structure):
+    """nsd_cov_layout of include/nsd.h: offsets inside one slot of a cov state, in 8-byte words"""
+    _fields_ = [(n, C.c_int64) for n in ("sum", "count", "skipped", "stride")]
+
+
+NSD_WHITEN_MAX_SWEEPS = 40
+NSD_WHITEN_FEW, NSD_WHITEN_NONFINITE, NSD_WHITEN_CLIPPED, NSD_WHITEN_NOT_CONVERGED = 1, 2, 4, 8
+
+
 class WsLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("hseq", "cseq", "gact", "inseq", "top", "alpha", "pooled", "fc0_pre",
                                           "dscore", "dpooled", "loss", "adpack", "slabs", "n_slabs", "hslabs", "da_seq", "din", "total")]
@@ -330,6 +350,13 @@ SYMBOLS = {
     "nsd_gate_reset": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
     "nsd_gate_step": (C.c_int, [_dp, _vp, _fp, _ip, _vp, C.c_int64, C.c_int32, _fp, _vp, _vp]),
     "nsd_gate_apply": (C.c_int, [_dp, _vp, _fp, _vp, _fp, _vp]),
+    # session alignment: channel covariance, whitening fit, spatial apply
+    "nsd_cov_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "nsd_cov_state_layout": (C.c_int, [C.c_int32, C.POINTER(CovLayout)]),
+    "nsd_cov_reset": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
+    "nsd_cov_step": (C.c_int, [_dp, _fp, _vp, _ip, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
+    "nsd_whiten_fit": (C.c_int, [C.c_int32, C.POINTER(Whiten), _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _fp, _vp, _vp]),
+    "nsd_spatial_apply": (C.c_int, [_dp, _fp, _fp, C.c_int32, _ip, _fp, _vp]),
 }
 NSD_MAX_MODELS = 32
 

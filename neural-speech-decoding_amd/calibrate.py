@@ -159,7 +159,7 @@ def _accuracy_and_loss(probs: np.ndarray, labels: np.ndarray):
     return acc, loss
 
 
-def calibrate_predictor(predictor, trials, labels, **fit_kw) -> dict:
+def calibrate_predictor(predictor, trials, labels, align: bool = True, **fit_kw) -> dict:
     """SimplePredictor.calibrate / EnsemblePredictor.calibrate: run `trials` ([N,T,C] numpy, or a list of [T,C]) through open_stream on
     reset slots, read the pooled features, fit the read-out(s) on (features, labels), and report loss and accuracy on the calibration
     trials before and after.  labels: class indices [N].  fit_kw: HeadFit's keywords.  Returns dict(n, epochs, loss_before, loss_after,
@@ -174,8 +174,22 @@ def calibrate_predictor(predictor, trials, labels, **fit_kw) -> dict:
     K = len(predictor.class_names)
     if y.min() < 0 or y.max() >= K:
         raise ValueError(f"calibrate: labels must be class indices in [0, {K})")
-    stream = predictor.open_stream(streams=N, chunk_transform=fit_kw.pop("chunk_transform", None))
-    before, _ = stream.push(x)
+    chunk_transform = fit_kw.pop("chunk_transform", None)
+    stream = predictor.open_stream(streams=N, chunk_transform=chunk_transform)
+    align_record = None
+    if align and getattr(predictor.model, "align", None) is not None:
+        # label-free, first: the session's matrix from the second moment of all calibration trials as the live stream delivers them,
+        # then a fresh decoder that starts from it -- features and the head fit run on aligned input
+        stream.decoder.align_accumulate(True)
+        before, _ = stream.push(x)
+        W, rec = ops.whiten_fit(predictor.model.spec.C, predictor.model.align, state=stream.decoder.cov_state)
+        align_record = ops.whiten_records(rec, 1)[0]
+        if not (align_record["few"] or align_record["nonfinite"]):
+            predictor.model.set_alignment(W[0], record=align_record)
+        stream = predictor.open_stream(streams=N, chunk_transform=chunk_transform)
+        stream.push(x)
+    else:
+        before, _ = stream.push(x)
     feats = stream.decoder.features()
     fit = HeadFit(predictor.model, **fit_kw)          # an EEG_LSTM, or the ensemble an EnsemblePredictor holds
     losses = fit.fit(feats, y)
@@ -185,7 +199,7 @@ def calibrate_predictor(predictor, trials, labels, **fit_kw) -> dict:
     acc0, loss0 = _accuracy_and_loss(before, y)
     acc1, loss1 = _accuracy_and_loss(after, y)
     return dict(n=N, epochs=fit.epochs_done(), loss_before=loss0, loss_after=loss1, acc_before=acc0, acc_after=acc1,
-                fit_losses=losses.cpu().numpy(), status=fit.status())
+                fit_losses=losses.cpu().numpy(), status=fit.status(), **({} if align_record is None else {"align": align_record}))
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -204,6 +218,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--train", default="ln,fc0,fc3", help="tensor groups to fit, of ln, fc0, fc3")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
     ap.add_argument("--head-dropout", type=float, default=None, help="train-mode noise of the head during the fit (default: eval-mode fit)")
+    ap.add_argument("--align", action="store_true", help="refit the session alignment of a checkpoint that carries one (nsd_align) from the "
+                    "calibration trials, label-free, before the read-out is fitted (without it the checkpoint's matrix stays)")
     ap.add_argument("--out", required=True, help="calibrated checkpoint; with several --model: <out stem>_m<i>.pth per member")
     return ap
 
@@ -248,7 +264,7 @@ def main(argv=None) -> int:
     acc0 = held_out_accuracy()
     loss = Loss(label_smoothing=args.label_smoothing) if args.label_smoothing else None
     rep = pred.calibrate(ts.x[cal], ts.y[cal], epochs=args.epochs, lr=args.lr, weight_decay=args.weight_decay,
-                         train=tuple(s for s in args.train.split(",") if s), head_dropout=args.head_dropout, loss=loss, seed=args.seed)
+                         train=tuple(s for s in args.train.split(",") if s), head_dropout=args.head_dropout, loss=loss, seed=args.seed, align=args.align)
     acc1 = held_out_accuracy()
     members = getattr(pred, "members", None) or [pred.model]
     stem, ext = os.path.splitext(args.out)

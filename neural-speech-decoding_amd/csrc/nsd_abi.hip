@@ -1862,4 +1862,102 @@ int nsd_gate_apply(const nsd_dims *d, const nsd_gate *g, const float *v, const u
     return nsd_gate_apply_launch(a, (hipStream_t)stream);
 }
 
+// ---- session alignment (nsd_cov_* / nsd_whiten_fit / nsd_spatial_apply, include/nsd.h; nsd_align.hip) ----
+// the preamble of the entry points that touch a cov state: channels, slot count, size
+static int cov_enter(int32_t C, const char *who, const void *state, int64_t state_bytes, int32_t S) {
+    if (!gate_channels(C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, C); return NSD_E_INVALID; }
+    if (!state) { nsd_set_error("%s: null state", who); return NSD_E_INVALID; }
+    if ((uintptr_t)state % 8) { nsd_set_error("%s: state is not 8-byte aligned (it holds doubles and int64 counts)", who); return NSD_E_INVALID; }
+    if (S < 1) { nsd_set_error("%s: S = %d slots", who, S); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)S * cov_stride(C) * (int64_t)sizeof(double);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_cov_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int64_t nsd_cov_state_bytes(int32_t C, int32_t S) {
+    if (!gate_channels(C) || S < 1) { nsd_set_error("cov_state_bytes: C outside [1, 32], or S < 1"); return NSD_E_INVALID; }
+    return (int64_t)S * cov_stride(C) * (int64_t)sizeof(double);
+}
+
+int nsd_cov_state_layout(int32_t C, nsd_cov_layout *out) {
+    if (!gate_channels(C) || !out) { nsd_set_error("cov_state_layout: C outside [1, 32], or null pointer"); return NSD_E_INVALID; }
+    out->sum = COV_SUM; out->count = cov_count(C); out->skipped = cov_skipped(C); out->stride = cov_stride(C);
+    return NSD_OK;
+}
+
+int nsd_cov_reset(int32_t C, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n, void *stream) {
+    static const char *who = "cov_reset";
+    if (const int rc = cov_enter(C, who, state, state_bytes, S)) return rc;
+    if (slots && (n < 0 || n > S)) { nsd_set_error("%s: n = %d slots of S = %d", who, n, S); return NSD_E_INVALID; }
+    const int count = slots ? n : S;
+    if (count == 0) return NSD_OK;
+    return nsd_cov_reset_launch((double *)state, C, S, slots, count, (hipStream_t)stream);
+}
+
+int nsd_cov_step(const nsd_dims *d, const float *v, const uint32_t *mask, const int32_t *slots, void *state, int64_t state_bytes,
+                 int32_t S, double *sums, int64_t *counts, void *stream) {
+    static const char *who = "cov_step";
+    if (!d || !v) { nsd_set_error("%s: null pointer (d, v)", who); return NSD_E_INVALID; }
+    if (!gate_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if (slots && !state) { nsd_set_error("%s: slots without a state (window mode takes neither)", who); return NSD_E_INVALID; }
+    if (state) {
+        if (sums || counts) { nsd_set_error("%s: sums / counts with a state (stream mode keeps them in the state)", who); return NSD_E_INVALID; }
+        if (const int rc = cov_enter(d->C, who, state, state_bytes, S)) return rc;
+        if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    } else if (!sums || !counts) {
+        nsd_set_error("%s: window mode needs sums and counts", who); return NSD_E_INVALID;
+    } else if ((uintptr_t)sums % 8 || (uintptr_t)counts % 8) {
+        nsd_set_error("%s: sums / counts are not 8-byte aligned", who); return NSD_E_INVALID;
+    }
+    if (d->B == 0) return NSD_OK;
+    CovArgs a;
+    memset(&a, 0, sizeof(a));
+    a.v = v; a.mask = mask; a.slots = slots; a.state = (double *)state; a.sums = sums; a.counts = (long long *)counts;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.S = state ? S : 0;
+    return nsd_cov_launch(a, (hipStream_t)stream);
+}
+
+int nsd_whiten_fit(int32_t C, const nsd_whiten *w, const double *sums, int64_t sum_stride, const int64_t *counts, int64_t count_stride,
+                   int32_t N, const int32_t *group, int32_t G, float *W, nsd_whiten_record *records, void *stream) {
+    static const char *who = "whiten_fit";
+    if (!w || !W || !records) { nsd_set_error("%s: null pointer (w, W, records)", who); return NSD_E_INVALID; }
+    if (!gate_channels(C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, C); return NSD_E_INVALID; }
+    if (N < 0 || G < 1) { nsd_set_error("%s: N = %d accumulators, G = %d groups (N >= 0, G >= 1)", who, N, G); return NSD_E_INVALID; }
+    if (N > 0 && (!sums || !counts)) { nsd_set_error("%s: null pointer (sums, counts)", who); return NSD_E_INVALID; }
+    if (N > 0 && ((uintptr_t)sums % 8 || (uintptr_t)counts % 8)) { nsd_set_error("%s: sums / counts are not 8-byte aligned", who); return NSD_E_INVALID; }
+    if ((uintptr_t)records % 16) { nsd_set_error("%s: records are not 16-byte aligned", who); return NSD_E_INVALID; }
+    if (sum_stride < (int64_t)C * C || count_stride < 2) {
+        nsd_set_error("%s: sum_stride = %lld (>= C*C), count_stride = %lld (>= 2)", who, (long long)sum_stride, (long long)count_stride);
+        return NSD_E_INVALID;
+    }
+    if (!(w->shrinkage >= 0.f && w->shrinkage <= 1.f)) { nsd_set_error("%s: shrinkage %g outside [0, 1]", who, w->shrinkage); return NSD_E_INVALID; }
+    if (!(w->floor > 0.f && w->floor <= 1.f)) { nsd_set_error("%s: floor %g outside (0, 1]", who, w->floor); return NSD_E_INVALID; }
+    if (w->min_steps < 1) { nsd_set_error("%s: min_steps = %d < 1", who, w->min_steps); return NSD_E_INVALID; }
+    WhitenArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sums = sums; a.counts = (const long long *)counts; a.sum_stride = sum_stride; a.count_stride = count_stride; a.group = group;
+    a.W = W; a.records = records; a.C = C; a.N = N; a.G = G; a.min_steps = w->min_steps;
+    a.shrinkage = (double)w->shrinkage; a.floor = (double)w->floor;
+    return nsd_whiten_launch(a, (hipStream_t)stream);
+}
+
+int nsd_spatial_apply(const nsd_dims *d, const float *v, const float *W, int32_t n_mat, const int32_t *sel, float *out, void *stream) {
+    static const char *who = "spatial_apply";
+    if (!d || !v || !W || !out) { nsd_set_error("%s: null pointer (d, v, W, out)", who); return NSD_E_INVALID; }
+    if (!gate_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if (n_mat < 1) { nsd_set_error("%s: n_mat = %d matrices", who, n_mat); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (v != out && v < out + n && out < v + n) { nsd_set_error("%s: out overlaps v partially (in place means out == v)", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    SpatialArgs a;
+    memset(&a, 0, sizeof(a));
+    a.v = v; a.W = W; a.sel = sel; a.out = out; a.B = d->B; a.T = d->T; a.C = d->C; a.n_mat = n_mat;
+    return nsd_spatial_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -393,3 +393,32 @@ struct GateApplyArgs {
     int C, max_bad, zero;
 };
 int nsd_gate_apply_launch(const GateApplyArgs &a, hipStream_t st);
+
+// session alignment (nsd_cov_* / nsd_whiten_fit / nsd_spatial_apply of nsd.h; nsd_align.hip).  One slot of a cov state in 8-byte words --
+// the public layout nsd_cov_state_layout reports: sum[C][C] double, then count and skipped (int64)
+constexpr int COV_SUM = 0;
+__host__ __device__ constexpr int cov_count(int C) { return C * C; }
+__host__ __device__ constexpr int cov_skipped(int C) { return C * C + 1; }
+__host__ __device__ constexpr int cov_stride(int C) { return C * C + 2; }
+struct CovArgs {
+    const float *v; const uint32_t *mask;    // [B,T,C]; null, or [B,T]
+    const int32_t *slots;                    // null: stream b lives in slot b
+    double *state;                           // null: window mode (every trial from zero, results to sums / counts)
+    double *sums; long long *counts;         // window mode: [B][C][C], [B][2]
+    int B, T, C, S;
+};
+int nsd_cov_launch(const CovArgs &a, hipStream_t st);
+int nsd_cov_reset_launch(double *state, int C, int S, const int32_t *slots, int n, hipStream_t st);
+struct WhitenArgs {
+    const double *sums; const long long *counts; long sum_stride, count_stride;
+    const int32_t *group;                    // null: every accumulator in group 0
+    float *W; nsd_whiten_record *records;    // [G][C][C], [G]
+    int C, N, G, min_steps;
+    double shrinkage, floor;
+};
+int nsd_whiten_launch(const WhitenArgs &a, hipStream_t st);
+struct SpatialArgs {
+    const float *v; const float *W; const int32_t *sel; float *out;   // v, out [B,T,C] (out == v allowed), W [n_mat][C][C], sel null or [B]
+    int B, T, C, n_mat;
+};
+int nsd_spatial_launch(const SpatialArgs &a, hipStream_t st);

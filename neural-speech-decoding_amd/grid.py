@@ -118,7 +118,7 @@ def main(argv=None) -> int:
     from .ops import Augment, Crop, Loss
     from .prep import CausalPrep
     from .train import (average_for, concurrent_epoch, concurrent_runs, crop_for, drop_bad_trials, early_stop_settings, evaluate, evaluate_cropped,
-                        gate_for, loss_for,
+                        align_for, fit_alignment, gate_for, loss_for,
                         padded_parts, parse_class_weights, sam_for, schedule_for, selection_text)
 
     ap = build_parser()
@@ -163,6 +163,12 @@ def main(argv=None) -> int:
         ap.error(str(e))
     if gate is not None and args.normalize:
         ap.error("--gate-* with --normalize: the whole-window z-score would be taken over held and zeroed channels")
+    try:
+        align = align_for(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if align is not None and args.normalize:
+        ap.error("--align with --normalize: the whole-window z-score would undo the whitening channel by channel")
 
     # every configuration as the options `train` would see, checked before anything runs
     cfg_args, augments = [], []
@@ -237,7 +243,7 @@ def main(argv=None) -> int:
         models = []
         for c, k in members:
             torch.manual_seed(runs[k]["seed"])
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, cfg_args[c].dropout, normalize=args.normalize, prep=prep_all, crop=crop_train, gate=gate).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, cfg_args[c].dropout, normalize=args.normalize, prep=prep_all, crop=crop_train, gate=gate, align=align).to(dev).train())
         per = lambda f: [f(c, k) for c, k in members]                                         # noqa: E731
         mbt = ModelBatchTrainer(
             models, lr=per(lambda c, k: cfg_args[c].lr), weight_decay=per(lambda c, k: cfg_args[c].weight_decay),
@@ -246,6 +252,8 @@ def main(argv=None) -> int:
             clip_grad_norm=per(lambda c, k: cfg_args[c].clip_grad_norm), lr_schedule=schedule_for(args, args.epochs * steps_per_epoch),
             average=per(lambda c, k: average_for(cfg_args[c], steps_per_epoch)), sam=per(lambda c, k: sam_for(cfg_args[c])),
             crop=crop_train)
+        if align is not None:            # every member's matrix from its own fold's training part (label-free; not a grid axis)
+            mbt.set_alignment(torch.stack([fit_alignment(mdl, x_all[tr_devs[k]], f"grid fold {k}")[0] for (_, k), mdl in zip(members, models)]))
         opt_on, avg_on, inner, es_epoch0 = mbt._opt_on, args.avg is not None, None, 0
         avg_start = average_for(cfg_args[0], steps_per_epoch).start_step if avg_on else 0      # (kind, start and stride are shared)
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in members]

@@ -24,6 +24,7 @@ import torch.nn as nn
 from . import ops, step_recipe as sr
 from ._lib import NsdError
 from .gate import SignalGate
+from .align import SessionAlign
 from .prep import CausalPrep
 
 CLASS_NAMES = ["Food", "Water", "BG-Noise"]   # verbatim from lstm_eeg_model.py:11
@@ -189,6 +190,10 @@ class EEG_LSTM(nn.Module):
                      window mode, nsd_gate_apply): a bad channel is held through the front end and zeroed in front of the LSTM; in
                      eval mode a trial with a rejected step has NaN logits ("no decision"), in train mode nothing is rejected.
                      Not together with normalize; no input gradient is offered through it.
+      align          a SessionAlign: session alignment behind the front end (gate -> prep -> apply -> align -> LSTM; nsd_spatial_apply):
+                     every step is multiplied by the model's alignment matrix, a non-persistent buffer `align_matrix` [C,C] that is the
+                     identity until set (align_matrix=, set_alignment(), SessionAlign.fit).  Not together with normalize; no input
+                     gradient is offered through it.
       crop           an ops.Crop: the window the model was (or is being) trained on by cropped training (Trainer(crop=)).  It changes
                      nothing in forward(); it travels with the model and its checkpoints so that predict_trials(), SimplePredictor and
                      open_stream() know the trained window.
@@ -196,8 +201,23 @@ class EEG_LSTM(nn.Module):
 
     def __init__(self, input_size=8, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, *,
                  residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32",
-                 prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None, gate: Optional[SignalGate] = None):
+                 prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None, gate: Optional[SignalGate] = None,
+                 align: Optional[SessionAlign] = None, align_matrix=None):
         super().__init__()
+        if align is not None and not isinstance(align, SessionAlign):
+            raise ValueError(f"align={align!r}: expected a SessionAlign")
+        if align is not None and normalize:
+            raise ValueError("align together with normalize=True: the whole-window z-score would undo the whitening channel by channel "
+                             "(CausalPrep.design(zscore_seconds=...) is its running form in front of the alignment)")
+        if align is not None and not 1 <= input_size <= 32:
+            raise ValueError(f"align: session alignment covers 1 .. 32 channels, input_size = {input_size}")
+        if align is None and align_matrix is not None:
+            raise ValueError("align_matrix without align=SessionAlign(...)")
+        self.align, self.align_record = align, None         # (the record of the fit the matrix came from, where it came from one)
+        if align is not None:
+            self.register_buffer("align_matrix", torch.eye(input_size, dtype=torch.float32), persistent=False)
+            if align_matrix is not None:
+                self.set_alignment(align_matrix)
         if gate is not None and not isinstance(gate, SignalGate):
             raise ValueError(f"gate={gate!r}: expected a SignalGate")
         if gate is not None and normalize:
@@ -281,7 +301,9 @@ class EEG_LSTM(nn.Module):
         if row.dtype != torch.float32 or row.dim() != 1 or row.numel() != sp.param_count or not row.is_contiguous():
             raise NsdError(f"EEG_LSTM.view_of: row must be a contiguous float32 vector of {sp.param_count} elements")
         twin = EEG_LSTM(sp.C, sp.H, sp.L, sp.K, self.head_dropout_p, residual=self.residual, normalize=self.normalize,
-                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop, gate=self.gate)
+                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop, gate=self.gate, align=self.align)
+        if self.align is not None:
+            twin.align_matrix, twin.align_record = self.align_matrix, self.align_record   # (shared: the twin follows a later set_alignment)
         offs = sp.offsets()
         with torch.no_grad():
             for n, p in twin._named_in_order():
@@ -295,6 +317,18 @@ class EEG_LSTM(nn.Module):
         self._flat = None        # .to()/.cuda() re-created the storages
         return out
 
+    def set_alignment(self, W, record: Optional[dict] = None) -> None:
+        """Write the alignment matrix [C,C] (a tensor on any device, or an array) into the model's buffer, in place.  record: the
+        nsd_whiten_fit record it came with (ops.whiten_records); it travels in the model's checkpoints."""
+        if self.align is None:
+            raise NsdError("EEG_LSTM.set_alignment: the model was built without align=SessionAlign(...)")
+        W = torch.as_tensor(W, dtype=torch.float32)
+        if tuple(W.shape) != tuple(self.align_matrix.shape):
+            raise ValueError(f"set_alignment: expected a {list(self.align_matrix.shape)} matrix, got {tuple(W.shape)}")
+        with torch.no_grad():
+            self.align_matrix.copy_(W)
+        self.align_record = None if record is None else dict(record)
+
     # ---- forward --------------------------------------------------------------------------------------
     def _front_end(self, x: torch.Tensor) -> torch.Tensor:
         """What stands between the caller's window and the LSTM: the z-score (normalize), the signal-quality gate around the causal
@@ -306,12 +340,16 @@ class EEG_LSTM(nn.Module):
             if x.requires_grad and torch.is_grad_enabled():
                 raise NsdError("EEG_LSTM(prep=...): dx through the causal front end is not offered -- x.requires_grad would get no "
                                "gradient; detach x, or differentiate a prep-free model on ops.prep_step(x, prep)")
-        if self.gate is not None or self.prep is not None:
-            return self._gate_prep(x)
+        if self.align is not None and x.requires_grad and torch.is_grad_enabled():
+            raise NsdError("EEG_LSTM(align=...): dx through the session alignment is not offered -- x.requires_grad would get no "
+                           "gradient; detach x, or differentiate an align-free model on ops.spatial_apply(x, W)")
+        if self.gate is not None or self.prep is not None or self.align is not None:
+            return self._front(x)
         return ops.zscore(x) if self.normalize else x
 
-    def _gate_prep(self, x: torch.Tensor) -> torch.Tensor:
-        """gate -> prep -> apply over whole windows, each stage where the model has it.  Train mode never rejects a step."""
+    def _gate_prep(self, x: torch.Tensor, want_mask: bool = False):
+        """gate -> prep -> apply over whole windows, each stage where the model has it.  Train mode never rejects a step.
+        want_mask: -> (x, the gate's mask words or None)."""
         mask = None
         if self.gate is not None:
             x, mask = ops.gate_step(x, self.gate)
@@ -319,7 +357,14 @@ class EEG_LSTM(nn.Module):
             x = ops.prep_step(x, self.prep, out=x if mask is not None else None)
         if mask is not None:
             x = ops.gate_apply(x, self.gate, mask, out=x, max_bad=self.spec.C if self.training else None)
-        return x
+        return (x, mask) if want_mask else x
+
+    def _front(self, x: torch.Tensor) -> torch.Tensor:
+        """gate -> prep -> apply -> align over whole windows: what stands in front of the (crop and the) LSTM."""
+        y = self._gate_prep(x)
+        if self.align is not None:
+            y = ops.spatial_apply(y, self.align_matrix, out=y if y is not x else None)   # (in place in a buffer of this call's own)
+        return y
 
     def _train_masks(self, B: int, T: int, device):
         if self._mask_override is not None:
@@ -412,7 +457,7 @@ class EEG_LSTM(nn.Module):
             raise ValueError(f"Expected x of shape [B, T, {self.spec.C}], got {tuple(x.shape)}")
         B, T, _ = x.shape
         grid = ops.Crop.grid(T, int(window), hop)
-        x = self._gate_prep(x)
+        x = self._front(x)
         xc, _, _ = ops.crop(x, grid)
         if self.normalize:
             ops.zscore(xc, out=xc)
@@ -517,7 +562,7 @@ class SimplePredictor:
                  normalize: bool = False, bidirectional: bool = False, precision: str = "fp32"):
         """A checkpoint written from a model with a causal front end carries it ({"state_dict": ..., "nsd_prep": CausalPrep.to_dict()},
         trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep.  A signal-quality gate travels the same way
-        ("nsd_gate": SignalGate.to_dict()).  One written from a model trained on
+        ("nsd_gate": SignalGate.to_dict()), session alignment as "nsd_align": {config, matrix, record}.  One written from a model trained on
         crops carries "nsd_crop" = {window, crops, hop} beside it: the model is rebuilt with that ops.Crop (predict_trial, open_stream)."""
         self.device = torch.device(device)
         self.sr = sr
@@ -535,15 +580,19 @@ class SimplePredictor:
                            "no CPU fallback")
         self.gpu = torch.device(gpu)
         state = torch.load(pth_path, map_location="cpu", weights_only=True)
-        prep = crop = gate = None
+        prep = crop = gate = align = align_state = None
         if isinstance(state, dict) and "state_dict" in state:     # both forms, as lstm_eeg_model.py:79-80
+            align_state = state.get("nsd_align")
+            align = SessionAlign.from_dict(align_state["config"]) if align_state is not None else None
             prep = CausalPrep.from_dict(state["nsd_prep"]) if state.get("nsd_prep") is not None else None
             crop = ops.Crop(**{k: int(v) for k, v in state["nsd_crop"].items()}) if state.get("nsd_crop") is not None else None
             gate = SignalGate.from_dict(state["nsd_gate"]) if state.get("nsd_gate") is not None else None
             state = state["state_dict"]
         self.model = EEG_LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
                               num_classes=num_classes, dropout=dropout, residual=residual, normalize=normalize,
-                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop, gate=gate)
+                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop, gate=gate, align=align)
+        if align_state is not None:
+            self.model.set_alignment(align_state["matrix"], record=align_state.get("record"))
         self.model.load_state_dict(state, strict=True)
         self.model.to(self.gpu).eval()
         self.model.flatten_parameters()
@@ -626,13 +675,16 @@ class SimplePredictor:
             return PredictorSlidingStream(self, streams, chunk_transform, int(round(window_seconds * self.sr)), int(round(hop_seconds * self.sr)))
         return PredictorStream(self, streams, chunk_transform)
 
-    def calibrate(self, trials, labels, **fit_kw) -> dict:
+    def calibrate(self, trials, labels, align: bool = True, **fit_kw) -> dict:
         """Session calibration (an extension, see calibrate.py): refit the read-out (LayerNorm, fc.0, fc.3; the LSTM stack and the
         attention stay frozen) on a few cued trials of a new session.  trials [N,T,C] (N <= 256), labels [N] class indices.  The
         trials run through open_stream on reset slots -- preprocessing and a causal front end are exactly what the live stream
         applies -- their pooled features are read and the read-out is fitted by nsd_amd.HeadFit(**fit_kw) in one launch (of an
         EnsemblePredictor: all members together, each on its own features).  chunk_transform=: as open_stream's.  The model is updated
         in place: a decoder that is open keeps its state, and its next read-out uses the fitted head.  Returns a dict with loss and
-        accuracy on the calibration trials before and after, the fit's loss curve and its status."""
+        accuracy on the calibration trials before and after, the fit's loss curve and its status.
+        align (a model with session alignment only): the alignment matrix is refitted from the calibration trials first -- label-free,
+        one nsd_whiten_fit over the accumulators of all trials -- and features and the head fit then run on aligned input; decoders
+        opened afterwards start from the new matrix.  A fit that kept the identity (too few steps) leaves the matrix as it was."""
         from .calibrate import calibrate_predictor
-        return calibrate_predictor(self, trials, labels, **fit_kw)
+        return calibrate_predictor(self, trials, labels, align=align, **fit_kw)

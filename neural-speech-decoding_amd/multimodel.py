@@ -27,7 +27,8 @@ def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
         raise NsdError(f"{what}: the same module is passed more than once (each model needs its own parameters)")
     for i, mdl in enumerate(models):
         if (mdl.spec != sp or mdl.residual != models[0].residual or mdl.precision != models[0].precision
-                or mdl.normalize != models[0].normalize or mdl.prep != models[0].prep or mdl.gate != models[0].gate):
+                or mdl.normalize != models[0].normalize or mdl.prep != models[0].prep or mdl.gate != models[0].gate
+                or getattr(mdl, "align", None) != getattr(models[0], "align", None)):
             raise NsdError(f"{what}: model {i} has another shape / options than model 0 (mixed shapes: one launch runs one shape)")
     if models[0].residual or models[0].precision != "fp32" or sp.D != 1:
         raise NsdError(f"{what}: the model-batched path runs the plain fp32 stack (no residual extension, no bf16)")
@@ -187,6 +188,11 @@ class ModelBatchTrainer:
                              avg=self.average if self._avg_on else None, avg_state=self._avg_state, **self.recipe.sam_args(self._sam_state))
         self._last = (B, T)
 
+    def set_alignment(self, W) -> None:
+        """The M alignment matrices [M,C,C] of models built with align=SessionAlign(...) (SessionAlign.fit(model, trials, groups) forms
+        them, one group per fold): written into the step's table and each model's buffer."""
+        self.recipe.set_alignment(W)
+
     # ---- device-resident batches --------------------------------------------------------------------------------------------------
     def bind_batches(self, trials, schedule) -> None:
         """Keep the trials (a data.DeviceTrialSet with labels) and the M models' index schedule (a data.BatchSchedule, e.g.
@@ -309,7 +315,9 @@ class ModelBatchTrainer:
             raise NsdError(f"ModelBatchTrainer.{who}: y must be [M,B] = [{M},{B}] or [B], got {tuple(y.shape)}")
         x = x.contiguous().float()
         if self.models[0].prep is not None or self.models[0].gate is not None:
-            x = self.models[0]._gate_prep(x)
+            x = self.recipe.align_apply(self.models[0]._gate_prep(x), fresh=True)
+        elif self.recipe.align is not None:
+            x = self.recipe.align_apply(x, fresh=False)
         elif self.models[0].normalize and crop is None:
             x = ops.zscore(x.reshape(-1, T, Cc)).view(x.shape)
         if crop is None:
@@ -421,7 +429,20 @@ class _EnsembleModel:
         self.models = list(models)
         self.spec, self.precision, self.normalize, self.prep = models[0].spec, "fp32", models[0].normalize, models[0].prep
         self.gate = models[0].gate
+        self.align = getattr(models[0], "align", None)      # (the front end is shared: member 0's matrix is the ensemble's)
         self.params = torch.stack([m.flat_parameters() for m in self.models]).contiguous()
+
+    @property
+    def align_matrix(self):
+        return self.models[0].align_matrix
+
+    @property
+    def align_record(self):
+        return self.models[0].align_record
+
+    def set_alignment(self, W, record=None) -> None:
+        for m in self.models:
+            m.set_alignment(W, record=record)
 
     def predict_proba(self, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous().float()

@@ -2200,3 +2200,157 @@ def gate_quality(C_: int, state: torch.Tensor, slots=None) -> dict:
     steps = words[:, int(C_) + 1].copy()
     n = np.maximum(steps, 1).astype(np.float64)
     return {"bad_fraction": words[:, :int(C_)] / n[:, None], "rejected_fraction": words[:, int(C_)] / n, "steps": steps}
+
+
+# ---- session alignment: channel covariance, whitening fit, spatial apply (nsd_cov_* / nsd_whiten_fit / nsd_spatial_apply of
+# include/nsd.h; the configuration: align.SessionAlign) ----
+
+def _dev_typed(t: Optional[torch.Tensor], name: str, dtype, numel: Optional[int] = None) -> Optional[int]:
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (numel is not None and int(t.numel()) != int(numel)):
+        raise NsdError(f"{name}: expected a contiguous {dtype} tensor{'' if numel is None else f' of {numel} elements'} on the device, "
+                       f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.data_ptr()
+
+
+def cov_layout(C_: int) -> "_lib.CovLayout":
+    """Offsets, in 8-byte words, of sum[C][C] (double), count and skipped (int64) inside one slot of a cov state, and the slot stride."""
+    lay = _lib.CovLayout()
+    check(_lib.lib().nsd_cov_state_layout(int(C_), C.byref(lay)), "nsd_cov_state_layout")
+    return lay
+
+
+def cov_state(C_: int, S: int, device="cuda") -> torch.Tensor:
+    """A reset cov state of S slots on `device`: [S, C*C + 2] 8-byte words carried as float64 (the two counts are bit patterns: read
+    them through .view(torch.int64), or with cov_counts)."""
+    state = torch.empty((int(S), int(cov_layout(C_).stride)), dtype=torch.float64, device=device)
+    cov_reset(C_, state)
+    return state
+
+
+def cov_reset(C_: int, state: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """Reset all slots of `state`, or the ones a device int32 tensor names: everything zero."""
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    n = 0 if slots is None else int(slots.numel())
+    if slots is not None and n == 0:
+        return
+    _call("nsd_cov_reset", state.device, int(C_), _dev_typed(state, "cov_reset: state", torch.float64), _nbytes(state), S,
+          _slots_ptr(slots, "cov_reset"), n, STREAM)
+
+
+def cov_step(v: torch.Tensor, state: Optional[torch.Tensor] = None, *, mask: Optional[torch.Tensor] = None,
+             slots: Optional[torch.Tensor] = None, out=None):
+    """nsd_cov_step on v [B,n,C] (or [M,B,n,C]: M*B trials), with the gate's mask int32 [B,n] where given.  state=None: window mode ->
+    (sums float64 [B,C,C], counts int64 [B,2]: {used, skipped}) from zero for every trial (out: the two caller-owned buffers).
+    state [S, C*C+2]: stream mode, stream b adds the chunk to slot slots[b] (or b); returns the state."""
+    if v.dim() not in (3, 4):
+        raise NsdError(f"cov_step: v must be [B,n,C] or [M,B,n,C], got {tuple(v.shape)}")
+    T, Cc = int(v.shape[-2]), int(v.shape[-1])
+    B = int(v.numel()) // max(T * Cc, 1)
+    if state is None and slots is not None:
+        raise NsdError("cov_step: slots without a state")
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"cov_step: {int(slots.numel())} slot indices for {B} streams")
+    if state is not None and out is not None:
+        raise NsdError("cov_step: out with a state (stream mode keeps the sums in the state)")
+    sums = counts = None
+    if state is None:
+        if out is None:
+            out = (torch.empty((B, Cc, Cc), dtype=torch.float64, device=v.device), torch.empty((B, 2), dtype=torch.int64, device=v.device))
+        sums, counts = out
+    if B > 0:
+        S = 0 if state is None else (int(state.shape[0]) if state.dim() == 2 else 0)
+        d = Dims(B, T, Cc, 1, 1, 1, 1)
+        _call("nsd_cov_step", v.device, C.byref(d), _dev_f32(v, "v"), None if mask is None else _mask_ptr(mask, "cov_step", B * T),
+              _slots_ptr(slots, "cov_step"), _dev_typed(state, "cov_step: state", torch.float64), 0 if state is None else _nbytes(state), S,
+              _dev_typed(sums, "cov_step: sums", torch.float64, B * Cc * Cc), _dev_typed(counts, "cov_step: counts", torch.int64, B * 2), STREAM)
+    return state if state is not None else (sums, counts)
+
+
+def cov_counts(C_: int, state: torch.Tensor, slots=None):
+    """{used, skipped} of a cov state's slots (all, or the listed ones) as int64 numpy [n,2], in one copy."""
+    lay = cov_layout(C_)
+    rows = state if slots is None else state[torch.as_tensor(list(slots), dtype=torch.long, device=state.device)]
+    return rows[:, int(lay.count):int(lay.count) + 2].contiguous().view(torch.int64).cpu().numpy()
+
+
+WHITEN_RECORD_BYTES = C.sizeof(_lib.WhitenRecord)
+WHITEN_STATUS = {"few": _lib.NSD_WHITEN_FEW, "nonfinite": _lib.NSD_WHITEN_NONFINITE, "clipped": _lib.NSD_WHITEN_CLIPPED,
+                 "not_converged": _lib.NSD_WHITEN_NOT_CONVERGED}
+
+
+def whiten_fit(C_: int, align, sums: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, *,
+               state: Optional[torch.Tensor] = None, group: Optional[torch.Tensor] = None, G: int = 1,
+               out: Optional[torch.Tensor] = None, records: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """nsd_whiten_fit with the SessionAlign `align`: one matrix per group from N accumulators -> (W float32 [G,C,C], records: a uint8
+    buffer of G nsd_whiten_record, read with whiten_records).  The accumulators are window-mode outputs (sums float64 [N,C,C], counts
+    int64 [N,2]) or a cov state [N, C*C+2] read in place (state=).  group: device int32 [N] (None: all in group 0).  Nothing is read
+    back: the call can be captured (out, records: caller-owned buffers)."""
+    Cc, G = int(C_), int(G)
+    if (state is None) == (sums is None) or (sums is None) != (counts is None):
+        raise NsdError("whiten_fit: give either sums and counts, or state")
+    if state is not None:
+        lay = cov_layout(Cc)
+        if state.dim() != 2 or int(state.shape[1]) != int(lay.stride):
+            raise NsdError(f"whiten_fit: state must be [N, {int(lay.stride)}], got {tuple(state.shape)}")
+        N, dev = int(state.shape[0]), state.device
+        base = _dev_typed(state, "whiten_fit: state", torch.float64)
+        sp, ss, cp, cs = base, int(lay.stride), (None if base is None else base + 8 * int(lay.count)), int(lay.stride)
+    else:
+        N, dev = int(counts.numel()) // 2, sums.device
+        sp, ss = _dev_typed(sums, "whiten_fit: sums", torch.float64, N * Cc * Cc), Cc * Cc
+        cp, cs = _dev_typed(counts, "whiten_fit: counts", torch.int64, N * 2), 2
+    if N == 0:
+        sp = cp = None
+    if group is not None and (group.dtype != torch.int32 or not group.is_cuda or not group.is_contiguous() or int(group.numel()) != N):
+        raise NsdError(f"whiten_fit: group must be a contiguous int32 tensor of {N} indices on the device")
+    if out is None:
+        out = torch.empty((G, Cc, Cc), dtype=torch.float32, device=dev)
+    if records is None:
+        records = torch.empty(max(G, 1) * C.sizeof(_lib.WhitenRecord), dtype=torch.uint8, device=dev)
+    if int(out.numel()) != G * Cc * Cc or records.dtype != torch.uint8 or int(records.numel()) < G * C.sizeof(_lib.WhitenRecord) \
+            or not records.is_cuda or not records.is_contiguous():
+        raise NsdError(f"whiten_fit: out must hold [{G},{Cc},{Cc}] float32 and records {G * C.sizeof(_lib.WhitenRecord)} bytes (uint8) on the device")
+    w = align.struct(Cc)
+    _call("nsd_whiten_fit", dev, Cc, C.byref(w), sp, ss, cp, cs, N, None if group is None or N == 0 else group.data_ptr(), G,
+          _dev_f32(out, "whiten_fit: out"), records.data_ptr(), STREAM)
+    return out, records
+
+
+def whiten_records(records: torch.Tensor, G: int) -> List[dict]:
+    """The G records whiten_fit wrote: [{steps, skipped, trace_mean, eig_min, eig_max, sweeps, status, accumulators, ignored, and one
+    bool per status bit: few, nonfinite, clipped, not_converged}] (one copy; synchronises)."""
+    recs = []
+    for r in _records(records, G, _lib.WhitenRecord, "whiten_records"):
+        d = dict(steps=int(r.steps), skipped=int(r.skipped), trace_mean=float(r.trace_mean), eig_min=float(r.eig_min),
+                 eig_max=float(r.eig_max), sweeps=int(r.sweeps), status=int(r.status), accumulators=int(r.accumulators),
+                 ignored=int(r.ignored))
+        d.update({name: bool(d["status"] & bit) for name, bit in WHITEN_STATUS.items()})
+        recs.append(d)
+    return recs
+
+
+def spatial_apply(v: torch.Tensor, W: torch.Tensor, *, sel: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nsd_spatial_apply on v [B,n,C] (or [M,B,n,C]: M*B rows): out[b,t,:] = W[sel[b]] . v[b,t,:], the sum over the input channel taken
+    serially in fp32.  W [C,C] or [n_mat,C,C]; sel: device int32 [B] (None: matrix 0 for every row; an entry outside the table gives
+    NaN rows).  out is v: in place."""
+    if v.dim() not in (3, 4):
+        raise NsdError(f"spatial_apply: v must be [B,n,C] or [M,B,n,C], got {tuple(v.shape)}")
+    T, Cc = int(v.shape[-2]), int(v.shape[-1])
+    B = int(v.numel()) // max(T * Cc, 1)
+    if W.dim() not in (2, 3) or tuple(W.shape[-2:]) != (Cc, Cc):
+        raise NsdError(f"spatial_apply: W must be [{Cc},{Cc}] or [n_mat,{Cc},{Cc}], got {tuple(W.shape)}")
+    n_mat = 1 if W.dim() == 2 else int(W.shape[0])
+    if sel is not None and (sel.dtype != torch.int32 or not sel.is_cuda or not sel.is_contiguous() or int(sel.numel()) != B):
+        raise NsdError(f"spatial_apply: sel must be a contiguous int32 tensor of {B} indices on the device")
+    if out is None:
+        out = torch.empty_like(v)
+    if out.numel() != v.numel():
+        raise NsdError(f"spatial_apply: out has {out.numel()} elements for {tuple(v.shape)}")
+    if B == 0:
+        return out
+    d = Dims(B, T, Cc, 1, 1, 1, 1)
+    _call("nsd_spatial_apply", v.device, C.byref(d), _dev_f32(v, "v"), _dev_f32(W, "W"), n_mat, None if sel is None else sel.data_ptr(),
+          _dev_f32(out, "out"), STREAM)
+    return out

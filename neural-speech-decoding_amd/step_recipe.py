@@ -65,11 +65,21 @@ class StepRecipe:
 
     A model with a signal-quality gate (EEG_LSTM(gate=...)) adds its two stages around the front end, in window mode: gather -> augment
     -> gate -> prep -> apply -> crop -> mixup.  The apply stage of a training step never rejects (max_bad = C), so the loss stays finite;
-    bad trials are dropped at the data-set level (data.screen_trials)."""
+    bad trials are dropped at the data-set level (data.screen_trials).
+
+    A model with session alignment (EEG_LSTM(align=...)) adds the stage behind the front end and in front of the crop: gather ->
+    augment -> gate -> prep -> apply -> align -> crop -> mixup.  One nsd_spatial_apply, in place in the buffer the front end wrote (or
+    into bufs["xn"]); it draws nothing and moves no stream.  One model uses its own matrix (sel = NULL); with models= the recipe holds
+    one matrix per model ([M,C,C], a copy of the models' at construction: set_alignment() writes both) and a static int32 selection
+    [M*B], model m's rows naming matrix m."""
 
     def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None, crop=None):
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
         self.gate = getattr(model, "gate", None)
+        self.align = getattr(model, "align", None)
+        self.align_W, self._align_models, self._align_sel = None, models, {}
+        if self.align is not None:
+            self.align_W = model.align_matrix if models is None else torch.stack([m.align_matrix for m in models]).contiguous()
         self.p_lstm, self.p_head = model.dropout_p, model.head_dropout_p
         self.probs = [(m.dropout_p, m.head_dropout_p) for m in models] if models is not None else None
         M = len(models) if models is not None else 1
@@ -221,10 +231,40 @@ class StepRecipe:
             raise ops.NsdError(f"{who}: the batch schedule of model(s) {bad} named a trial outside the resident set of "
                                f"{len(bound['trials'])}: those rows were NaN and their steps skipped or spoilt.  Results are invalid")
 
+    def set_alignment(self, W) -> None:
+        """Write the alignment matrices ([C,C] for one model, [M,C,C] with models=) into the recipe's table and the models' buffers, in
+        place: a captured step reads the new matrices at its next replay."""
+        if self.align is None:
+            raise ops.NsdError("StepRecipe.set_alignment: the model was built without align=SessionAlign(...)")
+        W = torch.as_tensor(W, dtype=torch.float32)
+        if tuple(W.shape) != tuple(self.align_W.shape):
+            raise ValueError(f"set_alignment: expected matrices of shape {tuple(self.align_W.shape)}, got {tuple(W.shape)}")
+        with torch.no_grad():
+            self.align_W.copy_(W)
+            for m, mdl in enumerate(self._align_models or ()):
+                mdl.align_matrix.copy_(self.align_W[m])
+
+    def align_apply(self, x: torch.Tensor, *, fresh: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The align stage on x [B,T,C] or [M,B,T,C] (no-op without align): in place where x is a buffer of this step's own (fresh),
+        else into out (or a new buffer).  With one matrix per model a shared [B,T,C] becomes [M,B,T,C]."""
+        if self.align is None:
+            return x
+        W = self.align_W
+        if W.dim() == 2:
+            return ops.spatial_apply(x, W, out=x if fresh else out)
+        M, B = int(W.shape[0]), int(x.shape[-3])
+        if x.dim() == 3:
+            x, fresh = x.unsqueeze(0).expand(M, *x.shape).contiguous(), True
+        key = (B, x.device)
+        if key not in self._align_sel:
+            self._align_sel[key] = torch.arange(M, dtype=torch.int32, device=x.device).repeat_interleave(B).contiguous()
+        return ops.spatial_apply(x, W, sel=self._align_sel[key], out=x if fresh else out)
+
     def static_buffers(self, x: torch.Tensor) -> dict:
         """The outputs of prepare() for the static windows x [B,T,C] of a hipGraph step: nothing is allocated inside a capture."""
         buf = {}
-        if self.augment is not None or self.prep is not None or self.gate is not None or (self.normalize and self.crop is None):
+        if (self.augment is not None or self.prep is not None or self.gate is not None or self.align is not None
+                or (self.normalize and self.crop is None)):
             buf["xn"] = torch.empty_like(x)
         if self.gate is not None:                    # the mask words of the signal-quality gate, one per (trial, step)
             buf["gm"] = torch.empty(tuple(x.shape[:-1]), dtype=torch.int32, device=x.device)
@@ -267,6 +307,8 @@ class StepRecipe:
             x = ops.prep_step(x, self.prep, out=x if (self.augment is not None or mask is not None) else bufs.get("xn"))
         if mask is not None:               # a bad channel is zeroed; inside a training step nothing is rejected (the loss stays finite)
             x = ops.gate_apply(x, self.gate, mask, out=x, max_bad=int(Cc))
+        if self.align is not None:         # ... -> apply -> align -> crop: in place in the buffer the front end wrote, or into xn
+            x = self.align_apply(x, fresh=self.augment is not None or mask is not None or self.prep is not None, out=bufs.get("xn"))
         if self.crop is not None:          # ... -> prep -> crop -> mixup: the step's dimensions become (B * R, W) here
             self.crop.check_trial(T)
             soft = y.is_floating_point()

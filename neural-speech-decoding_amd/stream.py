@@ -62,6 +62,13 @@ class StreamDecoder:
     A model with a signal-quality gate (EEG_LSTM(gate=...)) adds a gate state of the same slots: push runs nsd_gate_step -> (nsd_prep_step)
     -> nsd_gate_apply -> the step; a rejected step is NaN, so this decoder and the ensemble one read NaN until the slot is reset, while the
     sliding decoders lose exactly the windows that contain it.  quality(slots=None) reports what the gate has seen.
+    A model with session alignment (EEG_LSTM(align=...)) adds a table of one matrix per slot, each the model's matrix at first, and a
+    second-moment accumulator per slot: push ends its front end with nsd_spatial_apply (sel = the slots), and
+      align_accumulate(on)                   nsd_cov_step inside push, behind the gate's apply and in front of the spatial apply
+      refit_alignment(slots=None)            one nsd_whiten_fit from the accumulators into those slots' matrices; nothing is read back
+      alignment(slots=None)                  (matrices [n,C,C] numpy, records) in one copy
+      set_alignment(slots, W)                write matrices; reset_alignment(slots): back to the model's matrix, accumulators zero
+    reset() restarts a stream, not its session: the matrices and the accumulators stay.
     """
 
     def __init__(self, model, streams: int = 1):
@@ -81,6 +88,15 @@ class StreamDecoder:
         self.gate = getattr(model, "gate", None)
         self.gate_state = None if self.gate is None else ops.gate_state(C_, self.streams, self.device)
         self._gated = {}                                    # chunk shape -> (held samples, mask words)
+        self.align = getattr(model, "align", None)
+        if self.align is not None:
+            S = self.streams
+            self.align_table = model.align_matrix.detach().to(self.device).unsqueeze(0).repeat(S, 1, 1).contiguous()
+            self.cov_state = ops.cov_state(C_, S, self.device)
+            self.align_records = torch.zeros((S, ops.WHITEN_RECORD_BYTES), dtype=torch.uint8, device=self.device)
+            self._all_slots = torch.arange(S, dtype=torch.int32, device=self.device)
+            self._accumulate = False
+            self._aligned = {}                              # chunk shape -> output (a model without gate and prep: x is the caller's)
 
     def _front(self, x: torch.Tensor, slots) -> torch.Tensor:
         """gate -> prep -> apply on a chunk, in stream mode: a bad channel is held through the front end and zeroed behind it, a step
@@ -99,7 +115,74 @@ class StreamDecoder:
             x = ops.prep_step(x, self.prep, self.prep_state, slots=slots, out=out)
         if mask is not None:
             x = ops.gate_apply(x, self.gate, mask, out=x)
+        if self.align is not None:
+            if self._accumulate:
+                ops.cov_step(x, self.cov_state, mask=mask, slots=slots)
+            out = x
+            if self.gate is None and self.prep is None:
+                out = self._aligned.get(tuple(x.shape))
+                if out is None:
+                    out = self._aligned[tuple(x.shape)] = torch.empty_like(x)
+            x = ops.spatial_apply(x, self.align_table, sel=slots if slots is not None else self._all_slots[:x.shape[0]], out=out)
         return x
+
+    # ---- session alignment ----
+    def _need_align(self, who: str) -> None:
+        if self.align is None:
+            raise NsdError(f"{type(self).__name__}.{who}: the model has no session alignment (EEG_LSTM(align=SessionAlign(...)))")
+
+    def align_accumulate(self, on: bool = True) -> None:
+        """Turn the second-moment accumulator inside push on or off (off at first): every pushed step that is finite and clean of
+        gate bits is added to its slot's sums."""
+        self._need_align("align_accumulate")
+        self._accumulate = bool(on)
+
+    @torch.no_grad()
+    def refit_alignment(self, slots=None) -> None:
+        """One nsd_whiten_fit from the accumulators of all slots, or the named ones, into those slots' matrices and records.  Nothing
+        is read back; a slot with fewer than the configuration's min_steps used steps gets the identity (record: few)."""
+        self._need_align("refit_alignment")
+        C_, S = self.model.spec.C, self.streams
+        if slots is None:
+            ops.whiten_fit(C_, self.align, state=self.cov_state, group=self._all_slots, G=S, out=self.align_table,
+                           records=self.align_records.view(-1))
+            return
+        idx = self._slots(slots)
+        n, at = int(idx.numel()), idx.long()
+        group = torch.full((S,), -1, dtype=torch.int32, device=self.device)
+        group[at] = self._all_slots[:n]
+        W, rec = ops.whiten_fit(C_, self.align, state=self.cov_state, group=group, G=n)
+        self.align_table.index_copy_(0, at, W)
+        self.align_records.index_copy_(0, at, rec.view(n, -1))
+
+    def alignment(self, slots=None):
+        """(matrices float32 numpy [n,C,C], the n records of their last fit as dicts) of all slots or the named ones, in one copy.  A
+        slot that was never refitted has an all-zero record."""
+        self._need_align("alignment")
+        at = self._all_slots.long() if slots is None else self._slots(slots).long()
+        n, C_ = int(at.numel()), self.model.spec.C
+        raw = torch.cat([self.align_table[at].view(n, -1).view(torch.uint8), self.align_records[at]], dim=1).cpu()
+        W = raw[:, :4 * C_ * C_].contiguous().view(torch.float32).view(n, C_, C_).numpy().copy()
+        return W, ops.whiten_records(raw[:, 4 * C_ * C_:].contiguous().view(-1), n)
+
+    @torch.no_grad()
+    def set_alignment(self, slots, W) -> None:
+        """Write W ([C,C] for every named slot, or [n,C,C]) into the named slots' matrices (slots None: all)."""
+        self._need_align("set_alignment")
+        at = self._all_slots.long() if slots is None else self._slots(slots).long()
+        C_ = self.model.spec.C
+        W = torch.as_tensor(W, dtype=torch.float32).to(self.device)
+        if tuple(W.shape) not in ((C_, C_), (int(at.numel()), C_, C_)):
+            raise NsdError(f"{type(self).__name__}.set_alignment: W must be [{C_},{C_}] or [{int(at.numel())},{C_},{C_}], got {tuple(W.shape)}")
+        self.align_table[at] = W
+        self.align_records[at] = 0
+
+    @torch.no_grad()
+    def reset_alignment(self, slots=None) -> None:
+        """The named slots (None: all) go back to the model's matrix, their accumulators to zero."""
+        self._need_align("reset_alignment")
+        self.set_alignment(slots, self.model.align_matrix)
+        ops.cov_reset(self.model.spec.C, self.cov_state, self._slots(slots))
 
     def _reset_front(self, slots) -> None:
         C_ = self.model.spec.C
@@ -113,6 +196,9 @@ class StreamDecoder:
             sd["prep_state"] = self.prep_state.detach().cpu().clone()
         if self.gate is not None:
             sd["gate_state"] = self.gate_state.detach().cpu().clone()
+        if self.align is not None:
+            sd["align_table"] = self.align_table.detach().cpu().clone()
+            sd["cov_state"] = self.cov_state.detach().cpu().clone()
         return sd
 
     def _check_front_state(self, sd: dict, who: str):
@@ -121,13 +207,20 @@ class StreamDecoder:
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their causal front end's state")
         if (gs is None) != (self.gate is None) or (gs is not None and tuple(gs.shape) != tuple(self.gate_state.shape)):
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their signal-quality gate's state")
-        return ps, gs
+        at, cs = sd.get("align_table"), sd.get("cov_state")
+        if ((at is None) != (self.align is None) or (cs is None) != (self.align is None)
+                or (at is not None and (tuple(at.shape) != tuple(self.align_table.shape) or tuple(cs.shape) != tuple(self.cov_state.shape)))):
+            raise NsdError(f"{who}: the checkpoint and the decoder differ in their session alignment's state")
+        return ps, gs, at, cs
 
-    def _load_front_state(self, ps, gs) -> None:
+    def _load_front_state(self, ps, gs, at=None, cs=None) -> None:
         if ps is not None:
             self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
         if gs is not None:
             self.gate_state.copy_(gs.to(self.device, dtype=torch.float32))
+        if at is not None:
+            self.align_table.copy_(at.to(self.device, dtype=torch.float32))
+            self.cov_state.copy_(cs.to(self.device, dtype=torch.float64))
 
     def quality(self, slots=None) -> dict:
         """What the signal-quality gate has seen per slot since its reset, read from its state in one copy: {"bad_fraction": [n, C]
@@ -193,9 +286,9 @@ class StreamDecoder:
         st = sd["state"]
         if tuple(st.shape) != tuple(self.state.shape) or int(sd.get("stride", st.shape[-1])) != int(self._layout.stride):
             raise NsdError(f"StreamDecoder.load_state_dict: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
-        ps, gs = self._check_front_state(sd, "StreamDecoder.load_state_dict")
+        front = self._check_front_state(sd, "StreamDecoder.load_state_dict")
         self.state.copy_(st.to(self.device, dtype=torch.float32))
-        self._load_front_state(ps, gs)
+        self._load_front_state(*front)
 
 
 def _check_ensemble(dec, models, streams, who: str, path):
@@ -374,9 +467,9 @@ class SlidingStreamDecoder(StreamDecoder):
         st = sd["state"]
         if tuple(st.shape) != tuple(self.state.shape):
             raise NsdError(f"{who}: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
-        ps, gs = self._check_front_state(sd, who)
+        front = self._check_front_state(sd, who)
         self.state.copy_(st.to(self.device, dtype=torch.float32))
-        self._load_front_state(ps, gs)
+        self._load_front_state(*front)
         self._last_end.copy_(sd["last_end"].to(self.device))
         self._last_probs.copy_(sd["last_probs"].to(self.device))
 

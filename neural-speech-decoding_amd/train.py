@@ -23,6 +23,7 @@ from . import data as D
 from .lstm_eeg_model import EEG_LSTM
 from .ops import Augment, Average, Crop, Loss, LrSchedule, Sam
 from .gate import SignalGate
+from .align import SessionAlign
 from .prep import CausalPrep
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
@@ -71,6 +72,28 @@ def gate_for(args) -> Optional[SignalGate]:
                              pp_seconds=0.5 if args.gate_pp_seconds is None else args.gate_pp_seconds,
                              hold_seconds=0.0 if args.gate_hold_seconds is None else args.gate_hold_seconds,
                              max_bad_channels=args.gate_max_bad_channels)
+
+
+ALIGN_OPTIONS = ("align", "align_shrinkage", "align_floor")
+
+
+def align_for(args) -> Optional[SessionAlign]:
+    """The session alignment the --align* options describe (None without --align); ValueError names a bad option."""
+    if not args.align:
+        if args.align_shrinkage is not None or args.align_floor is not None:
+            raise ValueError("--align-shrinkage / --align-floor without --align")
+        return None
+    return SessionAlign(shrinkage=0.0 if args.align_shrinkage is None else args.align_shrinkage,
+                        floor=1e-4 if args.align_floor is None else args.align_floor)
+
+
+def fit_alignment(model: EEG_LSTM, x_train: torch.Tensor, who: str):
+    """--align: the model's matrix from its own training trials (label-free), before the first step -> (W [C,C] on the device, record)"""
+    W, recs = model.align.fit(model, x_train)
+    if recs[0]["few"] or recs[0]["nonfinite"]:
+        print(f"{who}: --align: the fit kept the identity (status {recs[0]['status']}, {recs[0]['steps']} steps)", file=sys.stderr)
+    model.set_alignment(W[0], record=recs[0])
+    return W[0], recs[0]
 
 
 def drop_bad_trials(x_np, y_np, gate: Optional[SignalGate], fraction: Optional[float], who: str):
@@ -323,6 +346,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gate-hold-seconds", type=float, default=None, help="signal-quality gate: a channel stays bad this long after its last bad sample")
     ap.add_argument("--gate-max-bad-channels", type=int, default=None, help="signal-quality gate: a step with more bad channels than this is "
                                                                              "rejected: no decision (default: never)")
+    ap.add_argument("--align", action="store_true", help="session alignment (SessionAlign): whiten the channels by the inverse square root of "
+                    "their mean second moment, fitted per fold on the training trials before the first step and applied to the held-out ones")
+    ap.add_argument("--align-shrinkage", type=float, default=None, help="session alignment: shrink the moment towards its mean diagonal, in [0, 1] (default 0)")
+    ap.add_argument("--align-floor", type=float, default=None, help="session alignment: eigenvalues below this share of the largest are raised to it (default 1e-4)")
     ap.add_argument("--gate-drop-trials", type=float, default=None, metavar="FRACTION",
                     help="signal-quality gate: drop the trials whose share of rejected steps exceeds FRACTION before the folds are made")
     ap.add_argument("--early-stop-patience", type=int, default=None,
@@ -382,6 +409,12 @@ def main(argv=None) -> int:
         ap.error(str(e))
     if gate is not None and args.normalize:
         ap.error("--gate-* with --normalize: the whole-window z-score would be taken over held and zeroed channels")
+    try:
+        align = align_for(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if align is not None and args.normalize:
+        ap.error("--align with --normalize: the whole-window z-score would undo the whitening channel by channel")
 
     def prep_for(idx):
         """The front end of a run trained on the trials idx: the design, its starting variance calibrated on those trials."""
@@ -475,7 +508,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + GATE_OPTIONS + ("sam_rho",) or v is not None)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + GATE_OPTIONS + ("sam_rho",) or v is not None) and (k not in ALIGN_OPTIONS or v)}
 
     def score(mdl, xs, ys):
         """(accuracy, first-window accuracy or None): whole trials, or with --crop-seconds trials pooled over the evaluation grid"""
@@ -491,7 +524,9 @@ def main(argv=None) -> int:
         what is written / scored -- the number of epochs is fixed beforehand, nothing is selected."""
         torch.manual_seed(seed)           # (Trainer also broadcasts rank 0's parameters when world > 1)
         model = EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, precision=args.precision,
-                         bidirectional=args.bidirectional, prep=prep_for(tr_idx), crop=crop_train, gate=gate).to(dev).train()
+                         bidirectional=args.bidirectional, prep=prep_for(tr_idx), crop=crop_train, gate=gate, align=align).to(dev).train()
+        if align is not None:            # label-free, on this run's training trials; the held-out trials are scored through it
+            fit_alignment(model, x_all[torch.from_numpy(tr_idx).to(dev)], f"train {tag}")
         steps_per_epoch = sum(1 for _ in D.epoch_batches(len(tr_idx), args.batch, seed, 0, drop_last=len(tr_idx) >= args.batch))
         average = average_for(args, steps_per_epoch)
         trainer = Trainer(model, lr=args.lr, weight_decay=args.weight_decay, seed=seed + 1, augment=augment, loss=loss_for(args, y_np[tr_idx]),
@@ -556,7 +591,7 @@ def main(argv=None) -> int:
         models, prep_all = [], prep_for(np.arange(len(y_np)))
         for r in runs:
             torch.manual_seed(r["seed"])     # the initial parameters of the sequential run of this fold
-            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all, crop=crop_train, gate=gate).to(dev).train())
+            models.append(EEG_LSTM(8, args.hidden, 2, args.classes, args.dropout, normalize=args.normalize, prep=prep_all, crop=crop_train, gate=gate, align=align).to(dev).train())
         steps_per_epoch = concurrent_epoch(runs, args.batch, 0, lambda idxs: None)
         average = average_for(args, steps_per_epoch)
         mbt = ModelBatchTrainer(models, lr=args.lr, weight_decay=args.weight_decay, seeds=[r["seed"] + 1 for r in runs], augment=augment,
@@ -566,6 +601,8 @@ def main(argv=None) -> int:
         opt_on = args.clip_grad_norm is not None or args.lr_schedule is not None or average is not None or sam_for(args) is not None
         avg_on, inner, es_epoch0 = average is not None, None, 0
         tr_devs = [torch.from_numpy(r["tr"]).to(dev) for r in runs]
+        if align is not None:            # every fold's matrix from its own training part
+            mbt.set_alignment(torch.stack([fit_alignment(mdl, x_all[tr_devs[k]], f"train run {k}")[0] for k, mdl in enumerate(models)]))
         t0 = time.time()
         res = [dict(acc_train_last=float("nan"), acc_val_last=float("nan")) for _ in runs]
 

@@ -554,15 +554,20 @@ def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:
     key names on CPU; lstm_eeg_model.py:77-81).  A model with a causal front end is written in the dict form both loaders accept,
     {"state_dict": ..., "nsd_prep": prep.to_dict()}: the reference's loader reads the weights, SimplePredictor here rebuilds the prep too.
     A model trained on crops (model.crop) adds "nsd_crop" = {window, crops, hop} to that dict, one with a signal-quality gate
-    "nsd_gate" = gate.to_dict(); a model with neither is written as before."""
+    "nsd_gate" = gate.to_dict(), one with session alignment "nsd_align" = {config, matrix [C,C], record of its fit or None}; a model with
+    none of them is written as before."""
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     crop, gate = getattr(model, "crop", None), getattr(model, "gate", None)
-    if model.prep is None and crop is None and gate is None:
+    align = getattr(model, "align", None)
+    if model.prep is None and crop is None and gate is None and align is None:
         torch.save(sd, path)
         return
     extra = {} if model.prep is None else {"nsd_prep": model.prep.to_dict()}
     if gate is not None:
         extra["nsd_gate"] = gate.to_dict()
+    if align is not None:
+        extra["nsd_align"] = {"config": align.to_dict(), "matrix": model.align_matrix.detach().cpu().clone(),
+                              "record": None if model.align_record is None else dict(model.align_record)}
     if crop is not None:
         extra["nsd_crop"] = {"window": int(crop.window), "crops": int(crop.crops), "hop": int(crop.hop)}
     torch.save({"state_dict": sd, **extra}, path)
