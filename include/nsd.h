@@ -1146,6 +1146,55 @@ int     nsd_whiten_fit(int32_t C, const nsd_whiten *w, const double *sums, int64
 int     nsd_spatial_apply(const nsd_dims *d, const float *v, const float *W, int32_t n_mat, const int32_t *sel, float *out, void *stream);
 
 /*
+ * ---- supervised session alignment: the backward of nsd_spatial_apply and an Adam step on the matrix (an EXTENSION) ----
+ *
+ * nsd_spatial_apply is the forward of a linear layer in front of the model; with nsd_lstm_bwd's dx (nsd_dx_path) these two calls fit its
+ * matrix on labelled trials by gradient descent through the frozen model, everything on the device.
+ *
+ * nsd_spatial_bwd.  v, dy, dv [B,T,C] fp32, W and dW [n_mat][C][C] fp32, sel as in the apply, C in [1, 32].  d->B, T, C are read.
+ *   dv (NULL: not formed): dv[b,t,j] = ((W[0][j]*dy[0] + W[1][j]*dy[1]) + ...) serially over i with W = W[sel[b]], every fp32 operation
+ *     rounding on its own -- the apply with the matrix transposed, in the apply's kernel.  A sel entry outside [0, n_mat) gives NaN rows.
+ *     dv == dy is allowed, a partial overlap is refused.
+ *   dW (NULL: not formed), in two fixed stages:
+ *     1. p[b][i][j] is ONE serial chain over t ascending in double, s = s + (double)dy[b,t,i] * (double)v[b,t,j] (an exact product, one
+ *        rounding per sum), one workgroup per row b;
+ *     2. dW[m][i][j] = (float) of ONE serial double chain over b ascending with sel[b] == m -- a second small launch behind the first.
+ *     The bits therefore do not depend on the grid, the tiling, the HIP stream or a graph replay.  A row with sel outside the table is
+ *     left out.  counts (NULL, or int64[2], written with dW): {rows used, rows left out}.  Non-finite input is NOT masked: it reaches
+ *     the entries of its row i or column j.  A matrix no row selects gets zeros.
+ *   p lives in the caller's scratch, needed with dW only: nsd_spatial_bwd_scratch_bytes(d) = B * C * C * 8 bytes, 8-byte aligned.
+ *   NSD_E_INVALID before any launch: NULL d / v / dy / W; dv and dW both NULL; C outside [1, 32]; T < 1; B < 0; n_mat < 1; dW without a
+ *   scratch, or a scratch that is not 8-byte aligned; dv overlapping dy partially.  NSD_E_WORKSPACE: scratch_bytes below the size.
+ *   B = 0 launches stage 2 alone (dW is zero).
+ *
+ * nsd_spatial_fit_step.  One Adam step on A [n_mat][C][C] fp32 from dW, one workgroup per matrix:
+ *   g = dW + decay * (A - A0), each operation rounded in fp32 (A0 [n_mat][C][C]: the prior the fit is pulled towards; NULL: g = dW);
+ *   then nsd_adam_step's arithmetic in its order with weight_decay 0 and grad_scale 1, at step = the matrix's own counter + 1:
+ *     m = b1*m + (1-b1)*g;  v = b2*v + ((1-b2)*g)*g;  A = A - (float)(lr / bc1) * (m / (sqrtf(v) * (float)(1 / sqrt(bc2)) + eps)),
+ *     bc = 1 - beta^step in double, the power by repeated squaring (exact products: a host restatement gives the same bits).
+ *   State (nsd_spatial_fit_state_bytes(C, n_mat); nsd_spatial_fit_state_layout, offsets in BYTES): per matrix m[C][C], v[C][C] (float),
+ *   step, skipped (int64), status (uint32); behind the last matrix one int64 counter of calls.  A reset state is all zero.  The
+ *   counters advance on the device: the call can be captured and replayed.
+ *   If any g of a matrix is not finite, that matrix, its moments and its step stay bitwise as they were, NSD_SPATIAL_FIT_NONFINITE is
+ *   set in its status and its skipped counter advances; the other matrices proceed.
+ *   loss_in (NULL, or a device float, what nsd_loss_sum wrote) is copied to loss_out[calls] while calls < loss_cap: the per-epoch losses
+ *   need no host read.
+ *   NSD_E_INVALID before any launch, naming the field: NULL A / dW / fit / state; C outside [1, 32]; n_mat < 1; lr or decay negative or
+ *   not finite; a beta outside [0, 1); eps not positive or not finite; a state that is not 8-byte aligned or smaller than
+ *   nsd_spatial_fit_state_bytes(); loss_in without loss_out, or loss_cap < 0.
+ */
+#define NSD_SPATIAL_FIT_NONFINITE 1u
+typedef struct nsd_spatial_fit { float lr, beta1, beta2, eps, decay; } nsd_spatial_fit;
+typedef struct nsd_spatial_fit_layout { int64_t m, v, step, skipped, status, stride; } nsd_spatial_fit_layout;   /* bytes in a slot; depends on C only */
+int64_t nsd_spatial_bwd_scratch_bytes(const nsd_dims *d);
+int     nsd_spatial_bwd(const nsd_dims *d, const float *v, const float *dy, const float *W, int32_t n_mat, const int32_t *sel,
+                        float *dv, float *dW, int64_t *counts, void *scratch, int64_t scratch_bytes, void *stream);
+int64_t nsd_spatial_fit_state_bytes(int32_t C, int32_t n_mat);
+int     nsd_spatial_fit_state_layout(int32_t C, nsd_spatial_fit_layout *out);
+int     nsd_spatial_fit_step(int32_t C, int32_t n_mat, float *A, const float *A0, const float *dW, const nsd_spatial_fit *fit,
+                             void *state, int64_t state_bytes, const float *loss_in, float *loss_out, int32_t loss_cap, void *stream);
+
+/*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----
  *
  * Building block, exported so that it can be tested and timed on its own: C[M,N] = A . B with bf16 operands (device

@@ -190,6 +190,17 @@ class CovLayout(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("sum", "count", "skipped", "stride")]
 
 
+class SpatialFitCfg(C.Structure):
+    """nsd_spatial_fit of include/nsd.h"""
+    _fields_ = [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "decay")]
+
+
+class SpatialFitLayout(C.Structure):
+    """nsd_spatial_fit_layout of include/nsd.h: offsets inside one matrix's slot of a fit state, in bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("m", "v", "step", "skipped", "status", "stride")]
+
+
+NSD_SPATIAL_FIT_NONFINITE = 1
 NSD_WHITEN_MAX_SWEEPS = 40
 NSD_WHITEN_FEW, NSD_WHITEN_NONFINITE, NSD_WHITEN_CLIPPED, NSD_WHITEN_NOT_CONVERGED = 1, 2, 4, 8
 
@@ -357,6 +368,12 @@ SYMBOLS = {
     "nsd_cov_step": (C.c_int, [_dp, _fp, _vp, _ip, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "nsd_whiten_fit": (C.c_int, [C.c_int32, C.POINTER(Whiten), _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _fp, _vp, _vp]),
     "nsd_spatial_apply": (C.c_int, [_dp, _fp, _fp, C.c_int32, _ip, _fp, _vp]),
+    # supervised session alignment: the apply's backward and the Adam step on the matrix
+    "nsd_spatial_bwd_scratch_bytes": (C.c_int64, [_dp]),
+    "nsd_spatial_bwd": (C.c_int, [_dp, _fp, _fp, _fp, C.c_int32, _ip, _fp, _fp, _vp, _vp, C.c_int64, _vp]),
+    "nsd_spatial_fit_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "nsd_spatial_fit_state_layout": (C.c_int, [C.c_int32, C.POINTER(SpatialFitLayout)]),
+    "nsd_spatial_fit_step": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, C.POINTER(SpatialFitCfg), _vp, C.c_int64, _fp, _fp, C.c_int32, _vp]),
 }
 NSD_MAX_MODELS = 32
 

@@ -162,3 +162,177 @@ class SessionAlign:
             W, rec = ops.whiten_fit(model.spec.C, self, sums, counts, group=group, G=G)
         return W, ops.whiten_records(rec, G)
 
+
+def check_spatial_fit(epochs, lr, decay, betas, eps) -> None:
+    """The configuration nsd_spatial_fit_step would refuse, refused on the host with the field's name."""
+    if isinstance(epochs, bool) or int(epochs) != epochs or int(epochs) < 1:
+        raise ValueError(f"SpatialFit: epochs {epochs!r} must be an integer >= 1")
+    for name, v in (("lr", lr), ("decay", decay)):
+        if not (math.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"SpatialFit: {name} {v!r} must be finite and >= 0")
+    if len(tuple(betas)) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError(f"SpatialFit: betas {betas!r} must be two values in [0, 1)")
+    if not (math.isfinite(float(eps)) and float(eps) > 0.0):
+        raise ValueError(f"SpatialFit: eps {eps!r} must be finite and > 0")
+
+
+class SpatialFit:
+    """Supervised session alignment: fit the model's alignment matrix A [C,C] on a few labelled trials of the new session by gradient
+    descent THROUGH the frozen model (nsd_spatial_bwd / nsd_spatial_fit_step of include/nsd.h), everything on the device.  Whitening
+    restores the second moment and leaves a rotation open; the labels close it.
+
+      fit(trials, labels) -> losses [E]   trials [N,T,C], labels [N] class indices.  The model's own gate -> prep -> apply runs over
+                                          the trials ONCE, in eval mode: these inputs v are frozen.  Every epoch then runs, full batch:
+                                          nsd_spatial_apply(v, A) -> nsd_lstm_head_train[_soft] -> nsd_lstm_bwd with dx -> nsd_loss_sum ->
+                                          nsd_spatial_bwd (dA) -> nsd_spatial_fit_step (Adam on A with g = dA + decay * (A - A0)).  The
+                                          forward takes eval-mode noise (no dropout, the eval RReLU slope) through the explicit mask
+                                          arguments, as dx needs.  The model's parameters are read and never written.  Epoch 1 runs
+                                          eagerly; epochs 2 .. E replay one captured graph where capture works (graph=None), the same
+                                          launches eagerly where it does not (or with graph=False): the bits are the same.  losses[e]: the
+                                          mean loss before epoch e's update, copied on the device.  The fitted matrix is written with
+                                          model.set_alignment; its record gains "spatial_fit".  A second call continues the run (Adam's
+                                          moments and step live in the state): 2 + 3 epochs leave the bits 5 leave.
+      reset()                             forget the moments, the step and the status (the matrix stays as it is)
+      status()                            [status word]: 1 where an epoch's gradient was not finite -- those epochs left A untouched
+      check()                             raises NsdError where the status is set
+
+    A0, the prior the fit starts from and is pulled towards, is the matrix the model holds at construction: the whitening matrix of a
+    label-free refit, or the identity (a model without align= gains the stage through EEG_LSTM.enable_alignment()).
+    epochs = 50, lr = 1e-2 and decay = 1e-2 are CHOICES, not measurements: nothing here has tuned them on held-out data.
+    loss: an nsd_amd.Loss -- label smoothing and class weights build the target rows as HeadFit.targets does; mixup is refused (the
+    inputs are frozen whole trials)."""
+
+    def __init__(self, model, *, epochs: int = 50, lr: float = 1e-2, decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
+                 loss=None, graph: Optional[bool] = None):
+        from . import ops
+        from .lstm_eeg_model import EEG_LSTM
+        if not isinstance(model, EEG_LSTM):
+            raise _lib.NsdError("SpatialFit: expected an EEG_LSTM (an ensemble is fitted member by member)")
+        check_spatial_fit(epochs, lr, decay, betas, eps)
+        sp = model.spec
+        if model.precision != "fp32" or sp.D != 1 or not ops.dx_path(sp, 1, 1) or not (sp.H == 48 and sp.L == 2 and sp.C <= 8):
+            raise _lib.NsdError(f"SpatialFit: model shape {sp} is outside nsd_dx_path's fast path -- the input gradient the fit descends "
+                                "along is formed for fp32 models of hidden size 48, 2 layers and <= 8 channels")
+        if loss is not None and loss.mixup:
+            raise _lib.NsdError("SpatialFit: mixup is refused -- the inputs are frozen whole trials; label smoothing and class weights apply")
+        if loss is not None:
+            loss.check_classes(sp.K)
+        flat = model.flat_parameters()
+        if not flat.is_cuda:
+            raise _lib.NsdError("SpatialFit runs only on the MI355X HIP path: move the model to the GPU first; there is no CPU fallback")
+        model.enable_alignment()
+        self.model, self.spec, self.device = model, sp, flat.device
+        self.epochs, self.lr, self.decay, self.betas, self.eps = int(epochs), float(lr), float(decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.loss, self.graph = loss, graph
+        self.A0 = model.align_matrix.detach().to(self.device).clone().contiguous()
+        self.A = self.A0.clone()
+        self.state = ops.spatial_fit_state(sp.C, 1, self.device)
+        self.replayed = False                                  # whether the last fit() replayed a captured graph
+        self.capture_error = None                              # the last failed capture's error (graph=None falls back to eager)
+        self._losses = []                                      # the mean losses of every epoch since the reset
+
+    def targets(self, labels, N: int):
+        """(int32 labels [N] on the device, target rows [N,K] or None): the rows where a Loss asks for them, one nsd_mixup launch at mix = 0"""
+        import torch
+        from . import ops
+        y = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+        y = y.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        if int(y.numel()) != N:
+            raise _lib.NsdError(f"SpatialFit.fit: {int(y.numel())} labels for {N} trials")
+        return y, (None if self.loss is None else ops.target_rows(y, self.spec.K, 1, self.loss))
+
+    def fit(self, trials, labels, epochs: Optional[int] = None):
+        import torch
+        from . import ops
+        sp, dev, model = self.spec, self.device, self.model
+        E = self.epochs if epochs is None else int(epochs)
+        if E < 1:
+            raise ValueError(f"SpatialFit.fit: epochs {epochs!r} must be >= 1")
+        x = torch.as_tensor(trials, dtype=torch.float32).to(dev).contiguous()
+        if x.dim() != 3 or x.shape[-1] != sp.C or x.shape[0] < 1:
+            raise ValueError(f"SpatialFit.fit: trials must be [N >= 1, T, {sp.C}], got {tuple(x.shape)}")
+        N, T = int(x.shape[0]), int(x.shape[1])
+        if not ops.dx_path(sp, N, T):
+            raise _lib.NsdError(f"SpatialFit.fit: {N} trials of {T} steps for {sp} are outside nsd_dx_path (hidden size 48, 2 layers, <= 8 channels)")
+        with torch.no_grad():
+            y, q = self.targets(labels, N)
+            was = model.training
+            model.eval()
+            try:
+                v = model._gate_prep(x)                        # the frozen inputs: the model's own front end, once
+            finally:
+                model.train(was)
+            v = v.clone() if v is x else v
+            flat = model.flat_parameters()
+            xa, dx = torch.empty_like(v), torch.empty_like(v)
+            ws = ops.new_workspace(sp, N, T, dev)
+            logits = torch.empty((N, sp.K), dtype=torch.float32, device=dev)
+            dA = torch.empty((1, sp.C, sp.C), dtype=torch.float32, device=dev)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            scratch = torch.empty(N * sp.C * sp.C, dtype=torch.float64, device=dev)
+            loss1 = torch.zeros(1, dtype=torch.float32, device=dev)
+            losses = torch.full((E,), float("nan"), dtype=torch.float32, device=dev)
+            self.state[-8:].zero_()                            # the call counter indexes this call's losses
+
+            def epoch():
+                ops.spatial_apply(v, self.A, out=xa)
+                ops.train_dx(sp, flat, xa, ws, logits, dx, labels=y, targets=q, rrelu_slope=None, residual=model.residual, loss_out=loss1)
+                ops.spatial_bwd(v, dx, self.A, want_dv=False, dW=dA, counts=counts, scratch=scratch)
+                ops.spatial_fit_step(self.A, dA, self.state, A0=self.A0, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                                     decay=self.decay, loss_in=loss1, loss_out=losses)
+
+            epoch()
+            g = self._capture(epoch) if E > 1 and self.graph is not False else None
+            self.replayed = g is not None
+            for _ in range(E - 1):
+                if g is not None:
+                    g.replay()
+                else:
+                    epoch()
+            mean = losses / float(N)
+            host = [float(l) for l in mean.cpu()]
+            self._losses.extend(host)
+            rec = dict(model.align_record or {})
+            rec["spatial_fit"] = dict(epochs=len(self._losses), lr=self.lr, decay=self.decay, loss_first=self._losses[0],
+                                      loss_last=self._losses[-1], status=self.status()[0])
+            model.set_alignment(self.A, record=rec)
+        return mean
+
+    def _capture(self, epoch):
+        """One epoch as a captured graph, or None where capture does not work (graph=True: the error is raised).  Capture runs nothing:
+        the state is as the eager epochs left it."""
+        import torch
+        try:
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                epoch()
+            return g
+        except Exception as e:                                 # (graph=None: eager is the fallback and leaves the same bits -- but say so)
+            if self.graph:
+                raise
+            import warnings
+            self.capture_error = repr(e)
+            warnings.warn(f"SpatialFit: capturing the epoch as a graph failed ({e!r}); the remaining epochs run eagerly", RuntimeWarning)
+            torch.cuda.synchronize(self.device)
+            return None
+
+    def reset(self) -> None:
+        self.state.zero_()
+        self._losses = []
+
+    def _records(self):
+        from . import ops
+        return ops.spatial_fit_records(self.spec.C, 1, self.state)
+
+    def epochs_done(self) -> int:
+        return self._records()[0]["step"]
+
+    def status(self) -> list:
+        return [int(r["status"]) for r in self._records()]
+
+    def check(self) -> None:
+        if any(self.status()):
+            raise _lib.NsdError("SpatialFit: an epoch's gradient of the alignment matrix was not finite (a non-finite input step, or a loss "
+                                "that overflowed); those epochs left the matrix untouched.  reset() clears the status")
+

@@ -159,11 +159,15 @@ def _accuracy_and_loss(probs: np.ndarray, labels: np.ndarray):
     return acc, loss
 
 
-def calibrate_predictor(predictor, trials, labels, align: bool = True, **fit_kw) -> dict:
+def calibrate_predictor(predictor, trials, labels, align: bool = True, spatial: Optional[dict] = None, **fit_kw) -> dict:
     """SimplePredictor.calibrate / EnsemblePredictor.calibrate: run `trials` ([N,T,C] numpy, or a list of [T,C]) through open_stream on
     reset slots, read the pooled features, fit the read-out(s) on (features, labels), and report loss and accuracy on the calibration
     trials before and after.  labels: class indices [N].  fit_kw: HeadFit's keywords.  Returns dict(n, epochs, loss_before, loss_after,
-    acc_before, acc_after, fit_losses [M,E] numpy, status).  The predictor's model(s) are updated in place."""
+    acc_before, acc_after, fit_losses [M,E] numpy, status).  The predictor's model(s) are updated in place.
+    spatial: None (nothing more is launched), or a dict of align.SpatialFit's keywords ({} for its defaults): the supervised fit of the
+    alignment matrix through the frozen model, between the label-free whitening refit and the features -- the order is whitening refit
+    (if align), SpatialFit, features, HeadFit.  A model without an alignment stage gains one at the identity.  The report gains
+    spatial_losses [E], spatial_status, and loss_spatial / acc_spatial: the calibration trials after the spatial stage alone."""
     x = np.stack([np.asarray(t, dtype=np.float32) for t in trials]) if not isinstance(trials, np.ndarray) else trials
     if x.ndim != 3:
         raise ValueError(f"calibrate: trials must be [N, T, C], got {x.shape}")
@@ -175,6 +179,16 @@ def calibrate_predictor(predictor, trials, labels, align: bool = True, **fit_kw)
     if y.min() < 0 or y.max() >= K:
         raise ValueError(f"calibrate: labels must be class indices in [0, {K})")
     chunk_transform = fit_kw.pop("chunk_transform", None)
+    if spatial is not None:                               # refused before anything runs: a refused call leaves the predictor as it was
+        from .align import check_spatial_fit
+        cfg = dict(epochs=50, lr=1e-2, decay=1e-2, betas=(0.9, 0.999), eps=1e-8)
+        check_spatial_fit(**{k: spatial.get(k, d) for k, d in cfg.items()})
+        if hasattr(predictor.model, "models"):
+            raise NsdError("calibrate: spatial= for an ensemble is not offered -- the model-batched backward forms no input gradient and an "
+                           "ensemble's decoders share one alignment matrix; fit the members one by one (align.SpatialFit) and serve them apart")
+        if chunk_transform is not None:
+            raise NsdError("calibrate: spatial= with chunk_transform= is not offered -- the fit runs the model's own front end over the "
+                           "trials; give the model a CausalPrep")
     stream = predictor.open_stream(streams=N, chunk_transform=chunk_transform)
     align_record = None
     if align and getattr(predictor.model, "align", None) is not None:
@@ -186,10 +200,20 @@ def calibrate_predictor(predictor, trials, labels, align: bool = True, **fit_kw)
         align_record = ops.whiten_records(rec, 1)[0]
         if not (align_record["few"] or align_record["nonfinite"]):
             predictor.model.set_alignment(W[0], record=align_record)
-        stream = predictor.open_stream(streams=N, chunk_transform=chunk_transform)
-        stream.push(x)
+        if spatial is None:                               # (with a spatial stage the decoder behind it is the one that is read)
+            stream = predictor.open_stream(streams=N, chunk_transform=chunk_transform)
+            stream.push(x)
     else:
         before, _ = stream.push(x)
+    spatial_report = {}
+    if spatial is not None:
+        from .align import SpatialFit
+        sfit = SpatialFit(predictor.model, **dict(spatial))
+        sl = sfit.fit(x, y)
+        stream = predictor.open_stream(streams=N)              # a fresh decoder: it starts from the fitted matrix
+        mid, _ = stream.push(x)
+        acc_s, loss_s = _accuracy_and_loss(mid, y)
+        spatial_report = dict(spatial_losses=sl.cpu().numpy(), spatial_status=sfit.status(), loss_spatial=loss_s, acc_spatial=acc_s)
     feats = stream.decoder.features()
     fit = HeadFit(predictor.model, **fit_kw)          # an EEG_LSTM, or the ensemble an EnsemblePredictor holds
     losses = fit.fit(feats, y)
@@ -199,7 +223,8 @@ def calibrate_predictor(predictor, trials, labels, align: bool = True, **fit_kw)
     acc0, loss0 = _accuracy_and_loss(before, y)
     acc1, loss1 = _accuracy_and_loss(after, y)
     return dict(n=N, epochs=fit.epochs_done(), loss_before=loss0, loss_after=loss1, acc_before=acc0, acc_after=acc1,
-                fit_losses=losses.cpu().numpy(), status=fit.status(), **({} if align_record is None else {"align": align_record}))
+                fit_losses=losses.cpu().numpy(), status=fit.status(), **({} if align_record is None else {"align": align_record}),
+                **spatial_report)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -220,6 +245,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--head-dropout", type=float, default=None, help="train-mode noise of the head during the fit (default: eval-mode fit)")
     ap.add_argument("--align", action="store_true", help="refit the session alignment of a checkpoint that carries one (nsd_align) from the "
                     "calibration trials, label-free, before the read-out is fitted (without it the checkpoint's matrix stays)")
+    ap.add_argument("--fit-spatial", action="store_true", help="fit the alignment matrix on the labelled calibration trials by gradient "
+                    "descent through the frozen model (align.SpatialFit), behind --align's label-free refit and before the read-out is "
+                    "fitted; a checkpoint without nsd_align gains a matrix that starts at the identity; one --model only (an ensemble is refused)")
+    ap.add_argument("--spatial-epochs", type=int, default=50, help="a choice, not tuned on held-out data")
+    ap.add_argument("--spatial-lr", type=float, default=1e-2, help="a choice, not tuned on held-out data")
+    ap.add_argument("--spatial-decay", type=float, default=1e-2, help="pull towards the matrix the fit starts from; a choice")
     ap.add_argument("--out", required=True, help="calibrated checkpoint; with several --model: <out stem>_m<i>.pth per member")
     return ap
 
@@ -244,6 +275,8 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.calib_per_class < 1:
         ap.error("--calib-per-class must be at least 1")
+    if args.fit_spatial and len(args.model) > 1:
+        ap.error("--fit-spatial takes one --model: an ensemble's decoders share one alignment matrix")
     if not torch.cuda.is_available():
         print("calibrate: needs an MI355X (no CPU path)", file=sys.stderr)
         return 2
@@ -263,7 +296,8 @@ def main(argv=None) -> int:
 
     acc0 = held_out_accuracy()
     loss = Loss(label_smoothing=args.label_smoothing) if args.label_smoothing else None
-    rep = pred.calibrate(ts.x[cal], ts.y[cal], epochs=args.epochs, lr=args.lr, weight_decay=args.weight_decay,
+    spatial = dict(epochs=args.spatial_epochs, lr=args.spatial_lr, decay=args.spatial_decay) if args.fit_spatial else None
+    rep = pred.calibrate(ts.x[cal], ts.y[cal], spatial=spatial, epochs=args.epochs, lr=args.lr, weight_decay=args.weight_decay,
                          train=tuple(s for s in args.train.split(",") if s), head_dropout=args.head_dropout, loss=loss, seed=args.seed, align=args.align)
     acc1 = held_out_accuracy()
     members = getattr(pred, "members", None) or [pred.model]
@@ -273,7 +307,10 @@ def main(argv=None) -> int:
         save_reference_checkpoint(m, path)
     print(json.dumps(dict(models=len(members), calib_trials=int(len(cal)), held_out_trials=int(len(held)), epochs=rep["epochs"],
                           calib_loss_before=rep["loss_before"], calib_loss_after=rep["loss_after"], calib_acc_before=rep["acc_before"],
-                          calib_acc_after=rep["acc_after"], held_out_acc_before=acc0, held_out_acc_after=acc1, status=rep["status"],
+                          calib_acc_after=rep["acc_after"],
+                          **({"spatial_loss_first": float(rep["spatial_losses"][0]), "spatial_loss_last": float(rep["spatial_losses"][-1]),
+                              "spatial_status": rep["spatial_status"], "calib_acc_spatial": rep["acc_spatial"]} if args.fit_spatial else {}),
+                          held_out_acc_before=acc0, held_out_acc_after=acc1, status=rep["status"],
                           out=outs)))
     return 0
 

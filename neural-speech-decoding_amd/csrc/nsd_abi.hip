@@ -1960,4 +1960,74 @@ int nsd_spatial_apply(const nsd_dims *d, const float *v, const float *W, int32_t
     return nsd_spatial_launch(a, (hipStream_t)stream);
 }
 
+// ---- supervised session alignment (nsd_spatial_bwd / nsd_spatial_fit_step, include/nsd.h; nsd_align.hip) ----
+int64_t nsd_spatial_bwd_scratch_bytes(const nsd_dims *d) {
+    if (!d || !gate_channels(d->C) || d->B < 0) { nsd_set_error("spatial_bwd_scratch_bytes: null d, C outside [1, 32], or B < 0"); return NSD_E_INVALID; }
+    return (int64_t)d->B * d->C * d->C * (int64_t)sizeof(double);
+}
+
+int nsd_spatial_bwd(const nsd_dims *d, const float *v, const float *dy, const float *W, int32_t n_mat, const int32_t *sel,
+                    float *dv, float *dW, int64_t *counts, void *scratch, int64_t scratch_bytes, void *stream) {
+    static const char *who = "spatial_bwd";
+    if (!d || !v || !dy || !W) { nsd_set_error("%s: null pointer (d, v, dy, W)", who); return NSD_E_INVALID; }
+    if (!dv && !dW) { nsd_set_error("%s: neither dv nor dW", who); return NSD_E_INVALID; }
+    if (!gate_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if (n_mat < 1) { nsd_set_error("%s: n_mat = %d matrices", who, n_mat); return NSD_E_INVALID; }
+    const int64_t n = (int64_t)d->B * d->T * d->C;
+    if (dv && dv != dy && dy < dv + n && dv < dy + n) { nsd_set_error("%s: dv overlaps dy partially (in place means dv == dy)", who); return NSD_E_INVALID; }
+    if (dW && d->B > 0) {
+        if (!scratch) { nsd_set_error("%s: dW without a scratch", who); return NSD_E_INVALID; }
+        if ((uintptr_t)scratch % 8) { nsd_set_error("%s: scratch is not 8-byte aligned (it holds doubles)", who); return NSD_E_INVALID; }
+        const int64_t need = (int64_t)d->B * d->C * d->C * (int64_t)sizeof(double);
+        if (scratch_bytes < need) {
+            nsd_set_error("%s: scratch of %lld bytes is smaller than nsd_spatial_bwd_scratch_bytes() = %lld", who, (long long)scratch_bytes, (long long)need);
+            return NSD_E_WORKSPACE;
+        }
+    }
+    if (counts && (uintptr_t)counts % 8) { nsd_set_error("%s: counts are not 8-byte aligned", who); return NSD_E_INVALID; }
+    SpatialBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.v = v; a.dy = dy; a.W = W; a.sel = sel; a.dv = dv; a.dW = dW; a.counts = (long long *)counts; a.p = (double *)scratch;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.n_mat = n_mat;
+    return nsd_spatial_bwd_launch(a, (hipStream_t)stream);
+}
+
+int64_t nsd_spatial_fit_state_bytes(int32_t C, int32_t n_mat) {
+    if (!gate_channels(C) || n_mat < 1) { nsd_set_error("spatial_fit_state_bytes: C outside [1, 32], or n_mat < 1"); return NSD_E_INVALID; }
+    return (int64_t)n_mat * sfit_stride(C) + (int64_t)sizeof(int64_t);
+}
+
+int nsd_spatial_fit_state_layout(int32_t C, nsd_spatial_fit_layout *out) {
+    if (!gate_channels(C) || !out) { nsd_set_error("spatial_fit_state_layout: C outside [1, 32], or null pointer"); return NSD_E_INVALID; }
+    out->m = sfit_m(C); out->v = sfit_v(C); out->step = sfit_step(C); out->skipped = sfit_skipped(C); out->status = sfit_status(C);
+    out->stride = sfit_stride(C);
+    return NSD_OK;
+}
+
+int nsd_spatial_fit_step(int32_t C, int32_t n_mat, float *A, const float *A0, const float *dW, const nsd_spatial_fit *fit,
+                         void *state, int64_t state_bytes, const float *loss_in, float *loss_out, int32_t loss_cap, void *stream) {
+    static const char *who = "spatial_fit_step";
+    if (!A || !dW || !fit || !state) { nsd_set_error("%s: null pointer (A, dW, fit, state)", who); return NSD_E_INVALID; }
+    if (!gate_channels(C)) { nsd_set_error("%s: C = %d channels outside [1, 32]", who, C); return NSD_E_INVALID; }
+    if (n_mat < 1) { nsd_set_error("%s: n_mat = %d matrices", who, n_mat); return NSD_E_INVALID; }
+    if (!(fit->lr >= 0.f) || !std::isfinite(fit->lr)) { nsd_set_error("%s: lr %g negative or not finite", who, fit->lr); return NSD_E_INVALID; }
+    if (!(fit->decay >= 0.f) || !std::isfinite(fit->decay)) { nsd_set_error("%s: decay %g negative or not finite", who, fit->decay); return NSD_E_INVALID; }
+    if (!(fit->beta1 >= 0.f && fit->beta1 < 1.f)) { nsd_set_error("%s: beta1 %g outside [0, 1)", who, fit->beta1); return NSD_E_INVALID; }
+    if (!(fit->beta2 >= 0.f && fit->beta2 < 1.f)) { nsd_set_error("%s: beta2 %g outside [0, 1)", who, fit->beta2); return NSD_E_INVALID; }
+    if (!(fit->eps > 0.f) || !std::isfinite(fit->eps)) { nsd_set_error("%s: eps %g not positive or not finite", who, fit->eps); return NSD_E_INVALID; }
+    if ((uintptr_t)state % 8) { nsd_set_error("%s: state is not 8-byte aligned (it holds int64 counters)", who); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)n_mat * sfit_stride(C) + (int64_t)sizeof(int64_t);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_spatial_fit_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_INVALID;
+    }
+    if (loss_in && (!loss_out || loss_cap < 0)) { nsd_set_error("%s: loss_in without loss_out, or loss_cap = %d < 0", who, loss_cap); return NSD_E_INVALID; }
+    SpatialFitArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = A; a.A0 = A0; a.dW = dW; a.state = (unsigned char *)state; a.loss_in = loss_in; a.loss_out = loss_out; a.loss_cap = loss_in ? loss_cap : 0;
+    a.C = C; a.n_mat = n_mat; a.lr = fit->lr; a.b1 = fit->beta1; a.b2 = fit->beta2; a.eps = fit->eps; a.decay = fit->decay;
+    return nsd_spatial_fit_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

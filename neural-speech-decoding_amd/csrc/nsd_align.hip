@@ -18,6 +18,11 @@
 // spatial_kernel: one workgroup per (row b, tile of SP_TS steps): the row's matrix and the tile are staged into LDS (odd row strides),
 // then a thread forms one output -- or four outputs of one step and one 16-byte store where C % 4 == 0 and the pointers allow -- by
 // the serial sum over j.  A workgroup reads its whole tile before it writes, and no other workgroup reads it: out == v is safe.
+//
+// The supervised fit of that matrix (nsd_spatial_bwd / nsd_spatial_fit_step): dv is spatial_kernel with the matrix staged transposed;
+// dW is spatial_dw_kernel (cov_kernel's shape over two operands: one serial double chain over t per row and entry) and
+// spatial_dw_sum_kernel (a second small launch: one serial double chain over the rows per matrix); spatial_fit_kernel is one Adam step
+// per matrix with its counters in the caller's state.
 // No atomics, no private segment, vector stores only.
 #include "nsd_args.h"
 
@@ -266,7 +271,8 @@ __global__ __launch_bounds__(64) void whiten_kernel(const WhitenArgs a) {
 constexpr int SP_BLOCK = 256;
 constexpr int SP_TS = 64;                                  // steps of a tile
 
-template <bool VEC>
+// TR: the matrix is staged transposed -- out[b,t,j] = sum_i W[i][j] * v[b,t,i], the input gradient of the apply (nsd_spatial_bwd's dv)
+template <bool VEC, bool TR = false>
 __global__ __launch_bounds__(SP_BLOCK) void spatial_kernel(const SpatialArgs a) {
     constexpr int Q = VEC ? 4 : 1;
     __shared__ float wt[ALIGN_MAXC * ALIGN_LD];            // [C][CP]: the row's matrix
@@ -289,7 +295,12 @@ __global__ __launch_bounds__(SP_BLOCK) void spatial_kernel(const SpatialArgs a) 
             }
             continue;
         }
-        stage_rows<false>(a.W + (size_t)m * C * C, wt, C, C, CP, tid, SP_BLOCK);
+        if constexpr (TR) {
+            const float *Wm = a.W + (size_t)m * C * C;
+            for (int e = tid; e < C * C; e += SP_BLOCK) { const int i = e / C, j = e - i * C; wt[j * CP + i] = Wm[e]; }
+        } else {
+            stage_rows<false>(a.W + (size_t)m * C * C, wt, C, C, CP, tid, SP_BLOCK);
+        }
         stage_rows<VEC>(a.v + base, vt, nt, C, CP, tid, SP_BLOCK);
         __syncthreads();
         for (int idx = tid; idx < nq; idx += SP_BLOCK) {
@@ -310,7 +321,189 @@ __global__ __launch_bounds__(SP_BLOCK) void spatial_kernel(const SpatialArgs a) 
     }
 }
 
+// ---- nsd_spatial_bwd's dW, stage 1: p[b][i][j] = the serial chain over t of (double)dy[b,t,i] * (double)v[b,t,j].  cov_kernel's shape: one
+// workgroup per row, tiles of DW_TT steps of both operands through LDS, up to COV_ENT entries per thread.  Nothing is masked: a
+// non-finite value reaches the entries of its row and column.  A row whose selection lies outside the table is skipped whole (stage 2
+// never reads its p).
+constexpr int DW_UN = 8;                                   // steps whose operands are in flight at once
+constexpr int DW_TT = 128;                                 // steps staged at once (two operands: 33 KB of LDS)
+// NE: the entries a thread walks, 1 up to C = 16 (C * C <= COV_BLOCK), else COV_ENT -- a compile-time count keeps the walk free of branches
+template <bool VEC, int NE>
+__global__ __launch_bounds__(COV_BLOCK) void spatial_dw_kernel(const SpatialBwdArgs a) {
+    __shared__ float yt[DW_TT * ALIGN_LD], xt[DW_TT * ALIGN_LD];   // [DW_TT][CP]: dy and v
+    const int C = a.C, T = a.T, tid = threadIdx.x, CC = C * C, CP = C | 1;
+    int ei[COV_ENT], ej[COV_ENT];
+#pragma unroll
+    for (int k = 0; k < COV_ENT; ++k) {
+        const int e = tid + k * COV_BLOCK;
+        ei[k] = e < CC ? e / C : 0;
+        ej[k] = e < CC ? e - ei[k] * C : 0;
+    }
+    for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const int m = a.sel ? a.sel[b] : 0;
+        if ((unsigned)m >= (unsigned)a.n_mat) continue;    // (the whole workgroup)
+        double acc[COV_ENT];
+#pragma unroll
+        for (int k = 0; k < COV_ENT; ++k) acc[k] = 0.0;
+        for (int t0 = 0; t0 < T; t0 += DW_TT) {
+            const int nt = T - t0 < DW_TT ? T - t0 : DW_TT;
+            const size_t base = ((size_t)b * T + t0) * C;
+            stage_rows<VEC>(a.dy + base, yt, nt, C, CP, tid, COV_BLOCK);
+            stage_rows<VEC>(a.v + base, xt, nt, C, CP, tid, COV_BLOCK);
+            __syncthreads();
+            // the chain is serial, its operands are not: DW_UN steps' LDS reads are issued before their DW_UN dependent additions
+            // (an entry beyond C * C reads (0, 0) and is never stored; a whole wave beyond it skips the walk)
+            if (tid - (tid & 63) < CC) {
+                int t = 0;
+                for (; t + DW_UN <= nt; t += DW_UN) {
+                    float yv[DW_UN][NE], xv[DW_UN][NE];
+#pragma unroll
+                    for (int u = 0; u < DW_UN; ++u)
+#pragma unroll
+                        for (int k = 0; k < NE; ++k) { yv[u][k] = yt[(t + u) * CP + ei[k]]; xv[u][k] = xt[(t + u) * CP + ej[k]]; }
+#pragma unroll
+                    for (int u = 0; u < DW_UN; ++u)
+#pragma unroll
+                        for (int k = 0; k < NE; ++k) acc[k] = acc[k] + (double)yv[u][k] * (double)xv[u][k];
+                }
+                for (; t < nt; ++t) {
+                    const float *yr = yt + t * CP, *xr = xt + t * CP;
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) acc[k] = acc[k] + (double)yr[ei[k]] * (double)xr[ej[k]];
+                }
+            }
+            __syncthreads();                               // (the next tile is staged over this one)
+        }
+        double *dst = a.p + (size_t)b * CC;
+#pragma unroll
+        for (int k = 0; k < COV_ENT; ++k) {
+            const int e = tid + k * COV_BLOCK;
+            if (e < CC) dst[e] = acc[k];
+        }
+    }
+}
+
+// stage 2, a second launch behind stage 1 on the stream: one workgroup per matrix sums the p of its rows in ascending b, in double, and
+// rounds once.  Workgroup 0 also counts the rows.
+__global__ __launch_bounds__(COV_BLOCK) void spatial_dw_sum_kernel(const SpatialBwdArgs a) {
+    const int m = blockIdx.x, CC = a.C * a.C, tid = threadIdx.x;
+    double acc[COV_ENT];
+#pragma unroll
+    for (int k = 0; k < COV_ENT; ++k) acc[k] = 0.0;
+    long long used = 0, left = 0;
+    for (int b = 0; b < a.B; ++b) {
+        const int mb = a.sel ? a.sel[b] : 0;
+        if ((unsigned)mb >= (unsigned)a.n_mat) { ++left; continue; }
+        ++used;
+        if (mb != m) continue;
+        const double *src = a.p + (size_t)b * CC;
+#pragma unroll
+        for (int k = 0; k < COV_ENT; ++k) {
+            const int e = tid + k * COV_BLOCK;
+            if (e < CC) acc[k] = acc[k] + src[e];
+        }
+    }
+    float *dst = a.dW + (size_t)m * CC;
+#pragma unroll
+    for (int k = 0; k < COV_ENT; ++k) {
+        const int e = tid + k * COV_BLOCK;
+        if (e < CC) dst[e] = (float)acc[k];
+    }
+    if (m == 0 && tid == 0 && a.counts) { a.counts[0] = used; a.counts[1] = left; }
+}
+
+// b^s by squaring: the same products on the host restatement (pow() differs from libm's in the last place)
+__device__ __forceinline__ double sfit_pow(double b, long long s) {
+    double r = 1.0;
+    while (s) { if (s & 1) r *= b; b *= b; s >>= 1; }
+    return r;
+}
+
+// ---- nsd_spatial_fit_step: one workgroup per matrix, up to COV_ENT entries per thread.  g = dW + decay * (A - A0), tested whole; a
+// matrix with a g that is not finite only records it.  The update is adam_kernel's arithmetic in its order (weight decay 0, scale 1),
+// the bias corrections formed in double from the slot's own counter, which advances here: the call replays from a graph.
+__global__ __launch_bounds__(COV_BLOCK) void spatial_fit_kernel(const SpatialFitArgs a) {
+    const int m = blockIdx.x, C = a.C, CC = C * C, tid = threadIdx.x;
+    unsigned char *slot = a.state + (size_t)m * sfit_stride(C);
+    float *mom = reinterpret_cast<float *>(slot + sfit_m(C)), *var = reinterpret_cast<float *>(slot + sfit_v(C));
+    long long *step = reinterpret_cast<long long *>(slot + sfit_step(C)), *skipped = reinterpret_cast<long long *>(slot + sfit_skipped(C));
+    unsigned *status = reinterpret_cast<unsigned *>(slot + sfit_status(C));
+    if (m == 0 && tid == 0) {                              // the loss of this call, by the call counter behind the last slot
+        long long *calls = reinterpret_cast<long long *>(a.state + (size_t)a.n_mat * sfit_stride(C));
+        const long long n = calls[0];
+        if (a.loss_in && n >= 0 && n < (long long)a.loss_cap) a.loss_out[n] = a.loss_in[0];   // (n < 0: a state nobody reset)
+        calls[0] = n + 1;
+    }
+    float *A = a.A + (size_t)m * CC;
+    float g[COV_ENT], pi[COV_ENT];
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < COV_ENT; ++k) {
+        const int e = tid + k * COV_BLOCK;
+        g[k] = pi[k] = 0.f;
+        if (e < CC) {
+            pi[k] = A[e];
+            const float d = a.dW[(size_t)m * CC + e];
+            g[k] = a.A0 ? __fadd_rn(d, __fmul_rn(a.decay, __fsub_rn(pi[k], a.A0[(size_t)m * CC + e]))) : d;
+            fin &= finite_f(g[k]);
+        }
+    }
+    const long long s = step[0];                           // (read by every thread above the barrier, written by thread 0 below it)
+    const bool bad = __syncthreads_or(!fin) != 0;
+    if (bad) {
+        if (tid == 0) { status[0] |= NSD_SPATIAL_FIT_NONFINITE; skipped[0] += 1; }
+        return;
+    }
+    const double bc1 = 1.0 - sfit_pow((double)a.b1, s + 1), bc2 = 1.0 - sfit_pow((double)a.b2, s + 1);
+    const float lr_over_bc1 = (float)((double)a.lr / bc1), rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
+#pragma unroll
+    for (int k = 0; k < COV_ENT; ++k) {
+        const int e = tid + k * COV_BLOCK;
+        if (e < CC) {
+            const float gi = g[k];
+            const float mi = a.b1 * mom[e] + (1.f - a.b1) * gi;
+            const float vi = a.b2 * var[e] + (1.f - a.b2) * gi * gi;
+            mom[e] = mi; var[e] = vi;
+            const float denom = sqrtf(vi) * rsqrt_bc2 + a.eps;
+            A[e] = pi[k] - lr_over_bc1 * (mi / denom);
+        }
+    }
+    if (tid == 0) step[0] = s + 1;
+}
+
 }  // namespace
+
+int nsd_spatial_bwd_launch(const SpatialBwdArgs &a, hipStream_t st) {
+    if (a.dv && a.B > 0) {                                 // the apply's kernel on dy with the matrix transposed
+        SpatialArgs s;
+        s.v = a.dy; s.W = a.W; s.sel = a.sel; s.out = a.dv; s.B = a.B; s.T = a.T; s.C = a.C; s.n_mat = a.n_mat;
+        const bool vec = a.C % 4 == 0 && ((uintptr_t)a.dy | (uintptr_t)a.dv) % 16 == 0;
+        const long units = (long)a.B * ((a.T + SP_TS - 1) / SP_TS);
+        const dim3 grid((unsigned)(units < 4 * PREP_GRID_CAP ? units : 4 * PREP_GRID_CAP)), block(SP_BLOCK);
+        if (vec) hipLaunchKernelGGL((spatial_kernel<true, true>), grid, block, 0, st, s);
+        else hipLaunchKernelGGL((spatial_kernel<false, true>), grid, block, 0, st, s);
+        NSD_CHECK_LAUNCH("spatial_bwd (dv)");
+    }
+    if (a.dW) {
+        if (a.B > 0) {
+            const dim3 grid((unsigned)(a.B < PREP_GRID_CAP ? a.B : PREP_GRID_CAP)), block(COV_BLOCK);
+            const bool vec = ((long)a.T * a.C) % 4 == 0 && ((uintptr_t)a.v | (uintptr_t)a.dy) % 16 == 0;
+            const bool one = a.C * a.C <= COV_BLOCK;
+            hipLaunchKernelGGL(vec ? (one ? spatial_dw_kernel<true, 1> : spatial_dw_kernel<true, COV_ENT>)
+                                   : (one ? spatial_dw_kernel<false, 1> : spatial_dw_kernel<false, COV_ENT>), grid, block, 0, st, a);
+            NSD_CHECK_LAUNCH("spatial_bwd (dW, stage 1)");
+        }
+        hipLaunchKernelGGL(spatial_dw_sum_kernel, dim3(a.n_mat), dim3(COV_BLOCK), 0, st, a);
+        NSD_CHECK_LAUNCH("spatial_bwd (dW, stage 2)");
+    }
+    return NSD_OK;
+}
+
+int nsd_spatial_fit_launch(const SpatialFitArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(spatial_fit_kernel, dim3(a.n_mat), dim3(COV_BLOCK), 0, st, a);
+    NSD_CHECK_LAUNCH("spatial_fit_step");
+    return NSD_OK;
+}
 
 int nsd_cov_launch(const CovArgs &a, hipStream_t st) {
     const dim3 grid((unsigned)(a.B < PREP_GRID_CAP ? a.B : PREP_GRID_CAP)), block(COV_BLOCK);

@@ -422,3 +422,29 @@ struct SpatialArgs {
     int B, T, C, n_mat;
 };
 int nsd_spatial_launch(const SpatialArgs &a, hipStream_t st);
+
+// supervised session alignment (nsd_spatial_bwd / nsd_spatial_fit_step of nsd.h; nsd_align.hip).  One matrix's slot of a fit state in
+// BYTES -- the public layout nsd_spatial_fit_state_layout reports: m[C][C], v[C][C] (float), step, skipped (int64), status, reserved
+// (uint32); the int64 call counter follows the last slot
+__host__ __device__ constexpr long sfit_m(int) { return 0; }
+__host__ __device__ constexpr long sfit_v(int C) { return 4L * C * C; }
+__host__ __device__ constexpr long sfit_step(int C) { return 8L * C * C; }
+__host__ __device__ constexpr long sfit_skipped(int C) { return 8L * C * C + 8; }
+__host__ __device__ constexpr long sfit_status(int C) { return 8L * C * C + 16; }
+__host__ __device__ constexpr long sfit_stride(int C) { return 8L * C * C + 24; }
+struct SpatialBwdArgs {
+    const float *v, *dy, *W; const int32_t *sel;   // v, dy [B,T,C]; W [n_mat][C][C]; sel null or [B]
+    float *dv, *dW;                          // null, or [B,T,C]; null, or [n_mat][C][C]
+    long long *counts;                       // null, or {rows used, rows left out} (written with dW)
+    double *p;                               // scratch [B][C][C]: stage 1 of dW
+    int B, T, C, n_mat;
+};
+int nsd_spatial_bwd_launch(const SpatialBwdArgs &a, hipStream_t st);
+struct SpatialFitArgs {
+    float *A; const float *A0, *dW;          // [n_mat][C][C]; A0 null: no pull
+    unsigned char *state;                    // n_mat slots, then the call counter
+    const float *loss_in; float *loss_out; int loss_cap;
+    int C, n_mat;
+    float lr, b1, b2, eps, decay;
+};
+int nsd_spatial_fit_launch(const SpatialFitArgs &a, hipStream_t st);

@@ -192,8 +192,11 @@ class EEG_LSTM(nn.Module):
                      Not together with normalize; no input gradient is offered through it.
       align          a SessionAlign: session alignment behind the front end (gate -> prep -> apply -> align -> LSTM; nsd_spatial_apply):
                      every step is multiplied by the model's alignment matrix, a non-persistent buffer `align_matrix` [C,C] that is the
-                     identity until set (align_matrix=, set_alignment(), SessionAlign.fit).  Not together with normalize; no input
-                     gradient is offered through it.
+                     identity until set (align_matrix=, set_alignment(), SessionAlign.fit, align.SpatialFit).  Not together with
+                     normalize.  enable_alignment() gives a model built without one the stage at the identity.
+      align_grad     True: x.requires_grad differentiates through the alignment stage (ops.spatial_apply as an autograd node,
+                     nsd_spatial_bwd behind it: x.grad = W^T . dL/d(aligned x), where the kernels form dx at all).  False (default):
+                     asking for an input gradient through align= is refused, as through gate= and prep=, which stay refused.
       crop           an ops.Crop: the window the model was (or is being) trained on by cropped training (Trainer(crop=)).  It changes
                      nothing in forward(); it travels with the model and its checkpoints so that predict_trials(), SimplePredictor and
                      open_stream() know the trained window.
@@ -202,8 +205,9 @@ class EEG_LSTM(nn.Module):
     def __init__(self, input_size=8, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, *,
                  residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32",
                  prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None, gate: Optional[SignalGate] = None,
-                 align: Optional[SessionAlign] = None, align_matrix=None):
+                 align: Optional[SessionAlign] = None, align_matrix=None, align_grad: bool = False):
         super().__init__()
+        self.align_grad = bool(align_grad)
         if align is not None and not isinstance(align, SessionAlign):
             raise ValueError(f"align={align!r}: expected a SessionAlign")
         if align is not None and normalize:
@@ -301,7 +305,8 @@ class EEG_LSTM(nn.Module):
         if row.dtype != torch.float32 or row.dim() != 1 or row.numel() != sp.param_count or not row.is_contiguous():
             raise NsdError(f"EEG_LSTM.view_of: row must be a contiguous float32 vector of {sp.param_count} elements")
         twin = EEG_LSTM(sp.C, sp.H, sp.L, sp.K, self.head_dropout_p, residual=self.residual, normalize=self.normalize,
-                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop, gate=self.gate, align=self.align)
+                        bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop, gate=self.gate, align=self.align,
+                        align_grad=self.align_grad)
         if self.align is not None:
             twin.align_matrix, twin.align_record = self.align_matrix, self.align_record   # (shared: the twin follows a later set_alignment)
         offs = sp.offsets()
@@ -316,6 +321,20 @@ class EEG_LSTM(nn.Module):
         out = super()._apply(fn, *a, **kw)
         self._flat = None        # .to()/.cuda() re-created the storages
         return out
+
+    def enable_alignment(self, align: Optional[SessionAlign] = None) -> "EEG_LSTM":
+        """Give a model built (or loaded) without align= the alignment stage, at the identity: the start and the prior of a supervised
+        fit (align.SpatialFit).  A model that has the stage keeps it, and its matrix, as they are."""
+        if self.align is not None:
+            return self
+        if self.normalize:
+            raise ValueError("enable_alignment on a normalize=True model: the whole-window z-score would undo the matrix channel by channel")
+        if not 1 <= self.spec.C <= 32:
+            raise ValueError(f"enable_alignment: session alignment covers 1 .. 32 channels, the model has {self.spec.C}")
+        self.align = align if align is not None else SessionAlign()
+        dev = next(self.parameters()).device
+        self.register_buffer("align_matrix", torch.eye(self.spec.C, dtype=torch.float32, device=dev), persistent=False)
+        return self
 
     def set_alignment(self, W, record: Optional[dict] = None) -> None:
         """Write the alignment matrix [C,C] (a tensor on any device, or an array) into the model's buffer, in place.  record: the
@@ -340,9 +359,10 @@ class EEG_LSTM(nn.Module):
             if x.requires_grad and torch.is_grad_enabled():
                 raise NsdError("EEG_LSTM(prep=...): dx through the causal front end is not offered -- x.requires_grad would get no "
                                "gradient; detach x, or differentiate a prep-free model on ops.prep_step(x, prep)")
-        if self.align is not None and x.requires_grad and torch.is_grad_enabled():
+        if self.align is not None and not self.align_grad and x.requires_grad and torch.is_grad_enabled():
             raise NsdError("EEG_LSTM(align=...): dx through the session alignment is not offered -- x.requires_grad would get no "
-                           "gradient; detach x, or differentiate an align-free model on ops.spatial_apply(x, W)")
+                           "gradient; detach x, build the model with align_grad=True, or differentiate an align-free model on "
+                           "ops.spatial_apply(x, W)")
         if self.gate is not None or self.prep is not None or self.align is not None:
             return self._front(x)
         return ops.zscore(x) if self.normalize else x
@@ -685,6 +705,9 @@ class SimplePredictor:
         accuracy on the calibration trials before and after, the fit's loss curve and its status.
         align (a model with session alignment only): the alignment matrix is refitted from the calibration trials first -- label-free,
         one nsd_whiten_fit over the accumulators of all trials -- and features and the head fit then run on aligned input; decoders
-        opened afterwards start from the new matrix.  A fit that kept the identity (too few steps) leaves the matrix as it was."""
+        opened afterwards start from the new matrix.  A fit that kept the identity (too few steps) leaves the matrix as it was.
+        spatial=dict(...) (align.SpatialFit's keywords; {} for its defaults): behind that refit and in front of the features, the
+        alignment matrix is fitted on the labelled trials by gradient descent through the frozen model; the report gains
+        spatial_losses, spatial_status, loss_spatial and acc_spatial.  spatial=None (default): nothing more is launched."""
         from .calibrate import calibrate_predictor
         return calibrate_predictor(self, trials, labels, align=align, **fit_kw)

@@ -2344,6 +2344,19 @@ def spatial_apply(v: torch.Tensor, W: torch.Tensor, *, sel: Optional[torch.Tenso
     n_mat = 1 if W.dim() == 2 else int(W.shape[0])
     if sel is not None and (sel.dtype != torch.int32 or not sel.is_cuda or not sel.is_contiguous() or int(sel.numel()) != B):
         raise NsdError(f"spatial_apply: sel must be a contiguous int32 tensor of {B} indices on the device")
+    if torch.is_grad_enabled() and (v.requires_grad or W.requires_grad):
+        # somebody differentiates through the stage: the same launch as an autograd node, nsd_spatial_bwd behind it
+        if out is not None:
+            raise NsdError("spatial_apply: out= with a gradient requested (v or W requires grad) -- the node owns its output")
+        return _SpatialApply.apply(v, W, sel)
+    return _spatial_apply(v, W, sel, out)
+
+
+def _spatial_apply(v: torch.Tensor, W: torch.Tensor, sel: Optional[torch.Tensor], out: Optional[torch.Tensor]) -> torch.Tensor:
+    """the launch of spatial_apply on checked arguments"""
+    T, Cc = int(v.shape[-2]), int(v.shape[-1])
+    B = int(v.numel()) // max(T * Cc, 1)
+    n_mat = 1 if W.dim() == 2 else int(W.shape[0])
     if out is None:
         out = torch.empty_like(v)
     if out.numel() != v.numel():
@@ -2354,3 +2367,150 @@ def spatial_apply(v: torch.Tensor, W: torch.Tensor, *, sel: Optional[torch.Tenso
     _call("nsd_spatial_apply", v.device, C.byref(d), _dev_f32(v, "v"), _dev_f32(W, "W"), n_mat, None if sel is None else sel.data_ptr(),
           _dev_f32(out, "out"), STREAM)
     return out
+
+
+class _SpatialApply(torch.autograd.Function):
+    """nsd_spatial_apply as an autograd node: backward is nsd_spatial_bwd (dv = W^T . dy serially in fp32; dW in two fixed double stages)."""
+
+    @staticmethod
+    def forward(ctx, v, W, sel):
+        vc = v.detach().contiguous()
+        ctx.save_for_backward(vc, W.detach().contiguous())
+        ctx.sel = sel
+        return _spatial_apply(vc, W.detach().contiguous(), sel, None)
+
+    @staticmethod
+    def backward(ctx, dy):
+        v, W = ctx.saved_tensors
+        dv, dW, _ = spatial_bwd(v, dy.contiguous().float(), W, sel=ctx.sel, want_dv=ctx.needs_input_grad[0], want_dW=ctx.needs_input_grad[1])
+        return dv, (None if dW is None else dW.view(W.shape)), None
+
+
+def spatial_bwd_scratch_bytes(B: int, T: int, C_: int) -> int:
+    """nsd_spatial_bwd_scratch_bytes: stage 1 of dW, B * C * C doubles"""
+    d = Dims(int(B), int(T), int(C_), 1, 1, 1, 1)
+    n = int(_lib.lib().nsd_spatial_bwd_scratch_bytes(C.byref(d)))
+    if n < 0:
+        check(n, "nsd_spatial_bwd_scratch_bytes")
+    return n
+
+
+def spatial_bwd(v: torch.Tensor, dy: torch.Tensor, W: torch.Tensor, *, sel: Optional[torch.Tensor] = None, want_dv: bool = True,
+                want_dW: bool = True, dv: Optional[torch.Tensor] = None, dW: Optional[torch.Tensor] = None,
+                counts: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+    """nsd_spatial_bwd, the backward of spatial_apply: v, dy [B,n,C] (or [M,B,n,C]), W [C,C] or [n_mat,C,C], sel as in the apply ->
+    (dv [B,n,C] or None, dW [n_mat,C,C] or None, counts int64 [2] {rows used, rows left out} or None).  dv[b,t,j] = sum_i W[i][j]
+    dy[b,t,i] serially in fp32; dW[m] = the sum over the rows with sel == m and over t of dy (x) v, one double chain over t per row, then
+    one over the rows, rounded once.  dv / dW / counts / scratch (float64, B*C*C elements): caller-owned buffers; nothing is read back."""
+    if v.dim() not in (3, 4) or tuple(dy.shape) != tuple(v.shape):
+        raise NsdError(f"spatial_bwd: v and dy must be [B,n,C] or [M,B,n,C] of one shape, got {tuple(v.shape)} and {tuple(dy.shape)}")
+    T, Cc = int(v.shape[-2]), int(v.shape[-1])
+    B = int(v.numel()) // max(T * Cc, 1)
+    if W.dim() not in (2, 3) or tuple(W.shape[-2:]) != (Cc, Cc):
+        raise NsdError(f"spatial_bwd: W must be [{Cc},{Cc}] or [n_mat,{Cc},{Cc}], got {tuple(W.shape)}")
+    n_mat = 1 if W.dim() == 2 else int(W.shape[0])
+    if sel is not None and (sel.dtype != torch.int32 or not sel.is_cuda or not sel.is_contiguous() or int(sel.numel()) != B):
+        raise NsdError(f"spatial_bwd: sel must be a contiguous int32 tensor of {B} indices on the device")
+    want_dv, want_dW = want_dv or dv is not None, want_dW or dW is not None
+    if not (want_dv or want_dW):
+        return None, None, None
+    if want_dv and dv is None:
+        dv = torch.empty_like(v)
+    if want_dW:
+        if dW is None:
+            dW = torch.empty((n_mat, Cc, Cc), dtype=torch.float32, device=v.device)
+        if counts is None:
+            counts = torch.empty(2, dtype=torch.int64, device=v.device)
+        if scratch is None:
+            scratch = torch.empty(max(B * Cc * Cc, 1), dtype=torch.float64, device=v.device)
+        if int(dW.numel()) != n_mat * Cc * Cc:
+            raise NsdError(f"spatial_bwd: dW has {int(dW.numel())} elements for [{n_mat},{Cc},{Cc}]")
+    else:
+        counts = scratch = None
+    if want_dv and int(dv.numel()) != int(v.numel()):
+        raise NsdError(f"spatial_bwd: dv has {int(dv.numel())} elements for {tuple(v.shape)}")
+    d = Dims(B, T, Cc, 1, 1, 1, 1)
+    _call("nsd_spatial_bwd", v.device, C.byref(d), _dev_f32(v, "v"), _dev_f32(dy, "dy"), _dev_f32(W, "W"), n_mat,
+          None if sel is None else sel.data_ptr(), _dev_f32(dv, "dv"), _dev_f32(dW, "dW"),
+          _dev_typed(counts, "spatial_bwd: counts", torch.int64, 2), _dev_typed(scratch, "spatial_bwd: scratch", torch.float64),
+          0 if scratch is None else _nbytes(scratch), STREAM)
+    return dv, dW, counts
+
+
+SPATIAL_FIT_NONFINITE = _lib.NSD_SPATIAL_FIT_NONFINITE
+
+
+def spatial_fit_layout(C_: int) -> "_lib.SpatialFitLayout":
+    """Offsets, in bytes, of m, v (float [C,C]), step, skipped (int64) and status (uint32) inside one matrix's slot of a fit state, and the
+    slot stride; the int64 call counter follows the last slot."""
+    lay = _lib.SpatialFitLayout()
+    check(_lib.lib().nsd_spatial_fit_state_layout(int(C_), C.byref(lay)), "nsd_spatial_fit_state_layout")
+    return lay
+
+
+def spatial_fit_state(C_: int, n_mat: int = 1, device="cuda") -> torch.Tensor:
+    """A reset fit state of n_mat matrices: zero bytes (uint8 [nsd_spatial_fit_state_bytes]); all-zero is the reset state."""
+    n = int(_lib.lib().nsd_spatial_fit_state_bytes(int(C_), int(n_mat)))
+    if n < 0:
+        check(n, "nsd_spatial_fit_state_bytes")
+    return torch.zeros(n // 8, dtype=torch.int64, device=device).view(torch.uint8)       # (8-byte aligned whatever the allocator does)
+
+
+def spatial_fit_records(C_: int, n_mat: int, state: torch.Tensor) -> List[dict]:
+    """Per matrix {step, skipped, status, m [C,C], v [C,C] numpy} of a fit state, and "calls" in every record (one copy; synchronises)."""
+    import numpy as np
+    lay, Cc = spatial_fit_layout(C_), int(C_)
+    raw = state.detach().view(torch.uint8).cpu().numpy()
+    calls = int(raw[int(n_mat) * int(lay.stride):][:8].view(np.int64)[0])
+    recs = []
+    for m in range(int(n_mat)):
+        s = raw[m * int(lay.stride):(m + 1) * int(lay.stride)]
+        recs.append(dict(step=int(s[int(lay.step):][:8].view(np.int64)[0]), skipped=int(s[int(lay.skipped):][:8].view(np.int64)[0]),
+                         status=int(s[int(lay.status):][:4].view(np.uint32)[0]), calls=calls,
+                         m=s[int(lay.m):][:4 * Cc * Cc].view(np.float32).reshape(Cc, Cc).copy(),
+                         v=s[int(lay.v):][:4 * Cc * Cc].view(np.float32).reshape(Cc, Cc).copy()))
+    return recs
+
+
+def spatial_fit_step(A: torch.Tensor, dW: torch.Tensor, state: torch.Tensor, *, A0: Optional[torch.Tensor] = None, lr: float = 1e-2,
+                     beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, decay: float = 0.0,
+                     loss_in: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None) -> None:
+    """nsd_spatial_fit_step: one Adam step on A [C,C] or [n_mat,C,C] in place from dW, with g = dW + decay * (A - A0) (A0 None: no
+    pull).  state: ops.spatial_fit_state; its counters advance on the device (the call can be captured).  A matrix whose g is not finite
+    stays as it is and records it (spatial_fit_records).  loss_in (device float [1]) is copied to loss_out[call] while call < len(loss_out)."""
+    if A.dim() not in (2, 3) or A.shape[-1] != A.shape[-2]:
+        raise NsdError(f"spatial_fit_step: A must be [C,C] or [n_mat,C,C], got {tuple(A.shape)}")
+    Cc, n_mat = int(A.shape[-1]), (1 if A.dim() == 2 else int(A.shape[0]))
+    if int(dW.numel()) != int(A.numel()) or (A0 is not None and int(A0.numel()) != int(A.numel())):
+        raise NsdError(f"spatial_fit_step: dW / A0 must hold {int(A.numel())} elements as A does")
+    if (loss_in is None) != (loss_out is None):
+        raise NsdError("spatial_fit_step: loss_in and loss_out go together")
+    fit = _lib.SpatialFitCfg(float(lr), float(beta1), float(beta2), float(eps), float(decay))
+    _call("nsd_spatial_fit_step", A.device, Cc, n_mat, _dev_f32(A, "A"), _dev_f32(A0, "A0"), _dev_f32(dW, "dW"), C.byref(fit),
+          _dev_typed(state, "spatial_fit_step: state", torch.uint8), _nbytes(state), _dev_f32(loss_in, "loss_in"),
+          _dev_f32(loss_out, "loss_out"), 0 if loss_out is None else int(loss_out.numel()), STREAM)
+
+
+def train_dx(spec: ModelSpec, flat: torch.Tensor, x: torch.Tensor, ws: torch.Tensor, logits: torch.Tensor, dx: torch.Tensor, *,
+             labels: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+             rrelu_slope: Optional[torch.Tensor] = None, residual: bool = False, loss_out: Optional[torch.Tensor] = None) -> None:
+    """The input gradient of the mean loss through a FROZEN model: nsd_lstm_head_train[_soft] -> nsd_lstm_bwd with dx -> nsd_loss_sum
+    (where loss_out, a device float [1], is given).  No dropout; rrelu_slope [B,F] are the explicit slopes (the eval slope for an
+    eval-mode pass).  The parameter-gradient slabs stay in the workspace unreduced: `flat` is read, never written.  Needs dx_path."""
+    B, T, _ = x.shape
+    if not dx_path(spec, B, T):
+        raise NsdError(f"train_dx: {spec} at batch {B} is outside nsd_dx_path (hidden size 48, 2 layers, <= 8 channels on the fast path)")
+    d = spec.dims(B, T)
+    flags = _lib.NSD_FLAG_TRAIN | (_lib.NSD_FLAG_RESIDUAL if residual else 0) | _extra_flags
+    pp = _dev_f32(flat, "params", (spec.param_count,))
+    xp, wsp, wsn, dev = _dev_f32(x, "x", (B, T, spec.C)), _dev_f32(ws, "workspace"), _nbytes(ws), x.device
+    sl, lp = _dev_f32(rrelu_slope, "rrelu_slope", (B, spec.F)), _dev_f32(logits, "logits", (B, spec.K))
+    scale = (1.0 / max(B, 1)) if scale is None else float(scale)
+    if targets is not None:
+        _call("nsd_lstm_head_train_soft", dev, C.byref(d), pp, xp, None, sl, None, None, _dev_f32(targets, "targets", (B, spec.K)), scale,
+              flags, wsp, wsn, lp, STREAM)
+    else:
+        _call("nsd_lstm_head_train", dev, C.byref(d), pp, xp, None, sl, None, _labels_ptr(labels), scale, flags, wsp, wsn, lp, STREAM)
+    _call("nsd_lstm_bwd", dev, C.byref(d), pp, xp, None, flags, wsp, wsn, _dev_f32(dx, "dx", (B, T, spec.C)), STREAM)
+    if loss_out is not None:
+        _call("nsd_loss_sum", dev, C.byref(d), wsp, wsn, _dev_f32(loss_out, "loss_out"), STREAM)
