@@ -476,8 +476,8 @@ int nsd_adam_step_clip(int64_t n, float *p, const float *g, float *m, float *v, 
  * nsd_grad_reduce(_adam) on its own; the kernels dispatch on the M*B trials of the launch as the single-model entry points do on B.
  * Where nsd_multi_path(d, M) == 0 every entry point returns NSD_E_INVALID before any launch (nsd_last_error says why), as it does for
  * M outside [1, NSD_MAX_MODELS], NULL pointers, mismatched rng probabilities, NSD_FLAG_RESIDUAL or a negative / overlapping
- * x_model_stride; a workspace smaller than nsd_multi_workspace_bytes gives NSD_E_WORKSPACE.  The residual extension and dx are not
- * offered here.
+ * x_model_stride; a workspace smaller than nsd_multi_workspace_bytes gives NSD_E_WORKSPACE.  The residual extension is not offered
+ * here; dx is, for frozen models (nsd_multi_train_bwd_dx, below).
  *   nsd_multi_path            1 for H = 48, L = 2, C <= 8, T <= 1024, F <= 64, K <= 8 and 1 <= M <= NSD_MAX_MODELS, else 0
  *   nsd_multi_train_fwd       forward + head + mean CE per model + head backward; logits [M*B][K]
  *   nsd_multi_train_bwd       BPTT into the per-workgroup slabs (same rng as the forward call)
@@ -508,6 +508,44 @@ int nsd_multi_loss_sum(const nsd_dims *d, int32_t M, const float *workspace, int
 int64_t nsd_multi_infer_scratch_bytes(const nsd_dims *d, int32_t M);
 int nsd_multi_infer(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,
                     float *logits, float *probs, void *scratch, void *stream);
+
+/*
+ * ---- input gradients of M frozen models: dL/dx through an ensemble ----
+ *
+ * Additive (NSD_VERSION stays 301; callers detect the feature by the symbol nsd_multi_dx_path).  The backward that follows
+ * nsd_multi_train_fwd[_soft] called with rng == NULL (eval-mode noise: no dropout, the eval RReLU slope), with dL/dx formed behind it.
+ * There is no rng parameter: the single-model nsd_lstm_bwd_rng forms no dx either, and the use is a frozen model (saliency, fitting an
+ * input-side matrix through the models: nsd_spatial_bwd).
+ *   nsd_multi_dx_path         1 where nsd_multi_path(d, M) and nsd_dx_path(d) both hold, else 0
+ *   nsd_multi_train_bwd_dx    nsd_multi_train_bwd(rng = NULL) + dx.  The parameter-gradient slabs are written exactly as
+ *                             nsd_multi_train_bwd writes them (the reduce entry points that follow stay valid).  Layer 0's saved gates are
+ *                             consumed -- da0 lands in their place: ONE backward per forward, as for nsd_lstm_bwd's dx.  The one-trial
+ *                             backward kernel runs whatever the batch; open attention records (the fused forward leaves them from 513
+ *                             trials in the launch on) are closed first, over all M*B trials.
+ *       reduce = NSD_DX_PER_MODEL   dx [M*B][T][C]: model m's rows hold the gradient of ITS mean loss with respect to ITS windows.  Every
+ *                             element is one fmaf chain over the 4H gate rows ascending, as nsd_lstm_bwd's dx.  Below 513 trials in
+ *                             the launch (M*B: the one- and two-trial forward kernels, which save the same bits) model m's rows are bit
+ *                             for bit nsd_lstm_bwd's dx for that model alone on the same windows.  From 513 trials the four-trial forward
+ *                             forms the gate products on the matrix pipe; a single model of B < 513 trials does not, the saved
+ *                             activations differ in their last bits and so does dx (both within the dx bound against the oracle).
+ *       reduce = NSD_DX_MEAN  dx [B][T][C], dx[r,c] = (((d_0 + d_1) + ...) + d_{M-1}) / (float)M with d_m model m's per-model value: a
+ *                             serial fp32 sum over m ascending, every addition rounded on its own, then one correctly rounded division
+ *                             (the convention of nsd_multi_stream_step's mean).  Requires x_model_stride == 0 (every model saw the same
+ *                             windows).  At M = 1 it is the per-model value, bitwise.
+ *                             M = 1 runs nsd_lstm_bwd with dx.
+ *   nsd_multi_loss_mean       out[0] (device) = the serial fp32 sum over m ascending of the values nsd_multi_loss_sum writes, divided by
+ *                             (float)M: the ensemble objective's numerator, e.g. nsd_spatial_fit_step's loss_in without a host read
+ * NSD_E_INVALID before any launch (nsd_last_error names the cause): NULL d / params / x / workspace / dx; a shape outside
+ * nsd_multi_dx_path; reduce outside {0, 1}; NSD_DX_MEAN with a non-zero x_model_stride; the refusals of the entry points above (residual
+ * flag, x_model_stride in (0, B*T*C)); B * T * H * 4 bytes per model reaching 2 GB (the one-trial kernel's 32-bit offsets).
+ * NSD_E_WORKSPACE as for nsd_multi_train_bwd.  B = 0 launches nothing.  No host synchronisation, no allocation: capturable on one stream.
+ */
+#define NSD_DX_PER_MODEL 0
+#define NSD_DX_MEAN      1
+int nsd_multi_dx_path(const nsd_dims *d, int32_t M);
+int nsd_multi_train_bwd_dx(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,
+                           float *workspace, int64_t workspace_bytes, float *dx, int32_t reduce, void *stream);
+int nsd_multi_loss_mean(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream);
 
 /*
  * ---- per-model step settings: a hyper-parameter grid (configurations x folds) in the launches one model uses ----

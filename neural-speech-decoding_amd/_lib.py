@@ -292,6 +292,10 @@ SYMBOLS = {
     "nsd_adam_step_clip": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _fp, _vp, C.c_int64, _vp]),
     "nsd_multi_grad_reduce_clip_adam": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _vp, C.c_int32, _vp, _vp, C.c_int64, _vp]),
     "nsd_multi_loss_sum": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
+    # input gradients of M frozen models (ensemble saliency, the shared spatial fit)
+    "nsd_multi_dx_path": (C.c_int, [_dp, C.c_int32]),
+    "nsd_multi_train_bwd_dx": (C.c_int, [_dp, C.c_int32, _fp, _fp, C.c_int64, C.c_uint32, _fp, C.c_int64, _fp, C.c_int32, _vp]),
+    "nsd_multi_loss_mean": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _fp, _vp]),
     # per-model step settings (hyper-parameter grids): the `_each` twins take M entries of nsd_aug / nsd_mix / nsd_opt
     "nsd_multi_hyper_path": (C.c_int, [_dp, C.c_int32]),
     "nsd_augment_each": (C.c_int, [_dp, C.c_int32, _fp, C.c_int64, _vp, _vp, _vp, C.c_uint32, _fp, _vp]),
@@ -376,6 +380,7 @@ SYMBOLS = {
     "nsd_spatial_fit_step": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, C.POINTER(SpatialFitCfg), _vp, C.c_int64, _fp, _fp, C.c_int32, _vp]),
 }
 NSD_MAX_MODELS = 32
+NSD_DX_PER_MODEL, NSD_DX_MEAN = 0, 1     # nsd_multi_train_bwd_dx's reduce
 
 
 class DiagGemm(C.Structure):
@@ -395,6 +400,7 @@ DIAG_SYMBOLS = {
     "nsd_seq_profile_read": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "nsd_diag_force_fwd48": (C.c_int, [C.c_int32]),
     "nsd_diag_force_bwd48": (C.c_int, [C.c_int32]),
+    "nsd_diag_dx": (C.c_int, [_fp, _fp, C.c_int64, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
 }
 DIAG_LIB_PATH = os.path.join(_HERE, "libnsd_hip_diag.so")
 

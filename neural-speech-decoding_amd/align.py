@@ -163,6 +163,20 @@ class SessionAlign:
         return W, ops.whiten_records(rec, G)
 
 
+def mean_over_models(d) -> np.ndarray:
+    """The numpy restatement of NSD_DX_MEAN and nsd_multi_loss_mean (include/nsd.h): d [M, ...] fp32 -> (((d[0] + d[1]) + ...) + d[M-1])
+    / float32(M) -- a serial fp32 sum over m ascending, every addition rounded on its own, then one division.  M = 1 returns d[0]'s
+    bits; a non-finite value stays in its own element."""
+    d = np.asarray(d, np.float32)
+    if d.ndim < 1 or d.shape[0] < 1:
+        raise ValueError(f"mean_over_models: expected [M >= 1, ...], got {d.shape}")
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = d[0].copy()
+        for m in range(1, d.shape[0]):
+            s = (s + d[m]).astype(np.float32)
+        return (s / np.float32(d.shape[0])).astype(np.float32)
+
+
 def check_spatial_fit(epochs, lr, decay, betas, eps) -> None:
     """The configuration nsd_spatial_fit_step would refuse, refused on the host with the field's name."""
     if isinstance(epochs, bool) or int(epochs) != epochs or int(epochs) < 1:
@@ -336,3 +350,162 @@ class SpatialFit:
             raise _lib.NsdError("SpatialFit: an epoch's gradient of the alignment matrix was not finite (a non-finite input step, or a loss "
                                 "that overflowed); those epochs left the matrix untouched.  reset() clears the status")
 
+
+class EnsembleSpatialFit(SpatialFit):
+    """SpatialFit for the object the ensemble decoders serve: ONE alignment matrix A [C,C] fitted through M frozen models at once, on
+    the objective (1/M) sum_m mean_n CE_m -- the members share one front end (member 0's gate -> prep -> apply -> A), so M matrices
+    fitted member by member could not be served.
+
+      models    a sequence of EEG_LSTM of one shape, or the ensemble an EnsemblePredictor holds (`predictor.model`), as HeadFit takes them
+      fit(trials, labels) -> losses [E]   member 0's gate -> prep -> apply runs over the trials ONCE, in eval mode.  Every epoch is
+                                          nsd_spatial_apply(v, A) -> nsd_multi_train_fwd[_soft] (x_model_stride = 0, rng NULL: eval-mode
+                                          noise) -> nsd_multi_train_bwd_dx(NSD_DX_MEAN) -> nsd_multi_loss_mean -> nsd_spatial_bwd ->
+                                          nsd_spatial_fit_step: the launches of a single model's epoch, whatever M.  dx is the serial
+                                          fp32 mean over the members (mean_over_models), losses[e] the same mean of the members' mean
+                                          losses before epoch e's update.  Epoch 1 runs eagerly, epochs 2 .. E replay one captured graph
+                                          (graph=, replayed, capture_error: SpatialFit's).  The members' parameters are read, never
+                                          written.  The fitted matrix is written to EVERY member with set_alignment; the record's
+                                          "spatial_fit" carries members = M and shared = True.
+      reset / status / check / epochs_done, continuation (2 + 3 epochs leave the bits of 5) and the refusals are SpatialFit's.
+
+    A0 is the matrix the members share at construction; members without the stage gain it at the identity (enable_alignment()),
+    members that hold different matrices are refused.  One member, or two copies of one model, leave SpatialFit's bits.
+    The defaults are SpatialFit's: choices, not measurements."""
+
+    def __init__(self, models, *, epochs: int = 50, lr: float = 1e-2, decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
+                 loss=None, graph: Optional[bool] = None):
+        import torch
+        from . import ops
+        from .lstm_eeg_model import EEG_LSTM
+        from .multimodel import _check_models
+        self._ensemble = None
+        if hasattr(models, "models") and hasattr(models, "params"):
+            self._ensemble, members = models, list(models.models)
+        elif isinstance(models, EEG_LSTM):
+            members = [models]
+        else:
+            try:
+                members = list(models)
+            except TypeError:
+                members = [models]
+        if not members or not all(isinstance(m, EEG_LSTM) for m in members):
+            raise _lib.NsdError("EnsembleSpatialFit: expected a sequence of EEG_LSTM, or the ensemble an EnsemblePredictor holds")
+        _check_models(members, "EnsembleSpatialFit")
+        check_spatial_fit(epochs, lr, decay, betas, eps)
+        sp, M = members[0].spec, len(members)
+        if not ops.multi_dx_path(sp, M):
+            raise _lib.NsdError(f"EnsembleSpatialFit: {M} models of shape {sp} are outside nsd_multi_dx_path -- the input gradient the fit "
+                                "descends along is formed for fp32 models of hidden size 48, 2 layers and <= 8 channels")
+        if loss is not None and loss.mixup:
+            raise _lib.NsdError("EnsembleSpatialFit: mixup is refused -- the inputs are frozen whole trials; label smoothing and class weights apply")
+        if loss is not None:
+            loss.check_classes(sp.K)
+        if members[0].align is not None:
+            for i, m in enumerate(members[1:], 1):
+                if not torch.equal(m.align_matrix.detach().cpu(), members[0].align_matrix.detach().cpu()):
+                    raise _lib.NsdError(f"EnsembleSpatialFit: member {i} holds another alignment matrix than member 0 -- the members share "
+                                        "one front end and the fit starts from ONE matrix; set_alignment the same matrix on all first")
+        flats = [m.flat_parameters() for m in members]
+        if not all(f.is_cuda for f in flats):
+            raise _lib.NsdError("EnsembleSpatialFit runs only on the MI355X HIP path: move the models to the GPU first; there is no CPU fallback")
+        if self._ensemble is not None:
+            self._ensemble.enable_alignment()
+        else:
+            for m in members:
+                m.enable_alignment()
+        self.members, self.model, self.spec, self.device = members, members[0], sp, flats[0].device
+        self.epochs, self.lr, self.decay, self.betas, self.eps = int(epochs), float(lr), float(decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.loss, self.graph = loss, graph
+        self.A0 = members[0].align_matrix.detach().to(self.device).clone().contiguous()
+        self.A = self.A0.clone()
+        self.state = ops.spatial_fit_state(sp.C, 1, self.device)
+        self.replayed = False
+        self.capture_error = None
+        self._losses = []
+
+    @property
+    def M(self) -> int:
+        return len(self.members)
+
+    def _params(self):
+        """[M,P]: the ensemble's own stacked buffer (what its decoders read), or a gathered copy of the members' vectors"""
+        import torch
+        if self._ensemble is not None:
+            return self._ensemble.params
+        return torch.stack([m.flat_parameters() for m in self.members]).contiguous()
+
+    def targets(self, labels, N: int):
+        """(int32 labels [M*N] on the device -- the same N for every member --, target rows [M*N,K] or None)"""
+        import torch
+        from . import ops
+        y = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+        y = y.to(device=self.device, dtype=torch.int32).reshape(-1)
+        if int(y.numel()) != N:
+            raise _lib.NsdError(f"EnsembleSpatialFit.fit: {int(y.numel())} labels for {N} trials")
+        y = y.repeat(self.M).contiguous()
+        return y, (None if self.loss is None else ops.target_rows(y, self.spec.K, self.M, self.loss))
+
+    def fit(self, trials, labels, epochs: Optional[int] = None):
+        import torch
+        from . import ops
+        sp, dev, M = self.spec, self.device, self.M
+        E = self.epochs if epochs is None else int(epochs)
+        if E < 1:
+            raise ValueError(f"EnsembleSpatialFit.fit: epochs {epochs!r} must be >= 1")
+        x = torch.as_tensor(trials, dtype=torch.float32).to(dev).contiguous()
+        if x.dim() != 3 or x.shape[-1] != sp.C or x.shape[0] < 1:
+            raise ValueError(f"EnsembleSpatialFit.fit: trials must be [N >= 1, T, {sp.C}], got {tuple(x.shape)}")
+        N, T = int(x.shape[0]), int(x.shape[1])
+        if not ops.multi_dx_path(sp, M, N, T):
+            raise _lib.NsdError(f"EnsembleSpatialFit.fit: {N} trials of {T} steps for {M} models of {sp} are outside nsd_multi_dx_path "
+                                "(hidden size 48, 2 layers, <= 8 channels, T <= 1024)")
+        with torch.no_grad():
+            y, q = self.targets(labels, N)
+            front = self.members[0]
+            was = front.training
+            front.eval()
+            try:
+                v = front._gate_prep(x)                        # the frozen inputs: the shared front end (member 0's), once
+            finally:
+                front.train(was)
+            v = v.clone() if v is x else v
+            params = self._params()
+            xa, dx = torch.empty_like(v), torch.empty_like(v)
+            ws = ops.multi_workspace(sp, M, N, T, dev)
+            logits = torch.empty((M * N, sp.K), dtype=torch.float32, device=dev)
+            dA = torch.empty((1, sp.C, sp.C), dtype=torch.float32, device=dev)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            scratch = torch.empty(N * sp.C * sp.C, dtype=torch.float64, device=dev)
+            loss1 = torch.zeros(1, dtype=torch.float32, device=dev)
+            losses = torch.full((E,), float("nan"), dtype=torch.float32, device=dev)
+            self.state[-8:].zero_()                            # the call counter indexes this call's losses
+
+            def epoch():
+                ops.spatial_apply(v, self.A, out=xa)
+                ops.multi_train_dx(sp, params, xa, ws, logits, dx, labels=y, targets=q, reduce="mean", loss_out=loss1)
+                ops.spatial_bwd(v, dx, self.A, want_dv=False, dW=dA, counts=counts, scratch=scratch)
+                ops.spatial_fit_step(self.A, dA, self.state, A0=self.A0, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                                     decay=self.decay, loss_in=loss1, loss_out=losses)
+
+            epoch()
+            g = self._capture(epoch) if E > 1 and self.graph is not False else None
+            self.replayed = g is not None
+            for _ in range(E - 1):
+                if g is not None:
+                    g.replay()
+                else:
+                    epoch()
+            mean = losses / float(N)
+            host = [float(l) for l in mean.cpu()]
+            self._losses.extend(host)
+            rec = dict(self.members[0].align_record or {})
+            rec["spatial_fit"] = dict(epochs=len(self._losses), lr=self.lr, decay=self.decay, loss_first=self._losses[0],
+                                      loss_last=self._losses[-1], status=self.status()[0], members=M, shared=True)
+            for m in self.members:
+                m.set_alignment(self.A, record=rec)
+        return mean
+
+    def check(self) -> None:
+        if any(self.status()):
+            raise _lib.NsdError("EnsembleSpatialFit: an epoch's gradient of the alignment matrix was not finite (a non-finite input step, or "
+                                "a loss that overflowed); those epochs left the matrix untouched.  reset() clears the status")

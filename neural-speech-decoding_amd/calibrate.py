@@ -167,7 +167,10 @@ def calibrate_predictor(predictor, trials, labels, align: bool = True, spatial: 
     spatial: None (nothing more is launched), or a dict of align.SpatialFit's keywords ({} for its defaults): the supervised fit of the
     alignment matrix through the frozen model, between the label-free whitening refit and the features -- the order is whitening refit
     (if align), SpatialFit, features, HeadFit.  A model without an alignment stage gains one at the identity.  The report gains
-    spatial_losses [E], spatial_status, and loss_spatial / acc_spatial: the calibration trials after the spatial stage alone."""
+    spatial_losses [E], spatial_status, and loss_spatial / acc_spatial: the calibration trials after the spatial stage alone.
+    An ensemble takes spatial=dict(shared=True, ...): ONE matrix is fitted through all members (align.EnsembleSpatialFit: the launches
+    of a single model's epoch, dx the serial mean over the members) and written to every member; without the key an ensemble is refused
+    before anything runs.  shared=True on a single model is SpatialFit."""
     x = np.stack([np.asarray(t, dtype=np.float32) for t in trials]) if not isinstance(trials, np.ndarray) else trials
     if x.ndim != 3:
         raise ValueError(f"calibrate: trials must be [N, T, C], got {x.shape}")
@@ -183,9 +186,12 @@ def calibrate_predictor(predictor, trials, labels, align: bool = True, spatial: 
         from .align import check_spatial_fit
         cfg = dict(epochs=50, lr=1e-2, decay=1e-2, betas=(0.9, 0.999), eps=1e-8)
         check_spatial_fit(**{k: spatial.get(k, d) for k, d in cfg.items()})
-        if hasattr(predictor.model, "models"):
-            raise NsdError("calibrate: spatial= for an ensemble is not offered -- the model-batched backward forms no input gradient and an "
-                           "ensemble's decoders share one alignment matrix; fit the members one by one (align.SpatialFit) and serve them apart")
+        if not isinstance(spatial.get("shared", False), bool):
+            raise ValueError(f"calibrate: spatial['shared'] {spatial['shared']!r} must be True or False")
+        if hasattr(predictor.model, "models") and not spatial.get("shared"):
+            raise NsdError("calibrate: spatial= for an ensemble needs the key shared=True -- an ensemble's decoders share one alignment "
+                           "matrix, so ONE matrix is fitted through all members (align.EnsembleSpatialFit); without the key nothing is "
+                           "fitted.  (Members fitted one by one with align.SpatialFit hold M matrices and have to be served apart)")
         if chunk_transform is not None:
             raise NsdError("calibrate: spatial= with chunk_transform= is not offered -- the fit runs the model's own front end over the "
                            "trials; give the model a CausalPrep")
@@ -207,8 +213,10 @@ def calibrate_predictor(predictor, trials, labels, align: bool = True, spatial: 
         before, _ = stream.push(x)
     spatial_report = {}
     if spatial is not None:
-        from .align import SpatialFit
-        sfit = SpatialFit(predictor.model, **dict(spatial))
+        from .align import EnsembleSpatialFit, SpatialFit
+        skw = {k: v for k, v in spatial.items() if k != "shared"}
+        # (shared=True on a single model is SpatialFit; an ensemble -- refused above without the key -- fits one matrix through all members)
+        sfit = EnsembleSpatialFit(predictor.model, **skw) if hasattr(predictor.model, "models") else SpatialFit(predictor.model, **skw)
         sl = sfit.fit(x, y)
         stream = predictor.open_stream(streams=N)              # a fresh decoder: it starts from the fitted matrix
         mid, _ = stream.push(x)
@@ -247,7 +255,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "calibration trials, label-free, before the read-out is fitted (without it the checkpoint's matrix stays)")
     ap.add_argument("--fit-spatial", action="store_true", help="fit the alignment matrix on the labelled calibration trials by gradient "
                     "descent through the frozen model (align.SpatialFit), behind --align's label-free refit and before the read-out is "
-                    "fitted; a checkpoint without nsd_align gains a matrix that starts at the identity; one --model only (an ensemble is refused)")
+                    "fitted; a checkpoint without nsd_align gains a matrix that starts at the identity; with several --model ONE matrix is fitted "
+                    "through all members (align.EnsembleSpatialFit) and every member's checkpoint carries it")
     ap.add_argument("--spatial-epochs", type=int, default=50, help="a choice, not tuned on held-out data")
     ap.add_argument("--spatial-lr", type=float, default=1e-2, help="a choice, not tuned on held-out data")
     ap.add_argument("--spatial-decay", type=float, default=1e-2, help="pull towards the matrix the fit starts from; a choice")
@@ -275,8 +284,6 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.calib_per_class < 1:
         ap.error("--calib-per-class must be at least 1")
-    if args.fit_spatial and len(args.model) > 1:
-        ap.error("--fit-spatial takes one --model: an ensemble's decoders share one alignment matrix")
     if not torch.cuda.is_available():
         print("calibrate: needs an MI355X (no CPU path)", file=sys.stderr)
         return 2
@@ -297,6 +304,8 @@ def main(argv=None) -> int:
     acc0 = held_out_accuracy()
     loss = Loss(label_smoothing=args.label_smoothing) if args.label_smoothing else None
     spatial = dict(epochs=args.spatial_epochs, lr=args.spatial_lr, decay=args.spatial_decay) if args.fit_spatial else None
+    if spatial is not None and len(args.model) > 1:
+        spatial["shared"] = True                              # an ensemble's decoders share one matrix: one fit through all members
     rep = pred.calibrate(ts.x[cal], ts.y[cal], spatial=spatial, epochs=args.epochs, lr=args.lr, weight_decay=args.weight_decay,
                          train=tuple(s for s in args.train.split(",") if s), head_dropout=args.head_dropout, loss=loss, seed=args.seed, align=args.align)
     acc1 = held_out_accuracy()

@@ -1101,6 +1101,52 @@ int nsd_multi_train_bwd(const nsd_dims *d, int32_t M, const float *params, const
     return nsd_lstm2_multi_bwd_launch(a, s, M, c.st);
 }
 
+// ---- the input gradient of M frozen models (eval-mode noise: the forward ran with rng == NULL) ----
+int nsd_multi_dx_path(const nsd_dims *d, int32_t M) { return nsd_multi_path(d, M) && nsd_dx_path(d) ? 1 : 0; }
+
+int nsd_multi_train_bwd_dx(const nsd_dims *d, int32_t M, const float *params, const float *x, int64_t x_model_stride, uint32_t flags,
+                           float *workspace, int64_t workspace_bytes, float *dx, int32_t reduce, void *stream) {
+    static const char *who = "multi_train_bwd_dx";
+    if (const int rc = multi_common(d, M, x_model_stride, flags, who)) return rc;
+    if (!params || !x || !workspace || !dx) { nsd_set_error("%s: null pointer (params, x, workspace and dx are required)", who); return NSD_E_INVALID; }
+    if (!nsd_multi_dx_path(d, M)) { nsd_set_error("%s: shape outside nsd_multi_dx_path (nsd_multi_path and nsd_dx_path)", who); return NSD_E_INVALID; }
+    if (reduce != NSD_DX_PER_MODEL && reduce != NSD_DX_MEAN) {
+        nsd_set_error("%s: reduce = %d: NSD_DX_PER_MODEL (0) or NSD_DX_MEAN (1)", who, reduce);
+        return NSD_E_INVALID;
+    }
+    if (reduce == NSD_DX_MEAN && x_model_stride != 0) {
+        nsd_set_error("%s: NSD_DX_MEAN with x_model_stride %lld: the mean over the models is that of ONE window set (x_model_stride = 0)", who,
+                      (long long)x_model_stride);
+        return NSD_E_INVALID;
+    }
+    // (only the one-trial backward kernel writes da0, and it addresses a model's saved rows with 32-bit offsets)
+    if ((int64_t)d->B * d->T * d->H * 4 >= 0x7fffffffLL) {
+        nsd_set_error("%s: B * T * H * 4 = %lld bytes per model reach 2 GB: the input gradient needs the one-trial backward kernel", who,
+                      (long long)d->B * d->T * d->H * 4);
+        return NSD_E_INVALID;
+    }
+    flags &= ~NSD_FLAG_MODEL_P;
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream)) return leave(rc);
+    if (M == 1) return lstm_bwd_impl(d, params, x, nullptr, nullptr, flags, workspace, workspace_bytes, dx, stream);
+    Lstm2BwdArgs a = build_lstm_bwd(c, params, x, flags);
+    a.da0_out = c.at(c.w.gact);                                     // (in place of layer 0's saved gates, as nsd_lstm_bwd's: [M*B][T][4H])
+    // the fused forward of >= X4_MIN_B trials left the attention records open: close those of all M*B trials (global trial indices)
+    if (const int rc = nsd_att_close_launch(a.hseq1, a.pooled, a.dpooled, c.at(c.w.adpack), a.dscore_out, a.hslabs, a.Ph, a.o_attn_w,
+                                            a.o_attn_b, M * d->B, d->T, d->H, c.st)) return rc;
+    if (const int rc = nsd_lstm2_multi_bwd_launch(a, model_split(d, x_model_stride), M, c.st)) return rc;
+    return nsd_multi_dx_launch(a.da0_out, params + c.pl.w_ih[0], c.pl.total, dx, (long)d->B * d->T, M, reduce == NSD_DX_MEAN, 4 * d->H, d->C, c.st);
+}
+
+int nsd_multi_loss_mean(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *out, void *stream) {
+    static const char *who = "multi_loss_mean";
+    if (const int rc = multi_check(d, M, who)) return rc;
+    if (!out) { nsd_set_error("%s: null pointer", who); return NSD_E_INVALID; }
+    Ctx c;
+    if (const int rc = bind_ws(&c, d, M, workspace, workspace_bytes, who, stream); rc < 0) return rc;
+    return nsd_loss_mean_launch(c.at(c.w.loss), d->B, M, out, who, c.st);
+}
+
 // (M = 1 goes through the single-model entry point, as the two above do)
 int nsd_multi_grad_reduce(const nsd_dims *d, int32_t M, const float *workspace, int64_t workspace_bytes, float *grads, void *stream) {
     static const char *who = "multi_grad_reduce";

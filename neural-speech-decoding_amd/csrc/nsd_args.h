@@ -252,6 +252,11 @@ int nsd_loss_sum_launch(const float *loss, int B, int M, bool per_model, float *
 // dx[r][c] = sum_k da0[r][k] * w_ih0[k][c]: r = (trial, step), k = gate * H + unit (nn.LSTM weight_ih_l0 is [4H][C] row-major)
 int nsd_dx_launch(const float *da0, const float *w_ih0, float *dx, long rows, int G4, int C, hipStream_t st);
 bool nsd_dx_ok(int G4, int C);            // the dx kernel's domain (C channels, 4H gate rows: W_ih0 staged in 64 KB of LDS)
+// the same for M models in one launch: da0 [M][rows][G4], model m's matrix at w_ih0 + m * P, C <= 8.  mean: dx [rows][C], the serial fp32
+// sum over m ascending / (float)M; else dx [M][rows][C], each model's rows bit for bit those of nsd_dx_launch
+int nsd_multi_dx_launch(const float *da0, const float *w_ih0, long P, float *dx, long rows, int M, bool mean, int G4, int C, hipStream_t st);
+// out[0] = the serial fp32 sum over m ascending of nsd_loss_sum_launch(per_model)'s M values / (float)M
+int nsd_loss_mean_launch(const float *loss, int B, int M, float *out, const char *who, hipStream_t st);
 // H = 48, input gradient requested: closes OPEN attention records (left by lstm2_fwd48x4 with defer_att) in front of lstm2_bwd48_kernel<1>
 int nsd_att_close_launch(const float *hseq1, const float *pooled, const float *dpooled, float *adpack, float *dscore, float *hslabs,
                          long Ph, long o_attn_w, long o_attn_b, int B, int T, int H, hipStream_t st);

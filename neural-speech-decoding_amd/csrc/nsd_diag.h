@@ -54,5 +54,10 @@ int nsd_diag_gemm_bf16(const nsd_diag_gemm *args, void *stream);
 // of [4H][N] floats, i < I <= N (seq_reduce_dw_kernel); b_ih[g*H + u] = b_hh[g*H + u] = sum_z part[z][4u + g] (seq_reduce_db_kernel).
 int nsd_diag_reduce_dw(const float *part, int32_t nparts, int32_t H, int32_t N, int32_t I, float *out, void *stream);
 int nsd_diag_reduce_db(const float *part, int32_t nparts, int32_t H, float *b_ih, float *b_hh, void *stream);
+// The input-gradient kernels alone on caller-made operands: da0 [M][rows][G4], model m's W_ih0 [G4][C] at w_ih0 + m * P.  mode 0: M calls
+// of the single-model launch into dx [M][rows][C]; 1: the model-batched launch, per model, into dx [M][rows][C]; 2: its mean over the
+// models (serial fp32 sum over m ascending / (float)M) into dx [rows][C].  tests/ tie 1 to 0 bit for bit; tools/ time the three.
+int nsd_diag_dx(const float *da0, const float *w_ih0, int64_t P, float *dx, int64_t rows, int32_t M, int32_t mode, int32_t G4, int32_t C,
+                void *stream);
 }
 #endif

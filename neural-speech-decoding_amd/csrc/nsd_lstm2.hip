@@ -513,6 +513,20 @@ extern "C" int nsd_diag_force_fwd48(int32_t nb) {
     return NSD_OK;
 }
 static int nsd_diag_forced_fwd48() { return g_force_fwd48; }
+// The dx kernels alone (nsd_misc.hip) on caller-made da0 [M][rows][4H] and parameters [M][P] (w_ih0: model 0's matrix): mode 0 = M calls of
+// nsd_dx_launch, model after model, into dx [M][rows][C] (the existing path); 1 / 2 = ONE nsd_multi_dx_launch, per model / the mean.
+extern "C" int nsd_diag_dx(const float *da0, const float *w_ih0, int64_t P, float *dx, int64_t rows, int32_t M, int32_t mode, int32_t G4,
+                           int32_t C, void *stream) {
+    if (!da0 || !w_ih0 || !dx || rows < 0 || M < 1 || M > NSD_MAX_MODELS || mode < 0 || mode > 2) {
+        nsd_set_error("nsd_diag_dx: null pointer, rows < 0, M outside [1, %d] or mode outside 0 .. 2", NSD_MAX_MODELS);
+        return NSD_E_INVALID;
+    }
+    if (mode != 0) return nsd_multi_dx_launch(da0, w_ih0, (long)P, dx, (long)rows, M, mode == 2, G4, C, (hipStream_t)stream);
+    for (int m = 0; m < M; ++m)
+        if (const int rc = nsd_dx_launch(da0 + (size_t)m * rows * G4, w_ih0 + (size_t)m * P, dx + (size_t)m * rows * C, (long)rows, G4, C,
+                                         (hipStream_t)stream)) return rc;
+    return NSD_OK;
+}
 #else
 static int nsd_diag_forced_fwd48() { return 0; }
 static int nsd_diag_forced_bwd48() { return 0; }

@@ -1076,10 +1076,10 @@ __global__ __launch_bounds__(NTHREADS) void lstm2_bwd48_multi_kernel(Lstm2BwdArg
 
 // The instantiation that serves nb trials per workgroup, or 0 with the error set.  The one-trial instantiation's dW waves address the saved
 // rows through buffer descriptors with 32-bit offsets (0x80000000 = "switched off"): a batch whose [B][T][H] arrays reach 2 GB takes the
-// two-trial instantiation (64-bit addresses; any grid).  Only the one-trial instantiation writes the input gradient.
-static int bwd48_domain(const Lstm2BwdArgs &a, int nb, bool models, const char *who) {
+// two-trial instantiation (64-bit addresses; any grid).  Only the one-trial instantiation writes the input gradient (its model-batched
+// twin too: a.B is the trials of one model there, and so is the 2 GB bound).
+static int bwd48_domain(const Lstm2BwdArgs &a, int nb, const char *who) {
     if (nb == 1 && (long)a.B * a.T * H * 4 >= 0x7fffffffL) nb = 2;
-    if (a.da0_out && models) { nsd_set_error("%s: no input gradient on the model-batched path", who); return 0; }
     if (a.da0_out && nb != 1) { nsd_set_error("%s: the input gradient needs the one-trial instantiation (B * T * H * 4 < 2 GB)", who); return 0; }
     if (nb != 1 && nb != 2) { nsd_set_error("%s: NB=%d not built (register / LDS budget)", who, nb); return 0; }
     return nb;
@@ -1087,7 +1087,7 @@ static int bwd48_domain(const Lstm2BwdArgs &a, int nb, bool models, const char *
 
 #if !NSD_MULTI_TU
 int nsd_lstm2_bwd48_launch(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t st) {
-    nb = bwd48_domain(a, nb, false, "lstm2_bwd48");
+    nb = bwd48_domain(a, nb, "lstm2_bwd48");
     if (nb == 0) return NSD_E_INVALID;
     if (nb == 1) hipLaunchKernelGGL((lstm2_bwd48_kernel<1>), dim3(grid), dim3(NTHREADS), 0, st, a);
     else         hipLaunchKernelGGL((lstm2_bwd48_kernel<2>), dim3(grid), dim3(NTHREADS), 0, st, a);
@@ -1097,7 +1097,7 @@ int nsd_lstm2_bwd48_launch(const Lstm2BwdArgs &a, int nb, int grid, hipStream_t 
 
 #else
 int nsd_lstm2_bwd48_multi_launch(const Lstm2BwdArgs &a, const ModelSplit &s, int M, int nb, hipStream_t st) {
-    nb = bwd48_domain(a, nb, true, "lstm2_bwd48 (models)");
+    nb = bwd48_domain(a, nb, "lstm2_bwd48 (models)");
     if (nb == 0) return NSD_E_INVALID;
     if (nb == 1) hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<1>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s);
     else         hipLaunchKernelGGL((lstm2_bwd48_multi_kernel<2>), dim3(M * s.G), dim3(NTHREADS), 0, st, a, s);

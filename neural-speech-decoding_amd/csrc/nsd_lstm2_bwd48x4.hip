@@ -697,7 +697,7 @@ __global__ __launch_bounds__(NTHR) void lstm2_bwd48x4_multi_kernel(Lstm2BwdArgs 
     __shared__ ModelView<Lstm2BwdArgs> a;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (tid == 0) a = model_view(a_in, s);
+    if (tid == 0) a = model_view<false>(a_in, s);
     __syncthreads();
     const int n_steps = ((a_in.T + 3 + XCH - 1) / XCH) * XCH;
     const int g = wave & 3, q = wave >> 2;

@@ -332,6 +332,83 @@ int nsd_dx_launch(const float *da0, const float *w_ih0, float *dx, long rows, in
     return NSD_OK;
 }
 
+// The model-batched twin (nsd_multi_train_bwd_dx): da0 [M][rows][G4], W_ih0 of model m at w_ih0 + m * P, all models in one launch.
+// Every output is the ONE fmaf chain over k ascending that dx_kernel forms, so a model's rows carry the bits nsd_dx_launch gives for it.
+// What differs is who walks it: a THREAD PER OUTPUT ELEMENT (row e / C, channel e % C) instead of a thread per row.  At calibration
+// shapes (60 trials x 625 steps) a thread per row leaves 30 workgroups whose lanes each run C chains of 4H steps behind their own
+// 768-byte row: 85 us per model measured for dx_kernel there (profiles/ensemble_spatial_fit.md).  Here the C lanes of a row read the
+// same 16 bytes of it (one request), their chains are independent, the matrix column of a lane is conflict-free in LDS (consecutive
+// lanes, consecutive words) and consecutive lanes store consecutive floats of dx.
+//   MEAN = false: blockIdx.y = model m; dx [M][rows][C].
+//   MEAN = true:  a thread walks the models in ascending order for its element, the workgroup stages one model's matrix at a time (never
+//                 all M), each finished chain joins a running sum -- (((d_0 + d_1) + ...) + d_{M-1}) / (float)M, every operation rounded on
+//                 its own, the convention of multi_stream_mean_kernel; dx [rows][C].
+template <bool MEAN>
+__global__ __launch_bounds__(256) void multi_dx_kernel(const float *da0, const float *w_ih0, long P, float *dx, long rows, int M, int G4, int C) {
+    extern __shared__ __align__(16) float wl[];                    // [G4][C]
+    const long e = (long)blockIdx.x * 256 + threadIdx.x, n = rows * C;
+    const long r = e / C;
+    const int c = (int)(e - r * C);
+    const int m0 = MEAN ? 0 : (int)blockIdx.y, m1 = MEAN ? M : m0 + 1;
+    float sum = 0.f;
+    for (int m = m0; m < m1; ++m) {
+        if (m > m0) __syncthreads();                               // (the matrix of model m - 1 is still being read)
+        const float *w = w_ih0 + (size_t)m * P;
+        for (int i = threadIdx.x; i < G4 * C; i += 256) wl[i] = w[i];
+        __syncthreads();
+        if (e >= n) continue;
+        const float4 *dr = reinterpret_cast<const float4 *>(da0 + ((size_t)m * rows + r) * G4);     // (G4 = 4H: 16-byte rows)
+        const float *wc = wl + c;
+        float acc = 0.f;
+#pragma unroll 4
+        for (int k4 = 0; k4 < G4 / 4; ++k4) {
+            const float4 q = dr[k4];
+            acc = fmaf(q.x, wc[(4 * k4 + 0) * C], acc);
+            acc = fmaf(q.y, wc[(4 * k4 + 1) * C], acc);
+            acc = fmaf(q.z, wc[(4 * k4 + 2) * C], acc);
+            acc = fmaf(q.w, wc[(4 * k4 + 3) * C], acc);
+        }
+        sum = m == m0 ? acc : sum + acc;
+    }
+    if (e >= n) return;
+    dx[(size_t)(MEAN ? 0 : m0) * n + e] = MEAN ? sum / (float)M : sum;
+}
+
+int nsd_multi_dx_launch(const float *da0, const float *w_ih0, long P, float *dx, long rows, int M, bool mean, int G4, int C, hipStream_t st) {
+    if (rows <= 0) return NSD_OK;
+    if (!nsd_dx_ok(G4, C) || (G4 & 3) || M < 1 || M > NSD_MAX_MODELS || rows * C > 0x7fffffffL * 256) {
+        nsd_set_error("multi_dx: C = %d, 4H = %d, M = %d, rows = %ld outside the kernel's domain", C, G4, M, rows);
+        return NSD_E_INVALID;
+    }
+    const unsigned gx = (unsigned)((rows * C + 255) / 256);
+    if (mean) hipLaunchKernelGGL(multi_dx_kernel<true>, dim3(gx), dim3(256), (size_t)G4 * C * 4, st, da0, w_ih0, P, dx, rows, M, G4, C);
+    else      hipLaunchKernelGGL(multi_dx_kernel<false>, dim3(gx, M), dim3(256), (size_t)G4 * C * 4, st, da0, w_ih0, P, dx, rows, M, G4, C);
+    NSD_CHECK_LAUNCH("multi_dx");
+    return NSD_OK;
+}
+
+// out[0] = (((s_0 + s_1) + ...) + s_{M-1}) / (float)M, s_m = model m's loss sum as loss_sum_kernel<true> forms it (nsd_multi_loss_mean)
+__global__ __launch_bounds__(256) void loss_mean_kernel(const float *loss, int B, int M, float *out) {
+    __shared__ float red[4];
+    float total = 0.f;
+    for (int m = 0; m < M; ++m) {
+        float s = 0.f;
+        for (int i = threadIdx.x; i < B; i += 256) s += loss[(size_t)m * B + i];
+        s = wave_sum(s);
+        __syncthreads();                                           // (red of model m - 1 has been read)
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+        __syncthreads();
+        const float sm = (red[0] + red[1]) + (red[2] + red[3]);
+        total = m == 0 ? sm : total + sm;
+    }
+    if (threadIdx.x == 0) out[0] = total / (float)M;
+}
+int nsd_loss_mean_launch(const float *loss, int B, int M, float *out, const char *who, hipStream_t st) {
+    hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(256), 0, st, loss, B, M, out);
+    NSD_CHECK_LAUNCH(who);
+    return NSD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Closing the attention records of an H = 48 batch in front of the one-trial backward kernel (the input gradient is requested).
 // lstm2_fwd48x4_kernel with the head fused leaves OPEN records {alpha_t, 0, 1, 0} when the four-trial backward kernel is to follow:

@@ -77,6 +77,8 @@ __device__ __forceinline__ ModelView<Lstm2FwdArgs> model_view(const Lstm2FwdArgs
     return v;
 }
 
+// DX (false in the four-trial kernel, which writes no da0: its code object stays what it was): the view moves da0_out as well
+template <bool DX = true>
 __device__ __forceinline__ ModelView<Lstm2BwdArgs> model_view(const Lstm2BwdArgs &a, const ModelSplit &s) {
     const int m = nsd_multi_detail::model_of_block(s);
     ModelView<Lstm2BwdArgs> v;
@@ -84,7 +86,8 @@ __device__ __forceinline__ ModelView<Lstm2BwdArgs> model_view(const Lstm2BwdArgs
     v.wg = (int)blockIdx.x - m * s.G;
     v.nwg = s.G;
     const size_t P = (size_t)s.P * m, b = (size_t)m * a.B, bt = b * a.T, bth = bt * 48;
-    // (every pointer but mask / da0_out -- null on the model-batched path -- is set by the host launcher)
+    // (every pointer but mask -- null on the model-batched path -- and da0_out -- null unless nsd_multi_train_bwd_dx asks for the input
+    // gradient -- is set by the host launcher)
     v.x = a.x + (size_t)s.x_stride * m;
     v.w_hh0 = a.w_hh0 + P; v.w_ih1 = a.w_ih1 + P; v.w_hh1 = a.w_hh1 + P; v.attn_w = a.attn_w + P;
     v.hseq0 = a.hseq0 + bth; v.hseq1 = a.hseq1 + bth; v.cseq0 = a.cseq0 + bth; v.cseq1 = a.cseq1 + bth;
@@ -93,6 +96,7 @@ __device__ __forceinline__ ModelView<Lstm2BwdArgs> model_view(const Lstm2BwdArgs
     v.dsc_pack = a.dsc_pack + 4 * bt; v.pooled = a.pooled + b * 48; v.dscore_out = a.dscore_out + bt;
     v.hslabs = a.hslabs + b * a.Ph;
     v.slabs = a.slabs + (size_t)m * s.G * a.slab_stride;
+    if constexpr (DX) v.da0_out = nsd_multi_detail::mv(a.da0_out, 4 * bth);
     if (s.rng_on) {
         const ModelSplit::Drop &r = s.drop[m];
         v.rng.seed = s.seed[m]; v.rng.base = s.base[m];

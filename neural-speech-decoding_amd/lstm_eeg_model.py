@@ -708,6 +708,8 @@ class SimplePredictor:
         opened afterwards start from the new matrix.  A fit that kept the identity (too few steps) leaves the matrix as it was.
         spatial=dict(...) (align.SpatialFit's keywords; {} for its defaults): behind that refit and in front of the features, the
         alignment matrix is fitted on the labelled trials by gradient descent through the frozen model; the report gains
-        spatial_losses, spatial_status, loss_spatial and acc_spatial.  spatial=None (default): nothing more is launched."""
+        spatial_losses, spatial_status, loss_spatial and acc_spatial.  spatial=None (default): nothing more is launched.  An
+        EnsemblePredictor takes spatial=dict(shared=True, ...): ONE matrix is fitted through all members (align.EnsembleSpatialFit)
+        and written to each; without the key an ensemble is refused before anything runs."""
         from .calibrate import calibrate_predictor
         return calibrate_predictor(self, trials, labels, align=align, **fit_kw)

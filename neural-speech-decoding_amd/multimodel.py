@@ -10,6 +10,7 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import ops
@@ -444,6 +445,14 @@ class _EnsembleModel:
         for m in self.models:
             m.set_alignment(W, record=record)
 
+    def enable_alignment(self, align=None):
+        """Every member gains the alignment stage at the identity where it has none (EEG_LSTM.enable_alignment), and so does the shared
+        front end: the start of align.EnsembleSpatialFit."""
+        for m in self.models:
+            m.enable_alignment(align if align is not None else self.models[0].align)
+        self.align = self.models[0].align
+        return self
+
     def predict_proba(self, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous().float()
         x = self.models[0]._front_end(x)
@@ -466,3 +475,31 @@ class EnsemblePredictor(SimplePredictor):
             models.append(SimplePredictor(p, sr, **{**kw, "preprocess": "identity"}).model)
         self.members = models
         self.model = _EnsembleModel(models)
+
+    def input_gradient(self, trials, labels, reduce: str = "mean") -> np.ndarray:
+        """The ensemble's saliency: dL/dx of the members' mean cross-entropy on `trials` [N,T,C] with `labels` [N] class indices, all
+        members in the launches one model uses (ops.multi_train_dx on the shared windows, eval-mode noise; the members are read, never
+        written).  reduce="mean" -> [N,T,C], the gradient of (1/M) sum_m mean_n CE_m (the serial fp32 mean over the members,
+        align.mean_over_models); "per_model" -> [M,N,T,C].  The gradient is with respect to what the LSTM is fed, behind the z-score or
+        the alignment matrix where the members have one; members with a signal-quality gate or a causal front end are refused, as
+        EEG_LSTM.forward refuses x.requires_grad through them."""
+        em = self.model
+        if em.gate is not None or em.prep is not None:
+            raise NsdError("EnsemblePredictor.input_gradient: dx through the signal-quality gate / the causal front end is not offered; "
+                           "differentiate gate- and prep-free members on the front end's output (ops.gate_step, ops.prep_step)")
+        x = torch.as_tensor(np.asarray(trials, dtype=np.float32)).to(self.gpu).contiguous()
+        sp, M = em.spec, len(em.models)
+        if x.dim() != 3 or x.shape[-1] != sp.C or x.shape[0] < 1:
+            raise ValueError(f"EnsemblePredictor.input_gradient: trials must be [N >= 1, T, {sp.C}], got {tuple(x.shape)}")
+        N, T = int(x.shape[0]), int(x.shape[1])
+        y = torch.as_tensor(np.asarray(labels).astype(np.int32).reshape(-1)).to(self.gpu)
+        if int(y.numel()) != N:
+            raise ValueError(f"EnsemblePredictor.input_gradient: {int(y.numel())} labels for {N} trials")
+        with torch.no_grad():
+            x = em.models[0]._front_end(x)
+            x = x.contiguous()
+            ws = ops.multi_workspace(sp, M, N, T, x.device)
+            logits = torch.empty((M * N, sp.K), dtype=torch.float32, device=x.device)
+            dx = torch.empty((N, T, sp.C) if reduce == "mean" else (M, N, T, sp.C), dtype=torch.float32, device=x.device)
+            ops.multi_train_dx(sp, em.params, x, ws, logits, dx, labels=y.repeat(M).contiguous(), reduce=reduce)
+        return dx.cpu().numpy()

@@ -1250,6 +1250,24 @@ def reduce_db_diag(part: torch.Tensor, nparts: int, H: int) -> Tuple[torch.Tenso
     return b_ih, b_hh
 
 
+DX_DIAG_MODES = {"single_calls": 0, "per_model": 1, "mean": 2}
+
+
+def dx_diag(spec: ModelSpec, da0: torch.Tensor, params: torch.Tensor, mode: str, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Diagnostic build only: the input-gradient kernels alone (nsd_diag_dx) on da0 [M,rows,4H] and params [M,P].  mode "single_calls": M
+    launches of the single-model kernel, one per model; "per_model": the model-batched kernel's one launch -> dx [M,rows,C] either way;
+    "mean": its serial mean over the models -> dx [rows,C]."""
+    if not _lib.diag_active():
+        raise NsdError("dx_diag: diagnostic build only: use `with _lib.diagnostic_library():`")
+    M, rows, G4 = (int(v) for v in da0.shape)
+    if G4 != 4 * spec.H or tuple(params.shape) != (M, spec.param_count):
+        raise NsdError(f"dx_diag: da0 must be [M, rows, {4 * spec.H}] and params [M, {spec.param_count}]")
+    dx = _out_f32(dx, (rows, spec.C) if mode == "mean" else (M, rows, spec.C), da0.device, "dx_diag: dx")
+    _call("nsd_diag_dx", da0.device, _dev_f32(da0, "da0"), params.data_ptr() + 4 * spec.offsets()["lstm.weight_ih_l0"], spec.param_count,
+          dx.data_ptr(), rows, M, DX_DIAG_MODES[mode], G4, spec.C, STREAM)
+    return dx
+
+
 # ---- sequence-batched path (nsd_seq_*): large hidden sizes, optional bidirectional, bf16 operands -------------------------
 def seq_workspace(spec: ModelSpec, B: int, T: int, device) -> torch.Tensor:
     d = spec.dims(B, T)
@@ -1511,6 +1529,60 @@ def multi_loss_sum(spec: ModelSpec, ws: torch.Tensor, M: int, B: int, T: int, ou
     d = spec.dims(B, T)
     _call("nsd_multi_loss_sum", ws.device, C.byref(d), int(M), ws.data_ptr(), _nbytes(ws), _dev_f32(out, "out", (M,)), STREAM)
     return out
+
+
+def multi_dx_path(spec: ModelSpec, M: int, B: int = 32, T: int = 1) -> bool:
+    """True where nsd_multi_train_bwd_dx forms the input gradient of M models of this shape (nsd_multi_path and nsd_dx_path)."""
+    d = spec.dims(B, T)
+    return bool(_lib.lib().nsd_multi_dx_path(C.byref(d), int(M)))
+
+
+DX_REDUCE = {"per_model": _lib.NSD_DX_PER_MODEL, "mean": _lib.NSD_DX_MEAN}
+
+
+def multi_loss_mean(spec: ModelSpec, ws: torch.Tensor, M: int, B: int, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[0] = the serial fp32 sum over m ascending of multi_loss_sum's M values / float32(M) (device float [1]: spatial_fit_step's
+    loss_in takes it without a host read)."""
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=ws.device)
+    d = spec.dims(B, T)
+    _call("nsd_multi_loss_mean", ws.device, C.byref(d), int(M), ws.data_ptr(), _nbytes(ws), _dev_f32(out, "out", (1,)), STREAM)
+    return out
+
+
+def multi_train_dx(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, ws: torch.Tensor, logits: torch.Tensor, dx: torch.Tensor, *,
+                   labels: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None, reduce: str = "mean",
+                   loss_out: Optional[torch.Tensor] = None) -> None:
+    """The model-batched twin of train_dx: the input gradient through M FROZEN models in the launches one model uses --
+    nsd_multi_train_fwd[_soft] (rng NULL: no dropout, the eval RReLU slope) -> nsd_multi_train_bwd_dx -> nsd_multi_loss_mean (where
+    loss_out, a device float [1], is given).  params [M,P] are read, never written; x [B,T,C] (shared) or [M,B,T,C]; labels [M*B] int32
+    or targets [M*B,K]; ws: ops.multi_workspace; logits [M*B,K].
+    reduce="per_model": dx [M,B,T,C], model m's slice the gradient of ITS mean loss with respect to ITS windows.
+    reduce="mean":      dx [B,T,C] = align.mean_over_models of those (shared windows only): the gradient of (1/M) sum_m mean_n CE_m.
+    The parameter-gradient slabs stay in the workspace unreduced.  Needs multi_dx_path."""
+    if reduce not in DX_REDUCE:
+        raise NsdError(f"multi_train_dx: reduce {reduce!r} must be 'mean' or 'per_model'")
+    M = int(params.shape[0])
+    B, T, stride = _multi_x(spec, x, M)
+    if not multi_dx_path(spec, M, B, T):
+        raise NsdError(f"multi_train_dx: {M} models of {spec} at batch {B} are outside nsd_multi_dx_path (hidden size 48, 2 layers, <= 8 "
+                       "channels, T <= 1024)")
+    if reduce == "mean" and stride != 0:
+        raise NsdError("multi_train_dx: reduce='mean' needs shared windows x [B,T,C] (the mean over the models is that of one window set)")
+    d = spec.dims(B, T)
+    dev = params.device
+    pp, xp = _dev_f32(params, "params", (M, spec.param_count)), _dev_f32(x, "x")
+    wsp, wsn, lp = _dev_f32(ws, "workspace"), _nbytes(ws), _dev_f32(logits, "logits", (M * B, spec.K))
+    dxp = _dev_f32(dx, "dx", (B, T, spec.C) if reduce == "mean" else (M, B, T, spec.C))
+    if targets is not None:
+        _call("nsd_multi_train_fwd_soft", dev, C.byref(d), M, pp, xp, stride, None, _dev_f32(targets, "targets", (M * B, spec.K)), 0, wsp, wsn, lp, STREAM)
+    else:
+        if labels is None or labels.numel() != M * B:
+            raise NsdError(f"multi_train_dx: labels must be contiguous int32 [M*B] = [{M * B}]")
+        _call("nsd_multi_train_fwd", dev, C.byref(d), M, pp, xp, stride, None, _labels_ptr(labels), 0, wsp, wsn, lp, STREAM)
+    _call("nsd_multi_train_bwd_dx", dev, C.byref(d), M, pp, xp, stride, 0, wsp, wsn, dxp, DX_REDUCE[reduce], STREAM)
+    if loss_out is not None:
+        _call("nsd_multi_loss_mean", dev, C.byref(d), M, wsp, wsn, _dev_f32(loss_out, "loss_out", (1,)), STREAM)
 
 
 def multi_infer(spec: ModelSpec, params: torch.Tensor, x: torch.Tensor, *, want_probs: bool = True, logits: Optional[torch.Tensor] = None,
