@@ -69,6 +69,10 @@ class StreamDecoder:
       alignment(slots=None)                  (matrices [n,C,C] numpy, records) in one copy
       set_alignment(slots, W)                write matrices; reset_alignment(slots): back to the model's matrix, accumulators zero
     reset() restarts a stream, not its session: the matrices and the accumulators stay.
+    state_dict() carries the session with the stream: the matrix table, the accumulators and the records of the last fits
+    (align_records), so alignment() of a restored decoder returns what the original's returns; a checkpoint written before the records
+    travelled loads with all-zero records ("never refitted").  align_accumulate's switch is configuration, not state: it does not
+    travel, and a restored decoder accumulates only once it is told to.
     """
 
     def __init__(self, model, streams: int = 1):
@@ -199,6 +203,7 @@ class StreamDecoder:
         if self.align is not None:
             sd["align_table"] = self.align_table.detach().cpu().clone()
             sd["cov_state"] = self.cov_state.detach().cpu().clone()
+            sd["align_records"] = self.align_records.detach().cpu().clone()
         return sd
 
     def _check_front_state(self, sd: dict, who: str):
@@ -211,9 +216,12 @@ class StreamDecoder:
         if ((at is None) != (self.align is None) or (cs is None) != (self.align is None)
                 or (at is not None and (tuple(at.shape) != tuple(self.align_table.shape) or tuple(cs.shape) != tuple(self.cov_state.shape)))):
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their session alignment's state")
-        return ps, gs, at, cs
+        ar = sd.get("align_records")                        # (a checkpoint from before the records travelled has none: zero records)
+        if ar is not None and (at is None or tuple(ar.shape) != tuple(self.align_records.shape)):
+            raise NsdError(f"{who}: the checkpoint and the decoder differ in their session alignment's records")
+        return ps, gs, at, cs, ar
 
-    def _load_front_state(self, ps, gs, at=None, cs=None) -> None:
+    def _load_front_state(self, ps, gs, at=None, cs=None, ar=None) -> None:
         if ps is not None:
             self.prep_state.copy_(ps.to(self.device, dtype=torch.float32))
         if gs is not None:
@@ -221,6 +229,10 @@ class StreamDecoder:
         if at is not None:
             self.align_table.copy_(at.to(self.device, dtype=torch.float32))
             self.cov_state.copy_(cs.to(self.device, dtype=torch.float64))
+            if ar is not None:
+                self.align_records.copy_(ar.to(self.device, dtype=torch.uint8))
+            else:
+                self.align_records.zero_()
 
     def quality(self, slots=None) -> dict:
         """What the signal-quality gate has seen per slot since its reset, read from its state in one copy: {"bad_fraction": [n, C]
@@ -238,11 +250,11 @@ class StreamDecoder:
         if not torch.is_tensor(slots):
             idx = [int(v) for v in np.asarray(slots).reshape(-1)]
             if any(v < 0 or v >= self.streams for v in idx) or len(set(idx)) != len(idx):
-                raise NsdError(f"StreamDecoder: slots {idx} must be distinct indices in [0, {self.streams})")
+                raise NsdError(f"{type(self).__name__}: slots {idx} must be distinct indices in [0, {self.streams})")
             slots = torch.tensor(idx, dtype=torch.int32)
         slots = slots.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
         if n is not None and int(slots.numel()) != n:
-            raise NsdError(f"StreamDecoder: {int(slots.numel())} slots for {n} streams")
+            raise NsdError(f"{type(self).__name__}: {int(slots.numel())} slots for {n} streams")
         return slots
 
     @torch.no_grad()
@@ -283,10 +295,11 @@ class StreamDecoder:
         return self._front_state_dict({"state": self.state.detach().cpu().clone(), "stride": int(self._layout.stride)})
 
     def load_state_dict(self, sd: dict) -> None:
+        who = f"{type(self).__name__}.load_state_dict"
         st = sd["state"]
         if tuple(st.shape) != tuple(self.state.shape) or int(sd.get("stride", st.shape[-1])) != int(self._layout.stride):
-            raise NsdError(f"StreamDecoder.load_state_dict: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
-        front = self._check_front_state(sd, "StreamDecoder.load_state_dict")
+            raise NsdError(f"{who}: state of shape {tuple(st.shape)} for a decoder of {tuple(self.state.shape)}")
+        front = self._check_front_state(sd, who)
         self.state.copy_(st.to(self.device, dtype=torch.float32))
         self._load_front_state(*front)
 

@@ -1,0 +1,399 @@
+"""The composed serving reference and its case table (tests/serve_ref.py), the parts that need no GPU:
+
+  * the table is a pairwise cover of its factors over the allowed combinations (by enumeration against refused()), every level appears
+    and the full-chain rows exist for all four decoders, eager and replayed;
+  * ServeRef does not depend on the cut; streamed it equals window_ref_windows bit for bit (the README's "a streamed model is fed
+    exactly what predict feeds it", stated on the reference); reset(slot) restarts that slot's stream and nothing else; a rejected step
+    costs a sliding decoder exactly the windows that contain it;
+  * in every row every enabled stage changes the bits of its input, the reference alone leaves the finite decisions the GPU rows count,
+    and a refit row's fit is a clean one (the assertions that condition the inputs);
+  * stream.py on the host with the launches replaced by recording stand-ins: the order of the calls in _front for every stage subset,
+    nsd_cov_step behind the gate's apply and in front of the spatial apply with the gate's mask, the slots reaching every stage, reset
+    touching neither matrices, records nor accumulators (and an ensemble's reset naming m*S + s), and the checkpoint's records."""
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+import nsd_amd
+from nsd_amd import ops
+from nsd_amd import stream as st_mod
+from tests import align_ref, gate_ref, window_ref
+from tests import serve_ref as sv
+
+IDS = [sv.case_id(c) for c in sv.CASES]
+SUBSETS = list(itertools.product((0, 1), repeat=3))                   # (gate, prep, align)
+
+
+# ---- the table --------------------------------------------------------------------------------------------------------------------
+def _pairs(c):
+    names = list(sv.FACTORS)
+    return {((a, c[a]), (b, c[b])) for i, a in enumerate(names) for b in names[i + 1:]}
+
+
+def test_the_table_covers_every_allowed_pair():
+    names = list(sv.FACTORS)
+    for f, levels in sv.FACTORS.items():
+        assert len(set(levels)) == len(levels), f
+    rows = [dict(zip(names, v)) for v in itertools.product(*sv.FACTORS.values())]
+    allowed = [r for r in rows if sv.refused(r) is None]
+    need = set().union(*(_pairs(r) for r in allowed))
+    table = [{f: getattr(c, f) for f in names} for c in sv.CASES]
+    for c, r in zip(sv.CASES, table):
+        assert all(r[f] in sv.FACTORS[f] for f in names) and sv.refused(r) is None, c
+    uncovered = sorted(need - set().union(*(_pairs(r) for r in table)), key=repr)
+    print(f"{len(sv.CASES)} rows; {len(allowed)} allowed combinations of {len(rows)}; {len(need)} allowed pairs; uncovered: {uncovered}")
+    assert uncovered == []
+    assert 25 <= len(sv.CASES) <= 35 and [c.id for c in sv.CASES] == list(range(len(sv.CASES)))
+    for f, levels in sv.FACTORS.items():
+        assert {r[f] for r in table} == set(levels), f
+    # every pair that no allowed combination holds is one a refusal names: refit / set-reset without align (2), pop without a gate (1),
+    # an event with one chunk (4), replay with another cut than the fixed one (4)
+    every = {((a, la), (b, lb)) for i, a in enumerate(names) for b in names[i + 1:] for la in sv.FACTORS[a] for lb in sv.FACTORS[b]}
+    assert len(every - need) == 11, sorted(every - need, key=repr)
+    # the two full-chain blocks: each decoder with gate + prep + align, eager and replayed
+    full = [c for c in sv.CASES if c.id in sv.FULL_CHAIN_IDS]
+    assert all((c.gate, c.prep, c.align) == (1, 1, 1) for c in full)
+    assert sorted((c.decoder, c.drive) for c in full) == sorted(itertools.product(sv.FACTORS["decoder"], sv.FACTORS["drive"]))
+    assert {c.event for c in full} == {"refit", "state_dict"} and {c.poison for c in full} == {"pop", "nan"}
+    # the cuts are the stated ones; the fixed one is off the hop grid
+    assert all(sum(v) == sv.T for v in sv.CUTS.values()) and sv.CUTS["14s"][0] % sv.HOP != 0
+    # the poison is neither first nor last in a chunk of any cut and lies in two windows, also when counted from a reset behind 12 samples
+    for cut in sv.CUTS.values():
+        ends = np.cumsum(cut)
+        assert sv.POISON_AT not in set(ends) | set(ends - 1) | {0}
+    inside = lambda t: [e for e in range(sv.WINDOW, sv.T + 1, sv.HOP) if e - sv.WINDOW <= t < e]
+    assert len(inside(sv.POISON_AT)) == 2 and len(inside(sv.POISON_AT - 12)) == 2
+
+
+# ---- the reference ----------------------------------------------------------------------------------------------------------------
+def _cfg(gate, prep, window=sv.WINDOW):
+    G = nsd_amd.SignalGate(**sv.GATE) if gate else None
+    P = nsd_amd.CausalPrep.design(**sv.PREP) if prep else None
+    return sv.ref_settings(G, P, window)
+
+
+def _run(x, cut, slots, W0, accumulate=True, **cfg):
+    ref = sv.ServeRef(sv.S, sv.C, align=W0, accumulate=accumulate, **cfg)
+    outs, masks, wins, t = [], [], [[] for _ in range(x.shape[0])], 0
+    for n in cut:
+        o, m, w = ref.push(x[:, t:t + n], slots)
+        t += n
+        outs.append(o)
+        masks.append(m)
+        for b, lst in enumerate(w or []):
+            wins[b] += [(e, p) for e, _, p in lst]
+    return ref, np.concatenate(outs, 1), None if masks[0] is None else np.concatenate(masks, 1), wins
+
+
+@pytest.mark.parametrize("gate,prep,align", SUBSETS)
+def test_the_reference_does_not_depend_on_the_cut(gate, prep, align):
+    rs = np.random.RandomState(7)
+    W0 = sv.matrices(1, rs)[0] if align else None
+    for poison in ("none", "nan") + (("pop",) if gate else ()):
+        x = sv.signal(sv.B, np.random.RandomState(8), poison)
+        whole = _run(x, [sv.T], sv.SLOT_LIST, W0, **_cfg(gate, prep))
+        for name, cut in sv.CUTS.items():
+            got = _run(x, cut, sv.SLOT_LIST, W0, **_cfg(gate, prep))
+            assert not sv._differs(got[1], whole[1]), (poison, name)
+            assert (got[2] is None and whole[2] is None) or np.array_equal(got[2], whole[2]), (poison, name)
+            assert got[3] == whole[3], (poison, name)
+            assert sv.same_snapshot(got[0].snapshot(), whole[0].snapshot()), (poison, name)
+        # the windows: every end of the hop grid from the first full window on, once
+        assert all([e for e, _ in w] == list(range(sv.WINDOW, sv.T + 1, sv.HOP)) for w in whole[3])
+        assert whole[0].n.tolist() == [sv.T, 0, sv.T, sv.T]                  # slots 3, 0, 2 were pushed
+
+
+@pytest.mark.parametrize("gate,prep,align", SUBSETS)
+def test_streamed_the_reference_equals_the_whole_window_chain(gate, prep, align):
+    rs = np.random.RandomState(9)
+    W0 = sv.matrices(1, rs)[0] if align else None
+    x = sv.signal(sv.B, rs)
+    cfg = _cfg(gate, prep, None)
+    trace = {}
+    want = sv.window_ref_windows(x, gate=cfg["gate"], prep=cfg["prep"], align=W0, trace=trace)
+    assert all(trace.values()) and list(trace) == [s for s in ("gate", "prep", "apply", "align") if dict(gate=gate, prep=prep, apply=gate, align=align)[s]]
+    assert np.isfinite(want).all() and (gate or prep or align or not sv._differs(want, x))
+    for name, cut in sv.CUTS.items():
+        for slots in (None, sv.SLOT_LIST):
+            _, got, _, _ = _run(x, cut, slots, W0, **cfg)
+            assert not sv._differs(got, want), (name, slots)
+
+
+def test_reset_restarts_that_slots_stream_and_nothing_else():
+    rs = np.random.RandomState(10)
+    W0, x = sv.matrices(1, rs)[0], sv.signal(sv.B, rs)
+    cfg = _cfg(1, 1)
+    cut = 40
+    ref = sv.ServeRef(sv.S, sv.C, align=W0, accumulate=True, **cfg)
+    twin = sv.ServeRef(sv.S, sv.C, align=W0, accumulate=True, **cfg)          # never reset
+    fresh = sv.ServeRef(sv.S, sv.C, align=W0, **cfg)                         # fed only the later samples
+    ref.push(x[:, :cut], sv.SLOT_LIST)
+    twin.push(x[:, :cut], sv.SLOT_LIST)
+    ref.set_alignment([0], sv.matrices(1, rs)[0])
+    twin.set_alignment([0], ref.table[0])
+    before = ref.snapshot()
+    ref.reset([0])                                                           # the slot of pushed stream 1
+    after = ref.snapshot()
+    for k in ("table", "sums", "counts", "records"):
+        assert sv.same_snapshot({k: before[k]}, {k: after[k]}), k
+    assert after["counts"][0, 0] > 0 and not np.array_equal(after["table"][0], W0)
+    assert ref.n.tolist() == [0, 0, cut, cut] and not ref.gate_rows()[0].any() and not ref.prep_rows()[0].any()
+    o1, m1, w1 = ref.push(x[:, cut:], sv.SLOT_LIST)
+    o2, m2, w2 = twin.push(x[:, cut:], sv.SLOT_LIST)
+    fresh.table[0] = ref.table[0]
+    o3, m3, w3 = fresh.push(x[1:2, cut:], [0])
+    assert not sv._differs(o1[1:2], o3) and np.array_equal(m1[1:2], m3) and w1[1] == w3[0]
+    assert sv._differs(o1[1:2], o2[1:2])                                     # the reset is visible in the bits
+    assert not sv._differs(o1[[0, 2]], o2[[0, 2]]) and np.array_equal(m1[[0, 2]], m2[[0, 2]]) and w1[0] == w2[0] and w1[2] == w2[2]
+    assert [e for e, _, _ in w1[1]] == [20, 30] and [e for e, _, _ in w1[0]] == [50, 60, 70]
+    for k in (3, 2):                                                         # the other slots' states: those of the twin
+        assert np.array_equal(ref.gate_rows()[k], twin.gate_rows()[k]) and np.array_equal(ref.prep_rows()[k], twin.prep_rows()[k])
+    assert np.array_equal(ref.sums[[3, 2]].view(np.uint64), twin.sums[[3, 2]].view(np.uint64))
+
+
+@pytest.mark.parametrize("prep,align", [(0, 0), (1, 0), (0, 1), (1, 1)])
+def test_a_rejected_step_costs_exactly_the_windows_that_contain_it(prep, align):
+    rs = np.random.RandomState(11)
+    W0 = sv.matrices(1, rs)[0] if align else None
+    x = sv.signal(sv.B, rs, "pop")
+    for name, cut in sv.CUTS.items():
+        ref, out, mask, wins = _run(x, cut, None, W0, **_cfg(1, prep))
+        nan_steps = np.isnan(out).any(2)
+        rejected = gate_ref.popcount(mask) > sv.GATE["max_bad"]
+        assert np.array_equal(nan_steps, rejected) and np.isnan(out[rejected]).all()
+        hold = sv.GATE["hold_samples"]
+        assert np.flatnonzero(rejected[sv.POISON_STREAM]).tolist() == list(range(sv.POISON_AT, sv.POISON_AT + hold + 1)) and not rejected[[0, 2]].any()
+        for b in range(sv.B):
+            want = [(e, bool(rejected[b, e - sv.WINDOW:e].any())) for _, e, _ in window_ref.completed(0, sv.T, sv.WINDOW, sv.HOP)]
+            assert wins[b] == want, (name, b)
+        assert [e for e, p in wins[sv.POISON_STREAM] if p] == [40, 50]
+        assert ref.quality()["rejected_fraction"].tolist() == [0.0, (hold + 1) / sv.T, 0.0, 0.0]
+
+
+@pytest.mark.parametrize("c", sv.CASES, ids=IDS)
+def test_in_every_row_every_enabled_stage_acts_and_the_decisions_the_gpu_rows_count_are_there(c):
+    inp = sv.inputs(c)
+    ref, chunks = sv.run_ref(c, inp=inp)
+    nB, slots = sv.pushed(c)
+    want = sv.expected_stages(c)
+    acted = {s: False for s in want}
+    for o, m, w, trace in chunks:
+        assert list(trace) == want and o.dtype == np.float32 and o.shape[0] == nB
+        assert (m is not None) == bool(c.gate) and (w is not None) == sv.sliding(c)
+        for s in want:
+            acted[s] |= bool(trace[s])
+    assert all(acted.values()), acted                    # (not in every chunk: a one-sample first chunk leaves prep's zeros as they are)
+    # what the GPU rows count: every unpoisoned stream ends with a finite decision; a sliding row has at least two finite windows
+    # per stream, and a poisoned stream loses some
+    x = np.concatenate([o for o, _, _, _ in chunks], 1)
+    for b in range(nB):
+        s = sv.slot_of(c, b)
+        hit = sv.poison_reaches_the_step(c) and b == sv.POISON_STREAM
+        if sv.sliding(c):
+            wins = [p for _, _, w, _ in chunks for _, _, p in w[b]]
+            assert wins.count(False) >= 2, (b, wins)
+            swallowed = c.event == "reset" and b == sv.EVENT_STREAM         # (a reset may come before any window with the step in it ends)
+            assert (True in wins) == hit or (hit and swallowed), (b, wins)
+        else:
+            recovered = c.event == "reset" and b == sv.EVENT_STREAM and sv.event_chunk(c) is not None and \
+                int(np.cumsum(sv.CUTS[c.cut])[sv.event_chunk(c)]) > sv.POISON_AT
+            assert ref.poisoned(s) == (hit and not recovered), (b, ref.nan_at[s])
+        assert np.isnan(x[b]).any() == hit
+    assert not any(ref.poisoned(sv.slot_of(c, b)) for b in range(nB) if b != sv.POISON_STREAM)
+    # the event stands between two chunks, and a refit is a fit: enough steps, no clipped eigenvalue
+    k = sv.event_chunk(c)
+    assert (k is None) == (c.event == "none") and (k is None or 0 <= k < len(sv.CUTS[c.cut]) - 1)
+    if c.event == "refit":
+        probe = sv.new_ref(c, inp)
+        t = 0
+        for n in sv.CUTS[c.cut][:k + 1]:
+            probe.push(inp["x"][:, t:t + n], slots)
+            t += n
+        one = sv.slot_of(c, sv.EVENT_STREAM)
+        W, recs = probe.host_fit([one], sv.ALIGN)
+        print(f"{sv.case_id(c)}: refit after {t} samples: {recs[0]}")
+        assert recs[0]["status"] == 0 and recs[0]["steps"] >= sv.ALIGN["min_steps"] and recs[0]["steps"] + recs[0]["skipped"] == t
+        assert not np.array_equal(W[0], inp["W0"]) and np.array_equal(ref.table[one], W[0]) and ref.records[one]["steps"] == recs[0]["steps"]
+        others = [s for s in range(sv.S) if s != one]
+        assert all(np.array_equal(ref.table[s], inp["W0"]) and ref.records[s] == sv.ZERO_RECORD for s in others)
+    if c.event == "set-reset":
+        one, other = sv.slot_of(c, sv.EVENT_STREAM), sv.slot_of(c, sv.SET_STREAM)
+        assert np.array_equal(ref.table[other], inp["Wset"]) and np.array_equal(ref.table[one], inp["W0"])
+        assert ref.counts[one, 0] + ref.counts[one, 1] == sv.T - int(np.cumsum(sv.CUTS[c.cut])[k])      # cleared at the event, counting since
+        assert ref.counts[other, 0] + ref.counts[other, 1] == sv.T
+    # the same row in one chunk per side of the event gives the same bits (the cut factor changes nothing the decoder may see)
+    if c.event == "none":
+        _, whole = sv.run_ref(c, cut=[sv.T], inp=inp)
+        assert not sv._differs(whole[0][0], x)
+
+
+# ---- stream.py on the host: recording stand-ins for the launches ---------------------------------------------------------------------
+def _ptr(t):
+    return t.untyped_storage().data_ptr()
+
+
+@pytest.fixture
+def launches(monkeypatch):
+    rec = []
+
+    def gate_step(x, gate, state=None, *, slots=None, out=None, mask=None):
+        rec.append(dict(name="gate_step", x=x, state=state, slots=slots, out=out, mask=mask))
+        return out, mask
+
+    def prep_step(x, prep, state=None, *, slots=None, out=None):
+        rec.append(dict(name="prep_step", x=x, state=state, slots=slots, out=out))
+        return out
+
+    def gate_apply(v, gate, mask, *, out=None, max_bad=None):
+        rec.append(dict(name="gate_apply", x=v, mask=mask, out=out, max_bad=max_bad))
+        return out
+
+    def cov_step(v, state=None, *, mask=None, slots=None, out=None):
+        rec.append(dict(name="cov_step", x=v, state=state, mask=mask, slots=slots))
+        return state
+
+    def spatial_apply(v, W, *, sel=None, out=None):
+        rec.append(dict(name="spatial_apply", x=v, W=W, sel=sel, out=out))
+        return out
+
+    def reset_of(name):
+        def f(*a):
+            rec.append(dict(name=name, args=a))
+        return f
+
+    for f in (gate_step, prep_step, gate_apply, cov_step, spatial_apply):
+        monkeypatch.setattr(ops, f.__name__, f)
+    for name in ("gate_reset", "prep_reset", "cov_reset", "stream_reset", "window_reset"):
+        monkeypatch.setattr(ops, name, reset_of(name))
+    monkeypatch.setattr(ops, "gate_state", lambda C_, S_, device=None: torch.ones((S_, 12)))
+    monkeypatch.setattr(ops, "prep_state", lambda C_, S_, device=None: torch.ones((S_, 10)))
+    monkeypatch.setattr(ops, "cov_state", lambda C_, S_, device=None: torch.ones((S_, C_ * C_ + 2), dtype=torch.float64))
+    return rec
+
+
+CLASSES = dict(stream=st_mod.StreamDecoder, **{"ens-stream": st_mod.EnsembleStreamDecoder, "sliding": st_mod.SlidingStreamDecoder,
+                                                "ens-sliding": st_mod.EnsembleSlidingStreamDecoder})
+
+
+def _stand_in(kind, gate, prep, align):
+    """a decoder of class `kind` on the host: what __init__ sets, without the model living on a GPU"""
+    cfg = dict(gate=nsd_amd.SignalGate(**sv.GATE) if gate else None, prep=nsd_amd.CausalPrep.design(**sv.PREP) if prep else None,
+               align=nsd_amd.SessionAlign(**sv.ALIGN) if align else None)
+    W = sv.matrices(1, np.random.RandomState(3))[0]
+    model = nsd_amd.EEG_LSTM(align_matrix=W if align else None, **cfg).eval()
+    dec = CLASSES[kind].__new__(CLASSES[kind])
+    dec.model, dec.streams, dec.device = model, sv.S, torch.device("cpu")
+    ens = kind.startswith("ens")
+    dec.members = [model, model] if ens else None
+    dec.state = torch.zeros((sv.M, sv.S, 16) if ens else (sv.S, 16))
+    if "sliding" in kind:
+        dec.window, dec.hop = sv.WINDOW, sv.HOP
+        dec._all = torch.arange(sv.S)
+        dec._last_end, dec._last_probs = torch.zeros(sv.S, dtype=torch.int64), torch.zeros((sv.S, sv.K))
+    dec._init_front(model)
+    return dec
+
+
+@pytest.mark.parametrize("gate,prep,align", SUBSETS)
+def test_front_calls_the_stages_in_the_documented_order_with_the_slots_and_the_mask(launches, gate, prep, align):
+    for accumulate in ((False, True) if align else (False,)):
+        for slots in (None, torch.tensor(sv.SLOT_LIST, dtype=torch.int32)):
+            del launches[:]
+            dec = _stand_in("stream", gate, prep, align)
+            if accumulate:
+                dec.align_accumulate(True)
+            x = torch.zeros((sv.B, 14, sv.C))
+            out = dec._front(x, slots)
+            want = (["gate_step"] if gate else []) + (["prep_step"] if prep else []) + (["gate_apply"] if gate else []) \
+                + (["cov_step"] if accumulate else []) + (["spatial_apply"] if align else [])
+            assert [r["name"] for r in launches] == want, (accumulate, slots)
+            by = {r["name"]: r for r in launches}
+            # the chain: each stage reads what the one in front of it wrote; nobody is handed the caller's chunk to write
+            src = x
+            for r in launches:
+                assert r["x"] is src or _ptr(r["x"]) == _ptr(src), r["name"]
+                if r["name"] != "cov_step":
+                    assert r["out"] is not None and _ptr(r["out"]) != _ptr(x), r["name"]
+                    src = r["out"]
+            assert (out is x) if not want else _ptr(out) == _ptr(src)
+            # the per-slot states are the decoder's own, and every stage with one is told the slots
+            if gate:
+                assert by["gate_step"]["state"] is dec.gate_state and by["gate_step"]["slots"] is slots
+                assert by["gate_apply"]["mask"] is by["gate_step"]["mask"] and by["gate_apply"]["max_bad"] is None      # the gate's own max_bad
+                assert by["gate_apply"]["mask"].dtype == torch.int32 and tuple(by["gate_apply"]["mask"].shape) == (sv.B, 14)
+            if prep:
+                assert by["prep_step"]["state"] is dec.prep_state and by["prep_step"]["slots"] is slots
+            if accumulate:                               # behind the gate's apply, in front of the spatial apply, under the gate's mask
+                cv = by["cov_step"]
+                assert cv["state"] is dec.cov_state and cv["slots"] is slots
+                assert cv["mask"] is (by["gate_step"]["mask"] if gate else None)
+                assert want.index("cov_step") == len(want) - 2 and (not gate or want.index("gate_apply") == want.index("cov_step") - 1)
+            if align:
+                sa = by["spatial_apply"]
+                assert sa["W"] is dec.align_table and tuple(sa["W"].shape) == (sv.S, sv.C, sv.C)
+                assert sa["sel"] is slots if slots is not None else sa["sel"].tolist() == list(range(sv.B))
+
+
+@pytest.mark.parametrize("kind", list(CLASSES))
+def test_reset_restarts_stream_gate_and_prep_and_leaves_the_session(launches, kind):
+    dec = _stand_in(kind, 1, 1, 1)
+    dec.align_records.fill_(7)
+    kept = [t.clone() for t in (dec.align_table, dec.align_records, dec.cov_state)]
+    for slots in (None, [3, 1]):
+        del launches[:]
+        dec.reset(slots)
+        names = [r["name"] for r in launches]
+        own = "window_reset" if "sliding" in kind else "stream_reset"
+        assert sorted(names) == sorted([own, "prep_reset", "gate_reset"]), names
+        by = {r["name"]: r["args"] for r in launches}
+        given = by[own][-1] if slots is not None else None
+        if slots is None:
+            assert by["prep_reset"][-1] is None and by["gate_reset"][-1] is None
+            assert len(by[own]) == (4 if "sliding" in kind else 2) or by[own][-1] is None
+        else:
+            assert by["prep_reset"][-1].tolist() == slots and by["gate_reset"][-1].tolist() == slots
+            assert by["prep_reset"][1] is dec.prep_state and by["gate_reset"][1] is dec.gate_state
+            # an ensemble's state is [M, S, .]: slot s of model m is row m*S + s of the flat state
+            assert given.tolist() == ([m * sv.S + s for m in range(sv.M) for s in slots] if kind.startswith("ens") else slots)
+        assert all(torch.equal(a, b) for a, b in zip(kept, (dec.align_table, dec.align_records, dec.cov_state)))
+
+
+def test_the_checkpoint_carries_the_records_and_an_old_one_loads_with_zero_records(launches):
+    a, b = _stand_in("stream", 1, 1, 1), _stand_in("stream", 1, 1, 1)
+    a.align_records.copy_(torch.arange(sv.S * ops.WHITEN_RECORD_BYTES, dtype=torch.int64).view(sv.S, -1).to(torch.uint8))
+    a.align_table.mul_(2.0)
+    a.prep_state.mul_(3.0)
+    a.gate_state.mul_(5.0)
+    a.cov_state.mul_(7.0)
+    a.align_accumulate(True)
+    sd = a._front_state_dict({})
+    assert set(sd) == {"prep_state", "gate_state", "align_table", "cov_state", "align_records"}
+    assert not any("accumulate" in k for k in sd)                             # the switch is configuration: it does not travel
+    b._load_front_state(*b._check_front_state(sd, "who"))
+    assert torch.equal(b.align_records, a.align_records) and torch.equal(b.align_table, a.align_table) and b._accumulate is False
+    assert torch.equal(b.prep_state, a.prep_state) and torch.equal(b.gate_state, a.gate_state) and torch.equal(b.cov_state, a.cov_state)
+    old = {k: v for k, v in sd.items() if k != "align_records"}
+    b._load_front_state(*b._check_front_state(old, "who"))
+    assert not b.align_records.any() and torch.equal(b.align_table, a.align_table)
+    with pytest.raises(nsd_amd.NsdError, match="who: .*session alignment's records"):
+        b._check_front_state(dict(sd, align_records=sd["align_records"][:2]), "who")
+    plain = _stand_in("stream", 1, 1, 0)
+    with pytest.raises(nsd_amd.NsdError, match="session alignment"):
+        plain._check_front_state(sd, "who")
+
+
+@pytest.mark.parametrize("kind", list(CLASSES))
+def test_refusals_name_the_class_that_raised(launches, kind):
+    dec = _stand_in(kind, 0, 0, 0)
+    name = CLASSES[kind].__name__
+    with pytest.raises(nsd_amd.NsdError, match=f"^{name}: slots .* must be distinct"):
+        dec._slots([1, 1])
+    with pytest.raises(nsd_amd.NsdError, match=f"^{name}: slots .* must be distinct"):
+        dec._slots([sv.S])
+    with pytest.raises(nsd_amd.NsdError, match=f"^{name}: 2 slots for 3 streams"):
+        dec._slots([0, 1], 3)
+    sd = dict(state=torch.zeros((1, 1)), window=sv.WINDOW, hop=sv.HOP)
+    with pytest.raises(nsd_amd.NsdError, match=f"^{name}.load_state_dict: state of shape"):
+        dec.load_state_dict(sd)
