@@ -1233,6 +1233,55 @@ int     nsd_spatial_fit_step(int32_t C, int32_t n_mat, float *A, const float *A0
                              void *state, int64_t state_bytes, const float *loss_in, float *loss_out, int32_t loss_cap, void *stream);
 
 /*
+ * ---- rate conversion: stage 0 of the front end (an EXTENSION: the reference's board and every recorded trial run at 125 Hz) ----
+ *
+ * A causal rational-ratio polyphase FIR resampler in front of nsd_gate_step / nsd_prep_step, so that a stream at any amplifier rate
+ * reaches the models at theirs without leaving the device.  out / in rate = L / M with gcd(L, M) = 1, P taps per phase; `taps` is a
+ * DEVICE table [L][P], caller-owned, taps[ph*P + i] = h[ph + i*L] of the prototype filter h (never read on the host: non-finite taps
+ * give non-finite outputs by the arithmetic).  For one stream, xa[k] = the k-th sample since the slot's reset and xa[k] = 0 for
+ * k < 0, c the channel.  Output j:
+ *   p = j*M (int64),  ph = p mod L,  q = p div L
+ *   acc = +0.0f;  for i = 0 .. P-1 ascending:  acc = acc + taps[ph*P + i] * xa[q - i]      (one rounded product, one rounded sum)
+ *   y[j] = acc
+ * Every fp32 operation rounds on its own (no FMA contraction).  Output j exists once q <= n_in - 1: a call that adds T samples to a
+ * slot holding n_in emits the outputs j in [ceil(n_in*L/M), ceil((n_in+T)*L/M)) -- floor(T*L/M) or ceil(T*L/M) of them, possibly none.
+ * Outputs and state are bit for bit a function of the samples alone -- not of the cut, the slot, the other streams of the call, the
+ * HIP stream or a graph replay.  A non-finite sample at index n makes exactly the outputs with q in [n, n+P-1] non-finite and nothing
+ * after them: unlike the IIR sections the stage heals itself.
+ *   nsd_resample_path          1 where nsd_resample_step covers C channels with r (r == NULL: C alone), else 0
+ *   nsd_resample_out_steps     ceil((n_in+T)*L/M) - ceil(n_in*L/M); <0 for a refused r, n_in < 0 or T < 0
+ *   nsd_resample_state_bytes   bytes of a state of S >= 1 slots (S * stride * 4); <0 for a refused C / r or S < 1
+ *   nsd_resample_state_layout  offsets inside a slot in 4-byte words: hist[P-1][C] (fp32, hist[k][c] = xa[n_in - (P-1) + k] -- linear
+ *                              and chronological, not a ring, so the state is a function of the samples alone), n_in (int64, 8-byte
+ *                              aligned), and the stride.  The layout depends on (C, P); P = 1 has no history.  A slot can be
+ *                              checkpointed and restored by copying its stride words.
+ *   nsd_resample_reset         as nsd_prep_reset: slots == NULL: all S slots; else the n slots of the DEVICE array slots[n] (indices
+ *                              outside [0, S) are skipped).  A reset slot is all zero.
+ *   nsd_resample_step          x [B,T,C], y [B,To,C] (of d only B, T, C are read).  y is written completely: row b holds its cnt[b]
+ *                              outputs and NaN behind them; cnt: DEVICE int32[B], or NULL.  y must not overlap x.
+ *     stream mode (state != NULL): To >= ceil(T*L/M); slots as in nsd_prep_step.  A slot index outside [0, S) is skipped: its row
+ *       of y is NaN, its cnt 0 and no state is touched; so is a slot whose n_in lies outside [0, 2^40] (one that was never reset).
+ *       No host synchronisation, no allocation: the call can be captured (the counts of a replay are those of the capture only
+ *       where M divides T*L -- L/M = 1/2 with even T, say; the kernel itself reads n_in from the slot on every run).
+ *     window mode (state == NULL, slots == NULL, S ignored): every trial starts from rest, To == ceil(T*L/M), nothing is stored.
+ * NSD_E_INVALID before any launch: NULL d / r / taps / x / y; C outside [1, 64]; T < 1; B < 0; L or M outside [1, 1024]; gcd(L, M)
+ * != 1; P outside [1, 256]; L*P > 65536; B > S or S < 1, a state that is not 8-byte aligned (stream mode); slots without a state; To
+ * below ceil(T*L/M) (stream mode) or different from it (window mode); T*C or To*64 beyond 2^31 - 1; y overlapping x.  NSD_E_WORKSPACE: state_bytes <
+ * nsd_resample_state_bytes(C, r, S).  B = 0 (n = 0) launches nothing.  Additive: NSD_VERSION stays 301, a caller detects the feature
+ * by the symbols.
+ */
+typedef struct nsd_resample { int32_t L, M, P; } nsd_resample;   /* out/in rate = L/M, gcd(L,M)=1; P taps per phase */
+typedef struct nsd_resample_layout { int64_t hist, n_in, stride; } nsd_resample_layout;  /* 4-byte words in a slot; depends on (C, P) */
+int     nsd_resample_path(int32_t C, const nsd_resample *r);
+int64_t nsd_resample_out_steps(const nsd_resample *r, int64_t n_in, int64_t T);
+int64_t nsd_resample_state_bytes(int32_t C, const nsd_resample *r, int32_t S);
+int     nsd_resample_state_layout(int32_t C, const nsd_resample *r, nsd_resample_layout *out);
+int     nsd_resample_reset(int32_t C, const nsd_resample *r, void *state, int64_t state_bytes, int32_t S,
+                           const int32_t *slots, int32_t n, void *stream);
+int     nsd_resample_step(const nsd_dims *d, const nsd_resample *r, const float *taps, const float *x, const int32_t *slots,
+                          void *state, int64_t state_bytes, int32_t S, float *y, int64_t To, int32_t *cnt, void *stream);
+
+/*
  * ---- sequence-batched path for large hidden sizes (BASELINE cfg3: H=256, K=5, B=1024 bf16; cfg5: bidirectional H=512) ----
  *
  * Building block, exported so that it can be tested and timed on its own: C[M,N] = A . B with bf16 operands (device

@@ -8,6 +8,7 @@ from .lstm_eeg_model import CLASS_NAMES, EEG_LSTM, IdentityPreProcessor, SimpleP
 from .multimodel import EnsemblePredictor, ModelBatchTrainer
 from .ops import Augment, Average, Crop, Loss, LrSchedule, ModelSpec, Sam
 from .prep import CausalPrep
+from .resample import Resample
 from .gate import SignalGate
 from .align import EnsembleSpatialFit, SessionAlign, SpatialFit
 from .calibrate import HeadFit
@@ -16,4 +17,4 @@ from .streaming_process import StreamingProcess
 from .tester import DEFAULT_MODEL, DEFAULT_SERIAL, TrialResult, run_trials
 
 __all__ = ["EEG_LSTM", "SimplePredictor", "CLASS_NAMES", "run_trials", "TrialResult", "StreamingProcess",
-           "ModelSpec", "Augment", "Average", "Crop", "Sam", "Loss", "LrSchedule", "CausalPrep", "SignalGate", "SessionAlign", "SpatialFit", "EnsembleSpatialFit", "HeadFit", "ModelBatchTrainer", "EnsemblePredictor", "StreamDecoder", "EnsembleStreamDecoder", "SlidingStreamDecoder", "EnsembleSlidingStreamDecoder", "PredictorStream", "PredictorSlidingStream", "NsdError", "IdentityPreProcessor", "resolve_reference_preprocessor", "build_library", "load_library", "DEFAULT_MODEL", "DEFAULT_SERIAL"]
+           "ModelSpec", "Augment", "Average", "Crop", "Sam", "Loss", "LrSchedule", "CausalPrep", "Resample", "SignalGate", "SessionAlign", "SpatialFit", "EnsembleSpatialFit", "HeadFit", "ModelBatchTrainer", "EnsemblePredictor", "StreamDecoder", "EnsembleStreamDecoder", "SlidingStreamDecoder", "EnsembleSlidingStreamDecoder", "PredictorStream", "PredictorSlidingStream", "NsdError", "IdentityPreProcessor", "resolve_reference_preprocessor", "build_library", "load_library", "DEFAULT_MODEL", "DEFAULT_SERIAL"]

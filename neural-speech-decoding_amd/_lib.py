@@ -160,6 +160,16 @@ class PrepLayout(C.Structure):
 NSD_PREP_MAX_SECTIONS, NSD_PREP_BASELINE, NSD_PREP_CAR = 4, 1, 2
 
 
+class Resample(C.Structure):
+    """nsd_resample of include/nsd.h: out / in rate = L / M, P taps per phase"""
+    _fields_ = [("L", C.c_int32), ("M", C.c_int32), ("P", C.c_int32)]
+
+
+class ResampleLayout(C.Structure):
+    """nsd_resample_layout of include/nsd.h: offsets inside one slot of a resample state, in 4-byte words"""
+    _fields_ = [(n, C.c_int64) for n in ("hist", "n_in", "stride")]
+
+
 class Gate(C.Structure):
     """nsd_gate of include/nsd.h"""
     _fields_ = [("rail", C.c_float), ("jump", C.c_float), ("flat_eps", C.c_float), ("flat_samples", C.c_int32), ("pp", C.c_float),
@@ -358,6 +368,13 @@ SYMBOLS = {
     "nsd_prep_state_layout": (C.c_int, [C.c_int32, C.POINTER(PrepLayout)]),
     "nsd_prep_reset": (C.c_int, [C.c_int32, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
     "nsd_prep_step": (C.c_int, [_dp, _vp, _fp, _ip, _vp, C.c_int64, C.c_int32, _fp, _vp]),
+    # rate conversion: stage 0 of the front end
+    "nsd_resample_path": (C.c_int, [C.c_int32, _vp]),
+    "nsd_resample_out_steps": (C.c_int64, [_vp, C.c_int64, C.c_int64]),
+    "nsd_resample_state_bytes": (C.c_int64, [C.c_int32, _vp, C.c_int32]),
+    "nsd_resample_state_layout": (C.c_int, [C.c_int32, _vp, C.POINTER(ResampleLayout)]),
+    "nsd_resample_reset": (C.c_int, [C.c_int32, _vp, _vp, C.c_int64, C.c_int32, _ip, C.c_int32, _vp]),
+    "nsd_resample_step": (C.c_int, [_dp, _vp, _fp, _fp, _ip, _vp, C.c_int64, C.c_int32, _fp, C.c_int64, _ip, _vp]),
     # signal-quality gate around the front end
     "nsd_gate_path": (C.c_int, [C.c_int32, _vp]),
     "nsd_gate_state_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

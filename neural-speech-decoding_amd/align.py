@@ -144,6 +144,8 @@ class SessionAlign:
         x = x.to(dev).contiguous()
         if x.dim() != 3 or x.shape[-1] != model.spec.C:
             raise ValueError(f"SessionAlign.fit: trials must be [N, T, {model.spec.C}], got {tuple(x.shape)}")
+        if getattr(model, "resample", None) is not None:    # stage 0 of the model's front end: the trials are at the amplifier's rate
+            x = ops.resample_trials(x, model.resample)
         G, group = 1, None
         if groups is not None:
             g = np.asarray(groups, np.int64).reshape(-1)
@@ -265,6 +267,8 @@ class SpatialFit:
         x = torch.as_tensor(trials, dtype=torch.float32).to(dev).contiguous()
         if x.dim() != 3 or x.shape[-1] != sp.C or x.shape[0] < 1:
             raise ValueError(f"SpatialFit.fit: trials must be [N >= 1, T, {sp.C}], got {tuple(x.shape)}")
+        if getattr(model, "resample", None) is not None:    # stage 0 of the model's front end: the trials are at the amplifier's rate
+            x = ops.resample_trials(x, model.resample)
         N, T = int(x.shape[0]), int(x.shape[1])
         if not ops.dx_path(sp, N, T):
             raise _lib.NsdError(f"SpatialFit.fit: {N} trials of {T} steps for {sp} are outside nsd_dx_path (hidden size 48, 2 layers, <= 8 channels)")
@@ -455,6 +459,8 @@ class EnsembleSpatialFit(SpatialFit):
         x = torch.as_tensor(trials, dtype=torch.float32).to(dev).contiguous()
         if x.dim() != 3 or x.shape[-1] != sp.C or x.shape[0] < 1:
             raise ValueError(f"EnsembleSpatialFit.fit: trials must be [N >= 1, T, {sp.C}], got {tuple(x.shape)}")
+        if getattr(self.members[0], "resample", None) is not None:    # stage 0 of the shared front end
+            x = ops.resample_trials(x, self.members[0].resample)
         N, T = int(x.shape[0]), int(x.shape[1])
         if not ops.multi_dx_path(sp, M, N, T):
             raise _lib.NsdError(f"EnsembleSpatialFit.fit: {N} trials of {T} steps for {M} models of {sp} are outside nsd_multi_dx_path "

@@ -242,6 +242,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--x-key", default="x", help="array of the windows inside a packed .npz")
     ap.add_argument("--classes", type=int, default=3, choices=(3, 5))
     ap.add_argument("--sr", type=int, default=125)
+    ap.add_argument("--model-rate", type=float, default=None, metavar="HZ",
+                    help="the rate the model decides at, where --sr is another and the checkpoint records no rate conversion: one is "
+                         "designed (Resample.design) and the trials go through it on the device (default: the checkpoint's, or none)")
     ap.add_argument("--T", type=int, default=625, help="samples per trial")
     ap.add_argument("--calib-per-class", type=int, default=4, help="cued trials per class the read-out is fitted on; the rest is held out")
     ap.add_argument("--seed", type=int, default=0, help="which trials calibrate (a seeded permutation per class)")
@@ -290,6 +293,8 @@ def main(argv=None) -> int:
     label_map = LABELS_5CLASS if args.classes == 5 else None
     ts = load_trials_npz(args.data, label_map, x_key=args.x_key) if args.data.endswith(".npz") else load_trials(args.data, label_map, samples=args.T)
     kw = dict(num_classes=args.classes, preprocess="identity")
+    if args.model_rate is not None:
+        kw["model_rate"] = args.model_rate
     pred = EnsemblePredictor(args.model, args.sr, **kw) if len(args.model) > 1 else SimplePredictor(args.model[0], args.sr, **kw)
     cal, held = split_calibration(ts.y, args.calib_per_class, args.seed)
     if len(cal) > 256:

@@ -1814,6 +1814,100 @@ int nsd_prep_step(const nsd_dims *d, const nsd_prep *p, const float *x, const in
     return nsd_prep_launch(a, (hipStream_t)stream);
 }
 
+// ---- rate conversion (nsd_resample_*, include/nsd.h; nsd_resample.hip) ----
+static int resample_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+// the configuration alone: ratio and taps per phase (who == NULL: a silent query)
+static bool resample_config(const nsd_resample *r, const char *who) {
+#define RS_REFUSE(...) do { if (who) nsd_set_error(__VA_ARGS__); return false; } while (0)
+    if (r->L < 1 || r->L > 1024 || r->M < 1 || r->M > 1024) RS_REFUSE("%s: L / M = %d / %d outside [1, 1024]", who, r->L, r->M);
+    if (resample_gcd(r->L, r->M) != 1) RS_REFUSE("%s: L / M = %d / %d is not reduced (gcd %d)", who, r->L, r->M, resample_gcd(r->L, r->M));
+    if (r->P < 1 || r->P > 256) RS_REFUSE("%s: P = %d taps per phase outside [1, 256]", who, r->P);
+    if ((int64_t)r->L * r->P > 65536) RS_REFUSE("%s: L * P = %lld taps, more than 65536", who, (long long)r->L * r->P);
+#undef RS_REFUSE
+    return true;
+}
+// the preamble of the entry points that touch a resample state: channels, configuration, slot count, size
+static int resample_enter(int32_t C, const nsd_resample *r, const char *who, const void *state, int64_t state_bytes, int32_t S) {
+    if (!prep_channels(C)) { nsd_set_error("%s: C = %d channels outside [1, 64]", who, C); return NSD_E_INVALID; }
+    if (!r) { nsd_set_error("%s: null configuration", who); return NSD_E_INVALID; }
+    if (!resample_config(r, who)) return NSD_E_INVALID;
+    if (!state) { nsd_set_error("%s: null state", who); return NSD_E_INVALID; }
+    if ((uintptr_t)state % 8) { nsd_set_error("%s: state is not 8-byte aligned (it holds an int64 count)", who); return NSD_E_INVALID; }
+    if (S < 1) { nsd_set_error("%s: S = %d slots", who, S); return NSD_E_INVALID; }
+    const int64_t need = (int64_t)S * rs_stride(C, r->P) * (int64_t)sizeof(float);
+    if (state_bytes < need) {
+        nsd_set_error("%s: state of %lld bytes is smaller than nsd_resample_state_bytes() = %lld", who, (long long)state_bytes, (long long)need);
+        return NSD_E_WORKSPACE;
+    }
+    return NSD_OK;
+}
+
+int nsd_resample_path(int32_t C, const nsd_resample *r) { return prep_channels(C) && (!r || resample_config(r, nullptr)) ? 1 : 0; }
+
+int64_t nsd_resample_out_steps(const nsd_resample *r, int64_t n_in, int64_t T) {
+    static const char *who = "resample_out_steps";
+    if (!r) { nsd_set_error("%s: null configuration", who); return NSD_E_INVALID; }
+    if (!resample_config(r, who)) return NSD_E_INVALID;
+    if (n_in < 0 || T < 0 || n_in > RS_MAX_N_IN || T > RS_MAX_N_IN) {
+        nsd_set_error("%s: n_in = %lld, T = %lld outside [0, 2^40]", who, (long long)n_in, (long long)T);
+        return NSD_E_INVALID;
+    }
+    return rs_ceil_div((n_in + T) * r->L, r->M) - rs_ceil_div(n_in * r->L, r->M);
+}
+
+int64_t nsd_resample_state_bytes(int32_t C, const nsd_resample *r, int32_t S) {
+    if (!prep_channels(C) || !r || S < 1) { nsd_set_error("resample_state_bytes: C outside [1, 64], null configuration, or S < 1"); return NSD_E_INVALID; }
+    if (!resample_config(r, "resample_state_bytes")) return NSD_E_INVALID;
+    return (int64_t)S * rs_stride(C, r->P) * (int64_t)sizeof(float);
+}
+
+int nsd_resample_state_layout(int32_t C, const nsd_resample *r, nsd_resample_layout *out) {
+    if (!prep_channels(C) || !r || !out) { nsd_set_error("resample_state_layout: C outside [1, 64], or null pointer"); return NSD_E_INVALID; }
+    if (!resample_config(r, "resample_state_layout")) return NSD_E_INVALID;
+    out->hist = RS_HIST; out->n_in = rs_n_in(C, r->P); out->stride = rs_stride(C, r->P);
+    return NSD_OK;
+}
+
+int nsd_resample_reset(int32_t C, const nsd_resample *r, void *state, int64_t state_bytes, int32_t S, const int32_t *slots, int32_t n,
+                       void *stream) {
+    static const char *who = "resample_reset";
+    if (const int rc = resample_enter(C, r, who, state, state_bytes, S)) return rc;
+    if (slots && (n < 0 || n > S)) { nsd_set_error("%s: n = %d slots of S = %d", who, n, S); return NSD_E_INVALID; }
+    const int count = slots ? n : S;
+    if (count == 0) return NSD_OK;
+    return nsd_resample_reset_launch((float *)state, rs_stride(C, r->P), S, slots, count, (hipStream_t)stream);
+}
+
+int nsd_resample_step(const nsd_dims *d, const nsd_resample *r, const float *taps, const float *x, const int32_t *slots, void *state,
+                      int64_t state_bytes, int32_t S, float *y, int64_t To, int32_t *cnt, void *stream) {
+    static const char *who = "resample_step";
+    if (!d || !r || !taps || !x || !y) { nsd_set_error("%s: null pointer (d, r, taps, x, y)", who); return NSD_E_INVALID; }
+    if (!prep_channels(d->C)) { nsd_set_error("%s: C = %d channels outside [1, 64]", who, d->C); return NSD_E_INVALID; }
+    if (d->T < 1 || d->B < 0) { nsd_set_error("%s: shape B=%d T=%d (B >= 0, T >= 1)", who, d->B, d->T); return NSD_E_INVALID; }
+    if ((int64_t)d->T * d->C > 0x7fffffff) { nsd_set_error("%s: T * C = %lld values per stream in one call", who, (long long)d->T * d->C); return NSD_E_INVALID; }
+    if (!resample_config(r, who)) return NSD_E_INVALID;
+    if (slots && !state) { nsd_set_error("%s: slots without a state (window mode takes neither)", who); return NSD_E_INVALID; }
+    if (state) {
+        if (const int rc = resample_enter(d->C, r, who, state, state_bytes, S)) return rc;
+        if (d->B > S) { nsd_set_error("%s: B = %d streams, S = %d slots", who, d->B, S); return NSD_E_INVALID; }
+    }
+    const int64_t most = rs_ceil_div((int64_t)d->T * r->L, r->M);
+    if (state ? To < most : To != most) {
+        nsd_set_error("%s: To = %lld rows of y, ceil(T * L / M) = %lld (stream mode: at least; window mode: exactly)", who, (long long)To, (long long)most);
+        return NSD_E_INVALID;
+    }
+    if (To > 0x7fffffff / 64) { nsd_set_error("%s: To = %lld rows of y in one call", who, (long long)To); return NSD_E_INVALID; }
+    const int64_t nx = (int64_t)d->B * d->T * d->C, ny = (int64_t)d->B * To * d->C;
+    if (x < y + ny && y < x + nx) { nsd_set_error("%s: y overlaps x", who); return NSD_E_INVALID; }
+    if (d->B == 0) return NSD_OK;
+    ResampleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.y = y; a.taps = taps; a.slots = slots; a.state = (float *)state; a.cnt = cnt; a.To = To;
+    a.B = d->B; a.T = d->T; a.C = d->C; a.S = state ? S : 0;
+    a.L = r->L; a.M = r->M; a.P = r->P;
+    return nsd_resample_launch(a, (hipStream_t)stream);
+}
+
 // ---- signal-quality gate (nsd_gate_*, include/nsd.h; nsd_gate.hip) ----
 static bool gate_channels(int32_t C) { return C >= 1 && C <= 32; }
 // the configuration alone (who == NULL: a silent query)

@@ -369,6 +369,29 @@ struct CausalPrepArgs {
 int nsd_prep_launch(const CausalPrepArgs &a, hipStream_t st);
 int nsd_prep_reset_launch(float *state, int C, int S, const int32_t *slots, int n, hipStream_t st);
 
+// rate conversion (nsd_resample_* of nsd.h; nsd_resample.hip).  One slot of the caller's state in 4-byte words -- the public layout
+// nsd_resample_state_layout reports; it depends on (C, P): hist[P-1][C] fp32, then the int64 n_in
+constexpr int RS_HIST = 0;
+constexpr int RS_TI = 256;                   // input samples staged through LDS at once (with the P - 1 in front of them)
+constexpr int RS_GRID_CAP = 1024;            // workgroups of a launch; larger calls walk their work units grid-stride
+constexpr int RS_TAPS_LDS = 768;             // the tap table [L][P] lives in LDS up to this many floats, else it is read through the caches
+constexpr long long RS_MAX_N_IN = 1LL << 40; // a slot's n_in beyond it (or below 0) was never reset: the slot is skipped
+__host__ __device__ constexpr int rs_n_in(int C, int P) { return ((P - 1) * C + 1) & ~1; }   // int64: 8-byte aligned
+__host__ __device__ constexpr int rs_stride(int C, int P) { return (rs_n_in(C, P) + 2 + 3) & ~3; }
+__host__ __device__ constexpr long long rs_ceil_div(long long a, long long b) { return (a + b - 1) / b; }   // a >= 0, b > 0
+struct ResampleArgs {
+    const float *x; float *y;                // [B,T,C], [B,To,C]; no overlap
+    const float *taps;                       // [L][P]
+    const int32_t *slots;                    // null: stream b lives in slot b
+    float *state;                            // null: window mode (every trial from rest, nothing stored)
+    int32_t *cnt;                            // null, or [B]
+    long long To;
+    int B, T, C, S;
+    int L, M, P;
+};
+int nsd_resample_launch(const ResampleArgs &a, hipStream_t st);
+int nsd_resample_reset_launch(float *state, int stride, int S, const int32_t *slots, int n, hipStream_t st);
+
 // signal-quality gate (nsd_gate_* of nsd.h; nsd_gate.hip).  One slot of the caller's state in 4-byte words -- the public layout
 // nsd_gate_state_layout reports; it depends on C alone.  prev / held / ring are fp32, run / hang int32, bad / rejected / steps int64
 constexpr int GATE_SPAN = NSD_GATE_MAX_SPAN;                          // rows of the ring, the longest peak-to-peak span

@@ -118,7 +118,7 @@ def main(argv=None) -> int:
     from .ops import Augment, Crop, Loss
     from .prep import CausalPrep
     from .train import (average_for, concurrent_epoch, concurrent_runs, crop_for, drop_bad_trials, early_stop_settings, evaluate, evaluate_cropped,
-                        align_for, fit_alignment, gate_for, loss_for,
+                        align_for, fit_alignment, gate_for, loss_for, resample_for, resample_loaded,
                         padded_parts, parse_class_weights, sam_for, schedule_for, selection_text)
 
     ap = build_parser()
@@ -169,6 +169,10 @@ def main(argv=None) -> int:
         ap.error(str(e))
     if align is not None and args.normalize:
         ap.error("--align with --normalize: the whole-window z-score would undo the whitening channel by channel")
+    try:
+        resample = resample_for(args)
+    except ValueError as e:
+        ap.error(str(e))
 
     # every configuration as the options `train` would see, checked before anything runs
     cfg_args, augments = [], []
@@ -211,6 +215,10 @@ def main(argv=None) -> int:
         if ts.x.shape[1] != args.T:
             ap.error(f"--T {args.T} but the trials have {ts.x.shape[1]} samples")
         x_np, y_np = ts.x, ts.y
+    if resample is not None:             # (as train: the runs see trials at the models' rate; --T counts the recorded samples)
+        x_np = resample_loaded(x_np, resample, dev)
+        if max(a.max_shift for a in augments) >= x_np.shape[1]:
+            ap.error(f"aug_shift must be smaller than the {x_np.shape[1]} samples of a trial at --model-rate")
     x_np, y_np = drop_bad_trials(x_np, y_np, gate, args.gate_drop_trials, "grid")
     try:
         runs = concurrent_runs(y_np, args.kfold, args.kfold_seeds, args.seed, args.batch, es["inner_fraction"] if es else None)

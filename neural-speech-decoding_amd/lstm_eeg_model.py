@@ -26,6 +26,7 @@ from ._lib import NsdError
 from .gate import SignalGate
 from .align import SessionAlign
 from .prep import CausalPrep
+from .resample import Resample
 
 CLASS_NAMES = ["Food", "Water", "BG-Noise"]   # verbatim from lstm_eeg_model.py:11
 
@@ -197,6 +198,12 @@ class EEG_LSTM(nn.Module):
       align_grad     True: x.requires_grad differentiates through the alignment stage (ops.spatial_apply as an autograd node,
                      nsd_spatial_bwd behind it: x.grad = W^T . dL/d(aligned x), where the kernels form dx at all).  False (default):
                      asking for an input gradient through align= is refused, as through gate= and prep=, which stay refused.
+      resample       a Resample: rate conversion as stage 0 of the front end (resample -> gate -> prep -> apply -> align -> LSTM;
+                     nsd_resample_step in window mode: every trial from rest).  The caller's windows are at the amplifier's rate;
+                     everything behind the stage counts samples at the model's rate -- the gate's spans, the sections' corners,
+                     window / hop of crops and sliding decoders, quality().  The gate's rail and jump detectors therefore see
+                     filtered samples, not the amplifier's.  Not together with normalize (the z-score would be taken over the
+                     filter's start-up); no input gradient is offered through it.
       crop           an ops.Crop: the window the model was (or is being) trained on by cropped training (Trainer(crop=)).  It changes
                      nothing in forward(); it travels with the model and its checkpoints so that predict_trials(), SimplePredictor and
                      open_stream() know the trained window.
@@ -205,8 +212,17 @@ class EEG_LSTM(nn.Module):
     def __init__(self, input_size=8, hidden_size=48, num_layers=2, num_classes=3, dropout=0.60, *,
                  residual: bool = False, normalize: bool = False, bidirectional: bool = False, precision: str = "fp32",
                  prep: Optional[CausalPrep] = None, crop: Optional["ops.Crop"] = None, gate: Optional[SignalGate] = None,
-                 align: Optional[SessionAlign] = None, align_matrix=None, align_grad: bool = False):
+                 align: Optional[SessionAlign] = None, align_matrix=None, align_grad: bool = False,
+                 resample: Optional[Resample] = None):
         super().__init__()
+        if resample is not None and not isinstance(resample, Resample):
+            raise ValueError(f"resample={resample!r}: expected a Resample")
+        if resample is not None and normalize:
+            raise ValueError("resample together with normalize=True: the whole-window z-score would be taken over the filter's start-up "
+                             "(CausalPrep.design(zscore_seconds=...) is its running form behind the rate conversion)")
+        if resample is not None and not 1 <= input_size <= 64:
+            raise ValueError(f"resample: the rate conversion covers 1 .. 64 channels, input_size = {input_size}")
+        self.resample = resample
         self.align_grad = bool(align_grad)
         if align is not None and not isinstance(align, SessionAlign):
             raise ValueError(f"align={align!r}: expected a SessionAlign")
@@ -306,7 +322,7 @@ class EEG_LSTM(nn.Module):
             raise NsdError(f"EEG_LSTM.view_of: row must be a contiguous float32 vector of {sp.param_count} elements")
         twin = EEG_LSTM(sp.C, sp.H, sp.L, sp.K, self.head_dropout_p, residual=self.residual, normalize=self.normalize,
                         bidirectional=sp.D == 2, precision=self.precision, prep=self.prep, crop=self.crop, gate=self.gate, align=self.align,
-                        align_grad=self.align_grad)
+                        align_grad=self.align_grad, resample=self.resample)
         if self.align is not None:
             twin.align_matrix, twin.align_record = self.align_matrix, self.align_record   # (shared: the twin follows a later set_alignment)
         offs = sp.offsets()
@@ -352,6 +368,9 @@ class EEG_LSTM(nn.Module):
     def _front_end(self, x: torch.Tensor) -> torch.Tensor:
         """What stands between the caller's window and the LSTM: the z-score (normalize), the signal-quality gate around the causal
         front end (gate -> prep -> apply), or nothing."""
+        if self.resample is not None and x.requires_grad and torch.is_grad_enabled():
+            raise NsdError("EEG_LSTM(resample=...): dx through the rate conversion is not offered -- x.requires_grad would get no "
+                           "gradient; detach x, or differentiate a resample-free model on ops.resample_trials(x, resample)")
         if self.gate is not None and x.requires_grad and torch.is_grad_enabled():
             raise NsdError("EEG_LSTM(gate=...): dx through the signal-quality gate is not offered -- x.requires_grad would get no "
                            "gradient; detach x, or differentiate a gate-free model on the gated windows (ops.gate_step, ops.gate_apply)")
@@ -363,7 +382,7 @@ class EEG_LSTM(nn.Module):
             raise NsdError("EEG_LSTM(align=...): dx through the session alignment is not offered -- x.requires_grad would get no "
                            "gradient; detach x, build the model with align_grad=True, or differentiate an align-free model on "
                            "ops.spatial_apply(x, W)")
-        if self.gate is not None or self.prep is not None or self.align is not None:
+        if self.resample is not None or self.gate is not None or self.prep is not None or self.align is not None:
             return self._front(x)
         return ops.zscore(x) if self.normalize else x
 
@@ -380,7 +399,9 @@ class EEG_LSTM(nn.Module):
         return (x, mask) if want_mask else x
 
     def _front(self, x: torch.Tensor) -> torch.Tensor:
-        """gate -> prep -> apply -> align over whole windows: what stands in front of the (crop and the) LSTM."""
+        """resample -> gate -> prep -> apply -> align over whole windows: what stands in front of the (crop and the) LSTM."""
+        if self.resample is not None:
+            x = ops.resample_trials(x, self.resample)
         y = self._gate_prep(x)
         if self.align is not None:
             y = ops.spatial_apply(y, self.align_matrix, out=y if y is not x else None)   # (in place in a buffer of this call's own)
@@ -476,6 +497,8 @@ class EEG_LSTM(nn.Module):
         if x.dim() != 3 or x.shape[-1] != self.spec.C:
             raise ValueError(f"Expected x of shape [B, T, {self.spec.C}], got {tuple(x.shape)}")
         B, T, _ = x.shape
+        if self.resample is not None:
+            T = self.resample.out_steps(0, T)               # (window and hop count samples at the model's rate)
         grid = ops.Crop.grid(T, int(window), hop)
         x = self._front(x)
         xc, _, _ = ops.crop(x, grid)
@@ -579,11 +602,15 @@ class SimplePredictor:
                  num_layers: int = 2, num_classes: int = 3, dropout: float = 0.60, device: str = "cpu",
                  tailoring_lambda: float = 1.25e-29, class_names=None, *, preprocess=None,
                  preprocess_package: Optional[str] = None, gpu: str = "cuda", residual: bool = False,
-                 normalize: bool = False, bidirectional: bool = False, precision: str = "fp32"):
+                 normalize: bool = False, bidirectional: bool = False, precision: str = "fp32", model_rate: Optional[float] = None):
         """A checkpoint written from a model with a causal front end carries it ({"state_dict": ..., "nsd_prep": CausalPrep.to_dict()},
         trainer.save_reference_checkpoint): the predictor's model is rebuilt with that prep.  A signal-quality gate travels the same way
         ("nsd_gate": SignalGate.to_dict()), session alignment as "nsd_align": {config, matrix, record}.  One written from a model trained on
-        crops carries "nsd_crop" = {window, crops, hop} beside it: the model is rebuilt with that ops.Crop (predict_trial, open_stream)."""
+        crops carries "nsd_crop" = {window, crops, hop} beside it: the model is rebuilt with that ops.Crop (predict_trial, open_stream).
+        A rate conversion travels as "nsd_resample" = Resample.to_dict(): the model is rebuilt with it, `sr` is then the amplifier's rate
+        and self.model_rate = sr * L / M the model's.  model_rate= (default None: the checkpoint's conversion, or none) names the model's
+        rate where the checkpoint records no conversion: with sr != model_rate the predictor designs one, Resample.design(sr, model_rate).
+        With neither, nothing is converted and model_rate is sr."""
         self.device = torch.device(device)
         self.sr = sr
         self.class_names = class_names or CLASS_NAMES
@@ -600,17 +627,25 @@ class SimplePredictor:
                            "no CPU fallback")
         self.gpu = torch.device(gpu)
         state = torch.load(pth_path, map_location="cpu", weights_only=True)
-        prep = crop = gate = align = align_state = None
+        prep = crop = gate = align = align_state = resample = None
         if isinstance(state, dict) and "state_dict" in state:     # both forms, as lstm_eeg_model.py:79-80
             align_state = state.get("nsd_align")
             align = SessionAlign.from_dict(align_state["config"]) if align_state is not None else None
             prep = CausalPrep.from_dict(state["nsd_prep"]) if state.get("nsd_prep") is not None else None
             crop = ops.Crop(**{k: int(v) for k, v in state["nsd_crop"].items()}) if state.get("nsd_crop") is not None else None
             gate = SignalGate.from_dict(state["nsd_gate"]) if state.get("nsd_gate") is not None else None
+            resample = Resample.from_dict(state["nsd_resample"]) if state.get("nsd_resample") is not None else None
             state = state["state_dict"]
+        if resample is None and model_rate is not None and float(model_rate) != float(sr):
+            resample = Resample.design(sr, model_rate)
+        self.model_rate = float(sr) if resample is None else float(sr) * resample.L / resample.M
+        if resample is not None and model_rate is not None and abs(self.model_rate - float(model_rate)) > 1e-6 * float(model_rate):
+            raise NsdError(f"SimplePredictor: the checkpoint's rate conversion is L / M = {resample.L} / {resample.M}: sr = {sr} Hz gives the "
+                           f"model {self.model_rate} Hz, model_rate = {model_rate}")
         self.model = EEG_LSTM(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers,
                               num_classes=num_classes, dropout=dropout, residual=residual, normalize=normalize,
-                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop, gate=gate, align=align)
+                              bidirectional=bidirectional, precision=precision, prep=prep, crop=crop, gate=gate, align=align,
+                              resample=resample)
         if align_state is not None:
             self.model.set_alignment(align_state["matrix"], record=align_state.get("record"))
         self.model.load_state_dict(state, strict=True)
@@ -634,7 +669,7 @@ class SimplePredictor:
         if crop is None:
             raise NsdError("SimplePredictor.predict_trial: the checkpoint carries no trained window (nsd_crop): it was trained on whole "
                            "trials -- use predict()")
-        hop = max(crop.window // 2, 1) if hop_seconds is None else int(round(hop_seconds * self.sr))
+        hop = max(crop.window // 2, 1) if hop_seconds is None else int(round(hop_seconds * self.model_rate))
         if hop < 1:
             raise ValueError(f"SimplePredictor.predict_trial: hop_seconds {hop_seconds!r} is less than one sample")
         win_probs, _ = self.predict_windows(trial_TxC, crop.window, hop)
@@ -684,7 +719,7 @@ class SimplePredictor:
         from .stream import PredictorSlidingStream, PredictorStream
         crop = getattr(self.model, "crop", None)
         if window_seconds is None and hop_seconds is not None and crop is not None:
-            window_seconds = crop.window / float(self.sr)         # a model trained on crops: the window it was trained to decide on
+            window_seconds = crop.window / float(self.model_rate)   # a model trained on crops: the window it was trained to decide on
         if (window_seconds is None) != (hop_seconds is None):
             raise ValueError("SimplePredictor.open_stream: window_seconds and hop_seconds go together (both, or neither)")
         if chunk_transform is None and not isinstance(self.pre, IdentityPreProcessor):
@@ -692,7 +727,9 @@ class SimplePredictor:
                            "works on a whole window and is not causal, so a stream cannot be filtered with it chunk by chunk; pass "
                            "chunk_transform=<causal [n,C] -> [n,C] callable>, or build the predictor with preprocess=\"identity\"")
         if window_seconds is not None:
-            return PredictorSlidingStream(self, streams, chunk_transform, int(round(window_seconds * self.sr)), int(round(hop_seconds * self.sr)))
+            # (window and hop count samples at the model's rate: behind a rate conversion that is not the rate of the pushed chunks)
+            return PredictorSlidingStream(self, streams, chunk_transform, int(round(window_seconds * self.model_rate)),
+                                          int(round(hop_seconds * self.model_rate)))
         return PredictorStream(self, streams, chunk_transform)
 
     def calibrate(self, trials, labels, align: bool = True, **fit_kw) -> dict:

@@ -29,7 +29,8 @@ def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
     for i, mdl in enumerate(models):
         if (mdl.spec != sp or mdl.residual != models[0].residual or mdl.precision != models[0].precision
                 or mdl.normalize != models[0].normalize or mdl.prep != models[0].prep or mdl.gate != models[0].gate
-                or getattr(mdl, "align", None) != getattr(models[0], "align", None)):
+                or getattr(mdl, "align", None) != getattr(models[0], "align", None)
+                or getattr(mdl, "resample", None) != getattr(models[0], "resample", None)):
             raise NsdError(f"{what}: model {i} has another shape / options than model 0 (mixed shapes: one launch runs one shape)")
     if models[0].residual or models[0].precision != "fp32" or sp.D != 1:
         raise NsdError(f"{what}: the model-batched path runs the plain fp32 stack (no residual extension, no bf16)")
@@ -430,6 +431,7 @@ class _EnsembleModel:
         self.models = list(models)
         self.spec, self.precision, self.normalize, self.prep = models[0].spec, "fp32", models[0].normalize, models[0].prep
         self.gate = models[0].gate
+        self.resample = getattr(models[0], "resample", None)
         self.align = getattr(models[0], "align", None)      # (the front end is shared: member 0's matrix is the ensemble's)
         self.params = torch.stack([m.flat_parameters() for m in self.models]).contiguous()
 
@@ -484,8 +486,8 @@ class EnsemblePredictor(SimplePredictor):
         the alignment matrix where the members have one; members with a signal-quality gate or a causal front end are refused, as
         EEG_LSTM.forward refuses x.requires_grad through them."""
         em = self.model
-        if em.gate is not None or em.prep is not None:
-            raise NsdError("EnsemblePredictor.input_gradient: dx through the signal-quality gate / the causal front end is not offered; "
+        if em.gate is not None or em.prep is not None or em.resample is not None:
+            raise NsdError("EnsemblePredictor.input_gradient: dx through the rate conversion / the signal-quality gate / the causal front end is not offered; "
                            "differentiate gate- and prep-free members on the front end's output (ops.gate_step, ops.prep_step)")
         x = torch.as_tensor(np.asarray(trials, dtype=np.float32)).to(self.gpu).contiguous()
         sp, M = em.spec, len(em.models)

@@ -2170,6 +2170,88 @@ def prep_step(x: torch.Tensor, prep, state: Optional[torch.Tensor] = None, *, sl
     return out
 
 
+# ---- rate conversion, stage 0 of the front end (nsd_resample_* of include/nsd.h; the configuration: resample.Resample) ----
+
+def _resample_ptr(resample):
+    return C.cast(C.pointer(resample.struct()), C.c_void_p)
+
+
+def resample_path(C_: int, resample=None) -> bool:
+    """True where nsd_resample_step covers C_ channels (with the Resample `resample`, when given)."""
+    return bool(_lib.lib().nsd_resample_path(int(C_), None if resample is None else _resample_ptr(resample)))
+
+
+def resample_out_steps(resample, n_in: int, T: int) -> int:
+    """Outputs a call that adds T samples to a stream holding n_in emits: ceil((n_in+T) L / M) - ceil(n_in L / M)."""
+    n = int(_lib.lib().nsd_resample_out_steps(_resample_ptr(resample), int(n_in), int(T)))
+    if n < 0:
+        check(n, "nsd_resample_out_steps")
+    return n
+
+
+def resample_layout(C_: int, resample) -> "_lib.ResampleLayout":
+    """Offsets, in 4-byte words, of hist[P-1][C] (fp32) and the int64 n_in inside one slot, and the slot stride."""
+    lay = _lib.ResampleLayout()
+    check(_lib.lib().nsd_resample_state_layout(int(C_), _resample_ptr(resample), C.byref(lay)), "nsd_resample_state_layout")
+    return lay
+
+
+def resample_state(C_: int, resample, S: int, device="cuda") -> torch.Tensor:
+    """A reset resample state of S slots on `device`: [S, stride] 4-byte words carried as float32 (one row per stream; resample_layout
+    names the columns, n_in is a bit pattern: read it through .view(torch.int64))."""
+    state = torch.empty((int(S), int(resample_layout(C_, resample).stride)), dtype=torch.float32, device=device)
+    resample_reset(C_, resample, state)
+    return state
+
+
+def resample_reset(C_: int, resample, state: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """Reset all slots of `state`, or the ones a device int32 tensor names: everything zero."""
+    S = int(state.shape[0]) if state.dim() == 2 else 0
+    n = 0 if slots is None else int(slots.numel())
+    if slots is not None and n == 0:
+        return
+    _call("nsd_resample_reset", state.device, int(C_), _resample_ptr(resample), _dev_f32(state, "state"), _nbytes(state), S,
+          _slots_ptr(slots, "resample_reset"), n, STREAM)
+
+
+def resample_step(x: torch.Tensor, resample, state: Optional[torch.Tensor] = None, *, slots: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, cnt: Optional[torch.Tensor] = None, taps: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nsd_resample_step on x [B,n,C] (or [M,B,n,C]: M*B trials) -> y [B,To,C].  state=None: window mode, every trial from rest and
+    To = ceil(n L / M).  state [S,stride]: stream mode, stream b advances slot slots[b] (or b) by the chunk; row b of y holds its
+    outputs and NaN behind them, cnt (device int32 [B], optional) their number.  out: a caller-owned buffer [..,To,C] with
+    To >= ceil(n L / M) (window mode: equal).  taps: the device table, default the Resample's own on x's device."""
+    if x.dim() not in (3, 4):
+        raise NsdError(f"resample_step: x must be [B,n,C] or [M,B,n,C], got {tuple(x.shape)}")
+    T, Cc = int(x.shape[-2]), int(x.shape[-1])
+    B = int(x.numel()) // max(T * Cc, 1)
+    if state is None and slots is not None:
+        raise NsdError("resample_step: slots without a state")
+    if slots is not None and int(slots.numel()) != B:
+        raise NsdError(f"resample_step: {int(slots.numel())} slot indices for {B} streams")
+    if out is None:
+        out = torch.empty(tuple(x.shape[:-2]) + (-((-T * resample.L) // resample.M), Cc), dtype=torch.float32, device=x.device)
+    if out.dim() != x.dim() or tuple(out.shape[:-2]) != tuple(x.shape[:-2]) or int(out.shape[-1]) != Cc:
+        raise NsdError(f"resample_step: out of shape {tuple(out.shape)} for x {tuple(x.shape)}")
+    if cnt is not None and (cnt.dtype != torch.int32 or not cnt.is_cuda or not cnt.is_contiguous() or int(cnt.numel()) != B):
+        raise NsdError(f"resample_step: cnt must be a contiguous int32 tensor of {B} counts on the device")
+    if B == 0:
+        return out
+    if taps is None:
+        taps = resample.device_taps(x.device)
+    S = 0 if state is None else (int(state.shape[0]) if state.dim() == 2 else 0)
+    d = Dims(B, T, Cc, 1, 1, 1, 1)
+    _call("nsd_resample_step", x.device, C.byref(d), _resample_ptr(resample), _dev_f32(taps, "taps", (resample.L, resample.P)),
+          _dev_f32(x, "x"), _slots_ptr(slots, "resample_step"), _dev_f32(state, "state"), 0 if state is None else _nbytes(state), S,
+          _dev_f32(out, "out"), int(out.shape[-2]), None if cnt is None else cnt.data_ptr(), STREAM)
+    return out
+
+
+def resample_trials(x: torch.Tensor, resample) -> torch.Tensor:
+    """Whole trials x [B,n,C] (or [M,B,n,C]) at the amplifier's rate -> [.., ceil(n L / M), C] at the models': window mode, every
+    trial from rest."""
+    return resample_step(x, resample)
+
+
 # ---- signal-quality gate around the front end (nsd_gate_* of include/nsd.h; the configuration: gate.SignalGate) ----
 
 def gate_path(C_: int, gate=None) -> bool:

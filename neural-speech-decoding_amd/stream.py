@@ -69,6 +69,13 @@ class StreamDecoder:
       alignment(slots=None)                  (matrices [n,C,C] numpy, records) in one copy
       set_alignment(slots, W)                write matrices; reset_alignment(slots): back to the model's matrix, accumulators zero
     reset() restarts a stream, not its session: the matrices and the accumulators stay.
+    A model with a rate conversion (EEG_LSTM(resample=...)) is pushed samples at the amplifier's rate: push runs nsd_resample_step
+    (stream mode) in front of everything above, on a resample state of the same slots, and the stages behind it -- and `steps` --
+    count samples at the model's rate; input_steps counts the amplifier's.  A host mirror of every slot's sample count gives the
+    number of steps a push emits without a read-back (slots given as a device tensor are read once).  The streams of one push must
+    emit the same number of steps: a push whose slots would not is refused before any launch -- push those slots separately.  A push
+    that emits no step (a chunk shorter than M / L samples can) advances the rate conversion alone and returns None (a sliding
+    decoder: no decisions).
     state_dict() carries the session with the stream: the matrix table, the accumulators and the records of the last fits
     (align_records), so alignment() of a restored decoder returns what the original's returns; a checkpoint written before the records
     travelled loads with all-zero records ("never refitted").  align_accumulate's switch is configuration, not state: it does not
@@ -86,6 +93,10 @@ class StreamDecoder:
         """What runs in front of the model's step, each with a state of the decoder's slots: the signal-quality gate (model.gate) and
         the causal front end (model.prep).  Their outputs go to one set of buffers per chunk shape: push allocates nothing new."""
         C_ = model.spec.C
+        self.resample = getattr(model, "resample", None)
+        self.resample_state = None if self.resample is None else ops.resample_state(C_, self.resample, self.streams, self.device)
+        self._resampled = {}                                # (chunk shape, steps) -> (all rows the call may write, the steps it emitted)
+        self._n_in = np.zeros(self.streams, np.int64)       # the host's mirror of every slot's n_in
         self.prep = model.prep
         self.prep_state = None if self.prep is None else ops.prep_state(C_, self.streams, self.device)
         self._prepped = {}
@@ -188,14 +199,59 @@ class StreamDecoder:
         self.set_alignment(slots, self.model.align_matrix)
         ops.cov_reset(self.model.spec.C, self.cov_state, self._slots(slots))
 
+    def _resample_push(self, x: torch.Tensor, slots, idx) -> Optional[torch.Tensor]:
+        """Stage 0 on a chunk at the amplifier's rate -> the chunk at the model's rate, or None where it emits no step.  idx: the
+        pushed slots on the host.  The count comes from the mirror; mixed counts are refused before any launch."""
+        r, T = self.resample, int(x.shape[1])
+        held = self._n_in[idx]                              # (idx: a slice, or an index array)
+        counts = -((-(held + T) * r.L) // r.M) + ((-held * r.L) // r.M)          # ceil((n+T) L / M) - ceil(n L / M), all slots at once
+        n = int(counts[0])
+        if (counts != n).any():
+            raise NsdError(f"{type(self).__name__}.push: the pushed streams hold {held.tolist()} samples and a chunk of {T} would emit "
+                           f"{sorted(set(counts.tolist()))} steps at L / M = {r.L} / {r.M}: push those slots separately")
+        most = r.out_steps(0, T)                            # ceil(T L / M): the rows the call may write
+        key = (tuple(x.shape), n)
+        bufs = self._resampled.get(key)
+        if bufs is None:
+            full = torch.empty((x.shape[0], most, x.shape[2]), dtype=torch.float32, device=x.device)
+            bufs = self._resampled[key] = (full, full if n == most else torch.empty((x.shape[0], n, x.shape[2]), dtype=torch.float32,
+                                                                                   device=x.device))
+        full, cut = bufs
+        ops.resample_step(x, r, self.resample_state, slots=slots, out=full)
+        self._n_in[idx] += T
+        if n == 0:
+            return None
+        if cut is not full:
+            cut.copy_(full[:, :n])                          # (a chunk that emits floor(T L / M) steps: the stages behind want them dense)
+        return cut
+
+    def _no_steps(self, x: torch.Tensor):
+        """What push returns where the chunk emitted no step at the model's rate."""
+        return None
+
+    @property
+    def input_steps(self) -> np.ndarray:
+        """Samples pushed per slot since its reset, at the rate they were pushed at (int64 numpy [streams]); `steps` counts the
+        model's."""
+        return self._n_in.copy() if getattr(self, "resample", None) is not None else self.steps
+
     def _reset_front(self, slots) -> None:
         C_ = self.model.spec.C
+        if getattr(self, "resample", None) is not None:
+            ops.resample_reset(C_, self.resample, self.resample_state, slots)
+            if slots is None:
+                self._n_in[:] = 0
+            else:
+                self._n_in[[int(v) for v in slots.cpu().tolist()]] = 0
         if self.prep is not None:
             ops.prep_reset(C_, self.prep_state, slots)
         if self.gate is not None:
             ops.gate_reset(C_, self.gate_state, slots)
 
     def _front_state_dict(self, sd: dict) -> dict:
+        if getattr(self, "resample", None) is not None:
+            sd["resample_state"] = self.resample_state.detach().cpu().clone()
+            sd["resample_n_in"] = torch.from_numpy(self._n_in.copy())
         if self.prep is not None:
             sd["prep_state"] = self.prep_state.detach().cpu().clone()
         if self.gate is not None:
@@ -207,6 +263,9 @@ class StreamDecoder:
         return sd
 
     def _check_front_state(self, sd: dict, who: str):
+        rs, mine = sd.get("resample_state"), getattr(self, "resample", None)
+        if (rs is None) != (mine is None) or (rs is not None and tuple(rs.shape) != tuple(self.resample_state.shape)):
+            raise NsdError(f"{who}: the checkpoint and the decoder differ in their rate conversion's state")
         ps, gs = sd.get("prep_state"), sd.get("gate_state")
         if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their causal front end's state")
@@ -220,6 +279,18 @@ class StreamDecoder:
         if ar is not None and (at is None or tuple(ar.shape) != tuple(self.align_records.shape)):
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their session alignment's records")
         return ps, gs, at, cs, ar
+
+    def _load_resample_state(self, sd: dict) -> None:
+        """The rate conversion's state and the host's mirror of its counts (checked by _check_front_state)."""
+        rs = sd.get("resample_state")
+        if rs is None:
+            return
+        self.resample_state.copy_(rs.to(self.device, dtype=torch.float32))
+        mirror = sd.get("resample_n_in")
+        if mirror is None:                                  # (the counts are in the state itself)
+            col = int(ops.resample_layout(self.model.spec.C, self.resample).n_in) // 2
+            mirror = rs.to(torch.float32).contiguous().view(torch.int64)[:, col]
+        self._n_in[:] = np.asarray(mirror.cpu().numpy() if torch.is_tensor(mirror) else mirror, np.int64)
 
     def _load_front_state(self, ps, gs, at=None, cs=None, ar=None) -> None:
         if ps is not None:
@@ -268,7 +339,16 @@ class StreamDecoder:
         if x.shape[0] > self.streams:
             raise NsdError(f"StreamDecoder.push: {x.shape[0]} streams pushed, the decoder has {self.streams}")
         x = x.to(self.device, non_blocking=True).contiguous().float()
-        slots = self._slots(slots, int(x.shape[0]))
+        if getattr(self, "resample", None) is not None:
+            idx = (slice(0, int(x.shape[0])) if slots is None
+                   else np.asarray(slots.cpu().tolist() if torch.is_tensor(slots) else slots, dtype=np.int64).reshape(-1))
+            slots = self._slots(slots, int(x.shape[0]))
+            xr = self._resample_push(x, slots, idx)
+            if xr is None:
+                return self._no_steps(x)
+            x = xr
+        else:
+            slots = self._slots(slots, int(x.shape[0]))
         return self._step(self._front(x, slots), slots, read)
 
     def _step(self, x: torch.Tensor, slots, read: bool) -> Optional[torch.Tensor]:
@@ -302,6 +382,7 @@ class StreamDecoder:
         front = self._check_front_state(sd, who)
         self.state.copy_(st.to(self.device, dtype=torch.float32))
         self._load_front_state(*front)
+        self._load_resample_state(sd)
 
 
 def _check_ensemble(dec, models, streams, who: str, path):
@@ -446,6 +527,11 @@ class SlidingStreamDecoder(StreamDecoder):
         newest = probs.gather(1, row[:, None, None].expand(-1, 1, probs.shape[2]))[:, 0]
         self._last_probs[idx] = torch.where(has[:, None], newest, self._last_probs[idx])
 
+    def _no_steps(self, x: torch.Tensor):
+        B = int(x.shape[0])
+        return (torch.empty((B, 0, self.model.spec.K), dtype=torch.float32, device=x.device),
+                torch.empty((B, 0), dtype=torch.int64, device=x.device), torch.zeros((B,), dtype=torch.int32, device=x.device))
+
     def features(self, slots=None):
         raise NsdError(f"{type(self).__name__}.features: a sliding decoder's phase slots are in the middle of their windows; read the "
                        "pooled features of cued trials from a StreamDecoder (open_stream without window_seconds)")
@@ -483,6 +569,7 @@ class SlidingStreamDecoder(StreamDecoder):
         front = self._check_front_state(sd, who)
         self.state.copy_(st.to(self.device, dtype=torch.float32))
         self._load_front_state(*front)
+        self._load_resample_state(sd)
         self._last_end.copy_(sd["last_end"].to(self.device))
         self._last_probs.copy_(sd["last_probs"].to(self.device))
 

@@ -144,7 +144,8 @@ def run_trials(trials: int = 10, serial_port: str = DEFAULT_SERIAL, num_channels
     Positional / keyword interface: the reference's.  Keyword-only additions: `producer_factory`
     (callable(serial_port=, num_channels=, window_seconds=, out_queue=) -> process; default StreamingProcess),
     `queue_timeout` (the reference hard-codes 6.5 s), `predictor_kwargs` (extra SimplePredictor kwargs, e.g.
-    {"preprocess": "identity"} when the reference's MindsAI filter is not importable), `chunk_seconds` (None: the window mode
+    {"preprocess": "identity"} when the reference's MindsAI filter is not importable, or {"model_rate": 125} for a producer whose
+    payloads carry another `sr`: the predictor then converts the rate on the device, nsd_amd.Resample), `chunk_seconds` (None: the window mode
     above; a value: the producer cuts every window into chunks of that length and a resumable decoder -- SimplePredictor.open_stream
     -- advances while they arrive; the trial's decision is read at its last chunk) with `chunk_transform` (open_stream's).
     `hop_seconds` (with chunk_seconds): no cue -- the decoder is not reset between the producer's windows, their chunks form one

@@ -25,6 +25,7 @@ from .ops import Augment, Average, Crop, Loss, LrSchedule, Sam
 from .gate import SignalGate
 from .align import SessionAlign
 from .prep import CausalPrep
+from .resample import Resample
 from .trainer import Trainer, init_distributed, save_reference_checkpoint, shard_range
 
 
@@ -75,6 +76,26 @@ def gate_for(args) -> Optional[SignalGate]:
 
 
 ALIGN_OPTIONS = ("align", "align_shrinkage", "align_floor")
+RESAMPLE_OPTIONS = ("input_rate", "model_rate", "resample_zeros")
+
+
+def resample_for(args):
+    """--input-rate R [--model-rate 125 --resample-zeros Z] -> the Resample that brings the loaded trials to the models' rate, or None
+    (no --input-rate, or the two rates are equal).  ValueError for rates the rate conversion does not cover."""
+    if args.input_rate is None:
+        return None
+    if not (args.input_rate > 0 and args.model_rate > 0):
+        raise ValueError(f"--input-rate {args.input_rate} / --model-rate {args.model_rate}: both positive")
+    if float(args.input_rate) == float(args.model_rate):
+        return None
+    return Resample.design(args.input_rate, args.model_rate, zeros=args.resample_zeros)
+
+
+def resample_loaded(x_np: np.ndarray, resample, dev) -> np.ndarray:
+    """The loaded trials [N,T,C] at the amplifier's rate -> [N, ceil(T L / M), C] at the models', once, on the device (window mode:
+    every trial from rest).  The trainers and everything they score are handed these."""
+    from . import ops
+    return ops.resample_trials(torch.from_numpy(np.ascontiguousarray(x_np, dtype=np.float32)).to(dev), resample).cpu().numpy()
 
 
 def align_for(args) -> Optional[SessionAlign]:
@@ -350,6 +371,12 @@ def build_parser() -> argparse.ArgumentParser:
                     "their mean second moment, fitted per fold on the training trials before the first step and applied to the held-out ones")
     ap.add_argument("--align-shrinkage", type=float, default=None, help="session alignment: shrink the moment towards its mean diagonal, in [0, 1] (default 0)")
     ap.add_argument("--align-floor", type=float, default=None, help="session alignment: eigenvalues below this share of the largest are raised to it (default 1e-4)")
+    ap.add_argument("--input-rate", type=float, default=None, metavar="HZ",
+                    help="rate conversion (Resample): the loaded trials were recorded at this rate; they are brought to --model-rate once, on "
+                         "the device, before anything else sees them (--T counts the recorded samples), and the checkpoint carries the "
+                         "conversion so that a predictor or a stream decoder built from it takes samples at this rate")
+    ap.add_argument("--model-rate", type=float, default=125.0, metavar="HZ", help="rate conversion: the rate the model decides at (default 125)")
+    ap.add_argument("--resample-zeros", type=int, default=10, help="rate conversion: zero crossings of the windowed sinc on each side (default 10)")
     ap.add_argument("--gate-drop-trials", type=float, default=None, metavar="FRACTION",
                     help="signal-quality gate: drop the trials whose share of rejected steps exceeds FRACTION before the folds are made")
     ap.add_argument("--early-stop-patience", type=int, default=None,
@@ -415,6 +442,15 @@ def main(argv=None) -> int:
         ap.error(str(e))
     if align is not None and args.normalize:
         ap.error("--align with --normalize: the whole-window z-score would undo the whitening channel by channel")
+    try:
+        resample = resample_for(args)
+    except ValueError as e:
+        ap.error(str(e))
+    if resample is not None and args.normalize:
+        ap.error("--input-rate with --normalize: a predictor built from the checkpoint would z-score over the filter's start-up")
+    # (the models below are built without the conversion: they are trained and scored on trials already at their rate; the
+    # checkpoints carry it)
+    save_checkpoint = save_reference_checkpoint if resample is None else (lambda mdl, path: save_reference_checkpoint(mdl, path, resample=resample))
 
     def prep_for(idx):
         """The front end of a run trained on the trials idx: the design, its starting variance calibrated on those trials."""
@@ -482,6 +518,11 @@ def main(argv=None) -> int:
         if ts.x.shape[1] != args.T:
             ap.error(f"--T {args.T} but the trials have {ts.x.shape[1]} samples")
         x_np, y_np = ts.x, ts.y
+    if resample is not None:
+        x_np = resample_loaded(x_np, resample, dev)
+        args.T = int(x_np.shape[1])
+        if augment.max_shift >= args.T:
+            ap.error(f"--aug-shift {augment.max_shift} must be smaller than the {args.T} samples of a trial at --model-rate")
     x_np, y_np = drop_bad_trials(x_np, y_np, gate, args.gate_drop_trials, "train")
     tr_idx, va_idx = D.stratified_split(y_np, args.val_fraction, args.seed)
     x_all = torch.from_numpy(x_np).to(dev)
@@ -508,7 +549,7 @@ def main(argv=None) -> int:
         return {"fold_checkpoints": fold_paths} if args.save_folds else {}
 
     def shown_args() -> dict:
-        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + GATE_OPTIONS + ("sam_rho",) or v is not None) and (k not in ALIGN_OPTIONS or v)}
+        return {k: v for k, v in vars(args).items() if (k != "save_folds" or v) and k != "device_batches" and (k not in EARLY_STOP_OPTIONS + AVG_OPTIONS + CROP_OPTIONS + GATE_OPTIONS + ("sam_rho",) or v is not None) and (k not in ALIGN_OPTIONS or v) and (k not in RESAMPLE_OPTIONS or args.input_rate is not None)}
 
     def score(mdl, xs, ys):
         """(accuracy, first-window accuracy or None): whole trials, or with --crop-seconds trials pooled over the evaluation grid"""
@@ -564,7 +605,7 @@ def main(argv=None) -> int:
                 acc_va, acc_va_first = score(scored, x_all[va_idx], y_all[va_idx]) if len(va_idx) else (float("nan"), None)
                 if keep_best and out_path and acc_va > best[0]:
                     best = (acc_va, epoch)
-                    save_reference_checkpoint(scored, out_path)
+                    save_checkpoint(scored, out_path)
                 extra = {"grad_norm": trainer.last_grad_norm(), "lr": trainer.last_lr(), "skipped": trainer.skipped_steps()} if opt_on else {}
                 if acc_va_first is not None:
                     extra["acc_val_first_window"] = round(acc_va_first, 4)
@@ -574,7 +615,7 @@ def main(argv=None) -> int:
                 emit({"run": tag, "epoch": epoch, "loss_last_batch": round(trainer.last_loss(), 5), "acc_train": round(acc_tr, 4),
                       "acc_val": round(acc_va, 4), "elapsed_s": round(time.time() - t0, 2), **extra})
         if rank == 0 and out_path and (not keep_best or best[1] < 0):
-            save_reference_checkpoint(scored, out_path)
+            save_checkpoint(scored, out_path)
         return {"acc_train_last": acc_tr, "acc_val_last": acc_va, "best_val_acc": best[0], "best_epoch": best[1],
                 "acc_val_last_iterate": acc_va_last_iterate}
 
@@ -664,7 +705,7 @@ def main(argv=None) -> int:
             if args.save_folds:
                 fold_paths.append(fold_path(tag(r)))
                 # (with early stopping restore_best has put the selected row -- the averaged one with --avg -- into the model)
-                save_reference_checkpoint(models[k] if es or not avg_on else mbt.averaged_models()[k], fold_paths[-1])
+                save_checkpoint(models[k] if es or not avg_on else mbt.averaged_models()[k], fold_paths[-1])
             rec = {"fold": r["fold"], "n_train": int(len(r["tr"])), "n_val": int(len(r["va"])),
                    "acc_val_last_epoch": round(res[k]["acc_val_last"], 4), "acc_train_last_epoch": round(res[k]["acc_train_last"], 4),
                    "concurrent": True}

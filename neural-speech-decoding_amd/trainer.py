@@ -549,20 +549,23 @@ class Trainer:
             self._avg_state[:4].view(torch.int32).fill_(int(sd["avg_n"]))
 
 
-def save_reference_checkpoint(model: EEG_LSTM, path: str) -> None:
+def save_reference_checkpoint(model: EEG_LSTM, path: str, resample=None) -> None:
     """Write a .pth the reference's SimplePredictor loads unchanged (raw state_dict with the reference's
     key names on CPU; lstm_eeg_model.py:77-81).  A model with a causal front end is written in the dict form both loaders accept,
     {"state_dict": ..., "nsd_prep": prep.to_dict()}: the reference's loader reads the weights, SimplePredictor here rebuilds the prep too.
     A model trained on crops (model.crop) adds "nsd_crop" = {window, crops, hop} to that dict, one with a signal-quality gate
-    "nsd_gate" = gate.to_dict(), one with session alignment "nsd_align" = {config, matrix [C,C], record of its fit or None}; a model with
-    none of them is written as before."""
+    "nsd_gate" = gate.to_dict(), one with session alignment "nsd_align" = {config, matrix [C,C], record of its fit or None}, one with a
+    rate conversion "nsd_resample" = resample.to_dict() (L, M, P and the tap table); a model with none of them is written as before.  resample=: the conversion to
+    write for a model that was trained without the stage on trials already brought to its rate (train --input-rate)."""
     sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     crop, gate = getattr(model, "crop", None), getattr(model, "gate", None)
-    align = getattr(model, "align", None)
-    if model.prep is None and crop is None and gate is None and align is None:
+    align, resample = getattr(model, "align", None), resample if resample is not None else getattr(model, "resample", None)
+    if model.prep is None and crop is None and gate is None and align is None and resample is None:
         torch.save(sd, path)
         return
     extra = {} if model.prep is None else {"nsd_prep": model.prep.to_dict()}
+    if resample is not None:
+        extra["nsd_resample"] = resample.to_dict()
     if gate is not None:
         extra["nsd_gate"] = gate.to_dict()
     if align is not None:
