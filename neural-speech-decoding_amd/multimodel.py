@@ -16,7 +16,7 @@ import torch
 from . import ops
 from ._lib import NsdError
 from .lstm_eeg_model import EEG_LSTM, SimplePredictor
-from .step_recipe import StepRecipe, trainer_seed
+from .step_recipe import StepRecipe, refuse_resample, trainer_seed
 
 
 def _check_models(models: Sequence[EEG_LSTM], what: str) -> None:
@@ -81,6 +81,7 @@ class ModelBatchTrainer:
         import torch.distributed as dist
         self.models: List[EEG_LSTM] = list(models)
         _check_models(self.models, "ModelBatchTrainer")
+        refuse_resample(self.models, "ModelBatchTrainer")
         if group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
             raise NsdError("ModelBatchTrainer: world size > 1 is not supported (model batching is single-GPU; use Trainer for data parallel)")
         M = len(self.models)

@@ -29,6 +29,15 @@ def step_rng(seed: int, step: int, p_lstm: float = 0.0, p_head: float = 0.0) -> 
     return dict(seed=seed, base_stream=base_stream(step), p_lstm=p_lstm, p_head=p_head)
 
 
+def refuse_resample(models, who: str) -> None:
+    """A trainer's batches are at the model's rate: prepare() runs no stage 0, so a model with a rate conversion would be trained on
+    unconverted windows and evaluated on converted ones.  Refused where the trainer is built."""
+    if any(getattr(m, "resample", None) is not None for m in models):
+        raise ops.NsdError(f"{who}: the model has a rate conversion (EEG_LSTM(resample=...)), and a training step converts no rate: train "
+                           "a resample-free model on converted trials (ops.resample_trials(x, resample)) and hand resample= to "
+                           "save_reference_checkpoint, which writes the conversion into the checkpoint")
+
+
 class StepRecipe:
     """What a trainer does to a batch before the step's kernels, and with which streams.  `model`: an EEG_LSTM (spec, dropout_p,
     head_dropout_p, normalize, prep).  augment / loss are the EFFECTIVE ones: augmentation and mixup belong to the stochastic parts, so
@@ -71,9 +80,12 @@ class StepRecipe:
     augment -> gate -> prep -> apply -> align -> crop -> mixup.  One nsd_spatial_apply, in place in the buffer the front end wrote (or
     into bufs["xn"]); it draws nothing and moves no stream.  One model uses its own matrix (sel = NULL); with models= the recipe holds
     one matrix per model ([M,C,C], a copy of the models' at construction: set_alignment() writes both) and a static int32 selection
-    [M*B], model m's rows naming matrix m."""
+    [M*B], model m's rows naming matrix m.
+
+    A model with a rate conversion (EEG_LSTM(resample=...)) is refused: prepare() has no stage 0, the batches are at the model's rate."""
 
     def __init__(self, model, stochastic: bool, augment, loss, device, models: Optional[Sequence] = None, sam=None, crop=None):
+        refuse_resample([model] if models is None else models, "StepRecipe")
         self.spec, self.stochastic, self.normalize, self.prep = model.spec, stochastic, model.normalize, model.prep
         self.gate = getattr(model, "gate", None)
         self.align = getattr(model, "align", None)

@@ -72,7 +72,9 @@ class StreamDecoder:
     A model with a rate conversion (EEG_LSTM(resample=...)) is pushed samples at the amplifier's rate: push runs nsd_resample_step
     (stream mode) in front of everything above, on a resample state of the same slots, and the stages behind it -- and `steps` --
     count samples at the model's rate; input_steps counts the amplifier's.  A host mirror of every slot's sample count gives the
-    number of steps a push emits without a read-back (slots given as a device tensor are read once).  The streams of one push must
+    number of steps a push emits without a read-back (slots given as a device tensor are read once).  The mirror follows push / reset /
+    load_state_dict only: a caller who replays captured launches on the decoder's states must go through a checkpoint (state_dict ->
+    load_state_dict, which reads the counts from the state) before pushing eagerly.  The streams of one push must
     emit the same number of steps: a push whose slots would not is refused before any launch -- push those slots separately.  A push
     that emits no step (a chunk shorter than M / L samples can) advances the rate conversion alone and returns None (a sliding
     decoder: no decisions).
@@ -251,7 +253,7 @@ class StreamDecoder:
     def _front_state_dict(self, sd: dict) -> dict:
         if getattr(self, "resample", None) is not None:
             sd["resample_state"] = self.resample_state.detach().cpu().clone()
-            sd["resample_n_in"] = torch.from_numpy(self._n_in.copy())
+            sd["resample_n_in"] = self._state_n_in(sd["resample_state"]).clone()     # (the state's own words, not the mirror)
         if self.prep is not None:
             sd["prep_state"] = self.prep_state.detach().cpu().clone()
         if self.gate is not None:
@@ -266,6 +268,8 @@ class StreamDecoder:
         rs, mine = sd.get("resample_state"), getattr(self, "resample", None)
         if (rs is None) != (mine is None) or (rs is not None and tuple(rs.shape) != tuple(self.resample_state.shape)):
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their rate conversion's state")
+        if rs is not None:
+            self._checked_n_in(sd)
         ps, gs = sd.get("prep_state"), sd.get("gate_state")
         if (ps is None) != (self.prep is None) or (ps is not None and tuple(ps.shape) != tuple(self.prep_state.shape)):
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their causal front end's state")
@@ -280,17 +284,31 @@ class StreamDecoder:
             raise NsdError(f"{who}: the checkpoint and the decoder differ in their session alignment's records")
         return ps, gs, at, cs, ar
 
+    def _state_n_in(self, rs: torch.Tensor) -> torch.Tensor:
+        """The n_in words of a resample state on the host -> int64 [streams]."""
+        col = int(ops.resample_layout(self.model.spec.C, self.resample).n_in) // 2
+        return rs.to(torch.float32).contiguous().view(torch.int64)[:, col]
+
+    def _checked_n_in(self, sd: dict) -> np.ndarray:
+        """The counts a checkpoint's resample_state holds; a "resample_n_in" beside it that disagrees with them is refused."""
+        held = self._state_n_in(sd["resample_state"].detach().cpu()).numpy().astype(np.int64)
+        given = sd.get("resample_n_in")
+        if given is not None:
+            given = np.asarray(given.cpu().numpy() if torch.is_tensor(given) else given, np.int64).reshape(-1)
+            if given.shape != held.shape or (given != held).any():
+                raise NsdError(f"{type(self).__name__}.load_state_dict: resample_n_in {given.tolist()} disagrees with the counts "
+                               f"{held.tolist()} inside resample_state")
+        return held
+
     def _load_resample_state(self, sd: dict) -> None:
-        """The rate conversion's state and the host's mirror of its counts (checked by _check_front_state)."""
+        """The rate conversion's state and the host's mirror of its counts (checked by _check_front_state, before anything is
+        written).  The mirror is derived from the state's own n_in words, never taken from the checkpoint's copy of a mirror."""
         rs = sd.get("resample_state")
         if rs is None:
             return
+        held = self._checked_n_in(sd)
         self.resample_state.copy_(rs.to(self.device, dtype=torch.float32))
-        mirror = sd.get("resample_n_in")
-        if mirror is None:                                  # (the counts are in the state itself)
-            col = int(ops.resample_layout(self.model.spec.C, self.resample).n_in) // 2
-            mirror = rs.to(torch.float32).contiguous().view(torch.int64)[:, col]
-        self._n_in[:] = np.asarray(mirror.cpu().numpy() if torch.is_tensor(mirror) else mirror, np.int64)
+        self._n_in[:] = held
 
     def _load_front_state(self, ps, gs, at=None, cs=None, ar=None) -> None:
         if ps is not None:

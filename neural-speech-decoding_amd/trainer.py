@@ -32,7 +32,7 @@ import torch.distributed as dist
 
 from . import ops
 from .lstm_eeg_model import EEG_LSTM
-from .step_recipe import StepRecipe, base_stream, trainer_seed
+from .step_recipe import StepRecipe, base_stream, refuse_resample, trainer_seed
 
 
 def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
@@ -118,6 +118,7 @@ class Trainer:
         parameters (averaged_model()); no extra launch.  Averaging switches the guarded tail on, as clip_grad_norm=0.0 does: it does
         not clip, and a step whose gradient norm is not finite is skipped and counted (skipped_steps()); a skipped step does not
         average.  World > 1: every rank averages its identical replica, with no communication.  None: today's calls, launch for launch."""
+        refuse_resample([model], "Trainer")
         self.model = model
         self.spec = model.spec
         self.flat = model.flat_parameters()

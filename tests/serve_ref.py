@@ -5,9 +5,12 @@ ServeRef states what a stream decoder's step must see, chunk by chunk and slot b
 restatements under tests/ -- gate_ref.State / gate_ref / apply_ref, prep_ref.State / prep_ref, align_ref.cov_ref (sums= / counts= carried)
 and align_ref.apply_ref (sel=), window_ref.completed -- in the order the StreamDecoder docstring states,
 
-    gate -> prep -> gate-apply -> (second-moment accumulator) -> spatial apply (sel = the slots) -> the decoder's step,
+    (rate conversion) -> gate -> prep -> gate-apply -> (second-moment accumulator) -> spatial apply (sel = the slots) -> the decoder's step,
 
-on four per-slot states (gate, prep, accumulator, matrix table) and the sample count of the slot.  The rules it encodes are the
+on four per-slot states (gate, prep, accumulator, matrix table) and the sample count of the slot.  Stage 0, the rate conversion
+(resample_ref.step_batch on a count and a history per slot), takes the chunk at the amplifier's rate; everything behind it, the sample
+count included, is at the model's.  A chunk that emits no step moves stage 0 alone; streams that would emit different numbers of steps
+cannot share a push (counts() / groups() say how a caller has to split them).  The rules it encodes are the
 documented ones: outside training the apply stage rejects with the gate's own max_bad; the accumulator sees what stands behind the
 gate's apply, under the gate's mask; reset(slots) restarts gate, prep and the sample count and leaves matrices, records and
 accumulators; set_alignment writes matrices and zeroes their records; reset_alignment goes back to the model's matrix and zeroes the
@@ -23,7 +26,9 @@ predict_trials must feed the model.
 
 CASES is the table: two full-chain blocks (gate + prep + align in each of the four decoders, once pushed eagerly and once replayed
 from a captured graph), a pairwise cover of FACTORS over the allowed combinations (tests/test_serve_pipeline_cpu.py proves the cover
-by enumeration) and one row beyond the pairs: a reset with gate, prep, align and the accumulators all present.  Imports without a GPU.
+by enumeration) and one row beyond the pairs: a reset with gate, prep, align and the accumulators all present -- these 33 rows run
+without a rate conversion, with the inputs they always had -- then two full-chain rows per ratio behind one (eager with a refit, and
+replayed) and the rows that restore the pairwise cover over the factor `rate`.  Imports without a GPU.
 """
 import copy
 from collections import namedtuple
@@ -31,10 +36,12 @@ from collections import namedtuple
 import numpy as np
 
 from tests import align_ref, gate_ref, prep_ref, window_ref
+from tests import resample_ref as rr
 from tests.pipeline_ref import GATE, PREP
 
 F32 = np.float32
-STAGES = ("gate", "prep", "apply", "cov", "align")       # the documented order
+STAGES = ("resample", "gate", "prep", "apply", "cov", "align")       # the documented order
+NO_STEP = (None, None, None)                             # what push returns for a chunk that emits no step at the model's rate
 
 
 def _bits(a):
@@ -65,19 +72,29 @@ ZERO_RECORD = dict(steps=0, skipped=0, status=0)
 class ServeRef:
     """Per-slot state machine of a decoder's front end.  S slots of C channels; gate: the gate's fields (SignalGate.to_dict()) or
     None; prep: prep_ref's keywords or None; align: the model's matrix [C,C] or None; window, hop: of a sliding decoder, else None.
-    accumulate: the switch align_accumulate sets (configuration: snapshot / restore do not carry it)."""
+    accumulate: the switch align_accumulate sets (configuration: snapshot / restore do not carry it).  resample: dict(L, M, taps [L,P])
+    or None -- stage 0; push then takes chunks at the amplifier's rate, and rn / rh are the slots' counts and histories."""
 
-    def __init__(self, S, C, *, gate=None, prep=None, align=None, window=None, hop=None, accumulate=False):
+    def __init__(self, S, C, *, gate=None, prep=None, align=None, window=None, hop=None, accumulate=False, resample=None):
         self.S, self.C, self.gate, self.prep, self.window, self.hop = int(S), int(C), gate, prep, window, hop
         self.accumulate = bool(accumulate)
+        self.resample = None
+        if resample is not None:
+            taps = np.array(resample["taps"], F32)
+            self.resample = dict(L=int(resample["L"]), M=int(resample["M"]), taps=taps)
+            assert taps.shape[0] == self.resample["L"]
+            self.rn = np.zeros(S, np.int64)               # samples at the amplifier's rate since the slot's reset
+            self.rh = np.zeros((S, taps.shape[1] - 1, C), F32)
+            self.stage0 = None                            # the last push: (all rows the call may write, NaN behind the emitted ones; cnt [B])
         self.g = gate_ref.State(S, C) if gate is not None else None
         self.p = prep_ref.State(S, C) if prep is not None else None
         self.W0 = None if align is None else np.array(align, F32)
         if self.W0 is not None:
             assert self.W0.shape == (C, C)
             self.table = np.repeat(self.W0[None], S, axis=0)
-            self.sums, self.counts = np.zeros((S, C, C), np.float64), np.zeros((S, 2), np.int64)
+            self.sums, self.used = np.zeros((S, C, C), np.float64), np.zeros((S, 2), np.int64)
             self.records = [dict(ZERO_RECORD) for _ in range(S)]
+        # (used: per slot the accumulator's two counts, steps used and steps skipped -- counts() is stage 0's)
         self.n = np.zeros(S, np.int64)                    # samples since the slot's reset
         self.nan_at = [[] for _ in range(S)]              # ... and which of them reached the decoder's step with a NaN in them
         self.trace = {}                                   # stage -> did it change the bits of its input, in the last push
@@ -87,15 +104,42 @@ class ServeRef:
         assert len(set(idx)) == len(idx) and all(0 <= s < self.S for s in idx) and (B is None or len(idx) == B)
         return idx
 
+    def counts(self, slots, n):
+        """the steps each named slot (None: all) would emit for a chunk of n samples -> [int]"""
+        idx = self._idx(slots)
+        if self.resample is None:
+            return [int(n)] * len(idx)
+        return [rr.out_steps(self.resample["L"], self.resample["M"], int(self.rn[s]), int(n)) for s in idx]
+
+    def groups(self, slots, n):
+        """the named slots in groups of equal count, slots and groups in the order of the slot argument -> [[slot]]"""
+        idx, out = self._idx(slots), {}
+        for s, k in zip(idx, self.counts(idx, n)):
+            out.setdefault(k, []).append(s)
+        return list(out.values())
+
     def push(self, chunk, slots=None):
         """chunk [B,n,C] of the streams in `slots` (None: 0 .. B-1) -> (what the decoder's step must see, float32 [B,n,C]; the gate's
         mask words uint32 [B,n] or None; per stream the [(end, row, poisoned)] of the windows the chunk completes, or None for a decoder
-        that is not sliding)"""
+        that is not sliding).  With a rate conversion the chunk is at the amplifier's rate, the three at the model's, and a chunk that
+        emits no step gives NO_STEP and touches nothing behind stage 0."""
         v = np.ascontiguousarray(chunk, dtype=F32)
         B, n, C = v.shape
         assert C == self.C and n >= 1
         idx = self._idx(slots, B)
         self.trace, mask = {}, None
+        if self.resample is not None:
+            L, M, taps = self.resample["L"], self.resample["M"], self.resample["taps"]
+            cnt = self.counts(idx, n)
+            assert len(set(cnt)) == 1, f"the pushed slots would emit {cnt} steps: push them by groups()"
+            w, got, self.rn[idx], self.rh[idx] = rr.step_batch(v, taps, L, M, rr.ceil_div(n * L, M), self.rn[idx], self.rh[idx])
+            assert got.tolist() == cnt
+            self.stage0 = (w, got)
+            self.trace["resample"] = True                 # (another rate: another chunk)
+            if cnt[0] == 0:
+                return NO_STEP
+            v = np.ascontiguousarray(w[:, :cnt[0]])
+            n = cnt[0]
         if self.g is not None:
             sub = _take(self.g, idx)
             w, mask = gate_ref.gate_ref(v, self.gate, sub)
@@ -111,9 +155,9 @@ class ServeRef:
             self.trace["apply"], v = _differs(v, w), w
         if self.W0 is not None:
             if self.accumulate:
-                s, c = align_ref.cov_ref(v, mask, sums=self.sums[idx], counts=self.counts[idx])
-                self.trace["cov"] = bool((c != self.counts[idx]).any())
-                self.sums[idx], self.counts[idx] = s, c
+                s, c = align_ref.cov_ref(v, mask, sums=self.sums[idx], counts=self.used[idx])
+                self.trace["cov"] = bool((c != self.used[idx]).any())
+                self.sums[idx], self.used[idx] = s, c
             w = align_ref.apply_ref(v, self.table, sel=idx)
             self.trace["align"], v = _differs(v, w), w
         bad = np.isnan(v).any(axis=2)
@@ -132,8 +176,10 @@ class ServeRef:
         return bool(self.nan_at[int(slot)])
 
     def reset(self, slots=None):
-        """a stream restarts, not its session: gate, prep and the sample count; matrices, records and accumulators stay"""
+        """a stream restarts, not its session: rate conversion, gate, prep and the sample count; matrices, records and accumulators stay"""
         idx = self._idx(slots)
+        if self.resample is not None:
+            self.rn[idx], self.rh[idx] = 0, 0.0
         if self.g is not None:
             _put(self.g, idx, gate_ref.State(len(idx), self.C))
         if self.p is not None:
@@ -150,7 +196,7 @@ class ServeRef:
     def reset_alignment(self, slots=None):
         idx = self._idx(slots)
         self.set_alignment(idx, self.W0)
-        self.sums[idx], self.counts[idx] = 0.0, 0
+        self.sums[idx], self.used[idx] = 0.0, 0
 
     def refit(self, slots, W):
         """the whitening link (module docstring): W [n,C,C] float32 are the matrices nsd_whiten_fit gave the named slots (None: all)"""
@@ -159,17 +205,17 @@ class ServeRef:
         assert W.shape == (len(idx), self.C, self.C)
         self.table[idx] = W
         for s in idx:
-            self.records[s] = dict(steps=int(self.counts[s, 0]), skipped=int(self.counts[s, 1]), status=None)   # status: the fit's own
+            self.records[s] = dict(steps=int(self.used[s, 0]), skipped=int(self.used[s, 1]), status=None)   # status: the fit's own
 
     def host_fit(self, slots, align_cfg):
         """what the CPU tests hand to refit(): whiten_ref of the reference's own accumulators, float64 rounded once -> (W, records)"""
         idx = self._idx(slots)
-        out = [align_ref.whiten_ref(self.sums[s:s + 1], self.counts[s:s + 1], **align_cfg) for s in idx]
+        out = [align_ref.whiten_ref(self.sums[s:s + 1], self.used[s:s + 1], **align_cfg) for s in idx]
         return np.stack([w[0] for w, _ in out]), [r[0] for _, r in out]
 
     def snapshot(self):
         """what a state_dict round trip must preserve: everything but the accumulate switch"""
-        keep = {k: copy.deepcopy(v) for k, v in vars(self).items() if k not in ("accumulate", "trace")}
+        keep = {k: copy.deepcopy(v) for k, v in vars(self).items() if k not in ("accumulate", "trace", "stage0")}
         return keep
 
     def restore(self, snap, accumulate=False):
@@ -177,6 +223,8 @@ class ServeRef:
         for k, v in snap.items():
             setattr(self, k, copy.deepcopy(v))
         self.accumulate, self.trace = bool(accumulate), {}
+        if self.resample is not None:
+            self.stage0 = None
         return self
 
     def quality(self, slots=None):
@@ -190,6 +238,9 @@ class ServeRef:
     def prep_rows(self):
         return self.p.slot_rows()                         # float32 [S, stride]
 
+    def resample_rows(self, layout_n_in, stride):
+        return rr.state_words(self.rn, self.rh, layout_n_in, stride)          # uint32 [S, stride]
+
 
 def same_snapshot(a, b):
     """two ServeRef.snapshot()s hold the same bits"""
@@ -198,15 +249,24 @@ def same_snapshot(a, b):
             return all(eq(getattr(u, k), getattr(v, k)) for k in vars(u))
         if isinstance(u, np.ndarray):
             return u.shape == v.shape and u.dtype == v.dtype and u.tobytes() == v.tobytes()
+        if isinstance(u, (dict, tuple, list)) and type(u) is type(v) and len(u) == len(v) and any(isinstance(e, np.ndarray) for e in
+                                                                                                 (u.values() if isinstance(u, dict) else u)):
+            if isinstance(u, dict):
+                return set(u) == set(v) and all(eq(u[k], v[k]) for k in u)
+            return all(eq(a_, b_) for a_, b_ in zip(u, v))
         return u == v
     return set(a) == set(b) and all(eq(a[k], b[k]) for k in a)
 
 
-def window_ref_windows(x, *, gate=None, prep=None, align=None, trace=None):
+def window_ref_windows(x, *, gate=None, prep=None, align=None, trace=None, resample=None):
     """x [B,T,C] whole trials -> what forward (eval) / predict_proba / predict_trials must feed the model: the chain from fresh states;
-    outside training the apply stage uses the gate's own max_bad.  trace: receives stage -> changed the bits"""
+    outside training the apply stage uses the gate's own max_bad.  trace: receives stage -> changed the bits.  resample: dict(L, M,
+    taps) -- the trials are at the amplifier's rate and converted from rest first"""
     v, mask = np.ascontiguousarray(x, dtype=F32), None
     trace = {} if trace is None else trace
+    if resample is not None:
+        v = np.ascontiguousarray(rr.trials(v, np.asarray(resample["taps"], F32), int(resample["L"]), int(resample["M"])))
+        trace["resample"] = True
     if gate is not None:
         w, mask = gate_ref.gate_ref(v, gate)
         trace["gate"], v = _differs(v, w), w
@@ -241,6 +301,27 @@ RAIL_AT = (18, 21, 27)               # stream i rails channel i at sample RAIL_A
 EVENT_STREAM, SET_STREAM = 1, 0      # reset / refit / reset_alignment name the slot of pushed stream 1, set_alignment that of stream 0
 EVENT_AFTER = 35                     # an event stands at the first chunk boundary at or after this many samples, else at the last one
                                      # in front of the final chunk ("ones-58": after 12 samples)
+# Stage 0.  The comparison is bitwise, so a designed filter buys nothing: short tables of random taps of both signs, built as _rs of
+# tests/test_gpu_resample.py builds them -- a poisoned sample then smears over about four samples at the model's rate (a designed filter:
+# about 24).  DESIGN_ID names the one row that runs Resample.design(250, 125) instead (47 taps; no poison).  Streams have T_IN samples
+# at the amplifier's rate, so every stream still yields T = 70 steps.
+RATES = {"none": None, "1/2": (1, 2, 7), "5/8": (5, 8, 6)}           # rate -> (L, M, P)
+T_IN = {"none": T, "1/2": 140, "5/8": 112}
+# The cuts of the rate rows, at the amplifier's rate, under the names of the model-rate cuts whose role they keep.  Per ratio they hold a
+# chunk that emits no step (one sample at an odd count for 1/2; the eighth sample for 5/8, where the ceiling does not move), chunks that
+# emit floor(n L / M) steps (the decoder's dense copy) and chunks that emit ceil(n L / M) (its alias branch); "14s" is the one fixed
+# length a captured graph replays, a multiple of M: its count is the same at every replay.
+CUTS_IN = {
+    "1/2": {"7-1-32-30": [7, 1, 1, 66, 65], "13s": [27] * 5 + [5], "whole": [140], "ones-58": [1] * 25 + [115], "14s": [14] * 10},
+    "5/8": {"7-1-32-30": [7, 1, 53, 51], "13s": [21] * 5 + [7], "whole": [112], "ones-58": [1] * 20 + [92], "14s": [16] * 7},
+}
+POISON_IN = {"1/2": 68, "5/8": 54}   # the input sample whose first output is output POISON_AT: 2 * 34, and (34 * 8) div 5
+RAIL_IN = {"1/2": tuple(2 * t for t in RAIL_AT), "5/8": tuple((8 * t) // 5 for t in RAIL_AT)}
+RAIL_UNITS = {"1/2": 1500.0, "5/8": 1500.0}          # behind random taps of about 0.4 a 300-unit rail can stay under the gate's 100: the rail is
+                                     # raised, not the threshold lowered (tests/test_serve_pipeline_cpu.py holds that the gate fires)
+EVENT_AFTER_IN = {"1/2": 70, "5/8": 56}              # EVENT_AFTER at the amplifier's rate.  In the cuts "7-1-32-30", "13s" and "ones-58" the event
+                                     # then stands at 75 / 81 / 25 samples (1/2) and 61 / 63 / 20 (5/8): counts with n L mod M != 0, so
+                                     # a slot reset there stands at another phase than its neighbours
 ALIGN = dict(shrinkage=0.1, floor=1e-4, min_steps=10)          # SessionAlign's fields: a refit after 12 samples is a fit, not "few", and
                                      # behind PREP's common average reference (a covariance one direction short of singular) the
                                      # shrinkage keeps every eigenvalue above the floor: status 0, nothing clipped
@@ -255,7 +336,8 @@ FACTORS = dict(
     # behind a refit of stream 0's slot);  refit: refit_alignment of stream 1's slot;  set-reset: set_alignment of stream 0's slot, then
     # reset_alignment of stream 1's
     poison=("none", "nan", "pop"),
-    drive=("eager", "replay"))
+    drive=("eager", "replay"),
+    rate=tuple(RATES))               # the rate conversion in front: none, or L / M with the taps of RATES
 # Rows with align and an event accumulate from the start (align_accumulate(True)), so that the accumulators are there for reset, state_dict
 # and reset_alignment to keep, carry or clear; rows without an event run with the switch off (no nsd_cov_step is launched).
 
@@ -273,7 +355,7 @@ def refused(c):
     return None
 
 
-Case = namedtuple("Case", "id decoder gate prep align slots cut event poison drive")
+Case = namedtuple("Case", "id decoder gate prep align slots cut event poison drive rate", defaults=("none",))
 _ROWS = [
     # gate + prep + align in each of the four decoders, pushed eagerly: a permuted slot list, a refit between chunks, a rejected step
     (0,  "stream",      1, 1, 1, "list",    "7-1-32-30", "refit",      "pop",  "eager"),
@@ -313,14 +395,37 @@ _ROWS = [
     # beyond the pairs: reset(slot) with gate, prep, align and the accumulators all present -- it must restart the first two and the
     # decoder's state and leave the matrices and accumulators; the rejected step lies before it, so the reset slot decides again
     (32, "stream",      1, 1, 1, "list",    "13s",       "reset",      "pop",  "eager"),
+    # the rate conversion in front of the full chain, two rows per ratio: eager with a permuted slot list and a refit, and replayed
+    (33, "stream",      1, 1, 1, "list",    "7-1-32-30", "refit",      "pop",  "eager",  "1/2"),
+    (34, "ens-sliding", 1, 1, 1, "tensor",  "14s",       "state_dict", "none", "replay", "1/2"),       # DESIGN_ID
+    (35, "sliding",     1, 1, 1, "list",    "7-1-32-30", "refit",      "nan",  "eager",  "5/8"),
+    (36, "ens-stream",  1, 1, 1, "tensor",  "14s",       "state_dict", "nan",  "replay", "5/8"),
+    # the pairwise cover of rate against every other factor
+    (37, "sliding",     0, 0, 0, "default", "13s",       "reset",      "nan",  "eager",  "1/2"),
+    (38, "ens-stream",  0, 1, 1, "partial", "ones-58",   "set-reset",  "none", "eager",  "1/2"),
+    (39, "ens-sliding", 1, 0, 0, "default", "whole",     "none",       "pop",  "eager",  "1/2"),
+    (40, "stream",      0, 1, 0, "tensor",  "ones-58",   "reset",      "nan",  "eager",  "1/2"),
+    (41, "sliding",     1, 1, 1, "partial", "7-1-32-30", "reset",      "pop",  "eager",  "1/2"),
+    (42, "ens-stream",  1, 0, 1, "list",    "14s",       "reset",      "none", "replay", "1/2"),
+    (43, "stream",      1, 1, 1, "list",    "13s",       "reset",      "pop",  "eager",  "1/2"),       # row 32 behind the conversion
+    (44, "stream",      0, 0, 0, "partial", "13s",       "reset",      "none", "eager",  "5/8"),
+    (45, "ens-sliding", 1, 1, 1, "default", "ones-58",   "set-reset",  "pop",  "eager",  "5/8"),
+    (46, "ens-stream",  0, 1, 0, "default", "whole",     "none",       "none", "eager",  "5/8"),
+    (47, "ens-sliding", 1, 0, 0, "tensor",  "7-1-32-30", "reset",      "pop",  "eager",  "5/8"),
+    (48, "stream",      1, 1, 0, "list",    "ones-58",   "state_dict", "nan",  "eager",  "5/8"),       # a checkpoint at a phase that is not 0
+    (49, "sliding",     0, 0, 1, "partial", "14s",       "set-reset",  "none", "replay", "5/8"),
+    (50, "stream",      1, 1, 1, "list",    "13s",       "reset",      "pop",  "eager",  "5/8"),       # row 32 behind the conversion
 ]
 CASES = [Case(*r) for r in _ROWS]
 FULL_CHAIN_IDS = (0, 1, 2, 3, 4, 5, 6, 7)
+FULL_CHAIN_RATE_IDS = (33, 34, 35, 36)
+DESIGN_ID = 34
 
 
 def case_id(c):
     on = "".join(ch for ch, f in zip("GPL", (c.gate, c.prep, c.align)) if f) or "none"
-    return f"{c.id:02d}-{c.decoder}-{on}-{c.slots}-{c.cut}-{c.event}-{c.poison}-{c.drive}"
+    rate = "" if c.rate == "none" else "-r" + c.rate.replace("/", "of")
+    return f"{c.id:02d}-{c.decoder}-{on}-{c.slots}-{c.cut}-{c.event}-{c.poison}-{c.drive}{rate}"
 
 
 def sliding(c):
@@ -340,8 +445,11 @@ def poison_reaches_the_step(c):
 def nan_by_position(c):
     """the rows in which a NaN is COMPUTED from a NaN input: a NaN sample reaches nsd_prep_step (no gate holds it), whose arithmetic
     spreads it over the channels and its states.  For such a NaN the project's rule is prep_ref.same_bits': finite values bitwise, NaNs
-    by position (the sign of a NaN result is open in IEEE 754, and host and GPU differ in it).  Every other row compares every word."""
-    return bool(c.prep) and not c.gate and c.poison == "nan"
+    by position (the sign of a NaN result is open in IEEE 754, and host and GPU differ in it).  Every other row compares every word.
+    Stage 0 computes a NaN too (a tap times the NaN sample): its own output is always compared under resample_ref.same_bits, that
+    file's rule, and a gate behind it holds the channel, so nothing computed from it goes further; without a gate the computed NaN is
+    what every stage behind -- and the decoder's step and state -- is fed, so those rows compare by position as well."""
+    return not c.gate and c.poison == "nan" and (bool(c.prep) or c.rate != "none")
 
 
 def pushed(c):
@@ -356,12 +464,31 @@ def slot_of(c, stream):
     return stream if slots is None else slots[stream]
 
 
+def cuts_of(c):
+    """the row's cut, at the rate its chunks are pushed at"""
+    return CUTS[c.cut] if c.rate == "none" else CUTS_IN[c.rate][c.cut]
+
+
+def converter(c):
+    """the row's rate conversion as ServeRef takes it: dict(L, M, taps), or None"""
+    if c.rate == "none":
+        return None
+    L, M_, P = RATES[c.rate]
+    if c.id == DESIGN_ID:
+        from nsd_amd.resample import Resample
+        r = Resample.design(250, 125)
+        assert (r.L, r.M) == (L, M_)
+        return dict(L=L, M=M_, taps=np.array(r.taps, F32))
+    rs = np.random.RandomState(1000 * L + 10 * M_ + P)
+    return dict(L=L, M=M_, taps=(rs.standard_normal((L, P)) / np.sqrt(P)).astype(F32))
+
+
 def event_chunk(c):
     """the event stands behind this chunk of the cut (None: no event)"""
     if c.event == "none":
         return None
-    ends = np.cumsum(CUTS[c.cut])[:-1]
-    late = [k for k, e in enumerate(ends) if e >= EVENT_AFTER]
+    ends = np.cumsum(cuts_of(c))[:-1]
+    late = [k for k, e in enumerate(ends) if e >= (EVENT_AFTER if c.rate == "none" else EVENT_AFTER_IN[c.rate])]
     return int(late[0]) if late else len(ends) - 1
 
 
@@ -377,8 +504,13 @@ def settings(c):
     import nsd_amd
     gate = nsd_amd.SignalGate(**GATE) if c.gate else None
     prep = nsd_amd.CausalPrep.design(**PREP) if c.prep else None
-    return dict(model=dict(gate=gate, prep=prep, align=nsd_amd.SessionAlign(**ALIGN) if c.align else None),
-                ref=ref_settings(gate, prep, WINDOW if sliding(c) else None))
+    model = dict(gate=gate, prep=prep, align=nsd_amd.SessionAlign(**ALIGN) if c.align else None)
+    ref = ref_settings(gate, prep, WINDOW if sliding(c) else None)
+    r = converter(c)
+    if r is not None:                                     # (rows without a conversion keep the keywords they had)
+        model["resample"] = nsd_amd.Resample(L=r["L"], M=r["M"], P=r["taps"].shape[1], taps=r["taps"])
+        ref["resample"] = r
+    return dict(model=model, ref=ref)
 
 
 def ref_settings(gate, prep, window=None):
@@ -400,6 +532,19 @@ def signal(n, rs, poison="none"):
     return x
 
 
+def signal_in(n, rs, rate, poison="none"):
+    """signal() at the amplifier's rate of a rate row: T_IN[rate] samples, the rails (of RAIL_UNITS) and the poison at the input samples
+    whose outputs stand where signal() has them"""
+    x = np.clip(10.0 * rs.standard_normal((n, T_IN[rate], C)), -40, 40).astype(F32)
+    for i in range(n):
+        x[i, RAIL_IN[rate][i], i] = RAIL_UNITS[rate] if i % 2 == 0 else -RAIL_UNITS[rate]
+    if poison == "nan":
+        x[POISON_STREAM, POISON_IN[rate], 5] = np.nan
+    elif poison == "pop":
+        x[POISON_STREAM, POISON_IN[rate], 1:4] = 500.0
+    return x
+
+
 def matrices(n, rs):
     """non-symmetric alignment matrices near the identity [n,C,C]"""
     return (np.eye(C) + 0.15 * rs.standard_normal((n, C, C))).astype(F32)
@@ -409,7 +554,7 @@ def inputs(c):
     """-> dict(x [B,T,C], W0: the model's matrix (or None), Wset: what set_alignment writes)"""
     rs = np.random.RandomState(2000 + c.id)
     n, _ = pushed(c)
-    x = signal(n, rs, c.poison)
+    x = signal(n, rs, c.poison) if c.rate == "none" else signal_in(n, rs, c.rate, c.poison)
     W = matrices(2, rs)
     return dict(x=x, W0=W[0] if c.align else None, Wset=W[1] if c.align else None)
 
@@ -438,17 +583,30 @@ def apply_event(c, ref, inp, fit=None):
     return ref
 
 
+def sub_pushes(c, ref, n):
+    """how a chunk of n samples reaches the row's streams: one push of all of them with the row's slot argument, or -- where the
+    reference's slots would emit different numbers of steps (behind a reset at another phase) -- one push per group of equal count
+    -> [(positions in the pushed batch, slots or None)]"""
+    nB, slots = pushed(c)
+    named = list(range(nB)) if slots is None else list(slots)
+    groups = ref.groups(named, n)
+    if len(groups) == 1:
+        return [(list(range(nB)), slots)]
+    return [([named.index(s) for s in g], list(g)) for g in groups]
+
+
 def run_ref(c, cut=None, fit=None, inp=None):
-    """the whole row on the reference -> (ref, [(out, mask, windows, trace) per chunk]).  fit: as apply_event's; None: host_fit"""
+    """the whole row on the reference -> (ref, [(out, mask, windows, trace, positions, samples pushed) per push]): one push per chunk,
+    or one per group of sub_pushes(); out is None for a push that emits no step.  fit: as apply_event's; None: host_fit"""
     inp, st = inp or inputs(c), settings(c)
     ref = new_ref(c, inp, st)
-    _, slots = pushed(c)
-    cut = CUTS[c.cut] if cut is None else cut
-    at = event_chunk(c) if cut == CUTS[c.cut] else None
+    cut = cuts_of(c) if cut is None else cut
+    at = event_chunk(c) if cut == cuts_of(c) else None
     out, t = [], 0
     for k, n in enumerate(cut):
-        o, m, w = ref.push(inp["x"][:, t:t + n], slots)
-        out.append((o, m, w, dict(ref.trace)))
+        for pos, sl in sub_pushes(c, ref, n):
+            o, m, w = ref.push(inp["x"][pos, t:t + n], sl)
+            out.append((o, m, w, dict(ref.trace), pos, n))
         t += n
         if at is not None and k == at:
             ref = apply_event(c, ref, inp, fit or (lambda sl, r=ref: r.host_fit(sl, ALIGN)[0]))
@@ -456,5 +614,5 @@ def run_ref(c, cut=None, fit=None, inp=None):
 
 
 def expected_stages(c):
-    on = dict(gate=c.gate, prep=c.prep, apply=c.gate, cov=accumulates(c), align=c.align)
+    on = dict(resample=c.rate != "none", gate=c.gate, prep=c.prep, apply=c.gate, cov=accumulates(c), align=c.align)
     return [s for s in STAGES if on[s]]

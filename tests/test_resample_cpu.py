@@ -220,12 +220,22 @@ def test_validation_on_the_host():
 S, Cc, K = 4, 8, 3
 
 
+def _n_in_words(state, r):
+    """the int64 n_in of every slot inside a resample state [S, stride] (a view)"""
+    return state.view(torch.int64)[:, ops.resample_layout(Cc, r).n_in // 2]
+
+
+def _rows(slots, n):
+    return list(range(n)) if slots is None else [int(v) for v in slots.tolist()]
+
+
 @pytest.fixture
 def launches(monkeypatch):
     rec = []
 
     def resample_step(x, resample, state=None, *, slots=None, out=None, cnt=None, taps=None):
         rec.append(dict(name="resample_step", x=x, state=state, slots=slots, out=out))
+        _n_in_words(state, resample)[_rows(slots, x.shape[0])] += x.shape[1]      # as the kernel: the count lives in the state
         return out
 
     def prep_step(x, prep, state=None, *, slots=None, out=None):
@@ -252,13 +262,19 @@ def launches(monkeypatch):
     def reset_of(name):
         def f(*a):
             rec.append(dict(name=name, args=a))
+            if name == "resample_reset":                                        # (C, resample, state, slots)
+                _n_in_words(a[2], a[1])[_rows(a[3], S)] = 0
         return f
 
-    for f in (resample_step, prep_step, gate_step, gate_apply, stream_step, window_step):
+    def resample_state(C_, r, S_, device=None):
+        st = torch.ones((S_, ops.resample_layout(C_, r).stride))
+        _n_in_words(st, r)[:] = 0
+        return st
+
+    for f in (resample_step, prep_step, gate_step, gate_apply, stream_step, window_step, resample_state):
         monkeypatch.setattr(ops, f.__name__, f)
     for name in ("resample_reset", "prep_reset", "gate_reset", "stream_reset", "window_reset"):
         monkeypatch.setattr(ops, name, reset_of(name))
-    monkeypatch.setattr(ops, "resample_state", lambda C_, r, S_, device=None: torch.ones((S_, ops.resample_layout(C_, r).stride)))
     monkeypatch.setattr(ops, "prep_state", lambda C_, S_, device=None: torch.ones((S_, 10)))
     monkeypatch.setattr(ops, "gate_state", lambda C_, S_, device=None: torch.ones((S_, 12)))
     return rec
@@ -326,9 +342,10 @@ def test_reset_and_the_checkpoint_cover_the_conversion(launches):
     r = Resample.design(250, 125)
     a, b, plain = _stand_in("stream", r), _stand_in("stream", r), _stand_in("stream", None)
     a.push(torch.zeros((3, 10, Cc)))
-    a.resample_state.mul_(3.0)
+    a.resample_state[:, :ops.resample_layout(Cc, r).n_in].mul_(3.0)             # (the history words)
     sd = a._front_state_dict({})
     assert set(sd) == {"resample_state", "resample_n_in", "prep_state"} and sd["resample_n_in"].tolist() == [10, 10, 10, 0]
+    assert sd["resample_n_in"].tolist() == _n_in_words(sd["resample_state"], r).tolist()
     b._load_front_state(*b._check_front_state(sd, "who"))
     b._load_resample_state(sd)
     assert torch.equal(b.resample_state, a.resample_state) and list(b.input_steps) == [10, 10, 10, 0]
@@ -337,7 +354,13 @@ def test_reset_and_the_checkpoint_cover_the_conversion(launches):
     st = torch.zeros_like(a.resample_state)
     st.view(torch.int64)[:, col] = torch.tensor([5, 0, 7, 9])
     b._load_resample_state({"resample_state": st})
-    assert list(b.input_steps) == [5, 0, 7, 9]
+    assert list(b.input_steps) == [5, 0, 7, 9] and torch.equal(b.resample_state, st)
+    # ... and a resample_n_in that disagrees with it is refused, with neither the state nor the mirror written
+    for state, wrong in ((sd["resample_state"], torch.tensor([10, 10, 11, 0])), (sd["resample_state"], torch.tensor([10, 10, 10])),
+                         (torch.zeros_like(st), [5, 0, 7, 9])):
+        with pytest.raises(nsd_amd.NsdError, match="load_state_dict: resample_n_in .* disagrees with the counts"):
+            b._load_resample_state({"resample_state": state, "resample_n_in": wrong})
+        assert list(b.input_steps) == [5, 0, 7, 9] and torch.equal(b.resample_state, st)
     # a checkpoint without the key loads into a decoder without a conversion, and only there
     old = {"prep_state": sd["prep_state"]}
     plain._load_front_state(*plain._check_front_state(old, "who"))
@@ -357,3 +380,31 @@ def test_reset_and_the_checkpoint_cover_the_conversion(launches):
     del launches[:]
     plain.reset()
     assert sorted(c["name"] for c in launches) == ["prep_reset", "stream_reset"]
+
+
+@pytest.mark.parametrize("kind", ["stream", "sliding"])
+def test_the_mirror_is_never_trusted_over_the_state(launches, kind):
+    """A decoder whose launches were replayed (here: the stand-in launch called on its state, as a captured graph does) has a mirror
+    that never moved.  Its checkpoint carries the state's counts, and a fresh decoder loaded from it cuts an odd chunk by them."""
+    r = Resample.design(250, 125)
+    a, fresh = _stand_in(kind, r), _stand_in(kind, r)
+    a.push(torch.zeros((3, 10, Cc)))
+    ops.resample_step(torch.zeros((3, 3, Cc)), r, a.resample_state, slots=None, out=torch.zeros((3, 2, Cc)))     # the replay: 13 samples held
+    assert list(a.input_steps) == [10, 10, 10, 0] and _n_in_words(a.resample_state, r).tolist() == [13, 13, 13, 0]
+    sd = a._front_state_dict({})
+    assert sd["resample_n_in"].tolist() == _n_in_words(sd["resample_state"], r).tolist() == [13, 13, 13, 0]
+    fresh._load_front_state(*fresh._check_front_state(sd, "who"))
+    fresh._load_resample_state(sd)
+    assert list(fresh.input_steps) == [13, 13, 13, 0]
+    # one more sample at 1 / 2: ceil(14 / 2) - ceil(13 / 2) = 0 steps (the stale count of 10 would emit one, a NaN row)
+    del launches[:]
+    out = fresh.push(torch.zeros((3, 1, Cc)))
+    assert [c["name"] for c in launches] == ["resample_step"] and list(fresh.input_steps) == [14, 14, 14, 0]
+    assert out is None if kind == "stream" else tuple(out[0].shape) == (3, 0, K)
+    # ... and the next one emits exactly one
+    del launches[:]
+    fresh.push(torch.zeros((3, 1, Cc)))
+    assert tuple(launches[-1]["x"].shape) == (3, 1, Cc) and _n_in_words(fresh.resample_state, r).tolist() == list(fresh.input_steps)
+    # the stale mirror travelling beside the state (a checkpoint written before the counts came from the state) is refused
+    with pytest.raises(nsd_amd.NsdError, match="disagrees with the counts"):
+        _stand_in(kind, r)._load_resample_state(dict(sd, resample_n_in=torch.tensor([10, 10, 10, 0])))

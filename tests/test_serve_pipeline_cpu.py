@@ -20,6 +20,7 @@ import nsd_amd
 from nsd_amd import ops
 from nsd_amd import stream as st_mod
 from tests import align_ref, gate_ref, window_ref
+from tests import resample_ref as rr
 from tests import serve_ref as sv
 
 IDS = [sv.case_id(c) for c in sv.CASES]
@@ -45,7 +46,9 @@ def test_the_table_covers_every_allowed_pair():
     uncovered = sorted(need - set().union(*(_pairs(r) for r in table)), key=repr)
     print(f"{len(sv.CASES)} rows; {len(allowed)} allowed combinations of {len(rows)}; {len(need)} allowed pairs; uncovered: {uncovered}")
     assert uncovered == []
-    assert 25 <= len(sv.CASES) <= 35 and [c.id for c in sv.CASES] == list(range(len(sv.CASES)))
+    # 33 rows without a rate conversion (unchanged), 4 full-chain rows behind one, and the cover of rate against every other factor
+    assert 45 <= len(sv.CASES) <= 55 and [c.id for c in sv.CASES] == list(range(len(sv.CASES)))
+    assert all(c.rate == "none" for c in sv.CASES[:33]) and all(c.rate != "none" for c in sv.CASES[33:])
     for f, levels in sv.FACTORS.items():
         assert {r[f] for r in table} == set(levels), f
     # every pair that no allowed combination holds is one a refusal names: refit / set-reset without align (2), pop without a gate (1),
@@ -57,6 +60,15 @@ def test_the_table_covers_every_allowed_pair():
     assert all((c.gate, c.prep, c.align) == (1, 1, 1) for c in full)
     assert sorted((c.decoder, c.drive) for c in full) == sorted(itertools.product(sv.FACTORS["decoder"], sv.FACTORS["drive"]))
     assert {c.event for c in full} == {"refit", "state_dict"} and {c.poison for c in full} == {"pop", "nan"}
+    # ... and behind the rate conversion, per ratio: one eager with a permuted slot list and a refit, one replayed; one of them runs the
+    # designed filter, without a poison
+    for rate in ("1/2", "5/8"):
+        two = [c for c in sv.CASES if c.id in sv.FULL_CHAIN_RATE_IDS and c.rate == rate]
+        assert all((c.gate, c.prep, c.align) == (1, 1, 1) for c in two)
+        assert sorted((c.drive, c.slots, c.event) for c in two) == [("eager", "list", "refit"), ("replay", "tensor", "state_dict")]
+    assert len({c.decoder for c in sv.CASES if c.id in sv.FULL_CHAIN_RATE_IDS}) == 4
+    design = sv.CASES[sv.DESIGN_ID]
+    assert design.id in sv.FULL_CHAIN_RATE_IDS and design.poison == "none" and sv.converter(design)["taps"].shape == (1, 47)
     # the cuts are the stated ones; the fixed one is off the hop grid
     assert all(sum(v) == sv.T for v in sv.CUTS.values()) and sv.CUTS["14s"][0] % sv.HOP != 0
     # the poison is neither first nor last in a chunk of any cut and lies in two windows, also when counted from a reset behind 12 samples
@@ -65,6 +77,32 @@ def test_the_table_covers_every_allowed_pair():
         assert sv.POISON_AT not in set(ends) | set(ends - 1) | {0}
     inside = lambda t: [e for e in range(sv.WINDOW, sv.T + 1, sv.HOP) if e - sv.WINDOW <= t < e]
     assert len(inside(sv.POISON_AT)) == 2 and len(inside(sv.POISON_AT - 12)) == 2
+    # the cuts at the amplifier's rate: the same names, T_IN samples that give T steps; per ratio a chunk that emits no step, one that emits
+    # floor(n L / M) and one that emits ceil(n L / M) steps (not the same number), the fixed length a multiple of M, and the poison --
+    # the input sample whose first output is output POISON_AT -- neither first nor last in a chunk
+    assert set(sv.CUTS_IN) == set(sv.RATES) - {"none"} == set(sv.T_IN) - {"none"}
+    for rate, cuts in sv.CUTS_IN.items():
+        L, M, P = sv.RATES[rate]
+        assert set(cuts) == set(sv.CUTS) and rr.ceil_div(sv.T_IN[rate] * L, M) == sv.T
+        assert sorted(rr.poisoned_outputs(L, M, P, sv.POISON_IN[rate], sv.T_IN[rate]))[0] == sv.POISON_AT
+        assert len(rr.poisoned_outputs(L, M, P, sv.POISON_IN[rate], sv.T_IN[rate])) <= 4
+        kinds = set()
+        for name, cut in cuts.items():
+            ends = np.cumsum(cut)
+            assert ends[-1] == sv.T_IN[rate] and sv.POISON_IN[rate] not in set(ends) | set(ends - 1) | {0}, (rate, name)
+            for n0, n in zip(ends - cut, cut):
+                k, lo, hi = rr.out_steps(L, M, int(n0), int(n)), (n * L) // M, rr.ceil_div(n * L, M)
+                kinds |= {"zero"} if k == 0 else set()
+                kinds |= {"floor"} if (k == lo and lo != hi and k > 0) else {"ceil"} if (k == hi and lo != hi) else set()
+        assert kinds == {"zero", "floor", "ceil"}, (rate, kinds)
+        fixed = cuts["14s"]
+        assert len(set(fixed)) == 1 and fixed[0] % M == 0 and fixed[0] == {"1/2": 14, "5/8": 16}[rate]
+        assert len({rr.out_steps(L, M, int(n0), fixed[0]) for n0 in np.cumsum(fixed) - fixed[0]}) == 1      # the same count at every replay
+        # a reset at the event of the other cuts leaves the slot at another phase than its neighbours
+        for name in ("7-1-32-30", "13s", "ones-58"):
+            c = next(c for c in sv.CASES if c.rate == rate and c.cut == name and c.event != "none")
+            at = int(np.cumsum(cuts[name])[sv.event_chunk(c)])
+            assert (at * L) % M != 0, (rate, name, at)
 
 
 # ---- the reference ----------------------------------------------------------------------------------------------------------------
@@ -136,9 +174,9 @@ def test_reset_restarts_that_slots_stream_and_nothing_else():
     before = ref.snapshot()
     ref.reset([0])                                                           # the slot of pushed stream 1
     after = ref.snapshot()
-    for k in ("table", "sums", "counts", "records"):
+    for k in ("table", "sums", "used", "records"):
         assert sv.same_snapshot({k: before[k]}, {k: after[k]}), k
-    assert after["counts"][0, 0] > 0 and not np.array_equal(after["table"][0], W0)
+    assert after["used"][0, 0] > 0 and not np.array_equal(after["table"][0], W0)
     assert ref.n.tolist() == [0, 0, cut, cut] and not ref.gate_rows()[0].any() and not ref.prep_rows()[0].any()
     o1, m1, w1 = ref.push(x[:, cut:], sv.SLOT_LIST)
     o2, m2, w2 = twin.push(x[:, cut:], sv.SLOT_LIST)
@@ -179,38 +217,44 @@ def test_in_every_row_every_enabled_stage_acts_and_the_decisions_the_gpu_rows_co
     nB, slots = sv.pushed(c)
     want = sv.expected_stages(c)
     acted = {s: False for s in want}
-    for o, m, w, trace in chunks:
-        assert list(trace) == want and o.dtype == np.float32 and o.shape[0] == nB
+    for o, m, w, trace, pos, _ in chunks:
+        if o is None:                                    # a push that emits no step: stage 0 alone
+            assert list(trace) == ["resample"] and m is None and w is None and c.rate != "none"
+            continue
+        assert list(trace) == want and o.dtype == np.float32 and o.shape[0] == len(pos)
         assert (m is not None) == bool(c.gate) and (w is not None) == sv.sliding(c)
         for s in want:
             acted[s] |= bool(trace[s])
     assert all(acted.values()), acted                    # (not in every chunk: a one-sample first chunk leaves prep's zeros as they are)
+    assert c.rate != "none" or all(pos == list(range(nB)) for _, _, _, _, pos, _ in chunks)
     # what the GPU rows count: every unpoisoned stream ends with a finite decision; a sliding row has at least two finite windows
     # per stream, and a poisoned stream loses some
-    x = np.concatenate([o for o, _, _, _ in chunks], 1)
+    x = [np.concatenate([o[pos.index(b)] for o, _, _, _, pos, _ in chunks if o is not None and b in pos], 0) for b in range(nB)]
+    poison_at = sv.POISON_AT if c.rate == "none" else sv.POISON_IN[c.rate]
     for b in range(nB):
         s = sv.slot_of(c, b)
         hit = sv.poison_reaches_the_step(c) and b == sv.POISON_STREAM
         if sv.sliding(c):
-            wins = [p for _, _, w, _ in chunks for _, _, p in w[b]]
+            wins = [p for o, _, w, _, pos, _ in chunks if o is not None and b in pos for _, _, p in w[pos.index(b)]]
             assert wins.count(False) >= 2, (b, wins)
             swallowed = c.event == "reset" and b == sv.EVENT_STREAM         # (a reset may come before any window with the step in it ends)
             assert (True in wins) == hit or (hit and swallowed), (b, wins)
         else:
             recovered = c.event == "reset" and b == sv.EVENT_STREAM and sv.event_chunk(c) is not None and \
-                int(np.cumsum(sv.CUTS[c.cut])[sv.event_chunk(c)]) > sv.POISON_AT
+                int(np.cumsum(sv.cuts_of(c))[sv.event_chunk(c)]) > poison_at
             assert ref.poisoned(s) == (hit and not recovered), (b, ref.nan_at[s])
         assert np.isnan(x[b]).any() == hit
     assert not any(ref.poisoned(sv.slot_of(c, b)) for b in range(nB) if b != sv.POISON_STREAM)
     # the event stands between two chunks, and a refit is a fit: enough steps, no clipped eigenvalue
     k = sv.event_chunk(c)
-    assert (k is None) == (c.event == "none") and (k is None or 0 <= k < len(sv.CUTS[c.cut]) - 1)
+    assert (k is None) == (c.event == "none") and (k is None or 0 <= k < len(sv.cuts_of(c)) - 1)
     if c.event == "refit":
         probe = sv.new_ref(c, inp)
         t = 0
-        for n in sv.CUTS[c.cut][:k + 1]:
+        for n in sv.cuts_of(c)[:k + 1]:
             probe.push(inp["x"][:, t:t + n], slots)
             t += n
+        t = int(probe.n[sv.slot_of(c, sv.EVENT_STREAM)])                    # (steps at the model's rate)
         one = sv.slot_of(c, sv.EVENT_STREAM)
         W, recs = probe.host_fit([one], sv.ALIGN)
         print(f"{sv.case_id(c)}: refit after {t} samples: {recs[0]}")
@@ -221,12 +265,146 @@ def test_in_every_row_every_enabled_stage_acts_and_the_decisions_the_gpu_rows_co
     if c.event == "set-reset":
         one, other = sv.slot_of(c, sv.EVENT_STREAM), sv.slot_of(c, sv.SET_STREAM)
         assert np.array_equal(ref.table[other], inp["Wset"]) and np.array_equal(ref.table[one], inp["W0"])
-        assert ref.counts[one, 0] + ref.counts[one, 1] == sv.T - int(np.cumsum(sv.CUTS[c.cut])[k])      # cleared at the event, counting since
-        assert ref.counts[other, 0] + ref.counts[other, 1] == sv.T
+        before = int(np.cumsum(sv.cuts_of(c))[k])
+        if c.rate != "none":
+            before = rr.ceil_div(before * sv.RATES[c.rate][0], sv.RATES[c.rate][1])
+        assert ref.used[one, 0] + ref.used[one, 1] == sv.T - before          # cleared at the event, counting since
+        assert ref.used[other, 0] + ref.used[other, 1] == sv.T
     # the same row in one chunk per side of the event gives the same bits (the cut factor changes nothing the decoder may see)
     if c.event == "none":
-        _, whole = sv.run_ref(c, cut=[sv.T], inp=inp)
-        assert not sv._differs(whole[0][0], x)
+        _, whole = sv.run_ref(c, cut=[sv.T_IN[c.rate]], inp=inp)
+        assert not sv._differs(whole[0][0], np.stack(x)) and whole[0][0].shape[1] == sv.T
+
+
+# ---- the rate conversion in the reference and in the table -------------------------------------------------------------------------
+RATE_ROWS = [c for c in sv.CASES if c.rate != "none"]
+BY_POSITION = [9, 16, 24, 26, 27, 37, 40]                 # the rows a NaN computed from a NaN input reaches a compared word in (pinned)
+
+
+def test_the_rows_that_compare_nans_by_position_are_these():
+    assert [c.id for c in sv.CASES if sv.nan_by_position(c)] == BY_POSITION
+    for c in sv.CASES:                                    # a NaN sample, and no gate to hold it, in front of arithmetic: prep or stage 0
+        assert sv.nan_by_position(c) == (c.poison == "nan" and not c.gate and (bool(c.prep) or c.rate != "none")), c
+
+
+@pytest.mark.parametrize("rate", ["1/2", "5/8"])
+@pytest.mark.parametrize("gate,prep,align", [(0, 0, 0), (1, 1, 1), (0, 1, 0), (1, 0, 1)])
+def test_behind_the_rate_conversion_the_reference_does_not_depend_on_the_cut_and_equals_the_whole_window_chain(rate, gate, prep, align):
+    c = next(c for c in RATE_ROWS if c.rate == rate and c.id != sv.DESIGN_ID)
+    r = sv.converter(c)
+    rs = np.random.RandomState(12)
+    W0 = sv.matrices(1, rs)[0] if align else None
+    for poison in ("none", "nan") + (("pop",) if gate else ()):
+        x = sv.signal_in(sv.B, np.random.RandomState(13), rate, poison)
+        cfg = _cfg(gate, prep)
+        trace = {}
+        want = sv.window_ref_windows(x, gate=cfg["gate"], prep=cfg["prep"], align=W0, trace=trace, resample=r)
+        assert want.shape == (sv.B, sv.T, sv.C) and list(trace)[0] == "resample" and all(trace.values())
+        whole = None
+        for name, cut in sv.CUTS_IN[rate].items():
+            ref = sv.ServeRef(sv.S, sv.C, align=W0, accumulate=True, resample=r, **cfg)
+            outs, wins, t, zero = [], [[] for _ in range(sv.B)], 0, 0
+            for n in cut:
+                before = ref.snapshot()
+                assert ref.groups(sv.SLOT_LIST, n) == [sv.SLOT_LIST] and len(set(ref.counts(sv.SLOT_LIST, n))) == 1
+                o, m, w = ref.push(x[:, t:t + n], sv.SLOT_LIST)
+                t += n
+                assert ref.rn.tolist() == [t, 0, t, t] and ref.stage0[1].tolist() == [rr.out_steps(r["L"], r["M"], t - n, n)] * sv.B
+                if o is None:                             # "no step": stage 0 moved, and nothing else did
+                    zero += 1
+                    after = ref.snapshot()
+                    assert (o, m, w) == sv.NO_STEP and all(sv.same_snapshot({k: before[k]}, {k: after[k]}) for k in before if k not in ("rn", "rh"))
+                    continue
+                outs.append(o)
+                for b, lst in enumerate(w):
+                    wins[b] += [(e, p) for e, _, p in lst]
+            got = (np.concatenate(outs, 1), wins, ref.snapshot())
+            assert (zero > 0) == (name in ("7-1-32-30", "ones-58")), (name, zero)
+            assert rr.same_bits(got[0], want), (poison, name)            # streamed = the whole-window chain
+            whole = whole or got
+            assert rr.same_bits(got[0], whole[0]) and got[1] == whole[1] and sv.same_snapshot(got[2], whole[2]), (poison, name)
+            assert ref.n.tolist() == [sv.T, 0, sv.T, sv.T]
+
+
+@pytest.mark.parametrize("rate", ["1/2", "5/8"])
+def test_reset_restarts_stage_0_and_the_slots_then_emit_different_counts(rate):
+    c = next(c for c in RATE_ROWS if c.rate == rate and c.id != sv.DESIGN_ID)
+    L, M, _ = sv.RATES[rate]
+    ref = sv.ServeRef(sv.S, sv.C, resample=sv.converter(c), **_cfg(0, 0))
+    x = sv.signal_in(sv.B, np.random.RandomState(14), rate)
+    n0 = {"1/2": 3, "5/8": 7}[rate]                       # a count with n L mod M != 0 at which one more sample emits no step
+    ref.push(x[:, :n0], sv.SLOT_LIST)
+    ref.reset([0])
+    assert ref.rn.tolist() == [0, 0, n0, n0] and not ref.rh[0].any() and ref.rh[3].any() and ref.n.tolist()[0] == 0
+    assert ref.counts(sv.SLOT_LIST, 1) == [rr.out_steps(L, M, n0, 1), 1, rr.out_steps(L, M, n0, 1)] and rr.out_steps(L, M, n0, 1) == 0
+    assert ref.groups(sv.SLOT_LIST, 1) == [[3, 2], [0]] and ref.groups(None, 1) == [[0, 1], [2, 3]] and ref.groups([0, 1], M) == [[0, 1]]
+    with pytest.raises(AssertionError, match="push them by groups"):
+        ref.push(x[:, n0:n0 + 1], sv.SLOT_LIST)
+    fresh = sv.ServeRef(sv.S, sv.C, resample=sv.converter(c), **_cfg(0, 0))
+    o1, _, _ = ref.push(x[1:2, n0:], [0])
+    o2, _, _ = fresh.push(x[1:2, n0:], [0])
+    assert not sv._differs(o1, o2)                        # the reset slot is a fresh one
+    snap = ref.snapshot()
+    other = sv.ServeRef(sv.S, sv.C, resample=sv.converter(c), **_cfg(0, 0)).restore(snap)
+    assert sv.same_snapshot(other.snapshot(), snap) and other.rn.tolist() == ref.rn.tolist()
+    other.push(x[:1, n0:n0 + 3], [3])
+    assert not sv.same_snapshot(other.snapshot(), snap) and sv.same_snapshot(ref.snapshot(), snap)          # (a copy, not a view)
+
+
+@pytest.mark.parametrize("c", RATE_ROWS, ids=[sv.case_id(c) for c in RATE_ROWS])
+def test_the_conditions_of_the_rate_rows(c):
+    L, M, P = sv.RATES[c.rate]
+    inp = sv.inputs(c)
+    ref, pushes = sv.run_ref(c, inp=inp)
+    nB, _ = sv.pushed(c)
+    assert inp["x"].shape == (nB, sv.T_IN[c.rate], sv.C)
+    # the 33 rows in front draw what they drew: the same first numbers from RandomState(2000 + id)
+    old = sv.CASES[c.id % 33]
+    assert np.array_equal(sv.inputs(old)["x"], sv.signal(sv.pushed(old)[0], np.random.RandomState(2000 + old.id), old.poison), equal_nan=True)
+    # the gate fires in every stream behind the conversion: the bit of the stream's own railed channel, in some push
+    if c.gate:
+        for b in range(nB):
+            words = np.concatenate([m[pos.index(b)] for o, m, _, _, pos, _ in pushes if o is not None and b in pos])
+            assert ((words >> b) & 1).any(), b
+    # a poisoned sliding stream keeps at least two finite decisions before the poison and one after it
+    if sv.sliding(c) and c.poison != "none":
+        wins = [p for o, _, w, _, pos, _ in pushes if o is not None and sv.POISON_STREAM in pos for _, _, p in w[pos.index(sv.POISON_STREAM)]]
+        if True in wins:
+            first, last = wins.index(True), len(wins) - 1 - wins[::-1].index(True)
+            assert wins[:first].count(False) >= 2 and wins[last + 1:].count(False) >= 1, wins
+        else:                                             # a NaN sample a gate held, or a reset in front of the windows that held the step
+            assert (c.poison == "nan" and c.gate) or c.event == "reset", wins
+            assert wins.count(False) >= 3, wins
+    # a reset row (but for the fixed cut, whose chunks keep every slot in phase) really produces unequal counts
+    counts = [[int(o.shape[1]) if o is not None else 0, n] for o, _, _, _, _, n in pushes]
+    split = len(pushes) > len(sv.cuts_of(c))
+    assert split == (c.event == "reset" and c.cut != "14s"), (split, counts)
+    if split:
+        k = sv.event_chunk(c)
+        at = int(np.cumsum(sv.cuts_of(c))[k])
+        assert (at * L) % M != 0
+        behind = pushes[k + 1:k + 3]                      # the chunk behind the event: two pushes, by groups, of different counts
+        assert behind[0][5] == behind[1][5] and sorted(behind[0][4] + behind[1][4]) == list(range(nB))
+        assert behind[1][4] == [sv.EVENT_STREAM] and counts[k + 1][0] != counts[k + 2][0]
+
+
+@pytest.mark.parametrize("rate", ["1/2", "5/8"])
+def test_every_ratios_rows_hold_a_zero_step_a_floor_and_a_ceil_push(rate):
+    L, M, _ = sv.RATES[rate]
+    kinds = {}
+    for c in RATE_ROWS:
+        if c.rate != rate:
+            continue
+        for o, _, _, _, _, n in sv.run_ref(c)[1]:
+            k, lo, hi = (0 if o is None else o.shape[1]), (n * L) // M, rr.ceil_div(n * L, M)
+            assert k in (lo, hi)
+            kind = "zero" if k == 0 else None if lo == hi else "floor" if k == lo else "ceil"
+            kinds.setdefault(kind, set()).add(c.id)
+    print(rate, {k: sorted(v) for k, v in kinds.items()})
+    assert {"zero", "floor", "ceil"} <= set(kinds)
+    # ... and so do its full-chain eager row and, all three, the rows of at least two decoders
+    full = next(c.id for c in RATE_ROWS if c.rate == rate and c.id in sv.FULL_CHAIN_RATE_IDS and c.drive == "eager")
+    assert all(full in kinds[k] for k in ("zero", "floor", "ceil"))
 
 
 # ---- stream.py on the host: recording stand-ins for the launches ---------------------------------------------------------------------
@@ -277,10 +455,12 @@ CLASSES = dict(stream=st_mod.StreamDecoder, **{"ens-stream": st_mod.EnsembleStre
                                                 "ens-sliding": st_mod.EnsembleSlidingStreamDecoder})
 
 
-def _stand_in(kind, gate, prep, align):
+def _stand_in(kind, gate, prep, align, resample=None):
     """a decoder of class `kind` on the host: what __init__ sets, without the model living on a GPU"""
     cfg = dict(gate=nsd_amd.SignalGate(**sv.GATE) if gate else None, prep=nsd_amd.CausalPrep.design(**sv.PREP) if prep else None,
                align=nsd_amd.SessionAlign(**sv.ALIGN) if align else None)
+    if resample is not None:
+        cfg["resample"] = resample
     W = sv.matrices(1, np.random.RandomState(3))[0]
     model = nsd_amd.EEG_LSTM(align_matrix=W if align else None, **cfg).eval()
     dec = CLASSES[kind].__new__(CLASSES[kind])
@@ -397,3 +577,140 @@ def test_refusals_name_the_class_that_raised(launches, kind):
     sd = dict(state=torch.zeros((1, 1)), window=sv.WINDOW, hop=sv.HOP)
     with pytest.raises(nsd_amd.NsdError, match=f"^{name}.load_state_dict: state of shape"):
         dec.load_state_dict(sd)
+
+
+# ---- stage 0 on the host: the count, the mirror, the dense copy and the buffer cache ----------------------------------------------------
+def _n_in_words(state, r):
+    return state.view(torch.int64)[:, ops.resample_layout(sv.C, r).n_in // 2]
+
+
+@pytest.fixture
+def launches0(launches, monkeypatch):
+    """`launches`, and stand-ins for stage 0 and the decoders' steps.  The stage-0 stand-in does what the kernel does to the count (it
+    lives in the state) and marks the rows it may write: row j of every stream holds j, the rows behind the emitted ones NaN"""
+    rec = launches
+
+    def rows(slots, n):
+        return list(range(n)) if slots is None else [int(v) for v in slots.tolist()]
+
+    def resample_step(x, r, state=None, *, slots=None, out=None, cnt=None, taps=None):
+        at = rows(slots, x.shape[0])
+        held = _n_in_words(state, r)[at].tolist()
+        emitted = [rr.out_steps(r.L, r.M, h, x.shape[1]) for h in held]
+        out.fill_(float("nan"))
+        for b, k in enumerate(emitted):
+            out[b, :k] = torch.arange(k, dtype=torch.float32)[:, None]
+        _n_in_words(state, r)[at] += x.shape[1]
+        rec.append(dict(name="resample_step", x=x, state=state, slots=slots, out=out, emitted=emitted))
+        return out
+
+    def resample_reset(C_, r, state, slots=None):
+        rec.append(dict(name="resample_reset", args=(C_, r, state, slots)))
+        _n_in_words(state, r)[rows(slots, sv.S)] = 0
+
+    def resample_state(C_, r, S_, device=None):
+        st = torch.ones((S_, ops.resample_layout(C_, r).stride))
+        _n_in_words(st, r)[:] = 0
+        return st
+
+    def stream_step(spec, flat, x, state, *, slots=None, residual=False, read=True):
+        rec.append(dict(name="stream_step", x=x, slots=slots, seen=x.clone()))
+        return None, torch.zeros((x.shape[0], sv.K))
+
+    def window_step(spec, flat, x, state, *, window, hop, slots=None, residual=False):
+        rec.append(dict(name="window_step", x=x, slots=slots, seen=x.clone()))
+        D = -(-x.shape[1] // hop)
+        return None, torch.zeros((x.shape[0], D, sv.K)), torch.zeros((x.shape[0], D), dtype=torch.int64), torch.zeros(x.shape[0], dtype=torch.int32)
+
+    for f in (resample_step, resample_reset, resample_state, stream_step, window_step):
+        monkeypatch.setattr(ops, f.__name__, f)
+    return rec
+
+
+def _converter(rate):
+    L, M, P = sv.RATES[rate]
+    taps = (np.random.RandomState(1000 * L + 10 * M + P).standard_normal((L, P)) / np.sqrt(P)).astype(np.float32)
+    return nsd_amd.Resample(L=L, M=M, P=P, taps=taps)
+
+
+def _host_decoder(kind, r, gate=1, prep=1, align=1):
+    dec = _stand_in(kind, gate, prep, align, resample=r)
+    dec.model.flat_parameters = lambda: None
+    return dec
+
+
+def _front_words(dec):
+    """every state of the front end and the mirror, as bytes"""
+    ts = [dec.resample_state, dec.gate_state, dec.prep_state, dec.cov_state, dec.align_table, dec.align_records, dec.state]
+    return [t.clone() for t in ts] + [torch.from_numpy(dec.input_steps.copy())]
+
+
+@pytest.mark.parametrize("rate", ["1/2", "5/8"])
+@pytest.mark.parametrize("kind", ["stream", "sliding"])
+@pytest.mark.parametrize("how", ["default", "list", "tensor"])
+def test_push_converts_first_counts_from_the_mirror_and_hands_on_the_emitted_rows_dense(launches0, kind, rate, how):
+    r = _converter(rate)
+    dec = _host_decoder(kind, r)
+    dec.align_accumulate(True)
+    arg = {"default": None, "list": list(sv.SLOT_LIST), "tensor": torch.tensor(sv.SLOT_LIST, dtype=torch.int32)}[how]
+    named = list(range(sv.B)) if arg is None else list(sv.SLOT_LIST)
+    own = "stream_step" if kind == "stream" else "window_step"
+    held, kinds = 0, set()
+    for T in sv.CUTS_IN[rate]["7-1-32-30"] + [3, 3, 3, 5, 1, 1, 2]:          # (the same chunk shape at different phases among them)
+        del launches0[:]
+        before = _front_words(dec)
+        out = dec.push(torch.zeros((sv.B, T, sv.C)), arg)
+        n, most = rr.out_steps(r.L, r.M, held, T), rr.ceil_div(T * r.L, r.M)
+        held += T
+        first = launches0[0]
+        # stage 0 runs first, on the caller's rate, its own state and the slots; it may write ceil(T L / M) rows
+        assert first["name"] == "resample_step" and first["state"] is dec.resample_state and tuple(first["x"].shape) == (sv.B, T, sv.C)
+        assert tuple(first["out"].shape) == (sv.B, most, sv.C) and first["emitted"] == [n] * sv.B
+        assert (first["slots"] is None) if arg is None else first["slots"].tolist() == named
+        want = np.zeros(sv.S, np.int64)
+        want[named] = held
+        assert dec.input_steps.tolist() == want.tolist() == _n_in_words(dec.resample_state, r).tolist()      # the mirror is the state's count
+        if n == 0:                                        # nothing else is launched, no other state moves, and nothing is decided
+            kinds.add("zero")
+            assert [c["name"] for c in launches0] == ["resample_step"]
+            after = _front_words(dec)
+            assert all(torch.equal(a, b) for a, b in zip(before[1:-1], after[1:-1]))
+            assert out is None if kind == "stream" else (tuple(out[0].shape) == (sv.B, 0, sv.K) and out[2].tolist() == [0] * sv.B)
+            continue
+        kinds.add("ceil" if n == most else "floor")
+        assert [c["name"] for c in launches0] == ["resample_step", "gate_step", "prep_step", "gate_apply", "cov_step", "spatial_apply", own]
+        fed = launches0[1]["x"]                           # what the gate is handed: the n emitted rows, dense, none of the NaN rows behind
+        assert tuple(fed.shape) == (sv.B, n, sv.C) and fed.is_contiguous() and not torch.isnan(fed).any()
+        assert torch.equal(fed[0, :, 0], torch.arange(n, dtype=torch.float32))
+        assert (_ptr(fed) == _ptr(first["out"])) == (n == most)
+        assert tuple(launches0[-1]["x"].shape) == (sv.B, n, sv.C)
+    assert kinds == {"zero", "floor", "ceil"}
+
+
+@pytest.mark.parametrize("rate", ["1/2", "5/8"])
+@pytest.mark.parametrize("kind", ["stream", "sliding"])
+def test_behind_a_reset_the_slots_are_refused_together_and_nothing_moves(launches0, kind, rate):
+    r = _converter(rate)
+    dec = _host_decoder(kind, r)
+    T0 = {"1/2": 3, "5/8": 7}[rate]
+    dec.push(torch.zeros((sv.B, T0, sv.C)), sv.SLOT_LIST)
+    for slots in ([0], torch.tensor([0], dtype=torch.int32)):                # reset(slots) restarts stage 0 and the mirror of that slot
+        dec._n_in[0] = T0
+        del launches0[:]
+        dec.reset(slots)
+        assert dec.input_steps.tolist() == [0, 0, T0, T0] == _n_in_words(dec.resample_state, r).tolist()
+        assert sorted(c["name"] for c in launches0) == sorted(["resample_reset", "prep_reset", "gate_reset",
+                                                                "stream_reset" if kind == "stream" else "window_reset"])
+    del launches0[:]
+    before = _front_words(dec)
+    for arg in (list(sv.SLOT_LIST), torch.tensor(sv.SLOT_LIST, dtype=torch.int32), None):
+        with pytest.raises(nsd_amd.NsdError, match="push those slots separately"):
+            dec.push(torch.zeros((sv.B, 1, sv.C)), arg)
+    assert launches0 == [] and all(torch.equal(a, b) for a, b in zip(before, _front_words(dec)))
+    # by groups it goes: the slots in phase emit nothing, the reset one a step
+    assert dec.push(torch.zeros((2, 1, sv.C)), [3, 2]) is None or kind == "sliding"
+    assert [c["name"] for c in launches0] == ["resample_step"]
+    dec.push(torch.zeros((1, 1, sv.C)), [0])
+    assert tuple(launches0[-1]["x"].shape) == (1, 1, sv.C) and dec.input_steps.tolist() == [1, 0, T0 + 1, T0 + 1]
+    dec.reset()
+    assert dec.input_steps.tolist() == [0] * sv.S == _n_in_words(dec.resample_state, r).tolist()
